@@ -34,7 +34,8 @@ C oracle when that binary is absent) on one host core over a bounded sample of t
 (float and double), with the host CPU's model and core count beside it.  `parity_check` compares two utterances of the
 TIMED output buffer with the oracle after the timed region (the oracle is the checker here, never the thing measured);
 `end_to_end` times the host-buffer entries (H2D frames + kernel + D2H samples through page-locked buffers, float32 and
-int16 output) beside the kernel-only `value`, never instead of it.
+int16 output) beside the kernel-only `value`, never instead of it.  `--dump-outputs DIR` writes what the last timed step
+handed back (samples, counts, peaks; a seeded subset of the utterances when they exceed 48 MB) to DIR/*.npy.
 """
 import argparse
 import json
@@ -99,10 +100,14 @@ def parse_args(argv=None):
     ap.add_argument("--single-device", action="store_true", help="rehearsal only: every rank uses GPU 0")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-buffer (H2D + kernel + D2H) measurements")
     ap.add_argument("--no-parity-check", action="store_true", help="skip the oracle comparison of the timed output")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed back to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="no GPU work at all: the ranks only rendezvous (gloo), cut the batch into their shards and rank 0 prints "
                          "them -- a CPU rehearsal of the launcher and the rank logic, not a measurement")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.model in (4, 5):
         # the other tubes keep round 1's 256 x 2 s workload (one utterance per workgroup at that size)
         if args.batch is None:
@@ -328,6 +333,32 @@ def parity_check(d_audio, host_tracks, rows, precision, delay, frames, output_ra
             "against": "oracle/vtm_oracle.c (pinned to reference-made vectors), same tracks, after the timed region", "pass": bool(ok)}
 
 
+DUMP_MAX_SAMPLES = 12_000_000  # float32 samples in audio.npy (48 MB): with counts and peaks a dump stays under 64 MB
+DUMP_SEED = 20240531           # which utterances audio.npy holds when not all of them fit
+
+
+def dump_outputs(out_dir, d_audio, d_counts, d_max, batch, n_out):
+    """--dump-outputs DIR: what the timed launches handed back, as .npy files, for comparing two builds output for output.
+
+    counts.npy (float64) and maxabs.npy (float32): per-utterance sample counts and peaks, every utterance of the shard.
+    audio.npy (float32, [rows][samples]): the samples of every utterance when they fit in DUMP_MAX_SAMPLES, otherwise of a
+    fixed, seeded sample of utterances (whole rows; a row longer than the budget keeps its leading samples);
+    audio_rows.npy (float64) names those utterances.  The inputs are seeded, so the same arguments give the same files."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    k = min(batch, max(1, DUMP_MAX_SAMPLES // max(n_out, 1)))
+    rows = np.arange(batch) if k == batch else np.sort(np.random.default_rng(DUMP_SEED).choice(batch, k, replace=False))
+    cols = min(n_out, DUMP_MAX_SAMPLES)
+    audio = d_audio[torch.from_numpy(rows).to(d_audio.device), :cols].cpu().numpy()
+    arrays = {"audio": audio, "audio_rows": rows.astype(np.float64),
+              "counts": d_counts[:batch].cpu().numpy().astype(np.float64), "maxabs": d_max[:batch].cpu().numpy()}
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+    return {name: list(x.shape) for name, x in arrays.items()}
+
+
 def end_to_end(g, plan, host_pool, batch, frames, n_timed, kernel_only_rate, label):
     """The host-buffer entries on page-locked buffers: H2D frames + kernel + D2H samples, float32 and int16 output
     (include/gama_vtm.h: gvtm_synthesize_batch_host, gvtm_synthesize_batch_host_pcm16)."""
@@ -470,6 +501,10 @@ def main():
     plan.set_timing(False)
     if batch:
         assert int(d_counts[:batch].min().item()) == n_out and int(d_counts[:batch].max().item()) == n_out
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # before extras(), which reuses d_audio
+        dumped = dump_outputs(args.dump_outputs, d_audio, d_counts, d_max, batch, n_out)
     parity = None
     if rank == 0 and batch and not args.no_parity_check:
         # two utterances of the buffer the timed launches wrote, against the oracle (outside the timed region)
@@ -546,6 +581,8 @@ def main():
             },
         }
         line["parity_check"] = parity
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped, "of": "rank 0's shard, last timed step"}
         plain = not model5 and not model4
         if world == 1 and not args.no_extras and plain:
             line["extras"] = extras(args, g, make_plan, tiled, d_audio, d_counts, stream, n_out, host_pool)

@@ -322,10 +322,25 @@ def ref_synthesize(params, model="0", output_rate=44100, control_rate=250, confi
     """Run the compiled reference on float32 frames; returns (audio float32, info dict).
     poll > 0: the interactive caller contract (model constructed with interactive = true, outputBuffer() polled and
     drained the way the editor's JACK callback does, `poll` samples per callback; oracle/ref_driver.cpp)."""
-    import tempfile
     exe = ref_binary(kind)
     if exe is None:
         raise FileNotFoundError("oracle/_ref not built")
+    return _run_driver(exe, params, model, output_rate, control_rate, config, repeat, tmpdir, poll)
+
+
+PLUGIN_HOST = os.path.join(ORACLE_DIR, "_build", "vtm_plugin_host")
+
+
+def plugin_synthesize(params, plugin, output_rate=44100, control_rate=250, config=VOICE_MALE, repeat=1, tmpdir=None, poll=0):
+    """ref_synthesize(params, "2000:" + plugin, ...) through oracle/_build/vtm_plugin_host (oracle/plugin_host.cpp): the
+    plugin loaded and driven as GamaTTS's loader and Controller / editor loops do, without the reference's sources."""
+    if not os.path.exists(PLUGIN_HOST):
+        raise FileNotFoundError("%s is missing: run build()" % PLUGIN_HOST)
+    return _run_driver(PLUGIN_HOST, params, "2000:" + plugin, output_rate, control_rate, config, repeat, tmpdir, poll)
+
+
+def _run_driver(exe, params, model, output_rate, control_rate, config, repeat, tmpdir, poll):
+    import tempfile
     params = np.ascontiguousarray(params, dtype=np.float32)
     with tempfile.TemporaryDirectory(dir=tmpdir) as td:
         pin = os.path.join(td, "p.f32")
@@ -335,7 +350,7 @@ def ref_synthesize(params, model="0", output_rate=44100, control_rate=250, confi
                             str(params.shape[0]), pout, str(repeat)] + (["poll=%d" % poll] if poll else []),
                            capture_output=True, text=True)
         if r.returncode != 0:
-            raise RuntimeError("ref_vtm failed: " + r.stderr)
+            raise RuntimeError("%s failed: %s" % (os.path.basename(exe), r.stderr))
         info = dict(kv.split("=") for kv in r.stdout.split())
         return np.fromfile(pout, dtype=np.float32), info
 

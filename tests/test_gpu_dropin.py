@@ -1,5 +1,6 @@
-"""Drop-in boundary on the GPU: the GamaTTS plugin loaded by the REAL reference loader, and
-the batched `gama_tts vtm` counterpart (C++ host over the C ABI)."""
+"""Drop-in boundary on the GPU: the GamaTTS plugin loaded the way GamaTTS's plugin loader loads it
+(oracle/plugin_host.cpp; also by the REAL reference loader where oracle/_ref is built), and the batched
+`gama_tts vtm` counterpart (C++ host over the C ABI)."""
 import os
 import struct
 import subprocess
@@ -17,16 +18,27 @@ PLUGIN = os.path.join(LIBDIR, "libgama_vtm_plugin.so")
 CLI = os.path.join(LIBDIR, "gama_vtm_batch")
 
 
-@pytest.mark.skipif(oracle.ref_binary() is None, reason="oracle/_ref/ref_vtm (the compiled reference) not present")
+def _through_loaders(tr, tmp_path, **kw):
+    """The plugin loaded and driven by oracle/_build/vtm_plugin_host (GamaTTS's loader and driver loops restated, built
+    in every checkout) and, where oracle/_ref/ref_vtm (the reference's own loader, compiled from its sources) is present,
+    by that binary too: both must hand back the same samples."""
+    out, info = oracle.plugin_synthesize(tr, PLUGIN, tmpdir=str(tmp_path), **kw)
+    if oracle.ref_binary() is not None:
+        ref_out, ref_info = oracle.ref_synthesize(tr, "2000:" + PLUGIN, tmpdir=str(tmp_path), **kw)
+        untimed = lambda d: {k: v for k, v in d.items() if k not in ("sec", "ns_per_step")}  # noqa: E731
+        assert np.array_equal(out, ref_out) and untimed(ref_info) == untimed(info)
+    return out, info
+
+
 @pytest.mark.parametrize("name", ["hello_m0", "rand5_m0"])
 def test_plugin_through_reference_loader(name, golden, tmp_path):
-    """ref_vtm is the reference's own VocalTractModel::getInstance + VocalTractModelPlugin
-    (dlopen/dlsym, vtm/VocalTractModelPlugin.cpp:57-91) driven by Controller::synthesize's loop;
+    """The loader (dlopen/dlsym, vtm/VocalTractModelPlugin.cpp:57-91) driven by Controller::synthesize's loop:
+    vtm_plugin_host restates both, ref_vtm is the reference's own VocalTractModel::getInstance + VocalTractModelPlugin;
     with model = 2000 every virtual call lands in our plugin object."""
     import golden_cases
     case = next(c for c in golden_cases.CASES if c["name"] == name)
     tr = golden_cases.track_for(case, golden)
-    out, info = oracle.ref_synthesize(tr, "2000:" + PLUGIN, tmpdir=str(tmp_path))
+    out, info = _through_loaders(tr, tmp_path)
     ref = golden[name + "__out"]
     assert out.size == ref.size == int(info["N"])
     assert float(info["fs"]) == 20034.0
@@ -34,7 +46,6 @@ def test_plugin_through_reference_loader(name, golden, tmp_path):
     assert _within(out, ref, 1e-9), _peak_err(out, ref)
 
 
-@pytest.mark.skipif(oracle.ref_binary() is None, reason="oracle/_ref/ref_vtm (the compiled reference) not present")
 def test_plugin_float_model_through_reference_loader(golden, tmp_path):
     """`gpu_precision = f32` makes the plugin stand in for model 1 (VocalTractModel0<float>)."""
     keys = oracle.read_config_file(oracle.VOICE_MALE)
@@ -46,7 +57,7 @@ def test_plugin_float_model_through_reference_loader(golden, tmp_path):
     import golden_cases
     case = next(c for c in golden_cases.CASES if c["name"] == "rand5_m1")
     tr = golden_cases.track_for(case, golden)
-    out, info = oracle.ref_synthesize(tr, "2000:" + PLUGIN, config=cfg, tmpdir=str(tmp_path))
+    out, info = _through_loaders(tr, tmp_path, config=cfg)
     ref = golden["rand5_m1__out"]
     assert out.size == ref.size and float(info["fs"]) == 20034.0
     assert np.array_equal(out, ref)  # the float path is bit-identical to the float model
@@ -63,14 +74,13 @@ def test_plugin_thirty_section_tube_through_reference_loader(golden, tmp_path):
     import golden_cases
     case = next(c for c in golden_cases.CASES if c["name"] == "rand5_m4")
     tr = golden_cases.track_for(case, golden)
-    out, info = oracle.ref_synthesize(tr, "2000:" + PLUGIN, config=cfg, tmpdir=str(tmp_path))
+    out, info = _through_loaders(tr, tmp_path, config=cfg)
     ref = golden["rand5_m4__out"]
     assert out.size == ref.size and float(info["fs"]) == 60102.0
     from test_gpu_parity import _within, _peak_err
     assert _within(out, ref, 1e-9), _peak_err(out, ref)
 
 
-@pytest.mark.skipif(oracle.ref_binary() is None, reason="oracle/_ref/ref_vtm (the compiled reference) not present")
 @pytest.mark.parametrize("poll", [64, 1024])
 @pytest.mark.parametrize("precision,name", [("f64", "hello_m0"), ("f32", "rand5_m1")])
 def test_plugin_interactive_protocol_through_reference_loader(precision, name, poll, golden, tmp_path):
@@ -86,7 +96,7 @@ def test_plugin_interactive_protocol_through_reference_loader(precision, name, p
     import golden_cases
     case = next(c for c in golden_cases.CASES if c["name"] == name)
     tr = golden_cases.track_for(case, golden)
-    out, info = oracle.ref_synthesize(tr, "2000:" + PLUGIN, config=cfg, tmpdir=str(tmp_path), poll=poll)
+    out, info = _through_loaders(tr, tmp_path, config=cfg, poll=poll)
     ref = golden[name + "__out"]
     assert out.size == ref.size == int(info["N"]) and int(info["callbacks"]) >= ref.size // poll
     if precision == "f32":
@@ -95,18 +105,17 @@ def test_plugin_interactive_protocol_through_reference_loader(precision, name, p
         from test_gpu_parity import _within, _peak_err
         assert _within(out, ref, 1e-9), _peak_err(out, ref)
     # and the same samples as our own batch protocol, bit for bit
-    batch, _ = oracle.ref_synthesize(tr, "2000:" + PLUGIN, config=cfg, tmpdir=str(tmp_path))
+    batch, _ = _through_loaders(tr, tmp_path, config=cfg)
     assert np.array_equal(out, batch)
 
 
-@pytest.mark.skipif(oracle.ref_binary() is None, reason="oracle/_ref/ref_vtm (the compiled reference) not present")
 def test_plugin_consecutive_utterances_through_reference_loader(golden, tmp_path):
     """Two syntheses on one plugin object, reset() in between as Controller does (Controller.cpp:231): the second
     utterance must not inherit anything from the first (recorded steps, failure flags)."""
     import golden_cases
     case = next(c for c in golden_cases.CASES if c["name"] == "rand5_m0")
     tr = golden_cases.track_for(case, golden)
-    out, info = oracle.ref_synthesize(tr, "2000:" + PLUGIN, tmpdir=str(tmp_path), repeat=3)
+    out, info = _through_loaders(tr, tmp_path, repeat=3)
     ref = golden["rand5_m0__out"]
     assert out.size == ref.size
     from test_gpu_parity import _within, _peak_err
@@ -273,7 +282,6 @@ def test_batched_cli_shards_across_device_slots(golden, tmp_path):
     assert len(outs["one"][0]) > 44 and len(outs["one"][4]) > 44
 
 
-@pytest.mark.skipif(oracle.ref_binary() is None, reason="oracle/_ref/ref_vtm (the compiled reference) not present")
 def test_plugin_model5_through_reference_loader(golden, golden5, tmp_path):
     """`gpu_model = 5` in vtm.txt makes the plugin stand in for reference model 5 (VocalTractModel5<double,1>); the
     reference's own loader and driver loop see its non-integer internal rate."""
@@ -286,7 +294,7 @@ def test_plugin_model5_through_reference_loader(golden, golden5, tmp_path):
     import golden5_cases
     case = next(c for c in golden5_cases.CASES if c["name"] == "rand5_m5")
     tr = golden5_cases.track_for(case, golden)
-    out, info = oracle.ref_synthesize(tr, "2000:" + PLUGIN, output_rate=48000, config=cfg, tmpdir=str(tmp_path))
+    out, info = _through_loaders(tr, tmp_path, output_rate=48000, config=cfg)
     ref = golden5["rand5_m5__out"]
     assert out.size == ref.size == int(info["N"])
     assert abs(float(info["fs"]) - golden5["manifest"]["rand5_m5"]["fs"]) < 1e-6
@@ -294,7 +302,6 @@ def test_plugin_model5_through_reference_loader(golden, golden5, tmp_path):
     _check(out, ref)
 
 
-@pytest.mark.skipif(oracle.ref_binary() is None, reason="oracle/_ref/ref_vtm (the compiled reference) not present")
 @pytest.mark.parametrize("poll", [64, 1024])
 def test_plugin_model5_interactive_protocol_through_reference_loader(poll, golden, golden5, tmp_path):
     """interactive = true with `gpu_model = 5`: the reference's loader constructs the object for the editor's caller contract
@@ -310,12 +317,12 @@ def test_plugin_model5_interactive_protocol_through_reference_loader(poll, golde
     import golden5_cases
     case = next(c for c in golden5_cases.CASES if c["name"] == "rand5_m5")
     tr = golden5_cases.track_for(case, golden)
-    out, info = oracle.ref_synthesize(tr, "2000:" + PLUGIN, output_rate=48000, config=cfg, tmpdir=str(tmp_path), poll=poll)
+    out, info = _through_loaders(tr, tmp_path, output_rate=48000, config=cfg, poll=poll)
     ref = golden5["rand5_m5__out"]
     assert out.size == ref.size == int(info["N"]) and int(info["callbacks"]) >= ref.size // poll
     from test_gpu_model5 import _check
     _check(out, ref)
-    batch, _ = oracle.ref_synthesize(tr, "2000:" + PLUGIN, output_rate=48000, config=cfg, tmpdir=str(tmp_path))
+    batch, _ = _through_loaders(tr, tmp_path, output_rate=48000, config=cfg)
     assert np.array_equal(out, batch)
 
 

@@ -1,24 +1,43 @@
-"""Oracle vs the REAL reference binary on fresh random tracks.
+"""Oracle vs the REAL reference on seeded random tracks.
 
-oracle/_ref/ref_vtm is compiled from /root/reference by oracle/Makefile in the build
-container and travels to the GPU box as a binary; when it is absent (a checkout that
-never saw the reference) these tests skip and the committed goldens remain the pin.
+tests/golden/random_golden.npz holds what oracle/_ref/ref_vtm (compiled from the reference sources by oracle/Makefile)
+produced for these tracks: sample count, SHA-256 of the float32 output and a strided subset
+(tests/golden/make_random_golden.py), so that the comparison runs in every checkout.
 """
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
+import golden_cases
 import oracle
 import tracks
 
-pytestmark = pytest.mark.skipif(oracle.ref_binary() is None, reason="oracle/_ref/ref_vtm not built")
+
+def random_golden():
+    z = np.load(os.path.join(oracle.GOLDEN_DIR, "random_golden.npz"), allow_pickle=False)
+    data = {k: z[k] for k in z.files}
+    data["manifest"] = json.loads(bytes(data.pop("manifest_json")).decode())
+    return data
+
+
+def check_against_random_golden(out, model, seed):
+    """`out` against the reference's output for (model, seed): same count, bit for bit (digest and strided samples)."""
+    g = random_golden()
+    key = "m%s_s%d" % (model.replace(":", "d"), seed)
+    m = g["manifest"][key]
+    assert out.size == m["n"]
+    assert np.array_equal(out[:: golden_cases.DIGEST_STRIDE], g[key + "__strided"])
+    assert hashlib.sha256(out.tobytes()).hexdigest() == m["sha256"]
+    return m
 
 
 @pytest.mark.parametrize("model,delay,layout,fm", [("0", 1, 0, 0), ("2", 1, 0, 0), ("2:2", 2, 0, 0), ("3", 3, 0, 0), ("4", 1, 1, 0),
                                                     ("1", 1, 0, 1), ("2f:2", 2, 0, 1), ("2f:4", 4, 0, 1), ("4f", 1, 1, 1)])
 @pytest.mark.parametrize("seed", [11, 12])
-def test_bit_identical_on_random_tracks(model, delay, layout, fm, seed, tmp_path):
+def test_bit_identical_on_random_tracks(model, delay, layout, fm, seed):
     tr = tracks.random_track(90, seed, consonant_heavy=bool(seed & 1))
-    ref, info = oracle.ref_synthesize(tr, model, tmpdir=str(tmp_path))
     out = oracle.synthesize(oracle.male_config(section_delay=delay, layout=layout, float_model=fm), tr)
-    assert out.size == int(info["N"])
-    assert np.array_equal(out, ref)
+    check_against_random_golden(out, model, seed)
