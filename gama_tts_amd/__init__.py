@@ -11,6 +11,7 @@ from .capi import (  # noqa: F401
     Plan,
     Stream,
     TrackConfig,
+    VoicesPlan,
     config5_from_dict,
     config_from_dict,
     device_count,

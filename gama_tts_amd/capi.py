@@ -173,6 +173,23 @@ def load_library(diagnostics=False):
     L.gvtm_stream_push.restype = i32
     L.gvtm_stream_finish.argtypes = [vp, vp, sz, vp, vp]
     L.gvtm_stream_finish.restype = i32
+    if hasattr(L, "gvtm_plan_create_voices"):  # (library variants built before plans of several voices still load: tools/ab.py)
+        L.gvtm_plan_create_voices.argtypes = [ctypes.POINTER(Config), sz, dbl, i32, ctypes.POINTER(vp)]
+        L.gvtm_plan_create_voices.restype = i32
+        L.gvtm_plan_voice_count.argtypes = [vp]
+        L.gvtm_plan_voice_count.restype = i32
+        L.gvtm_plan_voice_info.argtypes = [vp, i32, ctypes.POINTER(Info)]
+        L.gvtm_plan_voice_info.restype = i32
+        L.gvtm_voice_output_count.argtypes = [vp, i32, sz]
+        L.gvtm_voice_output_count.restype = sz
+        L.gvtm_voices_output_capacity.argtypes = [vp, sz]
+        L.gvtm_voices_output_capacity.restype = sz
+        L.gvtm_synthesize_voices_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
+        L.gvtm_synthesize_voices_device.restype = i32
+        L.gvtm_synthesize_voices_host.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp]
+        L.gvtm_synthesize_voices_host.restype = i32
+        L.gvtm_synthesize_voices_host_pcm16.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
+        L.gvtm_synthesize_voices_host_pcm16.restype = i32
     L.gvtm_plan_set_timing.argtypes = [vp, i32]
     L.gvtm_plan_set_timing.restype = i32
     L.gvtm_plan_take_kernel_ms.argtypes = [vp, ctypes.POINTER(i32)]
@@ -185,6 +202,8 @@ def load_library(diagnostics=False):
         L.gvtm_debug_dpp_selftest.argtypes = [vp, vp]
         L.gvtm_debug_short_math.argtypes = [i32, vp, sz, vp]
         L.gvtm_debug_device_float_math.argtypes = [vp, i32, vp, sz, vp]
+        L.gvtm_debug_group_voices.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp]
+        L.gvtm_debug_group_voices.restype = i32
     _libs[diagnostics] = L
     return L
 
@@ -477,6 +496,81 @@ class Plan:
         self._check(self._lib.gvtm_normalize_batch_device(
             self._h, _ptr(d_audio), int(batch), int(audio_stride), _ptr(d_counts), _ptr(d_maxabs), _ptr(d_out_f32),
             _ptr(d_out_i16), _ptr(d_scales), _ptr(stream)))
+
+
+class VoicesPlan(Plan):
+    """Owns a gvtm_plan of several voices (gvtm_plan_create_voices): configs[v] is voice v.  Its batches mix voices, one
+    voice id per utterance; the single-voice entries (Plan.synthesize_*, Stream) are refused on it when it has two or more."""
+
+    def __init__(self, configs, control_rate=250.0, device=0, diagnostics=False, rows=0):
+        self._lib = load_library(diagnostics)
+        self.diagnostics = bool(diagnostics)
+        self._h = ctypes.c_void_p()
+        self.configs = list(configs)
+        self.config = self.configs[0] if self.configs else None
+        arr = (Config * max(len(self.configs), 1))(*self.configs)
+        self._check(self._lib.gvtm_plan_create_voices(arr, len(self.configs), float(control_rate), int(device), ctypes.byref(self._h)))
+        self.n_voices = int(self._lib.gvtm_plan_voice_count(self._h))
+        self.info = self.voice_info(0)
+        if rows:
+            if not diagnostics:
+                raise ValueError("rows can only be forced on a diagnostics plan")
+            self._check(self._lib.gvtm_debug_set_rows(self._h, int(rows)))
+
+    def voice_info(self, voice):
+        info = Info()
+        self._check(self._lib.gvtm_plan_voice_info(self._h, int(voice), ctypes.byref(info)))
+        return info
+
+    def voice_output_count(self, voice, frames):
+        return int(self._lib.gvtm_voice_output_count(self._h, int(voice), int(frames)))
+
+    def voices_output_capacity(self, max_frames):
+        """Row length that holds every utterance of any mix of voices (ragged frame counts included)."""
+        return int(self._lib.gvtm_voices_output_capacity(self._h, int(max_frames)))
+
+    def synthesize_voices_device(self, d_params, d_voice_ids, batch, max_frames, d_audio, audio_stride, d_frame_counts=None,
+                                 d_out_counts=None, d_maxabs=None, stream=None):
+        """gvtm_synthesize_voices_device; all arguments are device pointers (torch tensors or raw ints)."""
+        self._check(self._lib.gvtm_synthesize_voices_device(
+            self._h, _ptr(d_params), _ptr(d_frame_counts), _ptr(d_voice_ids), int(max_frames), int(batch), _ptr(d_audio),
+            int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(stream)))
+
+    def _host_args(self, params, voice_ids, frame_counts):
+        params = np.ascontiguousarray(params, dtype=np.float32)
+        assert params.ndim == 3 and params.shape[2] == N_PARAM
+        batch, frames = params.shape[:2]
+        ids = np.ascontiguousarray(voice_ids, dtype=np.int32)
+        assert ids.shape == (batch,)
+        fc = None
+        if frame_counts is not None:
+            fc = np.ascontiguousarray(frame_counts, dtype=np.int32)
+            assert fc.shape == (batch,)
+        return params, ids, fc, batch, frames
+
+    def synthesize_host(self, params, voice_ids, frame_counts=None):
+        """params float32 [B][F][16], voice_ids int [B] -> (audio float32 [B][stride], counts int64 [B], maxabs float32 [B]);
+        stride = voices_output_capacity(F), rows zero beyond their count."""
+        params, ids, fc, batch, frames = self._host_args(params, voice_ids, frame_counts)
+        stride = self.voices_output_capacity(frames)
+        audio = np.zeros((batch, stride), dtype=np.float32)
+        counts = np.zeros(batch, dtype=np.int64)
+        maxabs = np.zeros(batch, dtype=np.float32)
+        self._check(self._lib.gvtm_synthesize_voices_host(
+            self._h, _ptr(params), _ptr(fc), _ptr(ids), frames, batch, _ptr(audio), stride, _ptr(counts), _ptr(maxabs)))
+        return audio, counts, maxabs
+
+    def synthesize_host_pcm16(self, params, voice_ids, frame_counts=None):
+        """-> (pcm int16 [B][stride], counts int64 [B], maxabs float32 [B], scales float32 [B])"""
+        params, ids, fc, batch, frames = self._host_args(params, voice_ids, frame_counts)
+        stride = self.voices_output_capacity(frames)
+        pcm = np.zeros((batch, stride), dtype=np.int16)
+        counts = np.zeros(batch, dtype=np.int64)
+        maxabs = np.zeros(batch, dtype=np.float32)
+        scales = np.zeros(batch, dtype=np.float32)
+        self._check(self._lib.gvtm_synthesize_voices_host_pcm16(
+            self._h, _ptr(params), _ptr(fc), _ptr(ids), frames, batch, _ptr(pcm), stride, _ptr(counts), _ptr(maxabs), _ptr(scales)))
+        return pcm, counts, maxabs, scales
 
 
 class Stream:

@@ -87,6 +87,10 @@ private:
 
 struct gvtm_plan {
 	gvtm::Design design;
+	// a plan of several voices (gvtm_plan_create_voices): `design` is voice 0, voices[v - 1] voice v; d_consts and
+	// d_wavetable then hold one block per voice, the FIR and the converter's tables (the same for every voice) one
+	int n_voices = 1;
+	std::vector<gvtm::Design> voices;
 	int device = 0;
 	int precision = GVTM_PRECISION_F64;
 	int rows = 0;       // utterances per workgroup; 0 = by batch size (a diagnostics build can force it)
@@ -104,6 +108,8 @@ struct gvtm_plan {
 	gvtm::Model5Constants* d_consts5 = nullptr; // model 5 plans only
 	// staging for the host-buffer entry point
 	DeviceBuffer s_params, s_frames, s_audio, s_counts, s_maxabs, s_pcm, s_scales;
+	// launches of several voices: the voice ids of the host entries, the row map / group voices / sort counts
+	DeviceBuffer s_voice_ids, s_groups;
 	int compute_units = 0; // of the plan's device (the host entries cut big batches into slices that fill them once)
 	// kernel timing (HIP events on the launch stream)
 	bool timing = false;
@@ -120,6 +126,7 @@ struct gvtm_plan {
 	// costs what one of 60 does, and the tube wavefronts slow down from 268 to 430 cycles per step next to five busy
 	// helpers.  A diagnostics build can still force it (tests hold it to the one-utterance shape's samples bit for bit).
 	int rows5_for(size_t) const { return rows == 2 ? 2 : 1; }
+	const gvtm::Design& voice(int v) const { return v == 0 ? design : voices[static_cast<size_t>(v) - 1]; }
 };
 
 namespace {
@@ -155,6 +162,8 @@ void free_plan(gvtm_plan* p)
 	p->s_maxabs.release();
 	p->s_pcm.release();
 	p->s_scales.release();
+	p->s_voice_ids.release();
+	p->s_groups.release();
 	if (p->h2d_stream) (void) hipStreamDestroy(p->h2d_stream);
 	if (p->compute_stream) (void) hipStreamDestroy(p->compute_stream);
 	if (p->copy_stream) (void) hipStreamDestroy(p->copy_stream);
@@ -193,15 +202,36 @@ int gvtm_device_count(void)
 	return n;
 }
 
-int gvtm_plan_create(const gvtm_config* config, double control_rate, int device, gvtm_plan** plan_out)
+} // extern "C"
+
+namespace {
+
+// gvtm_plan_create (n_voices == 1) and gvtm_plan_create_voices
+int create_plan(const gvtm_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
 {
-	if (!config || !plan_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null config or plan_out");
+	if (!configs || !plan_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null config or plan_out");
 	*plan_out = nullptr;
+	if (n_voices == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "a plan needs at least one voice");
+	if (n_voices > 0x7fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "too many voices");
+	for (size_t v = 1; v < n_voices; ++v) {
+		const gvtm_config& c0 = configs[0];
+		const gvtm_config& c = configs[v];
+		if (c.output_rate != c0.output_rate || c.section_delay != c0.section_delay || c.precision != c0.precision || c.tube_layout != c0.tube_layout) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "voice " + std::to_string(v) + ": output_rate, section_delay, precision and tube_layout must be "
+					"those of voice 0 (one plan is one model at one output rate)");
+		}
+	}
 	try {
 		std::unique_ptr<gvtm_plan, void (*)(gvtm_plan*)> plan(new gvtm_plan, free_plan);
-		const std::string why = gvtm::design_plan(*config, control_rate, plan->design);
-		if (!why.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, why);
-		plan->precision = config->precision;
+		const std::string why = gvtm::design_plan(configs[0], control_rate, plan->design);
+		if (!why.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, n_voices > 1 ? "voice 0: " + why : why);
+		plan->precision = configs[0].precision;
+		plan->n_voices = static_cast<int>(n_voices);
+		plan->voices.resize(n_voices - 1);
+		for (size_t v = 1; v < n_voices; ++v) {
+			const std::string why_v = gvtm::design_plan(configs[v], control_rate, plan->voices[v - 1]);
+			if (!why_v.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice " + std::to_string(v) + ": " + why_v);
+		}
 
 		if (device == GVTM_DEVICE_NONE) {
 			// design-only plan: info, tables and output counts work, synthesis reports NO_DEVICE
@@ -225,18 +255,29 @@ int gvtm_plan_create(const gvtm_config* config, double control_rate, int device,
 		}
 		plan->compute_units = prop.multiProcessorCount;
 		const gvtm::Design& dg = plan->design;
+		// one wavetable and one constants block per voice, back to back (the glottal FIR and the converter's tables depend
+		// on no configuration key: voice 0's serve all)
+		std::vector<gvtm::DeviceConstants> consts;
+		std::vector<double> wavetables;
+		std::vector<float> wavetables_f;
+		for (size_t v = 0; v < n_voices; ++v) {
+			const gvtm::Design& dv = plan->voice(static_cast<int>(v));
+			consts.push_back(dv.k);
+			wavetables.insert(wavetables.end(), dv.wavetable.begin(), dv.wavetable.end());
+			wavetables_f.insert(wavetables_f.end(), dv.wavetable_f.begin(), dv.wavetable_f.end());
+		}
 		if (dg.f32) {
-			if ((e = upload(&plan->d_wavetable, dg.wavetable_f)) != hipSuccess) return fail_hip(e, "upload wavetable");
+			if ((e = upload(&plan->d_wavetable, wavetables_f)) != hipSuccess) return fail_hip(e, "upload wavetable");
 			if ((e = upload(&plan->d_fir, dg.fir_f)) != hipSuccess) return fail_hip(e, "upload fir");
 			if ((e = upload(&plan->d_src_h, dg.src_h_f)) != hipSuccess) return fail_hip(e, "upload src_h");
 			if ((e = upload(&plan->d_src_dh, dg.src_dh_f)) != hipSuccess) return fail_hip(e, "upload src_dh");
 		} else {
-			if ((e = upload(&plan->d_wavetable, dg.wavetable)) != hipSuccess) return fail_hip(e, "upload wavetable");
+			if ((e = upload(&plan->d_wavetable, wavetables)) != hipSuccess) return fail_hip(e, "upload wavetable");
 			if ((e = upload(&plan->d_fir, dg.fir)) != hipSuccess) return fail_hip(e, "upload fir");
 			if ((e = upload(&plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
 			if ((e = upload(&plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
 		}
-		if ((e = upload(&plan->d_consts, std::vector<gvtm::DeviceConstants>(1, plan->design.k))) != hipSuccess) return fail_hip(e, "upload constants");
+		if ((e = upload(&plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
 		*plan_out = plan.release();
 		return GVTM_OK;
 	} catch (const std::bad_alloc&) {
@@ -244,6 +285,87 @@ int gvtm_plan_create(const gvtm_config* config, double control_rate, int device,
 	} catch (const std::exception& ex) {
 		return fail(GVTM_ERR_INVALID_ARGUMENT, ex.what());
 	}
+}
+
+// The single-voice entry points on a plan of several voices: which voice would they synthesize?
+int refuse_voices(const gvtm_plan* plan, const char* entry)
+{
+	return fail(GVTM_ERR_INVALID_ARGUMENT, std::string(entry) + ": the plan has " + std::to_string(plan->n_voices) +
+			" voices; use gvtm_synthesize_voices_* (one voice id per utterance)");
+}
+
+void fill_info(const gvtm_plan* plan, const gvtm::Design& dg, gvtm_info* info)
+{
+	const gvtm::DeviceConstants& k = dg.k;
+	info->internal_sample_rate = k.sample_rate;
+	info->control_steps = k.control_steps;
+	info->output_rate = dg.config.output_rate;
+	info->control_rate = dg.control_rate;
+	info->fir_taps = k.fir_taps;
+	info->time_register_increment = k.time_inc;
+	info->phase_increment = k.phase_inc;
+	info->pad_size = k.pad;
+	info->upsampling = k.upsampling;
+	info->device = plan->device;
+	info->precision = plan->precision;
+	info->section_delay = k.section_delay;
+	info->model5 = dg.model5 ? 1 : 0;
+	info->reserved_ = 0;
+	info->internal_rate_hz = dg.model5 ? dg.k5.sample_rate : static_cast<double>(k.sample_rate);
+}
+
+size_t design_output_count(const gvtm::Design& dg, size_t n_frames)
+{
+	const gvtm::DeviceConstants& k = dg.k;
+	return static_cast<size_t>(gvtm::src_output_count(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(n_frames) * k.control_steps));
+}
+
+size_t design_output_capacity(const gvtm::Design& dg, size_t max_frames)
+{
+	const gvtm::DeviceConstants& k = dg.k;
+	return static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(max_frames) * k.control_steps));
+}
+
+} // namespace
+
+extern "C" {
+
+int gvtm_plan_create(const gvtm_config* config, double control_rate, int device, gvtm_plan** plan_out)
+{
+	return create_plan(config, 1, control_rate, device, plan_out);
+}
+
+int gvtm_plan_create_voices(const gvtm_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
+{
+	return create_plan(configs, n_voices, control_rate, device, plan_out);
+}
+
+int gvtm_plan_voice_count(const gvtm_plan* plan)
+{
+	if (!plan) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	return plan->n_voices;
+}
+
+int gvtm_plan_voice_info(const gvtm_plan* plan, int voice, gvtm_info* info)
+{
+	if (!plan || !info) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or info");
+	if (voice < 0 || voice >= plan->n_voices) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice index out of range");
+	fill_info(plan, plan->voice(voice), info);
+	return GVTM_OK;
+}
+
+size_t gvtm_voice_output_count(const gvtm_plan* plan, int voice, size_t n_frames)
+{
+	if (!plan || voice < 0 || voice >= plan->n_voices) return static_cast<size_t>(-1);
+	return design_output_count(plan->voice(voice), n_frames);
+}
+
+size_t gvtm_voices_output_capacity(const gvtm_plan* plan, size_t max_frames)
+{
+	if (!plan) return static_cast<size_t>(-1);
+	size_t m = 0;
+	for (int v = 0; v < plan->n_voices; ++v) m = std::max(m, design_output_capacity(plan->voice(v), max_frames));
+	return m;
 }
 
 int gvtm_plan_create_model5(const gvtm5_config* config, double control_rate, int device, gvtm_plan** plan_out)
@@ -295,22 +417,7 @@ void gvtm_plan_destroy(gvtm_plan* plan)
 int gvtm_plan_info(const gvtm_plan* plan, gvtm_info* info)
 {
 	if (!plan || !info) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or info");
-	const gvtm::DeviceConstants& k = plan->design.k;
-	info->internal_sample_rate = k.sample_rate;
-	info->control_steps = k.control_steps;
-	info->output_rate = plan->design.config.output_rate;
-	info->control_rate = plan->design.control_rate;
-	info->fir_taps = k.fir_taps;
-	info->time_register_increment = k.time_inc;
-	info->phase_increment = k.phase_inc;
-	info->pad_size = k.pad;
-	info->upsampling = k.upsampling;
-	info->device = plan->device;
-	info->precision = plan->precision;
-	info->section_delay = k.section_delay;
-	info->model5 = plan->design.model5 ? 1 : 0;
-	info->reserved_ = 0;
-	info->internal_rate_hz = plan->design.model5 ? plan->design.k5.sample_rate : static_cast<double>(k.sample_rate);
+	fill_info(plan, plan->design, info); // (a plan of several voices: voice 0)
 	return GVTM_OK;
 }
 
@@ -334,15 +441,13 @@ int gvtm_plan_table(const gvtm_plan* plan, int which, double* out, size_t capaci
 size_t gvtm_output_count(const gvtm_plan* plan, size_t n_frames)
 {
 	if (!plan) return static_cast<size_t>(-1);
-	const gvtm::DeviceConstants& k = plan->design.k;
-	return static_cast<size_t>(gvtm::src_output_count(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(n_frames) * k.control_steps));
+	return design_output_count(plan->design, n_frames);
 }
 
 size_t gvtm_output_capacity(const gvtm_plan* plan, size_t max_frames)
 {
 	if (!plan) return static_cast<size_t>(-1);
-	const gvtm::DeviceConstants& k = plan->design.k;
-	return static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(max_frames) * k.control_steps));
+	return design_output_capacity(plan->design, max_frames);
 }
 
 #ifdef GVTM_DIAGNOSTICS
@@ -449,6 +554,28 @@ int gvtm_debug_device_float_math(gvtm_plan* plan, int kind, const float* x, size
 	(void) hipFree(dx);
 	(void) hipFree(dout);
 	if (e != hipSuccess) return fail_hip(e, "float math probe");
+	return GVTM_OK;
+}
+
+/* Test hook: the grouping kernel of gvtm_synthesize_voices_device alone, for `rows` utterances per workgroup, on device
+ * buffers: d_row_map [groups][rows] and d_group_voice [groups] with groups = ceil(batch / rows) + n_voices; d_out_counts /
+ * d_maxabs may be null.  Synchronous. */
+int gvtm_debug_group_voices(gvtm_plan* plan, const int32_t* d_voice_ids, size_t batch, int rows, int32_t* d_row_map, int32_t* d_group_voice,
+		int64_t* d_out_counts, float* d_maxabs)
+{
+	if (!plan || !d_voice_ids || !d_row_map || !d_group_voice || batch == 0 || rows < 1) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
+	DeviceScope scope(plan->device);
+	hipError_t e = scope.status();
+	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+	int32_t* counts = nullptr;
+	if ((e = hipMalloc(reinterpret_cast<void**>(&counts), sizeof(int32_t) * plan->n_voices * gvtm::kGroupVoicesThreads)) != hipSuccess) return fail_hip(e, "hipMalloc");
+	const size_t groups = (batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices);
+	gvtm::GroupVoicesArgs ga{d_voice_ids, batch, plan->n_voices, rows, groups, d_row_map, d_group_voice, counts, d_out_counts, d_maxabs};
+	e = gvtm::launch_group_voices(ga, nullptr);
+	if (e == hipSuccess) e = hipDeviceSynchronize();
+	(void) hipFree(counts);
+	if (e != hipSuccess) return fail_hip(e, "vtm_group_voices_kernel");
 	return GVTM_OK;
 }
 
@@ -571,11 +698,45 @@ struct StreamLaunch {
 	int rows;     // 1 unless the utterances are in lockstep
 };
 
+// The float model's noise samples for launches of up to `steps` internal steps per utterance: the plan's table, grown
+// (synchronously) when it is shorter; beyond the cap args.noise_lp stays null and the kernel generates them.
+int use_noise_table(gvtm_plan* plan, size_t steps, gvtm::SynthArgs& args)
+{
+	hipError_t e = hipSuccess;
+	constexpr size_t kNoiseTableMaxSteps = size_t(1) << 26; // 256 MB of table (~55 min of audio per utterance): beyond it the kernel generates the samples
+	if (steps > kNoiseTableMaxSteps) {
+		// (args.noise_lp stays null)
+	} else if (steps > plan->noise_len) {
+		// geometric growth (at least twice the old table, in units of 2^18 steps): a caller whose lengths creep up
+		// retires at most eight tables on the way to the cap
+		size_t want = ((steps + (size_t(1) << 18) - 1) >> 18) << 18;
+		want = std::min(std::max(want, 2 * plan->noise_len), kNoiseTableMaxSteps);
+		const bool f32 = true; // (the double paths generate the samples in the kernel: measured faster there)
+		std::vector<unsigned char> host(want * (f32 ? sizeof(float) : sizeof(double)));
+		gvtm::design_noise_table(want, f32, host.data());
+		void* fresh = nullptr;
+		if ((e = hipMalloc(&fresh, host.size())) != hipSuccess) return fail_hip(e, "hipMalloc (noise table)");
+		if ((e = hipMemcpy(fresh, host.data(), host.size(), hipMemcpyHostToDevice)) != hipSuccess) {
+			(void) hipFree(fresh);
+			return fail_hip(e, "hipMemcpy (noise table)");
+		}
+		if (plan->d_noise) plan->noise_retired.push_back(plan->d_noise);
+		plan->d_noise = fresh;
+		plan->noise_len = want;
+	}
+	if (steps <= kNoiseTableMaxSteps) {
+		args.noise_lp = plan->d_noise;
+		args.noise_len = plan->noise_len;
+	}
+	return GVTM_OK;
+}
+
 int launch_batch(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts,
 		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
 		int64_t* d_out_counts, float* d_maxabs, void* hip_stream, const StreamLaunch* sl)
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (plan->n_voices > 1) return refuse_voices(plan, sl ? "gvtm_stream_*" : "gvtm_synthesize_batch_device");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	if (batch == 0) return GVTM_OK;
 	if (!d_audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
@@ -628,32 +789,8 @@ int launch_batch(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_
 	args.src_dh = plan->d_src_dh;
 	if (!model5 && !sl && GVTM_NOISE_TABLE && plan->precision == GVTM_PRECISION_F32) {
 		// one-shot launches read the noise samples from the plan's table (streams generate them: their length has no bound)
-		const size_t steps = max_frames * static_cast<size_t>(k.control_steps);
-		constexpr size_t kNoiseTableMaxSteps = size_t(1) << 26; // 256 MB of table (~55 min of audio per utterance): beyond it the kernel generates the samples
-		if (steps > kNoiseTableMaxSteps) {
-			// (args.noise_lp stays null)
-		} else if (steps > plan->noise_len) {
-			// geometric growth (at least twice the old table, in units of 2^18 steps): a caller whose lengths creep up
-			// retires at most eight tables on the way to the cap
-			size_t want = ((steps + (size_t(1) << 18) - 1) >> 18) << 18;
-			want = std::min(std::max(want, 2 * plan->noise_len), kNoiseTableMaxSteps);
-			const bool f32 = true; // (the double paths generate the samples in the kernel: measured faster there)
-			std::vector<unsigned char> host(want * (f32 ? sizeof(float) : sizeof(double)));
-			gvtm::design_noise_table(want, f32, host.data());
-			void* fresh = nullptr;
-			if ((e = hipMalloc(&fresh, host.size())) != hipSuccess) return fail_hip(e, "hipMalloc (noise table)");
-			if ((e = hipMemcpy(fresh, host.data(), host.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-				(void) hipFree(fresh);
-				return fail_hip(e, "hipMemcpy (noise table)");
-			}
-			if (plan->d_noise) plan->noise_retired.push_back(plan->d_noise);
-			plan->d_noise = fresh;
-			plan->noise_len = want;
-		}
-		if (steps <= kNoiseTableMaxSteps) {
-			args.noise_lp = plan->d_noise;
-			args.noise_len = plan->noise_len;
-		}
+		const int rc = use_noise_table(plan, max_frames * static_cast<size_t>(k.control_steps), args);
+		if (rc != GVTM_OK) return rc;
 	}
 	args.max_frames = max_frames;
 	args.audio_stride = audio_stride;
@@ -689,6 +826,110 @@ int launch_batch(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_
 	return GVTM_OK;
 }
 
+// gvtm_synthesize_voices_device: the grouping kernel builds the row map from the voice ids, then the voice variant of the
+// synthesis kernel runs ceil(batch / rows) + n_voices workgroups (the bound for any mix of ids; those past the last
+// voice's groups exit at once), each on one voice's constants, wavetable and ring.  Enqueue-only: no read-back.
+int launch_voices(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts, const int32_t* d_voice_ids,
+		size_t max_frames, size_t batch, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, void* hip_stream)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (plan->design.model5) return fail(GVTM_ERR_INVALID_ARGUMENT, "model 5 plans have one voice: gvtm_synthesize_batch_*");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	if (batch == 0) return GVTM_OK;
+	if (!d_audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
+	if (!d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
+	if (max_frames > 0 && !d_params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
+	if (batch > 0x3fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
+	unsigned max_steps = 0;
+	for (int v = 0; v < plan->n_voices; ++v) max_steps = std::max(max_steps, plan->voice(v).k.control_steps);
+	if (static_cast<unsigned long long>(max_frames) * max_steps + 4096ull >= (1ull << 31)) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
+	}
+	for (int v = 0; v < plan->n_voices; ++v) {
+		if (audio_stride < design_output_count(plan->voice(v), max_frames)) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_voice_output_count(plan, voice, max_frames) of voice " + std::to_string(v));
+		}
+	}
+	const gvtm::DeviceConstants& k = plan->design.k;
+	constexpr size_t kLdsPerWorkgroup = 160 * 1024;
+	// the product's shapes (1, 2 or 4 rows); the LDS holds the longest ring of the voices (a down-sampling voice keeps the
+	// reference's 1024-sample ring), and a shape it does not fit gives way to the next smaller one, as in launch_batch
+	int rows = std::min(gvtm::synth_rows(plan->precision, batch, plan->rows, k.section_delay), 4);
+	auto longest_ring = [&](int r) {
+		int xr = 0;
+		for (int v = 0; v < plan->n_voices; ++v) xr = std::max(xr, gvtm::synth_ring_length(plan->voice(v).k, plan->precision, r));
+		return xr;
+	};
+	while (rows > 1 && gvtm::synth_lds_bytes(k, plan->precision, rows, longest_ring(rows)) > kLdsPerWorkgroup) rows /= 2;
+	const int xr = longest_ring(rows);
+	if (gvtm::synth_lds_bytes(k, plan->precision, rows, xr) > kLdsPerWorkgroup) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
+
+	DeviceScope scope(plan->device);
+	hipError_t e = scope.status();
+	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+	hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+
+	const size_t groups = (batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices);
+	const size_t map_ints = groups * rows, count_ints = static_cast<size_t>(plan->n_voices) * gvtm::kGroupVoicesThreads;
+	// (the scratch is the plan's: launches on one plan are ordered on one stream, as for gvtm_synthesize_events_device)
+	if ((e = plan->s_groups.ensure(sizeof(int32_t) * (map_ints + groups + count_ints))) != hipSuccess) return fail_hip(e, "hipMalloc row map");
+	int32_t* const d_map = static_cast<int32_t*>(plan->s_groups.ptr);
+	gvtm::GroupVoicesArgs ga{d_voice_ids, batch, plan->n_voices, rows, groups, d_map, d_map + map_ints, d_map + map_ints + groups, d_out_counts, d_maxabs};
+	if ((e = gvtm::launch_group_voices(ga, stream)) != hipSuccess) return fail_hip(e, "vtm_group_voices_kernel launch");
+
+	gvtm::SynthArgs args;
+	args.k = k;
+	args.kconst = plan->d_consts;
+	args.params = d_params;
+	args.frame_counts = d_frame_counts;
+	args.audio = d_audio;
+	args.out_counts = d_out_counts;
+	args.maxabs = d_maxabs;
+	args.wavetable = plan->d_wavetable;
+	args.fir = plan->d_fir;
+	std::memset(&args.fir_k, 0, sizeof(args.fir_k));
+	const gvtm::Design& dg = plan->design;
+	if (dg.f32) {
+		for (size_t i = 0; i < dg.fir_f.size() && i < 64; ++i) args.fir_k.f[i] = dg.fir_f[i];
+	} else {
+		for (size_t i = 0; i < dg.fir.size() && i < 49; ++i) args.fir_k.d[i] = dg.fir[i];
+	}
+	args.src_h = plan->d_src_h;
+	args.src_dh = plan->d_src_dh;
+	if (GVTM_NOISE_TABLE && plan->precision == GVTM_PRECISION_F32) {
+		// one table for every voice (every utterance starts from the same seed), as long as the voice with the most steps needs
+		const int rc = use_noise_table(plan, max_frames * static_cast<size_t>(max_steps), args);
+		if (rc != GVTM_OK) return rc;
+	}
+	args.max_frames = max_frames;
+	args.audio_stride = audio_stride;
+	args.batch = batch;
+	args.xr = xr;
+	args.debug_taps = nullptr;
+	args.phase_cycles = nullptr;
+	args.row_map = d_map;
+	args.group_voice = d_map + map_ints;
+
+	EventPair ev;
+	if (plan->timing) {
+		if (!plan->pool.empty()) {
+			ev = plan->pool.back();
+			plan->pool.pop_back();
+		} else {
+			if ((e = hipEventCreate(&ev.start)) != hipSuccess) return fail_hip(e, "hipEventCreate");
+			if ((e = hipEventCreate(&ev.stop)) != hipSuccess) return fail_hip(e, "hipEventCreate");
+		}
+		if ((e = hipEventRecord(ev.start, stream)) != hipSuccess) return fail_hip(e, "hipEventRecord");
+	}
+	e = gvtm::launch_synth_voices(args, groups, plan->precision, rows, stream);
+	if (plan->timing) {
+		(void) hipEventRecord(ev.stop, stream);
+		plan->pending.push_back(ev);
+	}
+	if (e != hipSuccess) return fail_hip(e, "vtm_synth_kernel launch (voices)");
+	return GVTM_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -700,11 +941,18 @@ int gvtm_synthesize_batch_device(gvtm_plan* plan, const float* d_params, const i
 	return launch_batch(plan, d_params, d_frame_counts, batch, max_frames, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream, nullptr);
 }
 
+int gvtm_synthesize_voices_device(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts, const int32_t* d_voice_ids,
+		size_t max_frames, size_t batch, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, void* hip_stream)
+{
+	return launch_voices(plan, d_params, d_frame_counts, d_voice_ids, max_frames, batch, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream);
+}
+
 int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* config, const gvtm_event* d_events,
 		const int64_t* d_event_offsets, size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
 		int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream)
 {
 	if (!plan || !config) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or config");
+	if (plan->n_voices > 1) return refuse_voices(plan, "gvtm_synthesize_events_device");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	if (batch == 0) return GVTM_OK;
 	if (!d_events || !d_event_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events or event_offsets");
@@ -742,6 +990,7 @@ namespace {
 struct HostJob {
 	const float* params;
 	const int32_t* frame_counts;
+	const int32_t* voice_ids; // null: the plan's one voice (gvtm_synthesize_batch_host*), else gvtm_synthesize_voices_host*
 	size_t batch, max_frames;
 	float* audio;      // float32 output [batch][stride], or null
 	int16_t* pcm;      // int16 output [batch][stride], or null
@@ -759,13 +1008,18 @@ struct HostJob {
 int host_pipeline(gvtm_plan* plan, const HostJob& j)
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	const bool voices = j.voice_ids != nullptr;
+	if (!voices && plan->n_voices > 1) return refuse_voices(plan, j.pcm ? "gvtm_synthesize_batch_host_pcm16" : "gvtm_synthesize_batch_host");
+	if (voices && plan->design.model5) return fail(GVTM_ERR_INVALID_ARGUMENT, "model 5 plans have one voice: gvtm_synthesize_batch_*");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	const size_t batch = j.batch, max_frames = j.max_frames, audio_stride = j.stride;
 	if (batch == 0) return GVTM_OK;
 	if (!j.audio && !j.pcm) return fail(GVTM_ERR_INVALID_ARGUMENT, "null output buffer");
 	if (max_frames > 0 && !j.params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
-	if (audio_stride < gvtm_output_count(plan, max_frames)) {
-		return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_output_count(plan, max_frames)");
+	for (int v = 0; v < plan->n_voices; ++v) {
+		if (audio_stride < design_output_count(plan->voice(v), max_frames)) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_output_count(plan, max_frames)");
+		}
 	}
 	// A frame count outside [0, max_frames] fails THAT utterance (out_counts[b] = -1, no samples); the others are
 	// synthesized.  The device sees it as an empty utterance.
@@ -779,6 +1033,12 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 					sane[b] = 0;
 					bad.push_back(b);
 				}
+			}
+		}
+		// a voice id outside [0, n_voices) fails that utterance the same way (the device leaves it out of the row map)
+		if (voices) {
+			for (size_t b = 0; b < batch; ++b) {
+				if (j.voice_ids[b] < 0 || j.voice_ids[b] >= plan->n_voices) bad.push_back(b);
 			}
 		}
 	} catch (const std::bad_alloc&) {
@@ -797,6 +1057,7 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 	if ((e = plan->s_counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
 	if ((e = plan->s_maxabs.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc maxabs");
 	if (counts_in && (e = plan->s_frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
+	if (voices && (e = plan->s_voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
 	if (j.pcm && (e = plan->s_pcm.ensure(obytes ? obytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc pcm");
 	if (j.pcm && (e = plan->s_scales.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc scales");
 	if (!plan->h2d_stream && (e = hipStreamCreateWithFlags(&plan->h2d_stream, hipStreamNonBlocking)) != hipSuccess) return fail_hip(e, "hipStreamCreate");
@@ -813,8 +1074,13 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 	if (counts_in && (e = hipMemcpy(plan->s_frames.ptr, counts_in, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
 		return fail_hip(e, "H2D frame_counts");
 	}
-	// rows come back zero beyond their sample count (the staging buffers are reused between calls)
-	const bool ragged = counts_in != nullptr || audio_stride > gvtm_output_count(plan, max_frames);
+	const int32_t* const d_voice_ids = voices ? static_cast<const int32_t*>(plan->s_voice_ids.ptr) : nullptr;
+	if (voices && (e = hipMemcpy(plan->s_voice_ids.ptr, j.voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
+		return fail_hip(e, "H2D voice_ids");
+	}
+	// rows come back zero beyond their sample count (the staging buffers are reused between calls; the voices of a mixed
+	// batch give different counts)
+	const bool ragged = counts_in != nullptr || voices || audio_stride > gvtm_output_count(plan, max_frames);
 
 	// the shape of the whole batch, and how many utterances fill the machine once in it
 	const bool model5 = plan->design.model5;
@@ -848,8 +1114,13 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 		if (ragged && j.pcm && (e = hipMemsetAsync(d_pcm + lo * audio_stride, 0, sizeof(int16_t) * n * audio_stride, plan->compute_stream)) != hipSuccess) {
 			rc = fail_hip(e, "hipMemsetAsync"); break;
 		}
-		rc = gvtm_synthesize_batch_device(plan, d_params + lo * row_in, d_frames ? d_frames + lo : nullptr, n, max_frames,
-				d_audio + lo * audio_stride, audio_stride, d_counts + lo, d_maxabs + lo, plan->compute_stream);
+		if (voices) {
+			rc = gvtm_synthesize_voices_device(plan, d_params + lo * row_in, d_frames ? d_frames + lo : nullptr, d_voice_ids + lo, max_frames, n,
+					d_audio + lo * audio_stride, audio_stride, d_counts + lo, d_maxabs + lo, plan->compute_stream);
+		} else {
+			rc = gvtm_synthesize_batch_device(plan, d_params + lo * row_in, d_frames ? d_frames + lo : nullptr, n, max_frames,
+					d_audio + lo * audio_stride, audio_stride, d_counts + lo, d_maxabs + lo, plan->compute_stream);
+		}
 		if (rc != GVTM_OK) break;
 		if (j.pcm) {
 			// (normalize takes at most 65535 utterances per launch: a slice is far below that unless the batch is one slice)
@@ -892,7 +1163,8 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 		if (j.audio) std::fill(j.audio + b * audio_stride, j.audio + (b + 1) * audio_stride, 0.0f);
 		if (j.pcm) std::fill(j.pcm + b * audio_stride, j.pcm + (b + 1) * audio_stride, int16_t(0));
 	}
-	if (!bad.empty()) g_last_error = "frame_counts entry outside [0, max_frames]: those utterances have out_counts = -1";
+	if (!bad.empty()) g_last_error = voices ? "frame_counts entry outside [0, max_frames] or voice id outside [0, n_voices): those utterances have out_counts = -1"
+	                                        : "frame_counts entry outside [0, max_frames]: those utterances have out_counts = -1";
 	return GVTM_OK;
 }
 
@@ -905,7 +1177,15 @@ int gvtm_synthesize_batch_host(gvtm_plan* plan, const float* params, const int32
 		int64_t* out_counts, float* maxabs)
 {
 	if (batch != 0 && !audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
-	return host_pipeline(plan, HostJob{params, frame_counts, batch, max_frames, audio, nullptr, audio_stride, out_counts, maxabs, nullptr});
+	return host_pipeline(plan, HostJob{params, frame_counts, nullptr, batch, max_frames, audio, nullptr, audio_stride, out_counts, maxabs, nullptr});
+}
+
+int gvtm_synthesize_voices_host(gvtm_plan* plan, const float* params, const int32_t* frame_counts, const int32_t* voice_ids,
+		size_t max_frames, size_t batch, float* audio, size_t audio_stride, int64_t* out_counts, float* maxabs)
+{
+	if (batch != 0 && !audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
+	if (batch != 0 && !voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
+	return host_pipeline(plan, HostJob{params, frame_counts, voice_ids, batch, max_frames, audio, nullptr, audio_stride, out_counts, maxabs, nullptr});
 }
 
 int gvtm_synthesize_batch_host_pcm16(gvtm_plan* plan, const float* params, const int32_t* frame_counts,
@@ -913,7 +1193,15 @@ int gvtm_synthesize_batch_host_pcm16(gvtm_plan* plan, const float* params, const
 		int64_t* out_counts, float* maxabs, float* scales)
 {
 	if (batch != 0 && !pcm) return fail(GVTM_ERR_INVALID_ARGUMENT, "null pcm buffer");
-	return host_pipeline(plan, HostJob{params, frame_counts, batch, max_frames, nullptr, pcm, pcm_stride, out_counts, maxabs, scales});
+	return host_pipeline(plan, HostJob{params, frame_counts, nullptr, batch, max_frames, nullptr, pcm, pcm_stride, out_counts, maxabs, scales});
+}
+
+int gvtm_synthesize_voices_host_pcm16(gvtm_plan* plan, const float* params, const int32_t* frame_counts, const int32_t* voice_ids,
+		size_t max_frames, size_t batch, int16_t* pcm, size_t pcm_stride, int64_t* out_counts, float* maxabs, float* scales)
+{
+	if (batch != 0 && !pcm) return fail(GVTM_ERR_INVALID_ARGUMENT, "null pcm buffer");
+	if (batch != 0 && !voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
+	return host_pipeline(plan, HostJob{params, frame_counts, voice_ids, batch, max_frames, nullptr, pcm, pcm_stride, out_counts, maxabs, scales});
 }
 
 int gvtm_host_alloc(size_t bytes, void** ptr_out)
@@ -1078,6 +1366,7 @@ int gvtm_stream_create(gvtm_plan* plan, size_t batch, gvtm_stream** stream_out)
 {
 	if (!plan || !stream_out || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan / stream_out or empty batch");
 	*stream_out = nullptr;
+	if (plan->n_voices > 1) return refuse_voices(plan, "gvtm_stream_create");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	try {
 		std::unique_ptr<gvtm_stream> s(new gvtm_stream);

@@ -125,6 +125,19 @@ double amplitude_60db(double db);
 // BEYOND its end pointer.  If fewer fills than that overshoot follow before flushBuffer()'s explicit dataEmpty(), it
 // finds endPtr < emptyPtr_, adds BUFFER_SIZE and converts one more lap of the ring: outputs [k_from, k_to) with read
 // positions up to fills + 1024, taken from the ring's leftovers.  Returns whether that happens.
+// internal-rate ring of a workgroup row for a chunk of `chunk` steps: a power of two holding two chunks, the resampler's
+// history and the flush zeros (+ 64: the resampler emits on a 64-aligned grid of outputs, so up to 63 outputs = at most
+// 64 inputs wait a chunk longer); the reference's own BUFFER_SIZE when down-sampling (the flush overrun reads the ring's
+// leftovers modulo that length, vtm_kernel_v2.inc's epilogue).  The host sizes launches with it, and a launch of several
+// voices computes each workgroup's own from its voice's constants.
+GVTM_DESIGN_HD int synth_ring_for(int upsampling, int pad, int chunk)
+{
+	if (!upsampling) return kSrcRing;
+	int xr = 128;
+	while (xr < 2 * chunk + 4 * pad + 64) xr *= 2;
+	return xr;
+}
+
 GVTM_DESIGN_HD bool src_flush_overrun(unsigned time_inc, int pad, uint64_t steps, uint64_t& k_from, uint64_t& k_to)
 {
 	const uint64_t fills = steps + 2ull * static_cast<uint64_t>(pad);

@@ -364,9 +364,33 @@ constexpr int serial_waves()
 	return TubeLayout<LAYOUT>::kWaveWide ? U + 4 : 5 * ((U + 3) / 4);
 }
 
-template <typename CT, typename ST, int D, int U, int C, int NH, int LAYOUT>
-__global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_synth_kernel(const SynthArgs a)
+// Several voices in one launch (gvtm_synthesize_voices_device): the kernel's last template argument carries, besides the tube
+// layout in bit 0, the flag kVoicesFlag (default off).  With it, workgroup g synthesizes the utterances
+// a.row_map[g * U .. g * U + U) (-1: an empty row, only ever at the end of a group) of voice a.group_voice[g] (-1: a group past
+// the last voice's, which exits at once), and that voice picks the constants a.kconst[voice], the wavetable at
+// a.wavetable + voice * 512 and the ring length; the LDS is sized for the longest ring of the launch (the ring is the last
+// region).  Without the flag every expression below is the one it was before the flag existed: each voice-dependent one is
+// a conditional on the constant VOICES whose voice arm the compiler never emits, so the single-voice kernels compile to
+// the same code.  (A separate bool parameter would rename every kernel, a wrapper kernel around an inlined body changes
+// what the register allocator spills: float, eight rows 476 -> 620 bytes of scratch.)
+constexpr int kVoicesFlag = 2;
+
+__device__ __forceinline__ size_t voice_row(const SynthArgs& a, size_t slot)
 {
+	const int r = a.row_map[slot];
+	return r < 0 ? a.batch : static_cast<size_t>(r);
+}
+
+template <typename CT, typename ST, int D, int U, int C, int NH, int LAYOUT_FLAGS>
+__global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) void vtm_synth_kernel(const SynthArgs a)
+{
+	constexpr int LAYOUT = LAYOUT_FLAGS & 1; // gvtm_tube_layout
+	constexpr bool VOICES = (LAYOUT_FLAGS & kVoicesFlag) != 0;
+	int voice = 0;
+	if constexpr (VOICES) {
+		voice = a.group_voice[blockIdx.x];
+		if (voice < 0) return; // (uniform across the workgroup, before any barrier)
+	}
 	using TL = TubeLayout<LAYOUT>;
 	static_assert(!TL::kWaveWide || U <= 4, "wave-wide tubes: one tube wavefront per utterance, at most four");
 	constexpr int kSerial = serial_waves<U, LAYOUT>(); // serial wavefronts; the helpers follow
@@ -377,7 +401,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 	// internal-rate ring length: a power of two >= 2 chunks + resampler history + flush zeros, checked by the host
 	// (v2_ring_length); 1024 = the reference's BUFFER_SIZE when down-sampling, which makes the ring alias exactly as
 	// the reference's does in its flush overrun (see the epilogue below)
-	const int XR = a.xr;
+	const int XR = VOICES ? synth_ring_for(a.kconst[voice].upsampling, a.kconst[voice].pad, C) : a.xr;
 	const int XRS = XR + kXMirror; // samples from one utterance's ring to the next one's (ring + mirror)
 	static_assert(NH >= 1, "at least one helper wavefront");
 	constexpr int kThreads = (kSerial + NH) * 64;
@@ -417,6 +441,8 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 	const int wave = tid >> 6;
 	const int hl = lane;      // helper lane index inside its wavefront
 	const size_t group = blockIdx.x;
+	// GVTM_ROW_UTT(u, single-voice expression): the utterance of row u, a.batch for an empty row (see kVoicesFlag)
+#define GVTM_ROW_UTT(u, ...) (VOICES ? voice_row(a, group * U + (u)) : __VA_ARGS__)
 	// gvtm_stream_*: a launch continues utterances from the state an earlier launch left in device memory (a.stream)
 	// and leaves its own behind.  A push synthesizes whole frames, keeps the converter's flush for later and finds the
 	// frame AFTER its last one in the buffer; finish (and the one-shot entry) flushes.
@@ -469,12 +495,12 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 
 	// ---- constants, extents and design tables into LDS; clear rings and pre-rolls
 	{
-		const int* src = reinterpret_cast<const int*>(a.kconst);
+		const int* src = reinterpret_cast<const int*>(VOICES ? a.kconst + voice : a.kconst);
 		int* dst = reinterpret_cast<int*>(sm.kc);
 		for (int i = tid; i < static_cast<int>(sizeof(DeviceConstants) / sizeof(int)); i += kThreads) dst[i] = src[i];
 	}
 	// design tables: fp64 in device memory, or float as designed by the host when everything runs in float
-	for (int i = tid; i < kWavetableLength; i += kThreads) sm.wavetable[i] = static_cast<const CT*>(a.wavetable)[i];
+	for (int i = tid; i < kWavetableLength; i += kThreads) sm.wavetable[i] = VOICES ? static_cast<const CT*>(a.wavetable)[static_cast<size_t>(voice) * kWavetableLength + i] : static_cast<const CT*>(a.wavetable)[i];
 	for (int i = tid; i < kSrcFilterLength; i += kThreads) {
 		if constexpr (kSrcHOnly<CT, ST, U>) {
 			reinterpret_cast<ST*>(sm.src)[i] = static_cast<ST>(static_cast<const CT*>(a.src_h)[i]);
@@ -489,7 +515,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 	__syncthreads();
 	if (tid < U) {
 		Extent e{0, 0, 0, 0, 0ull, 0ull};
-		const size_t ug = group * U + tid;
+		const size_t ug = GVTM_ROW_UTT(tid, group * U + tid);
 		unsigned peak0 = 0u;
 		if (ug < a.batch) {
 			// a stream's push carries one more row than it synthesizes: the next frame, which the last one interpolates towards
@@ -550,8 +576,8 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 	if (a.stream) {
 		// the resampler's ring, the decimator's pre-roll (the 48 oversampled source values in front of the next step)
 		for (int u = 0; u < U; ++u) {
-			if (group * U + u >= a.batch) break;
-			const unsigned char* sb = a.stream + (group * U + u) * a.stream_stride;
+			if (GVTM_ROW_UTT(u, group * U + u) >= a.batch) break;
+			const unsigned char* sb = a.stream + GVTM_ROW_UTT(u, (group * U + u)) * a.stream_stride;
 			const ST* ring = reinterpret_cast<const ST*>(sb + SL::ring(kTubeLanes, kTubeWords));
 			for (int i = tid; i < XRS; i += kThreads) sm.x[u * XRS + i] = ring[i < XR ? i : i - XR];
 			const CT* pre = reinterpret_cast<const CT*>(sb + SL::wpre(kTubeLanes, kTubeWords));
@@ -620,7 +646,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 		const int frames = sm.ext[rowp].frames;
 		const int last = sm.ext[rowp].last_frame;
 		if (frames > 0) {
-			const float* __restrict__ P = a.params + (group * U + rowp) * a.max_frames * 16;
+			const float* __restrict__ P = a.params + GVTM_ROW_UTT(rowp, (group * U + rowp)) * a.max_frames * 16;
 			ip_this = P[Lp];
 			ip_next = P[static_cast<size_t>(last > 1 ? 1 : last) * 16 + Lp];
 			ip_next2 = P[static_cast<size_t>(last > 2 ? 2 : last) * 16 + Lp];
@@ -630,9 +656,9 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 	// a stream's recurrence states as the previous launch left them (all zero and the fresh noise seed after create / reset)
 	const int tube_utt = kTubePerWave ? sub : urow;           // utterance of a tube lane
 	const int serial_utt = (role == 0) ? tube_utt : urow;      // utterance of a lane of any serial wavefront
-	const bool serial_live = role < 4 && serial_utt < U && group * U + serial_utt < a.batch;
+	const bool serial_live = role < 4 && serial_utt < U && GVTM_ROW_UTT(serial_utt, group * U + serial_utt) < a.batch;
 	if (a.stream && serial_live) {
-		const unsigned char* sb = a.stream + (group * U + serial_utt) * a.stream_stride;
+		const unsigned char* sb = a.stream + GVTM_ROW_UTT(serial_utt, (group * U + serial_utt)) * a.stream_stride;
 		const CT* sc = reinterpret_cast<const CT*>(sb + SL::scalars());
 		if (role == 1) {
 			sc_pos = sc[kSsPos];
@@ -707,7 +733,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 				CT* slot = sm.w + (static_cast<size_t>(c % 3) * U + u) * (kWPre + 2 * C);
 				slot[kWPre + h] = v;
 				if (GVTM_KERNEL_TAPS && a.debug_taps) {
-					a.debug_taps[((group * U + u) * a.max_frames * k.control_steps + static_cast<size_t>(c) * C + (h >> 1)) * 8 + 5 + (h & 1)] = p;
+					a.debug_taps[(GVTM_ROW_UTT(u, (group * U + u)) * a.max_frames * k.control_steps + static_cast<size_t>(c) * C + (h >> 1)) * 8 + 5 + (h & 1)] = p;
 				}
 				if (h >= 2 * C - kWPre) {
 					CT* next = sm.w + (static_cast<size_t>((c + 1) % 3) * U + u) * (kWPre + 2 * C);
@@ -750,7 +776,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 			CT* slot = sm.w + (static_cast<size_t>(c % 3) * U + u[q]) * (kWPre + 2 * C);
 			slot[kWPre + h[q]] = v;
 			if (GVTM_KERNEL_TAPS && a.debug_taps) {
-				a.debug_taps[((group * U + u[q]) * a.max_frames * k.control_steps + static_cast<size_t>(c) * C + (h[q] >> 1)) * 8 + 5 + (h[q] & 1)] = p[q];
+				a.debug_taps[(GVTM_ROW_UTT(u[q], (group * U + u[q])) * a.max_frames * k.control_steps + static_cast<size_t>(c) * C + (h[q] >> 1)) * 8 + 5 + (h[q] & 1)] = p[q];
 			}
 			if (h[q] >= 2 * C - kWPre) {
 				// the tail of a chunk doubles as the FIR pre-roll of the next one
@@ -858,7 +884,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 			usg[kF1Sig * C] = signal;
 			usg[kF1Thr * C] = throat_in;
 			if (GVTM_KERNEL_TAPS && a.debug_taps) {
-				double* t = a.debug_taps + ((group * U + u) * a.max_frames * k.control_steps + static_cast<size_t>(c) * C + s) * 8;
+				double* t = a.debug_taps + (GVTM_ROW_UTT(u, (group * U + u)) * a.max_frames * k.control_steps + static_cast<size_t>(c) * C + s) * 8;
 				t[0] = tube_in; t[1] = signal; t[2] = throat_in; t[3] = acc; t[4] = lp;
 			}
 		}
@@ -1149,7 +1175,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 			const float y = (ko < k_hi[u]) ? static_cast<float>(acc[u]) : 0.0f;
 			// (a stream's launch numbers its samples from its own first one)
 			const uint64_t kout = ko - sm.ext[u0 + u].k_first;
-			if (ko < k_hi[u] && kout < a.audio_stride) a.audio[(group * U + u0 + u) * a.audio_stride + kout] = y;
+			if (ko < k_hi[u] && kout < a.audio_stride) a.audio[GVTM_ROW_UTT(u0 + u, (group * U + u0 + u)) * a.audio_stride + kout] = y;
 			// maximum of every 16-lane row by DPP rotations (lanes that have left the pass supply 0), one LDS atomic per row
 			// and utterance.  (The butterfly over the whole wavefront with __shfl_xor was six ds_bpermute round trips in a
 			// row per utterance -- 24 dependent LDS round trips at the end of a pass, most of its ~7800 cycles.)
@@ -1200,7 +1226,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 		const int valid = valid_in(u, c);
 		if (valid <= 0) return;
 		const int last = sm.ext[u].last_frame;
-		const float* __restrict__ P = a.params + (group * U + u) * a.max_frames * 16;
+		const float* __restrict__ P = a.params + GVTM_ROW_UTT(u, (group * U + u)) * a.max_frames * 16;
 		float* out = sm.prm + at_prm(c & 1, u) + Lp;
 		const uint32_t cs = k.control_steps;
 		const float coef = k.interp_coef;
@@ -1470,7 +1496,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 				CT sample = oy + from_right(oy); // lane 0: mouth + nose
 				sample += cb.t[q];
 				out[q] = static_cast<ST>(sample);
-				if (dbg) a.debug_taps[((group * U + u) * a.max_frames * k.control_steps + static_cast<uint32_t>(c) * C + s0 + q) * 8 + 7] = sample;
+				if (dbg) a.debug_taps[(GVTM_ROW_UTT(u, (group * U + u)) * a.max_frames * k.control_steps + static_cast<uint32_t>(c) * C + s0 + q) * 8 + 7] = sample;
 			}
 			const unsigned slot = (n0 + s0) & (XR - 1); // n0 + s0 is a multiple of four: the block does not wrap
 			ST* xw = x_owner ? xr + slot : x_dump;
@@ -2044,7 +2070,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 					ph += k.phase_inc;
 				}
 				const float y = static_cast<float>(acc);
-				if (ko - e.k_first < a.audio_stride) a.audio[(group * U + u) * a.audio_stride + (ko - e.k_first)] = y;
+				if (ko - e.k_first < a.audio_stride) a.audio[GVTM_ROW_UTT(u, (group * U + u)) * a.audio_stride + (ko - e.k_first)] = y;
 				mx = fmaxf(mx, fabsf(y));
 			}
 			if (mx > 0.0f) atomicMax(&sm.peak[u], __float_as_uint(mx));
@@ -2054,7 +2080,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 	// ---- per-utterance peak (for Util::calculateOutputScale) and sample count
 	__syncthreads();
 	if (tid < U) {
-		const size_t ug = group * U + tid;
+		const size_t ug = GVTM_ROW_UTT(tid, group * U + tid);
 		if (ug < a.batch) {
 			if (a.maxabs) a.maxabs[ug] = __uint_as_float(sm.peak[tid]);
 			const Extent e = sm.ext[tid];
@@ -2067,7 +2093,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 	// ---- a stream's states for the next launch
 	if (a.stream) {
 		if (serial_live && (kTubePerWave && role == 0 ? true : (U >= 4 || row < U))) {
-			unsigned char* sb = a.stream + (group * U + serial_utt) * a.stream_stride;
+			unsigned char* sb = a.stream + GVTM_ROW_UTT(serial_utt, (group * U + serial_utt)) * a.stream_stride;
 			CT* sc = reinterpret_cast<CT*>(sb + SL::scalars());
 			if (role == 1 && L == 0) {
 				sc[kSsPos] = sc_pos;
@@ -2090,9 +2116,9 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 			}
 		}
 		for (int u = 0; u < U; ++u) {
-			if (group * U + u >= a.batch) break;
+			if (GVTM_ROW_UTT(u, group * U + u) >= a.batch) break;
 			const Extent e = sm.ext[u];
-			unsigned char* sb = a.stream + (group * U + u) * a.stream_stride;
+			unsigned char* sb = a.stream + GVTM_ROW_UTT(u, (group * U + u)) * a.stream_stride;
 			ST* ring = reinterpret_cast<ST*>(sb + SL::ring(kTubeLanes, kTubeWords));
 			for (int i = tid; i < XR; i += kThreads) ring[i] = sm.x[u * XRS + i];
 			// the decimator's pre-roll for the next step: the 48 oversampled source values in front of it, which end
@@ -2110,5 +2136,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT>() + NH) * 64) void vtm_syn
 		}
 	}
 }
+
+#undef GVTM_ROW_UTT
 
 } // namespace v2

@@ -96,16 +96,10 @@ struct V2Shape {
 	static constexpr int kWaves = 5 * ((U_ + 3) / 4) + NH;
 };
 
-// internal-rate ring of a workgroup row: a power of two holding two chunks, the resampler's history and the
-// flush zeros; the reference's own BUFFER_SIZE when down-sampling (the flush overrun reads the ring's leftovers
-// modulo that length, vtm_kernel_v2.inc's epilogue)
+// internal-rate ring of a workgroup row (vtm_design.hpp: synth_ring_for)
 static int ring_length(const DeviceConstants& k, int chunk)
 {
-	if (!k.upsampling) return kSrcRing;
-	int xr = 128;
-	// (+ 64: the resampler emits on a 64-aligned grid of outputs, so up to 63 outputs = at most 64 inputs wait a chunk longer)
-	while (xr < 2 * chunk + 4 * k.pad + 64) xr *= 2;
-	return xr;
+	return synth_ring_for(k.upsampling, k.pad, chunk);
 }
 
 // helper wavefronts of the 48-section tube's workgroups: U tube wavefronts + 4 other serial ones + helpers = 12
@@ -122,13 +116,15 @@ constexpr int wide_helpers()
 	return U == 1 ? GVTM_TUNE_NH_SINGLE : (U == 2 ? GVTM_TUNE_WIDE_NH2 : GVTM_TUNE_WIDE_NH4);
 }
 
-template <typename CT, typename ST, int D, int U, int LAYOUT = 0>
+// VOICES: a launch of several voices (the kernel's kVoicesFlag); `batch` is then the number of workgroups, and args.xr the
+// longest ring of the launch's voices (what the LDS is sized for)
+template <typename CT, typename ST, int D, int U, int LAYOUT = 0, bool VOICES = false>
 static hipError_t launch_v2(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
 	using S = V2Shape<CT, ST, U, D>;
 	constexpr int NH = LAYOUT == 1 ? wide_helpers<U>() : S::NH;
 	constexpr int kWaves = v2::serial_waves<U, LAYOUT>() + NH;
-	auto fn = v2::vtm_synth_kernel<CT, ST, D, S::U, S::C, NH, LAYOUT>;
+	auto fn = v2::vtm_synth_kernel<CT, ST, D, S::U, S::C, NH, LAYOUT | (VOICES ? v2::kVoicesFlag : 0)>;
 	// (a stream keeps ONE ring length for all shapes, the one-row shape's: longer than this shape needs, never shorter)
 	if (args.xr < ring_length(args.k, S::C) || (args.xr & (args.xr - 1)) != 0 || 2 * S::C + 4 * args.k.pad + 64 > args.xr) return hipErrorInvalidValue;
 	if (!args.k.upsampling && args.xr != kSrcRing) return hipErrorInvalidValue;
@@ -136,7 +132,7 @@ static hipError_t launch_v2(const SynthArgs& args, size_t batch, hipStream_t str
 	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
 			static_cast<int>(lds));
 	if (e != hipSuccess) return e;
-	const unsigned groups = static_cast<unsigned>((batch + S::U - 1) / S::U);
+	const unsigned groups = static_cast<unsigned>(VOICES ? batch : (batch + S::U - 1) / S::U);
 	hipLaunchKernelGGL(fn, dim3(groups), dim3(kWaves * 64), lds, stream, args);
 	return hipGetLastError();
 }
@@ -250,6 +246,99 @@ hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int 
 	if (precision == GVTM_PRECISION_F32) return launch_v2_rows<float, float>(args, batch, rows, stream);
 	if (precision == GVTM_PRECISION_MIXED) return launch_v2_rows<double, float>(args, batch, rows, stream);
 	return launch_v2_rows<double, double>(args, batch, rows, stream);
+}
+
+// ---- several voices in one launch: the product's shapes only (synth_rows picks 1, 2 or 4 rows; eight are a diagnostics
+// build's forced shape)
+template <typename CT, typename ST, int U>
+static hipError_t launch_voices_d(const SynthArgs& args, size_t groups, hipStream_t stream)
+{
+	if (args.k.layout == 1) {
+		if (args.k.section_delay != 1) return hipErrorInvalidValue;
+		return launch_v2<CT, ST, 1, U, 1, true>(args, groups, stream);
+	}
+	switch (args.k.section_delay) {
+	case 1: return launch_v2<CT, ST, 1, U, 0, true>(args, groups, stream);
+	case 2: return launch_v2<CT, ST, 2, U, 0, true>(args, groups, stream);
+	case 3: return launch_v2<CT, ST, 3, U, 0, true>(args, groups, stream);
+	case 4: return launch_v2<CT, ST, 4, U, 0, true>(args, groups, stream);
+	}
+	return hipErrorInvalidValue;
+}
+
+template <typename CT, typename ST>
+static hipError_t launch_voices_rows(const SynthArgs& args, size_t groups, int rows, hipStream_t stream)
+{
+	if (rows == 4) return launch_voices_d<CT, ST, 4>(args, groups, stream);
+	if (rows == 2) return launch_voices_d<CT, ST, 2>(args, groups, stream);
+	if (rows == 1) return launch_voices_d<CT, ST, 1>(args, groups, stream);
+	return hipErrorInvalidValue;
+}
+
+hipError_t launch_synth_voices(const SynthArgs& args, size_t groups, int precision, int rows, hipStream_t stream)
+{
+	if (!args.row_map || !args.group_voice) return hipErrorInvalidValue;
+	if (precision == GVTM_PRECISION_F32) return launch_voices_rows<float, float>(args, groups, rows, stream);
+	if (precision == GVTM_PRECISION_MIXED) return launch_voices_rows<double, float>(args, groups, rows, stream);
+	return launch_voices_rows<double, double>(args, groups, rows, stream);
+}
+
+// The row map of a launch of several voices, on the device (the launch stays enqueue-only): a stable counting sort of the
+// utterances by voice, each voice's list padded to a multiple of `rows`.  One workgroup; thread t takes a contiguous
+// stretch of the ids and counts it per voice into column t of a.counts, a scan per voice over the columns (in thread
+// order, so that the sort is stable) turns the counts into first slots, and a second walk over the stretch scatters.
+// An id outside [0, n_voices) is left out of the map: its utterance gets out_counts = -1, maxabs = 0.
+constexpr int kGroupThreads = kGroupVoicesThreads;
+__global__ __launch_bounds__(kGroupThreads) void vtm_group_voices_kernel(const GroupVoicesArgs a)
+{
+	constexpr int T = kGroupThreads;
+	__shared__ int scan[T];
+	const int t = threadIdx.x;
+	const size_t per = (a.batch + T - 1) / T;
+	const size_t lo = static_cast<size_t>(t) * per < a.batch ? static_cast<size_t>(t) * per : a.batch;
+	const size_t hi = lo + per < a.batch ? lo + per : a.batch;
+	int* const cnt = a.counts + t; // cnt[v * T]: utterances of voice v in my stretch, then my first slot for voice v
+	for (int v = 0; v < a.n_voices; ++v) cnt[static_cast<size_t>(v) * T] = 0;
+	for (size_t i = lo; i < hi; ++i) {
+		const int v = a.voice_ids[i];
+		if (v >= 0 && v < a.n_voices) {
+			++cnt[static_cast<size_t>(v) * T];
+		} else {
+			if (a.out_counts) a.out_counts[i] = -1;
+			if (a.maxabs) a.maxabs[i] = 0.0f;
+		}
+	}
+	for (size_t i = t; i < a.groups * static_cast<size_t>(a.rows); i += T) a.row_map[i] = -1;
+	for (size_t g = t; g < a.groups; g += T) a.group_voice[g] = -1;
+	__syncthreads();
+	size_t first_group = 0;
+	for (int v = 0; v < a.n_voices; ++v) {
+		const int mine = cnt[static_cast<size_t>(v) * T];
+		scan[t] = mine;
+		__syncthreads();
+		for (int off = 1; off < T; off <<= 1) {
+			const int x = t >= off ? scan[t - off] : 0;
+			__syncthreads();
+			scan[t] += x;
+			__syncthreads();
+		}
+		const size_t total = static_cast<size_t>(scan[T - 1]);
+		cnt[static_cast<size_t>(v) * T] = static_cast<int>(first_group * a.rows) + scan[t] - mine;
+		const size_t n_groups = (total + a.rows - 1) / a.rows;
+		for (size_t g = t; g < n_groups; g += T) a.group_voice[first_group + g] = v;
+		first_group += n_groups;
+		__syncthreads();
+	}
+	for (size_t i = lo; i < hi; ++i) {
+		const int v = a.voice_ids[i];
+		if (v >= 0 && v < a.n_voices) a.row_map[cnt[static_cast<size_t>(v) * T]++] = static_cast<int>(i);
+	}
+}
+
+hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream)
+{
+	hipLaunchKernelGGL(vtm_group_voices_kernel, dim3(1), dim3(kGroupThreads), 0, stream, args);
+	return hipGetLastError();
 }
 
 // reference model 5.  One utterance per workgroup: chunk of 60 steps (one 64-lane pass per per-step stage), three helper

@@ -34,6 +34,10 @@
  *   gvtm_synthesize_events_device
  *                               EventList::generateOutput (vtm_control_model/EventList.cpp:930-1091) followed by
  *                               Controller::synthesize in one call: event lists in, samples out
+ *   gvtm_plan_create_voices / gvtm_synthesize_voices_*
+ *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
+ *                               (data/voice/english/0_male/vtm.txt + variant/{male,female,large_child,small_child,baby}.txt,
+ *                               merged by Controller.cpp:48-49), all of them in one launch
  *   gvtm_normalize_batch_device Controller::writeOutputToBuffer / writeOutputToFile scaling,
  *                               Util::calculateOutputScale (Controller.cpp:315-340,
  *                               vtm/VTMUtil.cpp:48-67, WAVEFileWriter.cpp:122-125)
@@ -254,6 +258,48 @@ int gvtm_synthesize_batch_host(gvtm_plan* plan, const float* params, const int32
 int gvtm_synthesize_batch_host_pcm16(gvtm_plan* plan, const float* params, const int32_t* frame_counts,
 		size_t batch, size_t max_frames, int16_t* pcm, size_t pcm_stride,
 		int64_t* out_counts, float* maxabs, float* scales);
+
+/* ---------------------------------------------------------------------------------------------
+ * Several voices in one plan: a batch whose utterances are spoken by different voices (GamaTTS voice variants: male,
+ * female, children, ...) synthesized in one launch.  Each voice is a gvtm_config of its own; voice v's utterances come out
+ * bit for bit as a single-voice plan made from configs[v] synthesizes them, in every precision.
+ */
+
+/* configs[n_voices]: one model, several voices.  output_rate, section_delay, precision and tube_layout must be equal
+ * across configs (else GVTM_ERR_INVALID_ARGUMENT); every other key may differ per voice.  The design runs per voice; the
+ * device holds one constants block and one glottal wavetable per voice, and one glottal FIR, one set of converter tables
+ * and (GVTM_PRECISION_F32) one noise-sample table for all of them.  n_voices == 1 makes exactly the plan gvtm_plan_create
+ * makes.  GVTM_DEVICE_NONE works as for gvtm_plan_create.  A plan of two or more voices refuses the single-voice
+ * entry points (gvtm_synthesize_batch_*, gvtm_stream_create, gvtm_synthesize_events_device) with
+ * GVTM_ERR_INVALID_ARGUMENT; gvtm_plan_info, gvtm_output_count and gvtm_output_capacity describe voice 0.  Reference
+ * model 5 plans (gvtm_plan_create_model5) have one voice. */
+int    gvtm_plan_create_voices(const gvtm_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out);
+/* Number of voices of a plan (1 for gvtm_plan_create / _model5 plans); a negative status for a null plan. */
+int    gvtm_plan_voice_count(const gvtm_plan* plan);
+/* gvtm_plan_info of one voice (internal rate, control steps, converter increments and up-sampling differ by voice). */
+int    gvtm_plan_voice_info(const gvtm_plan* plan, int voice, gvtm_info* info_out);
+/* gvtm_output_count for an utterance of that voice; (size_t)-1 for a null plan or a voice out of range. */
+size_t gvtm_voice_output_count(const gvtm_plan* plan, int voice, size_t n_frames);
+/* max over voices of gvtm_output_capacity: the audio_stride for any mix of voices */
+size_t gvtm_voices_output_capacity(const gvtm_plan* plan, size_t max_frames);
+
+/* d_voice_ids [batch] int32: voice of each utterance, in any order; the rest as gvtm_synthesize_batch_device (NOTE the
+ * order of max_frames and batch).  audio_stride >= gvtm_voice_output_count(plan, v, max_frames) for every voice v is
+ * required, gvtm_voices_output_capacity(plan, max_frames) holds any mix.  An utterance whose voice id is outside
+ * [0, n_voices) fails on its own, as a bad frame count does in the host entries: its out_counts = -1, maxabs = 0, its row
+ * is left untouched; the call still succeeds.  Enqueue-only: a small grouping kernel sorts the utterances by voice on the
+ * device (stable, each voice padded to whole workgroups), then one synthesis launch runs every voice.  The plan keeps the
+ * grouping's scratch: calls on one plan must be ordered (one stream), as for gvtm_synthesize_events_device. */
+int gvtm_synthesize_voices_device(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts,
+		const int32_t* d_voice_ids, size_t max_frames, size_t batch, float* d_audio, size_t audio_stride,
+		int64_t* d_out_counts, float* d_maxabs, void* hip_stream);
+/* Same with host buffers, through the three-stream pipeline of gvtm_synthesize_batch_host; a bad voice id or frame count
+ * fails that utterance only (out_counts = -1, maxabs = 0, its row zeroed). */
+int gvtm_synthesize_voices_host(gvtm_plan* plan, const float* params, const int32_t* frame_counts, const int32_t* voice_ids,
+		size_t max_frames, size_t batch, float* audio, size_t audio_stride, int64_t* out_counts, float* maxabs);
+/* As gvtm_synthesize_batch_host_pcm16 (scales = 0 for a failed utterance). */
+int gvtm_synthesize_voices_host_pcm16(gvtm_plan* plan, const float* params, const int32_t* frame_counts, const int32_t* voice_ids,
+		size_t max_frames, size_t batch, int16_t* pcm, size_t pcm_stride, int64_t* out_counts, float* maxabs, float* scales);
 
 /* Page-locked host memory for the buffers of the host entries (hipHostMalloc, portable across devices), for callers
  * that do not link the HIP runtime themselves.  gvtm_host_free(NULL) is a no-op. */
