@@ -698,8 +698,24 @@ struct StreamLaunch {
 	int rows;     // 1 unless the utterances are in lockstep
 };
 
+// One synthesis launch: the device buffers of a gvtm_synthesize_*_device call, of a slice of the host entries or of a stream
+struct LaunchRequest {
+	const float* params;
+	const int32_t* frame_counts;
+	size_t batch, max_frames;
+	float* audio;
+	size_t audio_stride;
+	int64_t* out_counts;
+	float* maxabs;
+	void* hip_stream;
+	bool voices = false;                // gvtm_synthesize_voices_*: voice_ids[b] is utterance b's voice
+	const int32_t* voice_ids = nullptr;
+	const StreamLaunch* sl = nullptr;   // or null: a one-shot launch
+};
+
 // The float model's noise samples for launches of up to `steps` internal steps per utterance: the plan's table, grown
 // (synchronously) when it is shorter; beyond the cap args.noise_lp stays null and the kernel generates them.
+// (The double paths generate the samples in the kernel: measured faster there.)
 int use_noise_table(gvtm_plan* plan, size_t steps, gvtm::SynthArgs& args)
 {
 	hipError_t e = hipSuccess;
@@ -711,9 +727,8 @@ int use_noise_table(gvtm_plan* plan, size_t steps, gvtm::SynthArgs& args)
 		// retires at most eight tables on the way to the cap
 		size_t want = ((steps + (size_t(1) << 18) - 1) >> 18) << 18;
 		want = std::min(std::max(want, 2 * plan->noise_len), kNoiseTableMaxSteps);
-		const bool f32 = true; // (the double paths generate the samples in the kernel: measured faster there)
-		std::vector<unsigned char> host(want * (f32 ? sizeof(float) : sizeof(double)));
-		gvtm::design_noise_table(want, f32, host.data());
+		std::vector<unsigned char> host(want * sizeof(float));
+		gvtm::design_noise_table(want, true, host.data());
 		void* fresh = nullptr;
 		if ((e = hipMalloc(&fresh, host.size())) != hipSuccess) return fail_hip(e, "hipMalloc (noise table)");
 		if ((e = hipMemcpy(fresh, host.data(), host.size(), hipMemcpyHostToDevice)) != hipSuccess) {
@@ -731,54 +746,23 @@ int use_noise_table(gvtm_plan* plan, size_t steps, gvtm::SynthArgs& args)
 	return GVTM_OK;
 }
 
-int launch_batch(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts,
-		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
-		int64_t* d_out_counts, float* d_maxabs, void* hip_stream, const StreamLaunch* sl)
+// The kernel arguments that follow from the plan and the request alone (launch_synthesis adds the ring length, the noise
+// table and the row map)
+gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 {
-	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
-	if (plan->n_voices > 1) return refuse_voices(plan, sl ? "gvtm_stream_*" : "gvtm_synthesize_batch_device");
-	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
-	if (batch == 0) return GVTM_OK;
-	if (!d_audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
-	if (max_frames > 0 && !d_params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
-	if (batch > 0x7fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
-	if (static_cast<unsigned long long>(max_frames) * plan->design.k.control_steps + 4096ull >= (1ull << 31)) {
-		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
-	}
-	if (!sl && audio_stride < gvtm_output_count(plan, max_frames)) {
-		return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_output_count(plan, max_frames)");
-	}
-	const bool model5 = plan->design.model5;
-	const gvtm::DeviceConstants& k = plan->design.k;
-	constexpr size_t kLdsPerWorkgroup = 160 * 1024;
-	int rows = model5 ? plan->rows5_for(batch) : gvtm::synth_rows(plan->precision, batch, plan->rows, k.section_delay);
-	if (sl && sl->rows == 1) rows = 1;
-	const int xr_fixed = sl ? sl->xr : 0;
-	// a shape whose rings do not fit (down-sampling plans carry the reference's 1024-sample ring per row) gives way to
-	// the next smaller one
-	while (!model5 && rows > 1 && gvtm::synth_lds_bytes(k, plan->precision, rows, xr_fixed) > kLdsPerWorkgroup) rows /= 2;
-	if ((model5 ? gvtm::synth5_lds_bytes(rows) : gvtm::synth_lds_bytes(k, plan->precision, rows, xr_fixed)) > kLdsPerWorkgroup) {
-		return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
-	}
-
-	DeviceScope scope(plan->device);
-	hipError_t e = scope.status();
-	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-
+	const gvtm::Design& dg = plan->design;
 	gvtm::SynthArgs args;
-	args.k = k;
+	args.k = dg.k;
 	args.kconst = plan->d_consts;
-	args.params = d_params;
-	args.frame_counts = d_frame_counts;
-	args.audio = d_audio;
-	args.out_counts = d_out_counts;
-	args.maxabs = d_maxabs;
+	args.params = r.params;
+	args.frame_counts = r.frame_counts;
+	args.audio = r.audio;
+	args.out_counts = r.out_counts;
+	args.maxabs = r.maxabs;
 	args.wavetable = plan->d_wavetable;
 	args.fir = plan->d_fir;
 	std::memset(&args.fir_k, 0, sizeof(args.fir_k));
-	if (!model5) {
-		const gvtm::Design& dg = plan->design;
+	if (!dg.model5) {
 		if (dg.f32) {
 			for (size_t i = 0; i < dg.fir_f.size() && i < 64; ++i) args.fir_k.f[i] = dg.fir_f[i];
 		} else {
@@ -787,24 +771,26 @@ int launch_batch(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_
 	}
 	args.src_h = plan->d_src_h;
 	args.src_dh = plan->d_src_dh;
-	if (!model5 && !sl && GVTM_NOISE_TABLE && plan->precision == GVTM_PRECISION_F32) {
-		// one-shot launches read the noise samples from the plan's table (streams generate them: their length has no bound)
-		const int rc = use_noise_table(plan, max_frames * static_cast<size_t>(k.control_steps), args);
-		if (rc != GVTM_OK) return rc;
+	args.max_frames = r.max_frames;
+	args.audio_stride = r.audio_stride;
+	args.batch = r.batch;
+	if (r.sl) {
+		args.stream = r.sl->d_state;
+		args.stream_stride = r.sl->stride;
+		args.stream_mode = r.sl->mode;
 	}
-	args.max_frames = max_frames;
-	args.audio_stride = audio_stride;
-	args.batch = batch;
-	args.xr = model5 ? 0 : (sl ? sl->xr : gvtm::synth_ring_length(k, plan->precision, rows));
-	if (sl) {
-		args.stream = sl->d_state;
-		args.stream_stride = sl->stride;
-		args.stream_mode = sl->mode;
-	}
-	args.debug_taps = plan->debug_taps;
-	args.phase_cycles = plan->phase_cycles;
+	// (not for several voices: the hooks' buffers are sized for voice 0's steps and ceil(batch / rows) workgroups)
+	args.debug_taps = r.voices ? nullptr : plan->debug_taps;
+	args.phase_cycles = r.voices ? nullptr : plan->phase_cycles;
 	args.k5const = plan->d_consts5;
+	return args;
+}
 
+// launch() between the two events of a pair when the plan times its kernels (gvtm_plan_set_timing)
+template <typename Launch>
+int timed_launch(gvtm_plan* plan, hipStream_t stream, const char* what, Launch launch)
+{
+	hipError_t e;
 	EventPair ev;
 	if (plan->timing) {
 		if (!plan->pool.empty()) {
@@ -816,118 +802,90 @@ int launch_batch(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_
 		}
 		if ((e = hipEventRecord(ev.start, stream)) != hipSuccess) return fail_hip(e, "hipEventRecord");
 	}
-	e = model5 ? gvtm::launch_synth5(args, batch, rows, stream)
-	           : gvtm::launch_synth(args, batch, plan->precision, rows, stream);
+	e = launch();
 	if (plan->timing) {
 		(void) hipEventRecord(ev.stop, stream);
 		plan->pending.push_back(ev);
 	}
-	if (e != hipSuccess) return fail_hip(e, "vtm_synth_kernel launch");
+	if (e != hipSuccess) return fail_hip(e, what);
 	return GVTM_OK;
 }
 
-// gvtm_synthesize_voices_device: the grouping kernel builds the row map from the voice ids, then the voice variant of the
-// synthesis kernel runs ceil(batch / rows) + n_voices workgroups (the bound for any mix of ids; those past the last
-// voice's groups exit at once), each on one voice's constants, wavetable and ring.  Enqueue-only: no read-back.
-int launch_voices(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts, const int32_t* d_voice_ids,
-		size_t max_frames, size_t batch, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, void* hip_stream)
+// Every synthesis launch, enqueue-only.  With voices, the grouping kernel first builds the row map from the voice ids, then
+// the voice variant of the synthesis kernel runs ceil(batch / rows) + n_voices workgroups (the bound for any mix of ids;
+// those past the last voice's groups exit at once), each on one voice's constants, wavetable and ring.
+int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
-	if (plan->design.model5) return fail(GVTM_ERR_INVALID_ARGUMENT, "model 5 plans have one voice: gvtm_synthesize_batch_*");
+	// (the single-voice entries would not know which voice to synthesize; the voices entries take a one-voice plan too)
+	if (!r.voices && plan->n_voices > 1) return refuse_voices(plan, r.sl ? "gvtm_stream_*" : "gvtm_synthesize_batch_device");
+	if (r.voices && plan->design.model5) return fail(GVTM_ERR_INVALID_ARGUMENT, "model 5 plans have one voice: gvtm_synthesize_batch_*");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
-	if (batch == 0) return GVTM_OK;
-	if (!d_audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
-	if (!d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
-	if (max_frames > 0 && !d_params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
-	if (batch > 0x3fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
+	if (r.batch == 0) return GVTM_OK;
+	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
+	if (r.voices && !r.voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
+	if (r.max_frames > 0 && !r.params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
+	// (several voices: the row map's int32 slots also count up to n_voices partly empty workgroups)
+	if (r.batch > (r.voices ? 0x3fffffffu : 0x7fffffffu)) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
 	unsigned max_steps = 0;
 	for (int v = 0; v < plan->n_voices; ++v) max_steps = std::max(max_steps, plan->voice(v).k.control_steps);
-	if (static_cast<unsigned long long>(max_frames) * max_steps + 4096ull >= (1ull << 31)) {
+	if (static_cast<unsigned long long>(r.max_frames) * max_steps + 4096ull >= (1ull << 31)) {
 		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
 	}
-	for (int v = 0; v < plan->n_voices; ++v) {
-		if (audio_stride < design_output_count(plan->voice(v), max_frames)) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_voice_output_count(plan, voice, max_frames) of voice " + std::to_string(v));
+	// (a stream checks its stride against what each call produces: stream_launch)
+	for (int v = 0; !r.sl && v < plan->n_voices; ++v) {
+		if (r.audio_stride < design_output_count(plan->voice(v), r.max_frames)) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, r.voices ? "audio_stride smaller than gvtm_voice_output_count(plan, voice, max_frames) of voice " + std::to_string(v)
+			                                                : "audio_stride smaller than gvtm_output_count(plan, max_frames)");
 		}
 	}
+	const bool model5 = plan->design.model5;
 	const gvtm::DeviceConstants& k = plan->design.k;
-	constexpr size_t kLdsPerWorkgroup = 160 * 1024;
-	// the product's shapes (1, 2 or 4 rows); the LDS holds the longest ring of the voices (a down-sampling voice keeps the
-	// reference's 1024-sample ring), and a shape it does not fit gives way to the next smaller one, as in launch_batch
-	int rows = std::min(gvtm::synth_rows(plan->precision, batch, plan->rows, k.section_delay), 4);
-	auto longest_ring = [&](int r) {
+	int rows = model5 ? plan->rows5_for(r.batch) : gvtm::synth_rows(plan->precision, r.batch, plan->rows, k.section_delay);
+	// (the voice variant has the product's shapes only: eight rows are a diagnostics build's forced shape)
+	if (r.voices) rows = std::min(rows, 4);
+	if (r.sl && r.sl->rows == 1) rows = 1;
+	// the LDS holds the stream's ring (one for all shapes) or the longest ring of the voices; a shape it does not fit
+	// (a down-sampling voice carries the reference's 1024-sample ring per row) gives way to the next smaller one
+	auto ring = [&](int rw) {
+		if (r.sl) return r.sl->xr;
 		int xr = 0;
-		for (int v = 0; v < plan->n_voices; ++v) xr = std::max(xr, gvtm::synth_ring_length(plan->voice(v).k, plan->precision, r));
+		for (int v = 0; v < plan->n_voices; ++v) xr = std::max(xr, gvtm::synth_ring_length(plan->voice(v).k, plan->precision, rw));
 		return xr;
 	};
-	while (rows > 1 && gvtm::synth_lds_bytes(k, plan->precision, rows, longest_ring(rows)) > kLdsPerWorkgroup) rows /= 2;
-	const int xr = longest_ring(rows);
-	if (gvtm::synth_lds_bytes(k, plan->precision, rows, xr) > kLdsPerWorkgroup) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
+	auto lds = [&](int rw) { return model5 ? gvtm::synth5_lds_bytes(rw) : gvtm::synth_lds_bytes(k, plan->precision, rw, ring(rw)); };
+	constexpr size_t kLdsPerWorkgroup = 160 * 1024;
+	while (!model5 && rows > 1 && lds(rows) > kLdsPerWorkgroup) rows /= 2;
+	if (lds(rows) > kLdsPerWorkgroup) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
 
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+	hipStream_t stream = static_cast<hipStream_t>(r.hip_stream);
 
-	const size_t groups = (batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices);
-	const size_t map_ints = groups * rows, count_ints = static_cast<size_t>(plan->n_voices) * gvtm::kGroupVoicesThreads;
-	// (the scratch is the plan's: launches on one plan are ordered on one stream, as for gvtm_synthesize_events_device)
-	if ((e = plan->s_groups.ensure(sizeof(int32_t) * (map_ints + groups + count_ints))) != hipSuccess) return fail_hip(e, "hipMalloc row map");
-	int32_t* const d_map = static_cast<int32_t*>(plan->s_groups.ptr);
-	gvtm::GroupVoicesArgs ga{d_voice_ids, batch, plan->n_voices, rows, groups, d_map, d_map + map_ints, d_map + map_ints + groups, d_out_counts, d_maxabs};
-	if ((e = gvtm::launch_group_voices(ga, stream)) != hipSuccess) return fail_hip(e, "vtm_group_voices_kernel launch");
-
-	gvtm::SynthArgs args;
-	args.k = k;
-	args.kconst = plan->d_consts;
-	args.params = d_params;
-	args.frame_counts = d_frame_counts;
-	args.audio = d_audio;
-	args.out_counts = d_out_counts;
-	args.maxabs = d_maxabs;
-	args.wavetable = plan->d_wavetable;
-	args.fir = plan->d_fir;
-	std::memset(&args.fir_k, 0, sizeof(args.fir_k));
-	const gvtm::Design& dg = plan->design;
-	if (dg.f32) {
-		for (size_t i = 0; i < dg.fir_f.size() && i < 64; ++i) args.fir_k.f[i] = dg.fir_f[i];
-	} else {
-		for (size_t i = 0; i < dg.fir.size() && i < 49; ++i) args.fir_k.d[i] = dg.fir[i];
+	gvtm::SynthArgs args = synth_args(plan, r);
+	args.xr = model5 ? 0 : ring(rows);
+	size_t work = r.batch; // what launch_synth takes: utterances, or with voices workgroups
+	if (r.voices) {
+		work = (r.batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices);
+		const size_t map_ints = work * rows, count_ints = static_cast<size_t>(plan->n_voices) * gvtm::kGroupVoicesThreads;
+		// (the scratch is the plan's: launches on one plan are ordered on one stream, as for gvtm_synthesize_events_device)
+		if ((e = plan->s_groups.ensure(sizeof(int32_t) * (map_ints + work + count_ints))) != hipSuccess) return fail_hip(e, "hipMalloc row map");
+		int32_t* const d_map = static_cast<int32_t*>(plan->s_groups.ptr);
+		gvtm::GroupVoicesArgs ga{r.voice_ids, r.batch, plan->n_voices, rows, work, d_map, d_map + map_ints, d_map + map_ints + work, r.out_counts, r.maxabs};
+		if ((e = gvtm::launch_group_voices(ga, stream)) != hipSuccess) return fail_hip(e, "vtm_group_voices_kernel launch");
+		args.row_map = d_map;
+		args.group_voice = d_map + map_ints;
 	}
-	args.src_h = plan->d_src_h;
-	args.src_dh = plan->d_src_dh;
-	if (GVTM_NOISE_TABLE && plan->precision == GVTM_PRECISION_F32) {
-		// one table for every voice (every utterance starts from the same seed), as long as the voice with the most steps needs
-		const int rc = use_noise_table(plan, max_frames * static_cast<size_t>(max_steps), args);
+	if (!model5 && !r.sl && GVTM_NOISE_TABLE && plan->precision == GVTM_PRECISION_F32) {
+		// one-shot launches read the noise samples from the plan's table, one for every voice (every utterance starts from
+		// the same seed), as long as the voice with the most steps needs (streams generate them: their length has no bound)
+		const int rc = use_noise_table(plan, r.max_frames * static_cast<size_t>(max_steps), args);
 		if (rc != GVTM_OK) return rc;
 	}
-	args.max_frames = max_frames;
-	args.audio_stride = audio_stride;
-	args.batch = batch;
-	args.xr = xr;
-	args.debug_taps = nullptr;
-	args.phase_cycles = nullptr;
-	args.row_map = d_map;
-	args.group_voice = d_map + map_ints;
-
-	EventPair ev;
-	if (plan->timing) {
-		if (!plan->pool.empty()) {
-			ev = plan->pool.back();
-			plan->pool.pop_back();
-		} else {
-			if ((e = hipEventCreate(&ev.start)) != hipSuccess) return fail_hip(e, "hipEventCreate");
-			if ((e = hipEventCreate(&ev.stop)) != hipSuccess) return fail_hip(e, "hipEventCreate");
-		}
-		if ((e = hipEventRecord(ev.start, stream)) != hipSuccess) return fail_hip(e, "hipEventRecord");
-	}
-	e = gvtm::launch_synth_voices(args, groups, plan->precision, rows, stream);
-	if (plan->timing) {
-		(void) hipEventRecord(ev.stop, stream);
-		plan->pending.push_back(ev);
-	}
-	if (e != hipSuccess) return fail_hip(e, "vtm_synth_kernel launch (voices)");
-	return GVTM_OK;
+	return timed_launch(plan, stream, r.voices ? "vtm_synth_kernel launch (voices)" : "vtm_synth_kernel launch", [&] {
+		return model5 ? gvtm::launch_synth5(args, r.batch, rows, stream) : gvtm::launch_synth(args, work, plan->precision, rows, stream);
+	});
 }
 
 } // namespace
@@ -938,13 +896,14 @@ int gvtm_synthesize_batch_device(gvtm_plan* plan, const float* d_params, const i
 		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
 		int64_t* d_out_counts, float* d_maxabs, void* hip_stream)
 {
-	return launch_batch(plan, d_params, d_frame_counts, batch, max_frames, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream, nullptr);
+	return launch_synthesis(plan, LaunchRequest{d_params, d_frame_counts, batch, max_frames, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream});
 }
 
 int gvtm_synthesize_voices_device(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts, const int32_t* d_voice_ids,
 		size_t max_frames, size_t batch, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, void* hip_stream)
 {
-	return launch_voices(plan, d_params, d_frame_counts, d_voice_ids, max_frames, batch, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream);
+	return launch_synthesis(plan, LaunchRequest{d_params, d_frame_counts, batch, max_frames, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream,
+			true, d_voice_ids});
 }
 
 int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* config, const gvtm_event* d_events,
@@ -976,8 +935,8 @@ int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* conf
 	int rc = gvtm_generate_tracks_device(plan->device, config, d_events, d_event_offsets, batch, max_frames, static_cast<float*>(plan->s_params.ptr), counts,
 			d_drift, hip_stream);
 	if (rc != GVTM_OK) return rc;
-	return launch_batch(plan, static_cast<const float*>(plan->s_params.ptr), counts, batch, max_frames, d_audio, audio_stride, d_out_counts, d_maxabs,
-			hip_stream, nullptr);
+	return launch_synthesis(plan, LaunchRequest{static_cast<const float*>(plan->s_params.ptr), counts, batch, max_frames, d_audio, audio_stride,
+			d_out_counts, d_maxabs, hip_stream});
 }
 
 } // extern "C"
@@ -1114,13 +1073,8 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 		if (ragged && j.pcm && (e = hipMemsetAsync(d_pcm + lo * audio_stride, 0, sizeof(int16_t) * n * audio_stride, plan->compute_stream)) != hipSuccess) {
 			rc = fail_hip(e, "hipMemsetAsync"); break;
 		}
-		if (voices) {
-			rc = gvtm_synthesize_voices_device(plan, d_params + lo * row_in, d_frames ? d_frames + lo : nullptr, d_voice_ids + lo, max_frames, n,
-					d_audio + lo * audio_stride, audio_stride, d_counts + lo, d_maxabs + lo, plan->compute_stream);
-		} else {
-			rc = gvtm_synthesize_batch_device(plan, d_params + lo * row_in, d_frames ? d_frames + lo : nullptr, n, max_frames,
-					d_audio + lo * audio_stride, audio_stride, d_counts + lo, d_maxabs + lo, plan->compute_stream);
-		}
+		rc = launch_synthesis(plan, LaunchRequest{d_params + lo * row_in, d_frames ? d_frames + lo : nullptr, n, max_frames, d_audio + lo * audio_stride,
+				audio_stride, d_counts + lo, d_maxabs + lo, plan->compute_stream, voices, voices ? d_voice_ids + lo : nullptr});
 		if (rc != GVTM_OK) break;
 		if (j.pcm) {
 			// (normalize takes at most 65535 utterances per launch: a slice is far below that unless the batch is one slice)
@@ -1335,9 +1289,10 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	if ((e = hipMemcpy(s->d_params.ptr, s->staging.data(), pbytes, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D params");
 	if ((e = hipMemcpy(s->d_frames.ptr, s->counts.data(), sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D frame counts");
 	if ((e = hipMemsetAsync(s->d_audio.ptr, 0, abytes, nullptr)) != hipSuccess) return fail_hip(e, "hipMemsetAsync");
-	StreamLaunch sl{static_cast<unsigned char*>(s->d_state.ptr), s->state_stride, final ? gvtm::kStreamFinish : gvtm::kStreamPush, s->xr, lockstep ? 0 : 1};
-	const int rc = launch_batch(plan, static_cast<const float*>(s->d_params.ptr), static_cast<const int32_t*>(s->d_frames.ptr), batch, rows_max,
-			static_cast<float*>(s->d_audio.ptr), audio_stride, static_cast<int64_t*>(s->d_counts.ptr), static_cast<float*>(s->d_maxabs.ptr), nullptr, &sl);
+	const StreamLaunch sl{static_cast<unsigned char*>(s->d_state.ptr), s->state_stride, final ? gvtm::kStreamFinish : gvtm::kStreamPush, s->xr, lockstep ? 0 : 1};
+	const int rc = launch_synthesis(plan, LaunchRequest{static_cast<const float*>(s->d_params.ptr), static_cast<const int32_t*>(s->d_frames.ptr), batch,
+			rows_max, static_cast<float*>(s->d_audio.ptr), audio_stride, static_cast<int64_t*>(s->d_counts.ptr), static_cast<float*>(s->d_maxabs.ptr), nullptr,
+			false, nullptr, &sl});
 	if (rc != GVTM_OK) return rc;
 	if (launched) *launched = true;
 	if ((e = hipDeviceSynchronize()) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");

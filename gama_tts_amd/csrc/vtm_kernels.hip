@@ -116,9 +116,9 @@ constexpr int wide_helpers()
 	return U == 1 ? GVTM_TUNE_NH_SINGLE : (U == 2 ? GVTM_TUNE_WIDE_NH2 : GVTM_TUNE_WIDE_NH4);
 }
 
-// VOICES: a launch of several voices (the kernel's kVoicesFlag); `batch` is then the number of workgroups, and args.xr the
-// longest ring of the launch's voices (what the LDS is sized for)
-template <typename CT, typename ST, int D, int U, int LAYOUT = 0, bool VOICES = false>
+// VOICES: a launch of several voices (the kernel's kVoicesFlag; args.row_map is set); `batch` is then the number of
+// workgroups, and args.xr the longest ring of the launch's voices (what the LDS is sized for)
+template <typename CT, typename ST, int D, int U, int LAYOUT, bool VOICES>
 static hipError_t launch_v2(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
 	using S = V2Shape<CT, ST, U, D>;
@@ -211,76 +211,51 @@ size_t synth_lds_bytes(const DeviceConstants& k, int precision, int rows, int xr
 	return n.lds_fixed + ((n.ring_elem * static_cast<size_t>(xr > 0 ? xr : ring_length(k, n.chunk)) + 15) & ~size_t(15));
 }
 
-template <typename CT, typename ST, int U>
+template <typename CT, typename ST, int U, bool VOICES>
 static hipError_t launch_v2_d(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
 	if (args.k.layout == 1) {
 		// VocalTractModel4: 48 section lanes = one utterance per tube wavefront (up to four of them per
 		// workgroup), SectionDelay 1 only
 		if (args.k.section_delay != 1) return hipErrorInvalidValue;
-		if constexpr (U >= 4) return launch_v2<CT, ST, 1, 4, 1>(args, batch, stream);
-		else return launch_v2<CT, ST, 1, U, 1>(args, batch, stream);
+		if constexpr (U >= 4) return launch_v2<CT, ST, 1, 4, 1, VOICES>(args, batch, stream);
+		else return launch_v2<CT, ST, 1, U, 1, VOICES>(args, batch, stream);
 	}
 	switch (args.k.section_delay) {
-	case 1: return launch_v2<CT, ST, 1, U>(args, batch, stream);
-	case 2: return launch_v2<CT, ST, 2, U>(args, batch, stream);
-	case 3: return launch_v2<CT, ST, 3, U>(args, batch, stream);
-	case 4: return launch_v2<CT, ST, 4, U>(args, batch, stream);
+	case 1: return launch_v2<CT, ST, 1, U, 0, VOICES>(args, batch, stream);
+	case 2: return launch_v2<CT, ST, 2, U, 0, VOICES>(args, batch, stream);
+	case 3: return launch_v2<CT, ST, 3, U, 0, VOICES>(args, batch, stream);
+	case 4: return launch_v2<CT, ST, 4, U, 0, VOICES>(args, batch, stream);
 	}
 	return hipErrorInvalidValue;
 }
 
-template <typename CT, typename ST>
+template <typename CT, typename ST, bool VOICES>
 static hipError_t launch_v2_rows(const SynthArgs& args, size_t batch, int rows, hipStream_t stream)
 {
-	if constexpr (sizeof(CT) == 4) {
-		if (rows == 8) return launch_v2_d<CT, ST, 8>(args, batch, stream);
+	if constexpr (sizeof(CT) == 4 && !VOICES) {
+		if (rows == 8) return launch_v2_d<CT, ST, 8, VOICES>(args, batch, stream);
 	}
-	if (rows == 4) return launch_v2_d<CT, ST, 4>(args, batch, stream);
-	if (rows == 2) return launch_v2_d<CT, ST, 2>(args, batch, stream);
-	return launch_v2_d<CT, ST, 1>(args, batch, stream);
+	if (rows == 4) return launch_v2_d<CT, ST, 4, VOICES>(args, batch, stream);
+	if (rows == 2) return launch_v2_d<CT, ST, 2, VOICES>(args, batch, stream);
+	// several voices: the product's shapes only (synth_rows picks 1, 2 or 4 rows; eight are a diagnostics build's forced shape)
+	if (VOICES && rows != 1) return hipErrorInvalidValue;
+	return launch_v2_d<CT, ST, 1, VOICES>(args, batch, stream);
+}
+
+template <bool VOICES>
+static hipError_t launch_v2_precision(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream)
+{
+	if (precision == GVTM_PRECISION_F32) return launch_v2_rows<float, float, VOICES>(args, batch, rows, stream);
+	if (precision == GVTM_PRECISION_MIXED) return launch_v2_rows<double, float, VOICES>(args, batch, rows, stream);
+	return launch_v2_rows<double, double, VOICES>(args, batch, rows, stream);
 }
 
 hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream)
 {
-	if (precision == GVTM_PRECISION_F32) return launch_v2_rows<float, float>(args, batch, rows, stream);
-	if (precision == GVTM_PRECISION_MIXED) return launch_v2_rows<double, float>(args, batch, rows, stream);
-	return launch_v2_rows<double, double>(args, batch, rows, stream);
-}
-
-// ---- several voices in one launch: the product's shapes only (synth_rows picks 1, 2 or 4 rows; eight are a diagnostics
-// build's forced shape)
-template <typename CT, typename ST, int U>
-static hipError_t launch_voices_d(const SynthArgs& args, size_t groups, hipStream_t stream)
-{
-	if (args.k.layout == 1) {
-		if (args.k.section_delay != 1) return hipErrorInvalidValue;
-		return launch_v2<CT, ST, 1, U, 1, true>(args, groups, stream);
-	}
-	switch (args.k.section_delay) {
-	case 1: return launch_v2<CT, ST, 1, U, 0, true>(args, groups, stream);
-	case 2: return launch_v2<CT, ST, 2, U, 0, true>(args, groups, stream);
-	case 3: return launch_v2<CT, ST, 3, U, 0, true>(args, groups, stream);
-	case 4: return launch_v2<CT, ST, 4, U, 0, true>(args, groups, stream);
-	}
-	return hipErrorInvalidValue;
-}
-
-template <typename CT, typename ST>
-static hipError_t launch_voices_rows(const SynthArgs& args, size_t groups, int rows, hipStream_t stream)
-{
-	if (rows == 4) return launch_voices_d<CT, ST, 4>(args, groups, stream);
-	if (rows == 2) return launch_voices_d<CT, ST, 2>(args, groups, stream);
-	if (rows == 1) return launch_voices_d<CT, ST, 1>(args, groups, stream);
-	return hipErrorInvalidValue;
-}
-
-hipError_t launch_synth_voices(const SynthArgs& args, size_t groups, int precision, int rows, hipStream_t stream)
-{
-	if (!args.row_map || !args.group_voice) return hipErrorInvalidValue;
-	if (precision == GVTM_PRECISION_F32) return launch_voices_rows<float, float>(args, groups, rows, stream);
-	if (precision == GVTM_PRECISION_MIXED) return launch_voices_rows<double, float>(args, groups, rows, stream);
-	return launch_voices_rows<double, double>(args, groups, rows, stream);
+	if (!args.row_map) return launch_v2_precision<false>(args, batch, precision, rows, stream);
+	if (!args.group_voice) return hipErrorInvalidValue;
+	return launch_v2_precision<true>(args, batch, precision, rows, stream);
 }
 
 // The row map of a launch of several voices, on the device (the launch stays enqueue-only): a stable counting sort of the

@@ -91,7 +91,7 @@ struct SynthArgs {
 	double* debug_taps;          // null, or [batch][max_frames*control_steps][8] per-step taps (tests only)
 	unsigned long long* phase_cycles; // null, or [workgroups][16] shader cycles per role wavefront and helper stage (diagnostics only)
 	const Model5Constants* k5const = nullptr; // model 5 only: its constants in device memory
-	// launches of several voices (launch_synth_voices): kconst and wavetable then hold one block per voice
+	// launches of several voices (set: launch_synth runs the voice variant): kconst and wavetable then hold one block per voice
 	const int32_t* row_map = nullptr;     // [groups][rows] utterance of each workgroup row, -1 = none
 	const int32_t* group_voice = nullptr; // [groups] voice of each workgroup, -1 = none (the workgroup exits)
 };
@@ -128,14 +128,14 @@ int synth_rows(int precision, size_t batch, int requested, int section_delay = 1
 // resampler's history and the flush zeros
 int synth_ring_length(const DeviceConstants& k, int precision, int rows);
 size_t synth_lds_bytes(const DeviceConstants& k, int precision, int rows, int xr = 0 /* 0: the shape's own ring length */);
+// batch: utterances, or with args.row_map set (several voices) the workgroups of launch_group_voices' map, of one voice
+// each (args.xr: the longest ring of the voices)
 hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream);
 // bytes of one utterance's stream state for a plan (ring length of the one-row shape: streams whose utterances are not in
 // lockstep run one utterance per workgroup, and every shape of a stream uses that ring length)
 size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr);
 // several voices: builds args.row_map / args.group_voice from the voice ids (one small workgroup, stable counting sort)
 hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream);
-// then synthesizes `groups` workgroups of `rows` utterances, each of one voice (args.xr: the longest ring of the voices)
-hipError_t launch_synth_voices(const SynthArgs& args, size_t groups, int precision, int rows, hipStream_t stream);
 // reference model 5 (VocalTractModel5<double,1>), fp64: rows = utterances per workgroup, 1 or 2
 size_t synth5_lds_bytes(int rows = 1);
 hipError_t launch_synth5(const SynthArgs& args, size_t batch, int rows, hipStream_t stream);
