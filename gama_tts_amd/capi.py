@@ -190,6 +190,9 @@ def load_library(diagnostics=False):
         L.gvtm_synthesize_voices_host.restype = i32
         L.gvtm_synthesize_voices_host_pcm16.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
         L.gvtm_synthesize_voices_host_pcm16.restype = i32
+    if hasattr(L, "gvtm_plan_create_model5_voices"):
+        L.gvtm_plan_create_model5_voices.argtypes = [ctypes.POINTER(Config5), sz, dbl, i32, ctypes.POINTER(vp)]
+        L.gvtm_plan_create_model5_voices.restype = i32
     L.gvtm_plan_set_timing.argtypes = [vp, i32]
     L.gvtm_plan_set_timing.restype = i32
     L.gvtm_plan_take_kernel_ms.argtypes = [vp, ctypes.POINTER(i32)]
@@ -499,8 +502,9 @@ class Plan:
 
 
 class VoicesPlan(Plan):
-    """Owns a gvtm_plan of several voices (gvtm_plan_create_voices): configs[v] is voice v.  Its batches mix voices, one
-    voice id per utterance; the single-voice entries (Plan.synthesize_*, Stream) are refused on it when it has two or more."""
+    """Owns a gvtm_plan of several voices: configs[v] is voice v, all Config (gvtm_plan_create_voices) or all Config5
+    (gvtm_plan_create_model5_voices).  Its batches mix voices, one voice id per utterance; the single-voice entries
+    (Plan.synthesize_*, Stream) are refused on it when it has two or more."""
 
     def __init__(self, configs, control_rate=250.0, device=0, diagnostics=False, rows=0):
         self._lib = load_library(diagnostics)
@@ -508,8 +512,12 @@ class VoicesPlan(Plan):
         self._h = ctypes.c_void_p()
         self.configs = list(configs)
         self.config = self.configs[0] if self.configs else None
-        arr = (Config * max(len(self.configs), 1))(*self.configs)
-        self._check(self._lib.gvtm_plan_create_voices(arr, len(self.configs), float(control_rate), int(device), ctypes.byref(self._h)))
+        model5 = isinstance(self.config, Config5)
+        if any(isinstance(c, Config5) != model5 for c in self.configs):
+            raise TypeError("a plan's voices are all Config or all Config5")
+        ctype, create = (Config5, self._lib.gvtm_plan_create_model5_voices) if model5 else (Config, self._lib.gvtm_plan_create_voices)
+        arr = (ctype * max(len(self.configs), 1))(*self.configs)
+        self._check(create(arr, len(self.configs), float(control_rate), int(device), ctypes.byref(self._h)))
         self.n_voices = int(self._lib.gvtm_plan_voice_count(self._h))
         self.info = self.voice_info(0)
         if rows:

@@ -206,6 +206,25 @@ int gvtm_device_count(void)
 
 namespace {
 
+// The device part of every plan: a HIP device at that index, a gfx950 one, and its compute units
+int open_device(gvtm_plan* plan, int device)
+{
+	int n = 0;
+	hipError_t e = hipGetDeviceCount(&n);
+	if (e != hipSuccess || n <= 0) {
+		return fail(GVTM_ERR_NO_DEVICE, "no HIP device available (libgama_vtm has no CPU path)");
+	}
+	if (device < 0 || device >= n) return fail(GVTM_ERR_NO_DEVICE, "device index out of range");
+	plan->device = device;
+	hipDeviceProp_t prop;
+	if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return fail_hip(e, "hipGetDeviceProperties");
+	if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+		return fail(GVTM_ERR_NO_DEVICE, std::string("kernels are built for gfx950 only, device is ") + prop.gcnArchName);
+	}
+	plan->compute_units = prop.multiProcessorCount;
+	return GVTM_OK;
+}
+
 // gvtm_plan_create (n_voices == 1) and gvtm_plan_create_voices
 int create_plan(const gvtm_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
 {
@@ -239,21 +258,11 @@ int create_plan(const gvtm_config* configs, size_t n_voices, double control_rate
 			*plan_out = plan.release();
 			return GVTM_OK;
 		}
-		int n = 0;
-		hipError_t e = hipGetDeviceCount(&n);
-		if (e != hipSuccess || n <= 0) {
-			return fail(GVTM_ERR_NO_DEVICE, "no HIP device available (libgama_vtm has no CPU path)");
-		}
-		if (device < 0 || device >= n) return fail(GVTM_ERR_NO_DEVICE, "device index out of range");
-		plan->device = device;
+		const int rc = open_device(plan.get(), device);
+		if (rc != GVTM_OK) return rc;
 		DeviceScope scope(device);
-		if ((e = scope.status()) != hipSuccess) return fail_hip(e, "hipSetDevice");
-		hipDeviceProp_t prop;
-		if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return fail_hip(e, "hipGetDeviceProperties");
-		if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-			return fail(GVTM_ERR_NO_DEVICE, std::string("kernels are built for gfx950 only, device is ") + prop.gcnArchName);
-		}
-		plan->compute_units = prop.multiProcessorCount;
+		hipError_t e = scope.status();
+		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
 		const gvtm::Design& dg = plan->design;
 		// one wavetable and one constants block per voice, back to back (the glottal FIR and the converter's tables depend
 		// on no configuration key: voice 0's serve all)
@@ -278,6 +287,62 @@ int create_plan(const gvtm_config* configs, size_t n_voices, double control_rate
 			if ((e = upload(&plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
 		}
 		if ((e = upload(&plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
+		*plan_out = plan.release();
+		return GVTM_OK;
+	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	} catch (const std::exception& ex) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, ex.what());
+	}
+}
+
+// gvtm_plan_create_model5 (n_voices == 1) and gvtm_plan_create_model5_voices
+int create_plan5(const gvtm5_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
+{
+	if (!configs || !plan_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null config or plan_out");
+	*plan_out = nullptr;
+	if (n_voices == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "a plan needs at least one voice");
+	if (n_voices > 0x7fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "too many voices");
+	for (size_t v = 1; v < n_voices; ++v) {
+		if (configs[v].output_rate != configs[0].output_rate || configs[v].precision != configs[0].precision) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "voice " + std::to_string(v) + ": output_rate and precision must be those of voice 0 "
+					"(one plan is one model at one output rate)");
+		}
+	}
+	try {
+		std::unique_ptr<gvtm_plan, void (*)(gvtm_plan*)> plan(new gvtm_plan, free_plan);
+		const std::string why = gvtm::design_plan5(configs[0], control_rate, plan->design);
+		if (!why.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, n_voices > 1 ? "voice 0: " + why : why);
+		plan->precision = GVTM_PRECISION_F64;
+		plan->n_voices = static_cast<int>(n_voices);
+		plan->voices.resize(n_voices - 1);
+		for (size_t v = 1; v < n_voices; ++v) {
+			const std::string why_v = gvtm::design_plan5(configs[v], control_rate, plan->voices[v - 1]);
+			if (!why_v.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice " + std::to_string(v) + ": " + why_v);
+		}
+		if (device == GVTM_DEVICE_NONE) {
+			plan->device = GVTM_DEVICE_NONE;
+			*plan_out = plan.release();
+			return GVTM_OK;
+		}
+		const int rc = open_device(plan.get(), device);
+		if (rc != GVTM_OK) return rc;
+		DeviceScope scope(device);
+		hipError_t e = scope.status();
+		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+		// one constants block of each kind per voice, back to back (the converter's tables depend on no configuration
+		// key: voice 0's serve all)
+		std::vector<gvtm::DeviceConstants> consts;
+		std::vector<gvtm::Model5Constants> consts5;
+		for (size_t v = 0; v < n_voices; ++v) {
+			consts.push_back(plan->voice(static_cast<int>(v)).k);
+			consts5.push_back(plan->voice(static_cast<int>(v)).k5);
+		}
+		const gvtm::Design& dg = plan->design;
+		if ((e = upload(&plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
+		if ((e = upload(&plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
+		if ((e = upload(&plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
+		if ((e = upload(&plan->d_consts5, consts5)) != hipSuccess) return fail_hip(e, "upload model 5 constants");
 		*plan_out = plan.release();
 		return GVTM_OK;
 	} catch (const std::bad_alloc&) {
@@ -370,43 +435,12 @@ size_t gvtm_voices_output_capacity(const gvtm_plan* plan, size_t max_frames)
 
 int gvtm_plan_create_model5(const gvtm5_config* config, double control_rate, int device, gvtm_plan** plan_out)
 {
-	if (!config || !plan_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null config or plan_out");
-	*plan_out = nullptr;
-	try {
-		std::unique_ptr<gvtm_plan, void (*)(gvtm_plan*)> plan(new gvtm_plan, free_plan);
-		const std::string why = gvtm::design_plan5(*config, control_rate, plan->design);
-		if (!why.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, why);
-		plan->precision = GVTM_PRECISION_F64;
-		if (device == GVTM_DEVICE_NONE) {
-			plan->device = GVTM_DEVICE_NONE;
-			*plan_out = plan.release();
-			return GVTM_OK;
-		}
-		int n = 0;
-		hipError_t e = hipGetDeviceCount(&n);
-		if (e != hipSuccess || n <= 0) return fail(GVTM_ERR_NO_DEVICE, "no HIP device available (libgama_vtm has no CPU path)");
-		if (device < 0 || device >= n) return fail(GVTM_ERR_NO_DEVICE, "device index out of range");
-		plan->device = device;
-		DeviceScope scope(device);
-		if ((e = scope.status()) != hipSuccess) return fail_hip(e, "hipSetDevice");
-		hipDeviceProp_t prop;
-		if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return fail_hip(e, "hipGetDeviceProperties");
-		if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-			return fail(GVTM_ERR_NO_DEVICE, std::string("kernels are built for gfx950 only, device is ") + prop.gcnArchName);
-		}
-		plan->compute_units = prop.multiProcessorCount;
-		const gvtm::Design& dg = plan->design;
-		if ((e = upload(&plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
-		if ((e = upload(&plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
-		if ((e = upload(&plan->d_consts, std::vector<gvtm::DeviceConstants>(1, dg.k))) != hipSuccess) return fail_hip(e, "upload constants");
-		if ((e = upload(&plan->d_consts5, std::vector<gvtm::Model5Constants>(1, dg.k5))) != hipSuccess) return fail_hip(e, "upload model 5 constants");
-		*plan_out = plan.release();
-		return GVTM_OK;
-	} catch (const std::bad_alloc&) {
-		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
-	} catch (const std::exception& ex) {
-		return fail(GVTM_ERR_INVALID_ARGUMENT, ex.what());
-	}
+	return create_plan5(config, 1, control_rate, device, plan_out);
+}
+
+int gvtm_plan_create_model5_voices(const gvtm5_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
+{
+	return create_plan5(configs, n_voices, control_rate, device, plan_out);
 }
 
 void gvtm_plan_destroy(gvtm_plan* plan)
@@ -819,7 +853,6 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
 	// (the single-voice entries would not know which voice to synthesize; the voices entries take a one-voice plan too)
 	if (!r.voices && plan->n_voices > 1) return refuse_voices(plan, r.sl ? "gvtm_stream_*" : "gvtm_synthesize_batch_device");
-	if (r.voices && plan->design.model5) return fail(GVTM_ERR_INVALID_ARGUMENT, "model 5 plans have one voice: gvtm_synthesize_batch_*");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	if (r.batch == 0) return GVTM_OK;
 	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
@@ -842,8 +875,9 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	const bool model5 = plan->design.model5;
 	const gvtm::DeviceConstants& k = plan->design.k;
 	int rows = model5 ? plan->rows5_for(r.batch) : gvtm::synth_rows(plan->precision, r.batch, plan->rows, k.section_delay);
-	// (the voice variant has the product's shapes only: eight rows are a diagnostics build's forced shape)
-	if (r.voices) rows = std::min(rows, 4);
+	// (the voice variant has the product's shapes only: eight rows are a diagnostics build's forced shape, and model 5's
+	// voices run one utterance per workgroup, a diagnostics build's forced two-utterance shape included)
+	if (r.voices) rows = std::min(rows, model5 ? 1 : 4);
 	if (r.sl && r.sl->rows == 1) rows = 1;
 	// the LDS holds the stream's ring (one for all shapes) or the longest ring of the voices; a shape it does not fit
 	// (a down-sampling voice carries the reference's 1024-sample ring per row) gives way to the next smaller one
@@ -884,7 +918,7 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 		if (rc != GVTM_OK) return rc;
 	}
 	return timed_launch(plan, stream, r.voices ? "vtm_synth_kernel launch (voices)" : "vtm_synth_kernel launch", [&] {
-		return model5 ? gvtm::launch_synth5(args, r.batch, rows, stream) : gvtm::launch_synth(args, work, plan->precision, rows, stream);
+		return model5 ? gvtm::launch_synth5(args, work, rows, stream) : gvtm::launch_synth(args, work, plan->precision, rows, stream);
 	});
 }
 
@@ -969,7 +1003,6 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
 	const bool voices = j.voice_ids != nullptr;
 	if (!voices && plan->n_voices > 1) return refuse_voices(plan, j.pcm ? "gvtm_synthesize_batch_host_pcm16" : "gvtm_synthesize_batch_host");
-	if (voices && plan->design.model5) return fail(GVTM_ERR_INVALID_ARGUMENT, "model 5 plans have one voice: gvtm_synthesize_batch_*");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	const size_t batch = j.batch, max_frames = j.max_frames, audio_stride = j.stride;
 	if (batch == 0) return GVTM_OK;

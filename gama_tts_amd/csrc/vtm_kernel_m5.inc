@@ -1,6 +1,8 @@
 // Reference model 5 (VocalTractModel5<double,1>, vtm/VocalTractModel5.h) on the device.
-// Included by vtm_kernels.hip inside namespace gvtm, after vtm_kernel_v2.inc (whose wave-wide DPP helpers
-// and Extent it shares).
+// Included inside namespace gvtm, after vtm_kernel_v2.inc (whose wave-wide DPP helpers, Extent and voice_row it shares),
+// by two translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
+// (kVoices5Flag) in a code object of its own.  Besides the kernel, the file defines what both launch it with: the shape
+// constants (kM5Ring, kM5Chunk1/2, kM5Helpers1/2) and launch_synth5_shape, at the end.
 //
 // Same organisation as generation 2: a workgroup owns U utterances (1 or 2; the tube has 30 + 21 = 51 sections, one
 // per lane of a wavefront, so every utterance has a tube wavefront of its own, while the scan, filter and interpolation
@@ -108,9 +110,26 @@ struct Offsets {
 
 } // namespace
 
-template <int C, int NH, int XR, int U>
-__global__ __launch_bounds__((3 + U + NH) * 64) void vtm5_synth_kernel(const SynthArgs a)
+// Several voices in one launch (gvtm_synthesize_voices_device on a gvtm_plan_create_model5_voices plan): the kernel's last
+// template argument carries, besides the utterances per workgroup in bits 0-1, the flag kVoices5Flag (default off; one
+// utterance per workgroup only).  With it, workgroup g synthesizes utterance a.row_map[g] of voice a.group_voice[g] (-1: a
+// group past the last voice's, which exits at once) from that voice's constants a.kconst[voice] and a.k5const[voice].
+// Everything downstream reads the staged copies; only the utterance's rows in HBM (extent, frames, samples, count, peak)
+// follow the row map.  As in vtm_kernel_v2.inc (kVoicesFlag), each voice-dependent expression is a conditional on the
+// constant VOICES, so the single-voice kernels compile to the code they had before the flag existed.
+constexpr int kVoices5Flag = 4;
+
+template <int C, int NH, int XR, int U_FLAGS>
+__global__ __launch_bounds__((3 + (U_FLAGS & 3) + NH) * 64) void vtm5_synth_kernel(const SynthArgs a)
 {
+	constexpr int U = U_FLAGS & 3;
+	constexpr bool VOICES = (U_FLAGS & kVoices5Flag) != 0;
+	static_assert(!VOICES || U == 1, "the voice variant has the one-utterance shape only");
+	int voice = 0;
+	if constexpr (VOICES) {
+		voice = a.group_voice[blockIdx.x];
+		if (voice < 0) return; // (uniform across the workgroup, before any barrier)
+	}
 	static_assert(U == 1 || U == 2, "one or two utterances per workgroup");
 	static_assert(C % 4 == 0 && U * C <= 64, "one helper pass per per-step stage, serial stages in blocks of four");
 	static_assert((XR & (XR - 1)) == 0 && XR >= 2 * C + 4 * kMaxPad, "ring must hold 2 chunks + history + flush");
@@ -176,13 +195,15 @@ __global__ __launch_bounds__((3 + U + NH) * 64) void vtm5_synth_kernel(const Syn
 		tube_u = wave < U ? wave : 0;
 	}
 	const size_t group = blockIdx.x;
+	// GVTM_M5_UTT(u, single-voice expression): the utterance of row u (see kVoices5Flag; a voice's group is never empty)
+#define GVTM_M5_UTT(u, ...) (VOICES ? v2::voice_row(a, group * U + (u)) : __VA_ARGS__)
 
 	// ---- constants, extent and the resampler table into LDS; clear the rings
 	{
-		const int* src = reinterpret_cast<const int*>(a.kconst);
+		const int* src = reinterpret_cast<const int*>(VOICES ? a.kconst + voice : a.kconst);
 		int* dst = reinterpret_cast<int*>(s_kc);
 		for (int i = tid; i < static_cast<int>(sizeof(DeviceConstants) / sizeof(int)); i += kThreads) dst[i] = src[i];
-		const int* src5 = reinterpret_cast<const int*>(a.k5const);
+		const int* src5 = reinterpret_cast<const int*>(VOICES ? a.k5const + voice : a.k5const);
 		int* dst5 = reinterpret_cast<int*>(s_k5);
 		for (int i = tid; i < static_cast<int>(sizeof(Model5Constants) / sizeof(int)); i += kThreads) dst5[i] = src5[i];
 	}
@@ -199,12 +220,13 @@ __global__ __launch_bounds__((3 + U + NH) * 64) void vtm5_synth_kernel(const Syn
 	// gvtm_stream_*: a launch continues utterances from the state an earlier launch left in device memory (a.stream,
 	// layout: Stream5Layout in vtm_kernels.hpp) and leaves its own behind.  A push synthesizes whole frames, keeps the
 	// converter's flush for later and finds the frame AFTER its last one in the buffer; finish (and the one-shot entry) flushes.
-	const bool kPush = a.stream_mode == kStreamPush;
+	// (streams have one voice: the voice variant never streams)
+	const bool kPush = !VOICES && a.stream_mode == kStreamPush;
 	const bool kFinal = !kPush;
-	const bool streaming = a.stream != nullptr;
+	const bool streaming = !VOICES && a.stream != nullptr;
 	if (tid < U) {
 		Extent e{0, 0, 0, 0, 0ull, 0ull};
-		const size_t ug = group * U + tid;
+		const size_t ug = GVTM_M5_UTT(tid, group * U + tid);
 		unsigned peak0 = 0u;
 		if (ug < a.batch) {
 			// a stream's push carries one more row than it synthesizes: the next frame, which the last one interpolates towards
@@ -647,7 +669,7 @@ __global__ __launch_bounds__((3 + U + NH) * 64) void vtm5_synth_kernel(const Syn
 				y = static_cast<float>(static_cast<double>(d) * k5.output_rate);
 			}
 			const uint64_t kout = ko - s_ext[u].k_first; // (a stream's launch numbers its samples from its own first one)
-			if (kout < a.audio_stride) a.audio[(group * U + u) * a.audio_stride + kout] = y;
+			if (kout < a.audio_stride) a.audio[GVTM_M5_UTT(u, (group * U + u)) * a.audio_stride + kout] = y;
 		}
 		// reduced once, after the last tick
 		if (U == 1 || u == 0) lane_peak[0] = fmaxf(lane_peak[0], fabsf(y));
@@ -672,7 +694,7 @@ __global__ __launch_bounds__((3 + U + NH) * 64) void vtm5_synth_kernel(const Syn
 	const int ip_u = lane >> 4; // lanes 16u .. 16u + 15 interpolate utterance u
 	const int ip_frames = ip_u < U ? s_ext[ip_u].frames : 0;
 	const int ip_last = ip_u < U ? s_ext[ip_u].last_frame : 0; // last readable row: frames - 1, or the look-ahead frame of a push
-	const float* __restrict__ P = a.params + (group * U + (ip_u < U ? ip_u : 0)) * a.max_frames * 16;
+	const float* __restrict__ P = a.params + GVTM_M5_UTT(0, (group * U + (ip_u < U ? ip_u : 0))) * a.max_frames * 16;
 	if (role == 3 && ip_u < U && ip_frames > 0) {
 		ip_this = P[Lp];
 		ip_next = P[static_cast<size_t>(ip_last > 1 ? 1 : ip_last) * 16 + Lp];
@@ -977,7 +999,7 @@ __global__ __launch_bounds__((3 + U + NH) * 64) void vtm5_synth_kernel(const Syn
 	if (role == 0) __builtin_amdgcn_s_setprio(3);
 	else if (role < 4) __builtin_amdgcn_s_setprio(1);
 
-	const bool stamping = a.phase_cycles != nullptr && lane == 0;
+	const bool stamping = !VOICES && a.phase_cycles != nullptr && lane == 0;
 	unsigned long long busy = 0;
 	const int n_ticks = max_chunks + 14;
 	for (int t = 0; t < n_ticks; ++t) {
@@ -1087,7 +1109,7 @@ __global__ __launch_bounds__((3 + U + NH) * 64) void vtm5_synth_kernel(const Syn
 					const float d = v - v2;
 					y = static_cast<float>(static_cast<double>(d) * k5.output_rate);
 				}
-				if (ko - e.k_first < a.audio_stride) a.audio[(group * U + u) * a.audio_stride + (ko - e.k_first)] = y;
+				if (ko - e.k_first < a.audio_stride) a.audio[GVTM_M5_UTT(u, (group * U + u)) * a.audio_stride + (ko - e.k_first)] = y;
 				lane_peak[u] = fmaxf(lane_peak[u], fabsf(y));
 			}
 		}
@@ -1103,10 +1125,10 @@ __global__ __launch_bounds__((3 + U + NH) * 64) void vtm5_synth_kernel(const Syn
 	// diagnostics: busy cycles per wavefront (in wavefront order; see role mapping above), then per helper stage
 	if (stamping && wave < 7) a.phase_cycles[group * 16 + wave] = busy;
 	__syncthreads();
-	if (a.phase_cycles != nullptr && tid < 9) a.phase_cycles[group * 16 + 7 + tid] = s_diag[tid];
+	if (!VOICES && a.phase_cycles != nullptr && tid < 9) a.phase_cycles[group * 16 + 7 + tid] = s_diag[tid];
 
 	if (tid < U) {
-		const size_t ug = group * U + tid;
+		const size_t ug = GVTM_M5_UTT(tid, group * U + tid);
 		if (ug < a.batch) {
 			if (a.maxabs) a.maxabs[ug] = __uint_as_float(s_peak[tid]);
 			const Extent e = s_ext[tid];
@@ -1162,6 +1184,31 @@ __global__ __launch_bounds__((3 + U + NH) * 64) void vtm5_synth_kernel(const Syn
 			}
 		}
 	}
+#undef GVTM_M5_UTT
 }
 
 } // namespace m5
+
+// reference model 5.  One utterance per workgroup: chunk of 60 steps (one 64-lane pass per per-step stage), three helper
+// wavefronts.  Two utterances per workgroup (batches beyond one workgroup per compute unit): two tube wavefronts, chunk of
+// 24 steps (2 x 24 items per per-step pass; what LDS holds with two 62-entry tube records per step), five helpers.
+constexpr int kM5Ring = kSrcRing; // the reference's BUFFER_SIZE: see the flush-overrun epilogue
+constexpr int kM5Chunk1 = 60, kM5Helpers1 = 3;
+#ifndef GVTM_TUNE_M5_NH2
+#define GVTM_TUNE_M5_NH2 5
+#endif
+constexpr int kM5Chunk2 = 24, kM5Helpers2 = GVTM_TUNE_M5_NH2;
+
+// VOICES: a launch of several voices (the kernel's kVoices5Flag; args.row_map is set), one utterance per workgroup only;
+// `batch` is then the number of workgroups
+template <int C, int NH, int U, bool VOICES>
+static hipError_t launch_synth5_shape(const SynthArgs& args, size_t batch, hipStream_t stream)
+{
+	static_assert(!VOICES || U == 1, "the voice variant has the one-utterance shape only");
+	auto fn = m5::vtm5_synth_kernel<C, NH, kM5Ring, U | (VOICES ? m5::kVoices5Flag : 0)>;
+	const size_t lds = m5::Offsets<C, kM5Ring, U>().total;
+	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(VOICES ? batch : (batch + U - 1) / U)), dim3((3 + U + NH) * 64), lds, stream, args);
+	return hipGetLastError();
+}

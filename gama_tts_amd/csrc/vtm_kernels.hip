@@ -3,7 +3,8 @@
 //   vtm_synth_kernel   (vtm_kernel_v2.inc)  VocalTractModel0 / 2 / 4 semantics: a workgroup owns 1, 2, 4 or 8 utterances and
 //                      5 + NH wavefronts with fixed roles (tube, scans, pre-/post-tube filters, interpolation, helpers),
 //                      software-pipelined over chunks of internal-rate steps with one barrier per tick; see that file's header
-//   vtm5_synth_kernel  (vtm_kernel_m5.inc)  VocalTractModel5 semantics, same organisation
+//   vtm5_synth_kernel  (vtm_kernel_m5.inc)  VocalTractModel5 semantics, same organisation (its voice variant is compiled
+//                      in vtm_kernels_m5v.hip)
 //   vtm_normalize_kernel                    output scaling of Controller::writeOutputToBuffer / writeOutputToFile
 //
 // Everything between the parameter frames (HBM in) and the audio samples (HBM out) lives in LDS; there is no
@@ -316,37 +317,21 @@ hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream)
 	return hipGetLastError();
 }
 
-// reference model 5.  One utterance per workgroup: chunk of 60 steps (one 64-lane pass per per-step stage), three helper
-// wavefronts.  Two utterances per workgroup (batches beyond one workgroup per compute unit): two tube wavefronts, chunk of
-// 24 steps (2 x 24 items per per-step pass; what LDS holds with two 62-entry tube records per step), five helpers.
-constexpr int kM5Ring = kSrcRing; // the reference's BUFFER_SIZE: see the flush-overrun epilogue
-constexpr int kM5Chunk1 = 60, kM5Helpers1 = 3;
-#ifndef GVTM_TUNE_M5_NH2
-#define GVTM_TUNE_M5_NH2 5
-#endif
-constexpr int kM5Chunk2 = 24, kM5Helpers2 = GVTM_TUNE_M5_NH2;
-
 size_t synth5_lds_bytes(int rows)
 {
 	return rows == 2 ? m5::Offsets<kM5Chunk2, kM5Ring, 2>().total : m5::Offsets<kM5Chunk1, kM5Ring, 1>().total;
 }
 
-template <int C, int NH, int U>
-static hipError_t launch_synth5_shape(const SynthArgs& args, size_t batch, hipStream_t stream)
-{
-	auto fn = m5::vtm5_synth_kernel<C, NH, kM5Ring, U>;
-	const size_t lds = m5::Offsets<C, kM5Ring, U>().total;
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>((batch + U - 1) / U)), dim3((3 + U + NH) * 64), lds, stream, args);
-	return hipGetLastError();
-}
-
 hipError_t launch_synth5(const SynthArgs& args, size_t batch, int rows, hipStream_t stream)
 {
 	if (!args.k5const) return hipErrorInvalidValue;
-	if (rows == 2) return launch_synth5_shape<kM5Chunk2, kM5Helpers2, 2>(args, batch, stream);
-	return launch_synth5_shape<kM5Chunk1, kM5Helpers1, 1>(args, batch, stream);
+	// (the voice variant lives in vtm_kernels_m5v.hip: this file's code object keeps the single-voice kernels only)
+	if (!args.row_map) {
+		if (rows == 2) return launch_synth5_shape<kM5Chunk2, kM5Helpers2, 2, false>(args, batch, stream);
+		return launch_synth5_shape<kM5Chunk1, kM5Helpers1, 1, false>(args, batch, stream);
+	}
+	if (!args.group_voice || rows != 1) return hipErrorInvalidValue;
+	return launch_synth5_voices(args, batch, stream);
 }
 
 hipError_t launch_normalize(const NormalizeArgs& args, size_t batch, hipStream_t stream)

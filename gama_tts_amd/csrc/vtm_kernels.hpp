@@ -91,7 +91,8 @@ struct SynthArgs {
 	double* debug_taps;          // null, or [batch][max_frames*control_steps][8] per-step taps (tests only)
 	unsigned long long* phase_cycles; // null, or [workgroups][16] shader cycles per role wavefront and helper stage (diagnostics only)
 	const Model5Constants* k5const = nullptr; // model 5 only: its constants in device memory
-	// launches of several voices (set: launch_synth runs the voice variant): kconst and wavetable then hold one block per voice
+	// launches of several voices (set: launch_synth / launch_synth5 run the voice variant): kconst and wavetable (model 5:
+	// kconst and k5const) then hold one block per voice
 	const int32_t* row_map = nullptr;     // [groups][rows] utterance of each workgroup row, -1 = none
 	const int32_t* group_voice = nullptr; // [groups] voice of each workgroup, -1 = none (the workgroup exits)
 };
@@ -136,9 +137,12 @@ hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int 
 size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr);
 // several voices: builds args.row_map / args.group_voice from the voice ids (one small workgroup, stable counting sort)
 hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream);
-// reference model 5 (VocalTractModel5<double,1>), fp64: rows = utterances per workgroup, 1 or 2
+// reference model 5 (VocalTractModel5<double,1>), fp64: rows = utterances per workgroup, 1 or 2; with args.row_map set
+// (several voices: one constants block of each kind per voice) 1 only, and `batch` is the number of workgroups
 size_t synth5_lds_bytes(int rows = 1);
 hipError_t launch_synth5(const SynthArgs& args, size_t batch, int rows, hipStream_t stream);
+// the voice variant alone (vtm_kernels_m5v.hip; launch_synth5 calls it): `groups` workgroups of one utterance each
+hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_t stream);
 constexpr int kDppSelftestInts = 640;
 hipError_t launch_dpp_selftest(int* d_out /* [kDppSelftestInts] */, hipStream_t stream);
 hipError_t launch_float_math_probe(int kind, const float* d_x, size_t n, float* d_out, hipStream_t stream);

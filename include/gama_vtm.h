@@ -34,10 +34,10 @@
  *   gvtm_synthesize_events_device
  *                               EventList::generateOutput (vtm_control_model/EventList.cpp:930-1091) followed by
  *                               Controller::synthesize in one call: event lists in, samples out
- *   gvtm_plan_create_voices / gvtm_synthesize_voices_*
+ *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
- *                               (data/voice/english/0_male/vtm.txt + variant/{male,female,large_child,small_child,baby}.txt,
- *                               merged by Controller.cpp:48-49), all of them in one launch
+ *                               (data/voice/english/0_male/vtm.txt resp. 5_male/vtm.txt + variant/{male,female,
+ *                               large_child,small_child,baby}.txt, merged by Controller.cpp:48-49), all of them in one launch
  *   gvtm_normalize_batch_device Controller::writeOutputToBuffer / writeOutputToFile scaling,
  *                               Util::calculateOutputScale (Controller.cpp:315-340,
  *                               vtm/VTMUtil.cpp:48-67, WAVEFileWriter.cpp:122-125)
@@ -134,7 +134,7 @@ typedef struct gvtm_info {
 	int32_t device;
 	int32_t precision;
 	int32_t section_delay;
-	int32_t model5;                   /* 1 for a plan made by gvtm_plan_create_model5 */
+	int32_t model5;                   /* 1 for a plan made by gvtm_plan_create_model5 / _model5_voices */
 	int32_t reserved_;
 	double internal_rate_hz;          /* the internal rate as the model holds it: an integer for models 0-4, not for
 	                                     model 5 (vtm/VocalTractModel5.h:465 keeps it in TFloat) */
@@ -272,11 +272,22 @@ int gvtm_synthesize_batch_host_pcm16(gvtm_plan* plan, const float* params, const
  * makes.  GVTM_DEVICE_NONE works as for gvtm_plan_create.  A plan of two or more voices refuses the single-voice
  * entry points (gvtm_synthesize_batch_*, gvtm_stream_create, gvtm_synthesize_events_device) with
  * GVTM_ERR_INVALID_ARGUMENT; gvtm_plan_info, gvtm_output_count and gvtm_output_capacity describe voice 0.  Reference
- * model 5 plans (gvtm_plan_create_model5) have one voice. */
+ * model 5 has an entry of its own, gvtm_plan_create_model5_voices. */
 int    gvtm_plan_create_voices(const gvtm_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out);
+/* The same for reference model 5: configs[n_voices], one gvtm5_config per voice (the 5_male voice's variants, say).
+ * output_rate and precision (GVTM_PRECISION_F64) must be equal across configs (else GVTM_ERR_INVALID_ARGUMENT); every
+ * other key may differ per voice, bypass and constant_radius_mouth_impedance included (none of them feeds a decision the
+ * host makes for the launch).  A voice the design refuses, as gvtm_plan_create_model5 would, fails the call with a
+ * message naming it ("voice 3: ...").  The device holds one constants block of each kind per voice and one set of
+ * converter tables for all of them.  n_voices == 1 makes exactly the plan gvtm_plan_create_model5 makes; GVTM_DEVICE_NONE
+ * gives a design-only plan; the rest is as for gvtm_plan_create_voices.  The kernel runs one utterance per workgroup
+ * (the one-utterance shape of model 5), so voices whose internal rates differ (longer and shorter tracts) share a launch
+ * without changing each other's shape. */
+int    gvtm_plan_create_model5_voices(const gvtm5_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out);
 /* Number of voices of a plan (1 for gvtm_plan_create / _model5 plans); a negative status for a null plan. */
 int    gvtm_plan_voice_count(const gvtm_plan* plan);
-/* gvtm_plan_info of one voice (internal rate, control steps, converter increments and up-sampling differ by voice). */
+/* gvtm_plan_info of one voice (internal rate, control steps, converter increments and up-sampling differ by voice; model 5
+ * voices: model5 = 1 and the voice's non-integer internal_rate_hz). */
 int    gvtm_plan_voice_info(const gvtm_plan* plan, int voice, gvtm_info* info_out);
 /* gvtm_output_count for an utterance of that voice; (size_t)-1 for a null plan or a voice out of range. */
 size_t gvtm_voice_output_count(const gvtm_plan* plan, int voice, size_t n_frames);

@@ -1,0 +1,49 @@
+#!/usr/bin/env python3
+"""Generates tests/golden/voices5_golden.npz by running the REAL reference's VocalTractModel5 with the four 5_male
+variants besides male (tests/golden/voice5_{female,large_child,small_child,baby}.txt).
+
+Build-container only: executes oracle/_ref/ref_vtm (compiled in place from /root/reference by oracle/Makefile with
+-O2 -ffp-contract=off).  The .npz holds data only: reference output samples (or their digest), counts, the internal
+rate.  Input frames are the recipes of tests/golden5_voices_cases.py (the "hello" frames are the ones stored in
+vtm_golden.npz).
+
+    python tests/golden/make_voices5_golden.py
+"""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+import golden5_voices_cases as cases  # noqa: E402
+import oracle  # noqa: E402
+
+
+def main():
+    if oracle.ref_binary() is None:
+        sys.exit("oracle/_ref/ref_vtm is not built (build() makes it where the reference sources are)")
+    hello = {"hello_params": np.load(os.path.join(HERE, "vtm_golden.npz"), allow_pickle=False)["hello_params"]}
+    out, manifest = {}, {}
+    for case in cases.CASES:
+        name = case["name"]
+        tr = cases.track_for(case, hello)
+        ref, info = oracle.ref_synthesize(tr, "5", case["rate"], cases.CRATE, config=cases.voice_path(case["voice"]))
+        manifest[name] = dict(n=int(ref.size), steps=int(info["steps"]), fs=float(info["fs"]),
+                              sum=float(ref.astype(np.float64).sum()), maxabs=float(np.abs(ref).max()) if ref.size else 0.0,
+                              sha256=hashlib.sha256(ref.tobytes()).hexdigest())
+        if case["store"] == "full":
+            out[name + "__out"] = ref
+        else:
+            out[name + "__strided"] = ref[:: cases.DIGEST_STRIDE].copy()
+        if case["store"] == "tail":
+            out[name + "__tail"] = ref[-cases.OVERRUN_TAIL:].copy()
+        print(name, ref.size, manifest[name]["fs"], manifest[name]["sha256"][:12])
+    out["manifest_json"] = np.frombuffer(json.dumps(manifest, sort_keys=True).encode(), dtype=np.uint8)
+    np.savez_compressed(os.path.join(HERE, "voices5_golden.npz"), **out)
+
+
+if __name__ == "__main__":
+    main()
