@@ -173,6 +173,11 @@ def load_library(diagnostics=False):
     L.gvtm_stream_push.restype = i32
     L.gvtm_stream_finish.argtypes = [vp, vp, sz, vp, vp]
     L.gvtm_stream_finish.restype = i32
+    if hasattr(L, "gvtm_stream_create_voices"):
+        L.gvtm_stream_create_voices.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+        L.gvtm_stream_create_voices.restype = i32
+        L.gvtm_stream_reset_voices.argtypes = [vp, vp]
+        L.gvtm_stream_reset_voices.restype = i32
     if hasattr(L, "gvtm_plan_create_voices"):  # (library variants built before plans of several voices still load: tools/ab.py)
         L.gvtm_plan_create_voices.argtypes = [ctypes.POINTER(Config), sz, dbl, i32, ctypes.POINTER(vp)]
         L.gvtm_plan_create_voices.restype = i32
@@ -582,14 +587,25 @@ class VoicesPlan(Plan):
 
 
 class Stream:
-    """Owns a gvtm_stream: `batch` utterances of a plan synthesized piece by piece (include/gama_vtm.h, "Streams")."""
+    """Owns a gvtm_stream: `batch` utterances of a plan synthesized piece by piece (include/gama_vtm.h, "Streams").
+    With voice_ids (int [batch]), utterance b is spoken by voice voice_ids[b] of a VoicesPlan (gvtm_stream_create_voices)."""
 
-    def __init__(self, plan, batch):
+    def __init__(self, plan, batch, voice_ids=None):
         self._plan = plan  # keeps the plan alive
         self._lib = plan._lib
         self._h = ctypes.c_void_p()
         self.batch = int(batch)
-        plan._check(self._lib.gvtm_stream_create(plan._h, self.batch, ctypes.byref(self._h)))
+        if voice_ids is None:
+            plan._check(self._lib.gvtm_stream_create(plan._h, self.batch, ctypes.byref(self._h)))
+        else:
+            ids = self._ids(voice_ids)
+            plan._check(self._lib.gvtm_stream_create_voices(plan._h, _ptr(ids), self.batch, ctypes.byref(self._h)))
+
+    def _ids(self, voice_ids):
+        ids = np.ascontiguousarray(voice_ids, dtype=np.int32)
+        if ids.ndim != 1 or ids.shape[0] != self.batch:
+            raise ValueError("voice_ids must hold one voice id per utterance (%d), got shape %s" % (self.batch, ids.shape))
+        return ids
 
     def close(self):
         if self._h:
@@ -602,8 +618,12 @@ class Stream:
         except Exception:
             pass
 
-    def reset(self):
-        self._plan._check(self._lib.gvtm_stream_reset(self._h))
+    def reset(self, voice_ids=None):
+        """Every utterance back to its fresh state; with voice_ids, the utterances then take those voices."""
+        if voice_ids is None:
+            self._plan._check(self._lib.gvtm_stream_reset(self._h))
+        else:
+            self._plan._check(self._lib.gvtm_stream_reset_voices(self._h, _ptr(self._ids(voice_ids))))
 
     def capacity(self, max_new_frames):
         return int(self._lib.gvtm_stream_capacity(self._h, int(max_new_frames)))

@@ -728,8 +728,8 @@ struct StreamLaunch {
 	unsigned char* d_state;
 	size_t stride;
 	int mode;     // gvtm::StreamMode
-	int xr;       // the stream's ring length (one for all shapes)
-	int rows;     // 1 unless the utterances are in lockstep
+	int xr;       // the stream's ring length (one for all shapes; several voices: the longest of the plan's voices)
+	int rows;     // 1 unless the utterances are in lockstep (several voices: within each voice)
 };
 
 // One synthesis launch: the device buffers of a gvtm_synthesize_*_device call, of a slice of the host entries or of a stream
@@ -812,6 +812,9 @@ gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 		args.stream = r.sl->d_state;
 		args.stream_stride = r.sl->stride;
 		args.stream_mode = r.sl->mode;
+		// several voices: each voice's ring is its single-voice stream's, fixed by the one-row shape's chunk (voices share the
+		// precision, SectionDelay and tube layout the chunk follows)
+		if (r.voices && !dg.model5) args.stream_chunk = gvtm::synth_chunk_length(dg.k, plan->precision, 1);
 	}
 	// (not for several voices: the hooks' buffers are sized for voice 0's steps and ceil(batch / rows) workgroups)
 	args.debug_taps = r.voices ? nullptr : plan->debug_taps;
@@ -1217,10 +1220,14 @@ void gvtm_host_free(void* ptr)
 struct gvtm_stream {
 	gvtm_plan* plan = nullptr;
 	size_t batch = 0;
-	size_t state_stride = 0;
-	int xr = 0;
-	unsigned granule_frames = 1;          // pushes are synthesized in multiples of this many frames (12 internal steps)
-	DeviceBuffer d_state, d_params, d_frames, d_audio, d_counts, d_maxabs;
+	size_t state_stride = 0;              // the largest of the plan's voices (reset_voices never reallocates)
+	int xr = 0;                           // ring length: the longest of the plan's voices (each voice keeps its own in the kernel)
+	std::vector<unsigned> granule_frames; // per voice of the plan: pushes are synthesized in multiples of this many frames
+	// a plan of several voices (gvtm_stream_create_voices): utterance b is spoken by voice_ids[b], a copy of which is on the
+	// device for the grouping kernel
+	bool voices = false;
+	std::vector<int32_t> voice_ids;
+	DeviceBuffer d_state, d_params, d_frames, d_audio, d_counts, d_maxabs, d_voice_ids;
 	std::vector<std::vector<float>> held; // per utterance: frames pushed but not yet synthesized (the last one is the look-ahead)
 	std::vector<uint64_t> steps_done;     // per utterance: internal steps synthesized
 	std::vector<float> staging;
@@ -1236,6 +1243,11 @@ unsigned gcd_u(unsigned a, unsigned b)
 	return a;
 }
 
+int voice_of(const gvtm_stream* s, size_t b)
+{
+	return s->voices ? s->voice_ids[b] : 0;
+}
+
 int stream_upload_fresh_state(gvtm_stream* s)
 {
 	std::vector<unsigned char> init(s->state_stride * s->batch, 0);
@@ -1247,7 +1259,7 @@ int stream_upload_fresh_state(gvtm_stream* s)
 		if (model5) {
 			// VocalTractModel5::reset (vtm/VocalTractModel5.h:423-453): RosenbergBGlottalSource::reset leaves t2 at the end of the
 			// longest falling phase, the noise source starts from its seed, everything else is zero
-			const gvtm::Model5Constants& k5 = s->plan->design.k5;
+			const gvtm::Model5Constants& k5 = s->plan->voice(voice_of(s, b)).k5;
 			double sc[gvtm::kStream5Scalars] = {};
 			sc[gvtm::kS5Scan + 1] = k5.rb_t1 + k5.rb_tn_max;
 			sc[gvtm::kS5Scan + 2] = 0.7892347;
@@ -1269,20 +1281,24 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 		float* maxabs, bool* launched = nullptr)
 {
 	gvtm_plan* plan = s->plan;
-	const gvtm::DeviceConstants& k = plan->design.k;
 	const size_t batch = s->batch;
 	size_t rows_max = 0;
 	bool lockstep = true, any = final;
+	// (lockstep is judged per voice: a workgroup only ever holds one voice; first[v] is voice v's first utterance)
+	std::vector<size_t> first(static_cast<size_t>(plan->n_voices), batch);
 	for (size_t b = 0; b < batch; ++b) {
 		const size_t rows = n_frames[b] + (final ? 0 : 1); // a push carries the look-ahead frame behind its last one
 		rows_max = std::max(rows_max, n_frames[b] ? rows : size_t(0));
-		if (n_frames[b] != n_frames[0] || s->steps_done[b] != s->steps_done[0]) lockstep = false;
+		size_t& f = first[static_cast<size_t>(voice_of(s, b))];
+		if (f == batch) f = b;
+		if (n_frames[b] != n_frames[f] || s->steps_done[b] != s->steps_done[f]) lockstep = false;
 		if (n_frames[b]) any = true;
 	}
 	// exact sample counts, known before the launch
 	size_t need = 0;
 	std::vector<int64_t> want(batch, 0);
 	for (size_t b = 0; b < batch; ++b) {
+		const gvtm::DeviceConstants& k = plan->voice(voice_of(s, b)).k;
 		const uint64_t after = s->steps_done[b] + static_cast<uint64_t>(n_frames[b]) * k.control_steps;
 		if (after + 4096ull >= (1ull << 31)) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
 		const uint64_t k0 = outputs_before(k, s->steps_done[b]);
@@ -1325,7 +1341,7 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	const StreamLaunch sl{static_cast<unsigned char*>(s->d_state.ptr), s->state_stride, final ? gvtm::kStreamFinish : gvtm::kStreamPush, s->xr, lockstep ? 0 : 1};
 	const int rc = launch_synthesis(plan, LaunchRequest{static_cast<const float*>(s->d_params.ptr), static_cast<const int32_t*>(s->d_frames.ptr), batch,
 			rows_max, static_cast<float*>(s->d_audio.ptr), audio_stride, static_cast<int64_t*>(s->d_counts.ptr), static_cast<float*>(s->d_maxabs.ptr), nullptr,
-			false, nullptr, &sl});
+			s->voices, s->voices ? static_cast<const int32_t*>(s->d_voice_ids.ptr) : nullptr, &sl});
 	if (rc != GVTM_OK) return rc;
 	if (launched) *launched = true;
 	if ((e = hipDeviceSynchronize()) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");
@@ -1340,10 +1356,73 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	if (out_counts) std::copy(got.begin(), got.end(), out_counts);
 	if (maxabs && (e = hipMemcpy(maxabs, s->d_maxabs.ptr, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H maxabs");
 	for (size_t b = 0; b < batch; ++b) {
-		s->steps_done[b] += static_cast<uint64_t>(n_frames[b]) * k.control_steps;
+		s->steps_done[b] += static_cast<uint64_t>(n_frames[b]) * plan->voice(voice_of(s, b)).k.control_steps;
 		s->held[b].erase(s->held[b].begin(), s->held[b].begin() + static_cast<std::ptrdiff_t>(n_frames[b] * GVTM_N_PARAM));
 	}
 	return GVTM_OK;
+}
+
+// Host voice ids of gvtm_stream_create_voices / gvtm_stream_reset_voices: all of them in [0, n_voices), or the call is refused
+int check_voice_ids(const gvtm_plan* plan, const int32_t* voice_ids, size_t batch)
+{
+	for (size_t b = 0; b < batch; ++b) {
+		if (voice_ids[b] < 0 || voice_ids[b] >= plan->n_voices) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "utterance " + std::to_string(b) + ": voice id " + std::to_string(voice_ids[b]) + " outside [0, " +
+					std::to_string(plan->n_voices) + ")");
+		}
+	}
+	return GVTM_OK;
+}
+
+// gvtm_stream_create (voice_ids null) and gvtm_stream_create_voices on a plan of several voices.  The state stride and
+// the ring are sized for the largest voice of the plan, whichever voices the ids name, so that gvtm_stream_reset_voices
+// never reallocates.
+int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_stream** stream_out)
+{
+	try {
+		std::unique_ptr<gvtm_stream> s(new gvtm_stream);
+		s->plan = plan;
+		s->batch = batch;
+		s->voices = voice_ids != nullptr;
+		if (s->voices) s->voice_ids.assign(voice_ids, voice_ids + batch);
+		for (int v = 0; v < plan->n_voices; ++v) {
+			const gvtm::DeviceConstants& k = plan->voice(v).k;
+			if (plan->design.model5) {
+				// reference model 5: its own state block (vtm_kernels.hpp: Stream5Layout); the serial wavefronts work in blocks
+				// of four steps (vtm_kernel_m5.inc)
+				s->state_stride = gvtm::Stream5Layout::bytes();
+				s->granule_frames.push_back(4u / gcd_u(k.control_steps, 4u));
+			} else {
+				// each voice's ring is the one-row shape's, whatever shape a launch takes (the kernel derives it per voice)
+				const int xr = gvtm::synth_ring_length(k, plan->precision, 1);
+				s->xr = std::max(s->xr, xr);
+				s->state_stride = std::max(s->state_stride, gvtm::stream_state_bytes(k, plan->precision, xr));
+				// the serial wavefronts work in blocks of 2, 4 and 4 or 6 steps (vtm_kernel_v2.inc): their states are exact at
+				// multiples of 12 steps, so a push synthesizes a multiple of 12 / gcd(control_steps, 12) frames and keeps the rest
+				s->granule_frames.push_back(12u / gcd_u(k.control_steps, 12u));
+			}
+		}
+		s->held.resize(batch);
+		s->steps_done.assign(batch, 0);
+		DeviceScope scope(plan->device);
+		hipError_t e = scope.status();
+		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+		if ((e = s->d_state.ensure(s->state_stride * batch)) != hipSuccess) return fail_hip(e, "hipMalloc stream state");
+		if (s->voices) {
+			if ((e = s->d_voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) { s->d_state.release(); return fail_hip(e, "hipMalloc voice ids"); }
+			if ((e = hipMemcpy(s->d_voice_ids.ptr, voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
+				s->d_state.release();
+				s->d_voice_ids.release();
+				return fail_hip(e, "H2D voice ids");
+			}
+		}
+		const int rc = stream_upload_fresh_state(s.get());
+		if (rc != GVTM_OK) { s->d_state.release(); s->d_voice_ids.release(); return rc; }
+		*stream_out = s.release();
+		return GVTM_OK;
+	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
 }
 
 } // namespace
@@ -1356,37 +1435,18 @@ int gvtm_stream_create(gvtm_plan* plan, size_t batch, gvtm_stream** stream_out)
 	*stream_out = nullptr;
 	if (plan->n_voices > 1) return refuse_voices(plan, "gvtm_stream_create");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
-	try {
-		std::unique_ptr<gvtm_stream> s(new gvtm_stream);
-		s->plan = plan;
-		s->batch = batch;
-		const gvtm::DeviceConstants& k = plan->design.k;
-		if (plan->design.model5) {
-			// reference model 5: its own state block (vtm_kernels.hpp: Stream5Layout); the serial wavefronts work in blocks
-			// of four steps (vtm_kernel_m5.inc)
-			s->xr = 0;
-			s->state_stride = gvtm::Stream5Layout::bytes();
-			s->granule_frames = 4u / gcd_u(k.control_steps, 4u);
-		} else {
-			s->xr = gvtm::synth_ring_length(k, plan->precision, 1);
-			s->state_stride = gvtm::stream_state_bytes(k, plan->precision, s->xr);
-			// the serial wavefronts work in blocks of 2, 4 and 4 or 6 steps (vtm_kernel_v2.inc): their states are exact at
-			// multiples of 12 steps, so a push synthesizes a multiple of 12 / gcd(control_steps, 12) frames and keeps the rest
-			s->granule_frames = 12u / gcd_u(k.control_steps, 12u);
-		}
-		s->held.resize(batch);
-		s->steps_done.assign(batch, 0);
-		DeviceScope scope(plan->device);
-		hipError_t e = scope.status();
-		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-		if ((e = s->d_state.ensure(s->state_stride * batch)) != hipSuccess) return fail_hip(e, "hipMalloc stream state");
-		const int rc = stream_upload_fresh_state(s.get());
-		if (rc != GVTM_OK) { s->d_state.release(); return rc; }
-		*stream_out = s.release();
-		return GVTM_OK;
-	} catch (const std::bad_alloc&) {
-		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
-	}
+	return create_stream(plan, batch, nullptr, stream_out);
+}
+
+int gvtm_stream_create_voices(gvtm_plan* plan, const int32_t* voice_ids, size_t batch, gvtm_stream** stream_out)
+{
+	if (stream_out) *stream_out = nullptr;
+	if (!plan || !stream_out || !voice_ids || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan / stream_out / voice_ids or empty batch");
+	const int rc = check_voice_ids(plan, voice_ids, batch);
+	if (rc != GVTM_OK) return rc;
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	// (a plan of one voice: every id is 0, and the stream is the one gvtm_stream_create makes)
+	return create_stream(plan, batch, plan->n_voices > 1 ? voice_ids : nullptr, stream_out);
 }
 
 void gvtm_stream_destroy(gvtm_stream* s)
@@ -1395,6 +1455,7 @@ void gvtm_stream_destroy(gvtm_stream* s)
 	{
 		DeviceScope scope(s->plan->device);
 		s->d_state.release(); s->d_params.release(); s->d_frames.release(); s->d_audio.release(); s->d_counts.release(); s->d_maxabs.release();
+		s->d_voice_ids.release();
 	}
 	delete s;
 }
@@ -1410,13 +1471,39 @@ int gvtm_stream_reset(gvtm_stream* s)
 	return stream_upload_fresh_state(s);
 }
 
+int gvtm_stream_reset_voices(gvtm_stream* s, const int32_t* voice_ids)
+{
+	if (!s || !voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream or voice_ids");
+	const int rc = check_voice_ids(s->plan, voice_ids, s->batch);
+	if (rc != GVTM_OK) return rc;
+	// past the checks the stream takes the new ids; a device error from here on leaves it finished (pushes refused) until a
+	// reset succeeds, so that no push runs on half-reset state
+	if (s->voices) {
+		std::copy(voice_ids, voice_ids + s->batch, s->voice_ids.begin());
+		DeviceScope scope(s->plan->device);
+		// (the buffer holds batch ids since create: no reallocation)
+		const hipError_t e = scope.status() != hipSuccess ? scope.status()
+		                                                   : hipMemcpy(s->d_voice_ids.ptr, voice_ids, sizeof(int32_t) * s->batch, hipMemcpyHostToDevice);
+		if (e != hipSuccess) { s->finished = true; return fail_hip(e, "H2D voice ids"); }
+	}
+	const int rc_reset = gvtm_stream_reset(s);
+	if (rc_reset != GVTM_OK) s->finished = true;
+	return rc_reset;
+}
+
 size_t gvtm_stream_capacity(const gvtm_stream* s, size_t max_new_frames)
 {
 	if (!s) return static_cast<size_t>(-1);
-	const gvtm::DeviceConstants& k = s->plan->design.k;
-	// at most the new frames plus what a push can have kept (granule_frames frames), flushed, with the overrun's lap
-	const uint64_t steps = static_cast<uint64_t>(max_new_frames + s->granule_frames) * k.control_steps;
-	return static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, steps) + 1);
+	// the largest over the stream's voices: at most the new frames plus what a push can have kept (the voice's granule),
+	// flushed, with the overrun's lap
+	size_t m = 0;
+	for (int v = 0; v < s->plan->n_voices; ++v) {
+		if (s->voices && std::find(s->voice_ids.begin(), s->voice_ids.end(), v) == s->voice_ids.end()) continue;
+		const gvtm::DeviceConstants& k = s->plan->voice(v).k;
+		const uint64_t steps = static_cast<uint64_t>(max_new_frames + s->granule_frames[static_cast<size_t>(v)]) * k.control_steps;
+		m = std::max(m, static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, steps) + 1));
+	}
+	return m;
 }
 
 int gvtm_stream_push(gvtm_stream* s, const float* params, const int32_t* frame_counts, size_t max_frames,
@@ -1447,7 +1534,8 @@ int gvtm_stream_push(gvtm_stream* s, const float* params, const int32_t* frame_c
 			s->held[b].insert(s->held[b].end(), src, src + add * GVTM_N_PARAM);
 			const size_t have = s->held[b].size() / GVTM_N_PARAM;
 			// the last frame held is the look-ahead of the one before it (Controller.cpp:297-300 interpolates towards the NEXT frame)
-			n[b] = have > 0 ? ((have - 1) / s->granule_frames) * s->granule_frames : 0;
+			const unsigned granule = s->granule_frames[static_cast<size_t>(voice_of(s, b))];
+			n[b] = have > 0 ? ((have - 1) / granule) * granule : 0;
 		}
 		bool launched = false;
 		const int rc = stream_launch(s, n, false, audio, audio_stride, out_counts, nullptr, &launched);

@@ -114,8 +114,8 @@ struct Offsets {
 // template argument carries, besides the utterances per workgroup in bits 0-1, the flag kVoices5Flag (default off; one
 // utterance per workgroup only).  With it, workgroup g synthesizes utterance a.row_map[g] of voice a.group_voice[g] (-1: a
 // group past the last voice's, which exits at once) from that voice's constants a.kconst[voice] and a.k5const[voice].
-// Everything downstream reads the staged copies; only the utterance's rows in HBM (extent, frames, samples, count, peak)
-// follow the row map.  As in vtm_kernel_v2.inc (kVoicesFlag), each voice-dependent expression is a conditional on the
+// Everything downstream reads the staged copies; only the utterance's rows in HBM (extent, frames, samples, count, peak,
+// stream state) follow the row map.  As in vtm_kernel_v2.inc (kVoicesFlag), each voice-dependent expression is a conditional on the
 // constant VOICES, so the single-voice kernels compile to the code they had before the flag existed.
 constexpr int kVoices5Flag = 4;
 
@@ -220,10 +220,10 @@ __global__ __launch_bounds__((3 + (U_FLAGS & 3) + NH) * 64) void vtm5_synth_kern
 	// gvtm_stream_*: a launch continues utterances from the state an earlier launch left in device memory (a.stream,
 	// layout: Stream5Layout in vtm_kernels.hpp) and leaves its own behind.  A push synthesizes whole frames, keeps the
 	// converter's flush for later and finds the frame AFTER its last one in the buffer; finish (and the one-shot entry) flushes.
-	// (streams have one voice: the voice variant never streams)
-	const bool kPush = !VOICES && a.stream_mode == kStreamPush;
+	// (the voice variant streams too: every stream-state address follows the row map, GVTM_M5_UTT)
+	const bool kPush = a.stream_mode == kStreamPush;
 	const bool kFinal = !kPush;
-	const bool streaming = !VOICES && a.stream != nullptr;
+	const bool streaming = a.stream != nullptr;
 	if (tid < U) {
 		Extent e{0, 0, 0, 0, 0ull, 0ull};
 		const size_t ug = GVTM_M5_UTT(tid, group * U + tid);
@@ -253,8 +253,8 @@ __global__ __launch_bounds__((3 + (U_FLAGS & 3) + NH) * 64) void vtm5_synth_kern
 	if (streaming) {
 		// the two rings, and what the feed-forward halves of the filters need from the step before this launch's first one
 		for (int u = 0; u < U; ++u) {
-			if (group * U + u >= a.batch) break;
-			const unsigned char* sb = a.stream + (group * U + u) * a.stream_stride;
+			if (GVTM_M5_UTT(u, group * U + u) >= a.batch) break;
+			const unsigned char* sb = a.stream + GVTM_M5_UTT(u, (group * U + u)) * a.stream_stride;
 			const double* ring = reinterpret_cast<const double*>(sb + Stream5Layout::ring());
 			for (int i = tid; i < XR; i += kThreads) s_x[u * XR + i] = ring[i];
 			const float* yr = reinterpret_cast<const float*>(sb + Stream5Layout::yring());
@@ -741,22 +741,22 @@ __global__ __launch_bounds__((3 + (U_FLAGS & 3) + NH) * 64) void vtm5_synth_kern
 	}
 	// a stream's recurrence states as the previous launch left them (a fresh stream holds the values above and zeros)
 	if (streaming) {
-		if (role == 1 && lane < U && group * U + lane < a.batch) {
-			const double* sc = reinterpret_cast<const double*>(a.stream + (group * U + lane) * a.stream_stride + Stream5Layout::scalars());
+		if (role == 1 && lane < U && GVTM_M5_UTT(lane, group * U + lane) < a.batch) {
+			const double* sc = reinterpret_cast<const double*>(a.stream + GVTM_M5_UTT(lane, (group * U + lane)) * a.stream_stride + Stream5Layout::scalars());
 #pragma unroll
 			for (int i = 0; i < 9; ++i) st[i] = sc[kS5Scan + i];
-		} else if (role == 2 && lane < 2 * U && group * U + (lane >> 1) < a.batch) {
+		} else if (role == 2 && lane < 2 * U && GVTM_M5_UTT(lane >> 1, group * U + (lane >> 1)) < a.batch) {
 			// (lane u: glottal low-pass and band-pass memories of utterance u; lanes 2u, 2u + 1: its transmitted-flow memories)
-			const double* sc2 = reinterpret_cast<const double*>(a.stream + (group * U + (lane >> 1)) * a.stream_stride + Stream5Layout::scalars());
+			const double* sc2 = reinterpret_cast<const double*>(a.stream + GVTM_M5_UTT(lane >> 1, (group * U + (lane >> 1))) * a.stream_stride + Stream5Layout::scalars());
 			st[3] = sc2[kS5Fo + (lane & 1)];
-			if (lane < U && group * U + lane < a.batch) {
-				const double* sc = reinterpret_cast<const double*>(a.stream + (group * U + lane) * a.stream_stride + Stream5Layout::scalars());
+			if (lane < U && GVTM_M5_UTT(lane, group * U + lane) < a.batch) {
+				const double* sc = reinterpret_cast<const double*>(a.stream + GVTM_M5_UTT(lane, (group * U + lane)) * a.stream_stride + Stream5Layout::scalars());
 				st[0] = sc[kS5Gp];
 				st[1] = sc[kS5Bp];
 				st[2] = sc[kS5Bp + 1];
 			}
-		} else if (role == 0 && lane <= kNose && group * U + tube_u < a.batch) {
-			const double* tb = reinterpret_cast<const double*>(a.stream + (group * U + tube_u) * a.stream_stride + Stream5Layout::tube()) + lane * 4;
+		} else if (role == 0 && lane <= kNose && GVTM_M5_UTT(tube_u, group * U + tube_u) < a.batch) {
+			const double* tb = reinterpret_cast<const double*>(a.stream + GVTM_M5_UTT(tube_u, (group * U + tube_u)) * a.stream_stride + Stream5Layout::tube()) + lane * 4;
 #pragma unroll
 			for (int i = 0; i < 4; ++i) st[i] = tb[i];
 		}
@@ -1140,28 +1140,28 @@ __global__ __launch_bounds__((3 + (U_FLAGS & 3) + NH) * 64) void vtm5_synth_kern
 
 	// ---- a stream's states for the next launch
 	if (streaming) {
-		if (role == 1 && lane < U && group * U + lane < a.batch) {
-			double* sc = reinterpret_cast<double*>(a.stream + (group * U + lane) * a.stream_stride + Stream5Layout::scalars());
+		if (role == 1 && lane < U && GVTM_M5_UTT(lane, group * U + lane) < a.batch) {
+			double* sc = reinterpret_cast<double*>(a.stream + GVTM_M5_UTT(lane, (group * U + lane)) * a.stream_stride + Stream5Layout::scalars());
 #pragma unroll
 			for (int i = 0; i < 9; ++i) sc[kS5Scan + i] = st[i];
-		} else if (role == 2 && lane < 2 * U && group * U + (lane >> 1) < a.batch) {
-			double* sc2 = reinterpret_cast<double*>(a.stream + (group * U + (lane >> 1)) * a.stream_stride + Stream5Layout::scalars());
+		} else if (role == 2 && lane < 2 * U && GVTM_M5_UTT(lane >> 1, group * U + (lane >> 1)) < a.batch) {
+			double* sc2 = reinterpret_cast<double*>(a.stream + GVTM_M5_UTT(lane >> 1, (group * U + (lane >> 1))) * a.stream_stride + Stream5Layout::scalars());
 			sc2[kS5Fo + (lane & 1)] = st[3];
-			if (lane < U && group * U + lane < a.batch) {
-				double* sc = reinterpret_cast<double*>(a.stream + (group * U + lane) * a.stream_stride + Stream5Layout::scalars());
+			if (lane < U && GVTM_M5_UTT(lane, group * U + lane) < a.batch) {
+				double* sc = reinterpret_cast<double*>(a.stream + GVTM_M5_UTT(lane, (group * U + lane)) * a.stream_stride + Stream5Layout::scalars());
 				sc[kS5Gp] = st[0];
 				sc[kS5Bp] = st[1];
 				sc[kS5Bp + 1] = st[2];
 			}
-		} else if (role == 0 && lane <= kNose && group * U + tube_u < a.batch) {
-			double* tb = reinterpret_cast<double*>(a.stream + (group * U + tube_u) * a.stream_stride + Stream5Layout::tube()) + lane * 4;
+		} else if (role == 0 && lane <= kNose && GVTM_M5_UTT(tube_u, group * U + tube_u) < a.batch) {
+			double* tb = reinterpret_cast<double*>(a.stream + GVTM_M5_UTT(tube_u, (group * U + tube_u)) * a.stream_stride + Stream5Layout::tube()) + lane * 4;
 #pragma unroll
 			for (int i = 0; i < 4; ++i) tb[i] = st[i];
 		}
 		for (int u = 0; u < U; ++u) {
-			if (group * U + u >= a.batch) break;
+			if (GVTM_M5_UTT(u, group * U + u) >= a.batch) break;
 			const Extent e = s_ext[u];
-			unsigned char* sb = a.stream + (group * U + u) * a.stream_stride;
+			unsigned char* sb = a.stream + GVTM_M5_UTT(u, (group * U + u)) * a.stream_stride;
 			double* ring = reinterpret_cast<double*>(sb + Stream5Layout::ring());
 			for (int i = tid; i < XR; i += kThreads) ring[i] = s_x[u * XR + i];
 			float* yr = reinterpret_cast<float*>(sb + Stream5Layout::yring());

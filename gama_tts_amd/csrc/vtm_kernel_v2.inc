@@ -368,8 +368,8 @@ constexpr int serial_waves()
 // layout in bit 0, the flag kVoicesFlag (default off).  With it, workgroup g synthesizes the utterances
 // a.row_map[g * U .. g * U + U) (-1: an empty row, only ever at the end of a group) of voice a.group_voice[g] (-1: a group past
 // the last voice's, which exits at once), and that voice picks the constants a.kconst[voice], the wavetable at
-// a.wavetable + voice * 512 and the ring length; the LDS is sized for the longest ring of the launch (the ring is the last
-// region).  Without the flag every expression below is the one it was before the flag existed: each voice-dependent one is
+// a.wavetable + voice * 512 and the ring length (a stream's: that of the voice's single-voice stream); the LDS is sized for
+// the longest ring of the launch (the ring is the last region).  Without the flag every expression below is the one it was before the flag existed: each voice-dependent one is
 // a conditional on the constant VOICES whose voice arm the compiler never emits, so the single-voice kernels compile to
 // the same code.  (A separate bool parameter would rename every kernel, a wrapper kernel around an inlined body changes
 // what the register allocator spills: float, eight rows 476 -> 620 bytes of scratch.)
@@ -401,7 +401,9 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	// internal-rate ring length: a power of two >= 2 chunks + resampler history + flush zeros, checked by the host
 	// (v2_ring_length); 1024 = the reference's BUFFER_SIZE when down-sampling, which makes the ring alias exactly as
 	// the reference's does in its flush overrun (see the epilogue below)
-	const int XR = VOICES ? synth_ring_for(a.kconst[voice].upsampling, a.kconst[voice].pad, C) : a.xr;
+	// (several voices in a stream: each voice's ring is its single-voice stream's, whatever this launch's shape --
+	// a.stream_chunk is the one-row shape's chunk, which fixes that ring)
+	const int XR = VOICES ? synth_ring_for(a.kconst[voice].upsampling, a.kconst[voice].pad, a.stream ? a.stream_chunk : C) : a.xr;
 	const int XRS = XR + kXMirror; // samples from one utterance's ring to the next one's (ring + mirror)
 	static_assert(NH >= 1, "at least one helper wavefront");
 	constexpr int kThreads = (kSerial + NH) * 64;

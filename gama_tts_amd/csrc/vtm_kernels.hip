@@ -118,7 +118,8 @@ constexpr int wide_helpers()
 }
 
 // VOICES: a launch of several voices (the kernel's kVoicesFlag; args.row_map is set); `batch` is then the number of
-// workgroups, and args.xr the longest ring of the launch's voices (what the LDS is sized for)
+// workgroups, and args.xr the longest ring of the launch's voices (what the LDS is sized for; a stream's: of the voices'
+// stream rings, which args.stream_chunk fixes)
 template <typename CT, typename ST, int D, int U, int LAYOUT, bool VOICES>
 static hipError_t launch_v2(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
@@ -193,9 +194,14 @@ static ShapeNumbers shape_numbers(int precision, int rows, int delay, int layout
 	return v2_numbers_rows<double, double, 1>(rows, layout);
 }
 
+int synth_chunk_length(const DeviceConstants& k, int precision, int rows)
+{
+	return shape_numbers(precision, rows, k.section_delay, k.layout).chunk;
+}
+
 int synth_ring_length(const DeviceConstants& k, int precision, int rows)
 {
-	return ring_length(k, shape_numbers(precision, rows, k.section_delay, k.layout).chunk);
+	return ring_length(k, synth_chunk_length(k, precision, rows));
 }
 
 size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr)

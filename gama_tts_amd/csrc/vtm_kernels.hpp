@@ -95,6 +95,10 @@ struct SynthArgs {
 	// kconst and k5const) then hold one block per voice
 	const int32_t* row_map = nullptr;     // [groups][rows] utterance of each workgroup row, -1 = none
 	const int32_t* group_voice = nullptr; // [groups] voice of each workgroup, -1 = none (the workgroup exits)
+	// several voices in a stream (v2 kernel): the chunk that fixes each voice's ring, synth_ring_for(its upsampling, its
+	// pad, stream_chunk) -- the one-row shape's, so that every launch shape keeps the ring a single-voice stream of that
+	// voice has
+	int stream_chunk = 0;
 };
 
 struct GroupVoicesArgs {
@@ -128,9 +132,11 @@ int synth_rows(int precision, size_t batch, int requested, int section_delay = 1
 // overrun aliases as the reference's ring does; otherwise the smallest power of two holding two chunks, the
 // resampler's history and the flush zeros
 int synth_ring_length(const DeviceConstants& k, int precision, int rows);
+// the chunk length (internal steps per tick) of that shape, which synth_ring_length follows
+int synth_chunk_length(const DeviceConstants& k, int precision, int rows);
 size_t synth_lds_bytes(const DeviceConstants& k, int precision, int rows, int xr = 0 /* 0: the shape's own ring length */);
 // batch: utterances, or with args.row_map set (several voices) the workgroups of launch_group_voices' map, of one voice
-// each (args.xr: the longest ring of the voices)
+// each (args.xr: the longest ring of the voices; a stream's rings follow args.stream_chunk)
 hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream);
 // bytes of one utterance's stream state for a plan (ring length of the one-row shape: streams whose utterances are not in
 // lockstep run one utterance per workgroup, and every shape of a stream uses that ring length)

@@ -271,8 +271,9 @@ int gvtm_synthesize_batch_host_pcm16(gvtm_plan* plan, const float* params, const
  * and (GVTM_PRECISION_F32) one noise-sample table for all of them.  n_voices == 1 makes exactly the plan gvtm_plan_create
  * makes.  GVTM_DEVICE_NONE works as for gvtm_plan_create.  A plan of two or more voices refuses the single-voice
  * entry points (gvtm_synthesize_batch_*, gvtm_stream_create, gvtm_synthesize_events_device) with
- * GVTM_ERR_INVALID_ARGUMENT; gvtm_plan_info, gvtm_output_count and gvtm_output_capacity describe voice 0.  Reference
- * model 5 has an entry of its own, gvtm_plan_create_model5_voices. */
+ * GVTM_ERR_INVALID_ARGUMENT; gvtm_plan_info, gvtm_output_count and gvtm_output_capacity describe voice 0.  Its streams
+ * come from gvtm_stream_create_voices ("Streams" below).  Reference model 5 has an entry of its own,
+ * gvtm_plan_create_model5_voices. */
 int    gvtm_plan_create_voices(const gvtm_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out);
 /* The same for reference model 5: configs[n_voices], one gvtm5_config per voice (the 5_male voice's variants, say).
  * output_rate and precision (GVTM_PRECISION_F64) must be equal across configs (else GVTM_ERR_INVALID_ARGUMENT); every
@@ -338,12 +339,32 @@ void gvtm_host_free(void* ptr);
  * workgroup takes one utterance.  Plans of reference model 5 have streams too (vtm/VocalTractModel5.h:523-579: its scans,
  * filter memories, section flows, radiation-impedance memories, converter ring and the difference filter's look-back are
  * the state; pushes go in multiples of four internal steps).
+ *
+ * A plan of several voices has streams of gvtm_stream_create_voices: utterance b is spoken by voice voice_ids[b], and its
+ * samples, counts and maxabs are, bit for bit and in every precision, those of a gvtm_stream_create stream on a
+ * single-voice plan of that voice pushed with the same frames.  Each voice keeps its own granule of frames per push and
+ * its own converter ring; lockstep is judged per voice (a workgroup only ever holds utterances of one voice), and model 5
+ * runs one utterance per workgroup.  push, finish, reset and destroy take such a stream as they are; its capacity is the
+ * largest over its voices.  Each launch first runs the grouping kernel of gvtm_synthesize_voices_device with the plan's
+ * scratch: stream calls and gvtm_synthesize_voices_device calls on one plan must not overlap.
  */
 typedef struct gvtm_stream gvtm_stream;
 
 int gvtm_stream_create(gvtm_plan* plan, size_t batch, gvtm_stream** stream_out);
+/* A stream over a plan of one or more voices: utterance b is spoken by voice voice_ids[b] (host array of `batch`).
+ * Refused with GVTM_ERR_INVALID_ARGUMENT for a null plan, stream_out or voice_ids or an empty batch, then for any id
+ * outside [0, n_voices) (the message names the first such utterance; the ids are host memory, so the whole call is
+ * refused), then with GVTM_ERR_NO_DEVICE for a design-only plan.  The state is sized for the plan's largest voice, so
+ * that gvtm_stream_reset_voices never reallocates.  On a plan of one voice it is the stream gvtm_stream_create makes. */
+int gvtm_stream_create_voices(gvtm_plan* plan, const int32_t* voice_ids, size_t batch, gvtm_stream** stream_out);
 void gvtm_stream_destroy(gvtm_stream* stream);
+/* (a stream of several voices keeps its voice ids) */
 int gvtm_stream_reset(gvtm_stream* stream);
+/* gvtm_stream_reset, then the utterances take new voices: voice_ids [batch] (host), checked as gvtm_stream_create_voices
+ * checks them; a call refused for its arguments leaves the stream unchanged.  A device error after the checks leaves the
+ * stream with the new ids, finished (pushes refused) until a reset succeeds.  A server reusing its utterance slots for
+ * new clients. */
+int gvtm_stream_reset_voices(gvtm_stream* stream, const int32_t* voice_ids);
 /* Samples per utterance that a push of at most max_new_frames frames, or the finish after it, can return: the
  * audio_stride to allocate. */
 size_t gvtm_stream_capacity(const gvtm_stream* stream, size_t max_new_frames);
