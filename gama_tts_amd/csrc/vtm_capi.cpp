@@ -635,6 +635,8 @@ int gvtm_generate_tracks_device(int device, const gvtm_track_config* config, con
 	if (why[0]) return fail(GVTM_ERR_INVALID_ARGUMENT, why);
 	if (batch == 0) return GVTM_OK;
 	if (!d_events) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events");
+	// frames leave the kernel as float4 stores
+	if (reinterpret_cast<uintptr_t>(d_params) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params must be 16-byte aligned");
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(GVTM_ERR_NO_DEVICE, "no HIP device available (track generation has no CPU path)");
 	if (device < 0 || device >= n) return fail(GVTM_ERR_NO_DEVICE, "device index out of range");

@@ -44,7 +44,8 @@ __device__ __forceinline__ double column(const gvtm_event* e, int c)
 
 constexpr int kRingFrames = 32;   // frames collected in LDS before they leave as one 2 KB store
 constexpr int kTableEvents = 240; // event lists up to this length get a "next event that sets column c" table in LDS
-constexpr int kFar = 255;         // table entry: no event within 254 sets the column
+constexpr int kFar = 255;         // table entry: no later event of the list sets the column
+static_assert(kTableEvents < kFar, "every distance inside a tabled list fits below kFar");
 
 // What the boundary at which `target` becomes T looks at, requested one boundary earlier (nothing in the walker wavefront
 // stores to memory, so these loads are waited for exactly where they are used -- a whole inter-event gap later).
@@ -135,11 +136,9 @@ __device__ __forceinline__ void tracks_row(const TrackArgs& a, size_t utt, int l
 	// first event >= q that sets column c of my lane (c = j: parameter, 16 + j: special), n_events if none; the reference
 	// walks there event by event (:1037-1046, :1055-1064), and so does this for lists too long for the table
 	auto first_set = [&](int64_t q, int c) -> int64_t {
-		if (tabled) {
+		if (tabled) { // a tabled list has at most kTableEvents < kFar events: kFar can only mean "none"
 			const int d = ahead[q][c];
-			if (d < kFar) return q + d;
-			q += kFar - 1; // nothing in [q, q + 254): on from there
-			if (q >= n_events) return n_events;
+			return d < kFar ? q + d : n_events;
 		}
 		while (q < n_events && is_empty(column(ev + q, c))) ++q;
 		return q;

@@ -434,7 +434,8 @@ size_t gvtm_tracks_frame_count(const gvtm_track_config* config, const gvtm_event
  * Batch generation, everything resident in device memory.
  *   d_events        all utterances' events back to back
  *   d_event_offsets [batch + 1] int64: utterance b owns events [offsets[b], offsets[b+1])
- *   d_params        [batch][max_frames][16] float32 out; frames beyond max_frames are dropped
+ *   d_params        [batch][max_frames][16] float32 out, 16-byte aligned (the frames leave as 16-byte stores;
+ *                   GVTM_ERR_INVALID_ARGUMENT otherwise); frames beyond max_frames are dropped
  *   d_frame_counts  [batch] int32 out: frames generateOutput() produces (may exceed max_frames), may be NULL
  *   d_drift         [batch] in/out drift-generator states, or NULL: a fresh generator per utterance
  * d_params / d_frame_counts are exactly what gvtm_synthesize_batch_device() takes.
