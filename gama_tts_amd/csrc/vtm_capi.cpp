@@ -9,6 +9,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/gama_vtm.h"
@@ -32,29 +33,54 @@ int fail_hip(hipError_t e, const char* what)
 	return fail(GVTM_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// Device memory with one owner, grown on demand; freed when the owner goes
 struct DeviceBuffer {
 	void* ptr = nullptr;
 	size_t bytes = 0;
+	DeviceBuffer() = default;
+	DeviceBuffer(DeviceBuffer&& o) noexcept : ptr(std::exchange(o.ptr, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+	DeviceBuffer& operator=(DeviceBuffer&& o) noexcept
+	{
+		std::swap(ptr, o.ptr);
+		std::swap(bytes, o.bytes);
+		return *this;
+	}
+	~DeviceBuffer()
+	{
+		if (ptr) (void) hipFree(ptr);
+	}
 	hipError_t ensure(size_t need)
 	{
 		if (need <= bytes) return hipSuccess;
-		if (ptr) (void) hipFree(ptr);
-		ptr = nullptr;
-		bytes = 0;
+		*this = DeviceBuffer(); // (the old memory goes before the new is taken)
 		hipError_t e = hipMalloc(&ptr, need);
 		if (e == hipSuccess) bytes = need;
 		return e;
 	}
-	void release()
-	{
-		if (ptr) (void) hipFree(ptr);
-		ptr = nullptr;
-		bytes = 0;
-	}
 };
 
+// A HIP stream or event with one owner, destroyed when the owner goes
+template <typename H, hipError_t (*Destroy)(H)>
+struct Owned {
+	H h = nullptr;
+	Owned() = default;
+	Owned(Owned&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+	Owned& operator=(Owned&& o) noexcept
+	{
+		std::swap(h, o.h);
+		return *this;
+	}
+	~Owned()
+	{
+		if (h) (void) Destroy(h);
+	}
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+
+// the two events around a timed launch: in the plan's pool, pending until gvtm_plan_take_kernel_ms, or destroyed
 struct EventPair {
-	hipEvent_t start = nullptr, stop = nullptr;
+	Event start, stop;
 };
 
 // Makes the plan's device current for the duration of an entry point and gives the caller's device back afterwards.
@@ -86,30 +112,31 @@ private:
 #endif
 
 struct gvtm_plan {
-	gvtm::Design design;
-	// a plan of several voices (gvtm_plan_create_voices): `design` is voice 0, voices[v - 1] voice v; d_consts and
-	// d_wavetable then hold one block per voice, the FIR and the converter's tables (the same for every voice) one
-	int n_voices = 1;
-	std::vector<gvtm::Design> voices;
+	// one design per voice, voice 0 first (gvtm_plan_create_voices: several); d_consts, d_consts5 and d_wavetable hold one
+	// block per voice, the FIR and the converter's tables (the same for every voice) one
+	std::vector<gvtm::Design> designs;
 	int device = 0;
 	int precision = GVTM_PRECISION_F64;
 	int rows = 0;       // utterances per workgroup; 0 = by batch size (a diagnostics build can force it)
 	// design tables on the device: double, or float (as designed) for GVTM_PRECISION_F32
-	void* d_wavetable = nullptr;
-	void* d_fir = nullptr;
-	void* d_src_h = nullptr;
-	void* d_src_dh = nullptr;
+	DeviceBuffer d_wavetable, d_fir, d_src_h, d_src_dh;
+	DeviceBuffer d_consts, d_consts5; // gvtm::DeviceConstants, gvtm::Model5Constants (model 5 plans only)
 	// the noise source's samples by internal step (the same for every utterance), grown on demand; superseded buffers stay
-	// allocated until the plan goes (a launch in flight on the caller's stream may still read them)
-	void* d_noise = nullptr;
+	// allocated until the plan goes (a launch in flight on the caller's stream may still read them; the growth is
+	// geometric, so together they are smaller than the live one)
+	DeviceBuffer d_noise;
 	size_t noise_len = 0;
-	std::vector<void*> noise_retired;
-	gvtm::DeviceConstants* d_consts = nullptr;
-	gvtm::Model5Constants* d_consts5 = nullptr; // model 5 plans only
-	// staging for the host-buffer entry point
-	DeviceBuffer s_params, s_frames, s_audio, s_counts, s_maxabs, s_pcm, s_scales;
-	// launches of several voices: the voice ids of the host entries, the row map / group voices / sort counts
-	DeviceBuffer s_voice_ids, s_groups;
+	std::vector<DeviceBuffer> noise_retired;
+	// scratch, one set per user, so that no call overwrites what another call's queued kernels still read:
+	// the host entries' staging and grouping (each call drains its own streams before it returns) ...
+	struct {
+		DeviceBuffer params, frames, audio, counts, maxabs, pcm, scales, voice_ids, groups;
+	} host;
+	// ... and the enqueue-only entries' (gvtm_synthesize_events_device's frames and frame counts, the grouping of
+	// gvtm_synthesize_voices_device): calls to those on one plan must be ordered on one stream
+	struct {
+		DeviceBuffer params, frames, groups;
+	} async;
 	int compute_units = 0; // of the plan's device (the host entries cut big batches into slices that fill them once)
 	// kernel timing (HIP events on the launch stream)
 	bool timing = false;
@@ -118,59 +145,31 @@ struct gvtm_plan {
 	std::vector<EventPair> pending;
 	std::vector<EventPair> pool;
 	// host-buffer entries: frames in on one stream, kernels on a second, samples out on a third (created on first use)
-	hipStream_t h2d_stream = nullptr, compute_stream = nullptr, copy_stream = nullptr;
-	std::vector<hipEvent_t> slice_done; // two per slice: frames arrived, samples ready
-	// model 5: utterances per workgroup.  One, whatever the batch: the two-utterance shape (two tube wavefronts, chunk of 24
-	// steps -- what LDS holds of the 62-entry tube records) measured SLOWER at every batch size (batch 512 x 250 frames:
-	// 17.3 ms against 2 x 6.97 ms; profiles/r03_role_cycles_m5.txt): the passes are latency-bound, so a chunk of 24 steps
-	// costs what one of 60 does, and the tube wavefronts slow down from 268 to 430 cycles per step next to five busy
-	// helpers.  A diagnostics build can still force it (tests hold it to the one-utterance shape's samples bit for bit).
-	int rows5_for(size_t) const { return rows == 2 ? 2 : 1; }
-	const gvtm::Design& voice(int v) const { return v == 0 ? design : voices[static_cast<size_t>(v) - 1]; }
+	Stream h2d_stream, compute_stream, copy_stream;
+	std::vector<Event> slice_done; // two per slice: frames arrived, samples ready
+
+	int n_voices() const { return static_cast<int>(designs.size()); }
+	// utterances per workgroup of a launch of `batch` utterances.  Model 5: one, whatever the batch: the two-utterance shape
+	// (two tube wavefronts, chunk of 24 steps -- what LDS holds of the 62-entry tube records) measured SLOWER at every batch
+	// size (batch 512 x 250 frames: 17.3 ms against 2 x 6.97 ms; profiles/r03_role_cycles_m5.txt): the passes are
+	// latency-bound, so a chunk of 24 steps costs what one of 60 does, and the tube wavefronts slow down from 268 to 430
+	// cycles per step next to five busy helpers.  A diagnostics build can still force it (tests hold it to the
+	// one-utterance shape's samples bit for bit).
+	int rows_for(size_t batch) const
+	{
+		const gvtm::Design& dg = designs[0];
+		return dg.model5 ? (rows == 2 ? 2 : 1) : gvtm::synth_rows(precision, batch, rows, dg.k.section_delay);
+	}
 };
 
 namespace {
 
-template <typename P, typename T>
-hipError_t upload(P** dst, const std::vector<T>& src)
+template <typename T>
+hipError_t upload(DeviceBuffer& dst, const std::vector<T>& src)
 {
-	hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), sizeof(T) * src.size());
+	hipError_t e = dst.ensure(sizeof(T) * src.size());
 	if (e != hipSuccess) return e;
-	return hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice);
-}
-
-void free_plan(gvtm_plan* p)
-{
-	if (!p) return;
-	if (p->device == GVTM_DEVICE_NONE) {
-		delete p;
-		return;
-	}
-	DeviceScope scope(p->device);
-	if (p->d_wavetable) (void) hipFree(p->d_wavetable);
-	if (p->d_fir) (void) hipFree(p->d_fir);
-	if (p->d_src_h) (void) hipFree(p->d_src_h);
-	if (p->d_src_dh) (void) hipFree(p->d_src_dh);
-	if (p->d_noise) (void) hipFree(p->d_noise);
-	for (void* q : p->noise_retired) (void) hipFree(q);
-	if (p->d_consts) (void) hipFree(p->d_consts);
-	if (p->d_consts5) (void) hipFree(p->d_consts5);
-	p->s_params.release();
-	p->s_frames.release();
-	p->s_audio.release();
-	p->s_counts.release();
-	p->s_maxabs.release();
-	p->s_pcm.release();
-	p->s_scales.release();
-	p->s_voice_ids.release();
-	p->s_groups.release();
-	if (p->h2d_stream) (void) hipStreamDestroy(p->h2d_stream);
-	if (p->compute_stream) (void) hipStreamDestroy(p->compute_stream);
-	if (p->copy_stream) (void) hipStreamDestroy(p->copy_stream);
-	for (hipEvent_t ev : p->slice_done) (void) hipEventDestroy(ev);
-	for (auto& ev : p->pending) { (void) hipEventDestroy(ev.start); (void) hipEventDestroy(ev.stop); }
-	for (auto& ev : p->pool) { (void) hipEventDestroy(ev.start); (void) hipEventDestroy(ev.stop); }
-	delete p;
+	return hipMemcpy(dst.ptr, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice);
 }
 
 } // namespace
@@ -225,124 +224,91 @@ int open_device(gvtm_plan* plan, int device)
 	return GVTM_OK;
 }
 
-// gvtm_plan_create (n_voices == 1) and gvtm_plan_create_voices
-int create_plan(const gvtm_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
+// The device tables of a plan of the models 0 and 1: one wavetable and one constants block per voice, back to back (the
+// glottal FIR and the converter's tables depend on no configuration key: voice 0's serve all)
+int upload_tables(gvtm_plan* plan)
+{
+	std::vector<gvtm::DeviceConstants> consts;
+	std::vector<double> wavetables;
+	std::vector<float> wavetables_f;
+	for (const gvtm::Design& dv : plan->designs) {
+		consts.push_back(dv.k);
+		wavetables.insert(wavetables.end(), dv.wavetable.begin(), dv.wavetable.end());
+		wavetables_f.insert(wavetables_f.end(), dv.wavetable_f.begin(), dv.wavetable_f.end());
+	}
+	const gvtm::Design& dg = plan->designs[0];
+	hipError_t e;
+	if (dg.f32) {
+		if ((e = upload(plan->d_wavetable, wavetables_f)) != hipSuccess) return fail_hip(e, "upload wavetable");
+		if ((e = upload(plan->d_fir, dg.fir_f)) != hipSuccess) return fail_hip(e, "upload fir");
+		if ((e = upload(plan->d_src_h, dg.src_h_f)) != hipSuccess) return fail_hip(e, "upload src_h");
+		if ((e = upload(plan->d_src_dh, dg.src_dh_f)) != hipSuccess) return fail_hip(e, "upload src_dh");
+	} else {
+		if ((e = upload(plan->d_wavetable, wavetables)) != hipSuccess) return fail_hip(e, "upload wavetable");
+		if ((e = upload(plan->d_fir, dg.fir)) != hipSuccess) return fail_hip(e, "upload fir");
+		if ((e = upload(plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
+		if ((e = upload(plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
+	}
+	if ((e = upload(plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
+	return GVTM_OK;
+}
+
+// Model 5's: one constants block of each kind per voice, back to back (the converter's tables depend on no configuration
+// key: voice 0's serve all)
+int upload_tables5(gvtm_plan* plan)
+{
+	std::vector<gvtm::DeviceConstants> consts;
+	std::vector<gvtm::Model5Constants> consts5;
+	for (const gvtm::Design& dv : plan->designs) {
+		consts.push_back(dv.k);
+		consts5.push_back(dv.k5);
+	}
+	const gvtm::Design& dg = plan->designs[0];
+	hipError_t e;
+	if ((e = upload(plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
+	if ((e = upload(plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
+	if ((e = upload(plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
+	if ((e = upload(plan->d_consts5, consts5)) != hipSuccess) return fail_hip(e, "upload model 5 constants");
+	return GVTM_OK;
+}
+
+// Every plan: `differs` refuses a voice that does not share `shared_keys` with voice 0, `design` designs each voice, and
+// `upload` puts the tables on the device (gvtm_config: design_plan and upload_tables, gvtm5_config: design_plan5 and
+// upload_tables5)
+template <typename Config, typename Differs>
+int create_plan(const Config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out, const char* shared_keys,
+		Differs differs, std::string (*design)(const Config&, double, gvtm::Design&), int (*upload)(gvtm_plan*))
 {
 	if (!configs || !plan_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null config or plan_out");
 	*plan_out = nullptr;
 	if (n_voices == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "a plan needs at least one voice");
 	if (n_voices > 0x7fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "too many voices");
 	for (size_t v = 1; v < n_voices; ++v) {
-		const gvtm_config& c0 = configs[0];
-		const gvtm_config& c = configs[v];
-		if (c.output_rate != c0.output_rate || c.section_delay != c0.section_delay || c.precision != c0.precision || c.tube_layout != c0.tube_layout) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "voice " + std::to_string(v) + ": output_rate, section_delay, precision and tube_layout must be "
-					"those of voice 0 (one plan is one model at one output rate)");
+		if (differs(configs[0], configs[v])) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "voice " + std::to_string(v) + ": " + shared_keys + " must be those of voice 0 "
+					"(one plan is one model at one output rate)");
 		}
 	}
 	try {
-		std::unique_ptr<gvtm_plan, void (*)(gvtm_plan*)> plan(new gvtm_plan, free_plan);
-		const std::string why = gvtm::design_plan(configs[0], control_rate, plan->design);
-		if (!why.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, n_voices > 1 ? "voice 0: " + why : why);
-		plan->precision = configs[0].precision;
-		plan->n_voices = static_cast<int>(n_voices);
-		plan->voices.resize(n_voices - 1);
-		for (size_t v = 1; v < n_voices; ++v) {
-			const std::string why_v = gvtm::design_plan(configs[v], control_rate, plan->voices[v - 1]);
-			if (!why_v.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice " + std::to_string(v) + ": " + why_v);
+		std::unique_ptr<gvtm_plan, void (*)(gvtm_plan*)> plan(new gvtm_plan, gvtm_plan_destroy);
+		plan->designs.resize(n_voices);
+		for (size_t v = 0; v < n_voices; ++v) {
+			const std::string why = design(configs[v], control_rate, plan->designs[v]);
+			if (!why.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, n_voices > 1 ? "voice " + std::to_string(v) + ": " + why : why);
 		}
-
+		plan->precision = configs[0].precision; // (model 5: fp64, the only precision its design takes)
 		if (device == GVTM_DEVICE_NONE) {
 			// design-only plan: info, tables and output counts work, synthesis reports NO_DEVICE
 			plan->device = GVTM_DEVICE_NONE;
 			*plan_out = plan.release();
 			return GVTM_OK;
 		}
-		const int rc = open_device(plan.get(), device);
+		int rc = open_device(plan.get(), device);
 		if (rc != GVTM_OK) return rc;
 		DeviceScope scope(device);
 		hipError_t e = scope.status();
 		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-		const gvtm::Design& dg = plan->design;
-		// one wavetable and one constants block per voice, back to back (the glottal FIR and the converter's tables depend
-		// on no configuration key: voice 0's serve all)
-		std::vector<gvtm::DeviceConstants> consts;
-		std::vector<double> wavetables;
-		std::vector<float> wavetables_f;
-		for (size_t v = 0; v < n_voices; ++v) {
-			const gvtm::Design& dv = plan->voice(static_cast<int>(v));
-			consts.push_back(dv.k);
-			wavetables.insert(wavetables.end(), dv.wavetable.begin(), dv.wavetable.end());
-			wavetables_f.insert(wavetables_f.end(), dv.wavetable_f.begin(), dv.wavetable_f.end());
-		}
-		if (dg.f32) {
-			if ((e = upload(&plan->d_wavetable, wavetables_f)) != hipSuccess) return fail_hip(e, "upload wavetable");
-			if ((e = upload(&plan->d_fir, dg.fir_f)) != hipSuccess) return fail_hip(e, "upload fir");
-			if ((e = upload(&plan->d_src_h, dg.src_h_f)) != hipSuccess) return fail_hip(e, "upload src_h");
-			if ((e = upload(&plan->d_src_dh, dg.src_dh_f)) != hipSuccess) return fail_hip(e, "upload src_dh");
-		} else {
-			if ((e = upload(&plan->d_wavetable, wavetables)) != hipSuccess) return fail_hip(e, "upload wavetable");
-			if ((e = upload(&plan->d_fir, dg.fir)) != hipSuccess) return fail_hip(e, "upload fir");
-			if ((e = upload(&plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
-			if ((e = upload(&plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
-		}
-		if ((e = upload(&plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
-		*plan_out = plan.release();
-		return GVTM_OK;
-	} catch (const std::bad_alloc&) {
-		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
-	} catch (const std::exception& ex) {
-		return fail(GVTM_ERR_INVALID_ARGUMENT, ex.what());
-	}
-}
-
-// gvtm_plan_create_model5 (n_voices == 1) and gvtm_plan_create_model5_voices
-int create_plan5(const gvtm5_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
-{
-	if (!configs || !plan_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null config or plan_out");
-	*plan_out = nullptr;
-	if (n_voices == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "a plan needs at least one voice");
-	if (n_voices > 0x7fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "too many voices");
-	for (size_t v = 1; v < n_voices; ++v) {
-		if (configs[v].output_rate != configs[0].output_rate || configs[v].precision != configs[0].precision) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "voice " + std::to_string(v) + ": output_rate and precision must be those of voice 0 "
-					"(one plan is one model at one output rate)");
-		}
-	}
-	try {
-		std::unique_ptr<gvtm_plan, void (*)(gvtm_plan*)> plan(new gvtm_plan, free_plan);
-		const std::string why = gvtm::design_plan5(configs[0], control_rate, plan->design);
-		if (!why.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, n_voices > 1 ? "voice 0: " + why : why);
-		plan->precision = GVTM_PRECISION_F64;
-		plan->n_voices = static_cast<int>(n_voices);
-		plan->voices.resize(n_voices - 1);
-		for (size_t v = 1; v < n_voices; ++v) {
-			const std::string why_v = gvtm::design_plan5(configs[v], control_rate, plan->voices[v - 1]);
-			if (!why_v.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice " + std::to_string(v) + ": " + why_v);
-		}
-		if (device == GVTM_DEVICE_NONE) {
-			plan->device = GVTM_DEVICE_NONE;
-			*plan_out = plan.release();
-			return GVTM_OK;
-		}
-		const int rc = open_device(plan.get(), device);
-		if (rc != GVTM_OK) return rc;
-		DeviceScope scope(device);
-		hipError_t e = scope.status();
-		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-		// one constants block of each kind per voice, back to back (the converter's tables depend on no configuration
-		// key: voice 0's serve all)
-		std::vector<gvtm::DeviceConstants> consts;
-		std::vector<gvtm::Model5Constants> consts5;
-		for (size_t v = 0; v < n_voices; ++v) {
-			consts.push_back(plan->voice(static_cast<int>(v)).k);
-			consts5.push_back(plan->voice(static_cast<int>(v)).k5);
-		}
-		const gvtm::Design& dg = plan->design;
-		if ((e = upload(&plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
-		if ((e = upload(&plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
-		if ((e = upload(&plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
-		if ((e = upload(&plan->d_consts5, consts5)) != hipSuccess) return fail_hip(e, "upload model 5 constants");
+		if ((rc = upload(plan.get())) != GVTM_OK) return rc;
 		*plan_out = plan.release();
 		return GVTM_OK;
 	} catch (const std::bad_alloc&) {
@@ -355,7 +321,7 @@ int create_plan5(const gvtm5_config* configs, size_t n_voices, double control_ra
 // The single-voice entry points on a plan of several voices: which voice would they synthesize?
 int refuse_voices(const gvtm_plan* plan, const char* entry)
 {
-	return fail(GVTM_ERR_INVALID_ARGUMENT, std::string(entry) + ": the plan has " + std::to_string(plan->n_voices) +
+	return fail(GVTM_ERR_INVALID_ARGUMENT, std::string(entry) + ": the plan has " + std::to_string(plan->n_voices()) +
 			" voices; use gvtm_synthesize_voices_* (one voice id per utterance)");
 }
 
@@ -397,61 +363,72 @@ extern "C" {
 
 int gvtm_plan_create(const gvtm_config* config, double control_rate, int device, gvtm_plan** plan_out)
 {
-	return create_plan(config, 1, control_rate, device, plan_out);
+	return gvtm_plan_create_voices(config, 1, control_rate, device, plan_out);
 }
 
 int gvtm_plan_create_voices(const gvtm_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
 {
-	return create_plan(configs, n_voices, control_rate, device, plan_out);
+	auto differs = [](const gvtm_config& c0, const gvtm_config& c) {
+		return c.output_rate != c0.output_rate || c.section_delay != c0.section_delay || c.precision != c0.precision || c.tube_layout != c0.tube_layout;
+	};
+	return create_plan(configs, n_voices, control_rate, device, plan_out, "output_rate, section_delay, precision and tube_layout", differs,
+			gvtm::design_plan, upload_tables);
 }
 
 int gvtm_plan_voice_count(const gvtm_plan* plan)
 {
 	if (!plan) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
-	return plan->n_voices;
+	return plan->n_voices();
 }
 
 int gvtm_plan_voice_info(const gvtm_plan* plan, int voice, gvtm_info* info)
 {
 	if (!plan || !info) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or info");
-	if (voice < 0 || voice >= plan->n_voices) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice index out of range");
-	fill_info(plan, plan->voice(voice), info);
+	if (voice < 0 || voice >= plan->n_voices()) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice index out of range");
+	fill_info(plan, plan->designs[voice], info);
 	return GVTM_OK;
 }
 
 size_t gvtm_voice_output_count(const gvtm_plan* plan, int voice, size_t n_frames)
 {
-	if (!plan || voice < 0 || voice >= plan->n_voices) return static_cast<size_t>(-1);
-	return design_output_count(plan->voice(voice), n_frames);
+	if (!plan || voice < 0 || voice >= plan->n_voices()) return static_cast<size_t>(-1);
+	return design_output_count(plan->designs[voice], n_frames);
 }
 
 size_t gvtm_voices_output_capacity(const gvtm_plan* plan, size_t max_frames)
 {
 	if (!plan) return static_cast<size_t>(-1);
 	size_t m = 0;
-	for (int v = 0; v < plan->n_voices; ++v) m = std::max(m, design_output_capacity(plan->voice(v), max_frames));
+	for (int v = 0; v < plan->n_voices(); ++v) m = std::max(m, design_output_capacity(plan->designs[v], max_frames));
 	return m;
 }
 
 int gvtm_plan_create_model5(const gvtm5_config* config, double control_rate, int device, gvtm_plan** plan_out)
 {
-	return create_plan5(config, 1, control_rate, device, plan_out);
+	return gvtm_plan_create_model5_voices(config, 1, control_rate, device, plan_out);
 }
 
 int gvtm_plan_create_model5_voices(const gvtm5_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
 {
-	return create_plan5(configs, n_voices, control_rate, device, plan_out);
+	auto differs = [](const gvtm5_config& c0, const gvtm5_config& c) { return c.output_rate != c0.output_rate || c.precision != c0.precision; };
+	return create_plan(configs, n_voices, control_rate, device, plan_out, "output_rate and precision", differs, gvtm::design_plan5, upload_tables5);
 }
 
 void gvtm_plan_destroy(gvtm_plan* plan)
 {
-	free_plan(plan);
+	if (!plan) return;
+	if (plan->device == GVTM_DEVICE_NONE) { // (a design-only plan holds nothing on a device)
+		delete plan;
+		return;
+	}
+	DeviceScope scope(plan->device);
+	delete plan;
 }
 
 int gvtm_plan_info(const gvtm_plan* plan, gvtm_info* info)
 {
 	if (!plan || !info) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or info");
-	fill_info(plan, plan->design, info); // (a plan of several voices: voice 0)
+	fill_info(plan, plan->designs[0], info); // (a plan of several voices: voice 0)
 	return GVTM_OK;
 }
 
@@ -460,10 +437,10 @@ int gvtm_plan_table(const gvtm_plan* plan, int which, double* out, size_t capaci
 	if (!plan || !out) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or out");
 	const std::vector<double>* src = nullptr;
 	switch (which) {
-	case GVTM_TABLE_FIR: src = &plan->design.fir; break;
-	case GVTM_TABLE_SRC_H: src = &plan->design.src_h; break;
-	case GVTM_TABLE_SRC_DH: src = &plan->design.src_dh; break;
-	case GVTM_TABLE_WAVETABLE: src = &plan->design.wavetable; break;
+	case GVTM_TABLE_FIR: src = &plan->designs[0].fir; break;
+	case GVTM_TABLE_SRC_H: src = &plan->designs[0].src_h; break;
+	case GVTM_TABLE_SRC_DH: src = &plan->designs[0].src_dh; break;
+	case GVTM_TABLE_WAVETABLE: src = &plan->designs[0].wavetable; break;
 	default: return -fail(GVTM_ERR_INVALID_ARGUMENT, "unknown table");
 	}
 	if (src->empty()) return -fail(GVTM_ERR_INVALID_ARGUMENT, "this model has no such table");
@@ -475,13 +452,13 @@ int gvtm_plan_table(const gvtm_plan* plan, int which, double* out, size_t capaci
 size_t gvtm_output_count(const gvtm_plan* plan, size_t n_frames)
 {
 	if (!plan) return static_cast<size_t>(-1);
-	return design_output_count(plan->design, n_frames);
+	return design_output_count(plan->designs[0], n_frames);
 }
 
 size_t gvtm_output_capacity(const gvtm_plan* plan, size_t max_frames)
 {
 	if (!plan) return static_cast<size_t>(-1);
-	return design_output_capacity(plan->design, max_frames);
+	return design_output_capacity(plan->designs[0], max_frames);
 }
 
 #ifdef GVTM_DIAGNOSTICS
@@ -500,8 +477,8 @@ int gvtm_debug_set_rows(gvtm_plan* plan, int rows)
 size_t gvtm_debug_lds_bytes(const gvtm_plan* plan, int rows)
 {
 	if (!plan) return 0;
-	if (plan->design.model5) return gvtm::synth5_lds_bytes(rows == 2 ? 2 : 1);
-	return gvtm::synth_lds_bytes(plan->design.k, plan->precision, rows, 0);
+	if (plan->designs[0].model5) return gvtm::synth5_lds_bytes(rows == 2 ? 2 : 1);
+	return gvtm::synth_lds_bytes(plan->designs[0].k, plan->precision, rows, 0);
 }
 
 /* The plan-level noise-sample table as the host builds it (n floats or doubles); needs no device. */
@@ -539,11 +516,10 @@ int gvtm_debug_dpp_selftest(gvtm_plan* plan, int* out)
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	int* d = nullptr;
-	if ((e = hipMalloc(reinterpret_cast<void**>(&d), gvtm::kDppSelftestInts * sizeof(int))) != hipSuccess) return fail_hip(e, "hipMalloc");
-	e = gvtm::launch_dpp_selftest(d, nullptr);
-	if (e == hipSuccess) e = hipMemcpy(out, d, gvtm::kDppSelftestInts * sizeof(int), hipMemcpyDeviceToHost);
-	(void) hipFree(d);
+	DeviceBuffer d;
+	if ((e = d.ensure(gvtm::kDppSelftestInts * sizeof(int))) != hipSuccess) return fail_hip(e, "hipMalloc");
+	e = gvtm::launch_dpp_selftest(static_cast<int*>(d.ptr), nullptr);
+	if (e == hipSuccess) e = hipMemcpy(out, d.ptr, gvtm::kDppSelftestInts * sizeof(int), hipMemcpyDeviceToHost);
 	if (e != hipSuccess) return fail_hip(e, "dpp selftest");
 	return GVTM_OK;
 }
@@ -579,14 +555,12 @@ int gvtm_debug_device_float_math(gvtm_plan* plan, int kind, const float* x, size
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	float *dx = nullptr, *dout = nullptr;
-	if ((e = hipMalloc(reinterpret_cast<void**>(&dx), n * sizeof(float))) != hipSuccess) return fail_hip(e, "hipMalloc");
-	if ((e = hipMalloc(reinterpret_cast<void**>(&dout), n * sizeof(float))) != hipSuccess) { (void) hipFree(dx); return fail_hip(e, "hipMalloc"); }
-	e = hipMemcpy(dx, x, n * sizeof(float), hipMemcpyHostToDevice);
-	if (e == hipSuccess) e = gvtm::launch_float_math_probe(kind, dx, n, dout, nullptr);
-	if (e == hipSuccess) e = hipMemcpy(out, dout, n * sizeof(float), hipMemcpyDeviceToHost);
-	(void) hipFree(dx);
-	(void) hipFree(dout);
+	DeviceBuffer dx, dout;
+	if ((e = dx.ensure(n * sizeof(float))) != hipSuccess) return fail_hip(e, "hipMalloc");
+	if ((e = dout.ensure(n * sizeof(float))) != hipSuccess) return fail_hip(e, "hipMalloc");
+	e = hipMemcpy(dx.ptr, x, n * sizeof(float), hipMemcpyHostToDevice);
+	if (e == hipSuccess) e = gvtm::launch_float_math_probe(kind, static_cast<const float*>(dx.ptr), n, static_cast<float*>(dout.ptr), nullptr);
+	if (e == hipSuccess) e = hipMemcpy(out, dout.ptr, n * sizeof(float), hipMemcpyDeviceToHost);
 	if (e != hipSuccess) return fail_hip(e, "float math probe");
 	return GVTM_OK;
 }
@@ -602,13 +576,12 @@ int gvtm_debug_group_voices(gvtm_plan* plan, const int32_t* d_voice_ids, size_t 
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	int32_t* counts = nullptr;
-	if ((e = hipMalloc(reinterpret_cast<void**>(&counts), sizeof(int32_t) * plan->n_voices * gvtm::kGroupVoicesThreads)) != hipSuccess) return fail_hip(e, "hipMalloc");
-	const size_t groups = (batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices);
-	gvtm::GroupVoicesArgs ga{d_voice_ids, batch, plan->n_voices, rows, groups, d_row_map, d_group_voice, counts, d_out_counts, d_maxabs};
+	DeviceBuffer counts;
+	if ((e = counts.ensure(sizeof(int32_t) * plan->n_voices() * gvtm::kGroupVoicesThreads)) != hipSuccess) return fail_hip(e, "hipMalloc");
+	const size_t groups = (batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices());
+	gvtm::GroupVoicesArgs ga{d_voice_ids, batch, plan->n_voices(), rows, groups, d_row_map, d_group_voice, static_cast<int32_t*>(counts.ptr), d_out_counts, d_maxabs};
 	e = gvtm::launch_group_voices(ga, nullptr);
 	if (e == hipSuccess) e = hipDeviceSynchronize();
-	(void) hipFree(counts);
 	if (e != hipSuccess) return fail_hip(e, "vtm_group_voices_kernel");
 	return GVTM_OK;
 }
@@ -673,25 +646,23 @@ int gvtm_generate_tracks_host(int device, const gvtm_track_config* config, const
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
 	const size_t n_events = static_cast<size_t>(event_offsets[batch]);
 	DeviceBuffer d_ev, d_off, d_par, d_cnt, d_dr;
-	int rc = GVTM_OK;
-	auto done = [&](int code) { d_ev.release(); d_off.release(); d_par.release(); d_cnt.release(); d_dr.release(); return code; };
-	if ((e = d_ev.ensure(sizeof(gvtm_event) * (n_events ? n_events : 1))) != hipSuccess) return done(fail_hip(e, "hipMalloc"));
-	if ((e = d_off.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return done(fail_hip(e, "hipMalloc"));
-	if ((e = d_par.ensure(sizeof(float) * 16 * (batch * max_frames ? batch * max_frames : 1))) != hipSuccess) return done(fail_hip(e, "hipMalloc"));
-	if ((e = d_cnt.ensure(sizeof(int32_t) * batch)) != hipSuccess) return done(fail_hip(e, "hipMalloc"));
-	if (drift && (e = d_dr.ensure(sizeof(gvtm_drift_state) * batch)) != hipSuccess) return done(fail_hip(e, "hipMalloc"));
-	if (n_events && (e = hipMemcpy(d_ev.ptr, events, sizeof(gvtm_event) * n_events, hipMemcpyHostToDevice)) != hipSuccess) return done(fail_hip(e, "H2D events"));
-	if ((e = hipMemcpy(d_off.ptr, event_offsets, sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return done(fail_hip(e, "H2D offsets"));
-	if (drift && (e = hipMemcpy(d_dr.ptr, drift, sizeof(gvtm_drift_state) * batch, hipMemcpyHostToDevice)) != hipSuccess) return done(fail_hip(e, "H2D drift"));
-	if ((e = hipMemset(d_par.ptr, 0, sizeof(float) * 16 * batch * max_frames)) != hipSuccess) return done(fail_hip(e, "hipMemset"));
-	rc = gvtm_generate_tracks_device(device, config, static_cast<const gvtm_event*>(d_ev.ptr), static_cast<const int64_t*>(d_off.ptr), batch,
+	if ((e = d_ev.ensure(sizeof(gvtm_event) * (n_events ? n_events : 1))) != hipSuccess) return fail_hip(e, "hipMalloc");
+	if ((e = d_off.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc");
+	if ((e = d_par.ensure(sizeof(float) * 16 * (batch * max_frames ? batch * max_frames : 1))) != hipSuccess) return fail_hip(e, "hipMalloc");
+	if ((e = d_cnt.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc");
+	if (drift && (e = d_dr.ensure(sizeof(gvtm_drift_state) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc");
+	if (n_events && (e = hipMemcpy(d_ev.ptr, events, sizeof(gvtm_event) * n_events, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D events");
+	if ((e = hipMemcpy(d_off.ptr, event_offsets, sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D offsets");
+	if (drift && (e = hipMemcpy(d_dr.ptr, drift, sizeof(gvtm_drift_state) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D drift");
+	if ((e = hipMemset(d_par.ptr, 0, sizeof(float) * 16 * batch * max_frames)) != hipSuccess) return fail_hip(e, "hipMemset");
+	const int rc = gvtm_generate_tracks_device(device, config, static_cast<const gvtm_event*>(d_ev.ptr), static_cast<const int64_t*>(d_off.ptr), batch,
 			max_frames, static_cast<float*>(d_par.ptr), static_cast<int32_t*>(d_cnt.ptr), drift ? static_cast<gvtm_drift_state*>(d_dr.ptr) : nullptr, nullptr);
-	if (rc != GVTM_OK) return done(rc);
-	if ((e = hipDeviceSynchronize()) != hipSuccess) return done(fail_hip(e, "track generation kernel"));
-	if (params && (e = hipMemcpy(params, d_par.ptr, sizeof(float) * 16 * batch * max_frames, hipMemcpyDeviceToHost)) != hipSuccess) return done(fail_hip(e, "D2H frames"));
-	if (frame_counts && (e = hipMemcpy(frame_counts, d_cnt.ptr, sizeof(int32_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return done(fail_hip(e, "D2H counts"));
-	if (drift && (e = hipMemcpy(drift, d_dr.ptr, sizeof(gvtm_drift_state) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return done(fail_hip(e, "D2H drift"));
-	return done(GVTM_OK);
+	if (rc != GVTM_OK) return rc;
+	if ((e = hipDeviceSynchronize()) != hipSuccess) return fail_hip(e, "track generation kernel");
+	if (params && (e = hipMemcpy(params, d_par.ptr, sizeof(float) * 16 * batch * max_frames, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H frames");
+	if (frame_counts && (e = hipMemcpy(frame_counts, d_cnt.ptr, sizeof(int32_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H counts");
+	if (drift && (e = hipMemcpy(drift, d_dr.ptr, sizeof(gvtm_drift_state) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H drift");
+	return GVTM_OK;
 }
 
 int gvtm_plan_set_timing(gvtm_plan* plan, int enabled)
@@ -708,13 +679,13 @@ double gvtm_plan_take_kernel_ms(gvtm_plan* plan, int* launches_out)
 	DeviceScope scope(plan->device);
 	double total = 0.0;
 	int n = 0;
-	for (auto& ev : plan->pending) {
+	for (EventPair& ev : plan->pending) {
 		float ms = 0.f;
-		if (hipEventSynchronize(ev.stop) == hipSuccess && hipEventElapsedTime(&ms, ev.start, ev.stop) == hipSuccess) {
+		if (hipEventSynchronize(ev.stop.h) == hipSuccess && hipEventElapsedTime(&ms, ev.start.h, ev.stop.h) == hipSuccess) {
 			total += ms;
 			++n;
 		}
-		plan->pool.push_back(ev);
+		plan->pool.push_back(std::move(ev));
 	}
 	plan->pending.clear();
 	if (launches_out) *launches_out = n;
@@ -731,7 +702,6 @@ struct StreamLaunch {
 	size_t stride;
 	int mode;     // gvtm::StreamMode
 	int xr;       // the stream's ring length (one for all shapes; several voices: the longest of the plan's voices)
-	int rows;     // 1 unless the utterances are in lockstep (several voices: within each voice)
 };
 
 // One synthesis launch: the device buffers of a gvtm_synthesize_*_device call, of a slice of the host entries or of a stream
@@ -744,8 +714,10 @@ struct LaunchRequest {
 	int64_t* out_counts;
 	float* maxabs;
 	void* hip_stream;
+	int rows = 0;                       // utterances per workgroup; 0 = by this launch's batch (gvtm_plan::rows_for)
 	bool voices = false;                // gvtm_synthesize_voices_*: voice_ids[b] is utterance b's voice
 	const int32_t* voice_ids = nullptr;
+	DeviceBuffer* groups = nullptr;     // voices: the caller's scratch for the row map, group voices and sort counts
 	const StreamLaunch* sl = nullptr;   // or null: a one-shot launch
 };
 
@@ -765,18 +737,15 @@ int use_noise_table(gvtm_plan* plan, size_t steps, gvtm::SynthArgs& args)
 		want = std::min(std::max(want, 2 * plan->noise_len), kNoiseTableMaxSteps);
 		std::vector<unsigned char> host(want * sizeof(float));
 		gvtm::design_noise_table(want, true, host.data());
-		void* fresh = nullptr;
-		if ((e = hipMalloc(&fresh, host.size())) != hipSuccess) return fail_hip(e, "hipMalloc (noise table)");
-		if ((e = hipMemcpy(fresh, host.data(), host.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-			(void) hipFree(fresh);
-			return fail_hip(e, "hipMemcpy (noise table)");
-		}
-		if (plan->d_noise) plan->noise_retired.push_back(plan->d_noise);
-		plan->d_noise = fresh;
+		DeviceBuffer fresh;
+		if ((e = fresh.ensure(host.size())) != hipSuccess) return fail_hip(e, "hipMalloc (noise table)");
+		if ((e = hipMemcpy(fresh.ptr, host.data(), host.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy (noise table)");
+		if (plan->d_noise.ptr) plan->noise_retired.push_back(std::move(plan->d_noise));
+		plan->d_noise = std::move(fresh);
 		plan->noise_len = want;
 	}
 	if (steps <= kNoiseTableMaxSteps) {
-		args.noise_lp = plan->d_noise;
+		args.noise_lp = plan->d_noise.ptr;
 		args.noise_len = plan->noise_len;
 	}
 	return GVTM_OK;
@@ -786,17 +755,17 @@ int use_noise_table(gvtm_plan* plan, size_t steps, gvtm::SynthArgs& args)
 // table and the row map)
 gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 {
-	const gvtm::Design& dg = plan->design;
+	const gvtm::Design& dg = plan->designs[0];
 	gvtm::SynthArgs args;
 	args.k = dg.k;
-	args.kconst = plan->d_consts;
+	args.kconst = static_cast<const gvtm::DeviceConstants*>(plan->d_consts.ptr);
 	args.params = r.params;
 	args.frame_counts = r.frame_counts;
 	args.audio = r.audio;
 	args.out_counts = r.out_counts;
 	args.maxabs = r.maxabs;
-	args.wavetable = plan->d_wavetable;
-	args.fir = plan->d_fir;
+	args.wavetable = plan->d_wavetable.ptr;
+	args.fir = plan->d_fir.ptr;
 	std::memset(&args.fir_k, 0, sizeof(args.fir_k));
 	if (!dg.model5) {
 		if (dg.f32) {
@@ -805,8 +774,8 @@ gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 			for (size_t i = 0; i < dg.fir.size() && i < 49; ++i) args.fir_k.d[i] = dg.fir[i];
 		}
 	}
-	args.src_h = plan->d_src_h;
-	args.src_dh = plan->d_src_dh;
+	args.src_h = plan->d_src_h.ptr;
+	args.src_dh = plan->d_src_dh.ptr;
 	args.max_frames = r.max_frames;
 	args.audio_stride = r.audio_stride;
 	args.batch = r.batch;
@@ -821,7 +790,7 @@ gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 	// (not for several voices: the hooks' buffers are sized for voice 0's steps and ceil(batch / rows) workgroups)
 	args.debug_taps = r.voices ? nullptr : plan->debug_taps;
 	args.phase_cycles = r.voices ? nullptr : plan->phase_cycles;
-	args.k5const = plan->d_consts5;
+	args.k5const = static_cast<const gvtm::Model5Constants*>(plan->d_consts5.ptr);
 	return args;
 }
 
@@ -833,18 +802,18 @@ int timed_launch(gvtm_plan* plan, hipStream_t stream, const char* what, Launch l
 	EventPair ev;
 	if (plan->timing) {
 		if (!plan->pool.empty()) {
-			ev = plan->pool.back();
+			ev = std::move(plan->pool.back());
 			plan->pool.pop_back();
 		} else {
-			if ((e = hipEventCreate(&ev.start)) != hipSuccess) return fail_hip(e, "hipEventCreate");
-			if ((e = hipEventCreate(&ev.stop)) != hipSuccess) return fail_hip(e, "hipEventCreate");
+			if ((e = hipEventCreate(&ev.start.h)) != hipSuccess) return fail_hip(e, "hipEventCreate");
+			if ((e = hipEventCreate(&ev.stop.h)) != hipSuccess) return fail_hip(e, "hipEventCreate");
 		}
-		if ((e = hipEventRecord(ev.start, stream)) != hipSuccess) return fail_hip(e, "hipEventRecord");
+		if ((e = hipEventRecord(ev.start.h, stream)) != hipSuccess) return fail_hip(e, "hipEventRecord");
 	}
 	e = launch();
 	if (plan->timing) {
-		(void) hipEventRecord(ev.stop, stream);
-		plan->pending.push_back(ev);
+		(void) hipEventRecord(ev.stop.h, stream);
+		plan->pending.push_back(std::move(ev));
 	}
 	if (e != hipSuccess) return fail_hip(e, what);
 	return GVTM_OK;
@@ -857,7 +826,7 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
 	// (the single-voice entries would not know which voice to synthesize; the voices entries take a one-voice plan too)
-	if (!r.voices && plan->n_voices > 1) return refuse_voices(plan, r.sl ? "gvtm_stream_*" : "gvtm_synthesize_batch_device");
+	if (!r.voices && plan->n_voices() > 1) return refuse_voices(plan, r.sl ? "gvtm_stream_*" : "gvtm_synthesize_batch_device");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	if (r.batch == 0) return GVTM_OK;
 	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
@@ -866,30 +835,29 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	// (several voices: the row map's int32 slots also count up to n_voices partly empty workgroups)
 	if (r.batch > (r.voices ? 0x3fffffffu : 0x7fffffffu)) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
 	unsigned max_steps = 0;
-	for (int v = 0; v < plan->n_voices; ++v) max_steps = std::max(max_steps, plan->voice(v).k.control_steps);
+	for (int v = 0; v < plan->n_voices(); ++v) max_steps = std::max(max_steps, plan->designs[v].k.control_steps);
 	if (static_cast<unsigned long long>(r.max_frames) * max_steps + 4096ull >= (1ull << 31)) {
 		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
 	}
 	// (a stream checks its stride against what each call produces: stream_launch)
-	for (int v = 0; !r.sl && v < plan->n_voices; ++v) {
-		if (r.audio_stride < design_output_count(plan->voice(v), r.max_frames)) {
+	for (int v = 0; !r.sl && v < plan->n_voices(); ++v) {
+		if (r.audio_stride < design_output_count(plan->designs[v], r.max_frames)) {
 			return fail(GVTM_ERR_INVALID_ARGUMENT, r.voices ? "audio_stride smaller than gvtm_voice_output_count(plan, voice, max_frames) of voice " + std::to_string(v)
 			                                                : "audio_stride smaller than gvtm_output_count(plan, max_frames)");
 		}
 	}
-	const bool model5 = plan->design.model5;
-	const gvtm::DeviceConstants& k = plan->design.k;
-	int rows = model5 ? plan->rows5_for(r.batch) : gvtm::synth_rows(plan->precision, r.batch, plan->rows, k.section_delay);
+	const bool model5 = plan->designs[0].model5;
+	const gvtm::DeviceConstants& k = plan->designs[0].k;
+	int rows = r.rows ? r.rows : plan->rows_for(r.batch);
 	// (the voice variant has the product's shapes only: eight rows are a diagnostics build's forced shape, and model 5's
 	// voices run one utterance per workgroup, a diagnostics build's forced two-utterance shape included)
 	if (r.voices) rows = std::min(rows, model5 ? 1 : 4);
-	if (r.sl && r.sl->rows == 1) rows = 1;
 	// the LDS holds the stream's ring (one for all shapes) or the longest ring of the voices; a shape it does not fit
 	// (a down-sampling voice carries the reference's 1024-sample ring per row) gives way to the next smaller one
 	auto ring = [&](int rw) {
 		if (r.sl) return r.sl->xr;
 		int xr = 0;
-		for (int v = 0; v < plan->n_voices; ++v) xr = std::max(xr, gvtm::synth_ring_length(plan->voice(v).k, plan->precision, rw));
+		for (int v = 0; v < plan->n_voices(); ++v) xr = std::max(xr, gvtm::synth_ring_length(plan->designs[v].k, plan->precision, rw));
 		return xr;
 	};
 	auto lds = [&](int rw) { return model5 ? gvtm::synth5_lds_bytes(rw) : gvtm::synth_lds_bytes(k, plan->precision, rw, ring(rw)); };
@@ -906,12 +874,11 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	args.xr = model5 ? 0 : ring(rows);
 	size_t work = r.batch; // what launch_synth takes: utterances, or with voices workgroups
 	if (r.voices) {
-		work = (r.batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices);
-		const size_t map_ints = work * rows, count_ints = static_cast<size_t>(plan->n_voices) * gvtm::kGroupVoicesThreads;
-		// (the scratch is the plan's: launches on one plan are ordered on one stream, as for gvtm_synthesize_events_device)
-		if ((e = plan->s_groups.ensure(sizeof(int32_t) * (map_ints + work + count_ints))) != hipSuccess) return fail_hip(e, "hipMalloc row map");
-		int32_t* const d_map = static_cast<int32_t*>(plan->s_groups.ptr);
-		gvtm::GroupVoicesArgs ga{r.voice_ids, r.batch, plan->n_voices, rows, work, d_map, d_map + map_ints, d_map + map_ints + work, r.out_counts, r.maxabs};
+		work = (r.batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices());
+		const size_t map_ints = work * rows, count_ints = static_cast<size_t>(plan->n_voices()) * gvtm::kGroupVoicesThreads;
+		if ((e = r.groups->ensure(sizeof(int32_t) * (map_ints + work + count_ints))) != hipSuccess) return fail_hip(e, "hipMalloc row map");
+		int32_t* const d_map = static_cast<int32_t*>(r.groups->ptr);
+		gvtm::GroupVoicesArgs ga{r.voice_ids, r.batch, plan->n_voices(), rows, work, d_map, d_map + map_ints, d_map + map_ints + work, r.out_counts, r.maxabs};
 		if ((e = gvtm::launch_group_voices(ga, stream)) != hipSuccess) return fail_hip(e, "vtm_group_voices_kernel launch");
 		args.row_map = d_map;
 		args.group_voice = d_map + map_ints;
@@ -941,8 +908,9 @@ int gvtm_synthesize_batch_device(gvtm_plan* plan, const float* d_params, const i
 int gvtm_synthesize_voices_device(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts, const int32_t* d_voice_ids,
 		size_t max_frames, size_t batch, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, void* hip_stream)
 {
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
 	return launch_synthesis(plan, LaunchRequest{d_params, d_frame_counts, batch, max_frames, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream,
-			true, d_voice_ids});
+			0, true, d_voice_ids, &plan->async.groups});
 }
 
 int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* config, const gvtm_event* d_events,
@@ -950,17 +918,17 @@ int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* conf
 		int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream)
 {
 	if (!plan || !config) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or config");
-	if (plan->n_voices > 1) return refuse_voices(plan, "gvtm_synthesize_events_device");
+	if (plan->n_voices() > 1) return refuse_voices(plan, "gvtm_synthesize_events_device");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	if (batch == 0) return GVTM_OK;
 	if (!d_events || !d_event_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events or event_offsets");
 	gvtm::TrackConstants tk{};
 	const char* why = gvtm::design_tracks(*config, tk);
 	if (why[0]) return fail(GVTM_ERR_INVALID_ARGUMENT, why);
-	if (static_cast<double>(tk.control_period) * plan->design.control_rate != 1000.0) {
+	if (static_cast<double>(tk.control_period) * plan->designs[0].control_rate != 1000.0) {
 		return fail(GVTM_ERR_INVALID_ARGUMENT, "control_period_ms of the track configuration and the plan's control rate disagree");
 	}
-	// Two launches on the caller's stream with a frame buffer of the plan's in between.  (Walking the event lists inside the
+	// Two launches on the caller's stream with a frame buffer of the plan's in between (the enqueue-only entries' scratch).  (Walking the event lists inside the
 	// synthesis kernel's interpolation wavefront was built and measured: bit-identical, no frame buffer, and 17.2 -> 33.1 ms
 	// per 4096 x 80 events -- an event boundary is a round trip to memory in the middle of a tick, three times over because
 	// the parameter groups run at different lags -- and 125 ms with the next events prefetched into registers, which that
@@ -968,13 +936,13 @@ int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* conf
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	if ((e = plan->s_params.ensure(sizeof(float) * batch * std::max<size_t>(max_frames, 1) * GVTM_N_PARAM)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
-	if ((e = plan->s_frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
-	int32_t* const counts = d_frame_counts ? d_frame_counts : static_cast<int32_t*>(plan->s_frames.ptr);
-	int rc = gvtm_generate_tracks_device(plan->device, config, d_events, d_event_offsets, batch, max_frames, static_cast<float*>(plan->s_params.ptr), counts,
+	if ((e = plan->async.params.ensure(sizeof(float) * batch * std::max<size_t>(max_frames, 1) * GVTM_N_PARAM)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
+	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
+	int32_t* const counts = d_frame_counts ? d_frame_counts : static_cast<int32_t*>(plan->async.frames.ptr);
+	int rc = gvtm_generate_tracks_device(plan->device, config, d_events, d_event_offsets, batch, max_frames, static_cast<float*>(plan->async.params.ptr), counts,
 			d_drift, hip_stream);
 	if (rc != GVTM_OK) return rc;
-	return launch_synthesis(plan, LaunchRequest{static_cast<const float*>(plan->s_params.ptr), counts, batch, max_frames, d_audio, audio_stride,
+	return launch_synthesis(plan, LaunchRequest{static_cast<const float*>(plan->async.params.ptr), counts, batch, max_frames, d_audio, audio_stride,
 			d_out_counts, d_maxabs, hip_stream});
 }
 
@@ -1007,14 +975,14 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
 	const bool voices = j.voice_ids != nullptr;
-	if (!voices && plan->n_voices > 1) return refuse_voices(plan, j.pcm ? "gvtm_synthesize_batch_host_pcm16" : "gvtm_synthesize_batch_host");
+	if (!voices && plan->n_voices() > 1) return refuse_voices(plan, j.pcm ? "gvtm_synthesize_batch_host_pcm16" : "gvtm_synthesize_batch_host");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	const size_t batch = j.batch, max_frames = j.max_frames, audio_stride = j.stride;
 	if (batch == 0) return GVTM_OK;
 	if (!j.audio && !j.pcm) return fail(GVTM_ERR_INVALID_ARGUMENT, "null output buffer");
 	if (max_frames > 0 && !j.params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
-	for (int v = 0; v < plan->n_voices; ++v) {
-		if (audio_stride < design_output_count(plan->voice(v), max_frames)) {
+	for (int v = 0; v < plan->n_voices(); ++v) {
+		if (audio_stride < design_output_count(plan->designs[v], max_frames)) {
 			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_output_count(plan, max_frames)");
 		}
 	}
@@ -1035,7 +1003,7 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 		// a voice id outside [0, n_voices) fails that utterance the same way (the device leaves it out of the row map)
 		if (voices) {
 			for (size_t b = 0; b < batch; ++b) {
-				if (j.voice_ids[b] < 0 || j.voice_ids[b] >= plan->n_voices) bad.push_back(b);
+				if (j.voice_ids[b] < 0 || j.voice_ids[b] >= plan->n_voices()) bad.push_back(b);
 			}
 		}
 	} catch (const std::bad_alloc&) {
@@ -1049,83 +1017,81 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 	const size_t pbytes = sizeof(float) * batch * row_in;
 	const size_t abytes = sizeof(float) * batch * audio_stride;
 	const size_t obytes = sizeof(int16_t) * batch * audio_stride;
-	if ((e = plan->s_params.ensure(pbytes ? pbytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc params");
-	if ((e = plan->s_audio.ensure(abytes ? abytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc audio");
-	if ((e = plan->s_counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
-	if ((e = plan->s_maxabs.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc maxabs");
-	if (counts_in && (e = plan->s_frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
-	if (voices && (e = plan->s_voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
-	if (j.pcm && (e = plan->s_pcm.ensure(obytes ? obytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc pcm");
-	if (j.pcm && (e = plan->s_scales.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc scales");
-	if (!plan->h2d_stream && (e = hipStreamCreateWithFlags(&plan->h2d_stream, hipStreamNonBlocking)) != hipSuccess) return fail_hip(e, "hipStreamCreate");
-	if (!plan->compute_stream && (e = hipStreamCreateWithFlags(&plan->compute_stream, hipStreamNonBlocking)) != hipSuccess) return fail_hip(e, "hipStreamCreate");
-	if (!plan->copy_stream && (e = hipStreamCreateWithFlags(&plan->copy_stream, hipStreamNonBlocking)) != hipSuccess) return fail_hip(e, "hipStreamCreate");
+	auto& sc = plan->host;
+	if ((e = sc.params.ensure(pbytes ? pbytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc params");
+	if ((e = sc.audio.ensure(abytes ? abytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc audio");
+	if ((e = sc.counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
+	if ((e = sc.maxabs.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc maxabs");
+	if (counts_in && (e = sc.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
+	if (voices && (e = sc.voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
+	if (j.pcm && (e = sc.pcm.ensure(obytes ? obytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc pcm");
+	if (j.pcm && (e = sc.scales.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc scales");
+	for (Stream* st : {&plan->h2d_stream, &plan->compute_stream, &plan->copy_stream}) {
+		if (!st->h && (e = hipStreamCreateWithFlags(&st->h, hipStreamNonBlocking)) != hipSuccess) return fail_hip(e, "hipStreamCreate");
+	}
+	const hipStream_t h2d_stream = plan->h2d_stream.h, compute_stream = plan->compute_stream.h, copy_stream = plan->copy_stream.h;
 
-	float* const d_params = static_cast<float*>(plan->s_params.ptr);
-	const int32_t* const d_frames = counts_in ? static_cast<const int32_t*>(plan->s_frames.ptr) : nullptr;
-	float* const d_audio = static_cast<float*>(plan->s_audio.ptr);
-	int16_t* const d_pcm = j.pcm ? static_cast<int16_t*>(plan->s_pcm.ptr) : nullptr;
-	float* const d_scales = j.pcm ? static_cast<float*>(plan->s_scales.ptr) : nullptr;
-	int64_t* const d_counts = static_cast<int64_t*>(plan->s_counts.ptr);
-	float* const d_maxabs = static_cast<float*>(plan->s_maxabs.ptr);
-	if (counts_in && (e = hipMemcpy(plan->s_frames.ptr, counts_in, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
+	float* const d_params = static_cast<float*>(sc.params.ptr);
+	const int32_t* const d_frames = counts_in ? static_cast<const int32_t*>(sc.frames.ptr) : nullptr;
+	float* const d_audio = static_cast<float*>(sc.audio.ptr);
+	int16_t* const d_pcm = j.pcm ? static_cast<int16_t*>(sc.pcm.ptr) : nullptr;
+	float* const d_scales = j.pcm ? static_cast<float*>(sc.scales.ptr) : nullptr;
+	int64_t* const d_counts = static_cast<int64_t*>(sc.counts.ptr);
+	float* const d_maxabs = static_cast<float*>(sc.maxabs.ptr);
+	if (counts_in && (e = hipMemcpy(sc.frames.ptr, counts_in, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
 		return fail_hip(e, "H2D frame_counts");
 	}
-	const int32_t* const d_voice_ids = voices ? static_cast<const int32_t*>(plan->s_voice_ids.ptr) : nullptr;
-	if (voices && (e = hipMemcpy(plan->s_voice_ids.ptr, j.voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
+	const int32_t* const d_voice_ids = voices ? static_cast<const int32_t*>(sc.voice_ids.ptr) : nullptr;
+	if (voices && (e = hipMemcpy(sc.voice_ids.ptr, j.voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
 		return fail_hip(e, "H2D voice_ids");
 	}
 	// rows come back zero beyond their sample count (the staging buffers are reused between calls; the voices of a mixed
 	// batch give different counts)
 	const bool ragged = counts_in != nullptr || voices || audio_stride > gvtm_output_count(plan, max_frames);
 
-	// the shape of the whole batch, and how many utterances fill the machine once in it
-	const bool model5 = plan->design.model5;
-	const int rows_all = model5 ? plan->rows5_for(batch) : gvtm::synth_rows(plan->precision, batch, plan->rows, plan->design.k.section_delay);
+	// the shape of the whole batch (every slice is launched in it), and how many utterances fill the machine once in it
+	const int rows_all = plan->rows_for(batch);
 	const size_t machine = static_cast<size_t>(rows_all) * static_cast<size_t>(plan->compute_units > 0 ? plan->compute_units : 256);
 	const size_t slice = batch >= 2 * machine ? machine : batch;
 	const size_t n_slices = (batch + slice - 1) / slice;
 	while (plan->slice_done.size() < 2 * n_slices) {
-		hipEvent_t ev = nullptr;
-		if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return fail_hip(e, "hipEventCreate");
-		plan->slice_done.push_back(ev);
+		Event ev;
+		if ((e = hipEventCreateWithFlags(&ev.h, hipEventDisableTiming)) != hipSuccess) return fail_hip(e, "hipEventCreate");
+		plan->slice_done.push_back(std::move(ev));
 	}
 	auto drain = [&]() {
-		(void) hipStreamSynchronize(plan->h2d_stream);
-		(void) hipStreamSynchronize(plan->compute_stream);
-		(void) hipStreamSynchronize(plan->copy_stream);
+		(void) hipStreamSynchronize(h2d_stream);
+		(void) hipStreamSynchronize(compute_stream);
+		(void) hipStreamSynchronize(copy_stream);
 	};
-	const int saved_rows = plan->rows;
-	if (plan->rows == 0) plan->rows = rows_all; // every slice in the whole batch's shape
 	int rc = GVTM_OK;
 	for (size_t i = 0; i < n_slices && rc == GVTM_OK; ++i) {
 		const size_t lo = i * slice, n = std::min(slice, batch - lo);
-		hipEvent_t in_done = plan->slice_done[2 * i], out_ready = plan->slice_done[2 * i + 1];
+		hipEvent_t in_done = plan->slice_done[2 * i].h, out_ready = plan->slice_done[2 * i + 1].h;
 		if (pbytes && (e = hipMemcpyAsync(d_params + lo * row_in, j.params + lo * row_in, sizeof(float) * n * row_in, hipMemcpyHostToDevice,
-				plan->h2d_stream)) != hipSuccess) { rc = fail_hip(e, "H2D params"); break; }
-		if ((e = hipEventRecord(in_done, plan->h2d_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
-		if ((e = hipStreamWaitEvent(plan->compute_stream, in_done, 0)) != hipSuccess) { rc = fail_hip(e, "hipStreamWaitEvent"); break; }
-		if (ragged && !j.pcm && (e = hipMemsetAsync(d_audio + lo * audio_stride, 0, sizeof(float) * n * audio_stride, plan->compute_stream)) != hipSuccess) {
+				h2d_stream)) != hipSuccess) { rc = fail_hip(e, "H2D params"); break; }
+		if ((e = hipEventRecord(in_done, h2d_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
+		if ((e = hipStreamWaitEvent(compute_stream, in_done, 0)) != hipSuccess) { rc = fail_hip(e, "hipStreamWaitEvent"); break; }
+		if (ragged && !j.pcm && (e = hipMemsetAsync(d_audio + lo * audio_stride, 0, sizeof(float) * n * audio_stride, compute_stream)) != hipSuccess) {
 			rc = fail_hip(e, "hipMemsetAsync"); break;
 		}
-		if (ragged && j.pcm && (e = hipMemsetAsync(d_pcm + lo * audio_stride, 0, sizeof(int16_t) * n * audio_stride, plan->compute_stream)) != hipSuccess) {
+		if (ragged && j.pcm && (e = hipMemsetAsync(d_pcm + lo * audio_stride, 0, sizeof(int16_t) * n * audio_stride, compute_stream)) != hipSuccess) {
 			rc = fail_hip(e, "hipMemsetAsync"); break;
 		}
 		rc = launch_synthesis(plan, LaunchRequest{d_params + lo * row_in, d_frames ? d_frames + lo : nullptr, n, max_frames, d_audio + lo * audio_stride,
-				audio_stride, d_counts + lo, d_maxabs + lo, plan->compute_stream, voices, voices ? d_voice_ids + lo : nullptr});
+				audio_stride, d_counts + lo, d_maxabs + lo, compute_stream, rows_all, voices, voices ? d_voice_ids + lo : nullptr, &sc.groups});
 		if (rc != GVTM_OK) break;
 		if (j.pcm) {
 			// (normalize takes at most 65535 utterances per launch: a slice is far below that unless the batch is one slice)
 			for (size_t q = 0; q < n && rc == GVTM_OK; q += 32768) {
 				const size_t m = std::min<size_t>(32768, n - q);
 				rc = gvtm_normalize_batch_device(plan, d_audio + (lo + q) * audio_stride, m, audio_stride, d_counts + lo + q, d_maxabs + lo + q, nullptr,
-						d_pcm + (lo + q) * audio_stride, d_scales + lo + q, plan->compute_stream);
+						d_pcm + (lo + q) * audio_stride, d_scales + lo + q, compute_stream);
 			}
 			if (rc != GVTM_OK) break;
 		}
-		if ((e = hipEventRecord(out_ready, plan->compute_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
+		if ((e = hipEventRecord(out_ready, compute_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
 	}
-	plan->rows = saved_rows;
 	if (rc != GVTM_OK) {
 		drain();
 		return rc;
@@ -1134,17 +1100,14 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 	// so every kernel is queued before the first of them)
 	for (size_t i = 0; i < n_slices; ++i) {
 		const size_t lo = i * slice, n = std::min(slice, batch - lo);
-		if ((e = hipStreamWaitEvent(plan->copy_stream, plan->slice_done[2 * i + 1], 0)) != hipSuccess) { drain(); return fail_hip(e, "hipStreamWaitEvent"); }
-		if (j.pcm) e = hipMemcpyAsync(j.pcm + lo * audio_stride, d_pcm + lo * audio_stride, sizeof(int16_t) * n * audio_stride, hipMemcpyDeviceToHost, plan->copy_stream);
-		else e = hipMemcpyAsync(j.audio + lo * audio_stride, d_audio + lo * audio_stride, sizeof(float) * n * audio_stride, hipMemcpyDeviceToHost, plan->copy_stream);
+		if ((e = hipStreamWaitEvent(copy_stream, plan->slice_done[2 * i + 1].h, 0)) != hipSuccess) { drain(); return fail_hip(e, "hipStreamWaitEvent"); }
+		if (j.pcm) e = hipMemcpyAsync(j.pcm + lo * audio_stride, d_pcm + lo * audio_stride, sizeof(int16_t) * n * audio_stride, hipMemcpyDeviceToHost, copy_stream);
+		else e = hipMemcpyAsync(j.audio + lo * audio_stride, d_audio + lo * audio_stride, sizeof(float) * n * audio_stride, hipMemcpyDeviceToHost, copy_stream);
 		if (e != hipSuccess) { drain(); return fail_hip(e, "D2H samples"); }
 	}
-	if ((e = hipStreamSynchronize(plan->copy_stream)) != hipSuccess) { drain(); return fail_hip(e, "vtm_synth_kernel execution / D2H samples"); }
-	if ((e = hipStreamSynchronize(plan->compute_stream)) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");
-	if ((e = hipStreamSynchronize(plan->h2d_stream)) != hipSuccess) return fail_hip(e, "H2D params");
-	// (everything this plan has launched so far is complete: superseded noise tables can go)
-	for (void* q : plan->noise_retired) (void) hipFree(q);
-	plan->noise_retired.clear();
+	if ((e = hipStreamSynchronize(copy_stream)) != hipSuccess) { drain(); return fail_hip(e, "vtm_synth_kernel execution / D2H samples"); }
+	if ((e = hipStreamSynchronize(compute_stream)) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");
+	if ((e = hipStreamSynchronize(h2d_stream)) != hipSuccess) return fail_hip(e, "H2D params");
 	if (j.out_counts && (e = hipMemcpy(j.out_counts, d_counts, sizeof(int64_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H counts");
 	if (j.maxabs && (e = hipMemcpy(j.maxabs, d_maxabs, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H maxabs");
 	if (j.scales && d_scales && (e = hipMemcpy(j.scales, d_scales, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H scales");
@@ -1229,7 +1192,7 @@ struct gvtm_stream {
 	// device for the grouping kernel
 	bool voices = false;
 	std::vector<int32_t> voice_ids;
-	DeviceBuffer d_state, d_params, d_frames, d_audio, d_counts, d_maxabs, d_voice_ids;
+	DeviceBuffer d_state, d_params, d_frames, d_audio, d_counts, d_maxabs, d_voice_ids, d_groups;
 	std::vector<std::vector<float>> held; // per utterance: frames pushed but not yet synthesized (the last one is the look-ahead)
 	std::vector<uint64_t> steps_done;     // per utterance: internal steps synthesized
 	std::vector<float> staging;
@@ -1253,7 +1216,7 @@ int voice_of(const gvtm_stream* s, size_t b)
 int stream_upload_fresh_state(gvtm_stream* s)
 {
 	std::vector<unsigned char> init(s->state_stride * s->batch, 0);
-	const bool model5 = s->plan->design.model5;
+	const bool model5 = s->plan->designs[0].model5;
 	for (size_t b = 0; b < s->batch; ++b) {
 		gvtm::StreamHeader h{};
 		h.seed = 0.7892347; // NoiseSource::reset (vtm/NoiseSource.h:32-34)
@@ -1261,7 +1224,7 @@ int stream_upload_fresh_state(gvtm_stream* s)
 		if (model5) {
 			// VocalTractModel5::reset (vtm/VocalTractModel5.h:423-453): RosenbergBGlottalSource::reset leaves t2 at the end of the
 			// longest falling phase, the noise source starts from its seed, everything else is zero
-			const gvtm::Model5Constants& k5 = s->plan->voice(voice_of(s, b)).k5;
+			const gvtm::Model5Constants& k5 = s->plan->designs[voice_of(s, b)].k5;
 			double sc[gvtm::kStream5Scalars] = {};
 			sc[gvtm::kS5Scan + 1] = k5.rb_t1 + k5.rb_tn_max;
 			sc[gvtm::kS5Scan + 2] = 0.7892347;
@@ -1287,7 +1250,7 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	size_t rows_max = 0;
 	bool lockstep = true, any = final;
 	// (lockstep is judged per voice: a workgroup only ever holds one voice; first[v] is voice v's first utterance)
-	std::vector<size_t> first(static_cast<size_t>(plan->n_voices), batch);
+	std::vector<size_t> first(static_cast<size_t>(plan->n_voices()), batch);
 	for (size_t b = 0; b < batch; ++b) {
 		const size_t rows = n_frames[b] + (final ? 0 : 1); // a push carries the look-ahead frame behind its last one
 		rows_max = std::max(rows_max, n_frames[b] ? rows : size_t(0));
@@ -1300,7 +1263,7 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	size_t need = 0;
 	std::vector<int64_t> want(batch, 0);
 	for (size_t b = 0; b < batch; ++b) {
-		const gvtm::DeviceConstants& k = plan->voice(voice_of(s, b)).k;
+		const gvtm::DeviceConstants& k = plan->designs[voice_of(s, b)].k;
 		const uint64_t after = s->steps_done[b] + static_cast<uint64_t>(n_frames[b]) * k.control_steps;
 		if (after + 4096ull >= (1ull << 31)) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
 		const uint64_t k0 = outputs_before(k, s->steps_done[b]);
@@ -1340,10 +1303,11 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	if ((e = hipMemcpy(s->d_params.ptr, s->staging.data(), pbytes, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D params");
 	if ((e = hipMemcpy(s->d_frames.ptr, s->counts.data(), sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D frame counts");
 	if ((e = hipMemsetAsync(s->d_audio.ptr, 0, abytes, nullptr)) != hipSuccess) return fail_hip(e, "hipMemsetAsync");
-	const StreamLaunch sl{static_cast<unsigned char*>(s->d_state.ptr), s->state_stride, final ? gvtm::kStreamFinish : gvtm::kStreamPush, s->xr, lockstep ? 0 : 1};
+	const StreamLaunch sl{static_cast<unsigned char*>(s->d_state.ptr), s->state_stride, final ? gvtm::kStreamFinish : gvtm::kStreamPush, s->xr};
+	// (one utterance per workgroup unless the utterances are in lockstep)
 	const int rc = launch_synthesis(plan, LaunchRequest{static_cast<const float*>(s->d_params.ptr), static_cast<const int32_t*>(s->d_frames.ptr), batch,
 			rows_max, static_cast<float*>(s->d_audio.ptr), audio_stride, static_cast<int64_t*>(s->d_counts.ptr), static_cast<float*>(s->d_maxabs.ptr), nullptr,
-			s->voices, s->voices ? static_cast<const int32_t*>(s->d_voice_ids.ptr) : nullptr, &sl});
+			lockstep ? 0 : 1, s->voices, s->voices ? static_cast<const int32_t*>(s->d_voice_ids.ptr) : nullptr, &s->d_groups, &sl});
 	if (rc != GVTM_OK) return rc;
 	if (launched) *launched = true;
 	if ((e = hipDeviceSynchronize()) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");
@@ -1358,7 +1322,7 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	if (out_counts) std::copy(got.begin(), got.end(), out_counts);
 	if (maxabs && (e = hipMemcpy(maxabs, s->d_maxabs.ptr, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H maxabs");
 	for (size_t b = 0; b < batch; ++b) {
-		s->steps_done[b] += static_cast<uint64_t>(n_frames[b]) * plan->voice(voice_of(s, b)).k.control_steps;
+		s->steps_done[b] += static_cast<uint64_t>(n_frames[b]) * plan->designs[voice_of(s, b)].k.control_steps;
 		s->held[b].erase(s->held[b].begin(), s->held[b].begin() + static_cast<std::ptrdiff_t>(n_frames[b] * GVTM_N_PARAM));
 	}
 	return GVTM_OK;
@@ -1368,9 +1332,9 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 int check_voice_ids(const gvtm_plan* plan, const int32_t* voice_ids, size_t batch)
 {
 	for (size_t b = 0; b < batch; ++b) {
-		if (voice_ids[b] < 0 || voice_ids[b] >= plan->n_voices) {
+		if (voice_ids[b] < 0 || voice_ids[b] >= plan->n_voices()) {
 			return fail(GVTM_ERR_INVALID_ARGUMENT, "utterance " + std::to_string(b) + ": voice id " + std::to_string(voice_ids[b]) + " outside [0, " +
-					std::to_string(plan->n_voices) + ")");
+					std::to_string(plan->n_voices()) + ")");
 		}
 	}
 	return GVTM_OK;
@@ -1382,14 +1346,14 @@ int check_voice_ids(const gvtm_plan* plan, const int32_t* voice_ids, size_t batc
 int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_stream** stream_out)
 {
 	try {
-		std::unique_ptr<gvtm_stream> s(new gvtm_stream);
+		std::unique_ptr<gvtm_stream, void (*)(gvtm_stream*)> s(new gvtm_stream, gvtm_stream_destroy);
 		s->plan = plan;
 		s->batch = batch;
 		s->voices = voice_ids != nullptr;
 		if (s->voices) s->voice_ids.assign(voice_ids, voice_ids + batch);
-		for (int v = 0; v < plan->n_voices; ++v) {
-			const gvtm::DeviceConstants& k = plan->voice(v).k;
-			if (plan->design.model5) {
+		for (int v = 0; v < plan->n_voices(); ++v) {
+			const gvtm::DeviceConstants& k = plan->designs[v].k;
+			if (plan->designs[0].model5) {
 				// reference model 5: its own state block (vtm_kernels.hpp: Stream5Layout); the serial wavefronts work in blocks
 				// of four steps (vtm_kernel_m5.inc)
 				s->state_stride = gvtm::Stream5Layout::bytes();
@@ -1411,15 +1375,11 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
 		if ((e = s->d_state.ensure(s->state_stride * batch)) != hipSuccess) return fail_hip(e, "hipMalloc stream state");
 		if (s->voices) {
-			if ((e = s->d_voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) { s->d_state.release(); return fail_hip(e, "hipMalloc voice ids"); }
-			if ((e = hipMemcpy(s->d_voice_ids.ptr, voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
-				s->d_state.release();
-				s->d_voice_ids.release();
-				return fail_hip(e, "H2D voice ids");
-			}
+			if ((e = s->d_voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
+			if ((e = hipMemcpy(s->d_voice_ids.ptr, voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D voice ids");
 		}
 		const int rc = stream_upload_fresh_state(s.get());
-		if (rc != GVTM_OK) { s->d_state.release(); s->d_voice_ids.release(); return rc; }
+		if (rc != GVTM_OK) return rc;
 		*stream_out = s.release();
 		return GVTM_OK;
 	} catch (const std::bad_alloc&) {
@@ -1435,7 +1395,7 @@ int gvtm_stream_create(gvtm_plan* plan, size_t batch, gvtm_stream** stream_out)
 {
 	if (!plan || !stream_out || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan / stream_out or empty batch");
 	*stream_out = nullptr;
-	if (plan->n_voices > 1) return refuse_voices(plan, "gvtm_stream_create");
+	if (plan->n_voices() > 1) return refuse_voices(plan, "gvtm_stream_create");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	return create_stream(plan, batch, nullptr, stream_out);
 }
@@ -1448,17 +1408,13 @@ int gvtm_stream_create_voices(gvtm_plan* plan, const int32_t* voice_ids, size_t 
 	if (rc != GVTM_OK) return rc;
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
 	// (a plan of one voice: every id is 0, and the stream is the one gvtm_stream_create makes)
-	return create_stream(plan, batch, plan->n_voices > 1 ? voice_ids : nullptr, stream_out);
+	return create_stream(plan, batch, plan->n_voices() > 1 ? voice_ids : nullptr, stream_out);
 }
 
 void gvtm_stream_destroy(gvtm_stream* s)
 {
 	if (!s) return;
-	{
-		DeviceScope scope(s->plan->device);
-		s->d_state.release(); s->d_params.release(); s->d_frames.release(); s->d_audio.release(); s->d_counts.release(); s->d_maxabs.release();
-		s->d_voice_ids.release();
-	}
+	DeviceScope scope(s->plan->device);
 	delete s;
 }
 
@@ -1499,9 +1455,9 @@ size_t gvtm_stream_capacity(const gvtm_stream* s, size_t max_new_frames)
 	// the largest over the stream's voices: at most the new frames plus what a push can have kept (the voice's granule),
 	// flushed, with the overrun's lap
 	size_t m = 0;
-	for (int v = 0; v < s->plan->n_voices; ++v) {
+	for (int v = 0; v < s->plan->n_voices(); ++v) {
 		if (s->voices && std::find(s->voice_ids.begin(), s->voice_ids.end(), v) == s->voice_ids.end()) continue;
-		const gvtm::DeviceConstants& k = s->plan->voice(v).k;
+		const gvtm::DeviceConstants& k = s->plan->designs[v].k;
 		const uint64_t steps = static_cast<uint64_t>(max_new_frames + s->granule_frames[static_cast<size_t>(v)]) * k.control_steps;
 		m = std::max(m, static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, steps) + 1));
 	}

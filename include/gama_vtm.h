@@ -300,8 +300,9 @@ size_t gvtm_voices_output_capacity(const gvtm_plan* plan, size_t max_frames);
  * required, gvtm_voices_output_capacity(plan, max_frames) holds any mix.  An utterance whose voice id is outside
  * [0, n_voices) fails on its own, as a bad frame count does in the host entries: its out_counts = -1, maxabs = 0, its row
  * is left untouched; the call still succeeds.  Enqueue-only: a small grouping kernel sorts the utterances by voice on the
- * device (stable, each voice padded to whole workgroups), then one synthesis launch runs every voice.  The plan keeps the
- * grouping's scratch: calls on one plan must be ordered (one stream), as for gvtm_synthesize_events_device. */
+ * device (stable, each voice padded to whole workgroups), then one synthesis launch runs every voice.  The grouping's
+ * scratch is the plan's: calls to this entry and to gvtm_synthesize_events_device on one plan must be ordered on one
+ * stream (the host entries and streams have scratch of their own). */
 int gvtm_synthesize_voices_device(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts,
 		const int32_t* d_voice_ids, size_t max_frames, size_t batch, float* d_audio, size_t audio_stride,
 		int64_t* d_out_counts, float* d_maxabs, void* hip_stream);
@@ -453,7 +454,9 @@ int gvtm_generate_tracks_device(int device, const gvtm_track_config* config, con
  *                   more is cut there
  *   d_frame_counts  [batch] int32 out: frames each list yields, may be NULL
  *   d_drift         [batch] in/out drift-generator states, or NULL (a fresh generator per utterance)
- * The remaining arguments are gvtm_synthesize_batch_device's.
+ * The remaining arguments are gvtm_synthesize_batch_device's.  The frame buffer is the plan's: calls to this entry and to
+ * gvtm_synthesize_voices_device on one plan must be ordered on one stream (the host entries and streams have buffers of
+ * their own).
  */
 int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* config, const gvtm_event* d_events,
 		const int64_t* d_event_offsets, size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,

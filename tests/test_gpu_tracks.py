@@ -245,3 +245,43 @@ def test_events_entry_truncates_at_max_frames_and_serves_every_model():
         assert torch.equal(outs[0][1], outs[1][1]) and torch.equal(outs[0][2], outs[1][2])
         assert torch.equal(outs[0][3].view(torch.int64), outs[1][3].view(torch.int64))
         assert outs[1][2][0].item() == plan.output_count(cut) and outs[1][2][1].item() == plan.output_count(counts[1])
+
+
+@pytest.mark.parametrize("precision", [capi.PRECISION_F32, capi.PRECISION_F64], ids=["f32", "f64"])
+def test_events_entry_keeps_its_frames_while_a_host_entry_runs(precision):
+    """gvtm_synthesize_events_device only enqueues.  A host entry called on the same plan while its kernels are still
+    queued (other frames, more of them per utterance: the host entry grows its own staging and the noise-sample table)
+    must leave the events entry's frames and tables alone: both calls come out bit for bit as each does alone."""
+    import torch
+    import tracks
+    cfgv = np.array([4, 1, 1, 1, 1, -20.0, -6.0, 4.0, 250.0, 4.0])
+    tc = _product_config(cfgv)
+    pool = [_singable_event_table(700 + b, n) for b, n in enumerate([40, 25, 60, 33])]
+    batch = 4096  # some milliseconds of synthesis: the host entry is called long before it is done
+    max_frames = max(capi.tracks_frame_count(tc, capi.events_from_table(t)) for t in pool)
+    d_events, d_offsets = _events_on_device([pool[b % len(pool)] for b in range(batch)])
+    dev = d_events.device
+    plan = g.Plan(g.config_from_dict(g.read_config_file(oracle.VOICE_MALE), 44100.0, 1, precision), 250.0, 0)
+    stride = plan.output_capacity(max_frames)
+    host_params = tracks.random_tracks(64, 2 * max_frames, seed0=17, consonant_heavy=True)
+    side = torch.cuda.Stream()  # a non-blocking stream: nothing orders it against the host entry's own streams
+
+    def enqueue_events():
+        a = torch.zeros((batch, stride), dtype=torch.float32, device=dev)
+        f = torch.zeros(batch, dtype=torch.int32, device=dev)
+        n = torch.zeros(batch, dtype=torch.int64, device=dev)
+        m = torch.zeros(batch, dtype=torch.float32, device=dev)
+        side.wait_stream(torch.cuda.current_stream())
+        plan.synthesize_events_device(tc, d_events, d_offsets, batch, max_frames, a, stride, f, n, m, None, side.cuda_stream)
+        return a, f, n, m
+
+    both = enqueue_events()
+    host_both = plan.synthesize_host(host_params)  # no synchronisation in between
+    torch.cuda.synchronize()
+    alone = enqueue_events()
+    torch.cuda.synchronize()
+    host_alone = plan.synthesize_host(host_params)
+    for x, y in zip(both, alone):  # samples, frame counts, sample counts, peaks: bit for bit
+        assert torch.equal(x.view(torch.uint8), y.view(torch.uint8))
+    for x, y in zip(host_both, host_alone):
+        assert x.tobytes() == y.tobytes()

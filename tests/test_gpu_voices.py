@@ -205,6 +205,40 @@ def test_host_entries_slice_a_big_mixed_batch(precision):
     assert np.array_equal(scales, ds.cpu().numpy())
 
 
+@pytest.mark.parametrize("precision", [capi.PRECISION_F32, capi.PRECISION_F64], ids=["f32", "f64"])
+def test_device_entry_keeps_its_grouping_while_a_host_entry_runs(precision):
+    """gvtm_synthesize_voices_device only enqueues.  The voices host entry called on the same plan while its kernels are
+    still queued (other utterances, more frames each) groups its own batch in scratch of its own: both calls come out bit
+    for bit as each does alone."""
+    import torch
+    plan = g.VoicesPlan(configs(precision=precision), 250.0, 0)
+    batch, max_frames = 4096, 250  # some milliseconds of synthesis: the host entry is called long before it is done
+    params, ids, frames = mixed_batch(batch, max_frames, 5, seed=91)
+    h_params, h_ids, h_frames = mixed_batch(64, 2 * max_frames, 5, seed=92)
+    stride = plan.voices_output_capacity(max_frames)
+    dp, di, df = (torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (params, ids, frames))
+    side = torch.cuda.Stream()  # a non-blocking stream: nothing orders it against the host entry's own streams
+
+    def enqueue_device():
+        da = torch.zeros((batch, stride), dtype=torch.float32, device="cuda")
+        dc = torch.zeros(batch, dtype=torch.int64, device="cuda")
+        dm = torch.zeros(batch, dtype=torch.float32, device="cuda")
+        side.wait_stream(torch.cuda.current_stream())
+        plan.synthesize_voices_device(dp, di, batch, max_frames, da, stride, df, dc, dm, side.cuda_stream)
+        return da, dc, dm
+
+    both = enqueue_device()
+    host_both = plan.synthesize_host(h_params, h_ids, h_frames)  # no synchronisation in between
+    torch.cuda.synchronize()
+    alone = enqueue_device()
+    torch.cuda.synchronize()
+    host_alone = plan.synthesize_host(h_params, h_ids, h_frames)
+    for x, y in zip(both, alone):  # samples, sample counts, peaks: bit for bit
+        assert torch.equal(x.view(torch.uint8), y.view(torch.uint8))
+    for x, y in zip(host_both, host_alone):
+        assert x.tobytes() == y.tobytes()
+
+
 def _numpy_grouping(ids, n_voices, rows):
     groups = (len(ids) + rows - 1) // rows + n_voices
     row_map = np.full(groups * rows, -1, dtype=np.int32)
