@@ -11,7 +11,7 @@ single-GPU entry of `configs`: configs[3], "Batch=4096 30s long-form tracks, 2x 
 tube, fp32 vs fp64 sweep" = 4096 utterances x 7500 frames, VocalTractModel2<TFloat,2>
 semantics (SectionDelay 2, 40 068 Hz internal), 44.1 kHz out; 1.97 GB of frames in and
 21.6 GB of samples out per launch, all resident in HBM.  The headline runs it in float (the
-reference's TFloat = float class, output bit-identical to it); `extras` carries the same
+reference's TFloat = float class, output bit-identical to it); with `--full`, `extras` carries the same
 workload in mixed and fp64 (the sweep), 4096 x 2 s and configs[1] (256 x 2 s, VTM0) in all
 three, and for each precision how far its samples are from the fp64 path's.  For N>1 the driver
 starts one process per GPU (torch.distributed.run): the global batch (default 4096 per GPU =
@@ -28,14 +28,18 @@ unchanged.
 Rank 0 prints one JSON line.  `roofline.achieved` = algorithmic bytes per launch (64 B per
 input frame + 4 B per output sample) / the synthesis kernel's mean duration
 measured with HIP events on the launch stream; `roofline.valu` prices the same launches against
-the vector-ALU peak (the resource that actually binds).  `cpu_baseline` times the
-real reference (oracle/_ref, compiled from /root/reference in the build container; "port" = our
-C oracle when that binary is absent) on one host core over a bounded sample of the same workload, once per reference class
-(float and double), with the host CPU's model and core count beside it.  `parity_check` compares two utterances of the
-TIMED output buffer with the oracle after the timed region (the oracle is the checker here, never the thing measured);
-`end_to_end` times the host-buffer entries (H2D frames + kernel + D2H samples through page-locked buffers, float32 and
-int16 output) beside the kernel-only `value`, never instead of it.  `--dump-outputs DIR` writes what the last timed step
+the vector-ALU peak (the resource that actually binds).  `--dump-outputs DIR` writes what the last timed step
 handed back (samples, counts, peaks; a seeded subset of the utterances when they exceed 48 MB) to DIR/*.npy.
+
+A plain run does only that: set up, warm up, time the steps, dump, print.  `--full` adds what takes runs or host time of
+its own, after the timed region (`--no-parity-check`, `--no-extras`, `--no-end-to-end`, `--no-cpu-baseline` drop single
+legs of it).  `parity_check` compares two utterances of the TIMED output buffer with the oracle (the oracle is the checker
+here, never the thing measured; a mismatch ends the run with an error).  `extras`: see above; one GPU, model 0 only.
+`end_to_end` times the host-buffer entries (H2D frames + kernel + D2H samples through page-locked buffers, float32 and
+int16 output) beside the kernel-only `value`, never instead of it; one GPU, model 0 only.  `cpu_baseline` times the real
+reference (oracle/_ref, built by oracle/Makefile where the reference's sources are at hand; "port" = our C oracle when
+that binary is absent) on one host core over a bounded sample of the same workload, once per reference class (float and
+double), with the host CPU's model and core count beside it; one GPU only.
 """
 import argparse
 import json
@@ -94,12 +98,16 @@ def parse_args(argv=None):
                     help="0: the VocalTractModel0/2 path (default, BASELINE configs); 4: the 30+18-section tube of VocalTractModel4 "
                          "(--precision f64 = reference model 4, f32 = VocalTractModel4<float,1>; --delay ignored); 5: reference model 5 "
                          "(VocalTractModel5<double,1>, its own kernel; fp64, --delay / --precision ignored); 4 and 5 default to 256 x 500 frames")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra single-GPU measurements (other precisions and sizes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also check the timed output against the oracle (parity_check) and measure "
+                         "the other precisions and sizes (extras), the host-buffer entries (end_to_end) and one host core "
+                         "(cpu_baseline); without it a run only sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the host-core baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra single-GPU measurements (other precisions and sizes)")
     ap.add_argument("--dist-backend", default="nccl", help="process-group backend (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal only: every rank uses GPU 0")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the host-buffer (H2D + kernel + D2H) measurements")
-    ap.add_argument("--no-parity-check", action="store_true", help="skip the oracle comparison of the timed output")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the host-buffer (H2D + kernel + D2H) measurements")
+    ap.add_argument("--no-parity-check", action="store_true", help="with --full: skip the oracle comparison of the timed output")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one handed back to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--rehearse-launch", action="store_true",
@@ -410,6 +418,23 @@ def traffic_entry(batch, frames, delay, precision, model):
         return None
 
 
+def full_legs(args, world):
+    """What rank 0 runs after the headline: nothing without --full; with it the oracle check of the timed output and,
+    on one GPU, the extras and host-buffer entries (model 0 only) and the host-core baseline, less what --no-* drops."""
+    if not args.full:
+        return set()
+    legs = {"parity_check", "extras", "end_to_end", "cpu_baseline"}
+    if world > 1:
+        legs = {"parity_check"}
+    if args.model != 0:
+        legs -= {"extras", "end_to_end"}
+    for leg, off in (("parity_check", args.no_parity_check), ("extras", args.no_extras),
+                     ("end_to_end", args.no_end_to_end), ("cpu_baseline", args.no_cpu_baseline)):
+        if off:
+            legs.discard(leg)
+    return legs
+
+
 def main():
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -431,6 +456,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit("bench.py --gpus %d: the launcher started %d ranks" % (args.gpus, world))
+    legs = full_legs(args, world)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the VTM path has no CPU fallback")
     if args.single_device:
@@ -506,7 +532,7 @@ def main():
         # before extras(), which reuses d_audio
         dumped = dump_outputs(args.dump_outputs, d_audio, d_counts, d_max, batch, n_out)
     parity = None
-    if rank == 0 and batch and not args.no_parity_check:
+    if rank == 0 and batch and "parity_check" in legs:
         # two utterances of the buffer the timed launches wrote, against the oracle (outside the timed region)
         parity = parity_check(d_audio, host_pool, sorted({0, min(batch, pool) - 1}), args.precision, args.delay, args.frames, args.output_rate, args.model)
         if not parity["pass"]:
@@ -584,16 +610,16 @@ def main():
         if dumped is not None:
             line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped, "of": "rank 0's shard, last timed step"}
         plain = not model5 and not model4
-        if world == 1 and not args.no_extras and plain:
+        if "extras" in legs:
             line["extras"] = extras(args, g, make_plan, tiled, d_audio, d_counts, stream, n_out, host_pool)
-        if world == 1 and not args.no_end_to_end and plain:
+        if "end_to_end" in legs:
             # kernel-only rates beside which the host-buffer entries are quoted
             k2s = next((e["value"] for e in line.get("extras", []) if (e["precision"], e["batch"], e["frames"], e["section_delay"]) == (args.precision, 4096, 500, 1)), None)
             e2e = end_to_end(g, make_plan(args.precision, 1), host_pool, 4096, 500, 3, k2s, "4096 x 500 frames (2 s), SectionDelay 1, %s" % args.precision)
             if (batch, args.frames) == (DEFAULT_BATCH_PER_GPU, DEFAULT_FRAMES):
                 e2e += end_to_end(g, plan, host_pool, batch, args.frames, 2, value, "BASELINE configs[3]: %d x %d frames, SectionDelay %d, %s" % (batch, args.frames, args.delay, args.precision))
             line["end_to_end"] = e2e
-        if world == 1 and not args.no_cpu_baseline:
+        if "cpu_baseline" in legs:
             # one core of this host through the compiled reference, once per reference class (float / double)
             by_class = {}
             for cls, fm in (("float", True), ("double", False)):

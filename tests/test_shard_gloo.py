@@ -83,6 +83,23 @@ def test_bench_rank_workload_defaults_match_baseline_configs():
     assert (a5.batch, a5.frames, a5.delay, a5.precision, a5.output_rate) == (256, 500, 1, "f64", 48000.0)
 
 
+def test_bench_runs_only_the_headline_without_full():
+    """A plain run times its steps and prints the line; the oracle check, extras, host-buffer entries and host-core
+    baseline come with --full alone, and there the --no-* options drop single legs."""
+    everything = {"parity_check", "extras", "end_to_end", "cpu_baseline"}
+    for argv in ([], ["--precision", "f64"], ["--model", "5"], ["--gpus", "2"], ["--no-extras"]):
+        a = bench.parse_args(argv)
+        assert not a.full and bench.full_legs(a, a.gpus) == set()
+    a = bench.parse_args(["--full"])
+    assert bench.full_legs(a, 1) == everything
+    assert bench.full_legs(bench.parse_args(["--full", "--gpus", "2"]), 2) == {"parity_check"}
+    for model in ("4", "5"):
+        assert bench.full_legs(bench.parse_args(["--full", "--model", model]), 1) == {"parity_check", "cpu_baseline"}
+    for flag, leg in (("--no-parity-check", "parity_check"), ("--no-extras", "extras"),
+                      ("--no-end-to-end", "end_to_end"), ("--no-cpu-baseline", "cpu_baseline")):
+        assert bench.full_legs(bench.parse_args(["--full", flag]), 1) == everything - {leg}
+
+
 def test_launch_plan_is_what_a_launcher_would_export():
     """`python bench.py --gpus N` without torch.distributed.run: one child per device with the launcher's environment."""
     plan = bench.launch_plan(4, ["--gpus", "4", "--steps", "3"], 29123)

@@ -6,7 +6,7 @@ set -e
 tag=${1:-r03}
 out=gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-python3 bench.py --steps 10 --warmup 2 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full --steps 10 --warmup 2 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 echo "bench done"
 C="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"
 for p in f32 mixed f64; do
@@ -29,9 +29,9 @@ for cfg in "4096 1000 2 2" "4096 1000 1 2" "4096 1000 0 2" "4096 500 2 1" "4096 
   python3 tests/tools/role_cycles.py $cfg > $out/${tag}_role_cycles_b$1_p$3_d$4.txt 2>/dev/null
 done
 python3 tests/tools/role_cycles_m5.py 256 500 > $out/${tag}_role_cycles_m5_b256.txt 2>/dev/null
-python3 bench.py --precision f64 --steps 5 --warmup 1 --no-extras > $out/${tag}_bench_f64.json 2> $out/${tag}_bench_f64.err
-python3 bench.py --model 5 --steps 10 --warmup 2 > $out/${tag}_bench_model5.json 2> $out/${tag}_bench_model5.err
-python3 bench.py --model 4 --steps 10 --warmup 2 --precision f64 > $out/${tag}_bench_model4.json 2> $out/${tag}_bench_model4.err
+python3 bench.py --full --precision f64 --steps 5 --warmup 1 --no-extras > $out/${tag}_bench_f64.json 2> $out/${tag}_bench_f64.err
+python3 bench.py --full --model 5 --steps 10 --warmup 2 > $out/${tag}_bench_model5.json 2> $out/${tag}_bench_model5.err
+python3 bench.py --full --model 4 --steps 10 --warmup 2 --precision f64 > $out/${tag}_bench_model4.json 2> $out/${tag}_bench_model4.err
 python3 tests/tools/parity_report.py > $out/${tag}_config3_parity.json 2> $out/${tag}_config3_parity.err
 python3 tests/tools/bench_aux.py > $out/${tag}_bench_aux.json 2> $out/${tag}_bench_aux.err
 python3 tests/tools/bench_models.py > $out/${tag}_bench_models.txt 2> $out/${tag}_bench_models.err

@@ -9,5 +9,5 @@ python -m pytest tests -x -q -m "not gpu"
 if [ "$1" = "gpu" ]; then
   python -m pytest tests -x -q -m gpu
   python -c "import __graft_entry__ as g; g.smoke()"
-  python bench.py
+  python bench.py --full
 fi
