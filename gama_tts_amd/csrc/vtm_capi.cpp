@@ -149,16 +149,10 @@ struct gvtm_plan {
 	std::vector<Event> slice_done; // two per slice: frames arrived, samples ready
 
 	int n_voices() const { return static_cast<int>(designs.size()); }
-	// utterances per workgroup of a launch of `batch` utterances.  Model 5: one, whatever the batch: the two-utterance shape
-	// (two tube wavefronts, chunk of 24 steps -- what LDS holds of the 62-entry tube records) measured SLOWER at every batch
-	// size (batch 512 x 250 frames: 17.3 ms against 2 x 6.97 ms; profiles/r03_role_cycles_m5.txt): the passes are
-	// latency-bound, so a chunk of 24 steps costs what one of 60 does, and the tube wavefronts slow down from 268 to 430
-	// cycles per step next to five busy helpers.  A diagnostics build can still force it (tests hold it to the
-	// one-utterance shape's samples bit for bit).
-	int rows_for(size_t batch) const
+	// the shape of a launch of `batch` utterances (vtm_kernels.hpp: synth_launch_shape; forced_rows 0: the plan's own)
+	gvtm::LaunchShape launch_shape(size_t batch, int forced_rows, bool voices, int stream_ring = 0, bool fit = true) const
 	{
-		const gvtm::Design& dg = designs[0];
-		return dg.model5 ? (rows == 2 ? 2 : 1) : gvtm::synth_rows(precision, batch, rows, dg.k.section_delay);
+		return gvtm::synth_launch_shape(designs.data(), n_voices(), precision, batch, forced_rows ? forced_rows : rows, voices, stream_ring, fit);
 	}
 };
 
@@ -477,8 +471,19 @@ int gvtm_debug_set_rows(gvtm_plan* plan, int rows)
 size_t gvtm_debug_lds_bytes(const gvtm_plan* plan, int rows)
 {
 	if (!plan) return 0;
-	if (plan->designs[0].model5) return gvtm::synth5_lds_bytes(rows == 2 ? 2 : 1);
-	return gvtm::synth_lds_bytes(plan->designs[0].k, plan->precision, rows, 0);
+	// (of these rows, whether they fit or not; rows no launch has answer as the shape a launch forced to them has)
+	return gvtm::synth_launch_shape(plan->designs.data(), 1, plan->precision, 0, rows, false, 0, false).lds;
+}
+
+/* The shape a launch of `batch` utterances of this plan takes (voices != 0: a gvtm_synthesize_voices_* launch), as
+   launch_synthesis asks for it: out = {rows, ring length, LDS bytes}.  Needs no device. */
+int gvtm_debug_launch_shape(const gvtm_plan* plan, size_t batch, int voices, size_t out[3])
+{
+	if (!plan || !out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or buffer");
+	const gvtm::LaunchShape shape = plan->launch_shape(batch, 0, voices != 0);
+	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
+	out[0] = static_cast<size_t>(shape.rows), out[1] = static_cast<size_t>(shape.ring), out[2] = shape.lds;
+	return GVTM_OK;
 }
 
 /* The plan-level noise-sample table as the host builds it (n floats or doubles); needs no device. */
@@ -714,7 +719,7 @@ struct LaunchRequest {
 	int64_t* out_counts;
 	float* maxabs;
 	void* hip_stream;
-	int rows = 0;                       // utterances per workgroup; 0 = by this launch's batch (gvtm_plan::rows_for)
+	int rows = 0;                       // utterances per workgroup; 0 = by this launch's batch (gvtm_plan::launch_shape)
 	bool voices = false;                // gvtm_synthesize_voices_*: voice_ids[b] is utterance b's voice
 	const int32_t* voice_ids = nullptr;
 	DeviceBuffer* groups = nullptr;     // voices: the caller's scratch for the row map, group voices and sort counts
@@ -847,23 +852,9 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 		}
 	}
 	const bool model5 = plan->designs[0].model5;
-	const gvtm::DeviceConstants& k = plan->designs[0].k;
-	int rows = r.rows ? r.rows : plan->rows_for(r.batch);
-	// (the voice variant has the product's shapes only: eight rows are a diagnostics build's forced shape, and model 5's
-	// voices run one utterance per workgroup, a diagnostics build's forced two-utterance shape included)
-	if (r.voices) rows = std::min(rows, model5 ? 1 : 4);
-	// the LDS holds the stream's ring (one for all shapes) or the longest ring of the voices; a shape it does not fit
-	// (a down-sampling voice carries the reference's 1024-sample ring per row) gives way to the next smaller one
-	auto ring = [&](int rw) {
-		if (r.sl) return r.sl->xr;
-		int xr = 0;
-		for (int v = 0; v < plan->n_voices(); ++v) xr = std::max(xr, gvtm::synth_ring_length(plan->designs[v].k, plan->precision, rw));
-		return xr;
-	};
-	auto lds = [&](int rw) { return model5 ? gvtm::synth5_lds_bytes(rw) : gvtm::synth_lds_bytes(k, plan->precision, rw, ring(rw)); };
-	constexpr size_t kLdsPerWorkgroup = 160 * 1024;
-	while (!model5 && rows > 1 && lds(rows) > kLdsPerWorkgroup) rows /= 2;
-	if (lds(rows) > kLdsPerWorkgroup) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
+	const gvtm::LaunchShape shape = plan->launch_shape(r.batch, r.rows, r.voices, r.sl ? r.sl->xr : 0);
+	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
+	const int rows = shape.rows;
 
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
@@ -871,7 +862,7 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	hipStream_t stream = static_cast<hipStream_t>(r.hip_stream);
 
 	gvtm::SynthArgs args = synth_args(plan, r);
-	args.xr = model5 ? 0 : ring(rows);
+	args.xr = shape.ring;
 	size_t work = r.batch; // what launch_synth takes: utterances, or with voices workgroups
 	if (r.voices) {
 		work = (r.batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices());
@@ -1050,7 +1041,8 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 	const bool ragged = counts_in != nullptr || voices || audio_stride > gvtm_output_count(plan, max_frames);
 
 	// the shape of the whole batch (every slice is launched in it), and how many utterances fill the machine once in it
-	const int rows_all = plan->rows_for(batch);
+	// (the rows the batch size picks: a launch still gives way to fewer where the LDS does not hold them)
+	const int rows_all = plan->launch_shape(batch, 0, false, 0, false).rows;
 	const size_t machine = static_cast<size_t>(rows_all) * static_cast<size_t>(plan->compute_units > 0 ? plan->compute_units : 256);
 	const size_t slice = batch >= 2 * machine ? machine : batch;
 	const size_t n_slices = (batch + slice - 1) / slice;
@@ -1360,7 +1352,7 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 				s->granule_frames.push_back(4u / gcd_u(k.control_steps, 4u));
 			} else {
 				// each voice's ring is the one-row shape's, whatever shape a launch takes (the kernel derives it per voice)
-				const int xr = gvtm::synth_ring_length(k, plan->precision, 1);
+				const int xr = gvtm::synth_launch_shape(&plan->designs[v], 1, plan->precision, 1, 1, false).ring;
 				s->xr = std::max(s->xr, xr);
 				s->state_stride = std::max(s->state_stride, gvtm::stream_state_bytes(k, plan->precision, xr));
 				// the serial wavefronts work in blocks of 2, 4 and 4 or 6 steps (vtm_kernel_v2.inc): their states are exact at

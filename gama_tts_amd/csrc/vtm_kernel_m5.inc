@@ -1,8 +1,8 @@
 // Reference model 5 (VocalTractModel5<double,1>, vtm/VocalTractModel5.h) on the device.
 // Included inside namespace gvtm, after vtm_kernel_v2.inc (whose wave-wide DPP helpers, Extent and voice_row it shares),
 // by two translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
-// (kVoices5Flag) in a code object of its own.  Besides the kernel, the file defines what both launch it with: the shape
-// constants (kM5Ring, kM5Chunk1/2, kM5Helpers1/2) and launch_synth5_shape, at the end.
+// (kVoices5Flag) in a code object of its own.  Besides the kernel, the file defines what both launch it with: the
+// description of its two shapes (m5_shape, kM5Ring), before the kernel, and launch_synth5_shape, at the end.
 //
 // Same organisation as generation 2: a workgroup owns U utterances (1 or 2; the tube has 30 + 21 = 51 sections, one
 // per lane of a wavefront, so every utterance has a tube wavefront of its own, while the scan, filter and interpolation
@@ -35,6 +35,18 @@
 //   tick c+11  H    X(c)   mouth + nose (or the glottal signal when bypassed)                             -> x ring
 //   tick c+12  H    P6(c)  sample-rate conversion, one lane per output sample                             -> y ring (float)
 //   tick c+13  H    P7(c)  difference filter * output rate (VocalTractModel5.h:507-513)                    -> HBM, peak
+
+// The kernel's two shapes.  One utterance per workgroup: chunk of 60 steps (one 64-lane pass per per-step stage), three
+// helper wavefronts.  Two utterances per workgroup (batches beyond one workgroup per compute unit): two tube wavefronts,
+// chunk of 24 steps (2 x 24 items per per-step pass; what LDS holds with two 62-entry tube records per step), five helpers.
+// Wavefronts: I, S and F, a tube wavefront per utterance, the helpers.
+struct M5Shape { int rows, chunk, helpers, waves; };
+constexpr int m5_waves(int rows, int helpers) { return 3 + rows + helpers; }
+constexpr M5Shape m5_shape(int rows)
+{
+	return rows == 2 ? M5Shape{2, 24, 5, m5_waves(2, 5)} : M5Shape{1, 60, 3, m5_waves(1, 3)};
+}
+constexpr int kM5Ring = kSrcRing; // the reference's BUFFER_SIZE: see the flush-overrun epilogue
 
 namespace m5 {
 
@@ -120,7 +132,7 @@ struct Offsets {
 constexpr int kVoices5Flag = 4;
 
 template <int C, int NH, int XR, int U_FLAGS>
-__global__ __launch_bounds__((3 + (U_FLAGS & 3) + NH) * 64) void vtm5_synth_kernel(const SynthArgs a)
+__global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_kernel(const SynthArgs a)
 {
 	constexpr int U = U_FLAGS & 3;
 	constexpr bool VOICES = (U_FLAGS & kVoices5Flag) != 0;
@@ -1189,26 +1201,24 @@ __global__ __launch_bounds__((3 + (U_FLAGS & 3) + NH) * 64) void vtm5_synth_kern
 
 } // namespace m5
 
-// reference model 5.  One utterance per workgroup: chunk of 60 steps (one 64-lane pass per per-step stage), three helper
-// wavefronts.  Two utterances per workgroup (batches beyond one workgroup per compute unit): two tube wavefronts, chunk of
-// 24 steps (2 x 24 items per per-step pass; what LDS holds with two 62-entry tube records per step), five helpers.
-constexpr int kM5Ring = kSrcRing; // the reference's BUFFER_SIZE: see the flush-overrun epilogue
-constexpr int kM5Chunk1 = 60, kM5Helpers1 = 3;
-#ifndef GVTM_TUNE_M5_NH2
-#define GVTM_TUNE_M5_NH2 5
-#endif
-constexpr int kM5Chunk2 = 24, kM5Helpers2 = GVTM_TUNE_M5_NH2;
+// LDS bytes of a workgroup of U utterances
+template <int U>
+static size_t m5_lds_bytes()
+{
+	return m5::Offsets<m5_shape(U).chunk, kM5Ring, U>().total;
+}
 
 // VOICES: a launch of several voices (the kernel's kVoices5Flag; args.row_map is set), one utterance per workgroup only;
 // `batch` is then the number of workgroups
-template <int C, int NH, int U, bool VOICES>
+template <int U, bool VOICES>
 static hipError_t launch_synth5_shape(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
 	static_assert(!VOICES || U == 1, "the voice variant has the one-utterance shape only");
-	auto fn = m5::vtm5_synth_kernel<C, NH, kM5Ring, U | (VOICES ? m5::kVoices5Flag : 0)>;
-	const size_t lds = m5::Offsets<C, kM5Ring, U>().total;
+	constexpr M5Shape s = m5_shape(U);
+	auto fn = m5::vtm5_synth_kernel<s.chunk, s.helpers, kM5Ring, U | (VOICES ? m5::kVoices5Flag : 0)>;
+	const size_t lds = m5_lds_bytes<U>();
 	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
 	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(VOICES ? batch : (batch + U - 1) / U)), dim3((3 + U + NH) * 64), lds, stream, args);
+	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(VOICES ? batch : (batch + U - 1) / U)), dim3(s.waves * 64), lds, stream, args);
 	return hipGetLastError();
 }

@@ -7,11 +7,14 @@
 //                      in vtm_kernels_m5v.hip)
 //   vtm_normalize_kernel                    output scaling of Controller::writeOutputToBuffer / writeOutputToFile
 //
+// Which shape a launch has (rows, chunk length, helpers, ring, LDS) is decided here and only here: "kernel shapes" below.
 // Everything between the parameter frames (HBM in) and the audio samples (HBM out) lives in LDS; there is no
 // intermediate global traffic.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 #include "vtm_design.hpp"
 #include "vtm_kernels.hpp"
@@ -46,56 +49,118 @@ __global__ __launch_bounds__(256) void vtm_normalize_kernel(const NormalizeArgs 
 	}
 }
 
-// kernel geometry: utterances per workgroup (DPP rows), chunk length, helper wavefronts,
-// internal-rate ring length
-template <typename CT, typename ST, int U_, int D_ = 1>
-struct V2Shape {
-	static constexpr int U = U_;
-	// Chunk length C: a multiple of 4 (scan blocks) and of the tube unroll (2 for SectionDelay 1, D for
-	// even D, 6 for 3), i.e. of 12.
-	//   U = 1: the tick time is the tube wavefront's plus what a tick costs besides (barrier, stage prologues): measured
-	//          on batch 256 in float, C = 60 / 96 / 120 / 144 / 168 / 192 -> 3.73 / 3.58 / 3.53 / 3.48 / 3.52 / 3.59 ms (108 and
-	//          180, whose last 64-item helper pass is half empty: 3.73 / 3.70); mixed 60 / 96 / 120 -> 4.19 / 4.04 / 4.15;
-	//          fp64 60 / 72 / 84 -> 4.14 / 4.65 / 4.07 (LDS ends there).  No power-of-two lengths (LDS strides).
-	//   U > 1: every tick has fixed costs (barrier, stage prologues, ticket traffic, partly filled 64-item
-	//          passes), so the longest chunk LDS allows wins: measured on batch 4096 in float, C = 24 / 36 / 48
-	//          -> 24.8 / 21.6 / 18.4 ms; batch 512, C = 24 / 48 / 96 -> 4.71 / 4.64 / 4.38 ms.
+// ---- kernel shapes ----
+//
+// A shape is what one vtm_synth_kernel launch is built from: precision <CT, ST>, SectionDelay D, utterances per workgroup
+// U (DPP rows), tube layout; and from those the chunk length C, the helper wavefronts NH, the wavefronts per workgroup,
+// the ring length and the LDS bytes.  v2_shape() below is the ONE description of it and with_shape() the ONE place where
+// a runtime (precision, rows, SectionDelay, layout) becomes template arguments: the launch, the queries of the launch
+// interface and synth_launch_shape() all go through them, so they cannot disagree.  A new shape is a new line here.
+struct KernelShape { int rows, chunk, helpers, waves; };
+
+template <typename CT, typename ST, int D, int U, int LAYOUT>
+constexpr KernelShape v2_shape()
+{
+	constexpr bool f32 = sizeof(CT) == 4, mixed = sizeof(CT) == 8 && sizeof(ST) == 4, wide = LAYOUT == 1;
+	// Chunk length C: a multiple of 4 (scan blocks) and of the tube unroll (2 for SectionDelay 1, D for even D, 6 for 3).
+	// Helpers NH: 8 resp. 12 wavefronts per workgroup on the 10 + 6 tube (16 in float with four or eight rows); the
+	// 48-section tube's workgroups have U tube wavefronts + 4 other serial ones + helpers = 8 resp. 12 (three wavefronts
+	// per SIMD: 168 registers each).
 	// LDS per workgroup: tests/tools/lds_sizes.py (float 1x144 120 KB, 2x96 152, 4x48 154; mixed 4x32 154; fp64 4x32 159).
 	// (fp64 with several rows: resampler table without its delta half)
-	static constexpr bool kAllFloat = sizeof(CT) == 4;
-	static constexpr bool kMixed = sizeof(CT) == 8 && sizeof(ST) == 4;
-#ifdef GVTM_TUNE_C1
-	static constexpr int C = (U_ == 1) ? GVTM_TUNE_C1 : (U_ == 2 ? GVTM_TUNE_C2 : GVTM_TUNE_C4);
-#else
-	// four rows in double: 32 steps = two FULL 64-item passes per stage (24 steps left the second pass half empty and
-	// made every pass a large share of a tick); SectionDelay 3 unrolls the tube by 6 and keeps 24.  (28 steps for
-	// SectionDelay 1, so that the resampler's 61.6 outputs per chunk fill ONE pass, measured slower: 12.7 vs 13.3 G.)
-	static constexpr int C = (U_ == 1) ? (kAllFloat ? 144 : (kMixed ? 96 : 84))
-	                                   : (U_ == 2 ? (kAllFloat ? 96 : 48) : (U_ == 8 ? 24 : (kAllFloat ? (D_ == 3 ? 36 : 48) : (D_ == 3 ? 24 : 32))));
-	// (float, four rows, SectionDelay 3: 36 -- reference model 3 down-samples to 44.1 kHz, so its rings are 1024 samples each,
-	// and with the lane-indexed tube record 48 steps no longer fit)
-#endif
-#ifndef GVTM_TUNE_NH_MULTI
-#define GVTM_TUNE_NH_MULTI 7
-#endif
-#ifndef GVTM_TUNE_NH_SINGLE
-#define GVTM_TUNE_NH_SINGLE 3
-#endif
-#ifndef GVTM_TUNE_NH_OCTO
-#define GVTM_TUNE_NH_OCTO 6
-#endif
-	// 8 resp. 12 wavefronts per workgroup (16 in float with four rows, below); eight rows: two wavefronts per serial role + 6 helpers = 16
-	// Float, four utterances per workgroup: ELEVEN helpers = 16 wavefronts, the most a workgroup can have (128 registers
-	// each).  With the tube record in blocks of four steps the tube and pre-tube filter wavefronts need 177 / 150 cycles per
-	// step and the helper pool is the tick: same box, 4096 utterances, SectionDelay 2 x 2000 frames: 7 / 8 / 9 / 11 helpers
-	// -> 107.6 / 106.2 / 103.6 / 100.0 ms; SectionDelay 1 x 500 frames: 14.24 / 14.00 / 13.68 / 13.11 ms.  (Round 2, when
-	// the tube was the tick: 14 / 16 wavefronts 63.0 -> 62.6 ms.  The double models spill at 128 registers: fp64 22.8 -> 24.5 ms.)
-#ifndef GVTM_TUNE_NH_F32_4
-#define GVTM_TUNE_NH_F32_4 11
-#endif
-	static constexpr int NH = (U_ == 1) ? GVTM_TUNE_NH_SINGLE : (U_ == 8 ? GVTM_TUNE_NH_OCTO : ((U_ == 4 && kAllFloat) ? GVTM_TUNE_NH_F32_4 : GVTM_TUNE_NH_MULTI));
-	static constexpr int kWaves = 5 * ((U_ + 3) / 4) + NH;
+	int C = 0, NH = 0;
+	switch (U) {
+	case 1:
+		// the tick time is the tube wavefront's plus what a tick costs besides (barrier, stage prologues): measured
+		// on batch 256 in float, C = 60 / 96 / 120 / 144 / 168 / 192 -> 3.73 / 3.58 / 3.53 / 3.48 / 3.52 / 3.59 ms (108 and
+		// 180, whose last 64-item helper pass is half empty: 3.73 / 3.70); mixed 60 / 96 / 120 -> 4.19 / 4.04 / 4.15;
+		// fp64 60 / 72 / 84 -> 4.14 / 4.65 / 4.07 (LDS ends there).  No power-of-two lengths (LDS strides).
+		C = f32 ? 144 : (mixed ? 96 : 84), NH = 3;
+		break;
+	case 2:
+		// U > 1: every tick has fixed costs (barrier, stage prologues, ticket traffic, partly filled 64-item
+		// passes), so the longest chunk LDS allows wins: measured on batch 4096 in float, C = 24 / 36 / 48
+		// -> 24.8 / 21.6 / 18.4 ms; batch 512, C = 24 / 48 / 96 -> 4.71 / 4.64 / 4.38 ms.
+		C = f32 ? 96 : 48, NH = wide ? 6 : 7;
+		break;
+	case 4:
+		// in double: 32 steps = two FULL 64-item passes per stage (24 steps left the second pass half empty and
+		// made every pass a large share of a tick); SectionDelay 3 unrolls the tube by 6 and keeps 24.  (28 steps for
+		// SectionDelay 1, so that the resampler's 61.6 outputs per chunk fill ONE pass, measured slower: 12.7 vs 13.3 G.)
+		// (float, SectionDelay 3: 36 -- reference model 3 down-samples to 44.1 kHz, so its rings are 1024 samples each,
+		// and with the lane-indexed tube record 48 steps no longer fit)
+		C = f32 ? (D == 3 ? 36 : 48) : (D == 3 ? 24 : 32);
+		// Float: ELEVEN helpers = 16 wavefronts, the most a workgroup can have (128 registers each).  With the tube
+		// record in blocks of four steps the tube and pre-tube filter wavefronts need 177 / 150 cycles per step and the
+		// helper pool is the tick: same box, 4096 utterances, SectionDelay 2 x 2000 frames: 7 / 8 / 9 / 11 helpers
+		// -> 107.6 / 106.2 / 103.6 / 100.0 ms; SectionDelay 1 x 500 frames: 14.24 / 14.00 / 13.68 / 13.11 ms.  (Round 2, when
+		// the tube was the tick: 14 / 16 wavefronts 63.0 -> 62.6 ms.  The double models spill at 128 registers: fp64 22.8 -> 24.5 ms.)
+		NH = wide ? 4 : (f32 ? 11 : 7);
+		break;
+	case 8:
+		// float on the 10 + 6 tube only: two wavefronts per serial role + 6 helpers = 16
+		C = 24, NH = 6;
+		break;
+	}
+	return KernelShape{U, C, NH, v2::serial_waves<U, LAYOUT>() + NH};
+}
+
+template <typename CT_, typename ST_, int D_, int U_, int LAYOUT_>
+struct V2Shape {
+	using CT = CT_;
+	using ST = ST_;
+	static constexpr int D = D_, U = U_, LAYOUT = LAYOUT_;
+	static constexpr KernelShape k = v2_shape<CT, ST, D, U, LAYOUT>();
+	static constexpr int C = k.chunk, NH = k.helpers, kWaves = k.waves;
+	static_assert(U == 1 || U == 2 || U == 4 || (U == 8 && sizeof(CT) == 4 && LAYOUT == 0), "eight rows: float on the 10 + 6 tube only");
+	static_assert(LAYOUT == 0 || (LAYOUT == 1 && D == 1), "the 48-lane layout runs with SectionDelay 1");
+	static_assert(D >= 1 && D <= kMaxSectionDelay && C > 0 && C % 4 == 0 && C % (D == 3 ? 6 : (D == 1 ? 2 : D)) == 0, "chunk: whole scan blocks and tube unrolls");
+	static_assert(kWaves <= 16, "a workgroup has at most 16 wavefronts");
+	// (a stream keeps ONE ring length for all shapes, the one-row shape's: longer than this shape needs, never shorter)
+	static_assert(C <= v2_shape<CT, ST, D, 1, LAYOUT>().chunk, "a stream's ring, the one-row shape's, holds every shape's chunks");
+	// LDS bytes of a workgroup whose internal-rate rings hold xr samples each
+	static size_t lds_bytes(int xr) { return v2::smem_bytes<CT, ST, U, C, v2::lane_rec<CT, LAYOUT>()>(xr); }
 };
+
+// Calls f(V2Shape<...>{}) for the shape of a runtime (precision, rows, SectionDelay, layout); `refused` where there is none.
+// Eight rows exist in float only; the 48-lane layout (VocalTractModel4: 48 section lanes = one utterance per tube
+// wavefront) has SectionDelay 1 only and up to four tube wavefronts per workgroup, so more rows become four.
+// f must not name the kernel unless it launches it: naming vtm_synth_kernel<...> instantiates it.
+template <typename R, typename F>
+static R with_shape(int precision, int rows, int delay, int layout, R refused, F f)
+{
+	const bool wide = layout == 1;
+	auto with_delay = [&](auto ct, auto st, auto u) -> R {
+		using CT = decltype(ct);
+		using ST = decltype(st);
+		constexpr int U = decltype(u)::value;
+		if (wide) return delay == 1 ? f(V2Shape<CT, ST, 1, (U < 4 ? U : 4), 1>{}) : refused;
+		switch (delay) {
+		case 1: return f(V2Shape<CT, ST, 1, U, 0>{});
+		case 2: return f(V2Shape<CT, ST, 2, U, 0>{});
+		case 3: return f(V2Shape<CT, ST, 3, U, 0>{});
+		case 4: return f(V2Shape<CT, ST, 4, U, 0>{});
+		}
+		return refused;
+	};
+	auto with_rows = [&](auto ct, auto st) -> R {
+		if constexpr (sizeof(ct) == 4) {
+			if (rows == 8) return with_delay(ct, st, std::integral_constant<int, 8>{});
+		}
+		switch (rows) {
+		case 4: return with_delay(ct, st, std::integral_constant<int, 4>{});
+		case 2: return with_delay(ct, st, std::integral_constant<int, 2>{});
+		case 1: return with_delay(ct, st, std::integral_constant<int, 1>{});
+		}
+		return refused;
+	};
+	switch (precision) {
+	case GVTM_PRECISION_F32: return with_rows(float{}, float{});
+	case GVTM_PRECISION_MIXED: return with_rows(double{}, float{});
+	case GVTM_PRECISION_F64: return with_rows(double{}, double{});
+	}
+	return refused;
+}
 
 // internal-rate ring of a workgroup row (vtm_design.hpp: synth_ring_for)
 static int ring_length(const DeviceConstants& k, int chunk)
@@ -103,166 +168,102 @@ static int ring_length(const DeviceConstants& k, int chunk)
 	return synth_ring_for(k.upsampling, k.pad, chunk);
 }
 
-// helper wavefronts of the 48-section tube's workgroups: U tube wavefronts + 4 other serial ones + helpers = 12
-// (three wavefronts per SIMD: 168 registers each)
-#ifndef GVTM_TUNE_WIDE_NH2
-#define GVTM_TUNE_WIDE_NH2 6
-#endif
-#ifndef GVTM_TUNE_WIDE_NH4
-#define GVTM_TUNE_WIDE_NH4 4
-#endif
-template <int U>
-constexpr int wide_helpers()
-{
-	return U == 1 ? GVTM_TUNE_NH_SINGLE : (U == 2 ? GVTM_TUNE_WIDE_NH2 : GVTM_TUNE_WIDE_NH4);
-}
-
 // VOICES: a launch of several voices (the kernel's kVoicesFlag; args.row_map is set); `batch` is then the number of
 // workgroups, and args.xr the longest ring of the launch's voices (what the LDS is sized for; a stream's: of the voices'
 // stream rings, which args.stream_chunk fixes)
-template <typename CT, typename ST, int D, int U, int LAYOUT, bool VOICES>
+template <typename S, bool VOICES>
 static hipError_t launch_v2(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
-	using S = V2Shape<CT, ST, U, D>;
-	constexpr int NH = LAYOUT == 1 ? wide_helpers<U>() : S::NH;
-	constexpr int kWaves = v2::serial_waves<U, LAYOUT>() + NH;
-	auto fn = v2::vtm_synth_kernel<CT, ST, D, S::U, S::C, NH, LAYOUT | (VOICES ? v2::kVoicesFlag : 0)>;
-	// (a stream keeps ONE ring length for all shapes, the one-row shape's: longer than this shape needs, never shorter)
-	if (args.xr < ring_length(args.k, S::C) || (args.xr & (args.xr - 1)) != 0 || 2 * S::C + 4 * args.k.pad + 64 > args.xr) return hipErrorInvalidValue;
-	if (!args.k.upsampling && args.xr != kSrcRing) return hipErrorInvalidValue;
-	const size_t lds = v2::smem_bytes<CT, ST, S::U, S::C, v2::lane_rec<CT, LAYOUT>()>(args.xr);
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-			static_cast<int>(lds));
-	if (e != hipSuccess) return e;
-	const unsigned groups = static_cast<unsigned>(VOICES ? batch : (batch + S::U - 1) / S::U);
-	hipLaunchKernelGGL(fn, dim3(groups), dim3(kWaves * 64), lds, stream, args);
-	return hipGetLastError();
+	if constexpr (VOICES && S::U == 8) {
+		// several voices: the product's shapes only (eight rows are a diagnostics build's forced shape)
+		return hipErrorInvalidValue;
+	} else {
+		auto fn = v2::vtm_synth_kernel<typename S::CT, typename S::ST, S::D, S::U, S::C, S::NH, S::LAYOUT | (VOICES ? v2::kVoicesFlag : 0)>;
+		if (args.xr < ring_length(args.k, S::C) || (args.xr & (args.xr - 1)) != 0 || 2 * S::C + 4 * args.k.pad + 64 > args.xr) return hipErrorInvalidValue;
+		if (!args.k.upsampling && args.xr != kSrcRing) return hipErrorInvalidValue;
+		const size_t lds = S::lds_bytes(args.xr);
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+				static_cast<int>(lds));
+		if (e != hipSuccess) return e;
+		const unsigned groups = static_cast<unsigned>(VOICES ? batch : (batch + S::U - 1) / S::U);
+		hipLaunchKernelGGL(fn, dim3(groups), dim3(S::kWaves * 64), lds, stream, args);
+		return hipGetLastError();
+	}
 }
 
-int synth_rows(int precision, size_t batch, int requested, int section_delay)
+hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream)
 {
-	// utterances per workgroup = DPP rows used by the serial wavefronts.  One row keeps the most
-	// workgroups in flight (best latency for small batches); more rows amortise the serial
-	// instruction streams once there are more utterances than compute units.
-	// eight rows (two wavefronts per serial role) fit in float only
-	const int max_rows = precision == GVTM_PRECISION_F32 ? 8 : 4;
-	int rows = requested;
-	if (rows != 1 && rows != 2 && rows != 4 && rows != 8) {
-		rows = batch > 512 ? 4 : (batch > 256 ? 2 : 1);
-		// (fp64 used to stop at two rows: with the compact records four fit with a chunk of 32 and run faster)
-		// mixed with SectionDelay 3 or 4 (deeper fp64 delay lines per lane): measured 3.36 vs 2.63 and 2.07 vs 1.65 G samples/s
-		if (precision != GVTM_PRECISION_F32 && section_delay >= 3 && rows > 2) rows = 2;
-	}
-	return rows > max_rows ? max_rows : rows;
-}
-
-// what depends on the workgroup shape V2Shape picks: chunk length -> ring length -> LDS bytes
-struct ShapeNumbers { int chunk; size_t lds_fixed; size_t ring_elem; };
-
-template <typename CT, typename ST, int U, int D>
-static ShapeNumbers v2_numbers(int layout)
-{
-	using S = V2Shape<CT, ST, U, D>;
-	const size_t lds = layout == 1 ? v2::smem_bytes<CT, ST, S::U, S::C, v2::lane_rec<CT, 1>()>(0) : v2::smem_bytes<CT, ST, S::U, S::C, v2::lane_rec<CT, 0>()>(0);
-	return ShapeNumbers{S::C, lds, sizeof(ST) * S::U};
-}
-
-template <typename CT, typename ST, int D>
-static ShapeNumbers v2_numbers_rows(int rows, int layout)
-{
-	if constexpr (sizeof(CT) == 4) {
-		if (rows == 8) return v2_numbers<CT, ST, 8, D>(layout);
-	}
-	return rows == 4 ? v2_numbers<CT, ST, 4, D>(layout) : (rows == 2 ? v2_numbers<CT, ST, 2, D>(layout) : v2_numbers<CT, ST, 1, D>(layout));
-}
-
-static ShapeNumbers shape_numbers(int precision, int rows, int delay, int layout)
-{
-	// the chunk length depends on the SectionDelay through "1, 3 or another"
-	if (delay == 3) {
-		if (precision == GVTM_PRECISION_F32) return v2_numbers_rows<float, float, 3>(rows, layout);
-		if (precision == GVTM_PRECISION_MIXED) return v2_numbers_rows<double, float, 3>(rows, layout);
-		return v2_numbers_rows<double, double, 3>(rows, layout);
-	}
-	if (delay != 1) {
-		if (precision == GVTM_PRECISION_F32) return v2_numbers_rows<float, float, 2>(rows, layout);
-		if (precision == GVTM_PRECISION_MIXED) return v2_numbers_rows<double, float, 2>(rows, layout);
-		return v2_numbers_rows<double, double, 2>(rows, layout);
-	}
-	if (precision == GVTM_PRECISION_F32) return v2_numbers_rows<float, float, 1>(rows, layout);
-	if (precision == GVTM_PRECISION_MIXED) return v2_numbers_rows<double, float, 1>(rows, layout);
-	return v2_numbers_rows<double, double, 1>(rows, layout);
+	const auto launch = [&](auto voices) {
+		return with_shape(precision, rows, args.k.section_delay, args.k.layout, hipErrorInvalidValue,
+				[&](auto s) { return launch_v2<decltype(s), decltype(voices)::value>(args, batch, stream); });
+	};
+	// (one pass over the shapes per variant, single voice first: the order the code object has its kernels in)
+	if (!args.row_map) return launch(std::false_type{});
+	if (!args.group_voice) return hipErrorInvalidValue;
+	return launch(std::true_type{});
 }
 
 int synth_chunk_length(const DeviceConstants& k, int precision, int rows)
 {
-	return shape_numbers(precision, rows, k.section_delay, k.layout).chunk;
-}
-
-int synth_ring_length(const DeviceConstants& k, int precision, int rows)
-{
-	return ring_length(k, synth_chunk_length(k, precision, rows));
+	return with_shape(precision, rows, k.section_delay, k.layout, 0, [](auto s) { return decltype(s)::C; });
 }
 
 size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr)
 {
 	const int lanes = k.layout == 1 ? 48 : 16, words = 2 * k.section_delay + 1;
-	if (precision == GVTM_PRECISION_F32) return StreamLayout<float, float>::bytes(lanes, words, xr);
-	if (precision == GVTM_PRECISION_MIXED) return StreamLayout<double, float>::bytes(lanes, words, xr);
-	return StreamLayout<double, double>::bytes(lanes, words, xr);
+	return with_shape(precision, 1, k.section_delay, k.layout, size_t(0), [&](auto s) {
+		return StreamLayout<typename decltype(s)::CT, typename decltype(s)::ST>::bytes(lanes, words, xr);
+	});
 }
 
-size_t synth_lds_bytes(const DeviceConstants& k, int precision, int rows, int xr)
+// the shape of `rows` utterances per workgroup of one voice: its rows as launched, its ring (xr, or with xr == 0 its own)
+// and its LDS bytes; rows == 0 where there is no such shape
+static LaunchShape shape_of_rows(const DeviceConstants& k, int precision, int rows, int xr)
 {
-	const ShapeNumbers n = shape_numbers(precision, rows, k.section_delay, k.layout);
-	return n.lds_fixed + ((n.ring_elem * static_cast<size_t>(xr > 0 ? xr : ring_length(k, n.chunk)) + 15) & ~size_t(15));
+	return with_shape(precision, rows, k.section_delay, k.layout, LaunchShape{}, [&](auto s) {
+		using S = decltype(s);
+		const int ring = xr > 0 ? xr : ring_length(k, S::C);
+		return LaunchShape{S::U, ring, S::lds_bytes(ring)};
+	});
 }
 
-template <typename CT, typename ST, int U, bool VOICES>
-static hipError_t launch_v2_d(const SynthArgs& args, size_t batch, hipStream_t stream)
+LaunchShape synth_launch_shape(const Design* voices, int n_voices, int precision, size_t batch, int forced_rows, bool several_voices,
+		int stream_ring, bool fit)
 {
-	if (args.k.layout == 1) {
-		// VocalTractModel4: 48 section lanes = one utterance per tube wavefront (up to four of them per
-		// workgroup), SectionDelay 1 only
-		if (args.k.section_delay != 1) return hipErrorInvalidValue;
-		if constexpr (U >= 4) return launch_v2<CT, ST, 1, 4, 1, VOICES>(args, batch, stream);
-		else return launch_v2<CT, ST, 1, U, 1, VOICES>(args, batch, stream);
+	const auto fits = [&](const LaunchShape& s) { return !fit || s.lds <= kLdsPerWorkgroup; };
+	if (voices[0].model5) {
+		// Model 5: one, whatever the batch: the two-utterance shape (two tube wavefronts, chunk of 24 steps -- what LDS
+		// holds of the 62-entry tube records) measured SLOWER at every batch size (batch 512 x 250 frames: 17.3 ms against
+		// 2 x 6.97 ms; profiles/r03_role_cycles_m5.txt): the passes are latency-bound, so a chunk of 24 steps costs what
+		// one of 60 does, and the tube wavefronts slow down from 268 to 430 cycles per step next to five busy helpers.  A
+		// diagnostics build can still force it (tests hold it to the one-utterance shape's samples bit for bit); the
+		// voice variant has the one-utterance shape only.
+		const int rows = forced_rows == 2 && !several_voices ? 2 : 1;
+		const LaunchShape s{rows, 0, rows == 2 ? m5_lds_bytes<2>() : m5_lds_bytes<1>()};
+		return fits(s) ? s : LaunchShape{};
 	}
-	switch (args.k.section_delay) {
-	case 1: return launch_v2<CT, ST, 1, U, 0, VOICES>(args, batch, stream);
-	case 2: return launch_v2<CT, ST, 2, U, 0, VOICES>(args, batch, stream);
-	case 3: return launch_v2<CT, ST, 3, U, 0, VOICES>(args, batch, stream);
-	case 4: return launch_v2<CT, ST, 4, U, 0, VOICES>(args, batch, stream);
+	// utterances per workgroup = DPP rows used by the serial wavefronts.  One row keeps the most
+	// workgroups in flight (best latency for small batches); more rows amortise the serial
+	// instruction streams once there are more utterances than compute units.
+	int rows = forced_rows;
+	if (rows != 1 && rows != 2 && rows != 4 && rows != 8) {
+		rows = batch > 512 ? 4 : (batch > 256 ? 2 : 1);
+		// (fp64 used to stop at two rows: with the compact records four fit with a chunk of 32 and run faster)
+		// mixed with SectionDelay 3 or 4 (deeper fp64 delay lines per lane): measured 3.36 vs 2.63 and 2.07 vs 1.65 G samples/s
+		if (precision != GVTM_PRECISION_F32 && voices[0].k.section_delay >= 3 && rows > 2) rows = 2;
 	}
-	return hipErrorInvalidValue;
-}
-
-template <typename CT, typename ST, bool VOICES>
-static hipError_t launch_v2_rows(const SynthArgs& args, size_t batch, int rows, hipStream_t stream)
-{
-	if constexpr (sizeof(CT) == 4 && !VOICES) {
-		if (rows == 8) return launch_v2_d<CT, ST, 8, VOICES>(args, batch, stream);
+	// eight rows (two wavefronts per serial role) fit in float only, and the voice variant has the product's shapes only
+	if (rows > 4 && (precision != GVTM_PRECISION_F32 || several_voices)) rows = 4;
+	// the LDS holds the stream's ring (one for all shapes) or the longest ring of the voices; a shape it does not fit
+	// (a down-sampling voice carries the reference's 1024-sample ring per row) gives way to the next smaller one
+	for (;; rows /= 2) {
+		int ring = stream_ring;
+		for (int v = 0; !stream_ring && v < n_voices; ++v) ring = std::max(ring, shape_of_rows(voices[v].k, precision, rows, 0).ring);
+		const LaunchShape s = shape_of_rows(voices[0].k, precision, rows, ring);
+		if (s.rows == 0 || fits(s)) return s;
+		if (s.rows == 1) return LaunchShape{};
+		rows = s.rows;
 	}
-	if (rows == 4) return launch_v2_d<CT, ST, 4, VOICES>(args, batch, stream);
-	if (rows == 2) return launch_v2_d<CT, ST, 2, VOICES>(args, batch, stream);
-	// several voices: the product's shapes only (synth_rows picks 1, 2 or 4 rows; eight are a diagnostics build's forced shape)
-	if (VOICES && rows != 1) return hipErrorInvalidValue;
-	return launch_v2_d<CT, ST, 1, VOICES>(args, batch, stream);
-}
-
-template <bool VOICES>
-static hipError_t launch_v2_precision(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream)
-{
-	if (precision == GVTM_PRECISION_F32) return launch_v2_rows<float, float, VOICES>(args, batch, rows, stream);
-	if (precision == GVTM_PRECISION_MIXED) return launch_v2_rows<double, float, VOICES>(args, batch, rows, stream);
-	return launch_v2_rows<double, double, VOICES>(args, batch, rows, stream);
-}
-
-hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream)
-{
-	if (!args.row_map) return launch_v2_precision<false>(args, batch, precision, rows, stream);
-	if (!args.group_voice) return hipErrorInvalidValue;
-	return launch_v2_precision<true>(args, batch, precision, rows, stream);
 }
 
 // The row map of a launch of several voices, on the device (the launch stays enqueue-only): a stable counting sort of the
@@ -323,18 +324,13 @@ hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream)
 	return hipGetLastError();
 }
 
-size_t synth5_lds_bytes(int rows)
-{
-	return rows == 2 ? m5::Offsets<kM5Chunk2, kM5Ring, 2>().total : m5::Offsets<kM5Chunk1, kM5Ring, 1>().total;
-}
-
 hipError_t launch_synth5(const SynthArgs& args, size_t batch, int rows, hipStream_t stream)
 {
 	if (!args.k5const) return hipErrorInvalidValue;
 	// (the voice variant lives in vtm_kernels_m5v.hip: this file's code object keeps the single-voice kernels only)
 	if (!args.row_map) {
-		if (rows == 2) return launch_synth5_shape<kM5Chunk2, kM5Helpers2, 2, false>(args, batch, stream);
-		return launch_synth5_shape<kM5Chunk1, kM5Helpers1, 1, false>(args, batch, stream);
+		if (rows == 2) return launch_synth5_shape<2, false>(args, batch, stream);
+		return launch_synth5_shape<1, false>(args, batch, stream);
 	}
 	if (!args.group_voice || rows != 1) return hipErrorInvalidValue;
 	return launch_synth5_voices(args, batch, stream);

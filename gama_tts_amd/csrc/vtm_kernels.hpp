@@ -84,7 +84,7 @@ struct SynthArgs {
 	size_t max_frames;
 	size_t audio_stride;
 	size_t batch;
-	int xr;                      // internal-rate ring length per utterance (a power of two; synth_ring_length())
+	int xr;                      // internal-rate ring length per utterance (a power of two; synth_launch_shape())
 	unsigned char* stream = nullptr; // null, or [batch] stream states of stream_stride bytes each (layout above)
 	size_t stream_stride = 0;
 	int stream_mode = kStreamNone;   // StreamMode
@@ -125,16 +125,24 @@ struct NormalizeArgs {
 	size_t audio_stride;
 };
 
-// rows: utterances per workgroup (1, 2, 4 or 8); synth_rows() picks it from the batch size unless `requested` names one
-// precision: gvtm_precision
-int synth_rows(int precision, size_t batch, int requested, int section_delay = 1);
-// internal-rate ring length for a plan: the reference's BUFFER_SIZE (1024) when down-sampling, so that the flush
-// overrun aliases as the reference's ring does; otherwise the smallest power of two holding two chunks, the
-// resampler's history and the flush zeros
-int synth_ring_length(const DeviceConstants& k, int precision, int rows);
-// the chunk length (internal steps per tick) of that shape, which synth_ring_length follows
+// The shape of one synthesis launch: utterances per workgroup (1, 2, 4 or 8; model 5: 1 or 2), samples of an utterance's
+// internal-rate ring (model 5: 0, its ring is a constant of its kernel), LDS bytes per workgroup.  rows == 0: none fits.
+struct LaunchShape {
+	int rows = 0;
+	int ring = 0;
+	size_t lds = 0;
+};
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;
+// THE row choice, for every caller.  voices: the plan's designs (voices[0] says whether model 5); forced_rows: 1, 2, 4 or 8
+// (model 5: 2) names the rows, anything else leaves them to `batch`; several_voices: the kernel's voice variant (at most
+// 4 rows, model 5: 1); stream_ring: a stream's fixed ring, or 0 for the longest own ring of the voices (the reference's
+// BUFFER_SIZE (1024) when down-sampling, so that the flush overrun aliases as the reference's ring does; otherwise the
+// smallest power of two holding two chunks, the resampler's history and the flush zeros).  With `fit`, rows whose LDS
+// exceeds kLdsPerWorkgroup give way to half as many (not model 5) or to "none fits"; without, they stay whatever their LDS.
+LaunchShape synth_launch_shape(const Design* voices, int n_voices, int precision, size_t batch, int forced_rows, bool several_voices,
+		int stream_ring = 0, bool fit = true);
+// the chunk length (internal steps per tick) of a shape, which its own ring length follows; 0: no such shape
 int synth_chunk_length(const DeviceConstants& k, int precision, int rows);
-size_t synth_lds_bytes(const DeviceConstants& k, int precision, int rows, int xr = 0 /* 0: the shape's own ring length */);
 // batch: utterances, or with args.row_map set (several voices) the workgroups of launch_group_voices' map, of one voice
 // each (args.xr: the longest ring of the voices; a stream's rings follow args.stream_chunk)
 hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream);
@@ -145,7 +153,6 @@ size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr);
 hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream);
 // reference model 5 (VocalTractModel5<double,1>), fp64: rows = utterances per workgroup, 1 or 2; with args.row_map set
 // (several voices: one constants block of each kind per voice) 1 only, and `batch` is the number of workgroups
-size_t synth5_lds_bytes(int rows = 1);
 hipError_t launch_synth5(const SynthArgs& args, size_t batch, int rows, hipStream_t stream);
 // the voice variant alone (vtm_kernels_m5v.hip; launch_synth5 calls it): `groups` workgroups of one utterance each
 hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_t stream);

@@ -20,7 +20,7 @@ namespace {
 
 hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_t stream)
 {
-	return launch_synth5_shape<kM5Chunk1, kM5Helpers1, 1, true>(args, groups, stream);
+	return launch_synth5_shape<1, true>(args, groups, stream);
 }
 
 } // namespace gvtm
