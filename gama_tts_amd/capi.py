@@ -195,6 +195,13 @@ def load_library(diagnostics=False):
         L.gvtm_synthesize_voices_host.restype = i32
         L.gvtm_synthesize_voices_host_pcm16.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
         L.gvtm_synthesize_voices_host_pcm16.restype = i32
+    if hasattr(L, "gvtm_plan_set_voice_tracks"):
+        L.gvtm_plan_set_voice_tracks.argtypes = [vp, ctypes.POINTER(TrackConfig), sz]
+        L.gvtm_plan_set_voice_tracks.restype = i32
+        L.gvtm_generate_tracks_voices_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
+        L.gvtm_generate_tracks_voices_device.restype = i32
+        L.gvtm_synthesize_events_voices_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
+        L.gvtm_synthesize_events_voices_device.restype = i32
     if hasattr(L, "gvtm_plan_create_model5_voices"):
         L.gvtm_plan_create_model5_voices.argtypes = [ctypes.POINTER(Config5), sz, dbl, i32, ctypes.POINTER(vp)]
         L.gvtm_plan_create_model5_voices.restype = i32
@@ -548,6 +555,27 @@ class VoicesPlan(Plan):
         self._check(self._lib.gvtm_synthesize_voices_device(
             self._h, _ptr(d_params), _ptr(d_frame_counts), _ptr(d_voice_ids), int(max_frames), int(batch), _ptr(d_audio),
             int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(stream)))
+
+    def set_voice_tracks(self, configs):
+        """gvtm_plan_set_voice_tracks: configs[v] is the TrackConfig of voice v (one per voice of the plan)."""
+        configs = list(configs)
+        arr = (TrackConfig * max(len(configs), 1))(*configs)
+        self._check(self._lib.gvtm_plan_set_voice_tracks(self._h, arr, len(configs)))
+
+    def generate_tracks_voices_device(self, d_events, d_offsets, d_voice_ids, batch, max_frames, d_params, d_frame_counts=None,
+                                      d_drift=None, stream=None):
+        """gvtm_generate_tracks_voices_device; all pointers are device memory."""
+        self._check(self._lib.gvtm_generate_tracks_voices_device(
+            self._h, _ptr(d_events), _ptr(d_offsets), _ptr(d_voice_ids), int(batch), int(max_frames), _ptr(d_params),
+            _ptr(d_frame_counts), _ptr(d_drift), _ptr(stream)))
+
+    def synthesize_events_voices_device(self, d_events, d_offsets, d_voice_ids, batch, max_frames, d_audio, audio_stride,
+                                        d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, stream=None):
+        """Event lists of a mix of voices in, samples out (gvtm_synthesize_events_voices_device); all pointers are device
+        memory."""
+        self._check(self._lib.gvtm_synthesize_events_voices_device(
+            self._h, _ptr(d_events), _ptr(d_offsets), _ptr(d_voice_ids), int(batch), int(max_frames), _ptr(d_audio),
+            int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift), _ptr(stream)))
 
     def _host_args(self, params, voice_ids, frame_counts):
         params = np.ascontiguousarray(params, dtype=np.float32)

@@ -137,6 +137,10 @@ struct gvtm_plan {
 	struct {
 		DeviceBuffer params, frames, groups;
 	} async;
+	// gvtm_plan_set_voice_tracks: one designed track configuration per voice, and (device plans) the table the voice
+	// variant of the tracks kernel reads; empty until the first call that succeeds
+	std::vector<gvtm::TrackConstants> voice_tracks;
+	DeviceBuffer d_voice_tracks;
 	int compute_units = 0; // of the plan's device (the host entries cut big batches into slices that fill them once)
 	// kernel timing (HIP events on the launch stream)
 	bool timing = false;
@@ -316,7 +320,13 @@ int create_plan(const Config* configs, size_t n_voices, double control_rate, int
 int refuse_voices(const gvtm_plan* plan, const char* entry)
 {
 	return fail(GVTM_ERR_INVALID_ARGUMENT, std::string(entry) + ": the plan has " + std::to_string(plan->n_voices()) +
-			" voices; use gvtm_synthesize_voices_* (one voice id per utterance)");
+			" voices; use gvtm_synthesize_voices_* resp. gvtm_synthesize_events_voices_device (one voice id per utterance)");
+}
+
+// does the track configuration's control period agree with the plan's control rate?
+bool control_period_matches(const gvtm_plan* plan, const gvtm::TrackConstants& tk)
+{
+	return static_cast<double>(tk.control_period) * plan->designs[0].control_rate == 1000.0;
 }
 
 void fill_info(const gvtm_plan* plan, const gvtm::Design& dg, gvtm_info* info)
@@ -824,6 +834,18 @@ int timed_launch(gvtm_plan* plan, hipStream_t stream, const char* what, Launch l
 	return GVTM_OK;
 }
 
+// a one-shot launch's rows hold max_frames frames of every voice
+int check_audio_stride(const gvtm_plan* plan, size_t audio_stride, size_t max_frames, bool voices)
+{
+	for (int v = 0; v < plan->n_voices(); ++v) {
+		if (audio_stride < design_output_count(plan->designs[v], max_frames)) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, voices ? "audio_stride smaller than gvtm_voice_output_count(plan, voice, max_frames) of voice " + std::to_string(v)
+			                                              : "audio_stride smaller than gvtm_output_count(plan, max_frames)");
+		}
+	}
+	return GVTM_OK;
+}
+
 // Every synthesis launch, enqueue-only.  With voices, the grouping kernel first builds the row map from the voice ids, then
 // the voice variant of the synthesis kernel runs ceil(batch / rows) + n_voices workgroups (the bound for any mix of ids;
 // those past the last voice's groups exit at once), each on one voice's constants, wavetable and ring.
@@ -845,11 +867,9 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
 	}
 	// (a stream checks its stride against what each call produces: stream_launch)
-	for (int v = 0; !r.sl && v < plan->n_voices(); ++v) {
-		if (r.audio_stride < design_output_count(plan->designs[v], r.max_frames)) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, r.voices ? "audio_stride smaller than gvtm_voice_output_count(plan, voice, max_frames) of voice " + std::to_string(v)
-			                                                : "audio_stride smaller than gvtm_output_count(plan, max_frames)");
-		}
+	if (!r.sl) {
+		const int rc = check_audio_stride(plan, r.audio_stride, r.max_frames, r.voices);
+		if (rc != GVTM_OK) return rc;
 	}
 	const bool model5 = plan->designs[0].model5;
 	const gvtm::LaunchShape shape = plan->launch_shape(r.batch, r.rows, r.voices, r.sl ? r.sl->xr : 0);
@@ -916,7 +936,7 @@ int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* conf
 	gvtm::TrackConstants tk{};
 	const char* why = gvtm::design_tracks(*config, tk);
 	if (why[0]) return fail(GVTM_ERR_INVALID_ARGUMENT, why);
-	if (static_cast<double>(tk.control_period) * plan->designs[0].control_rate != 1000.0) {
+	if (!control_period_matches(plan, tk)) {
 		return fail(GVTM_ERR_INVALID_ARGUMENT, "control_period_ms of the track configuration and the plan's control rate disagree");
 	}
 	// Two launches on the caller's stream with a frame buffer of the plan's in between (the enqueue-only entries' scratch).  (Walking the event lists inside the
@@ -935,6 +955,119 @@ int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* conf
 	if (rc != GVTM_OK) return rc;
 	return launch_synthesis(plan, LaunchRequest{static_cast<const float*>(plan->async.params.ptr), counts, batch, max_frames, d_audio, audio_stride,
 			d_out_counts, d_maxabs, hip_stream});
+}
+
+int gvtm_plan_set_voice_tracks(gvtm_plan* plan, const gvtm_track_config* configs, size_t n_configs)
+{
+	if (!plan || !configs) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or configs");
+	if (n_configs != static_cast<size_t>(plan->n_voices())) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, std::to_string(n_configs) + " track configurations for a plan of " + std::to_string(plan->n_voices()) + " voices");
+	}
+	try {
+		// (the whole table is designed before any of it replaces the plan's: a refused call changes nothing)
+		std::vector<gvtm::TrackConstants> table(n_configs);
+		for (size_t v = 0; v < n_configs; ++v) {
+			const std::string voice = "voice " + std::to_string(v) + ": ";
+			const char* why = gvtm::design_tracks(configs[v], table[v]);
+			if (why[0]) return fail(GVTM_ERR_INVALID_ARGUMENT, voice + why);
+			if (!control_period_matches(plan, table[v])) {
+				return fail(GVTM_ERR_INVALID_ARGUMENT, voice + "control_period_ms of the track configuration and the plan's control rate disagree");
+			}
+		}
+		if (plan->device != GVTM_DEVICE_NONE) {
+			DeviceScope scope(plan->device);
+			hipError_t e = scope.status();
+			if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+			// (the same size every time: the buffer is allocated once, and a call in flight must not see it rewritten)
+			if ((e = upload(plan->d_voice_tracks, table)) != hipSuccess) return fail_hip(e, "upload voice track constants");
+		}
+		plan->voice_tracks = std::move(table);
+		return GVTM_OK;
+	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
+}
+
+} // extern "C"
+
+namespace {
+
+// What the two events-voices entries share up to the tracks launch: the checks in the order the header gives them, then the
+// voice variant of the tracks kernel on the caller's stream.
+int launch_voice_tracks(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets, const int32_t* d_voice_ids, size_t batch,
+		size_t max_frames, float* d_params, int32_t* d_frame_counts, gvtm_drift_state* d_drift, void* hip_stream)
+{
+	if (batch == 0) return GVTM_OK;
+	if (!d_events || !d_event_offsets || !d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events, event_offsets or voice ids");
+	if (!d_params && max_frames > 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
+	// frames leave the kernel as float4 stores
+	if (reinterpret_cast<uintptr_t>(d_params) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params must be 16-byte aligned");
+	if (batch > 0x7fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
+	gvtm::TrackVoicesArgs args{};
+	args.k.control_period = plan->voice_tracks[0].control_period; // (every voice's is the plan's: gvtm_plan_set_voice_tracks)
+	args.events = d_events;
+	args.event_offsets = d_event_offsets;
+	args.batch = batch;
+	args.max_frames = max_frames;
+	args.params = d_params;
+	args.frame_counts = d_frame_counts;
+	args.drift = d_drift;
+	args.voice_k = static_cast<const gvtm::TrackConstants*>(plan->d_voice_tracks.ptr);
+	args.voice_ids = d_voice_ids;
+	args.n_voices = plan->n_voices();
+	const hipError_t e = gvtm::launch_tracks_voices(args, static_cast<hipStream_t>(hip_stream));
+	if (e != hipSuccess) return fail_hip(e, "track generation launch (voices)");
+	return GVTM_OK;
+}
+
+// null plan, no table yet, design-only plan: in this order (a design-only plan still tells whether its table is set)
+int check_voice_tracks_plan(const gvtm_plan* plan, const char* entry)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, std::string(entry) + ": the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	return GVTM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int gvtm_generate_tracks_voices_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets, const int32_t* d_voice_ids,
+		size_t batch, size_t max_frames, float* d_params, int32_t* d_frame_counts, gvtm_drift_state* d_drift, void* hip_stream)
+{
+	const int rc = check_voice_tracks_plan(plan, "gvtm_generate_tracks_voices_device");
+	if (rc != GVTM_OK) return rc;
+	DeviceScope scope(plan->device);
+	const hipError_t e = scope.status();
+	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+	return launch_voice_tracks(plan, d_events, d_event_offsets, d_voice_ids, batch, max_frames, d_params, d_frame_counts, d_drift, hip_stream);
+}
+
+int gvtm_synthesize_events_voices_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets, const int32_t* d_voice_ids,
+		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs,
+		gvtm_drift_state* d_drift, void* hip_stream)
+{
+	int rc = check_voice_tracks_plan(plan, "gvtm_synthesize_events_voices_device");
+	if (rc != GVTM_OK) return rc;
+	if (batch == 0) return GVTM_OK;
+	// (what the synthesis launch would refuse is refused before the tracks kernel advances the drift states)
+	if (!d_audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
+	if ((rc = check_audio_stride(plan, audio_stride, max_frames, true)) != GVTM_OK) return rc;
+	// As gvtm_synthesize_events_device: two launches on the caller's stream with the plan's frame buffer in between; the
+	// frame counts of the tracks kernel (0 for a bad voice id, which the grouping kernel fails on its own) are the
+	// synthesis launch's.
+	DeviceScope scope(plan->device);
+	hipError_t e = scope.status();
+	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+	if ((e = plan->async.params.ensure(sizeof(float) * batch * std::max<size_t>(max_frames, 1) * GVTM_N_PARAM)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
+	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
+	int32_t* const counts = d_frame_counts ? d_frame_counts : static_cast<int32_t*>(plan->async.frames.ptr);
+	rc = launch_voice_tracks(plan, d_events, d_event_offsets, d_voice_ids, batch, max_frames, static_cast<float*>(plan->async.params.ptr), counts, d_drift,
+			hip_stream);
+	if (rc != GVTM_OK) return rc;
+	return launch_synthesis(plan, LaunchRequest{static_cast<const float*>(plan->async.params.ptr), counts, batch, max_frames, d_audio, audio_stride,
+			d_out_counts, d_maxabs, hip_stream, 0, true, d_voice_ids, &plan->async.groups});
 }
 
 } // extern "C"

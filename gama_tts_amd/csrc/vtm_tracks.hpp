@@ -25,4 +25,15 @@ struct TrackArgs {
 
 hipError_t launch_tracks(const TrackArgs& args, hipStream_t stream);
 
+// A batch that mixes voices: utterance b walks its list with voice_k[voice_ids[b]] (mean and initial pitch, intonation
+// flags, drift set-up and filter); k.control_period, one for the launch, is all that is read of k.  An id outside
+// [0, n_voices) yields frame_counts[b] = 0 and leaves the utterance's frames and drift state untouched.
+struct TrackVoicesArgs : TrackArgs {
+	const TrackConstants* voice_k; // [n_voices], device memory
+	const int32_t* voice_ids;      // [batch]
+	int32_t n_voices;
+};
+
+hipError_t launch_tracks_voices(const TrackVoicesArgs& args, hipStream_t stream);
+
 } // namespace gvtm

@@ -34,6 +34,9 @@
  *   gvtm_synthesize_events_device
  *                               EventList::generateOutput (vtm_control_model/EventList.cpp:930-1091) followed by
  *                               Controller::synthesize in one call: event lists in, samples out
+ *   gvtm_plan_set_voice_tracks / gvtm_generate_tracks_voices_device / gvtm_synthesize_events_voices_device
+ *                               the same for a batch that mixes voices: one EventList set-up per voice
+ *                               (vtm_control_model/Controller.cpp:70-81)
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
  *                               (data/voice/english/0_male/vtm.txt resp. 5_male/vtm.txt + variant/{male,female,
@@ -271,7 +274,8 @@ int gvtm_synthesize_batch_host_pcm16(gvtm_plan* plan, const float* params, const
  * and (GVTM_PRECISION_F32) one noise-sample table for all of them.  n_voices == 1 makes exactly the plan gvtm_plan_create
  * makes.  GVTM_DEVICE_NONE works as for gvtm_plan_create.  A plan of two or more voices refuses the single-voice
  * entry points (gvtm_synthesize_batch_*, gvtm_stream_create, gvtm_synthesize_events_device) with
- * GVTM_ERR_INVALID_ARGUMENT; gvtm_plan_info, gvtm_output_count and gvtm_output_capacity describe voice 0.  Its streams
+ * GVTM_ERR_INVALID_ARGUMENT; its event lists go through gvtm_synthesize_events_voices_device, with one track configuration
+ * per voice (gvtm_plan_set_voice_tracks, "Parameter-track generation" below); gvtm_plan_info, gvtm_output_count and gvtm_output_capacity describe voice 0.  Its streams
  * come from gvtm_stream_create_voices ("Streams" below).  Reference model 5 has an entry of its own,
  * gvtm_plan_create_model5_voices. */
 int    gvtm_plan_create_voices(const gvtm_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out);
@@ -301,8 +305,8 @@ size_t gvtm_voices_output_capacity(const gvtm_plan* plan, size_t max_frames);
  * [0, n_voices) fails on its own, as a bad frame count does in the host entries: its out_counts = -1, maxabs = 0, its row
  * is left untouched; the call still succeeds.  Enqueue-only: a small grouping kernel sorts the utterances by voice on the
  * device (stable, each voice padded to whole workgroups), then one synthesis launch runs every voice.  The grouping's
- * scratch is the plan's: calls to this entry and to gvtm_synthesize_events_device on one plan must be ordered on one
- * stream (the host entries and streams have scratch of their own). */
+ * scratch is the plan's: calls to this entry, to gvtm_synthesize_events_device and to gvtm_synthesize_events_voices_device
+ * on one plan must be ordered on one stream (the host entries and streams have scratch of their own). */
 int gvtm_synthesize_voices_device(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts,
 		const int32_t* d_voice_ids, size_t max_frames, size_t batch, float* d_audio, size_t audio_stride,
 		int64_t* d_out_counts, float* d_maxabs, void* hip_stream);
@@ -454,12 +458,57 @@ int gvtm_generate_tracks_device(int device, const gvtm_track_config* config, con
  *                   more is cut there
  *   d_frame_counts  [batch] int32 out: frames each list yields, may be NULL
  *   d_drift         [batch] in/out drift-generator states, or NULL (a fresh generator per utterance)
- * The remaining arguments are gvtm_synthesize_batch_device's.  The frame buffer is the plan's: calls to this entry and to
- * gvtm_synthesize_voices_device on one plan must be ordered on one stream (the host entries and streams have buffers of
- * their own).
+ * The remaining arguments are gvtm_synthesize_batch_device's.  The frame buffer is the plan's: calls to this entry, to
+ * gvtm_synthesize_voices_device and to gvtm_synthesize_events_voices_device on one plan must be ordered on one stream (the
+ * host entries and streams have buffers of their own).
  */
 int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* config, const gvtm_event* d_events,
 		const int64_t* d_event_offsets, size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
+		int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream);
+
+/*
+ * Event lists of a batch that mixes voices.  Track generation depends on the voice: every reference Controller sets its
+ * EventList's mean pitch to pitch_offset + reference_glottal_pitch of its voice variant (Controller.cpp:71; -12 / 0 / 2.5 /
+ * 5 / 7.5 semitones for male / female / large_child / small_child / baby) and carries its own initial pitch, intonation
+ * flags and drift generator set-up (Controller.cpp:70-81).  So a plan of several voices takes one gvtm_track_config per
+ * voice, and the tracks kernel picks utterance b's by d_voice_ids[b].
+ */
+
+/* Per-voice track configurations of a plan: configs[n_configs], n_configs == gvtm_plan_voice_count(plan).  Synchronous:
+ * designs each voice's drift filter and uploads the table into a buffer the plan owns.  Refused with
+ * GVTM_ERR_INVALID_ARGUMENT, the message naming the voice ("voice 3: ..."): a null argument, n_configs different from the
+ * plan's voice count, a configuration gvtm_tracks_frame_count would refuse, a control_period_ms that disagrees with the
+ * plan's control rate.  Works on GVTM_DEVICE_NONE plans (the configurations are checked and kept on the host).  May be
+ * called again; a refused call leaves the previous table in place.  It rewrites the table the queued kernels read: it must
+ * not run while a gvtm_generate_tracks_voices_device / gvtm_synthesize_events_voices_device call on that plan is in flight. */
+int gvtm_plan_set_voice_tracks(gvtm_plan* plan, const gvtm_track_config* configs, size_t n_configs);
+
+/* gvtm_generate_tracks_device for a mix of voices: utterance b is generated under the plan's track configuration of voice
+ * d_voice_ids[b] ([batch] int32, device memory) -- frames, frame counts and drift states bit for bit those of
+ * gvtm_generate_tracks_device with that configuration.  The arguments follow gvtm_generate_tracks_device, with d_voice_ids
+ * after the offsets (NOTE: batch before max_frames here, as in the events entries and unlike gvtm_synthesize_voices_*).
+ * d_params must be 16-byte aligned.  Enqueue-only.  An utterance whose voice id is outside [0, n_voices) fails on its
+ * own: d_frame_counts[b] = 0, its row of d_params and d_drift[b] are left untouched; the call still succeeds.
+ * GVTM_ERR_INVALID_ARGUMENT before gvtm_plan_set_voice_tracks has succeeded on the plan, GVTM_ERR_NO_DEVICE on a design-only
+ * plan; batch == 0 returns GVTM_OK.  Takes a one-voice plan too, and plans of reference model 5 (the frames do not depend
+ * on the vocal-tract model). */
+int gvtm_generate_tracks_voices_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets,
+		const int32_t* d_voice_ids, size_t batch, size_t max_frames, float* d_params, int32_t* d_frame_counts,
+		gvtm_drift_state* d_drift, void* hip_stream);
+
+/* gvtm_synthesize_events_device for a mix of voices: gvtm_generate_tracks_voices_device into the plan's frame buffer, then
+ * gvtm_synthesize_voices_device, both enqueued on hip_stream.  The arguments follow gvtm_synthesize_events_device, with
+ * d_voice_ids after the offsets (NOTE: batch before max_frames, unlike gvtm_synthesize_voices_*) and the track
+ * configurations taken from the plan.  Voice v's utterances come out bit for bit -- samples, counts, peaks, frame counts,
+ * drift states -- as gvtm_synthesize_events_device on a single-voice plan of that voice with that voice's configuration.
+ * audio_stride is checked per voice as in gvtm_synthesize_voices_device.  An utterance whose voice id is outside
+ * [0, n_voices) fails on its own: frame_counts = 0, out_counts = -1, maxabs = 0, its audio row and drift state are left
+ * untouched; the call still succeeds.  Status codes and the one-voice and model-5 plans as for
+ * gvtm_generate_tracks_voices_device.  The frame buffer and the grouping's scratch are the plan's: calls to this entry, to
+ * gvtm_synthesize_events_device and to gvtm_synthesize_voices_device on one plan must be ordered on one stream (the host
+ * entries and streams have buffers of their own and may overlap with it). */
+int gvtm_synthesize_events_voices_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets,
+		const int32_t* d_voice_ids, size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
 		int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream);
 
 /* Same with host buffers (H2D, kernel, D2H, synchronous). */
