@@ -20,6 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 import golden5_voices_cases as cases  # noqa: E402
 import oracle  # noqa: E402
+import voice_files  # noqa: E402
 
 
 def main():
@@ -30,7 +31,7 @@ def main():
     for case in cases.CASES:
         name = case["name"]
         tr = cases.track_for(case, hello)
-        ref, info = oracle.ref_synthesize(tr, "5", case["rate"], cases.CRATE, config=cases.voice_path(case["voice"]))
+        ref, info = oracle.ref_synthesize(tr, "5", case["rate"], cases.CRATE, config=voice_files.voice_path(case["voice"], model5=True))
         manifest[name] = dict(n=int(ref.size), steps=int(info["steps"]), fs=float(info["fs"]),
                               sum=float(ref.astype(np.float64).sum()), maxabs=float(np.abs(ref).max()) if ref.size else 0.0,
                               sha256=hashlib.sha256(ref.tobytes()).hexdigest())

@@ -5,14 +5,11 @@ male), tests/test_oracle5_voices_vs_golden.py and tests/test_gpu_voices5.py.  Ev
 250 Hz control rate and 48 kHz output (one overrun case: 44.1 kHz), one voice file, one track recipe
 (golden_cases.track_for); "full" stores the output, "digest" a strided subset, "tail" that and the last OVERRUN_TAIL samples.
 """
-import os
-
 import golden_cases
 import oracle
+import voice_files
 
-# voice id v of the tests' mixed plans is VOICES[v]
-VOICES = ["male", "female", "large_child", "small_child", "baby"]
-NEW_VOICES = VOICES[1:]
+NEW_VOICES = voice_files.VOICES[1:]
 RATE, CRATE = 48000.0, 250.0
 
 # Internal rate (331.4 + 0.6 * 35) * 30 * 100 / L Hz (VocalTractModel5.h:462-465) and control steps per 250 Hz frame
@@ -28,12 +25,8 @@ OVERRUN_RATE = {"female": 44100.0, "large_child": RATE, "small_child": RATE, "ba
 OVERRUN_TAIL = golden_cases.OVERRUN_TAIL
 
 
-def voice_path(name):
-    return os.path.join(oracle.GOLDEN_DIR, "voice5_%s.txt" % name)
-
-
 def oracle_config(name, rate=RATE):
-    return oracle.config5_from_dict(oracle.read_config_file(voice_path(name)), rate)
+    return oracle.config5_from_dict(oracle.read_config_file(voice_files.voice_path(name, model5=True)), rate)
 
 
 def C(name, voice, track, store="full", rate=RATE):

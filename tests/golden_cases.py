@@ -6,8 +6,13 @@ Each case: name, track recipe, model string for ref_vtm, SectionDelay for our si
 output rate, control rate, config overrides (on top of tests/golden/voice_male.txt),
 and how much of the reference output is stored ("full" or "digest").
 """
+import hashlib
+import json
+import os
+
 import numpy as np
 
+import oracle
 import tracks
 
 
@@ -141,3 +146,22 @@ OVERRUN_CASES = [
     O("ovr_m5_44k_106f", 106, 40, "5", model5=True, store="full"),
     O("ovr_m5_22k_696f", 696, 41, "5", rate=22050.0, model5=True),
 ]
+
+
+def random_golden():
+    """What the reference binary produced for seeded random tracks (tests/golden/make_random_golden.py)."""
+    z = np.load(os.path.join(oracle.GOLDEN_DIR, "random_golden.npz"), allow_pickle=False)
+    data = {k: z[k] for k in z.files}
+    data["manifest"] = json.loads(bytes(data.pop("manifest_json")).decode())
+    return data
+
+
+def check_against_random_golden(out, model, seed):
+    """`out` against the reference's output for (model, seed): same count, bit for bit (digest and strided samples)."""
+    g = random_golden()
+    key = "m%s_s%d" % (model.replace(":", "d"), seed)
+    m = g["manifest"][key]
+    assert out.size == m["n"]
+    assert np.array_equal(out[:: DIGEST_STRIDE], g[key + "__strided"])
+    assert hashlib.sha256(out.tobytes()).hexdigest() == m["sha256"]
+    return m

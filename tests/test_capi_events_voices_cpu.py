@@ -8,33 +8,15 @@ import pytest
 import gama_tts_amd as g
 from gama_tts_amd import capi
 
-import golden5_voices_cases
-from test_capi_voices_cpu import VOICES, configs, voice_path
+from voice_cases import configs, configs5, track_configs
 
 OK, INVALID_ARGUMENT, NO_DEVICE = 0, 1, 2
 REFERENCE_GLOTTAL_PITCH = [-12.0, 0.0, 2.5, 5.0, 7.5]  # of the five variants, in VOICES' order
 
 
-def track_configs(path_of=voice_path, names=VOICES):
-    """A voice's track configuration as Controller.cpp:70-81 sets its EventList up: 0_male/vtm_control_model.txt (control
-    period 4, pitch offset -4, initial pitch -20, drift deviation 4 at 250 Hz with a 4 Hz low-pass, every intonation flag on)
-    and mean pitch = pitch offset + the reference_glottal_pitch of the voice's variant file."""
-    out = []
-    for n in names:
-        c = g.TrackConfig()
-        c.control_period_ms = 4
-        c.macro_intonation = c.micro_intonation = c.intonation_drift = c.smooth_intonation = 1
-        c.initial_pitch = -20.0
-        c.mean_pitch = -4.0 + float(g.read_config_file(path_of(n))["reference_glottal_pitch"])
-        c.drift_deviation, c.drift_sample_rate, c.drift_lowpass_cutoff = 4.0, 250.0, 4.0
-        out.append(c)
-    return out
-
-
 def plans():
     return [g.VoicesPlan(configs(), 250.0, capi.DEVICE_NONE),
-            g.VoicesPlan([g.config5_from_dict(g.read_config_file(golden5_voices_cases.voice_path(n)), 48000.0) for n in VOICES], 250.0,
-                         capi.DEVICE_NONE)]
+            g.VoicesPlan(configs5(48000.0), 250.0, capi.DEVICE_NONE)]
 
 
 @pytest.fixture(params=[0, 1], ids=["models0-4", "model5"])
@@ -63,14 +45,13 @@ def device_entries(plan):
 
 
 def test_mean_pitches_follow_the_variant_files():
-    for path_of in (voice_path, golden5_voices_cases.voice_path):
-        assert [c.mean_pitch for c in track_configs(path_of)] == [-4.0 + p for p in REFERENCE_GLOTTAL_PITCH] == [-16.0, -4.0, -1.5, 1.0, 3.5]
+    for model5 in (False, True):
+        assert [c.mean_pitch for c in track_configs(model5=model5)] == [-4.0 + p for p in REFERENCE_GLOTTAL_PITCH] == [-16.0, -4.0, -1.5, 1.0, 3.5]
 
 
 def test_five_configurations_are_accepted(plan):
-    path_of = golden5_voices_cases.voice_path if plan.info.model5 else voice_path
-    plan.set_voice_tracks(track_configs(path_of))
-    plan.set_voice_tracks(track_configs(path_of))  # and again
+    plan.set_voice_tracks(track_configs(model5=bool(plan.info.model5)))
+    plan.set_voice_tracks(track_configs(model5=bool(plan.info.model5)))  # and again
 
 
 def test_device_entries_want_the_table_first_and_then_a_device(plan):

@@ -10,29 +10,16 @@ import gama_tts_amd as g
 from gama_tts_amd import capi
 import golden5_voices_cases as cases
 import oracle
+from voice_cases import configs5, create
+from voice_files import VOICES, voice_path
 
-VOICES = cases.VOICES
 VARIANT_KEYS = {"vocal_tract_length", "glottal_pulse_tn_min", "glottal_pulse_tn_max", "reference_glottal_pitch", "breathiness",
                 "global_nasal_radius_coef", "global_radius_coef", "min_glottal_loss", "max_glottal_loss",
                 "glottal_lowpass_cutoff", "intonation_factor", "mouth_impedance_radius"}
 
 
-def configs(rate=cases.RATE, names=VOICES):
-    return [g.config5_from_dict(g.read_config_file(cases.voice_path(n)), rate) for n in names]
-
-
-def create(cfgs, n=None, control_rate=250.0):
-    lib = g.load_library()
-    h = ctypes.c_void_p()
-    arr = (capi.Config5 * max(len(cfgs), 1))(*cfgs) if cfgs else None
-    rc = lib.gvtm_plan_create_model5_voices(arr, len(cfgs) if n is None else n, control_rate, capi.DEVICE_NONE, ctypes.byref(h))
-    if rc == 0:
-        lib.gvtm_plan_destroy(h)
-    return rc, h
-
-
 def test_fixtures_differ_exactly_where_the_variants_do():
-    files = {n: g.read_config_file(cases.voice_path(n)) for n in VOICES}
+    files = {n: g.read_config_file(voice_path(n, model5=True)) for n in VOICES}
     male = files["male"]
     assert male == g.read_config_file(oracle.VOICE5_MALE)
     for n in VOICES[1:]:
@@ -45,7 +32,7 @@ def test_fixtures_differ_exactly_where_the_variants_do():
 
 def test_one_voice_plan_is_the_model5_plan():
     for name in ("male", "baby"):
-        cfg = configs(names=[name])
+        cfg = configs5(names=[name])
         vp = g.VoicesPlan(cfg, 250.0, capi.DEVICE_NONE)
         p = g.Plan(cfg[0], 250.0, capi.DEVICE_NONE)
         assert vp.n_voices == 1
@@ -60,7 +47,7 @@ def test_one_voice_plan_is_the_model5_plan():
 
 
 def test_five_voices_info_matches_the_oracle_and_the_issue_table():
-    cfgs = configs()
+    cfgs = configs5()
     vp = g.VoicesPlan(cfgs, 250.0, capi.DEVICE_NONE)
     assert vp.n_voices == 5
     for v, name in enumerate(VOICES):
@@ -79,7 +66,7 @@ def test_five_voices_info_matches_the_oracle_and_the_issue_table():
 
 
 def test_per_voice_counts_and_capacity():
-    cfgs = configs()
+    cfgs = configs5()
     vp = g.VoicesPlan(cfgs, 250.0, capi.DEVICE_NONE)
     singles = [g.Plan(c, 250.0, capi.DEVICE_NONE) for c in cfgs]
     for v, name in enumerate(VOICES):
@@ -97,7 +84,7 @@ def test_per_voice_counts_and_capacity():
     lib = vp._lib
     for name in cases.NEW_VOICES:
         v, f = VOICES.index(name), cases.OVERRUN_FRAMES[name]
-        at = vp if cases.OVERRUN_RATE[name] == cases.RATE else g.VoicesPlan(configs(cases.OVERRUN_RATE[name]), 250.0, capi.DEVICE_NONE)
+        at = vp if cases.OVERRUN_RATE[name] == cases.RATE else g.VoicesPlan(configs5(cases.OVERRUN_RATE[name]), 250.0, capi.DEVICE_NONE)
         info = at.voice_info(v)
         plain = -(-((f * info.control_steps + 2 * info.pad_size) << 16) // info.time_register_increment)
         assert at.voice_output_count(v, f) > plain  # the overrun's extra lap
@@ -107,7 +94,7 @@ def test_per_voice_counts_and_capacity():
 
 
 def test_voices_may_differ_in_every_other_key():
-    cfgs = configs()
+    cfgs = configs5()
     cfgs[1].bypass = 1
     cfgs[2].constant_radius_mouth_impedance = 1
     cfgs[3].waveform = 1
@@ -117,7 +104,7 @@ def test_voices_may_differ_in_every_other_key():
 
 @pytest.mark.parametrize("field,value", [("output_rate", 44100.0), ("precision", capi.PRECISION_F32)])
 def test_refuses_mismatched_model_keys(field, value):
-    cfgs = configs()
+    cfgs = configs5()
     setattr(cfgs[3], field, value)
     rc, h = create(cfgs)
     assert rc == 1 and not h.value
@@ -125,7 +112,7 @@ def test_refuses_mismatched_model_keys(field, value):
 
 
 def test_refuses_a_precision_other_than_f64():
-    cfgs = configs()
+    cfgs = configs5()
     for c in cfgs:
         c.precision = capi.PRECISION_MIXED
     rc, h = create(cfgs)
@@ -137,20 +124,20 @@ def test_refuses_no_voices_and_null_configs():
     lib = g.load_library()
     h = ctypes.c_void_p()
     assert lib.gvtm_plan_create_model5_voices(None, 2, 250.0, capi.DEVICE_NONE, ctypes.byref(h)) == 1
-    arr = (capi.Config5 * 5)(*configs())
+    arr = (capi.Config5 * 5)(*configs5())
     assert lib.gvtm_plan_create_model5_voices(arr, 0, 250.0, capi.DEVICE_NONE, ctypes.byref(h)) == 1
     assert not h.value
     assert lib.gvtm_plan_create_model5_voices(arr, 5, 250.0, capi.DEVICE_NONE, None) == 1
 
 
 def test_refuses_a_bad_voice_and_names_it():
-    cfgs = configs()
+    cfgs = configs5()
     cfgs[2].vocal_tract_length = 25.0  # 352.4 * 30 * 100 / 25 = 42.3 kHz: below the 50 kHz model 5 needs
     rc, h = create(cfgs)
     assert rc == 1 and not h.value
     msg = g.load_library().gvtm_last_error()
     assert msg.startswith(b"voice 2: ") and b"50 kHz" in msg
-    cfgs = configs()
+    cfgs = configs5()
     cfgs[0].vocal_tract_length = 25.0
     assert create(cfgs)[0] == 1 and g.load_library().gvtm_last_error().startswith(b"voice 0: ")
     # a one-voice plan reports as gvtm_plan_create_model5 does
@@ -158,7 +145,7 @@ def test_refuses_a_bad_voice_and_names_it():
 
 
 def test_voice_info_out_of_range():
-    vp = g.VoicesPlan(configs(), 250.0, capi.DEVICE_NONE)
+    vp = g.VoicesPlan(configs5(), 250.0, capi.DEVICE_NONE)
     info = capi.Info()
     assert vp._lib.gvtm_plan_voice_info(vp._h, 5, ctypes.byref(info)) == 1
     assert vp._lib.gvtm_plan_voice_info(vp._h, -1, ctypes.byref(info)) == 1
@@ -166,12 +153,12 @@ def test_voice_info_out_of_range():
 
 def test_mixing_model5_and_other_configs_is_a_type_error():
     with pytest.raises(TypeError):
-        g.VoicesPlan([configs(names=["male"])[0], g.config_from_dict(g.read_config_file(oracle.VOICE_MALE), 48000.0)],
+        g.VoicesPlan([configs5(names=["male"])[0], g.config_from_dict(g.read_config_file(oracle.VOICE_MALE), 48000.0)],
                      250.0, capi.DEVICE_NONE)
 
 
 def test_single_voice_entry_points_refused_on_a_five_voice_plan():
-    vp = g.VoicesPlan(configs(), 250.0, capi.DEVICE_NONE)
+    vp = g.VoicesPlan(configs5(), 250.0, capi.DEVICE_NONE)
     lib = vp._lib
     params = np.zeros((2, 4, 16), dtype=np.float32)
     audio = np.zeros((2, 8192), dtype=np.float32)
@@ -196,7 +183,7 @@ def test_single_voice_entry_points_refused_on_a_five_voice_plan():
 
 def test_one_voice_model5_plan_takes_the_voices_entries_design_only():
     # before plans of several model 5 voices, the voices entries refused model 5 plans (GVTM_ERR_INVALID_ARGUMENT)
-    p = g.Plan(configs(names=["female"])[0], 250.0, capi.DEVICE_NONE)
+    p = g.Plan(configs5(names=["female"])[0], 250.0, capi.DEVICE_NONE)
     lib = p._lib
     params = np.zeros((1, 4, 16), dtype=np.float32)
     audio = np.zeros((1, 8192), dtype=np.float32)

@@ -1,7 +1,6 @@
 """Plans of several voices (gvtm_plan_create_voices) on a design-only plan: creation, refusals, per-voice info and
 output counts against the C oracle's vtmo_derive, and the single-voice entry points refused.  No GPU needed."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -10,25 +9,10 @@ import gama_tts_amd as g
 from gama_tts_amd import capi
 
 import oracle
+from voice_cases import configs, create, oracle_config
+from voice_files import VOICES, voice_path
 
-VOICES = ["male", "female", "large_child", "small_child", "baby"]
 TRACT_CM = [17.5, 15.0, 12.5, 10.0, 7.5]
-
-
-def voice_path(name):
-    return os.path.join(oracle.GOLDEN_DIR, "voice_%s.txt" % name)
-
-
-def configs(rate=44100.0, delay=1, precision=capi.PRECISION_F64, layout=capi.TUBE_10_6, names=VOICES):
-    return [g.config_from_dict(g.read_config_file(voice_path(n)), rate, delay, precision, layout) for n in names]
-
-
-def create(cfgs, n=None, control_rate=250.0):
-    lib = g.load_library()
-    h = ctypes.c_void_p()
-    arr = (capi.Config * max(len(cfgs), 1))(*cfgs) if cfgs else None
-    rc = lib.gvtm_plan_create_voices(arr, len(cfgs) if n is None else n, control_rate, capi.DEVICE_NONE, ctypes.byref(h))
-    return rc, h
 
 
 def test_fixtures_differ_where_the_variants_do():
@@ -60,8 +44,7 @@ def test_five_voices_info_matches_the_oracle(precision, rate, delay, layout):
     for v, name in enumerate(VOICES):
         info = vp.voice_info(v)
         single = g.Plan(cfgs[v], 250.0, capi.DEVICE_NONE)
-        ocfg = oracle.config_from_dict(oracle.read_config_file(voice_path(name)), rate, delay, layout,
-                                       1 if precision == capi.PRECISION_F32 else 0)
+        ocfg = oracle_config(name, rate, delay, layout, precision)
         d = oracle.derive(ocfg)
         assert info.internal_sample_rate == d.sample_rate
         assert info.control_steps == d.control_steps
@@ -93,8 +76,7 @@ def test_per_voice_counts_and_capacity(precision):
     vp = g.VoicesPlan(cfgs, 250.0, capi.DEVICE_NONE)
     singles = [g.Plan(c, 250.0, capi.DEVICE_NONE) for c in cfgs]
     for v, name in enumerate(VOICES):
-        ocfg = oracle.config_from_dict(oracle.read_config_file(voice_path(name)), 44100.0, 1, 0,
-                                       1 if precision == capi.PRECISION_F32 else 0)
+        ocfg = oracle_config(name, 44100.0, 1, 0, precision)
         for f in (0, 1, 2, 3, 25, 250, 501):
             assert vp.voice_output_count(v, f) == singles[v].output_count(f) == oracle.output_count(ocfg, f)
     for f in (0, 1, 7, 250, 500, 2000):

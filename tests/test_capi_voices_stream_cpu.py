@@ -2,29 +2,23 @@
 five 0_male voices (tests/golden/voice_*.txt) and the five 5_male voices (voice5_*.txt): the argument checks and their
 order, the Python binding, and gvtm_stream_create still refused on those plans.  No GPU needed."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
 import gama_tts_amd as g
 from gama_tts_amd import capi
-import golden5_voices_cases as cases5
-import oracle
+from voice_cases import configs, configs5
 
-VOICES = ["male", "female", "large_child", "small_child", "baby"]
 INVALID, NO_DEVICE = 1, 2
 
 
 def plan_v2():
-    cfgs = [g.config_from_dict(g.read_config_file(os.path.join(oracle.GOLDEN_DIR, "voice_%s.txt" % n)), 44100.0, 1)
-            for n in VOICES]
-    return g.VoicesPlan(cfgs, 250.0, capi.DEVICE_NONE)
+    return g.VoicesPlan(configs(), 250.0, capi.DEVICE_NONE)
 
 
 def plan_m5():
-    cfgs = [g.config5_from_dict(g.read_config_file(cases5.voice_path(n)), cases5.RATE) for n in cases5.VOICES]
-    return g.VoicesPlan(cfgs, 250.0, capi.DEVICE_NONE)
+    return g.VoicesPlan(configs5(), 250.0, capi.DEVICE_NONE)
 
 
 PLANS = [plan_v2, plan_m5]
@@ -97,7 +91,7 @@ def test_stream_create_still_refused_on_several_voices(make):
 
 
 def test_one_voice_plans_take_the_voices_entry_design_only():
-    cfg = g.config_from_dict(g.read_config_file(os.path.join(oracle.GOLDEN_DIR, "voice_female.txt")), 44100.0, 1)
+    cfg = configs(names=["female"])[0]
     for plan in (g.Plan(cfg, 250.0, capi.DEVICE_NONE), g.VoicesPlan([cfg], 250.0, capi.DEVICE_NONE)):
         rc, _ = create(plan._lib, plan._h, [0, 0], 2)
         assert rc == NO_DEVICE

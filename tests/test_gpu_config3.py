@@ -8,10 +8,11 @@ ulp of the sample; the float path bit-identical to the float oracle; the mixed p
 import numpy as np
 import pytest
 
-import gama_tts_amd as g
 from gama_tts_amd import capi
 import oracle
 import tracks
+from parity_rules import peak_err, within
+from voice_cases import male_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -30,8 +31,7 @@ def corpus():
 
 
 def _run(precision, params):
-    plan = g.Plan(g.config_from_dict(g.read_config_file(oracle.VOICE_MALE), 44100.0, 1, precision), 250.0, 0)
-    return plan.synthesize_host(params)
+    return male_plan(precision=precision).synthesize_host(params)
 
 
 def test_config3_fp64_all_256_against_the_double_oracle(corpus):
@@ -42,11 +42,8 @@ def test_config3_fp64_all_256_against_the_double_oracle(corpus):
     for b in range(BATCH):
         r = refs64[b]
         assert r.size == 88108
-        d = np.abs(audio[b].astype(np.float64) - r)
-        ulp = np.spacing(np.abs(r)).astype(np.float64)
-        peak = float(np.abs(r).max())
-        assert (d <= np.maximum(ulp, 1e-9 * peak)).all(), (b, float(d.max() / peak))
-        worst = max(worst, float(d.max() / peak))
+        assert within(audio[b], r, 1e-9), (b, peak_err(audio[b], r))
+        worst = max(worst, peak_err(audio[b], r))
         same += int(np.array_equal(audio[b], r))
     assert worst <= 6e-8      # one float32 ulp of a peak sample at most
     assert same >= BATCH * 9 // 10
@@ -64,5 +61,5 @@ def test_config3_mixed_all_256_within_north_star_tolerance(corpus):
     params, refs64, _ = corpus
     audio, counts, _ = _run(capi.PRECISION_MIXED, params)
     assert (counts == 88108).all()
-    worst = max(float(np.abs(audio[b].astype(np.float64) - refs64[b]).max() / np.abs(refs64[b]).max()) for b in range(BATCH))
+    worst = max(peak_err(audio[b], refs64[b]) for b in range(BATCH))
     assert worst <= 1e-5, worst

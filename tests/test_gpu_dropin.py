@@ -10,6 +10,7 @@ import pytest
 
 import gama_tts_amd as g
 import oracle
+from parity_rules import check_model5, peak_err, within
 
 pytestmark = pytest.mark.gpu
 
@@ -42,8 +43,7 @@ def test_plugin_through_reference_loader(name, golden, tmp_path):
     ref = golden[name + "__out"]
     assert out.size == ref.size == int(info["N"])
     assert float(info["fs"]) == 20034.0
-    from test_gpu_parity import _within, _peak_err
-    assert _within(out, ref, 1e-9), _peak_err(out, ref)
+    assert within(out, ref, 1e-9), peak_err(out, ref)
 
 
 def test_plugin_float_model_through_reference_loader(golden, tmp_path):
@@ -77,8 +77,7 @@ def test_plugin_thirty_section_tube_through_reference_loader(golden, tmp_path):
     out, info = _through_loaders(tr, tmp_path, config=cfg)
     ref = golden["rand5_m4__out"]
     assert out.size == ref.size and float(info["fs"]) == 60102.0
-    from test_gpu_parity import _within, _peak_err
-    assert _within(out, ref, 1e-9), _peak_err(out, ref)
+    assert within(out, ref, 1e-9), peak_err(out, ref)
 
 
 @pytest.mark.parametrize("poll", [64, 1024])
@@ -102,8 +101,7 @@ def test_plugin_interactive_protocol_through_reference_loader(precision, name, p
     if precision == "f32":
         assert np.array_equal(out, ref)
     else:
-        from test_gpu_parity import _within, _peak_err
-        assert _within(out, ref, 1e-9), _peak_err(out, ref)
+        assert within(out, ref, 1e-9), peak_err(out, ref)
     # and the same samples as our own batch protocol, bit for bit
     batch, _ = _through_loaders(tr, tmp_path, config=cfg)
     assert np.array_equal(out, batch)
@@ -118,8 +116,7 @@ def test_plugin_consecutive_utterances_through_reference_loader(golden, tmp_path
     out, info = _through_loaders(tr, tmp_path, repeat=3)
     ref = golden["rand5_m0__out"]
     assert out.size == ref.size
-    from test_gpu_parity import _within, _peak_err
-    assert _within(out, ref, 1e-9), _peak_err(out, ref)
+    assert within(out, ref, 1e-9), peak_err(out, ref)
 
 
 def _make_voice_dir(root, model="0", rate=None):
@@ -298,8 +295,7 @@ def test_plugin_model5_through_reference_loader(golden, golden5, tmp_path):
     ref = golden5["rand5_m5__out"]
     assert out.size == ref.size == int(info["N"])
     assert abs(float(info["fs"]) - golden5["manifest"]["rand5_m5"]["fs"]) < 1e-6
-    from test_gpu_model5 import _check
-    _check(out, ref)
+    check_model5(out, ref)
 
 
 @pytest.mark.parametrize("poll", [64, 1024])
@@ -320,8 +316,7 @@ def test_plugin_model5_interactive_protocol_through_reference_loader(poll, golde
     out, info = _through_loaders(tr, tmp_path, output_rate=48000, config=cfg, poll=poll)
     ref = golden5["rand5_m5__out"]
     assert out.size == ref.size == int(info["N"]) and int(info["callbacks"]) >= ref.size // poll
-    from test_gpu_model5 import _check
-    _check(out, ref)
+    check_model5(out, ref)
     batch, _ = _through_loaders(tr, tmp_path, output_rate=48000, config=cfg)
     assert np.array_equal(out, batch)
 

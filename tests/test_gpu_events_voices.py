@@ -14,10 +14,11 @@ from gama_tts_amd import capi
 import event_lists
 import golden5_voices_cases as cases5
 import oracle
-from test_gpu_model5 import _check
-from test_gpu_tracks import _events_on_device, _singable_event_table
-from test_gpu_voices import TOL, VOICES, configs, mixed_batch, oracle_config, within
-from test_tracks_cpu import TEXTS, _product_config
+from device_io import events_on_device, generate_tracks, synthesize_events
+from parity_rules import TOL, check_model5, within
+from track_cases import fresh_drift, product_config, singable_event_table, used_drift
+from voice_cases import configs, configs5, mixed_batch, oracle_config
+from voice_files import VOICES
 
 pytestmark = pytest.mark.gpu
 
@@ -36,83 +37,14 @@ DIVERSE_TRACKS = [np.array([4, 1, 1, 1, 1, -20.0, -16.0, 4.0, 250.0, 4.0]),
 SINGABLE = [(300, 40), (301, 2), (302, 1), (303, 17), (305, 3), (306, 55), (307, 9), (308, 33), (309, 25)]
 
 
-def fresh_drift(batch):
-    return np.tile(np.array(oracle.FRESH_DRIFT, dtype=np.float64), (batch, 1))
-
-
-def used_drift(batch, seed=5):
-    d = fresh_drift(batch)
-    d[:, 0] = 0.1 + 0.8 * np.random.default_rng(seed).random(batch)  # generators that have run before
-    return d
-
-
 def frame_counts_of(cfgvs, tables, ids):
-    return [capi.tracks_frame_count(_product_config(cfgvs[v]), capi.events_from_table(t)) if 0 <= v < len(cfgvs) else 0
+    return [capi.tracks_frame_count(product_config(cfgvs[v]), capi.events_from_table(t)) if 0 <= v < len(cfgvs) else 0
             for t, v in zip(tables, ids)]
-
-
-def generate_voices(plan, tables, ids, max_frames, drift0, fill=7.0):
-    """gvtm_generate_tracks_voices_device -> (frames [B][max_frames][16], counts, drift states after); the frames and the
-    counts start out filled with a pattern."""
-    import torch
-    batch = len(tables)
-    d_events, d_offsets = _events_on_device(tables)
-    dev = d_events.device
-    d_ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev)
-    d_params = torch.full((batch, max_frames, 16), fill, dtype=torch.float32, device=dev)
-    d_counts = torch.full((batch,), 99, dtype=torch.int32, device=dev)
-    d_drift = torch.from_numpy(drift0.copy()).to(dev)
-    plan.generate_tracks_voices_device(d_events, d_offsets, d_ids, batch, max_frames, d_params, d_counts, d_drift,
-                                       torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return d_params.cpu().numpy(), d_counts.cpu().numpy(), d_drift.cpu().numpy()
-
-
-def generate_single(cfgv, tables, max_frames, drift0):
-    """The single-configuration kernel on the whole batch under one configuration."""
-    import torch
-    batch = len(tables)
-    d_events, d_offsets = _events_on_device(tables)
-    dev = d_events.device
-    d_params = torch.zeros((batch, max_frames, 16), dtype=torch.float32, device=dev)
-    d_counts = torch.zeros(batch, dtype=torch.int32, device=dev)
-    d_drift = torch.from_numpy(drift0.copy()).to(dev)
-    capi.generate_tracks_device(_product_config(cfgv), d_events, d_offsets, batch, max_frames, d_params, d_counts, d_drift,
-                                torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return d_params.cpu().numpy(), d_counts.cpu().numpy(), d_drift.cpu().numpy()
-
-
-def synthesize_events(plan, tables, max_frames, stride, drift0, ids=None, track_config=None, fill=0.0, stream=None, wait=True):
-    """gvtm_synthesize_events_voices_device (ids given) or gvtm_synthesize_events_device (track_config given) ->
-    dict of audio [B][stride], frames int32 [B], counts int64 [B], maxabs [B], drift [B][5]; every output starts out
-    filled with a pattern."""
-    import torch
-    batch = len(tables)
-    d_events, d_offsets = _events_on_device(tables)
-    dev = d_events.device
-    out = dict(audio=torch.full((batch, stride), fill, dtype=torch.float32, device=dev),
-               frames=torch.full((batch,), 99, dtype=torch.int32, device=dev),
-               counts=torch.full((batch,), 99, dtype=torch.int64, device=dev),
-               maxabs=torch.full((batch,), 5.0, dtype=torch.float32, device=dev),
-               drift=torch.from_numpy(drift0.copy()).to(dev))
-    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    if ids is not None:
-        d_ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev)
-        plan.synthesize_events_voices_device(d_events, d_offsets, d_ids, batch, max_frames, out["audio"], stride, out["frames"],
-                                             out["counts"], out["maxabs"], out["drift"], s)
-    else:
-        plan.synthesize_events_device(track_config, d_events, d_offsets, batch, max_frames, out["audio"], stride, out["frames"],
-                                      out["counts"], out["maxabs"], out["drift"], s)
-    if not wait:
-        return out
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
 
 
 def voices_plan(cfgs, cfgvs):
     plan = g.VoicesPlan(cfgs, 250.0, 0)
-    plan.set_voice_tracks([_product_config(c) for c in cfgvs])
+    plan.set_voice_tracks([product_config(c) for c in cfgvs])
     return plan
 
 
@@ -137,8 +69,8 @@ def test_frames_counts_and_drift_states_are_those_of_each_voices_configuration()
             for b, (t, v) in enumerate(zip(tables, ids))]
     max_frames = max(w[0].shape[0] for w in want if w)
     plan = voices_plan(configs(precision=capi.PRECISION_F32), DIVERSE_TRACKS)
-    params, counts, drift = generate_voices(plan, tables, ids, max_frames, drift0)
-    singles = [generate_single(c, tables, max_frames, drift0) for c in DIVERSE_TRACKS]
+    params, counts, drift = generate_tracks(tables, max_frames, drift0, plan=plan, ids=ids)
+    singles = [generate_tracks(tables, max_frames, drift0, track_config=product_config(c)) for c in DIVERSE_TRACKS]
     for b, v in enumerate(ids):
         if b == bad:
             assert counts[b] == 0
@@ -159,7 +91,7 @@ def test_frames_counts_and_drift_states_are_those_of_each_voices_configuration()
     # rows shorter than the longest list: cut there, the counts and the drift states still those of the whole lists
     cut = max_frames - 37
     assert sum(1 for w in want if w and w[0].shape[0] > cut) >= 1 and cut > 0
-    params2, counts2, drift2 = generate_voices(plan, tables, ids, cut, drift0)
+    params2, counts2, drift2 = generate_tracks(tables, cut, drift0, plan=plan, ids=ids)
     assert np.array_equal(counts2, counts) and same_bits(drift2, drift)
     for b in range(batch):
         if b == bad:
@@ -180,20 +112,20 @@ def test_captured_reference_calls_next_to_other_voices(golden_tracks):
         c[6] += shift
         cfgvs.append(c)
     plan = voices_plan(configs(precision=capi.PRECISION_F32), cfgvs)
-    captured = [event_lists.load_golden(golden_tracks, name, 0) for name in TEXTS]
+    captured = [event_lists.load_golden(golden_tracks, name, 0) for name in event_lists.CAPTURED]
     tables, ids = [], []
     for q, (_, events, _) in enumerate(captured):  # each text under voice 2 and, next to it, under one of the others
         tables += [events, events]
         ids += [2, [0, 1, 3, 4][q]]
     batch = len(tables)
     max_frames = max(c[2].shape[0] for c in captured) + 3
-    params, counts, drift = generate_voices(plan, tables, ids, max_frames, fresh_drift(batch))
+    params, counts, drift = generate_tracks(tables, max_frames, fresh_drift(batch), plan=plan, ids=ids)
     for q, (cfg, events, frames) in enumerate(captured):
         n = frames.shape[0]
         assert counts[2 * q] == n and counts[2 * q + 1] == n
-        assert np.array_equal(params[2 * q, :n].view(np.uint32), frames.view(np.uint32)), TEXTS[q]
+        assert np.array_equal(params[2 * q, :n].view(np.uint32), frames.view(np.uint32)), event_lists.CAPTURED[q]
         other, state = oracle.tracks_generate(oracle.track_config(cfgvs[ids[2 * q + 1]]), events)
-        assert np.array_equal(params[2 * q + 1, :n].view(np.uint32), other.view(np.uint32)), TEXTS[q]
+        assert np.array_equal(params[2 * q + 1, :n].view(np.uint32), other.view(np.uint32)), event_lists.CAPTURED[q]
         assert tuple(drift[2 * q + 1]) == state
         assert not np.array_equal(params[2 * q + 1, :n, 0], params[2 * q, :n, 0])  # another mean pitch
 
@@ -201,7 +133,7 @@ def test_captured_reference_calls_next_to_other_voices(golden_tracks):
 # ---- 3. audio equals the single-voice events entry
 
 def singable_batch(batch):
-    pool = [_singable_event_table(seed, n) for seed, n in SINGABLE]
+    pool = [singable_event_table(seed, n) for seed, n in SINGABLE]
     tables = [pool[(7 * b) % len(pool)] for b in range(batch)]  # (the first five: 40, 33, 55, 17 and 2 events)
     ids = np.array([b % 5 for b in range(batch)], dtype=np.int32)
     return tables, ids
@@ -219,7 +151,7 @@ def singles_of_events(make_plan, cfgvs, tables, ids, max_frames, drift0):
         idx = np.concatenate([sel, np.zeros(len(ids) - sel.size, dtype=np.intp)])
         plan = make_plan(v)
         r = synthesize_events(plan, [tables[i] for i in idx], max_frames, plan.output_capacity(max_frames), drift0[idx],
-                              track_config=_product_config(cfgvs[v]))
+                              track_config=product_config(cfgvs[v]))
         for j, b in enumerate(sel):
             out[int(b)] = {k: a[j] for k, a in r.items()}
     return out
@@ -268,7 +200,7 @@ def test_events_voices_entry_equals_the_single_voice_events_entry(batch, precisi
 
 
 def test_events_voices_entry_on_a_model5_plan():
-    cfgs = [g.config5_from_dict(g.read_config_file(cases5.voice_path(n)), 48000.0) for n in VOICES]
+    cfgs = configs5(48000.0)
     plan = voices_plan(cfgs, VARIANT_TRACKS)
     batch = 15
     tables, ids = singable_batch(batch)
@@ -284,7 +216,7 @@ def test_events_voices_entry_on_a_model5_plan():
         frames, _ = oracle.tracks_generate(oracle.track_config(VARIANT_TRACKS[v]), tables[b])
         ref, _ = oracle.synthesize5(cases5.oracle_config(name, 48000.0), frames)
         assert got["counts"][b] == ref.size and np.isfinite(ref).all()
-        _check(got["audio"][b, : ref.size], ref)
+        check_model5(got["audio"][b, : ref.size], ref)
 
 
 # ---- 4. a one-voice plan
@@ -300,7 +232,7 @@ def test_one_voice_plan_equals_the_events_entry(precision):
     stride = plan.voices_output_capacity(max_frames)
     drift0 = fresh_drift(batch)
     got = synthesize_events(plan, tables, max_frames, stride, drift0, ids=np.zeros(batch, dtype=np.int32))
-    want = synthesize_events(g.Plan(cfg[0], 250.0, 0), tables, max_frames, stride, drift0, track_config=_product_config(cfgv))
+    want = synthesize_events(g.Plan(cfg[0], 250.0, 0), tables, max_frames, stride, drift0, track_config=product_config(cfgv))
     assert (want["frames"] > 0).sum() >= batch // 2
     for k in want:
         assert same_bits(got[k], want[k]), k
@@ -340,14 +272,14 @@ def test_events_voices_entry_keeps_its_buffers_while_a_host_entry_runs(precision
     alone."""
     import torch
     plan = voices_plan(configs(precision=precision), VARIANT_TRACKS)
-    pool = [_singable_event_table(700 + b, n) for b, n in enumerate([40, 25, 60, 33])]
+    pool = [singable_event_table(700 + b, n) for b, n in enumerate([40, 25, 60, 33])]
     batch = 4096  # some milliseconds of synthesis: the host entry is called long before it is done
     tables = [pool[b % len(pool)] for b in range(batch)]
     ids = np.array([(b // 4 + b) % 5 for b in range(batch)], dtype=np.int32)
-    max_frames = max(capi.tracks_frame_count(_product_config(VARIANT_TRACKS[0]), capi.events_from_table(t)) for t in pool)
+    max_frames = max(capi.tracks_frame_count(product_config(VARIANT_TRACKS[0]), capi.events_from_table(t)) for t in pool)
     stride = plan.voices_output_capacity(max_frames)
     h_params, h_ids, h_frames = mixed_batch(64, 2 * max_frames, 5, seed=92)
-    d_events, d_offsets = _events_on_device(tables)
+    d_events, d_offsets = events_on_device(tables)
     dev = d_events.device
     d_ids = torch.from_numpy(ids).to(dev)
     side = torch.cuda.Stream()  # a non-blocking stream: nothing orders it against the host entry's own streams

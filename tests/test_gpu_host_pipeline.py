@@ -10,12 +10,10 @@ import gama_tts_amd as g
 from gama_tts_amd import capi
 import oracle
 import tracks
+from device_io import run_batch_device
+from voice_cases import male_plan
 
 pytestmark = pytest.mark.gpu
-
-
-def _plan(precision, delay=1, rate=44100.0, layout=0):
-    return g.Plan(g.config_from_dict(g.read_config_file(oracle.VOICE_MALE), rate, delay, precision, layout), 250.0, 0)
 
 
 def _pcm_rule(x, scale):
@@ -39,7 +37,7 @@ def _ragged(batch, max_frames, seed):
 def test_pcm16_entry_is_the_float_entry_scaled_and_rounded(batch, precision):
     """2100 utterances = four per workgroup x 256 compute units twice over: three slices through the pipeline."""
     params, frames = _ragged(batch, 14, 99 + batch)
-    plan = _plan(precision)
+    plan = male_plan(precision=precision)
     audio, counts, maxabs = plan.synthesize_host(params, frames)
     pcm, counts16, maxabs16, scales = plan.synthesize_host_pcm16(params, frames)
     assert np.array_equal(counts, counts16) and np.array_equal(maxabs, maxabs16)
@@ -51,16 +49,8 @@ def test_pcm16_entry_is_the_float_entry_scaled_and_rounded(batch, precision):
         assert np.array_equal(pcm[b, :n], _pcm_rule(audio[b, :n], scales[b])), b
         assert not pcm[b, n:].any() and not audio[b, n:].any()
     # the device entry in ONE launch gives the pipeline's samples bit for bit
-    import torch
-    dp = torch.from_numpy(params).cuda()
-    df = torch.from_numpy(frames).cuda()
-    stride = audio.shape[1]
-    da = torch.zeros((batch, stride), dtype=torch.float32, device="cuda")
-    dc = torch.zeros(batch, dtype=torch.int64, device="cuda")
-    plan.synthesize_device(dp, batch, params.shape[1], da, stride, df, dc, None, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert np.array_equal(dc.cpu().numpy(), counts)
-    got = da.cpu().numpy()
+    got, got_counts = run_batch_device(plan, params, frames, audio.shape[1])
+    assert np.array_equal(got_counts, counts)
     for b in range(batch):
         assert np.array_equal(got[b, : counts[b]], audio[b, : counts[b]]), b
 
@@ -70,7 +60,7 @@ def test_page_locked_buffers_and_bad_frame_counts():
     count outside [0, max_frames]: that utterance fails alone (count -1, zero row), the others are untouched."""
     batch, max_frames = 2060, 10
     params, frames = _ragged(batch, max_frames, 4242)
-    plan = _plan(capi.PRECISION_F32)
+    plan = male_plan(precision=capi.PRECISION_F32)
     pcm_ref, counts_ref, _, scales_ref = plan.synthesize_host_pcm16(params, frames)
     stride = pcm_ref.shape[1]
     p_in = g.PinnedArray(params.shape, np.float32)
@@ -102,7 +92,7 @@ def test_pcm16_against_the_float_oracle_end_to_end():
     samples are bit-identical to VocalTractModel0<float>'s; the scaling rule is pinned to reference-written WAV files in
     tests/test_oracle_vs_golden.py)."""
     params = tracks.random_tracks(6, 30, seed0=31, consonant_heavy=True)
-    plan = _plan(capi.PRECISION_F32)
+    plan = male_plan(precision=capi.PRECISION_F32)
     pcm, counts, _, _ = plan.synthesize_host_pcm16(params)
     cfg = oracle.male_config(44100.0, 1, float_model=1)
     for b in range(6):

@@ -4,8 +4,8 @@
 Tolerance.  Both sides compute in fp64 and differ at the 1e-13 level (device libm, fused multiply-adds); the
 resampler's output is rounded to float32 and THEN differenced and multiplied by the output rate
 (VocalTractModel5.h:507-513), so a float32 sample whose rounding flips (one ulp, 6e-8 of the sample) turns into
-an output error of ulp * output_rate, a few 1e-7 of the output's peak.  The bar: every sample within
-TOL = 2e-6 of the utterance's peak, at least 90 % of the samples bit-identical, sample counts exact.  In bypass
+an output error of ulp * output_rate, a few 1e-7 of the output's peak.  The bar (parity_rules.check_model5): every sample within
+TOL5 = 2e-6 of the utterance's peak, at least 90 % of the samples bit-identical, sample counts exact.  In bypass
 mode (no difference filter) the bar is the fp64 path's of the other models: 1e-9 of peak or one float32 ulp.
 """
 import numpy as np
@@ -16,32 +16,10 @@ from gama_tts_amd import capi
 import golden5_cases
 import oracle
 import tracks
+from parity_rules import TOL5, check_model5
+from voice_cases import male5_plan
 
 pytestmark = pytest.mark.gpu
-
-TOL = 2e-6
-MIN_EXACT = 0.90
-
-
-def _plan(overrides=None, rate=48000.0, crate=250.0):
-    d = g.read_config_file(oracle.VOICE5_MALE)
-    d.update({k: str(v) for k, v in (overrides or {}).items()})
-    return g.Plan(g.config5_from_dict(d, rate), crate, 0)
-
-
-def _check(got, ref, bypass=False, peak=None):
-    assert got.shape == ref.shape
-    ref64 = ref.astype(np.float64)
-    peak = float(np.abs(ref64).max()) if peak is None else float(peak)
-    d = np.abs(got.astype(np.float64) - ref64)
-    if bypass:
-        ulp = np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
-        assert (d <= np.maximum(ulp, 1e-9 * peak)).all(), float(d.max() / max(peak, 1e-300))
-    else:
-        assert float(d.max()) <= TOL * max(peak, 1e-300), float(d.max() / max(peak, 1e-300))
-        if got.size >= 200:
-            assert float((got == ref).mean()) >= MIN_EXACT, float((got == ref).mean())
-
 
 DOUBLE_CASES = [c for c in golden5_cases.CASES if not c["float_model"]]
 
@@ -50,7 +28,7 @@ DOUBLE_CASES = [c for c in golden5_cases.CASES if not c["float_model"]]
 def test_reference_vectors(case, golden, golden5):
     m = golden5["manifest"][case["name"]]
     tr = golden5_cases.track_for(case, golden)
-    plan = _plan(case["overrides"], case["rate"], case["crate"])
+    plan = male5_plan(case["overrides"], case["rate"], case["crate"])
     assert plan.info.model5 == 1
     assert abs(plan.info.internal_rate_hz - m["fs"]) < 1e-6
     assert plan.info.control_steps * tr.shape[0] == m["steps"]
@@ -60,10 +38,10 @@ def test_reference_vectors(case, golden, golden5):
     out = audio[0]
     bypass = int(case["overrides"].get("bypass", 0)) == 1
     if case["store"] == "full":
-        _check(out, golden5[case["name"] + "__out"], bypass, m["maxabs"])
+        check_model5(out, golden5[case["name"] + "__out"], bypass, m["maxabs"])
     else:
-        _check(out[:: golden5_cases.DIGEST_STRIDE], golden5[case["name"] + "__strided"], bypass, m["maxabs"])
-    assert maxabs[0] == pytest.approx(m["maxabs"], rel=10 * TOL, abs=1e-12)
+        check_model5(out[:: golden5_cases.DIGEST_STRIDE], golden5[case["name"] + "__strided"], bypass, m["maxabs"])
+    assert maxabs[0] == pytest.approx(m["maxabs"], rel=10 * TOL5, abs=1e-12)
     assert maxabs[0] == np.abs(out).max()
 
 
@@ -71,20 +49,20 @@ def test_ragged_batch_against_oracle():
     # utterances of different lengths in one launch (0, 1, 2, ... frames), consonant-heavy tracks
     frames = [0, 1, 2, 3, 7, 25, 40, 40, 13, 31]
     params = tracks.random_tracks(len(frames), 40, seed0=900, consonant_heavy=True)
-    plan = _plan()
+    plan = male5_plan()
     audio, counts, maxabs = plan.synthesize_host(params, frame_counts=frames)
     cfg = oracle.male5_config(48000.0)
     for b, f in enumerate(frames):
         ref, _ = oracle.synthesize5(cfg, params[b, :f])
         assert counts[b] == ref.size
-        _check(audio[b, : ref.size], ref)
+        check_model5(audio[b, : ref.size], ref)
         assert maxabs[b] == np.abs(audio[b, : ref.size]).max()
 
 
 def test_batch_of_identical_tracks_is_identical():
     one = tracks.random_track(30, 77, True)
     params = np.repeat(one[None], 70, axis=0)
-    audio, _, _ = _plan().synthesize_host(params)
+    audio, _, _ = male5_plan().synthesize_host(params)
     assert (audio == audio[0]).all()
 
 
@@ -93,14 +71,14 @@ def test_upsampling_branch(rate):
     # an output rate above the 60.4 kHz internal rate: the resampler's other branch (SampleRateConverter.h:320-360);
     # 176.4 kHz is close to the largest ratio the sink's ring takes (3x, refused above)
     tr = tracks.random_track(30, 5, True)
-    plan = _plan(rate=rate)
+    plan = male5_plan(rate=rate)
     assert plan.info.upsampling == 1
     audio, counts, _ = plan.synthesize_host(tr[None])
     ref, _ = oracle.synthesize5(oracle.male5_config(rate), tr)
     assert counts[0] == ref.size
-    _check(audio[0, : ref.size], ref)
+    check_model5(audio[0, : ref.size], ref)
     with pytest.raises(g.GvtmError):
-        _plan(rate=192000.0)
+        male5_plan(rate=192000.0)
 
 
 def test_rejects_what_the_reference_rejects():
@@ -120,13 +98,13 @@ def test_long_utterance_next_to_short_ones():
     params = np.zeros((3, 7500, 16), np.float32)
     params[0] = long_tr
     params[1, :1] = long_tr[:1]
-    plan = _plan()
+    plan = male5_plan()
     audio, counts, maxabs = plan.synthesize_host(params, frame_counts=[7500, 1, 0])
     cfg = oracle.male5_config(48000.0)
     for b, f in enumerate((7500, 1, 0)):
         ref, _ = oracle.synthesize5(cfg, params[b, :f])
         assert counts[b] == ref.size
-        _check(audio[b, : ref.size], ref)
+        check_model5(audio[b, : ref.size], ref)
         assert maxabs[b] == np.abs(audio[b, : ref.size]).max()
 
 
@@ -137,7 +115,7 @@ def test_full_batch_on_the_device_by_tiling():
     dev = torch.device("cuda:0")
     batch, frames, pool_n = 4096, 500, 64
     pool = tracks.random_tracks(pool_n, frames, seed0=515100, consonant_heavy=True)
-    plan = _plan()
+    plan = male5_plan()
     n = plan.output_count(frames)
     d_params = torch.from_numpy(pool).to(dev).repeat((batch // pool_n, 1, 1)).contiguous()
     d_audio = torch.empty((batch, n), dtype=torch.float32, device=dev)
@@ -153,7 +131,7 @@ def test_full_batch_on_the_device_by_tiling():
     cfg = oracle.male5_config(48000.0)
     for b in (5, 60):
         ref, _ = oracle.synthesize5(cfg, pool[b])
-        _check(tiles[33, b].cpu().numpy(), ref)
+        check_model5(tiles[33, b].cpu().numpy(), ref)
 
 
 def test_special_case_frames():
@@ -161,12 +139,12 @@ def test_special_case_frames():
     at the floor, velum 0, pitch and band-pass extremes), alone and inside a batch."""
     tr = tracks.edge_track(48)
     ref, _ = oracle.synthesize5(oracle.male5_config(48000.0), tr)
-    plan = _plan()
+    plan = male5_plan()
     batch = np.stack([tr, tracks.random_track(48, 3, True), tr])
     for params in (tr[None], batch):
         audio, counts, _ = plan.synthesize_host(params)
         assert counts[0] == ref.size and np.isfinite(audio).all()
-        _check(audio[0, : ref.size], ref)
+        check_model5(audio[0, : ref.size], ref)
     assert np.array_equal(audio[2], audio[0])
 
 
@@ -175,23 +153,16 @@ def test_host_entry_slices_large_batches():
     pool = tracks.random_tracks(50, frames, seed0=717000, consonant_heavy=True)
     params = np.ascontiguousarray(np.tile(pool, (batch // 50, 1, 1)))
     fc = (np.arange(batch) % (frames + 1)).astype(np.int32)
-    plan = _plan()
+    plan = male5_plan()
     audio, counts, _ = plan.synthesize_host(params, fc)
     cfg = oracle.male5_config(48000.0)
     for b in (0, 1023, 1024, 2047, 2048, batch - 1):
         ref, _ = oracle.synthesize5(cfg, params[b, : fc[b]])
         assert counts[b] == ref.size
-        _check(audio[b, : ref.size], ref)
+        check_model5(audio[b, : ref.size], ref)
     # the pool repeats every 50 utterances, the frame counts every 7: 350 apart the utterances are the same
     valid = np.arange(audio.shape[1])[None, :] < counts[:350, None]
     assert np.array_equal(audio[:350][valid], audio[1050:1400][valid]) and np.array_equal(audio[:350][valid], audio[1750:2100][valid])
-
-
-def _plan_rows(rows, overrides=None, rate=48000.0, crate=250.0):
-    """A diagnostics plan with the utterances per workgroup forced (1: one tube wavefront, chunk 60; 2: two, chunk 24)."""
-    d = g.read_config_file(oracle.VOICE5_MALE)
-    d.update({k: str(v) for k, v in (overrides or {}).items()})
-    return g.Plan(g.config5_from_dict(d, rate), crate, 0, diagnostics=True, rows=rows)
 
 
 @pytest.mark.parametrize("case", DOUBLE_CASES, ids=lambda c: c["name"])
@@ -200,7 +171,7 @@ def test_reference_vectors_two_utterances_per_workgroup(case, golden, golden5):
     beyond one workgroup per compute unit get), the vector in BOTH slots of a workgroup and beside a different neighbour."""
     tr = golden5_cases.track_for(case, golden)
     other = tracks.random_track(tr.shape[0], 77, True)
-    plan = _plan_rows(2, case["overrides"], case["rate"], case["crate"])
+    plan = male5_plan(case["overrides"], case["rate"], case["crate"], rows=2)
     audio, counts, _ = plan.synthesize_host(np.stack([tr, other, other, tr, tr]))
     m = golden5["manifest"][case["name"]]
     bypass = int(case["overrides"].get("bypass", 0)) == 1
@@ -208,9 +179,9 @@ def test_reference_vectors_two_utterances_per_workgroup(case, golden, golden5):
         assert counts[b] == m["n"]
         out = audio[b, : m["n"]]
         if case["store"] == "full":
-            _check(out, golden5[case["name"] + "__out"], bypass, m["maxabs"])
+            check_model5(out, golden5[case["name"] + "__out"], bypass, m["maxabs"])
         else:
-            _check(out[:: golden5_cases.DIGEST_STRIDE], golden5[case["name"] + "__strided"], bypass, m["maxabs"])
+            check_model5(out[:: golden5_cases.DIGEST_STRIDE], golden5[case["name"] + "__strided"], bypass, m["maxabs"])
     assert np.array_equal(audio[0], audio[3]) and np.array_equal(audio[0], audio[4])
 
 
@@ -219,15 +190,15 @@ def test_two_utterances_per_workgroup_ragged_against_the_one_utterance_shape_and
     one-utterance shape's samples bit for bit, and both the oracle's."""
     frames = np.array([40, 0, 1, 106, 2, 40, 17, 106, 33, 5, 40], dtype=np.int32)
     params = tracks.random_tracks(len(frames), 106, seed0=5150, consonant_heavy=True)
-    a1, c1, m1 = _plan_rows(1).synthesize_host(params, frames)
-    a2, c2, m2 = _plan_rows(2).synthesize_host(params, frames)
+    a1, c1, m1 = male5_plan(rows=1).synthesize_host(params, frames)
+    a2, c2, m2 = male5_plan(rows=2).synthesize_host(params, frames)
     assert np.array_equal(c1, c2) and np.array_equal(m1, m2)
     assert np.array_equal(a1, a2)
     cfg = oracle.male5_config(48000.0)
     for b in (0, 2, 3, 6, 10):
         ref, _ = oracle.synthesize5(cfg, params[b, : frames[b]])
         assert c2[b] == ref.size
-        _check(a2[b, : ref.size], ref)
+        check_model5(a2[b, : ref.size], ref)
 
 
 def test_product_library_on_a_batch_beyond_one_workgroup_per_compute_unit():
@@ -237,13 +208,13 @@ def test_product_library_on_a_batch_beyond_one_workgroup_per_compute_unit():
     pool = tracks.random_tracks(len(pool_f), 30, seed0=6000, consonant_heavy=True)
     batch = 601
     idx = np.arange(batch) % len(pool_f)
-    plan = _plan()
+    plan = male5_plan()
     audio, counts, maxabs = plan.synthesize_host(pool[idx], pool_f[idx])
     cfg = oracle.male5_config(48000.0)
     for t in range(len(pool_f)):
         ref, _ = oracle.synthesize5(cfg, pool[t, : pool_f[t]])
         assert counts[t] == ref.size
-        _check(audio[t, : ref.size], ref)
+        check_model5(audio[t, : ref.size], ref)
         assert maxabs[t] == (np.abs(audio[t, : ref.size]).max() if ref.size else 0.0)
     for b in range(len(pool_f), batch):
         assert counts[b] == counts[b % len(pool_f)] and np.array_equal(audio[b], audio[b % len(pool_f)]), b

@@ -8,21 +8,21 @@ import hashlib
 import numpy as np
 import pytest
 
-import gama_tts_amd as g
 from gama_tts_amd import capi
 import golden_cases
 import oracle
 import tracks
+from device_io import run_batch_device
+from parity_rules import within
+from voice_cases import male5_plan, male_plan
 
 pytestmark = pytest.mark.gpu
 
 
-def _plan(case, precision, rows=0):
+def _plan(case, precision):
     if case["model5"]:
-        return g.Plan(g.config5_from_dict(g.read_config_file(oracle.VOICE5_MALE), case["rate"]), case["crate"], 0)
-    d = g.read_config_file(oracle.VOICE_MALE)
-    return g.Plan(g.config_from_dict(d, case["rate"], case["delay"], precision, case.get("layout", 0)), case["crate"], 0,
-                  diagnostics=bool(rows), rows=rows)
+        return male5_plan(rate=case["rate"], crate=case["crate"])
+    return male_plan(rate=case["rate"], delay=case["delay"], crate=case["crate"], precision=precision, layout=case.get("layout", 0))
 
 
 def _check(case, out, m, z, tol):
@@ -32,12 +32,7 @@ def _check(case, out, m, z, tol):
         pieces = [(out[:: golden_cases.DIGEST_STRIDE], z[case["name"] + "__strided"]),
                   (out[-golden_cases.OVERRUN_TAIL:], z[case["name"] + "__tail"])]
     for got, ref in pieces:
-        if tol == 0.0:
-            assert np.array_equal(got, ref)
-        else:
-            d = np.abs(got.astype(np.float64) - ref.astype(np.float64))
-            ulp = np.spacing(np.abs(ref)).astype(np.float64)
-            assert (d <= np.maximum(ulp, tol * m["maxabs"])).all(), float(d.max() / m["maxabs"])
+        assert within(got, ref, tol, m["maxabs"]), float(np.abs(got.astype(np.float64) - ref).max() / m["maxabs"])
 
 
 @pytest.mark.parametrize("case", golden_cases.OVERRUN_CASES, ids=lambda c: c["name"])
@@ -71,8 +66,7 @@ def test_one_overrun_utterance_in_a_ragged_batch(rows):
     frames = np.array([79, 40, 18, 80, 17, 79, 0, 19, 78], dtype=np.int32)
     params = tracks.random_tracks(len(frames), 80, seed0=4400, consonant_heavy=True)
     cfg = oracle.male_config(rate, delay, float_model=1)
-    d = g.read_config_file(oracle.VOICE_MALE)
-    plan = g.Plan(g.config_from_dict(d, rate, delay, capi.PRECISION_F32), 250.0, 0, diagnostics=True, rows=rows)
+    plan = male_plan(rate=rate, delay=delay, precision=capi.PRECISION_F32, rows=rows)
     longest = max(plan.output_count(int(f)) for f in frames)
     assert plan.output_count(79) > plan.output_count(80)      # the overrun makes the shorter utterance longer
     assert plan.output_capacity(80) >= longest
@@ -89,21 +83,13 @@ def test_one_overrun_utterance_in_a_ragged_batch(rows):
 def test_device_resident_frame_counts_with_overrun():
     """gvtm_synthesize_batch_device with d_frame_counts: nothing can be validated on the host, the kernel decides per
     utterance; a stride of gvtm_output_count(max_frames) drops what does not fit and still reports the full count."""
-    import torch
     delay, rate = 2, 22050.0
     frames = np.array([79, 80, 18, 60], dtype=np.int32)
     params = tracks.random_tracks(4, 80, seed0=4500, consonant_heavy=True)
-    d = g.read_config_file(oracle.VOICE_MALE)
-    plan = g.Plan(g.config_from_dict(d, rate, delay, capi.PRECISION_F64), 250.0, 0)
+    plan = male_plan(rate=rate, delay=delay)
     cfg = oracle.male_config(rate, delay)
-    dev = torch.device("cuda:0")
-    dp, dfc = torch.from_numpy(params).to(dev), torch.from_numpy(frames).to(dev)
     for stride in (plan.output_capacity(80), plan.output_count(80)):
-        da = torch.zeros((4, stride), dtype=torch.float32, device=dev)
-        dc = torch.zeros(4, dtype=torch.int64, device=dev)
-        plan.synthesize_device(dp, 4, 80, da, stride, dfc, dc, None)
-        torch.cuda.synchronize()
-        a, c = da.cpu().numpy(), dc.cpu().numpy()
+        a, c = run_batch_device(plan, params, frames, stride)
         for b, f in enumerate(frames):
             ref = oracle.synthesize(cfg, params[b, :f])
             assert c[b] == ref.size

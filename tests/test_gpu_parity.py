@@ -8,45 +8,21 @@ a per-sample relative error is meaningless at zero crossings).
     configs[2], 251 utterances are bit-identical and the rest carry a handful of such flips,
     profiles/r01d_config3_parity.json).
   * mixed path: 1e-5 (BASELINE.json north_star)
-Sample counts are exact in both.
+Sample counts are exact in both.  The rule itself is parity_rules.within, the tolerances parity_rules.TOL.
 """
 import numpy as np
 import pytest
 
-import gama_tts_amd as g
 from gama_tts_amd import capi
 import golden_cases
 import oracle
 import tracks
+from parity_rules import TOL, peak_err, within
+from voice_cases import male_plan
 
 pytestmark = pytest.mark.gpu
 
-TOL_F64 = 1e-9
-TOL_MIXED = 1e-5
-
-
-def _plan(case_overrides=None, rate=44100.0, delay=1, crate=250.0, precision=capi.PRECISION_F64, layout=0, rows=0):
-    """rows != 0: a plan of the diagnostics library (same kernels) with that many utterances per workgroup forced."""
-    d = g.read_config_file(oracle.VOICE_MALE)
-    d.update({k: str(v) for k, v in (case_overrides or {}).items()})
-    return g.Plan(g.config_from_dict(d, rate, delay, precision, layout), crate, 0, diagnostics=bool(rows), rows=rows)
-
-
-def _within(got, ref, tol, peak=None):
-    """Every sample within max(tol * peak, one float32 ulp of the reference sample)."""
-    ref64 = ref.astype(np.float64)
-    peak = float(np.abs(ref64).max()) if peak is None else float(peak)
-    d = np.abs(got.astype(np.float64) - ref64)
-    ulp = np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
-    return bool((d <= np.maximum(ulp, tol * max(peak, 1e-300))).all())
-
-
-def _peak_err(got, ref):
-    ref = ref.astype(np.float64)
-    peak = np.abs(ref).max()
-    if peak == 0:
-        return float(np.abs(got).max())
-    return float(np.abs(got.astype(np.float64) - ref).max() / peak)
+TOL_F64, TOL_MIXED = TOL[capi.PRECISION_F64], TOL[capi.PRECISION_MIXED]
 
 
 @pytest.mark.parametrize("precision,tol", [(capi.PRECISION_F64, TOL_F64), (capi.PRECISION_MIXED, TOL_MIXED)],
@@ -55,7 +31,7 @@ def _peak_err(got, ref):
 def test_reference_vectors(case, precision, tol, golden):
     m = golden["manifest"][case["name"]]
     tr = golden_cases.track_for(case, golden)
-    plan = _plan(case["overrides"], case["rate"], case["delay"], case["crate"], precision, case.get("layout", 0))
+    plan = male_plan(case["overrides"], case["rate"], case["delay"], case["crate"], precision, case.get("layout", 0))
     assert plan.info.internal_sample_rate == int(m["fs"])
     assert plan.output_count(tr.shape[0]) == m["n"]
     audio, counts, maxabs = plan.synthesize_host(tr[None])
@@ -64,10 +40,10 @@ def test_reference_vectors(case, precision, tol, golden):
     scale = m["maxabs"] if m["maxabs"] > 0 else 1.0
     if case["store"] == "full":
         ref = golden[case["name"] + "__out"]
-        assert _within(out, ref, tol, scale), _peak_err(out, ref)
+        assert within(out, ref, tol, scale), peak_err(out, ref)
     else:
         ref = golden[case["name"] + "__strided"]
-        assert _within(out[:: golden_cases.DIGEST_STRIDE], ref, tol, scale)
+        assert within(out[:: golden_cases.DIGEST_STRIDE], ref, tol, scale)
         assert abs(float(out.astype(np.float64).sum()) - m["sum"]) <= 50 * max(tol, 1e-8) * scale * m["n"] ** 0.5 + 1e-12
     assert maxabs[0] == pytest.approx(m["maxabs"], rel=max(10 * tol, 2e-7), abs=1e-12)
 
@@ -75,31 +51,31 @@ def test_reference_vectors(case, precision, tol, golden):
 @pytest.mark.parametrize("delay", [1, 2, 3])
 def test_random_batch_against_oracle(delay):
     params = tracks.random_tracks(12, 40, seed0=300 + delay, consonant_heavy=True)
-    plan = _plan(delay=delay)
+    plan = male_plan(delay=delay)
     audio, counts, _ = plan.synthesize_host(params)
     ref = oracle.synthesize_batch(oracle.male_config(44100.0, delay), params)
     assert audio.shape == ref.shape and (counts == ref.shape[1]).all()
     for b in range(params.shape[0]):
-        assert _within(audio[b], ref[b], TOL_F64), _peak_err(audio[b], ref[b])
+        assert within(audio[b], ref[b], TOL_F64), peak_err(audio[b], ref[b])
 
 
 def test_ragged_and_empty_utterances():
     frames = np.array([0, 1, 7, 40, 33, 40, 2, 19], dtype=np.int32)
     params = tracks.random_tracks(len(frames), 40, seed0=77)
-    plan = _plan()
+    plan = male_plan()
     audio, counts, maxabs = plan.synthesize_host(params, frames)
     cfg = oracle.male_config()
     for b, f in enumerate(frames):
         ref = oracle.synthesize(cfg, params[b, :f]) if f else np.zeros(oracle.output_count(cfg, 0), np.float32)
         assert counts[b] == ref.size == plan.output_count(int(f))
-        assert _within(audio[b, : ref.size], ref, TOL_F64), _peak_err(audio[b, : ref.size], ref)
+        assert within(audio[b, : ref.size], ref, TOL_F64), peak_err(audio[b, : ref.size], ref)
     assert maxabs[0] == 0.0
 
 
 def test_normalize_matches_reference_scaling():
     import torch
     params = tracks.random_tracks(3, 30, seed0=5)
-    plan = _plan()
+    plan = male_plan()
     n = plan.output_count(30)
     dev = torch.device("cuda:0")
     d_params = torch.from_numpy(params).to(dev)
@@ -133,7 +109,7 @@ def test_full_size_properties_config2():
     causality (a prefix track reproduces the head of the long one), peak bookkeeping,
     plus a spot check of a few utterances against the oracle."""
     params = tracks.random_tracks(256, 500, seed0=1000)
-    plan = _plan()
+    plan = male_plan()
     audio, counts, maxabs = plan.synthesize_host(params)
     assert audio.shape == (256, 88108) and (counts == 88108).all()
     audio2, _, _ = plan.synthesize_host(params)
@@ -149,7 +125,7 @@ def test_full_size_properties_config2():
     assert np.array_equal(head[:, :safe], audio[:8, :safe])
     cfg = oracle.male_config()
     for b in (0, 101, 255):
-        assert _within(audio[b], oracle.synthesize(cfg, params[b]), TOL_F64), _peak_err(audio[b], oracle.synthesize(cfg, params[b]))
+        assert within(audio[b], oracle.synthesize(cfg, params[b]), TOL_F64), peak_err(audio[b], oracle.synthesize(cfg, params[b]))
 
 
 @pytest.mark.parametrize("rows,precision,tol", [(2, capi.PRECISION_F64, TOL_F64), (4, capi.PRECISION_F64, TOL_F64),
@@ -160,13 +136,13 @@ def test_multi_row_workgroups(rows, precision, tol, delay):
     lengths, a batch that does not fill the last workgroup."""
     frames = np.array([40, 0, 17, 33, 40, 1, 25, 40, 8, 39, 40], dtype=np.int32)
     params = tracks.random_tracks(len(frames), 40, seed0=900 + rows, consonant_heavy=True)
-    plan = _plan(delay=delay, precision=precision, rows=rows)
+    plan = male_plan(delay=delay, precision=precision, rows=rows)
     audio, counts, maxabs = plan.synthesize_host(params, frames)
     cfg = oracle.male_config(44100.0, delay)
     for b, f in enumerate(frames):
         ref = oracle.synthesize(cfg, params[b, :f]) if f else np.zeros(oracle.output_count(cfg, 0), np.float32)
         assert counts[b] == ref.size
-        assert _within(audio[b, : ref.size], ref, tol), _peak_err(audio[b, : ref.size], ref)
+        assert within(audio[b, : ref.size], ref, tol), peak_err(audio[b, : ref.size], ref)
         assert maxabs[b] == np.abs(audio[b, : ref.size]).max()
 
 
@@ -174,8 +150,7 @@ def test_multi_row_workgroups(rows, precision, tol, delay):
 def test_one_step_per_frame_and_chunk_aligned_lengths(frames):
     """The plugin's mode of operation (control rate == internal rate, one frame per step) with
     lengths that are exact multiples of the kernel's chunk: the flush tail must be complete."""
-    d = g.read_config_file(oracle.VOICE_MALE)
-    plan = g.Plan(g.config_from_dict(d, 44100.0, 1), 20034.0, 0)
+    plan = male_plan(crate=20034.0)
     assert plan.info.control_steps == 1
     params = tracks.random_tracks(2, frames, seed0=4242, consonant_heavy=True)
     audio, counts, _ = plan.synthesize_host(params)
@@ -183,7 +158,7 @@ def test_one_step_per_frame_and_chunk_aligned_lengths(frames):
     for b in range(2):
         ref = oracle.synthesize(cfg, params[b], control_rate=20034.0)
         assert counts[b] == ref.size
-        assert _within(audio[b, : ref.size], ref, TOL_F64), _peak_err(audio[b, : ref.size], ref)
+        assert within(audio[b, : ref.size], ref, TOL_F64), peak_err(audio[b, : ref.size], ref)
 
 
 # Over 1.2 M internal steps the last-bit differences between the device's and glibc's exp2/pow
@@ -199,7 +174,7 @@ def test_long_form_oversampled_tube(precision, tol):
     utterances checked against the oracle, the rest through determinism of the tiled batch."""
     pool = tracks.random_tracks(2, 7500, seed0=31337, consonant_heavy=True)
     params = np.concatenate([pool, pool, pool])  # 6 utterances, rows 0/2/4 and 1/3/5 identical
-    plan = _plan(delay=2, precision=precision)
+    plan = male_plan(delay=2, precision=precision)
     assert plan.info.internal_sample_rate == 40068 and plan.info.control_steps == 160
     audio, counts, maxabs = plan.synthesize_host(params)
     n = plan.output_count(7500)
@@ -208,7 +183,7 @@ def test_long_form_oversampled_tube(precision, tol):
     for b in range(2):
         ref = oracle.synthesize(cfg, pool[b])
         assert ref.size == n
-        assert _within(audio[b], ref, tol), _peak_err(audio[b], ref)
+        assert within(audio[b], ref, tol), peak_err(audio[b], ref)
         assert np.array_equal(audio[b], audio[b + 2]) and np.array_equal(audio[b], audio[b + 4])
 
 
@@ -217,14 +192,14 @@ def test_thirty_section_tube_batch_against_oracle():
     ragged batch, against the oracle."""
     frames = np.array([30, 0, 7, 30, 19], dtype=np.int32)
     params = tracks.random_tracks(len(frames), 30, seed0=440, consonant_heavy=True)
-    plan = _plan(layout=1)
+    plan = male_plan(layout=1)
     assert plan.info.internal_sample_rate == 60102
     audio, counts, _ = plan.synthesize_host(params, frames)
     cfg = oracle.male_config(44100.0, 1, 1)
     for b, f in enumerate(frames):
         ref = oracle.synthesize(cfg, params[b, :f]) if f else np.zeros(oracle.output_count(cfg, 0), np.float32)
         assert counts[b] == ref.size
-        assert _within(audio[b, : ref.size], ref, TOL_F64), _peak_err(audio[b, : ref.size], ref)
+        assert within(audio[b, : ref.size], ref, TOL_F64), peak_err(audio[b, : ref.size], ref)
 
 
 @pytest.mark.parametrize("delay,layout", [(1, 0), (3, 0), (1, 1)])
@@ -232,11 +207,11 @@ def test_special_case_frames(delay, layout):
     """tracks.edge_track: volumes 0 / 60 dB, frication at the first / last section, radii at the floor, velum 0, pitch and
     band-pass extremes — fp64 path against the double oracle."""
     tr = tracks.edge_track(48)
-    plan = _plan(delay=delay, layout=layout)
+    plan = male_plan(delay=delay, layout=layout)
     ref = oracle.synthesize(oracle.male_config(44100.0, delay, layout), tr)
     audio, counts, _ = plan.synthesize_host(np.stack([tr, tracks.random_track(48, 3, True), tr]))
     assert counts[0] == ref.size and np.isfinite(audio).all()
-    assert _within(audio[0, : ref.size], ref, TOL_F64), _peak_err(audio[0, : ref.size], ref)
+    assert within(audio[0, : ref.size], ref, TOL_F64), peak_err(audio[0, : ref.size], ref)
     assert np.array_equal(audio[2], audio[0])
 
 
@@ -245,12 +220,12 @@ def test_samples_do_not_depend_on_the_row_in_the_workgroup(precision, rows):
     """Several utterances per workgroup (the shape a big batch would get, forced through the diagnostics library): the same
     track must give the same samples, bit for bit, in whichever DPP row and workgroup it lands (the resampler's per-row
     code is unrolled)."""
-    plan = _plan(delay=2, precision=precision, rows=rows)
+    plan = male_plan(delay=2, precision=precision, rows=rows)
     pool = tracks.random_tracks(3, 60, seed0=8100, consonant_heavy=True)
     order = [0, 1, 2, 2, 0, 1, 1, 2, 0, 0, 0]  # every track in several rows and workgroups
     audio, counts, _ = plan.synthesize_host(pool[order])
     first = {t: order.index(t) for t in range(3)}
     for b, t in enumerate(order):
         assert np.array_equal(audio[b], audio[first[t]]), (b, t)
-    alone, _, _ = _plan(delay=2, precision=precision).synthesize_host(pool[:1])
+    alone, _, _ = male_plan(delay=2, precision=precision).synthesize_host(pool[:1])
     assert np.array_equal(alone[0], audio[0])  # and the same as one utterance per workgroup

@@ -18,19 +18,12 @@ import gama_tts_amd as g
 from gama_tts_amd import capi
 import oracle
 import tracks
+from parity_rules import TOL, peak_err, within
 
 pytestmark = pytest.mark.gpu
 
 MAX_FRAMES = 36
 POOL = 32
-
-
-def _within(got, ref, tol):
-    ref64 = ref.astype(np.float64)
-    peak = float(np.abs(ref64).max())
-    d = np.abs(got.astype(np.float64) - ref64)
-    ulp = np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
-    return bool((d <= np.maximum(ulp, tol * max(peak, 1e-300))).all())
 
 
 def _pool(seed):
@@ -43,7 +36,7 @@ def _pool(seed):
 
 
 @pytest.mark.parametrize("batch,expect_rows", [(384, 2), (640, 4), (1027, 4)], ids=["b384_two_rows", "b640_four_rows", "b1027_four_rows"])
-@pytest.mark.parametrize("precision,float_model,tol", [(capi.PRECISION_F64, 0, 1e-9), (capi.PRECISION_MIXED, 0, 1e-5), (capi.PRECISION_F32, 1, 0.0)],
+@pytest.mark.parametrize("precision,float_model,tol", [(p, int(p == capi.PRECISION_F32), TOL[p]) for p in (capi.PRECISION_F64, capi.PRECISION_MIXED, capi.PRECISION_F32)],
                          ids=["f64", "mixed", "f32"])
 @pytest.mark.parametrize("delay", [2, 1], ids=["d2", "d1"])
 def test_product_library_shape_selection_against_the_oracle(batch, expect_rows, precision, float_model, tol, delay):
@@ -63,10 +56,7 @@ def test_product_library_shape_selection_against_the_oracle(batch, expect_rows, 
         r = refs[t]
         assert counts[t] == r.size, (t, counts[t], r.size)
         got = audio[t, : r.size]
-        if float_model:
-            assert np.array_equal(got, r), t
-        else:
-            assert _within(got, r, tol), (t, float(np.abs(got.astype(np.float64) - r).max() / max(np.abs(r).max(), 1e-300)))
+        assert within(got, r, tol), (t, peak_err(got, r))
         assert maxabs[t] == (np.abs(got).max() if r.size else 0.0)
         assert not audio[t, r.size:].any()  # the rest of a ragged row comes back zero
     for b in range(POOL, batch):

@@ -9,13 +9,10 @@ import gama_tts_amd as g
 from gama_tts_amd import capi
 import oracle
 import tracks
+from parity_rules import largest_error_within
+from voice_cases import male5_plan, male_plan
 
 pytestmark = pytest.mark.gpu
-
-
-def _plan(precision, delay=1, rate=44100.0, layout=0, crate=250.0, rows=0):
-    d = g.read_config_file(oracle.VOICE_MALE)
-    return g.Plan(g.config_from_dict(d, rate, delay, precision, layout), crate, 0, diagnostics=bool(rows), rows=rows)
 
 
 def _stream_one(plan, track, blocks):
@@ -40,7 +37,7 @@ def _stream_one(plan, track, blocks):
 def test_uneven_blocks_equal_one_shot_bit_for_bit(precision, delay, rate, layout):
     frames = 83 if rate == 22050.0 else 97   # 83 frames at 22.05 kHz: the converter's flush overrun at finish
     track = tracks.random_track(frames, 5100 + delay, True)
-    plan = _plan(precision, delay, rate, layout)
+    plan = male_plan(rate=rate, delay=delay, precision=precision, layout=layout)
     whole, counts, peak = plan.synthesize_host(track[None])
     got, maxabs, _ = _stream_one(plan, track, [1, 7, 3, 1, 1, 40, 2, 13, 5, 1, 9])
     assert got.size == counts[0]
@@ -51,13 +48,13 @@ def test_uneven_blocks_equal_one_shot_bit_for_bit(precision, delay, rate, layout
         assert np.array_equal(got, ref)   # and therefore bit-identical to the reference's float class
     elif precision == capi.PRECISION_F64:
         ref = oracle.synthesize(oracle.male_config(rate, delay, layout), track)
-        assert np.abs(got.astype(np.float64) - ref).max() <= 1e-9 * np.abs(ref).max() + np.spacing(np.float32(np.abs(ref).max()))
+        assert largest_error_within(got, ref, 1e-9)
 
 
 def test_single_frame_pushes_and_reset():
     """One frame at a time (the converter, the decimator and every recurrence cross a launch boundary again and
     again), then the same stream object reused after reset()."""
-    plan = _plan(capi.PRECISION_F32)
+    plan = male_plan(precision=capi.PRECISION_F32)
     a, b = tracks.random_track(30, 61, True), tracks.random_track(17, 62, False)
     ref_a = oracle.synthesize(oracle.male_config(float_model=1), a)
     ref_b = oracle.synthesize(oracle.male_config(float_model=1), b)
@@ -72,7 +69,7 @@ def test_single_frame_pushes_and_reset():
 
 
 def test_empty_and_tiny_utterances():
-    plan = _plan(capi.PRECISION_F64)
+    plan = male_plan(precision=capi.PRECISION_F64)
     st = g.Stream(plan, 1)
     tail, maxabs = st.finish()                       # nothing pushed: the flush of an empty utterance
     assert tail[0].size == plan.output_count(0) and not tail[0].any() and maxabs[0] == 0.0
@@ -88,7 +85,7 @@ def test_empty_and_tiny_utterances():
 def test_batch_stream_ragged_pushes(rows):
     """Five utterances pushed with different frame counts each time (one workgroup per utterance), and in lockstep
     (shared workgroups, the shape forced through the diagnostics library)."""
-    plan = _plan(capi.PRECISION_F32, delay=2, rows=rows)
+    plan = male_plan(delay=2, precision=capi.PRECISION_F32, rows=rows)
     total = np.array([50, 0, 37, 50, 12], dtype=np.int32) if rows == 0 else np.array([48] * 5, dtype=np.int32)
     params = tracks.random_tracks(5, 50, seed0=6400, consonant_heavy=True)
     cfg = oracle.male_config(44100.0, 2, float_model=1)
@@ -118,7 +115,7 @@ def test_batch_stream_ragged_pushes(rows):
 
 def test_long_track_in_one_second_pieces():
     """The streaming use the one-shot entry cannot serve in bounded memory: a 30 s utterance, one second at a time."""
-    plan = _plan(capi.PRECISION_F32)
+    plan = male_plan(precision=capi.PRECISION_F32)
     track = tracks.random_track(7500, 6500)
     whole, counts, _ = plan.synthesize_host(track[None])
     got, _, _ = _stream_one(plan, track, [250] * 30)
@@ -135,18 +132,13 @@ def test_stream_refusals():
 
 # ---- reference model 5 as a stateful object (vtm/VocalTractModel5.h:523-579) -------------------------------------------
 
-def _plan5(rate=48000.0, crate=250.0, rows=0):
-    d = g.read_config_file(oracle.VOICE5_MALE)
-    return g.Plan(g.config5_from_dict(d, rate), crate, 0, diagnostics=bool(rows), rows=rows)
-
-
 @pytest.mark.parametrize("rate,frames", [(48000.0, 97), (44100.0, 106), (96000.0, 41)], ids=["48k", "44k_overrun106", "96k_up"])
 def test_model5_uneven_blocks_equal_one_shot_bit_for_bit(rate, frames):
     """Pieces of 1..40 frames (every recurrence, the feed-forward halves' predecessors, the converter's ring and the
     difference filter's look-back cross launch boundaries at arbitrary places); 106 frames at 44.1 kHz finishes on a flush
     overrun of the converter."""
     track = tracks.random_track(frames, 5500, True)
-    plan = _plan5(rate)
+    plan = male5_plan(rate=rate)
     whole, counts, peak = plan.synthesize_host(track[None])
     got, maxabs, _ = _stream_one(plan, track, [1, 7, 3, 1, 1, 40, 2, 13, 5, 1, 9])
     assert got.size == counts[0]
@@ -158,7 +150,7 @@ def test_model5_uneven_blocks_equal_one_shot_bit_for_bit(rate, frames):
 
 
 def test_model5_single_frame_pushes_reset_and_ragged_batch():
-    plan = _plan5()
+    plan = male5_plan()
     track = tracks.random_track(23, 5600, True)
     whole, counts, _ = plan.synthesize_host(track[None])
     got, _, st = _stream_one(plan, track, [1] * 23)

@@ -13,13 +13,13 @@ import os
 import numpy as np
 import pytest
 
-import gama_tts_amd as g
 from gama_tts_amd import capi
 import event_lists
 import oracle
 import tracks_edges_cases as cases
-from test_gpu_tracks import _events_on_device
-from test_tracks_cpu import _product_config
+from device_io import events_chain_and_entry, events_on_device
+from track_cases import product_config
+from voice_cases import male_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -103,14 +103,14 @@ def _launch(cfg, tabs, max_frames, drift_in):
     """gvtm_generate_tracks_device on a buffer filled with SENTINEL (GUARD_FRAMES more frames behind the last row) ->
     (params [B][max_frames][16], guard, counts, drift out), all on the host."""
     import torch
-    d_events, d_offsets = _events_on_device(tabs)
+    d_events, d_offsets = events_on_device(tabs)
     dev = d_events.device
     b = len(tabs)
     buf = torch.full(((b * max_frames + GUARD_FRAMES) * 16,), SENTINEL, dtype=torch.int32, device=dev).view(torch.float32)
     counts = torch.full((b,), -7, dtype=torch.int32, device=dev)
     drift = torch.from_numpy(np.ascontiguousarray(drift_in, dtype=np.float64)).to(dev)
     stream = torch.cuda.current_stream().cuda_stream
-    capi.generate_tracks_device(_product_config(cfg), d_events, d_offsets, b, max_frames, buf, counts, drift, stream)
+    capi.generate_tracks_device(product_config(cfg), d_events, d_offsets, b, max_frames, buf, counts, drift, stream)
     torch.cuda.synchronize()
     out = buf.cpu().numpy()
     params = out[: b * max_frames * 16].reshape(b, max_frames, 16)
@@ -147,7 +147,7 @@ def _chain(names, tables, calls, drift0, max_frames=None):
     tabs = [tables[n] for n in names]
     drift = np.array(drift0, dtype=np.float64)
     for i, cfg in enumerate(calls):
-        mf = max_frames or max(1, max(capi.tracks_frame_count(_product_config(cfg), capi.events_from_table(t)) for t in tabs))
+        mf = max_frames or max(1, max(capi.tracks_frame_count(product_config(cfg), capi.events_from_table(t)) for t in tabs))
         got = _launch(cfg, tabs, mf, drift)
         yield i, cfg, tabs, mf, got, drift
         drift = got[3].copy()
@@ -209,7 +209,7 @@ def test_ring_flushes_and_truncation(max_frames, tables):
         names += [n, "e0" if k % 2 else "e1"]
     cfg = cases.cfg()
     for n in longs:
-        assert capi.tracks_frame_count(_product_config(cfg), capi.events_from_table(tables[n])) == int(n[6:])
+        assert capi.tracks_frame_count(product_config(cfg), capi.events_from_table(tables[n])) == int(n[6:])
     drift0 = _states(len(names), 13)
     got = _launch(cfg, [tables[n] for n in names], max_frames, drift0)
     _check_rows(cfg, [tables[n] for n in names], max_frames, drift0, got, "ring max_frames=%d" % max_frames)
@@ -266,29 +266,16 @@ def test_events_entry_at_the_edges(tables):
     names = ["b240", "b241", "b239", "e2", "b241", "e0", "b242", "b240", "joined3000"]
     tabs = [tables[n] for n in names]
     cfgv = cases.cfg(4, 0, 1, 1, 1)
-    tc = _product_config(cfgv)
+    tc = product_config(cfgv)
     frames_of = [capi.tracks_frame_count(tc, capi.events_from_table(t)) for t in tabs]
     max_frames = max(frames_of)
-    d_events, d_offsets = _events_on_device(tabs)
-    dev = d_events.device
-    stream = torch.cuda.current_stream().cuda_stream
     batch = len(tabs)
     drift0 = _states(batch, 17)
-    plan = g.Plan(g.config_from_dict(g.read_config_file(oracle.VOICE_MALE), 44100.0, 1, capi.PRECISION_F32), 250.0, 0)
+    plan = male_plan(precision=capi.PRECISION_F32)
     stride = plan.output_capacity(max_frames)
-
-    def fresh():
-        return (torch.zeros((batch, stride), dtype=torch.float32, device=dev), torch.zeros(batch, dtype=torch.int32, device=dev),
-                torch.zeros(batch, dtype=torch.int64, device=dev), torch.zeros(batch, dtype=torch.float32, device=dev),
-                torch.from_numpy(drift0.copy()).to(dev))
-
-    a1, f1, n1, m1, dr1 = fresh()
-    d_params = torch.zeros((batch, max_frames, 16), dtype=torch.float32, device=dev)
-    capi.generate_tracks_device(tc, d_events, d_offsets, batch, max_frames, d_params, f1, dr1, stream)
-    plan.synthesize_device(d_params, batch, max_frames, a1, stride, f1, n1, m1, stream)
-    a2, f2, n2, m2, dr2 = fresh()
-    plan.synthesize_events_device(tc, d_events, d_offsets, batch, max_frames, a2, stride, f2, n2, m2, dr2, stream)
-    torch.cuda.synchronize()
+    chain, entry, d_params = events_chain_and_entry(plan, tc, tabs, max_frames, stride, drift0)
+    a1, f1, n1, m1, dr1 = chain
+    a2, f2, n2, m2, dr2 = entry
     assert f2.cpu().tolist() == frames_of
     assert torch.equal(f1, f2) and torch.equal(n1, n2)
     assert torch.equal(dr1.view(torch.int64), dr2.view(torch.int64))

@@ -5,8 +5,6 @@ The five GamaTTS variants of data/voice/english/0_male (tests/golden/voice_*.txt
 of its voice synthesizes it in the same workgroup shape, and within the parity tests' tolerances of the oracle (float:
 bit-identical).  The grouping kernel (a stable counting sort by voice, each voice padded to whole workgroups) is checked
 on its own against a numpy restatement."""
-import os
-
 import numpy as np
 import pytest
 
@@ -14,61 +12,12 @@ import gama_tts_amd as g
 from gama_tts_amd import capi
 import oracle
 import tracks
+from device_io import run_voices_device
+from parity_rules import TOL, within
+from voice_cases import CASE_IDS, CASES, configs, mixed_batch, oracle_config
+from voice_files import VOICES
 
 pytestmark = pytest.mark.gpu
-
-VOICES = ["male", "female", "large_child", "small_child", "baby"]
-TOL = {capi.PRECISION_F64: 1e-9, capi.PRECISION_MIXED: 1e-5, capi.PRECISION_F32: 0.0}
-
-
-def voice_path(name):
-    return os.path.join(oracle.GOLDEN_DIR, "voice_%s.txt" % name)
-
-
-def configs(rate=44100.0, delay=1, precision=capi.PRECISION_F64, layout=0, names=VOICES):
-    return [g.config_from_dict(g.read_config_file(voice_path(n)), rate, delay, precision, layout) for n in names]
-
-
-def oracle_config(name, rate, delay, layout, precision):
-    return oracle.config_from_dict(oracle.read_config_file(voice_path(name)), rate, delay, layout,
-                                   1 if precision == capi.PRECISION_F32 else 0)
-
-
-def within(got, ref, tol):
-    """Every sample within max(tol * peak, one float32 ulp of the reference sample) (test_gpu_parity's rule)."""
-    if tol == 0.0:
-        return np.array_equal(got, ref)
-    ref64 = ref.astype(np.float64)
-    peak = float(np.abs(ref64).max()) if ref.size else 0.0
-    d = np.abs(got.astype(np.float64) - ref64)
-    ulp = np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
-    return bool((d <= np.maximum(ulp, tol * max(peak, 1e-300))).all())
-
-
-def mixed_batch(batch, max_frames, n_voices, seed):
-    """Interleaved, ragged ids; 0-, 1- and 2-frame utterances of every voice."""
-    rng = np.random.default_rng(seed)
-    ids = rng.integers(0, n_voices, size=batch).astype(np.int32)
-    ids[: 3 * n_voices] = np.repeat(np.arange(n_voices, dtype=np.int32), 3)
-    frames = rng.integers(3, max_frames + 1, size=batch).astype(np.int32)
-    frames[: 3 * n_voices] = np.tile([0, 1, 2], n_voices)
-    perm = rng.permutation(batch)
-    params = tracks.random_tracks(batch, max_frames, seed0=seed, consonant_heavy=True)
-    return params, ids[perm], frames[perm]
-
-
-def run_device(plan, params, ids, frames, stride, fill=0.0):
-    import torch
-    batch, max_frames = params.shape[:2]
-    dp = torch.from_numpy(np.ascontiguousarray(params)).cuda()
-    di = torch.from_numpy(np.ascontiguousarray(ids)).cuda()
-    df = torch.from_numpy(np.ascontiguousarray(frames)).cuda()
-    da = torch.full((batch, stride), fill, dtype=torch.float32, device="cuda")
-    dc = torch.zeros(batch, dtype=torch.int64, device="cuda")
-    dm = torch.full((batch,), 5.0, dtype=torch.float32, device="cuda")
-    plan.synthesize_voices_device(dp, di, batch, max_frames, da, stride, df, dc, dm, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return da.cpu().numpy(), dc.cpu().numpy(), dm.cpu().numpy()
 
 
 def singles_of(cfgs, params, ids, frames, diagnostics=False, rows=0):
@@ -87,20 +36,13 @@ def singles_of(cfgs, params, ids, frames, diagnostics=False, rows=0):
     return out
 
 
-CASES = [(capi.PRECISION_F32, 1, 44100.0, 0), (capi.PRECISION_F32, 2, 44100.0, 0),
-         (capi.PRECISION_MIXED, 1, 44100.0, 0), (capi.PRECISION_MIXED, 2, 44100.0, 0),
-         (capi.PRECISION_F64, 1, 44100.0, 0), (capi.PRECISION_F64, 2, 44100.0, 0),
-         (capi.PRECISION_F64, 1, 22050.0, 1)]
-
-
-@pytest.mark.parametrize("precision,delay,rate,layout", CASES,
-                         ids=["f32-d1", "f32-d2", "mixed-d1", "mixed-d2", "f64-d1", "f64-d2", "f64-layout1-22k"])
+@pytest.mark.parametrize("precision,delay,rate,layout", CASES, ids=CASE_IDS)
 def test_five_voices_in_one_launch(precision, delay, rate, layout):
     cfgs = configs(rate, delay, precision, layout)
     plan = g.VoicesPlan(cfgs, 250.0, 0)
     params, ids, frames = mixed_batch(48, 30, 5, seed=11 + delay + 3 * precision + 7 * layout)
     stride = plan.voices_output_capacity(params.shape[1])
-    audio, counts, maxabs = run_device(plan, params, ids, frames, stride)
+    audio, counts, maxabs = run_voices_device(plan, params, ids, frames, stride)
     singles = singles_of(cfgs, params, ids, frames)
     for b in range(len(ids)):
         v = int(ids[b])
@@ -126,7 +68,7 @@ def test_uneven_voices_in_four_row_workgroups(precision):
     params = tracks.random_tracks(6, 20, seed0=321, consonant_heavy=True)
     frames = np.array([20, 7, 13, 1, 0, 19], dtype=np.int32)
     stride = plan.voices_output_capacity(20)
-    audio, counts, maxabs = run_device(plan, params, ids, frames, stride)
+    audio, counts, maxabs = run_voices_device(plan, params, ids, frames, stride)
     singles = singles_of(cfgs, params, ids, frames, diagnostics=True, rows=4)
     for b in range(6):
         ref_audio, ref_n, ref_max = singles[b]
@@ -141,8 +83,8 @@ def test_out_of_range_voice_ids_fail_alone():
     bad = ids.copy()
     bad[[3, 10, 17]] = [-1, 5, 1 << 20]
     stride = plan.voices_output_capacity(16)
-    good_audio, good_counts, good_max = run_device(plan, params, ids, frames, stride)
-    audio, counts, maxabs = run_device(plan, params, bad, frames, stride, fill=7.0)
+    good_audio, good_counts, good_max = run_voices_device(plan, params, ids, frames, stride)
+    audio, counts, maxabs = run_voices_device(plan, params, bad, frames, stride, fill=7.0)
     for b in range(24):
         if b in (3, 10, 17):
             assert counts[b] == -1 and maxabs[b] == 0.0
@@ -175,7 +117,7 @@ def test_host_entries_slice_a_big_mixed_batch(precision):
     idx = np.random.default_rng(3).integers(0, pool, size=batch)
     params, ids, frames = pp[idx], pids[idx], pf[idx]
     stride = plan.voices_output_capacity(max_frames)
-    d_audio, d_counts, d_max = run_device(plan, params, ids, frames, stride)
+    d_audio, d_counts, d_max = run_voices_device(plan, params, ids, frames, stride)
     for b in range(batch):  # ragged rows: zero beyond the count only in the host entries; compare the counted part
         assert d_counts[b] == plan.voice_output_count(int(ids[b]), int(frames[b]))
     audio, counts, maxabs = plan.synthesize_host(params, ids, frames)

@@ -2,27 +2,20 @@
 
 The five variants of data/voice/english/5_male (tests/golden/voice5_*.txt: vocal tract 17.5 / 15 / 12.5 / 10 / 7.5 cm,
 242 to 564 internal steps per frame) mixed in one batch, ids interleaved and ragged.  Every utterance must come out bit for
-bit as a single-voice model 5 plan of its voice synthesizes it, and within test_gpu_model5.py's bar of the oracle and of
+bit as a single-voice model 5 plan of its voice synthesizes it, and within model 5's bar (parity_rules.check_model5) of the oracle and of
 the reference vectors of tests/golden/voices5_golden.npz."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 import gama_tts_amd as g
 import golden5_voices_cases as cases
 import oracle
-from test_gpu_model5 import _check
-from test_gpu_voices import mixed_batch, run_device
+import voice_files
+from device_io import run_voices_device
+from parity_rules import check_model5
+from voice_cases import configs5, mixed_batch
 
 pytestmark = pytest.mark.gpu
-
-VOICES = cases.VOICES
-
-
-def configs(rate=cases.RATE, names=VOICES):
-    return [g.config5_from_dict(g.read_config_file(cases.voice_path(n)), rate) for n in names]
 
 
 def singles_of(cfgs, params, ids, frames):
@@ -48,44 +41,41 @@ def assert_as_singles(audio, counts, maxabs, singles, ids):
 
 @pytest.fixture(scope="module")
 def plan5():
-    return g.VoicesPlan(configs(), 250.0, 0)
+    return g.VoicesPlan(configs5(), 250.0, 0)
 
 
 def test_five_voices_in_one_launch(plan5):
-    cfgs = configs()
+    cfgs = configs5()
     assert plan5.n_voices == 5 and all(plan5.voice_info(v).model5 == 1 for v in range(5))
     params, ids, frames = mixed_batch(45, 14, 5, seed=51)
     stride = plan5.voices_output_capacity(14)
-    audio, counts, maxabs = run_device(plan5, params, ids, frames, stride)
+    audio, counts, maxabs = run_voices_device(plan5, params, ids, frames, stride)
     for b in range(len(ids)):
         assert counts[b] == plan5.voice_output_count(int(ids[b]), int(frames[b]))
     assert_as_singles(audio, counts, maxabs, singles_of(cfgs, params, ids, frames), ids)
     # the two longest utterances of every voice against the oracle
-    for v, name in enumerate(VOICES):
+    for v, name in enumerate(voice_files.VOICES):
         sel = np.nonzero(ids == v)[0]
         for b in sel[np.argsort(frames[sel])[-2:]]:
             ref, _ = oracle.synthesize5(cases.oracle_config(name), params[b, : frames[b]])
             assert counts[b] == ref.size
-            _check(audio[b, : ref.size], ref)
+            check_model5(audio[b, : ref.size], ref)
 
 
 def test_diagnostics_two_row_shape_gives_one_row_to_voices(plan5):
     # a plan that forces two utterances per workgroup runs its voices launches with one (the voice variant's only shape)
     params, ids, frames = mixed_batch(20, 8, 5, seed=52)
     stride = plan5.voices_output_capacity(8)
-    want = run_device(plan5, params, ids, frames, stride)
-    diag = g.VoicesPlan(configs(), 250.0, 0, diagnostics=True, rows=2)
-    got = run_device(diag, params, ids, frames, stride)
+    want = run_voices_device(plan5, params, ids, frames, stride)
+    diag = g.VoicesPlan(configs5(), 250.0, 0, diagnostics=True, rows=2)
+    got = run_voices_device(diag, params, ids, frames, stride)
     for w, x in zip(want, got):
         assert np.array_equal(w, x)
 
 
 @pytest.fixture(scope="module")
 def golden5v():
-    z = np.load(os.path.join(oracle.GOLDEN_DIR, "voices5_golden.npz"), allow_pickle=False)
-    data = {k: z[k] for k in z.files}
-    data["manifest"] = json.loads(bytes(data.pop("manifest_json")).decode())
-    return data
+    return voice_files.golden5v()
 
 
 @pytest.mark.parametrize("rate", sorted({c["rate"] for c in cases.CASES}), ids=lambda r: "%dHz" % r)
@@ -96,12 +86,12 @@ def test_reference_vectors_through_a_mixed_launch(rate, golden, golden5v):
     trs = [cases.track_for(c, golden) for c in sel]
     male = cases.track_for(dict(track=("random", 60, 70, True)))
     trs.append(male)
-    ids = np.array([VOICES.index(c["voice"]) for c in sel] + [0], dtype=np.int32)
+    ids = np.array([voice_files.VOICES.index(c["voice"]) for c in sel] + [0], dtype=np.int32)
     frames = np.array([t.shape[0] for t in trs], dtype=np.int32)
     params = np.zeros((len(trs), int(frames.max()), 16), dtype=np.float32)
     for b, t in enumerate(trs):
         params[b, : t.shape[0]] = t
-    plan = g.VoicesPlan(configs(rate), 250.0, 0)
+    plan = g.VoicesPlan(configs5(rate), 250.0, 0)
     audio, counts, maxabs = plan.synthesize_host(params, ids, frames)
     for b, c in enumerate(sel):
         m = golden5v["manifest"][c["name"]]
@@ -109,15 +99,15 @@ def test_reference_vectors_through_a_mixed_launch(rate, golden, golden5v):
         assert counts[b] == m["n"], c["name"]
         out = audio[b, : m["n"]]
         if c["store"] == "full":
-            _check(out, golden5v[c["name"] + "__out"], peak=m["maxabs"])
+            check_model5(out, golden5v[c["name"] + "__out"], peak=m["maxabs"])
         else:
-            _check(out[:: cases.DIGEST_STRIDE], golden5v[c["name"] + "__strided"], peak=m["maxabs"])
+            check_model5(out[:: cases.DIGEST_STRIDE], golden5v[c["name"] + "__strided"], peak=m["maxabs"])
         if c["store"] == "tail":
-            _check(out[-cases.OVERRUN_TAIL:], golden5v[c["name"] + "__tail"], peak=m["maxabs"])
+            check_model5(out[-cases.OVERRUN_TAIL:], golden5v[c["name"] + "__tail"], peak=m["maxabs"])
         assert maxabs[b] == pytest.approx(m["maxabs"], rel=1e-5)
     ref, _ = oracle.synthesize5(cases.oracle_config("male", rate), male)
     assert counts[-1] == ref.size
-    _check(audio[-1, : ref.size], ref)
+    check_model5(audio[-1, : ref.size], ref)
 
 
 def test_out_of_range_voice_ids_fail_alone(plan5):
@@ -125,8 +115,8 @@ def test_out_of_range_voice_ids_fail_alone(plan5):
     bad = ids.copy()
     bad[[3, 10, 17]] = [-1, 5, 1 << 20]
     stride = plan5.voices_output_capacity(10)
-    good_audio, good_counts, good_max = run_device(plan5, params, ids, frames, stride)
-    audio, counts, maxabs = run_device(plan5, params, bad, frames, stride, fill=7.0)
+    good_audio, good_counts, good_max = run_voices_device(plan5, params, ids, frames, stride)
+    audio, counts, maxabs = run_voices_device(plan5, params, bad, frames, stride, fill=7.0)
     for b in range(24):
         if b in (3, 10, 17):
             assert counts[b] == -1 and maxabs[b] == 0.0
@@ -142,15 +132,15 @@ def test_out_of_range_voice_ids_fail_alone(plan5):
 def test_a_batch_of_one_voice_only(plan5):
     params, _, frames = mixed_batch(20, 10, 5, seed=54)
     ids = np.full(20, 4, dtype=np.int32)  # baby: 564 steps per frame
-    audio, counts, maxabs = run_device(plan5, params, ids, frames, plan5.voices_output_capacity(10))
-    assert_as_singles(audio, counts, maxabs, singles_of(configs(), params, ids, frames), ids)
+    audio, counts, maxabs = run_voices_device(plan5, params, ids, frames, plan5.voices_output_capacity(10))
+    assert_as_singles(audio, counts, maxabs, singles_of(configs5(), params, ids, frames), ids)
 
 
 def test_more_workgroups_than_compute_units(plan5):
     # 600 utterances: more than one workgroup per compute unit, and a padding workgroup per voice past the last one
     params, ids, frames = mixed_batch(600, 6, 5, seed=55)
-    audio, counts, maxabs = run_device(plan5, params, ids, frames, plan5.voices_output_capacity(6))
-    assert_as_singles(audio, counts, maxabs, singles_of(configs(), params, ids, frames), ids)
+    audio, counts, maxabs = run_voices_device(plan5, params, ids, frames, plan5.voices_output_capacity(6))
+    assert_as_singles(audio, counts, maxabs, singles_of(configs5(), params, ids, frames), ids)
 
 
 def test_host_entries_slice_a_big_mixed_batch(plan5):
@@ -160,7 +150,7 @@ def test_host_entries_slice_a_big_mixed_batch(plan5):
     batch, max_frames = 2 * torch.cuda.get_device_properties(0).multi_processor_count + 77, 5
     params, ids, frames = mixed_batch(batch, max_frames, 5, seed=56)
     stride = plan5.voices_output_capacity(max_frames)
-    d_audio, d_counts, d_max = run_device(plan5, params, ids, frames, stride)
+    d_audio, d_counts, d_max = run_voices_device(plan5, params, ids, frames, stride)
     audio, counts, maxabs = plan5.synthesize_host(params, ids, frames)
     assert np.array_equal(counts, d_counts) and np.array_equal(maxabs, d_max)
     for b in range(batch):
@@ -178,7 +168,7 @@ def test_host_entries_slice_a_big_mixed_batch(plan5):
 
 
 def test_one_voice_model5_plan_takes_the_voices_entries():
-    cfg = configs(names=["small_child"])
+    cfg = configs5(names=["small_child"])
     params, _, frames = mixed_batch(9, 8, 1, seed=57)
     ids = np.zeros(9, dtype=np.int32)
     single = g.Plan(cfg[0], 250.0, 0)

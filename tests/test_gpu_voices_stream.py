@@ -4,9 +4,6 @@ Utterance b of a voices stream must come out, bit for bit (samples, counts, maxa
 single-voice plan of its voice gives it for the same frames, whatever the split of the pushes, the mix of ids and the
 workgroup shape.  The five 0_male variants (tests/golden/voice_*.txt) in every precision, the five 5_male variants
 (voice5_*.txt) with their flush-overrun lengths against the reference vectors of tests/golden/voices5_golden.npz."""
-import json
-import os
-
 import numpy as np
 import pytest
 
@@ -15,14 +12,11 @@ from gama_tts_amd import capi
 import golden5_voices_cases as cases5
 import oracle
 import tracks
-from test_gpu_model5 import _check
-from test_gpu_voices import CASES, VOICES, configs, oracle_config
+import voice_files
+from parity_rules import check_model5
+from voice_cases import CASE_IDS, CASES, configs, configs5, oracle_config
 
 pytestmark = pytest.mark.gpu
-
-
-def configs5(rate=cases5.RATE, names=cases5.VOICES):
-    return [g.config5_from_dict(g.read_config_file(cases5.voice_path(n)), rate) for n in names]
 
 
 def ragged_schedule(total, rng, max_piece=25, single_rounds=0):
@@ -100,8 +94,7 @@ def overrun_length(plan, voice, lo=1, hi=400):
     return None
 
 
-@pytest.mark.parametrize("precision,delay,rate,layout", CASES,
-                         ids=["f32-d1", "f32-d2", "mixed-d1", "mixed-d2", "f64-d1", "f64-d2", "f64-layout1-22k"])
+@pytest.mark.parametrize("precision,delay,rate,layout", CASES, ids=CASE_IDS)
 def test_five_voices_ragged_pushes(precision, delay, rate, layout):
     cfgs = configs(rate, delay, precision, layout)
     plan = g.VoicesPlan(cfgs, 250.0, 0)
@@ -132,7 +125,7 @@ def test_five_voices_ragged_pushes(precision, delay, rate, layout):
         at = sum(int(r[b]) for r in rounds)
         assert samples[b].size == plan.voice_output_count(v, at), b
         if precision == capi.PRECISION_F32:
-            want = oracle.synthesize(oracle_config(VOICES[v], rate, delay, layout, precision), params[b, :at])
+            want = oracle.synthesize(oracle_config(voice_files.VOICES[v], rate, delay, layout, precision), params[b, :at])
             assert np.array_equal(samples[b], want), (b, v)
 
 
@@ -166,7 +159,7 @@ def test_workgroup_shape_changes_between_pushes(precision):
     with a ring of its own fits next to the stream's ring: two rows of 96 steps already take 512.)  Every launch must
     keep each voice's ring at its single-voice stream's length, or the state one shape saves is not the one the next
     reads.  References: single-voice streams, whose launches all have one row."""
-    names = VOICES[:4]
+    names = voice_files.VOICES[:4]
     cfgs = configs(precision=precision, names=names)
     plan = g.VoicesPlan(cfgs, 250.0, 0, diagnostics=True, rows=4)
     for v in range(4):
@@ -193,10 +186,7 @@ def test_workgroup_shape_changes_between_pushes(precision):
 
 @pytest.fixture(scope="module")
 def golden5v():
-    z = np.load(os.path.join(oracle.GOLDEN_DIR, "voices5_golden.npz"), allow_pickle=False)
-    data = {k: z[k] for k in z.files}
-    data["manifest"] = json.loads(bytes(data.pop("manifest_json")).decode())
-    return data
+    return voice_files.golden5v()
 
 
 @pytest.mark.parametrize("rate", sorted({c["rate"] for c in cases5.CASES}), ids=lambda r: "%dHz" % r)
@@ -207,7 +197,7 @@ def test_model5_five_voices_with_overrun_lengths(rate, golden, golden5v):
     plan = g.VoicesPlan(cfgs, 250.0, 0)
     sel = [c for c in cases5.CASES if c["rate"] == rate and c["store"] == "tail"]
     trs = [cases5.track_for(c, golden) for c in sel]
-    ids = [cases5.VOICES.index(c["voice"]) for c in sel]
+    ids = [voice_files.VOICES.index(c["voice"]) for c in sel]
     rng = np.random.default_rng(int(rate))
     for v in range(5):  # two more utterances of every voice
         for _ in range(2):
@@ -228,8 +218,8 @@ def test_model5_five_voices_with_overrun_lengths(rate, golden, golden5v):
         m = golden5v["manifest"][c["name"]]
         out = samples[b]
         assert out.size == m["n"], c["name"]
-        _check(out[:: cases5.DIGEST_STRIDE], golden5v[c["name"] + "__strided"], peak=m["maxabs"])
-        _check(out[-cases5.OVERRUN_TAIL:], golden5v[c["name"] + "__tail"], peak=m["maxabs"])
+        check_model5(out[:: cases5.DIGEST_STRIDE], golden5v[c["name"] + "__strided"], peak=m["maxabs"])
+        check_model5(out[-cases5.OVERRUN_TAIL:], golden5v[c["name"] + "__tail"], peak=m["maxabs"])
         assert maxabs[b] == pytest.approx(m["maxabs"], rel=1e-5)
 
 

@@ -33,44 +33,8 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 import gama_tts_amd as g  # noqa: E402
-import oracle  # noqa: E402
 from gama_tts_amd import capi  # noqa: E402
-
-GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_shapes.json")
-PRECISIONS = (("f64", capi.PRECISION_F64), ("mixed", capi.PRECISION_MIXED), ("f32", capi.PRECISION_F32))
-ROWS = (1, 2, 4, 8)
-
-
-def plans():
-    """(name, config, is_model5) of every plan of the enumeration, in a fixed order."""
-    cfgd = g.read_config_file(oracle.VOICE_MALE)
-    for pname, prec in PRECISIONS:
-        for layout, delays in ((capi.TUBE_10_6, (1, 2, 3, 4)), (capi.TUBE_30_18, (1,))):
-            for delay in delays:
-                for rate in (44100, 22050):
-                    yield ("%s delay %d rate %d layout %d" % (pname, delay, rate, layout), g.config_from_dict(cfgd, float(rate), delay, prec, layout), False)
-    yield ("model5", g.config5_from_dict(g.read_config_file(oracle.VOICE5_MALE)), True)
-
-
-def launched_rows(name, rows):
-    """The rows of the shape a launch with `rows` forced has (module docstring)."""
-    if rows == 8 and (not name.startswith("f32") or name.endswith("layout 1")):
-        return 4
-    return rows
-
-
-def lds_bytes():
-    """{(plan name, rows): bytes} of every case, as the diagnostics library answers."""
-    lib = g.load_library(diagnostics=True)
-    lib.gvtm_debug_lds_bytes.restype = ctypes.c_size_t
-    lib.gvtm_debug_lds_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    out = {}
-    for name, config, model5 in plans():
-        plan = g.Plan(config, 250.0, capi.DEVICE_NONE, diagnostics=True)
-        for rows in ((1, 2) if model5 else ROWS):
-            out[name, rows] = int(lib.gvtm_debug_lds_bytes(plan._h, rows))
-        plan.close()
-    return out
+from kernel_shape_cases import GOLDEN, ROWS, launched_rows, lds_bytes, plans  # noqa: E402
 
 
 def test_lds_bytes_of_every_shape_are_the_recorded_ones():

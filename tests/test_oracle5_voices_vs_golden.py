@@ -3,22 +3,18 @@ reference classes for the four 5_male variants besides male (tests/golden/voices
 tests/golden/make_voices5_golden.py): the bar of test_oracle5_vs_golden.py, on voices whose internal rates (70.5 to
 141 kHz) the 5_male vectors never reach."""
 import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
 import golden5_voices_cases as cases
 import oracle
+import voice_files
 
 
 @pytest.fixture(scope="module")
 def golden5v():
-    z = np.load(os.path.join(oracle.GOLDEN_DIR, "voices5_golden.npz"), allow_pickle=False)
-    data = {k: z[k] for k in z.files}
-    data["manifest"] = json.loads(bytes(data.pop("manifest_json")).decode())
-    return data
+    return voice_files.golden5v()
 
 
 @pytest.mark.parametrize("case", cases.CASES, ids=lambda c: c["name"])

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import golden5_cases
+import golden_cases
 import oracle
 
 
@@ -50,9 +51,8 @@ def test_model5_internal_rate():
 def test_oracle5_matches_reference_binary_on_fresh_tracks(model, fm):
     """Seeded random tracks against what the reference binary produced for them (tests/golden/random_golden.npz)."""
     import tracks
-    from test_oracle_vs_reference import check_against_random_golden
     for seed in (31, 32):
         tr = tracks.random_track(60, seed, seed % 2 == 0)
         out, rate = oracle.synthesize5(oracle.male5_config(48000.0, fm), tr)
-        m = check_against_random_golden(out, model, seed)
+        m = golden_cases.check_against_random_golden(out, model, seed)
         assert abs(rate - m["fs"]) < 2e-3

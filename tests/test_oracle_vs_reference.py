@@ -4,34 +4,11 @@ tests/golden/random_golden.npz holds what oracle/_ref/ref_vtm (compiled from the
 produced for these tracks: sample count, SHA-256 of the float32 output and a strided subset
 (tests/golden/make_random_golden.py), so that the comparison runs in every checkout.
 """
-import hashlib
-import json
-import os
-
-import numpy as np
 import pytest
 
 import golden_cases
 import oracle
 import tracks
-
-
-def random_golden():
-    z = np.load(os.path.join(oracle.GOLDEN_DIR, "random_golden.npz"), allow_pickle=False)
-    data = {k: z[k] for k in z.files}
-    data["manifest"] = json.loads(bytes(data.pop("manifest_json")).decode())
-    return data
-
-
-def check_against_random_golden(out, model, seed):
-    """`out` against the reference's output for (model, seed): same count, bit for bit (digest and strided samples)."""
-    g = random_golden()
-    key = "m%s_s%d" % (model.replace(":", "d"), seed)
-    m = g["manifest"][key]
-    assert out.size == m["n"]
-    assert np.array_equal(out[:: golden_cases.DIGEST_STRIDE], g[key + "__strided"])
-    assert hashlib.sha256(out.tobytes()).hexdigest() == m["sha256"]
-    return m
 
 
 @pytest.mark.parametrize("model,delay,layout,fm", [("0", 1, 0, 0), ("2", 1, 0, 0), ("2:2", 2, 0, 0), ("3", 3, 0, 0), ("4", 1, 1, 0),
@@ -40,4 +17,4 @@ def check_against_random_golden(out, model, seed):
 def test_bit_identical_on_random_tracks(model, delay, layout, fm, seed):
     tr = tracks.random_track(90, seed, consonant_heavy=bool(seed & 1))
     out = oracle.synthesize(oracle.male_config(section_delay=delay, layout=layout, float_model=fm), tr)
-    check_against_random_golden(out, model, seed)
+    golden_cases.check_against_random_golden(out, model, seed)

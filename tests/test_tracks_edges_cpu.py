@@ -10,7 +10,7 @@ from gama_tts_amd import capi
 import event_lists
 import oracle
 import tracks_edges_cases as cases
-from test_tracks_cpu import _product_config
+from track_cases import product_config
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -50,7 +50,7 @@ def test_oracle_matches_reference_at_the_edges(name, edges, tables):
 def test_frame_count_matches_reference_at_the_edges(name, edges, tables):
     ev = capi.events_from_table(tables[name])
     for i, c in enumerate(cases.calls(name)):
-        assert capi.tracks_frame_count(_product_config(c), ev) == int(edges["%s__%d__count" % (name, i)]), (name, i)
+        assert capi.tracks_frame_count(product_config(c), ev) == int(edges["%s__%d__count" % (name, i)]), (name, i)
 
 
 def test_edge_lists_have_the_shapes_they_are_named_for(tables):
@@ -91,7 +91,7 @@ def test_generator_options():
 def test_generate_tracks_device_rejects_unaligned_params():
     """Frames leave the kernel as 16-byte stores: a d_params that is not 16-byte aligned is refused before anything touches
     a device (the pointers here are never dereferenced)."""
-    cfg = _product_config(cases.cfg())
+    cfg = product_config(cases.cfg())
     with pytest.raises(capi.GvtmError) as ei:
         capi.generate_tracks_device(cfg, 0x2000, 0x3000, 1, 8, 0x1004)
     assert ei.value.status == 1  # GVTM_ERR_INVALID_ARGUMENT

@@ -22,18 +22,10 @@ sys.path.insert(0, "tests")
 import gama_tts_amd as g  # noqa: E402
 from gama_tts_amd import capi  # noqa: E402
 import event_lists  # noqa: E402
-import oracle  # noqa: E402
-
-VOICES = ["male", "female", "large_child", "small_child", "baby"]
-
-
-def track_config(voice):
-    """0_male/vtm_control_model.txt with mean pitch = pitch offset (-4) + the variant's reference_glottal_pitch"""
-    tc = g.TrackConfig()
-    tc.control_period_ms, tc.macro_intonation, tc.micro_intonation, tc.intonation_drift, tc.smooth_intonation = 4, 1, 1, 1, 1
-    tc.initial_pitch, tc.drift_deviation, tc.drift_sample_rate, tc.drift_lowpass_cutoff = -20.0, 4.0, 250.0, 4.0
-    tc.mean_pitch = -4.0 + float(g.read_config_file(os.path.join(oracle.GOLDEN_DIR, "voice_%s.txt" % voice))["reference_glottal_pitch"])
-    return tc
+from device_io import events_on_device  # noqa: E402
+from track_cases import make_singable  # noqa: E402
+from voice_cases import configs, track_configs  # noqa: E402
+from voice_files import VOICES  # noqa: E402
 
 
 def timed_alternating(fns, reps, inner):
@@ -55,12 +47,6 @@ def timed_alternating(fns, reps, inner):
     return {k: float(np.median(v)) for k, v in times.items()}, {k: [min(v), max(v)] for k, v in times.items()}
 
 
-def on_device(evs):
-    offsets = np.zeros(len(evs) + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum([len(e) for e in evs])
-    return torch.from_numpy(np.concatenate(evs).view(np.uint8)).cuda(), torch.from_numpy(offsets).cuda()
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
@@ -70,17 +56,16 @@ def main():
     args = ap.parse_args()
     batch = args.batch
     stream = torch.cuda.current_stream().cuda_stream
-    tcs = [track_config(v) for v in VOICES]
-    cfgs = [g.config_from_dict(g.read_config_file(os.path.join(oracle.GOLDEN_DIR, "voice_%s.txt" % n)), 44100.0, 1, capi.PRECISION_F32) for n in VOICES]
+    tcs = track_configs()
+    cfgs = configs(precision=capi.PRECISION_F32)
     plan = g.VoicesPlan(cfgs, 250.0, 0)
     plan.set_voice_tracks(tcs)
     results = {"batch": batch, "events_per_list": 80, "reps": args.reps, "voices": VOICES}
 
     # --- track generation alone: bench_tracks.py's lists
     tables = [event_lists.random_event_table(s, n_events=80, control_period=4, max_gap_periods=12) for s in range(64)]
-    pool = [capi.events_from_table(t) for t in tables]
-    max_frames = max(capi.tracks_frame_count(tcs[0], e) for e in pool)
-    d_events, d_offsets = on_device([pool[b % 64] for b in range(batch)])
+    max_frames = max(capi.tracks_frame_count(tcs[0], capi.events_from_table(t)) for t in tables)
+    d_events, d_offsets = events_on_device([tables[b % 64] for b in range(batch)])
     ids = (np.arange(batch) % len(VOICES)).astype(np.int32)
     d_ids = torch.from_numpy(ids).cuda()
     d_one = torch.zeros(batch, dtype=torch.int32, device="cuda")
@@ -96,16 +81,11 @@ def main():
     print(json.dumps({"tracks": results["tracks"]}), flush=True)
     del d_params
 
-    # --- end to end, float: lists the models can sing (test_gpu_tracks._singable_event_table's polynomials)
+    # --- end to end, float: lists the models can sing (track_cases.singable_event_table's polynomials)
     if not args.skip_synthesis:
-        for t in tables:
-            t[:, 2] = 0.0
-            t[:, 3] = 0.0
-            t[:, 4] *= 0.1
-            t[:, 5] *= 0.5
-        pool = [capi.events_from_table(t) for t in tables]
-        lists = [pool[b % 64] for b in range(batch)]
-        d_events, d_offsets = on_device(lists)
+        singable = [make_singable(t) for t in tables]
+        lists = [singable[b % 64] for b in range(batch)]
+        d_events, d_offsets = events_on_device(lists)
         stride = plan.voices_output_capacity(max_frames)
         audio = torch.zeros((batch, stride), dtype=torch.float32, device="cuda")
         counts = torch.zeros(batch, dtype=torch.int64, device="cuda")
@@ -113,7 +93,7 @@ def main():
         per_voice = []
         for v in range(len(VOICES)):
             sel = np.nonzero(ids == v)[0]
-            ev, off = on_device([lists[b] for b in sel])
+            ev, off = events_on_device([lists[b] for b in sel])
             per_voice.append((ev, off, sel.size, torch.zeros((sel.size, stride), dtype=torch.float32, device="cuda"),
                               torch.zeros(sel.size, dtype=torch.int64, device="cuda")))
 

@@ -19,10 +19,10 @@ sys.path.insert(0, ".")
 sys.path.insert(0, "tests")
 import gama_tts_amd as g  # noqa: E402
 from gama_tts_amd import capi  # noqa: E402
-import oracle  # noqa: E402
 import tracks  # noqa: E402
+from voice_cases import configs  # noqa: E402
+from voice_files import VOICES  # noqa: E402
 
-VOICES = ["male", "female", "large_child", "small_child", "baby"]
 PRECISIONS = {"f32": capi.PRECISION_F32, "mixed": capi.PRECISION_MIXED, "f64": capi.PRECISION_F64}
 
 
@@ -50,7 +50,7 @@ def main():
     prec = PRECISIONS[args.precision]
     frames = args.frames
     stream = torch.cuda.current_stream().cuda_stream
-    cfgs = [g.config_from_dict(g.read_config_file(os.path.join(oracle.GOLDEN_DIR, "voice_%s.txt" % n)), 44100.0, 1, prec) for n in VOICES]
+    cfgs = configs(precision=prec)
     mixed_plan = g.VoicesPlan(cfgs, 250.0, 0)
     singles = [g.Plan(c, 250.0, 0) for c in cfgs]
     base = torch.from_numpy(tracks.random_tracks(64, frames, seed0=1000)).cuda()

@@ -23,8 +23,8 @@ sys.path.insert(0, "tests")
 import gama_tts_amd as g  # noqa: E402
 import golden5_voices_cases as cases  # noqa: E402
 import tracks  # noqa: E402
-
-VOICES = cases.VOICES
+from voice_cases import configs5  # noqa: E402
+from voice_files import VOICES  # noqa: E402
 
 
 def timed(fn, reps):
@@ -50,7 +50,7 @@ def main():
     args = ap.parse_args()
     frames = args.frames
     stream = torch.cuda.current_stream().cuda_stream
-    cfgs = [g.config5_from_dict(g.read_config_file(cases.voice_path(n)), cases.RATE) for n in VOICES]
+    cfgs = configs5(cases.RATE)
     mixed_plan = g.VoicesPlan(cfgs, 250.0, 0)
     reversed_plan = g.VoicesPlan(cfgs[::-1], 250.0, 0)
     singles = [g.Plan(c, 250.0, 0) for c in cfgs]

@@ -21,18 +21,15 @@ sys.path.insert(0, "tests")
 import gama_tts_amd as g  # noqa: E402
 from gama_tts_amd import capi  # noqa: E402
 import golden5_voices_cases as cases5  # noqa: E402
-import oracle  # noqa: E402
 import tracks  # noqa: E402
-
-VOICES = ["male", "female", "large_child", "small_child", "baby"]
+from voice_cases import configs, configs5  # noqa: E402
+from voice_files import VOICES  # noqa: E402
 
 
 def model_configs(model):
     if model == "model5":
-        return [g.config5_from_dict(g.read_config_file(cases5.voice_path(n)), cases5.RATE) for n in VOICES]
-    precision = capi.PRECISION_F32 if model == "f32" else capi.PRECISION_F64
-    return [g.config_from_dict(g.read_config_file(os.path.join(oracle.GOLDEN_DIR, "voice_%s.txt" % n)), 44100.0, 1, precision)
-            for n in VOICES]
+        return configs5(cases5.RATE)
+    return configs(precision=capi.PRECISION_F32 if model == "f32" else capi.PRECISION_F64)
 
 
 def push_round(stream, block, stride, audio, counts):

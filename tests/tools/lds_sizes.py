@@ -1,10 +1,10 @@
 """LDS bytes per workgroup of every kernel shape (runs without a GPU; diagnostics library): the enumeration
-tests/test_kernel_shapes.py pins, in KB."""
+of tests/kernel_shape_cases.py (pinned by tests/test_kernel_shapes.py), in KB."""
 import sys
 
 sys.path.insert(0, ".")
 sys.path.insert(0, "tests")
-import test_kernel_shapes as shapes  # noqa: E402
+import kernel_shape_cases as shapes  # noqa: E402
 
 by_plan = {}
 for (name, rows), lds in shapes.lds_bytes().items():

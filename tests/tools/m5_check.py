@@ -11,6 +11,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gama_tts_amd as g  # noqa: E402
 import oracle  # noqa: E402
 import tracks  # noqa: E402
+from parity_rules import peak_err  # noqa: E402
 
 
 def main():
@@ -29,7 +30,7 @@ def main():
             peak = np.abs(ref).max()
             first = int(np.argmax(dlt > 0)) if dlt.max() > 0 else -1
             print("%-8s utt %d n %d/%d peak %.4g maxerr/peak %.3g exact %.4f first-diff %d" % (
-                name, b, counts[b], ref.size, peak, dlt.max() / max(peak, 1e-300), float((got == ref).mean()), first), flush=True)
+                name, b, counts[b], ref.size, peak, peak_err(got, ref), float((got == ref).mean()), first), flush=True)
 
 
 if __name__ == "__main__":

@@ -9,6 +9,7 @@ sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import gama_tts_amd as g
 from gama_tts_amd import capi
 import oracle, tracks
+from parity_rules import peak_err
 
 BATCH, FRAMES = 256, 500
 params = tracks.random_tracks(BATCH, FRAMES, seed0=2000, consonant_heavy=True)
@@ -28,7 +29,7 @@ with ProcessPoolExecutor(8) as ex:
         for b in range(BATCH):
             r = refs[b]
             assert counts[b] == r.size
-            errs.append(float(np.abs(audio[b, :r.size].astype(np.float64) - r).max() / np.abs(r).max()))
+            errs.append(peak_err(audio[b, :r.size], r))
             same += int(np.array_equal(audio[b, :r.size], r))
         out[name] = {"samples_per_utterance": int(counts[0]), "counts_exact": True, "worst_peak_relative_error": max(errs),
                      "median_peak_relative_error": float(np.median(errs)), "bit_identical_utterances": same, "utterances": BATCH,

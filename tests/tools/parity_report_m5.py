@@ -11,6 +11,7 @@ sys.path.insert(0, "tests")
 import gama_tts_amd as g  # noqa: E402
 import oracle  # noqa: E402
 import tracks  # noqa: E402
+from parity_rules import peak_err  # noqa: E402
 
 BATCH, FRAMES = 256, 250
 params = tracks.random_tracks(BATCH, FRAMES, seed0=5000, consonant_heavy=True)
@@ -29,7 +30,7 @@ errs, same = [], 0
 for b in range(BATCH):
     r = refs[b]
     assert counts[b] == r.size
-    errs.append(float(np.abs(audio[b, : r.size].astype(np.float64) - r).max() / np.abs(r).max()))
+    errs.append(peak_err(audio[b, : r.size], r))
     same += int(np.array_equal(audio[b, : r.size], r))
 out["fp64_vs_model5_double"] = {
     "samples_per_utterance": int(counts[0]), "counts_exact": True, "worst_peak_relative_error": max(errs),
