@@ -205,6 +205,9 @@ def load_library(diagnostics=False):
     if hasattr(L, "gvtm_plan_create_model5_voices"):
         L.gvtm_plan_create_model5_voices.argtypes = [ctypes.POINTER(Config5), sz, dbl, i32, ctypes.POINTER(vp)]
         L.gvtm_plan_create_model5_voices.restype = i32
+    if hasattr(L, "gvtm_plan_create_model5_float"):
+        L.gvtm_plan_create_model5_float.argtypes = [ctypes.POINTER(Config5), dbl, i32, ctypes.POINTER(vp)]
+        L.gvtm_plan_create_model5_float.restype = i32
     L.gvtm_plan_set_timing.argtypes = [vp, i32]
     L.gvtm_plan_set_timing.restype = i32
     L.gvtm_plan_take_kernel_ms.argtypes = [vp, ctypes.POINTER(i32)]
@@ -391,14 +394,19 @@ def _ptr(x):
 class Plan:
     """Owns a gvtm_plan.  device=DEVICE_NONE gives a design-only plan (no GPU needed)."""
 
-    def __init__(self, config, control_rate=250.0, device=0, diagnostics=False, rows=0):
+    def __init__(self, config, control_rate=250.0, device=0, diagnostics=False, rows=0, float_model5=False):
         """diagnostics=True binds the plan to libgama_vtm_diag.so (gvtm_debug_* hooks); rows (diagnostics only) forces
-        the utterances per workgroup, i.e. the kernel shape a big batch would get."""
+        the utterances per workgroup, i.e. the kernel shape a big batch would get.  float_model5=True (a Config5 with
+        precision PRECISION_F32) makes the plan of VocalTractModel5<float,1> through gvtm_plan_create_model5_float."""
         self._lib = load_library(diagnostics)
         self.diagnostics = bool(diagnostics)
         self._h = ctypes.c_void_p()
         self.config = config
         create = self._lib.gvtm_plan_create_model5 if isinstance(config, Config5) else self._lib.gvtm_plan_create
+        if float_model5:
+            if not isinstance(config, Config5):
+                raise ValueError("float_model5 needs a Config5")
+            create = self._lib.gvtm_plan_create_model5_float
         rc = create(ctypes.byref(config), float(control_rate), int(device), ctypes.byref(self._h))
         self._check(rc)
         info = Info()

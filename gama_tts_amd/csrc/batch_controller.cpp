@@ -87,7 +87,7 @@ gvtm_config config_from_keys(const std::map<std::string, std::string>& k, int pr
 	return c;
 }
 
-gvtm5_config config5_from_keys(const std::map<std::string, std::string>& k)
+gvtm5_config config5_from_keys(const std::map<std::string, std::string>& k, int precision)
 {
 	gvtm5_config c{};
 	auto flag = [&](const char* key) {
@@ -120,7 +120,8 @@ gvtm5_config config5_from_keys(const std::map<std::string, std::string>& k)
 	c.max_glottal_loss = num(k, "max_glottal_loss");
 	c.glottal_lowpass_cutoff = num(k, "glottal_lowpass_cutoff");
 	if (c.constant_radius_mouth_impedance) c.mouth_impedance_radius = num(k, "mouth_impedance_radius");
-	c.precision = GVTM_PRECISION_F64;
+	// the factory's model 5 is the double class; `-f` asks for VocalTractModel5<float,1> (gvtm_plan_create_model5_float)
+	c.precision = precision == GVTM_PRECISION_F32 ? GVTM_PRECISION_F32 : GVTM_PRECISION_F64;
 	return c;
 }
 
@@ -131,7 +132,7 @@ void BatchController::init(const std::map<std::string, std::string>& keys, unsig
 	const bool model5 = keys.count("model") && static_cast<int>(num(keys, "model")) == 5; // VocalTractModel.cpp:47-48
 	gvtm5_config config5{};
 	if (model5) {
-		config5 = config5_from_keys(keys);
+		config5 = config5_from_keys(keys, precision);
 		config_ = gvtm_config{};
 		config_.output_rate = config5.output_rate;
 	} else {
@@ -140,7 +141,9 @@ void BatchController::init(const std::map<std::string, std::string>& keys, unsig
 	const double control_rate = 1000.0 / control_period_ms;
 	for (int device : devices) {
 		gvtm_plan* plan = nullptr;
-		const int rc = model5 ? gvtm_plan_create_model5(&config5, control_rate, device, &plan) : gvtm_plan_create(&config_, control_rate, device, &plan);
+		const int rc = !model5 ? gvtm_plan_create(&config_, control_rate, device, &plan)
+		               : (config5.precision == GVTM_PRECISION_F32 ? gvtm_plan_create_model5_float(&config5, control_rate, device, &plan)
+		                                                          : gvtm_plan_create_model5(&config5, control_rate, device, &plan));
 		if (rc != GVTM_OK) {
 			const std::string why = gvtm_last_error();
 			for (gvtm_plan* p : plans_) gvtm_plan_destroy(p);

@@ -23,8 +23,9 @@ std::map<std::string, std::string> read_key_value_file(const std::string& path);
 // 0, 2 -> SectionDelay 1; 3 -> SectionDelay 3; 4 -> the 30+18-section tube (VocalTractModel.cpp:40-49);
 // 1 -> model 0 in float; 5 is handled by config5_from_keys; others are refused.
 gvtm_config config_from_keys(const std::map<std::string, std::string>& keys, int precision);
-// the keys of a model-5 voice (VocalTractModel5::loadConfiguration, vtm/VocalTractModel5.h:375-421) -> gvtm5_config
-gvtm5_config config5_from_keys(const std::map<std::string, std::string>& keys);
+// the keys of a model-5 voice (VocalTractModel5::loadConfiguration, vtm/VocalTractModel5.h:375-421) -> gvtm5_config;
+// precision GVTM_PRECISION_F32 (the CLI's -f) asks for VocalTractModel5<float,1>, anything else for the factory's double class
+gvtm5_config config5_from_keys(const std::map<std::string, std::string>& keys, int precision = GVTM_PRECISION_F64);
 
 class BatchController {
 public:

@@ -40,7 +40,7 @@ int main(int argc, char** argv)
 			if (devices.empty()) { std::cerr << "no device" << std::endl; return EXIT_FAILURE; }
 		}
 		else if (std::strcmp(argv[i], "-m") == 0) precision = GVTM_PRECISION_MIXED;
-		else if (std::strcmp(argv[i], "-f") == 0) precision = GVTM_PRECISION_F32; // reference model 1 (float) semantics
+		else if (std::strcmp(argv[i], "-f") == 0) precision = GVTM_PRECISION_F32; // reference model 1 (float) semantics; a model-5 voice: VocalTractModel5<float,1>
 		else { std::cerr << "unknown option " << argv[i] << std::endl; return EXIT_FAILURE; }
 	}
 	if (argc - i < 3) {

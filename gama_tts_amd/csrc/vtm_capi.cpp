@@ -263,8 +263,13 @@ int upload_tables5(gvtm_plan* plan)
 	}
 	const gvtm::Design& dg = plan->designs[0];
 	hipError_t e;
-	if ((e = upload(plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
-	if ((e = upload(plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
+	if (dg.f32) { // (the float class: its converter's tables as designed in float)
+		if ((e = upload(plan->d_src_h, dg.src_h_f)) != hipSuccess) return fail_hip(e, "upload src_h");
+		if ((e = upload(plan->d_src_dh, dg.src_dh_f)) != hipSuccess) return fail_hip(e, "upload src_dh");
+	} else {
+		if ((e = upload(plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
+		if ((e = upload(plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
+	}
 	if ((e = upload(plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
 	if ((e = upload(plan->d_consts5, consts5)) != hipSuccess) return fail_hip(e, "upload model 5 constants");
 	return GVTM_OK;
@@ -418,6 +423,12 @@ int gvtm_plan_create_model5_voices(const gvtm5_config* configs, size_t n_voices,
 	return create_plan(configs, n_voices, control_rate, device, plan_out, "output_rate and precision", differs, gvtm::design_plan5, upload_tables5);
 }
 
+int gvtm_plan_create_model5_float(const gvtm5_config* config, double control_rate, int device, gvtm_plan** plan_out)
+{
+	auto differs = [](const gvtm5_config&, const gvtm5_config&) { return false; }; // (one voice)
+	return create_plan(config, 1, control_rate, device, plan_out, "", differs, gvtm::design_plan5_float, upload_tables5);
+}
+
 void gvtm_plan_destroy(gvtm_plan* plan)
 {
 	if (!plan) return;
@@ -541,7 +552,7 @@ int gvtm_debug_dpp_selftest(gvtm_plan* plan, int* out)
 
 /* Test hook: the short elementary functions of csrc/vtm_math.hpp evaluated on the host
  * (kind 0 = 2^x, 1 = 10^x, 2 = cos, 3 = tan; 4 = powf(2, x), 5 = powf(10, x), 6 = cosf, 7 = tanf of the
- * all-float path, arguments and results carried as doubles). */
+ * all-float path, 8 = sinf of the float model 5's sine waveform, arguments and results carried as doubles). */
 int gvtm_debug_short_math(int kind, const double* x, size_t n, double* out)
 {
 	if (!x || !out) return GVTM_ERR_INVALID_ARGUMENT;
@@ -555,17 +566,18 @@ int gvtm_debug_short_math(int kind, const double* x, size_t n, double* out)
 		case 5: out[i] = gvtm::vmath::powf_base10(static_cast<float>(x[i])); break;
 		case 6: out[i] = gvtm::vmath::cosf_glibc(static_cast<float>(x[i])); break;
 		case 7: out[i] = gvtm::vmath::tanf_glibc(static_cast<float>(x[i])); break;
+		case 8: out[i] = gvtm::vmath::sinf_glibc(static_cast<float>(x[i])); break;
 		default: return GVTM_ERR_INVALID_ARGUMENT;
 		}
 	}
 	return GVTM_OK;
 }
 
-/* Test hook: Util::frequency / Util::amplitude60dB / tan / cos of the all-float path evaluated by a
- * kernel on the plan's device (kind 0..3), host arrays in and out. */
+/* Test hook: Util::frequency / Util::amplitude60dB / tan / cos of the all-float path (kind 0..3), its scaling-free
+ * division (4) and the float model 5's sin (5) evaluated by a kernel on the plan's device, host arrays in and out. */
 int gvtm_debug_device_float_math(gvtm_plan* plan, int kind, const float* x, size_t n, float* out)
 {
-	if (!plan || !x || !out || kind < 0 || kind > 4) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (!plan || !x || !out || kind < 0 || kind > 5) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
@@ -872,6 +884,9 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 		if (rc != GVTM_OK) return rc;
 	}
 	const bool model5 = plan->designs[0].model5;
+	if (r.voices && model5 && plan->designs[0].f32) {
+		return fail(GVTM_ERR_UNSUPPORTED, "the float model 5 has no launch of several voices (gvtm_plan_create_model5_float: one voice per plan)");
+	}
 	const gvtm::LaunchShape shape = plan->launch_shape(r.batch, r.rows, r.voices, r.sl ? r.sl->xr : 0);
 	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
 	const int rows = shape.rows;
@@ -901,7 +916,7 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 		if (rc != GVTM_OK) return rc;
 	}
 	return timed_launch(plan, stream, r.voices ? "vtm_synth_kernel launch (voices)" : "vtm_synth_kernel launch", [&] {
-		return model5 ? gvtm::launch_synth5(args, work, rows, stream) : gvtm::launch_synth(args, work, plan->precision, rows, stream);
+		return model5 ? gvtm::launch_synth5(args, work, plan->precision, rows, shape.variant, stream) : gvtm::launch_synth(args, work, plan->precision, rows, stream);
 	});
 }
 
@@ -1175,7 +1190,9 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 
 	// the shape of the whole batch (every slice is launched in it), and how many utterances fill the machine once in it
 	// (the rows the batch size picks: a launch still gives way to fewer where the LDS does not hold them)
-	const int rows_all = plan->launch_shape(batch, 0, false, 0, false).rows;
+	// (the float model 5's second shape -- one utterance per workgroup, two workgroups per compute unit -- goes by "rows 2")
+	const gvtm::LaunchShape shape_all = plan->launch_shape(batch, 0, false, 0, false);
+	const int rows_all = shape_all.variant == 1 ? 2 : shape_all.rows;
 	const size_t machine = static_cast<size_t>(rows_all) * static_cast<size_t>(plan->compute_units > 0 ? plan->compute_units : 256);
 	const size_t slice = batch >= 2 * machine ? machine : batch;
 	const size_t n_slices = (batch + slice - 1) / slice;
@@ -1351,7 +1368,9 @@ int stream_upload_fresh_state(gvtm_stream* s)
 			// longest falling phase, the noise source starts from its seed, everything else is zero
 			const gvtm::Model5Constants& k5 = s->plan->designs[voice_of(s, b)].k5;
 			double sc[gvtm::kStream5Scalars] = {};
-			sc[gvtm::kS5Scan + 1] = k5.rb_t1 + k5.rb_tn_max;
+			// (the float class adds in float)
+			sc[gvtm::kS5Scan + 1] = s->plan->designs[0].f32 ? static_cast<double>(static_cast<float>(k5.rb_t1) + static_cast<float>(k5.rb_tn_max))
+			                                                : k5.rb_t1 + k5.rb_tn_max;
 			sc[gvtm::kS5Scan + 2] = 0.7892347;
 			std::memcpy(init.data() + b * s->state_stride + gvtm::Stream5Layout::scalars(), sc, sizeof(sc));
 		}

@@ -101,6 +101,8 @@ void design_noise_table(size_t n, bool as_float, void* out);
 std::string design_plan(const gvtm_config& cfg, double control_rate, Design& out);
 
 std::string design_plan5(const gvtm5_config& cfg, double control_rate, Design& out);
+// VocalTractModel5<float,1>: cfg.precision must be GVTM_PRECISION_F32; out.f32 is set, the constants are floats widened
+std::string design_plan5_float(const gvtm5_config& cfg, double control_rate, Design& out);
 
 // PoleZeroRadiationImpedance::update (vtm/PoleZeroRadiationImpedance.h:139-177): radius in metres -> cT1..3, cR1..3
 void radiation_impedance(double radius, double period, double out[6]);

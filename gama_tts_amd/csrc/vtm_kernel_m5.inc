@@ -1,8 +1,9 @@
 // Reference model 5 (VocalTractModel5<double,1>, vtm/VocalTractModel5.h) on the device.
 // Included inside namespace gvtm, after vtm_kernel_v2.inc (whose wave-wide DPP helpers, Extent and voice_row it shares),
-// by two translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
-// (kVoices5Flag) in a code object of its own.  Besides the kernel, the file defines what both launch it with: the
-// description of its two shapes (m5_shape, kM5Ring), before the kernel, and launch_synth5_shape, at the end.
+// by three translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
+// (kVoices5Flag) and vtm_kernels_m5f.hip the float class, VocalTractModel5<float,1> (kFloat5Flag), each in a code object of
+// its own.  Besides the kernel, the file defines what they launch it with: the description of its shapes (m5_shape,
+// m5_float_shape, kM5Ring), before the kernel, and launch_synth5_shape / launch_synth5_float_shape, at the end.
 //
 // Same organisation as generation 2: a workgroup owns U utterances (1 or 2; the tube has 30 + 21 = 51 sections, one
 // per lane of a wavefront, so every utterance has a tube wavefront of its own, while the scan, filter and interpolation
@@ -40,11 +41,20 @@
 // helper wavefronts.  Two utterances per workgroup (batches beyond one workgroup per compute unit): two tube wavefronts,
 // chunk of 24 steps (2 x 24 items per per-step pass; what LDS holds with two 62-entry tube records per step), five helpers.
 // Wavefronts: I, S and F, a tube wavefront per utterance, the helpers.
+// The float class (VocalTractModel5<float,1>, kFloat5Flag below) has one utterance per workgroup and two shapes, measured
+// against each other in DESIGN.md 4b (profiles/r08_bench_model5_float.json).  Variant 0, chunk 60 with three helpers, is
+// the double shape with every record halved (84 992 B of LDS): one workgroup per compute unit, the longest chunk.
+// Variant 1, chunk 56 with three helpers, is the longest chunk whose workgroup stays at or below 80 KB (80 800 B), so
+// that two workgroups share a compute unit.  synth_launch_shape picks between them by batch size.
 struct M5Shape { int rows, chunk, helpers, waves; };
 constexpr int m5_waves(int rows, int helpers) { return 3 + rows + helpers; }
 constexpr M5Shape m5_shape(int rows)
 {
 	return rows == 2 ? M5Shape{2, 24, 5, m5_waves(2, 5)} : M5Shape{1, 60, 3, m5_waves(1, 3)};
+}
+constexpr M5Shape m5_float_shape(int variant)
+{
+	return variant == 1 ? M5Shape{1, 56, 3, m5_waves(1, 3)} : M5Shape{1, 60, 3, m5_waves(1, 3)};
 }
 constexpr int kM5Ring = kSrcRing; // the reference's BUFFER_SIZE: see the flush-overrun epilogue
 
@@ -68,7 +78,7 @@ constexpr int kRfr = 4; // A1b record: frication amplitude, left share, right sh
 constexpr int kMouth = 29, kNose = 50, kNasalFirst = 30, kThreeLeft = 11, kThreeRight = 12;
 constexpr int kYr = 512; // ring of converted samples waiting for the difference filter
 
-template <int C, int XR, int U = 1>
+template <int C, int XR, int U = 1, typename R = double>
 struct Offsets {
 	size_t kc, k5, ext, kb, src, prm, rd, rm, rst, rn, val, u, pl, rfr, rb0, ra12, inp, fnm, ub, bp, mg, ru, side, ox, rmo, yv, oo, carry, x, y, peak, ticket, diag, dump, total;
 	__host__ __device__ constexpr Offsets()
@@ -81,12 +91,12 @@ struct Offsets {
 			off += (bytes + 15) & ~size_t(15);
 			return at;
 		};
-		constexpr size_t D = sizeof(double);
+		constexpr size_t D = sizeof(R);
 		kc = take(sizeof(DeviceConstants));
 		k5 = take(sizeof(Model5Constants));
 		ext = take(sizeof(Extent) * U);
 		kb = take(sizeof(unsigned long long) * 4 * 2 * U); // output sample range of a chunk, (c & 3)
-		src = take(sizeof(double) * (kSrcFilterLength + 1)); // h only, delta formed on the fly (26 KB for the tube records)
+		src = take(sizeof(R) * (kSrcFilterLength + 1)); // h only, delta formed on the fly (26 KB for the tube records)
 		prm = take(U * (sizeof(float) * 2 * C * 16));
 		rd = take(U * (D * 2 * (C + 4) * 2));   // {dt, t2 target}                    A1a -> S      (c & 1)
 		rm = take(U * (D * 5 * C * 2));         // {glottal, aspiration amplitude}    A1a -> M      (c % 5)
@@ -130,12 +140,31 @@ struct Offsets {
 // stream state) follow the row map.  As in vtm_kernel_v2.inc (kVoicesFlag), each voice-dependent expression is a conditional on the
 // constant VOICES, so the single-voice kernels compile to the code they had before the flag existed.
 constexpr int kVoices5Flag = 4;
+// VocalTractModel5<float,1> (gvtm_plan_create_model5_float; instantiated by vtm_kernels_m5f.hip alone, which compiles with
+// FMA contraction off): the flag kFloat5Flag in the same argument makes R, the type of every LDS record, every recurrence
+// and the tube, float instead of double.  The constants arrive as floats widened in the double fields of DeviceConstants /
+// Model5Constants and are narrowed where they are used (R(k5.x): exact); the resampler's table is the float design's; a
+// stream's state keeps its double slots (Stream5Layout), a float stored widened being exact; the noise generator's seed
+// stays double (NoiseSource.h:41-54).  With R = double every R(...) below is the identity, so the double kernels are
+// the code they were.
+constexpr int kFloat5Flag = 8;
+__device__ __forceinline__ double sin_m5(double t) { return sin(t); }
+__device__ __forceinline__ float sin_m5(float t) { return vmath::sinf_glibc(t); } // std::sin(float), RosenbergBGlottalSource.h:139
+
+// wavefronts per SIMD a shape is compiled for: the float class's 80 KB shape must leave room for a second workgroup (7 + 7
+// wavefronts: four on a SIMD, 128 registers each); every other shape gets what its workgroup size implies (a request
+// below that is no request)
+constexpr int m5_waves_per_simd(int chunk, int u_flags) { return (u_flags & kFloat5Flag) != 0 && chunk == m5_float_shape(1).chunk ? 4 : 1; }
 
 template <int C, int NH, int XR, int U_FLAGS>
-__global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_kernel(const SynthArgs a)
+__global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C, U_FLAGS)) void vtm5_synth_kernel(const SynthArgs a)
 {
 	constexpr int U = U_FLAGS & 3;
 	constexpr bool VOICES = (U_FLAGS & kVoices5Flag) != 0;
+	constexpr bool FLOAT = (U_FLAGS & kFloat5Flag) != 0;
+	using R = std::conditional_t<FLOAT, float, double>;
+	using R2 = typename Pair<R>::type;
+	static_assert(!FLOAT || (U == 1 && !VOICES), "the float class has the one-utterance, one-voice shape only");
 	static_assert(!VOICES || U == 1, "the voice variant has the one-utterance shape only");
 	int voice = 0;
 	if constexpr (VOICES) {
@@ -153,42 +182,42 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 	              kN_ox = 2 * C * 2, kN_rmo = 4 * C * 3, kN_yv = 2 * (C + 2) * 4, kN_oo = 2 * C * 2, kN_carry = 4;
 
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-	constexpr Offsets<C, XR, U> so;
+	constexpr Offsets<C, XR, U, R> so;
 	DeviceConstants* const s_kc = reinterpret_cast<DeviceConstants*>(smem_raw + so.kc);
 	Model5Constants* const s_k5 = reinterpret_cast<Model5Constants*>(smem_raw + so.k5);
 	Extent* const s_ext = reinterpret_cast<Extent*>(smem_raw + so.ext);
 	unsigned long long* const s_kb = reinterpret_cast<unsigned long long*>(smem_raw + so.kb);
-	double* const s_src = reinterpret_cast<double*>(smem_raw + so.src);
+	R* const s_src = reinterpret_cast<R*>(smem_raw + so.src);
 	int* const s_side = reinterpret_cast<int*>(smem_raw + so.side);
 	float* const s_prm = reinterpret_cast<float*>(smem_raw + so.prm);
-	auto dptr = [&](size_t off) { return reinterpret_cast<double*>(smem_raw + off); };
-	double* const s_rd = dptr(so.rd);
-	double* const s_rm = dptr(so.rm);
-	double* const s_rst = dptr(so.rst);
-	double* const s_rn = dptr(so.rn);
-	double* const s_val = dptr(so.val);
-	double* const s_u = dptr(so.u);
-	double* const s_pl = dptr(so.pl);
-	double* const s_rfr = dptr(so.rfr);
-	double* const s_rb0 = dptr(so.rb0);
-	double* const s_ra12 = dptr(so.ra12);
-	double* const s_inp = dptr(so.inp);
-	double* const s_fnm = dptr(so.fnm);
-	double* const s_ub = dptr(so.ub);
-	double* const s_bp = dptr(so.bp);
-	double* const s_mg = dptr(so.mg);
-	double* const s_ru = dptr(so.ru);
-	double* const s_ox = dptr(so.ox);
-	double* const s_rmo = dptr(so.rmo);
-	double* const s_yv = dptr(so.yv);
-	double* const s_oo = dptr(so.oo);
-	double* const s_carry = dptr(so.carry);
-	double* const s_x = dptr(so.x);
-	double* const s_x_all = s_x;
+	auto dptr = [&](size_t off) { return reinterpret_cast<R*>(smem_raw + off); };
+	R* const s_rd = dptr(so.rd);
+	R* const s_rm = dptr(so.rm);
+	R* const s_rst = dptr(so.rst);
+	R* const s_rn = dptr(so.rn);
+	R* const s_val = dptr(so.val);
+	R* const s_u = dptr(so.u);
+	R* const s_pl = dptr(so.pl);
+	R* const s_rfr = dptr(so.rfr);
+	R* const s_rb0 = dptr(so.rb0);
+	R* const s_ra12 = dptr(so.ra12);
+	R* const s_inp = dptr(so.inp);
+	R* const s_fnm = dptr(so.fnm);
+	R* const s_ub = dptr(so.ub);
+	R* const s_bp = dptr(so.bp);
+	R* const s_mg = dptr(so.mg);
+	R* const s_ru = dptr(so.ru);
+	R* const s_ox = dptr(so.ox);
+	R* const s_rmo = dptr(so.rmo);
+	R* const s_yv = dptr(so.yv);
+	R* const s_oo = dptr(so.oo);
+	R* const s_carry = dptr(so.carry);
+	R* const s_x = dptr(so.x);
+	R* const s_x_all = s_x;
 	float* const s_y = reinterpret_cast<float*>(smem_raw + so.y);
 	unsigned* const s_peak = reinterpret_cast<unsigned*>(smem_raw + so.peak);
 	unsigned* const s_ticket = reinterpret_cast<unsigned*>(smem_raw + so.ticket);
-	double* const s_dump = dptr(so.dump);
+	R* const s_dump = dptr(so.dump);
 	unsigned long long* const s_diag = reinterpret_cast<unsigned long long*>(smem_raw + so.diag);
 
 	const int tid = threadIdx.x;
@@ -220,11 +249,11 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 		for (int i = tid; i < static_cast<int>(sizeof(Model5Constants) / sizeof(int)); i += kThreads) dst5[i] = src5[i];
 	}
 	for (int i = tid; i <= kSrcFilterLength; i += kThreads) {
-		s_src[i] = i < kSrcFilterLength ? static_cast<const double*>(a.src_h)[i] : 0.0; // deltaH_[last] = 0 - h_[last] (SampleRateConverter.h:254)
+		s_src[i] = i < kSrcFilterLength ? static_cast<const R*>(a.src_h)[i] : R(0.0); // deltaH_[last] = 0 - h_[last] (SampleRateConverter.h:254)
 	}
-	for (int i = tid; i < U * kN_ru; i += kThreads) s_ru[i] = 0.0;
+	for (int i = tid; i < U * kN_ru; i += kThreads) s_ru[i] = R(0.0);
 	for (int i = tid; i < U * kN_side; i += kThreads) s_side[i] = kAddNone;
-	for (int i = tid; i < U * XR; i += kThreads) s_x[i] = 0.0;
+	for (int i = tid; i < U * XR; i += kThreads) s_x[i] = R(0.0);
 	for (int i = tid; i < U * kYr; i += kThreads) s_y[i] = 0.0f;
 	__syncthreads();
 	const DeviceConstants& k = *s_kc;
@@ -268,17 +297,17 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 			if (GVTM_M5_UTT(u, group * U + u) >= a.batch) break;
 			const unsigned char* sb = a.stream + GVTM_M5_UTT(u, (group * U + u)) * a.stream_stride;
 			const double* ring = reinterpret_cast<const double*>(sb + Stream5Layout::ring());
-			for (int i = tid; i < XR; i += kThreads) s_x[u * XR + i] = ring[i];
+			for (int i = tid; i < XR; i += kThreads) s_x[u * XR + i] = static_cast<R>(ring[i]);
 			const float* yr = reinterpret_cast<const float*>(sb + Stream5Layout::yring());
 			for (int i = tid; i < kYr; i += kThreads) s_y[u * kYr + i] = yr[i];
 			if (tid == 0) {
 				const double* sc = reinterpret_cast<const double*>(sb + Stream5Layout::scalars());
 				// (chunk 0 looks for its predecessor's last values in slot 1, where chunk -1 would have left them)
-				s_val[u * kN_val + C + C - 1] = sc[kS5ValLast];
-				s_fnm[u * kN_fnm + C + C - 2] = sc[kS5FnmLast];
-				s_fnm[u * kN_fnm + C + C - 1] = sc[kS5FnmLast + 1];
-				s_carry[u * kN_carry + 2] = sc[kS5Carry];
-				s_carry[u * kN_carry + 3] = sc[kS5Carry + 1];
+				s_val[u * kN_val + C + C - 1] = static_cast<R>(sc[kS5ValLast]);
+				s_fnm[u * kN_fnm + C + C - 2] = static_cast<R>(sc[kS5FnmLast]);
+				s_fnm[u * kN_fnm + C + C - 1] = static_cast<R>(sc[kS5FnmLast + 1]);
+				s_carry[u * kN_carry + 2] = static_cast<R>(sc[kS5Carry]);
+				s_carry[u * kN_carry + 3] = static_cast<R>(sc[kS5Carry + 1]);
 			}
 		}
 		__syncthreads();
@@ -312,16 +341,16 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 		const int u = item_u, s = item_s;
 		if (u >= U || s >= valid_in(u, c)) return;
 		const float* pv = s_prm + u * kN_prm + (static_cast<size_t>(c & 1) * C + s) * 16;
-		const double pitch = pv[0], gv = pv[1], av = pv[2];
-		const double f0 = frequency_dev(pitch);
-		const double ga = amplitude_60db_dev(gv);
-		double* rd = s_rd + u * kN_rd + (static_cast<size_t>(c & 1) * (C + 4) + s) * 2;
-		rd[0] = f0 / k5.sample_rate;
+		const R pitch = pv[0], gv = pv[1], av = pv[2];
+		const R f0 = frequency_dev(pitch);
+		const R ga = amplitude_60db_dev(gv);
+		R* rd = s_rd + u * kN_rd + (static_cast<size_t>(c & 1) * (C + 4) + s) * 2;
+		rd[0] = f0 / R(k5.sample_rate);
 		// the amplitude-dependent end of the falling phase: a pure function of the amplitude (setup() skips the
 		// assignment only when it would store the same value)
-		rd[1] = (k5.rb_tn_min == k5.rb_tn_max) ? k5.rb_t1 + k5.rb_tn_max
-		                                       : k5.rb_t1 + k5.rb_tn_max - ga * (k5.rb_tn_max - k5.rb_tn_min);
-		double* rm = s_rm + u * kN_rm + (static_cast<size_t>(c % 5) * C + s) * 2;
+		rd[1] = (R(k5.rb_tn_min) == R(k5.rb_tn_max)) ? R(k5.rb_t1) + R(k5.rb_tn_max)
+		                                       : R(k5.rb_t1) + R(k5.rb_tn_max) - ga * (R(k5.rb_tn_max) - R(k5.rb_tn_min));
+		R* rm = s_rm + u * kN_rm + (static_cast<size_t>(c % 5) * C + s) * 2;
 		rm[0] = ga;
 		rm[1] = amplitude_60db_dev(av);
 	};
@@ -331,22 +360,22 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 		const int u = item_u, s = item_s;
 		if (u >= U || s >= valid_in(u, c)) return;
 		const float* pv = s_prm + u * kN_prm + (static_cast<size_t>(c & 1) * C + s) * 16;
-		const double fvol = pv[3], fpos = pv[4], fcf = pv[5], fbw = pv[6];
-		double* r = s_rfr + u * kN_rfr + (static_cast<size_t>(c & 3) * C + s) * kRfr;
-		const double offset = (27 - 5) * (fpos / 7.0);
+		const R fvol = pv[3], fpos = pv[4], fcf = pv[5], fbw = pv[6];
+		R* r = s_rfr + u * kN_rfr + (static_cast<size_t>(c & 3) * C + s) * kRfr;
+		const R offset = (27 - 5) * (fpos / R(7.0));
 		const int oi = static_cast<int>(offset);
-		const double right = offset - oi;
+		const R right = offset - oi;
 		r[0] = amplitude_60db_dev(fvol);
-		r[1] = 1.0 - right;
-		r[2] = (5 + oi < 27) ? right : 0.0; // the right neighbour only gets its share below S28 (:723-725)
-		r[3] = static_cast<double>(5 + oi);
-		const double pi = 3.14159265358979323846;
-		const double tan_v = tan_dev(pi * fbw * k.bp_T);
-		const double cos_v = cos_dev(2.0 * pi * fcf * k.bp_T);
-		const double a2 = (1.0 - tan_v) / (1.0 + tan_v);
-		s_rb0[u * kN_rb0 + (c % 3) * C + s] = 0.5 - 0.5 * a2;
-		double* a12 = s_ra12 + u * kN_ra12 + (static_cast<size_t>(c % 3) * (C + 4) + s) * 2;
-		a12[0] = -(1.0 + a2) * cos_v;
+		r[1] = R(1.0) - right;
+		r[2] = (5 + oi < 27) ? right : R(0.0); // the right neighbour only gets its share below S28 (:723-725)
+		r[3] = static_cast<R>(5 + oi);
+		const R pi = R(3.14159265358979323846);
+		const R tan_v = tan_dev(pi * fbw * R(k.bp_T));
+		const R cos_v = cos_dev(R(2.0) * pi * fcf * R(k.bp_T));
+		const R a2 = (R(1.0) - tan_v) / (R(1.0) + tan_v);
+		s_rb0[u * kN_rb0 + (c % 3) * C + s] = R(0.5) - R(0.5) * a2;
+		R* a12 = s_ra12 + u * kN_ra12 + (static_cast<size_t>(c % 3) * (C + 4) + s) * 2;
+		a12[0] = -(R(1.0) + a2) * cos_v;
 		a12[1] = a2;
 	};
 
@@ -355,68 +384,68 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 		const int u = item_u, s = item_s;
 		if (u >= U || s >= valid_in(u, c)) return;
 		const float* cur = s_prm + u * kN_prm + (static_cast<size_t>(c & 1) * C + s) * 16 + 7;
-		double r2[8];
-		double r8 = 0.0;
+		R r2[8];
+		R r8 = R(0.0);
 #pragma unroll
 		for (int q = 0; q < 8; ++q) {
-			double r = static_cast<double>(cur[q]) * k.radius_coef[q];
-			r = r > 0.01 ? r : 0.01; // GS_VTM5_MIN_RADIUS
+			R r = static_cast<R>(cur[q]) * R(k.radius_coef[q]);
+			r = r > R(0.01) ? r : R(0.01); // GS_VTM5_MIN_RADIUS
 			r2[q] = r * r;
 			r8 = r;
 		}
-		const double velum = cur[8];
-		const double v2 = velum * velum;
-		double* rk = s_ru + u * kN_ru + (static_cast<size_t>(c & 1) * (C + 2) + s) * kRu;
+		const R velum = cur[8];
+		const R v2 = velum * velum;
+		R* rk = s_ru + u * kN_ru + (static_cast<size_t>(c & 1) * (C + 2) + s) * kRu;
 #pragma unroll
 		for (int q = 0; q < 7; ++q) rk[kRkJ + q] = (r2[q] - r2[q + 1]) / (r2[q] + r2[q + 1]);
-		rk[kRkNk] = (v2 - k5.nasal_r1_sq) / (v2 + k5.nasal_r1_sq);
+		rk[kRkNk] = (v2 - R(k5.nasal_r1_sq)) / (v2 + R(k5.nasal_r1_sq));
 		// Junction3::configure(r4, r4, velum): left and right coefficients coincide.  The lanes that take the
 		// junction's outputs through their LEFT link read the negated value (their formula subtracts).
-		const double cc = 1.0 / (r2[3] + r2[3] + v2);
-		const double vl = cc * ((r2[3] - r2[3]) - v2);
-		const double vu = cc * ((v2 - r2[3]) - r2[3]);
+		const R cc = R(1.0) / (r2[3] + r2[3] + v2);
+		const R vl = cc * ((r2[3] - r2[3]) - v2);
+		const R vu = cc * ((v2 - r2[3]) - r2[3]);
 		rk[kRkVl] = vl;
 		rk[kRkNVl] = -vl;
 		rk[kRkNVu] = -vu;
 		// the values that never change, replicated (see kRu)
 #pragma unroll
-		for (int q = 0; q < 5; ++q) rk[kRuNasal + q] = k5.nasal_k[q + 1];
+		for (int q = 0; q < 5; ++q) rk[kRuNasal + q] = R(k5.nasal_k[q + 1]);
 		// the tube only needs the reflection side of an impedance: cR1 (= cT1), cR2, cR3 (k5.*_c: cT1, cT2, cT3, cR1, cR2, cR3)
-		rk[kRuNose + 0] = k5.nose_c[3];
-		rk[kRuNose + 1] = k5.nose_c[4];
-		rk[kRuNose + 2] = k5.nose_c[5];
-		rk[kRuZero] = 0.0;
-		double* rmo = s_rmo + u * kN_rmo + (static_cast<size_t>(c & 3) * C + s) * 3; // the transmission side, for Y and Fo
+		rk[kRuNose + 0] = R(k5.nose_c[3]);
+		rk[kRuNose + 1] = R(k5.nose_c[4]);
+		rk[kRuNose + 2] = R(k5.nose_c[5]);
+		rk[kRuZero] = R(0.0);
+		R* rmo = s_rmo + u * kN_rmo + (static_cast<size_t>(c & 3) * C + s) * 3; // the transmission side, for Y and Fo
 		if (k5.constant_mouth) {
-			rk[kRkMouth + 0] = k5.mouth_c[3];
-			rk[kRkMouth + 1] = k5.mouth_c[4];
-			rk[kRkMouth + 2] = k5.mouth_c[5];
-			rmo[0] = k5.mouth_c[0];
-			rmo[1] = k5.mouth_c[1];
-			rmo[2] = k5.mouth_c[2];
+			rk[kRkMouth + 0] = R(k5.mouth_c[3]);
+			rk[kRkMouth + 1] = R(k5.mouth_c[4]);
+			rk[kRkMouth + 2] = R(k5.mouth_c[5]);
+			rmo[0] = R(k5.mouth_c[0]);
+			rmo[1] = R(k5.mouth_c[1]);
+			rmo[2] = R(k5.mouth_c[2]);
 		}
 		if (!k5.constant_mouth) {
 			// PoleZeroRadiationImpedance::update (vtm/PoleZeroRadiationImpedance.h:139-177), radius in metres
-			const double radius = r8 * static_cast<double>(1.0e-2f);
-			const double transition = 0.5e-2;
-			const double rr = radius < transition ? transition : radius;
-			const double trans_freq = 62.3371 / rr + 320.204;
-			const double cos_wt = cos_dev((2.0 * 3.14159265358979323846) * trans_freq * k5.period);
-			const double qa = 2.0 * cos_wt;
-			const double qb = -2.0 * (cos_wt + 1.0);
-			const double qc = cos_wt + 1.0;
-			const double delta = qb * qb - 4.0 * qa * qc;
-			double aa = (-qb - sqrt(delta)) / (2.0 * qa);
-			const double bb = 2.0 * aa - 1.0;
-			if (radius < transition) aa *= 40391.2 * (radius * radius);
-			const double coef = 1.0 / (aa + 1.0);
-			const double c1 = (aa + bb) * coef;
+			const R radius = r8 * static_cast<R>(1.0e-2f);
+			const R transition = R(0.5e-2);
+			const R rr = radius < transition ? transition : radius;
+			const R trans_freq = R(62.3371) / rr + R(320.204);
+			const R cos_wt = cos_dev(R(2.0 * 3.14159265358979323846) * trans_freq * R(k5.period));
+			const R qa = R(2.0) * cos_wt;
+			const R qb = -R(2.0) * (cos_wt + R(1.0));
+			const R qc = cos_wt + R(1.0);
+			const R delta = qb * qb - R(4.0) * qa * qc;
+			R aa = (-qb - sqrt(delta)) / (R(2.0) * qa);
+			const R bb = R(2.0) * aa - R(1.0);
+			if (radius < transition) aa *= R(40391.2) * (radius * radius);
+			const R coef = R(1.0) / (aa + R(1.0));
+			const R c1 = (aa + bb) * coef;
 			rk[kRkMouth + 0] = c1;                // cR1 = cT1
-			rk[kRkMouth + 1] = (aa - 1.0) * coef; // cR2
+			rk[kRkMouth + 1] = (aa - R(1.0)) * coef; // cR2
 			rk[kRkMouth + 2] = (bb - aa) * coef;  // cR3
 			rmo[0] = c1;
-			rmo[1] = 2.0 * coef;                  // cT2
-			rmo[2] = -2.0 * bb * coef;            // cT3
+			rmo[1] = R(2.0) * coef;                  // cT2
+			rmo[2] = -R(2.0) * bb * coef;            // cT3
 		}
 	};
 
@@ -425,26 +454,26 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 	auto stage_b = [&](int c) {
 		const int u = item_u < U ? item_u : U - 1, s = item_s;
 		const int valid = item_u < U ? valid_in(u, c) : -1;
-		double value = 0.0;
+		R value = R(0.0);
 		if (s < valid) {
-			const double* rs = s_rst + u * kN_rst + (static_cast<size_t>(c & 1) * C + s) * 2;
-			const double t = rs[0], t2 = rs[1];
+			const R* rs = s_rst + u * kN_rst + (static_cast<size_t>(c & 1) * C + s) * 2;
+			const R t = rs[0], t2 = rs[1];
 			if (k.waveform == 0) {
-				if (t < k5.rb_t1) {
-					const double x = t / k5.rb_t1;
-					value = (x * x) * (3.0 - 2.0 * x);
+				if (t < R(k5.rb_t1)) {
+					const R x = t / R(k5.rb_t1);
+					value = (x * x) * (R(3.0) - R(2.0) * x);
 				} else if (t < t2) {
-					const double x = (t - k5.rb_t1) / (t2 - k5.rb_t1);
-					value = 1.0 - x * x;
+					const R x = (t - R(k5.rb_t1)) / (t2 - R(k5.rb_t1));
+					value = R(1.0) - x * x;
 				}
 			} else {
-				value = sin(t * (2.0 * 3.14159265358979323846));
+				value = sin_m5(t * R(2.0 * 3.14159265358979323846));
 			}
 			s_val[u * kN_val + (c & 1) * C + s] = value;
 		}
-		double prev = __shfl_up(value, 1);
-		if (s == 0) prev = (c > 0 || streaming) ? s_val[u * kN_val + ((c - 1) & 1) * C + C - 1] : 0.0;
-		if (s < valid) s_u[u * kN_u + (c & 1) * (C + 4) + s] = k5.gp_b0 * (value + prev);
+		R prev = __shfl_up(value, 1);
+		if (s == 0) prev = (c > 0 || streaming) ? s_val[u * kN_val + ((c - 1) & 1) * C + C - 1] : R(0.0);
+		if (s < valid) s_u[u * kN_u + (c & 1) * (C + 4) + s] = R(k5.gp_b0) * (value + prev);
 	};
 
 	// M: source mix, tube input, glottal loss (VocalTractModel5.h:553-573) and the feed-forward half of the
@@ -452,33 +481,33 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 	auto stage_m = [&](int c) {
 		const int u = item_u < U ? item_u : U - 1, s = item_s;
 		const int valid = item_u < U ? valid_in(u, c) : -1;
-		double fn = 0.0;
+		R fn = R(0.0);
 		if (s < valid) {
-			const double pulse = s_pl[u * kN_pl + (c & 1) * C + s];
-			const double* rn = s_rn + u * kN_rn + (static_cast<size_t>(c & 3) * C + s) * 2;
-			const double* rm = s_rm + u * kN_rm + (static_cast<size_t>(c % 5) * C + s) * 2;
-			const double gn = rn[0], ga = rm[0], asp = rm[1];
+			const R pulse = s_pl[u * kN_pl + (c & 1) * C + s];
+			const R* rn = s_rn + u * kN_rn + (static_cast<size_t>(c & 3) * C + s) * 2;
+			const R* rm = s_rm + u * kN_rm + (static_cast<size_t>(c % 5) * C + s) * 2;
+			const R gn = rn[0], ga = rm[0], asp = rm[1];
 			fn = rn[1];
-			const double bf = k.breathiness;
-			const double pulsed_noise = gn * pulse;
-			const double noisy_pulse = ga * (pulse * (1.0 - bf) + pulsed_noise * bf);
+			const R bf = R(k.breathiness);
+			const R pulsed_noise = gn * pulse;
+			const R noisy_pulse = ga * (pulse * (R(1.0) - bf) + pulsed_noise * bf);
 			if (k.modulation) {
-				double cm = ga * k.crossmix_factor;
-				cm = cm < 1.0 ? cm : 1.0;
-				fn = fn * (noisy_pulse * cm + (1.0 - cm));
+				R cm = ga * R(k.crossmix_factor);
+				cm = cm < R(1.0) ? cm : R(1.0);
+				fn = fn * (noisy_pulse * cm + (R(1.0) - cm));
 			}
-			const double input = noisy_pulse + asp * fn;
-			const double min_l = 1.0 - ga * k5.min_loss;
-			const double max_l = 1.0 - ga * k5.max_loss;
-			const double gloss = min_l + (max_l - min_l) * pulse;
-			double* mg = s_mg + u * kN_mg + (static_cast<size_t>(c % 3) * C + s) * 2;
+			const R input = noisy_pulse + asp * fn;
+			const R min_l = R(1.0) - ga * R(k5.min_loss);
+			const R max_l = R(1.0) - ga * R(k5.max_loss);
+			const R gloss = min_l + (max_l - min_l) * pulse;
+			R* mg = s_mg + u * kN_mg + (static_cast<size_t>(c % 3) * C + s) * 2;
 			mg[0] = -gloss; // S1's left link computes X - k P
 			mg[1] = input;
 			s_inp[u * kN_inp + (c % 7) * C + s] = input;
 			s_fnm[u * kN_fnm + (c & 1) * C + s] = fn;
 		}
-		double x2 = __shfl_up(fn, 2);
-		if (s < 2) x2 = (c > 0 || streaming) ? s_fnm[u * kN_fnm + ((c - 1) & 1) * C + C - 2 + s] : 0.0;
+		R x2 = __shfl_up(fn, 2);
+		if (s < 2) x2 = (c > 0 || streaming) ? s_fnm[u * kN_fnm + ((c - 1) & 1) * C + C - 2 + s] : R(0.0);
 		if (s < valid) s_ub[u * kN_ub + (c & 1) * (C + 4) + s] = s_rb0[u * kN_rb0 + (c % 3) * C + s] * (fn - x2);
 	};
 
@@ -486,22 +515,22 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 	auto stage_n = [&](int c) {
 		const int u = item_u, s = item_s;
 		if (u >= U || s >= valid_in(u, c)) return;
-		const double* r = s_rfr + u * kN_rfr + (static_cast<size_t>(c & 3) * C + s) * kRfr;
-		const double fv = r[0] * (k5.frication_factor * s_bp[u * kN_bp + (c & 1) * C + s]);
-		const double* mg = s_mg + u * kN_mg + (static_cast<size_t>(c % 3) * C + s) * 2;
-		double* ru = s_ru + u * kN_ru + (static_cast<size_t>(c & 1) * (C + 2) + s) * kRu;
+		const R* r = s_rfr + u * kN_rfr + (static_cast<size_t>(c & 3) * C + s) * kRfr;
+		const R fv = r[0] * (R(k5.frication_factor) * s_bp[u * kN_bp + (c & 1) * C + s]);
+		const R* mg = s_mg + u * kN_mg + (static_cast<size_t>(c % 3) * C + s) * 2;
+		R* ru = s_ru + u * kN_ru + (static_cast<size_t>(c & 1) * (C + 2) + s) * kRu;
 		ru[kRuLoss] = mg[0];
 		// the dense "added to the new top" lanes: clear what this record held two chunks ago, then S1 <- tube input and
 		// the two frication sections (a position outside the tube, which the reference would index out of bounds, is dropped)
 		int* side = s_side + u * kN_side + (c & 1) * C + s;
 		const int old = *side;
-		double* add = ru + kRuAdd;
-		add[old] = 0.0;
-		add[old + 1] = 0.0;
+		R* add = ru + kRuAdd;
+		add[old] = R(0.0);
+		add[old + 1] = R(0.0);
 		const int fl = static_cast<int>(r[3]);
 		const int at = (fl >= 1 && fl <= 28) ? fl : kAddNone;
-		add[at] = fl == at ? fv * r[1] : 0.0;
-		add[at + 1] = fl == at ? fv * r[2] : 0.0;
+		add[at] = fl == at ? fv * r[1] : R(0.0);
+		add[at + 1] = fl == at ? fv * r[2] : R(0.0);
 		add[0] = mg[1];
 		*side = at;
 	};
@@ -512,24 +541,24 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 	auto stage_y = [&](int c) {
 		const int u = item_u < U ? item_u : U - 1, s = item_s;
 		const int valid = item_u < U ? valid_in(u, c) : -1;
-		double in_m = 0.0, in_n = 0.0;
+		R in_m = R(0.0), in_n = R(0.0);
 		if (s < valid) {
-			const double* ox = s_ox + u * kN_ox + (static_cast<size_t>(c & 1) * C + s) * 2;
+			const R* ox = s_ox + u * kN_ox + (static_cast<size_t>(c & 1) * C + s) * 2;
 			in_m = ox[0];
 			in_n = ox[1];
 		}
-		double pm = __shfl_up(in_m, 1), pn = __shfl_up(in_n, 1);
+		R pm = __shfl_up(in_m, 1), pn = __shfl_up(in_n, 1);
 		if (s == 0) {
-			pm = (c > 0 || streaming) ? s_carry[u * kN_carry + ((c - 1) & 1) * 2] : 0.0;
-			pn = (c > 0 || streaming) ? s_carry[u * kN_carry + ((c - 1) & 1) * 2 + 1] : 0.0;
+			pm = (c > 0 || streaming) ? s_carry[u * kN_carry + ((c - 1) & 1) * 2] : R(0.0);
+			pn = (c > 0 || streaming) ? s_carry[u * kN_carry + ((c - 1) & 1) * 2 + 1] : R(0.0);
 		}
 		if (s < valid) {
-			const double* rmo = s_rmo + u * kN_rmo + (static_cast<size_t>(c & 3) * C + s) * 3;
-			double* yv = s_yv + u * kN_yv + (static_cast<size_t>(c & 1) * (C + 2) + s) * 4;
+			const R* rmo = s_rmo + u * kN_rmo + (static_cast<size_t>(c & 3) * C + s) * 3;
+			R* yv = s_yv + u * kN_yv + (static_cast<size_t>(c & 1) * (C + 2) + s) * 4;
 			yv[0] = rmo[1] * in_m;
 			yv[1] = rmo[2] * pm;
-			yv[2] = k5.nose_c[1] * in_n;
-			yv[3] = k5.nose_c[2] * pn;
+			yv[2] = R(k5.nose_c[1]) * in_n;
+			yv[3] = R(k5.nose_c[2]) * pn;
 		}
 		if (s == valid - 1 && item_u < U) { // (a chunk's last step: the next chunk's -- or the next launch's -- predecessor)
 			s_carry[u * kN_carry + (c & 1) * 2] = in_m;
@@ -544,8 +573,8 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 			const int u = item_u, s = item_s;
 			if (u < U && s < valid_in(u, c)) {
 				const uint32_t n0 = static_cast<uint32_t>(s_ext[u].step_base) + static_cast<uint32_t>(c) * C; // ring slots go by the stream's sample number
-				const double* oo = s_oo + u * kN_oo + (static_cast<size_t>(c & 1) * C + s) * 2;
-				const double v = k5.bypass ? s_inp[u * kN_inp + (c % 7) * C + s] : oo[0] + oo[1];
+				const R* oo = s_oo + u * kN_oo + (static_cast<size_t>(c & 1) * C + s) * 2;
+				const R v = k5.bypass ? s_inp[u * kN_inp + (c % 7) * C + s] : oo[0] + oo[1];
 				s_x[u * XR + ((n0 + s) & (XR - 1))] = v;
 			}
 		}
@@ -554,7 +583,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 			for (int u = 0; u < U; ++u) {
 				const Extent e = s_ext[u];
 				if (c == e.nchunks - 1 && valid_in(u, c) >= 0) {
-					for (int i = lane; i < 2 * k.pad; i += 64) s_x[u * XR + ((static_cast<uint32_t>(e.step_base) + e.steps + i) & (XR - 1))] = 0.0;
+					for (int i = lane; i < 2 * k.pad; i += 64) s_x[u * XR + ((static_cast<uint32_t>(e.step_base) + e.steps + i) & (XR - 1))] = R(0.0);
 				}
 			}
 		}
@@ -585,30 +614,30 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 	// P6: SampleRateConverter::dataEmpty (SampleRateConverter.h:295-416) evaluated per output sample
 	// the converter's output sample ko from the ring as it stands
 	auto src_value = [&](int u, uint64_t ko) -> float {
-		const double* const s_x = s_x_all + u * XR; // (this utterance's ring)
+		const R* const s_x = s_x_all + u * XR; // (this utterance's ring)
 		const uint64_t t = ko * k.time_inc;
 		const int base = static_cast<int>(t >> 16) - k.pad; // ring index p holds internal sample p - pad
 		const unsigned frac = static_cast<unsigned>(t & 0xFFFFu);
-		double acc = 0.0;
+		R acc = R(0.0);
 		// {h, deltaH} of a tap: deltaH_[i] = h_[i+1] - h_[i] as initializeFilter formed it (SampleRateConverter.h:250-254)
 		auto src_tap = [&](unsigned i) {
-			const double h0 = s_src[i], h1 = s_src[i + 1];
-			return SrcTap<double>{h0, h1 - h0};
+			const R h0 = s_src[i], h1 = s_src[i + 1];
+			return SrcTap<R>{h0, h1 - h0};
 		};
 		if (k.upsampling) {
 			const unsigned l = frac >> 8, m = frac & 0xFFu;
-			const double interp = static_cast<double>(m) / 256.0;
+			const R interp = static_cast<R>(m) / R(256.0);
 #pragma unroll
 			for (int j = 0; j < kSrcZeroCrossings; ++j) {
-				const SrcTap<double> cf = src_tap(l + 256 * j);
+				const SrcTap<R> cf = src_tap(l + 256 * j);
 				acc += s_x[(base - j) & (XR - 1)] * (cf.h + cf.dh * interp);
 			}
 			const unsigned nfrac = (~frac) & 0xFFFFu;
 			const unsigned l2 = nfrac >> 8, m2 = nfrac & 0xFFu;
-			const double interp2 = static_cast<double>(m2) / 256.0;
+			const R interp2 = static_cast<R>(m2) / R(256.0);
 #pragma unroll
 			for (int j = 0; j < kSrcZeroCrossings; ++j) {
-				const SrcTap<double> cf = src_tap(l2 + 256 * j);
+				const SrcTap<R> cf = src_tap(l2 + 256 * j);
 				acc += s_x[(base + 1 + j) & (XR - 1)] * (cf.h + cf.dh * interp2);
 			}
 		} else {
@@ -619,23 +648,23 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 			const int n_taps = static_cast<int>((limit + k.phase_inc - 1) / k.phase_inc);
 			auto wing = [&](unsigned ph0, int first, int dir) {
 				for (int j0 = 0; j0 < n_taps; j0 += 4) {
-					SrcTap<double> cf[4];
-					double xv[4], w[4];
+					SrcTap<R> cf[4];
+					R xv[4], w[4];
 #pragma unroll
 					for (int q = 0; q < 4; ++q) {
 						const unsigned ph = ph0 + static_cast<unsigned>(j0 + q) * k.phase_inc;
 						const bool in = ph < limit;
 						cf[q] = src_tap(in ? (ph >> 8) : 0u);
 						xv[q] = s_x[(first + dir * (j0 + q)) & (XR - 1)];
-						w[q] = in ? static_cast<double>(ph & 0xFFu) / 256.0 : 0.0;
-						if (!in) cf[q] = SrcTap<double>{0.0, 0.0};
+						w[q] = in ? static_cast<R>(ph & 0xFFu) / R(256.0) : R(0.0);
+						if (!in) cf[q] = SrcTap<R>{R(0.0), R(0.0)};
 					}
 #pragma unroll
 					for (int q = 0; q < 4; ++q) acc += xv[q] * (cf[q].h + cf[q].dh * w[q]);
 				}
 			};
-			wing(static_cast<unsigned>(rint(static_cast<double>(frac) * k.src_ratio)), base, -1);
-			wing(static_cast<unsigned>(rint(static_cast<double>((~frac) & 0xFFFFu) * k.src_ratio)), base + 1, 1);
+			wing(static_cast<unsigned>(rint(static_cast<R>(frac) * R(k.src_ratio))), base, -1);
+			wing(static_cast<unsigned>(rint(static_cast<R>((~frac) & 0xFFFFu) * R(k.src_ratio))), base + 1, 1);
 		}
 		return static_cast<float>(acc);
 	};
@@ -678,7 +707,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 			} else {
 				const float v2 = ko >= 2 ? yr[(ko - 2) & (kYr - 1)] : 0.0f;
 				const float d = v - v2;
-				y = static_cast<float>(static_cast<double>(d) * k5.output_rate);
+				y = static_cast<float>(static_cast<R>(d) * R(k5.output_rate));
 			}
 			const uint64_t kout = ko - s_ext[u].k_first; // (a stream's launch numbers its samples from its own first one)
 			if (kout < a.audio_stride) a.audio[GVTM_M5_UTT(u, (group * U + u)) * a.audio_stride + kout] = y;
@@ -693,9 +722,9 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 
 	// A wavefront runs ONE serial role for the whole kernel, so the recurrence states of the roles share one
 	// register array (each role names its own view of it) instead of each occupying registers in every wavefront.
-	double st[9];
+	R st[9];
 #pragma unroll
-	for (int i = 0; i < 9; ++i) st[i] = 0.0;
+	for (int i = 0; i < 9; ++i) st[i] = R(0.0);
 
 	// I: Controller::synthesize's interpolation (Controller.cpp:294-311), lane p owns parameter p and runs the
 	// chunk its consumer pass needs next
@@ -744,71 +773,79 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 	// Butterworth1 and the frication-noise Butterworth2 (VocalTractModel5.h:549-551, :559).  Blocks of four steps,
 	// the next block's inputs fetched while this one is computed; a partial last block runs on (the state is
 	// never used after the utterance's last chunk); only lane 0 stores.
-	double &sc_t = st[0], &sc_t2 = st[1], &sc_seed = st[2];
-	double &gn_x1 = st[3], &gn_y1 = st[4];
-	double &fn_x1 = st[5], &fn_x2 = st[6], &fn_y1 = st[7], &fn_y2 = st[8];
+	// (the noise generator's seed is double in every class, NoiseSource.h:41-54: the float class keeps it beside st[])
+	double seed_wide = 0.0;
+	auto seed_slot = [&]() -> double& {
+		if constexpr (FLOAT) return seed_wide;
+		else return st[2];
+	};
+	R &sc_t = st[0], &sc_t2 = st[1];
+	double& sc_seed = seed_slot();
+	R &gn_x1 = st[3], &gn_y1 = st[4];
+	R &fn_x1 = st[5], &fn_x2 = st[6], &fn_y1 = st[7], &fn_y2 = st[8];
 	if (role == 1) {
-		sc_t2 = k5.rb_t1 + k5.rb_tn_max; // RosenbergBGlottalSource::reset
-		sc_seed = 0.7892347;              // NoiseSource's initial seed (NoiseSource.h:32-34)
+		sc_t2 = R(k5.rb_t1) + R(k5.rb_tn_max); // RosenbergBGlottalSource::reset
+		sc_seed = 0.7892347;                 // NoiseSource's initial seed (NoiseSource.h:32-34)
 	}
 	// a stream's recurrence states as the previous launch left them (a fresh stream holds the values above and zeros)
 	if (streaming) {
 		if (role == 1 && lane < U && GVTM_M5_UTT(lane, group * U + lane) < a.batch) {
 			const double* sc = reinterpret_cast<const double*>(a.stream + GVTM_M5_UTT(lane, (group * U + lane)) * a.stream_stride + Stream5Layout::scalars());
 #pragma unroll
-			for (int i = 0; i < 9; ++i) st[i] = sc[kS5Scan + i];
+			for (int i = 0; i < 9; ++i) st[i] = static_cast<R>(sc[kS5Scan + i]);
+			if constexpr (FLOAT) seed_wide = sc[kS5Scan + 2];
 		} else if (role == 2 && lane < 2 * U && GVTM_M5_UTT(lane >> 1, group * U + (lane >> 1)) < a.batch) {
 			// (lane u: glottal low-pass and band-pass memories of utterance u; lanes 2u, 2u + 1: its transmitted-flow memories)
 			const double* sc2 = reinterpret_cast<const double*>(a.stream + GVTM_M5_UTT(lane >> 1, (group * U + (lane >> 1))) * a.stream_stride + Stream5Layout::scalars());
-			st[3] = sc2[kS5Fo + (lane & 1)];
+			st[3] = static_cast<R>(sc2[kS5Fo + (lane & 1)]);
 			if (lane < U && GVTM_M5_UTT(lane, group * U + lane) < a.batch) {
 				const double* sc = reinterpret_cast<const double*>(a.stream + GVTM_M5_UTT(lane, (group * U + lane)) * a.stream_stride + Stream5Layout::scalars());
-				st[0] = sc[kS5Gp];
-				st[1] = sc[kS5Bp];
-				st[2] = sc[kS5Bp + 1];
+				st[0] = static_cast<R>(sc[kS5Gp]);
+				st[1] = static_cast<R>(sc[kS5Bp]);
+				st[2] = static_cast<R>(sc[kS5Bp + 1]);
 			}
 		} else if (role == 0 && lane <= kNose && GVTM_M5_UTT(tube_u, group * U + tube_u) < a.batch) {
 			const double* tb = reinterpret_cast<const double*>(a.stream + GVTM_M5_UTT(tube_u, (group * U + tube_u)) * a.stream_stride + Stream5Layout::tube()) + lane * 4;
 #pragma unroll
-			for (int i = 0; i < 4; ++i) st[i] = tb[i];
+			for (int i = 0; i < 4; ++i) st[i] = static_cast<R>(tb[i]);
 		}
 	}
 	// (lane u runs utterance u; the lanes beyond mirror the last one and store nothing)
 	const int su = lane < U ? lane : U - 1;
 	auto stage_s = [&](int c) {
 		const int valid = valid_any(c);
-		const double2* rd = reinterpret_cast<const double2*>(s_rd + su * kN_rd + static_cast<size_t>(c & 1) * (C + 4) * 2);
-		double2* rst = reinterpret_cast<double2*>(s_rst + su * kN_rst + static_cast<size_t>(c & 1) * C * 2);
-		double2* rn = reinterpret_cast<double2*>(s_rn + su * kN_rn + static_cast<size_t>(c & 3) * C * 2);
-		const double gb0 = k5.gn_b0, ga1 = k5.gn_a1, fb0 = k5.fn_b0, fb1 = k5.fn_b1, fa1 = k5.fn_a1, fa2 = k5.fn_a2;
-		double2 nx[4];
+		const R2* rd = reinterpret_cast<const R2*>(s_rd + su * kN_rd + static_cast<size_t>(c & 1) * (C + 4) * 2);
+		R2* rst = reinterpret_cast<R2*>(s_rst + su * kN_rst + static_cast<size_t>(c & 1) * C * 2);
+		R2* rn = reinterpret_cast<R2*>(s_rn + su * kN_rn + static_cast<size_t>(c & 3) * C * 2);
+		const R gb0 = R(k5.gn_b0), ga1 = R(k5.gn_a1), fb0 = R(k5.fn_b0), fb1 = R(k5.fn_b1), fa1 = R(k5.fn_a1), fa2 = R(k5.fn_a2);
+		R2 nx[4];
 #pragma unroll
 		for (int q = 0; q < 4; ++q) nx[q] = rd[q];
 		for (int s0 = 0; s0 < valid; s0 += 4) {
-			double2 in[4];
+			R2 in[4];
 #pragma unroll
 			for (int q = 0; q < 4; ++q) in[q] = nx[q];
 #pragma unroll
 			for (int q = 0; q < 4; ++q) nx[q] = rd[s0 + 4 + q]; // the last block reads the four pad entries
-			double2 ot[4], on[4];
+			R2 ot[4], on[4];
 #pragma unroll
 			for (int q = 0; q < 4; ++q) {
-				ot[q] = double2{sc_t, sc_t2};
-				double tn = sc_t + in[q].x;
-				const bool wrap = tn > 1.0;
-				sc_t = wrap ? tn - 1.0 : tn;
+				ot[q] = R2{sc_t, sc_t2};
+				R tn = sc_t + in[q].x;
+				const bool wrap = tn > R(1.0);
+				sc_t = wrap ? tn - R(1.0) : tn;
 				sc_t2 = wrap ? in[q].y : sc_t2;
 				sc_seed = noise_advance(sc_seed);
-				const double white = sc_seed - 0.5;
-				const double gn = gb0 * (white + gn_x1) - ga1 * gn_y1;
+				const R white = static_cast<R>(sc_seed - 0.5);
+				const R gn = gb0 * (white + gn_x1) - ga1 * gn_y1;
 				gn_x1 = white;
 				gn_y1 = gn;
-				const double fn = fb0 * (white + fn_x2) + fb1 * fn_x1 - fa1 * fn_y1 - fa2 * fn_y2;
+				const R fn = fb0 * (white + fn_x2) + fb1 * fn_x1 - fa1 * fn_y1 - fa2 * fn_y2;
 				fn_x2 = fn_x1;
 				fn_x1 = white;
 				fn_y2 = fn_y1;
 				fn_y1 = fn;
-				on[q] = double2{gn, fn};
+				on[q] = R2{gn, fn};
 			}
 			if (lane < U) {
 #pragma unroll
@@ -821,82 +858,89 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 	};
 
 	// F: the recursive half of the glottal low-pass, pulse = u - a1 pulse[-1]
-	double& gp_y1 = st[0];
+	R& gp_y1 = st[0];
 	auto stage_f = [&](int c) {
 		const int valid = valid_any(c);
-		const double2* up = reinterpret_cast<const double2*>(s_u + su * kN_u + static_cast<size_t>(c & 1) * (C + 4));
-		double2* pl = reinterpret_cast<double2*>(s_pl + su * kN_pl + static_cast<size_t>(c & 1) * C);
-		const double a1 = k5.gp_a1;
-		double2 n0 = up[0], n1 = up[1];
+		const R2* up = reinterpret_cast<const R2*>(s_u + su * kN_u + static_cast<size_t>(c & 1) * (C + 4));
+		R2* pl = reinterpret_cast<R2*>(s_pl + su * kN_pl + static_cast<size_t>(c & 1) * C);
+		const R a1 = R(k5.gp_a1);
+		R2 n0 = up[0], n1 = up[1];
 		for (int s0 = 0; s0 < valid; s0 += 4) {
-			const double2 i0 = n0, i1 = n1;
+			const R2 i0 = n0, i1 = n1;
 			n0 = up[s0 / 2 + 2];
 			n1 = up[s0 / 2 + 3];
-			const double y0 = i0.x - a1 * gp_y1;
-			const double y1 = i0.y - a1 * y0;
-			const double y2 = i1.x - a1 * y1;
-			const double y3 = i1.y - a1 * y2;
+			const R y0 = i0.x - a1 * gp_y1;
+			const R y1 = i0.y - a1 * y0;
+			const R y2 = i1.x - a1 * y1;
+			const R y3 = i1.y - a1 * y2;
 			gp_y1 = y3;
 			if (lane < U) {
-				pl[s0 / 2] = double2{y0, y1};
-				pl[s0 / 2 + 1] = double2{y2, y3};
+				pl[s0 / 2] = R2{y0, y1};
+				pl[s0 / 2 + 1] = R2{y2, y3};
 			}
 		}
 	};
 
 	// Fb: the recursive half of the frication band-pass, y = ub - a1 y[-1] - a2 y[-2] (coefficients change per step)
-	double &bp_y1 = st[1], &bp_y2 = st[2];
+	R &bp_y1 = st[1], &bp_y2 = st[2];
 	auto stage_fb = [&](int c) {
 		const int valid = valid_any(c);
-		const double2* ub = reinterpret_cast<const double2*>(s_ub + su * kN_ub + static_cast<size_t>(c & 1) * (C + 4));
-		const double2* a12 = reinterpret_cast<const double2*>(s_ra12 + su * kN_ra12 + static_cast<size_t>(c % 3) * (C + 4) * 2);
-		double2* bp = reinterpret_cast<double2*>(s_bp + su * kN_bp + static_cast<size_t>(c & 1) * C);
-		double2 n0 = ub[0], n1 = ub[1];
-		double2 nc[4];
+		const R2* ub = reinterpret_cast<const R2*>(s_ub + su * kN_ub + static_cast<size_t>(c & 1) * (C + 4));
+		const R2* a12 = reinterpret_cast<const R2*>(s_ra12 + su * kN_ra12 + static_cast<size_t>(c % 3) * (C + 4) * 2);
+		R2* bp = reinterpret_cast<R2*>(s_bp + su * kN_bp + static_cast<size_t>(c & 1) * C);
+		R2 n0 = ub[0], n1 = ub[1];
+		R2 nc[4];
 #pragma unroll
 		for (int q = 0; q < 4; ++q) nc[q] = a12[q];
 		for (int s0 = 0; s0 < valid; s0 += 4) {
-			const double2 i0 = n0, i1 = n1;
-			double2 cf[4];
+			const R2 i0 = n0, i1 = n1;
+			R2 cf[4];
 #pragma unroll
 			for (int q = 0; q < 4; ++q) cf[q] = nc[q];
 			n0 = ub[s0 / 2 + 2];
 			n1 = ub[s0 / 2 + 3];
 #pragma unroll
 			for (int q = 0; q < 4; ++q) nc[q] = a12[s0 + 4 + q];
-			const double y0 = i0.x - cf[0].x * bp_y1 - cf[0].y * bp_y2;
-			const double y1 = i0.y - cf[1].x * y0 - cf[1].y * bp_y1;
-			const double y2 = i1.x - cf[2].x * y1 - cf[2].y * y0;
-			const double y3 = i1.y - cf[3].x * y2 - cf[3].y * y1;
+			const R y0 = i0.x - cf[0].x * bp_y1 - cf[0].y * bp_y2;
+			const R y1 = i0.y - cf[1].x * y0 - cf[1].y * bp_y1;
+			const R y2 = i1.x - cf[2].x * y1 - cf[2].y * y0;
+			const R y3 = i1.y - cf[3].x * y2 - cf[3].y * y1;
 			bp_y2 = y2;
 			bp_y1 = y3;
 			if (lane < U) {
-				bp[s0 / 2] = double2{y0, y1};
-				bp[s0 / 2 + 1] = double2{y2, y3};
+				bp[s0 / 2] = R2{y0, y1};
+				bp[s0 / 2 + 1] = R2{y2, y3};
 			}
 		}
 	};
 
 	// Fo: recursion of the transmitted flow, outT = (cT1 outT[-1] + cT2 in) + cT3 in[-1]; lane 0 the mouth (cT1 changes
 	// per step), lane 1 the nose
-	double& fo_y1 = st[3];
+	R& fo_y1 = st[3];
 	// (lanes 2u, 2u + 1: mouth and nose of utterance u)
 	const int fo_u = (lane >> 1) < U ? (lane >> 1) : U - 1;
 	auto stage_fo = [&](int c) {
 		const int valid = valid_any(c);
 		const bool mouth = (lane & 1) == 0;
-		const double* pc = mouth ? s_rmo + fo_u * kN_rmo + static_cast<size_t>(c & 3) * C * 3 : &s_k5->nose_c[0];
+		const R* pc;
+		if constexpr (FLOAT) {
+			// (the nose's constant cT1 is a widened float in the constants block: the nose lane walks a narrowed copy)
+			if (lane == 1) s_dump[0] = R(k5.nose_c[0]);
+			pc = mouth ? s_rmo + fo_u * kN_rmo + static_cast<size_t>(c & 3) * C * 3 : s_dump;
+		} else {
+			pc = mouth ? s_rmo + fo_u * kN_rmo + static_cast<size_t>(c & 3) * C * 3 : &s_k5->nose_c[0];
+		}
 		const int c_stride = mouth ? 3 : 0;
-		const double* pv = s_yv + fo_u * kN_yv + static_cast<size_t>(c & 1) * (C + 2) * 4 + (mouth ? 0 : 2);
-		double* po = s_oo + fo_u * kN_oo + static_cast<size_t>(c & 1) * C * 2 + (mouth ? 0 : 1);
-		double nc = pc[0];
-		double2 nv = *reinterpret_cast<const double2*>(pv);
+		const R* pv = s_yv + fo_u * kN_yv + static_cast<size_t>(c & 1) * (C + 2) * 4 + (mouth ? 0 : 2);
+		R* po = s_oo + fo_u * kN_oo + static_cast<size_t>(c & 1) * C * 2 + (mouth ? 0 : 1);
+		R nc = pc[0];
+		R2 nv = *reinterpret_cast<const R2*>(pv);
 		for (int s = 0; s < valid; ++s) {
-			const double c1 = nc;
-			const double2 v = nv;
+			const R c1 = nc;
+			const R2 v = nv;
 			nc = pc[(s + 1) * c_stride];   // (the mouth lane reads one entry past the chunk: the next slot's, never used)
-			nv = *reinterpret_cast<const double2*>(pv + (s + 1) * 4);
-			const double y = (c1 * fo_y1 + v.x) + v.y;
+			nv = *reinterpret_cast<const R2*>(pv + (s + 1) * 4);
+			const R y = (c1 * fo_y1 + v.x) + v.y;
 			fo_y1 = y;
 			if (lane < 2 * U) po[s * 2] = y;
 		}
@@ -912,13 +956,13 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 	// S1: Tl' = 0, kl = -glottal loss, dl = 1, add = tube input (:652); S13 / S12: et / eb = N1's bottom, k = -/+ the
 	// velum coefficient; N1: Tl' = S12.top + S13.bottom (:297-303); S30, N21: Br' = the reflected flow of the
 	// radiation impedance (PoleZeroRadiationImpedance::process).
-	double &top = st[0], &bot = st[1];
-	double &ri_in1 = st[2], &ri_outR1 = st[3]; // PoleZeroRadiationImpedance state of an end lane (reflection side)
+	R &top = st[0], &bot = st[1];
+	R &ri_in1 = st[2], &ri_outR1 = st[3]; // PoleZeroRadiationImpedance state of an end lane (reflection side)
 	auto stage_tube = [&](int c) {
 		const int valid = valid_in(tube_u, c);
-		const double* ru = s_ru + tube_u * kN_ru + static_cast<size_t>(c & 1) * (C + 2) * kRu;
-		double* ox = s_ox + tube_u * kN_ox + static_cast<size_t>(c & 1) * C * 2;
-		const double d = k.damping;
+		const R* ru = s_ru + tube_u * kN_ru + static_cast<size_t>(c & 1) * (C + 2) * kRu;
+		R* ox = s_ox + tube_u * kN_ox + static_cast<size_t>(c & 1) * C * 2;
+		const R d = R(k.damping);
 		// record slot of the coefficient of the link on the LEFT of lane L (kRuZero: a plain damped link)
 		auto slot_left = [](int L) -> int {
 			switch (L) {
@@ -937,20 +981,20 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 		// coefficient); the open ends and the idle lanes have none
 		const bool has_right = lane != kMouth && lane < kNose;
 		const int sr = lane == kThreeLeft ? kRkVl : (has_right ? slot_left(lane + 1) : kRuZero);
-		const double* pkl = ru + slot_left(lane);
-		const double* pkr = ru + sr;
-		const double* pe = ru + (lane == kMouth ? kRkMouth : kRuNose); // lanes in between run the nose's (stable) filter on the side
-		const double* padd = ru + kRuAdd + (lane < kAddLanes ? lane : kAddLanes - 1); // what is added to my new top (0 beyond S29)
-		double* pox = is_end ? ox + (lane == kNose ? 1 : 0) : s_dump + 64 + lane;
+		const R* pkl = ru + slot_left(lane);
+		const R* pkr = ru + sr;
+		const R* pe = ru + (lane == kMouth ? kRkMouth : kRuNose); // lanes in between run the nose's (stable) filter on the side
+		const R* padd = ru + kRuAdd + (lane < kAddLanes ? lane : kAddLanes - 1); // what is added to my new top (0 beyond S29)
+		R* pox = is_end ? ox + (lane == kNose ? 1 : 0) : s_dump + 64 + lane;
 		const int ox_stride = is_end ? 2 : 0;
-		const double m_t = lane == kThreeRight ? 1.0 : 0.0, m_b = lane == kThreeLeft ? 1.0 : 0.0;
-		const double m_u = lane == kNasalFirst ? 1.0 : 0.0, nm_u = 1.0 - m_u;
-		const double d_left = is_first ? 1.0 : d;
+		const R m_t = lane == kThreeRight ? R(1.0) : R(0.0), m_b = lane == kThreeLeft ? R(1.0) : R(0.0);
+		const R m_u = lane == kNasalFirst ? R(1.0) : R(0.0), nm_u = R(1.0) - m_u;
+		const R d_left = is_first ? R(1.0) : d;
 
 		// Records are fetched a pair of steps ahead into two register sets that alternate (no copies).
-		struct Rec { double kl, kr, e0, e1, e2, add; };
+		struct Rec { R kl, kr, e0, e1, e2, add; };
 		// read cursors at the first step of the current block of four; the offsets below are immediates
-		using LdsPtr = const __attribute__((address_space(3))) double*;
+		using LdsPtr = const __attribute__((address_space(3))) R*;
 		LdsPtr ckl = (LdsPtr) pkl, ckr = (LdsPtr) pkr, ce = (LdsPtr) pe, ca = (LdsPtr) padd;
 		auto fetch = [&](Rec& r, int s) {
 			r.kl = ckl[s * kRu];
@@ -959,26 +1003,26 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 			r.e0 = e[0]; r.e1 = e[1]; r.e2 = e[2];
 			r.add = ca[s * kRu];
 		};
-		auto step = [&](double kl, double kr, double e0, double e1, double e2, double add, int s) {
-			const double T = top, B = bot;
-			const double Tl = from_left_wave(T), Br = from_right_wave(B);
+		auto step = [&](R kl, R kr, R e0, R e1, R e2, R add, int s) {
+			const R T = top, B = bot;
+			const R Tl = from_left_wave(T), Br = from_right_wave(B);
 			// open ends: the reflected flow outR = cR1 outR1 + cR2 in + cR3 in1 (PoleZeroRadiationImpedance::process); the
 			// transmitted flow is formed downstream from the recorded input (Y, Fo)
-			const double outR = e0 * ri_outR1 + e1 * T + e2 * ri_in1;
+			const R outR = e0 * ri_outR1 + e1 * T + e2 * ri_in1;
 			ri_in1 = T;
 			ri_outR1 = outR;
 			// (the sum below is only used where there is a right link: an end lane's kr is 0)
-			const double pb0 = T + Br;
-			const double b30 = lane_value<kNasalFirst>(B);
-			const double q11 = lane_value<kThreeLeft>(pb0); // S12.top + S13.bottom
-			const double Brp = is_end ? outR : Br;
-			const double et = b30 * m_t, eb = b30 * m_b;
-			const double Tlp = q11 * m_u + Tl * nm_u;
-			const double X = Tlp + et;
-			const double Pt = (Tlp + B) + et;
+			const R pb0 = T + Br;
+			const R b30 = lane_value<kNasalFirst>(B);
+			const R q11 = lane_value<kThreeLeft>(pb0); // S12.top + S13.bottom
+			const R Brp = is_end ? outR : Br;
+			const R et = b30 * m_t, eb = b30 * m_b;
+			const R Tlp = q11 * m_u + Tl * nm_u;
+			const R X = Tlp + et;
+			const R Pt = (Tlp + B) + et;
 			top = (X - kl * Pt) * d_left + add; // add: the tube input (S1) or my share of the frication noise (:716-726)
-			const double Xb = Brp + eb;
-			const double Pb = pb0 + eb;
+			const R Xb = Brp + eb;
+			const R Pb = pb0 + eb;
 			bot = (Xb + kr * Pb) * d;
 			pox[s * ox_stride] = T;
 		};
@@ -1119,7 +1163,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 				} else {
 					const float v2 = ko >= 2 ? v_at(ko - 2) : 0.0f;
 					const float d = v - v2;
-					y = static_cast<float>(static_cast<double>(d) * k5.output_rate);
+					y = static_cast<float>(static_cast<R>(d) * R(k5.output_rate));
 				}
 				if (ko - e.k_first < a.audio_stride) a.audio[GVTM_M5_UTT(u, (group * U + u)) * a.audio_stride + (ko - e.k_first)] = y;
 				lane_peak[u] = fmaxf(lane_peak[u], fabsf(y));
@@ -1156,6 +1200,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64) void vtm5_synth_ker
 			double* sc = reinterpret_cast<double*>(a.stream + GVTM_M5_UTT(lane, (group * U + lane)) * a.stream_stride + Stream5Layout::scalars());
 #pragma unroll
 			for (int i = 0; i < 9; ++i) sc[kS5Scan + i] = st[i];
+			if constexpr (FLOAT) sc[kS5Scan + 2] = seed_wide;
 		} else if (role == 2 && lane < 2 * U && GVTM_M5_UTT(lane >> 1, group * U + (lane >> 1)) < a.batch) {
 			double* sc2 = reinterpret_cast<double*>(a.stream + GVTM_M5_UTT(lane >> 1, (group * U + (lane >> 1))) * a.stream_stride + Stream5Layout::scalars());
 			sc2[kS5Fo + (lane & 1)] = st[3];
@@ -1208,6 +1253,13 @@ static size_t m5_lds_bytes()
 	return m5::Offsets<m5_shape(U).chunk, kM5Ring, U>().total;
 }
 
+// the same for the float class's shape `VARIANT`
+template <int VARIANT>
+static size_t m5_float_lds_bytes()
+{
+	return m5::Offsets<m5_float_shape(VARIANT).chunk, kM5Ring, 1, float>().total;
+}
+
 // VOICES: a launch of several voices (the kernel's kVoices5Flag; args.row_map is set), one utterance per workgroup only;
 // `batch` is then the number of workgroups
 template <int U, bool VOICES>
@@ -1220,5 +1272,17 @@ static hipError_t launch_synth5_shape(const SynthArgs& args, size_t batch, hipSt
 	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(VOICES ? batch : (batch + U - 1) / U)), dim3(s.waves * 64), lds, stream, args);
+	return hipGetLastError();
+}
+
+template <int VARIANT>
+static hipError_t launch_synth5_float_shape(const SynthArgs& args, size_t batch, hipStream_t stream)
+{
+	constexpr M5Shape s = m5_float_shape(VARIANT);
+	auto fn = m5::vtm5_synth_kernel<s.chunk, s.helpers, kM5Ring, 1 | m5::kFloat5Flag>;
+	const size_t lds = m5_float_lds_bytes<VARIANT>();
+	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+	if (e != hipSuccess) return e;
+	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(batch)), dim3(s.waves * 64), lds, stream, args);
 	return hipGetLastError();
 }

@@ -4,7 +4,7 @@
 //                      5 + NH wavefronts with fixed roles (tube, scans, pre-/post-tube filters, interpolation, helpers),
 //                      software-pipelined over chunks of internal-rate steps with one barrier per tick; see that file's header
 //   vtm5_synth_kernel  (vtm_kernel_m5.inc)  VocalTractModel5 semantics, same organisation (its voice variant is compiled
-//                      in vtm_kernels_m5v.hip)
+//                      in vtm_kernels_m5v.hip, its float class in vtm_kernels_m5f.hip)
 //   vtm_normalize_kernel                    output scaling of Controller::writeOutputToBuffer / writeOutputToFile
 //
 // Which shape a launch has (rows, chunk length, helpers, ring, LDS) is decided here and only here: "kernel shapes" below.
@@ -238,6 +238,14 @@ LaunchShape synth_launch_shape(const Design* voices, int n_voices, int precision
 		// one of 60 does, and the tube wavefronts slow down from 268 to 430 cycles per step next to five busy helpers.  A
 		// diagnostics build can still force it (tests hold it to the one-utterance shape's samples bit for bit); the
 		// voice variant has the one-utterance shape only.
+		if (precision == GVTM_PRECISION_F32) {
+			// The float class (one utterance per workgroup, one voice): up to one workgroup per compute unit the chunk of 60
+			// steps; beyond, the chunk of 56, whose 80 800 B let two workgroups share a compute unit (DESIGN.md 4b has the
+			// measurement).  A diagnostics build forces either: rows 1 the first, rows 2 the second.
+			const int variant = forced_rows == 1 ? 0 : (forced_rows == 2 ? 1 : (batch > 256 ? 1 : 0));
+			const LaunchShape s{1, 0, synth5_float_lds_bytes(variant), variant};
+			return fits(s) ? s : LaunchShape{};
+		}
 		const int rows = forced_rows == 2 && !several_voices ? 2 : 1;
 		const LaunchShape s{rows, 0, rows == 2 ? m5_lds_bytes<2>() : m5_lds_bytes<1>()};
 		return fits(s) ? s : LaunchShape{};
@@ -324,9 +332,11 @@ hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream)
 	return hipGetLastError();
 }
 
-hipError_t launch_synth5(const SynthArgs& args, size_t batch, int rows, hipStream_t stream)
+hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int rows, int variant, hipStream_t stream)
 {
 	if (!args.k5const) return hipErrorInvalidValue;
+	// (the float class lives in vtm_kernels_m5f.hip, as the voice variant does in vtm_kernels_m5v.hip)
+	if (precision == GVTM_PRECISION_F32) return rows == 1 ? launch_synth5_float(args, batch, variant, stream) : hipErrorInvalidValue;
 	// (the voice variant lives in vtm_kernels_m5v.hip: this file's code object keeps the single-voice kernels only)
 	if (!args.row_map) {
 		if (rows == 2) return launch_synth5_shape<2, false>(args, batch, stream);

@@ -131,6 +131,7 @@ struct LaunchShape {
 	int rows = 0;
 	int ring = 0;
 	size_t lds = 0;
+	int variant = 0; // the float model 5 only: 0 chunk 60, 1 chunk 56 (two workgroups per compute unit); vtm_kernel_m5.inc
 };
 constexpr size_t kLdsPerWorkgroup = 160 * 1024;
 // THE row choice, for every caller.  voices: the plan's designs (voices[0] says whether model 5); forced_rows: 1, 2, 4 or 8
@@ -151,9 +152,14 @@ hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int 
 size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr);
 // several voices: builds args.row_map / args.group_voice from the voice ids (one small workgroup, stable counting sort)
 hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream);
-// reference model 5 (VocalTractModel5<double,1>), fp64: rows = utterances per workgroup, 1 or 2; with args.row_map set
-// (several voices: one constants block of each kind per voice) 1 only, and `batch` is the number of workgroups
-hipError_t launch_synth5(const SynthArgs& args, size_t batch, int rows, hipStream_t stream);
+// reference model 5: VocalTractModel5<double,1> (GVTM_PRECISION_F64), rows = utterances per workgroup, 1 or 2; with
+// args.row_map set (several voices: one constants block of each kind per voice) 1 only, and `batch` is the number of
+// workgroups.  GVTM_PRECISION_F32: VocalTractModel5<float,1>, one utterance per workgroup, one voice.
+// (`variant`: LaunchShape::variant, which of the float class's two shapes)
+hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int rows, int variant, hipStream_t stream);
+// the float class alone (vtm_kernels_m5f.hip; launch_synth5 calls it), and the LDS bytes of a workgroup of its shape `variant`
+hipError_t launch_synth5_float(const SynthArgs& args, size_t batch, int variant, hipStream_t stream);
+size_t synth5_float_lds_bytes(int variant);
 // the voice variant alone (vtm_kernels_m5v.hip; launch_synth5 calls it): `groups` workgroups of one utterance each
 hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_t stream);
 constexpr int kDppSelftestInts = 640;

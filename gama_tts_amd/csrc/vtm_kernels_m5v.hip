@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "vtm_design.hpp"
 #include "vtm_kernels.hpp"

@@ -267,6 +267,51 @@ GVTM_HD float cosf_glibc(float y)
 	return static_cast<float>(d + x6 * d2);
 }
 
+// sinf AS glibc 2.35 COMPUTES IT (s_sinf.c: the same quadrant reduction and the same two polynomials as cosf, selected
+// by the quadrant itself instead of the quadrant + 1), for the sine waveform of the float model 5
+// (RosenbergBGlottalSource.h:139 calls std::sin on t * 2 pi, t in [0, 1]).  Bit-identical to this machine's libm on
+// every float of [2^-13, 2 pi] (tests/test_capi_model5_float_cpu.py).
+GVTM_HD float sinf_glibc(float y)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+	const uint32_t top = (float_bits(y) >> 20) & 0x7ffu;
+	if (!(top < ((float_bits(120.0f) >> 20) & 0x7ffu))) return static_cast<float>(std::sin(static_cast<double>(y)));
+	constexpr double hpi_inv = 0x1.45F306DC9C883p+23, hpi = 0x1.921FB54442D18p0;
+	constexpr double c0 = 0x1p0, c1 = -0x1.ffffffd0c621cp-2, c2 = 0x1.55553e1068f19p-5, c3 = -0x1.6c087e89a359dp-10,
+			c4 = 0x1.99343027bf8c3p-16;
+	constexpr double s1 = -0x1.555545995a603p-3, s2 = 0x1.1107605230bc4p-7, s3 = -0x1.994eb3774cf24p-13;
+	double x = y;
+	double x2 = x * x;
+	int n = 0;         // polynomial selector: even = sine polynomial, odd = cosine polynomial
+	double flip = 1.0; // sign of the cosine polynomial (second table of the reference)
+	if (top < ((float_bits(0x1.921FB6p-1f) >> 20) & 0x7ffu)) {
+		if (top < ((float_bits(0x1p-12f) >> 20) & 0x7ffu)) return y;
+	} else {
+		const double r = x * hpi_inv;
+		n = (static_cast<int32_t>(r) + 0x800000) >> 24;
+		x = x - n * hpi;
+		const double sgn = ((n & 3) == 1 || (n & 3) == 2) ? -1.0 : 1.0; // sign[] = {1, -1, -1, 1}
+		if (n & 2) flip = -1.0;
+		x2 = x * x;
+		x = x * sgn;
+	}
+	if ((n & 1) == 0) {
+		const double x3 = x * x2;
+		const double t1 = s2 + x2 * s3;
+		const double x7 = x3 * x2;
+		const double t = x + x3 * s1;
+		return static_cast<float>(t + x7 * t1);
+	}
+	const double x4 = x2 * x2;
+	const double d2 = flip * c3 + x2 * (flip * c4);
+	const double d1 = flip * c0 + x2 * (flip * c1);
+	const double x6 = x4 * x2;
+	const double d = d1 + x4 * (flip * c2);
+	return static_cast<float>(d + x6 * d2);
+}
+
 // __kernel_tanf(x, y, iy) for x >= 0
 GVTM_HD float tanf_kernel_glibc(float x, float y, int iy)
 {

@@ -104,15 +104,18 @@ public:
 			c5.max_glottal_loss = k.number("max_glottal_loss");
 			c5.glottal_lowpass_cutoff = k.number("glottal_lowpass_cutoff");
 			if (c5.constant_radius_mouth_impedance) c5.mouth_impedance_radius = k.number("mouth_impedance_radius");
-			c5.precision = GVTM_PRECISION_F64;
+			// gpu_precision = f32: the plugin stands in for VocalTractModel5<float,1>, the class the factory has no number for
+			const bool float5 = k.text("gpu_precision", "f64") == "f32";
+			c5.precision = float5 ? GVTM_PRECISION_F32 : GVTM_PRECISION_F64;
+			const auto create5 = float5 ? gvtm_plan_create_model5_float : gvtm_plan_create_model5;
 			gvtm_plan* probe = nullptr;
-			if (gvtm_plan_create_model5(&c5, 1000.0, GVTM_DEVICE_NONE, &probe) != GVTM_OK) throw std::runtime_error(gvtm_last_error());
+			if (create5(&c5, 1000.0, GVTM_DEVICE_NONE, &probe) != GVTM_OK) throw std::runtime_error(gvtm_last_error());
 			gvtm_info info{};
 			gvtm_plan_info(probe, &info);
 			gvtm_plan_destroy(probe);
 			internal_rate_ = info.internal_rate_hz; // not an integer (vtm/VocalTractModel5.h:465)
 			output_rate_ = c5.output_rate;
-			if (gvtm_plan_create_model5(&c5, info.internal_rate_hz, device, &plan_) != GVTM_OK) throw std::runtime_error(gvtm_last_error());
+			if (create5(&c5, info.internal_rate_hz, device, &plan_) != GVTM_OK) throw std::runtime_error(gvtm_last_error());
 			gvtm_plan_info(plan_, &info);
 			if (info.control_steps != 1) throw std::runtime_error("internal error: plugin plan must run one step per frame");
 			current_.assign(GVTM_N_PARAM, 0.0f);

@@ -15,6 +15,9 @@
  *                               for a whole batch
  *   gvtm_plan_create_model5     VocalTractModel5 constructor (vtm/VocalTractModel5.h:375-421, :455-521); synthesis
  *                               then replaces its execSynthesisStep / vocalTract (:523-579, :632-730)
+ *   gvtm_plan_create_model5_float
+ *                               the same constructor and steps of VocalTractModel5<float,1>, the class the factory has no
+ *                               number for
  *   gvtm_plan_info              VocalTractModel::internalSampleRate/outputSampleRate
  *                               (vtm/VocalTractModel.h:51-52) and the controlSteps of
  *                               Controller::synthesize (vtm_control_model/Controller.cpp:286)
@@ -137,7 +140,7 @@ typedef struct gvtm_info {
 	int32_t device;
 	int32_t precision;
 	int32_t section_delay;
-	int32_t model5;                   /* 1 for a plan made by gvtm_plan_create_model5 / _model5_voices */
+	int32_t model5;                   /* 1 for a plan made by gvtm_plan_create_model5 / _model5_voices / _model5_float */
 	int32_t reserved_;
 	double internal_rate_hz;          /* the internal rate as the model holds it: an integer for models 0-4, not for
 	                                     model 5 (vtm/VocalTractModel5.h:465 keeps it in TFloat) */
@@ -172,8 +175,9 @@ typedef struct gvtm5_config {
 	double max_glottal_loss;
 	double glottal_lowpass_cutoff;
 	double mouth_impedance_radius;            /* used when constant_radius_mouth_impedance != 0 */
-	int32_t precision;                        /* GVTM_PRECISION_F64 only: the factory's model 5 is VocalTractModel5<double,1>
-	                                             (vtm/VocalTractModel.cpp:47-48) */
+	int32_t precision;                        /* GVTM_PRECISION_F64 for gvtm_plan_create_model5 / _model5_voices: the factory's
+	                                             model 5 is VocalTractModel5<double,1> (vtm/VocalTractModel.cpp:47-48);
+	                                             GVTM_PRECISION_F32 for gvtm_plan_create_model5_float */
 	int32_t reserved_;                        /* must be 0 */
 } gvtm5_config;
 
@@ -207,6 +211,13 @@ int gvtm_plan_create(const gvtm_config* config, double control_rate, int device,
  * glottal pulse timings outside RosenbergBGlottalSource's checks, Butterworth cutoffs outside 1 Hz .. 0.48 of the internal
  * rate; and, a limit of this implementation, an output rate above 3x the internal rate. */
 int gvtm_plan_create_model5(const gvtm5_config* config, double control_rate, int device, gvtm_plan** plan_out);
+/* VocalTractModel5<float,1> (no factory number; oracle/ref_driver.cpp's "5f"): config->precision must be
+ * GVTM_PRECISION_F32 (else GVTM_ERR_INVALID_ARGUMENT).  Everything else as gvtm_plan_create_model5: the same refusals, the
+ * same synthesis, stream and events entry points, every constant designed in float as the class's constructors do and
+ * every rounding of its steps reproduced, so the samples are bit-identical to that class's.  gvtm_plan_info reports
+ * model5 = 1, precision = GVTM_PRECISION_F32 and the float class's internal_rate_hz; gvtm_plan_table serves the float
+ * resampler tables (widened).  One voice per plan: the gvtm_synthesize_voices_* entries refuse it (GVTM_ERR_UNSUPPORTED). */
+int gvtm_plan_create_model5_float(const gvtm5_config* config, double control_rate, int device, gvtm_plan** plan_out);
 void gvtm_plan_destroy(gvtm_plan* plan);
 int gvtm_plan_info(const gvtm_plan* plan, gvtm_info* info_out);
 /* Copies a design table into out[capacity]; returns the element count or a negative status. */

@@ -1,0 +1,44 @@
+"""GPU-box diagnostic for the float class of the model-5 kernel (gvtm_plan_create_model5_float): busy cycles per role
+wavefront and per helper stage, as tests/tools/role_cycles_m5.py gives them for the fp64 plan.
+usage: python tests/tools/role_cycles_m5_float.py [batch [frames [rows]]]   (rows 1 / 2: the plan forced to its chunk-60 /
+chunk-56 shape; default 1)"""
+import ctypes
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, ".")
+sys.path.insert(0, "tests")
+import gama_tts_amd as g  # noqa: E402
+import oracle  # noqa: E402
+import tracks  # noqa: E402
+from gama_tts_amd import capi  # noqa: E402
+
+batch = int(sys.argv[1]) if len(sys.argv) > 1 else 256
+frames = int(sys.argv[2]) if len(sys.argv) > 2 else 250
+rows = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+pool = tracks.random_tracks(min(batch, 64), frames, seed0=1000, consonant_heavy=True)
+params = np.concatenate([pool] * ((batch + len(pool) - 1) // len(pool)))[:batch]
+plan = g.Plan(g.config5_from_dict(g.read_config_file(oracle.VOICE5_MALE), None, capi.PRECISION_F32), 250.0, 0, diagnostics=True,
+              rows=rows, float_model5=True)
+n = plan.output_count(frames)
+dev = torch.device("cuda:0")
+d_params = torch.from_numpy(params).to(dev)
+d_audio = torch.zeros((batch, n), dtype=torch.float32, device=dev)
+d_cyc = torch.zeros((batch, 16), dtype=torch.int64, device=dev)
+lib = g.load_library(diagnostics=True)
+lib.gvtm_debug_set_phase_cycles.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+for rep in range(2):
+    lib.gvtm_debug_set_phase_cycles(plan._h, ctypes.c_void_p(d_cyc.data_ptr()))
+    plan.set_timing(True)
+    plan.synthesize_device(d_params, batch, frames, d_audio, n)
+    torch.cuda.synchronize()
+    ms, _ = plan.take_kernel_ms()
+cyc = d_cyc.cpu().numpy().astype(np.float64)
+steps = frames * plan.info.control_steps
+names = ["w0", "w1", "w2", "w3", "w4", "w5", "w6", "st A2", "st A1a", "st A1b", "st P6", "st B", "st M", "st N", "st X", "st P7"]
+print("model 5 float, chunk %d batch %d frames %d: kernel %.3f ms = %.1f ns/step" % (60 if rows == 1 else 56, batch, frames, ms, ms * 1e6 / steps))
+for i, nm in enumerate(names):
+    if cyc[:, i].max() > 0:
+        print("  %-10s busy %7.1f cycles/step (mean over workgroups; max %.1f)" % (nm, cyc[:, i].mean() / steps, cyc[:, i].max() / steps))
