@@ -222,65 +222,44 @@ int open_device(gvtm_plan* plan, int device)
 	return GVTM_OK;
 }
 
-// The device tables of a plan of the models 0 and 1: one wavetable and one constants block per voice, back to back (the
-// glottal FIR and the converter's tables depend on no configuration key: voice 0's serve all)
+// The device tables of a plan: one constants block per voice (model 5: one of each kind), back to back, and the
+// converter's tables, which depend on no configuration key: voice 0's serve all.  The other models add one wavetable per
+// voice and the glottal FIR (voice 0's, for the same reason).  A float plan (GVTM_PRECISION_F32, either model) uploads
+// the tables as designed in float.
 int upload_tables(gvtm_plan* plan)
 {
+	const gvtm::Design& dg = plan->designs[0];
 	std::vector<gvtm::DeviceConstants> consts;
+	std::vector<gvtm::Model5Constants> consts5;
 	std::vector<double> wavetables;
 	std::vector<float> wavetables_f;
 	for (const gvtm::Design& dv : plan->designs) {
 		consts.push_back(dv.k);
+		if (dg.model5) consts5.push_back(dv.k5);
 		wavetables.insert(wavetables.end(), dv.wavetable.begin(), dv.wavetable.end());
 		wavetables_f.insert(wavetables_f.end(), dv.wavetable_f.begin(), dv.wavetable_f.end());
 	}
-	const gvtm::Design& dg = plan->designs[0];
+	// the float or the double design of a table
+	auto upload_design = [&](DeviceBuffer& dst, const std::vector<double>& wide, const std::vector<float>& narrow) {
+		return dg.f32 ? upload(dst, narrow) : upload(dst, wide);
+	};
 	hipError_t e;
-	if (dg.f32) {
-		if ((e = upload(plan->d_wavetable, wavetables_f)) != hipSuccess) return fail_hip(e, "upload wavetable");
-		if ((e = upload(plan->d_fir, dg.fir_f)) != hipSuccess) return fail_hip(e, "upload fir");
-		if ((e = upload(plan->d_src_h, dg.src_h_f)) != hipSuccess) return fail_hip(e, "upload src_h");
-		if ((e = upload(plan->d_src_dh, dg.src_dh_f)) != hipSuccess) return fail_hip(e, "upload src_dh");
-	} else {
-		if ((e = upload(plan->d_wavetable, wavetables)) != hipSuccess) return fail_hip(e, "upload wavetable");
-		if ((e = upload(plan->d_fir, dg.fir)) != hipSuccess) return fail_hip(e, "upload fir");
-		if ((e = upload(plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
-		if ((e = upload(plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
+	if (!dg.model5) {
+		if ((e = upload_design(plan->d_wavetable, wavetables, wavetables_f)) != hipSuccess) return fail_hip(e, "upload wavetable");
+		if ((e = upload_design(plan->d_fir, dg.fir, dg.fir_f)) != hipSuccess) return fail_hip(e, "upload fir");
 	}
+	if ((e = upload_design(plan->d_src_h, dg.src_h, dg.src_h_f)) != hipSuccess) return fail_hip(e, "upload src_h");
+	if ((e = upload_design(plan->d_src_dh, dg.src_dh, dg.src_dh_f)) != hipSuccess) return fail_hip(e, "upload src_dh");
 	if ((e = upload(plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
+	if (dg.model5 && (e = upload(plan->d_consts5, consts5)) != hipSuccess) return fail_hip(e, "upload model 5 constants");
 	return GVTM_OK;
 }
 
-// Model 5's: one constants block of each kind per voice, back to back (the converter's tables depend on no configuration
-// key: voice 0's serve all)
-int upload_tables5(gvtm_plan* plan)
-{
-	std::vector<gvtm::DeviceConstants> consts;
-	std::vector<gvtm::Model5Constants> consts5;
-	for (const gvtm::Design& dv : plan->designs) {
-		consts.push_back(dv.k);
-		consts5.push_back(dv.k5);
-	}
-	const gvtm::Design& dg = plan->designs[0];
-	hipError_t e;
-	if (dg.f32) { // (the float class: its converter's tables as designed in float)
-		if ((e = upload(plan->d_src_h, dg.src_h_f)) != hipSuccess) return fail_hip(e, "upload src_h");
-		if ((e = upload(plan->d_src_dh, dg.src_dh_f)) != hipSuccess) return fail_hip(e, "upload src_dh");
-	} else {
-		if ((e = upload(plan->d_src_h, dg.src_h)) != hipSuccess) return fail_hip(e, "upload src_h");
-		if ((e = upload(plan->d_src_dh, dg.src_dh)) != hipSuccess) return fail_hip(e, "upload src_dh");
-	}
-	if ((e = upload(plan->d_consts, consts)) != hipSuccess) return fail_hip(e, "upload constants");
-	if ((e = upload(plan->d_consts5, consts5)) != hipSuccess) return fail_hip(e, "upload model 5 constants");
-	return GVTM_OK;
-}
-
-// Every plan: `differs` refuses a voice that does not share `shared_keys` with voice 0, `design` designs each voice, and
-// `upload` puts the tables on the device (gvtm_config: design_plan and upload_tables, gvtm5_config: design_plan5 and
-// upload_tables5)
+// Every plan: `differs` refuses a voice that does not share `shared_keys` with voice 0, `design` designs each voice
+// (gvtm_config: design_plan, gvtm5_config: design_plan5 or design_plan5_float), and upload_tables puts the tables on the device
 template <typename Config, typename Differs>
 int create_plan(const Config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out, const char* shared_keys,
-		Differs differs, std::string (*design)(const Config&, double, gvtm::Design&), int (*upload)(gvtm_plan*))
+		Differs differs, std::string (*design)(const Config&, double, gvtm::Design&))
 {
 	if (!configs || !plan_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null config or plan_out");
 	*plan_out = nullptr;
@@ -311,7 +290,7 @@ int create_plan(const Config* configs, size_t n_voices, double control_rate, int
 		DeviceScope scope(device);
 		hipError_t e = scope.status();
 		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-		if ((rc = upload(plan.get())) != GVTM_OK) return rc;
+		if ((rc = upload_tables(plan.get())) != GVTM_OK) return rc;
 		*plan_out = plan.release();
 		return GVTM_OK;
 	} catch (const std::bad_alloc&) {
@@ -381,7 +360,7 @@ int gvtm_plan_create_voices(const gvtm_config* configs, size_t n_voices, double 
 		return c.output_rate != c0.output_rate || c.section_delay != c0.section_delay || c.precision != c0.precision || c.tube_layout != c0.tube_layout;
 	};
 	return create_plan(configs, n_voices, control_rate, device, plan_out, "output_rate, section_delay, precision and tube_layout", differs,
-			gvtm::design_plan, upload_tables);
+			gvtm::design_plan);
 }
 
 int gvtm_plan_voice_count(const gvtm_plan* plan)
@@ -420,13 +399,13 @@ int gvtm_plan_create_model5(const gvtm5_config* config, double control_rate, int
 int gvtm_plan_create_model5_voices(const gvtm5_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
 {
 	auto differs = [](const gvtm5_config& c0, const gvtm5_config& c) { return c.output_rate != c0.output_rate || c.precision != c0.precision; };
-	return create_plan(configs, n_voices, control_rate, device, plan_out, "output_rate and precision", differs, gvtm::design_plan5, upload_tables5);
+	return create_plan(configs, n_voices, control_rate, device, plan_out, "output_rate and precision", differs, gvtm::design_plan5);
 }
 
 int gvtm_plan_create_model5_float(const gvtm5_config* config, double control_rate, int device, gvtm_plan** plan_out)
 {
 	auto differs = [](const gvtm5_config&, const gvtm5_config&) { return false; }; // (one voice)
-	return create_plan(config, 1, control_rate, device, plan_out, "", differs, gvtm::design_plan5_float, upload_tables5);
+	return create_plan(config, 1, control_rate, device, plan_out, "", differs, gvtm::design_plan5_float);
 }
 
 void gvtm_plan_destroy(gvtm_plan* plan)
@@ -916,7 +895,7 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 		if (rc != GVTM_OK) return rc;
 	}
 	return timed_launch(plan, stream, r.voices ? "vtm_synth_kernel launch (voices)" : "vtm_synth_kernel launch", [&] {
-		return model5 ? gvtm::launch_synth5(args, work, plan->precision, rows, shape.variant, stream) : gvtm::launch_synth(args, work, plan->precision, rows, stream);
+		return model5 ? gvtm::launch_synth5(args, work, plan->precision, shape.forced - 1, stream) : gvtm::launch_synth(args, work, plan->precision, rows, stream);
 	});
 }
 
@@ -1190,10 +1169,8 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 
 	// the shape of the whole batch (every slice is launched in it), and how many utterances fill the machine once in it
 	// (the rows the batch size picks: a launch still gives way to fewer where the LDS does not hold them)
-	// (the float model 5's second shape -- one utterance per workgroup, two workgroups per compute unit -- goes by "rows 2")
 	const gvtm::LaunchShape shape_all = plan->launch_shape(batch, 0, false, 0, false);
-	const int rows_all = shape_all.variant == 1 ? 2 : shape_all.rows;
-	const size_t machine = static_cast<size_t>(rows_all) * static_cast<size_t>(plan->compute_units > 0 ? plan->compute_units : 256);
+	const size_t machine = static_cast<size_t>(shape_all.per_cu) * static_cast<size_t>(plan->compute_units > 0 ? plan->compute_units : 256);
 	const size_t slice = batch >= 2 * machine ? machine : batch;
 	const size_t n_slices = (batch + slice - 1) / slice;
 	while (plan->slice_done.size() < 2 * n_slices) {
@@ -1221,7 +1198,7 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 			rc = fail_hip(e, "hipMemsetAsync"); break;
 		}
 		rc = launch_synthesis(plan, LaunchRequest{d_params + lo * row_in, d_frames ? d_frames + lo : nullptr, n, max_frames, d_audio + lo * audio_stride,
-				audio_stride, d_counts + lo, d_maxabs + lo, compute_stream, rows_all, voices, voices ? d_voice_ids + lo : nullptr, &sc.groups});
+				audio_stride, d_counts + lo, d_maxabs + lo, compute_stream, shape_all.forced, voices, voices ? d_voice_ids + lo : nullptr, &sc.groups});
 		if (rc != GVTM_OK) break;
 		if (j.pcm) {
 			// (normalize takes at most 65535 utterances per launch: a slice is far below that unless the batch is one slice)

@@ -378,202 +378,61 @@ void design_noise_table(size_t n, bool as_float, void* out)
 	}
 }
 
-void radiation_impedance(double radius, double period, double out[6])
+namespace {
+
+// PoleZeroRadiationImpedance<T>::update (vtm/PoleZeroRadiationImpedance.h:139-177), every operation in T
+template <typename T>
+void radiation_impedance_t(T radius, T period, double out[6])
 {
-	const double transition = 0.5e-2;
-	const double rr = radius < transition ? transition : radius;
-	const double trans_freq = 62.3371 / rr + 320.204;
-	const double cos_wt = std::cos((2.0 * kPi) * trans_freq * period);
-	const double qa = 2.0 * cos_wt;
-	const double qb = -2.0 * (cos_wt + 1.0);
-	const double qc = cos_wt + 1.0;
-	const double delta = qb * qb - 4.0 * qa * qc;
-	double a = (-qb - std::sqrt(delta)) / (2.0 * qa);
-	const double b = 2.0 * a - 1.0;
-	if (radius < transition) a *= 40391.2 * (radius * radius);
-	const double coef = 1.0 / (a + 1.0);
-	const double a_plus_b = a + b;
+	const T transition = T(0.5e-2);
+	const T rr = radius < transition ? transition : radius;
+	const T trans_freq = T(62.3371) / rr + T(320.204);
+	const T cos_wt = std::cos(T(2.0 * kPi) * trans_freq * period);
+	const T qa = T(2) * cos_wt;
+	const T qb = T(-2) * (cos_wt + T(1));
+	const T qc = cos_wt + T(1);
+	const T delta = qb * qb - T(4) * qa * qc;
+	T a = (-qb - std::sqrt(delta)) / (T(2) * qa);
+	const T b = T(2) * a - T(1);
+	if (radius < transition) a *= T(40391.2) * (radius * radius);
+	const T coef = T(1) / (a + T(1));
+	const T a_plus_b = a + b;
 	out[0] = a_plus_b * coef;
-	out[1] = 2.0 * coef;
-	out[2] = -2.0 * b * coef;
+	out[1] = T(2) * coef;
+	out[2] = T(-2) * b * coef;
 	out[3] = a_plus_b * coef;
-	out[4] = (a - 1.0) * coef;
+	out[4] = (a - T(1)) * coef;
 	out[5] = (b - a) * coef;
 }
 
-// VocalTractModel5: loadConfiguration (vtm/VocalTractModel5.h:375-421) and initializeSynthesizer (:455-521)
-// with TFloat = double, the checks its constructors make included.
-std::string design_plan5(const gvtm5_config& c, double control_rate, Design& out)
+// VocalTractModel5: loadConfiguration (vtm/VocalTractModel5.h:375-421) and initializeSynthesizer (:455-521), the checks
+// its constructors make included, for both of its classes: T = double is VocalTractModel5<double,1>, T = float
+// VocalTractModel5<float,1> (the class the factory has no number for).  With T = float every derived number is computed
+// in float with the machine's tanf / sqrtf / powf / cosf, as the class does on the host, and carried in the double fields
+// of DeviceConstants / Model5Constants (exact), which the float kernel narrows back.
+template <typename T>
+std::string design_plan5_t(const gvtm5_config& c, double control_rate, Design& out)
 {
+	constexpr bool kFloat = sizeof(T) == sizeof(float);
 	std::ostringstream err;
 	auto finite_pos = [](double v) { return std::isfinite(v) && v > 0.0; };
 	if (!finite_pos(c.output_rate)) return "output_rate must be > 0";
 	if (!finite_pos(control_rate)) return "control_rate must be > 0";
-	if (c.precision != GVTM_PRECISION_F64) return "model 5 computes in fp64 only (VocalTractModel5<double,1>)";
-	if (c.reserved_ != 0) return "reserved_ must be 0";
-	if (c.waveform != 0 && c.waveform != 1) return "waveform must be 0 (pulse) or 1 (sine)";
-	if (!(c.temperature > -273.0) || !std::isfinite(c.temperature)) return "temperature out of range";
-
-	out.model5 = true;
-	out.config5 = c;
-	out.config = gvtm_config{};
-	out.config.output_rate = c.output_rate;
-	out.control_rate = control_rate;
-	out.f32 = false;
-	DeviceConstants& k = out.k;
-	Model5Constants& m = out.k5;
-	k = DeviceConstants{};
-	m = Model5Constants{};
-	k.section_delay = 1;
-	k.layout = 2;
-	k.waveform = c.waveform;
-	k.modulation = c.noise_modulation != 0;
-	m.bypass = c.bypass == 1;
-	m.constant_mouth = c.constant_radius_mouth_impedance != 0;
-	m.output_rate = c.output_rate;
-
-	double length = c.vocal_tract_length_offset + c.vocal_tract_length;
-	length = std::min(std::max(length, 3.0), 30.0);
-	double nasal[7] = {0.0};
-	for (int i = 0; i < 6; ++i) {
-		nasal[i + 1] = c.nasal_radius[i] * c.global_nasal_radius_coef;
-		if (!finite_pos(nasal[i + 1])) return "nasal radii must be > 0";
-	}
-	for (int i = 0; i < 8; ++i) k.radius_coef[i] = c.radius_coef[i] * c.global_radius_coef;
-
-	const double speed = 331.4 + (0.6 * c.temperature);
-	m.sample_rate = (speed * (30 * 1) * 100.0f) / length;
-	// PoleZeroRadiationImpedance's constructor (vtm/PoleZeroRadiationImpedance.h:116-119)
-	if (!(m.sample_rate >= 50000.0)) return "model 5 needs an internal rate of at least 50 kHz (vocal tract too long / too cold)";
-	k.sample_rate = static_cast<int>(m.sample_rate);
-	k.breathiness = c.breathiness / 100.0f;
-	const double mix_amp = amplitude_60db_t<double>(c.mix_offset);
-	if (!(mix_amp > 0.0)) return "mix_offset must be > 0 dB";
-	k.crossmix_factor = 1.0f / mix_amp;
-	k.damping = 1.0f - (c.loss_factor / 100.0f);
-
-	// RosenbergBGlottalSource's constructor (vtm/RosenbergBGlottalSource.h:66-96)
-	m.rb_tn_min = c.glottal_pulse_tn_min / 100.0f;
-	m.rb_tn_max = c.glottal_pulse_tn_max / 100.0f;
-	m.rb_t1 = c.glottal_pulse_tp / 100.0f;
-	if (!(m.rb_t1 >= 1.0e-2) || !(m.rb_tn_min >= 1.0e-2) || !(m.rb_tn_max >= 1.0e-2) || m.rb_tn_min > m.rb_tn_max ||
-			m.rb_t1 + m.rb_tn_max > 1.0) {
-		return "glottal pulse shape needs tp, tn_min, tn_max >= 1 %, tn_min <= tn_max, tp + tn_max <= 100";
-	}
-
-	m.period = 1.0f / m.sample_rate;
-	if (m.constant_mouth) radiation_impedance(c.mouth_impedance_radius * 1.0e-2f, m.period, m.mouth_c);
-	// initializeNasalCavity (vtm/VocalTractModel5.h:593-603)
-	for (int i = 1; i < 6; ++i) m.nasal_k[i] = junction<double>(nasal[i], nasal[i + 1]);
-	radiation_impedance(std::sqrt(0.5f * nasal[6] * nasal[6]) * 1.0e-2f, m.period, m.nose_c);
-	m.nasal_r1_sq = nasal[1] * nasal[1];
-
-	// Butterworth filters (their update() range checks included)
-	auto butter_ok = [&](double cutoff) { return cutoff >= 1.0 && cutoff <= m.sample_rate * 0.48; };
-	if (!butter_ok(c.glottal_noise_cutoff) || !butter_ok(c.frication_noise_cutoff) || !butter_ok(c.glottal_lowpass_cutoff)) {
-		return "Butterworth cutoffs must lie between 1 Hz and 0.48 of the internal rate";
-	}
-	auto butter1 = [&](double cutoff, double& b0, double& a1) {
-		const double wcT = 2.0 * std::tan(kPi * cutoff / m.sample_rate);
-		const double c1 = 1.0 / (wcT + 2.0);
-		b0 = c1 * wcT;
-		a1 = c1 * (wcT - 2.0);
-	};
-	butter1(c.glottal_noise_cutoff, m.gn_b0, m.gn_a1);
-	butter1(c.glottal_lowpass_cutoff, m.gp_b0, m.gp_a1);
-	{
-		const double wcT = 2.0 * std::tan(kPi * c.frication_noise_cutoff / m.sample_rate);
-		const double wc2T2 = wcT * wcT;
-		const double c1 = 2.0 * std::sqrt(2.0) * wcT;
-		const double c2 = 1.0 / (wc2T2 + c1 + 4.0);
-		m.fn_b0 = c2 * wc2T2;
-		m.fn_b1 = 2.0 * m.fn_b0;
-		m.fn_a1 = c2 * (2.0 * wc2T2 - 8.0);
-		m.fn_a2 = c2 * (wc2T2 - c1 + 4.0);
-	}
-	m.frication_factor = c.frication_factor;
-	m.min_loss = c.min_glottal_loss / 100.0f;
-	m.max_loss = c.max_glottal_loss / 100.0f;
-	k.bp_T = 1.0 / m.sample_rate; // BandpassFilter::update (BandpassFilter.h:104)
-
-	// Controller::synthesize (vtm_control_model/Controller.cpp:286-287)
-	k.control_steps = static_cast<unsigned>(std::rint(m.sample_rate / control_rate));
-	if (k.control_steps == 0) return "control_rate above the internal sample rate";
-	k.interp_coef = 1.0f / k.control_steps;
-
-	// SampleRateConverter::initializeConversion (vtm/SampleRateConverter.h:136-164)
-	const double ratio = c.output_rate / m.sample_rate;
-	k.src_ratio = ratio;
-	k.time_inc = static_cast<unsigned>(std::rint(std::pow(2.0, 16) / ratio));
-	if (k.time_inc == 0) return "output_rate too high for the 16.16 time register";
-	const double rounded_ratio = std::pow(2.0, 16) / k.time_inc;
-	k.upsampling = ratio >= 1.0;
-	if (k.upsampling) {
-		k.phase_inc = 0;
-		k.pad = kSrcZeroCrossings;
+	if constexpr (kFloat) {
+		if (c.precision != GVTM_PRECISION_F32) return "the float model 5 computes in fp32 only (VocalTractModel5<float,1>)";
 	} else {
-		k.phase_inc = static_cast<unsigned>(std::rint(ratio * 65536));
-		k.pad = static_cast<int>(kSrcZeroCrossings / rounded_ratio) + 1;
+		if (c.precision != GVTM_PRECISION_F64) return "model 5 computes in fp64 only (VocalTractModel5<double,1>)";
 	}
-	if (k.pad > kMaxPad || (k.phase_inc == 0 && !k.upsampling)) {
-		err << "output_rate / internal rate = " << ratio << " is below the supported down-sampling range";
-		return err.str();
-	}
-	// the model 5 kernel parks converted samples in a 512-entry ring until the difference filter has emitted them in
-	// aligned blocks: two chunks of 60 steps must fit beside the held-back block
-	if (ratio > 3.0) return "output_rate above 3x the internal rate is not supported by the model 5 path";
-	design_src_filter<double>(out.src_h, out.src_dh);
-	out.fir.clear();
-	out.wavetable.clear();
-	return "";
-}
-
-// PoleZeroRadiationImpedance<float>::update: radiation_impedance() with every operation in float
-static void radiation_impedance_float(float radius, float period, double out[6])
-{
-	const float transition = static_cast<float>(0.5e-2);
-	const float rr = radius < transition ? transition : radius;
-	const float trans_freq = static_cast<float>(62.3371) / rr + static_cast<float>(320.204);
-	const float cos_wt = std::cos(static_cast<float>(2.0 * kPi) * trans_freq * period);
-	const float qa = 2.0f * cos_wt;
-	const float qb = -2.0f * (cos_wt + 1.0f);
-	const float qc = cos_wt + 1.0f;
-	const float delta = qb * qb - 4.0f * qa * qc;
-	float a = (-qb - std::sqrt(delta)) / (2.0f * qa);
-	const float b = 2.0f * a - 1.0f;
-	if (radius < transition) a *= static_cast<float>(40391.2) * (radius * radius);
-	const float coef = 1.0f / (a + 1.0f);
-	const float a_plus_b = a + b;
-	out[0] = a_plus_b * coef;
-	out[1] = 2.0f * coef;
-	out[2] = -2.0f * b * coef;
-	out[3] = a_plus_b * coef;
-	out[4] = (a - 1.0f) * coef;
-	out[5] = (b - a) * coef;
-}
-
-// The same constructors with TFloat = float (VocalTractModel5<float,1>, the class the factory has no number for): every
-// derived number is computed in float with the machine's tanf / sqrtf / powf / cosf, as the class does on the host, and
-// carried in the double fields of DeviceConstants / Model5Constants (exact), which the float kernel narrows back.
-std::string design_plan5_float(const gvtm5_config& c, double control_rate, Design& out)
-{
-	std::ostringstream err;
-	auto finite_pos = [](double v) { return std::isfinite(v) && v > 0.0; };
-	if (!finite_pos(c.output_rate)) return "output_rate must be > 0";
-	if (!finite_pos(control_rate)) return "control_rate must be > 0";
-	if (c.precision != GVTM_PRECISION_F32) return "the float model 5 computes in fp32 only (VocalTractModel5<float,1>)";
 	if (c.reserved_ != 0) return "reserved_ must be 0";
 	if (c.waveform != 0 && c.waveform != 1) return "waveform must be 0 (pulse) or 1 (sine)";
 	if (!(c.temperature > -273.0) || !std::isfinite(c.temperature)) return "temperature out of range";
 
-	using T = float;
-	auto f = [](double v) { return static_cast<T>(v); };
 	out.model5 = true;
 	out.config5 = c;
 	out.config = gvtm_config{};
 	out.config.output_rate = c.output_rate;
 	out.control_rate = control_rate;
-	out.f32 = true;
+	out.f32 = kFloat;
 	DeviceConstants& k = out.k;
 	Model5Constants& m = out.k5;
 	k = DeviceConstants{};
@@ -584,59 +443,65 @@ std::string design_plan5_float(const gvtm5_config& c, double control_rate, Desig
 	k.modulation = c.noise_modulation != 0;
 	m.bypass = c.bypass == 1;
 	m.constant_mouth = c.constant_radius_mouth_impedance != 0;
-	const T output_rate = f(c.output_rate);
+	const T output_rate = static_cast<T>(c.output_rate);
 	m.output_rate = output_rate;
 
-	T length = f(c.vocal_tract_length_offset) + f(c.vocal_tract_length);
+	T length = static_cast<T>(c.vocal_tract_length_offset) + static_cast<T>(c.vocal_tract_length);
 	length = std::min(std::max(length, T(3)), T(30));
 	T nasal[7] = {T(0)};
 	for (int i = 0; i < 6; ++i) {
-		nasal[i + 1] = f(c.nasal_radius[i]) * f(c.global_nasal_radius_coef);
+		nasal[i + 1] = static_cast<T>(c.nasal_radius[i]) * static_cast<T>(c.global_nasal_radius_coef);
 		if (!finite_pos(nasal[i + 1])) return "nasal radii must be > 0";
 	}
-	for (int i = 0; i < 8; ++i) k.radius_coef[i] = f(c.radius_coef[i]) * f(c.global_radius_coef);
+	for (int i = 0; i < 8; ++i) k.radius_coef[i] = static_cast<T>(c.radius_coef[i]) * static_cast<T>(c.global_radius_coef);
 
-	const T speed = f(331.4) + (f(0.6) * f(c.temperature));
-	const T sample_rate = (speed * (30 * 1) * T(100)) / length;
+	const T speed = T(331.4) + (T(0.6) * static_cast<T>(c.temperature));
+	const T sample_rate = (speed * (30 * 1) * 100.0f) / length;
 	m.sample_rate = sample_rate;
+	// PoleZeroRadiationImpedance's constructor (vtm/PoleZeroRadiationImpedance.h:116-119)
 	if (!(sample_rate >= T(50000))) return "model 5 needs an internal rate of at least 50 kHz (vocal tract too long / too cold)";
 	k.sample_rate = static_cast<int>(sample_rate);
-	k.breathiness = f(c.breathiness) / T(100);
-	const T mix_amp = amplitude_60db_t<T>(f(c.mix_offset));
+	k.breathiness = static_cast<T>(c.breathiness) / 100.0f;
+	const T mix_amp = amplitude_60db_t<T>(static_cast<T>(c.mix_offset));
 	if (!(mix_amp > T(0))) return "mix_offset must be > 0 dB";
-	k.crossmix_factor = T(1) / mix_amp;
-	k.damping = T(1) - (f(c.loss_factor) / T(100));
+	k.crossmix_factor = 1.0f / mix_amp;
+	k.damping = 1.0f - (static_cast<T>(c.loss_factor) / 100.0f);
 
-	const T tn_min = f(c.glottal_pulse_tn_min) / T(100), tn_max = f(c.glottal_pulse_tn_max) / T(100), t1 = f(c.glottal_pulse_tp) / T(100);
+	// RosenbergBGlottalSource's constructor (vtm/RosenbergBGlottalSource.h:66-96)
+	const T tn_min = static_cast<T>(c.glottal_pulse_tn_min) / 100.0f, tn_max = static_cast<T>(c.glottal_pulse_tn_max) / 100.0f,
+			t1 = static_cast<T>(c.glottal_pulse_tp) / 100.0f;
 	m.rb_tn_min = tn_min;
 	m.rb_tn_max = tn_max;
 	m.rb_t1 = t1;
-	if (!(t1 >= f(1.0e-2)) || !(tn_min >= f(1.0e-2)) || !(tn_max >= f(1.0e-2)) || tn_min > tn_max || t1 + tn_max > T(1)) {
+	if (!(t1 >= T(1.0e-2)) || !(tn_min >= T(1.0e-2)) || !(tn_max >= T(1.0e-2)) || tn_min > tn_max || t1 + tn_max > T(1)) {
 		return "glottal pulse shape needs tp, tn_min, tn_max >= 1 %, tn_min <= tn_max, tp + tn_max <= 100";
 	}
 
-	const T period = T(1) / sample_rate;
+	const T period = 1.0f / sample_rate;
 	m.period = period;
-	if (m.constant_mouth) radiation_impedance_float(f(c.mouth_impedance_radius) * 1.0e-2f, period, m.mouth_c);
+	if (m.constant_mouth) radiation_impedance_t<T>(static_cast<T>(c.mouth_impedance_radius) * 1.0e-2f, period, m.mouth_c);
+	// initializeNasalCavity (vtm/VocalTractModel5.h:593-603)
 	for (int i = 1; i < 6; ++i) m.nasal_k[i] = junction<T>(nasal[i], nasal[i + 1]);
-	radiation_impedance_float(std::sqrt(T(0.5) * nasal[6] * nasal[6]) * 1.0e-2f, period, m.nose_c);
+	radiation_impedance_t<T>(std::sqrt(0.5f * nasal[6] * nasal[6]) * 1.0e-2f, period, m.nose_c);
 	m.nasal_r1_sq = nasal[1] * nasal[1];
 
-	auto butter_ok = [&](T cutoff) { return cutoff >= T(1) && cutoff <= sample_rate * f(0.48); };
-	if (!butter_ok(f(c.glottal_noise_cutoff)) || !butter_ok(f(c.frication_noise_cutoff)) || !butter_ok(f(c.glottal_lowpass_cutoff))) {
+	// Butterworth filters (their update() range checks included)
+	auto butter_ok = [&](T cutoff) { return cutoff >= T(1) && cutoff <= sample_rate * T(0.48); };
+	if (!butter_ok(static_cast<T>(c.glottal_noise_cutoff)) || !butter_ok(static_cast<T>(c.frication_noise_cutoff)) ||
+			!butter_ok(static_cast<T>(c.glottal_lowpass_cutoff))) {
 		return "Butterworth cutoffs must lie between 1 Hz and 0.48 of the internal rate";
 	}
-	const T pi = f(kPi);
+	const T pi = T(kPi);
 	auto butter1 = [&](T cutoff, double& b0, double& a1) {
 		const T wcT = T(2) * std::tan(pi * cutoff / sample_rate);
 		const T c1 = T(1) / (wcT + T(2));
 		b0 = c1 * wcT;
 		a1 = c1 * (wcT - T(2));
 	};
-	butter1(f(c.glottal_noise_cutoff), m.gn_b0, m.gn_a1);
-	butter1(f(c.glottal_lowpass_cutoff), m.gp_b0, m.gp_a1);
+	butter1(static_cast<T>(c.glottal_noise_cutoff), m.gn_b0, m.gn_a1);
+	butter1(static_cast<T>(c.glottal_lowpass_cutoff), m.gp_b0, m.gp_a1);
 	{
-		const T wcT = T(2) * std::tan(pi * f(c.frication_noise_cutoff) / sample_rate);
+		const T wcT = T(2) * std::tan(pi * static_cast<T>(c.frication_noise_cutoff) / sample_rate);
 		const T wc2T2 = wcT * wcT;
 		const T c1 = T(2) * std::sqrt(T(2)) * wcT;
 		const T c2 = T(1) / (wc2T2 + c1 + T(4));
@@ -646,16 +511,17 @@ std::string design_plan5_float(const gvtm5_config& c, double control_rate, Desig
 		m.fn_a1 = c2 * (T(2) * wc2T2 - T(8));
 		m.fn_a2 = c2 * (wc2T2 - c1 + T(4));
 	}
-	m.frication_factor = f(c.frication_factor);
-	m.min_loss = f(c.min_glottal_loss) / T(100);
-	m.max_loss = f(c.max_glottal_loss) / T(100);
-	k.bp_T = T(1) / sample_rate;
+	m.frication_factor = static_cast<T>(c.frication_factor);
+	m.min_loss = static_cast<T>(c.min_glottal_loss) / 100.0f;
+	m.max_loss = static_cast<T>(c.max_glottal_loss) / 100.0f;
+	k.bp_T = T(1) / sample_rate; // BandpassFilter::update (BandpassFilter.h:104)
 
+	// Controller::synthesize (vtm_control_model/Controller.cpp:286-287)
 	k.control_steps = static_cast<unsigned>(std::rint(static_cast<double>(sample_rate) / control_rate));
 	if (k.control_steps == 0) return "control_rate above the internal sample rate";
 	k.interp_coef = 1.0f / k.control_steps;
 
-	// SampleRateConverter<float>::initializeConversion, as design_numbers<float> has it
+	// SampleRateConverter::initializeConversion (vtm/SampleRateConverter.h:136-164), as design_numbers<T> has it
 	const T ratio = output_rate / sample_rate;
 	k.src_ratio = ratio;
 	k.time_inc = static_cast<unsigned>(std::rint(std::pow(2.0, 16) / ratio)); // double arithmetic (:145)
@@ -673,13 +539,36 @@ std::string design_plan5_float(const gvtm5_config& c, double control_rate, Desig
 		err << "output_rate / internal rate = " << static_cast<double>(ratio) << " is below the supported down-sampling range";
 		return err.str();
 	}
+	// the model 5 kernel parks converted samples in a 512-entry ring until the difference filter has emitted them in
+	// aligned blocks: two chunks of 60 steps must fit beside the held-back block
 	if (ratio > T(3)) return "output_rate above 3x the internal rate is not supported by the model 5 path";
-	design_src_filter<float>(out.src_h_f, out.src_dh_f);
-	out.src_h.assign(out.src_h_f.begin(), out.src_h_f.end());
-	out.src_dh.assign(out.src_dh_f.begin(), out.src_dh_f.end());
+	if constexpr (kFloat) {
+		design_src_filter<float>(out.src_h_f, out.src_dh_f);
+		out.src_h.assign(out.src_h_f.begin(), out.src_h_f.end());
+		out.src_dh.assign(out.src_dh_f.begin(), out.src_dh_f.end());
+	} else {
+		design_src_filter<double>(out.src_h, out.src_dh);
+	}
 	out.fir.clear();
 	out.wavetable.clear();
 	return "";
+}
+
+} // namespace
+
+std::string design_plan5(const gvtm5_config& c, double control_rate, Design& out)
+{
+	return design_plan5_t<double>(c, control_rate, out);
+}
+
+std::string design_plan5_float(const gvtm5_config& c, double control_rate, Design& out)
+{
+	return design_plan5_t<float>(c, control_rate, out);
+}
+
+void radiation_impedance(double radius, double period, double out[6])
+{
+	radiation_impedance_t<double>(radius, period, out);
 }
 
 // --- parameter-track generation (vtm_tracks.hip) -----------------------------------------------------

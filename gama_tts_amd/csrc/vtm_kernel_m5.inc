@@ -3,7 +3,7 @@
 // by three translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
 // (kVoices5Flag) and vtm_kernels_m5f.hip the float class, VocalTractModel5<float,1> (kFloat5Flag), each in a code object of
 // its own.  Besides the kernel, the file defines what they launch it with: the description of its shapes (m5_shape,
-// m5_float_shape, kM5Ring), before the kernel, and launch_synth5_shape / launch_synth5_float_shape, at the end.
+// kM5Ring), before the kernel, and the LDS bytes and the launch of a shape (m5_lds_bytes, launch_synth5_shape), at the end.
 //
 // Same organisation as generation 2: a workgroup owns U utterances (1 or 2; the tube has 30 + 21 = 51 sections, one
 // per lane of a wavefront, so every utterance has a tube wavefront of its own, while the scan, filter and interpolation
@@ -37,24 +37,22 @@
 //   tick c+12  H    P6(c)  sample-rate conversion, one lane per output sample                             -> y ring (float)
 //   tick c+13  H    P7(c)  difference filter * output rate (VocalTractModel5.h:507-513)                    -> HBM, peak
 
-// The kernel's two shapes.  One utterance per workgroup: chunk of 60 steps (one 64-lane pass per per-step stage), three
-// helper wavefronts.  Two utterances per workgroup (batches beyond one workgroup per compute unit): two tube wavefronts,
-// chunk of 24 steps (2 x 24 items per per-step pass; what LDS holds with two 62-entry tube records per step), five helpers.
-// Wavefronts: I, S and F, a tube wavefront per utterance, the helpers.
-// The float class (VocalTractModel5<float,1>, kFloat5Flag below) has one utterance per workgroup and two shapes, measured
-// against each other in DESIGN.md 4b (profiles/r08_bench_model5_float.json).  Variant 0, chunk 60 with three helpers, is
+// The kernel's four shapes, two per class, by (class, index); synth_launch_shape picks the index.
+// The double class.  Index 0, one utterance per workgroup: chunk of 60 steps (one 64-lane pass per per-step stage), three
+// helper wavefronts.  Index 1, two utterances per workgroup (batches beyond one workgroup per compute unit): two tube
+// wavefronts, chunk of 24 steps (2 x 24 items per per-step pass; what LDS holds with two 62-entry tube records per step),
+// five helpers.  Wavefronts: I, S and F, a tube wavefront per utterance, the helpers.
+// The float class (VocalTractModel5<float,1>, kFloat5Flag below) has one utterance per workgroup in both, measured
+// against each other in DESIGN.md 4b (profiles/r08_bench_model5_float.json).  Index 0, chunk 60 with three helpers, is
 // the double shape with every record halved (84 992 B of LDS): one workgroup per compute unit, the longest chunk.
-// Variant 1, chunk 56 with three helpers, is the longest chunk whose workgroup stays at or below 80 KB (80 800 B), so
-// that two workgroups share a compute unit.  synth_launch_shape picks between them by batch size.
-struct M5Shape { int rows, chunk, helpers, waves; };
+// Index 1, chunk 56 with three helpers, is the longest chunk whose workgroup stays at or below 80 KB (80 800 B), so
+// that two workgroups share a compute unit.
+struct M5Shape { int rows, chunk, helpers, waves, groups_per_cu; }; // groups_per_cu: workgroups a compute unit holds at once
 constexpr int m5_waves(int rows, int helpers) { return 3 + rows + helpers; }
-constexpr M5Shape m5_shape(int rows)
+constexpr M5Shape m5_shape(bool float_class, int index)
 {
-	return rows == 2 ? M5Shape{2, 24, 5, m5_waves(2, 5)} : M5Shape{1, 60, 3, m5_waves(1, 3)};
-}
-constexpr M5Shape m5_float_shape(int variant)
-{
-	return variant == 1 ? M5Shape{1, 56, 3, m5_waves(1, 3)} : M5Shape{1, 60, 3, m5_waves(1, 3)};
+	if (float_class) return index == 1 ? M5Shape{1, 56, 3, m5_waves(1, 3), 2} : M5Shape{1, 60, 3, m5_waves(1, 3), 1};
+	return index == 1 ? M5Shape{2, 24, 5, m5_waves(2, 5), 1} : M5Shape{1, 60, 3, m5_waves(1, 3), 1};
 }
 constexpr int kM5Ring = kSrcRing; // the reference's BUFFER_SIZE: see the flush-overrun epilogue
 
@@ -151,10 +149,17 @@ constexpr int kFloat5Flag = 8;
 __device__ __forceinline__ double sin_m5(double t) { return sin(t); }
 __device__ __forceinline__ float sin_m5(float t) { return vmath::sinf_glibc(t); } // std::sin(float), RosenbergBGlottalSource.h:139
 
-// wavefronts per SIMD a shape is compiled for: the float class's 80 KB shape must leave room for a second workgroup (7 + 7
-// wavefronts: four on a SIMD, 128 registers each); every other shape gets what its workgroup size implies (a request
-// below that is no request)
-constexpr int m5_waves_per_simd(int chunk, int u_flags) { return (u_flags & kFloat5Flag) != 0 && chunk == m5_float_shape(1).chunk ? 4 : 1; }
+// wavefronts per SIMD a shape is compiled for: a shape of which a compute unit holds two workgroups (the float class's
+// 80 KB shape) must leave room for the second (7 + 7 wavefronts: four on a SIMD, 128 registers each); every other shape
+// gets what its workgroup size implies (a request below that is no request)
+constexpr int m5_waves_per_simd(int chunk, int u_flags)
+{
+	for (int index = 0; index < 2; ++index) {
+		const M5Shape s = m5_shape((u_flags & kFloat5Flag) != 0, index);
+		if (s.chunk == chunk && s.groups_per_cu > 1) return (s.groups_per_cu * s.waves + 3) / 4;
+	}
+	return 1;
+}
 
 template <int C, int NH, int XR, int U_FLAGS>
 __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C, U_FLAGS)) void vtm5_synth_kernel(const SynthArgs a)
@@ -1246,43 +1251,25 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 
 } // namespace m5
 
-// LDS bytes of a workgroup of U utterances
-template <int U>
+// LDS bytes of a workgroup of shape (FLOAT, INDEX)
+template <bool FLOAT, int INDEX>
 static size_t m5_lds_bytes()
 {
-	return m5::Offsets<m5_shape(U).chunk, kM5Ring, U>().total;
+	constexpr M5Shape s = m5_shape(FLOAT, INDEX);
+	return m5::Offsets<s.chunk, kM5Ring, s.rows, std::conditional_t<FLOAT, float, double>>().total;
 }
 
-// the same for the float class's shape `VARIANT`
-template <int VARIANT>
-static size_t m5_float_lds_bytes()
-{
-	return m5::Offsets<m5_float_shape(VARIANT).chunk, kM5Ring, 1, float>().total;
-}
-
-// VOICES: a launch of several voices (the kernel's kVoices5Flag; args.row_map is set), one utterance per workgroup only;
-// `batch` is then the number of workgroups
-template <int U, bool VOICES>
+// The launch of shape (FLOAT, INDEX).  VOICES: a launch of several voices (the kernel's kVoices5Flag; args.row_map is
+// set), the double class's one-utterance shape only; `batch` is then the number of workgroups
+template <bool FLOAT, int INDEX, bool VOICES = false>
 static hipError_t launch_synth5_shape(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
-	static_assert(!VOICES || U == 1, "the voice variant has the one-utterance shape only");
-	constexpr M5Shape s = m5_shape(U);
-	auto fn = m5::vtm5_synth_kernel<s.chunk, s.helpers, kM5Ring, U | (VOICES ? m5::kVoices5Flag : 0)>;
-	const size_t lds = m5_lds_bytes<U>();
+	constexpr M5Shape s = m5_shape(FLOAT, INDEX);
+	static_assert(!VOICES || (s.rows == 1 && !FLOAT), "the voice variant has the double class's one-utterance shape only");
+	auto fn = m5::vtm5_synth_kernel<s.chunk, s.helpers, kM5Ring, s.rows | (VOICES ? m5::kVoices5Flag : 0) | (FLOAT ? m5::kFloat5Flag : 0)>;
+	const size_t lds = m5_lds_bytes<FLOAT, INDEX>();
 	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
 	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(VOICES ? batch : (batch + U - 1) / U)), dim3(s.waves * 64), lds, stream, args);
-	return hipGetLastError();
-}
-
-template <int VARIANT>
-static hipError_t launch_synth5_float_shape(const SynthArgs& args, size_t batch, hipStream_t stream)
-{
-	constexpr M5Shape s = m5_float_shape(VARIANT);
-	auto fn = m5::vtm5_synth_kernel<s.chunk, s.helpers, kM5Ring, 1 | m5::kFloat5Flag>;
-	const size_t lds = m5_float_lds_bytes<VARIANT>();
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-	if (e != hipSuccess) return e;
-	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(batch)), dim3(s.waves * 64), lds, stream, args);
+	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(VOICES ? batch : (batch + s.rows - 1) / s.rows)), dim3(s.waves * 64), lds, stream, args);
 	return hipGetLastError();
 }

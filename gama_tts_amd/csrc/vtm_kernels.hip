@@ -223,7 +223,7 @@ static LaunchShape shape_of_rows(const DeviceConstants& k, int precision, int ro
 	return with_shape(precision, rows, k.section_delay, k.layout, LaunchShape{}, [&](auto s) {
 		using S = decltype(s);
 		const int ring = xr > 0 ? xr : ring_length(k, S::C);
-		return LaunchShape{S::U, ring, S::lds_bytes(ring)};
+		return LaunchShape{S::U, ring, S::lds_bytes(ring), S::U, S::U};
 	});
 }
 
@@ -232,22 +232,22 @@ LaunchShape synth_launch_shape(const Design* voices, int n_voices, int precision
 {
 	const auto fits = [&](const LaunchShape& s) { return !fit || s.lds <= kLdsPerWorkgroup; };
 	if (voices[0].model5) {
-		// Model 5: one, whatever the batch: the two-utterance shape (two tube wavefronts, chunk of 24 steps -- what LDS
-		// holds of the 62-entry tube records) measured SLOWER at every batch size (batch 512 x 250 frames: 17.3 ms against
-		// 2 x 6.97 ms; profiles/r03_role_cycles_m5.txt): the passes are latency-bound, so a chunk of 24 steps costs what
-		// one of 60 does, and the tube wavefronts slow down from 268 to 430 cycles per step next to five busy helpers.  A
-		// diagnostics build can still force it (tests hold it to the one-utterance shape's samples bit for bit); the
-		// voice variant has the one-utterance shape only.
-		if (precision == GVTM_PRECISION_F32) {
-			// The float class (one utterance per workgroup, one voice): up to one workgroup per compute unit the chunk of 60
-			// steps; beyond, the chunk of 56, whose 80 800 B let two workgroups share a compute unit (DESIGN.md 4b has the
-			// measurement).  A diagnostics build forces either: rows 1 the first, rows 2 the second.
-			const int variant = forced_rows == 1 ? 0 : (forced_rows == 2 ? 1 : (batch > 256 ? 1 : 0));
-			const LaunchShape s{1, 0, synth5_float_lds_bytes(variant), variant};
-			return fits(s) ? s : LaunchShape{};
-		}
-		const int rows = forced_rows == 2 && !several_voices ? 2 : 1;
-		const LaunchShape s{rows, 0, rows == 2 ? m5_lds_bytes<2>() : m5_lds_bytes<1>()};
+		// Model 5: the index of the shape in its class (m5_shape, vtm_kernel_m5.inc); a diagnostics build forces either:
+		// forced_rows 1 the first, 2 the second.
+		// The double class: index 0 (one utterance per workgroup), whatever the batch: the two-utterance shape (two tube
+		// wavefronts, chunk of 24 steps -- what LDS holds of the 62-entry tube records) measured SLOWER at every batch size
+		// (batch 512 x 250 frames: 17.3 ms against 2 x 6.97 ms; profiles/r03_role_cycles_m5.txt): the passes are
+		// latency-bound, so a chunk of 24 steps costs what one of 60 does, and the tube wavefronts slow down from 268 to
+		// 430 cycles per step next to five busy helpers.  Only forcing picks it (tests hold it to the one-utterance shape's
+		// samples bit for bit), and not for the voice variant, which has the one-utterance shape only.
+		// The float class (one utterance per workgroup, one voice): up to one workgroup per compute unit the chunk of 60
+		// steps; beyond, the chunk of 56, whose 80 800 B let two workgroups share a compute unit (DESIGN.md 4b has the
+		// measurement).
+		const bool float_class = precision == GVTM_PRECISION_F32;
+		const int index = float_class ? (forced_rows == 1 ? 0 : (forced_rows == 2 || batch > 256 ? 1 : 0)) : (forced_rows == 2 && !several_voices ? 1 : 0);
+		const M5Shape m = m5_shape(float_class, index);
+		const size_t lds = float_class ? synth5_float_lds_bytes(index) : (index == 1 ? m5_lds_bytes<false, 1>() : m5_lds_bytes<false, 0>());
+		const LaunchShape s{m.rows, 0, lds, index + 1, m.rows * m.groups_per_cu};
 		return fits(s) ? s : LaunchShape{};
 	}
 	// utterances per workgroup = DPP rows used by the serial wavefronts.  One row keeps the most
@@ -332,17 +332,17 @@ hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream)
 	return hipGetLastError();
 }
 
-hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int rows, int variant, hipStream_t stream)
+hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int index, hipStream_t stream)
 {
-	if (!args.k5const) return hipErrorInvalidValue;
+	if (!args.k5const || (index != 0 && index != 1)) return hipErrorInvalidValue;
 	// (the float class lives in vtm_kernels_m5f.hip, as the voice variant does in vtm_kernels_m5v.hip)
-	if (precision == GVTM_PRECISION_F32) return rows == 1 ? launch_synth5_float(args, batch, variant, stream) : hipErrorInvalidValue;
+	if (precision == GVTM_PRECISION_F32) return launch_synth5_float(args, batch, index, stream);
 	// (the voice variant lives in vtm_kernels_m5v.hip: this file's code object keeps the single-voice kernels only)
 	if (!args.row_map) {
-		if (rows == 2) return launch_synth5_shape<2, false>(args, batch, stream);
-		return launch_synth5_shape<1, false>(args, batch, stream);
+		if (index == 1) return launch_synth5_shape<false, 1>(args, batch, stream);
+		return launch_synth5_shape<false, 0>(args, batch, stream);
 	}
-	if (!args.group_voice || rows != 1) return hipErrorInvalidValue;
+	if (!args.group_voice || index != 0) return hipErrorInvalidValue;
 	return launch_synth5_voices(args, batch, stream);
 }
 

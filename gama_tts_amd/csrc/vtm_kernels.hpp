@@ -131,12 +131,14 @@ struct LaunchShape {
 	int rows = 0;
 	int ring = 0;
 	size_t lds = 0;
-	int variant = 0; // the float model 5 only: 0 chunk 60, 1 chunk 56 (two workgroups per compute unit); vtm_kernel_m5.inc
+	int forced = 0; // what names this shape again as synth_launch_shape's forced_rows: the rows; model 5 (either class): 1 + its shape's index
+	int per_cu = 0; // utterances one compute unit holds in this shape: rows x the workgroups it holds at once (model 5's float class: up to 2)
 };
 constexpr size_t kLdsPerWorkgroup = 160 * 1024;
 // THE row choice, for every caller.  voices: the plan's designs (voices[0] says whether model 5); forced_rows: 1, 2, 4 or 8
-// (model 5: 2) names the rows, anything else leaves them to `batch`; several_voices: the kernel's voice variant (at most
-// 4 rows, model 5: 1); stream_ring: a stream's fixed ring, or 0 for the longest own ring of the voices (the reference's
+// names the rows (model 5: 1 or 2 name the shape of index 0 or 1 of its class, vtm_kernel_m5.inc: two utterances per
+// workgroup in the double class, the chunk of 56 steps in the float class), anything else leaves them to `batch`;
+// several_voices: the kernel's voice variant (at most 4 rows, model 5: 1); stream_ring: a stream's fixed ring, or 0 for the longest own ring of the voices (the reference's
 // BUFFER_SIZE (1024) when down-sampling, so that the flush overrun aliases as the reference's ring does; otherwise the
 // smallest power of two holding two chunks, the resampler's history and the flush zeros).  With `fit`, rows whose LDS
 // exceeds kLdsPerWorkgroup give way to half as many (not model 5) or to "none fits"; without, they stay whatever their LDS.
@@ -152,14 +154,13 @@ hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int 
 size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr);
 // several voices: builds args.row_map / args.group_voice from the voice ids (one small workgroup, stable counting sort)
 hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream);
-// reference model 5: VocalTractModel5<double,1> (GVTM_PRECISION_F64), rows = utterances per workgroup, 1 or 2; with
-// args.row_map set (several voices: one constants block of each kind per voice) 1 only, and `batch` is the number of
-// workgroups.  GVTM_PRECISION_F32: VocalTractModel5<float,1>, one utterance per workgroup, one voice.
-// (`variant`: LaunchShape::variant, which of the float class's two shapes)
-hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int rows, int variant, hipStream_t stream);
-// the float class alone (vtm_kernels_m5f.hip; launch_synth5 calls it), and the LDS bytes of a workgroup of its shape `variant`
-hipError_t launch_synth5_float(const SynthArgs& args, size_t batch, int variant, hipStream_t stream);
-size_t synth5_float_lds_bytes(int variant);
+// reference model 5: VocalTractModel5<double,1> (GVTM_PRECISION_F64) or VocalTractModel5<float,1> (GVTM_PRECISION_F32) in
+// the shape `index` (0 or 1: LaunchShape::forced - 1) of that class; with args.row_map set (several voices: one constants
+// block of each kind per voice) the double class's index 0 only, and `batch` is the number of workgroups.
+hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int index, hipStream_t stream);
+// the float class alone (vtm_kernels_m5f.hip; launch_synth5 calls it), and the LDS bytes of a workgroup of its shape `index`
+hipError_t launch_synth5_float(const SynthArgs& args, size_t batch, int index, hipStream_t stream);
+size_t synth5_float_lds_bytes(int index);
 // the voice variant alone (vtm_kernels_m5v.hip; launch_synth5 calls it): `groups` workgroups of one utterance each
 hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_t stream);
 constexpr int kDppSelftestInts = 640;

@@ -20,16 +20,15 @@ namespace {
 #include "vtm_kernel_v2.inc"
 #include "vtm_kernel_m5.inc"
 
-size_t synth5_float_lds_bytes(int variant)
+size_t synth5_float_lds_bytes(int index)
 {
-	return variant == 1 ? m5_float_lds_bytes<1>() : m5_float_lds_bytes<0>();
+	return index == 1 ? m5_lds_bytes<true, 1>() : m5_lds_bytes<true, 0>();
 }
 
-hipError_t launch_synth5_float(const SynthArgs& args, size_t batch, int variant, hipStream_t stream)
+hipError_t launch_synth5_float(const SynthArgs& args, size_t batch, int index, hipStream_t stream)
 {
 	if (args.row_map || !args.k5const) return hipErrorInvalidValue; // (one voice per plan)
-	if (variant == 1) return launch_synth5_float_shape<1>(args, batch, stream);
-	return launch_synth5_float_shape<0>(args, batch, stream);
+	return index == 1 ? launch_synth5_shape<true, 1>(args, batch, stream) : launch_synth5_shape<true, 0>(args, batch, stream);
 }
 
 } // namespace gvtm

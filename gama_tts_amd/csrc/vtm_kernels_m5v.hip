@@ -21,7 +21,7 @@ namespace {
 
 hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_t stream)
 {
-	return launch_synth5_shape<1, true>(args, groups, stream);
+	return launch_synth5_shape<false, 0, true>(args, groups, stream);
 }
 
 } // namespace gvtm
