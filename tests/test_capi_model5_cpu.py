@@ -6,21 +6,16 @@ import pytest
 
 import gama_tts_amd as g
 from gama_tts_amd import capi
-import golden5_cases
+import model5_cases as cases
 import oracle
+from voice_cases import model5_plan
 
 
-def _plan(case):
-    d = g.read_config_file(oracle.VOICE5_MALE)
-    d.update({k: str(v) for k, v in case["overrides"].items()})
-    return g.Plan(g.config5_from_dict(d, case["rate"]), case["crate"], capi.DEVICE_NONE)
-
-
-@pytest.mark.parametrize("case", [c for c in golden5_cases.CASES if not c["float_model"]], ids=lambda c: c["name"])
+@pytest.mark.parametrize("case", cases.MALE_DOUBLE_CASES, ids=lambda c: c["name"])
 def test_design_matches_the_reference_vectors(case, golden, golden5):
     m = golden5["manifest"][case["name"]]
-    tr = golden5_cases.track_for(case, golden)
-    plan = _plan(case)
+    tr = cases.track_for(case, golden)
+    plan = model5_plan("male", case["overrides"], case["rate"], case["crate"], device=capi.DEVICE_NONE)
     i = plan.info
     assert i.model5 == 1 and i.precision == capi.PRECISION_F64
     assert abs(i.internal_rate_hz - m["fs"]) < 1e-9 and i.internal_sample_rate == int(m["fs"])

@@ -8,6 +8,7 @@ The cosine's pinned range is not widened: model 5 calls cos on 2 pi f T with f t
 the internal rate: < pi) and with f = 62.3371 / r + 320.204 Hz, r >= 5 mm, of the radiation impedance (at most 12 788 Hz at
 an internal rate of at least 50 kHz: < 1.61), both inside the [2^-13, 3.2] tests/test_capi_cpu.py holds cosf_glibc to."""
 import ctypes
+import functools
 import os
 import shutil
 import subprocess
@@ -17,23 +18,15 @@ import pytest
 
 import gama_tts_amd as g
 from gama_tts_amd import capi
-import golden5_cases
-import golden5f_cases
 import golden_cases
+import model5_cases as cases
 import oracle
+from voice_cases import model5_plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLOAT_CASES = [c for c in golden5_cases.CASES if c["float_model"]] + golden5f_cases.CASES
 
 
-def _plan(overrides=None, rate=48000.0, crate=250.0, precision=capi.PRECISION_F32):
-    d = g.read_config_file(oracle.VOICE5_MALE)
-    d.update({k: str(v) for k, v in (overrides or {}).items()})
-    return g.Plan(g.config5_from_dict(d, rate, precision), crate, capi.DEVICE_NONE, float_model5=True)
-
-
-def _manifest(case, golden5):
-    return (golden5 if case in golden5_cases.CASES else golden5f_cases.golden5f())["manifest"][case["name"]]
+_plan = functools.partial(model5_plan, "male", float_class=True, device=capi.DEVICE_NONE)  # (overrides, rate, crate)
 
 
 def test_entry_takes_f32_only_and_the_factory_entry_still_refuses_it():
@@ -42,20 +35,20 @@ def test_entry_takes_f32_only_and_the_factory_entry_still_refuses_it():
     assert plan.info.model5 == 1 and plan.info.precision == capi.PRECISION_F32 and plan.info.device == capi.DEVICE_NONE
     for precision in (capi.PRECISION_F64, capi.PRECISION_MIXED):
         with pytest.raises(g.GvtmError) as ei:
-            _plan(precision=precision)
+            g.Plan(g.config5_from_dict(d, 48000.0, precision), 250.0, capi.DEVICE_NONE, float_model5=True)
         assert ei.value.status == 1
     with pytest.raises(g.GvtmError) as ei:  # gvtm_plan_create_model5 is the factory's model 5: VocalTractModel5<double,1>
         g.Plan(g.config5_from_dict(d, precision=capi.PRECISION_F32), 250.0, capi.DEVICE_NONE)
     assert ei.value.status == 1 and "fp64 only" in str(ei.value)
 
 
-@pytest.mark.parametrize("case", FLOAT_CASES, ids=lambda c: c["name"])
-def test_design_matches_the_reference_vectors(case, golden, golden5):
-    m = _manifest(case, golden5)
-    tr = golden5_cases.track_for(case, golden)
+@pytest.mark.parametrize("case", cases.MALE_FLOAT_CASES, ids=lambda c: c["name"])
+def test_design_matches_the_reference_vectors(case, golden):
+    m = cases.load(case["fixture"])["manifest"][case["name"]]
+    tr = cases.track_for(case, golden)
     plan = _plan(case["overrides"], case["rate"], case["crate"])
     i = plan.info
-    _, oracle_rate = oracle.synthesize5(golden5f_cases.oracle_config(case), np.zeros((0, 16), np.float32), case["crate"])
+    _, oracle_rate = oracle.synthesize5(cases.oracle_config(case), np.zeros((0, 16), np.float32), case["crate"])
     # (the oracle reports (int) (rate * 1000.0f), formed in float: the plan's rate must give exactly that figure)
     assert int(np.float32(i.internal_rate_hz) * np.float32(1000.0)) == round(oracle_rate * 1000.0)
     assert abs(i.internal_rate_hz - m["fs"]) < 2e-3 and i.internal_rate_hz == float(np.float32(i.internal_rate_hz))

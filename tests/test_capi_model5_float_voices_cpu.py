@@ -6,14 +6,16 @@ rate at the high end.  The ends are found here, per voice, from the converter's 
 (SampleRateConverter<float>::initializeConversion as oracle/vtm_oracle_body.inc:317-325 restates it), not taken from the
 product."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import gama_tts_amd as g
 from gama_tts_amd import capi
-import golden5f_voices_cases as cases
+import model5_cases as cases
 import oracle
+from voice_cases import model5_plan
 from voice_files import VOICES, voice_path
 
 f32 = np.float32
@@ -22,13 +24,11 @@ CONTROL_RATE_CASES = [("male", 16000.0, 1000.0, 60), ("female", 16000.0, 1000.0,
                       ("baby", 32000.0, 200.0, 705)]
 
 
-def _plan(voice, rate=cases.RATE, crate=cases.CRATE, **kw):
-    cfg = g.config5_from_dict(g.read_config_file(voice_path(voice, True)), rate, capi.PRECISION_F32)
-    return g.Plan(cfg, crate, capi.DEVICE_NONE, float_model5=True, **kw)
+_plan = functools.partial(model5_plan, float_class=True, device=capi.DEVICE_NONE)  # design-only, the float class
 
 
 def _oracle_count(voice, rate, frames, crate=cases.CRATE):
-    return oracle.synthesize5(cases.oracle_config(voice, rate), np.zeros((frames, 16), np.float32), crate)[0].size
+    return oracle.synthesize5(cases.voice_oracle_config(voice, rate, 1), np.zeros((frames, 16), np.float32), crate)[0].size
 
 
 def internal_rate(voice):
@@ -65,7 +65,7 @@ def _first_float(lo, hi, pred):
 
 def _refused(voice, rate):
     with pytest.raises(g.GvtmError) as ei:
-        _plan(voice, float(rate))
+        _plan(voice, rate=float(rate))
     return ei.value.status
 
 
@@ -73,7 +73,7 @@ def _refused(voice, rate):
 def test_rate_steps_and_branch(voice):
     fs = internal_rate(voice)
     for rate in (cases.RATE, 22050.0, 176400.0):
-        i = _plan(voice, rate).info
+        i = _plan(voice, rate=rate).info
         assert i.model5 == 1 and i.precision == capi.PRECISION_F32 and i.output_rate == rate
         assert i.internal_rate_hz == float(fs)  # (a float, and the class's)
         assert i.control_steps == cases.STEPS_PER_FRAME[voice] == round(float(fs) / cases.CRATE)
@@ -81,7 +81,7 @@ def test_rate_steps_and_branch(voice):
         assert i.upsampling == int(rate >= float(fs)) == int(ratio >= 1.0)
         assert i.time_register_increment == time_inc and i.pad_size == pad
     # what the reference's class reports for the voice
-    m = cases.golden5fv()["manifest"]
+    m = cases.load("voices5f")["manifest"]
     for c in cases.FLOAT_CASES:
         if c["voice"] == voice:
             assert abs(float(fs) - m[c["name"]]["fs"]) < 2e-3
@@ -90,22 +90,22 @@ def test_rate_steps_and_branch(voice):
 
 @pytest.mark.parametrize("case", cases.FLOAT_CASES, ids=lambda c: c["name"])
 def test_output_count_of_the_reference_vectors(case):
-    m = cases.golden5fv()["manifest"][case["name"]]
-    plan = _plan(case["voice"], case["rate"], case["crate"])
+    m = cases.load("voices5f")["manifest"][case["name"]]
+    plan = _plan(case["voice"], case["overrides"], case["rate"], case["crate"])
     assert plan.output_count(m["frames"]) == m["n"] <= plan.output_capacity(m["frames"])
 
 
 @pytest.mark.parametrize("voice", VOICES)
 def test_output_counts_follow_the_float_oracle(voice):
     """Every length up to 40 frames at 48 kHz, and the three lengths around the voice's flush overrun (male: 106 frames at
-    44.1 kHz, tests/golden5f_cases.py)."""
+    44.1 kHz, tests/model5_cases.py)."""
     plan = _plan(voice)
     counts = {f: plan.output_count(f) for f in range(41)}
     for f, n in counts.items():
         assert n == _oracle_count(voice, cases.RATE, f), f
     assert plan.output_capacity(40) >= max(counts.values())
     ovr, rate = (106, 44100.0) if voice == "male" else (cases.OVERRUN_FRAMES[voice], cases.OVERRUN_RATE[voice])
-    plan = _plan(voice, rate)
+    plan = _plan(voice, rate=rate)
     n = {f: plan.output_count(f) for f in (ovr - 1, ovr, ovr + 1)}
     for f in n:
         assert n[f] == _oracle_count(voice, rate, f), f
@@ -118,7 +118,7 @@ def test_lowest_accepted_rate_has_pad_96(voice):
     fs = internal_rate(voice)
     below, lowest = _first_float(1000.0, 0.5 * float(fs), lambda r: converter(fs, r)[2] <= cases.MAX_PAD)
     assert converter(fs, lowest)[2] == cases.MAX_PAD and converter(fs, below)[2] == cases.MAX_PAD + 1
-    plan = _plan(voice, float(lowest))
+    plan = _plan(voice, rate=float(lowest))
     assert plan.info.pad_size == cases.MAX_PAD and plan.info.upsampling == 0
     assert plan.info.time_register_increment == converter(fs, lowest)[1]
     for f in range(4):
@@ -131,7 +131,7 @@ def test_the_pad_96_vectors_have_pad_96():
     for voice, rate, what in cases.LIMITS:
         fs = internal_rate(voice)
         if what == "pad96":
-            assert converter(fs, rate)[2] == cases.MAX_PAD == _plan(voice, rate).info.pad_size
+            assert converter(fs, rate)[2] == cases.MAX_PAD == _plan(voice, rate=rate).info.pad_size
         else:
             assert converter(fs, rate)[0] == f32(3.0)
 
@@ -143,7 +143,7 @@ def test_highest_accepted_rate_is_three_times_the_internal_rate(voice):
     assert converter(fs, highest)[0] <= f32(3.0) < converter(fs, above)[0]
     if voice != "male":  # (male's 60 411.43 Hz has no float that is 3.0 times it: its highest ratio is 2.9999998)
         assert float(fs) * 3.0 == float(f32(3.0) * fs) <= float(highest) and converter(fs, highest)[0] == f32(3.0)
-    plan = _plan(voice, float(highest))
+    plan = _plan(voice, rate=float(highest))
     assert plan.info.upsampling == 1 and plan.info.pad_size == 13
     assert plan.info.time_register_increment == converter(fs, highest)[1]
     for f in range(4):
@@ -154,7 +154,7 @@ def test_highest_accepted_rate_is_three_times_the_internal_rate(voice):
 
 @pytest.mark.parametrize("voice,rate,crate,steps", CONTROL_RATE_CASES, ids=lambda v: str(v))
 def test_control_rates(voice, rate, crate, steps):
-    plan = _plan(voice, rate, crate)
+    plan = _plan(voice, None, rate, crate)
     assert plan.info.control_steps == steps == round(float(internal_rate(voice)) / crate)
     assert plan.info.control_rate == crate
     for f in range(9):

@@ -8,7 +8,7 @@ import pytest
 
 import gama_tts_amd as g
 from gama_tts_amd import capi
-import golden5_voices_cases as cases
+import model5_cases as cases
 import oracle
 from voice_cases import configs5, create
 from voice_files import VOICES, voice_path
@@ -55,7 +55,7 @@ def test_five_voices_info_matches_the_oracle_and_the_issue_table():
         single = g.Plan(cfgs[v], 250.0, capi.DEVICE_NONE)
         for field, _ in capi.Info._fields_:
             assert getattr(info, field) == getattr(single.info, field), (name, field)
-        _, rate = oracle.synthesize5(cases.oracle_config(name), np.zeros((0, 16), np.float32))
+        _, rate = oracle.synthesize5(cases.voice_oracle_config(name), np.zeros((0, 16), np.float32))
         assert info.model5 == 1 and info.output_rate == cases.RATE
         assert abs(info.internal_rate_hz - rate) < 2e-3  # the oracle reports millihertz
         assert info.internal_rate_hz == pytest.approx((331.4 + 0.6 * 35.0) * 30 * 100 / cases.TRACT_CM[name], rel=1e-12)
@@ -70,7 +70,7 @@ def test_per_voice_counts_and_capacity():
     vp = g.VoicesPlan(cfgs, 250.0, capi.DEVICE_NONE)
     singles = [g.Plan(c, 250.0, capi.DEVICE_NONE) for c in cfgs]
     for v, name in enumerate(VOICES):
-        ocfg = cases.oracle_config(name)
+        ocfg = cases.voice_oracle_config(name)
         frames = [0, 1, 2, 3, 25] + ([cases.OVERRUN_FRAMES[name]] if cases.OVERRUN_RATE.get(name) == cases.RATE else [])
         for f in frames:
             n = oracle.synthesize5(ocfg, np.zeros((f, 16), np.float32))[0].size

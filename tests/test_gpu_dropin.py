@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 
 import gama_tts_amd as g
+import model5_cases
 import oracle
+import voice_files
 from parity_rules import check_model5, peak_err, within
 
 pytestmark = pytest.mark.gpu
@@ -124,21 +126,7 @@ def _make_voice_dir(root, model="0", rate=None):
     keys["model"] = model
     if rate is not None:
         keys["output_rate"] = repr(float(rate))
-    os.makedirs(os.path.join(root, "variant"))
-    variant_keys = ("vocal_tract_length", "glottal_pulse_tp", "glottal_pulse_tn_min", "glottal_pulse_tn_max",
-                    "reference_glottal_pitch", "breathiness", "aperture_radius", "intonation_factor")
-    with open(os.path.join(root, "_index.txt"), "w") as f:
-        f.write("variant_dir = variant/\nvtm_control_model_file = vtm_control_model.txt\nvtm_file = vtm.txt\n")
-    with open(os.path.join(root, "vtm.txt"), "w") as f:
-        f.write("# test voice\n")
-        for k, v in keys.items():
-            if k not in variant_keys:
-                f.write("%s = %s\n" % (k, v))
-    with open(os.path.join(root, "variant", "male.txt"), "w") as f:
-        for k in variant_keys:
-            f.write("%s = %s\n" % (k, keys[k]))
-    with open(os.path.join(root, "vtm_control_model.txt"), "w") as f:
-        f.write("control_period = 4\nvariant_name = male\n")
+    voice_files.write_voice_dir(root, keys, voice_files.VARIANT_KEYS)
 
 
 def _read_wav(path):
@@ -288,9 +276,7 @@ def test_plugin_model5_through_reference_loader(golden, golden5, tmp_path):
     with open(cfg, "w") as f:
         for k, v in keys.items():
             f.write("%s = %s\n" % (k, v))
-    import golden5_cases
-    case = next(c for c in golden5_cases.CASES if c["name"] == "rand5_m5")
-    tr = golden5_cases.track_for(case, golden)
+    tr = model5_cases.track_for(model5_cases.by_name("rand5_m5"), golden)
     out, info = _through_loaders(tr, tmp_path, output_rate=48000, config=cfg)
     ref = golden5["rand5_m5__out"]
     assert out.size == ref.size == int(info["N"])
@@ -310,9 +296,7 @@ def test_plugin_model5_interactive_protocol_through_reference_loader(poll, golde
     with open(cfg, "w") as f:
         for k, v in keys.items():
             f.write("%s = %s\n" % (k, v))
-    import golden5_cases
-    case = next(c for c in golden5_cases.CASES if c["name"] == "rand5_m5")
-    tr = golden5_cases.track_for(case, golden)
+    tr = model5_cases.track_for(model5_cases.by_name("rand5_m5"), golden)
     out, info = _through_loaders(tr, tmp_path, output_rate=48000, config=cfg, poll=poll)
     ref = golden5["rand5_m5__out"]
     assert out.size == ref.size == int(info["N"]) and int(info["callbacks"]) >= ref.size // poll
@@ -325,21 +309,7 @@ def test_batched_vtm_cli_model5_voice(golden, tmp_path):
     """A voice directory whose vtm.txt says `model = 5` (the layout of data/voice/english/5_male): the batched CLI
     writes what `gama_tts vtm` writes for it."""
     voice = str(tmp_path / "voice5")
-    keys = oracle.read_config_file(oracle.VOICE5_MALE)
-    os.makedirs(os.path.join(voice, "variant"))
-    variant_keys = ("vocal_tract_length", "glottal_pulse_tp", "glottal_pulse_tn_min", "glottal_pulse_tn_max",
-                    "reference_glottal_pitch", "breathiness", "intonation_factor", "nasal_radius_2", "nasal_radius_3")
-    with open(os.path.join(voice, "_index.txt"), "w") as f:
-        f.write("variant_dir = variant/\nvtm_control_model_file = vtm_control_model.txt\nvtm_file = vtm.txt\n")
-    with open(os.path.join(voice, "vtm.txt"), "w") as f:
-        for k, v in keys.items():
-            if k not in variant_keys:
-                f.write("%s = %s\n" % (k, v))
-    with open(os.path.join(voice, "variant", "male.txt"), "w") as f:
-        for k in variant_keys:
-            f.write("%s = %s\n" % (k, keys[k]))
-    with open(os.path.join(voice, "vtm_control_model.txt"), "w") as f:
-        f.write("control_period = 4\nvariant_name = male\n")
+    voice_files.write_voice_dir(voice, oracle.read_config_file(oracle.VOICE5_MALE), voice_files.VARIANT_KEYS5)
     out_dir = str(tmp_path / "out5")
     os.makedirs(out_dir)
     tracks_ = {"hello": np.asarray(golden["hello_params"]), "short": np.asarray(golden["hello_params"])[:40]}

@@ -12,7 +12,7 @@ import pytest
 import gama_tts_amd as g
 from gama_tts_amd import capi
 import event_lists
-import golden5_voices_cases as cases5
+import model5_cases as cases5
 import oracle
 from device_io import events_on_device, generate_tracks, synthesize_events
 from parity_rules import TOL, check_model5, within
@@ -214,7 +214,7 @@ def test_events_voices_entry_on_a_model5_plan():
     for v, name in enumerate(VOICES):
         b = max((b for b in range(batch) if ids[b] == v), key=lambda b: frames_of[b])
         frames, _ = oracle.tracks_generate(oracle.track_config(VARIANT_TRACKS[v]), tables[b])
-        ref, _ = oracle.synthesize5(cases5.oracle_config(name, 48000.0), frames)
+        ref, _ = oracle.synthesize5(cases5.voice_oracle_config(name, 48000.0), frames)
         assert got["counts"][b] == ref.size and np.isfinite(ref).all()
         check_model5(got["audio"][b, : ref.size], ref)
 

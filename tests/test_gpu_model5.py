@@ -13,21 +13,19 @@ import pytest
 
 import gama_tts_amd as g
 from gama_tts_amd import capi
-import golden5_cases
+import model5_cases as cases
 import oracle
 import tracks
-from parity_rules import TOL5, check_model5
+from parity_rules import TOL5, check_batch, check_model5
 from voice_cases import male5_plan
 
 pytestmark = pytest.mark.gpu
 
-DOUBLE_CASES = [c for c in golden5_cases.CASES if not c["float_model"]]
 
-
-@pytest.mark.parametrize("case", DOUBLE_CASES, ids=lambda c: c["name"])
+@pytest.mark.parametrize("case", cases.MALE_DOUBLE_CASES, ids=lambda c: c["name"])
 def test_reference_vectors(case, golden, golden5):
     m = golden5["manifest"][case["name"]]
-    tr = golden5_cases.track_for(case, golden)
+    tr = cases.track_for(case, golden)
     plan = male5_plan(case["overrides"], case["rate"], case["crate"])
     assert plan.info.model5 == 1
     assert abs(plan.info.internal_rate_hz - m["fs"]) < 1e-6
@@ -37,10 +35,8 @@ def test_reference_vectors(case, golden, golden5):
     assert counts[0] == m["n"]
     out = audio[0]
     bypass = int(case["overrides"].get("bypass", 0)) == 1
-    if case["store"] == "full":
-        check_model5(out, golden5[case["name"] + "__out"], bypass, m["maxabs"])
-    else:
-        check_model5(out[:: golden5_cases.DIGEST_STRIDE], golden5[case["name"] + "__strided"], bypass, m["maxabs"])
+    for got, key in cases.stored(case, out):
+        check_model5(got, golden5[key], bypass, m["maxabs"])
     assert maxabs[0] == pytest.approx(m["maxabs"], rel=10 * TOL5, abs=1e-12)
     assert maxabs[0] == np.abs(out).max()
 
@@ -49,14 +45,9 @@ def test_ragged_batch_against_oracle():
     # utterances of different lengths in one launch (0, 1, 2, ... frames), consonant-heavy tracks
     frames = [0, 1, 2, 3, 7, 25, 40, 40, 13, 31]
     params = tracks.random_tracks(len(frames), 40, seed0=900, consonant_heavy=True)
-    plan = male5_plan()
-    audio, counts, maxabs = plan.synthesize_host(params, frame_counts=frames)
     cfg = oracle.male5_config(48000.0)
-    for b, f in enumerate(frames):
-        ref, _ = oracle.synthesize5(cfg, params[b, :f])
-        assert counts[b] == ref.size
-        check_model5(audio[b, : ref.size], ref)
-        assert maxabs[b] == np.abs(audio[b, : ref.size]).max()
+    refs = [oracle.synthesize5(cfg, params[b, :f])[0] for b, f in enumerate(frames)]
+    check_batch(*male5_plan().synthesize_host(params, frame_counts=frames), refs, False)
 
 
 def test_batch_of_identical_tracks_is_identical():
@@ -73,10 +64,8 @@ def test_upsampling_branch(rate):
     tr = tracks.random_track(30, 5, True)
     plan = male5_plan(rate=rate)
     assert plan.info.upsampling == 1
-    audio, counts, _ = plan.synthesize_host(tr[None])
     ref, _ = oracle.synthesize5(oracle.male5_config(rate), tr)
-    assert counts[0] == ref.size
-    check_model5(audio[0, : ref.size], ref)
+    check_batch(*plan.synthesize_host(tr[None]), [ref], False)
     with pytest.raises(g.GvtmError):
         male5_plan(rate=192000.0)
 
@@ -98,14 +87,9 @@ def test_long_utterance_next_to_short_ones():
     params = np.zeros((3, 7500, 16), np.float32)
     params[0] = long_tr
     params[1, :1] = long_tr[:1]
-    plan = male5_plan()
-    audio, counts, maxabs = plan.synthesize_host(params, frame_counts=[7500, 1, 0])
     cfg = oracle.male5_config(48000.0)
-    for b, f in enumerate((7500, 1, 0)):
-        ref, _ = oracle.synthesize5(cfg, params[b, :f])
-        assert counts[b] == ref.size
-        check_model5(audio[b, : ref.size], ref)
-        assert maxabs[b] == np.abs(audio[b, : ref.size]).max()
+    refs = [oracle.synthesize5(cfg, params[b, :f])[0] for b, f in enumerate((7500, 1, 0))]
+    check_batch(*male5_plan().synthesize_host(params, frame_counts=[7500, 1, 0]), refs, False)
 
 
 def test_full_batch_on_the_device_by_tiling():
@@ -153,23 +137,20 @@ def test_host_entry_slices_large_batches():
     pool = tracks.random_tracks(50, frames, seed0=717000, consonant_heavy=True)
     params = np.ascontiguousarray(np.tile(pool, (batch // 50, 1, 1)))
     fc = (np.arange(batch) % (frames + 1)).astype(np.int32)
-    plan = male5_plan()
-    audio, counts, _ = plan.synthesize_host(params, fc)
+    audio, counts, maxabs = male5_plan().synthesize_host(params, fc)
     cfg = oracle.male5_config(48000.0)
-    for b in (0, 1023, 1024, 2047, 2048, batch - 1):
-        ref, _ = oracle.synthesize5(cfg, params[b, : fc[b]])
-        assert counts[b] == ref.size
-        check_model5(audio[b, : ref.size], ref)
+    at = [0, 1023, 1024, 2047, 2048, batch - 1]
+    check_batch(audio[at], counts[at], maxabs[at], [oracle.synthesize5(cfg, params[b, : fc[b]])[0] for b in at], False)
     # the pool repeats every 50 utterances, the frame counts every 7: 350 apart the utterances are the same
     valid = np.arange(audio.shape[1])[None, :] < counts[:350, None]
     assert np.array_equal(audio[:350][valid], audio[1050:1400][valid]) and np.array_equal(audio[:350][valid], audio[1750:2100][valid])
 
 
-@pytest.mark.parametrize("case", DOUBLE_CASES, ids=lambda c: c["name"])
+@pytest.mark.parametrize("case", cases.MALE_DOUBLE_CASES, ids=lambda c: c["name"])
 def test_reference_vectors_two_utterances_per_workgroup(case, golden, golden5):
     """The reference-made vectors through the two-utterance workgroup shape (vtm5_synth_kernel<24, 5, 1024, 2>: what batches
     beyond one workgroup per compute unit get), the vector in BOTH slots of a workgroup and beside a different neighbour."""
-    tr = golden5_cases.track_for(case, golden)
+    tr = cases.track_for(case, golden)
     other = tracks.random_track(tr.shape[0], 77, True)
     plan = male5_plan(case["overrides"], case["rate"], case["crate"], rows=2)
     audio, counts, _ = plan.synthesize_host(np.stack([tr, other, other, tr, tr]))
@@ -177,11 +158,8 @@ def test_reference_vectors_two_utterances_per_workgroup(case, golden, golden5):
     bypass = int(case["overrides"].get("bypass", 0)) == 1
     for b in (0, 3, 4):
         assert counts[b] == m["n"]
-        out = audio[b, : m["n"]]
-        if case["store"] == "full":
-            check_model5(out, golden5[case["name"] + "__out"], bypass, m["maxabs"])
-        else:
-            check_model5(out[:: golden5_cases.DIGEST_STRIDE], golden5[case["name"] + "__strided"], bypass, m["maxabs"])
+        for got, key in cases.stored(case, audio[b, : m["n"]]):
+            check_model5(got, golden5[key], bypass, m["maxabs"])
     assert np.array_equal(audio[0], audio[3]) and np.array_equal(audio[0], audio[4])
 
 
@@ -195,10 +173,8 @@ def test_two_utterances_per_workgroup_ragged_against_the_one_utterance_shape_and
     assert np.array_equal(c1, c2) and np.array_equal(m1, m2)
     assert np.array_equal(a1, a2)
     cfg = oracle.male5_config(48000.0)
-    for b in (0, 2, 3, 6, 10):
-        ref, _ = oracle.synthesize5(cfg, params[b, : frames[b]])
-        assert c2[b] == ref.size
-        check_model5(a2[b, : ref.size], ref)
+    at = [0, 2, 3, 6, 10]
+    check_batch(a2[at], c2[at], m2[at], [oracle.synthesize5(cfg, params[b, : frames[b]])[0] for b in at], False)
 
 
 def test_product_library_on_a_batch_beyond_one_workgroup_per_compute_unit():
@@ -208,13 +184,8 @@ def test_product_library_on_a_batch_beyond_one_workgroup_per_compute_unit():
     pool = tracks.random_tracks(len(pool_f), 30, seed0=6000, consonant_heavy=True)
     batch = 601
     idx = np.arange(batch) % len(pool_f)
-    plan = male5_plan()
-    audio, counts, maxabs = plan.synthesize_host(pool[idx], pool_f[idx])
+    audio, counts, maxabs = male5_plan().synthesize_host(pool[idx], pool_f[idx])
     cfg = oracle.male5_config(48000.0)
-    for t in range(len(pool_f)):
-        ref, _ = oracle.synthesize5(cfg, pool[t, : pool_f[t]])
-        assert counts[t] == ref.size
-        check_model5(audio[t, : ref.size], ref)
-        assert maxabs[t] == (np.abs(audio[t, : ref.size]).max() if ref.size else 0.0)
+    check_batch(audio, counts, maxabs, [oracle.synthesize5(cfg, pool[t, : pool_f[t]])[0] for t in range(len(pool_f))], False)
     for b in range(len(pool_f), batch):
         assert counts[b] == counts[b % len(pool_f)] and np.array_equal(audio[b], audio[b % len(pool_f)]), b

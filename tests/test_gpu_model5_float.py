@@ -10,6 +10,7 @@ tests/test_oracle5_vs_golden.py and tests/test_oracle5f_vs_golden.py hold to tho
 The class has two workgroup shapes (vtm_kernel_m5.inc: chunk 60 up to 256 utterances, chunk 56 -- two workgroups per
 compute unit -- beyond); a diagnostics plan forces either (rows 1 / rows 2), and both must give the same bits."""
 import ctypes
+import functools
 import hashlib
 import os
 
@@ -18,44 +19,34 @@ import pytest
 
 import gama_tts_amd as g
 from gama_tts_amd import capi
-import golden5_cases
-import golden5f_cases
 import golden_cases
+import model5_cases as cases
 import oracle
 import tracks
+import voice_files
 from device_io import events_chain_and_entry
-from parity_rules import TOL, within
+from parity_rules import TOL, check_batch, within
 from track_cases import product_config, singable_event_table, used_drift
+from voice_cases import model5_plan, push_in_pieces
 
 pytestmark = pytest.mark.gpu
 
 BIT_IDENTICAL = TOL[capi.PRECISION_F32]
-FLOAT_CASES = [c for c in golden5_cases.CASES if c["float_model"]] + golden5f_cases.CASES
 LIBDIR = os.path.dirname(g.library_path())
 PLUGIN = os.path.join(LIBDIR, "libgama_vtm_plugin.so")
 
 
-def float5_plan(overrides=None, rate=48000.0, crate=250.0, rows=0):
-    """A float model-5 plan of the 5_male voice on device 0 (rows 1 / 2: a diagnostics plan forced to chunk 60 / chunk 56)."""
-    d = g.read_config_file(oracle.VOICE5_MALE)
-    d.update({k: str(v) for k, v in (overrides or {}).items()})
-    return g.Plan(g.config5_from_dict(d, rate, capi.PRECISION_F32), crate, 0, diagnostics=bool(rows), rows=rows, float_model5=True)
-
-
-def check_batch(audio, counts, maxabs, refs):
-    for b, ref in enumerate(refs):
-        assert counts[b] == ref.size, (b, counts[b], ref.size)
-        assert within(audio[b, : ref.size], ref, BIT_IDENTICAL), b
-        assert maxabs[b] == (np.abs(audio[b, : ref.size]).max() if ref.size else 0.0), b
+# float5_plan(overrides, rate, crate, rows): a float model-5 plan of the 5_male voice on device 0 (rows 1 / 2: a diagnostics
+# plan forced to chunk 60 / chunk 56)
+float5_plan = functools.partial(model5_plan, "male", float_class=True)
 
 
 @pytest.mark.parametrize("rows", [0, 2], ids=["product_shape", "chunk56"])
-@pytest.mark.parametrize("case", FLOAT_CASES, ids=lambda c: c["name"])
-def test_reference_vectors(case, rows, golden, golden5):
-    own = case in golden5f_cases.CASES
-    data = golden5f_cases.golden5f() if own else golden5
+@pytest.mark.parametrize("case", cases.MALE_FLOAT_CASES, ids=lambda c: c["name"])
+def test_reference_vectors(case, rows, golden):
+    data = cases.load(case["fixture"])
     m = data["manifest"][case["name"]]
-    tr = golden5_cases.track_for(case, golden)
+    tr = cases.track_for(case, golden)
     plan = float5_plan(case["overrides"], case["rate"], case["crate"], rows)
     assert plan.info.model5 == 1 and plan.info.precision == capi.PRECISION_F32
     assert plan.info.control_steps * tr.shape[0] == m["steps"]
@@ -63,10 +54,8 @@ def test_reference_vectors(case, rows, golden, golden5):
     assert counts[0] == m["n"] == plan.output_count(tr.shape[0])
     out = audio[0, : m["n"]]
     assert hashlib.sha256(out.tobytes()).hexdigest() == m["sha256"]
-    if case["store"] == "full":
-        assert within(out, data[case["name"] + "__out"], BIT_IDENTICAL)
-    else:
-        assert within(out[:: golden5_cases.DIGEST_STRIDE], data[case["name"] + "__strided"], BIT_IDENTICAL)
+    for got, key in cases.stored(case, out):
+        assert within(got, data[key], BIT_IDENTICAL), key
     assert maxabs[0] == np.abs(out).max() == np.float32(m["maxabs"])
 
 
@@ -86,7 +75,7 @@ def test_ragged_batch_with_the_flush_overrun_against_the_float_oracle():
     assert refs[10].size > oracle.synthesize5(cfg, np.zeros((107, 16), np.float32))[0].size  # (106 frames: the overrun)
     for rows in (0, 2):
         audio, counts, maxabs = float5_plan(rate=44100.0, rows=rows).synthesize_host(params, frame_counts=frames)
-        check_batch(audio, counts, maxabs, refs)
+        check_batch(audio, counts, maxabs, refs, True)
 
 
 def test_upsampling_branch():
@@ -94,7 +83,7 @@ def test_upsampling_branch():
     plan = float5_plan(rate=96000.0)
     assert plan.info.upsampling == 1
     audio, counts, maxabs = plan.synthesize_host(tr[None])
-    check_batch(audio, counts, maxabs, [oracle.synthesize5(oracle.male5_config(96000.0, 1), tr)[0]])
+    check_batch(audio, counts, maxabs, [oracle.synthesize5(oracle.male5_config(96000.0, 1), tr)[0]], True)
 
 
 def test_special_case_frames():
@@ -106,8 +95,8 @@ def test_special_case_frames():
     ref, ref_other = oracle.synthesize5(cfg, tr)[0], oracle.synthesize5(cfg, other)[0]
     assert np.isfinite(ref).all()
     plan = float5_plan()
-    check_batch(*plan.synthesize_host(tr[None]), [ref])
-    check_batch(*plan.synthesize_host(np.stack([tr, other, tr])), [ref, ref_other, ref])
+    check_batch(*plan.synthesize_host(tr[None]), [ref], True)
+    check_batch(*plan.synthesize_host(np.stack([tr, other, tr])), [ref, ref_other, ref], True)
 
 
 def test_long_utterance_next_to_short_ones():
@@ -119,7 +108,7 @@ def test_long_utterance_next_to_short_ones():
     params[1, :1] = long_tr[:1]
     cfg = oracle.male5_config(48000.0, 1)
     refs = [oracle.synthesize5(cfg, params[b, :f])[0] for b, f in enumerate((600, 1, 0))]
-    check_batch(*float5_plan().synthesize_host(params, frame_counts=[600, 1, 0]), refs)
+    check_batch(*float5_plan().synthesize_host(params, frame_counts=[600, 1, 0]), refs, True)
 
 
 def test_product_library_on_a_batch_beyond_two_workgroups_per_compute_unit():
@@ -132,31 +121,10 @@ def test_product_library_on_a_batch_beyond_two_workgroups_per_compute_unit():
     idx = np.arange(batch) % len(pool_f)
     audio, counts, maxabs = float5_plan().synthesize_host(pool[idx], pool_f[idx])
     cfg = oracle.male5_config(48000.0, 1)
-    check_batch(audio, counts, maxabs, [oracle.synthesize5(cfg, pool[t, : pool_f[t]])[0] for t in range(len(pool_f))])
+    check_batch(audio, counts, maxabs, [oracle.synthesize5(cfg, pool[t, : pool_f[t]])[0] for t in range(len(pool_f))], True)
     for b in range(len(pool_f), batch):
         assert counts[b] == counts[b % len(pool_f)] and np.array_equal(audio[b], audio[b % len(pool_f)]), b
         assert maxabs[b] == maxabs[b % len(pool_f)]
-
-
-def _push_in_pieces(plan, batch, total, pieces):
-    """The utterances of `batch` (total[b] frames each) pushed in pieces of at most pieces[i] frames, then finished ->
-    (samples per utterance, maxabs)."""
-    st = g.Stream(plan, len(total))
-    outs = [[] for _ in total]
-    done = np.zeros(len(total), dtype=np.int32)
-    lockstep = len(set(int(t) for t in total)) == 1
-    for n in pieces:
-        fc = np.minimum(n, total - done).astype(np.int32)
-        buf = np.zeros((len(total), n, 16), np.float32)
-        for b in range(len(total)):
-            buf[b, : fc[b]] = batch[b, done[b]: done[b] + fc[b]]
-        res = st.push(buf, None if lockstep else fc)
-        for b in range(len(total)):
-            outs[b].append(res[b])
-        done += fc
-    assert (done == total).all()
-    tails, maxabs = st.finish()
-    return [np.concatenate(outs[b] + [tails[b]]) for b in range(len(total))], maxabs
 
 
 @pytest.mark.parametrize("total", [[33, 33, 33], [33, 20, 8]], ids=["lockstep", "ragged"])
@@ -165,7 +133,7 @@ def test_stream_pieces_equal_the_one_shot_samples(total):
     batch = tracks.random_tracks(3, 33, seed0=5700, consonant_heavy=True)
     plan = float5_plan()
     one, c1, m1 = plan.synthesize_host(batch, total)
-    got, maxabs = _push_in_pieces(plan, batch, total, (7, 1, 25))
+    got, maxabs = push_in_pieces(plan, batch, total, (7, 1, 25))
     for b in range(3):
         assert got[b].size == c1[b] and np.array_equal(got[b], one[b, : c1[b]]), b
         assert maxabs[b] == m1[b]
@@ -178,7 +146,7 @@ def test_stream_finish_on_a_flush_overrun():
     track = tracks.random_track(106, 5500, True)
     plan = float5_plan(rate=44100.0)
     whole, counts, peak = plan.synthesize_host(track[None])
-    got, maxabs = _push_in_pieces(plan, track[None], np.array([106], dtype=np.int32), (7, 1, 25, 73))
+    got, maxabs = push_in_pieces(plan, track[None], np.array([106], dtype=np.int32), (7, 1, 25, 73))
     assert got[0].size == counts[0] == plan.output_count(106) > plan.output_count(107)
     assert np.array_equal(got[0], whole[0, : counts[0]]) and maxabs[0] == peak[0]
     assert within(got[0], oracle.synthesize5(oracle.male5_config(44100.0, 1), track)[0], BIT_IDENTICAL)
@@ -218,8 +186,7 @@ def test_plugin_with_gpu_model_5_and_gpu_precision_f32_through_the_loaders(golde
     with open(cfg, "w") as f:
         for k, v in keys.items():
             f.write("%s = %s\n" % (k, v))
-    case = next(c for c in golden5_cases.CASES if c["name"] == "rand5_m5f")
-    tr = golden5_cases.track_for(case, golden)
+    tr = cases.track_for(cases.by_name("rand5_m5f"), golden)
     out, info = oracle.plugin_synthesize(tr, PLUGIN, tmpdir=str(tmp_path), output_rate=48000, config=cfg)
     if oracle.ref_binary() is not None:
         ref_out, _ = oracle.ref_synthesize(tr, "2000:" + PLUGIN, tmpdir=str(tmp_path), output_rate=48000, config=cfg)
@@ -275,21 +242,7 @@ def test_batched_vtm_cli_with_f_on_a_model5_voice(golden, tmp_path):
     import struct
     import subprocess
     voice = str(tmp_path / "voice5")
-    keys = oracle.read_config_file(oracle.VOICE5_MALE)
-    os.makedirs(os.path.join(voice, "variant"))
-    variant_keys = ("vocal_tract_length", "glottal_pulse_tp", "glottal_pulse_tn_min", "glottal_pulse_tn_max",
-                    "reference_glottal_pitch", "breathiness", "intonation_factor", "nasal_radius_2", "nasal_radius_3")
-    with open(os.path.join(voice, "_index.txt"), "w") as f:
-        f.write("variant_dir = variant/\nvtm_control_model_file = vtm_control_model.txt\nvtm_file = vtm.txt\n")
-    with open(os.path.join(voice, "vtm.txt"), "w") as f:
-        for k, v in keys.items():
-            if k not in variant_keys:
-                f.write("%s = %s\n" % (k, v))
-    with open(os.path.join(voice, "variant", "male.txt"), "w") as f:
-        for k in variant_keys:
-            f.write("%s = %s\n" % (k, keys[k]))
-    with open(os.path.join(voice, "vtm_control_model.txt"), "w") as f:
-        f.write("control_period = 4\nvariant_name = male\n")
+    voice_files.write_voice_dir(voice, oracle.read_config_file(oracle.VOICE5_MALE), voice_files.VARIANT_KEYS5)
     out_dir = str(tmp_path / "out5f")
     os.makedirs(out_dir)
     tr = np.asarray(golden["hello_params"])[:40]

@@ -20,18 +20,19 @@ shape the product picks (chunk 60 up to 256 utterances) and with chunk 56 forced
 The converter limits -- a down-sampling pad of 96, the largest a plan accepts and what the kernel's ring is sized for, and
 an output rate of 3 x the internal rate -- are run in both classes: the float class bit for bit, the double class
 (gvtm_plan_create_model5; rows 2 is its two-utterance workgroup) to parity_rules.check_model5, test_gpu_model5.py's bar."""
+import functools
 import hashlib
 
 import numpy as np
 import pytest
 
-import gama_tts_amd as g
 from gama_tts_amd import capi
-import golden5f_voices_cases as cases
+import model5_cases as cases
 import oracle
 import tracks
-from parity_rules import TOL, TOL5, check_model5, within
-from voice_files import VOICES, voice_path
+from parity_rules import TOL, TOL5, check_batch, check_model5, within
+from voice_cases import model5_plan, padded, push_in_pieces
+from voice_files import VOICES
 
 pytestmark = pytest.mark.gpu
 
@@ -42,23 +43,9 @@ CONTROL_RATE_CASES = [("male", 16000.0, 1000.0, 60), ("female", 16000.0, 1000.0,
                       ("baby", 32000.0, 200.0, 705)]
 
 
-def float_plan(voice, rate=cases.RATE, crate=cases.CRATE, rows=0):
-    """A float model-5 plan of a voice on device 0 (rows 2: a diagnostics plan forced to chunk 56)."""
-    cfg = g.config5_from_dict(g.read_config_file(voice_path(voice, True)), rate, capi.PRECISION_F32)
-    return g.Plan(cfg, crate, 0, diagnostics=bool(rows), rows=rows, float_model5=True)
-
-
-def double_plan(voice, rate=cases.RATE, crate=cases.CRATE, rows=0):
-    """A model-5 plan of the double class (rows 2: a diagnostics plan forced to two utterances per workgroup)."""
-    cfg = g.config5_from_dict(g.read_config_file(voice_path(voice, True)), rate)
-    return g.Plan(cfg, crate, 0, diagnostics=bool(rows), rows=rows)
-
-
-def check_batch(audio, counts, maxabs, refs):
-    for b, ref in enumerate(refs):
-        assert counts[b] == ref.size, (b, counts[b], ref.size)
-        assert within(audio[b, : ref.size], ref, BIT_IDENTICAL), b
-        assert maxabs[b] == (np.abs(audio[b, : ref.size]).max() if ref.size else 0.0), b
+# a float model-5 plan of a voice on device 0 (rows 2: a diagnostics plan forced to chunk 56); model5_plan itself gives the
+# double class (rows 2: a diagnostics plan forced to two utterances per workgroup)
+float_plan = functools.partial(model5_plan, float_class=True)
 
 
 _refs = {}
@@ -67,21 +54,12 @@ _refs = {}
 def oracle_refs(key, voice, rate, crate, utterances, float_model=1):
     """The oracle's output for a list of utterances, computed once per `key` and shared by the shapes (read-only)."""
     if key not in _refs:
-        cfg = cases.oracle_config(voice, rate, float_model)
+        cfg = cases.voice_oracle_config(voice, rate, float_model)
         refs = [oracle.synthesize5(cfg, u, crate)[0] for u in utterances]
         for r in refs:
             r.setflags(write=False)
         _refs[key] = refs
     return _refs[key]
-
-
-def padded(utterances):
-    """Utterances of different lengths -> (params [B][max frames][16], frame counts)."""
-    frames = np.array([u.shape[0] for u in utterances], dtype=np.int32)
-    params = np.zeros((len(utterances), max(1, int(frames.max())), 16), np.float32)
-    for b, u in enumerate(utterances):
-        params[b, : u.shape[0]] = u
-    return params, frames
 
 
 # ---- reference vectors --------------------------------------------------------------------------------------------------
@@ -91,10 +69,10 @@ def padded(utterances):
 def test_reference_vectors(case, rows, golden):
     """Every float vector of voices5f_golden.npz, one utterance per launch: count and SHA-256, then the full, strided or
     tail samples (the tail of an overrun case covers the extra lap of the ring)."""
-    data = cases.golden5fv()
+    data = cases.load("voices5f")
     m = data["manifest"][case["name"]]
     tr = cases.track_for(case, golden)
-    plan = float_plan(case["voice"], case["rate"], case["crate"], rows)
+    plan = float_plan(case["voice"], case["overrides"], case["rate"], case["crate"], rows)
     assert plan.info.model5 == 1 and plan.info.precision == capi.PRECISION_F32
     assert plan.info.control_steps * tr.shape[0] == m["steps"]
     audio, counts, maxabs = plan.synthesize_host(tr[None])
@@ -129,7 +107,7 @@ def test_ragged_batch_against_the_float_oracle(voice, rows):
     refs = oracle_refs(("ragged", voice), voice, cases.RATE, cases.CRATE, us)
     assert all(np.isfinite(r).all() for r in refs)
     params, frames = padded(us)
-    check_batch(*float_plan(voice, rows=rows).synthesize_host(params, frames), refs)
+    check_batch(*float_plan(voice, rows=rows).synthesize_host(params, frames), refs, True)
 
 
 @SHAPES
@@ -142,19 +120,19 @@ def test_special_case_frames(voice, rows):
     refs = oracle_refs(("edge", voice), voice, cases.RATE, cases.CRATE, us)
     assert np.isfinite(refs[1]).all()
     plan = float_plan(voice, rows=rows)
-    check_batch(*plan.synthesize_host(edge[None]), [refs[1]])
+    check_batch(*plan.synthesize_host(edge[None]), [refs[1]], True)
     params, frames = padded(us)
-    check_batch(*plan.synthesize_host(params, frames), refs)
+    check_batch(*plan.synthesize_host(params, frames), refs, True)
 
 
 @SHAPES
 @pytest.mark.parametrize("voice,rate,crate,steps", CONTROL_RATE_CASES, ids=lambda v: str(v))
 def test_control_rates(voice, rate, crate, steps, rows):
     tr = tracks.random_track(9, 7100, True)
-    plan = float_plan(voice, rate, crate, rows)
+    plan = float_plan(voice, None, rate, crate, rows)
     assert plan.info.control_steps == steps
     refs = oracle_refs(("crate", voice, rate, crate), voice, rate, crate, [tr])
-    check_batch(*plan.synthesize_host(tr[None]), refs)
+    check_batch(*plan.synthesize_host(tr[None]), refs, True)
 
 
 def test_product_library_beyond_256_utterances_of_small_child():
@@ -166,34 +144,13 @@ def test_product_library_beyond_256_utterances_of_small_child():
     idx = np.arange(batch) % len(pool_f)
     audio, counts, maxabs = float_plan("small_child").synthesize_host(pool[idx], pool_f[idx])
     refs = oracle_refs(("pool", "small_child"), "small_child", cases.RATE, cases.CRATE, [pool[t, : pool_f[t]] for t in range(len(pool_f))])
-    check_batch(audio, counts, maxabs, refs)
+    check_batch(audio, counts, maxabs, refs, True)
     for b in range(len(pool_f), batch):
         assert counts[b] == counts[b % len(pool_f)] and np.array_equal(audio[b], audio[b % len(pool_f)]), b
         assert maxabs[b] == maxabs[b % len(pool_f)]
 
 
 # ---- streams ------------------------------------------------------------------------------------------------------------
-
-def _push_in_pieces(plan, batch, total, pieces):
-    """The utterances of `batch` (total[b] frames each) pushed in pieces of at most pieces[i] frames, then finished ->
-    (samples per utterance, maxabs)."""
-    st = g.Stream(plan, len(total))
-    outs = [[] for _ in total]
-    done = np.zeros(len(total), dtype=np.int32)
-    lockstep = len(set(int(t) for t in total)) == 1
-    for n in pieces:
-        fc = np.minimum(n, total - done).astype(np.int32)
-        buf = np.zeros((len(total), n, 16), np.float32)
-        for b in range(len(total)):
-            buf[b, : fc[b]] = batch[b, done[b]: done[b] + fc[b]]
-        res = st.push(buf, None if lockstep else fc)
-        for b in range(len(total)):
-            outs[b].append(res[b])
-        done += fc
-    assert (done == total).all()
-    tails, maxabs = st.finish()
-    return [np.concatenate(outs[b] + [tails[b]]) for b in range(len(total))], maxabs
-
 
 @SHAPES
 @pytest.mark.parametrize("voice", ["small_child", "large_child"])
@@ -204,7 +161,7 @@ def test_stream_pieces_equal_the_one_shot_samples(voice, rows):
     batch = tracks.random_tracks(3, 33, seed0=7300, consonant_heavy=True)
     plan = float_plan(voice, rows=rows)
     one, c1, m1 = plan.synthesize_host(batch, total)
-    got, maxabs = _push_in_pieces(plan, batch, total, (7, 1, 25))
+    got, maxabs = push_in_pieces(plan, batch, total, (7, 1, 25))
     refs = oracle_refs(("stream", voice), voice, cases.RATE, cases.CRATE, [batch[b, : total[b]] for b in range(3)])
     for b in range(3):
         assert got[b].size == c1[b] and np.array_equal(got[b], one[b, : c1[b]]), b
@@ -217,9 +174,9 @@ def test_stream_finish_on_a_flush_overrun_of_female(rows):
     """167 frames at 44.1 kHz: finish converts the extra lap of the ring, as the one-shot launch does."""
     f, rate = cases.OVERRUN_FRAMES["female"], cases.OVERRUN_RATE["female"]
     track = tracks.random_track(f, 7400, True)
-    plan = float_plan("female", rate, rows=rows)
+    plan = float_plan("female", rate=rate, rows=rows)
     whole, counts, peak = plan.synthesize_host(track[None])
-    got, maxabs = _push_in_pieces(plan, track[None], np.array([f], dtype=np.int32), (7, 1, 25, 134))
+    got, maxabs = push_in_pieces(plan, track[None], np.array([f], dtype=np.int32), (7, 1, 25, 134))
     assert got[0].size == counts[0] == plan.output_count(f) > plan.output_count(f + 1)
     assert np.array_equal(got[0], whole[0, : counts[0]]) and maxabs[0] == peak[0]
     assert within(got[0], oracle_refs(("stream_ovr",), "female", rate, cases.CRATE, [track])[0], BIT_IDENTICAL)
@@ -240,15 +197,15 @@ def limit_utterances():
 @pytest.mark.parametrize("voice,rate", PAD96, ids=lambda v: str(v))
 def test_pad_96_in_a_ragged_batch(voice, rate, rows):
     us = limit_utterances()
-    plan = float_plan(voice, rate, rows=rows)
+    plan = float_plan(voice, rate=rate, rows=rows)
     assert plan.info.pad_size == cases.MAX_PAD
     params, frames = padded(us)
-    check_batch(*plan.synthesize_host(params, frames), oracle_refs(("pad96", voice), voice, rate, cases.CRATE, us))
+    check_batch(*plan.synthesize_host(params, frames), oracle_refs(("pad96", voice), voice, rate, cases.CRATE, us), True)
 
 
 def test_limit_plans_sit_on_the_limits():
     for voice, rate, what in cases.LIMITS:
-        info = float_plan(voice, rate).info
+        info = float_plan(voice, rate=rate).info
         if what == "pad96":
             assert info.pad_size == cases.MAX_PAD and info.upsampling == 0
         else:
@@ -260,10 +217,10 @@ def test_limit_plans_sit_on_the_limits():
 @SHAPES
 @pytest.mark.parametrize("case", cases.DOUBLE_CASES, ids=lambda c: c["name"])
 def test_double_class_reference_vectors_at_the_converter_limits(case, rows, golden):
-    data = cases.golden5fv()
+    data = cases.load("voices5f")
     m = data["manifest"][case["name"]]
     tr = cases.track_for(case, golden)
-    plan = double_plan(case["voice"], case["rate"], case["crate"], rows)
+    plan = model5_plan(case["voice"], case["overrides"], case["rate"], case["crate"], rows)
     assert plan.info.model5 == 1 and plan.info.precision == capi.PRECISION_F64
     assert abs(plan.info.internal_rate_hz - m["fs"]) < 1e-6
     assert plan.info.control_steps * tr.shape[0] == m["steps"]
@@ -283,11 +240,8 @@ def test_double_class_reference_vectors_at_the_converter_limits(case, rows, gold
 @pytest.mark.parametrize("voice,rate", PAD96, ids=lambda v: str(v))
 def test_double_class_pad_96_in_a_ragged_batch(voice, rate, rows):
     us = limit_utterances()
-    plan = double_plan(voice, rate, rows=rows)
+    plan = model5_plan(voice, rate=rate, rows=rows)
     assert plan.info.pad_size == cases.MAX_PAD
     params, frames = padded(us)
-    audio, counts, maxabs = plan.synthesize_host(params, frames)
-    for b, ref in enumerate(oracle_refs(("pad96_double", voice), voice, rate, cases.CRATE, us, float_model=0)):
-        assert counts[b] == ref.size, b
-        check_model5(audio[b, : ref.size], ref)
-        assert maxabs[b] == (np.abs(audio[b, : ref.size]).max() if ref.size else 0.0), b
+    refs = oracle_refs(("pad96_double", voice), voice, rate, cases.CRATE, us, float_model=0)
+    check_batch(*plan.synthesize_host(params, frames), refs, False)

@@ -8,14 +8,16 @@ import numpy as np
 import pytest
 
 import gama_tts_amd as g
-import golden5_voices_cases as cases
+import model5_cases as cases
 import oracle
 import voice_files
 from device_io import run_voices_device
 from parity_rules import check_model5
-from voice_cases import configs5, mixed_batch
+from voice_cases import configs5, mixed_batch, padded
 
 pytestmark = pytest.mark.gpu
+
+CASES = cases.CASES["voices5"]
 
 
 def singles_of(cfgs, params, ids, frames):
@@ -57,7 +59,7 @@ def test_five_voices_in_one_launch(plan5):
     for v, name in enumerate(voice_files.VOICES):
         sel = np.nonzero(ids == v)[0]
         for b in sel[np.argsort(frames[sel])[-2:]]:
-            ref, _ = oracle.synthesize5(cases.oracle_config(name), params[b, : frames[b]])
+            ref, _ = oracle.synthesize5(cases.voice_oracle_config(name), params[b, : frames[b]])
             assert counts[b] == ref.size
             check_model5(audio[b, : ref.size], ref)
 
@@ -73,39 +75,27 @@ def test_diagnostics_two_row_shape_gives_one_row_to_voices(plan5):
         assert np.array_equal(w, x)
 
 
-@pytest.fixture(scope="module")
-def golden5v():
-    return voice_files.golden5v()
-
-
-@pytest.mark.parametrize("rate", sorted({c["rate"] for c in cases.CASES}), ids=lambda r: "%dHz" % r)
-def test_reference_vectors_through_a_mixed_launch(rate, golden, golden5v):
+@pytest.mark.parametrize("rate", sorted({c["rate"] for c in CASES}), ids=lambda r: "%dHz" % r)
+def test_reference_vectors_through_a_mixed_launch(rate, golden):
     """The reference's own output for the four new voices, every case of this output rate in one mixed launch (a male
     utterance in between)."""
-    sel = [c for c in cases.CASES if c["rate"] == rate]
+    golden5v = cases.load("voices5")
+    sel = [c for c in CASES if c["rate"] == rate]
     trs = [cases.track_for(c, golden) for c in sel]
     male = cases.track_for(dict(track=("random", 60, 70, True)))
     trs.append(male)
     ids = np.array([voice_files.VOICES.index(c["voice"]) for c in sel] + [0], dtype=np.int32)
-    frames = np.array([t.shape[0] for t in trs], dtype=np.int32)
-    params = np.zeros((len(trs), int(frames.max()), 16), dtype=np.float32)
-    for b, t in enumerate(trs):
-        params[b, : t.shape[0]] = t
+    params, frames = padded(trs)
     plan = g.VoicesPlan(configs5(rate), 250.0, 0)
     audio, counts, maxabs = plan.synthesize_host(params, ids, frames)
     for b, c in enumerate(sel):
         m = golden5v["manifest"][c["name"]]
         assert abs(plan.voice_info(int(ids[b])).internal_rate_hz - m["fs"]) < 1e-6
         assert counts[b] == m["n"], c["name"]
-        out = audio[b, : m["n"]]
-        if c["store"] == "full":
-            check_model5(out, golden5v[c["name"] + "__out"], peak=m["maxabs"])
-        else:
-            check_model5(out[:: cases.DIGEST_STRIDE], golden5v[c["name"] + "__strided"], peak=m["maxabs"])
-        if c["store"] == "tail":
-            check_model5(out[-cases.OVERRUN_TAIL:], golden5v[c["name"] + "__tail"], peak=m["maxabs"])
+        for got, key in cases.stored(c, audio[b, : m["n"]]):
+            check_model5(got, golden5v[key], peak=m["maxabs"])
         assert maxabs[b] == pytest.approx(m["maxabs"], rel=1e-5)
-    ref, _ = oracle.synthesize5(cases.oracle_config("male", rate), male)
+    ref, _ = oracle.synthesize5(cases.voice_oracle_config("male", rate), male)
     assert counts[-1] == ref.size
     check_model5(audio[-1, : ref.size], ref)
 

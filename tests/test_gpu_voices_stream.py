@@ -9,7 +9,7 @@ import pytest
 
 import gama_tts_amd as g
 from gama_tts_amd import capi
-import golden5_voices_cases as cases5
+import model5_cases as cases5
 import oracle
 import tracks
 import voice_files
@@ -184,18 +184,14 @@ def test_workgroup_shape_changes_between_pushes(precision):
         assert samples[b].size == plan.voice_output_count(int(ids[b]), int(total[b])), b
 
 
-@pytest.fixture(scope="module")
-def golden5v():
-    return voice_files.golden5v()
-
-
-@pytest.mark.parametrize("rate", sorted({c["rate"] for c in cases5.CASES}), ids=lambda r: "%dHz" % r)
-def test_model5_five_voices_with_overrun_lengths(rate, golden, golden5v):
+@pytest.mark.parametrize("rate", sorted({c["rate"] for c in cases5.CASES["voices5"]}), ids=lambda r: "%dHz" % r)
+def test_model5_five_voices_with_overrun_lengths(rate, golden):
     """Ragged and single-frame pushes of all five 5_male voices; the overrun cases of this output rate against the
     reference's vectors."""
     cfgs = configs5(rate)
     plan = g.VoicesPlan(cfgs, 250.0, 0)
-    sel = [c for c in cases5.CASES if c["rate"] == rate and c["store"] == "tail"]
+    golden5v = cases5.load("voices5")
+    sel = [c for c in cases5.CASES["voices5"] if c["rate"] == rate and c["store"] == "tail"]
     trs = [cases5.track_for(c, golden) for c in sel]
     ids = [voice_files.VOICES.index(c["voice"]) for c in sel]
     rng = np.random.default_rng(int(rate))
@@ -218,8 +214,8 @@ def test_model5_five_voices_with_overrun_lengths(rate, golden, golden5v):
         m = golden5v["manifest"][c["name"]]
         out = samples[b]
         assert out.size == m["n"], c["name"]
-        check_model5(out[:: cases5.DIGEST_STRIDE], golden5v[c["name"] + "__strided"], peak=m["maxabs"])
-        check_model5(out[-cases5.OVERRUN_TAIL:], golden5v[c["name"] + "__tail"], peak=m["maxabs"])
+        for got, key in cases5.stored(c, out):
+            check_model5(got, golden5v[key], peak=m["maxabs"])
         assert maxabs[b] == pytest.approx(m["maxabs"], rel=1e-5)
 
 

@@ -1,36 +1,19 @@
 """Pins the VocalTractModel5 restatement (oracle/vtm_oracle_body.inc, v5_*) bit for bit against vectors of
-the real reference classes (tests/golden/vtm5_golden.npz, made by tests/golden/make_vtm5_golden.py).
-
-Oracle only: the device path does not serve reference model 5 yet; these
-pins are what a later device kernel will be tested against.
+the real reference classes (tests/golden/vtm5_golden.npz, made by tests/golden/make_model5_golden.py): what the
+device tests of model 5 (test_gpu_model5.py, test_gpu_model5_float.py) lean on.
 """
-import hashlib
-
 import numpy as np
 import pytest
 
-import golden5_cases
 import golden_cases
+import model5_cases as cases
 import oracle
 
 
-def _config(case):
-    base = oracle.read_config_file(oracle.VOICE5_MALE)
-    base.update({k: str(v) for k, v in case["overrides"].items()})
-    return oracle.config5_from_dict(base, case["rate"], case["float_model"])
-
-
-@pytest.mark.parametrize("case", golden5_cases.CASES, ids=lambda c: c["name"])
-def test_oracle5_matches_reference_vector(case, golden, golden5):
-    m = golden5["manifest"][case["name"]]
-    tr = golden5_cases.track_for(case, golden)
-    out, rate = oracle.synthesize5(_config(case), tr, case["crate"])
-    assert abs(rate - m["fs"]) < 2e-3  # the internal rate is not an integer (VocalTractModel5.h:465)
+@pytest.mark.parametrize("case", cases.CASES["vtm5"], ids=lambda c: c["name"])
+def test_oracle5_matches_reference_vector(case, golden):
+    m, tr = cases.check_oracle_vector(case, golden)
     assert round(m["fs"] / case["crate"]) * tr.shape[0] == m["steps"]
-    assert out.size == m["n"]
-    assert hashlib.sha256(out.tobytes()).hexdigest() == m["sha256"]
-    key = case["name"] + ("__out" if case["store"] == "full" else "__strided")
-    assert np.array_equal(out if case["store"] == "full" else out[:: golden5_cases.DIGEST_STRIDE], golden5[key])
 
 
 def test_survey_known_answer_model5(golden5):

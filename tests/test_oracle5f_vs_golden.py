@@ -1,36 +1,25 @@
 """Pins the float instantiation of the VocalTractModel5 restatement (oracle/vtm_oracle_body.inc, v5_*, TFloat = float) bit
 for bit against vectors of the real VocalTractModel5<float,1> (tests/golden/vtm5f_golden.npz, made by
-tests/golden/make_vtm5f_golden.py): the sine waveform, a constant mouth impedance, no noise modulation, tn_min != tn_max,
+tests/golden/make_model5_golden.py): the sine waveform, a constant mouth impedance, no noise modulation, tn_min != tn_max,
 22.05 kHz at a 500 Hz control rate, and 44.1 kHz at 106 frames (a flush-overrun length of the float converter)."""
-import hashlib
-
 import numpy as np
 import pytest
 
-import golden5f_cases
+import model5_cases as cases
 
 
-@pytest.mark.parametrize("case", golden5f_cases.CASES, ids=lambda c: c["name"])
+@pytest.mark.parametrize("case", cases.CASES["vtm5f"], ids=lambda c: c["name"])
 def test_float_oracle5_matches_reference_vector(case):
-    import oracle
-    golden = golden5f_cases.golden5f()
-    m = golden["manifest"][case["name"]]
-    tr = golden5f_cases.track_for(case)
+    m, tr = cases.check_oracle_vector(case, None)
     assert tr.shape[0] == m["frames"] <= 120
-    out, rate = oracle.synthesize5(golden5f_cases.oracle_config(case), tr, case["crate"])
-    assert abs(rate - m["fs"]) < 2e-3  # (the oracle reports the rate in mHz)
     assert round(m["fs"] / case["crate"]) * tr.shape[0] == m["steps"]
-    assert out.size == m["n"]
-    assert hashlib.sha256(out.tobytes()).hexdigest() == m["sha256"]
-    key = case["name"] + ("__out" if case["store"] == "full" else "__strided")
-    assert np.array_equal(out if case["store"] == "full" else out[:: golden5f_cases.DIGEST_STRIDE], golden[key])
 
 
 def test_the_106_frame_vector_sits_on_a_flush_overrun_of_the_float_converter():
     """44.1 kHz: 106 frames give 924 samples more than 105, and 107 give 571 fewer than 106."""
     import oracle
-    case = next(c for c in golden5f_cases.CASES if c["name"] == "ovr_m5f_44k_106f")
-    cfg = golden5f_cases.oracle_config(case)
+    case = cases.by_name("ovr_m5f_44k_106f")
+    cfg = cases.oracle_config(case)
     n = {f: oracle.synthesize5(cfg, np.zeros((f, 16), np.float32))[0].size for f in (105, 106, 107)}
-    assert n[106] == golden5f_cases.golden5f()["manifest"][case["name"]]["n"]
+    assert n[106] == cases.load("vtm5f")["manifest"][case["name"]]["n"]
     assert n[106] - n[105] == 924 and n[107] - n[106] == -571

@@ -2,7 +2,7 @@
 import numpy as np
 import pytest
 
-from parity_rules import TOL5, check_model5, within
+from parity_rules import TOL5, check_batch, check_model5, within
 
 REF = np.linspace(-1.0, 1.0, 401, dtype=np.float32) ** 3 * np.float32(0.75)  # peak 0.75 at both ends, 0.0 in the middle
 PEAK_AT, SMALL_AT = 400, 230
@@ -76,3 +76,39 @@ def test_check_model5():
     check_model5(_ulps(PEAK_AT, 1), REF, bypass=True)
     with pytest.raises(AssertionError):
         check_model5(REF[:-1], REF)
+
+
+def _launch(outs, maxabs=None):
+    """(audio, counts, maxabs) as a launch returns them, rows padded with zeros."""
+    audio = np.zeros((len(outs), max(o.size for o in outs) + 3), np.float32)
+    for b, o in enumerate(outs):
+        audio[b, : o.size] = o
+    peaks = [np.abs(o).max() if o.size else 0.0 for o in outs]
+    return audio, np.array([o.size for o in outs]), np.array(peaks if maxabs is None else maxabs, np.float32)
+
+
+@pytest.mark.parametrize("float_class", [False, True], ids=["double", "float"])
+def test_check_batch_count_maxabs_and_empty_utterances(float_class):
+    empty = np.zeros(0, np.float32)
+    refs = [REF, empty, REF[:50]]
+    check_batch(*_launch(refs), refs, float_class)
+    audio, counts, maxabs = _launch(refs)
+    with pytest.raises(AssertionError):  # a wrong count, the samples right
+        check_batch(audio, counts + [0, 0, 1], maxabs, refs, float_class)
+    with pytest.raises(AssertionError):  # a wrong maxabs
+        check_batch(audio, counts, np.nextafter(maxabs, np.float32(1.0)), refs, float_class)
+    with pytest.raises(AssertionError):  # an empty utterance has maxabs 0
+        check_batch(audio, counts, maxabs + np.float32([0, 1e-3, 0]), refs, float_class)
+
+
+def test_check_batch_holds_each_class_to_its_bar():
+    one_ulp = _ulps(SMALL_AT, 1)
+    with pytest.raises(AssertionError):  # float: bit identity
+        check_batch(*_launch([REF, one_ulp]), [REF, REF], True)
+    check_batch(*_launch([REF, one_ulp]), [REF, REF], False)
+    check_batch(*_launch([_moved(SMALL_AT, 0.9 * TOL5 * 0.75)]), [REF], False)
+    with pytest.raises(AssertionError):  # double: TOL5 of the peak
+        check_batch(*_launch([_moved(SMALL_AT, 1.1 * TOL5 * 0.75)]), [REF], False)
+    check_batch(*_launch([_moved(SMALL_AT, 1.1 * TOL5 * 0.75)]), [REF], False, peak=3.0)
+    with pytest.raises(AssertionError):  # bypass: the fp64 rule
+        check_batch(*_launch([_ulps(PEAK_AT, 2)]), [REF], False, bypass=True)

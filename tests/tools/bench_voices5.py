@@ -21,7 +21,7 @@ import torch
 sys.path.insert(0, ".")
 sys.path.insert(0, "tests")
 import gama_tts_amd as g  # noqa: E402
-import golden5_voices_cases as cases  # noqa: E402
+import model5_cases as cases  # noqa: E402
 import tracks  # noqa: E402
 from voice_cases import configs5  # noqa: E402
 from voice_files import VOICES  # noqa: E402

@@ -1,6 +1,7 @@
 """Product configurations and plans of the voices of voice_files.py: the five 0_male variants and their reference model 5
-counterparts (fixture list and oracle configuration of the latter: golden5_voices_cases.py); the plan of the male voice
-with overrides that the parity tests start from; and a ragged batch that mixes the voices."""
+counterparts (fixture list and oracle configuration of the latter: model5_cases.py); the plan of the male voice with
+overrides that the parity tests start from, the model 5 plan of any voice in either class; utterances to a padded batch
+and through a stream in pieces; and a ragged batch that mixes the voices."""
 import ctypes
 
 import numpy as np
@@ -21,11 +22,49 @@ def male_plan(overrides=None, rate=44100.0, delay=1, crate=250.0, precision=capi
                   diagnostics=bool(rows) if diagnostics is None else diagnostics, rows=rows)
 
 
-def male5_plan(overrides=None, rate=48000.0, crate=250.0, rows=0):
-    """The same for reference model 5 (rows 1: one tube wavefront, chunk 60; 2: two, chunk 24)."""
-    d = g.read_config_file(oracle.VOICE5_MALE)
+def model5_plan(voice="male", overrides=None, rate=48000.0, crate=250.0, rows=0, float_class=False, device=0, diagnostics=None):
+    """The same for reference model 5 and one of its five voices: VocalTractModel5<double,1> (rows 1: one tube wavefront,
+    chunk 60; 2: two, chunk 24) or, float_class=True, VocalTractModel5<float,1> (rows 1: chunk 60; 2: chunk 56).
+    device=capi.DEVICE_NONE: a design-only plan."""
+    d = g.read_config_file(voice_path(voice, True))
     d.update({k: str(v) for k, v in (overrides or {}).items()})
-    return g.Plan(g.config5_from_dict(d, rate), crate, 0, diagnostics=bool(rows), rows=rows)
+    cfg = g.config5_from_dict(d, rate, capi.PRECISION_F32 if float_class else capi.PRECISION_F64)
+    return g.Plan(cfg, crate, device, diagnostics=bool(rows) if diagnostics is None else diagnostics, rows=rows,
+                  float_model5=float_class)
+
+
+def male5_plan(overrides=None, rate=48000.0, crate=250.0, rows=0):
+    return model5_plan("male", overrides, rate, crate, rows)
+
+
+def padded(utterances):
+    """Utterances of different lengths -> (params [B][max frames][16], frame counts)."""
+    frames = np.array([u.shape[0] for u in utterances], dtype=np.int32)
+    params = np.zeros((len(utterances), max(1, int(frames.max())), 16), np.float32)
+    for b, u in enumerate(utterances):
+        params[b, : u.shape[0]] = u
+    return params, frames
+
+
+def push_in_pieces(plan, batch, total, pieces):
+    """The utterances of `batch` (total[b] frames each) pushed into a stream in pieces of at most pieces[i] frames, then
+    finished -> (samples per utterance, maxabs)."""
+    st = g.Stream(plan, len(total))
+    outs = [[] for _ in total]
+    done = np.zeros(len(total), dtype=np.int32)
+    lockstep = len(set(int(t) for t in total)) == 1
+    for n in pieces:
+        fc = np.minimum(n, total - done).astype(np.int32)
+        buf = np.zeros((len(total), n, 16), np.float32)
+        for b in range(len(total)):
+            buf[b, : fc[b]] = batch[b, done[b]: done[b] + fc[b]]
+        res = st.push(buf, None if lockstep else fc)
+        for b in range(len(total)):
+            outs[b].append(res[b])
+        done += fc
+    assert (done == total).all()
+    tails, maxabs = st.finish()
+    return [np.concatenate(outs[b] + [tails[b]]) for b in range(len(total))], maxabs
 
 
 def configs(rate=44100.0, delay=1, precision=capi.PRECISION_F64, layout=0, names=VOICES):
