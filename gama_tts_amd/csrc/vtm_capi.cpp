@@ -158,6 +158,8 @@ struct gvtm_plan {
 	{
 		return gvtm::synth_launch_shape(designs.data(), n_voices(), precision, batch, forced_rows ? forced_rows : rows, voices, stream_ring, fit);
 	}
+	// the ring a stream keeps for voice v (not model 5): the one-row shape's, whatever shape a launch of the stream takes
+	int stream_ring(int v) const { return gvtm::synth_launch_shape(&designs[v], 1, precision, 1, 1, false).ring; }
 };
 
 namespace {
@@ -484,6 +486,31 @@ int gvtm_debug_launch_shape(const gvtm_plan* plan, size_t batch, int voices, siz
 	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
 	out[0] = static_cast<size_t>(shape.rows), out[1] = static_cast<size_t>(shape.ring), out[2] = shape.lds;
 	return GVTM_OK;
+}
+
+/* The same for a launch of a single-voice stream (not model 5) whose `batch` utterances are pushed in lockstep, which is
+   how they share workgroups: the stream keeps the one-row shape's ring for every shape, so rows that fit a one-shot
+   launch may not fit here and give way to half as many. */
+int gvtm_debug_stream_launch_shape(const gvtm_plan* plan, size_t batch, size_t out[3])
+{
+	if (!plan || !out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or buffer");
+	if (plan->designs[0].model5 || plan->n_voices() != 1) return fail(GVTM_ERR_UNSUPPORTED, "a single-voice plan of the models 0 to 4");
+	const gvtm::LaunchShape shape = plan->launch_shape(batch, 0, false, plan->stream_ring(0));
+	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
+	out[0] = static_cast<size_t>(shape.rows), out[1] = static_cast<size_t>(shape.ring), out[2] = shape.lds;
+	return GVTM_OK;
+}
+
+/* The chunk length (internal steps per tick) of the kernel shape a one-shot launch of `batch` utterances of this plan
+   takes: synth_chunk_length of the rows launch_synthesis picks.  0: no shape (model 5, or none fits); negative: a null
+   plan.  Needs no device. */
+int gvtm_debug_chunk_length(const gvtm_plan* plan, size_t batch)
+{
+	if (!plan) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (plan->designs[0].model5) return 0;
+	const gvtm::LaunchShape shape = plan->launch_shape(batch, 0, false);
+	if (!shape.rows) return 0;
+	return gvtm::synth_chunk_length(plan->designs[0].k, plan->precision, shape.rows);
 }
 
 /* The plan-level noise-sample table as the host builds it (n floats or doubles); needs no device. */
@@ -1481,7 +1508,7 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 				s->granule_frames.push_back(4u / gcd_u(k.control_steps, 4u));
 			} else {
 				// each voice's ring is the one-row shape's, whatever shape a launch takes (the kernel derives it per voice)
-				const int xr = gvtm::synth_launch_shape(&plan->designs[v], 1, plan->precision, 1, 1, false).ring;
+				const int xr = plan->stream_ring(v);
 				s->xr = std::max(s->xr, xr);
 				s->state_stride = std::max(s->state_stride, gvtm::stream_state_bytes(k, plan->precision, xr));
 				// the serial wavefronts work in blocks of 2, 4 and 4 or 6 steps (vtm_kernel_v2.inc): their states are exact at

@@ -1181,10 +1181,15 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			// maximum of every 16-lane row by DPP rotations (lanes that have left the pass supply 0), one LDS atomic per row
 			// and utterance.  (The butterfly over the whole wavefront with __shfl_xor was six ds_bpermute round trips in a
 			// row per utterance -- 24 dependent LDS round trips at the end of a pass, most of its ~7800 cycles.)
+			// row_rotate<N> hands lane i the value of lane i - N (mod 16): by 15, 14, 12 and 8 a lane takes in lanes i + 1,
+			// i + 2, i + 4 and i + 8, the following lanes, so the row's first lane ends up with the maximum of the whole
+			// row -- also of a row that is cut short, whose lanes that left are its last ones (the end of every launch of
+			// a stream, and of its first emission up to the aligned grid).  (By 1, 2, 4 and 8 the first lane of a cut row
+			// took in the lanes that had left and published its own sample alone.)
 			float mx = fabsf(y);
-			mx = fmaxf(mx, row_rotate<1>(mx));
-			mx = fmaxf(mx, row_rotate<2>(mx));
-			mx = fmaxf(mx, row_rotate<4>(mx));
+			mx = fmaxf(mx, row_rotate<15>(mx));
+			mx = fmaxf(mx, row_rotate<14>(mx));
+			mx = fmaxf(mx, row_rotate<12>(mx));
 			mx = fmaxf(mx, row_rotate<8>(mx));
 			if ((hl & 15) == 0) atomicMax(&sm.peak[u0 + u], __float_as_uint(mx));
 		}

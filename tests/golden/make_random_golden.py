@@ -23,7 +23,7 @@ import tracks  # noqa: E402
 
 # (reference model, seed, frames, consonant_heavy, output rate, voice)
 CASES = [(m, s, 90, bool(s & 1), 44100, oracle.VOICE_MALE)
-         for m in ("0", "2", "2:2", "3", "4", "1", "2f:2", "2f:4", "4f") for s in (11, 12)]
+         for m in ("0", "2", "2:2", "2:4", "3", "4", "1", "2f:2", "2f:4", "4f") for s in (11, 12)]
 CASES += [(m, s, 60, s % 2 == 0, 48000, oracle.VOICE5_MALE) for m in ("5", "5f") for s in (31, 32)]
 
 

@@ -361,8 +361,8 @@ def _run_driver(exe, params, model, output_rate, control_rate, config, repeat, t
 # already initialised HIP.
 
 def _job_male(job):
-    track, rate, delay, layout, float_model = job
-    return synthesize(male_config(rate, delay, layout, float_model=float_model), track)
+    track, rate, delay, layout, float_model = job[:5]
+    return synthesize(male_config(rate, delay, layout, float_model=float_model), track, *job[5:])
 
 
 def _job_male5(job):
@@ -371,7 +371,8 @@ def _job_male5(job):
 
 
 def synthesize_many(jobs, workers=8, model5=False):
-    """jobs: [(track[F][16], rate, delay, layout, float_model)] (model5: [(track, rate)]) -> list of oracle outputs."""
+    """jobs: [(track[F][16], rate, delay, layout, float_model)], or with a sixth member, the control rate (250 Hz without);
+    model5: [(track, rate)] -> list of oracle outputs."""
     from concurrent.futures import ThreadPoolExecutor
 
     jobs = list(jobs)

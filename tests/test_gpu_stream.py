@@ -10,7 +10,7 @@ from gama_tts_amd import capi
 import oracle
 import tracks
 from parity_rules import largest_error_within
-from voice_cases import male5_plan, male_plan
+from voice_cases import male5_plan, male_plan, push_in_pieces
 
 pytestmark = pytest.mark.gpu
 
@@ -66,6 +66,20 @@ def test_single_frame_pushes_and_reset():
     out = [st.push(b[None, i: i + 1])[0] for i in range(17)]
     tail, _ = st.finish()
     assert np.array_equal(np.concatenate(out + [tail[0]]), ref_b)
+
+
+def test_peak_of_frame_by_frame_pushes_is_the_largest_sample():
+    """maxabs of a stream is the largest of ALL its samples.  A launch of a stream begins its output off the 64-sample
+    grid and ends off it, so the resampler pass's 16-lane rows are cut short at both ends of every launch; the samples of a
+    cut row count like any other.  (A kernel that published a cut row's first sample alone lost the peak of half of these
+    utterances: at 22.05 kHz and a 500 Hz control rate a launch per frame is 44 samples, less than three rows.)"""
+    plan = male_plan(rate=22050.0, crate=500.0, precision=capi.PRECISION_F32)
+    params = tracks.random_tracks(16, 40, seed0=6700, consonant_heavy=True)
+    whole, counts, peak = plan.synthesize_host(params)
+    outs, maxabs = push_in_pieces(plan, params, np.full(16, 40, dtype=np.int32), [1] * 40)
+    for b in range(16):
+        assert np.array_equal(outs[b], whole[b, : counts[b]]), b
+        assert maxabs[b] == peak[b] == np.abs(outs[b]).max(), b
 
 
 def test_empty_and_tiny_utterances():

@@ -11,7 +11,7 @@ import oracle
 import tracks
 
 
-@pytest.mark.parametrize("model,delay,layout,fm", [("0", 1, 0, 0), ("2", 1, 0, 0), ("2:2", 2, 0, 0), ("3", 3, 0, 0), ("4", 1, 1, 0),
+@pytest.mark.parametrize("model,delay,layout,fm", [("0", 1, 0, 0), ("2", 1, 0, 0), ("2:2", 2, 0, 0), ("2:4", 4, 0, 0), ("3", 3, 0, 0), ("4", 1, 1, 0),
                                                     ("1", 1, 0, 1), ("2f:2", 2, 0, 1), ("2f:4", 4, 0, 1), ("4f", 1, 1, 1)])
 @pytest.mark.parametrize("seed", [11, 12])
 def test_bit_identical_on_random_tracks(model, delay, layout, fm, seed):

@@ -13,12 +13,14 @@ import tracks
 from voice_files import VOICES, voice_path
 
 
-def male_plan(overrides=None, rate=44100.0, delay=1, crate=250.0, precision=capi.PRECISION_F64, layout=0, rows=0, diagnostics=None):
+def male_plan(overrides=None, rate=44100.0, delay=1, crate=250.0, precision=capi.PRECISION_F64, layout=0, rows=0, diagnostics=None,
+              device=0):
     """A plan of the male voice with `overrides` on its file.  rows != 0: a plan of the diagnostics library (same kernels)
-    with that many utterances per workgroup forced; diagnostics=True asks for that library with nothing forced."""
+    with that many utterances per workgroup forced; diagnostics=True asks for that library with nothing forced.
+    device=capi.DEVICE_NONE: a design-only plan."""
     d = g.read_config_file(oracle.VOICE_MALE)
     d.update({k: str(v) for k, v in (overrides or {}).items()})
-    return g.Plan(g.config_from_dict(d, rate, delay, precision, layout), crate, 0,
+    return g.Plan(g.config_from_dict(d, rate, delay, precision, layout), crate, device,
                   diagnostics=bool(rows) if diagnostics is None else diagnostics, rows=rows)
 
 
