@@ -208,6 +208,9 @@ def load_library(diagnostics=False):
     if hasattr(L, "gvtm_plan_create_model5_float"):
         L.gvtm_plan_create_model5_float.argtypes = [ctypes.POINTER(Config5), dbl, i32, ctypes.POINTER(vp)]
         L.gvtm_plan_create_model5_float.restype = i32
+    if hasattr(L, "gvtm_plan_create_model5_float_voices"):
+        L.gvtm_plan_create_model5_float_voices.argtypes = [ctypes.POINTER(Config5), sz, dbl, i32, ctypes.POINTER(vp)]
+        L.gvtm_plan_create_model5_float_voices.restype = i32
     L.gvtm_plan_set_timing.argtypes = [vp, i32]
     L.gvtm_plan_set_timing.restype = i32
     L.gvtm_plan_take_kernel_ms.argtypes = [vp, ctypes.POINTER(i32)]
@@ -523,10 +526,11 @@ class Plan:
 
 class VoicesPlan(Plan):
     """Owns a gvtm_plan of several voices: configs[v] is voice v, all Config (gvtm_plan_create_voices) or all Config5
-    (gvtm_plan_create_model5_voices).  Its batches mix voices, one voice id per utterance; the single-voice entries
-    (Plan.synthesize_*, Stream) are refused on it when it has two or more."""
+    (gvtm_plan_create_model5_voices; with float_model5=True, and precision PRECISION_F32 in every Config5, the float class
+    through gvtm_plan_create_model5_float_voices).  Its batches mix voices, one voice id per utterance; the single-voice
+    entries (Plan.synthesize_*, Stream) are refused on it when it has two or more."""
 
-    def __init__(self, configs, control_rate=250.0, device=0, diagnostics=False, rows=0):
+    def __init__(self, configs, control_rate=250.0, device=0, diagnostics=False, rows=0, float_model5=False):
         self._lib = load_library(diagnostics)
         self.diagnostics = bool(diagnostics)
         self._h = ctypes.c_void_p()
@@ -535,7 +539,10 @@ class VoicesPlan(Plan):
         model5 = isinstance(self.config, Config5)
         if any(isinstance(c, Config5) != model5 for c in self.configs):
             raise TypeError("a plan's voices are all Config or all Config5")
-        ctype, create = (Config5, self._lib.gvtm_plan_create_model5_voices) if model5 else (Config, self._lib.gvtm_plan_create_voices)
+        if float_model5 and not model5:
+            raise ValueError("float_model5 needs Config5 voices")
+        create5 = "gvtm_plan_create_model5_float_voices" if float_model5 else "gvtm_plan_create_model5_voices"
+        ctype, create = (Config5, getattr(self._lib, create5)) if model5 else (Config, self._lib.gvtm_plan_create_voices)
         arr = (ctype * max(len(self.configs), 1))(*self.configs)
         self._check(create(arr, len(self.configs), float(control_rate), int(device), ctypes.byref(self._h)))
         self.n_voices = int(self._lib.gvtm_plan_voice_count(self._h))

@@ -118,6 +118,7 @@ struct gvtm_plan {
 	int device = 0;
 	int precision = GVTM_PRECISION_F64;
 	int rows = 0;       // utterances per workgroup; 0 = by batch size (a diagnostics build can force it)
+	bool float5_voices = false; // made by gvtm_plan_create_model5_float_voices: a float model 5 plan that takes the voices entries
 	// design tables on the device: double, or float (as designed) for GVTM_PRECISION_F32
 	DeviceBuffer d_wavetable, d_fir, d_src_h, d_src_dh;
 	DeviceBuffer d_consts, d_consts5; // gvtm::DeviceConstants, gvtm::Model5Constants (model 5 plans only)
@@ -258,10 +259,11 @@ int upload_tables(gvtm_plan* plan)
 }
 
 // Every plan: `differs` refuses a voice that does not share `shared_keys` with voice 0, `design` designs each voice
-// (gvtm_config: design_plan, gvtm5_config: design_plan5 or design_plan5_float), and upload_tables puts the tables on the device
+// (gvtm_config: design_plan, gvtm5_config: design_plan5 or design_plan5_float), and upload_tables puts the tables on the device;
+// float5_voices: the plan is gvtm_plan_create_model5_float_voices'
 template <typename Config, typename Differs>
 int create_plan(const Config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out, const char* shared_keys,
-		Differs differs, std::string (*design)(const Config&, double, gvtm::Design&))
+		Differs differs, std::string (*design)(const Config&, double, gvtm::Design&), bool float5_voices = false)
 {
 	if (!configs || !plan_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null config or plan_out");
 	*plan_out = nullptr;
@@ -280,7 +282,8 @@ int create_plan(const Config* configs, size_t n_voices, double control_rate, int
 			const std::string why = design(configs[v], control_rate, plan->designs[v]);
 			if (!why.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, n_voices > 1 ? "voice " + std::to_string(v) + ": " + why : why);
 		}
-		plan->precision = configs[0].precision; // (model 5: fp64, the only precision its design takes)
+		plan->precision = configs[0].precision; // (model 5: the one precision the design of its class takes)
+		plan->float5_voices = float5_voices;
 		if (device == GVTM_DEVICE_NONE) {
 			// design-only plan: info, tables and output counts work, synthesis reports NO_DEVICE
 			plan->device = GVTM_DEVICE_NONE;
@@ -408,6 +411,12 @@ int gvtm_plan_create_model5_float(const gvtm5_config* config, double control_rat
 {
 	auto differs = [](const gvtm5_config&, const gvtm5_config&) { return false; }; // (one voice)
 	return create_plan(config, 1, control_rate, device, plan_out, "", differs, gvtm::design_plan5_float);
+}
+
+int gvtm_plan_create_model5_float_voices(const gvtm5_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out)
+{
+	auto differs = [](const gvtm5_config& c0, const gvtm5_config& c) { return c.output_rate != c0.output_rate || c.precision != c0.precision; };
+	return create_plan(configs, n_voices, control_rate, device, plan_out, "output_rate and precision", differs, gvtm::design_plan5_float, true);
 }
 
 void gvtm_plan_destroy(gvtm_plan* plan)
@@ -890,8 +899,9 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 		if (rc != GVTM_OK) return rc;
 	}
 	const bool model5 = plan->designs[0].model5;
-	if (r.voices && model5 && plan->designs[0].f32) {
-		return fail(GVTM_ERR_UNSUPPORTED, "the float model 5 has no launch of several voices (gvtm_plan_create_model5_float: one voice per plan)");
+	if (r.voices && model5 && plan->designs[0].f32 && !plan->float5_voices) {
+		return fail(GVTM_ERR_UNSUPPORTED, "a gvtm_plan_create_model5_float plan has no launch of several voices (one voice per plan; "
+				"gvtm_plan_create_model5_float_voices makes the float plans that have)");
 	}
 	const gvtm::LaunchShape shape = plan->launch_shape(r.batch, r.rows, r.voices, r.sl ? r.sl->xr : 0);
 	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");

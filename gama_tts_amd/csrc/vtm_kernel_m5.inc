@@ -1,8 +1,9 @@
 // Reference model 5 (VocalTractModel5<double,1>, vtm/VocalTractModel5.h) on the device.
 // Included inside namespace gvtm, after vtm_kernel_v2.inc (whose wave-wide DPP helpers, Extent and voice_row it shares),
-// by three translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
-// (kVoices5Flag) and vtm_kernels_m5f.hip the float class, VocalTractModel5<float,1> (kFloat5Flag), each in a code object of
-// its own.  Besides the kernel, the file defines what they launch it with: the description of its shapes (m5_shape,
+// by four translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
+// (kVoices5Flag), vtm_kernels_m5f.hip the float class, VocalTractModel5<float,1> (kFloat5Flag), and vtm_kernels_m5fv.hip
+// the voice variant of the float class (both flags), each in a code object of its own.  Besides the kernel, the file
+// defines what they launch it with: the description of its shapes (m5_shape,
 // kM5Ring), before the kernel, and the LDS bytes and the launch of a shape (m5_lds_bytes, launch_synth5_shape), at the end.
 //
 // Same organisation as generation 2: a workgroup owns U utterances (1 or 2; the tube has 30 + 21 = 51 sections, one
@@ -130,7 +131,8 @@ struct Offsets {
 
 } // namespace
 
-// Several voices in one launch (gvtm_synthesize_voices_device on a gvtm_plan_create_model5_voices plan): the kernel's last
+// Several voices in one launch (gvtm_synthesize_voices_device on a gvtm_plan_create_model5_voices or
+// gvtm_plan_create_model5_float_voices plan): the kernel's last
 // template argument carries, besides the utterances per workgroup in bits 0-1, the flag kVoices5Flag (default off; one
 // utterance per workgroup only).  With it, workgroup g synthesizes utterance a.row_map[g] of voice a.group_voice[g] (-1: a
 // group past the last voice's, which exits at once) from that voice's constants a.kconst[voice] and a.k5const[voice].
@@ -138,8 +140,9 @@ struct Offsets {
 // stream state) follow the row map.  As in vtm_kernel_v2.inc (kVoicesFlag), each voice-dependent expression is a conditional on the
 // constant VOICES, so the single-voice kernels compile to the code they had before the flag existed.
 constexpr int kVoices5Flag = 4;
-// VocalTractModel5<float,1> (gvtm_plan_create_model5_float; instantiated by vtm_kernels_m5f.hip alone, which compiles with
-// FMA contraction off): the flag kFloat5Flag in the same argument makes R, the type of every LDS record, every recurrence
+// VocalTractModel5<float,1> (gvtm_plan_create_model5_float and _float_voices; instantiated by vtm_kernels_m5f.hip and, with
+// kVoices5Flag, vtm_kernels_m5fv.hip alone, which compile with FMA contraction off): the flag kFloat5Flag in the same
+// argument makes R, the type of every LDS record, every recurrence
 // and the tube, float instead of double.  The constants arrive as floats widened in the double fields of DeviceConstants /
 // Model5Constants and are narrowed where they are used (R(k5.x): exact); the resampler's table is the float design's; a
 // stream's state keeps its double slots (Stream5Layout), a float stored widened being exact; the noise generator's seed
@@ -169,7 +172,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 	constexpr bool FLOAT = (U_FLAGS & kFloat5Flag) != 0;
 	using R = std::conditional_t<FLOAT, float, double>;
 	using R2 = typename Pair<R>::type;
-	static_assert(!FLOAT || (U == 1 && !VOICES), "the float class has the one-utterance, one-voice shape only");
+	static_assert(!FLOAT || U == 1, "the float class has the one-utterance shape only");
 	static_assert(!VOICES || U == 1, "the voice variant has the one-utterance shape only");
 	int voice = 0;
 	if constexpr (VOICES) {
@@ -1260,12 +1263,13 @@ static size_t m5_lds_bytes()
 }
 
 // The launch of shape (FLOAT, INDEX).  VOICES: a launch of several voices (the kernel's kVoices5Flag; args.row_map is
-// set), the double class's one-utterance shape only; `batch` is then the number of workgroups
+// set), a one-utterance shape only (the double class's, either of the float class's); `batch` is then the number of
+// workgroups
 template <bool FLOAT, int INDEX, bool VOICES = false>
 static hipError_t launch_synth5_shape(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
 	constexpr M5Shape s = m5_shape(FLOAT, INDEX);
-	static_assert(!VOICES || (s.rows == 1 && !FLOAT), "the voice variant has the double class's one-utterance shape only");
+	static_assert(!VOICES || s.rows == 1, "the voice variant has the one-utterance shapes only");
 	auto fn = m5::vtm5_synth_kernel<s.chunk, s.helpers, kM5Ring, s.rows | (VOICES ? m5::kVoices5Flag : 0) | (FLOAT ? m5::kFloat5Flag : 0)>;
 	const size_t lds = m5_lds_bytes<FLOAT, INDEX>();
 	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));

@@ -4,7 +4,8 @@
 //                      5 + NH wavefronts with fixed roles (tube, scans, pre-/post-tube filters, interpolation, helpers),
 //                      software-pipelined over chunks of internal-rate steps with one barrier per tick; see that file's header
 //   vtm5_synth_kernel  (vtm_kernel_m5.inc)  VocalTractModel5 semantics, same organisation (its voice variant is compiled
-//                      in vtm_kernels_m5v.hip, its float class in vtm_kernels_m5f.hip)
+//                      in vtm_kernels_m5v.hip, its float class in vtm_kernels_m5f.hip, that class's voice variant in
+//                      vtm_kernels_m5fv.hip)
 //   vtm_normalize_kernel                    output scaling of Controller::writeOutputToBuffer / writeOutputToFile
 //
 // Which shape a launch has (rows, chunk length, helpers, ring, LDS) is decided here and only here: "kernel shapes" below.
@@ -240,9 +241,9 @@ LaunchShape synth_launch_shape(const Design* voices, int n_voices, int precision
 		// latency-bound, so a chunk of 24 steps costs what one of 60 does, and the tube wavefronts slow down from 268 to
 		// 430 cycles per step next to five busy helpers.  Only forcing picks it (tests hold it to the one-utterance shape's
 		// samples bit for bit), and not for the voice variant, which has the one-utterance shape only.
-		// The float class (one utterance per workgroup, one voice): up to one workgroup per compute unit the chunk of 60
-		// steps; beyond, the chunk of 56, whose 80 800 B let two workgroups share a compute unit (DESIGN.md 4b has the
-		// measurement).
+		// The float class (one utterance per workgroup; one voice or, in its voice variant, several: the same rule): up to
+		// one workgroup per compute unit the chunk of 60 steps; beyond, the chunk of 56, whose 80 800 B let two workgroups
+		// share a compute unit (DESIGN.md 4b has the measurement).
 		const bool float_class = precision == GVTM_PRECISION_F32;
 		const int index = float_class ? (forced_rows == 1 ? 0 : (forced_rows == 2 || batch > 256 ? 1 : 0)) : (forced_rows == 2 && !several_voices ? 1 : 0);
 		const M5Shape m = m5_shape(float_class, index);
@@ -335,8 +336,13 @@ hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream)
 hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int index, hipStream_t stream)
 {
 	if (!args.k5const || (index != 0 && index != 1)) return hipErrorInvalidValue;
-	// (the float class lives in vtm_kernels_m5f.hip, as the voice variant does in vtm_kernels_m5v.hip)
-	if (precision == GVTM_PRECISION_F32) return launch_synth5_float(args, batch, index, stream);
+	// (the float class lives in vtm_kernels_m5f.hip, as the voice variant does in vtm_kernels_m5v.hip, and the float class's
+	// voice variant in vtm_kernels_m5fv.hip)
+	if (precision == GVTM_PRECISION_F32) {
+		if (!args.row_map) return launch_synth5_float(args, batch, index, stream);
+		if (!args.group_voice) return hipErrorInvalidValue;
+		return launch_synth5_float_voices(args, batch, index, stream);
+	}
 	// (the voice variant lives in vtm_kernels_m5v.hip: this file's code object keeps the single-voice kernels only)
 	if (!args.row_map) {
 		if (index == 1) return launch_synth5_shape<false, 1>(args, batch, stream);

@@ -156,13 +156,16 @@ size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr);
 hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream);
 // reference model 5: VocalTractModel5<double,1> (GVTM_PRECISION_F64) or VocalTractModel5<float,1> (GVTM_PRECISION_F32) in
 // the shape `index` (0 or 1: LaunchShape::forced - 1) of that class; with args.row_map set (several voices: one constants
-// block of each kind per voice) the double class's index 0 only, and `batch` is the number of workgroups.
+// block of each kind per voice) the double class's index 0 only or either index of the float class, and `batch` is the
+// number of workgroups.
 hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int index, hipStream_t stream);
 // the float class alone (vtm_kernels_m5f.hip; launch_synth5 calls it), and the LDS bytes of a workgroup of its shape `index`
 hipError_t launch_synth5_float(const SynthArgs& args, size_t batch, int index, hipStream_t stream);
 size_t synth5_float_lds_bytes(int index);
 // the voice variant alone (vtm_kernels_m5v.hip; launch_synth5 calls it): `groups` workgroups of one utterance each
 hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_t stream);
+// the voice variant of the float class alone (vtm_kernels_m5fv.hip; launch_synth5 calls it), in the float class's shape `index`
+hipError_t launch_synth5_float_voices(const SynthArgs& args, size_t groups, int index, hipStream_t stream);
 constexpr int kDppSelftestInts = 640;
 hipError_t launch_dpp_selftest(int* d_out /* [kDppSelftestInts] */, hipStream_t stream);
 hipError_t launch_float_math_probe(int kind, const float* d_x, size_t n, float* d_out, hipStream_t stream);

@@ -40,7 +40,8 @@
  *   gvtm_plan_set_voice_tracks / gvtm_generate_tracks_voices_device / gvtm_synthesize_events_voices_device
  *                               the same for a batch that mixes voices: one EventList set-up per voice
  *                               (vtm_control_model/Controller.cpp:70-81)
- *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_synthesize_voices_*
+ *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
+ *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
  *                               (data/voice/english/0_male/vtm.txt resp. 5_male/vtm.txt + variant/{male,female,
  *                               large_child,small_child,baby}.txt, merged by Controller.cpp:48-49), all of them in one launch
@@ -140,7 +141,7 @@ typedef struct gvtm_info {
 	int32_t device;
 	int32_t precision;
 	int32_t section_delay;
-	int32_t model5;                   /* 1 for a plan made by gvtm_plan_create_model5 / _model5_voices / _model5_float */
+	int32_t model5;                   /* 1 for a plan made by gvtm_plan_create_model5 / _model5_voices / _model5_float / _model5_float_voices */
 	int32_t reserved_;
 	double internal_rate_hz;          /* the internal rate as the model holds it: an integer for models 0-4, not for
 	                                     model 5 (vtm/VocalTractModel5.h:465 keeps it in TFloat) */
@@ -177,7 +178,7 @@ typedef struct gvtm5_config {
 	double mouth_impedance_radius;            /* used when constant_radius_mouth_impedance != 0 */
 	int32_t precision;                        /* GVTM_PRECISION_F64 for gvtm_plan_create_model5 / _model5_voices: the factory's
 	                                             model 5 is VocalTractModel5<double,1> (vtm/VocalTractModel.cpp:47-48);
-	                                             GVTM_PRECISION_F32 for gvtm_plan_create_model5_float */
+	                                             GVTM_PRECISION_F32 for gvtm_plan_create_model5_float / _model5_float_voices */
 	int32_t reserved_;                        /* must be 0 */
 } gvtm5_config;
 
@@ -216,7 +217,8 @@ int gvtm_plan_create_model5(const gvtm5_config* config, double control_rate, int
  * same synthesis, stream and events entry points, every constant designed in float as the class's constructors do and
  * every rounding of its steps reproduced, so the samples are bit-identical to that class's.  gvtm_plan_info reports
  * model5 = 1, precision = GVTM_PRECISION_F32 and the float class's internal_rate_hz; gvtm_plan_table serves the float
- * resampler tables (widened).  One voice per plan: the gvtm_synthesize_voices_* entries refuse it (GVTM_ERR_UNSUPPORTED). */
+ * resampler tables (widened).  One voice per plan: the gvtm_synthesize_voices_* entries refuse it (GVTM_ERR_UNSUPPORTED);
+ * gvtm_plan_create_model5_float_voices makes the float plans they take. */
 int gvtm_plan_create_model5_float(const gvtm5_config* config, double control_rate, int device, gvtm_plan** plan_out);
 void gvtm_plan_destroy(gvtm_plan* plan);
 int gvtm_plan_info(const gvtm_plan* plan, gvtm_info* info_out);
@@ -300,7 +302,15 @@ int    gvtm_plan_create_voices(const gvtm_config* configs, size_t n_voices, doub
  * (the one-utterance shape of model 5), so voices whose internal rates differ (longer and shorter tracts) share a launch
  * without changing each other's shape. */
 int    gvtm_plan_create_model5_voices(const gvtm5_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out);
-/* Number of voices of a plan (1 for gvtm_plan_create / _model5 plans); a negative status for a null plan. */
+/* The same for the float class, VocalTractModel5<float,1>: every config's precision must be GVTM_PRECISION_F32, and a voice
+ * the float design refuses, as gvtm_plan_create_model5_float would, fails the call with a message naming it.  Voice v's
+ * utterances come out bit for bit as a gvtm_plan_create_model5_float plan made from configs[v] synthesizes them.  One set
+ * of float converter tables serves every voice.  The plan takes every several-voices entry point (synthesis, streams,
+ * voice tracks and event lists); with n_voices == 1 it takes the single-voice entries as well.  The plan remembers that
+ * this entry made it: a gvtm_plan_create_model5_float plan keeps refusing the gvtm_synthesize_voices_* entries.  The kernel
+ * runs one utterance per workgroup in the float class's two shapes, chosen by the batch size as for one voice. */
+int    gvtm_plan_create_model5_float_voices(const gvtm5_config* configs, size_t n_voices, double control_rate, int device, gvtm_plan** plan_out);
+/* Number of voices of a plan (1 for gvtm_plan_create / _model5 / _model5_float plans); a negative status for a null plan. */
 int    gvtm_plan_voice_count(const gvtm_plan* plan);
 /* gvtm_plan_info of one voice (internal rate, control steps, converter increments and up-sampling differ by voice; model 5
  * voices: model5 = 1 and the voice's non-integer internal_rate_hz). */
