@@ -161,6 +161,16 @@ struct gvtm_plan {
 	}
 	// the ring a stream keeps for voice v (not model 5): the one-row shape's, whatever shape a launch of the stream takes
 	int stream_ring(int v) const { return gvtm::synth_launch_shape(&designs[v], 1, precision, 1, 1, false).ring; }
+	// the ring the LDS of a stream's launches is sized for: the longest of the voices' (each voice keeps its own in the kernel)
+	int longest_stream_ring() const
+	{
+		int xr = 0;
+		for (int v = 0; v < n_voices(); ++v) xr = std::max(xr, stream_ring(v));
+		return xr;
+	}
+	// the shape of a launch on behalf of a stream whose LDS holds rings of xr samples; a stream of a plan of several
+	// voices launches the voice variant (gvtm_stream_create_voices)
+	gvtm::LaunchShape stream_launch_shape(size_t batch, int forced_rows, int xr) const { return launch_shape(batch, forced_rows, n_voices() > 1, xr); }
 };
 
 namespace {
@@ -497,14 +507,15 @@ int gvtm_debug_launch_shape(const gvtm_plan* plan, size_t batch, int voices, siz
 	return GVTM_OK;
 }
 
-/* The same for a launch of a single-voice stream (not model 5) whose `batch` utterances are pushed in lockstep, which is
-   how they share workgroups: the stream keeps the one-row shape's ring for every shape, so rows that fit a one-shot
-   launch may not fit here and give way to half as many. */
+/* The same for a launch of a stream (not model 5) whose `batch` utterances are pushed in lockstep, which is how they
+   share workgroups: the stream keeps the one-row shape's ring for every shape, so rows that fit a one-shot launch may
+   not fit here and give way to half as many.  A plan of several voices answers for a gvtm_stream_create_voices stream:
+   the voice variant, its LDS sized for the longest of the voices' stream rings. */
 int gvtm_debug_stream_launch_shape(const gvtm_plan* plan, size_t batch, size_t out[3])
 {
 	if (!plan || !out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or buffer");
-	if (plan->designs[0].model5 || plan->n_voices() != 1) return fail(GVTM_ERR_UNSUPPORTED, "a single-voice plan of the models 0 to 4");
-	const gvtm::LaunchShape shape = plan->launch_shape(batch, 0, false, plan->stream_ring(0));
+	if (plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "a plan of the models 0 to 4");
+	const gvtm::LaunchShape shape = plan->stream_launch_shape(batch, 0, plan->longest_stream_ring());
 	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
 	out[0] = static_cast<size_t>(shape.rows), out[1] = static_cast<size_t>(shape.ring), out[2] = shape.lds;
 	return GVTM_OK;
@@ -903,7 +914,8 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 		return fail(GVTM_ERR_UNSUPPORTED, "a gvtm_plan_create_model5_float plan has no launch of several voices (one voice per plan; "
 				"gvtm_plan_create_model5_float_voices makes the float plans that have)");
 	}
-	const gvtm::LaunchShape shape = plan->launch_shape(r.batch, r.rows, r.voices, r.sl ? r.sl->xr : 0);
+	// (a stream's launches are the voice variant's exactly when its plan has several voices: create_stream)
+	const gvtm::LaunchShape shape = r.sl ? plan->stream_launch_shape(r.batch, r.rows, r.sl->xr) : plan->launch_shape(r.batch, r.rows, r.voices);
 	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
 	const int rows = shape.rows;
 
@@ -1509,6 +1521,7 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 		s->batch = batch;
 		s->voices = voice_ids != nullptr;
 		if (s->voices) s->voice_ids.assign(voice_ids, voice_ids + batch);
+		if (!plan->designs[0].model5) s->xr = plan->longest_stream_ring();
 		for (int v = 0; v < plan->n_voices(); ++v) {
 			const gvtm::DeviceConstants& k = plan->designs[v].k;
 			if (plan->designs[0].model5) {
@@ -1519,7 +1532,6 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 			} else {
 				// each voice's ring is the one-row shape's, whatever shape a launch takes (the kernel derives it per voice)
 				const int xr = plan->stream_ring(v);
-				s->xr = std::max(s->xr, xr);
 				s->state_stride = std::max(s->state_stride, gvtm::stream_state_bytes(k, plan->precision, xr));
 				// the serial wavefronts work in blocks of 2, 4 and 4 or 6 steps (vtm_kernel_v2.inc): their states are exact at
 				// multiples of 12 steps, so a push synthesizes a multiple of 12 / gcd(control_steps, 12) frames and keeps the rest

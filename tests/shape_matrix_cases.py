@@ -23,7 +23,6 @@ different DPP rows of a two- or four-row workgroup, and the last workgroup is pa
 import collections
 import ctypes
 import functools
-import math
 
 import numpy as np
 
@@ -140,9 +139,12 @@ def oracle_job(cell, track, crate=250.0):
 
 def residues(steps, chunk):
     """The lengths of a last chunk (0: a whole one) that launch (a) asks for: none, the shortest and the longest partial
-    one a multiple of `steps` steps can leave."""
-    step = math.gcd(steps, chunk)
-    return (0, step % chunk, (chunk - step) % chunk)
+    one a multiple of `steps` steps can leave within MAX_FRAMES_A frames.  On the male voice every cell reaches 0,
+    gcd(steps, chunk) and chunk - gcd(steps, chunk); a voice whose steps per frame share no factor with a long chunk
+    (187 steps, chunk 144) ends no utterance of up to 48 frames on a whole chunk and has the other two only."""
+    reach = {(f * steps) % chunk for f in range(1, MAX_FRAMES_A + 1)}
+    partial = reach - {0}
+    return tuple(sorted(reach & {0}) + ([min(partial), max(partial)] if partial else []))
 
 
 def _fill(out, n, draw):

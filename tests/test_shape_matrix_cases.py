@@ -10,6 +10,8 @@ that what tests/test_gpu_shape_matrix.py runs on the device is what its docstrin
     one step per frame at control rate = internal rate;
     launch (a)'s frame counts end on the residues they claim, launch (b)'s sit around the chunk edges;
     gvtm_output_count is the oracle's count for every length of both launches, and gvtm_output_capacity holds it."""
+import math
+
 import numpy as np
 
 import oracle
@@ -108,6 +110,8 @@ def test_frame_counts_of_both_launches():
         chunk, steps = chunk_length(plan), int(plan.info.control_steps)
         fa = frames_a(chunk, steps, seed_of(c))
         assert fa.size == POOL == len(set(fa.tolist())) and {0, 1, 2} <= set(fa.tolist()) and fa.max() <= MAX_FRAMES_A, (cell_id(c), fa)
+        step = math.gcd(steps, chunk)
+        assert set(residues(steps, chunk)) == {0, step % chunk, (chunk - step) % chunk}, cell_id(c)  # all three in reach
         for r in residues(steps, chunk):
             assert 0 <= r < chunk
             assert [f for f in fa if f > 0 and (int(f) * steps) % chunk == r], (cell_id(c), r, fa)

@@ -48,10 +48,10 @@ def padded(utterances):
     return params, frames
 
 
-def push_in_pieces(plan, batch, total, pieces):
+def push_in_pieces(plan, batch, total, pieces, voice_ids=None):
     """The utterances of `batch` (total[b] frames each) pushed into a stream in pieces of at most pieces[i] frames, then
-    finished -> (samples per utterance, maxabs)."""
-    st = g.Stream(plan, len(total))
+    finished -> (samples per utterance, maxabs).  voice_ids: utterance b's voice, on a plan of several voices."""
+    st = g.Stream(plan, len(total), voice_ids=voice_ids)
     outs = [[] for _ in total]
     done = np.zeros(len(total), dtype=np.int32)
     lockstep = len(set(int(t) for t in total)) == 1
