@@ -202,6 +202,13 @@ def load_library(diagnostics=False):
         L.gvtm_generate_tracks_voices_device.restype = i32
         L.gvtm_synthesize_events_voices_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
         L.gvtm_synthesize_events_voices_device.restype = i32
+    if hasattr(L, "gvtm_tracks_chunks_frame_count"):
+        L.gvtm_tracks_chunks_frame_count.argtypes = [ctypes.POINTER(TrackConfig), vp, vp, sz]
+        L.gvtm_tracks_chunks_frame_count.restype = sz
+        L.gvtm_generate_tracks_chunks_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
+        L.gvtm_generate_tracks_chunks_device.restype = i32
+        L.gvtm_synthesize_events_chunks_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
+        L.gvtm_synthesize_events_chunks_device.restype = i32
     if hasattr(L, "gvtm_plan_create_model5_voices"):
         L.gvtm_plan_create_model5_voices.argtypes = [ctypes.POINTER(Config5), sz, dbl, i32, ctypes.POINTER(vp)]
         L.gvtm_plan_create_model5_voices.restype = i32
@@ -348,6 +355,17 @@ def tracks_frame_count(config, events):
     lib = load_library()
     events = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
     n = lib.gvtm_tracks_frame_count(ctypes.byref(config), _ptr(events), events.shape[0])
+    if n == ctypes.c_size_t(-1).value:
+        raise GvtmError(1, lib.gvtm_last_error().decode())
+    return n
+
+
+def tracks_chunks_frame_count(config, events, chunk_offsets):
+    """gvtm_tracks_chunks_frame_count: the frames of one utterance whose chunk c owns events[chunk_offsets[c]:chunk_offsets[c + 1]]."""
+    lib = load_library()
+    events = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
+    chunk_offsets = np.ascontiguousarray(chunk_offsets, dtype=np.int64)
+    n = lib.gvtm_tracks_chunks_frame_count(ctypes.byref(config), _ptr(events), _ptr(chunk_offsets), max(chunk_offsets.shape[0] - 1, 0))
     if n == ctypes.c_size_t(-1).value:
         raise GvtmError(1, lib.gvtm_last_error().decode())
     return n
@@ -591,6 +609,21 @@ class VoicesPlan(Plan):
         self._check(self._lib.gvtm_synthesize_events_voices_device(
             self._h, _ptr(d_events), _ptr(d_offsets), _ptr(d_voice_ids), int(batch), int(max_frames), _ptr(d_audio),
             int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift), _ptr(stream)))
+
+    def generate_tracks_chunks_device(self, d_events, d_chunk_offsets, d_utt_chunks, d_voice_ids, batch, max_frames, d_params,
+                                      d_frame_counts=None, d_drift=None, stream=None):
+        """gvtm_generate_tracks_chunks_device: utterances of several event lists; all pointers are device memory."""
+        self._check(self._lib.gvtm_generate_tracks_chunks_device(
+            self._h, _ptr(d_events), _ptr(d_chunk_offsets), _ptr(d_utt_chunks), _ptr(d_voice_ids), int(batch), int(max_frames),
+            _ptr(d_params), _ptr(d_frame_counts), _ptr(d_drift), _ptr(stream)))
+
+    def synthesize_events_chunks_device(self, d_events, d_chunk_offsets, d_utt_chunks, d_voice_ids, batch, max_frames, d_audio,
+                                        audio_stride, d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, stream=None):
+        """Utterances of several event lists in, samples out (gvtm_synthesize_events_chunks_device); all pointers are device
+        memory."""
+        self._check(self._lib.gvtm_synthesize_events_chunks_device(
+            self._h, _ptr(d_events), _ptr(d_chunk_offsets), _ptr(d_utt_chunks), _ptr(d_voice_ids), int(batch), int(max_frames),
+            _ptr(d_audio), int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift), _ptr(stream)))
 
     def _host_args(self, params, voice_ids, frame_counts):
         params = np.ascontiguousarray(params, dtype=np.float32)

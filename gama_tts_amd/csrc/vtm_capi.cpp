@@ -651,6 +651,20 @@ size_t gvtm_tracks_frame_count(const gvtm_track_config* config, const gvtm_event
 	return gvtm::tracks_frame_count(k.control_period, events, n_events);
 }
 
+size_t gvtm_tracks_chunks_frame_count(const gvtm_track_config* config, const gvtm_event* events, const int64_t* chunk_offsets, size_t n_chunks)
+{
+	if (!config || (n_chunks > 0 && (!events || !chunk_offsets))) { fail(GVTM_ERR_INVALID_ARGUMENT, "null config, events or chunk_offsets"); return static_cast<size_t>(-1); }
+	gvtm::TrackConstants k;
+	const char* why = gvtm::design_tracks(*config, k);
+	if (why[0]) { fail(GVTM_ERR_INVALID_ARGUMENT, why); return static_cast<size_t>(-1); }
+	size_t n = 0;
+	for (size_t c = 0; c < n_chunks; ++c) {
+		if (chunk_offsets[c] < 0 || chunk_offsets[c + 1] < chunk_offsets[c]) { fail(GVTM_ERR_INVALID_ARGUMENT, "chunk_offsets must not decrease"); return static_cast<size_t>(-1); }
+		n += gvtm::tracks_frame_count(k.control_period, events + chunk_offsets[c], static_cast<size_t>(chunk_offsets[c + 1] - chunk_offsets[c]));
+	}
+	return n;
+}
+
 int gvtm_generate_tracks_device(int device, const gvtm_track_config* config, const gvtm_event* d_events,
 		const int64_t* d_event_offsets, size_t batch, size_t max_frames, float* d_params, int32_t* d_frame_counts,
 		gvtm_drift_state* d_drift, void* hip_stream)
@@ -1035,31 +1049,47 @@ int gvtm_plan_set_voice_tracks(gvtm_plan* plan, const gvtm_track_config* configs
 
 namespace {
 
-// What the two events-voices entries share up to the tracks launch: the checks in the order the header gives them, then the
-// voice variant of the tracks kernel on the caller's stream.
-int launch_voice_tracks(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets, const int32_t* d_voice_ids, size_t batch,
-		size_t max_frames, float* d_params, int32_t* d_frame_counts, gvtm_drift_state* d_drift, void* hip_stream)
+// The event lists of a batch that mixes voices: one list per utterance (d_offsets [batch + 1], the events-voices entries) or
+// several (chunked: d_offsets the chunks' event offsets, d_utt_chunks [batch + 1] the utterances' chunks)
+struct VoiceEvents {
+	const gvtm_event* d_events;
+	const int64_t* d_offsets;
+	const int32_t* d_voice_ids;
+	bool chunked = false;
+	const int64_t* d_utt_chunks = nullptr;
+};
+
+// What the events-voices and events-chunks entries share up to the tracks launch: the checks in the order the header gives
+// them, then the voice or the chunk variant of the tracks kernel on the caller's stream.
+int launch_voice_tracks(gvtm_plan* plan, const VoiceEvents& lists, size_t batch, size_t max_frames, float* d_params, int32_t* d_frame_counts, gvtm_drift_state* d_drift, void* hip_stream)
 {
 	if (batch == 0) return GVTM_OK;
-	if (!d_events || !d_event_offsets || !d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events, event_offsets or voice ids");
+	if (!lists.d_events || !lists.d_offsets || !lists.d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events, offsets or voice ids");
+	if (lists.chunked && !lists.d_utt_chunks) return fail(GVTM_ERR_INVALID_ARGUMENT, "null utt_chunks");
 	if (!d_params && max_frames > 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	// frames leave the kernel as float4 stores
 	if (reinterpret_cast<uintptr_t>(d_params) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params must be 16-byte aligned");
 	if (batch > 0x7fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
-	gvtm::TrackVoicesArgs args{};
+	gvtm::TrackChunksArgs args{};
 	args.k.control_period = plan->voice_tracks[0].control_period; // (every voice's is the plan's: gvtm_plan_set_voice_tracks)
-	args.events = d_events;
-	args.event_offsets = d_event_offsets;
+	args.events = lists.d_events;
+	if (lists.chunked) {
+		args.chunk_offsets = lists.d_offsets;
+		args.utt_chunks = lists.d_utt_chunks;
+	} else {
+		args.event_offsets = lists.d_offsets;
+	}
 	args.batch = batch;
 	args.max_frames = max_frames;
 	args.params = d_params;
 	args.frame_counts = d_frame_counts;
 	args.drift = d_drift;
 	args.voice_k = static_cast<const gvtm::TrackConstants*>(plan->d_voice_tracks.ptr);
-	args.voice_ids = d_voice_ids;
+	args.voice_ids = lists.d_voice_ids;
 	args.n_voices = plan->n_voices();
-	const hipError_t e = gvtm::launch_tracks_voices(args, static_cast<hipStream_t>(hip_stream));
-	if (e != hipSuccess) return fail_hip(e, "track generation launch (voices)");
+	const hipError_t e = lists.chunked ? gvtm::launch_tracks_chunks(args, static_cast<hipStream_t>(hip_stream))
+	                                   : gvtm::launch_tracks_voices(args, static_cast<hipStream_t>(hip_stream));
+	if (e != hipSuccess) return fail_hip(e, lists.chunked ? "track generation launch (chunks)" : "track generation launch (voices)");
 	return GVTM_OK;
 }
 
@@ -1072,26 +1102,21 @@ int check_voice_tracks_plan(const gvtm_plan* plan, const char* entry)
 	return GVTM_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int gvtm_generate_tracks_voices_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets, const int32_t* d_voice_ids,
-		size_t batch, size_t max_frames, float* d_params, int32_t* d_frame_counts, gvtm_drift_state* d_drift, void* hip_stream)
+int generate_voice_tracks(gvtm_plan* plan, const char* entry, const VoiceEvents& lists, size_t batch, size_t max_frames, float* d_params,
+		int32_t* d_frame_counts, gvtm_drift_state* d_drift, void* hip_stream)
 {
-	const int rc = check_voice_tracks_plan(plan, "gvtm_generate_tracks_voices_device");
+	const int rc = check_voice_tracks_plan(plan, entry);
 	if (rc != GVTM_OK) return rc;
 	DeviceScope scope(plan->device);
 	const hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	return launch_voice_tracks(plan, d_events, d_event_offsets, d_voice_ids, batch, max_frames, d_params, d_frame_counts, d_drift, hip_stream);
+	return launch_voice_tracks(plan, lists, batch, max_frames, d_params, d_frame_counts, d_drift, hip_stream);
 }
 
-int gvtm_synthesize_events_voices_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets, const int32_t* d_voice_ids,
-		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs,
-		gvtm_drift_state* d_drift, void* hip_stream)
+int synthesize_voice_events(gvtm_plan* plan, const char* entry, const VoiceEvents& lists, size_t batch, size_t max_frames, float* d_audio,
+		size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream)
 {
-	int rc = check_voice_tracks_plan(plan, "gvtm_synthesize_events_voices_device");
+	int rc = check_voice_tracks_plan(plan, entry);
 	if (rc != GVTM_OK) return rc;
 	if (batch == 0) return GVTM_OK;
 	// (what the synthesis launch would refuse is refused before the tracks kernel advances the drift states)
@@ -1106,11 +1131,45 @@ int gvtm_synthesize_events_voices_device(gvtm_plan* plan, const gvtm_event* d_ev
 	if ((e = plan->async.params.ensure(sizeof(float) * batch * std::max<size_t>(max_frames, 1) * GVTM_N_PARAM)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
 	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
 	int32_t* const counts = d_frame_counts ? d_frame_counts : static_cast<int32_t*>(plan->async.frames.ptr);
-	rc = launch_voice_tracks(plan, d_events, d_event_offsets, d_voice_ids, batch, max_frames, static_cast<float*>(plan->async.params.ptr), counts, d_drift,
-			hip_stream);
+	rc = launch_voice_tracks(plan, lists, batch, max_frames, static_cast<float*>(plan->async.params.ptr), counts, d_drift, hip_stream);
 	if (rc != GVTM_OK) return rc;
 	return launch_synthesis(plan, LaunchRequest{static_cast<const float*>(plan->async.params.ptr), counts, batch, max_frames, d_audio, audio_stride,
-			d_out_counts, d_maxabs, hip_stream, 0, true, d_voice_ids, &plan->async.groups});
+			d_out_counts, d_maxabs, hip_stream, 0, true, lists.d_voice_ids, &plan->async.groups});
+}
+
+} // namespace
+
+extern "C" {
+
+int gvtm_generate_tracks_voices_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets, const int32_t* d_voice_ids,
+		size_t batch, size_t max_frames, float* d_params, int32_t* d_frame_counts, gvtm_drift_state* d_drift, void* hip_stream)
+{
+	return generate_voice_tracks(plan, "gvtm_generate_tracks_voices_device", VoiceEvents{d_events, d_event_offsets, d_voice_ids}, batch, max_frames,
+			d_params, d_frame_counts, d_drift, hip_stream);
+}
+
+int gvtm_synthesize_events_voices_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets, const int32_t* d_voice_ids,
+		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs,
+		gvtm_drift_state* d_drift, void* hip_stream)
+{
+	return synthesize_voice_events(plan, "gvtm_synthesize_events_voices_device", VoiceEvents{d_events, d_event_offsets, d_voice_ids}, batch, max_frames,
+			d_audio, audio_stride, d_frame_counts, d_out_counts, d_maxabs, d_drift, hip_stream);
+}
+
+int gvtm_generate_tracks_chunks_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_chunk_offsets, const int64_t* d_utt_chunks,
+		const int32_t* d_voice_ids, size_t batch, size_t max_frames, float* d_params, int32_t* d_frame_counts, gvtm_drift_state* d_drift,
+		void* hip_stream)
+{
+	return generate_voice_tracks(plan, "gvtm_generate_tracks_chunks_device", VoiceEvents{d_events, d_chunk_offsets, d_voice_ids, true, d_utt_chunks}, batch,
+			max_frames, d_params, d_frame_counts, d_drift, hip_stream);
+}
+
+int gvtm_synthesize_events_chunks_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_chunk_offsets, const int64_t* d_utt_chunks,
+		const int32_t* d_voice_ids, size_t batch, size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts,
+		int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream)
+{
+	return synthesize_voice_events(plan, "gvtm_synthesize_events_chunks_device", VoiceEvents{d_events, d_chunk_offsets, d_voice_ids, true, d_utt_chunks},
+			batch, max_frames, d_audio, audio_stride, d_frame_counts, d_out_counts, d_maxabs, d_drift, hip_stream);
 }
 
 } // extern "C"

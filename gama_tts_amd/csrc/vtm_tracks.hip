@@ -18,6 +18,9 @@
 // 0.31 ms per 4096 x 80 events (0.37 with one utterance per wavefront).  (Also measured: a separate writer wavefront per utterance, 0.51 ms -- two wavefronts per
 // utterance halve the utterances in flight; the events themselves staged in LDS, 1.29 ms -- 24-32 KB per utterance leave 4-6
 // workgroups per compute unit; four utterances per wavefront, 1.14 ms -- the rows diverge at their boundaries.)
+// Utterances of several lists (vtm_tracks_chunks_kernel, below), five voices interleaved, one process: 4096 x 4 chunks x 20
+// events 0.272 ms beside 4096 x 80 events through the voices kernel 0.298 ms (the 80-event lists as one chunk each: 0.264 ms;
+// per frame the restarts of a 20-event chunk -- table, first deltas, first staged boundary -- cost about 8 %).
 // Bit parity with the reference: same double operations in the same order, no FMA contraction.
 #include "vtm_tracks.hpp"
 
@@ -278,6 +281,196 @@ __global__ __launch_bounds__(64) void vtm_tracks_voices_kernel(const TrackVoices
 	tracks_workgroup<ROWS, true>(a);
 }
 
+// An utterance of several event lists (TrackChunksArgs), walked by the lanes of its row as tracks_row walks one list: the
+// row takes the utterance's chunks one after the other.  Carried from chunk to chunk: the frame counter n -- and with it
+// the place in the ring, which still leaves 32 frames at a time at out + first * 16 with `first` counted over the whole
+// utterance, the partial flush once after the last chunk -- and the drift state.  Everything else starts again per chunk
+// as in a fresh generateOutput() call (EventList.cpp:938-983): values and deltas from the chunk's event 0, the special
+// parameters at 0, the polynomial from initial_pitch, now = 0, target = 1, the staged boundary data and the table, which
+// is rebuilt in the row's one `ahead` (LDS per workgroup is what the other two kernels use).
+// The per-list walk is a copy of tracks_row's and not shared with it, so that the two kernels above keep their code.
+template <int LW>
+__device__ __forceinline__ void tracks_chunks_row(const TrackChunksArgs& a, size_t utt, int l, float (*ring)[16], unsigned char (*ahead)[32])
+{
+#pragma clang fp contract(off)
+	const int j = l & 15; // parameter
+	const int32_t voice = a.voice_ids[utt];
+	if (voice < 0 || voice >= a.n_voices) { // (as tracks_row: nothing of the utterance is read or written)
+		if (l == 0 && a.frame_counts) a.frame_counts[utt] = 0;
+		return;
+	}
+	TrackConstants k = a.voice_k[voice];
+	k.control_period = a.k.control_period;
+	const int cp = k.control_period;
+	const bool walker = l < 16;
+	float* out = a.params + utt * a.max_frames * 16;
+	gvtm_drift_state ds = {0.7892347, 0.0, 0.0, 0.0, 0.0}; // DriftGenerator.cpp:28, :40
+	if (j == 0 && a.drift) ds = a.drift[utt];
+	size_t n = 0; // frames of the utterance so far
+
+	auto flush = [&](size_t first, size_t end) { // (as tracks_row's)
+		if (end > a.max_frames) end = a.max_frames;
+		const float4* src = reinterpret_cast<const float4*>(&ring[0][0]);
+		float4* dst = reinterpret_cast<float4*>(out + first * 16);
+		for (int q = l; q < kRingFrames * 4; q += LW) {
+			if (first + static_cast<size_t>(q >> 2) < end) dst[q] = src[q];
+		}
+	};
+
+	const int64_t chunk_end = a.utt_chunks[utt + 1];
+	for (int64_t chunk = a.utt_chunks[utt]; chunk < chunk_end; ++chunk) {
+		const gvtm_event* ev = a.events + a.chunk_offsets[chunk];
+		const int64_t n_events = a.chunk_offsets[chunk + 1] - a.chunk_offsets[chunk];
+		if (n_events < 2) continue; // EventList.cpp:932-934: no frames, and the drift generator is not asked
+		const bool tabled = n_events <= kTableEvents;
+		// the previous chunk's walk has read the table for the last time: its LDS reads stay in front of the rebuild's writes
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+		if (tabled) {
+			const int ne = static_cast<int>(n_events);
+			for (int c = l; c < 32; c += LW) {
+				int last = ne + kFar; // none so far
+				ahead[ne][c] = kFar;
+#pragma unroll 8
+				for (int q = ne - 1; q >= 0; --q) {
+					if (!is_empty(column(ev + q, c))) last = q;
+					const int d = last - q;
+					ahead[q][c] = static_cast<unsigned char>(d < kFar ? d : kFar);
+				}
+			}
+		}
+		double cur = ev[0].param[j], delta = 0.0, scur = 0.0, sdelta = 0.0; // :944-954
+		{
+			int64_t q = 1;
+			double value;
+			while (is_empty(value = ev[q].param[j])) {
+				if (++q >= n_events) break;
+			}
+			if (q < n_events) delta = ((value - cur) / ev[q].time_ms) * cp;
+		}
+		double pa = 0.0, pb = 0.0, pc = 0.0, pd = 0.0; // :959-981
+		if (j == 0 && k.macro_intonation) {
+			int64_t q = 0;
+			for (; q < n_events; ++q) {
+				if (ev[q].has_interp) break;
+			}
+			if (q < n_events) {
+				const double y1 = k.initial_pitch;
+				const double x2 = ev[q].time_ms;
+				const double* d = ev[q].interp;
+				if (k.smooth_intonation) {
+					const double y2 = x2 * (x2 * (x2 * d[0] + d[1]) + d[2]) + d[3];
+					pc = (y2 - y1) / x2;
+					pd = y1;
+				} else {
+					const double y2 = x2 * d[0] + d[1];
+					pa = (y2 - y1) / x2;
+					pb = y1;
+				}
+			}
+		}
+		// the table is complete (as in tracks_row)
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+
+		auto first_set = [&](int64_t q, int c) -> int64_t {
+			if (tabled) {
+				const int d = ahead[q][c];
+				return d < kFar ? q + d : n_events;
+			}
+			while (q < n_events && is_empty(column(ev + q, c))) ++q;
+			return q;
+		};
+		auto stage = [&](int64_t T) { // T <= n_events
+			Staged st;
+			const gvtm_event* pe = ev + (T - 1);
+			st.prev_p = pe->param[j];
+			st.prev_s = pe->special[j];
+			st.prev_has_interp = pe->has_interp;
+			st.i0 = pe->interp[0]; st.i1 = pe->interp[1]; st.i2 = pe->interp[2]; st.i3 = pe->interp[3];
+			const int64_t Tc = T < n_events ? T : n_events - 1;
+			st.time_t = ev[Tc].time_ms;
+			const int64_t qp = first_set(Tc, j), qs = first_set(Tc, 16 + j);
+			st.next_p = HUGE_VAL; st.next_s = HUGE_VAL; st.next_p_time = 0; st.next_s_time = 0;
+			if (qp < n_events) { st.next_p = ev[qp].param[j]; st.next_p_time = ev[qp].time_ms; }
+			if (qs < n_events) { st.next_s = ev[qs].special[j]; st.next_s_time = ev[qs].time_ms; }
+			return st;
+		};
+
+		int64_t target = 1;
+		int target_time = ev[1].time_ms;
+		Staged st = stage(2);
+		int now = 0;
+		while (target < n_events) { // :988-1086
+			float p = static_cast<float>(cur + scur);
+			if (j == 0) {
+				if (!k.micro_intonation) p = 0.0f;
+				if (k.intonation_drift) { // DriftGenerator::drift (DriftGenerator.cpp:72-84)
+					const double temp = ds.seed * 377.0;
+					ds.seed = temp - static_cast<int>(temp);
+					const double x = (ds.seed * k.pitch_deviation) - k.pitch_offset;
+					const double y = k.b0 * (x + ds.x2) + k.b1 * ds.x1 - k.a1 * ds.y1 - k.a2 * ds.y2;
+					ds.x2 = ds.x1;
+					ds.x1 = x;
+					ds.y2 = ds.y1;
+					ds.y1 = y;
+					p += static_cast<float>(y);
+				}
+				if (k.macro_intonation) {
+					const double x = now;
+					const double intonation = k.smooth_intonation ? x * (x * (x * pa + pb) + pc) + pd : x * pa + pb;
+					p += static_cast<float>(intonation);
+				}
+				p += static_cast<float>(k.mean_pitch);
+			}
+			if (walker) ring[n % kRingFrames][j] = p;
+			++n;
+			if (n % kRingFrames == 0) flush(n - kRingFrames, n);
+
+			if (delta != 0.0) cur += delta;
+			if (sdelta != 0.0) scur += sdelta;
+			now += cp;
+			if (now >= target_time) {
+				if (++target == n_events) break;
+				const Staged s0 = st;
+				st = stage(target + 1);
+				target_time = s0.time_t;
+				if (!is_empty(s0.prev_p)) { // :1035-1052
+					delta = is_empty(s0.next_p) ? 0.0 : ((s0.next_p - cur) / (s0.next_p_time - now)) * cp;
+				}
+				if (!is_empty(s0.prev_s)) { // :1053-1070
+					sdelta = is_empty(s0.next_s) ? 0.0 : ((s0.next_s - scur) / (s0.next_s_time - now)) * cp;
+				}
+				if (j == 0 && k.macro_intonation && s0.prev_has_interp) { // :1072-1084
+					pa = s0.i0;
+					pb = s0.i1;
+					if (k.smooth_intonation) {
+						pc = s0.i2;
+						pd = s0.i3;
+					}
+				}
+			}
+		}
+	}
+	if (n % kRingFrames != 0) flush(n - n % kRingFrames, n);
+	if (l == 0) {
+		if (a.frame_counts) a.frame_counts[utt] = static_cast<int32_t>(n);
+		if (a.drift) a.drift[utt] = ds;
+	}
+}
+
+// the chunk variant: ROWS utterances per workgroup of one wavefront, as the two kernels above, each row walking its
+// utterance's chunks in order (a kernel of its own, so that those two keep their arguments and their code).  Timings: the
+// head of this file.
+template <int ROWS>
+__global__ __launch_bounds__(64) void vtm_tracks_chunks_kernel(const TrackChunksArgs a)
+{
+	__shared__ __attribute__((aligned(16))) float ring[ROWS][kRingFrames][16];
+	__shared__ unsigned char ahead[ROWS][kTableEvents + 1][32]; // (as tracks_workgroup's: one table per row, rebuilt per chunk)
+	const int tid = threadIdx.x;
+	const int row = tid / (64 / ROWS), l = tid % (64 / ROWS);
+	const size_t utt = static_cast<size_t>(blockIdx.x) * ROWS + row;
+	if (utt < a.batch) tracks_chunks_row<64 / ROWS>(a, utt, l, ring[row], ahead[row]);
+}
+
 hipError_t launch_tracks(const TrackArgs& args, hipStream_t stream)
 {
 	if (args.batch == 0) return hipSuccess;
@@ -297,6 +490,14 @@ hipError_t launch_tracks_voices(const TrackVoicesArgs& args, hipStream_t stream)
 	if (args.batch == 0) return hipSuccess;
 	constexpr int kRows = GVTM_TRACK_ROWS; // (as launch_tracks)
 	hipLaunchKernelGGL(vtm_tracks_voices_kernel<kRows>, dim3(static_cast<unsigned>((args.batch + kRows - 1) / kRows)), dim3(64), 0, stream, args);
+	return hipGetLastError();
+}
+
+hipError_t launch_tracks_chunks(const TrackChunksArgs& args, hipStream_t stream)
+{
+	if (args.batch == 0) return hipSuccess;
+	constexpr int kRows = GVTM_TRACK_ROWS; // (as launch_tracks)
+	hipLaunchKernelGGL(vtm_tracks_chunks_kernel<kRows>, dim3(static_cast<unsigned>((args.batch + kRows - 1) / kRows)), dim3(64), 0, stream, args);
 	return hipGetLastError();
 }
 

@@ -36,4 +36,16 @@ struct TrackVoicesArgs : TrackArgs {
 
 hipError_t launch_tracks_voices(const TrackVoicesArgs& args, hipStream_t stream);
 
+// Utterances of several event lists ("chunks": Controller::getParametersFromPhoneticString runs generateOutput() once per
+// /c chunk of the phonetic string, on one parameter list and with one drift generator, Controller.cpp:141-154).  Utterance
+// b owns the chunks [utt_chunks[b], utt_chunks[b + 1]), chunk c the events [chunk_offsets[c], chunk_offsets[c + 1]); its
+// frames are the chunks' frames one after the other, max_frames and frame_counts[b] count all of them, and drift[b] runs
+// on from chunk to chunk.  event_offsets is not read.  Everything else as TrackVoicesArgs.
+struct TrackChunksArgs : TrackVoicesArgs {
+	const int64_t* chunk_offsets;  // [chunks + 1], device memory
+	const int64_t* utt_chunks;     // [batch + 1], device memory
+};
+
+hipError_t launch_tracks_chunks(const TrackChunksArgs& args, hipStream_t stream);
+
 } // namespace gvtm

@@ -40,6 +40,9 @@
  *   gvtm_plan_set_voice_tracks / gvtm_generate_tracks_voices_device / gvtm_synthesize_events_voices_device
  *                               the same for a batch that mixes voices: one EventList set-up per voice
  *                               (vtm_control_model/Controller.cpp:70-81)
+ *   gvtm_generate_tracks_chunks_device / gvtm_synthesize_events_chunks_device
+ *                               the same for utterances of several event lists: the loop over the /c chunks of
+ *                               Controller::getParametersFromPhoneticString (vtm_control_model/Controller.cpp:141-154)
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
@@ -531,6 +534,51 @@ int gvtm_generate_tracks_voices_device(gvtm_plan* plan, const gvtm_event* d_even
 int gvtm_synthesize_events_voices_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_event_offsets,
 		const int32_t* d_voice_ids, size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
 		int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream);
+
+/*
+ * Utterances of several event lists.  The reference builds an utterance that way: Controller::getParametersFromPhoneticString
+ * (Controller.cpp:141-154) cuts the phonetic string at its /c markers (the text parser emits one chunk per phrase) and, per
+ * chunk, runs eventList_.setUp(), parses and calls eventList_.generateOutput(vtmParamList_) on the same parameter list: the
+ * utterance's frames are the chunks' frames one after the other, and the drift generator (one per Controller, never
+ * reseeded) runs on from chunk to chunk.  Here two offset tables describe the batch:
+ *   chunk_offsets  [n_chunks + 1] int64, non-decreasing: chunk c owns the events [chunk_offsets[c], chunk_offsets[c+1])
+ *   utt_chunks     [batch + 1] int64, non-decreasing: utterance b owns the chunks [utt_chunks[b], utt_chunks[b+1])
+ * Each chunk is generated as a list of its own (values, deltas, intonation polynomial and time start again, as in a fresh
+ * generateOutput() call); a chunk of fewer than two events yields nothing and leaves the drift state alone, an utterance
+ * without chunks yields 0 frames.
+ */
+
+/* Frames of one utterance of n_chunks chunks: the sum over the chunks of gvtm_tracks_frame_count (host-side, no device
+ * needed).  (size_t)-1 on a bad configuration, on a null argument with n_chunks > 0 (a null config always) and on offsets
+ * that decrease; 0 for n_chunks == 0. */
+size_t gvtm_tracks_chunks_frame_count(const gvtm_track_config* config, const gvtm_event* events,
+		const int64_t* chunk_offsets, size_t n_chunks);
+
+/* gvtm_generate_tracks_voices_device for utterances of several chunks, in one launch for the whole batch (the tables are
+ * device memory: the host never learns a count).  The frames of utterance b are the concatenation, over its chunks, of the
+ * frames gvtm_generate_tracks_voices_device yields for the chunk as a list of its own under voice d_voice_ids[b], the drift
+ * state a chunk leaves being the next chunk's; d_drift[b] leaves as the last chunk left it.  d_frame_counts[b] is the
+ * utterance's total, and max_frames is per utterance, all chunks together: frames beyond it are dropped, the count and the
+ * drift state still cover all of them.  With one chunk per utterance everything is bit for bit the voices entry's.
+ * Everything not named here -- the track configurations (gvtm_plan_set_voice_tracks), the order of the checks and the
+ * status codes, the 16-byte alignment of d_params, batch == 0, a voice id outside [0, n_voices), enqueue-only, one-voice
+ * and model-5 plans -- is gvtm_generate_tracks_voices_device's; a null d_utt_chunks is refused with the other nulls. */
+int gvtm_generate_tracks_chunks_device(gvtm_plan* plan, const gvtm_event* d_events,
+		const int64_t* d_chunk_offsets,   /* [n_chunks + 1] event offsets, non-decreasing */
+		const int64_t* d_utt_chunks,      /* [batch + 1]: utterance b owns chunks [d_utt_chunks[b], d_utt_chunks[b+1]) */
+		const int32_t* d_voice_ids, size_t batch, size_t max_frames, float* d_params,
+		int32_t* d_frame_counts, gvtm_drift_state* d_drift, void* hip_stream);
+
+/* gvtm_synthesize_events_voices_device for utterances of several chunks: gvtm_generate_tracks_chunks_device into the
+ * plan's frame buffer, then gvtm_synthesize_voices_device on its frames and counts, both enqueued on hip_stream -- one
+ * track per utterance, as the reference synthesizes the whole parameter list at once (one vocal-tract state, one
+ * converter flush, one peak).  Samples, counts, peaks, frame counts and drift states are bit for bit those of the two
+ * calls made separately.  Checks, status codes, a bad voice id, the plans accepted and the one-stream ordering rule of the
+ * plan's frame buffer and grouping scratch as for gvtm_synthesize_events_voices_device. */
+int gvtm_synthesize_events_chunks_device(gvtm_plan* plan, const gvtm_event* d_events,
+		const int64_t* d_chunk_offsets, const int64_t* d_utt_chunks, const int32_t* d_voice_ids,
+		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts,
+		int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream);
 
 /* Same with host buffers (H2D, kernel, D2H, synchronous). */
 int gvtm_generate_tracks_host(int device, const gvtm_track_config* config, const gvtm_event* events,
