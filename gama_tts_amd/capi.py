@@ -209,6 +209,13 @@ def load_library(diagnostics=False):
         L.gvtm_generate_tracks_chunks_device.restype = i32
         L.gvtm_synthesize_events_chunks_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
         L.gvtm_synthesize_events_chunks_device.restype = i32
+    if hasattr(L, "gvtm_stream_push_events"):
+        L.gvtm_stream_push_events.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
+        L.gvtm_stream_push_events.restype = i32
+        L.gvtm_stream_get_drift.argtypes = [vp, vp]
+        L.gvtm_stream_get_drift.restype = i32
+        L.gvtm_stream_set_drift.argtypes = [vp, vp]
+        L.gvtm_stream_set_drift.restype = i32
     if hasattr(L, "gvtm_plan_create_model5_voices"):
         L.gvtm_plan_create_model5_voices.argtypes = [ctypes.POINTER(Config5), sz, dbl, i32, ctypes.POINTER(vp)]
         L.gvtm_plan_create_model5_voices.restype = i32
@@ -232,6 +239,11 @@ def load_library(diagnostics=False):
         L.gvtm_debug_device_float_math.argtypes = [vp, i32, vp, sz, vp]
         L.gvtm_debug_group_voices.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp]
         L.gvtm_debug_group_voices.restype = i32
+        if hasattr(L, "gvtm_debug_tracks_append"):
+            L.gvtm_debug_tracks_append.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
+            L.gvtm_debug_tracks_append.restype = i32
+            L.gvtm_debug_carry_rows.argtypes = [vp, vp, vp, vp, sz, sz]
+            L.gvtm_debug_carry_rows.restype = i32
     _libs[diagnostics] = L
     return L
 
@@ -717,6 +729,46 @@ class Stream:
             fc = np.ascontiguousarray(frame_counts, dtype=np.int32)
         self._plan._check(self._lib.gvtm_stream_push(self._h, _ptr(params), _ptr(fc), frames, _ptr(audio), stride, _ptr(counts)))
         return [audio[b, : counts[b]].copy() for b in range(self.batch)]
+
+    def push_events(self, utterances, stride=None):
+        """gvtm_stream_push_events.  utterances[b]: the event tables (float64 [E][38] rows, events_from_table) of the chunks
+        utterance b receives in this push, possibly none -> (list of float32 arrays, the new samples of each utterance;
+        int32 [batch], the frames generated per utterance).  stride: the audio row length, by default capacity() of the
+        largest frame total of the push."""
+        assert len(utterances) == self.batch
+        chunks = [np.ascontiguousarray(events_from_table(t)) for u in utterances for t in u]
+        chunk_offsets = np.zeros(len(chunks) + 1, dtype=np.int64)
+        chunk_offsets[1:] = np.cumsum([len(c) for c in chunks])
+        utt_chunks = np.zeros(self.batch + 1, dtype=np.int64)
+        utt_chunks[1:] = np.cumsum([len(u) for u in utterances])
+        events = np.concatenate(chunks) if chunks else np.zeros(0, dtype=EVENT_DTYPE)
+        if stride is None:
+            # the frames of a list follow from its times and the control period alone, the plan's 1000 / control rate
+            counter = TrackConfig()
+            counter.control_period_ms = int(round(1000.0 / self._plan.info.control_rate))
+            new = [tracks_chunks_frame_count(counter, events[chunk_offsets[utt_chunks[b]]: chunk_offsets[utt_chunks[b + 1]]],
+                                             chunk_offsets[utt_chunks[b]: utt_chunks[b + 1] + 1] - chunk_offsets[utt_chunks[b]])
+                   for b in range(self.batch)]
+            stride = self.capacity(max(new))
+        audio = np.zeros((self.batch, max(int(stride), 1)), dtype=np.float32)
+        counts = np.zeros(self.batch, dtype=np.int64)
+        frames = np.zeros(self.batch, dtype=np.int32)
+        self._plan._check(self._lib.gvtm_stream_push_events(self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks), _ptr(audio),
+                                                            int(stride), _ptr(counts), _ptr(frames)))
+        return [audio[b, : counts[b]].copy() for b in range(self.batch)], frames
+
+    def get_drift(self):
+        """-> float64 [batch][5]: the drift generators' states (seed, x1, x2, y1, y2), one per utterance."""
+        states = np.zeros((self.batch, 5), dtype=np.float64)
+        self._plan._check(self._lib.gvtm_stream_get_drift(self._h, _ptr(states)))
+        return states
+
+    def set_drift(self, states=None):
+        """states float64 [batch][5], or None: fresh generators (the one call that reseeds them)."""
+        if states is not None:
+            states = np.ascontiguousarray(states, dtype=np.float64)
+            assert states.shape == (self.batch, 5)
+        self._plan._check(self._lib.gvtm_stream_set_drift(self._h, _ptr(states)))
 
     def finish(self):
         """-> (list of float32 arrays, maxabs float32 [batch])"""

@@ -639,6 +639,57 @@ int gvtm_debug_group_voices(gvtm_plan* plan, const int32_t* d_voice_ids, size_t 
 	return GVTM_OK;
 }
 
+/* Test hook: the append variant of the chunk tracks kernel alone, on device buffers of the caller's (so that a test can
+ * put sentinels around them): gvtm_generate_tracks_chunks_device with d_row_start [batch] int32 -- utterance b's frames
+ * leave at row d_row_start[b] of its block of max_frames rows, nothing at or beyond row max_frames, and d_frame_counts[b]
+ * counts this call's frames.  Synchronous. */
+int gvtm_debug_tracks_append(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_chunk_offsets, const int64_t* d_utt_chunks,
+		const int32_t* d_voice_ids, const int32_t* d_row_start, size_t batch, size_t max_frames, float* d_params, int32_t* d_frame_counts,
+		gvtm_drift_state* d_drift)
+{
+	if (!plan || !d_events || !d_chunk_offsets || !d_utt_chunks || !d_voice_ids || !d_row_start || !d_params || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (reinterpret_cast<uintptr_t>(d_params) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params must be 16-byte aligned");
+	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
+	DeviceScope scope(plan->device);
+	hipError_t e = scope.status();
+	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+	gvtm::TrackAppendArgs args{};
+	args.k.control_period = plan->voice_tracks[0].control_period;
+	args.events = d_events;
+	args.chunk_offsets = d_chunk_offsets;
+	args.utt_chunks = d_utt_chunks;
+	args.batch = batch;
+	args.max_frames = max_frames;
+	args.params = d_params;
+	args.frame_counts = d_frame_counts;
+	args.drift = d_drift;
+	args.voice_k = static_cast<const gvtm::TrackConstants*>(plan->d_voice_tracks.ptr);
+	args.voice_ids = d_voice_ids;
+	args.n_voices = plan->n_voices();
+	args.row_start = d_row_start;
+	e = gvtm::launch_tracks_append(args, nullptr);
+	if (e == hipSuccess) e = hipDeviceSynchronize();
+	if (e != hipSuccess) return fail_hip(e, "vtm_tracks_append_kernel");
+	return GVTM_OK;
+}
+
+/* Test hook: the carry kernel of an events-fed stream alone, on device buffers of the caller's: in utterance b's block of
+ * max_frames rows of d_params the rows [d_done[b], d_held[b]) move to the front.  Synchronous. */
+int gvtm_debug_carry_rows(gvtm_plan* plan, float* d_params, const int32_t* d_done, const int32_t* d_held, size_t batch, size_t max_frames)
+{
+	if (!plan || !d_params || !d_done || !d_held || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (reinterpret_cast<uintptr_t>(d_params) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params must be 16-byte aligned");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
+	DeviceScope scope(plan->device);
+	hipError_t e = scope.status();
+	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+	e = gvtm::launch_carry_rows(gvtm::CarryArgs{d_params, d_done, d_held, batch, max_frames}, nullptr);
+	if (e == hipSuccess) e = hipDeviceSynchronize();
+	if (e != hipSuccess) return fail_hip(e, "vtm_carry_rows_kernel");
+	return GVTM_OK;
+}
+
 #pragma GCC visibility pop
 #endif /* GVTM_DIAGNOSTICS */
 
@@ -1409,6 +1460,8 @@ void gvtm_host_free(void* ptr)
 
 } // extern "C"
 
+enum StreamFeed : int { kFeedNone = 0, kFeedFrames = 1, kFeedEvents = 2 };
+
 struct gvtm_stream {
 	gvtm_plan* plan = nullptr;
 	size_t batch = 0;
@@ -1425,6 +1478,19 @@ struct gvtm_stream {
 	std::vector<float> staging;
 	std::vector<int32_t> counts;
 	bool finished = false;
+	// how the stream has been fed since the last reset: frames (gvtm_stream_push) or event lists (gvtm_stream_push_events);
+	// one way per run
+	int feed = kFeedNone;
+	// an events-fed run keeps its unsynthesized frames on the device: utterance b's in the rows [0, held_rows[b]) of its block
+	// of held_cap rows of d_held ([batch][held_cap][16]; at least one row of a block stays spare: a push's launch reads
+	// max_frames - 1 rows at most).  The tracks kernel appends behind them, the synthesis launch reads them in place, the
+	// carry kernel moves what the launch left to the front.
+	DeviceBuffer d_held;
+	size_t held_cap = 0;
+	std::vector<size_t> held_rows;
+	// the drift generators, one per utterance (fresh at create; no reset touches them), and the tables of a push: events,
+	// the two offset tables, {row_start, rows held} [2][batch] and the frames the tracks kernel counted
+	DeviceBuffer d_drift, d_events, d_chunk_offsets, d_utt_chunks, d_rows, d_new_counts;
 };
 
 namespace {
@@ -1465,12 +1531,28 @@ int stream_upload_fresh_state(gvtm_stream* s)
 	return GVTM_OK;
 }
 
+// the stream's drift generators from host states, or (null) fresh ones (DriftGenerator.cpp:28, :40)
+int stream_upload_drift(gvtm_stream* s, const gvtm_drift_state* states)
+{
+	hipError_t e = s->d_drift.ensure(sizeof(gvtm_drift_state) * s->batch);
+	if (e != hipSuccess) return fail_hip(e, "hipMalloc drift states");
+	std::vector<gvtm_drift_state> fresh;
+	if (!states) {
+		fresh.assign(s->batch, gvtm_drift_state{0.7892347, 0.0, 0.0, 0.0, 0.0});
+		states = fresh.data();
+	}
+	if ((e = hipMemcpy(s->d_drift.ptr, states, sizeof(gvtm_drift_state) * s->batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D drift states");
+	return GVTM_OK;
+}
+
 uint64_t outputs_before(const gvtm::DeviceConstants& k, uint64_t steps)
 {
 	return ((steps << 16) + k.time_inc - 1) / k.time_inc;
 }
 
-// One launch on behalf of the stream: utterance b synthesizes n_frames[b] frames from the front of held[b].
+// One launch on behalf of the stream: utterance b synthesizes n_frames[b] frames from the front of held[b] -- or, in an
+// events-fed run, from the front of its block of d_held, which the launch reads in place (no staging, no copy of frames);
+// behind a push's launch the carry kernel then moves the rows it left to the front of the block.
 int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool final, float* audio, size_t audio_stride, int64_t* out_counts,
 		float* maxabs, bool* launched = nullptr)
 {
@@ -1506,12 +1588,14 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 		if (out_counts) std::fill(out_counts, out_counts + batch, int64_t(0));
 		return GVTM_OK;
 	}
+	const bool on_device = s->feed == kFeedEvents;
+	if (on_device) rows_max = s->held_cap; // (the row stride of d_held: every block has a row behind the frames a push synthesizes)
 	if (rows_max == 0) rows_max = 1;
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
 	try {
-		s->staging.assign(batch * rows_max * GVTM_N_PARAM, 0.0f);
+		s->staging.assign(on_device ? 0 : batch * rows_max * GVTM_N_PARAM, 0.0f);
 		s->counts.assign(batch, 0);
 	} catch (const std::bad_alloc&) {
 		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -1519,26 +1603,32 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	for (size_t b = 0; b < batch; ++b) {
 		if (!n_frames[b]) continue;
 		const size_t rows = n_frames[b] + (final ? 0 : 1);
-		std::memcpy(s->staging.data() + b * rows_max * GVTM_N_PARAM, s->held[b].data(), sizeof(float) * rows * GVTM_N_PARAM);
+		if (!on_device) std::memcpy(s->staging.data() + b * rows_max * GVTM_N_PARAM, s->held[b].data(), sizeof(float) * rows * GVTM_N_PARAM);
 		s->counts[b] = static_cast<int32_t>(n_frames[b]);
 	}
 	const size_t pbytes = sizeof(float) * s->staging.size();
 	const size_t abytes = sizeof(float) * batch * std::max<size_t>(audio_stride, 1);
-	if ((e = s->d_params.ensure(pbytes)) != hipSuccess) return fail_hip(e, "hipMalloc params");
+	if (!on_device && (e = s->d_params.ensure(pbytes)) != hipSuccess) return fail_hip(e, "hipMalloc params");
 	if ((e = s->d_frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
 	if ((e = s->d_audio.ensure(abytes)) != hipSuccess) return fail_hip(e, "hipMalloc audio");
 	if ((e = s->d_counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
 	if ((e = s->d_maxabs.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc maxabs");
-	if ((e = hipMemcpy(s->d_params.ptr, s->staging.data(), pbytes, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D params");
+	if (!on_device && (e = hipMemcpy(s->d_params.ptr, s->staging.data(), pbytes, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D params");
 	if ((e = hipMemcpy(s->d_frames.ptr, s->counts.data(), sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D frame counts");
 	if ((e = hipMemsetAsync(s->d_audio.ptr, 0, abytes, nullptr)) != hipSuccess) return fail_hip(e, "hipMemsetAsync");
 	const StreamLaunch sl{static_cast<unsigned char*>(s->d_state.ptr), s->state_stride, final ? gvtm::kStreamFinish : gvtm::kStreamPush, s->xr};
 	// (one utterance per workgroup unless the utterances are in lockstep)
-	const int rc = launch_synthesis(plan, LaunchRequest{static_cast<const float*>(s->d_params.ptr), static_cast<const int32_t*>(s->d_frames.ptr), batch,
+	float* const d_rows_in = static_cast<float*>(on_device ? s->d_held.ptr : s->d_params.ptr);
+	const int rc = launch_synthesis(plan, LaunchRequest{d_rows_in, static_cast<const int32_t*>(s->d_frames.ptr), batch,
 			rows_max, static_cast<float*>(s->d_audio.ptr), audio_stride, static_cast<int64_t*>(s->d_counts.ptr), static_cast<float*>(s->d_maxabs.ptr), nullptr,
 			lockstep ? 0 : 1, s->voices, s->voices ? static_cast<const int32_t*>(s->d_voice_ids.ptr) : nullptr, &s->d_groups, &sl});
 	if (rc != GVTM_OK) return rc;
 	if (launched) *launched = true;
+	if (on_device && !final) {
+		// (d_rows: the rows each block held when the launch began, behind the row starts of the push)
+		const gvtm::CarryArgs ca{d_rows_in, static_cast<const int32_t*>(s->d_frames.ptr), static_cast<const int32_t*>(s->d_rows.ptr) + batch, batch, rows_max};
+		if ((e = gvtm::launch_carry_rows(ca, nullptr)) != hipSuccess) return fail_hip(e, "vtm_carry_rows_kernel launch");
+	}
 	if ((e = hipDeviceSynchronize()) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");
 	std::vector<int64_t> got(batch, 0);
 	if ((e = hipMemcpy(got.data(), s->d_counts.ptr, sizeof(int64_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H counts");
@@ -1552,7 +1642,8 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	if (maxabs && (e = hipMemcpy(maxabs, s->d_maxabs.ptr, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H maxabs");
 	for (size_t b = 0; b < batch; ++b) {
 		s->steps_done[b] += static_cast<uint64_t>(n_frames[b]) * plan->designs[voice_of(s, b)].k.control_steps;
-		s->held[b].erase(s->held[b].begin(), s->held[b].begin() + static_cast<std::ptrdiff_t>(n_frames[b] * GVTM_N_PARAM));
+		if (on_device) s->held_rows[b] -= n_frames[b];
+		else s->held[b].erase(s->held[b].begin(), s->held[b].begin() + static_cast<std::ptrdiff_t>(n_frames[b] * GVTM_N_PARAM));
 	}
 	return GVTM_OK;
 }
@@ -1598,17 +1689,20 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 			}
 		}
 		s->held.resize(batch);
+		s->held_rows.assign(batch, 0);
 		s->steps_done.assign(batch, 0);
 		DeviceScope scope(plan->device);
 		hipError_t e = scope.status();
 		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
 		if ((e = s->d_state.ensure(s->state_stride * batch)) != hipSuccess) return fail_hip(e, "hipMalloc stream state");
-		if (s->voices) {
-			if ((e = s->d_voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
-			if ((e = hipMemcpy(s->d_voice_ids.ptr, voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D voice ids");
-		}
-		const int rc = stream_upload_fresh_state(s.get());
+		// (one voice: every utterance's id is 0, which only the tracks kernel of an events-fed run reads)
+		if ((e = s->d_voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
+		if (s->voices) e = hipMemcpy(s->d_voice_ids.ptr, voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice);
+		else e = hipMemset(s->d_voice_ids.ptr, 0, sizeof(int32_t) * batch);
+		if (e != hipSuccess) return fail_hip(e, "H2D voice ids");
+		int rc = stream_upload_fresh_state(s.get());
 		if (rc != GVTM_OK) return rc;
+		if ((rc = stream_upload_drift(s.get(), nullptr)) != GVTM_OK) return rc;
 		*stream_out = s.release();
 		return GVTM_OK;
 	} catch (const std::bad_alloc&) {
@@ -1653,8 +1747,10 @@ int gvtm_stream_reset(gvtm_stream* s)
 	DeviceScope scope(s->plan->device);
 	if (scope.status() != hipSuccess) return fail_hip(scope.status(), "hipSetDevice");
 	for (auto& h : s->held) h.clear();
+	std::fill(s->held_rows.begin(), s->held_rows.end(), size_t(0));
 	std::fill(s->steps_done.begin(), s->steps_done.end(), uint64_t(0));
 	s->finished = false;
+	s->feed = kFeedNone; // (the drift generators run on: the reference's Controller never reseeds its own)
 	return stream_upload_fresh_state(s);
 }
 
@@ -1698,6 +1794,7 @@ int gvtm_stream_push(gvtm_stream* s, const float* params, const int32_t* frame_c
 {
 	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
 	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
+	if (s->feed == kFeedEvents) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed event lists (gvtm_stream_push_events) until the next gvtm_stream_reset()");
 	if (max_frames > 0 && !params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	if (frame_counts) {
 		for (size_t b = 0; b < s->batch; ++b) {
@@ -1727,6 +1824,7 @@ int gvtm_stream_push(gvtm_stream* s, const float* params, const int32_t* frame_c
 		bool launched = false;
 		const int rc = stream_launch(s, n, false, audio, audio_stride, out_counts, nullptr, &launched);
 		if (rc != GVTM_OK && !launched) roll_back(); // (after the launch the device state has moved on: gvtm_stream_reset is the way out)
+		else s->feed = kFeedFrames;
 		return rc;
 	} catch (const std::bad_alloc&) {
 		roll_back();
@@ -1740,10 +1838,192 @@ int gvtm_stream_finish(gvtm_stream* s, float* audio, size_t audio_stride, int64_
 	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has already been finished");
 	try {
 		std::vector<size_t> n(s->batch, 0);
-		for (size_t b = 0; b < s->batch; ++b) n[b] = s->held[b].size() / GVTM_N_PARAM; // the last frame stands for its own successor (Controller.cpp:283)
+		// the last frame stands for its own successor (Controller.cpp:283)
+		for (size_t b = 0; b < s->batch; ++b) n[b] = s->feed == kFeedEvents ? s->held_rows[b] : s->held[b].size() / GVTM_N_PARAM;
 		const int rc = stream_launch(s, n, true, audio, audio_stride, out_counts, maxabs);
 		if (rc == GVTM_OK) s->finished = true;
 		return rc;
+	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
+}
+
+} // extern "C"
+
+namespace {
+
+// the most rows a block of d_held may have: launch_synthesis takes the row stride as max_frames, whose steps must fit its
+// 31-bit step counter
+size_t stream_block_limit(const gvtm_plan* plan)
+{
+	unsigned max_steps = 1;
+	for (int v = 0; v < plan->n_voices(); ++v) max_steps = std::max(max_steps, plan->designs[v].k.control_steps);
+	return static_cast<size_t>(((1ull << 31) - 4096ull - 1ull) / max_steps);
+}
+
+// What gvtm_stream_push_events does once its checks have passed: have[b] rows held after the push, fresh[b] of them new,
+// n[b] of them synthesized by it.  Up to the tracks launch a failure leaves the stream as it was; from there on
+// (*advanced) its drift generators have moved.
+int stream_append_and_launch(gvtm_stream* s, const gvtm_event* events, const int64_t* chunk_offsets, const int64_t* utt_chunks, size_t n_chunks,
+		size_t n_events, const std::vector<size_t>& fresh, const std::vector<size_t>& have, const std::vector<size_t>& n, float* audio,
+		size_t audio_stride, int64_t* out_counts, bool* advanced)
+{
+	gvtm_plan* plan = s->plan;
+	const size_t batch = s->batch;
+	DeviceScope scope(plan->device);
+	hipError_t e = scope.status();
+	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+	// the blocks of d_held: the rows held and one spare.  A larger buffer is a new one, the rows held copied over device to
+	// device (DeviceBuffer::ensure would free them first)
+	const size_t need_cap = *std::max_element(have.begin(), have.end()) + 1;
+	if (need_cap > s->held_cap) {
+		// (half as much again, within what a launch takes as max_frames)
+		const size_t new_cap = std::max(need_cap, std::min(s->held_cap + s->held_cap / 2, stream_block_limit(plan)));
+		const size_t kept = *std::max_element(s->held_rows.begin(), s->held_rows.end());
+		constexpr size_t row_bytes = sizeof(float) * GVTM_N_PARAM;
+		DeviceBuffer grown;
+		if ((e = grown.ensure(row_bytes * batch * new_cap)) != hipSuccess) return fail_hip(e, "hipMalloc held frames");
+		if (kept && (e = hipMemcpy2D(grown.ptr, row_bytes * new_cap, s->d_held.ptr, row_bytes * s->held_cap, row_bytes * kept, batch,
+				hipMemcpyDeviceToDevice)) != hipSuccess) return fail_hip(e, "D2D held frames");
+		s->d_held = std::move(grown); // (the old buffer goes with `grown`)
+		s->held_cap = new_cap;
+	}
+	// the tables of the push, one copy each into buffers of the stream's
+	std::vector<int64_t> no_chunks;
+	std::vector<int32_t> rows(2 * batch);
+	for (size_t b = 0; b < batch; ++b) {
+		rows[b] = static_cast<int32_t>(s->held_rows[b]);
+		rows[batch + b] = static_cast<int32_t>(have[b]);
+	}
+	if (!utt_chunks) {
+		no_chunks.assign(batch + 1, 0);
+		utt_chunks = no_chunks.data();
+	}
+	const int64_t zero = 0;
+	if (n_chunks == 0) chunk_offsets = &zero;
+	if ((e = s->d_events.ensure(sizeof(gvtm_event) * std::max<size_t>(n_events, 1))) != hipSuccess) return fail_hip(e, "hipMalloc events");
+	if ((e = s->d_chunk_offsets.ensure(sizeof(int64_t) * (n_chunks + 1))) != hipSuccess) return fail_hip(e, "hipMalloc chunk offsets");
+	if ((e = s->d_utt_chunks.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc utterance chunks");
+	if ((e = s->d_rows.ensure(sizeof(int32_t) * 2 * batch)) != hipSuccess) return fail_hip(e, "hipMalloc row starts");
+	if ((e = s->d_new_counts.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
+	if (n_events && (e = hipMemcpy(s->d_events.ptr, events, sizeof(gvtm_event) * n_events, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D events");
+	if ((e = hipMemcpy(s->d_chunk_offsets.ptr, chunk_offsets, sizeof(int64_t) * (n_chunks + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D chunk offsets");
+	if ((e = hipMemcpy(s->d_utt_chunks.ptr, utt_chunks, sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D utterance chunks");
+	if ((e = hipMemcpy(s->d_rows.ptr, rows.data(), sizeof(int32_t) * 2 * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D row starts");
+	// append, synthesis, carry: all on the stream's launch stream
+	gvtm::TrackAppendArgs ta{};
+	ta.k.control_period = plan->voice_tracks[0].control_period; // (every voice's is the plan's: gvtm_plan_set_voice_tracks)
+	ta.events = static_cast<const gvtm_event*>(s->d_events.ptr);
+	ta.chunk_offsets = static_cast<const int64_t*>(s->d_chunk_offsets.ptr);
+	ta.utt_chunks = static_cast<const int64_t*>(s->d_utt_chunks.ptr);
+	ta.batch = batch;
+	ta.max_frames = s->held_cap;
+	ta.params = static_cast<float*>(s->d_held.ptr);
+	ta.frame_counts = static_cast<int32_t*>(s->d_new_counts.ptr);
+	ta.drift = static_cast<gvtm_drift_state*>(s->d_drift.ptr);
+	ta.voice_k = static_cast<const gvtm::TrackConstants*>(plan->d_voice_tracks.ptr);
+	ta.voice_ids = static_cast<const int32_t*>(s->d_voice_ids.ptr);
+	ta.n_voices = plan->n_voices();
+	ta.row_start = static_cast<const int32_t*>(s->d_rows.ptr);
+	if ((e = gvtm::launch_tracks_append(ta, nullptr)) != hipSuccess) return fail_hip(e, "track generation launch (append)");
+	*advanced = true;
+	s->feed = kFeedEvents;
+	s->held_rows = have;
+	const int rc = stream_launch(s, n, false, audio, audio_stride, out_counts, nullptr);
+	if (rc != GVTM_OK) return rc;
+	// (a push that synthesizes nothing launches nothing behind the tracks kernel: the copy waits for it)
+	std::vector<int32_t> counted(batch, 0);
+	if ((e = hipMemcpy(counted.data(), s->d_new_counts.ptr, sizeof(int32_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H frame counts");
+	for (size_t b = 0; b < batch; ++b) {
+		if (static_cast<size_t>(counted[b]) != fresh[b]) return fail(GVTM_ERR_HIP, "internal error: the device's frame count differs from the host's");
+	}
+	return GVTM_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int gvtm_stream_push_events(gvtm_stream* s, const gvtm_event* events, const int64_t* chunk_offsets, const int64_t* utt_chunks, float* audio,
+		size_t audio_stride, int64_t* out_counts, int32_t* frame_counts_out)
+{
+	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
+	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
+	if (s->feed == kFeedFrames) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed frames (gvtm_stream_push) until the next gvtm_stream_reset()");
+	const gvtm_plan* plan = s->plan;
+	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "gvtm_stream_push_events: the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
+	const size_t batch = s->batch;
+	// (a null utt_chunks: no utterance receives a chunk)
+	const int64_t last_chunk = utt_chunks ? utt_chunks[batch] : 0;
+	if (last_chunk > 0 && (!events || !chunk_offsets)) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events or chunk_offsets");
+	if (utt_chunks) {
+		if (utt_chunks[0] < 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "utt_chunks must not be negative");
+		for (size_t b = 0; b < batch; ++b) {
+			if (utt_chunks[b + 1] < utt_chunks[b]) return fail(GVTM_ERR_INVALID_ARGUMENT, "utt_chunks must not decrease");
+		}
+	}
+	const size_t n_chunks = last_chunk > 0 ? static_cast<size_t>(last_chunk) : 0;
+	for (size_t c = 0; c < n_chunks; ++c) {
+		if (chunk_offsets[c] < 0 || chunk_offsets[c + 1] < chunk_offsets[c]) return fail(GVTM_ERR_INVALID_ARGUMENT, "chunk_offsets must not decrease");
+	}
+	const size_t n_events = n_chunks ? static_cast<size_t>(chunk_offsets[n_chunks]) : 0;
+	try {
+		// what the tracks kernel will generate, counted here: every sample count is known before anything is launched
+		const int cp = plan->voice_tracks[0].control_period; // (every voice's is the plan's: gvtm_plan_set_voice_tracks)
+		std::vector<size_t> fresh(batch, 0), have(batch, 0), n(batch, 0);
+		for (size_t b = 0; b < batch; ++b) {
+			for (int64_t c = utt_chunks ? utt_chunks[b] : 0; c < (utt_chunks ? utt_chunks[b + 1] : 0); ++c) {
+				fresh[b] += gvtm::tracks_frame_count(cp, events + chunk_offsets[c], static_cast<size_t>(chunk_offsets[c + 1] - chunk_offsets[c]));
+			}
+			have[b] = s->held_rows[b] + fresh[b];
+			// (the rows of a block, the spare one included, are the synthesis launch's max_frames)
+			if (have[b] + 1 > stream_block_limit(plan)) return fail(GVTM_ERR_INVALID_ARGUMENT, "utterance " + std::to_string(b) + ": too many frames for one push");
+			// as gvtm_stream_push: the last frame held is the look-ahead of the one before it
+			const unsigned granule = s->granule_frames[static_cast<size_t>(voice_of(s, b))];
+			n[b] = have[b] > 0 ? ((have[b] - 1) / granule) * granule : 0;
+		}
+		size_t need = 0;
+		bool too_long = false;
+		for (size_t b = 0; b < batch; ++b) {
+			const gvtm::DeviceConstants& k = plan->designs[voice_of(s, b)].k;
+			const uint64_t after = s->steps_done[b] + static_cast<uint64_t>(n[b]) * k.control_steps;
+			if (after + 4096ull >= (1ull << 31)) too_long = true;
+			need = std::max(need, static_cast<size_t>(outputs_before(k, after) - outputs_before(k, s->steps_done[b])));
+		}
+		if (need > audio_stride) return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than this call produces (gvtm_stream_capacity)");
+		if (need > 0 && !audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
+		if (too_long) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
+		bool advanced = false;
+		const int rc = stream_append_and_launch(s, events, chunk_offsets, utt_chunks, n_chunks, n_events, fresh, have, n, audio, audio_stride, out_counts, &advanced);
+		// past the tracks launch the drift generators and the held frames have moved on: no push until a reset
+		if (rc != GVTM_OK && advanced) s->finished = true;
+		if (rc == GVTM_OK && frame_counts_out) {
+			for (size_t b = 0; b < batch; ++b) frame_counts_out[b] = static_cast<int32_t>(fresh[b]);
+		}
+		return rc;
+	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
+}
+
+int gvtm_stream_get_drift(const gvtm_stream* s, gvtm_drift_state* states_out)
+{
+	if (!s || !states_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream or states_out");
+	DeviceScope scope(s->plan->device);
+	hipError_t e = scope.status();
+	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+	if ((e = hipMemcpy(states_out, s->d_drift.ptr, sizeof(gvtm_drift_state) * s->batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H drift states");
+	return GVTM_OK;
+}
+
+int gvtm_stream_set_drift(gvtm_stream* s, const gvtm_drift_state* states)
+{
+	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
+	if (s->feed == kFeedEvents) return fail(GVTM_ERR_INVALID_ARGUMENT, "the drift generators are running: gvtm_stream_reset() comes first");
+	try {
+		DeviceScope scope(s->plan->device);
+		if (scope.status() != hipSuccess) return fail_hip(scope.status(), "hipSetDevice");
+		return stream_upload_drift(s, states);
 	} catch (const std::bad_alloc&) {
 		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
 	}

@@ -26,6 +26,7 @@
 
 #include <cmath>
 #include <cstddef>
+#include <type_traits>
 
 namespace gvtm {
 
@@ -289,10 +290,13 @@ __global__ __launch_bounds__(64) void vtm_tracks_voices_kernel(const TrackVoices
 // parameters at 0, the polynomial from initial_pitch, now = 0, target = 1, the staged boundary data and the table, which
 // is rebuilt in the row's one `ahead` (LDS per workgroup is what the other two kernels use).
 // The per-list walk is a copy of tracks_row's and not shared with it, so that the two kernels above keep their code.
-template <int LW>
-__device__ __forceinline__ void tracks_chunks_row(const TrackChunksArgs& a, size_t utt, int l, float (*ring)[16], unsigned char (*ahead)[32])
+// APPEND (Args = TrackAppendArgs): the frames leave behind the row_start[utt] rows the utterance's block already holds,
+// and `room` rows are left for them; the ring, its place (n counts this call's frames) and the flushes are the same.
+template <int LW, typename Args>
+__device__ __forceinline__ void tracks_chunks_row(const Args& a, size_t utt, int l, float (*ring)[16], unsigned char (*ahead)[32])
 {
 #pragma clang fp contract(off)
+	constexpr bool APPEND = std::is_same_v<Args, TrackAppendArgs>;
 	const int j = l & 15; // parameter
 	const int32_t voice = a.voice_ids[utt];
 	if (voice < 0 || voice >= a.n_voices) { // (as tracks_row: nothing of the utterance is read or written)
@@ -304,12 +308,19 @@ __device__ __forceinline__ void tracks_chunks_row(const TrackChunksArgs& a, size
 	const int cp = k.control_period;
 	const bool walker = l < 16;
 	float* out = a.params + utt * a.max_frames * 16;
+	size_t room = a.max_frames; // rows the frames may take
+	if constexpr (APPEND) {
+		const int32_t start = a.row_start[utt];
+		const bool inside = start >= 0 && static_cast<size_t>(start) < a.max_frames;
+		room = inside ? a.max_frames - static_cast<size_t>(start) : 0;
+		if (inside) out += static_cast<size_t>(start) * 16; // (a row is 64 bytes: the float4 stores stay aligned)
+	}
 	gvtm_drift_state ds = {0.7892347, 0.0, 0.0, 0.0, 0.0}; // DriftGenerator.cpp:28, :40
 	if (j == 0 && a.drift) ds = a.drift[utt];
 	size_t n = 0; // frames of the utterance so far
 
 	auto flush = [&](size_t first, size_t end) { // (as tracks_row's)
-		if (end > a.max_frames) end = a.max_frames;
+		if (end > room) end = room;
 		const float4* src = reinterpret_cast<const float4*>(&ring[0][0]);
 		float4* dst = reinterpret_cast<float4*>(out + first * 16);
 		for (int q = l; q < kRingFrames * 4; q += LW) {
@@ -471,6 +482,35 @@ __global__ __launch_bounds__(64) void vtm_tracks_chunks_kernel(const TrackChunks
 	if (utt < a.batch) tracks_chunks_row<64 / ROWS>(a, utt, l, ring[row], ahead[row]);
 }
 
+// the append variant of the chunk kernel (a kernel of its own, so that the three above keep their arguments and their code)
+template <int ROWS>
+__global__ __launch_bounds__(64) void vtm_tracks_append_kernel(const TrackAppendArgs a)
+{
+	__shared__ __attribute__((aligned(16))) float ring[ROWS][kRingFrames][16];
+	__shared__ unsigned char ahead[ROWS][kTableEvents + 1][32]; // (as vtm_tracks_chunks_kernel's)
+	const int tid = threadIdx.x;
+	const int row = tid / (64 / ROWS), l = tid % (64 / ROWS);
+	const size_t utt = static_cast<size_t>(blockIdx.x) * ROWS + row;
+	if (utt < a.batch) tracks_chunks_row<64 / ROWS>(a, utt, l, ring[row], ahead[row]);
+}
+
+// CarryArgs: one wavefront per utterance, lane q one float4 of the rows that move (kCarryMaxRows rows of four).  Every lane
+// has its float4 in a register before any lane stores (one load instruction, then one store instruction, of the one
+// wavefront), so the rows may move onto themselves.
+__global__ __launch_bounds__(64) void vtm_carry_rows_kernel(const CarryArgs a)
+{
+	static_assert(kCarryMaxRows * 4 == 64, "one float4 per lane");
+	const size_t utt = blockIdx.x;
+	const int done = a.done[utt], held = a.held[utt];
+	if (done <= 0 || held <= done || static_cast<size_t>(held) > a.max_frames || held - done > kCarryMaxRows) return;
+	float4* block = reinterpret_cast<float4*>(a.params + utt * a.max_frames * 16);
+	const int q = threadIdx.x;
+	const bool mine = q < (held - done) * 4;
+	float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+	if (mine) v = block[static_cast<size_t>(done) * 4 + q];
+	if (mine) block[q] = v;
+}
+
 hipError_t launch_tracks(const TrackArgs& args, hipStream_t stream)
 {
 	if (args.batch == 0) return hipSuccess;
@@ -498,6 +538,21 @@ hipError_t launch_tracks_chunks(const TrackChunksArgs& args, hipStream_t stream)
 	if (args.batch == 0) return hipSuccess;
 	constexpr int kRows = GVTM_TRACK_ROWS; // (as launch_tracks)
 	hipLaunchKernelGGL(vtm_tracks_chunks_kernel<kRows>, dim3(static_cast<unsigned>((args.batch + kRows - 1) / kRows)), dim3(64), 0, stream, args);
+	return hipGetLastError();
+}
+
+hipError_t launch_tracks_append(const TrackAppendArgs& args, hipStream_t stream)
+{
+	if (args.batch == 0) return hipSuccess;
+	constexpr int kRows = GVTM_TRACK_ROWS; // (as launch_tracks)
+	hipLaunchKernelGGL(vtm_tracks_append_kernel<kRows>, dim3(static_cast<unsigned>((args.batch + kRows - 1) / kRows)), dim3(64), 0, stream, args);
+	return hipGetLastError();
+}
+
+hipError_t launch_carry_rows(const CarryArgs& args, hipStream_t stream)
+{
+	if (args.batch == 0) return hipSuccess;
+	hipLaunchKernelGGL(vtm_carry_rows_kernel, dim3(static_cast<unsigned>(args.batch)), dim3(64), 0, stream, args);
 	return hipGetLastError();
 }
 

@@ -48,4 +48,29 @@ struct TrackChunksArgs : TrackVoicesArgs {
 
 hipError_t launch_tracks_chunks(const TrackChunksArgs& args, hipStream_t stream);
 
+// The chunk kernel appending (an events-fed gvtm_stream): utterance b's rows [0, row_start[b]) of its block of max_frames
+// rows hold frames of earlier calls, and this call's frames leave behind them, at row row_start[b] + (frame of this call).
+// Nothing is written at or beyond row max_frames (a row_start outside [0, max_frames) writes nothing); frame_counts[b]
+// counts the frames of this call alone.  Everything else as TrackChunksArgs.
+struct TrackAppendArgs : TrackChunksArgs {
+	const int32_t* row_start;      // [batch], device memory
+};
+
+hipError_t launch_tracks_append(const TrackAppendArgs& args, hipStream_t stream);
+
+// What an events-fed stream keeps after a synthesis launch: in utterance b's block of max_frames rows of params, the rows
+// [done[b], held[b]) move to the front.  At most kCarryMaxRows rows move (a stream keeps at most its voice's granule,
+// 12 frames); an utterance with done <= 0, held <= done, held > max_frames or more rows to move is left as it is.
+constexpr int kCarryMaxRows = 16;
+
+struct CarryArgs {
+	float* params;                 // [batch][max_frames][16], 16-byte aligned
+	const int32_t* done;           // [batch]: rows the launch has used up
+	const int32_t* held;           // [batch]: rows that held frames before it
+	size_t batch;
+	size_t max_frames;
+};
+
+hipError_t launch_carry_rows(const CarryArgs& args, hipStream_t stream);
+
 } // namespace gvtm

@@ -376,6 +376,10 @@ void gvtm_host_free(void* ptr);
  * runs one utterance per workgroup.  push, finish, reset and destroy take such a stream as they are; its capacity is the
  * largest over its voices.  Each launch first runs the grouping kernel of gvtm_synthesize_voices_device with the plan's
  * scratch: stream calls and gvtm_synthesize_voices_device calls on one plan must not overlap.
+ *
+ * A stream also takes its utterances as event lists, chunk by chunk, and generates their frames itself:
+ * gvtm_stream_push_events, with gvtm_stream_get_drift / gvtm_stream_set_drift, declared behind the track-generation entries
+ * below ("Streams fed event lists").
  */
 typedef struct gvtm_stream gvtm_stream;
 
@@ -579,6 +583,55 @@ int gvtm_synthesize_events_chunks_device(gvtm_plan* plan, const gvtm_event* d_ev
 		const int64_t* d_chunk_offsets, const int64_t* d_utt_chunks, const int32_t* d_voice_ids,
 		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts,
 		int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream);
+
+/*
+ * Streams fed event lists.  The reference produces an utterance chunk by chunk (one generateOutput() per /c chunk,
+ * Controller.cpp:141-154); a stream takes the next chunk or chunks of each of its utterances as they are parsed, generates
+ * their frames on the device straight behind the frames it still holds, synthesizes what can be synthesized and returns
+ * the new samples.  The frames never leave the device, and the drift generators (one per utterance) live in the stream.
+ *
+ * gvtm_stream_push_events works on every stream of gvtm_stream_create and gvtm_stream_create_voices (models 0 to 4 in every
+ * precision, model 5 in both classes, one voice or several) whose plan has track configurations
+ * (gvtm_plan_set_voice_tracks, which takes a one-voice plan too); utterance b is generated under the configuration of its
+ * stream voice.
+ *   events, chunk_offsets [n_chunks + 1], utt_chunks [batch + 1]
+ *                     HOST memory: the two offset tables of gvtm_generate_tracks_chunks_device.  Utterance b receives the
+ *                     chunks [utt_chunks[b], utt_chunks[b+1]) -- none is allowed, and a NULL utt_chunks gives no utterance
+ *                     a chunk; n_chunks = utt_chunks[batch].
+ *   frame_counts_out  [batch] int32 (may be NULL): the frames this call generated per utterance
+ *   audio, audio_stride, out_counts: as gvtm_stream_push.  audio_stride comes from gvtm_stream_capacity(stream, n), n the
+ *                     largest per-utterance frame total of the push (gvtm_tracks_chunks_frame_count on the host).
+ * Each chunk is generated exactly as gvtm_generate_tracks_chunks_device generates it: a list of its own; fewer than two
+ * events yield nothing and leave the drift state alone; the drift state a chunk leaves is the next chunk's, within a push
+ * and from push to push.  The new frames go behind the utterance's held frames, and the push then does what
+ * gvtm_stream_push does.  gvtm_stream_finish and gvtm_stream_capacity take such a stream as they are.  Contract: an
+ * utterance's chunks pushed in any grouping over any number of calls and then finished give, bit for bit and in every
+ * precision, the samples, sample count, maxabs, total frame count and final drift state of one
+ * gvtm_synthesize_events_chunks_device call on the whole utterance with the same voice and the same initial drift state.
+ *
+ * One feeding mode per run: between two resets a stream is fed frames (gvtm_stream_push) or event lists, never both; once
+ * one entry has been used the other returns GVTM_ERR_INVALID_ARGUMENT until the next reset, and so does
+ * gvtm_stream_set_drift between a gvtm_stream_push_events and the next reset.
+ *
+ * The drift generators: gvtm_stream_create* starts every one fresh ({0.7892347, 0, 0, 0, 0}).  gvtm_stream_reset and
+ * gvtm_stream_reset_voices leave them as they are (the reference's Controller resets its model for every utterance and
+ * never reseeds its generator); gvtm_stream_set_drift(stream, NULL) is what reseeds them.
+ *
+ * Refused with GVTM_ERR_INVALID_ARGUMENT, in this order and before any device work: a null stream; a finished stream; a
+ * stream fed frames since its last reset; a plan without track configurations; null events or chunk_offsets while chunks
+ * are present; offsets that decrease or are negative; more frames than one push can hold; an audio_stride smaller than the
+ * call produces, or a null audio with samples due (the host counts every frame and sample in advance); more than 2^31
+ * internal steps since the reset.  A call refused here leaves the stream exactly as it found it: held frames, drift states
+ * and feeding mode.  A device error after the tracks launch leaves the stream finished (pushes refused) until a reset.
+ * Synchronous; the tracks kernel, the synthesis launch and the kernel that moves the kept frames to the front of the
+ * stream's frame buffer run in this order on the stream's launch stream.
+ */
+int gvtm_stream_push_events(gvtm_stream* stream, const gvtm_event* events, const int64_t* chunk_offsets,
+		const int64_t* utt_chunks, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* frame_counts_out);
+/* the stream's drift generators, one per utterance */
+int gvtm_stream_get_drift(const gvtm_stream* stream, gvtm_drift_state* states_out /* [batch], host */);
+/* states [batch] (host), or NULL: fresh generators -- the one call that reseeds them */
+int gvtm_stream_set_drift(gvtm_stream* stream, const gvtm_drift_state* states);
 
 /* Same with host buffers (H2D, kernel, D2H, synchronous). */
 int gvtm_generate_tracks_host(int device, const gvtm_track_config* config, const gvtm_event* events,
