@@ -887,7 +887,22 @@ gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 	std::memset(&args.fir_k, 0, sizeof(args.fir_k));
 	if (!dg.model5) {
 		if (dg.f32) {
-			for (size_t i = 0; i < dg.fir_f.size() && i < 64; ++i) args.fir_k.f[i] = dg.fir_f[i];
+			for (size_t i = 0; i < dg.fir_f.size() && i < static_cast<size_t>(gvtm::kFirKConsts); ++i) args.fir_k.f[i] = dg.fir_f[i];
+			// the float kernel's plan constants as floats (several voices: the kernel reads each voice's own from kconst)
+			float* kf = args.fir_k.f + gvtm::kFirKConsts;
+			for (int q = 0; q < 8; ++q) kf[gvtm::kKfRadiusCoef + q] = static_cast<float>(dg.k.radius_coef[q]);
+			kf[gvtm::kKfAperture2] = static_cast<float>(dg.k.aperture_radius2);
+			kf[gvtm::kKfNasalR2Sq] = static_cast<float>(dg.k.nasal_r2_sq);
+			kf[gvtm::kKfBasicIncrement] = static_cast<float>(dg.k.basic_increment);
+			kf[gvtm::kKfBpT] = static_cast<float>(dg.k.bp_T);
+			kf[gvtm::kKfBreathiness] = static_cast<float>(dg.k.breathiness);
+			kf[gvtm::kKfCrossmix] = static_cast<float>(dg.k.crossmix_factor);
+			kf[gvtm::kKfThroatB0] = static_cast<float>(dg.k.throat_b0);
+			kf[gvtm::kKfThroatA1] = static_cast<float>(dg.k.throat_a1);
+			kf[gvtm::kKfThroatGain] = static_cast<float>(dg.k.throat_gain);
+			kf[gvtm::kKfMouthARad] = static_cast<float>(dg.k.mouth_a_rad);
+			kf[gvtm::kKfNoseARad] = static_cast<float>(dg.k.nose_a_rad);
+			kf[gvtm::kKfNasalK5] = static_cast<float>(dg.k.nasal_k[5]);
 		} else {
 			for (size_t i = 0; i < dg.fir.size() && i < 49; ++i) args.fir_k.d[i] = dg.fir[i];
 		}

@@ -110,6 +110,7 @@ __device__ __forceinline__ float rmul(float a, float b)
 }
 
 // Util::amplitude60dB (vtm/VTMUtil.h:48-67)
+template <bool FAR_INLINE = false>
 __device__ __forceinline__ double amplitude_60db_dev(double db)
 {
 	if (db <= 0.0) return 0.0;
@@ -117,30 +118,34 @@ __device__ __forceinline__ double amplitude_60db_dev(double db)
 	return vmath::exp10_short((db - 60.0) * (1.0 / 20.0));
 }
 // TFloat = float: std::pow(10.0f, x) is powf, reproduced bit for bit (vtm_math.hpp)
+// (FAR_INLINE, here and below: the float routine's library fallback in line instead of as a cold call; nothing in double)
+template <bool FAR_INLINE = false>
 __device__ __forceinline__ float amplitude_60db_dev(float db)
 {
 	if (db <= 0.0f) return 0.0f;
 	if (db == 60.0f) return 1.0f;
 	const float y = rmul(db - 60.0f, static_cast<float>(1.0 / 20.0));
-	return vmath::powf_base10(y);
+	return vmath::powf_base10<FAR_INLINE>(y);
 }
 
 // Util::frequency (vtm/VTMUtil.h:74-84)
+template <bool FAR_INLINE = false>
 __device__ __forceinline__ double frequency_dev(double pitch)
 {
 	return 220.0 * vmath::exp2_short((pitch + 3.0) * (1.0 / 12.0));
 }
+template <bool FAR_INLINE = false>
 __device__ __forceinline__ float frequency_dev(float pitch)
 {
 	const float x = rmul(pitch + 3.0f, static_cast<float>(1.0 / 12.0));
-	return rmul(220.0f, vmath::powf_base2(x));
+	return rmul(220.0f, vmath::powf_base2<FAR_INLINE>(x));
 }
 
 // std::tan / std::cos of BandpassFilter::update (BandpassFilter.h:105-106): tanf / cosf for TFloat = float
-__device__ __forceinline__ double tan_dev(double t) { return vmath::tan_short(t); }
-__device__ __forceinline__ double cos_dev(double t) { return vmath::cos_short(t); }
-__device__ __forceinline__ float tan_dev(float t) { return vmath::tanf_glibc(t); }
-__device__ __forceinline__ float cos_dev(float t) { return vmath::cosf_glibc(t); }
+template <bool FAR_INLINE = false> __device__ __forceinline__ double tan_dev(double t) { return vmath::tan_short(t); }
+template <bool FAR_INLINE = false> __device__ __forceinline__ double cos_dev(double t) { return vmath::cos_short(t); }
+template <bool FAR_INLINE = false> __device__ __forceinline__ float tan_dev(float t) { return vmath::tanf_glibc<FAR_INLINE>(t); }
+template <bool FAR_INLINE = false> __device__ __forceinline__ float cos_dev(float t) { return vmath::cosf_glibc<FAR_INLINE>(t); }
 
 template <typename T> struct Pair;
 template <> struct Pair<double> { using type = double2; };

@@ -381,6 +381,11 @@ __device__ __forceinline__ size_t voice_row(const SynthArgs& a, size_t slot)
 	return r < 0 ? a.batch : static_cast<size_t>(r);
 }
 
+// which shapes keep the library fallbacks of the float routines in their passes, and which take their plan constants as
+// floats from the kernel arguments (SynthArgs::fir_k: the host fills the block for every float plan, launch_v2 checks it)
+template <int D, int U> constexpr bool far_calls_inline() { return D == 1 && U == 4; }
+template <typename CT, int D, int U, bool VOICES> constexpr bool float_arg_consts() { return sizeof(CT) == 4 && !VOICES && !far_calls_inline<D, U>(); }
+
 template <typename CT, typename ST, int D, int U, int C, int NH, int LAYOUT_FLAGS>
 __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) void vtm_synth_kernel(const SynthArgs a)
 {
@@ -448,6 +453,15 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	// gvtm_stream_*: a launch continues utterances from the state an earlier launch left in device memory (a.stream)
 	// and leaves its own behind.  A push synthesizes whole frames, keeps the converter's flush for later and finds the
 	// frame AFTER its last one in the buffer; finish (and the one-shot entry) flushes.
+	// All-float kernel, one voice: the plan constants its passes and filter wavefronts use come as floats with the kernel
+	// arguments (SynthArgs::fir_k, FloatConst) -- scalar loads, off the LDS pipe this kernel keeps busy -- instead of as
+	// DeviceConstants' doubles in LDS, a 64-bit read and a conversion per lane and pass.  A float plan's constants are floats
+	// widened, so both are the same number.  Several voices: each workgroup's voice has its own block, in LDS.
+	// The four-row shape at SectionDelay 1 keeps the LDS doubles and the library fallbacks in line: with either moved out it
+	// is 3-10 % slower (DESIGN.md 6; fewer spilled registers, a worse allocation of the helper loop).
+	constexpr bool kArgConsts = float_arg_consts<CT, D, U, VOICES>();
+	constexpr bool kFarInline = far_calls_inline<D, U>();
+#define GVTM_KF(idx, field) (kArgConsts ? static_cast<CT>(a.fir_k.f[kFirKConsts + (idx)]) : CT(k.field))
 	constexpr int kFr = fr_len<CT>();
 	constexpr bool kFrCompact = fr_compact<CT>();
 	// start of utterance u's records in a slot
@@ -707,10 +721,10 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			const float* pv = sm.prm + at_prm(c & 1, u) + s * kPrm;
 			const CT pitch = pv[0], gv = pv[1], av = pv[2];
 			// Util::frequency (VTMUtil.h:74-84) -> oscillator increment (WavetableGlottalSource.h:198, :218)
-			const CT f0 = frequency_dev(pitch);
-			sm.inc[((c & 1) * U + u) * C + s] = (f0 / CT(2.0)) * CT(k.basic_increment);
-			sm.amp[amp_at(c & 3, u, 0, s)] = amplitude_60db_dev(gv);
-			sm.amp[amp_at(c & 3, u, 1, s)] = amplitude_60db_dev(av);
+			const CT f0 = frequency_dev<kFarInline>(pitch);
+			sm.inc[((c & 1) * U + u) * C + s] = (f0 / CT(2.0)) * GVTM_KF(kKfBasicIncrement, basic_increment);
+			sm.amp[amp_at(c & 3, u, 0, s)] = amplitude_60db_dev<kFarInline>(gv);
+			sm.amp[amp_at(c & 3, u, 1, s)] = amplitude_60db_dev<kFarInline>(av);
 		}
 	};
 
@@ -871,10 +885,10 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			const CT lp = (kNoiseTable && a.noise_lp != nullptr) ? lp_table : sm.noise[((c % 3) * U + u) * C + s];
 			CT pulse = acc;
 			const CT pulsed_noise = rmul(lp, pulse);
-			pulse = rmul(ax, rmul(pulse, CT(1.0) - CT(k.breathiness)) + rmul(pulsed_noise, CT(k.breathiness)));
+			pulse = rmul(ax, rmul(pulse, CT(1.0) - GVTM_KF(kKfBreathiness, breathiness)) + rmul(pulsed_noise, GVTM_KF(kKfBreathiness, breathiness)));
 			CT signal;
 			if (k.modulation) {
-				CT cm = rmul(ax, CT(k.crossmix_factor));
+				CT cm = rmul(ax, GVTM_KF(kKfCrossmix, crossmix_factor));
 				cm = cm < CT(1.0) ? cm : CT(1.0);
 				signal = rmul(pulsed_noise, cm) + rmul(lp, CT(1.0) - cm);
 			} else {
@@ -901,7 +915,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			const CT fvol = pv[3], fpos = pv[4], fcf = pv[5], fbw = pv[6];
 			CT* fr = sm.fr + at_fr(c & 1, u) + s * kFr;
 			// setFricationTaps (VocalTractModel0.h:524-552)
-			const CT amp = amplitude_60db_dev(fvol);
+			const CT amp = amplitude_60db_dev<kFarInline>(fvol);
 			const int ipart = static_cast<int>(fpos);
 			const CT complement = fpos - ipart;
 			const CT remainder = CT(1.0) - complement;
@@ -924,8 +938,8 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			}
 			// BandpassFilter::update (BandpassFilter.h:91-110)
 			const CT pi = CT(3.14159265358979323846);
-			const CT tan_v = tan_dev(pi * fbw * CT(k.bp_T));
-			const CT cos_v = cos_dev(CT(2.0) * pi * fcf * CT(k.bp_T));
+			const CT tan_v = tan_dev<kFarInline>(pi * fbw * GVTM_KF(kKfBpT, bp_T));
+			const CT cos_v = cos_dev<kFarInline>(CT(2.0) * pi * fcf * GVTM_KF(kKfBpT, bp_T));
 			const CT a2 = (CT(1.0) - tan_v) / (CT(1.0) + tan_v);
 			CT* bpc = sm.usg + at_usg(c & 1, u) + s;
 			bpc[kF1B0 * C] = CT(0.5) - rmul(CT(0.5), a2);
@@ -944,7 +958,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			CT r2[8];
 #pragma unroll
 			for (int q = 0; q < 8; ++q) {
-				CT r = static_cast<CT>(cur[q]) * CT(k.radius_coef[q]);
+				CT r = static_cast<CT>(cur[q]) * GVTM_KF(kKfRadiusCoef + q, radius_coef[q]);
 				r = r > CT(0.01) ? r : CT(0.01);
 				r2[q] = rmul(r, r);
 			}
@@ -954,9 +968,9 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 #pragma unroll
 			// (fdiv_n: the division without range scaling -- squared radii are >= 1e-4 and of moderate size)
 			for (int q = 0; q < 7; ++q) kj[q] = fdiv_n(r2[q] - r2[q + 1], r2[q] + r2[q + 1]);
-			kj[7] = fdiv_n(r2[7] - CT(k.aperture_radius2), r2[7] + CT(k.aperture_radius2));
+			kj[7] = fdiv_n(r2[7] - GVTM_KF(kKfAperture2, aperture_radius2), r2[7] + GVTM_KF(kKfAperture2, aperture_radius2));
 			const CT asum = fdiv_n(CT(2.0), r2[3] + r2[3] + velum2);
-			const CT nk1 = fdiv_n(velum2 - CT(k.nasal_r2_sq), velum2 + CT(k.nasal_r2_sq));
+			const CT nk1 = fdiv_n(velum2 - GVTM_KF(kKfNasalR2Sq, nasal_r2_sq), velum2 + GVTM_KF(kKfNasalR2Sq, nasal_r2_sq));
 			// compact record: the tube lanes pick their slot through the layout table
 			CT* kl = sm.kl + at_kl(c & 1, u) + (kLaneRec ? 0 : s * kKlLen);
 			if constexpr (kLaneRec) {
@@ -1362,7 +1376,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 		const bool inj_lane = active && Lf < 9 && (kRowView || lane < 16);
 		const int my_section = Lf - 1; // compact record: the frication tap this lane scales (FC1..FC8 = taps 0..7 on lanes 1..8)
 		const int tap_idx = (Lf >= 1 && Lf <= 8) ? Lf - 1 : kFr - 1; // dense record: my tap, or the padding slot (always 0)
-		const CT tb0 = CT(k.throat_b0), ta1 = CT(k.throat_a1), tgain = CT(k.throat_gain);
+		const CT tb0 = GVTM_KF(kKfThroatB0, throat_b0), ta1 = GVTM_KF(kKfThroatA1, throat_a1), tgain = GVTM_KF(kKfThroatGain, throat_gain);
 		// lanes that own no result store into the dump area (no exec-mask juggling in the loop)
 		if (kMaskedSerial && !inj_lane) return; // (the other lanes used to read every input and store into a dump area: LDS time)
 		CT* inj_w = inj_lane ? inj + Lf : sm.dump + lane;
@@ -1462,7 +1476,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 		ST* xr = sm.x + u * XRS;
 		// lane 0 of the row filters the mouth, lane 1 the nose (the others mirror lane 1)
 		const int which = L == 0 ? 0 : 1;
-		const CT ra = L == 0 ? CT(k.mouth_a_rad) : CT(k.nose_a_rad);
+		const CT ra = L == 0 ? GVTM_KF(kKfMouthARad, mouth_a_rad) : GVTM_KF(kKfNoseARad, nose_a_rad);
 		const bool x_owner = active && L == 0; // the lane that writes the ring; the others store into the dump area
 		ST* const x_dump = reinterpret_cast<ST*>(sm.dump + 128 + lane);
 		const bool dbg = GVTM_KERNEL_TAPS && a.debug_taps != nullptr && active && L == 0;
@@ -1479,7 +1493,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 		// (1 + k) * top (VocalTractModel0.h:628, :655) is formed here, k being the mouth's coefficient of the step or the
 		// nose's constant one (two instructions less per step in the tube wavefront, whose chain is the longest)
 		const CT* pq = kLaneRec ? sm.opk + (static_cast<size_t>(c % 3) * U + u) * C : thy;
-		const CT opk_nose = CT(1.0) + CT(k.nasal_k[5]);
+		const CT opk_nose = CT(1.0) + GVTM_KF(kKfNasalK5, nasal_k[5]);
 		static_assert(C % 4 == 0, "post-tube filters work in blocks of four steps");
 		struct Blk2 { CT x[4], t[4], q[4]; };
 		auto fetch2 = [&]() {
@@ -2145,5 +2159,6 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 }
 
 #undef GVTM_ROW_UTT
+#undef GVTM_KF
 
 } // namespace v2

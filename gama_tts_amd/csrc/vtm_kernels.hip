@@ -182,6 +182,10 @@ static hipError_t launch_v2(const SynthArgs& args, size_t batch, hipStream_t str
 		auto fn = v2::vtm_synth_kernel<typename S::CT, typename S::ST, S::D, S::U, S::C, S::NH, S::LAYOUT | (VOICES ? v2::kVoicesFlag : 0)>;
 		if (args.xr < ring_length(args.k, S::C) || (args.xr & (args.xr - 1)) != 0 || 2 * S::C + 4 * args.k.pad + 64 > args.xr) return hipErrorInvalidValue;
 		if (!args.k.upsampling && args.xr != kSrcRing) return hipErrorInvalidValue;
+		// a kernel that takes its plan constants from the float block behind fir_k needs that block filled (synth_args does)
+		if constexpr (v2::float_arg_consts<typename S::CT, S::D, S::U, VOICES>()) {
+			if (args.fir_k.f[kFirKConsts + kKfBasicIncrement] != static_cast<float>(args.k.basic_increment)) return hipErrorInvalidValue;
+		}
 		const size_t lds = S::lds_bytes(args.xr);
 		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
 				static_cast<int>(lds));

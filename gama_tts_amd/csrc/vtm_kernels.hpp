@@ -63,6 +63,16 @@ struct Stream5Layout {
 	static constexpr size_t bytes() { return (yring() + sizeof(float) * 512 + 15) & ~size_t(15); }
 };
 
+// Plan constants of the all-float kernel as floats, by value behind the decimator's coefficients (SynthArgs::fir_k): the
+// helper passes and the filter wavefronts then take them from scalar registers instead of reading DeviceConstants' doubles
+// in LDS and converting them per lane and pass.  A float plan's constants are floats widened, so these are the same numbers.
+enum FloatConst : int {
+	kKfRadiusCoef = 0, // [8]
+	kKfAperture2 = 8, kKfNasalR2Sq, kKfBasicIncrement, kKfBpT, kKfBreathiness, kKfCrossmix, kKfThroatB0, kKfThroatA1, kKfThroatGain,
+	kKfMouthARad, kKfNoseARad, kKfNasalK5, kKfCount
+};
+constexpr int kFirKConsts = 64; // SynthArgs::fir_k.f[kFirKConsts + FloatConst]
+
 struct SynthArgs {
 	DeviceConstants k;              // by value (host-side launch decisions)
 	const DeviceConstants* kconst;  // the same constants in device memory (the kernel stages them in LDS)
@@ -75,7 +85,9 @@ struct SynthArgs {
 	const void* fir;             // [fir_taps]
 	// the same coefficients by value: kernel arguments are read with scalar loads, so the decimator's unrolled tap loop
 	// takes them from SGPRs (d: the double design, f: the float design of GVTM_PRECISION_F32)
-	union FirByValue { double d[49]; float f[64]; } fir_k;
+	// (the float view is as long as the double one: the float constants above sit behind the 64 coefficient slots)
+	union FirByValue { double d[49]; float f[98]; } fir_k;
+	static_assert(sizeof(FirByValue) == sizeof(double) * 49 && kFirKConsts + kKfCount <= 98, "float constants fit behind the float coefficients");
 	const void* src_h;           // [3328]
 	const void* src_dh;          // [3328]
 	const void* noise_lp = nullptr;  // [noise_len] the noise source's low-passed samples by internal step (one-shot launches), or

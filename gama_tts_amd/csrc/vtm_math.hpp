@@ -16,8 +16,12 @@
 
 #if defined(__HIPCC__)
 #define GVTM_HD __host__ __device__ __forceinline__
+// a routine the model's arguments never reach (the library fallbacks of the float restatements below): out of line, so
+// that its registers, its scratch and its several hundred instructions stay out of the caller's fast path
+#define GVTM_COLD __host__ __device__ inline __attribute__((noinline, cold))
 #else
 #define GVTM_HD inline
+#define GVTM_COLD inline __attribute__((noinline, cold))
 #endif
 
 namespace gvtm {
@@ -177,20 +181,31 @@ GVTM_HD float powf_exp2_core(double xd)
 	return static_cast<float>(y);
 }
 
+// the library routines behind the range checks of the float restatements (never taken by the model's arguments).  A caller
+// may ask for them in line instead (FAR_INLINE): the four-row kernel at SectionDelay 1 is faster with them in its passes
+// (DESIGN.md 6).
+GVTM_COLD float powf_base2_far(float x) { return static_cast<float>(std::exp2(static_cast<double>(x))); }
+GVTM_COLD float powf_base10_far(float y) { return static_cast<float>(std::pow(10.0, static_cast<double>(y))); }
+GVTM_COLD float cosf_far(float y) { return static_cast<float>(std::cos(static_cast<double>(y))); }
+GVTM_COLD float sinf_far(float y) { return static_cast<float>(std::sin(static_cast<double>(y))); }
+GVTM_COLD float tanf_far(float x) { return static_cast<float>(std::tan(static_cast<double>(x))); }
+
 // powf(2.0f, x), |x| < 100 (the model's pitch range gives |x| < 10)
+template <bool FAR_INLINE = false>
 GVTM_HD float powf_base2(float x)
 {
-	if (!(std::fabs(x) < 100.0f)) return static_cast<float>(std::exp2(static_cast<double>(x)));
+	if (!(std::fabs(x) < 100.0f)) return FAR_INLINE ? static_cast<float>(std::exp2(static_cast<double>(x))) : powf_base2_far(x);
 	return powf_exp2_core(static_cast<double>(x));
 }
 
 // powf(10.0f, y), |y| < 30 (dB conversions give -3 <= y < 0)
+template <bool FAR_INLINE = false>
 GVTM_HD float powf_base10(float y)
 {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-	if (!(std::fabs(y) < 30.0f)) return static_cast<float>(std::pow(10.0, static_cast<double>(y)));
+	if (!(std::fabs(y) < 30.0f)) return FAR_INLINE ? static_cast<float>(std::pow(10.0, static_cast<double>(y))) : powf_base10_far(y);
 	constexpr double log2_10_glibc = 0x1.a934f0979b22dp+1; // log2_inline(10.0f)
 	const double ylogx = static_cast<double>(y) * log2_10_glibc;
 	return powf_exp2_core(ylogx);
@@ -219,13 +234,14 @@ GVTM_HD float bits_float(uint32_t u)
 	return f;
 }
 
+template <bool FAR_INLINE = false>
 GVTM_HD float cosf_glibc(float y)
 {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
 	const uint32_t top = (float_bits(y) >> 20) & 0x7ffu;
-	if (!(top < ((float_bits(120.0f) >> 20) & 0x7ffu))) return static_cast<float>(std::cos(static_cast<double>(y)));
+	if (!(top < ((float_bits(120.0f) >> 20) & 0x7ffu))) return FAR_INLINE ? static_cast<float>(std::cos(static_cast<double>(y))) : cosf_far(y);
 	constexpr double hpi_inv = 0x1.45F306DC9C883p+23, hpi = 0x1.921FB54442D18p0;
 	constexpr double c0 = 0x1p0, c1 = -0x1.ffffffd0c621cp-2, c2 = 0x1.55553e1068f19p-5, c3 = -0x1.6c087e89a359dp-10,
 			c4 = 0x1.99343027bf8c3p-16;
@@ -277,7 +293,7 @@ GVTM_HD float sinf_glibc(float y)
 #pragma clang fp contract(off)
 #endif
 	const uint32_t top = (float_bits(y) >> 20) & 0x7ffu;
-	if (!(top < ((float_bits(120.0f) >> 20) & 0x7ffu))) return static_cast<float>(std::sin(static_cast<double>(y)));
+	if (!(top < ((float_bits(120.0f) >> 20) & 0x7ffu))) return sinf_far(y);
 	constexpr double hpi_inv = 0x1.45F306DC9C883p+23, hpi = 0x1.921FB54442D18p0;
 	constexpr double c0 = 0x1p0, c1 = -0x1.ffffffd0c621cp-2, c2 = 0x1.55553e1068f19p-5, c3 = -0x1.6c087e89a359dp-10,
 			c4 = 0x1.99343027bf8c3p-16;
@@ -361,12 +377,13 @@ GVTM_HD float tanf_kernel_glibc(float x, float y, int iy)
 	return t + a * (s + t * v);
 }
 
+template <bool FAR_INLINE = false>
 GVTM_HD float tanf_glibc(float x)
 {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-	if (!(x >= 0.0f && x <= 1.38f)) return static_cast<float>(std::tan(static_cast<double>(x)));
+	if (!(x >= 0.0f && x <= 1.38f)) return FAR_INLINE ? static_cast<float>(std::tan(static_cast<double>(x))) : tanf_far(x);
 	const uint32_t ix = float_bits(x);
 	if (ix <= 0x3f490fdau) return tanf_kernel_glibc(x, 0.0f, 1);
 	// __ieee754_rem_pio2f for pi/4 < x < 3pi/4: x - pi/2 in two floats
