@@ -216,18 +216,22 @@ int gvtm_device_count(void)
 
 namespace {
 
+// Is there a HIP device at this index?  (what: the caller, which has no CPU path)
+int check_device_index(int device, const char* what)
+{
+	int n = 0;
+	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(GVTM_ERR_NO_DEVICE, std::string("no HIP device available (") + what + " has no CPU path)");
+	if (device < 0 || device >= n) return fail(GVTM_ERR_NO_DEVICE, "device index out of range");
+	return GVTM_OK;
+}
+
 // The device part of every plan: a HIP device at that index, a gfx950 one, and its compute units
 int open_device(gvtm_plan* plan, int device)
 {
-	int n = 0;
-	hipError_t e = hipGetDeviceCount(&n);
-	if (e != hipSuccess || n <= 0) {
-		return fail(GVTM_ERR_NO_DEVICE, "no HIP device available (libgama_vtm has no CPU path)");
-	}
-	if (device < 0 || device >= n) return fail(GVTM_ERR_NO_DEVICE, "device index out of range");
+	if (const int rc = check_device_index(device, "libgama_vtm"); rc != GVTM_OK) return rc;
 	plan->device = device;
 	hipDeviceProp_t prop;
-	if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return fail_hip(e, "hipGetDeviceProperties");
+	if (const hipError_t e = hipGetDeviceProperties(&prop, device); e != hipSuccess) return fail_hip(e, "hipGetDeviceProperties");
 	if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
 		return fail(GVTM_ERR_NO_DEVICE, std::string("kernels are built for gfx950 only, device is ") + prop.gcnArchName);
 	}
@@ -326,6 +330,25 @@ int refuse_voices(const gvtm_plan* plan, const char* entry)
 bool control_period_matches(const gvtm_plan* plan, const gvtm::TrackConstants& tk)
 {
 	return static_cast<double>(tk.control_period) * plan->designs[0].control_rate == 1000.0;
+}
+
+// Track arguments for a batch of a plan of voices: from the plan its table on the device and the control period, which is
+// every voice's (gvtm_plan_set_voice_tracks); the kernel variant's offset tables (and row_start) are the caller's to add
+gvtm::TrackAppendArgs plan_track_args(const gvtm_plan* plan, const gvtm_event* d_events, const int32_t* d_voice_ids, size_t batch, size_t max_frames,
+		float* d_params, int32_t* d_frame_counts, gvtm_drift_state* d_drift)
+{
+	gvtm::TrackAppendArgs args{};
+	args.k.control_period = plan->voice_tracks[0].control_period;
+	args.events = d_events;
+	args.batch = batch;
+	args.max_frames = max_frames;
+	args.params = d_params;
+	args.frame_counts = d_frame_counts;
+	args.drift = d_drift;
+	args.voice_k = static_cast<const gvtm::TrackConstants*>(plan->d_voice_tracks.ptr);
+	args.voice_ids = d_voice_ids;
+	args.n_voices = plan->n_voices();
+	return args;
 }
 
 void fill_info(const gvtm_plan* plan, const gvtm::Design& dg, gvtm_info* info)
@@ -654,19 +677,9 @@ int gvtm_debug_tracks_append(gvtm_plan* plan, const gvtm_event* d_events, const 
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	gvtm::TrackAppendArgs args{};
-	args.k.control_period = plan->voice_tracks[0].control_period;
-	args.events = d_events;
+	gvtm::TrackAppendArgs args = plan_track_args(plan, d_events, d_voice_ids, batch, max_frames, d_params, d_frame_counts, d_drift);
 	args.chunk_offsets = d_chunk_offsets;
 	args.utt_chunks = d_utt_chunks;
-	args.batch = batch;
-	args.max_frames = max_frames;
-	args.params = d_params;
-	args.frame_counts = d_frame_counts;
-	args.drift = d_drift;
-	args.voice_k = static_cast<const gvtm::TrackConstants*>(plan->d_voice_tracks.ptr);
-	args.voice_ids = d_voice_ids;
-	args.n_voices = plan->n_voices();
 	args.row_start = d_row_start;
 	e = gvtm::launch_tracks_append(args, nullptr);
 	if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -728,9 +741,7 @@ int gvtm_generate_tracks_device(int device, const gvtm_track_config* config, con
 	if (!d_events) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events");
 	// frames leave the kernel as float4 stores
 	if (reinterpret_cast<uintptr_t>(d_params) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params must be 16-byte aligned");
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(GVTM_ERR_NO_DEVICE, "no HIP device available (track generation has no CPU path)");
-	if (device < 0 || device >= n) return fail(GVTM_ERR_NO_DEVICE, "device index out of range");
+	if (const int rc = check_device_index(device, "track generation"); rc != GVTM_OK) return rc;
 	DeviceScope scope(device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
@@ -756,9 +767,7 @@ int gvtm_generate_tracks_host(int device, const gvtm_track_config* config, const
 	for (size_t b = 0; b < batch; ++b) {
 		if (event_offsets[b + 1] < event_offsets[b] || event_offsets[0] != 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "event_offsets must start at 0 and not decrease");
 	}
-	int n = 0;
-	if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(GVTM_ERR_NO_DEVICE, "no HIP device available (track generation has no CPU path)");
-	if (device < 0 || device >= n) return fail(GVTM_ERR_NO_DEVICE, "device index out of range");
+	if (const int rc = check_device_index(device, "track generation"); rc != GVTM_OK) return rc;
 	DeviceScope scope(device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
@@ -1028,6 +1037,18 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	});
 }
 
+// What lies between the two launches of an events entry: the plan's frame buffer (the enqueue-only entries' scratch) and
+// the frame counts, the caller's or the plan's
+int events_scratch(gvtm_plan* plan, size_t batch, size_t max_frames, int32_t* d_frame_counts, float*& d_params, int32_t*& d_counts)
+{
+	hipError_t e;
+	if ((e = plan->async.params.ensure(sizeof(float) * batch * std::max<size_t>(max_frames, 1) * GVTM_N_PARAM)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
+	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
+	d_params = static_cast<float*>(plan->async.params.ptr);
+	d_counts = d_frame_counts ? d_frame_counts : static_cast<int32_t*>(plan->async.frames.ptr);
+	return GVTM_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1062,7 +1083,7 @@ int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* conf
 	if (!control_period_matches(plan, tk)) {
 		return fail(GVTM_ERR_INVALID_ARGUMENT, "control_period_ms of the track configuration and the plan's control rate disagree");
 	}
-	// Two launches on the caller's stream with a frame buffer of the plan's in between (the enqueue-only entries' scratch).  (Walking the event lists inside the
+	// Two launches on the caller's stream with a frame buffer of the plan's in between.  (Walking the event lists inside the
 	// synthesis kernel's interpolation wavefront was built and measured: bit-identical, no frame buffer, and 17.2 -> 33.1 ms
 	// per 4096 x 80 events -- an event boundary is a round trip to memory in the middle of a tick, three times over because
 	// the parameter groups run at different lags -- and 125 ms with the next events prefetched into registers, which that
@@ -1070,14 +1091,12 @@ int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* conf
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	if ((e = plan->async.params.ensure(sizeof(float) * batch * std::max<size_t>(max_frames, 1) * GVTM_N_PARAM)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
-	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
-	int32_t* const counts = d_frame_counts ? d_frame_counts : static_cast<int32_t*>(plan->async.frames.ptr);
-	int rc = gvtm_generate_tracks_device(plan->device, config, d_events, d_event_offsets, batch, max_frames, static_cast<float*>(plan->async.params.ptr), counts,
-			d_drift, hip_stream);
+	float* frames;
+	int32_t* counts;
+	int rc = events_scratch(plan, batch, max_frames, d_frame_counts, frames, counts);
+	if (rc == GVTM_OK) rc = gvtm_generate_tracks_device(plan->device, config, d_events, d_event_offsets, batch, max_frames, frames, counts, d_drift, hip_stream);
 	if (rc != GVTM_OK) return rc;
-	return launch_synthesis(plan, LaunchRequest{static_cast<const float*>(plan->async.params.ptr), counts, batch, max_frames, d_audio, audio_stride,
-			d_out_counts, d_maxabs, hip_stream});
+	return launch_synthesis(plan, LaunchRequest{frames, counts, batch, max_frames, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream});
 }
 
 int gvtm_plan_set_voice_tracks(gvtm_plan* plan, const gvtm_track_config* configs, size_t n_configs)
@@ -1136,23 +1155,9 @@ int launch_voice_tracks(gvtm_plan* plan, const VoiceEvents& lists, size_t batch,
 	// frames leave the kernel as float4 stores
 	if (reinterpret_cast<uintptr_t>(d_params) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params must be 16-byte aligned");
 	if (batch > 0x7fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
-	gvtm::TrackChunksArgs args{};
-	args.k.control_period = plan->voice_tracks[0].control_period; // (every voice's is the plan's: gvtm_plan_set_voice_tracks)
-	args.events = lists.d_events;
-	if (lists.chunked) {
-		args.chunk_offsets = lists.d_offsets;
-		args.utt_chunks = lists.d_utt_chunks;
-	} else {
-		args.event_offsets = lists.d_offsets;
-	}
-	args.batch = batch;
-	args.max_frames = max_frames;
-	args.params = d_params;
-	args.frame_counts = d_frame_counts;
-	args.drift = d_drift;
-	args.voice_k = static_cast<const gvtm::TrackConstants*>(plan->d_voice_tracks.ptr);
-	args.voice_ids = lists.d_voice_ids;
-	args.n_voices = plan->n_voices();
+	gvtm::TrackChunksArgs args = plan_track_args(plan, lists.d_events, lists.d_voice_ids, batch, max_frames, d_params, d_frame_counts, d_drift);
+	(lists.chunked ? args.chunk_offsets : args.event_offsets) = lists.d_offsets;
+	args.utt_chunks = lists.d_utt_chunks; // (null unless chunked)
 	const hipError_t e = lists.chunked ? gvtm::launch_tracks_chunks(args, static_cast<hipStream_t>(hip_stream))
 	                                   : gvtm::launch_tracks_voices(args, static_cast<hipStream_t>(hip_stream));
 	if (e != hipSuccess) return fail_hip(e, lists.chunked ? "track generation launch (chunks)" : "track generation launch (voices)");
@@ -1194,13 +1199,12 @@ int synthesize_voice_events(gvtm_plan* plan, const char* entry, const VoiceEvent
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-	if ((e = plan->async.params.ensure(sizeof(float) * batch * std::max<size_t>(max_frames, 1) * GVTM_N_PARAM)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
-	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
-	int32_t* const counts = d_frame_counts ? d_frame_counts : static_cast<int32_t*>(plan->async.frames.ptr);
-	rc = launch_voice_tracks(plan, lists, batch, max_frames, static_cast<float*>(plan->async.params.ptr), counts, d_drift, hip_stream);
-	if (rc != GVTM_OK) return rc;
-	return launch_synthesis(plan, LaunchRequest{static_cast<const float*>(plan->async.params.ptr), counts, batch, max_frames, d_audio, audio_stride,
-			d_out_counts, d_maxabs, hip_stream, 0, true, lists.d_voice_ids, &plan->async.groups});
+	float* frames;
+	int32_t* counts;
+	if ((rc = events_scratch(plan, batch, max_frames, d_frame_counts, frames, counts)) != GVTM_OK) return rc;
+	if ((rc = launch_voice_tracks(plan, lists, batch, max_frames, frames, counts, d_drift, hip_stream)) != GVTM_OK) return rc;
+	return launch_synthesis(plan, LaunchRequest{frames, counts, batch, max_frames, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream, 0, true,
+			lists.d_voice_ids, &plan->async.groups});
 }
 
 } // namespace
@@ -1565,6 +1569,28 @@ uint64_t outputs_before(const gvtm::DeviceConstants& k, uint64_t steps)
 	return ((steps << 16) + k.time_inc - 1) / k.time_inc;
 }
 
+// The samples of one launch on behalf of the stream, known before it: utterance b synthesizes n_frames[b] more frames.
+// want[b]: its exact sample count; need: the largest of them; too_long: an utterance would pass the 2^31-step limit.
+struct StreamSamples {
+	std::vector<int64_t> want;
+	size_t need = 0;
+	bool too_long = false;
+};
+
+StreamSamples stream_samples(const gvtm_stream* s, const std::vector<size_t>& n_frames, bool final)
+{
+	StreamSamples r{std::vector<int64_t>(s->batch, 0)};
+	for (size_t b = 0; b < s->batch; ++b) {
+		const gvtm::DeviceConstants& k = s->plan->designs[voice_of(s, b)].k;
+		const uint64_t after = s->steps_done[b] + static_cast<uint64_t>(n_frames[b]) * k.control_steps;
+		if (after + 4096ull >= (1ull << 31)) r.too_long = true;
+		const uint64_t k1 = final ? gvtm::src_output_count(k.time_inc, k.pad, k.upsampling, after) : outputs_before(k, after);
+		r.want[b] = static_cast<int64_t>(k1 - outputs_before(k, s->steps_done[b]));
+		r.need = std::max(r.need, static_cast<size_t>(r.want[b]));
+	}
+	return r;
+}
+
 // One launch on behalf of the stream: utterance b synthesizes n_frames[b] frames from the front of held[b] -- or, in an
 // events-fed run, from the front of its block of d_held, which the launch reads in place (no staging, no copy of frames);
 // behind a push's launch the carry kernel then moves the rows it left to the front of the block.
@@ -1585,20 +1611,10 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 		if (n_frames[b] != n_frames[f] || s->steps_done[b] != s->steps_done[f]) lockstep = false;
 		if (n_frames[b]) any = true;
 	}
-	// exact sample counts, known before the launch
-	size_t need = 0;
-	std::vector<int64_t> want(batch, 0);
-	for (size_t b = 0; b < batch; ++b) {
-		const gvtm::DeviceConstants& k = plan->designs[voice_of(s, b)].k;
-		const uint64_t after = s->steps_done[b] + static_cast<uint64_t>(n_frames[b]) * k.control_steps;
-		if (after + 4096ull >= (1ull << 31)) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
-		const uint64_t k0 = outputs_before(k, s->steps_done[b]);
-		const uint64_t k1 = final ? gvtm::src_output_count(k.time_inc, k.pad, k.upsampling, after) : outputs_before(k, after);
-		want[b] = static_cast<int64_t>(k1 - k0);
-		need = std::max(need, static_cast<size_t>(want[b]));
-	}
-	if (need > audio_stride) return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than this call produces (gvtm_stream_capacity)");
-	if (need > 0 && !audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
+	const StreamSamples samples = stream_samples(s, n_frames, final);
+	if (samples.too_long) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
+	if (samples.need > audio_stride) return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than this call produces (gvtm_stream_capacity)");
+	if (samples.need > 0 && !audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
 	if (!any) {
 		if (out_counts) std::fill(out_counts, out_counts + batch, int64_t(0));
 		return GVTM_OK;
@@ -1648,7 +1664,7 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	std::vector<int64_t> got(batch, 0);
 	if ((e = hipMemcpy(got.data(), s->d_counts.ptr, sizeof(int64_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H counts");
 	for (size_t b = 0; b < batch; ++b) {
-		if (got[b] != want[b]) return fail(GVTM_ERR_HIP, "internal error: the device's sample count differs from the host's");
+		if (got[b] != samples.want[b]) return fail(GVTM_ERR_HIP, "internal error: the device's sample count differs from the host's");
 	}
 	if (audio && audio_stride && (e = hipMemcpy(audio, s->d_audio.ptr, sizeof(float) * batch * audio_stride, hipMemcpyDeviceToHost)) != hipSuccess) {
 		return fail_hip(e, "D2H audio");
@@ -1926,19 +1942,10 @@ int stream_append_and_launch(gvtm_stream* s, const gvtm_event* events, const int
 	if ((e = hipMemcpy(s->d_utt_chunks.ptr, utt_chunks, sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D utterance chunks");
 	if ((e = hipMemcpy(s->d_rows.ptr, rows.data(), sizeof(int32_t) * 2 * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D row starts");
 	// append, synthesis, carry: all on the stream's launch stream
-	gvtm::TrackAppendArgs ta{};
-	ta.k.control_period = plan->voice_tracks[0].control_period; // (every voice's is the plan's: gvtm_plan_set_voice_tracks)
-	ta.events = static_cast<const gvtm_event*>(s->d_events.ptr);
+	gvtm::TrackAppendArgs ta = plan_track_args(plan, static_cast<const gvtm_event*>(s->d_events.ptr), static_cast<const int32_t*>(s->d_voice_ids.ptr), batch,
+			s->held_cap, static_cast<float*>(s->d_held.ptr), static_cast<int32_t*>(s->d_new_counts.ptr), static_cast<gvtm_drift_state*>(s->d_drift.ptr));
 	ta.chunk_offsets = static_cast<const int64_t*>(s->d_chunk_offsets.ptr);
 	ta.utt_chunks = static_cast<const int64_t*>(s->d_utt_chunks.ptr);
-	ta.batch = batch;
-	ta.max_frames = s->held_cap;
-	ta.params = static_cast<float*>(s->d_held.ptr);
-	ta.frame_counts = static_cast<int32_t*>(s->d_new_counts.ptr);
-	ta.drift = static_cast<gvtm_drift_state*>(s->d_drift.ptr);
-	ta.voice_k = static_cast<const gvtm::TrackConstants*>(plan->d_voice_tracks.ptr);
-	ta.voice_ids = static_cast<const int32_t*>(s->d_voice_ids.ptr);
-	ta.n_voices = plan->n_voices();
 	ta.row_start = static_cast<const int32_t*>(s->d_rows.ptr);
 	if ((e = gvtm::launch_tracks_append(ta, nullptr)) != hipSuccess) return fail_hip(e, "track generation launch (append)");
 	*advanced = true;
@@ -1997,17 +2004,10 @@ int gvtm_stream_push_events(gvtm_stream* s, const gvtm_event* events, const int6
 			const unsigned granule = s->granule_frames[static_cast<size_t>(voice_of(s, b))];
 			n[b] = have[b] > 0 ? ((have[b] - 1) / granule) * granule : 0;
 		}
-		size_t need = 0;
-		bool too_long = false;
-		for (size_t b = 0; b < batch; ++b) {
-			const gvtm::DeviceConstants& k = plan->designs[voice_of(s, b)].k;
-			const uint64_t after = s->steps_done[b] + static_cast<uint64_t>(n[b]) * k.control_steps;
-			if (after + 4096ull >= (1ull << 31)) too_long = true;
-			need = std::max(need, static_cast<size_t>(outputs_before(k, after) - outputs_before(k, s->steps_done[b])));
-		}
-		if (need > audio_stride) return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than this call produces (gvtm_stream_capacity)");
-		if (need > 0 && !audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
-		if (too_long) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
+		const StreamSamples samples = stream_samples(s, n, false);
+		if (samples.need > audio_stride) return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than this call produces (gvtm_stream_capacity)");
+		if (samples.need > 0 && !audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
+		if (samples.too_long) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
 		bool advanced = false;
 		const int rc = stream_append_and_launch(s, events, chunk_offsets, utt_chunks, n_chunks, n_events, fresh, have, n, audio, audio_stride, out_counts, &advanced);
 		// past the tracks launch the drift generators and the held frames have moved on: no push until a reset
