@@ -94,6 +94,15 @@ class Config5(ctypes.Structure):
     ]
 
 
+class PackedStats(ctypes.Structure):
+    """gvtm_packed_stats"""
+    _fields_ = [("staging_bytes", ctypes.c_size_t), ("limit", ctypes.c_size_t), ("slices", ctypes.c_size_t),
+                ("largest_slice", ctypes.c_size_t)]
+
+
+PACKED_ALIGN = 8  # GVTM_PACKED_ALIGN
+
+
 def library_path(diagnostics=False):
     return os.path.join(_HERE, "lib", "libgama_vtm_diag.so" if diagnostics else _LIB_NAME)
 
@@ -225,6 +234,19 @@ def load_library(diagnostics=False):
     if hasattr(L, "gvtm_plan_create_model5_float_voices"):
         L.gvtm_plan_create_model5_float_voices.argtypes = [ctypes.POINTER(Config5), sz, dbl, i32, ctypes.POINTER(vp)]
         L.gvtm_plan_create_model5_float_voices.restype = i32
+    if hasattr(L, "gvtm_synthesize_packed_host"):
+        L.gvtm_packed_sample_offsets.argtypes = [vp, vp, vp, sz, vp]
+        L.gvtm_packed_sample_offsets.restype = sz
+        L.gvtm_synthesize_packed_host.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]
+        L.gvtm_synthesize_packed_host.restype = i32
+        L.gvtm_synthesize_packed_host_pcm16.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]
+        L.gvtm_synthesize_packed_host_pcm16.restype = i32
+        L.gvtm_plan_set_staging_limit.argtypes = [vp, sz]
+        L.gvtm_plan_set_staging_limit.restype = i32
+        L.gvtm_plan_packed_stats.argtypes = [vp, ctypes.POINTER(PackedStats)]
+        L.gvtm_plan_packed_stats.restype = i32
+        L.gvtm_plan_reserve.argtypes = [vp, sz]
+        L.gvtm_plan_reserve.restype = i32
     L.gvtm_plan_set_timing.argtypes = [vp, i32]
     L.gvtm_plan_set_timing.restype = i32
     L.gvtm_plan_take_kernel_ms.argtypes = [vp, ctypes.POINTER(i32)]
@@ -539,6 +561,86 @@ class Plan:
         scales = np.zeros(batch, dtype=np.float32)
         self.synthesize_host_into(params, pcm, frame_counts, counts, maxabs, scales)
         return pcm, counts, maxabs, scales
+
+    # ---- ragged batches, packed in and packed out (a VoicesPlan has them too; voice_ids: one per utterance) ----
+
+    @staticmethod
+    def pack_utterances(utterances):
+        """A list of float32 [F_b][16] arrays -> (frames float32 [sum F_b][16] back to back, frame_offsets int64 [B + 1])."""
+        utterances = [np.ascontiguousarray(u, dtype=np.float32).reshape(-1, N_PARAM) for u in utterances]
+        offsets = np.zeros(len(utterances) + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([u.shape[0] for u in utterances])
+        frames = np.concatenate(utterances) if utterances else np.zeros((0, N_PARAM), np.float32)
+        return np.ascontiguousarray(frames), offsets
+
+    def _ids(self, voice_ids, batch):
+        if voice_ids is None:
+            return None
+        ids = np.ascontiguousarray(voice_ids, dtype=np.int32)
+        assert ids.shape == (batch,)
+        return ids
+
+    def packed_sample_offsets(self, frame_offsets, voice_ids=None):
+        """gvtm_packed_sample_offsets -> int64 [B + 1]: utterance b starts at [b], the output needs [B] samples."""
+        frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+        batch = frame_offsets.shape[0] - 1
+        out = np.zeros(batch + 1, dtype=np.int64)
+        n = self._lib.gvtm_packed_sample_offsets(self._h, _ptr(frame_offsets), _ptr(self._ids(voice_ids, batch)), batch, _ptr(out))
+        if n == ctypes.c_size_t(-1).value:
+            raise GvtmError(1, self._lib.gvtm_last_error().decode())
+        return out
+
+    def synthesize_packed_host_into(self, frames, frame_offsets, out, voice_ids=None, sample_offsets=None, counts=None, maxabs=None,
+                                    scales=None):
+        """The packed entries with caller-owned (e.g. page-locked) buffers: frames float32 [sum F_b][16], frame_offsets int64
+        [B + 1]; `out` float32 [capacity] takes the unscaled samples (gvtm_synthesize_packed_host), `out` int16 [capacity] the
+        scaled 16-bit ones (.._pcm16); sample_offsets int64 [B + 1], counts int64 [B], maxabs and scales float32 [B] or None."""
+        assert frames.dtype == np.float32 and frames.flags.c_contiguous
+        assert frame_offsets.dtype == np.int64 and frame_offsets.flags.c_contiguous and out.flags.c_contiguous and out.ndim == 1
+        batch = frame_offsets.shape[0] - 1
+        ids = self._ids(voice_ids, batch)
+        if out.dtype == np.int16:
+            self._check(self._lib.gvtm_synthesize_packed_host_pcm16(
+                self._h, _ptr(frames), _ptr(frame_offsets), _ptr(ids), batch, _ptr(out), out.shape[0], _ptr(sample_offsets),
+                _ptr(counts), _ptr(maxabs), _ptr(scales)))
+        else:
+            assert out.dtype == np.float32 and scales is None
+            self._check(self._lib.gvtm_synthesize_packed_host(
+                self._h, _ptr(frames), _ptr(frame_offsets), _ptr(ids), batch, _ptr(out), out.shape[0], _ptr(sample_offsets),
+                _ptr(counts), _ptr(maxabs)))
+
+    def _packed(self, utterances, voice_ids, dtype):
+        frames, frame_offsets = self.pack_utterances(utterances)
+        batch = len(utterances)
+        offsets = self.packed_sample_offsets(frame_offsets, voice_ids)
+        out = np.zeros(int(offsets[batch]), dtype=dtype)
+        counts = np.zeros(batch, dtype=np.int64)
+        maxabs = np.zeros(batch, dtype=np.float32)
+        scales = np.zeros(batch, dtype=np.float32) if dtype == np.int16 else None
+        self.synthesize_packed_host_into(frames, frame_offsets, out, voice_ids, offsets, counts, maxabs, scales)
+        return out, offsets, counts, maxabs, scales
+
+    def synthesize_packed_host(self, utterances, voice_ids=None):
+        """utterances: a list of float32 [F_b][16] arrays -> (audio float32 [capacity], sample offsets int64 [B + 1], counts
+        int64 [B], maxabs float32 [B]); utterance b's samples are audio[offsets[b]: offsets[b] + counts[b]]."""
+        return self._packed(utterances, voice_ids, np.float32)[:4]
+
+    def synthesize_packed_host_pcm16(self, utterances, voice_ids=None):
+        """-> (pcm int16 [capacity], sample offsets, counts, maxabs, scales float32 [B])"""
+        return self._packed(utterances, voice_ids, np.int16)
+
+    def set_staging_limit(self, nbytes):
+        """gvtm_plan_set_staging_limit: an upper bound on the packed entries' device staging; 0 = none."""
+        self._check(self._lib.gvtm_plan_set_staging_limit(self._h, int(nbytes)))
+
+    def packed_stats(self):
+        st = PackedStats()
+        self._check(self._lib.gvtm_plan_packed_stats(self._h, ctypes.byref(st)))
+        return st
+
+    def reserve(self, max_frames):
+        """gvtm_plan_reserve: what launches of up to max_frames frames would build on first use, now."""
+        self._check(self._lib.gvtm_plan_reserve(self._h, int(max_frames)))
 
     def synthesize_events_device(self, track_config, d_events, d_offsets, batch, max_frames, d_audio, audio_stride,
                                  d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, stream=None):

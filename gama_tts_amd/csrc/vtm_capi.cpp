@@ -15,6 +15,7 @@
 #include "../../include/gama_vtm.h"
 #include "vtm_design.hpp"
 #include "vtm_kernels.hpp"
+#include "vtm_pack.hpp"
 #include "vtm_tracks.hpp"
 #include "vtm_math.hpp"
 
@@ -138,6 +139,17 @@ struct gvtm_plan {
 	struct {
 		DeviceBuffer params, frames, groups;
 	} async;
+	// ... and the packed host entries' (gvtm_synthesize_packed_host*): three staging sets, each one allocation that a slice
+	// carves into its packed frames, padded frames, padded samples and packed output (gama_vtm.h: set_bytes), so that what is
+	// held is bounded by the slices and not by the batch; and the small per-utterance arrays of the whole batch
+	struct {
+		DeviceBuffer set[3];
+		DeviceBuffer frame_offsets, sample_offsets, frames, voice_ids, counts, maxabs, scales, groups;
+		size_t limit = 0;                       // gvtm_plan_set_staging_limit; 0: none
+		size_t slices = 0, largest_slice = 0;   // of the last call that ran
+		std::vector<Event> events;              // three per slice: frames arrived, packed output ready, output copied
+		size_t staging_bytes() const { return set[0].bytes + set[1].bytes + set[2].bytes; }
+	} packed;
 	// gvtm_plan_set_voice_tracks: one designed track configuration per voice, and (device plans) the table the voice
 	// variant of the tracks kernel reads; empty until the first call that succeeds
 	std::vector<gvtm::TrackConstants> voice_tracks;
@@ -2070,6 +2082,325 @@ int gvtm_normalize_batch_device(gvtm_plan* plan, const float* d_audio, size_t ba
 	e = gvtm::launch_normalize(args, batch, static_cast<hipStream_t>(hip_stream));
 	if (e != hipSuccess) return fail_hip(e, "vtm_normalize_kernel launch");
 	return GVTM_OK;
+}
+
+} // extern "C"
+
+/* ---------------------------------------------------------------------------------------------
+ * Ragged batches, packed in and packed out (include/gama_vtm.h, "Ragged batches").
+ */
+
+namespace {
+
+size_t round_up_packed(size_t n)
+{
+	return (n + GVTM_PACKED_ALIGN - 1) / GVTM_PACKED_ALIGN * GVTM_PACKED_ALIGN;
+}
+
+// The tables of a packed batch, all host memory, checked in the order the header lists the refusals; on success
+// offsets[b] is where utterance b starts in the packed output and offsets[batch] the capacity it needs.
+int packed_layout(const gvtm_plan* plan, const int64_t* frame_offsets, const int32_t* voice_ids, size_t batch, std::vector<int64_t>& offsets)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	offsets.assign(batch + 1, 0);
+	if (batch == 0) return GVTM_OK;
+	if (!frame_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null frame_offsets");
+	if (frame_offsets[0] != 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "frame_offsets must start at 0 and not decrease");
+	for (size_t b = 0; b < batch; ++b) {
+		if (frame_offsets[b + 1] < frame_offsets[b]) return fail(GVTM_ERR_INVALID_ARGUMENT, "frame_offsets must start at 0 and not decrease");
+	}
+	if (voice_ids) {
+		const int rc = check_voice_ids(plan, voice_ids, batch);
+		if (rc != GVTM_OK) return rc;
+	} else if (plan->n_voices() > 1) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids: the plan has " + std::to_string(plan->n_voices()) + " voices (one voice id per utterance)");
+	}
+	// (as launch_synthesis judges a launch: by the voice with the most steps per frame)
+	unsigned max_steps = 0;
+	for (int v = 0; v < plan->n_voices(); ++v) max_steps = std::max(max_steps, plan->designs[v].k.control_steps);
+	for (size_t b = 0; b < batch; ++b) {
+		const unsigned long long frames = static_cast<unsigned long long>(frame_offsets[b + 1] - frame_offsets[b]);
+		if (frames >= (1ull << 31) || frames * max_steps + 4096ull >= (1ull << 31)) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "utterance " + std::to_string(b) + ": frames * control_steps does not fit the 31-bit step counter");
+		}
+		const size_t count = design_output_count(plan->designs[voice_ids ? voice_ids[b] : 0], static_cast<size_t>(frames));
+		offsets[b + 1] = static_cast<int64_t>(round_up_packed(static_cast<size_t>(offsets[b]) + count));
+	}
+	return GVTM_OK;
+}
+
+struct PackedJob {
+	const float* frames;
+	const int64_t* frame_offsets;
+	const int32_t* voice_ids; // null: the plan's one voice through the single-voice launch, else the voices launch
+	size_t batch;
+	float* audio;     // float32 output, or null
+	int16_t* pcm;     // int16 output, or null
+	bool to_pcm;      // which of the two is due
+	size_t capacity;
+	int64_t* sample_offsets_out;
+	int64_t* out_counts;
+	float* maxabs;
+	float* scales;    // pcm only
+};
+
+// utterances [lo, hi) in one staging set: its longest utterance, the rows' length and the bytes of the header's formula
+struct PackedSlice {
+	size_t lo, hi, max_frames, stride, in_bytes, rows_bytes, audio_bytes, out_bytes;
+	size_t bytes() const { return in_bytes + rows_bytes + audio_bytes + out_bytes; }
+};
+
+PackedSlice packed_slice(const gvtm_plan* plan, const PackedJob& j, const std::vector<int64_t>& offsets, size_t lo, size_t hi, size_t max_frames)
+{
+	PackedSlice s{};
+	s.lo = lo, s.hi = hi, s.max_frames = max_frames;
+	// (the capacity, not the count of max_frames frames: a shorter utterance that hits the flush overrun is longer)
+	s.stride = round_up_packed(gvtm_voices_output_capacity(plan, max_frames));
+	const size_t n = hi - lo;
+	s.in_bytes = sizeof(float) * GVTM_N_PARAM * static_cast<size_t>(j.frame_offsets[hi] - j.frame_offsets[lo]);
+	s.rows_bytes = sizeof(float) * GVTM_N_PARAM * n * max_frames;
+	s.audio_bytes = sizeof(float) * n * s.stride;
+	s.out_bytes = (j.pcm ? sizeof(int16_t) : sizeof(float)) * static_cast<size_t>(offsets[hi] - offsets[lo]);
+	return s;
+}
+
+void packed_release(gvtm_plan* plan)
+{
+	for (DeviceBuffer& set : plan->packed.set) set = DeviceBuffer();
+}
+
+// Utterances in the caller's order, in contiguous slices of at most one machine-full and (with a limit) of at most a third
+// of the limit, three staging sets deep:
+//     H2D packed frames(i + 1)  ||  unpack + synthesis + pack(i)  ||  D2H packed output(i - 1)
+// Slice i uses set i % 3; its frames go up once the output of slice i - 3 has left.
+int packed_pipeline(gvtm_plan* plan, const PackedJob& j)
+{
+	std::vector<int64_t> offsets;
+	try {
+		int rc = packed_layout(plan, j.frame_offsets, j.voice_ids, j.batch, offsets);
+		if (rc != GVTM_OK) return rc;
+		const size_t batch = j.batch;
+		const bool voices = j.voice_ids != nullptr;
+		if (batch != 0) {
+			if (j.to_pcm ? !j.pcm : !j.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, j.to_pcm ? "null pcm buffer" : "null audio buffer");
+			if (j.frame_offsets[batch] > 0 && !j.frames) return fail(GVTM_ERR_INVALID_ARGUMENT, "null frames");
+			if (j.capacity < static_cast<size_t>(offsets[batch])) {
+				return fail(GVTM_ERR_INVALID_ARGUMENT, "capacity " + std::to_string(j.capacity) + " below gvtm_packed_sample_offsets (" + std::to_string(offsets[batch]) + " samples)");
+			}
+		}
+		if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+		if (batch == 0) {
+			if (j.sample_offsets_out) j.sample_offsets_out[0] = 0;
+			return GVTM_OK;
+		}
+		if (batch > 0x3fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large");
+
+		// the slices, on the host, before any device work: every slice in the shape of the whole batch, as host_pipeline's
+		const gvtm::LaunchShape shape_all = plan->launch_shape(batch, 0, false, 0, false);
+		const size_t machine = std::max<size_t>(1, static_cast<size_t>(shape_all.per_cu) * static_cast<size_t>(plan->compute_units > 0 ? plan->compute_units : 256));
+		const size_t limit = plan->packed.limit, set_limit = limit / 3;
+		std::vector<PackedSlice> slices;
+		size_t longest = 0;
+		for (size_t lo = 0; lo < batch;) {
+			size_t max_frames = static_cast<size_t>(j.frame_offsets[lo + 1] - j.frame_offsets[lo]);
+			PackedSlice s = packed_slice(plan, j, offsets, lo, lo + 1, max_frames);
+			if (limit && s.bytes() > set_limit) {
+				return fail(GVTM_ERR_OUT_OF_MEMORY, "utterance " + std::to_string(lo) + " needs a staging set of " + std::to_string(s.bytes()) +
+						" bytes, three of them " + std::to_string(3 * s.bytes()) + "; the staging limit is " + std::to_string(limit));
+			}
+			for (size_t hi = lo + 2; hi <= batch && hi - lo <= machine; ++hi) {
+				const size_t f = std::max(max_frames, static_cast<size_t>(j.frame_offsets[hi] - j.frame_offsets[hi - 1]));
+				const PackedSlice wider = packed_slice(plan, j, offsets, lo, hi, f);
+				if (limit && wider.bytes() > set_limit) break;
+				s = wider, max_frames = f;
+			}
+			longest = std::max(longest, s.max_frames);
+			slices.push_back(s);
+			lo = s.hi;
+		}
+		const size_t n_slices = slices.size(), n_sets = std::min<size_t>(3, n_slices);
+		size_t set_bytes = 16, largest = 0;
+		for (const PackedSlice& s : slices) set_bytes = std::max(set_bytes, s.bytes()), largest = std::max(largest, s.hi - s.lo);
+
+		DeviceScope scope(plan->device);
+		hipError_t e = scope.status();
+		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+		auto& sc = plan->packed;
+		// (sets only grow; under a limit none may stay larger than its third)
+		if (limit && std::max({sc.set[0].bytes, sc.set[1].bytes, sc.set[2].bytes}) > set_limit) packed_release(plan);
+		for (size_t q = 0; q < n_sets; ++q) {
+			if ((e = sc.set[q].ensure(set_bytes)) != hipSuccess) return e == hipErrorOutOfMemory ? fail(GVTM_ERR_OUT_OF_MEMORY, "hipMalloc staging set: out of memory") : fail_hip(e, "hipMalloc staging set");
+		}
+		if ((e = sc.frame_offsets.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc frame offsets");
+		if ((e = sc.sample_offsets.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc sample offsets");
+		if ((e = sc.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
+		if ((e = sc.counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
+		if ((e = sc.maxabs.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc maxabs");
+		if (j.pcm && (e = sc.scales.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc scales");
+		if (voices) {
+			if ((e = sc.voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
+			// the grouping's scratch for the largest slice in any shape (rows <= 8): no launch regrows it under a queued kernel
+			const size_t nv = static_cast<size_t>(plan->n_voices());
+			const size_t ints = (largest + 8 + 8 * nv) + (largest + nv) + nv * gvtm::kGroupVoicesThreads;
+			if ((e = sc.groups.ensure(sizeof(int32_t) * ints)) != hipSuccess) return fail_hip(e, "hipMalloc row map");
+		}
+		for (Stream* st : {&plan->h2d_stream, &plan->compute_stream, &plan->copy_stream}) {
+			if (!st->h && (e = hipStreamCreateWithFlags(&st->h, hipStreamNonBlocking)) != hipSuccess) return fail_hip(e, "hipStreamCreate");
+		}
+		const hipStream_t h2d_stream = plan->h2d_stream.h, compute_stream = plan->compute_stream.h, copy_stream = plan->copy_stream.h;
+		while (sc.events.size() < 3 * n_slices) {
+			Event ev;
+			if ((e = hipEventCreateWithFlags(&ev.h, hipEventDisableTiming)) != hipSuccess) return fail_hip(e, "hipEventCreate");
+			sc.events.push_back(std::move(ev));
+		}
+		// the noise table once, for the longest utterance: no slice regrows it in the middle of the pipeline
+		if ((rc = gvtm_plan_reserve(plan, longest)) != GVTM_OK) return rc;
+		if ((e = hipMemcpy(sc.frame_offsets.ptr, j.frame_offsets, sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D frame offsets");
+		if ((e = hipMemcpy(sc.sample_offsets.ptr, offsets.data(), sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D sample offsets");
+		if (voices && (e = hipMemcpy(sc.voice_ids.ptr, j.voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D voice_ids");
+		if (j.sample_offsets_out) std::copy(offsets.begin(), offsets.end(), j.sample_offsets_out);
+		sc.slices = n_slices, sc.largest_slice = largest;
+
+		const int64_t* const d_frame_offsets = static_cast<const int64_t*>(sc.frame_offsets.ptr);
+		const int64_t* const d_sample_offsets = static_cast<const int64_t*>(sc.sample_offsets.ptr);
+		int32_t* const d_frames = static_cast<int32_t*>(sc.frames.ptr);
+		const int32_t* const d_voice_ids = voices ? static_cast<const int32_t*>(sc.voice_ids.ptr) : nullptr;
+		int64_t* const d_counts = static_cast<int64_t*>(sc.counts.ptr);
+		float* const d_maxabs = static_cast<float*>(sc.maxabs.ptr);
+		float* const d_scales = j.pcm ? static_cast<float*>(sc.scales.ptr) : nullptr;
+		const size_t width = j.pcm ? sizeof(int16_t) : sizeof(float);
+		auto drain = [&]() {
+			(void) hipStreamSynchronize(h2d_stream);
+			(void) hipStreamSynchronize(compute_stream);
+			(void) hipStreamSynchronize(copy_stream);
+		};
+		// slice i's packed output leaves: one contiguous range [offset[lo], offset[hi])
+		auto copy_out = [&](size_t i) -> hipError_t {
+			const PackedSlice& s = slices[i];
+			const unsigned char* d_out = static_cast<const unsigned char*>(sc.set[i % 3].ptr) + s.in_bytes + s.rows_bytes + s.audio_bytes;
+			unsigned char* const host = j.pcm ? reinterpret_cast<unsigned char*>(j.pcm) : reinterpret_cast<unsigned char*>(j.audio);
+			hipError_t ce = hipStreamWaitEvent(copy_stream, sc.events[3 * i + 1].h, 0);
+			if (ce == hipSuccess && s.out_bytes) ce = hipMemcpyAsync(host + width * static_cast<size_t>(offsets[s.lo]), d_out, s.out_bytes, hipMemcpyDeviceToHost, copy_stream);
+			if (ce == hipSuccess) ce = hipEventRecord(sc.events[3 * i + 2].h, copy_stream);
+			return ce;
+		};
+		rc = GVTM_OK;
+		for (size_t i = 0; i < n_slices && rc == GVTM_OK; ++i) {
+			const PackedSlice& s = slices[i];
+			const size_t n = s.hi - s.lo;
+			unsigned char* const set = static_cast<unsigned char*>(sc.set[i % 3].ptr);
+			float* const d_in = reinterpret_cast<float*>(set);
+			float* const d_rows = reinterpret_cast<float*>(set + s.in_bytes);
+			float* const d_audio = reinterpret_cast<float*>(set + s.in_bytes + s.rows_bytes);
+			unsigned char* const d_out = set + s.in_bytes + s.rows_bytes + s.audio_bytes;
+			hipEvent_t in_done = sc.events[3 * i].h, out_ready = sc.events[3 * i + 1].h;
+			// (the set is free once slice i - 3's output has left: its D2H was queued two rounds ago)
+			if (i >= 3 && (e = hipStreamWaitEvent(h2d_stream, sc.events[3 * (i - 3) + 2].h, 0)) != hipSuccess) { rc = fail_hip(e, "hipStreamWaitEvent"); break; }
+			if (s.in_bytes && (e = hipMemcpyAsync(d_in, j.frames + GVTM_N_PARAM * static_cast<size_t>(j.frame_offsets[s.lo]), s.in_bytes, hipMemcpyHostToDevice,
+					h2d_stream)) != hipSuccess) { rc = fail_hip(e, "H2D frames"); break; }
+			if ((e = hipEventRecord(in_done, h2d_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
+			if ((e = hipStreamWaitEvent(compute_stream, in_done, 0)) != hipSuccess) { rc = fail_hip(e, "hipStreamWaitEvent"); break; }
+			if ((e = gvtm::launch_unpack_frames(gvtm::UnpackFramesArgs{d_in, d_frame_offsets + s.lo, d_rows, d_frames + s.lo, n, s.max_frames}, compute_stream)) != hipSuccess) {
+				rc = fail_hip(e, "vtm_unpack_frames_kernel launch"); break;
+			}
+			rc = launch_synthesis(plan, LaunchRequest{d_rows, d_frames + s.lo, n, s.max_frames, d_audio, s.stride, d_counts + s.lo, d_maxabs + s.lo, compute_stream,
+					shape_all.forced, voices, voices ? d_voice_ids + s.lo : nullptr, &sc.groups});
+			if (rc != GVTM_OK) break;
+			if ((e = gvtm::launch_pack_samples(gvtm::PackSamplesArgs{d_audio, d_counts + s.lo, d_maxabs + s.lo, d_sample_offsets + s.lo,
+					j.pcm ? nullptr : reinterpret_cast<float*>(d_out), j.pcm ? reinterpret_cast<int16_t*>(d_out) : nullptr, d_scales ? d_scales + s.lo : nullptr, n, s.stride},
+					compute_stream)) != hipSuccess) { rc = fail_hip(e, "vtm_pack_samples_kernel launch"); break; }
+			if ((e = hipEventRecord(out_ready, compute_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
+			// (behind the next slice's kernels: with pageable host memory a device-to-host copy blocks the calling thread)
+			if (i >= 1 && (e = copy_out(i - 1)) != hipSuccess) { rc = fail_hip(e, "D2H samples"); break; }
+		}
+		if (rc == GVTM_OK && (e = copy_out(n_slices - 1)) != hipSuccess) rc = fail_hip(e, "D2H samples");
+		if (rc != GVTM_OK) {
+			drain();
+			return rc;
+		}
+		if ((e = hipStreamSynchronize(copy_stream)) != hipSuccess) { drain(); return fail_hip(e, "vtm_synth_kernel execution / D2H samples"); }
+		if ((e = hipStreamSynchronize(compute_stream)) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");
+		if ((e = hipStreamSynchronize(h2d_stream)) != hipSuccess) return fail_hip(e, "H2D frames");
+		if (j.out_counts && (e = hipMemcpy(j.out_counts, d_counts, sizeof(int64_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H counts");
+		if (j.maxabs && (e = hipMemcpy(j.maxabs, d_maxabs, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H maxabs");
+		if (j.scales && (e = hipMemcpy(j.scales, d_scales, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H scales");
+		return GVTM_OK;
+	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
+}
+
+} // namespace
+
+extern "C" {
+
+size_t gvtm_packed_sample_offsets(const gvtm_plan* plan, const int64_t* frame_offsets, const int32_t* voice_ids, size_t batch, int64_t* sample_offsets_out)
+{
+	try {
+		std::vector<int64_t> offsets;
+		if (packed_layout(plan, frame_offsets, voice_ids, batch, offsets) != GVTM_OK) return static_cast<size_t>(-1);
+		if (sample_offsets_out) std::copy(offsets.begin(), offsets.end(), sample_offsets_out);
+		return static_cast<size_t>(offsets[batch]);
+	} catch (const std::bad_alloc&) {
+		fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+		return static_cast<size_t>(-1);
+	}
+}
+
+int gvtm_synthesize_packed_host(gvtm_plan* plan, const float* frames, const int64_t* frame_offsets, const int32_t* voice_ids, size_t batch,
+		float* audio, size_t audio_capacity, int64_t* sample_offsets_out, int64_t* out_counts, float* maxabs)
+{
+	return packed_pipeline(plan, PackedJob{frames, frame_offsets, voice_ids, batch, audio, nullptr, false, audio_capacity, sample_offsets_out, out_counts, maxabs, nullptr});
+}
+
+int gvtm_synthesize_packed_host_pcm16(gvtm_plan* plan, const float* frames, const int64_t* frame_offsets, const int32_t* voice_ids, size_t batch,
+		int16_t* pcm, size_t pcm_capacity, int64_t* sample_offsets_out, int64_t* out_counts, float* maxabs, float* scales)
+{
+	return packed_pipeline(plan, PackedJob{frames, frame_offsets, voice_ids, batch, nullptr, pcm, true, pcm_capacity, sample_offsets_out, out_counts, maxabs, scales});
+}
+
+int gvtm_plan_set_staging_limit(gvtm_plan* plan, size_t bytes)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	plan->packed.limit = bytes;
+	// what an earlier call holds beyond the new limit goes now (every packed call drains its streams before it returns)
+	if (bytes && plan->device != GVTM_DEVICE_NONE && plan->packed.staging_bytes() > bytes) {
+		DeviceScope scope(plan->device);
+		if (scope.status() != hipSuccess) return fail_hip(scope.status(), "hipSetDevice");
+		packed_release(plan);
+	}
+	return GVTM_OK;
+}
+
+int gvtm_plan_packed_stats(const gvtm_plan* plan, gvtm_packed_stats* out)
+{
+	if (!plan || !out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or out");
+	out->staging_bytes = plan->packed.staging_bytes();
+	out->limit = plan->packed.limit;
+	out->slices = plan->packed.slices;
+	out->largest_slice = plan->packed.largest_slice;
+	return GVTM_OK;
+}
+
+int gvtm_plan_reserve(gvtm_plan* plan, size_t max_frames)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	// (the plans whose one-shot launches read the table: launch_synthesis)
+	if (plan->designs[0].model5 || !GVTM_NOISE_TABLE || plan->precision != GVTM_PRECISION_F32) return GVTM_OK;
+	unsigned max_steps = 0;
+	for (int v = 0; v < plan->n_voices(); ++v) max_steps = std::max(max_steps, plan->designs[v].k.control_steps);
+	if (static_cast<unsigned long long>(max_frames) * max_steps + 4096ull >= (1ull << 31)) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
+	}
+	try {
+		DeviceScope scope(plan->device);
+		if (scope.status() != hipSuccess) return fail_hip(scope.status(), "hipSetDevice");
+		gvtm::SynthArgs unused;
+		return use_noise_table(plan, max_frames * static_cast<size_t>(max_steps), unused);
+	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
 }
 
 } // extern "C"

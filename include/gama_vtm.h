@@ -250,7 +250,9 @@ size_t gvtm_output_capacity(const gvtm_plan* plan, size_t max_frames);
  *   d_maxabs       [batch] float32 max|x| per utterance, may be NULL
  *   hip_stream     hipStream_t (NULL = default stream); the call only enqueues work
  *                  (GVTM_PRECISION_F32 plans: the first call, and a later one with more frames than any before, also builds
- *                  and uploads the plan's noise-sample table for max_frames frames, 4 bytes per internal step, synchronously)
+ *                  and uploads the plan's noise-sample table for max_frames frames, 4 bytes per internal step, synchronously;
+ *                  gvtm_plan_reserve(plan, max_frames) does that ahead of time, and every later call of up to that many
+ *                  frames is then really enqueue-only)
  */
 int gvtm_synthesize_batch_device(gvtm_plan* plan, const float* d_params, const int32_t* d_frame_counts,
 		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
@@ -341,6 +343,78 @@ int gvtm_synthesize_voices_host(gvtm_plan* plan, const float* params, const int3
 /* As gvtm_synthesize_batch_host_pcm16 (scales = 0 for a failed utterance). */
 int gvtm_synthesize_voices_host_pcm16(gvtm_plan* plan, const float* params, const int32_t* frame_counts, const int32_t* voice_ids,
 		size_t max_frames, size_t batch, int16_t* pcm, size_t pcm_stride, int64_t* out_counts, float* maxabs, float* scales);
+
+/* ---------------------------------------------------------------------------------------------
+ * Ragged batches: packed in, packed out.
+ *
+ * Real batches are ragged (an utterance of 1 s next to one of 30 s).  The entries above take and return rectangles, so
+ * the padding crosses PCIe and is staged on the device with everything else.  The packed entries take the utterances'
+ * frames back to back and return their samples back to back, both described by offset tables, and what they stage on the
+ * device is bounded by a slice of the batch, not by the batch.
+ */
+#define GVTM_PACKED_ALIGN 8   /* samples: every utterance starts at a multiple of it in the packed output */
+
+/* Host-only, works on GVTM_DEVICE_NONE plans.  frame_offsets [batch+1] int64, non-decreasing from 0: utterance b owns
+ * the frames [frame_offsets[b], frame_offsets[b+1]).  voice_ids [batch] or NULL (a one-voice plan; a plan of several voices
+ * requires them).  Writes sample_offsets_out [batch+1] (may be NULL) and returns sample_offsets_out[batch], the
+ * capacity (in samples) the output buffer needs; (size_t)-1 on a bad argument (the tables are checked as the synthesis
+ * entries below check them).
+ *   count[b]    = gvtm_voice_output_count(plan, voice b, frames b)      (exact, flush overrun included)
+ *   offset[0]   = 0,  offset[b+1] = round_up(offset[b] + count[b], GVTM_PACKED_ALIGN) */
+size_t gvtm_packed_sample_offsets(const gvtm_plan* plan, const int64_t* frame_offsets, const int32_t* voice_ids,
+		size_t batch, int64_t* sample_offsets_out);
+
+/* The packed form of gvtm_synthesize_voices_host (voice_ids given) resp. gvtm_synthesize_batch_host (voice_ids NULL, a
+ * one-voice plan: the single-voice launch, so a gvtm_plan_create_model5_float plan takes NULL ids only).
+ *   frames             [frame_offsets[batch]][16] float32: the utterances' frames back to back
+ *   audio              [audio_capacity] float32, audio_capacity >= gvtm_packed_sample_offsets(...): utterance b's unscaled
+ *                      samples occupy [offset[b], offset[b] + out_counts[b]); the gap up to offset[b+1] is written as
+ *                      zeros, so the whole of [0, offset[batch]) is defined and nothing beyond it is touched
+ *   sample_offsets_out [batch+1] the layout (may be NULL), out_counts [batch] (= the layout's counts), maxabs [batch]: may
+ *                      be NULL
+ * Samples, counts and peaks are bit for bit those the padded entry returns for the same utterance, in every precision,
+ * for the models 0 to 4 and both classes of model 5, one voice or several.  An utterance of 0 frames is valid (the
+ * converter's flush still yields samples).  Synchronous.
+ *
+ * All the tables are host memory, so a bad one refuses the whole call with GVTM_ERR_INVALID_ARGUMENT before any device
+ * work: a null table or buffer where one is due; offsets that do not start at 0 or that decrease; a voice id outside
+ * [0, n_voices) (the message names the first such utterance); NULL ids on a plan of several voices; an utterance whose
+ * frames x control_steps does not fit the 31-bit step counter; a capacity below gvtm_packed_sample_offsets.  After these
+ * a design-only plan returns GVTM_ERR_NO_DEVICE; batch == 0 returns GVTM_OK.
+ *
+ * Slices.  The utterances go in the caller's order, in contiguous slices, three staging sets deep on the plan's three
+ * streams:   H2D packed frames(i+1) || unpack + synthesis + pack(i) || D2H packed output(i-1),   each D2H one contiguous
+ * range [offset[lo], offset[hi]).  A slice of n utterances, the longest of F frames, holds in its set its packed frames,
+ * its padded frames [n][F][16], its padded float samples [n][S] with S = gvtm_voices_output_capacity(plan, F) rounded up
+ * to 8, and its packed output:
+ *   set_bytes = 64 * n * F + 64 * frames_of_slice + 4 * n * S + w * aligned_samples_of_slice        (w = 4, int16: 2)
+ * (aligned_samples_of_slice = offset[hi] - offset[lo]; the small per-utterance arrays -- offsets, counts, peaks, ids --
+ * are the batch's and are not counted).  A slice is closed when the next utterance would exceed one machine-full
+ * (utterances per compute unit x compute units) or, with a staging limit, when set_bytes would exceed limit / 3.  An
+ * utterance that does not fit a set on its own refuses the call with GVTM_ERR_OUT_OF_MEMORY before any device work (the
+ * message gives the bytes it needs).  The staging is the packed entries' own: they may not overlap each other on one
+ * plan, the other entries are not affected.  Float plans: gvtm_plan_reserve runs once, for the longest utterance, before
+ * the first slice. */
+int gvtm_synthesize_packed_host(gvtm_plan* plan, const float* frames, const int64_t* frame_offsets, const int32_t* voice_ids,
+		size_t batch, float* audio, size_t audio_capacity, int64_t* sample_offsets_out, int64_t* out_counts, float* maxabs);
+/* The same ending as gvtm_synthesize_batch_host_pcm16 ends: int16 samples scaled by scales[b] = 0.95 / max|x[b]| (0 for
+ * silence) and rounded, bit for bit the padded entry's; the gaps are zeros.  scales [batch] may be NULL. */
+int gvtm_synthesize_packed_host_pcm16(gvtm_plan* plan, const float* frames, const int64_t* frame_offsets, const int32_t* voice_ids,
+		size_t batch, int16_t* pcm, size_t pcm_capacity, int64_t* sample_offsets_out, int64_t* out_counts, float* maxabs,
+		float* scales);
+
+/* Upper bound, in bytes, on the three staging sets of the packed entries; 0 = none (the default).  Works on design-only
+ * plans (it is kept).  Staging an earlier call left beyond the new limit is freed. */
+int gvtm_plan_set_staging_limit(gvtm_plan* plan, size_t bytes);
+/* staging_bytes: device bytes the three sets hold now (they stay allocated between calls and only grow; with a limit
+ * never more than it); slices and largest_slice (utterances): of the last packed call that ran. */
+typedef struct gvtm_packed_stats { size_t staging_bytes, limit, slices, largest_slice; } gvtm_packed_stats;
+int gvtm_plan_packed_stats(const gvtm_plan* plan, gvtm_packed_stats* out);
+/* Builds and uploads, synchronously, what the plan's launches of up to max_frames frames would otherwise build on first
+ * use: the noise-sample table of a GVTM_PRECISION_F32 plan of the models 0 to 4.  GVTM_OK and nothing done for plans that
+ * keep no table; GVTM_ERR_NO_DEVICE on a design-only plan.  Like the growth it replaces, it must not run while another
+ * thread launches on the plan. */
+int gvtm_plan_reserve(gvtm_plan* plan, size_t max_frames);
 
 /* Page-locked host memory for the buffers of the host entries (hipHostMalloc, portable across devices), for callers
  * that do not link the HIP runtime themselves.  gvtm_host_free(NULL) is a no-op. */
