@@ -613,7 +613,8 @@ int gvtm_debug_dpp_selftest(gvtm_plan* plan, int* out)
 
 /* Test hook: the short elementary functions of csrc/vtm_math.hpp evaluated on the host
  * (kind 0 = 2^x, 1 = 10^x, 2 = cos, 3 = tan; 4 = powf(2, x), 5 = powf(10, x), 6 = cosf, 7 = tanf of the
- * all-float path, 8 = sinf of the float model 5's sine waveform, arguments and results carried as doubles). */
+ * all-float path, 8 = sinf of the float model 5's sine waveform, 9 = tanf in the form with its library fallback in line,
+ * arguments and results carried as doubles). */
 int gvtm_debug_short_math(int kind, const double* x, size_t n, double* out)
 {
 	if (!x || !out) return GVTM_ERR_INVALID_ARGUMENT;
@@ -628,6 +629,7 @@ int gvtm_debug_short_math(int kind, const double* x, size_t n, double* out)
 		case 6: out[i] = gvtm::vmath::cosf_glibc(static_cast<float>(x[i])); break;
 		case 7: out[i] = gvtm::vmath::tanf_glibc(static_cast<float>(x[i])); break;
 		case 8: out[i] = gvtm::vmath::sinf_glibc(static_cast<float>(x[i])); break;
+		case 9: out[i] = gvtm::vmath::tanf_glibc<true>(static_cast<float>(x[i])); break;
 		default: return GVTM_ERR_INVALID_ARGUMENT;
 		}
 	}
@@ -635,10 +637,10 @@ int gvtm_debug_short_math(int kind, const double* x, size_t n, double* out)
 }
 
 /* Test hook: Util::frequency / Util::amplitude60dB / tan / cos of the all-float path (kind 0..3), its scaling-free
- * division (4) and the float model 5's sin (5) evaluated by a kernel on the plan's device, host arrays in and out. */
+ * division (4), the float model 5's sin (5) and tan / cos with their library fallbacks in line (6, 7) evaluated by a kernel on the plan's device, host arrays in and out. */
 int gvtm_debug_device_float_math(gvtm_plan* plan, int kind, const float* x, size_t n, float* out)
 {
-	if (!plan || !x || !out || kind < 0 || kind > 5) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (!plan || !x || !out || kind < 0 || kind > 7) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
 	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();

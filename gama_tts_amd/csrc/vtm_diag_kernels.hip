@@ -42,7 +42,8 @@ hipError_t launch_dpp_selftest(int* d_out, hipStream_t stream)
 
 // Test hook: the all-float path's per-step conversions evaluated ON THE DEVICE
 // (kind 0 = Util::frequency, 1 = Util::amplitude60dB, 2 = tanf stand-in, 3 = cosf stand-in, 4 = the scaling-free division,
-// 5 = sinf stand-in of the float model 5's sine waveform)
+// 5 = sinf stand-in of the float model 5's sine waveform, 6 / 7 = 2 / 3 in the form with the library fallbacks in line,
+// as the four-row kernel at SectionDelay 1 instantiates them)
 __global__ void float_math_probe_kernel(int kind, const float* x, size_t n, float* out)
 {
 	const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -56,6 +57,8 @@ __global__ void float_math_probe_kernel(int kind, const float* x, size_t n, floa
 	case 3: r = cos_dev(v); break;
 	case 4: r = fdiv_n(v, x[i ^ 1]); break; // (n even)
 	case 5: r = vmath::sinf_glibc(v); break;
+	case 6: r = tan_dev<true>(v); break;
+	case 7: r = cos_dev<true>(v); break;
 	}
 	out[i] = r;
 }

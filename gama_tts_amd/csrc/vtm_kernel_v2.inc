@@ -920,18 +920,20 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			const CT complement = fpos - ipart;
 			const CT remainder = CT(1.0) - complement;
 			// taps[ipart] = remainder * amp, taps[ipart + 1] = complement * amp, the others 0 (a share that would go to a
-			// ninth section is dropped): the pre-tube filter wavefront hands each section its share
+			// ninth section is dropped): the pre-tube filter wavefront hands each section its share.  The reference writes
+			// the second share only from inside the i == ipart branch of its loop over sections 0..7, so for ipart == -1
+			// (a position in (-2, -1)) section 0 gets nothing either.
 			if constexpr (kFrCompact) {
 				fr[kFrTapA] = remainder * amp;
 				fr[kFrTapB] = complement * amp;
 				fr[kFrZero] = CT(0.0);
-				*reinterpret_cast<int*>(fr + kFrFirst) = ipart;
+				*reinterpret_cast<int*>(fr + kFrFirst) = ipart == -1 ? 8 : ipart; // (8: every section's distance is out of 0..1)
 			} else {
 #pragma unroll
 				for (int q = 0; q < 8; ++q) {
 					CT t = CT(0.0);
 					if (q == ipart) t = remainder * amp;
-					else if (q == ipart + 1) t = complement * amp;
+					else if (q >= 1 && q == ipart + 1) t = complement * amp;
 					fr[q] = t;
 				}
 				fr[kFr - 1] = CT(0.0); // the zero tap read by sections without frication injection

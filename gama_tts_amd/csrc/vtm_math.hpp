@@ -216,11 +216,20 @@ GVTM_HD float powf_base10(float y)
 // (BandpassFilter::update calls std::cos / std::tan on floats once per step; a last-bit difference in
 // a coefficient perturbs the frication noise, which in quiet passages is all there is).
 //   cosf: sysdeps/ieee754/flt-32/s_cosf.c, s_sincosf.h — double arithmetic, fast quadrant reduction,
-//         degree-8 / degree-7 polynomials;
+//         degree-8 / degree-7 polynomials.  x86-64 glibc dispatches cosf to its FMA build, which fuses the a + b * c of
+//         the reduction and the polynomials; here they are unfused (fp contract(off)), and the float rounding absorbs the
+//         difference on every float below 17.27 but not on eleven floats of [17.27, 108.5].  The restatement therefore
+//         takes |y| < 16 only.  (Spelled with std::fma it equals libm on all of (-120, 120), but the flagship kernel
+//         measured 1.3 % slower with it: profiles/domain_parity_ab.md.)
 //   tanf: s_tanf.c, k_tanf.c, e_rem_pio2f.c — the fdlibm float kernel (odd polynomial to x^27, the
-//         pi/4 - x reflection above 0.6744, -1/tan for the second octant).
-// Compared with this machine's libm over every float of the ranges in use (tests/test_capi_cpu.py):
-// cos on [0, 3.2], tan on [0, 1.38] (bandwidth < 0.44 fs) are bit-identical.
+//         pi/4 - x reflection above 0.6744, -1/tan for the second octant), float arithmetic, nothing fused; it works on
+//         |x| and restores the sign, and so does the restatement.
+// PINNED RANGES, compared with this machine's libm over EVERY float in them, zeros and subnormals included
+// (tests/test_capi_cpu.py; the device's evaluation on samples of them, tests/test_gpu_parity_f32.py):
+//   cos on (-16, 16) and tan on [-1.38, 1.38] (|bandwidth| <= 0.44 fs) are bit-identical.
+// Outside them the library answers ((float)cos((double)y), (float)tan((double)x)): last-bit differences from cosf / tanf
+// are expected there (tan: 4 154 of the 1 600 517 floats of [1.38, pi/2]; raising the bound to pi/2 on the restated kernel
+// leaves 256 differing floats from 1.38733172 on, hence 1.38).  glibc's large-argument reduction is not restated.
 GVTM_HD uint32_t float_bits(float f)
 {
 	uint32_t u;
@@ -241,7 +250,7 @@ GVTM_HD float cosf_glibc(float y)
 #pragma clang fp contract(off)
 #endif
 	const uint32_t top = (float_bits(y) >> 20) & 0x7ffu;
-	if (!(top < ((float_bits(120.0f) >> 20) & 0x7ffu))) return FAR_INLINE ? static_cast<float>(std::cos(static_cast<double>(y))) : cosf_far(y);
+	if (!(top < ((float_bits(16.0f) >> 20) & 0x7ffu))) return FAR_INLINE ? static_cast<float>(std::cos(static_cast<double>(y))) : cosf_far(y);
 	constexpr double hpi_inv = 0x1.45F306DC9C883p+23, hpi = 0x1.921FB54442D18p0;
 	constexpr double c0 = 0x1p0, c1 = -0x1.ffffffd0c621cp-2, c2 = 0x1.55553e1068f19p-5, c3 = -0x1.6c087e89a359dp-10,
 			c4 = 0x1.99343027bf8c3p-16;
@@ -377,15 +386,13 @@ GVTM_HD float tanf_kernel_glibc(float x, float y, int iy)
 	return t + a * (s + t * v);
 }
 
-template <bool FAR_INLINE = false>
-GVTM_HD float tanf_glibc(float x)
+// tanf for 0 <= x <= 1.38, ix = its bits
+GVTM_HD float tanf_glibc_first(float x, uint32_t ix)
 {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-	if (!(x >= 0.0f && x <= 1.38f)) return FAR_INLINE ? static_cast<float>(std::tan(static_cast<double>(x))) : tanf_far(x);
-	const uint32_t ix = float_bits(x);
-	if (ix <= 0x3f490fdau) return tanf_kernel_glibc(x, 0.0f, 1);
+	if (static_cast<int32_t>(ix) <= 0x3f490fda) return tanf_kernel_glibc(x, 0.0f, 1);
 	// __ieee754_rem_pio2f for pi/4 < x < 3pi/4: x - pi/2 in two floats
 	constexpr float pio2_1 = 1.5707855225e+00f, pio2_1t = 1.0804334124e-05f, pio2_2 = 1.0804273188e-05f,
 			pio2_2t = 6.0770999344e-11f;
@@ -401,6 +408,15 @@ GVTM_HD float tanf_glibc(float x)
 	// y0 < 0 here (x < pi/2): the kernel works on |y0| and the sign is restored by symmetry
 	const float m = tanf_kernel_glibc(-y0, -y1, -1);
 	return -m;
+}
+
+template <bool FAR_INLINE = false>
+GVTM_HD float tanf_glibc(float x)
+{
+	// tanf is odd bit for bit: fold the sign away and put it back
+	const uint32_t ix = float_bits(x), ax = ix & 0x7fffffffu;
+	if (!(ax <= 0x3fb0a3d7u)) return FAR_INLINE ? static_cast<float>(std::tan(static_cast<double>(x))) : tanf_far(x);
+	return bits_float(float_bits(tanf_glibc_first(bits_float(ax), ax)) ^ (ix & 0x80000000u));
 }
 
 } // namespace vmath

@@ -223,28 +223,41 @@ def test_powf_restatement_is_bit_identical_to_libm():
 
 
 def test_cosf_tanf_restatement_is_bit_identical_to_libm():
-    """glibc's cosf / tanf as the all-float band-pass design needs them (csrc/vtm_math.hpp): every float of
-    cos on [2^-13, 3.2] and tan on [2^-14, 1.38] (bandwidth up to 0.44 of the internal rate)."""
+    """glibc's cosf / tanf as the all-float band-pass design needs them (csrc/vtm_math.hpp): EVERY float of the ranges the
+    restatements take on themselves, cos on (-16, 16) and tan on [-1.38, 1.38] (bandwidth up to 0.44 of the internal rate),
+    zeros and subnormals included.  Outside them the library fallback answers, to the last bit or two."""
+    from concurrent.futures import ThreadPoolExecutor
     lib = g.load_library(diagnostics=True)
     ol = oracle.lib()
     ol.vtmo_libm_tanf_cosf.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    sign = np.uint32(0x80000000)
 
-    def check(kind, which, lo, hi):
-        a = np.array([lo, hi], dtype=np.float32).view(np.uint32)
-        step = 1 << 22
-        for start in range(int(a[0]), int(a[1]) + 1, step):
-            x = np.arange(start, min(start + step, int(a[1]) + 1), dtype=np.uint32).view(np.float32)
+    def differing(job):
+        kind, which, start, stop = job
+        n = 0
+        for negative in (False, True):
+            bits = np.arange(start, stop, dtype=np.uint32)
+            x = (bits | sign if negative else bits).view(np.float32)
             ref = np.empty_like(x)
             ol.vtmo_libm_tanf_cosf(which, x.ctypes.data, x.size, ref.ctypes.data)
             xd = x.astype(np.float64)
             out = np.empty_like(xd)
             assert lib.gvtm_debug_short_math(kind, xd.ctypes.data, xd.size, out.ctypes.data) == 0
-            assert np.array_equal(out.astype(np.float32).view(np.uint32), ref.view(np.uint32)), (kind, start)
+            n += int((out.astype(np.float32).view(np.uint32) != ref.view(np.uint32)).sum())
+        return n
 
-    check(6, 1, 2.0 ** -13, 3.2)
-    check(7, 0, 2.0 ** -14, 1.38)
-    for kind, which in ((6, 1), (7, 0)):  # zero, and arguments outside the restated ranges (library path)
-        x = np.array([0.0, 1e-30, 5.0, 100.0, 1000.0, -0.5], dtype=np.float32)
+    def scan(kind, which, stop):
+        """Floats of bit patterns [0, stop) and their negatives -> how many differ from libm (the calls release the GIL)."""
+        step = 1 << 22
+        with ThreadPoolExecutor(8) as ex:
+            return sum(ex.map(differing, [(kind, which, a, min(a + step, stop)) for a in range(0, stop, step)]))
+
+    bits_of = lambda v: int(np.array([v], dtype=np.float32).view(np.uint32)[0])  # noqa: E731
+    assert scan(6, 1, bits_of(16.0)) == 0           # |y| < 16
+    assert scan(7, 0, bits_of(1.38) + 1) == 0       # |x| <= 1.38f
+    assert scan(9, 0, bits_of(1.38) + 1) == 0       # ... and in the form the four-row kernel at SectionDelay 1 inlines
+    for kind, which in ((6, 1), (7, 0)):  # arguments outside the restated ranges (library path)
+        x = np.array([16.0, -16.0, 17.2787, 100.0, 120.0, 1000.0, -1000.0, 1.39, -1.39, 1.5, -1.57], dtype=np.float32)
         ref = np.empty_like(x)
         ol.vtmo_libm_tanf_cosf(which, x.ctypes.data, x.size, ref.ctypes.data)
         xd = x.astype(np.float64)

@@ -70,7 +70,9 @@ def edge_track(frames=48, seed=0):
     """Frames that sit ON the special cases of the per-step conversions: volumes 0 / 60 dB (Util::amplitude60dB's two
     shortcuts), frication position 0 and 7 (first / last injection section, the dropped right share), radii at and below
     the 0.01 floor, velum 0 (nasal junction coefficient -1), pitch at both ends, bandwidth / centre frequency extremes;
-    held for two frames each so that the interpolation passes THROUGH the values as well."""
+    held for two frames each so that the interpolation passes THROUGH the values as well.  Everything here stays inside
+    the editor's ranges (_RANGES) or on their ends; values OUTSIDE them -- negative positions, volumes above 60 dB,
+    bandwidths up to half the internal rate ... -- are the table of domain_cases.py."""
     base = const_track(1)[0]
     rows = []
     specials = [
