@@ -50,6 +50,7 @@ struct DeviceBuffer {
 	{
 		if (ptr) (void) hipFree(ptr);
 	}
+	template <typename T> T* as() const { return static_cast<T*>(ptr); }
 	hipError_t ensure(size_t need)
 	{
 		if (need <= bytes) return hipSuccess;
@@ -130,26 +131,25 @@ struct gvtm_plan {
 	size_t noise_len = 0;
 	std::vector<DeviceBuffer> noise_retired;
 	// scratch, one set per user, so that no call overwrites what another call's queued kernels still read:
-	// the host entries' staging and grouping (each call drains its own streams before it returns) ...
+	// the host entries' (one slice pipeline under two layouts, run_slices; each call drains its streams before it returns, so
+	// the layouts never use the set at once): per utterance of the whole batch the frame counts, voice ids, out_counts, maxabs,
+	// scales and the grouping's scratch; padded, the whole batch's staging; packed, two offset tables and three staging sets,
+	// each one allocation that a slice carves into its packed frames, padded frames, padded samples and packed output
+	// (gama_vtm.h: set_bytes), so that what is held is bounded by the slices and not by the batch ...
 	struct {
-		DeviceBuffer params, frames, audio, counts, maxabs, pcm, scales, voice_ids, groups;
+		DeviceBuffer frames, voice_ids, counts, maxabs, scales, groups;
+		DeviceBuffer params, audio, pcm;               // padded
+		DeviceBuffer set[3], frame_offsets, sample_offsets; // packed
+		size_t limit = 0;                       // gvtm_plan_set_staging_limit; 0: none
+		size_t slices = 0, largest_slice = 0;   // of the last packed call that ran
+		size_t staging_bytes() const { return set[0].bytes + set[1].bytes + set[2].bytes; }
+		void release_sets() { for (DeviceBuffer& s : set) s = DeviceBuffer(); }
 	} host;
 	// ... and the enqueue-only entries' (gvtm_synthesize_events_device's frames and frame counts, the grouping of
 	// gvtm_synthesize_voices_device): calls to those on one plan must be ordered on one stream
 	struct {
 		DeviceBuffer params, frames, groups;
 	} async;
-	// ... and the packed host entries' (gvtm_synthesize_packed_host*): three staging sets, each one allocation that a slice
-	// carves into its packed frames, padded frames, padded samples and packed output (gama_vtm.h: set_bytes), so that what is
-	// held is bounded by the slices and not by the batch; and the small per-utterance arrays of the whole batch
-	struct {
-		DeviceBuffer set[3];
-		DeviceBuffer frame_offsets, sample_offsets, frames, voice_ids, counts, maxabs, scales, groups;
-		size_t limit = 0;                       // gvtm_plan_set_staging_limit; 0: none
-		size_t slices = 0, largest_slice = 0;   // of the last call that ran
-		std::vector<Event> events;              // three per slice: frames arrived, packed output ready, output copied
-		size_t staging_bytes() const { return set[0].bytes + set[1].bytes + set[2].bytes; }
-	} packed;
 	// gvtm_plan_set_voice_tracks: one designed track configuration per voice, and (device plans) the table the voice
 	// variant of the tracks kernel reads; empty until the first call that succeeds
 	std::vector<gvtm::TrackConstants> voice_tracks;
@@ -163,7 +163,7 @@ struct gvtm_plan {
 	std::vector<EventPair> pool;
 	// host-buffer entries: frames in on one stream, kernels on a second, samples out on a third (created on first use)
 	Stream h2d_stream, compute_stream, copy_stream;
-	std::vector<Event> slice_done; // two per slice: frames arrived, samples ready
+	std::vector<Event> slice_events; // three per slice: input arrived, output ready, output copied (recorded where sets rotate)
 
 	int n_voices() const { return static_cast<int>(designs.size()); }
 	// the shape of a launch of `batch` utterances (vtm_kernels.hpp: synth_launch_shape; forced_rows 0: the plan's own)
@@ -336,6 +336,26 @@ int refuse_voices(const gvtm_plan* plan, const char* entry)
 {
 	return fail(GVTM_ERR_INVALID_ARGUMENT, std::string(entry) + ": the plan has " + std::to_string(plan->n_voices()) +
 			" voices; use gvtm_synthesize_voices_* resp. gvtm_synthesize_events_voices_device (one voice id per utterance)");
+}
+
+// Everything that launches a kernel, on a design-only plan
+int refuse_design_only()
+{
+	return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+}
+
+// the most steps per frame among the plan's voices: what a launch is judged by, and what the noise table is as long as
+unsigned max_control_steps(const gvtm_plan* plan)
+{
+	unsigned max_steps = 0;
+	for (int v = 0; v < plan->n_voices(); ++v) max_steps = std::max(max_steps, plan->designs[v].k.control_steps);
+	return max_steps;
+}
+
+// do utterances of `frames` frames fit the kernels' 31-bit step counter?
+bool fits_step_counter(const gvtm_plan* plan, unsigned long long frames)
+{
+	return frames < (1ull << 31) && frames * max_control_steps(plan) + 4096ull < (1ull << 31);
 }
 
 // does the track configuration's control period agree with the plan's control rate?
@@ -995,18 +1015,14 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
 	// (the single-voice entries would not know which voice to synthesize; the voices entries take a one-voice plan too)
 	if (!r.voices && plan->n_voices() > 1) return refuse_voices(plan, r.sl ? "gvtm_stream_*" : "gvtm_synthesize_batch_device");
-	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 	if (r.batch == 0) return GVTM_OK;
 	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
 	if (r.voices && !r.voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
 	if (r.max_frames > 0 && !r.params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	// (several voices: the row map's int32 slots also count up to n_voices partly empty workgroups)
 	if (r.batch > (r.voices ? 0x3fffffffu : 0x7fffffffu)) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
-	unsigned max_steps = 0;
-	for (int v = 0; v < plan->n_voices(); ++v) max_steps = std::max(max_steps, plan->designs[v].k.control_steps);
-	if (static_cast<unsigned long long>(r.max_frames) * max_steps + 4096ull >= (1ull << 31)) {
-		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
-	}
+	if (!fits_step_counter(plan, r.max_frames)) return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
 	// (a stream checks its stride against what each call produces: stream_launch)
 	if (!r.sl) {
 		const int rc = check_audio_stride(plan, r.audio_stride, r.max_frames, r.voices);
@@ -1043,7 +1059,7 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (!model5 && !r.sl && GVTM_NOISE_TABLE && plan->precision == GVTM_PRECISION_F32) {
 		// one-shot launches read the noise samples from the plan's table, one for every voice (every utterance starts from
 		// the same seed), as long as the voice with the most steps needs (streams generate them: their length has no bound)
-		const int rc = use_noise_table(plan, r.max_frames * static_cast<size_t>(max_steps), args);
+		const int rc = use_noise_table(plan, r.max_frames * static_cast<size_t>(max_control_steps(plan)), args);
 		if (rc != GVTM_OK) return rc;
 	}
 	return timed_launch(plan, stream, r.voices ? "vtm_synth_kernel launch (voices)" : "vtm_synth_kernel launch", [&] {
@@ -1088,7 +1104,7 @@ int gvtm_synthesize_events_device(gvtm_plan* plan, const gvtm_track_config* conf
 {
 	if (!plan || !config) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or config");
 	if (plan->n_voices() > 1) return refuse_voices(plan, "gvtm_synthesize_events_device");
-	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 	if (batch == 0) return GVTM_OK;
 	if (!d_events || !d_event_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events or event_offsets");
 	gvtm::TrackConstants tk{};
@@ -1183,7 +1199,7 @@ int check_voice_tracks_plan(const gvtm_plan* plan, const char* entry)
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
 	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, std::string(entry) + ": the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
-	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 	return GVTM_OK;
 }
 
@@ -1276,26 +1292,104 @@ struct HostJob {
 	float* scales;     // pcm only: the scale applied to each utterance, or null
 };
 
-// A batch of at least two machine-fulls goes in slices of one machine-full each (rows x compute units utterances: every
-// compute unit busy, in the shape the whole batch would use), three streams deep:
-//     H2D frames(i + 1)  ||  kernel(i) [+ scale -> int16(i)]  ||  D2H samples(i - 1)
-// With page-locked host buffers (gvtm_host_alloc) all three really overlap; with pageable ones the runtime stages the
-// copies itself and the call still returns the same bytes.
+// The shape of a whole batch of the host entries (every slice is launched in it), and in `machine` how many utterances fill
+// the machine once in it (the rows the batch size picks: a launch still gives way to fewer where the LDS does not hold them)
+gvtm::LaunchShape whole_batch_shape(const gvtm_plan* plan, size_t batch, size_t& machine)
+{
+	const gvtm::LaunchShape shape = plan->launch_shape(batch, 0, false, 0, false);
+	machine = std::max<size_t>(1, static_cast<size_t>(shape.per_cu) * static_cast<size_t>(plan->compute_units > 0 ? plan->compute_units : 256));
+	return shape;
+}
+
+// the grouping's scratch for a slice of `largest` utterances in any shape (rows <= 8), taken before the first slice: no
+// launch regrows it under a queued kernel
+hipError_t reserve_host_groups(gvtm_plan* plan, size_t largest)
+{
+	const size_t nv = static_cast<size_t>(plan->n_voices());
+	return plan->host.groups.ensure(sizeof(int32_t) * ((largest + 8 + 8 * nv) + (largest + nv) + nv * gvtm::kGroupVoicesThreads));
+}
+
+// The slice pipeline of the host entries, three streams deep:
+//     input(i + 1) on the H2D stream  ||  work(i) on the compute stream  ||  output(i - 1) on the copy stream
+// A layout gives the three as callables that queue slice i's part on the stream they are handed (input and output: one
+// copy, a hipError_t; work: kernels, a GVTM_* status with its message set), and two numbers.
+// trail: slice i's output is queued behind the work of slice i + trail, or of the last slice.  With pageable host memory a
+// device-to-host copy blocks the calling thread until its slice is done, so no output is queued before the kernels that may
+// run beside it: trail = n_slices where the whole batch is staged on the device; 1, the least, where sets rotate, which
+// needs the outputs queued in step (hipStreamWaitEvent on an event not recorded yet waits for nothing).  sets: slice i's
+// input waits until the output of slice i - sets has left; 0: no output's leaving is recorded or waited for.  With
+// page-locked host buffers (gvtm_host_alloc) all three really overlap; with pageable ones the runtime stages the copies
+// itself and the call returns the same bytes.  The streams are drained when this returns, failed or not.
+template <typename Input, typename Work, typename Output>
+int run_slices(gvtm_plan* plan, size_t n_slices, size_t trail, size_t sets, const char* input_what, Input input, Work work, Output output)
+{
+	hipError_t e;
+	for (Stream* st : {&plan->h2d_stream, &plan->compute_stream, &plan->copy_stream}) {
+		if (!st->h && (e = hipStreamCreateWithFlags(&st->h, hipStreamNonBlocking)) != hipSuccess) return fail_hip(e, "hipStreamCreate");
+	}
+	const hipStream_t h2d_stream = plan->h2d_stream.h, compute_stream = plan->compute_stream.h, copy_stream = plan->copy_stream.h;
+	while (plan->slice_events.size() < 3 * n_slices) {
+		Event ev;
+		if ((e = hipEventCreateWithFlags(&ev.h, hipEventDisableTiming)) != hipSuccess) return fail_hip(e, "hipEventCreate");
+		plan->slice_events.push_back(std::move(ev));
+	}
+	enum { kArrived, kReady, kCopied };
+	auto event = [&](size_t i, int which) { return plan->slice_events[3 * i + which].h; };
+	auto queue_output = [&](size_t i) -> int {
+		if ((e = hipStreamWaitEvent(copy_stream, event(i, kReady), 0)) != hipSuccess) return fail_hip(e, "hipStreamWaitEvent");
+		if ((e = output(i, copy_stream)) != hipSuccess) return fail_hip(e, "D2H samples");
+		if (sets && (e = hipEventRecord(event(i, kCopied), copy_stream)) != hipSuccess) return fail_hip(e, "hipEventRecord");
+		return GVTM_OK;
+	};
+	auto queue_slice = [&](size_t i) -> int {
+		if (sets && i >= sets && (e = hipStreamWaitEvent(h2d_stream, event(i - sets, kCopied), 0)) != hipSuccess) return fail_hip(e, "hipStreamWaitEvent");
+		if ((e = input(i, h2d_stream)) != hipSuccess) return fail_hip(e, input_what);
+		if ((e = hipEventRecord(event(i, kArrived), h2d_stream)) != hipSuccess) return fail_hip(e, "hipEventRecord");
+		if ((e = hipStreamWaitEvent(compute_stream, event(i, kArrived), 0)) != hipSuccess) return fail_hip(e, "hipStreamWaitEvent");
+		if (const int rc = work(i, compute_stream); rc != GVTM_OK) return rc;
+		if ((e = hipEventRecord(event(i, kReady), compute_stream)) != hipSuccess) return fail_hip(e, "hipEventRecord");
+		return i >= trail ? queue_output(i - trail) : GVTM_OK;
+	};
+	int rc = GVTM_OK;
+	for (size_t i = 0; i < n_slices && rc == GVTM_OK; ++i) rc = queue_slice(i);
+	for (size_t i = n_slices - std::min(trail, n_slices); i < n_slices && rc == GVTM_OK; ++i) rc = queue_output(i);
+	if (rc == GVTM_OK && (e = hipStreamSynchronize(copy_stream)) != hipSuccess) rc = fail_hip(e, "vtm_synth_kernel execution / D2H samples");
+	if (rc != GVTM_OK) {
+		for (hipStream_t st : {h2d_stream, compute_stream, copy_stream}) (void) hipStreamSynchronize(st);
+		return rc;
+	}
+	if ((e = hipStreamSynchronize(compute_stream)) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");
+	if ((e = hipStreamSynchronize(h2d_stream)) != hipSuccess) return fail_hip(e, input_what);
+	return GVTM_OK;
+}
+
+// out_counts, maxabs and scales of the whole batch, from the host entries' scratch to the caller's arrays where given
+int copy_back_results(gvtm_plan* plan, size_t batch, int64_t* out_counts, float* maxabs, float* scales)
+{
+	hipError_t e;
+	if (out_counts && (e = hipMemcpy(out_counts, plan->host.counts.ptr, sizeof(int64_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H counts");
+	if (maxabs && (e = hipMemcpy(maxabs, plan->host.maxabs.ptr, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H maxabs");
+	if (scales && (e = hipMemcpy(scales, plan->host.scales.ptr, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H scales");
+	return GVTM_OK;
+}
+
+// The padded layout: params [batch][max_frames] in, rows [batch][stride] out, staged on the device for the whole batch.  A
+// batch of at least two machine-fulls goes in slices of one machine-full each (rows x compute units utterances: every
+// compute unit busy, in the shape the whole batch would use), each a region of the whole-batch buffers:
+//     H2D frames(i + 1)  ||  kernel(i) [+ scale -> int16(i)]  ||  D2H samples, behind the last slice's kernels
 int host_pipeline(gvtm_plan* plan, const HostJob& j)
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
 	const bool voices = j.voice_ids != nullptr;
 	if (!voices && plan->n_voices() > 1) return refuse_voices(plan, j.pcm ? "gvtm_synthesize_batch_host_pcm16" : "gvtm_synthesize_batch_host");
-	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 	const size_t batch = j.batch, max_frames = j.max_frames, audio_stride = j.stride;
 	if (batch == 0) return GVTM_OK;
 	if (!j.audio && !j.pcm) return fail(GVTM_ERR_INVALID_ARGUMENT, "null output buffer");
 	if (max_frames > 0 && !j.params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
-	for (int v = 0; v < plan->n_voices(); ++v) {
-		if (audio_stride < design_output_count(plan->designs[v], max_frames)) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_output_count(plan, max_frames)");
-		}
-	}
+	// (with voices too the single-voice sentence)
+	int rc = check_audio_stride(plan, audio_stride, max_frames, false);
+	if (rc != GVTM_OK) return rc;
 	// A frame count outside [0, max_frames] fails THAT utterance (out_counts[b] = -1, no samples); the others are
 	// synthesized.  The device sees it as an empty utterance.
 	std::vector<int32_t> sane;
@@ -1320,108 +1414,66 @@ int host_pipeline(gvtm_plan* plan, const HostJob& j)
 		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
 	}
 	const int32_t* const counts_in = sane.empty() ? j.frame_counts : sane.data();
+	size_t machine;
+	const gvtm::LaunchShape shape_all = whole_batch_shape(plan, batch, machine);
+	const size_t slice = batch >= 2 * machine ? machine : batch;
+	const size_t n_slices = (batch + slice - 1) / slice;
+
 	DeviceScope scope(plan->device);
 	hipError_t e = scope.status();
 	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
 	const size_t row_in = max_frames * GVTM_N_PARAM;
 	const size_t pbytes = sizeof(float) * batch * row_in;
-	const size_t abytes = sizeof(float) * batch * audio_stride;
-	const size_t obytes = sizeof(int16_t) * batch * audio_stride;
 	auto& sc = plan->host;
 	if ((e = sc.params.ensure(pbytes ? pbytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc params");
-	if ((e = sc.audio.ensure(abytes ? abytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc audio");
+	if ((e = sc.audio.ensure(std::max<size_t>(16, sizeof(float) * batch * audio_stride))) != hipSuccess) return fail_hip(e, "hipMalloc audio");
 	if ((e = sc.counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
 	if ((e = sc.maxabs.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc maxabs");
 	if (counts_in && (e = sc.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
 	if (voices && (e = sc.voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
-	if (j.pcm && (e = sc.pcm.ensure(obytes ? obytes : 16)) != hipSuccess) return fail_hip(e, "hipMalloc pcm");
+	if (j.pcm && (e = sc.pcm.ensure(std::max<size_t>(16, sizeof(int16_t) * batch * audio_stride))) != hipSuccess) return fail_hip(e, "hipMalloc pcm");
 	if (j.pcm && (e = sc.scales.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc scales");
-	for (Stream* st : {&plan->h2d_stream, &plan->compute_stream, &plan->copy_stream}) {
-		if (!st->h && (e = hipStreamCreateWithFlags(&st->h, hipStreamNonBlocking)) != hipSuccess) return fail_hip(e, "hipStreamCreate");
-	}
-	const hipStream_t h2d_stream = plan->h2d_stream.h, compute_stream = plan->compute_stream.h, copy_stream = plan->copy_stream.h;
+	if (voices && (e = reserve_host_groups(plan, slice)) != hipSuccess) return fail_hip(e, "hipMalloc row map");
 
-	float* const d_params = static_cast<float*>(sc.params.ptr);
-	const int32_t* const d_frames = counts_in ? static_cast<const int32_t*>(sc.frames.ptr) : nullptr;
-	float* const d_audio = static_cast<float*>(sc.audio.ptr);
-	int16_t* const d_pcm = j.pcm ? static_cast<int16_t*>(sc.pcm.ptr) : nullptr;
-	float* const d_scales = j.pcm ? static_cast<float*>(sc.scales.ptr) : nullptr;
-	int64_t* const d_counts = static_cast<int64_t*>(sc.counts.ptr);
-	float* const d_maxabs = static_cast<float*>(sc.maxabs.ptr);
-	if (counts_in && (e = hipMemcpy(sc.frames.ptr, counts_in, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
-		return fail_hip(e, "H2D frame_counts");
-	}
-	const int32_t* const d_voice_ids = voices ? static_cast<const int32_t*>(sc.voice_ids.ptr) : nullptr;
-	if (voices && (e = hipMemcpy(sc.voice_ids.ptr, j.voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) {
-		return fail_hip(e, "H2D voice_ids");
-	}
+	if (counts_in && (e = hipMemcpy(sc.frames.ptr, counts_in, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D frame_counts");
+	if (voices && (e = hipMemcpy(sc.voice_ids.ptr, j.voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D voice_ids");
+	float* const d_params = sc.params.as<float>();
+	float* const d_audio = sc.audio.as<float>();
+	int16_t* const d_pcm = sc.pcm.as<int16_t>();
+	int64_t* const d_counts = sc.counts.as<int64_t>();
+	float* const d_maxabs = sc.maxabs.as<float>();
 	// rows come back zero beyond their sample count (the staging buffers are reused between calls; the voices of a mixed
 	// batch give different counts)
 	const bool ragged = counts_in != nullptr || voices || audio_stride > gvtm_output_count(plan, max_frames);
 
-	// the shape of the whole batch (every slice is launched in it), and how many utterances fill the machine once in it
-	// (the rows the batch size picks: a launch still gives way to fewer where the LDS does not hold them)
-	const gvtm::LaunchShape shape_all = plan->launch_shape(batch, 0, false, 0, false);
-	const size_t machine = static_cast<size_t>(shape_all.per_cu) * static_cast<size_t>(plan->compute_units > 0 ? plan->compute_units : 256);
-	const size_t slice = batch >= 2 * machine ? machine : batch;
-	const size_t n_slices = (batch + slice - 1) / slice;
-	while (plan->slice_done.size() < 2 * n_slices) {
-		Event ev;
-		if ((e = hipEventCreateWithFlags(&ev.h, hipEventDisableTiming)) != hipSuccess) return fail_hip(e, "hipEventCreate");
-		plan->slice_done.push_back(std::move(ev));
-	}
-	auto drain = [&]() {
-		(void) hipStreamSynchronize(h2d_stream);
-		(void) hipStreamSynchronize(compute_stream);
-		(void) hipStreamSynchronize(copy_stream);
+	// slice i: utterances [lo, lo + n)
+	auto count_of = [&](size_t i) { return std::min(slice, batch - i * slice); };
+	auto input = [&](size_t i, hipStream_t stream) {
+		const size_t lo = i * slice;
+		return pbytes ? hipMemcpyAsync(d_params + lo * row_in, j.params + lo * row_in, sizeof(float) * count_of(i) * row_in, hipMemcpyHostToDevice, stream) : hipSuccess;
 	};
-	int rc = GVTM_OK;
-	for (size_t i = 0; i < n_slices && rc == GVTM_OK; ++i) {
-		const size_t lo = i * slice, n = std::min(slice, batch - lo);
-		hipEvent_t in_done = plan->slice_done[2 * i].h, out_ready = plan->slice_done[2 * i + 1].h;
-		if (pbytes && (e = hipMemcpyAsync(d_params + lo * row_in, j.params + lo * row_in, sizeof(float) * n * row_in, hipMemcpyHostToDevice,
-				h2d_stream)) != hipSuccess) { rc = fail_hip(e, "H2D params"); break; }
-		if ((e = hipEventRecord(in_done, h2d_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
-		if ((e = hipStreamWaitEvent(compute_stream, in_done, 0)) != hipSuccess) { rc = fail_hip(e, "hipStreamWaitEvent"); break; }
-		if (ragged && !j.pcm && (e = hipMemsetAsync(d_audio + lo * audio_stride, 0, sizeof(float) * n * audio_stride, compute_stream)) != hipSuccess) {
-			rc = fail_hip(e, "hipMemsetAsync"); break;
+	auto work = [&](size_t i, hipStream_t stream) {
+		const size_t lo = i * slice, n = count_of(i);
+		const hipError_t we = !ragged ? hipSuccess : j.pcm ? hipMemsetAsync(d_pcm + lo * audio_stride, 0, sizeof(int16_t) * n * audio_stride, stream)
+		                                                   : hipMemsetAsync(d_audio + lo * audio_stride, 0, sizeof(float) * n * audio_stride, stream);
+		if (we != hipSuccess) return fail_hip(we, "hipMemsetAsync");
+		int wrc = launch_synthesis(plan, LaunchRequest{d_params + lo * row_in, counts_in ? sc.frames.as<int32_t>() + lo : nullptr, n, max_frames, d_audio + lo * audio_stride,
+				audio_stride, d_counts + lo, d_maxabs + lo, stream, shape_all.forced, voices, voices ? sc.voice_ids.as<int32_t>() + lo : nullptr, &sc.groups});
+		// (normalize takes at most 65535 utterances per launch: a slice is far below that unless the batch is one slice)
+		for (size_t q = 0; j.pcm && q < n && wrc == GVTM_OK; q += 32768) {
+			const size_t m = std::min<size_t>(32768, n - q);
+			wrc = gvtm_normalize_batch_device(plan, d_audio + (lo + q) * audio_stride, m, audio_stride, d_counts + lo + q, d_maxabs + lo + q, nullptr,
+					d_pcm + (lo + q) * audio_stride, sc.scales.as<float>() + lo + q, stream);
 		}
-		if (ragged && j.pcm && (e = hipMemsetAsync(d_pcm + lo * audio_stride, 0, sizeof(int16_t) * n * audio_stride, compute_stream)) != hipSuccess) {
-			rc = fail_hip(e, "hipMemsetAsync"); break;
-		}
-		rc = launch_synthesis(plan, LaunchRequest{d_params + lo * row_in, d_frames ? d_frames + lo : nullptr, n, max_frames, d_audio + lo * audio_stride,
-				audio_stride, d_counts + lo, d_maxabs + lo, compute_stream, shape_all.forced, voices, voices ? d_voice_ids + lo : nullptr, &sc.groups});
-		if (rc != GVTM_OK) break;
-		if (j.pcm) {
-			// (normalize takes at most 65535 utterances per launch: a slice is far below that unless the batch is one slice)
-			for (size_t q = 0; q < n && rc == GVTM_OK; q += 32768) {
-				const size_t m = std::min<size_t>(32768, n - q);
-				rc = gvtm_normalize_batch_device(plan, d_audio + (lo + q) * audio_stride, m, audio_stride, d_counts + lo + q, d_maxabs + lo + q, nullptr,
-						d_pcm + (lo + q) * audio_stride, d_scales + lo + q, compute_stream);
-			}
-			if (rc != GVTM_OK) break;
-		}
-		if ((e = hipEventRecord(out_ready, compute_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
-	}
-	if (rc != GVTM_OK) {
-		drain();
-		return rc;
-	}
-	// (second loop: with pageable host memory a device-to-host copy blocks the calling thread until its slice is done,
-	// so every kernel is queued before the first of them)
-	for (size_t i = 0; i < n_slices; ++i) {
-		const size_t lo = i * slice, n = std::min(slice, batch - lo);
-		if ((e = hipStreamWaitEvent(copy_stream, plan->slice_done[2 * i + 1].h, 0)) != hipSuccess) { drain(); return fail_hip(e, "hipStreamWaitEvent"); }
-		if (j.pcm) e = hipMemcpyAsync(j.pcm + lo * audio_stride, d_pcm + lo * audio_stride, sizeof(int16_t) * n * audio_stride, hipMemcpyDeviceToHost, copy_stream);
-		else e = hipMemcpyAsync(j.audio + lo * audio_stride, d_audio + lo * audio_stride, sizeof(float) * n * audio_stride, hipMemcpyDeviceToHost, copy_stream);
-		if (e != hipSuccess) { drain(); return fail_hip(e, "D2H samples"); }
-	}
-	if ((e = hipStreamSynchronize(copy_stream)) != hipSuccess) { drain(); return fail_hip(e, "vtm_synth_kernel execution / D2H samples"); }
-	if ((e = hipStreamSynchronize(compute_stream)) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");
-	if ((e = hipStreamSynchronize(h2d_stream)) != hipSuccess) return fail_hip(e, "H2D params");
-	if (j.out_counts && (e = hipMemcpy(j.out_counts, d_counts, sizeof(int64_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H counts");
-	if (j.maxabs && (e = hipMemcpy(j.maxabs, d_maxabs, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H maxabs");
-	if (j.scales && d_scales && (e = hipMemcpy(j.scales, d_scales, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H scales");
+		return wrc;
+	};
+	auto output = [&](size_t i, hipStream_t stream) {
+		const size_t lo = i * slice, n = count_of(i);
+		if (j.pcm) return hipMemcpyAsync(j.pcm + lo * audio_stride, d_pcm + lo * audio_stride, sizeof(int16_t) * n * audio_stride, hipMemcpyDeviceToHost, stream);
+		return hipMemcpyAsync(j.audio + lo * audio_stride, d_audio + lo * audio_stride, sizeof(float) * n * audio_stride, hipMemcpyDeviceToHost, stream);
+	};
+	if ((rc = run_slices(plan, n_slices, n_slices, 0, "H2D params", input, work, output)) != GVTM_OK) return rc;
+	if ((rc = copy_back_results(plan, batch, j.out_counts, j.maxabs, j.scales)) != GVTM_OK) return rc;
 	for (size_t b : bad) {
 		if (j.out_counts) j.out_counts[b] = -1;
 		if (j.maxabs) j.maxabs[b] = 0.0f;
@@ -1764,7 +1816,7 @@ int gvtm_stream_create(gvtm_plan* plan, size_t batch, gvtm_stream** stream_out)
 	if (!plan || !stream_out || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan / stream_out or empty batch");
 	*stream_out = nullptr;
 	if (plan->n_voices() > 1) return refuse_voices(plan, "gvtm_stream_create");
-	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 	return create_stream(plan, batch, nullptr, stream_out);
 }
 
@@ -1774,7 +1826,7 @@ int gvtm_stream_create_voices(gvtm_plan* plan, const int32_t* voice_ids, size_t 
 	if (!plan || !stream_out || !voice_ids || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan / stream_out / voice_ids or empty batch");
 	const int rc = check_voice_ids(plan, voice_ids, batch);
 	if (rc != GVTM_OK) return rc;
-	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 	// (a plan of one voice: every id is 0, and the stream is the one gvtm_stream_create makes)
 	return create_stream(plan, batch, plan->n_voices() > 1 ? voice_ids : nullptr, stream_out);
 }
@@ -2117,12 +2169,10 @@ int packed_layout(const gvtm_plan* plan, const int64_t* frame_offsets, const int
 	} else if (plan->n_voices() > 1) {
 		return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids: the plan has " + std::to_string(plan->n_voices()) + " voices (one voice id per utterance)");
 	}
-	// (as launch_synthesis judges a launch: by the voice with the most steps per frame)
-	unsigned max_steps = 0;
-	for (int v = 0; v < plan->n_voices(); ++v) max_steps = std::max(max_steps, plan->designs[v].k.control_steps);
 	for (size_t b = 0; b < batch; ++b) {
 		const unsigned long long frames = static_cast<unsigned long long>(frame_offsets[b + 1] - frame_offsets[b]);
-		if (frames >= (1ull << 31) || frames * max_steps + 4096ull >= (1ull << 31)) {
+		// (as launch_synthesis judges a launch: by the voice with the most steps per frame)
+		if (!fits_step_counter(plan, frames)) {
 			return fail(GVTM_ERR_INVALID_ARGUMENT, "utterance " + std::to_string(b) + ": frames * control_steps does not fit the 31-bit step counter");
 		}
 		const size_t count = design_output_count(plan->designs[voice_ids ? voice_ids[b] : 0], static_cast<size_t>(frames));
@@ -2166,13 +2216,8 @@ PackedSlice packed_slice(const gvtm_plan* plan, const PackedJob& j, const std::v
 	return s;
 }
 
-void packed_release(gvtm_plan* plan)
-{
-	for (DeviceBuffer& set : plan->packed.set) set = DeviceBuffer();
-}
-
-// Utterances in the caller's order, in contiguous slices of at most one machine-full and (with a limit) of at most a third
-// of the limit, three staging sets deep:
+// The packed layout: utterances in the caller's order, in contiguous slices of at most one machine-full and (with a limit)
+// of at most a third of the limit, three staging sets deep:
 //     H2D packed frames(i + 1)  ||  unpack + synthesis + pack(i)  ||  D2H packed output(i - 1)
 // Slice i uses set i % 3; its frames go up once the output of slice i - 3 has left.
 int packed_pipeline(gvtm_plan* plan, const PackedJob& j)
@@ -2190,7 +2235,7 @@ int packed_pipeline(gvtm_plan* plan, const PackedJob& j)
 				return fail(GVTM_ERR_INVALID_ARGUMENT, "capacity " + std::to_string(j.capacity) + " below gvtm_packed_sample_offsets (" + std::to_string(offsets[batch]) + " samples)");
 			}
 		}
-		if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+		if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 		if (batch == 0) {
 			if (j.sample_offsets_out) j.sample_offsets_out[0] = 0;
 			return GVTM_OK;
@@ -2198,9 +2243,10 @@ int packed_pipeline(gvtm_plan* plan, const PackedJob& j)
 		if (batch > 0x3fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large");
 
 		// the slices, on the host, before any device work: every slice in the shape of the whole batch, as host_pipeline's
-		const gvtm::LaunchShape shape_all = plan->launch_shape(batch, 0, false, 0, false);
-		const size_t machine = std::max<size_t>(1, static_cast<size_t>(shape_all.per_cu) * static_cast<size_t>(plan->compute_units > 0 ? plan->compute_units : 256));
-		const size_t limit = plan->packed.limit, set_limit = limit / 3;
+		size_t machine;
+		const gvtm::LaunchShape shape_all = whole_batch_shape(plan, batch, machine);
+		auto& sc = plan->host;
+		const size_t limit = sc.limit, set_limit = limit / 3;
 		std::vector<PackedSlice> slices;
 		size_t longest = 0;
 		for (size_t lo = 0; lo < batch;) {
@@ -2227,9 +2273,8 @@ int packed_pipeline(gvtm_plan* plan, const PackedJob& j)
 		DeviceScope scope(plan->device);
 		hipError_t e = scope.status();
 		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-		auto& sc = plan->packed;
 		// (sets only grow; under a limit none may stay larger than its third)
-		if (limit && std::max({sc.set[0].bytes, sc.set[1].bytes, sc.set[2].bytes}) > set_limit) packed_release(plan);
+		if (limit && std::max({sc.set[0].bytes, sc.set[1].bytes, sc.set[2].bytes}) > set_limit) plan->host.release_sets();
 		for (size_t q = 0; q < n_sets; ++q) {
 			if ((e = sc.set[q].ensure(set_bytes)) != hipSuccess) return e == hipErrorOutOfMemory ? fail(GVTM_ERR_OUT_OF_MEMORY, "hipMalloc staging set: out of memory") : fail_hip(e, "hipMalloc staging set");
 		}
@@ -2239,22 +2284,8 @@ int packed_pipeline(gvtm_plan* plan, const PackedJob& j)
 		if ((e = sc.counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
 		if ((e = sc.maxabs.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc maxabs");
 		if (j.pcm && (e = sc.scales.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc scales");
-		if (voices) {
-			if ((e = sc.voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
-			// the grouping's scratch for the largest slice in any shape (rows <= 8): no launch regrows it under a queued kernel
-			const size_t nv = static_cast<size_t>(plan->n_voices());
-			const size_t ints = (largest + 8 + 8 * nv) + (largest + nv) + nv * gvtm::kGroupVoicesThreads;
-			if ((e = sc.groups.ensure(sizeof(int32_t) * ints)) != hipSuccess) return fail_hip(e, "hipMalloc row map");
-		}
-		for (Stream* st : {&plan->h2d_stream, &plan->compute_stream, &plan->copy_stream}) {
-			if (!st->h && (e = hipStreamCreateWithFlags(&st->h, hipStreamNonBlocking)) != hipSuccess) return fail_hip(e, "hipStreamCreate");
-		}
-		const hipStream_t h2d_stream = plan->h2d_stream.h, compute_stream = plan->compute_stream.h, copy_stream = plan->copy_stream.h;
-		while (sc.events.size() < 3 * n_slices) {
-			Event ev;
-			if ((e = hipEventCreateWithFlags(&ev.h, hipEventDisableTiming)) != hipSuccess) return fail_hip(e, "hipEventCreate");
-			sc.events.push_back(std::move(ev));
-		}
+		if (voices && (e = sc.voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
+		if (voices && (e = reserve_host_groups(plan, largest)) != hipSuccess) return fail_hip(e, "hipMalloc row map");
 		// the noise table once, for the longest utterance: no slice regrows it in the middle of the pipeline
 		if ((rc = gvtm_plan_reserve(plan, longest)) != GVTM_OK) return rc;
 		if ((e = hipMemcpy(sc.frame_offsets.ptr, j.frame_offsets, sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D frame offsets");
@@ -2263,70 +2294,40 @@ int packed_pipeline(gvtm_plan* plan, const PackedJob& j)
 		if (j.sample_offsets_out) std::copy(offsets.begin(), offsets.end(), j.sample_offsets_out);
 		sc.slices = n_slices, sc.largest_slice = largest;
 
-		const int64_t* const d_frame_offsets = static_cast<const int64_t*>(sc.frame_offsets.ptr);
-		const int64_t* const d_sample_offsets = static_cast<const int64_t*>(sc.sample_offsets.ptr);
-		int32_t* const d_frames = static_cast<int32_t*>(sc.frames.ptr);
-		const int32_t* const d_voice_ids = voices ? static_cast<const int32_t*>(sc.voice_ids.ptr) : nullptr;
-		int64_t* const d_counts = static_cast<int64_t*>(sc.counts.ptr);
-		float* const d_maxabs = static_cast<float*>(sc.maxabs.ptr);
-		float* const d_scales = j.pcm ? static_cast<float*>(sc.scales.ptr) : nullptr;
-		const size_t width = j.pcm ? sizeof(int16_t) : sizeof(float);
-		auto drain = [&]() {
-			(void) hipStreamSynchronize(h2d_stream);
-			(void) hipStreamSynchronize(compute_stream);
-			(void) hipStreamSynchronize(copy_stream);
-		};
-		// slice i's packed output leaves: one contiguous range [offset[lo], offset[hi])
-		auto copy_out = [&](size_t i) -> hipError_t {
+		int32_t* const d_frames = sc.frames.as<int32_t>();
+		int64_t* const d_counts = sc.counts.as<int64_t>();
+		float* const d_maxabs = sc.maxabs.as<float>();
+		// slice i's set, carved: packed frames, padded frames, padded samples, packed output
+		auto set_of = [&](size_t i) { return static_cast<unsigned char*>(sc.set[i % 3].ptr); };
+		auto input = [&](size_t i, hipStream_t stream) {
 			const PackedSlice& s = slices[i];
-			const unsigned char* d_out = static_cast<const unsigned char*>(sc.set[i % 3].ptr) + s.in_bytes + s.rows_bytes + s.audio_bytes;
-			unsigned char* const host = j.pcm ? reinterpret_cast<unsigned char*>(j.pcm) : reinterpret_cast<unsigned char*>(j.audio);
-			hipError_t ce = hipStreamWaitEvent(copy_stream, sc.events[3 * i + 1].h, 0);
-			if (ce == hipSuccess && s.out_bytes) ce = hipMemcpyAsync(host + width * static_cast<size_t>(offsets[s.lo]), d_out, s.out_bytes, hipMemcpyDeviceToHost, copy_stream);
-			if (ce == hipSuccess) ce = hipEventRecord(sc.events[3 * i + 2].h, copy_stream);
-			return ce;
+			return s.in_bytes ? hipMemcpyAsync(set_of(i), j.frames + GVTM_N_PARAM * static_cast<size_t>(j.frame_offsets[s.lo]), s.in_bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
 		};
-		rc = GVTM_OK;
-		for (size_t i = 0; i < n_slices && rc == GVTM_OK; ++i) {
+		auto work = [&](size_t i, hipStream_t stream) -> int {
 			const PackedSlice& s = slices[i];
 			const size_t n = s.hi - s.lo;
-			unsigned char* const set = static_cast<unsigned char*>(sc.set[i % 3].ptr);
-			float* const d_in = reinterpret_cast<float*>(set);
-			float* const d_rows = reinterpret_cast<float*>(set + s.in_bytes);
-			float* const d_audio = reinterpret_cast<float*>(set + s.in_bytes + s.rows_bytes);
-			unsigned char* const d_out = set + s.in_bytes + s.rows_bytes + s.audio_bytes;
-			hipEvent_t in_done = sc.events[3 * i].h, out_ready = sc.events[3 * i + 1].h;
-			// (the set is free once slice i - 3's output has left: its D2H was queued two rounds ago)
-			if (i >= 3 && (e = hipStreamWaitEvent(h2d_stream, sc.events[3 * (i - 3) + 2].h, 0)) != hipSuccess) { rc = fail_hip(e, "hipStreamWaitEvent"); break; }
-			if (s.in_bytes && (e = hipMemcpyAsync(d_in, j.frames + GVTM_N_PARAM * static_cast<size_t>(j.frame_offsets[s.lo]), s.in_bytes, hipMemcpyHostToDevice,
-					h2d_stream)) != hipSuccess) { rc = fail_hip(e, "H2D frames"); break; }
-			if ((e = hipEventRecord(in_done, h2d_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
-			if ((e = hipStreamWaitEvent(compute_stream, in_done, 0)) != hipSuccess) { rc = fail_hip(e, "hipStreamWaitEvent"); break; }
-			if ((e = gvtm::launch_unpack_frames(gvtm::UnpackFramesArgs{d_in, d_frame_offsets + s.lo, d_rows, d_frames + s.lo, n, s.max_frames}, compute_stream)) != hipSuccess) {
-				rc = fail_hip(e, "vtm_unpack_frames_kernel launch"); break;
-			}
-			rc = launch_synthesis(plan, LaunchRequest{d_rows, d_frames + s.lo, n, s.max_frames, d_audio, s.stride, d_counts + s.lo, d_maxabs + s.lo, compute_stream,
-					shape_all.forced, voices, voices ? d_voice_ids + s.lo : nullptr, &sc.groups});
-			if (rc != GVTM_OK) break;
-			if ((e = gvtm::launch_pack_samples(gvtm::PackSamplesArgs{d_audio, d_counts + s.lo, d_maxabs + s.lo, d_sample_offsets + s.lo,
-					j.pcm ? nullptr : reinterpret_cast<float*>(d_out), j.pcm ? reinterpret_cast<int16_t*>(d_out) : nullptr, d_scales ? d_scales + s.lo : nullptr, n, s.stride},
-					compute_stream)) != hipSuccess) { rc = fail_hip(e, "vtm_pack_samples_kernel launch"); break; }
-			if ((e = hipEventRecord(out_ready, compute_stream)) != hipSuccess) { rc = fail_hip(e, "hipEventRecord"); break; }
-			// (behind the next slice's kernels: with pageable host memory a device-to-host copy blocks the calling thread)
-			if (i >= 1 && (e = copy_out(i - 1)) != hipSuccess) { rc = fail_hip(e, "D2H samples"); break; }
-		}
-		if (rc == GVTM_OK && (e = copy_out(n_slices - 1)) != hipSuccess) rc = fail_hip(e, "D2H samples");
-		if (rc != GVTM_OK) {
-			drain();
-			return rc;
-		}
-		if ((e = hipStreamSynchronize(copy_stream)) != hipSuccess) { drain(); return fail_hip(e, "vtm_synth_kernel execution / D2H samples"); }
-		if ((e = hipStreamSynchronize(compute_stream)) != hipSuccess) return fail_hip(e, "vtm_synth_kernel execution");
-		if ((e = hipStreamSynchronize(h2d_stream)) != hipSuccess) return fail_hip(e, "H2D frames");
-		if (j.out_counts && (e = hipMemcpy(j.out_counts, d_counts, sizeof(int64_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H counts");
-		if (j.maxabs && (e = hipMemcpy(j.maxabs, d_maxabs, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H maxabs");
-		if (j.scales && (e = hipMemcpy(j.scales, d_scales, sizeof(float) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H scales");
-		return GVTM_OK;
+			float* const d_rows = reinterpret_cast<float*>(set_of(i) + s.in_bytes);
+			float* const d_audio = reinterpret_cast<float*>(set_of(i) + s.in_bytes + s.rows_bytes);
+			unsigned char* const d_out = set_of(i) + s.in_bytes + s.rows_bytes + s.audio_bytes;
+			hipError_t we = gvtm::launch_unpack_frames(gvtm::UnpackFramesArgs{reinterpret_cast<float*>(set_of(i)), sc.frame_offsets.as<int64_t>() + s.lo, d_rows, d_frames + s.lo, n, s.max_frames}, stream);
+			if (we != hipSuccess) return fail_hip(we, "vtm_unpack_frames_kernel launch");
+			const int wrc = launch_synthesis(plan, LaunchRequest{d_rows, d_frames + s.lo, n, s.max_frames, d_audio, s.stride, d_counts + s.lo, d_maxabs + s.lo, stream,
+					shape_all.forced, voices, voices ? sc.voice_ids.as<int32_t>() + s.lo : nullptr, &sc.groups});
+			if (wrc != GVTM_OK) return wrc;
+			we = gvtm::launch_pack_samples(gvtm::PackSamplesArgs{d_audio, d_counts + s.lo, d_maxabs + s.lo, sc.sample_offsets.as<int64_t>() + s.lo,
+					j.pcm ? nullptr : reinterpret_cast<float*>(d_out), j.pcm ? reinterpret_cast<int16_t*>(d_out) : nullptr, j.pcm ? sc.scales.as<float>() + s.lo : nullptr, n, s.stride},
+					stream);
+			return we == hipSuccess ? GVTM_OK : fail_hip(we, "vtm_pack_samples_kernel launch");
+		};
+		// slice i's packed output leaves: one contiguous range [offset[lo], offset[hi])
+		auto output = [&](size_t i, hipStream_t stream) {
+			const PackedSlice& s = slices[i];
+			unsigned char* const host = j.pcm ? reinterpret_cast<unsigned char*>(j.pcm) : reinterpret_cast<unsigned char*>(j.audio);
+			unsigned char* const d_out = set_of(i) + s.in_bytes + s.rows_bytes + s.audio_bytes;
+			return s.out_bytes ? hipMemcpyAsync(host + (j.pcm ? sizeof(int16_t) : sizeof(float)) * static_cast<size_t>(offsets[s.lo]), d_out, s.out_bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+		};
+		if ((rc = run_slices(plan, n_slices, 1, 3, "H2D frames", input, work, output)) != GVTM_OK) return rc;
+		return copy_back_results(plan, batch, j.out_counts, j.maxabs, j.scales);
 	} catch (const std::bad_alloc&) {
 		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
 	}
@@ -2364,12 +2365,12 @@ int gvtm_synthesize_packed_host_pcm16(gvtm_plan* plan, const float* frames, cons
 int gvtm_plan_set_staging_limit(gvtm_plan* plan, size_t bytes)
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
-	plan->packed.limit = bytes;
+	plan->host.limit = bytes;
 	// what an earlier call holds beyond the new limit goes now (every packed call drains its streams before it returns)
-	if (bytes && plan->device != GVTM_DEVICE_NONE && plan->packed.staging_bytes() > bytes) {
+	if (bytes && plan->device != GVTM_DEVICE_NONE && plan->host.staging_bytes() > bytes) {
 		DeviceScope scope(plan->device);
 		if (scope.status() != hipSuccess) return fail_hip(scope.status(), "hipSetDevice");
-		packed_release(plan);
+		plan->host.release_sets();
 	}
 	return GVTM_OK;
 }
@@ -2377,29 +2378,25 @@ int gvtm_plan_set_staging_limit(gvtm_plan* plan, size_t bytes)
 int gvtm_plan_packed_stats(const gvtm_plan* plan, gvtm_packed_stats* out)
 {
 	if (!plan || !out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or out");
-	out->staging_bytes = plan->packed.staging_bytes();
-	out->limit = plan->packed.limit;
-	out->slices = plan->packed.slices;
-	out->largest_slice = plan->packed.largest_slice;
+	out->staging_bytes = plan->host.staging_bytes();
+	out->limit = plan->host.limit;
+	out->slices = plan->host.slices;
+	out->largest_slice = plan->host.largest_slice;
 	return GVTM_OK;
 }
 
 int gvtm_plan_reserve(gvtm_plan* plan, size_t max_frames)
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
-	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan (GVTM_DEVICE_NONE): there is no CPU synthesis path");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 	// (the plans whose one-shot launches read the table: launch_synthesis)
 	if (plan->designs[0].model5 || !GVTM_NOISE_TABLE || plan->precision != GVTM_PRECISION_F32) return GVTM_OK;
-	unsigned max_steps = 0;
-	for (int v = 0; v < plan->n_voices(); ++v) max_steps = std::max(max_steps, plan->designs[v].k.control_steps);
-	if (static_cast<unsigned long long>(max_frames) * max_steps + 4096ull >= (1ull << 31)) {
-		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
-	}
+	if (!fits_step_counter(plan, max_frames)) return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
 	try {
 		DeviceScope scope(plan->device);
 		if (scope.status() != hipSuccess) return fail_hip(scope.status(), "hipSetDevice");
 		gvtm::SynthArgs unused;
-		return use_noise_table(plan, max_frames * static_cast<size_t>(max_steps), unused);
+		return use_noise_table(plan, max_frames * static_cast<size_t>(max_control_steps(plan)), unused);
 	} catch (const std::bad_alloc&) {
 		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
 	}
