@@ -247,6 +247,13 @@ def load_library(diagnostics=False):
         L.gvtm_plan_packed_stats.restype = i32
         L.gvtm_plan_reserve.argtypes = [vp, sz]
         L.gvtm_plan_reserve.restype = i32
+    if hasattr(L, "gvtm_synthesize_events_packed_host"):
+        L.gvtm_events_packed_layout.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
+        L.gvtm_events_packed_layout.restype = sz
+        L.gvtm_synthesize_events_packed_host.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp]
+        L.gvtm_synthesize_events_packed_host.restype = i32
+        L.gvtm_synthesize_events_packed_host_pcm16.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
+        L.gvtm_synthesize_events_packed_host_pcm16.restype = i32
     L.gvtm_plan_set_timing.argtypes = [vp, i32]
     L.gvtm_plan_set_timing.restype = i32
     L.gvtm_plan_take_kernel_ms.argtypes = [vp, ctypes.POINTER(i32)]
@@ -266,6 +273,9 @@ def load_library(diagnostics=False):
             L.gvtm_debug_tracks_append.restype = i32
             L.gvtm_debug_carry_rows.argtypes = [vp, vp, vp, vp, sz, sz]
             L.gvtm_debug_carry_rows.restype = i32
+        if hasattr(L, "gvtm_debug_tracks_slice"):
+            L.gvtm_debug_tracks_slice.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
+            L.gvtm_debug_tracks_slice.restype = i32
     _libs[diagnostics] = L
     return L
 
@@ -642,6 +652,69 @@ class Plan:
         """gvtm_plan_reserve: what launches of up to max_frames frames would build on first use, now."""
         self._check(self._lib.gvtm_plan_reserve(self._h, int(max_frames)))
 
+    # ---- event lists in from host memory, packed samples out (a VoicesPlan has them too) ----
+
+    def set_voice_tracks(self, configs):
+        """gvtm_plan_set_voice_tracks: configs[v] is the TrackConfig of voice v (one per voice of the plan)."""
+        configs = list(configs)
+        arr = (TrackConfig * max(len(configs), 1))(*configs)
+        self._check(self._lib.gvtm_plan_set_voice_tracks(self._h, arr, len(configs)))
+
+    @staticmethod
+    def pack_event_lists(utterances):
+        """utterances[b]: the event tables (float64 [E][38] rows, events_from_table) of utterance b's chunks -> (gvtm_event
+        records of every chunk back to back, chunk_offsets int64 [chunks + 1], utt_chunks int64 [B + 1])."""
+        chunks = [np.ascontiguousarray(events_from_table(t)) for u in utterances for t in u]
+        chunk_offsets = np.zeros(len(chunks) + 1, dtype=np.int64)
+        chunk_offsets[1:] = np.cumsum([len(c) for c in chunks])
+        utt_chunks = np.zeros(len(utterances) + 1, dtype=np.int64)
+        utt_chunks[1:] = np.cumsum([len(u) for u in utterances])
+        events = np.concatenate(chunks) if chunks else np.zeros(0, dtype=EVENT_DTYPE)
+        return np.ascontiguousarray(events), chunk_offsets, utt_chunks
+
+    def events_packed_layout(self, events, chunk_offsets, utt_chunks, voice_ids=None):
+        """gvtm_events_packed_layout -> (frame offsets int64 [B + 1], sample offsets int64 [B + 1]): utterance b yields
+        frame_offsets[b + 1] - frame_offsets[b] frames and starts at sample_offsets[b]; the output needs sample_offsets[B]
+        samples."""
+        assert events.dtype == EVENT_DTYPE and events.flags.c_contiguous
+        chunk_offsets = np.ascontiguousarray(chunk_offsets, dtype=np.int64)
+        utt_chunks = np.ascontiguousarray(utt_chunks, dtype=np.int64)
+        batch = utt_chunks.shape[0] - 1
+        frame_offsets, sample_offsets = np.zeros(batch + 1, dtype=np.int64), np.zeros(batch + 1, dtype=np.int64)
+        n = self._lib.gvtm_events_packed_layout(self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks), _ptr(self._ids(voice_ids, batch)),
+                                                batch, _ptr(frame_offsets), _ptr(sample_offsets))
+        if n == ctypes.c_size_t(-1).value:
+            raise GvtmError(1, self._lib.gvtm_last_error().decode())
+        return frame_offsets, sample_offsets
+
+    def synthesize_events_packed_host_into(self, events, chunk_offsets, utt_chunks, out, voice_ids=None, sample_offsets=None,
+                                           frame_offsets=None, frames_out=None, counts=None, maxabs=None, scales=None, drift=None):
+        """The events-packed entries with caller-owned (e.g. page-locked) buffers: gvtm_event records, chunk_offsets int64
+        [chunks + 1], utt_chunks int64 [B + 1]; `out` float32 [capacity] takes the unscaled samples
+        (gvtm_synthesize_events_packed_host), `out` int16 [capacity] the scaled 16-bit ones (.._pcm16); sample_offsets and
+        frame_offsets int64 [B + 1], frames_out float32 [frames][16], counts int64 [B], maxabs and scales float32 [B], drift
+        float64 [B][5] in/out, or None."""
+        assert events.dtype == EVENT_DTYPE and events.flags.c_contiguous
+        assert chunk_offsets.dtype == np.int64 and chunk_offsets.flags.c_contiguous
+        assert utt_chunks.dtype == np.int64 and utt_chunks.flags.c_contiguous and out.flags.c_contiguous and out.ndim == 1
+        batch = utt_chunks.shape[0] - 1
+        ids = self._ids(voice_ids, batch)
+        frames_capacity = 0
+        if frames_out is not None:
+            assert frames_out.dtype == np.float32 and frames_out.flags.c_contiguous and frames_out.shape[-1] == N_PARAM
+            frames_capacity = frames_out.size // N_PARAM
+        if drift is not None:
+            assert drift.dtype == np.float64 and drift.flags.c_contiguous and drift.shape == (batch, 5)
+        if out.dtype == np.int16:
+            self._check(self._lib.gvtm_synthesize_events_packed_host_pcm16(
+                self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks), _ptr(ids), batch, _ptr(out), out.shape[0], _ptr(sample_offsets),
+                _ptr(frame_offsets), _ptr(frames_out), frames_capacity, _ptr(counts), _ptr(maxabs), _ptr(scales), _ptr(drift)))
+        else:
+            assert out.dtype == np.float32 and scales is None
+            self._check(self._lib.gvtm_synthesize_events_packed_host(
+                self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks), _ptr(ids), batch, _ptr(out), out.shape[0], _ptr(sample_offsets),
+                _ptr(frame_offsets), _ptr(frames_out), frames_capacity, _ptr(counts), _ptr(maxabs), _ptr(drift)))
+
     def synthesize_events_device(self, track_config, d_events, d_offsets, batch, max_frames, d_audio, audio_stride,
                                  d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, stream=None):
         """Event lists in, samples out, one launch (gvtm_synthesize_events_device); all pointers are device memory."""
@@ -702,12 +775,6 @@ class VoicesPlan(Plan):
         self._check(self._lib.gvtm_synthesize_voices_device(
             self._h, _ptr(d_params), _ptr(d_frame_counts), _ptr(d_voice_ids), int(max_frames), int(batch), _ptr(d_audio),
             int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(stream)))
-
-    def set_voice_tracks(self, configs):
-        """gvtm_plan_set_voice_tracks: configs[v] is the TrackConfig of voice v (one per voice of the plan)."""
-        configs = list(configs)
-        arr = (TrackConfig * max(len(configs), 1))(*configs)
-        self._check(self._lib.gvtm_plan_set_voice_tracks(self._h, arr, len(configs)))
 
     def generate_tracks_voices_device(self, d_events, d_offsets, d_voice_ids, batch, max_frames, d_params, d_frame_counts=None,
                                       d_drift=None, stream=None):

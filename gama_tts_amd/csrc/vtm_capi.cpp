@@ -135,11 +135,13 @@ struct gvtm_plan {
 	// the layouts never use the set at once): per utterance of the whole batch the frame counts, voice ids, out_counts, maxabs,
 	// scales and the grouping's scratch; padded, the whole batch's staging; packed, two offset tables and three staging sets,
 	// each one allocation that a slice carves into its packed frames, padded frames, padded samples and packed output
-	// (gama_vtm.h: set_bytes), so that what is held is bounded by the slices and not by the batch ...
+	// (gama_vtm.h: set_bytes), so that what is held is bounded by the slices and not by the batch; events-packed, the packed
+	// layout's with the slice's events in the place of its packed frames, and the batch's two chunk tables and drift states ...
 	struct {
 		DeviceBuffer frames, voice_ids, counts, maxabs, scales, groups;
 		DeviceBuffer params, audio, pcm;               // padded
-		DeviceBuffer set[3], frame_offsets, sample_offsets; // packed
+		DeviceBuffer set[3], frame_offsets, sample_offsets; // packed, events-packed
+		DeviceBuffer chunk_offsets, utt_chunks, drift;      // events-packed
 		size_t limit = 0;                       // gvtm_plan_set_staging_limit; 0: none
 		size_t slices = 0, largest_slice = 0;   // of the last packed call that ran
 		size_t staging_bytes() const { return set[0].bytes + set[1].bytes + set[2].bytes; }
@@ -718,6 +720,36 @@ int gvtm_debug_tracks_append(gvtm_plan* plan, const gvtm_event* d_events, const 
 	e = gvtm::launch_tracks_append(args, nullptr);
 	if (e == hipSuccess) e = hipDeviceSynchronize();
 	if (e != hipSuccess) return fail_hip(e, "vtm_tracks_append_kernel");
+	return GVTM_OK;
+}
+
+/* Test hook: the slice variant of the chunk tracks kernel alone, on device buffers of the caller's: a slice of `batch`
+ * utterances of a larger batch.  d_chunk_offsets is the whole batch's table; d_utt_chunks [batch + 1], d_voice_ids, d_drift,
+ * d_frame_counts and d_frame_offsets [batch + 1] point at the slice's first utterance; d_events at the slice's first event,
+ * which is event `event_base` of the batch.  d_params [batch][max_frames][16] takes the padded rows, d_packed (may be
+ * null; d_frame_offsets is then not read) the frames back to back.  Synchronous. */
+int gvtm_debug_tracks_slice(gvtm_plan* plan, const gvtm_event* d_events, int64_t event_base, const int64_t* d_chunk_offsets,
+		const int64_t* d_utt_chunks, const int32_t* d_voice_ids, const int64_t* d_frame_offsets, size_t batch, size_t max_frames, float* d_params,
+		float* d_packed, int32_t* d_frame_counts, gvtm_drift_state* d_drift)
+{
+	if (!plan || !d_events || !d_chunk_offsets || !d_utt_chunks || !d_voice_ids || !d_params || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (d_packed && !d_frame_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_packed needs d_frame_offsets");
+	if ((reinterpret_cast<uintptr_t>(d_params) | reinterpret_cast<uintptr_t>(d_packed)) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params and d_packed must be 16-byte aligned");
+	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
+	DeviceScope scope(plan->device);
+	hipError_t e = scope.status();
+	if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+	gvtm::TrackSliceArgs args{};
+	static_cast<gvtm::TrackChunksArgs&>(args) = plan_track_args(plan, d_events, d_voice_ids, batch, max_frames, d_params, d_frame_counts, d_drift);
+	args.chunk_offsets = d_chunk_offsets;
+	args.utt_chunks = d_utt_chunks;
+	args.event_base = event_base;
+	args.packed = d_packed;
+	args.frame_offsets = d_frame_offsets;
+	e = gvtm::launch_tracks_slice(args, nullptr);
+	if (e == hipSuccess) e = hipDeviceSynchronize();
+	if (e != hipSuccess) return fail_hip(e, "vtm_tracks_slice_kernel");
 	return GVTM_OK;
 }
 
@@ -1312,7 +1344,8 @@ hipError_t reserve_host_groups(gvtm_plan* plan, size_t largest)
 // The slice pipeline of the host entries, three streams deep:
 //     input(i + 1) on the H2D stream  ||  work(i) on the compute stream  ||  output(i - 1) on the copy stream
 // A layout gives the three as callables that queue slice i's part on the stream they are handed (input and output: one
-// copy, a hipError_t; work: kernels, a GVTM_* status with its message set), and two numbers.
+// copy, a hipError_t -- the events-packed layout's input also launches the tracks kernel behind its copy, its output may be
+// two copies; work: kernels, a GVTM_* status with its message set), and two numbers.
 // trail: slice i's output is queued behind the work of slice i + trail, or of the last slice.  With pageable host memory a
 // device-to-host copy blocks the calling thread until its slice is done, so no output is queued before the kernels that may
 // run beside it: trail = n_slices where the whole batch is staged on the device; 1, the least, where sets rotate, which
@@ -2196,24 +2229,116 @@ struct PackedJob {
 	float* scales;    // pcm only
 };
 
-// utterances [lo, hi) in one staging set: its longest utterance, the rows' length and the bytes of the header's formula
+// utterances [lo, hi) in one staging set: its longest utterance, the rows' length and the bytes of the header's formula.
+// The set, carved in this order: the slice's input (packed frames; events-packed: its events, rounded up to 64 bytes),
+// padded frames, padded samples, packed output and (events-packed with frames_out) the packed frames that go back
 struct PackedSlice {
-	size_t lo, hi, max_frames, stride, in_bytes, rows_bytes, audio_bytes, out_bytes;
-	size_t bytes() const { return in_bytes + rows_bytes + audio_bytes + out_bytes; }
+	size_t lo, hi, max_frames, stride, in_bytes, rows_bytes, audio_bytes, out_bytes, frames_bytes;
+	size_t bytes() const { return in_bytes + rows_bytes + audio_bytes + out_bytes + frames_bytes; }
+	float* rows(unsigned char* set) const { return reinterpret_cast<float*>(set + in_bytes); }
+	float* audio(unsigned char* set) const { return reinterpret_cast<float*>(set + in_bytes + rows_bytes); }
+	unsigned char* out(unsigned char* set) const { return set + in_bytes + rows_bytes + audio_bytes; }
+	float* frames(unsigned char* set) const { return reinterpret_cast<float*>(set + in_bytes + rows_bytes + audio_bytes + out_bytes); }
 };
 
-PackedSlice packed_slice(const gvtm_plan* plan, const PackedJob& j, const std::vector<int64_t>& offsets, size_t lo, size_t hi, size_t max_frames)
+// the part of a set every packed layout has (in_bytes and frames_bytes are the layout's to add); width: bytes per sample out
+PackedSlice packed_slice(const gvtm_plan* plan, size_t width, const std::vector<int64_t>& offsets, size_t lo, size_t hi, size_t max_frames)
 {
 	PackedSlice s{};
 	s.lo = lo, s.hi = hi, s.max_frames = max_frames;
 	// (the capacity, not the count of max_frames frames: a shorter utterance that hits the flush overrun is longer)
 	s.stride = round_up_packed(gvtm_voices_output_capacity(plan, max_frames));
 	const size_t n = hi - lo;
-	s.in_bytes = sizeof(float) * GVTM_N_PARAM * static_cast<size_t>(j.frame_offsets[hi] - j.frame_offsets[lo]);
 	s.rows_bytes = sizeof(float) * GVTM_N_PARAM * n * max_frames;
 	s.audio_bytes = sizeof(float) * n * s.stride;
-	s.out_bytes = (j.pcm ? sizeof(int16_t) : sizeof(float)) * static_cast<size_t>(offsets[hi] - offsets[lo]);
+	s.out_bytes = width * static_cast<size_t>(offsets[hi] - offsets[lo]);
 	return s;
+}
+
+// The slices of a packed batch, on the host, before any device work: utterances in the caller's order, a slice closed when
+// the next utterance would exceed one machine-full or (with a limit) a third of the limit.  slice_of(lo, hi, max_frames):
+// the layout's accounting of utterances [lo, hi).  longest: the most frames any utterance has.
+template <typename SliceOf>
+int cut_slices(const gvtm_plan* plan, const int64_t* frame_offsets, size_t batch, size_t machine, SliceOf slice_of, std::vector<PackedSlice>& slices, size_t& longest)
+{
+	const size_t limit = plan->host.limit, set_limit = limit / 3;
+	longest = 0;
+	for (size_t lo = 0; lo < batch;) {
+		size_t max_frames = static_cast<size_t>(frame_offsets[lo + 1] - frame_offsets[lo]);
+		PackedSlice s = slice_of(lo, lo + 1, max_frames);
+		if (limit && s.bytes() > set_limit) {
+			return fail(GVTM_ERR_OUT_OF_MEMORY, "utterance " + std::to_string(lo) + " needs a staging set of " + std::to_string(s.bytes()) +
+					" bytes, three of them " + std::to_string(3 * s.bytes()) + "; the staging limit is " + std::to_string(limit));
+		}
+		for (size_t hi = lo + 2; hi <= batch && hi - lo <= machine; ++hi) {
+			const size_t f = std::max(max_frames, static_cast<size_t>(frame_offsets[hi] - frame_offsets[hi - 1]));
+			const PackedSlice wider = slice_of(lo, hi, f);
+			if (limit && wider.bytes() > set_limit) break;
+			s = wider, max_frames = f;
+		}
+		longest = std::max(longest, s.max_frames);
+		slices.push_back(s);
+		lo = s.hi;
+	}
+	return GVTM_OK;
+}
+
+// What every packed layout holds on the device before its first slice: the staging sets, the batch's small arrays (the two
+// offset tables and the voice ids uploaded), the grouping's scratch and, for the longest utterance, the noise table
+int stage_packed_batch(gvtm_plan* plan, const std::vector<PackedSlice>& slices, size_t longest, size_t batch, const int64_t* frame_offsets,
+		const std::vector<int64_t>& offsets, const int32_t* voice_ids, bool pcm)
+{
+	auto& sc = plan->host;
+	const bool voices = voice_ids != nullptr;
+	const size_t limit = sc.limit, set_limit = limit / 3;
+	const size_t n_sets = std::min<size_t>(3, slices.size());
+	size_t set_bytes = 16, largest = 0;
+	for (const PackedSlice& s : slices) set_bytes = std::max(set_bytes, s.bytes()), largest = std::max(largest, s.hi - s.lo);
+	hipError_t e;
+	// (sets only grow; under a limit none may stay larger than its third)
+	if (limit && std::max({sc.set[0].bytes, sc.set[1].bytes, sc.set[2].bytes}) > set_limit) plan->host.release_sets();
+	for (size_t q = 0; q < n_sets; ++q) {
+		if ((e = sc.set[q].ensure(set_bytes)) != hipSuccess) return e == hipErrorOutOfMemory ? fail(GVTM_ERR_OUT_OF_MEMORY, "hipMalloc staging set: out of memory") : fail_hip(e, "hipMalloc staging set");
+	}
+	if ((e = sc.frame_offsets.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc frame offsets");
+	if ((e = sc.sample_offsets.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc sample offsets");
+	if ((e = sc.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
+	if ((e = sc.counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
+	if ((e = sc.maxabs.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc maxabs");
+	if (pcm && (e = sc.scales.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc scales");
+	if (voices && (e = sc.voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
+	if (voices && (e = reserve_host_groups(plan, largest)) != hipSuccess) return fail_hip(e, "hipMalloc row map");
+	// the noise table once, for the longest utterance: no slice regrows it in the middle of the pipeline
+	if (const int rc = gvtm_plan_reserve(plan, longest); rc != GVTM_OK) return rc;
+	if ((e = hipMemcpy(sc.frame_offsets.ptr, frame_offsets, sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D frame offsets");
+	if ((e = hipMemcpy(sc.sample_offsets.ptr, offsets.data(), sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D sample offsets");
+	if (voices && (e = hipMemcpy(sc.voice_ids.ptr, voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D voice_ids");
+	sc.slices = slices.size(), sc.largest_slice = largest;
+	return GVTM_OK;
+}
+
+// Behind a slice's padded frames and frame counts: the synthesis launch on its rows, then its samples packed into the set's
+// output region (int16: scaled and rounded on the way)
+int synthesize_and_pack(gvtm_plan* plan, const PackedSlice& s, unsigned char* set, bool pcm, bool voices, int forced_rows, hipStream_t stream)
+{
+	auto& sc = plan->host;
+	const size_t n = s.hi - s.lo;
+	int64_t* const d_counts = sc.counts.as<int64_t>() + s.lo;
+	float* const d_maxabs = sc.maxabs.as<float>() + s.lo;
+	const int rc = launch_synthesis(plan, LaunchRequest{s.rows(set), sc.frames.as<int32_t>() + s.lo, n, s.max_frames, s.audio(set), s.stride, d_counts, d_maxabs, stream,
+			forced_rows, voices, voices ? sc.voice_ids.as<int32_t>() + s.lo : nullptr, &sc.groups});
+	if (rc != GVTM_OK) return rc;
+	const hipError_t e = gvtm::launch_pack_samples(gvtm::PackSamplesArgs{s.audio(set), d_counts, d_maxabs, sc.sample_offsets.as<int64_t>() + s.lo,
+			pcm ? nullptr : reinterpret_cast<float*>(s.out(set)), pcm ? reinterpret_cast<int16_t*>(s.out(set)) : nullptr, pcm ? sc.scales.as<float>() + s.lo : nullptr, n, s.stride},
+			stream);
+	return e == hipSuccess ? GVTM_OK : fail_hip(e, "vtm_pack_samples_kernel launch");
+}
+
+// a slice's packed output leaves: one contiguous range [offset[lo], offset[hi]) of the caller's buffer (`host`: its start)
+hipError_t copy_out_packed(const PackedSlice& s, unsigned char* set, void* host, size_t width, const std::vector<int64_t>& offsets, hipStream_t stream)
+{
+	if (!s.out_bytes) return hipSuccess;
+	return hipMemcpyAsync(static_cast<unsigned char*>(host) + width * static_cast<size_t>(offsets[s.lo]), s.out(set), s.out_bytes, hipMemcpyDeviceToHost, stream);
 }
 
 // The packed layout: utterances in the caller's order, in contiguous slices of at most one machine-full and (with a limit)
@@ -2242,62 +2367,25 @@ int packed_pipeline(gvtm_plan* plan, const PackedJob& j)
 		}
 		if (batch > 0x3fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large");
 
-		// the slices, on the host, before any device work: every slice in the shape of the whole batch, as host_pipeline's
-		size_t machine;
+		// every slice in the shape of the whole batch, as host_pipeline's
+		size_t machine, longest;
 		const gvtm::LaunchShape shape_all = whole_batch_shape(plan, batch, machine);
 		auto& sc = plan->host;
-		const size_t limit = sc.limit, set_limit = limit / 3;
+		const size_t width = j.pcm ? sizeof(int16_t) : sizeof(float);
 		std::vector<PackedSlice> slices;
-		size_t longest = 0;
-		for (size_t lo = 0; lo < batch;) {
-			size_t max_frames = static_cast<size_t>(j.frame_offsets[lo + 1] - j.frame_offsets[lo]);
-			PackedSlice s = packed_slice(plan, j, offsets, lo, lo + 1, max_frames);
-			if (limit && s.bytes() > set_limit) {
-				return fail(GVTM_ERR_OUT_OF_MEMORY, "utterance " + std::to_string(lo) + " needs a staging set of " + std::to_string(s.bytes()) +
-						" bytes, three of them " + std::to_string(3 * s.bytes()) + "; the staging limit is " + std::to_string(limit));
-			}
-			for (size_t hi = lo + 2; hi <= batch && hi - lo <= machine; ++hi) {
-				const size_t f = std::max(max_frames, static_cast<size_t>(j.frame_offsets[hi] - j.frame_offsets[hi - 1]));
-				const PackedSlice wider = packed_slice(plan, j, offsets, lo, hi, f);
-				if (limit && wider.bytes() > set_limit) break;
-				s = wider, max_frames = f;
-			}
-			longest = std::max(longest, s.max_frames);
-			slices.push_back(s);
-			lo = s.hi;
-		}
-		const size_t n_slices = slices.size(), n_sets = std::min<size_t>(3, n_slices);
-		size_t set_bytes = 16, largest = 0;
-		for (const PackedSlice& s : slices) set_bytes = std::max(set_bytes, s.bytes()), largest = std::max(largest, s.hi - s.lo);
+		auto slice_of = [&](size_t lo, size_t hi, size_t max_frames) {
+			PackedSlice s = packed_slice(plan, width, offsets, lo, hi, max_frames);
+			s.in_bytes = sizeof(float) * GVTM_N_PARAM * static_cast<size_t>(j.frame_offsets[hi] - j.frame_offsets[lo]);
+			return s;
+		};
+		if ((rc = cut_slices(plan, j.frame_offsets, batch, machine, slice_of, slices, longest)) != GVTM_OK) return rc;
 
 		DeviceScope scope(plan->device);
-		hipError_t e = scope.status();
+		const hipError_t e = scope.status();
 		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
-		// (sets only grow; under a limit none may stay larger than its third)
-		if (limit && std::max({sc.set[0].bytes, sc.set[1].bytes, sc.set[2].bytes}) > set_limit) plan->host.release_sets();
-		for (size_t q = 0; q < n_sets; ++q) {
-			if ((e = sc.set[q].ensure(set_bytes)) != hipSuccess) return e == hipErrorOutOfMemory ? fail(GVTM_ERR_OUT_OF_MEMORY, "hipMalloc staging set: out of memory") : fail_hip(e, "hipMalloc staging set");
-		}
-		if ((e = sc.frame_offsets.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc frame offsets");
-		if ((e = sc.sample_offsets.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc sample offsets");
-		if ((e = sc.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
-		if ((e = sc.counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
-		if ((e = sc.maxabs.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc maxabs");
-		if (j.pcm && (e = sc.scales.ensure(sizeof(float) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc scales");
-		if (voices && (e = sc.voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
-		if (voices && (e = reserve_host_groups(plan, largest)) != hipSuccess) return fail_hip(e, "hipMalloc row map");
-		// the noise table once, for the longest utterance: no slice regrows it in the middle of the pipeline
-		if ((rc = gvtm_plan_reserve(plan, longest)) != GVTM_OK) return rc;
-		if ((e = hipMemcpy(sc.frame_offsets.ptr, j.frame_offsets, sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D frame offsets");
-		if ((e = hipMemcpy(sc.sample_offsets.ptr, offsets.data(), sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D sample offsets");
-		if (voices && (e = hipMemcpy(sc.voice_ids.ptr, j.voice_ids, sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D voice_ids");
+		if ((rc = stage_packed_batch(plan, slices, longest, batch, j.frame_offsets, offsets, j.voice_ids, j.pcm != nullptr)) != GVTM_OK) return rc;
 		if (j.sample_offsets_out) std::copy(offsets.begin(), offsets.end(), j.sample_offsets_out);
-		sc.slices = n_slices, sc.largest_slice = largest;
 
-		int32_t* const d_frames = sc.frames.as<int32_t>();
-		int64_t* const d_counts = sc.counts.as<int64_t>();
-		float* const d_maxabs = sc.maxabs.as<float>();
-		// slice i's set, carved: packed frames, padded frames, padded samples, packed output
 		auto set_of = [&](size_t i) { return static_cast<unsigned char*>(sc.set[i % 3].ptr); };
 		auto input = [&](size_t i, hipStream_t stream) {
 			const PackedSlice& s = slices[i];
@@ -2305,29 +2393,182 @@ int packed_pipeline(gvtm_plan* plan, const PackedJob& j)
 		};
 		auto work = [&](size_t i, hipStream_t stream) -> int {
 			const PackedSlice& s = slices[i];
-			const size_t n = s.hi - s.lo;
-			float* const d_rows = reinterpret_cast<float*>(set_of(i) + s.in_bytes);
-			float* const d_audio = reinterpret_cast<float*>(set_of(i) + s.in_bytes + s.rows_bytes);
-			unsigned char* const d_out = set_of(i) + s.in_bytes + s.rows_bytes + s.audio_bytes;
-			hipError_t we = gvtm::launch_unpack_frames(gvtm::UnpackFramesArgs{reinterpret_cast<float*>(set_of(i)), sc.frame_offsets.as<int64_t>() + s.lo, d_rows, d_frames + s.lo, n, s.max_frames}, stream);
+			const hipError_t we = gvtm::launch_unpack_frames(gvtm::UnpackFramesArgs{reinterpret_cast<float*>(set_of(i)), sc.frame_offsets.as<int64_t>() + s.lo, s.rows(set_of(i)),
+					sc.frames.as<int32_t>() + s.lo, s.hi - s.lo, s.max_frames}, stream);
 			if (we != hipSuccess) return fail_hip(we, "vtm_unpack_frames_kernel launch");
-			const int wrc = launch_synthesis(plan, LaunchRequest{d_rows, d_frames + s.lo, n, s.max_frames, d_audio, s.stride, d_counts + s.lo, d_maxabs + s.lo, stream,
-					shape_all.forced, voices, voices ? sc.voice_ids.as<int32_t>() + s.lo : nullptr, &sc.groups});
-			if (wrc != GVTM_OK) return wrc;
-			we = gvtm::launch_pack_samples(gvtm::PackSamplesArgs{d_audio, d_counts + s.lo, d_maxabs + s.lo, sc.sample_offsets.as<int64_t>() + s.lo,
-					j.pcm ? nullptr : reinterpret_cast<float*>(d_out), j.pcm ? reinterpret_cast<int16_t*>(d_out) : nullptr, j.pcm ? sc.scales.as<float>() + s.lo : nullptr, n, s.stride},
-					stream);
-			return we == hipSuccess ? GVTM_OK : fail_hip(we, "vtm_pack_samples_kernel launch");
+			return synthesize_and_pack(plan, s, set_of(i), j.pcm != nullptr, voices, shape_all.forced, stream);
 		};
-		// slice i's packed output leaves: one contiguous range [offset[lo], offset[hi])
+		auto output = [&](size_t i, hipStream_t stream) {
+			return copy_out_packed(slices[i], set_of(i), j.pcm ? static_cast<void*>(j.pcm) : static_cast<void*>(j.audio), width, offsets, stream);
+		};
+		if ((rc = run_slices(plan, slices.size(), 1, 3, "H2D frames", input, work, output)) != GVTM_OK) return rc;
+		return copy_back_results(plan, batch, j.out_counts, j.maxabs, j.scales);
+	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
+}
+
+// Event lists in, packed samples out: the chunk tables of a batch, all host memory
+struct EventsPackedJob {
+	const gvtm_event* events;
+	const int64_t* chunk_offsets; // [n_chunks + 1]
+	const int64_t* utt_chunks;    // [batch + 1]
+	const int32_t* voice_ids;     // null: the plan's one voice through the single-voice launch (the tracks kernel gets zeros)
+	size_t batch;
+	float* audio;
+	int16_t* pcm;
+	bool to_pcm;
+	size_t capacity;
+	int64_t* sample_offsets_out;
+	int64_t* frame_offsets_out;
+	float* frames_out;            // packed frames [frame_offsets[batch]][16], or null
+	size_t frames_capacity;       // in frames
+	int64_t* out_counts;
+	float* maxabs;
+	float* scales;                // pcm only
+	gvtm_drift_state* drift;      // [batch] in/out, or null
+};
+
+// The tables of an events-packed batch, checked in the order the header lists the refusals, up to the 31-bit counter; on
+// success frame_offsets is the prefix sum of the frames the host's walk counts per utterance (gvtm::tracks_frame_count over
+// its chunks, as gvtm_stream_push_events) and offsets the packed layout of those (packed_layout)
+int events_packed_layout(const gvtm_plan* plan, const gvtm_event* events, const int64_t* chunk_offsets, const int64_t* utt_chunks, const int32_t* voice_ids,
+		size_t batch, std::vector<int64_t>& frame_offsets, std::vector<int64_t>& offsets)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "gvtm_synthesize_events_packed_host: the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
+	frame_offsets.assign(batch + 1, 0);
+	offsets.assign(batch + 1, 0);
+	if (batch == 0) return GVTM_OK;
+	if (!chunk_offsets || !utt_chunks) return fail(GVTM_ERR_INVALID_ARGUMENT, "null chunk_offsets or utt_chunks");
+	// (read before the table is judged, but only to tell whether there are chunks: nothing is indexed with it yet)
+	if (utt_chunks[batch] > 0 && !events) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events while chunks are present");
+	if (utt_chunks[0] != 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "utt_chunks must start at 0 and not decrease");
+	for (size_t b = 0; b < batch; ++b) {
+		if (utt_chunks[b + 1] < utt_chunks[b]) return fail(GVTM_ERR_INVALID_ARGUMENT, "utt_chunks must start at 0 and not decrease");
+	}
+	const size_t n_chunks = static_cast<size_t>(utt_chunks[batch]);
+	if (chunk_offsets[0] != 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "chunk_offsets must start at 0 and not decrease");
+	for (size_t c = 0; c < n_chunks; ++c) {
+		if (chunk_offsets[c + 1] < chunk_offsets[c]) return fail(GVTM_ERR_INVALID_ARGUMENT, "chunk_offsets must start at 0 and not decrease");
+	}
+	const int cp = plan->voice_tracks[0].control_period; // (every voice's is the plan's: gvtm_plan_set_voice_tracks)
+	for (size_t b = 0; b < batch; ++b) {
+		size_t frames = 0;
+		for (int64_t c = utt_chunks[b]; c < utt_chunks[b + 1]; ++c) {
+			frames += gvtm::tracks_frame_count(cp, events + chunk_offsets[c], static_cast<size_t>(chunk_offsets[c + 1] - chunk_offsets[c]));
+		}
+		frame_offsets[b + 1] = frame_offsets[b] + static_cast<int64_t>(frames);
+	}
+	// the ids and the 31-bit counter, as the packed entry checks them
+	return packed_layout(plan, frame_offsets.data(), voice_ids, batch, offsets);
+}
+
+// The events-packed layout: the packed layout with a slice's events in the place of its packed frames and the tracks kernel
+// in the place of the unpack pass:
+//     H2D events + tracks(i + 1)  ||  synthesis + pack(i)  ||  D2H packed output [+ packed frames](i - 1)
+// The events of a slice are one contiguous range of the caller's; the two chunk tables, the ids and the drift states are the
+// batch's, uploaded once and indexed per slice.
+int events_packed_pipeline(gvtm_plan* plan, const EventsPackedJob& j)
+{
+	std::vector<int64_t> frame_offsets, offsets;
+	try {
+		int rc = events_packed_layout(plan, j.events, j.chunk_offsets, j.utt_chunks, j.voice_ids, j.batch, frame_offsets, offsets);
+		if (rc != GVTM_OK) return rc;
+		const size_t batch = j.batch;
+		const bool voices = j.voice_ids != nullptr, pcm = j.to_pcm;
+		if (batch != 0) {
+			if (pcm ? !j.pcm : !j.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, pcm ? "null pcm buffer" : "null audio buffer");
+			if (j.capacity < static_cast<size_t>(offsets[batch])) {
+				return fail(GVTM_ERR_INVALID_ARGUMENT, "capacity " + std::to_string(j.capacity) + " below gvtm_events_packed_layout (" + std::to_string(offsets[batch]) + " samples)");
+			}
+			if (j.frames_out && j.frames_capacity < static_cast<size_t>(frame_offsets[batch])) {
+				return fail(GVTM_ERR_INVALID_ARGUMENT, "frames_capacity " + std::to_string(j.frames_capacity) + " below the layout's " + std::to_string(frame_offsets[batch]) + " frames");
+			}
+		}
+		if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
+		if (batch == 0) {
+			if (j.sample_offsets_out) j.sample_offsets_out[0] = 0;
+			if (j.frame_offsets_out) j.frame_offsets_out[0] = 0;
+			return GVTM_OK;
+		}
+		if (batch > 0x3fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large");
+
+		size_t machine, longest;
+		const gvtm::LaunchShape shape_all = whole_batch_shape(plan, batch, machine);
+		auto& sc = plan->host;
+		const size_t width = pcm ? sizeof(int16_t) : sizeof(float);
+		const size_t n_chunks = static_cast<size_t>(j.utt_chunks[batch]);
+		// utterance b's first event, batch-wide (b = batch: the end of the last one's)
+		auto event_of = [&](size_t b) { return static_cast<size_t>(j.chunk_offsets[j.utt_chunks[b]]); };
+		std::vector<PackedSlice> slices;
+		auto slice_of = [&](size_t lo, size_t hi, size_t max_frames) {
+			PackedSlice s = packed_slice(plan, width, offsets, lo, hi, max_frames);
+			// (the rows behind the events are stored 16 bytes at a time)
+			s.in_bytes = (sizeof(gvtm_event) * (event_of(hi) - event_of(lo)) + 63) / 64 * 64;
+			if (j.frames_out) s.frames_bytes = sizeof(float) * GVTM_N_PARAM * static_cast<size_t>(frame_offsets[hi] - frame_offsets[lo]);
+			return s;
+		};
+		if ((rc = cut_slices(plan, frame_offsets.data(), batch, machine, slice_of, slices, longest)) != GVTM_OK) return rc;
+
+		DeviceScope scope(plan->device);
+		hipError_t e = scope.status();
+		if (e != hipSuccess) return fail_hip(e, "hipSetDevice");
+		if ((rc = stage_packed_batch(plan, slices, longest, batch, frame_offsets.data(), offsets, j.voice_ids, pcm)) != GVTM_OK) return rc;
+		if ((e = sc.chunk_offsets.ensure(sizeof(int64_t) * (n_chunks + 1))) != hipSuccess) return fail_hip(e, "hipMalloc chunk offsets");
+		if ((e = sc.utt_chunks.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc utterance chunks");
+		if ((e = hipMemcpy(sc.chunk_offsets.ptr, j.chunk_offsets, sizeof(int64_t) * (n_chunks + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D chunk offsets");
+		if ((e = hipMemcpy(sc.utt_chunks.ptr, j.utt_chunks, sizeof(int64_t) * (batch + 1), hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D utterance chunks");
+		if (!voices) { // the tracks kernel still reads an id per utterance: the one voice's
+			if ((e = sc.voice_ids.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc voice ids");
+			const std::vector<int32_t> zeros(batch, 0);
+			if ((e = hipMemcpy(sc.voice_ids.ptr, zeros.data(), sizeof(int32_t) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D voice_ids");
+		}
+		if (j.drift) {
+			if ((e = sc.drift.ensure(sizeof(gvtm_drift_state) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc drift states");
+			if ((e = hipMemcpy(sc.drift.ptr, j.drift, sizeof(gvtm_drift_state) * batch, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "H2D drift states");
+		}
+		if (j.sample_offsets_out) std::copy(offsets.begin(), offsets.end(), j.sample_offsets_out);
+		if (j.frame_offsets_out) std::copy(frame_offsets.begin(), frame_offsets.end(), j.frame_offsets_out);
+
+		auto set_of = [&](size_t i) { return static_cast<unsigned char*>(sc.set[i % 3].ptr); };
+		// slice i's events go up and its frames are generated behind them on the H2D stream: the walk is a chain of dependent
+		// steps (as long as the slice's longest list, however few the utterances) that one wavefront per two utterances runs, so it
+		// runs beside the synthesis kernels of the slice before instead of in front of its own
+		auto input = [&](size_t i, hipStream_t stream) {
+			const PackedSlice& s = slices[i];
+			const size_t first = event_of(s.lo), n_events = event_of(s.hi) - first;
+			const hipError_t ie = n_events ? hipMemcpyAsync(set_of(i), j.events + first, sizeof(gvtm_event) * n_events, hipMemcpyHostToDevice, stream) : hipSuccess;
+			if (ie != hipSuccess) return ie;
+			gvtm::TrackSliceArgs ta{};
+			static_cast<gvtm::TrackChunksArgs&>(ta) = plan_track_args(plan, reinterpret_cast<const gvtm_event*>(set_of(i)), sc.voice_ids.as<int32_t>() + s.lo, s.hi - s.lo,
+					s.max_frames, s.rows(set_of(i)), sc.frames.as<int32_t>() + s.lo, j.drift ? sc.drift.as<gvtm_drift_state>() + s.lo : nullptr);
+			ta.chunk_offsets = sc.chunk_offsets.as<int64_t>();
+			ta.utt_chunks = sc.utt_chunks.as<int64_t>() + s.lo;
+			ta.event_base = static_cast<int64_t>(first);
+			ta.packed = j.frames_out ? s.frames(set_of(i)) : nullptr;
+			ta.frame_offsets = sc.frame_offsets.as<int64_t>() + s.lo;
+			return gvtm::launch_tracks_slice(ta, stream);
+		};
+		auto work = [&](size_t i, hipStream_t stream) -> int {
+			return synthesize_and_pack(plan, slices[i], set_of(i), pcm, voices, shape_all.forced, stream);
+		};
 		auto output = [&](size_t i, hipStream_t stream) {
 			const PackedSlice& s = slices[i];
-			unsigned char* const host = j.pcm ? reinterpret_cast<unsigned char*>(j.pcm) : reinterpret_cast<unsigned char*>(j.audio);
-			unsigned char* const d_out = set_of(i) + s.in_bytes + s.rows_bytes + s.audio_bytes;
-			return s.out_bytes ? hipMemcpyAsync(host + (j.pcm ? sizeof(int16_t) : sizeof(float)) * static_cast<size_t>(offsets[s.lo]), d_out, s.out_bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+			const hipError_t oe = copy_out_packed(s, set_of(i), pcm ? static_cast<void*>(j.pcm) : static_cast<void*>(j.audio), width, offsets, stream);
+			if (oe != hipSuccess || !s.frames_bytes) return oe;
+			return hipMemcpyAsync(j.frames_out + GVTM_N_PARAM * static_cast<size_t>(frame_offsets[s.lo]), s.frames(set_of(i)), s.frames_bytes, hipMemcpyDeviceToHost, stream);
 		};
-		if ((rc = run_slices(plan, n_slices, 1, 3, "H2D frames", input, work, output)) != GVTM_OK) return rc;
-		return copy_back_results(plan, batch, j.out_counts, j.maxabs, j.scales);
+		if ((rc = run_slices(plan, slices.size(), 1, 3, "H2D events / track generation launch", input, work, output)) != GVTM_OK) return rc;
+		if ((rc = copy_back_results(plan, batch, j.out_counts, j.maxabs, j.scales)) != GVTM_OK) return rc;
+		if (j.drift && (e = hipMemcpy(j.drift, sc.drift.ptr, sizeof(gvtm_drift_state) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H drift states");
+		// what the tracks kernel counted against what the layout was built on
+		std::vector<int32_t> counted(batch, 0);
+		if ((e = hipMemcpy(counted.data(), sc.frames.ptr, sizeof(int32_t) * batch, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "D2H frame counts");
+		for (size_t b = 0; b < batch; ++b) {
+			if (static_cast<int64_t>(counted[b]) != frame_offsets[b + 1] - frame_offsets[b]) return fail(GVTM_ERR_HIP, "internal error: the device's frame count differs from the host's");
+		}
+		return GVTM_OK;
 	} catch (const std::bad_alloc&) {
 		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
 	}
@@ -2360,6 +2601,37 @@ int gvtm_synthesize_packed_host_pcm16(gvtm_plan* plan, const float* frames, cons
 		int16_t* pcm, size_t pcm_capacity, int64_t* sample_offsets_out, int64_t* out_counts, float* maxabs, float* scales)
 {
 	return packed_pipeline(plan, PackedJob{frames, frame_offsets, voice_ids, batch, nullptr, pcm, true, pcm_capacity, sample_offsets_out, out_counts, maxabs, scales});
+}
+
+size_t gvtm_events_packed_layout(const gvtm_plan* plan, const gvtm_event* events, const int64_t* chunk_offsets, const int64_t* utt_chunks,
+		const int32_t* voice_ids, size_t batch, int64_t* frame_offsets_out, int64_t* sample_offsets_out)
+{
+	try {
+		std::vector<int64_t> frame_offsets, offsets;
+		if (events_packed_layout(plan, events, chunk_offsets, utt_chunks, voice_ids, batch, frame_offsets, offsets) != GVTM_OK) return static_cast<size_t>(-1);
+		if (frame_offsets_out) std::copy(frame_offsets.begin(), frame_offsets.end(), frame_offsets_out);
+		if (sample_offsets_out) std::copy(offsets.begin(), offsets.end(), sample_offsets_out);
+		return static_cast<size_t>(offsets[batch]);
+	} catch (const std::bad_alloc&) {
+		fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+		return static_cast<size_t>(-1);
+	}
+}
+
+int gvtm_synthesize_events_packed_host(gvtm_plan* plan, const gvtm_event* events, const int64_t* chunk_offsets, const int64_t* utt_chunks,
+		const int32_t* voice_ids, size_t batch, float* audio, size_t audio_capacity, int64_t* sample_offsets_out, int64_t* frame_offsets_out,
+		float* frames_out, size_t frames_capacity, int64_t* out_counts, float* maxabs, gvtm_drift_state* drift)
+{
+	return events_packed_pipeline(plan, EventsPackedJob{events, chunk_offsets, utt_chunks, voice_ids, batch, audio, nullptr, false, audio_capacity, sample_offsets_out,
+			frame_offsets_out, frames_out, frames_capacity, out_counts, maxabs, nullptr, drift});
+}
+
+int gvtm_synthesize_events_packed_host_pcm16(gvtm_plan* plan, const gvtm_event* events, const int64_t* chunk_offsets, const int64_t* utt_chunks,
+		const int32_t* voice_ids, size_t batch, int16_t* pcm, size_t pcm_capacity, int64_t* sample_offsets_out, int64_t* frame_offsets_out,
+		float* frames_out, size_t frames_capacity, int64_t* out_counts, float* maxabs, float* scales, gvtm_drift_state* drift)
+{
+	return events_packed_pipeline(plan, EventsPackedJob{events, chunk_offsets, utt_chunks, voice_ids, batch, nullptr, pcm, true, pcm_capacity, sample_offsets_out,
+			frame_offsets_out, frames_out, frames_capacity, out_counts, maxabs, scales, drift});
 }
 
 int gvtm_plan_set_staging_limit(gvtm_plan* plan, size_t bytes)

@@ -605,20 +605,40 @@ const char* design_tracks(const gvtm_track_config& c, TrackConstants& k)
 	return "";
 }
 
-size_t tracks_frame_count(int control_period, const gvtm_event* events, size_t n_events)
+namespace {
+
+// PERIOD: the control period as a constant, or 0: `period`
+template <int PERIOD>
+size_t walk_frame_count(int period, const gvtm_event* events, size_t n_events)
 {
-	// the control-period loop of EventList::generateOutput (EventList.cpp:985-1032) without the arithmetic
-	if (n_events < 2) return 0;
-	size_t target = 1, n = 0;
+	const long long cp = PERIOD ? PERIOD : period;
+	size_t n = 0;
 	long long now = 0;
-	while (target < n_events) {
-		++n;
-		now += control_period;
-		if (now >= events[target].time_ms) {
-			if (++target == n_events) break;
-		}
+	for (size_t target = 1; target < n_events; ++target) {
+		const long long gap = events[target].time_ms - now;
+		const long long frames = gap > 0 ? (gap + cp - 1) / cp : 1;
+		n += static_cast<size_t>(frames);
+		now += frames * cp;
 	}
 	return n;
+}
+
+} // namespace
+
+size_t tracks_frame_count(int control_period, const gvtm_event* events, size_t n_events)
+{
+	// the control-period loop of EventList::generateOutput (EventList.cpp:985-1032) without the arithmetic, an event at a
+	// time: the loop pushes a frame and adds a period until `now` has reached the target's time -- once at least, and one
+	// target per frame -- so a target takes max(1, ceil((time - now) / period)) frames (the host entries that lay a batch
+	// out from its lists walk every list of it: per event, not per frame)
+	if (n_events < 2 || control_period <= 0) return 0;
+	switch (control_period) { // (the periods a configuration may have, each with a constant divisor)
+	case 1: return walk_frame_count<1>(1, events, n_events);
+	case 2: return walk_frame_count<2>(2, events, n_events);
+	case 3: return walk_frame_count<3>(3, events, n_events);
+	case 4: return walk_frame_count<4>(4, events, n_events);
+	default: return walk_frame_count<0>(control_period, events, n_events);
+	}
 }
 
 } // namespace gvtm

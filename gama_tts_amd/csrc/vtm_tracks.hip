@@ -292,11 +292,14 @@ __global__ __launch_bounds__(64) void vtm_tracks_voices_kernel(const TrackVoices
 // The per-list walk is a copy of tracks_row's and not shared with it, so that the two kernels above keep their code.
 // APPEND (Args = TrackAppendArgs): the frames leave behind the row_start[utt] rows the utterance's block already holds,
 // and `room` rows are left for them; the ring, its place (n counts this call's frames) and the flushes are the same.
+// SLICE (Args = TrackSliceArgs): the events are addressed from the slice's first one, and every flush may store the ring
+// a second time into the packed frames (vtm_tracks.hpp).
 template <int LW, typename Args>
 __device__ __forceinline__ void tracks_chunks_row(const Args& a, size_t utt, int l, float (*ring)[16], unsigned char (*ahead)[32])
 {
 #pragma clang fp contract(off)
 	constexpr bool APPEND = std::is_same_v<Args, TrackAppendArgs>;
+	constexpr bool SLICE = std::is_same_v<Args, TrackSliceArgs>;
 	const int j = l & 15; // parameter
 	const int32_t voice = a.voice_ids[utt];
 	if (voice < 0 || voice >= a.n_voices) { // (as tracks_row: nothing of the utterance is read or written)
@@ -318,10 +321,29 @@ __device__ __forceinline__ void tracks_chunks_row(const Args& a, size_t utt, int
 	gvtm_drift_state ds = {0.7892347, 0.0, 0.0, 0.0, 0.0}; // DriftGenerator.cpp:28, :40
 	if (j == 0 && a.drift) ds = a.drift[utt];
 	size_t n = 0; // frames of the utterance so far
+	// SLICE: the second, packed copy of the frames and the frames it may take
+	[[maybe_unused]] float* packed_out = nullptr;
+	[[maybe_unused]] size_t packed_room = 0;
+	if constexpr (SLICE) {
+		if (a.packed) {
+			const int64_t first = a.frame_offsets[utt], extent = a.frame_offsets[utt + 1] - first;
+			packed_out = a.packed + static_cast<size_t>(first - a.frame_offsets[0]) * 16; // (a frame is 64 bytes: the float4 stores stay aligned)
+			packed_room = extent > 0 ? static_cast<size_t>(extent) : 0;
+		}
+	}
 
 	auto flush = [&](size_t first, size_t end) { // (as tracks_row's)
-		if (end > room) end = room;
 		const float4* src = reinterpret_cast<const float4*>(&ring[0][0]);
+		if constexpr (SLICE) {
+			if (packed_out) {
+				const size_t pend = end < packed_room ? end : packed_room;
+				float4* pdst = reinterpret_cast<float4*>(packed_out + first * 16);
+				for (int q = l; q < kRingFrames * 4; q += LW) {
+					if (first + static_cast<size_t>(q >> 2) < pend) pdst[q] = src[q];
+				}
+			}
+		}
+		if (end > room) end = room;
 		float4* dst = reinterpret_cast<float4*>(out + first * 16);
 		for (int q = l; q < kRingFrames * 4; q += LW) {
 			if (first + static_cast<size_t>(q >> 2) < end) dst[q] = src[q];
@@ -330,7 +352,9 @@ __device__ __forceinline__ void tracks_chunks_row(const Args& a, size_t utt, int
 
 	const int64_t chunk_end = a.utt_chunks[utt + 1];
 	for (int64_t chunk = a.utt_chunks[utt]; chunk < chunk_end; ++chunk) {
-		const gvtm_event* ev = a.events + a.chunk_offsets[chunk];
+		int64_t first_event = a.chunk_offsets[chunk];
+		if constexpr (SLICE) first_event -= a.event_base; // (the table counts from the batch's first event, `events` from the slice's)
+		const gvtm_event* ev = a.events + first_event;
 		const int64_t n_events = a.chunk_offsets[chunk + 1] - a.chunk_offsets[chunk];
 		if (n_events < 2) continue; // EventList.cpp:932-934: no frames, and the drift generator is not asked
 		const bool tabled = n_events <= kTableEvents;
@@ -494,6 +518,18 @@ __global__ __launch_bounds__(64) void vtm_tracks_append_kernel(const TrackAppend
 	if (utt < a.batch) tracks_chunks_row<64 / ROWS>(a, utt, l, ring[row], ahead[row]);
 }
 
+// the slice variant of the chunk kernel (a kernel of its own, so that the four above keep their arguments and their code)
+template <int ROWS>
+__global__ __launch_bounds__(64) void vtm_tracks_slice_kernel(const TrackSliceArgs a)
+{
+	__shared__ __attribute__((aligned(16))) float ring[ROWS][kRingFrames][16];
+	__shared__ unsigned char ahead[ROWS][kTableEvents + 1][32]; // (as vtm_tracks_chunks_kernel's)
+	const int tid = threadIdx.x;
+	const int row = tid / (64 / ROWS), l = tid % (64 / ROWS);
+	const size_t utt = static_cast<size_t>(blockIdx.x) * ROWS + row;
+	if (utt < a.batch) tracks_chunks_row<64 / ROWS>(a, utt, l, ring[row], ahead[row]);
+}
+
 // CarryArgs: one wavefront per utterance, lane q one float4 of the rows that move (kCarryMaxRows rows of four).  Every lane
 // has its float4 in a register before any lane stores (one load instruction, then one store instruction, of the one
 // wavefront), so the rows may move onto themselves.
@@ -546,6 +582,14 @@ hipError_t launch_tracks_append(const TrackAppendArgs& args, hipStream_t stream)
 	if (args.batch == 0) return hipSuccess;
 	constexpr int kRows = GVTM_TRACK_ROWS; // (as launch_tracks)
 	hipLaunchKernelGGL(vtm_tracks_append_kernel<kRows>, dim3(static_cast<unsigned>((args.batch + kRows - 1) / kRows)), dim3(64), 0, stream, args);
+	return hipGetLastError();
+}
+
+hipError_t launch_tracks_slice(const TrackSliceArgs& args, hipStream_t stream)
+{
+	if (args.batch == 0) return hipSuccess;
+	constexpr int kRows = GVTM_TRACK_ROWS; // (as launch_tracks)
+	hipLaunchKernelGGL(vtm_tracks_slice_kernel<kRows>, dim3(static_cast<unsigned>((args.batch + kRows - 1) / kRows)), dim3(64), 0, stream, args);
 	return hipGetLastError();
 }
 

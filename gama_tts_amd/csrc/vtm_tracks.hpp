@@ -58,6 +58,21 @@ struct TrackAppendArgs : TrackChunksArgs {
 
 hipError_t launch_tracks_append(const TrackAppendArgs& args, hipStream_t stream);
 
+// The chunk kernel on a slice of a batch whose tables are the batch's (the events-packed host entries): chunk_offsets is
+// the whole batch's table and holds batch-wide event indices, utt_chunks, voice_ids, drift, frame_counts and frame_offsets
+// point at the slice's first utterance, and `events` at the slice's first event, which is event `event_base` of the batch:
+// chunk c's events start at events + (chunk_offsets[c] - event_base).  With `packed` the frames leave a second time, back
+// to back: utterance b's at packed + (frame_offsets[b] - frame_offsets[0]) * 16, by the same 16-byte stores at every flush
+// of the ring, and none at or beyond frame frame_offsets[b + 1] - frame_offsets[b] of the utterance (frame_offsets is not
+// read without `packed`).  Everything else as TrackChunksArgs.
+struct TrackSliceArgs : TrackChunksArgs {
+	int64_t event_base;
+	float* packed;                 // [frames of the slice][16], 16-byte aligned, or null
+	const int64_t* frame_offsets;  // [batch + 1], device memory
+};
+
+hipError_t launch_tracks_slice(const TrackSliceArgs& args, hipStream_t stream);
+
 // What an events-fed stream keeps after a synthesis launch: in utterance b's block of max_frames rows of params, the rows
 // [done[b], held[b]) move to the front.  At most kCarryMaxRows rows move (a stream keeps at most its voice's granule,
 // 12 frames); an utterance with done <= 0, held <= done, held > max_frames or more rows to move is left as it is.

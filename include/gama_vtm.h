@@ -43,6 +43,9 @@
  *   gvtm_generate_tracks_chunks_device / gvtm_synthesize_events_chunks_device
  *                               the same for utterances of several event lists: the loop over the /c chunks of
  *                               Controller::getParametersFromPhoneticString (vtm_control_model/Controller.cpp:141-154)
+ *   gvtm_synthesize_events_packed_host*
+ *                               Controller::synthesizePhoneticStringToFile (vtm_control_model/Controller.cpp:194-200 with
+ *                               :141-154) for a ragged batch: event lists in from host memory, int16 samples out
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
@@ -706,6 +709,79 @@ int gvtm_stream_push_events(gvtm_stream* stream, const gvtm_event* events, const
 int gvtm_stream_get_drift(const gvtm_stream* stream, gvtm_drift_state* states_out /* [batch], host */);
 /* states [batch] (host), or NULL: fresh generators -- the one call that reseeds them */
 int gvtm_stream_set_drift(gvtm_stream* stream, const gvtm_drift_state* states);
+
+/*
+ * Event lists in from host memory, packed samples out: what Controller::synthesizePhoneticStringToFile does for one
+ * utterance (Controller.cpp:194-200: the /c chunks' event lists in, the int16 samples out, and with vtmParamFile the
+ * parameter list it synthesized), for a whole ragged batch in one call.  The packed host entries above ("Ragged batches")
+ * with event lists in the place of frames: the frames are generated on the device and never cross PCIe unless the caller
+ * asks for them, and what is staged on the device is bounded by a slice.  For callers that do not link HIP.
+ *
+ * All arguments are host memory.
+ *   events, chunk_offsets [n_chunks + 1], utt_chunks [batch + 1]
+ *                      the two offset tables of gvtm_generate_tracks_chunks_device; here both must start at 0 and must not
+ *                      decrease; n_chunks = utt_chunks[batch].  The track configurations are the plan's
+ *                      (gvtm_plan_set_voice_tracks, which takes a one-voice plan too).
+ *   voice_ids          [batch], or NULL on a one-voice plan: the synthesis then goes through the single-voice launch, as in
+ *                      the packed entry (so a gvtm_plan_create_model5_float plan takes NULL ids only; the tracks kernel
+ *                      is given zeros)
+ *   frames of utterance b = the sum over its chunks of gvtm_tracks_frame_count (the host walks the lists, as
+ *                      gvtm_stream_push_events does); frame_offsets = their prefix sum; the sample offsets are exactly
+ *                      gvtm_packed_sample_offsets of those frame offsets.  No utterance is cut: there is no max_frames.
+ *   audio / pcm, sample_offsets_out, out_counts, maxabs, scales
+ *                      as gvtm_synthesize_packed_host* returns them: gaps are zeros, nothing beyond offset[batch] is touched
+ *   frame_offsets_out  [batch+1] (may be NULL)
+ *   frames_out         [frame_offsets[batch]][16] float32 (may be NULL), frames_capacity in frames: the frames that were
+ *                      synthesized, packed, in the layout gvtm_synthesize_packed_host takes as input (the reference's
+ *                      vtmParamFile, Controller.cpp:198, `gama_tts tts -p`)
+ *   drift              [batch] in/out as in the device entries; NULL: a fresh generator per utterance, nothing returned
+ *
+ * Contract.  Against gvtm_synthesize_events_chunks_device on the same plan, with the same ids and initial drift states and
+ * max_frames at least the longest utterance: every utterance's samples, sample count, maxabs, frame count and final drift
+ * state are bit for bit that call's, in every precision, for the models 0 to 4 and both classes of model 5, one voice or
+ * several.  The int16 samples and scales are bit for bit those of gvtm_synthesize_packed_host_pcm16 fed frames_out, and
+ * frames_out is bit for bit what gvtm_generate_tracks_chunks_device generates.
+ *
+ * Refused in this order, before any device work, with GVTM_ERR_INVALID_ARGUMENT unless another status is named: a null plan;
+ * a plan without track configurations; a null table; null events while chunks are present; tables that do not start at 0 or
+ * that decrease; the ids, as the packed entry checks them; an utterance whose frames x control_steps does not fit the 31-bit
+ * step counter; a null audio / pcm buffer; a capacity below the layout's (audio_capacity / pcm_capacity, and
+ * frames_capacity when frames_out is given); a design-only plan: GVTM_ERR_NO_DEVICE; batch == 0: GVTM_OK.  A refused call
+ * writes nothing to any output array.
+ *
+ * Slices, as the packed entries': three staging sets deep on the plan's three streams,
+ *   H2D events + tracks kernel(i+1) || synthesis + pack(i) || D2H packed output [+ packed frames](i-1)
+ * (the tracks kernel is queued behind its slice's events on the H2D stream: its walk is as long as the slice's longest list,
+ * and there it runs as the compute units of the slice before come free instead of in front of its own synthesis launch).
+ * The events of a slice are one contiguous range of `events`; the two tables, the ids and the drift states are the batch's,
+ * uploaded once.  A slice of n utterances, the longest of F frames, holds in its set its events (sizeof(gvtm_event) = 296;
+ * the rows behind them are stored 16 bytes at a time), its padded frames, its padded float samples, its packed output and,
+ * with frames_out, its packed frames:
+ *   set_bytes = round_up(296 * events_of_slice, 64) + 64 * n * F + 4 * n * S + w * aligned_samples_of_slice
+ *               (+ 64 * frames_of_slice with frames_out)                    (S and w as for the packed entries)
+ * The sets are the packed entries' own three: gvtm_plan_set_staging_limit and gvtm_plan_packed_stats govern and report
+ * these calls as they do those, slices are closed by the same rule, an utterance that does not fit a set on its own refuses
+ * the call with GVTM_ERR_OUT_OF_MEMORY (the message gives the bytes it needs), and the packed and the events-packed entries
+ * may not overlap each other on one plan.  Synchronous.  After the last slice the frame counts of the device are compared
+ * with the host's; a difference is an internal error (GVTM_ERR_HIP).
+ */
+
+/* The layout alone.  Host only, works on GVTM_DEVICE_NONE plans; the tables are checked as the synthesis entries check them
+ * (up to the 31-bit counter).  Returns the capacity in samples, sample_offsets_out[batch]; (size_t)-1 on a bad argument,
+ * with nothing written. */
+size_t gvtm_events_packed_layout(const gvtm_plan* plan, const gvtm_event* events, const int64_t* chunk_offsets,
+		const int64_t* utt_chunks, const int32_t* voice_ids, size_t batch,
+		int64_t* frame_offsets_out /* [batch+1] or NULL */, int64_t* sample_offsets_out /* [batch+1] or NULL */);
+
+int gvtm_synthesize_events_packed_host(gvtm_plan* plan, const gvtm_event* events, const int64_t* chunk_offsets,
+		const int64_t* utt_chunks, const int32_t* voice_ids, size_t batch, float* audio, size_t audio_capacity,
+		int64_t* sample_offsets_out, int64_t* frame_offsets_out, float* frames_out, size_t frames_capacity,
+		int64_t* out_counts, float* maxabs, gvtm_drift_state* drift);
+/* The same ending as gvtm_synthesize_packed_host_pcm16 ends; scales [batch] may be NULL. */
+int gvtm_synthesize_events_packed_host_pcm16(gvtm_plan* plan, const gvtm_event* events, const int64_t* chunk_offsets,
+		const int64_t* utt_chunks, const int32_t* voice_ids, size_t batch, int16_t* pcm, size_t pcm_capacity,
+		int64_t* sample_offsets_out, int64_t* frame_offsets_out, float* frames_out, size_t frames_capacity,
+		int64_t* out_counts, float* maxabs, float* scales, gvtm_drift_state* drift);
 
 /* Same with host buffers (H2D, kernel, D2H, synchronous). */
 int gvtm_generate_tracks_host(int device, const gvtm_track_config* config, const gvtm_event* events,
