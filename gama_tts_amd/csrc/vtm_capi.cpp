@@ -717,7 +717,7 @@ int gvtm_debug_tracks_append(gvtm_plan* plan, const gvtm_event* d_events, const 
 	args.chunk_offsets = d_chunk_offsets;
 	args.utt_chunks = d_utt_chunks;
 	args.row_start = d_row_start;
-	e = gvtm::launch_tracks_append(args, nullptr);
+	e = gvtm::launch_tracks(args, nullptr);
 	if (e == hipSuccess) e = hipDeviceSynchronize();
 	if (e != hipSuccess) return fail_hip(e, "vtm_tracks_append_kernel");
 	return GVTM_OK;
@@ -747,7 +747,7 @@ int gvtm_debug_tracks_slice(gvtm_plan* plan, const gvtm_event* d_events, int64_t
 	args.event_base = event_base;
 	args.packed = d_packed;
 	args.frame_offsets = d_frame_offsets;
-	e = gvtm::launch_tracks_slice(args, nullptr);
+	e = gvtm::launch_tracks(args, nullptr);
 	if (e == hipSuccess) e = hipDeviceSynchronize();
 	if (e != hipSuccess) return fail_hip(e, "vtm_tracks_slice_kernel");
 	return GVTM_OK;
@@ -1220,8 +1220,8 @@ int launch_voice_tracks(gvtm_plan* plan, const VoiceEvents& lists, size_t batch,
 	gvtm::TrackChunksArgs args = plan_track_args(plan, lists.d_events, lists.d_voice_ids, batch, max_frames, d_params, d_frame_counts, d_drift);
 	(lists.chunked ? args.chunk_offsets : args.event_offsets) = lists.d_offsets;
 	args.utt_chunks = lists.d_utt_chunks; // (null unless chunked)
-	const hipError_t e = lists.chunked ? gvtm::launch_tracks_chunks(args, static_cast<hipStream_t>(hip_stream))
-	                                   : gvtm::launch_tracks_voices(args, static_cast<hipStream_t>(hip_stream));
+	const hipError_t e = lists.chunked ? gvtm::launch_tracks<gvtm::TrackChunksArgs>(args, static_cast<hipStream_t>(hip_stream))
+	                                   : gvtm::launch_tracks<gvtm::TrackVoicesArgs>(args, static_cast<hipStream_t>(hip_stream));
 	if (e != hipSuccess) return fail_hip(e, lists.chunked ? "track generation launch (chunks)" : "track generation launch (voices)");
 	return GVTM_OK;
 }
@@ -2046,7 +2046,7 @@ int stream_append_and_launch(gvtm_stream* s, const gvtm_event* events, const int
 	ta.chunk_offsets = static_cast<const int64_t*>(s->d_chunk_offsets.ptr);
 	ta.utt_chunks = static_cast<const int64_t*>(s->d_utt_chunks.ptr);
 	ta.row_start = static_cast<const int32_t*>(s->d_rows.ptr);
-	if ((e = gvtm::launch_tracks_append(ta, nullptr)) != hipSuccess) return fail_hip(e, "track generation launch (append)");
+	if ((e = gvtm::launch_tracks(ta, nullptr)) != hipSuccess) return fail_hip(e, "track generation launch (append)");
 	*advanced = true;
 	s->feed = kFeedEvents;
 	s->held_rows = have;
@@ -2548,7 +2548,7 @@ int events_packed_pipeline(gvtm_plan* plan, const EventsPackedJob& j)
 			ta.event_base = static_cast<int64_t>(first);
 			ta.packed = j.frames_out ? s.frames(set_of(i)) : nullptr;
 			ta.frame_offsets = sc.frame_offsets.as<int64_t>() + s.lo;
-			return gvtm::launch_tracks_slice(ta, stream);
+			return gvtm::launch_tracks(ta, stream);
 		};
 		auto work = [&](size_t i, hipStream_t stream) -> int {
 			return synthesize_and_pack(plan, slices[i], set_of(i), pcm, voices, shape_all.forced, stream);

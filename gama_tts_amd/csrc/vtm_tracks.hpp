@@ -23,8 +23,6 @@ struct TrackArgs {
 	gvtm_drift_state* drift;       // [batch] in/out, or null (fresh generator per utterance)
 };
 
-hipError_t launch_tracks(const TrackArgs& args, hipStream_t stream);
-
 // A batch that mixes voices: utterance b walks its list with voice_k[voice_ids[b]] (mean and initial pitch, intonation
 // flags, drift set-up and filter); k.control_period, one for the launch, is all that is read of k.  An id outside
 // [0, n_voices) yields frame_counts[b] = 0 and leaves the utterance's frames and drift state untouched.
@@ -33,8 +31,6 @@ struct TrackVoicesArgs : TrackArgs {
 	const int32_t* voice_ids;      // [batch]
 	int32_t n_voices;
 };
-
-hipError_t launch_tracks_voices(const TrackVoicesArgs& args, hipStream_t stream);
 
 // Utterances of several event lists ("chunks": Controller::getParametersFromPhoneticString runs generateOutput() once per
 // /c chunk of the phonetic string, on one parameter list and with one drift generator, Controller.cpp:141-154).  Utterance
@@ -46,8 +42,6 @@ struct TrackChunksArgs : TrackVoicesArgs {
 	const int64_t* utt_chunks;     // [batch + 1], device memory
 };
 
-hipError_t launch_tracks_chunks(const TrackChunksArgs& args, hipStream_t stream);
-
 // The chunk kernel appending (an events-fed gvtm_stream): utterance b's rows [0, row_start[b]) of its block of max_frames
 // rows hold frames of earlier calls, and this call's frames leave behind them, at row row_start[b] + (frame of this call).
 // Nothing is written at or beyond row max_frames (a row_start outside [0, max_frames) writes nothing); frame_counts[b]
@@ -55,8 +49,6 @@ hipError_t launch_tracks_chunks(const TrackChunksArgs& args, hipStream_t stream)
 struct TrackAppendArgs : TrackChunksArgs {
 	const int32_t* row_start;      // [batch], device memory
 };
-
-hipError_t launch_tracks_append(const TrackAppendArgs& args, hipStream_t stream);
 
 // The chunk kernel on a slice of a batch whose tables are the batch's (the events-packed host entries): chunk_offsets is
 // the whole batch's table and holds batch-wide event indices, utt_chunks, voice_ids, drift, frame_counts and frame_offsets
@@ -71,7 +63,10 @@ struct TrackSliceArgs : TrackChunksArgs {
 	const int64_t* frame_offsets;  // [batch + 1], device memory
 };
 
-hipError_t launch_tracks_slice(const TrackSliceArgs& args, hipStream_t stream);
+// One launch for the five argument blocks above (instantiated for each of them in vtm_tracks.hip): ceil(batch / rows per
+// wavefront) workgroups of one wavefront on `stream`; a batch of 0 launches nothing.
+template <typename Args>
+hipError_t launch_tracks(const Args& args, hipStream_t stream);
 
 // What an events-fed stream keeps after a synthesis launch: in utterance b's block of max_frames rows of params, the rows
 // [done[b], held[b]) move to the front.  At most kCarryMaxRows rows move (a stream keeps at most its voice's granule,

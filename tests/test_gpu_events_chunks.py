@@ -1,5 +1,5 @@
 """Utterances of several event lists in one launch (gvtm_generate_tracks_chunks_device,
-gvtm_synthesize_events_chunks_device; vtm_tracks_chunks_kernel).
+gvtm_synthesize_events_chunks_device; vtm_tracks_kernel<TrackChunksArgs>).
 
 The reference builds an utterance from one generateOutput() call per /c chunk of the phonetic string, all on one parameter
 list and with one drift generator running on (Controller.cpp:141-154).  So an utterance's frames must be, bit for bit, the

@@ -1,5 +1,5 @@
 """Event lists in from host memory, packed samples out, on the device (gvtm_synthesize_events_packed_host*,
-vtm_tracks_slice_kernel).
+vtm_tracks_kernel<TrackSliceArgs>).
 
 The kernel alone, through the diagnostics library's hook, on a slice from the middle of a batch's tables: frames, counts and
 drift states against the chained tracks oracle, bit for bit, in the padded rows and in the packed frames, with the SENTINEL

@@ -1,4 +1,4 @@
-"""Streams fed event lists (gvtm_stream_push_events; vtm_tracks_append_kernel, vtm_carry_rows_kernel).
+"""Streams fed event lists (gvtm_stream_push_events; vtm_tracks_kernel<TrackAppendArgs>, vtm_carry_rows_kernel).
 
 A stream that receives its utterances chunk by chunk, as the reference's Controller produces them, generates the frames on
 the device behind the frames it still holds, synthesizes what can be synthesized and moves the rest to the front of its

@@ -3,7 +3,8 @@ the tracks oracle and, where the lists are those of tests/golden/tracks_edges_go
 lists on either side of the LDS table (kTableEvents = 240) in one wavefront (utterances 2k and 2k + 1), columns whose next
 set event lies far away, lists of up to 6,000 events, the 32-frame ring and its flushes against max_frames, times off the
 control-period grid and several events inside one period at control periods 1 to 4, every flag combination with drift
-generators that ran before, a batch of 4,097, and the events entry.
+generators that ran before, a batch of 4,097, the events entry, and the same walk as the voices and the chunks entries
+compile it (per-utterance constants; one list per utterance as one chunk).
 
 Frames are compared as bits (view(uint32)), drift states as bits (view(int64)).  One exception: where the oracle's frame is
 NaN the device's must be NaN, of any sign and payload (0 / 0 and inf - inf give the x86 default NaN, sign bit set, on the
@@ -13,13 +14,16 @@ import os
 import numpy as np
 import pytest
 
+import gama_tts_amd as g
 from gama_tts_amd import capi
 import event_lists
 import oracle
 import tracks_edges_cases as cases
-from device_io import events_chain_and_entry, events_on_device
+from chunk_cases import generate_tracks_chunks
+from device_io import current_stream, events_chain_and_entry, events_on_device, to_device
 from track_cases import product_config
-from voice_cases import male_plan
+from voice_cases import configs, male_plan
+from voice_files import VOICES
 
 pytestmark = pytest.mark.gpu
 
@@ -293,3 +297,57 @@ def test_events_entry_at_the_edges(tables):
     ref = oracle.synthesize(oracle.male_config(44100.0, 1, float_model=1), want)
     assert np.isfinite(ref).all() and n2[-1].item() == ref.size
     assert np.array_equal(a2[-1, : ref.size].cpu().numpy(), ref)
+
+
+def _launch_voices(plan, tabs, ids, max_frames, drift_in):
+    """_launch through gvtm_generate_tracks_voices_device: utterance b under the track configuration of voice ids[b] of
+    `plan`; the counts start out 99, as chunk_cases.generate_tracks_chunks' do."""
+    import torch
+    d_events, d_offsets = events_on_device(tabs)
+    b = len(tabs)
+    buf = torch.full(((b * max_frames + GUARD_FRAMES) * 16,), SENTINEL, dtype=torch.int32, device=d_events.device).view(torch.float32)
+    counts = torch.full((b,), 99, dtype=torch.int32, device=d_events.device)
+    d_ids, drift = to_device(np.asarray(ids, dtype=np.int32), np.ascontiguousarray(drift_in, dtype=np.float64).copy())
+    plan.generate_tracks_voices_device(d_events, d_offsets, d_ids, b, max_frames, buf, counts, drift, current_stream())
+    torch.cuda.synchronize()
+    out = buf.cpu().numpy()
+    return out[: b * max_frames * 16].reshape(b, max_frames, 16), out[b * max_frames * 16:], counts.cpu().numpy(), drift.cpu().numpy()
+
+
+def test_voices_and_chunks_entries_at_the_walk_edges(tables):
+    """The walk's edges through its other two compiles: gvtm_generate_tracks_voices_device and, each list as its
+    utterance's one chunk (utt_chunks = 0..9), gvtm_generate_tracks_chunks_device.  Two voices whose track configurations
+    have every flag the other way round, alternating inside the wavefronts; lists on both sides of the table next to each
+    other and next to a list of one event, a 1,000-event list next to a row whose voice id is outside the table, an empty
+    list, and a batch of 9, whose last workgroup holds one row; generators that ran before; cut at 33 frames (one flush of
+    the ring and one frame) and at 600.  Every row against the oracle under its voice's configuration, the short rows and
+    the row of the bad id untouched, and the two entries bit for bit each other's."""
+    cfgvs = [cases.calls("flags16")[6], cases.calls("flags16")[9]]
+    assert [c[1:5].tolist() for c in cfgvs] == [[0, 1, 1, 0], [1, 0, 0, 1]]
+    plan = g.VoicesPlan(configs(precision=capi.PRECISION_F32, names=VOICES[:2]), 250.0, 0)
+    plan.set_voice_tracks([product_config(c) for c in cfgvs])
+    names = ["b239", "b240", "b241", "e1", "far1000", "flags16", "e0", "b242", "unset_first"]
+    ids = [0, 1, 1, 0, 0, 2, 1, 0, 1]
+    bad, short = 5, (3, 6)
+    tabs = [tables[n] for n in names]
+    assert len(tabs) == 9 and [tabs[b].shape[0] for b in short] == [1, 0]
+    drift0 = _states(len(tabs), 18)
+    caches = [{}, {}]  # per voice: the oracle walks each list once for both buffer lengths and both entries
+    for max_frames in (33, 600):
+        got_v = _launch_voices(plan, tabs, ids, max_frames, drift0)
+        got_c = generate_tracks_chunks(plan, [[t] for t in tabs], ids, max_frames, drift0)
+        for entry, got in (("voices", got_v), ("chunks", got_c)):
+            params, guard, counts, drift = got
+            what = "%s entry, max_frames %d" % (entry, max_frames)
+            for b, v in enumerate(ids):
+                if b == bad:
+                    continue
+                _check_rows(cfgvs[v], tabs[b: b + 1], max_frames, drift0[b: b + 1],
+                            (params[b: b + 1], guard, counts[b: b + 1], drift[b: b + 1]), "%s, row %d" % (what, b), caches[v])
+            for b in (bad,) + short:
+                assert counts[b] == 0, (what, b)
+                assert (params[b].view(np.uint32) == SENTINEL).all(), (what, b)
+                assert np.array_equal(drift[b].view(np.int64), drift0[b].view(np.int64)), (what, b)
+            assert counts[4] > 600 and (counts[[0, 1, 2, 7, 8]] > 33).all()  # both buffers cut rows short
+        for x, y in zip(got_v, got_c):
+            assert x.dtype == y.dtype and x.tobytes() == y.tobytes(), "max_frames %d: the two entries differ" % max_frames
