@@ -1,0 +1,232 @@
+// The gvtm_debug_* hooks of the diagnostics library (libgama_vtm_diag.so; tests and tools only, not in the public header
+// and not in the product library): forced shapes, taps, cycle counters, math probes and single kernels on caller buffers.
+#include "vtm_host.hpp"
+#include "vtm_math.hpp"
+
+using namespace gvtm::host;
+
+// the hooks that run one kernel alone are synchronous: wait for what was launched on the null stream
+static int finish_kernel(hipError_t launched, const char* what)
+{
+	const hipError_t e = launched == hipSuccess ? hipDeviceSynchronize() : launched;
+	return e == hipSuccess ? GVTM_OK : fail_hip(e, what);
+}
+
+extern "C" {
+
+#pragma GCC visibility push(default)
+
+/* Forces the utterances per workgroup (1, 2, 4, 8; 0 = by batch size), i.e. the kernel shape a big batch would get. */
+int gvtm_debug_set_rows(gvtm_plan* plan, int rows)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	plan->rows = rows;
+	return GVTM_OK;
+}
+
+/* LDS bytes of a workgroup of `rows` utterances of this plan's one-shot kernel (0 = model 5's). */
+size_t gvtm_debug_lds_bytes(const gvtm_plan* plan, int rows)
+{
+	if (!plan) return 0;
+	// (of these rows, whether they fit or not; rows no launch has answer as the shape a launch forced to them has)
+	return gvtm::synth_launch_shape(plan->designs.data(), 1, plan->precision, 0, rows, false, 0, false).lds;
+}
+
+/* The shape a launch of `batch` utterances of this plan takes (voices != 0: a gvtm_synthesize_voices_* launch), as
+   launch_synthesis asks for it: out = {rows, ring length, LDS bytes}.  Needs no device. */
+int gvtm_debug_launch_shape(const gvtm_plan* plan, size_t batch, int voices, size_t out[3])
+{
+	if (!plan || !out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or buffer");
+	const gvtm::LaunchShape shape = plan->launch_shape(batch, 0, voices != 0);
+	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
+	out[0] = static_cast<size_t>(shape.rows), out[1] = static_cast<size_t>(shape.ring), out[2] = shape.lds;
+	return GVTM_OK;
+}
+
+/* The same for a launch of a stream (not model 5) whose `batch` utterances are pushed in lockstep, which is how they
+   share workgroups: the stream keeps the one-row shape's ring for every shape, so rows that fit a one-shot launch may
+   not fit here and give way to half as many.  A plan of several voices answers for a gvtm_stream_create_voices stream:
+   the voice variant, its LDS sized for the longest of the voices' stream rings. */
+int gvtm_debug_stream_launch_shape(const gvtm_plan* plan, size_t batch, size_t out[3])
+{
+	if (!plan || !out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or buffer");
+	if (plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "a plan of the models 0 to 4");
+	const gvtm::LaunchShape shape = plan->stream_launch_shape(batch, 0, plan->longest_stream_ring());
+	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
+	out[0] = static_cast<size_t>(shape.rows), out[1] = static_cast<size_t>(shape.ring), out[2] = shape.lds;
+	return GVTM_OK;
+}
+
+/* The chunk length (internal steps per tick) of the kernel shape a one-shot launch of `batch` utterances of this plan
+   takes: synth_chunk_length of the rows launch_synthesis picks.  0: no shape (model 5, or none fits); negative: a null
+   plan.  Needs no device. */
+int gvtm_debug_chunk_length(const gvtm_plan* plan, size_t batch)
+{
+	if (!plan) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (plan->designs[0].model5) return 0;
+	const gvtm::LaunchShape shape = plan->launch_shape(batch, 0, false);
+	if (!shape.rows) return 0;
+	return gvtm::synth_chunk_length(plan->designs[0].k, plan->precision, shape.rows);
+}
+
+/* The plan-level noise-sample table as the host builds it (n floats or doubles); needs no device. */
+int gvtm_debug_noise_table(size_t n, int as_float, void* out)
+{
+	if (!out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null buffer");
+	gvtm::design_noise_table(n, as_float != 0, out);
+	return GVTM_OK;
+}
+
+/* Test hook (not in the public header): device buffer [batch][max_frames*control_steps][8] of
+ * doubles that receives per-step intermediate values of the next synthesis calls; null disables. */
+int gvtm_debug_set_taps(gvtm_plan* plan, double* d_taps)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	plan->debug_taps = d_taps;
+	return GVTM_OK;
+}
+
+/* Diagnostic hook (not in the public header): device buffer [batch][16] of uint64 receiving the
+ * shader cycles workgroup `b` spent per phase (generation 1) or per role wavefront [0..7] and per
+ * helper stage [8..13] (generation 2). */
+int gvtm_debug_set_phase_cycles(gvtm_plan* plan, unsigned long long* d_cycles)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	plan->phase_cycles = d_cycles;
+	return GVTM_OK;
+}
+
+/* Diagnostic hook: what each lane receives through the cross-lane primitives of the tube
+ * wavefront (row_shr:1, row_shl:1, row_ror:6, row_ror:10, wave_shr:1, wave_shl:1); out[6][64] host ints. */
+int gvtm_debug_dpp_selftest(gvtm_plan* plan, int* out)
+{
+	if (!plan || !out || plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_INVALID_ARGUMENT, "needs a device plan");
+	DeviceScope scope(plan->device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	DeviceBuffer d;
+	hipError_t e = d.ensure(gvtm::kDppSelftestInts * sizeof(int));
+	if (e == hipSuccess) e = gvtm::launch_dpp_selftest(d.as<int>(), nullptr);
+	if (e != hipSuccess) return fail_hip(e, "dpp selftest");
+	return download(out, d, gvtm::kDppSelftestInts, "dpp selftest");
+}
+
+/* Test hook: the short elementary functions of csrc/vtm_math.hpp evaluated on the host
+ * (kind 0 = 2^x, 1 = 10^x, 2 = cos, 3 = tan; 4 = powf(2, x), 5 = powf(10, x), 6 = cosf, 7 = tanf of the
+ * all-float path, 8 = sinf of the float model 5's sine waveform, 9 = tanf in the form with its library fallback in line,
+ * arguments and results carried as doubles). */
+int gvtm_debug_short_math(int kind, const double* x, size_t n, double* out)
+{
+	if (!x || !out) return GVTM_ERR_INVALID_ARGUMENT;
+	for (size_t i = 0; i < n; ++i) {
+		switch (kind) {
+		case 0: out[i] = gvtm::vmath::exp2_short(x[i]); break;
+		case 1: out[i] = gvtm::vmath::exp10_short(x[i]); break;
+		case 2: out[i] = gvtm::vmath::cos_short(x[i]); break;
+		case 3: out[i] = gvtm::vmath::tan_short(x[i]); break;
+		case 4: out[i] = gvtm::vmath::powf_base2(static_cast<float>(x[i])); break;
+		case 5: out[i] = gvtm::vmath::powf_base10(static_cast<float>(x[i])); break;
+		case 6: out[i] = gvtm::vmath::cosf_glibc(static_cast<float>(x[i])); break;
+		case 7: out[i] = gvtm::vmath::tanf_glibc(static_cast<float>(x[i])); break;
+		case 8: out[i] = gvtm::vmath::sinf_glibc(static_cast<float>(x[i])); break;
+		case 9: out[i] = gvtm::vmath::tanf_glibc<true>(static_cast<float>(x[i])); break;
+		default: return GVTM_ERR_INVALID_ARGUMENT;
+		}
+	}
+	return GVTM_OK;
+}
+
+/* Test hook: Util::frequency / Util::amplitude60dB / tan / cos of the all-float path (kind 0..3), its scaling-free
+ * division (4), the float model 5's sin (5) and tan / cos with their library fallbacks in line (6, 7) evaluated by a kernel on the plan's device, host arrays in and out. */
+int gvtm_debug_device_float_math(gvtm_plan* plan, int kind, const float* x, size_t n, float* out)
+{
+	if (!plan || !x || !out || kind < 0 || kind > 7) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
+	DeviceScope scope(plan->device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	DeviceBuffer dx, dout;
+	if (const int rc = upload(dx, x, n, "float math probe"); rc != GVTM_OK) return rc;
+	hipError_t e = dout.ensure(n * sizeof(float));
+	if (e == hipSuccess) e = gvtm::launch_float_math_probe(kind, dx.as<float>(), n, dout.as<float>(), nullptr);
+	if (e != hipSuccess) return fail_hip(e, "float math probe");
+	return download(out, dout, n, "float math probe");
+}
+
+/* Test hook: the grouping kernel of gvtm_synthesize_voices_device alone, for `rows` utterances per workgroup, on device
+ * buffers: d_row_map [groups][rows] and d_group_voice [groups] with groups = ceil(batch / rows) + n_voices; d_out_counts /
+ * d_maxabs may be null.  Synchronous. */
+int gvtm_debug_group_voices(gvtm_plan* plan, const int32_t* d_voice_ids, size_t batch, int rows, int32_t* d_row_map, int32_t* d_group_voice,
+		int64_t* d_out_counts, float* d_maxabs)
+{
+	if (!plan || !d_voice_ids || !d_row_map || !d_group_voice || batch == 0 || rows < 1) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
+	DeviceScope scope(plan->device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	DeviceBuffer counts;
+	if (const hipError_t e = counts.ensure(sizeof(int32_t) * plan->n_voices() * gvtm::kGroupVoicesThreads); e != hipSuccess) return fail_hip(e, "hipMalloc");
+	const size_t groups = (batch + rows - 1) / rows + static_cast<size_t>(plan->n_voices());
+	gvtm::GroupVoicesArgs ga{d_voice_ids, batch, plan->n_voices(), rows, groups, d_row_map, d_group_voice, static_cast<int32_t*>(counts.ptr), d_out_counts, d_maxabs};
+	return finish_kernel(gvtm::launch_group_voices(ga, nullptr), "vtm_group_voices_kernel");
+}
+
+/* Test hook: the append variant of the chunk tracks kernel alone, on device buffers of the caller's (so that a test can
+ * put sentinels around them): gvtm_generate_tracks_chunks_device with d_row_start [batch] int32 -- utterance b's frames
+ * leave at row d_row_start[b] of its block of max_frames rows, nothing at or beyond row max_frames, and d_frame_counts[b]
+ * counts this call's frames.  Synchronous. */
+int gvtm_debug_tracks_append(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_chunk_offsets, const int64_t* d_utt_chunks,
+		const int32_t* d_voice_ids, const int32_t* d_row_start, size_t batch, size_t max_frames, float* d_params, int32_t* d_frame_counts,
+		gvtm_drift_state* d_drift)
+{
+	if (!plan || !d_events || !d_chunk_offsets || !d_utt_chunks || !d_voice_ids || !d_row_start || !d_params || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (reinterpret_cast<uintptr_t>(d_params) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params must be 16-byte aligned");
+	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
+	DeviceScope scope(plan->device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	gvtm::TrackAppendArgs args = plan_track_args(plan, d_events, d_voice_ids, batch, max_frames, d_params, d_frame_counts, d_drift);
+	args.chunk_offsets = d_chunk_offsets;
+	args.utt_chunks = d_utt_chunks;
+	args.row_start = d_row_start;
+	return finish_kernel(gvtm::launch_tracks(args, nullptr), "vtm_tracks_append_kernel");
+}
+
+/* Test hook: the slice variant of the chunk tracks kernel alone, on device buffers of the caller's: a slice of `batch`
+ * utterances of a larger batch.  d_chunk_offsets is the whole batch's table; d_utt_chunks [batch + 1], d_voice_ids, d_drift,
+ * d_frame_counts and d_frame_offsets [batch + 1] point at the slice's first utterance; d_events at the slice's first event,
+ * which is event `event_base` of the batch.  d_params [batch][max_frames][16] takes the padded rows, d_packed (may be
+ * null; d_frame_offsets is then not read) the frames back to back.  Synchronous. */
+int gvtm_debug_tracks_slice(gvtm_plan* plan, const gvtm_event* d_events, int64_t event_base, const int64_t* d_chunk_offsets,
+		const int64_t* d_utt_chunks, const int32_t* d_voice_ids, const int64_t* d_frame_offsets, size_t batch, size_t max_frames, float* d_params,
+		float* d_packed, int32_t* d_frame_counts, gvtm_drift_state* d_drift)
+{
+	if (!plan || !d_events || !d_chunk_offsets || !d_utt_chunks || !d_voice_ids || !d_params || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (d_packed && !d_frame_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_packed needs d_frame_offsets");
+	if ((reinterpret_cast<uintptr_t>(d_params) | reinterpret_cast<uintptr_t>(d_packed)) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params and d_packed must be 16-byte aligned");
+	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
+	DeviceScope scope(plan->device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	gvtm::TrackSliceArgs args{};
+	static_cast<gvtm::TrackChunksArgs&>(args) = plan_track_args(plan, d_events, d_voice_ids, batch, max_frames, d_params, d_frame_counts, d_drift);
+	args.chunk_offsets = d_chunk_offsets;
+	args.utt_chunks = d_utt_chunks;
+	args.event_base = event_base;
+	args.packed = d_packed;
+	args.frame_offsets = d_frame_offsets;
+	return finish_kernel(gvtm::launch_tracks(args, nullptr), "vtm_tracks_slice_kernel");
+}
+
+/* Test hook: the carry kernel of an events-fed stream alone, on device buffers of the caller's: in utterance b's block of
+ * max_frames rows of d_params the rows [d_done[b], d_held[b]) move to the front.  Synchronous. */
+int gvtm_debug_carry_rows(gvtm_plan* plan, float* d_params, const int32_t* d_done, const int32_t* d_held, size_t batch, size_t max_frames)
+{
+	if (!plan || !d_params || !d_done || !d_held || batch == 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "bad argument");
+	if (reinterpret_cast<uintptr_t>(d_params) & 15) return fail(GVTM_ERR_INVALID_ARGUMENT, "d_params must be 16-byte aligned");
+	if (plan->device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only plan");
+	DeviceScope scope(plan->device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	return finish_kernel(gvtm::launch_carry_rows(gvtm::CarryArgs{d_params, d_done, d_held, batch, max_frames}, nullptr), "vtm_carry_rows_kernel");
+}
+
+#pragma GCC visibility pop
+
+} // extern "C"

@@ -1,4 +1,4 @@
-// Launch interface between the C ABI (vtm_capi.cpp) and the kernels (vtm_kernels.hip).
+// Launch interface between the C ABI (vtm_capi_*.cpp, vtm_host.hpp) and the kernels (vtm_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -99,3 +99,16 @@ def test_pcm16_against_the_float_oracle_end_to_end():
         ref = oracle.synthesize(cfg, params[b])
         assert counts[b] == ref.size
         assert np.array_equal(pcm[b], _pcm_rule(ref, oracle.output_scale(ref)))
+
+
+def test_batch_without_frames():
+    """max_frames = 0: nothing is copied in (the kernel still gets a frame buffer), and every utterance is the empty one of
+    the device entry -- the same count, the same samples."""
+    params = np.zeros((3, 0, 16), dtype=np.float32)
+    plan = male_plan(precision=capi.PRECISION_F32)
+    audio, counts, maxabs = plan.synthesize_host(params)
+    got, got_counts = run_batch_device(plan, np.zeros((3, 1, 16), dtype=np.float32), np.zeros(3, dtype=np.int32), plan.output_capacity(1))
+    assert np.array_equal(counts, got_counts) and (counts == plan.output_count(0)).all()
+    assert np.array_equal(audio, got[:, : audio.shape[1]]) and np.array_equal(maxabs, np.abs(audio).max(axis=1, initial=0.0))
+    pcm, counts16, maxabs16, scales = plan.synthesize_host_pcm16(params)
+    assert np.array_equal(counts16, counts) and np.array_equal(maxabs16, maxabs) and pcm.shape == audio.shape

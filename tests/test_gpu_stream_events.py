@@ -347,3 +347,47 @@ def test_modes_refusals_and_the_drift_generators_across_resets():
     st = g.Stream(bare, 3, voice_ids=ids)
     assert status_of(st.push_events, push) == INVALID_ARGUMENT
     assert "gvtm_plan_set_voice_tracks" in bare._lib.gvtm_last_error().decode()
+
+
+# ---- 6. pushes that bring nothing
+
+def test_pushes_without_chunks_and_without_events():
+    """A push with a null utt_chunks, one whose utterances receive no chunk and one whose only chunk holds no event: each
+    generates no frame, returns no sample and leaves the drift states alone, before the first frames and while frames are
+    held; the samples of the run are those of a frames-fed stream given the chained tracks oracle's frames."""
+    plan = audio_plan("f32")
+    ids = [0, 1, 2]
+    chunks = [[make_singable(list_with_frames(c))] for c in (9, 5, 11)]
+    assert all(capi.events_from_table(u[0]).shape[0] <= 12 for u in chunks)
+    d0 = used_drift(3, seed=21)
+    st = g.Stream(plan, 3, voice_ids=ids)
+    st.set_drift(d0)
+
+    def push_nothing(how):
+        audio, counts, frames = np.full((3, 8), 5.0, np.float32), np.full(3, -1, np.int64), np.full(3, -1, np.int32)
+        before = st.get_drift()
+        if how == "null":
+            plan._check(plan._lib.gvtm_stream_push_events(st._h, None, None, None, capi._ptr(audio), 8, capi._ptr(counts), capi._ptr(frames)))
+        else:
+            got, frames = st.push_events([[], [], []] if how == "no chunk" else [[], [np.zeros((0, 38))], []])
+            counts = np.array([s.size for s in got])
+        assert not counts.any() and not frames.any() and st.get_drift().tobytes() == before.tobytes(), how
+
+    for how in ("null", "no chunk", "no event"):
+        push_nothing(how)
+    first, new = st.push_events(chunks)
+    assert new.tolist() == [frame_count(AUDIO_TRACKS[v], u) for v, u in zip(ids, chunks)] == [9, 5, 11]
+    for how in ("null", "no chunk", "no event"):  # (rows are held now)
+        push_nothing(how)
+    tails, maxabs = st.finish()
+
+    fed = g.Stream(plan, 3, voice_ids=ids)
+    rows = [chain_oracle(AUDIO_TRACKS[v], u, d0[b])[0] for b, (v, u) in enumerate(zip(ids, chunks))]
+    buf = np.zeros((3, 11, 16), dtype=np.float32)
+    for b, r in enumerate(rows):
+        buf[b, : r.shape[0]] = r
+    fed_first = fed.push(buf, np.array([r.shape[0] for r in rows], dtype=np.int32))
+    fed_tails, fed_maxabs = fed.finish()
+    for b in range(3):
+        assert first[b].tobytes() == fed_first[b].tobytes() and tails[b].tobytes() == fed_tails[b].tobytes() and tails[b].size > 0, b
+    assert maxabs.tobytes() == fed_maxabs.tobytes()

@@ -55,6 +55,24 @@ def test_truncation_and_fresh_generator_default():
     assert np.array_equal(params[0].view(np.uint32), frames[:50].view(np.uint32))
 
 
+def test_host_entry_with_an_empty_event_array():
+    """Three utterances without an event: no frame, the rows zero, the generators where they were -- as the host's count and
+    the oracle say."""
+    cfg = np.array([4, 1, 1, 1, 1, -20.0, -6.0, 4.0, 250.0, 4.0])
+    tables = [event_lists.random_event_table(60 + b, n_events=0) for b in range(3)]
+    lists = [capi.events_from_table(t) for t in tables]
+    drift0 = used_drift(3)
+    params, counts, dr = capi.generate_tracks_host(product_config(cfg), lists, 4, drift=[tuple(d) for d in drift0])
+    assert counts.tolist() == [capi.tracks_chunks_frame_count(product_config(cfg), e, np.zeros(2, np.int64)) for e in lists] == [0, 0, 0]
+    assert not params.any() and params.shape == (3, 4, 16)
+    for b, t in enumerate(tables):  # (the device entry refuses a null events pointer, which is what no event at all gives it)
+        frames, state = oracle.tracks_generate(oracle.track_config(cfg), t, tuple(drift0[b]))
+        assert frames.shape[0] == 0 and tuple(dr[b]) == state == tuple(drift0[b])
+    # no frames asked for either: nothing comes back but the counts
+    params0, counts0, _ = capi.generate_tracks_host(product_config(cfg), lists, 0)
+    assert params0.shape == (3, 0, 16) and not counts0.any()
+
+
 def test_events_to_audio_on_the_device(golden_tracks):
     """Event lists -> parameter frames -> audio, the frames produced and consumed in device memory: equals the
     oracle of the oracle (EventList::generateOutput then the vocal-tract model)."""
