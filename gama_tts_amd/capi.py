@@ -218,6 +218,13 @@ def load_library(diagnostics=False):
         L.gvtm_generate_tracks_chunks_device.restype = i32
         L.gvtm_synthesize_events_chunks_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
         L.gvtm_synthesize_events_chunks_device.restype = i32
+    if hasattr(L, "gvtm_intonation_apply_host"):
+        L.gvtm_intonation_apply_host.argtypes = [ctypes.POINTER(TrackConfig), vp, sz, vp, sz, vp, sz, vp]
+        L.gvtm_intonation_apply_host.restype = ctypes.c_int64
+        L.gvtm_apply_intonation_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]
+        L.gvtm_apply_intonation_device.restype = i32
+        L.gvtm_synthesize_intonation_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]
+        L.gvtm_synthesize_intonation_device.restype = i32
     if hasattr(L, "gvtm_stream_push_events"):
         L.gvtm_stream_push_events.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
         L.gvtm_stream_push_events.restype = i32
@@ -413,6 +420,33 @@ def tracks_chunks_frame_count(config, events, chunk_offsets):
     if n == ctypes.c_size_t(-1).value:
         raise GvtmError(1, lib.gvtm_last_error().decode())
     return n
+
+
+# gvtm_intonation_point as a numpy record layout (24 bytes)
+POINT_DTYPE = np.dtype([("time_ms", "<f8"), ("semitone", "<f8"), ("slope", "<f8")])
+MAX_INTONATION_POINTS = 64  # GVTM_MAX_INTONATION_POINTS
+
+
+def points_from_table(table):
+    """float64 [P][3] rows (time_ms, semitone, slope) -> gvtm_intonation_point records."""
+    return np.ascontiguousarray(np.asarray(table, dtype=np.float64).reshape(-1, 3)).view(POINT_DTYPE).reshape(-1)
+
+
+def intonation_apply_host(config, events, points, count_only=False, capacity=None):
+    """gvtm_intonation_apply_host: gvtm_event records and gvtm_intonation_point records -> (merged gvtm_event records, or
+    with count_only their number; status).  A refused utterance has no merged events and a status other than 0.
+    capacity: events the output is sized for (default: len(events) + len(points), which always holds them)."""
+    lib = load_library()
+    events = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
+    points = np.ascontiguousarray(points, dtype=POINT_DTYPE)
+    status = ctypes.c_int32(-1)
+    capacity = events.shape[0] + points.shape[0] if capacity is None else int(capacity)
+    out = None if count_only else np.zeros(max(capacity, 1), dtype=EVENT_DTYPE)
+    n = lib.gvtm_intonation_apply_host(ctypes.byref(config), _ptr(events), events.shape[0], _ptr(points), points.shape[0], _ptr(out),
+                                       capacity, ctypes.byref(status))
+    if n < 0:
+        raise GvtmError(1, lib.gvtm_last_error().decode())
+    return (int(n) if count_only else out[:n].copy()), int(status.value)
 
 
 def generate_tracks_host(config, event_lists, max_frames, drift=None, device=0):
@@ -714,6 +748,24 @@ class Plan:
             self._check(self._lib.gvtm_synthesize_events_packed_host(
                 self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks), _ptr(ids), batch, _ptr(out), out.shape[0], _ptr(sample_offsets),
                 _ptr(frame_offsets), _ptr(frames_out), frames_capacity, _ptr(counts), _ptr(maxabs), _ptr(drift)))
+
+    def apply_intonation_device(self, d_events, d_list_offsets, n_lists, d_list_ids, d_points, d_point_offsets, d_voice_ids, batch,
+                                d_events_out, out_capacity, d_event_offsets_out, d_status=None, stream=None):
+        """gvtm_apply_intonation_device: intonation points onto base event lists (d_list_ids None: utterance b's is list
+        b) -> merged lists, their offsets and statuses; all pointers are device memory."""
+        self._check(self._lib.gvtm_apply_intonation_device(
+            self._h, _ptr(d_events), _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_points), _ptr(d_point_offsets),
+            _ptr(d_voice_ids), int(batch), _ptr(d_events_out), int(out_capacity), _ptr(d_event_offsets_out), _ptr(d_status), _ptr(stream)))
+
+    def synthesize_intonation_device(self, d_events, d_list_offsets, n_lists, d_list_ids, d_points, d_point_offsets, d_voice_ids,
+                                     events_capacity, batch, max_frames, d_audio, audio_stride, d_frame_counts=None, d_out_counts=None,
+                                     d_maxabs=None, d_drift=None, d_status=None, stream=None):
+        """Base event lists and intonation points in, samples out (gvtm_synthesize_intonation_device); all pointers are
+        device memory."""
+        self._check(self._lib.gvtm_synthesize_intonation_device(
+            self._h, _ptr(d_events), _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_points), _ptr(d_point_offsets),
+            _ptr(d_voice_ids), int(events_capacity), int(batch), int(max_frames), _ptr(d_audio), int(audio_stride), _ptr(d_frame_counts),
+            _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift), _ptr(d_status), _ptr(stream)))
 
     def synthesize_events_device(self, track_config, d_events, d_offsets, batch, max_frames, d_audio, audio_stride,
                                  d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, stream=None):

@@ -1,6 +1,8 @@
-// C ABI of libgama_vtm.so, event lists on the device: the frame counts of the host's walk, track generation, and the
-// events entries, which put a synthesis launch behind the tracks kernel with a frame buffer of the plan's in between.
+// C ABI of libgama_vtm.so, event lists on the device: the frame counts of the host's walk, track generation, the
+// events entries, which put a synthesis launch behind the tracks kernel with a frame buffer of the plan's in between, and
+// the intonation entries, which put the contour's events and polynomials into the lists in front of all that.
 #include "vtm_host.hpp"
+#include "vtm_intonation.hpp"
 
 using namespace gvtm::host;
 
@@ -89,9 +91,111 @@ int synthesize_voice_events(gvtm_plan* plan, const char* entry, const VoiceEvent
 			lists.d_voice_ids, &plan->async.groups});
 }
 
+// The batch of an intonation entry as the caller gives it
+struct IntonationLists {
+	const gvtm_event* d_events;
+	const int64_t* d_list_offsets;
+	size_t n_lists;
+	const int32_t* d_list_ids;
+	const gvtm_intonation_point* d_points;
+	const int64_t* d_point_offsets;
+	const int32_t* d_voice_ids;
+};
+
+// What the two intonation entries refuse before any device work, in the order the header gives; GVTM_OK with batch == 0 is
+// the caller's to return.  null_output: the apply entry's own outputs, one of which is null.
+int check_intonation(const gvtm_plan* plan, const char* entry, const IntonationLists& in, size_t batch, bool null_output = false)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, std::string(entry) + ": the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
+	if (batch > 0) {
+		if (!in.d_events || !in.d_list_offsets || !in.d_points || !in.d_point_offsets || !in.d_voice_ids) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "null events, list offsets, points, point offsets or voice ids");
+		}
+		if (null_output) return fail(GVTM_ERR_INVALID_ARGUMENT, "null events_out or event_offsets_out");
+		if (!in.d_list_ids && in.n_lists != batch) return fail(GVTM_ERR_INVALID_ARGUMENT, "without list ids every utterance has a list of its own: n_lists must equal batch");
+		if (batch > 0x7fffffffu) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
+	}
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
+	return GVTM_OK;
+}
+
+// the three apply kernels on the caller's stream (the plan's device is current)
+int launch_intonation(gvtm_plan* plan, const IntonationLists& in, size_t batch, gvtm_event* d_events_out, size_t out_capacity, int64_t* d_event_offsets_out,
+		int32_t* d_status, void* hip_stream)
+{
+	gvtm::IntonationArgs args{};
+	args.events = in.d_events;
+	args.list_offsets = in.d_list_offsets;
+	args.n_lists = static_cast<int64_t>(std::min<size_t>(in.n_lists, INT64_MAX));
+	args.list_ids = in.d_list_ids;
+	args.points = in.d_points;
+	args.point_offsets = in.d_point_offsets;
+	args.voice_k = static_cast<const gvtm::TrackConstants*>(plan->d_voice_tracks.ptr);
+	args.voice_ids = in.d_voice_ids;
+	args.n_voices = plan->n_voices();
+	args.control_period = plan->voice_tracks[0].control_period;
+	args.batch = batch;
+	args.events_out = d_events_out;
+	args.out_capacity = static_cast<int64_t>(std::min<size_t>(out_capacity, INT64_MAX));
+	args.event_offsets_out = d_event_offsets_out;
+	args.status = d_status;
+	const hipError_t e = gvtm::launch_apply_intonation(args, static_cast<hipStream_t>(hip_stream));
+	return e == hipSuccess ? GVTM_OK : fail_hip(e, "intonation launch");
+}
+
 } // namespace
 
 extern "C" {
+
+int64_t gvtm_intonation_apply_host(const gvtm_track_config* config, const gvtm_event* events, size_t n_events, const gvtm_intonation_point* points,
+		size_t n_points, gvtm_event* events_out, size_t capacity, int32_t* status_out)
+{
+	if (!config || !status_out || (!events && n_events > 0) || (!points && n_points > 0)) { fail(GVTM_ERR_INVALID_ARGUMENT, "null config, status, events or points"); return -1; }
+	gvtm::TrackConstants k;
+	const char* why = gvtm::design_tracks(*config, k);
+	if (why[0]) { fail(GVTM_ERR_INVALID_ARGUMENT, why); return -1; }
+	const int64_t merged = gvtm::intonation_apply(k.control_period, k.smooth_intonation != 0, events, n_events, points, n_points, events_out, capacity, status_out);
+	if (merged < 0) fail(GVTM_ERR_INVALID_ARGUMENT, "the merged list does not fit capacity (at most n_events + n_points events)");
+	return merged;
+}
+
+int gvtm_apply_intonation_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
+		const gvtm_intonation_point* d_points, const int64_t* d_point_offsets, const int32_t* d_voice_ids, size_t batch, gvtm_event* d_events_out,
+		size_t out_capacity, int64_t* d_event_offsets_out, int32_t* d_status, void* hip_stream)
+{
+	const IntonationLists in{d_events, d_list_offsets, n_lists, d_list_ids, d_points, d_point_offsets, d_voice_ids};
+	int rc = check_intonation(plan, "gvtm_apply_intonation_device", in, batch, !d_events_out || !d_event_offsets_out);
+	if (rc != GVTM_OK || batch == 0) return rc;
+	DeviceScope scope(plan->device);
+	if ((rc = scope.entered()) != GVTM_OK) return rc;
+	return launch_intonation(plan, in, batch, d_events_out, out_capacity, d_event_offsets_out, d_status, hip_stream);
+}
+
+int gvtm_synthesize_intonation_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
+		const gvtm_intonation_point* d_points, const int64_t* d_point_offsets, const int32_t* d_voice_ids, size_t events_capacity, size_t batch,
+		size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift,
+		int32_t* d_status, void* hip_stream)
+{
+	const IntonationLists in{d_events, d_list_offsets, n_lists, d_list_ids, d_points, d_point_offsets, d_voice_ids};
+	int rc = check_intonation(plan, "gvtm_synthesize_intonation_device", in, batch);
+	if (rc != GVTM_OK || batch == 0) return rc;
+	// (what the synthesis launch would refuse is refused before the apply kernels write a status)
+	if (!d_audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
+	if ((rc = check_audio_stride(plan, audio_stride, max_frames, true)) != GVTM_OK) return rc;
+	if (events_capacity > SIZE_MAX / sizeof(gvtm_event)) return fail(GVTM_ERR_INVALID_ARGUMENT, "events_capacity too large");
+	DeviceScope scope(plan->device);
+	if ((rc = scope.entered()) != GVTM_OK) return rc;
+	hipError_t e;
+	// (the events' pointer goes to the kernels even when there is room for none)
+	if ((e = plan->async.events.ensure(sizeof(gvtm_event) * std::max<size_t>(events_capacity, 1))) != hipSuccess) return fail_hip(e, "hipMalloc merged events");
+	if ((e = plan->async.event_offsets.ensure(sizeof(int64_t) * (batch + 1))) != hipSuccess) return fail_hip(e, "hipMalloc merged event offsets");
+	gvtm_event* merged = plan->async.events.as<gvtm_event>();
+	int64_t* offsets = plan->async.event_offsets.as<int64_t>();
+	if ((rc = launch_intonation(plan, in, batch, merged, events_capacity, offsets, d_status, hip_stream)) != GVTM_OK) return rc;
+	return synthesize_voice_events(plan, "gvtm_synthesize_intonation_device", VoiceEvents{merged, offsets, d_voice_ids}, batch, max_frames, d_audio,
+			audio_stride, d_frame_counts, d_out_counts, d_maxabs, d_drift, hip_stream);
+}
 
 size_t gvtm_tracks_frame_count(const gvtm_track_config* config, const gvtm_event* events, size_t n_events)
 {

@@ -4,6 +4,7 @@
 // reproduce; tests/test_capi_cpu.py compares every table with the oracle
 // bit for bit through gvtm_plan_table().
 #include "vtm_design.hpp"
+#include "vtm_intonation.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -639,6 +640,56 @@ size_t tracks_frame_count(int control_period, const gvtm_event* events, size_t n
 	case 4: return walk_frame_count<4>(4, events, n_events);
 	default: return walk_frame_count<0>(control_period, events, n_events);
 	}
+}
+
+int64_t intonation_apply(int cp, bool smooth, const gvtm_event* events, size_t n_events, const gvtm_intonation_point* points, size_t n_points,
+		gvtm_event* events_out, size_t capacity, int32_t* status)
+{
+	// the refusals in the order of their numbers; every point is looked at for 3 before any pair is for 4
+	*status = kIntonationOk;
+	if (n_events == 0 || events[0].time_ms < 0) *status = kIntonationNoList;
+	for (size_t i = 1; i < n_events && *status == kIntonationOk; ++i) {
+		if (events[i].time_ms <= events[i - 1].time_ms) *status = kIntonationNoList;
+	}
+	if (*status == kIntonationOk && n_points > GVTM_MAX_INTONATION_POINTS) *status = kIntonationTooMany;
+	if (*status != kIntonationOk) return 0;
+	int q[GVTM_MAX_INTONATION_POINTS];
+	for (size_t j = 0; j < n_points; ++j) {
+		if (!intonation_point_time(points[j].time_ms, cp, events[n_events - 1].time_ms, q[j])) *status = kIntonationBadTime;
+	}
+	for (size_t j = 1; j < n_points && *status == kIntonationOk; ++j) {
+		if (q[j] <= q[j - 1]) *status = kIntonationNotIncreasing;
+	}
+	if (*status != kIntonationOk) return 0;
+
+	// base events and points are both in the order of their times: one merge
+	int64_t merged = 0;
+	size_t i = 0, j = 0;
+	while (i < n_events || j < n_points) {
+		const bool at_point = j < n_points && (i == n_events || q[j] <= events[i].time_ms);
+		const bool at_event = i < n_events && !(at_point && q[j] < events[i].time_ms);
+		if (events_out) {
+			if (static_cast<size_t>(merged) >= capacity) return -1;
+			gvtm_event& e = events_out[merged];
+			if (at_event) {
+				e = events[i];
+			} else { // Event::Event: every parameter EMPTY_PARAMETER (EventList.cpp:38-49)
+				e.time_ms = q[j];
+				for (int c = 0; c < 16; ++c) e.param[c] = e.special[c] = HUGE_VAL;
+			}
+			e.has_interp = 0;
+			for (double& v : e.interp) v = 0.0;
+			if (at_point && n_points >= 2) {
+				e.has_interp = 1;
+				if (j + 1 < n_points) intonation_segment(smooth, q[j], points[j].semitone, points[j].slope, q[j + 1], points[j + 1].semitone, points[j + 1].slope, e.interp);
+				else intonation_last(smooth, points[j].semitone, e.interp);
+			}
+		}
+		++merged;
+		if (at_event) ++i;
+		if (at_point) ++j;
+	}
+	return merged;
 }
 
 } // namespace gvtm

@@ -134,9 +134,11 @@ struct gvtm_plan {
 		unsigned char* set_of(size_t i) const { return set[i % 3].as<unsigned char>(); } // slice i's: the sets rotate
 	} host;
 	// ... and the enqueue-only entries' (gvtm_synthesize_events_device's frames and frame counts, the grouping of
-	// gvtm_synthesize_voices_device): calls to those on one plan must be ordered on one stream
+	// gvtm_synthesize_voices_device, the merged event lists and their offsets of gvtm_synthesize_intonation_device): calls to
+	// those on one plan must be ordered on one stream
 	struct {
 		DeviceBuffer params, frames, groups;
+		DeviceBuffer events, event_offsets;
 	} async;
 	// gvtm_plan_set_voice_tracks: one designed track configuration per voice, and (device plans) the table the voice
 	// variant of the tracks kernel reads; empty until the first call that succeeds

@@ -662,6 +662,93 @@ int gvtm_synthesize_events_chunks_device(gvtm_plan* plan, const gvtm_event* d_ev
 		int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift, void* hip_stream);
 
 /*
+ * Intonation contours applied to event lists.  Controller::synthesizeFromEventListToBuffer/File (Controller.cpp:158-168,
+ * 210-224) keeps the event list and changes the intonation: clearMacroIntonation(), prepareMacroIntonationInterpolation()
+ * (EventList.cpp:822-900, 1093-1099) from the list of IntonationPoints, then generateOutput() -- the editor's path after
+ * every edit of the contour, and for a batch one sentence spoken under many contours.  The entries below make the list
+ * those two calls leave, on the host or for a batch on the device, where many utterances may share one base list and
+ * only the points (24 bytes each) differ between them.
+ *
+ * The rule, for a base list of E events and P points under a configuration's control_period_ms (cp) and
+ * smooth_intonation:
+ *   1. every base event is kept bit for bit, except has_interp = 0 and interp = {0, 0, 0, 0} (also with P = 0);
+ *   2. duration = time of the last base event + 100, taken once, before anything is inserted (setFullTimeScale, :679-684);
+ *   3. point j: t = time_ms < 0 ? 0 : time_ms; q_j = (int)t, and with cp != 1, q_j -= q_j % cp (insertEvent, :302-315);
+ *   4. the merged list is the base list plus one event per q_j that no base event has, in the order of their times; a new
+ *      event has all 32 parameters at +infinity, has_interp = 0 and interp = 0;
+ *   5. with P >= 2 the event at q_j (j < P - 1) gets has_interp = 1 and the polynomial of :844-883 from x1 = q_j,
+ *      x2 = q_{j+1} (the events' times, not the points'), y = semitone, m = slope -- the cubic a, b, c, d in the reference's
+ *      order of operations with coef = 1.0 / (dx * dx * dx), or, linear, a = (y2 - y1) / dx, b = y1 - x1 * a, c = d = 0 --
+ *      and the event at q_{P-1} gets {0, 0, 0, semitone} (smooth) or {0, semitone, 0, 0} (linear);
+ *   6. with P = 1 the event at q_0 exists and no event carries a polynomial (the reference's loop does not run).
+ * Double arithmetic without FMA contraction on the host and on the device: bit for bit the reference's list.
+ *
+ * An utterance is refused on its own: its merged list has 0 events, so track generation gives it 0 frames and leaves its
+ * drift state alone.  Its status says why; the first that applies, every point being looked at for 3 before any for 4:
+ *   0  ok
+ *   1  empty base list; on the device also a list id outside [0, n_lists) or a voice id outside the plan's voices, on the
+ *      host also base times that are negative or not strictly increasing (the device does not look)
+ *   2  more than GVTM_MAX_INTONATION_POINTS points (on the device also point offsets that decrease)
+ *   3  a time_ms that is not finite or greater than duration + cp: insertEvent returns null and the reference throws
+ *      (:307-309, :829-842); also a time of 2^31 ms or more, which a list that ends within 100 ms of INT_MAX would admit
+ *   4  q_j not strictly increasing: the reference would compute 1 / 0 (its own addIntonationPoint keeps points two control
+ *      periods apart, :915-924); refused on purpose rather than restated
+ *   5  device only: the merged list does not fit behind the lists before it in out_capacity events
+ */
+typedef struct gvtm_intonation_point {
+	double time_ms;   /* IntonationPoint::absoluteTime(): beat of its rule + offset, IntonationPoint.cpp:43-52 */
+	double semitone;  /* IntonationPoint::semitone() */
+	double slope;     /* IntonationPoint::slope() (used with smooth_intonation only) */
+} gvtm_intonation_point;
+#define GVTM_MAX_INTONATION_POINTS 64   /* per utterance */
+
+/* The rule on the host; needs no device.  Returns the merged events (>= 0; 0 with *status_out != 0 for a refused
+ * utterance), or -1 on a bad call: a null config or status_out, a config gvtm_tracks_frame_count would refuse, null
+ * events / points with a count > 0, a capacity too small for the merged list.  events_out == NULL: count and status only
+ * (capacity is not read).  The merged list holds at most n_events + n_points events.  gvtm_tracks_frame_count on the merged
+ * list gives the frames generateOutput() yields for it: what to size max_frames with below.  (A bound without the walk:
+ * the last merged event lies at duration + cp at most, duration the last base event's time + 100, so no more than
+ * ceil((last base time + 100 + cp) / cp) + n_events + n_points frames.) */
+int64_t gvtm_intonation_apply_host(const gvtm_track_config* config, const gvtm_event* events, size_t n_events,
+		const gvtm_intonation_point* points, size_t n_points, gvtm_event* events_out, size_t capacity, int32_t* status_out);
+
+/* The rule for a batch, everything resident in device memory.
+ *   d_events, d_list_offsets [n_lists + 1]   base list l owns the events [off[l], off[l+1])
+ *   d_list_ids [batch] int32, or NULL        utterance b's base list; NULL: n_lists == batch and utterance b uses list b.
+ *                                            Many utterances may share one base list.
+ *   d_points, d_point_offsets [batch + 1]    utterance b owns the points [off[b], off[b+1])
+ *   d_voice_ids [batch] int32                as the chunks entry takes them: smooth_intonation comes from the plan's track
+ *                                            configuration of the utterance's voice (gvtm_plan_set_voice_tracks), the
+ *                                            control period is the plan's
+ *   d_events_out                             out, out_capacity events: the merged lists back to back.  The caller sizes it
+ *                                            as the sum over b of E(list of b) + P_b, which it knows from its host tables
+ *   d_event_offsets_out [batch + 1]          out: exactly the d_event_offsets the tracks entries take
+ *   d_status [batch] int32, may be NULL      out: the statuses above
+ * Merged lists, offsets and statuses are bit for bit gvtm_intonation_apply_host's, utterance by utterance.  Nothing is
+ * written at or beyond out_capacity events and nothing for a refused utterance; a list that would end beyond out_capacity
+ * is refused (5) and takes no room, so a shorter one behind it may still fit.  Enqueue-only: three small kernels on
+ * hip_stream, no scratch.  Refused before any device work, in this order: a null plan, a plan without track
+ * configurations, with batch > 0 a null argument (d_list_ids and d_status aside) or a NULL d_list_ids with n_lists !=
+ * batch (GVTM_ERR_INVALID_ARGUMENT); a design-only plan (GVTM_ERR_NO_DEVICE); batch == 0 returns GVTM_OK. */
+int gvtm_apply_intonation_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_list_offsets, size_t n_lists,
+		const int32_t* d_list_ids, const gvtm_intonation_point* d_points, const int64_t* d_point_offsets,
+		const int32_t* d_voice_ids, size_t batch, gvtm_event* d_events_out, size_t out_capacity,
+		int64_t* d_event_offsets_out, int32_t* d_status, void* hip_stream);
+
+/* The three steps behind one call: gvtm_apply_intonation_device into an event buffer the plan owns (grown to
+ * events_capacity events: the out_capacity above), then gvtm_synthesize_events_voices_device on the merged lists, all
+ * enqueued on hip_stream.  Samples, counts, peaks, frame counts, drift states and statuses are bit for bit those of the
+ * calls made separately; a refused utterance has 0 frames.  max_frames: gvtm_tracks_frame_count on the host-applied list,
+ * or the bound given with gvtm_intonation_apply_host.  The remaining arguments, checks, status codes and the one-stream
+ * ordering rule are gvtm_synthesize_events_voices_device's (the event buffer is one more of the plan's that the rule
+ * covers); the apply entry's refusals come first, then a null audio buffer and the stride. */
+int gvtm_synthesize_intonation_device(gvtm_plan* plan, const gvtm_event* d_events, const int64_t* d_list_offsets,
+		size_t n_lists, const int32_t* d_list_ids, const gvtm_intonation_point* d_points, const int64_t* d_point_offsets,
+		const int32_t* d_voice_ids, size_t events_capacity, size_t batch, size_t max_frames, float* d_audio,
+		size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift,
+		int32_t* d_status, void* hip_stream);
+
+/*
  * Streams fed event lists.  The reference produces an utterance chunk by chunk (one generateOutput() per /c chunk,
  * Controller.cpp:141-154); a stream takes the next chunk or chunks of each of its utterances as they are parsed, generates
  * their frames on the device straight behind the frames it still holds, synthesizes what can be synthesized and returns
