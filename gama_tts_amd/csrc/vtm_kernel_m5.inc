@@ -371,7 +371,12 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 		const R fvol = pv[3], fpos = pv[4], fcf = pv[5], fbw = pv[6];
 		R* r = s_rfr + u * kN_rfr + (static_cast<size_t>(c & 3) * C + s) * kRfr;
 		const R offset = (27 - 5) * (fpos / R(7.0));
-		const int oi = static_cast<int>(offset);
+		// inside the tube: the section S6 + (int) offset is one of S1..S30, the reference's own arithmetic.  Outside, the
+		// reference indexes its array out of bounds; the product injects nothing (include/gama_vtm.h): the record names
+		// the section kAddNone, which pass N drops.  Decided on the floating offset, so that no cast of a value beyond
+		// the range of int and no wrapped sum is relied upon.
+		const bool inside = offset > R(-6.0) && offset < R(25.0);
+		const int oi = inside ? static_cast<int>(offset) : kAddNone - 5;
 		const R right = offset - oi;
 		r[0] = amplitude_60db_dev(fvol);
 		r[1] = R(1.0) - right;
@@ -529,17 +534,21 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 		R* ru = s_ru + u * kN_ru + (static_cast<size_t>(c & 1) * (C + 2) + s) * kRu;
 		ru[kRuLoss] = mg[0];
 		// the dense "added to the new top" lanes: clear what this record held two chunks ago, then S1 <- tube input and
-		// the two frication sections (a position outside the tube, which the reference would index out of bounds, is dropped)
+		// the two frication sections, any of S1..S30 (A1b names kAddNone for a position outside the tube: nothing is
+		// injected).  S1's lane holds the tube input, so its share is folded into that: bottom * loss + (input + share)
+		// where the reference has (bottom * loss + input) + share (:652, :722), one rounding away (DESIGN.md 4b)
 		int* side = s_side + u * kN_side + (c & 1) * C + s;
 		const int old = *side;
 		R* add = ru + kRuAdd;
 		add[old] = R(0.0);
 		add[old + 1] = R(0.0);
 		const int fl = static_cast<int>(r[3]);
-		const int at = (fl >= 1 && fl <= 28) ? fl : kAddNone;
-		add[at] = fl == at ? fv * r[1] : R(0.0);
-		add[at + 1] = fl == at ? fv * r[2] : R(0.0);
-		add[0] = mg[1];
+		const bool in_tube = static_cast<unsigned>(fl) < static_cast<unsigned>(kAddNone);
+		const int at = in_tube ? fl : kAddNone;
+		const R left = fv * r[1];
+		add[at] = in_tube ? left : R(0.0);
+		add[at + 1] = in_tube ? fv * r[2] : R(0.0);
+		add[0] = fl == 0 ? mg[1] + left : mg[1];
 		*side = at;
 	};
 

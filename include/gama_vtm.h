@@ -155,7 +155,10 @@ typedef struct gvtm_info {
 
 /* The configuration keys VocalTractModel5::loadConfiguration reads (vtm/VocalTractModel5.h:375-421), as numbers:
  * reference model 5 — 30 + 21 sections with flow junctions, Rosenberg B glottal source, pole-zero radiation
- * impedance at mouth and nose, Butterworth noise/source filters, glottal loss, differentiated output. */
+ * impedance at mouth and nose, Butterworth noise/source filters, glottal loss, differentiated output.
+ * The frication enters the section S6 + (int)(22 fricPos / 7) and its right neighbour (:716-726): for every position whose
+ * section is one of S1..S30 (about -1.909 < fricPos < 7.954) a model 5 plan computes what the reference computes; for any
+ * other position, where the reference indexes its array out of bounds, nothing is injected. */
 typedef struct gvtm5_config {
 	double output_rate;
 	int32_t waveform;                         /* 0 pulse, 1 sine */

@@ -1070,13 +1070,19 @@ static real v5_vocal_tract(vtm5_model* m, real input, real frication, real glott
 
 	/* frication noise (:716-726) */
 	const real fric_offset = (27 - 5) * (m->cur[P_FRIC_POS] / RC(7.0 - 0.0));
-	const int fric_int = (int) fric_offset;
-	const real fric_right = fric_offset - fric_int;
-	const real fric_left = RC(1.0) - fric_right;
-	const real fric_amp = amplitude60dB(m->cur[P_FRIC_VOL]);
-	const real fric_value = fric_amp * frication;
-	ot[5 + fric_int][in] += fric_value * fric_left;
-	if (5 + fric_int < 27) ot[5 + fric_int + 1][in] += fric_value * fric_right;
+	/* THE PRODUCT'S RULE, not the reference's: the reference indexes oropharynx_[5 + (int) offset] unguarded, which is
+	 * defined only while that section is one of the 30 (S1..S30: -6 < offset < 25, the cast truncates towards zero).
+	 * Outside -- decided on the floating offset, before a cast that is itself undefined beyond the range of int --
+	 * nothing is injected.  Inside, this is the reference's arithmetic unchanged. */
+	if (fric_offset > RC(-6.0) && fric_offset < RC(25.0)) {
+		const int fric_int = (int) fric_offset;
+		const real fric_right = fric_offset - fric_int;
+		const real fric_left = RC(1.0) - fric_right;
+		const real fric_amp = amplitude60dB(m->cur[P_FRIC_VOL]);
+		const real fric_value = fric_amp * frication;
+		ot[5 + fric_int][in] += fric_value * fric_left;
+		if (5 + fric_int < 27) ot[5 + fric_int + 1][in] += fric_value * fric_right;
+	}
 
 	return mouth_flow + nasal_flow;
 }

@@ -2,8 +2,7 @@
 vectors in tests/golden/vtm_domain_golden.npz): the double and the float restatement reproduce every vector bit for bit,
 so that tests/test_gpu_domain.py may hold the kernels to the oracle there.
 
-Model 5 is not part of the family: its reference indexes its tap array out of bounds for such frication positions, and
-the kernel's rule for it (the share is dropped, csrc/vtm_kernel_m5.inc) has nothing to be compared with."""
+Reference model 5 has a table and a module of its own: tests/domain5_cases.py, tests/test_domain5_cpu.py."""
 import functools
 
 import numpy as np

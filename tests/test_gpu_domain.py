@@ -23,8 +23,7 @@ the rows are ragged, and a prefix ends in the middle of the ramp towards the out
                 female oracle (at ITS internal rate the bandwidth cases are inside tanf's range, 60 kHz stays outside cosf's).
     product     the product library with nothing forced.
 
-Model 5 is not touched: its reference indexes its taps out of bounds for such positions, and the kernel's rule (the share
-is dropped) has no reference to be compared with."""
+Reference model 5 has a table and a module of its own: tests/domain5_cases.py, tests/test_gpu_domain5.py."""
 import functools
 
 import numpy as np
