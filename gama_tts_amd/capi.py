@@ -275,6 +275,13 @@ def load_library(diagnostics=False):
         L.gvtm_debug_device_float_math.argtypes = [vp, i32, vp, sz, vp]
         L.gvtm_debug_group_voices.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp]
         L.gvtm_debug_group_voices.restype = i32
+        if hasattr(L, "gvtm_debug_fir_literals"):
+            L.gvtm_debug_fir_literals.argtypes = [vp]
+            L.gvtm_debug_fir_literals.restype = i32
+            L.gvtm_debug_plan_fir_literals.argtypes = [vp]
+            L.gvtm_debug_plan_fir_literals.restype = i32
+            L.gvtm_debug_force_generic_fir.argtypes = [vp]
+            L.gvtm_debug_force_generic_fir.restype = i32
         if hasattr(L, "gvtm_debug_tracks_append"):
             L.gvtm_debug_tracks_append.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
             L.gvtm_debug_tracks_append.restype = i32
@@ -285,6 +292,14 @@ def load_library(diagnostics=False):
             L.gvtm_debug_tracks_slice.restype = i32
     _libs[diagnostics] = L
     return L
+
+
+def fir_literal_table():
+    """The 47 float coefficients the float kernels hold as literals (diagnostics library)."""
+    out = np.empty(47, dtype=np.float32)
+    n = load_library(True).gvtm_debug_fir_literals(out.ctypes.data)
+    assert n == out.size, n
+    return out
 
 
 def device_count():
@@ -537,6 +552,17 @@ class Plan:
         if n < 0:
             self._check(-n)
         return buf[:n].copy()
+
+    def uses_fir_literals(self):
+        """Diagnostics plans: whether launches take the float decimator's coefficients from the kernels' literal table."""
+        rc = self._lib.gvtm_debug_plan_fir_literals(self._h)
+        if rc < 0:
+            self._check(-rc)
+        return bool(rc)
+
+    def force_generic_fir(self):
+        """Diagnostics plans: later launches run the generic tap loop over the plan's own coefficients."""
+        self._check(self._lib.gvtm_debug_force_generic_fir(self._h))
 
     def output_count(self, frames):
         return int(self._lib.gvtm_output_count(self._h, int(frames)))

@@ -1,5 +1,7 @@
 // The gvtm_debug_* hooks of the diagnostics library (libgama_vtm_diag.so; tests and tools only, not in the public header
 // and not in the product library): forced shapes, taps, cycle counters, math probes and single kernels on caller buffers.
+#include <cstring>
+
 #include "vtm_host.hpp"
 #include "vtm_math.hpp"
 
@@ -67,6 +69,31 @@ int gvtm_debug_chunk_length(const gvtm_plan* plan, size_t batch)
 	const gvtm::LaunchShape shape = plan->launch_shape(batch, 0, false);
 	if (!shape.rows) return 0;
 	return gvtm::synth_chunk_length(plan->designs[0].k, plan->precision, shape.rows);
+}
+
+/* The float decimator's coefficients as the float kernels hold them (gvtm::kGlottalFirF32): out[47].  Needs no device. */
+int gvtm_debug_fir_literals(float* out)
+{
+	if (!out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null buffer");
+	std::memcpy(out, gvtm::kGlottalFirF32, sizeof(gvtm::kGlottalFirF32));
+	return gvtm::kGlottalFirTapsF32;
+}
+
+/* 1: the plan's launches take the decimator's coefficients from that table (a float plan of the models 0 to 4 whose own
+   design equals it bit for bit), 0: they run the generic tap loop over the plan's coefficients; negative: a null plan. */
+int gvtm_debug_plan_fir_literals(const gvtm_plan* plan)
+{
+	if (!plan) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	return plan->fir_literals ? 1 : 0;
+}
+
+/* Makes the plan's later launches run the generic tap loop wherever they would take the literals (there is no way back:
+   make a new plan).  The two float shapes that keep the plan's coefficients in SGPRs (v2::fir_literal_taps) are not affected. */
+int gvtm_debug_force_generic_fir(gvtm_plan* plan)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	plan->fir_literals = false;
+	return GVTM_OK;
 }
 
 /* The plan-level noise-sample table as the host builds it (n floats or doubles); needs no device. */

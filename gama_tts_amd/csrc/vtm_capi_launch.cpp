@@ -57,8 +57,10 @@ gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 	args.wavetable = plan->d_wavetable.ptr;
 	args.fir = plan->d_fir.ptr;
 	std::memset(&args.fir_k, 0, sizeof(args.fir_k));
+	args.fir_literals = plan->fir_literals ? 1 : 0;
 	if (!dg.model5) {
 		if (dg.f32) {
+			// (the coefficients by value: for the two shapes that keep them in SGPRs, v2::fir_literal_taps)
 			for (size_t i = 0; i < dg.fir_f.size() && i < static_cast<size_t>(gvtm::kFirKConsts); ++i) args.fir_k.f[i] = dg.fir_f[i];
 			// the float kernel's plan constants as floats (several voices: the kernel reads each voice's own from kconst)
 			float* kf = args.fir_k.f + gvtm::kFirKConsts;
@@ -75,8 +77,6 @@ gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 			kf[gvtm::kKfMouthARad] = static_cast<float>(dg.k.mouth_a_rad);
 			kf[gvtm::kKfNoseARad] = static_cast<float>(dg.k.nose_a_rad);
 			kf[gvtm::kKfNasalK5] = static_cast<float>(dg.k.nasal_k[5]);
-		} else {
-			for (size_t i = 0; i < dg.fir.size() && i < 49; ++i) args.fir_k.d[i] = dg.fir[i];
 		}
 	}
 	args.src_h = plan->d_src_h.ptr;

@@ -109,6 +109,11 @@ int create_plan(const Config* configs, size_t n_voices, double control_rate, int
 		}
 		plan->precision = configs[0].precision; // (model 5: the one precision the design of its class takes)
 		plan->float5_voices = float5_voices;
+		// the float decimator as this host's libm designs it against the table the float kernels hold as literals: a host
+		// that designs another filter runs the generic tap loop over its own coefficients, and stays right
+		const gvtm::Design& d0 = plan->designs[0];
+		plan->fir_literals = !d0.model5 && d0.f32 && d0.fir_f.size() == static_cast<size_t>(gvtm::kGlottalFirTapsF32)
+				&& std::memcmp(d0.fir_f.data(), gvtm::kGlottalFirF32, sizeof(gvtm::kGlottalFirF32)) == 0;
 		if (device == GVTM_DEVICE_NONE) {
 			// design-only plan: info, tables and output counts work, synthesis reports NO_DEVICE
 			plan->device = GVTM_DEVICE_NONE;

@@ -22,6 +22,29 @@ constexpr int kMaxFirTaps = 64;
 constexpr int kMaxSectionDelay = 4;
 constexpr int kMaxPad = 96;
 
+// The 2:1 decimator of the glottal source as designed in float: design_glottal_fir<float>() (vtm_design.cpp) takes no
+// argument -- WavetableGlottalSourceFIRFilter::maximallyFlat with the three constants of WavetableGlottalSource.h:94-96 --
+// so these 47 coefficients are the same for every voice, rate and plan.  Host and device share them: the float kernels
+// take them as 32-bit literals, and a plan compares its own design with them bit for bit before it says so
+// (vtm_capi_plan.cpp; SynthArgs::fir_literals).  Made from this project's own design: the values design_glottal_fir<float>()
+// returns (a float plan's gvtm_plan_table(GVTM_TABLE_FIR)), each printed exactly as a hexadecimal float;
+// tests/test_fir_literals_cpu.py holds the two against each other.
+constexpr int kGlottalFirTapsF32 = 47;
+constexpr float kGlottalFirF32[kGlottalFirTapsF32] = {
+	0x1.7104f6p-24f, 0x1.e9efcap-23f, -0x1.a0e112p-25f, -0x1.45ce18p-19f,
+	-0x1.a55396p-18f, 0x1.2af00ap-19f, 0x1.6ac7fap-15f, 0x1.246622p-14f,
+	-0x1.6c9652p-14f, -0x1.c5647cp-12f, -0x1.2c53bp-12f, 0x1.28a494p-10f,
+	0x1.3159f6p-9f, -0x1.43030ep-11f, -0x1.d0b9fp-8f, -0x1.842804p-8f,
+	0x1.6f26b8p-7f, 0x1.9513bp-6f, -0x1.6560f2p-10f, -0x1.cb1d68p-5f,
+	-0x1.a3d234p-5f, 0x1.67d89cp-4f, 0x1.2f9eccp-2f, 0x1.9809a4p-2f,
+	0x1.2f9eccp-2f, 0x1.67d89cp-4f, -0x1.a3d234p-5f, -0x1.cb1d68p-5f,
+	-0x1.6560f2p-10f, 0x1.9513bp-6f, 0x1.6f26b8p-7f, -0x1.842804p-8f,
+	-0x1.d0b9fp-8f, -0x1.43030ep-11f, 0x1.3159f6p-9f, 0x1.28a494p-10f,
+	-0x1.2c53bp-12f, -0x1.c5647cp-12f, -0x1.6c9652p-14f, 0x1.246622p-14f,
+	0x1.6ac7fap-15f, 0x1.2af00ap-19f, -0x1.a55396p-18f, -0x1.45ce18p-19f,
+	-0x1.a0e112p-25f, 0x1.e9efcap-23f, 0x1.7104f6p-24f,
+};
+
 // Everything the kernels need besides the tables; plain data, copied to the device by value.
 struct DeviceConstants {
 	// rates and driver loop

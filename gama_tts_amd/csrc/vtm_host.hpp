@@ -106,6 +106,9 @@ struct gvtm_plan {
 	int precision = GVTM_PRECISION_F64;
 	int rows = 0;       // utterances per workgroup; 0 = by batch size (a diagnostics build can force it)
 	bool float5_voices = false; // made by gvtm_plan_create_model5_float_voices: a float model 5 plan that takes the voices entries
+	// a float plan of the models 0 to 4 whose designed decimator is gvtm::kGlottalFirF32 bit for bit (create_plan compares):
+	// its launches take the coefficients as literals (SynthArgs::fir_literals); a diagnostics build can clear it
+	bool fir_literals = false;
 	// design tables on the device: double, or float (as designed) for GVTM_PRECISION_F32
 	DeviceBuffer d_wavetable, d_fir, d_src_h, d_src_dh;
 	DeviceBuffer d_consts, d_consts5; // gvtm::DeviceConstants, gvtm::Model5Constants (model 5 plans only)

@@ -384,6 +384,12 @@ __device__ __forceinline__ size_t voice_row(const SynthArgs& a, size_t slot)
 // which shapes keep the library fallbacks of the float routines in their passes, and which take their plan constants as
 // floats from the kernel arguments (SynthArgs::fir_k: the host fills the block for every float plan, launch_v2 checks it)
 template <int D, int U> constexpr bool far_calls_inline() { return D == 1 && U == 4; }
+// which float shapes take the decimator's coefficients as literals (kGlottalFirF32) in their unrolled tap loop; the others
+// keep them in SGPRs (kernel arguments, SynthArgs::fir_k.f).  Literals for every shape, parent / literals, kernel ms, three
+// interleaved runs each, 500 frames (profiles/fir_literals_ab.md): four rows SectionDelay 2 (x 7500) 335.5 / 319.7 and
+// SectionDelay 1 12.247 / 11.819; one row SectionDelay 2 4.518 / 4.490; but two rows SectionDelay 2 4.777 / 4.793 and one row
+// SectionDelay 1 2.420 / 2.440, each slower by a little more than the parent's spread (0.015, 0.017): those two keep the SGPRs.
+template <int D, int U> constexpr bool fir_literal_taps() { return !((D == 1 && U == 1) || (D == 2 && U == 2)); }
 template <typename CT, int D, int U, bool VOICES> constexpr bool float_arg_consts() { return sizeof(CT) == 4 && !VOICES && !far_calls_inline<D, U>(); }
 
 template <typename CT, typename ST, int D, int U, int C, int NH, int LAYOUT_FLAGS>
@@ -824,13 +830,19 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 				else return __builtin_fma(w, cf, sum);
 			};
 			// The design always yields 49 taps in double and 47 in float (WavetableGlottalSourceFIRFilter.h:137-235 with the
-			// constants of WavetableGlottalSource.h:94-96): the tap loop is unrolled over that count with the coefficients in
-			// scalar registers (kernel arguments), so that the 24 paired LDS reads of a lane are all in flight together
-			// instead of one round trip per pair.
-			// (float only: in double the 98 coefficient SGPRs and the reads in flight cost more registers than the
-			// workgroup has to spare: measured 6-8 % slower at batch 4096)
-			constexpr int kNT = sizeof(CT) == 8 ? 49 : 47;
-			if (sizeof(CT) == 4 && taps == kNT) {
+			// constants of WavetableGlottalSource.h:94-96): the float tap loop is unrolled over that count, so that the 24
+			// paired LDS reads of a lane are all in flight together instead of one round trip per pair, and its coefficients
+			// are the 32-bit literals of kGlottalFirF32 (vtm_design.hpp) -- the same 47 floats for every voice, rate and plan,
+			// so they need no register, no load and no reload (as kernel arguments they were 47 SGPRs that spilled, and
+			// the block reloaded 37 of them lane by lane on the vector pipe).  a.fir_literals: the host found its own design
+			// equal to the table bit for bit; otherwise, and in double, the generic loop over the plan's coefficients in LDS.
+			// (The two shapes fir_literal_taps() leaves out keep the plan's own 47 coefficients in SGPRs, a.fir_k.f, under the
+			// condition they always had: right for any design of that length, so they have nothing to ask the flag.)
+			// (float only: a double is no literal, and 98 coefficient SGPRs with the reads in flight cost more registers than
+			// the workgroup has to spare: measured 6-8 % slower at batch 4096)
+			constexpr int kNT = kGlottalFirTapsF32;
+			constexpr bool kLiteralTaps = fir_literal_taps<D, U>();
+			if (sizeof(CT) == 4 && (kLiteralTaps ? a.fir_literals != 0 : taps == kNT)) {
 				// every read first (the compiler, left alone, issues them two at a time between the multiply-adds and waits
 				// for each pair: a dozen LDS round trips in a row made this the longest per-step pass), then the arithmetic
 				CT2 wv[kNT / 2];
@@ -840,18 +852,10 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 				asm volatile("" ::: "memory");
 #pragma unroll
 				for (int i = 0; i + 1 < kNT; i += 2) {
-					CT c0, c1;
-					if constexpr (sizeof(CT) == 8) { c0 = a.fir_k.d[i]; c1 = a.fir_k.d[i + 1]; }
-					else { c0 = a.fir_k.f[i]; c1 = a.fir_k.f[i + 1]; }
-					acc = fir_mad(wv[i / 2].y, c0, acc);
-					acc = fir_mad(wv[i / 2].x, c1, acc);
+					acc = fir_mad(wv[i / 2].y, CT(kLiteralTaps ? kGlottalFirF32[i] : a.fir_k.f[i]), acc);
+					acc = fir_mad(wv[i / 2].x, CT(kLiteralTaps ? kGlottalFirF32[i + 1] : a.fir_k.f[i + 1]), acc);
 				}
-				{
-					CT cl;
-					if constexpr (sizeof(CT) == 8) cl = a.fir_k.d[kNT - 1];
-					else cl = a.fir_k.f[kNT - 1];
-					acc = fir_mad(wlast, cl, acc);
-				}
+				acc = fir_mad(wlast, CT(kLiteralTaps ? kGlottalFirF32[kNT - 1] : a.fir_k.f[kNT - 1]), acc);
 			} else {
 				int i = 0;
 				if constexpr (U >= 4) {

@@ -63,7 +63,7 @@ struct Stream5Layout {
 	static constexpr size_t bytes() { return (yring() + sizeof(float) * 512 + 15) & ~size_t(15); }
 };
 
-// Plan constants of the all-float kernel as floats, by value behind the decimator's coefficients (SynthArgs::fir_k): the
+// Plan constants of the all-float kernel as floats, by value behind the 64 coefficient slots of SynthArgs::fir_k: the
 // helper passes and the filter wavefronts then take them from scalar registers instead of reading DeviceConstants' doubles
 // in LDS and converting them per lane and pass.  A float plan's constants are floats widened, so these are the same numbers.
 enum FloatConst : int {
@@ -83,9 +83,11 @@ struct SynthArgs {
 	float* maxabs;               // [batch] or null
 	const void* wavetable;       // [512]      design tables: double, or float for GVTM_PRECISION_F32
 	const void* fir;             // [fir_taps]
-	// the same coefficients by value: kernel arguments are read with scalar loads, so the decimator's unrolled tap loop
-	// takes them from SGPRs (d: the double design, f: the float design of GVTM_PRECISION_F32)
-	// (the float view is as long as the double one: the float constants above sit behind the 64 coefficient slots)
+	// by value, read with scalar loads: f[kFirKConsts + FloatConst] holds the float kernel's plan constants (above), f[0..47)
+	// the float design's coefficients.  The float decimator's unrolled tap loop takes its coefficients as the literals of
+	// kGlottalFirF32 (fir_literals below); only the two float shapes that measured slower that way read f[0..47), from SGPRs
+	// (vtm_kernel_v2.inc: fir_literal_taps).  The double and mixed kernels read `fir` through LDS.  (d is unused: it keeps
+	// the block's size and alignment, and with them the layout of the arguments behind it.)
 	union FirByValue { double d[49]; float f[98]; } fir_k;
 	static_assert(sizeof(FirByValue) == sizeof(double) * 49 && kFirKConsts + kKfCount <= 98, "float constants fit behind the float coefficients");
 	const void* src_h;           // [3328]
@@ -111,6 +113,9 @@ struct SynthArgs {
 	// pad, stream_chunk) -- the one-row shape's, so that every launch shape keeps the ring a single-voice stream of that
 	// voice has
 	int stream_chunk = 0;
+	// float plans: `fir` is kGlottalFirF32 bit for bit (the plan compared them when it was made), so the decimator's
+	// unrolled tap loop runs, with its coefficients from that table as literals; 0: the generic loop over `fir`
+	int fir_literals = 0;
 };
 
 struct GroupVoicesArgs {
