@@ -100,7 +100,122 @@ class PackedStats(ctypes.Structure):
                 ("largest_slice", ctypes.c_size_t)]
 
 
+class TrackConfig(ctypes.Structure):
+    """gvtm_track_config"""
+    _fields_ = [("control_period_ms", ctypes.c_int32), ("macro_intonation", ctypes.c_int32), ("micro_intonation", ctypes.c_int32),
+                ("intonation_drift", ctypes.c_int32), ("smooth_intonation", ctypes.c_int32), ("reserved_", ctypes.c_int32),
+                ("initial_pitch", ctypes.c_double), ("mean_pitch", ctypes.c_double), ("drift_deviation", ctypes.c_double),
+                ("drift_sample_rate", ctypes.c_double), ("drift_lowpass_cutoff", ctypes.c_double)]
+
+
 PACKED_ALIGN = 8  # GVTM_PACKED_ALIGN
+
+
+def _prototypes():
+    """The two prototype tables, name -> (restype, argtypes): every function include/gama_vtm.h declares, and every
+    gvtm_debug_* hook csrc/vtm_capi_hooks.cpp defines.  A pointer to one of the structures above is typed; every other
+    pointer is a c_void_p, which takes what _ptr() makes, a byref() and a ctypes array alike.  Written out, not derived:
+    tests/test_capi_prototypes_cpu.py compares them with the C sources."""
+    vp, sz, i, i64, dbl, text = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_char_p
+    config, config5, info = ctypes.POINTER(Config), ctypes.POINTER(Config5), ctypes.POINTER(Info)
+    tracks, stats = ctypes.POINTER(TrackConfig), ctypes.POINTER(PackedStats)
+    product = {
+        "gvtm_status_string": (text, [i]),
+        "gvtm_last_error": (text, []),
+        "gvtm_device_count": (i, []),
+        "gvtm_plan_create": (i, [config, dbl, i, vp]),
+        "gvtm_plan_create_model5": (i, [config5, dbl, i, vp]),
+        "gvtm_plan_create_model5_float": (i, [config5, dbl, i, vp]),
+        "gvtm_plan_destroy": (None, [vp]),
+        "gvtm_plan_info": (i, [vp, info]),
+        "gvtm_plan_table": (i, [vp, i, vp, sz]),
+        "gvtm_output_count": (sz, [vp, sz]),
+        "gvtm_output_capacity": (sz, [vp, sz]),
+        "gvtm_synthesize_batch_device": (i, [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]),
+        "gvtm_synthesize_batch_host": (i, [vp, vp, vp, sz, sz, vp, sz, vp, vp]),
+        "gvtm_synthesize_batch_host_pcm16": (i, [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]),
+        "gvtm_plan_create_voices": (i, [config, sz, dbl, i, vp]),
+        "gvtm_plan_create_model5_voices": (i, [config5, sz, dbl, i, vp]),
+        "gvtm_plan_create_model5_float_voices": (i, [config5, sz, dbl, i, vp]),
+        "gvtm_plan_voice_count": (i, [vp]),
+        "gvtm_plan_voice_info": (i, [vp, i, info]),
+        "gvtm_voice_output_count": (sz, [vp, i, sz]),
+        "gvtm_voices_output_capacity": (sz, [vp, sz]),
+        "gvtm_synthesize_voices_device": (i, [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]),
+        "gvtm_synthesize_voices_host": (i, [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp]),
+        "gvtm_synthesize_voices_host_pcm16": (i, [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]),
+        "gvtm_packed_sample_offsets": (sz, [vp, vp, vp, sz, vp]),
+        "gvtm_synthesize_packed_host": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]),
+        "gvtm_synthesize_packed_host_pcm16": (i, [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]),
+        "gvtm_plan_set_staging_limit": (i, [vp, sz]),
+        "gvtm_plan_packed_stats": (i, [vp, stats]),
+        "gvtm_plan_reserve": (i, [vp, sz]),
+        "gvtm_host_alloc": (i, [sz, vp]),
+        "gvtm_host_free": (None, [vp]),
+        "gvtm_stream_create": (i, [vp, sz, vp]),
+        "gvtm_stream_create_voices": (i, [vp, vp, sz, vp]),
+        "gvtm_stream_destroy": (None, [vp]),
+        "gvtm_stream_reset": (i, [vp]),
+        "gvtm_stream_reset_voices": (i, [vp, vp]),
+        "gvtm_stream_capacity": (sz, [vp, sz]),
+        "gvtm_stream_push": (i, [vp, vp, vp, sz, vp, sz, vp]),
+        "gvtm_stream_finish": (i, [vp, vp, sz, vp, vp]),
+        "gvtm_normalize_batch_device": (i, [vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]),
+        "gvtm_plan_set_timing": (i, [vp, i]),
+        "gvtm_plan_take_kernel_ms": (dbl, [vp, vp]),
+        "gvtm_tracks_frame_count": (sz, [tracks, vp, sz]),
+        "gvtm_generate_tracks_device": (i, [i, tracks, vp, vp, sz, sz, vp, vp, vp, vp]),
+        "gvtm_synthesize_events_device": (i, [vp, tracks, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]),
+        "gvtm_plan_set_voice_tracks": (i, [vp, tracks, sz]),
+        "gvtm_generate_tracks_voices_device": (i, [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]),
+        "gvtm_synthesize_events_voices_device": (i, [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]),
+        "gvtm_tracks_chunks_frame_count": (sz, [tracks, vp, vp, sz]),
+        "gvtm_generate_tracks_chunks_device": (i, [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]),
+        "gvtm_synthesize_events_chunks_device": (i, [vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]),
+        "gvtm_intonation_apply_host": (i64, [tracks, vp, sz, vp, sz, vp, sz, vp]),
+        "gvtm_apply_intonation_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]),
+        "gvtm_synthesize_intonation_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]),
+        "gvtm_stream_push_events": (i, [vp, vp, vp, vp, vp, sz, vp, vp]),
+        "gvtm_stream_get_drift": (i, [vp, vp]),
+        "gvtm_stream_set_drift": (i, [vp, vp]),
+        "gvtm_events_packed_layout": (sz, [vp, vp, vp, vp, vp, sz, vp, vp]),
+        "gvtm_synthesize_events_packed_host": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
+        "gvtm_synthesize_events_packed_host_pcm16": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]),
+        "gvtm_generate_tracks_host": (i, [i, tracks, vp, vp, sz, sz, vp, vp, vp]),
+    }
+    hooks = {
+        "gvtm_debug_set_rows": (i, [vp, i]),
+        "gvtm_debug_lds_bytes": (sz, [vp, i]),
+        "gvtm_debug_launch_shape": (i, [vp, sz, i, vp]),
+        "gvtm_debug_stream_launch_shape": (i, [vp, sz, vp]),
+        "gvtm_debug_chunk_length": (i, [vp, sz]),
+        "gvtm_debug_fir_literals": (i, [vp]),
+        "gvtm_debug_plan_fir_literals": (i, [vp]),
+        "gvtm_debug_force_generic_fir": (i, [vp]),
+        "gvtm_debug_noise_table": (i, [sz, i, vp]),
+        "gvtm_debug_set_taps": (i, [vp, vp]),
+        "gvtm_debug_set_phase_cycles": (i, [vp, vp]),
+        "gvtm_debug_dpp_selftest": (i, [vp, vp]),
+        "gvtm_debug_short_math": (i, [i, vp, sz, vp]),
+        "gvtm_debug_device_float_math": (i, [vp, i, vp, sz, vp]),
+        "gvtm_debug_group_voices": (i, [vp, vp, sz, i, vp, vp, vp, vp]),
+        "gvtm_debug_tracks_append": (i, [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]),
+        "gvtm_debug_tracks_slice": (i, [vp, vp, i64, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]),
+        "gvtm_debug_carry_rows": (i, [vp, vp, vp, vp, sz, sz]),
+    }
+    return product, hooks
+
+
+PROTOTYPES, HOOK_PROTOTYPES = _prototypes()
+# what every build of the library has had; the rest came later, and a variant built from an older commit (GVTM_LIBRARY,
+# tools/ab.py) that lacks some of it still loads: such an entry fails when it is called
+_REQUIRED = (
+    "gvtm_status_string", "gvtm_last_error", "gvtm_device_count", "gvtm_plan_create", "gvtm_plan_create_model5", "gvtm_plan_destroy",
+    "gvtm_plan_info", "gvtm_plan_table", "gvtm_output_count", "gvtm_output_capacity", "gvtm_synthesize_batch_device",
+    "gvtm_synthesize_batch_host", "gvtm_synthesize_batch_host_pcm16", "gvtm_host_alloc", "gvtm_host_free", "gvtm_normalize_batch_device",
+    "gvtm_tracks_frame_count", "gvtm_generate_tracks_device", "gvtm_synthesize_events_device", "gvtm_generate_tracks_host",
+    "gvtm_stream_create", "gvtm_stream_destroy", "gvtm_stream_reset", "gvtm_stream_capacity", "gvtm_stream_push", "gvtm_stream_finish",
+    "gvtm_plan_set_timing", "gvtm_plan_take_kernel_ms")
 
 
 def library_path(diagnostics=False):
@@ -130,168 +245,29 @@ def load_library(diagnostics=False):
     if not os.path.exists(path):
         raise ImportError("%s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(make -C gama_tts_amd/csrc). There is no fallback path." % path)
-    L = ctypes.CDLL(path)
-    vp, sz, dbl, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double, ctypes.c_int
-    L.gvtm_status_string.restype = ctypes.c_char_p
-    L.gvtm_status_string.argtypes = [i32]
-    L.gvtm_last_error.restype = ctypes.c_char_p
-    L.gvtm_device_count.restype = i32
-    L.gvtm_plan_create.argtypes = [ctypes.POINTER(Config), dbl, i32, ctypes.POINTER(vp)]
-    L.gvtm_plan_create.restype = i32
-    L.gvtm_plan_create_model5.argtypes = [ctypes.POINTER(Config5), dbl, i32, ctypes.POINTER(vp)]
-    L.gvtm_plan_create_model5.restype = i32
-    L.gvtm_plan_destroy.argtypes = [vp]
-    L.gvtm_plan_destroy.restype = None
-    L.gvtm_plan_info.argtypes = [vp, ctypes.POINTER(Info)]
-    L.gvtm_plan_info.restype = i32
-    L.gvtm_plan_table.argtypes = [vp, i32, vp, sz]
-    L.gvtm_plan_table.restype = i32
-    L.gvtm_output_count.argtypes = [vp, sz]
-    L.gvtm_output_count.restype = sz
-    L.gvtm_output_capacity.argtypes = [vp, sz]
-    L.gvtm_output_capacity.restype = sz
-    L.gvtm_synthesize_batch_device.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
-    L.gvtm_synthesize_batch_device.restype = i32
-    L.gvtm_synthesize_batch_host.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp]
-    L.gvtm_synthesize_batch_host.restype = i32
-    L.gvtm_synthesize_batch_host_pcm16.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
-    L.gvtm_synthesize_batch_host_pcm16.restype = i32
-    L.gvtm_host_alloc.argtypes = [sz, ctypes.POINTER(vp)]
-    L.gvtm_host_alloc.restype = i32
-    L.gvtm_host_free.argtypes = [vp]
-    L.gvtm_host_free.restype = None
-    L.gvtm_normalize_batch_device.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp, vp, vp]
-    L.gvtm_normalize_batch_device.restype = i32
-    L.gvtm_tracks_frame_count.argtypes = [ctypes.POINTER(TrackConfig), vp, sz]
-    L.gvtm_tracks_frame_count.restype = sz
-    L.gvtm_generate_tracks_device.argtypes = [i32, ctypes.POINTER(TrackConfig), vp, vp, sz, sz, vp, vp, vp, vp]
-    L.gvtm_generate_tracks_device.restype = i32
-    L.gvtm_synthesize_events_device.argtypes = [vp, ctypes.POINTER(TrackConfig), vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
-    L.gvtm_synthesize_events_device.restype = i32
-    L.gvtm_generate_tracks_host.argtypes = [i32, ctypes.POINTER(TrackConfig), vp, vp, sz, sz, vp, vp, vp]
-    L.gvtm_generate_tracks_host.restype = i32
-    L.gvtm_stream_create.argtypes = [vp, sz, ctypes.POINTER(vp)]
-    L.gvtm_stream_create.restype = i32
-    L.gvtm_stream_destroy.argtypes = [vp]
-    L.gvtm_stream_destroy.restype = None
-    L.gvtm_stream_reset.argtypes = [vp]
-    L.gvtm_stream_reset.restype = i32
-    L.gvtm_stream_capacity.argtypes = [vp, sz]
-    L.gvtm_stream_capacity.restype = sz
-    L.gvtm_stream_push.argtypes = [vp, vp, vp, sz, vp, sz, vp]
-    L.gvtm_stream_push.restype = i32
-    L.gvtm_stream_finish.argtypes = [vp, vp, sz, vp, vp]
-    L.gvtm_stream_finish.restype = i32
-    if hasattr(L, "gvtm_stream_create_voices"):
-        L.gvtm_stream_create_voices.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
-        L.gvtm_stream_create_voices.restype = i32
-        L.gvtm_stream_reset_voices.argtypes = [vp, vp]
-        L.gvtm_stream_reset_voices.restype = i32
-    if hasattr(L, "gvtm_plan_create_voices"):  # (library variants built before plans of several voices still load: tools/ab.py)
-        L.gvtm_plan_create_voices.argtypes = [ctypes.POINTER(Config), sz, dbl, i32, ctypes.POINTER(vp)]
-        L.gvtm_plan_create_voices.restype = i32
-        L.gvtm_plan_voice_count.argtypes = [vp]
-        L.gvtm_plan_voice_count.restype = i32
-        L.gvtm_plan_voice_info.argtypes = [vp, i32, ctypes.POINTER(Info)]
-        L.gvtm_plan_voice_info.restype = i32
-        L.gvtm_voice_output_count.argtypes = [vp, i32, sz]
-        L.gvtm_voice_output_count.restype = sz
-        L.gvtm_voices_output_capacity.argtypes = [vp, sz]
-        L.gvtm_voices_output_capacity.restype = sz
-        L.gvtm_synthesize_voices_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
-        L.gvtm_synthesize_voices_device.restype = i32
-        L.gvtm_synthesize_voices_host.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp]
-        L.gvtm_synthesize_voices_host.restype = i32
-        L.gvtm_synthesize_voices_host_pcm16.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp]
-        L.gvtm_synthesize_voices_host_pcm16.restype = i32
-    if hasattr(L, "gvtm_plan_set_voice_tracks"):
-        L.gvtm_plan_set_voice_tracks.argtypes = [vp, ctypes.POINTER(TrackConfig), sz]
-        L.gvtm_plan_set_voice_tracks.restype = i32
-        L.gvtm_generate_tracks_voices_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
-        L.gvtm_generate_tracks_voices_device.restype = i32
-        L.gvtm_synthesize_events_voices_device.argtypes = [vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
-        L.gvtm_synthesize_events_voices_device.restype = i32
-    if hasattr(L, "gvtm_tracks_chunks_frame_count"):
-        L.gvtm_tracks_chunks_frame_count.argtypes = [ctypes.POINTER(TrackConfig), vp, vp, sz]
-        L.gvtm_tracks_chunks_frame_count.restype = sz
-        L.gvtm_generate_tracks_chunks_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
-        L.gvtm_generate_tracks_chunks_device.restype = i32
-        L.gvtm_synthesize_events_chunks_device.argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]
-        L.gvtm_synthesize_events_chunks_device.restype = i32
-    if hasattr(L, "gvtm_intonation_apply_host"):
-        L.gvtm_intonation_apply_host.argtypes = [ctypes.POINTER(TrackConfig), vp, sz, vp, sz, vp, sz, vp]
-        L.gvtm_intonation_apply_host.restype = ctypes.c_int64
-        L.gvtm_apply_intonation_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]
-        L.gvtm_apply_intonation_device.restype = i32
-        L.gvtm_synthesize_intonation_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]
-        L.gvtm_synthesize_intonation_device.restype = i32
-    if hasattr(L, "gvtm_stream_push_events"):
-        L.gvtm_stream_push_events.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
-        L.gvtm_stream_push_events.restype = i32
-        L.gvtm_stream_get_drift.argtypes = [vp, vp]
-        L.gvtm_stream_get_drift.restype = i32
-        L.gvtm_stream_set_drift.argtypes = [vp, vp]
-        L.gvtm_stream_set_drift.restype = i32
-    if hasattr(L, "gvtm_plan_create_model5_voices"):
-        L.gvtm_plan_create_model5_voices.argtypes = [ctypes.POINTER(Config5), sz, dbl, i32, ctypes.POINTER(vp)]
-        L.gvtm_plan_create_model5_voices.restype = i32
-    if hasattr(L, "gvtm_plan_create_model5_float"):
-        L.gvtm_plan_create_model5_float.argtypes = [ctypes.POINTER(Config5), dbl, i32, ctypes.POINTER(vp)]
-        L.gvtm_plan_create_model5_float.restype = i32
-    if hasattr(L, "gvtm_plan_create_model5_float_voices"):
-        L.gvtm_plan_create_model5_float_voices.argtypes = [ctypes.POINTER(Config5), sz, dbl, i32, ctypes.POINTER(vp)]
-        L.gvtm_plan_create_model5_float_voices.restype = i32
-    if hasattr(L, "gvtm_synthesize_packed_host"):
-        L.gvtm_packed_sample_offsets.argtypes = [vp, vp, vp, sz, vp]
-        L.gvtm_packed_sample_offsets.restype = sz
-        L.gvtm_synthesize_packed_host.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]
-        L.gvtm_synthesize_packed_host.restype = i32
-        L.gvtm_synthesize_packed_host_pcm16.argtypes = [vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, vp]
-        L.gvtm_synthesize_packed_host_pcm16.restype = i32
-        L.gvtm_plan_set_staging_limit.argtypes = [vp, sz]
-        L.gvtm_plan_set_staging_limit.restype = i32
-        L.gvtm_plan_packed_stats.argtypes = [vp, ctypes.POINTER(PackedStats)]
-        L.gvtm_plan_packed_stats.restype = i32
-        L.gvtm_plan_reserve.argtypes = [vp, sz]
-        L.gvtm_plan_reserve.restype = i32
-    if hasattr(L, "gvtm_synthesize_events_packed_host"):
-        L.gvtm_events_packed_layout.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
-        L.gvtm_events_packed_layout.restype = sz
-        L.gvtm_synthesize_events_packed_host.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp]
-        L.gvtm_synthesize_events_packed_host.restype = i32
-        L.gvtm_synthesize_events_packed_host_pcm16.argtypes = [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]
-        L.gvtm_synthesize_events_packed_host_pcm16.restype = i32
-    L.gvtm_plan_set_timing.argtypes = [vp, i32]
-    L.gvtm_plan_set_timing.restype = i32
-    L.gvtm_plan_take_kernel_ms.argtypes = [vp, ctypes.POINTER(i32)]
-    L.gvtm_plan_take_kernel_ms.restype = dbl
-    if diagnostics:
-        L.gvtm_debug_set_rows.argtypes = [vp, i32]
-        L.gvtm_debug_set_rows.restype = i32
-        L.gvtm_debug_set_taps.argtypes = [vp, vp]
-        L.gvtm_debug_set_phase_cycles.argtypes = [vp, vp]
-        L.gvtm_debug_dpp_selftest.argtypes = [vp, vp]
-        L.gvtm_debug_short_math.argtypes = [i32, vp, sz, vp]
-        L.gvtm_debug_device_float_math.argtypes = [vp, i32, vp, sz, vp]
-        L.gvtm_debug_group_voices.argtypes = [vp, vp, sz, i32, vp, vp, vp, vp]
-        L.gvtm_debug_group_voices.restype = i32
-        if hasattr(L, "gvtm_debug_fir_literals"):
-            L.gvtm_debug_fir_literals.argtypes = [vp]
-            L.gvtm_debug_fir_literals.restype = i32
-            L.gvtm_debug_plan_fir_literals.argtypes = [vp]
-            L.gvtm_debug_plan_fir_literals.restype = i32
-            L.gvtm_debug_force_generic_fir.argtypes = [vp]
-            L.gvtm_debug_force_generic_fir.restype = i32
-        if hasattr(L, "gvtm_debug_tracks_append"):
-            L.gvtm_debug_tracks_append.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
-            L.gvtm_debug_tracks_append.restype = i32
-            L.gvtm_debug_carry_rows.argtypes = [vp, vp, vp, vp, sz, sz]
-            L.gvtm_debug_carry_rows.restype = i32
-        if hasattr(L, "gvtm_debug_tracks_slice"):
-            L.gvtm_debug_tracks_slice.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]
-            L.gvtm_debug_tracks_slice.restype = i32
-    _libs[diagnostics] = L
-    return L
+    lib = ctypes.CDLL(path)
+    table = {**PROTOTYPES, **HOOK_PROTOTYPES} if diagnostics else PROTOTYPES
+    for name, (restype, argtypes) in table.items():
+        fn = getattr(lib, name, None)  # None: a variant from before the entry existed
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
+        elif name in _REQUIRED:
+            raise ImportError("%s does not export %s: it is no build of include/gama_vtm.h. There is no fallback path." % (path, name))
+    _libs[diagnostics] = lib
+    return lib
+
+
+def _check(lib, rc):
+    """Raises GvtmError for a status other than 0, with the failing call's message or else the status's name."""
+    if rc != 0:
+        raise GvtmError(rc, lib.gvtm_last_error().decode() or lib.gvtm_status_string(rc).decode())
+
+
+def _count(lib, n):
+    """The result of an entry that returns a size_t, (size_t)-1 for a refused call."""
+    if n == ctypes.c_size_t(-1).value:
+        raise GvtmError(1, lib.gvtm_last_error().decode())
+    return n
 
 
 def fir_literal_table():
@@ -315,9 +291,7 @@ class PinnedArray:
         self.array = None
         self._ptr = ctypes.c_void_p()
         nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        rc = self._lib.gvtm_host_alloc(max(nbytes, 1), ctypes.byref(self._ptr))
-        if rc != 0:
-            raise GvtmError(rc, self._lib.gvtm_last_error().decode())
+        _check(self._lib, self._lib.gvtm_host_alloc(max(nbytes, 1), ctypes.byref(self._ptr)))
         buf = (ctypes.c_char * max(nbytes, 1)).from_address(self._ptr.value)
         self.array = np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
 
@@ -390,15 +364,7 @@ def config5_from_dict(d, output_rate=None, precision=PRECISION_F64):
     return c
 
 
-class TrackConfig(ctypes.Structure):
-    """gvtm_track_config"""
-    _fields_ = [("control_period_ms", ctypes.c_int32), ("macro_intonation", ctypes.c_int32), ("micro_intonation", ctypes.c_int32),
-                ("intonation_drift", ctypes.c_int32), ("smooth_intonation", ctypes.c_int32), ("reserved_", ctypes.c_int32),
-                ("initial_pitch", ctypes.c_double), ("mean_pitch", ctypes.c_double), ("drift_deviation", ctypes.c_double),
-                ("drift_sample_rate", ctypes.c_double), ("drift_lowpass_cutoff", ctypes.c_double)]
-
-
-# gvtm_event / gvtm_drift_state as numpy record layouts (296 and 40 bytes)
+# gvtm_event / gvtm_drift_state as numpy record layouts
 EVENT_DTYPE = np.dtype([("time_ms", "<i4"), ("has_interp", "<i4"), ("interp", "<f8", 4), ("param", "<f8", 16),
                         ("special", "<f8", 16)])
 DRIFT_DTYPE = np.dtype([("seed", "<f8"), ("x1", "<f8"), ("x2", "<f8"), ("y1", "<f8"), ("y2", "<f8")])
@@ -420,10 +386,7 @@ def events_from_table(table):
 def tracks_frame_count(config, events):
     lib = load_library()
     events = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
-    n = lib.gvtm_tracks_frame_count(ctypes.byref(config), _ptr(events), events.shape[0])
-    if n == ctypes.c_size_t(-1).value:
-        raise GvtmError(1, lib.gvtm_last_error().decode())
-    return n
+    return _count(lib, lib.gvtm_tracks_frame_count(ctypes.byref(config), _ptr(events), events.shape[0]))
 
 
 def tracks_chunks_frame_count(config, events, chunk_offsets):
@@ -431,10 +394,8 @@ def tracks_chunks_frame_count(config, events, chunk_offsets):
     lib = load_library()
     events = np.ascontiguousarray(events, dtype=EVENT_DTYPE)
     chunk_offsets = np.ascontiguousarray(chunk_offsets, dtype=np.int64)
-    n = lib.gvtm_tracks_chunks_frame_count(ctypes.byref(config), _ptr(events), _ptr(chunk_offsets), max(chunk_offsets.shape[0] - 1, 0))
-    if n == ctypes.c_size_t(-1).value:
-        raise GvtmError(1, lib.gvtm_last_error().decode())
-    return n
+    return _count(lib, lib.gvtm_tracks_chunks_frame_count(ctypes.byref(config), _ptr(events), _ptr(chunk_offsets),
+                                                          max(chunk_offsets.shape[0] - 1, 0)))
 
 
 # gvtm_intonation_point as a numpy record layout (24 bytes)
@@ -478,20 +439,16 @@ def generate_tracks_host(config, event_lists, max_frames, drift=None, device=0):
         dr = np.zeros(batch, dtype=DRIFT_DTYPE)
         for b, st in enumerate(drift):
             dr[b] = tuple(st)
-    rc = lib.gvtm_generate_tracks_host(int(device), ctypes.byref(config), _ptr(events), _ptr(offsets), batch, int(max_frames),
-                                       _ptr(params), _ptr(counts), _ptr(dr))
-    if rc != 0:
-        raise GvtmError(rc, lib.gvtm_last_error().decode() or lib.gvtm_status_string(rc).decode())
+    _check(lib, lib.gvtm_generate_tracks_host(int(device), ctypes.byref(config), _ptr(events), _ptr(offsets), batch, int(max_frames),
+                                              _ptr(params), _ptr(counts), _ptr(dr)))
     return params, counts, dr
 
 
 def generate_tracks_device(config, d_events, d_offsets, batch, max_frames, d_params, d_frame_counts=None, d_drift=None,
                            stream=None, device=0):
     lib = load_library()
-    rc = lib.gvtm_generate_tracks_device(int(device), ctypes.byref(config), _ptr(d_events), _ptr(d_offsets), int(batch),
-                                         int(max_frames), _ptr(d_params), _ptr(d_frame_counts), _ptr(d_drift), _ptr(stream))
-    if rc != 0:
-        raise GvtmError(rc, lib.gvtm_last_error().decode() or lib.gvtm_status_string(rc).decode())
+    _check(lib, lib.gvtm_generate_tracks_device(int(device), ctypes.byref(config), _ptr(d_events), _ptr(d_offsets), int(batch),
+                                                int(max_frames), _ptr(d_params), _ptr(d_frame_counts), _ptr(d_drift), _ptr(stream)))
 
 
 def _ptr(x):
@@ -512,28 +469,33 @@ class Plan:
         """diagnostics=True binds the plan to libgama_vtm_diag.so (gvtm_debug_* hooks); rows (diagnostics only) forces
         the utterances per workgroup, i.e. the kernel shape a big batch would get.  float_model5=True (a Config5 with
         precision PRECISION_F32) makes the plan of VocalTractModel5<float,1> through gvtm_plan_create_model5_float."""
-        self._lib = load_library(diagnostics)
-        self.diagnostics = bool(diagnostics)
-        self._h = ctypes.c_void_p()
+        self._open(diagnostics)
         self.config = config
         create = self._lib.gvtm_plan_create_model5 if isinstance(config, Config5) else self._lib.gvtm_plan_create
         if float_model5:
             if not isinstance(config, Config5):
                 raise ValueError("float_model5 needs a Config5")
             create = self._lib.gvtm_plan_create_model5_float
-        rc = create(ctypes.byref(config), float(control_rate), int(device), ctypes.byref(self._h))
+        self._created(create(ctypes.byref(config), float(control_rate), int(device), ctypes.byref(self._h)), rows)
+
+    def _open(self, diagnostics):
+        self._lib = load_library(diagnostics)
+        self.diagnostics = bool(diagnostics)
+        self._h = ctypes.c_void_p()
+
+    def _created(self, rc, rows):
+        """What follows gvtm_plan_create* for every plan: its status, the plan's info (voice 0's) and the forced rows."""
         self._check(rc)
-        info = Info()
-        self._check(self._lib.gvtm_plan_info(self._h, ctypes.byref(info)))
-        self.info = info
+        self.info = Info()
+        self._check(self._lib.gvtm_plan_info(self._h, ctypes.byref(self.info)))
         if rows:
-            if not diagnostics:
+            if not self.diagnostics:
                 raise ValueError("rows can only be forced on a diagnostics plan")
             self._check(self._lib.gvtm_debug_set_rows(self._h, int(rows)))
 
     def _check(self, rc):
         if rc != 0:
-            raise GvtmError(rc, self._lib.gvtm_last_error().decode() or self._lib.gvtm_status_string(rc).decode())
+            _check(self._lib, rc)
 
     def close(self):
         if self._h:
@@ -586,22 +548,30 @@ class Plan:
             self._h, _ptr(d_params), _ptr(d_frame_counts), int(batch), int(max_frames), _ptr(d_audio),
             int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(stream)))
 
-    def synthesize_host(self, params, frame_counts=None):
-        """params: float32 [B][F][16] numpy -> (audio float32 [B][stride], counts int64 [B], maxabs float32 [B])."""
+    @staticmethod
+    def _host_outputs(batch, shape, dtype):
+        """The arrays a host entry fills: (samples of dtype, [batch][stride] or packed [capacity]; counts int64 [batch]; maxabs
+        float32 [batch]; scales float32 [batch] with int16 samples, else None)."""
+        return (np.zeros(shape, dtype=dtype), np.zeros(batch, dtype=np.int64), np.zeros(batch, dtype=np.float32),
+                np.zeros(batch, dtype=np.float32) if dtype == np.int16 else None)
+
+    def _host(self, params, frame_counts, dtype):
         params = np.ascontiguousarray(params, dtype=np.float32)
         assert params.ndim == 3 and params.shape[2] == N_PARAM
         batch, frames = params.shape[:2]
+        assert frame_counts is None or np.shape(frame_counts) == (batch,)
         stride = self.output_count(frames) if frame_counts is None else self.output_capacity(frames)
-        audio = np.zeros((batch, stride), dtype=np.float32)
-        counts = np.zeros(batch, dtype=np.int64)
-        maxabs = np.zeros(batch, dtype=np.float32)
-        fc = None
-        if frame_counts is not None:
-            fc = np.ascontiguousarray(frame_counts, dtype=np.int32)
-            assert fc.shape == (batch,)
-        self._check(self._lib.gvtm_synthesize_batch_host(
-            self._h, _ptr(params), _ptr(fc), batch, frames, _ptr(audio), stride, _ptr(counts), _ptr(maxabs)))
-        return audio, counts, maxabs
+        out, counts, maxabs, scales = self._host_outputs(batch, (batch, stride), dtype)
+        self.synthesize_host_into(params, out, frame_counts, counts, maxabs, scales)
+        return out, counts, maxabs, scales
+
+    def synthesize_host(self, params, frame_counts=None):
+        """params: float32 [B][F][16] numpy -> (audio float32 [B][stride], counts int64 [B], maxabs float32 [B])."""
+        return self._host(params, frame_counts, np.float32)[:3]
+
+    def synthesize_host_pcm16(self, params, frame_counts=None):
+        """-> (pcm int16 [B][stride], counts int64 [B], maxabs float32 [B], scales float32 [B])"""
+        return self._host(params, frame_counts, np.int16)
 
     def synthesize_host_into(self, params, out, frame_counts=None, counts=None, maxabs=None, scales=None):
         """The host entries with caller-owned (e.g. page-locked) buffers: `out` float32 [B][stride] takes the unscaled
@@ -619,18 +589,6 @@ class Plan:
             assert out.dtype == np.float32 and scales is None
             self._check(self._lib.gvtm_synthesize_batch_host(
                 self._h, _ptr(params), _ptr(fc), batch, frames, _ptr(out), out.shape[1], _ptr(counts), _ptr(maxabs)))
-
-    def synthesize_host_pcm16(self, params, frame_counts=None):
-        """-> (pcm int16 [B][stride], counts int64 [B], maxabs float32 [B], scales float32 [B])"""
-        params = np.ascontiguousarray(params, dtype=np.float32)
-        batch, frames = params.shape[:2]
-        stride = self.output_count(frames) if frame_counts is None else self.output_capacity(frames)
-        pcm = np.zeros((batch, stride), dtype=np.int16)
-        counts = np.zeros(batch, dtype=np.int64)
-        maxabs = np.zeros(batch, dtype=np.float32)
-        scales = np.zeros(batch, dtype=np.float32)
-        self.synthesize_host_into(params, pcm, frame_counts, counts, maxabs, scales)
-        return pcm, counts, maxabs, scales
 
     # ---- ragged batches, packed in and packed out (a VoicesPlan has them too; voice_ids: one per utterance) ----
 
@@ -655,9 +613,7 @@ class Plan:
         frame_offsets = np.ascontiguousarray(frame_offsets, dtype=np.int64)
         batch = frame_offsets.shape[0] - 1
         out = np.zeros(batch + 1, dtype=np.int64)
-        n = self._lib.gvtm_packed_sample_offsets(self._h, _ptr(frame_offsets), _ptr(self._ids(voice_ids, batch)), batch, _ptr(out))
-        if n == ctypes.c_size_t(-1).value:
-            raise GvtmError(1, self._lib.gvtm_last_error().decode())
+        _count(self._lib, self._lib.gvtm_packed_sample_offsets(self._h, _ptr(frame_offsets), _ptr(self._ids(voice_ids, batch)), batch, _ptr(out)))
         return out
 
     def synthesize_packed_host_into(self, frames, frame_offsets, out, voice_ids=None, sample_offsets=None, counts=None, maxabs=None,
@@ -683,10 +639,7 @@ class Plan:
         frames, frame_offsets = self.pack_utterances(utterances)
         batch = len(utterances)
         offsets = self.packed_sample_offsets(frame_offsets, voice_ids)
-        out = np.zeros(int(offsets[batch]), dtype=dtype)
-        counts = np.zeros(batch, dtype=np.int64)
-        maxabs = np.zeros(batch, dtype=np.float32)
-        scales = np.zeros(batch, dtype=np.float32) if dtype == np.int16 else None
+        out, counts, maxabs, scales = self._host_outputs(batch, int(offsets[batch]), dtype)
         self.synthesize_packed_host_into(frames, frame_offsets, out, voice_ids, offsets, counts, maxabs, scales)
         return out, offsets, counts, maxabs, scales
 
@@ -741,10 +694,8 @@ class Plan:
         utt_chunks = np.ascontiguousarray(utt_chunks, dtype=np.int64)
         batch = utt_chunks.shape[0] - 1
         frame_offsets, sample_offsets = np.zeros(batch + 1, dtype=np.int64), np.zeros(batch + 1, dtype=np.int64)
-        n = self._lib.gvtm_events_packed_layout(self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks), _ptr(self._ids(voice_ids, batch)),
-                                                batch, _ptr(frame_offsets), _ptr(sample_offsets))
-        if n == ctypes.c_size_t(-1).value:
-            raise GvtmError(1, self._lib.gvtm_last_error().decode())
+        _count(self._lib, self._lib.gvtm_events_packed_layout(self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks),
+                                                              _ptr(self._ids(voice_ids, batch)), batch, _ptr(frame_offsets), _ptr(sample_offsets)))
         return frame_offsets, sample_offsets
 
     def synthesize_events_packed_host_into(self, events, chunk_offsets, utt_chunks, out, voice_ids=None, sample_offsets=None,
@@ -814,9 +765,7 @@ class VoicesPlan(Plan):
     entries (Plan.synthesize_*, Stream) are refused on it when it has two or more."""
 
     def __init__(self, configs, control_rate=250.0, device=0, diagnostics=False, rows=0, float_model5=False):
-        self._lib = load_library(diagnostics)
-        self.diagnostics = bool(diagnostics)
-        self._h = ctypes.c_void_p()
+        self._open(diagnostics)
         self.configs = list(configs)
         self.config = self.configs[0] if self.configs else None
         model5 = isinstance(self.config, Config5)
@@ -827,13 +776,8 @@ class VoicesPlan(Plan):
         create5 = "gvtm_plan_create_model5_float_voices" if float_model5 else "gvtm_plan_create_model5_voices"
         ctype, create = (Config5, getattr(self._lib, create5)) if model5 else (Config, self._lib.gvtm_plan_create_voices)
         arr = (ctype * max(len(self.configs), 1))(*self.configs)
-        self._check(create(arr, len(self.configs), float(control_rate), int(device), ctypes.byref(self._h)))
+        self._created(create(arr, len(self.configs), float(control_rate), int(device), ctypes.byref(self._h)), rows)
         self.n_voices = int(self._lib.gvtm_plan_voice_count(self._h))
-        self.info = self.voice_info(0)
-        if rows:
-            if not diagnostics:
-                raise ValueError("rows can only be forced on a diagnostics plan")
-            self._check(self._lib.gvtm_debug_set_rows(self._h, int(rows)))
 
     def voice_info(self, voice):
         info = Info()
@@ -884,7 +828,7 @@ class VoicesPlan(Plan):
             self._h, _ptr(d_events), _ptr(d_chunk_offsets), _ptr(d_utt_chunks), _ptr(d_voice_ids), int(batch), int(max_frames),
             _ptr(d_audio), int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift), _ptr(stream)))
 
-    def _host_args(self, params, voice_ids, frame_counts):
+    def _voices_host(self, params, voice_ids, frame_counts, dtype):
         params = np.ascontiguousarray(params, dtype=np.float32)
         assert params.ndim == 3 and params.shape[2] == N_PARAM
         batch, frames = params.shape[:2]
@@ -894,31 +838,24 @@ class VoicesPlan(Plan):
         if frame_counts is not None:
             fc = np.ascontiguousarray(frame_counts, dtype=np.int32)
             assert fc.shape == (batch,)
-        return params, ids, fc, batch, frames
+        stride = self.voices_output_capacity(frames)
+        out, counts, maxabs, scales = self._host_outputs(batch, (batch, stride), dtype)
+        if scales is None:
+            self._check(self._lib.gvtm_synthesize_voices_host(
+                self._h, _ptr(params), _ptr(fc), _ptr(ids), frames, batch, _ptr(out), stride, _ptr(counts), _ptr(maxabs)))
+        else:
+            self._check(self._lib.gvtm_synthesize_voices_host_pcm16(
+                self._h, _ptr(params), _ptr(fc), _ptr(ids), frames, batch, _ptr(out), stride, _ptr(counts), _ptr(maxabs), _ptr(scales)))
+        return out, counts, maxabs, scales
 
     def synthesize_host(self, params, voice_ids, frame_counts=None):
         """params float32 [B][F][16], voice_ids int [B] -> (audio float32 [B][stride], counts int64 [B], maxabs float32 [B]);
         stride = voices_output_capacity(F), rows zero beyond their count."""
-        params, ids, fc, batch, frames = self._host_args(params, voice_ids, frame_counts)
-        stride = self.voices_output_capacity(frames)
-        audio = np.zeros((batch, stride), dtype=np.float32)
-        counts = np.zeros(batch, dtype=np.int64)
-        maxabs = np.zeros(batch, dtype=np.float32)
-        self._check(self._lib.gvtm_synthesize_voices_host(
-            self._h, _ptr(params), _ptr(fc), _ptr(ids), frames, batch, _ptr(audio), stride, _ptr(counts), _ptr(maxabs)))
-        return audio, counts, maxabs
+        return self._voices_host(params, voice_ids, frame_counts, np.float32)[:3]
 
     def synthesize_host_pcm16(self, params, voice_ids, frame_counts=None):
         """-> (pcm int16 [B][stride], counts int64 [B], maxabs float32 [B], scales float32 [B])"""
-        params, ids, fc, batch, frames = self._host_args(params, voice_ids, frame_counts)
-        stride = self.voices_output_capacity(frames)
-        pcm = np.zeros((batch, stride), dtype=np.int16)
-        counts = np.zeros(batch, dtype=np.int64)
-        maxabs = np.zeros(batch, dtype=np.float32)
-        scales = np.zeros(batch, dtype=np.float32)
-        self._check(self._lib.gvtm_synthesize_voices_host_pcm16(
-            self._h, _ptr(params), _ptr(fc), _ptr(ids), frames, batch, _ptr(pcm), stride, _ptr(counts), _ptr(maxabs), _ptr(scales)))
-        return pcm, counts, maxabs, scales
+        return self._voices_host(params, voice_ids, frame_counts, np.int16)
 
 
 class Stream:
@@ -983,12 +920,7 @@ class Stream:
         int32 [batch], the frames generated per utterance).  stride: the audio row length, by default capacity() of the
         largest frame total of the push."""
         assert len(utterances) == self.batch
-        chunks = [np.ascontiguousarray(events_from_table(t)) for u in utterances for t in u]
-        chunk_offsets = np.zeros(len(chunks) + 1, dtype=np.int64)
-        chunk_offsets[1:] = np.cumsum([len(c) for c in chunks])
-        utt_chunks = np.zeros(self.batch + 1, dtype=np.int64)
-        utt_chunks[1:] = np.cumsum([len(u) for u in utterances])
-        events = np.concatenate(chunks) if chunks else np.zeros(0, dtype=EVENT_DTYPE)
+        events, chunk_offsets, utt_chunks = Plan.pack_event_lists(utterances)
         if stride is None:
             # the frames of a list follow from its times and the control period alone, the plan's 1000 / control rate
             counter = TrackConfig()

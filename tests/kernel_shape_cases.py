@@ -2,7 +2,6 @@
 
     precision {f64, mixed, f32} x SectionDelay {1, 2, 3, 4} x output rate {44100, 22050} x rows {1, 2, 4, 8}
     on the 10 + 6 tube, the same with SectionDelay 1 on the 30 + 18 tube (the 48-lane layout), and model 5 rows {1, 2}"""
-import ctypes
 import os
 
 import gama_tts_amd as g
@@ -35,8 +34,6 @@ def launched_rows(name, rows):
 def lds_bytes():
     """{(plan name, rows): bytes} of every case, as the diagnostics library answers."""
     lib = g.load_library(diagnostics=True)
-    lib.gvtm_debug_lds_bytes.restype = ctypes.c_size_t
-    lib.gvtm_debug_lds_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
     out = {}
     for name, config, model5 in plans():
         plan = g.Plan(config, 250.0, capi.DEVICE_NONE, diagnostics=True)

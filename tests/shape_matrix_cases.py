@@ -22,7 +22,6 @@ different DPP rows of a two- or four-row workgroup, and the last workgroup is pa
         running over the following chunks."""
 import collections
 import ctypes
-import functools
 
 import numpy as np
 
@@ -83,16 +82,8 @@ def plan_of(cell, crate=250.0, device=0, rows=None):
                      rows=cell.rows if rows is None else rows, device=device)
 
 
-@functools.lru_cache(maxsize=None)
 def hooks():
-    lib = g.load_library(diagnostics=True)
-    lib.gvtm_debug_stream_launch_shape.restype = ctypes.c_int
-    lib.gvtm_debug_stream_launch_shape.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
-    lib.gvtm_debug_launch_shape.restype = ctypes.c_int
-    lib.gvtm_debug_launch_shape.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
-    lib.gvtm_debug_chunk_length.restype = ctypes.c_int
-    lib.gvtm_debug_chunk_length.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-    return lib
+    return g.load_library(diagnostics=True)
 
 
 def launch_shape(plan, batch=BATCH):

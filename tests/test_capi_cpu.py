@@ -321,7 +321,6 @@ def test_noise_table_is_the_reference_sequence():
     NoiseSource::getSample + NoiseFilter::filter (vtm/NoiseSource.h:40-44, vtm/NoiseFilter.h:63-68): seed 0.7892347,
     seed = frac(seed * 377) with the product rounded first, sample seed - 0.5, y = x + x1 in TFloat."""
     lib = g.load_library(diagnostics=True)
-    lib.gvtm_debug_noise_table.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     n = 100000
     seed = np.float64(0.7892347)
     white = np.empty(n, np.float64)
@@ -343,8 +342,6 @@ def test_every_plan_has_a_workgroup_shape_that_fits_the_lds(precision):
     """160 KB of LDS per workgroup: one utterance per workgroup must always fit (the launch falls back to it), and the
     shapes the headline workloads use (four utterances per workgroup, up-sampling plans) must keep fitting."""
     lib = g.load_library(diagnostics=True)
-    lib.gvtm_debug_lds_bytes.restype = ctypes.c_size_t
-    lib.gvtm_debug_lds_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
     cfgd = g.read_config_file(oracle.VOICE_MALE)
     for delay in (1, 2, 3, 4):
         for rate in (16000.0, 22050.0, 44100.0, 48000.0):

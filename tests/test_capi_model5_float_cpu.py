@@ -157,10 +157,6 @@ def test_shapes_of_the_float_class_and_the_batch_size_that_picks_them():
     beyond; a diagnostics plan forces either as rows 1 / rows 2.  The numbers follow from Offsets<> in float
     (csrc/vtm_kernel_m5.inc) and are what DESIGN.md 4b states; the queries answer from the function every launch asks."""
     lib = g.load_library(diagnostics=True)
-    lib.gvtm_debug_lds_bytes.restype = ctypes.c_size_t
-    lib.gvtm_debug_lds_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.gvtm_debug_launch_shape.restype = ctypes.c_int
-    lib.gvtm_debug_launch_shape.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
     d = g.read_config_file(oracle.VOICE5_MALE)
     cfg = g.config5_from_dict(d, 48000.0, capi.PRECISION_F32)
     chunk60, chunk56 = 84992, 80800

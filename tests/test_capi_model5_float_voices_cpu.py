@@ -166,8 +166,6 @@ def test_launch_shapes_do_not_depend_on_the_voice(voice):
     """Chunk 60 (84 992 B of LDS) up to 256 utterances, chunk 56 (80 800 B) beyond: tests/test_capi_model5_float_cpu.py
     for the male voice."""
     lib = g.load_library(diagnostics=True)
-    lib.gvtm_debug_launch_shape.restype = ctypes.c_int
-    lib.gvtm_debug_launch_shape.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
     plan = _plan(voice, diagnostics=True)
     for batch, lds in ((1, 84992), (256, 84992), (257, 80800), (4096, 80800)):
         out = (ctypes.c_size_t * 3)()

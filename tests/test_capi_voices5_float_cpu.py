@@ -152,8 +152,6 @@ def test_a_design_only_plan_has_no_device_and_takes_voice_tracks():
 
 def test_the_shape_of_a_voices_launch_follows_the_float_class_rule():
     lib = g.load_library(diagnostics=True)
-    lib.gvtm_debug_launch_shape.restype = ctypes.c_int
-    lib.gvtm_debug_launch_shape.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
 
     def shape(plan, batch):
         out = (ctypes.c_size_t * 3)()

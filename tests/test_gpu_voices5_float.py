@@ -94,7 +94,6 @@ def test_more_than_256_utterances_take_the_chunk_56_voice_variant():
     probe = g.VoicesPlan(configs5f(), 250.0, capi.DEVICE_NONE, diagnostics=True, float_model5=True)
     import ctypes
     out = (ctypes.c_size_t * 3)()
-    lib.gvtm_debug_launch_shape.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
     assert lib.gvtm_debug_launch_shape(probe._h, 300, 1, out) == 0 and (out[0], out[2]) == (1, 80800)
     plan = plan_of()
     params, ids, frames = mixed_batch(300, 6, 5, seed=62)

@@ -75,8 +75,6 @@ def test_rows_of_a_launch_follow_batch_size_precision_forced_rows_voices_and_lds
     as many rows while the LDS of a workgroup exceeds 160 KB.  The LDS bytes of the chosen rows are the recorded ones."""
     golden = json.load(open(GOLDEN))["lds_bytes"]
     lib = g.load_library(diagnostics=True)
-    lib.gvtm_debug_launch_shape.restype = ctypes.c_int
-    lib.gvtm_debug_launch_shape.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
     halved = 0
     for name, config, model5 in plans():
         for forced in (0, 1, 2, 4, 8):

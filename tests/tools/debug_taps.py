@@ -26,7 +26,6 @@ d_params = torch.from_numpy(params).to(dev)
 d_audio = torch.zeros((2, n), dtype=torch.float32, device=dev)
 d_taps = torch.zeros((2, steps, 8), dtype=torch.float64, device=dev)
 lib = g.load_library(diagnostics=True)
-lib.gvtm_debug_set_taps.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 lib.gvtm_debug_set_taps(plan._h, ctypes.c_void_p(d_taps.data_ptr()))
 plan.synthesize_device(d_params, 2, frames, d_audio, n)
 torch.cuda.synchronize()

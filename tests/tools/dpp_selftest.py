@@ -1,5 +1,5 @@
 """GPU-box check of the DPP lane directions the tube wavefront relies on."""
-import ctypes, sys
+import sys
 import numpy as np
 sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import gama_tts_amd as g
@@ -7,7 +7,6 @@ import oracle
 plan = g.Plan(g.config_from_dict(g.read_config_file(oracle.VOICE_MALE)), 250.0, 0, diagnostics=True)
 lib = g.load_library(diagnostics=True)
 out = np.zeros(640, dtype=np.int32)
-lib.gvtm_debug_dpp_selftest.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 rc = lib.gvtm_debug_dpp_selftest(plan._h, out.ctypes.data)
 print("rc", rc)
 for name, row in zip(("from_left (row_shr:1)", "from_right (row_shl:1)", "row_ror:6", "row_ror:10", "wave_shr:1", "wave_shl:1",

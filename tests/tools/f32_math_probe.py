@@ -8,7 +8,6 @@ import oracle
 
 plan = g.Plan(g.config_from_dict(g.read_config_file(oracle.VOICE_MALE), precision=capi.PRECISION_F32), 250.0, 0, diagnostics=True)
 lib = g.load_library(diagnostics=True)
-lib.gvtm_debug_device_float_math.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
 ol = oracle.lib()
 ol.vtmo_libm_powf.argtypes = [ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
 ol.vtmo_libm_tanf_cosf.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]

@@ -25,7 +25,6 @@ d_params = torch.from_numpy(params).to(dev)
 d_audio = torch.zeros((batch, n), dtype=torch.float32, device=dev)
 d_cyc = torch.zeros((batch, 16), dtype=torch.int64, device=dev)
 lib = g.load_library(diagnostics=True)
-lib.gvtm_debug_set_phase_cycles.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
 for rep in range(2):
     lib.gvtm_debug_set_phase_cycles(plan._h, ctypes.c_void_p(d_cyc.data_ptr()))
     plan.set_timing(True)
