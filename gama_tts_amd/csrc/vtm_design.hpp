@@ -186,6 +186,45 @@ GVTM_DESIGN_HD uint64_t src_output_count(unsigned time_inc, int pad, int upsampl
 	return src_flush_overrun(time_inc, pad, steps, k_from, k_to) ? k_to : k_from;
 }
 
+// The output sample ranges of a launch's chunks without a division per chunk (host, device and
+// tests/test_bounds_recurrence_cpu.py run this text).
+//
+// The first output sample whose read position lies at or behind internal sample n is Q(n) = ceil(n * 2^16 / time_inc),
+// here as q = (n * 2^16 + time_inc - 1) / time_inc with its remainder r.  A chunk of C steps further on the numerator has
+// grown by C * 2^16 = dq * time_inc + dr, so q grows by dq and r by dr, with one carry into q when r reaches time_inc:
+// integers throughout, hence exactly the value the division gives.  The kernels that go this way divide twice per
+// utterance and launch (the quotient at step_base, which is Extent::k_first and whose remainder one multiplication gives,
+// and the end of the last chunk, which is no multiple of C away) and advance once per chunk.
+struct SrcBounds {
+	unsigned long long q; // (n * 2^16 + time_inc - 1) / time_inc
+	unsigned r;           // (n * 2^16 + time_inc - 1) % time_inc
+};
+struct SrcBoundsStep {
+	unsigned dq, dr; // (C * 2^16) / time_inc and % time_inc (dq is 0 when down-sampling by more than C)
+};
+
+GVTM_DESIGN_HD SrcBoundsStep src_bounds_step(unsigned time_inc, int chunk)
+{
+	const unsigned span = static_cast<unsigned>(chunk) << 16; // (a chunk is at most a few hundred steps)
+	return SrcBoundsStep{span / time_inc, span % time_inc};
+}
+
+GVTM_DESIGN_HD SrcBounds src_bounds_at(unsigned time_inc, uint64_t n)
+{
+	const uint64_t x = (n << 16) + time_inc - 1;
+	const uint64_t q = x / time_inc;
+	return SrcBounds{q, static_cast<unsigned>(x - q * time_inc)};
+}
+
+// from internal sample n to n + C
+GVTM_DESIGN_HD void src_bounds_advance(SrcBounds& b, SrcBoundsStep s, unsigned time_inc)
+{
+	// r + dr >= time_inc, asked without forming a sum that may not fit 32 bits (dr < time_inc)
+	const bool carry = b.r >= time_inc - s.dr;
+	b.q += static_cast<unsigned long long>(s.dq) + (carry ? 1u : 0u);
+	b.r = carry ? b.r - (time_inc - s.dr) : b.r + s.dr;
+}
+
 // the largest src_output_count() over all tracks of at most `steps` internal samples: what a row of a ragged batch
 // must be able to hold (a shorter track that runs into the flush overrun can be LONGER than the longest track)
 inline uint64_t src_output_capacity(unsigned time_inc, int pad, int upsampling, uint64_t steps)

@@ -235,6 +235,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 	// itself, which goes to the tube (the longest chain); the interpolation wavefront shares SIMD 0 with a helper.  Two
 	// utterances: the two tube wavefronts are wavefronts 0 and 1 (different SIMDs), then scan, filters, interpolation.
 	constexpr int kFirstHelper = 3 + U;
+	constexpr bool kBoundsRecurrence = sizeof(R) == 8; // the resampler's output ranges by running remainder (stage_bounds)
 	int role;           // 0 T, 1 S, 2 F, 3 I, 4 helpers
 	int tube_u = 0;     // utterance of a tube wavefront
 	if constexpr (U == 1) {
@@ -296,6 +297,13 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 		s_peak[tid] = peak0;
 	}
 	if (tid == 0) s_ticket[0] = s_ticket[1] = 0u;
+	if constexpr (kBoundsRecurrence) {
+		if (tid == 0) {
+			const SrcBoundsStep bstep = src_bounds_step(k.time_inc, C); // (the two spare words behind the counters: stage_bounds)
+			s_ticket[2] = bstep.dq;
+			s_ticket[3] = bstep.dr;
+		}
+	}
 	if (tid < 10) s_diag[tid] = 0ull;
 	__syncthreads();
 
@@ -608,13 +616,32 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 
 	// output sample range of chunk c: sample ko is produced once its read position floor(ko * inc / 2^16)
 	// lies before the filled length
-	// (two emulated 64-bit divisions: done once per chunk, by an idle lane of the interpolation wavefront, one tick
-	// before the resampler needs them)
+	// (once per chunk, by an idle lane of the interpolation wavefront, one tick before the resampler needs them.  In the
+	// double class the lane carries quotient and remainder of ceil((step_base + c * C) * 2^16 / time_inc) from chunk to chunk
+	// -- src_bounds_advance, csrc/vtm_design.hpp; chunk 0's quotient is k_first, one multiplication gives its remainder -- and
+	// divides out only the end of the last chunk, which is no whole chunk away: 256 x 500 frames 13.847 -> 13.741 ms
+	// (profiles/bounds_recurrence_ab.md).  The float class, which bench.py cannot time, keeps the two emulated 64-bit divisions
+	// per chunk.)
+	[[maybe_unused]] SrcBounds bnd{0ull, 0u};
+	if constexpr (kBoundsRecurrence) {
+		if (role == 3 && lane >= 16 * U && lane < 16 * U + U) {
+			const Extent e = s_ext[lane - 16 * U];
+			bnd.q = e.k_first;
+			bnd.r = static_cast<unsigned>((e.step_base << 16) + k.time_inc - 1 - e.k_first * k.time_inc);
+		}
+	}
 	auto stage_bounds = [&](int u, int c) {
 		if (c < 0 || c >= max_chunks) return;
 		const Extent e = s_ext[u];
 		unsigned long long lo = 0, hi = 0; // (a chunk the utterance does not have: an empty range)
-		if (c < e.nchunks) {
+		if constexpr (kBoundsRecurrence) {
+			const unsigned long long q0 = bnd.q;
+			src_bounds_advance(bnd, SrcBoundsStep{s_ticket[2], s_ticket[3]}, k.time_inc);
+			if (c < e.nchunks) {
+				lo = q0;
+				hi = (c == e.nchunks - 1) ? src_bounds_at(k.time_inc, e.step_base + e.steps + (kFinal ? 2ull * k.pad : 0ull)).q : bnd.q;
+			}
+		} else if (c < e.nchunks) {
 			const uint64_t n0 = e.step_base + static_cast<uint64_t>(c) * C;
 			const uint64_t filled = (c == e.nchunks - 1) ? e.step_base + e.steps + (kFinal ? 2ull * k.pad : 0ull) : n0 + C;
 			lo = c == 0 ? e.k_first : ((n0 << 16) + k.time_inc - 1) / k.time_inc;
@@ -759,7 +786,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 		ip_next2 = P[static_cast<size_t>(ip_last > 2 ? 2 : ip_last) * 16 + Lp];
 	}
 	auto stage_interp = [&](int t) {
-		// (two emulated 64-bit divisions per utterance: by idle lanes of this wavefront, one tick before the resampler needs them)
+		// (the resampler's output ranges: by idle lanes of this wavefront, one tick before the resampler needs them)
 		if (lane >= 16 * U && lane < 16 * U + U) stage_bounds(lane - 16 * U, t - 11);
 		if (ip_u >= U) return;
 		const int c = t - (Lp < 3 ? 0 : (Lp < 7 ? 3 : 6));

@@ -177,7 +177,8 @@ struct Smem { // (pointers only: the same for both record forms)
 	                     //                LAST region: every other offset is a compile-time constant
 	unsigned* peak;      // [U] max|y| as float bits
 	unsigned long long* kb; // [2][U + 1] first output index of a chunk and one-past-last per utterance, by tick parity
-	unsigned* ticket;    // [2] pass ticket counters of the helper wavefronts (by tick parity)
+	unsigned* ticket;    // [2] pass ticket counters of the helper wavefronts (by tick parity); [2], [3]: src_bounds_step() of the
+	                     // plan's time_inc and this kernel's chunk (stage_bounds, where it goes by running remainder)
 	unsigned long long* diag; // [8] cycles per helper stage (diagnostics)
 	CT* dump;        // [kDump] sink for lanes whose result is not needed (keeps the serial loops branch-free)
 };
@@ -390,6 +391,15 @@ template <int D, int U> constexpr bool far_calls_inline() { return D == 1 && U =
 // SectionDelay 1 12.247 / 11.819; one row SectionDelay 2 4.518 / 4.490; but two rows SectionDelay 2 4.777 / 4.793 and one row
 // SectionDelay 1 2.420 / 2.440, each slower by a little more than the parent's spread (0.015, 0.017): those two keep the SGPRs.
 template <int D, int U> constexpr bool fir_literal_taps() { return !((D == 1 && U == 1) || (D == 2 && U == 2)); }
+// which shapes carry the resampler's output ranges from tick to tick by running remainder (src_bounds_advance,
+// csrc/vtm_design.hpp) instead of dividing them out every tick (stage_bounds).  The kernel answers to any change of its
+// helper loop's registers, so this too went by measurement, shape by shape (profiles/bounds_recurrence_ab.md; parent / running
+// remainder, kernel ms, three interleaved runs each, 4096 utterances): float, four rows, SectionDelay 2 (x 7500 frames)
+// 320.68 / 317.80 and SectionDelay 3 (x 500) 56.07 / 54.14 take it; SectionDelay 1 11.896 / 11.917, SectionDelay 4 95.13 / 95.42,
+// two rows (512 utterances) SectionDelay 2 4.797 / 4.790 and SectionDelay 1 2.579 / 2.578, fp64 (x 1000) 77.91 / 77.94 and mixed
+// 73.84 / 83.77 do not gain or lose, and keep the divisions and the parent's instruction stream; so does the 48-lane layout,
+// which was not measured.
+template <typename CT, int D, int U, int LAYOUT> constexpr bool bounds_by_recurrence() { return sizeof(CT) == 4 && U == 4 && LAYOUT == 0 && (D == 2 || D == 3); }
 template <typename CT, int D, int U, bool VOICES> constexpr bool float_arg_consts() { return sizeof(CT) == 4 && !VOICES && !far_calls_inline<D, U>(); }
 
 template <typename CT, typename ST, int D, int U, int C, int NH, int LAYOUT_FLAGS>
@@ -491,6 +501,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	// 19.1, 2 37.1 / 36.4.
 	constexpr bool kHelperByRole = sizeof(CT) == 4 || D >= 3 || (sizeof(ST) == 8 && D == 2);
 	constexpr bool kNoiseTable = sizeof(CT) == 4; // one-shot launches of the float model read the noise samples from the plan's table
+	constexpr bool kBoundsRecurrence = bounds_by_recurrence<CT, D, U, LAYOUT>();
 	constexpr int kKlLen = kl_len(kLaneRec);
 	constexpr int kInjLen = kLaneRec ? kKlLen : kInj; // stride of a step's injection values
 	auto at_kl = [](int slot, int u) { return rec_at<C, U>(kKlLen, slot, u); };
@@ -592,6 +603,13 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	} else {
 		if (tid < 4) sm.ticket[tid] = 0u;
 	}
+	if constexpr (kBoundsRecurrence) {
+		if (tid == 0) {
+			const SrcBoundsStep bstep = src_bounds_step(sm.kc->time_inc, C);
+			sm.ticket[2] = bstep.dq;
+			sm.ticket[3] = bstep.dr;
+		}
+	}
 	for (int i = tid; i < kMaxFirTaps; i += kThreads) sm.fir[i] = i < sm.kc->fir_taps ? static_cast<const CT*>(a.fir)[i] : CT(0.0);
 	__syncthreads();
 
@@ -672,6 +690,19 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			ip_this = P[Lp];
 			ip_next = P[static_cast<size_t>(last > 1 ? 1 : last) * 16 + Lp];
 			ip_next2 = P[static_cast<size_t>(last > 2 ? 2 : last) * 16 + Lp];
+		}
+	}
+
+	// first helper wavefront, lanes 0 .. U (stage_bounds): quotient and remainder of src_bounds_advance (csrc/vtm_design.hpp)
+	// at the chunk boundary the lane reports next.  Lane 0 starts at utterance 0's step_base, where the quotient is k_first
+	// (one multiplication gives its remainder); lane 1 + u one chunk behind utterance u's.
+	[[maybe_unused]] SrcBounds bnd{0ull, 0u};
+	if constexpr (kBoundsRecurrence) {
+		if (wave == kFirstHelper && lane <= U) {
+			const Extent e = sm.ext[lane == 0 ? 0 : lane - 1];
+			bnd.q = e.k_first;
+			bnd.r = static_cast<unsigned>((e.step_base << 16) + k.time_inc - 1 - e.k_first * k.time_inc);
+			if (lane > 0) src_bounds_advance(bnd, SrcBoundsStep{sm.ticket[2], sm.ticket[3]}, k.time_inc);
 		}
 	}
 
@@ -1044,8 +1075,9 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 		const int u0 = (pass_and_group % kP6Groups) * UG; // first utterance of this pass
 		// Output sample ko of EVERY utterance has the same time register (t = ko * inc), hence the same
 		// filter phase: the polyphase coefficient of a tap is formed once and applied to the pass's rows.
-		// output index range of the chunk.  With several rows the (emulated 64-bit) divisions are done
-		// once per tick by stage_bounds, one tick earlier; with one row doing them here measured faster.
+		// output index range of the chunk.  With several rows stage_bounds has it ready, one tick earlier (by
+		// running remainder or, shape by shape, by division); with one row the (emulated 64-bit) divisions done
+		// here measured faster than a stage of their own, with either form of it.
 		uint64_t k_lo;
 		uint64_t k_hi[UG];
 		uint64_t k_hi_max = 0;
@@ -1231,15 +1263,27 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 				// (the rows of a workgroup share one output index range start: utterances of a stream that share a
 				// workgroup have been pushed in lockstep, the host launches one row per workgroup otherwise)
 				const Extent e = sm.ext[lane == 0 ? 0 : lane - 1];
-				const uint64_t n0 = e.step_base + static_cast<uint64_t>(cc) * C;
 				unsigned long long v = 0;
-				if (lane == 0) {
-					v = grid_floor(((n0 << 16) + k.time_inc - 1) / k.time_inc, e.k_first);
-				} else if (valid_in(lane - 1, cc) >= 0) {
-					const bool last = cc == e.nchunks - 1;
-					const uint64_t filled = last ? e.step_base + e.steps + (kFinal ? 2ull * k.pad : 0ull) : n0 + C;
-					const uint64_t avail = ((filled << 16) + k.time_inc - 1) / k.time_inc;
-					v = last ? avail : grid_floor(avail, e.k_first);
+				if constexpr (kBoundsRecurrence) {
+					// Lane 0 reports ceil((step_base + cc * C) * 2^16 / time_inc) of utterance 0 and lane 1 + u the same at
+					// (cc + 1) * C of utterance u: bnd, which moves on by one chunk per tick (the other branch's two emulated 64-bit
+					// divisions).  Only the end of an utterance's last chunk, no whole chunk away, is divided out: once per launch.
+					if (lane == 0 || cc < e.nchunks - 1) {
+						v = grid_floor(bnd.q, e.k_first);
+					} else if (cc == e.nchunks - 1) {
+						v = src_bounds_at(k.time_inc, e.step_base + e.steps + (kFinal ? 2ull * k.pad : 0ull)).q;
+					}
+					src_bounds_advance(bnd, SrcBoundsStep{sm.ticket[2], sm.ticket[3]}, k.time_inc);
+				} else {
+					const uint64_t n0 = e.step_base + static_cast<uint64_t>(cc) * C;
+					if (lane == 0) {
+						v = grid_floor(((n0 << 16) + k.time_inc - 1) / k.time_inc, e.k_first);
+					} else if (valid_in(lane - 1, cc) >= 0) {
+						const bool last = cc == e.nchunks - 1;
+						const uint64_t filled = last ? e.step_base + e.steps + (kFinal ? 2ull * k.pad : 0ull) : n0 + C;
+						const uint64_t avail = ((filled << 16) + k.time_inc - 1) / k.time_inc;
+						v = last ? avail : grid_floor(avail, e.k_first);
+					}
 				}
 				sm.kb[(cc & 1) * (U + 1) + lane] = v;
 			}
@@ -2019,9 +2063,11 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 					if constexpr (kHelperByRole || kStaticRounds > 0) sm.ticket[(t + 1) & 1] = static_cast<unsigned>(kStaticRounds * NH); // next tick's counter (idle this tick)
 					else sm.ticket[(t + 1) & 1] = 0u;
 				}
-				// (the resampler's output ranges for next tick.  Moving these two emulated 64-bit divisions per utterance to the
-				// interpolation or the pre-tube filter wavefront, which have time to spare, measured slower on configs[3] in every
-				// precision: 108.2 -> 111.5 / 108.6 ms in float, 148.5 -> 159.3 / 150.6 mixed, 156.3 -> 163.5 / 159.4 fp64 per 2000 frames)
+				// (the resampler's output ranges for next tick.  When they were two emulated 64-bit divisions per utterance, moving
+				// them to the interpolation or the pre-tube filter wavefront, which have time to spare, measured slower on configs[3]
+				// in every precision: 108.2 -> 111.5 / 108.6 ms in float, 148.5 -> 159.3 / 150.6 mixed, 156.3 -> 163.5 / 159.4 fp64
+				// per 2000 frames.  Where bounds_by_recurrence() says so they are carried from tick to tick now, in this
+				// wavefront's registers.)
 				if constexpr (U > 1) stage_bounds(t);
 			}
 			break;
