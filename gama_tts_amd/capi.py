@@ -175,6 +175,10 @@ def _prototypes():
         "gvtm_intonation_apply_host": (i64, [tracks, vp, sz, vp, sz, vp, sz, vp]),
         "gvtm_apply_intonation_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp]),
         "gvtm_synthesize_intonation_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]),
+        "gvtm_modification_filter_length": (i64, [vp, i]),
+        "gvtm_modification_apply_host": (i, [vp, i, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
+        "gvtm_apply_modifications_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]),
+        "gvtm_synthesize_modified_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]),
         "gvtm_stream_push_events": (i, [vp, vp, vp, vp, vp, sz, vp, vp]),
         "gvtm_stream_get_drift": (i, [vp, vp]),
         "gvtm_stream_set_drift": (i, [vp, vp]),
@@ -423,6 +427,42 @@ def intonation_apply_host(config, events, points, count_only=False, capacity=Non
     if n < 0:
         raise GvtmError(1, lib.gvtm_last_error().decode())
     return (int(n) if count_only else out[:n].copy()), int(status.value)
+
+
+MODIFICATION_ADD, MODIFICATION_MULTIPLY = 0, 1  # GVTM_MODIFICATION_*
+MAX_GESTURES = 64  # GVTM_MAX_GESTURES
+
+
+def pack_gestures(utterances):
+    """utterances[b]: the gestures of utterance b, each (parameter, operation, steps, values) -> (gestures int32 [G][2],
+    gesture_offsets int64 [G + 1], utt_gestures int64 [B + 1], point_steps int32, point_values float32): the tables of the
+    modification entries, the points of all gestures back to back."""
+    flat = [g for u in utterances for g in u]
+    gestures = np.array([[int(g[0]), int(g[1])] for g in flat], dtype=np.int32).reshape(-1, 2)
+    steps = [np.asarray(g[2], dtype=np.int32).reshape(-1) for g in flat]
+    values = [np.asarray(g[3], dtype=np.float32).reshape(-1) for g in flat]
+    assert all(s.shape == v.shape for s, v in zip(steps, values))
+    gesture_offsets = np.zeros(len(flat) + 1, dtype=np.int64)
+    gesture_offsets[1:] = np.cumsum([len(s) for s in steps])
+    utt_gestures = np.zeros(len(utterances) + 1, dtype=np.int64)
+    utt_gestures[1:] = np.cumsum([len(u) for u in utterances])
+    point_steps = np.concatenate(steps) if steps else np.zeros(0, np.int32)
+    point_values = np.concatenate(values) if values else np.zeros(0, np.float32)
+    return gestures, gesture_offsets, utt_gestures, np.ascontiguousarray(point_steps), np.ascontiguousarray(point_values)
+
+
+def modification_apply_host(plan, frames, gestures, voice=0, frames_out=None):
+    """gvtm_modification_apply_host: base frames float32 [F][16] under `gestures` (a list of (parameter, operation, steps,
+    values)) with the control steps and filter length of voice `voice` of `plan` -> (modified frames float32 [F][16],
+    status).  A refused utterance leaves frames_out (by default zeros) as it was."""
+    frames = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, N_PARAM)
+    table, offsets, _, steps, values = pack_gestures([gestures])
+    out = np.zeros_like(frames) if frames_out is None else frames_out
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.size >= frames.size
+    status = ctypes.c_int32(-1)
+    _check(plan._lib, plan._lib.gvtm_modification_apply_host(plan._h, int(voice), _ptr(frames), frames.shape[0], _ptr(table), _ptr(offsets),
+                                                             len(gestures), _ptr(steps), _ptr(values), _ptr(out), ctypes.byref(status)))
+    return out, int(status.value)
 
 
 def generate_tracks_host(config, event_lists, max_frames, drift=None, device=0):
@@ -743,6 +783,33 @@ class Plan:
             self._h, _ptr(d_events), _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_points), _ptr(d_point_offsets),
             _ptr(d_voice_ids), int(events_capacity), int(batch), int(max_frames), _ptr(d_audio), int(audio_stride), _ptr(d_frame_counts),
             _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift), _ptr(d_status), _ptr(stream)))
+
+    def modification_filter_length(self, voice=0):
+        """gvtm_modification_filter_length: the samples of the 20 ms moving average at the voice's internal rate."""
+        n = int(self._lib.gvtm_modification_filter_length(self._h, int(voice)))
+        if n < 0:
+            raise GvtmError(1, self._lib.gvtm_last_error().decode())
+        return n
+
+    def apply_modifications_device(self, d_base_params, d_base_frame_counts, n_bases, d_base_ids, d_gestures, d_gesture_offsets, d_utt_gestures,
+                                   d_point_steps, d_point_values, d_voice_ids, batch, max_frames, d_params_out, d_frame_counts_out,
+                                   d_status=None, stream=None):
+        """gvtm_apply_modifications_device: gestures (the tables of pack_gestures) onto base frames (d_base_ids None:
+        utterance b's is base b; d_voice_ids None: the plan's one voice) -> modified frames, frame counts and statuses; all
+        pointers are device memory."""
+        self._check(self._lib.gvtm_apply_modifications_device(
+            self._h, _ptr(d_base_params), _ptr(d_base_frame_counts), int(n_bases), _ptr(d_base_ids), _ptr(d_gestures), _ptr(d_gesture_offsets),
+            _ptr(d_utt_gestures), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_voice_ids), int(batch), int(max_frames), _ptr(d_params_out),
+            _ptr(d_frame_counts_out), _ptr(d_status), _ptr(stream)))
+
+    def synthesize_modified_device(self, d_base_params, d_base_frame_counts, n_bases, d_base_ids, d_gestures, d_gesture_offsets, d_utt_gestures,
+                                   d_point_steps, d_point_values, d_voice_ids, batch, max_frames, d_audio, audio_stride, d_frame_counts=None,
+                                   d_out_counts=None, d_maxabs=None, d_status=None, stream=None):
+        """Base frames and gestures in, samples out (gvtm_synthesize_modified_device); all pointers are device memory."""
+        self._check(self._lib.gvtm_synthesize_modified_device(
+            self._h, _ptr(d_base_params), _ptr(d_base_frame_counts), int(n_bases), _ptr(d_base_ids), _ptr(d_gestures), _ptr(d_gesture_offsets),
+            _ptr(d_utt_gestures), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_voice_ids), int(batch), int(max_frames), _ptr(d_audio),
+            int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status), _ptr(stream)))
 
     def synthesize_events_device(self, track_config, d_events, d_offsets, batch, max_frames, d_audio, audio_stride,
                                  d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, stream=None):

@@ -8,18 +8,6 @@ using namespace gvtm::host;
 
 namespace {
 
-// What lies between the two launches of an events entry: the plan's frame buffer (the enqueue-only entries' scratch) and
-// the frame counts, the caller's or the plan's
-int events_scratch(gvtm_plan* plan, size_t batch, size_t max_frames, int32_t* d_frame_counts, float*& d_params, int32_t*& d_counts)
-{
-	hipError_t e;
-	if ((e = plan->async.params.ensure(sizeof(float) * batch * std::max<size_t>(max_frames, 1) * GVTM_N_PARAM)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
-	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
-	d_params = static_cast<float*>(plan->async.params.ptr);
-	d_counts = d_frame_counts ? d_frame_counts : static_cast<int32_t*>(plan->async.frames.ptr);
-	return GVTM_OK;
-}
-
 // The event lists of a batch that mixes voices: one list per utterance (d_offsets [batch + 1], the events-voices entries) or
 // several (chunked: d_offsets the chunks' event offsets, d_utt_chunks [batch + 1] the utterances' chunks)
 struct VoiceEvents {

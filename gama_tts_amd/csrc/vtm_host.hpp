@@ -136,7 +136,7 @@ struct gvtm_plan {
 		void release_sets() { for (DeviceBuffer& s : set) s = DeviceBuffer(); }
 		unsigned char* set_of(size_t i) const { return set[i % 3].as<unsigned char>(); } // slice i's: the sets rotate
 	} host;
-	// ... and the enqueue-only entries' (gvtm_synthesize_events_device's frames and frame counts, the grouping of
+	// ... and the enqueue-only entries' (gvtm_synthesize_events_device's and gvtm_synthesize_modified_device's frames and frame counts, the grouping of
 	// gvtm_synthesize_voices_device, the merged event lists and their offsets of gvtm_synthesize_intonation_device): calls to
 	// those on one plan must be ordered on one stream
 	struct {
@@ -256,6 +256,18 @@ inline gvtm::TrackAppendArgs plan_track_args(const gvtm_plan* plan, const gvtm_e
 	args.voice_ids = d_voice_ids;
 	args.n_voices = plan->n_voices();
 	return args;
+}
+
+// What lies between the two launches of an events entry or of gvtm_synthesize_modified_device: the plan's frame buffer (the
+// enqueue-only entries' scratch) and the frame counts, the caller's or the plan's
+inline int events_scratch(gvtm_plan* plan, size_t batch, size_t max_frames, int32_t* d_frame_counts, float*& d_params, int32_t*& d_counts)
+{
+	hipError_t e;
+	if ((e = plan->async.params.ensure(sizeof(float) * batch * std::max<size_t>(max_frames, 1) * GVTM_N_PARAM)) != hipSuccess) return fail_hip(e, "hipMalloc frames");
+	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc frame counts");
+	d_params = static_cast<float*>(plan->async.params.ptr);
+	d_counts = d_frame_counts ? d_frame_counts : static_cast<int32_t*>(plan->async.frames.ptr);
+	return GVTM_OK;
 }
 
 inline size_t design_output_count(const gvtm::Design& dg, size_t n_frames)

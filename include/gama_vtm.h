@@ -46,6 +46,10 @@
  *   gvtm_synthesize_events_packed_host*
  *                               Controller::synthesizePhoneticStringToFile (vtm_control_model/Controller.cpp:194-200 with
  *                               :141-154) for a ragged batch: event lists in from host memory, int16 samples out
+ *   gvtm_apply_modifications_device / gvtm_synthesize_modified_device / gvtm_modification_apply_host
+ *                               the editor's parameter-modification window: what Processor::process leaves in its modified
+ *                               parameter list (gama_tts_editor/src/ParameterModificationSynthesis.cpp:117-194), then
+ *                               Controller::synthesizeToFile on it (ParameterModificationWindow.cpp:200-231, 281-322)
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
@@ -750,6 +754,113 @@ int gvtm_synthesize_intonation_device(gvtm_plan* plan, const gvtm_event* d_event
 		const int32_t* d_voice_ids, size_t events_capacity, size_t batch, size_t max_frames, float* d_audio,
 		size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, gvtm_drift_state* d_drift,
 		int32_t* d_status, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Parameter-modification gestures applied to frames.  The editor's parameter-modification window keeps an utterance's
+ * parameter list and, while the utterance plays, lets the user drag one of the 16 parameters; its processor smooths the
+ * drag with a 20 ms MovingAverageFilter<float> at the internal rate and writes original + filtered or original * filtered
+ * into every control frame (gama_tts_editor ParameterModificationSynthesis.cpp:117-194); "synthesize to file" hands the
+ * modified list to Controller::synthesizeToFile (ParameterModificationWindow.cpp:200-231, 281-322).  The entries below make
+ * the modified list, on the host or for a batch on the device, where many utterances may share one base list of frames and
+ * only the gestures' points (8 bytes each) differ between them.
+ *
+ * The rule, for base frames orig[F][16] (float), the voice's control_steps (cs) and N = (size_t)roundf((float)
+ * internal_rate_hz * (float)20.0e-3) -- a float product rounded half away from zero; gvtm_modification_filter_length gives
+ * it -- with invN = 1.0 / N in double.  An utterance has G gestures, applied in order; a gesture is a parameter p, an
+ * operation (GVTM_MODIFICATION_ADD or GVTM_MODIFICATION_MULTIPLY) and points (step_j, value_j): internal steps from the
+ * start of playback, strictly increasing, and float values.  The processor reads at most one modification per internal
+ * step, so every such list is something the reference can be made to do.
+ *   out = orig
+ *   for each gesture, in order (a fresh run: prepareSynthesis() resets the filter):
+ *     cur = none
+ *     for k = 1 .. F-1 (frame 0 is never modified), for i = 0 .. cs-1:
+ *       s = (k-1)*cs + i;  if the next point has step == s: cur = its value
+ *       if cur != none:
+ *         at the first filter call ever: ring[0 .. N) = cur; sum = (double)cur * (double)N
+ *         sum = sum - (double)ring[pos]; sum = sum + (double)cur; ring[pos] = cur; pos advances
+ *         fm = (float)(sum * invN)
+ *         if i == 0: out[k][p] = ADD ? orig[k][p] + fm : orig[k][p] * fm      (float arithmetic)
+ * What follows from it:
+ *   - points at or beyond step (F-1)*cs never act, and a gesture without an acting point changes nothing;
+ *   - a gesture reads orig, never out: on one parameter a later gesture overwrites an earlier one from its own first frame
+ *     ceil(step_0 / cs) + 1 to the end and leaves the frames before alone; gestures on different parameters accumulate;
+ *   - the two additions into sum are sequential double operations, each rounded, in this order: with values spread over
+ *     many decades the result differs from the exactly rounded window mean, and it is the sequential one that is computed,
+ *     without FMA contraction on the host and on the device: bit for bit the reference's frames (an orig entry that is NaN
+ *     gives a NaN whose sign and payload may differ: the NaN exception of the synthesis entries).
+ *
+ * An utterance is refused on its own: no frame of its output is written, and on the device its frame count is 0.  Its
+ * status says why; the first that applies, every gesture and point being looked at for 3 before any for 4:
+ *   0  ok
+ *   1  a base of fewer than 2 frames (the window's validData()); on the device also a base id outside [0, n_bases), a voice
+ *      id outside the plan's voices, a base of more than max_frames frames
+ *   2  more than GVTM_MAX_GESTURES gestures (on the device also gesture or point offsets that decrease or are negative)
+ *   3  a parameter outside [0, 16), an operation other than 0 / 1, a point value that is not finite
+ *   4  a negative step; steps not strictly increasing within a gesture
+ */
+#define GVTM_MODIFICATION_ADD 0
+#define GVTM_MODIFICATION_MULTIPLY 1
+#define GVTM_MAX_GESTURES 64   /* per utterance */
+
+/* N of the rule for a voice of the plan; -1 on a null plan or a voice outside the plan's.  Host only: works on
+ * GVTM_DEVICE_NONE plans. */
+int64_t gvtm_modification_filter_length(const gvtm_plan* plan, int voice);
+
+/* The rule on the host for one utterance under voice `voice` of the plan (its control_steps and N); needs no device and
+ * works on GVTM_DEVICE_NONE plans.
+ *   frames [n_frames][16]                        the base frames
+ *   gestures [n_gestures][2] int32               (parameter, operation) of gesture g
+ *   gesture_offsets [n_gestures + 1]             gesture g owns the points [off[g], off[g+1])
+ *   point_steps int32, point_values float        the points of all gestures back to back
+ *   frames_out [n_frames][16]                    out: the modified frames; must not overlap frames
+ *   status_out                                   out: the status above; a refused utterance leaves frames_out untouched
+ * GVTM_ERR_INVALID_ARGUMENT for a null plan, status_out or frames_out, null frames with n_frames > 0, null tables with
+ * counts > 0, a voice outside the plan's, gesture_offsets that are negative or decrease. */
+int gvtm_modification_apply_host(const gvtm_plan* plan, int voice, const float* frames, size_t n_frames,
+		const int32_t* gestures, const int64_t* gesture_offsets, size_t n_gestures, const int32_t* point_steps,
+		const float* point_values, float* frames_out, int32_t* status_out);
+
+/* The rule for a batch, everything resident in device memory.
+ *   d_base_params [n_bases][max_frames][16], d_base_frame_counts [n_bases] int32
+ *                                            base l holds d_base_frame_counts[l] frames at the start of its row
+ *   d_base_ids [batch] int32, or NULL        utterance b's base; NULL: n_bases == batch and utterance b uses base b.  Many
+ *                                            utterances may share one base.
+ *   d_gestures [n][2] int32, d_gesture_offsets [n + 1], d_utt_gestures [batch + 1]
+ *                                            the two-level tables of the chunks entries: utterance b owns the gestures
+ *                                            [d_utt_gestures[b], d_utt_gestures[b+1]), gesture g (parameter, operation) =
+ *                                            d_gestures[g] and the points [d_gesture_offsets[g], d_gesture_offsets[g+1])
+ *   d_point_steps int32, d_point_values float
+ *   d_voice_ids [batch] int32, or NULL       utterance b's voice (its control_steps and N); NULL on a one-voice plan
+ *   d_params_out [batch][max_frames][16]     out: utterance b's row holds the modified frames in its first F frames,
+ *                                            [F, max_frames) of the row is untouched; a refused utterance's row is untouched
+ *   d_frame_counts_out [batch] int32         out: F, or 0 for a refused utterance
+ *   d_status [batch] int32, may be NULL      out: the statuses above
+ * d_params_out and d_frame_counts_out are exactly what gvtm_synthesize_voices_device and gvtm_synthesize_batch_device take.
+ * Frames, counts and statuses are bit for bit gvtm_modification_apply_host's, utterance by utterance.  d_base_params and
+ * d_params_out must be 16-byte aligned and must not overlap (not checked).  Works on every plan.  Enqueue-only: two small
+ * kernels on hip_stream, no scratch.  Refused before any device work, in this order: a null plan; with batch > 0 a null
+ * table, buffer or count array (d_base_ids, d_status and, on a one-voice plan, d_voice_ids aside), a NULL d_base_ids with
+ * n_bases != batch, a NULL d_voice_ids on a plan of several voices, a misaligned buffer (GVTM_ERR_INVALID_ARGUMENT); a
+ * design-only plan (GVTM_ERR_NO_DEVICE), with batch == 0 too, as the neighbouring entries: without a device there is no
+ * call; on a plan with a device batch == 0 returns GVTM_OK and nothing but the plan is looked at. */
+int gvtm_apply_modifications_device(gvtm_plan* plan, const float* d_base_params, const int32_t* d_base_frame_counts,
+		size_t n_bases, const int32_t* d_base_ids, const int32_t* d_gestures, const int64_t* d_gesture_offsets,
+		const int64_t* d_utt_gestures, const int32_t* d_point_steps, const float* d_point_values,
+		const int32_t* d_voice_ids, size_t batch, size_t max_frames, float* d_params_out, int32_t* d_frame_counts_out,
+		int32_t* d_status, void* hip_stream);
+
+/* The two steps behind one call: gvtm_apply_modifications_device into the plan's frame buffer (the one the events entries
+ * use), then the synthesis launch on it with the plan's grouping scratch -- gvtm_synthesize_voices_device with
+ * d_voice_ids, gvtm_synthesize_batch_device with NULL ids (a gvtm_plan_create_model5_float plan takes NULL ids only) -- all
+ * enqueued on hip_stream.  Samples, counts, peaks, frame counts and statuses are bit for bit those of the two calls made
+ * separately; a refused utterance is synthesized as one of 0 frames.  d_frame_counts [batch] int32 may be NULL.  The
+ * remaining arguments, checks and the one-stream ordering rule are gvtm_synthesize_events_voices_device's; the apply
+ * entry's refusals come first, then a null audio buffer and the stride, then a design-only plan. */
+int gvtm_synthesize_modified_device(gvtm_plan* plan, const float* d_base_params, const int32_t* d_base_frame_counts,
+		size_t n_bases, const int32_t* d_base_ids, const int32_t* d_gestures, const int64_t* d_gesture_offsets,
+		const int64_t* d_utt_gestures, const int32_t* d_point_steps, const float* d_point_values,
+		const int32_t* d_voice_ids, size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
+		int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream);
 
 /*
  * Streams fed event lists.  The reference produces an utterance chunk by chunk (one generateOutput() per /c chunk,
