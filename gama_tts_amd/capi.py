@@ -196,6 +196,11 @@ def _prototypes():
         "gvtm_debug_fir_literals": (i, [vp]),
         "gvtm_debug_plan_fir_literals": (i, [vp]),
         "gvtm_debug_force_generic_fir": (i, [vp]),
+        "gvtm_debug_plan_src_phases": (i, [vp]),
+        "gvtm_debug_plan_src_phase_table": (i, [vp, vp, sz]),
+        "gvtm_debug_force_generic_src": (i, [vp]),
+        "gvtm_debug_plan_static_wavetable": (i, [vp]),
+        "gvtm_debug_force_dynamic_wavetable": (i, [vp]),
         "gvtm_debug_noise_table": (i, [sz, i, vp]),
         "gvtm_debug_set_taps": (i, [vp, vp]),
         "gvtm_debug_set_phase_cycles": (i, [vp, vp]),
@@ -565,6 +570,36 @@ class Plan:
     def force_generic_fir(self):
         """Diagnostics plans: later launches run the generic tap loop over the plan's own coefficients."""
         self._check(self._lib.gvtm_debug_force_generic_fir(self._h))
+
+    def _hook_count(self, rc):
+        if rc < 0:
+            self._check(-rc)
+        return int(rc)
+
+    def src_phases(self):
+        """Diagnostics plans: the output phases of the plan's table of converter coefficients, 0 for a plan without one."""
+        return self._hook_count(self._lib.gvtm_debug_plan_src_phases(self._h))
+
+    def src_phase_table(self):
+        """Diagnostics plans: that table as the host designs it, float32 [phases][28]; None for a plan without one."""
+        phases = self.src_phases()
+        if not phases:
+            return None
+        out = np.empty((phases, 28), dtype=np.float32)
+        assert self._hook_count(self._lib.gvtm_debug_plan_src_phase_table(self._h, out.ctypes.data, out.size)) == phases
+        return out
+
+    def force_generic_src(self):
+        """Diagnostics plans: later launches form the converter's coefficients in the kernel."""
+        self._check(self._lib.gvtm_debug_force_generic_src(self._h))
+
+    def says_static_wavetable(self):
+        """Diagnostics plans: whether the plan tells its launches that the wavetable never follows the amplitude."""
+        return bool(self._hook_count(self._lib.gvtm_debug_plan_static_wavetable(self._h)))
+
+    def force_dynamic_wavetable(self):
+        """Diagnostics plans: later launches ask per wavetable entry whether it follows the amplitude."""
+        self._check(self._lib.gvtm_debug_force_dynamic_wavetable(self._h))
 
     def output_count(self, frames):
         return int(self._lib.gvtm_output_count(self._h, int(frames)))

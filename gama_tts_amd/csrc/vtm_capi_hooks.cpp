@@ -96,6 +96,51 @@ int gvtm_debug_force_generic_fir(gvtm_plan* plan)
 	return GVTM_OK;
 }
 
+/* The output phases of the plan's table of converter coefficients (a one-voice float plan of the models 0 to 4 that
+   up-samples with at most gvtm::kSrcPhaseCap phases, and whose table found its memory), 0: the plan has none and its
+   launches form the coefficients in the kernel; negative: a null plan.  Needs no device. */
+int gvtm_debug_plan_src_phases(const gvtm_plan* plan)
+{
+	if (!plan) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	return static_cast<int>(plan->src_phases);
+}
+
+/* That table as the host designs it: out[phases][28] floats (13 coefficients of the first wing, 13 of the second, two
+   zeros); returns the phases, 0 for a plan without the table.  Needs no device. */
+int gvtm_debug_plan_src_phase_table(const gvtm_plan* plan, float* out, size_t capacity)
+{
+	if (!plan || !out) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or buffer");
+	if (!plan->src_phases) return 0;
+	const std::vector<float> table = gvtm::design_src_phase_table(plan->designs[0]);
+	if (capacity < table.size()) return -fail(GVTM_ERR_INVALID_ARGUMENT, "table buffer too small");
+	std::memcpy(out, table.data(), sizeof(float) * table.size());
+	return static_cast<int>(plan->src_phases);
+}
+
+/* Makes the plan's later launches form the converter's coefficients in the kernel (there is no way back: make a new plan). */
+int gvtm_debug_force_generic_src(gvtm_plan* plan)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	plan->src_phases = 0;
+	return GVTM_OK;
+}
+
+/* 1: the plan tells its launches that the wavetable never follows the amplitude (one voice with tn_min == tn_max, or the
+   sine), 0: their wavetable pass asks per entry; negative: a null plan.  Needs no device. */
+int gvtm_debug_plan_static_wavetable(const gvtm_plan* plan)
+{
+	if (!plan) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	return plan->static_wavetable ? 1 : 0;
+}
+
+/* Makes the plan's later launches ask per entry again (there is no way back: make a new plan). */
+int gvtm_debug_force_dynamic_wavetable(gvtm_plan* plan)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	plan->static_wavetable = false;
+	return GVTM_OK;
+}
+
 /* The plan-level noise-sample table as the host builds it (n floats or doubles); needs no device. */
 int gvtm_debug_noise_table(size_t n, int as_float, void* out)
 {

@@ -58,6 +58,11 @@ gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 	args.fir = plan->d_fir.ptr;
 	std::memset(&args.fir_k, 0, sizeof(args.fir_k));
 	args.fir_literals = plan->fir_literals ? 1 : 0;
+	if (plan->src_phases) {
+		args.src_phase = plan->d_src_phase.as<float>();
+		args.src_phase_mask = plan->src_phases - 1;
+	}
+	args.static_wavetable = plan->static_wavetable ? 1 : 0;
 	if (!dg.model5) {
 		if (dg.f32) {
 			// (the coefficients by value: for the two shapes that keep them in SGPRs, v2::fir_literal_taps)

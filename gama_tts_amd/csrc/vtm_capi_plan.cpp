@@ -80,6 +80,16 @@ int upload_tables(gvtm_plan* plan)
 	if ((rc = upload_design(plan->d_src_h, dg.src_h, dg.src_h_f, "upload src_h")) != GVTM_OK) return rc;
 	if ((rc = upload_design(plan->d_src_dh, dg.src_dh, dg.src_dh_f, "upload src_dh")) != GVTM_OK) return rc;
 	if ((rc = upload(plan->d_consts, consts, "upload constants")) != GVTM_OK) return rc;
+	if (plan->src_phases) {
+		// the converter's coefficients by output phase, once per plan; a plan that cannot have the memory does without
+		const std::vector<float> table = gvtm::design_src_phase_table(dg);
+		if (plan->d_src_phase.ensure(sizeof(float) * table.size()) != hipSuccess) {
+			(void) hipGetLastError();
+			plan->src_phases = 0;
+		} else if (const hipError_t e = hipMemcpy(plan->d_src_phase.ptr, table.data(), sizeof(float) * table.size(), hipMemcpyHostToDevice); e != hipSuccess) {
+			return fail_hip(e, "upload converter phase table");
+		}
+	}
 	return dg.model5 ? upload(plan->d_consts5, consts5, "upload model 5 constants") : GVTM_OK;
 }
 
@@ -114,6 +124,13 @@ int create_plan(const Config* configs, size_t n_voices, double control_rate, int
 		const gvtm::Design& d0 = plan->designs[0];
 		plan->fir_literals = !d0.model5 && d0.f32 && d0.fir_f.size() == static_cast<size_t>(gvtm::kGlottalFirTapsF32)
 				&& std::memcmp(d0.fir_f.data(), gvtm::kGlottalFirF32, sizeof(gvtm::kGlottalFirF32)) == 0;
+		// what is fixed for the plan and said once: the converter's coefficients by output phase and "the wavetable is
+		// static".  One voice only: the voices of a plan have each their own internal rate and pulse shape, and the voice
+		// variant of the kernel keeps forming both per pass
+		if (n_voices == 1 && !d0.model5) {
+			plan->src_phases = gvtm::src_phase_count(d0);
+			plan->static_wavetable = gvtm::static_wavetable(d0.k);
+		}
 		if (device == GVTM_DEVICE_NONE) {
 			// design-only plan: info, tables and output counts work, synthesis reports NO_DEVICE
 			plan->device = GVTM_DEVICE_NONE;

@@ -349,6 +349,35 @@ std::string design_plan(const gvtm_config& c, double control_rate, Design& out)
 	return "";
 }
 
+unsigned src_phase_count(const Design& d)
+{
+	const DeviceConstants& k = d.k;
+	if (d.model5 || !d.f32 || !k.upsampling || k.time_inc == 0 || k.time_inc > 65536u) return 0;
+	const unsigned low_bit = k.time_inc & (0u - k.time_inc); // gcd(time_inc, 2^16): time_inc's lowest set bit (time_inc <= 2^16)
+	const unsigned phases = 65536u / low_bit;
+	return phases <= kSrcPhaseCap ? phases : 0;
+}
+
+std::vector<float> design_src_phase_table(const Design& d)
+{
+	const unsigned phases = src_phase_count(d);
+	std::vector<float> table(static_cast<size_t>(phases) * kSrcPhaseRecord, 0.0f);
+	for (unsigned p = 0; p < phases; ++p) {
+		float* rec = table.data() + static_cast<size_t>(p) * kSrcPhaseRecord;
+		const unsigned frac = (p * d.k.time_inc) & 0xFFFFu; // (p < 2^14, time_inc <= 2^16)
+		const unsigned wing_frac[2] = {frac, (~frac) & 0xFFFFu};
+		for (int w = 0; w < 2; ++w) {
+			const unsigned l = wing_frac[w] >> 8;
+			const float interp = static_cast<float>(wing_frac[w] & 0xFFu) / 256.0f;
+			for (int j = 0; j < kSrcZeroCrossings; ++j) {
+				const float product = d.src_dh_f[l + 256 * j] * interp; // (rounded on its own: no contraction in this file)
+				rec[w * kSrcZeroCrossings + j] = d.src_h_f[l + 256 * j] + product;
+			}
+		}
+	}
+	return table;
+}
+
 // NoiseSource::getSample + NoiseFilter::filter (vtm/NoiseSource.h:40-44, vtm/NoiseFilter.h:63-68) for steps [0, n): the
 // generator is double whatever TFloat is; the one-zero low-pass adds in TFloat.
 void design_noise_table(size_t n, bool as_float, void* out)

@@ -120,6 +120,27 @@ struct Design {
 // once; `out` holds n floats (as_float: the sum formed in float as NoiseFilter<float> does) or n doubles.
 void design_noise_table(size_t n, bool as_float, void* out);
 
+// The up-sampling converter's polyphase coefficients by output phase, for a float plan of the models 0 to 4.
+//
+// Output sample ko reads the filter at frac = (ko * time_inc) & 0xFFFF (SampleRateConverter.h:330-372), so its 26
+// coefficients h + dh * (m / 256) are a function of ko mod P alone, P = 2^16 / gcd(time_inc, 2^16) -- a power of two.
+// A record is kSrcPhaseRecord floats: the 13 coefficients of the first wing (l = frac >> 8, m = frac & 255, entries
+// l + 256 j), the 13 of the second (the same of ~frac), in the order the wings consume them, and two zeros that make a
+// record seven 16-byte loads from one address.  Each coefficient is made with the float operations of the kernel's
+// mad(dh, m / 256, h) on the plan's own float tables: the product rounded on its own, then the add (vtm_design.cpp is
+// compiled without FMA contraction).
+// Plans beyond kSrcPhaseCap phases have none (16384 records are 1.8 MB, under half of an XCD's 4 MB of L2; the next
+// power of two would fill it), nor have down-sampling plans, whose phase walk has no fixed set of 26 entries.
+constexpr int kSrcPhaseRecord = 28;
+constexpr unsigned kSrcPhaseCap = 16384;
+// P for a plan that takes the table, 0 for one that does not
+unsigned src_phase_count(const Design& d);
+// [src_phase_count(d)][kSrcPhaseRecord] floats (empty where the count is 0)
+std::vector<float> design_src_phase_table(const Design& d);
+// a voice whose glottal wavetable never follows the amplitude (tn_min == tn_max, or the sine: the first test of the
+// kernels' wavetable_entry, decided once)
+inline bool static_wavetable(const DeviceConstants& k) { return k.tn_delta == 0.0 || k.waveform != 0; }
+
 // Returns "" on success, otherwise a description of the offending value.
 std::string design_plan(const gvtm_config& cfg, double control_rate, Design& out);
 

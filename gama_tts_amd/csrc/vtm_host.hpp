@@ -109,6 +109,14 @@ struct gvtm_plan {
 	// a float plan of the models 0 to 4 whose designed decimator is gvtm::kGlottalFirF32 bit for bit (create_plan compares):
 	// its launches take the coefficients as literals (SynthArgs::fir_literals); a diagnostics build can clear it
 	bool fir_literals = false;
+	// a one-voice float plan that up-samples with at most gvtm::kSrcPhaseCap output phases: their number (create_plan), and on
+	// a device plan the converter's coefficients by phase (upload_tables; 0 again where that allocation failed).  0: the
+	// launches form the coefficients in the kernel.  A diagnostics build can clear it
+	unsigned src_phases = 0;
+	DeviceBuffer d_src_phase;
+	// a one-voice plan whose wavetable never follows the amplitude (gvtm::static_wavetable; SynthArgs::static_wavetable); a
+	// diagnostics build can clear it
+	bool static_wavetable = false;
 	// design tables on the device: double, or float (as designed) for GVTM_PRECISION_F32
 	DeviceBuffer d_wavetable, d_fir, d_src_h, d_src_dh;
 	DeviceBuffer d_consts, d_consts5; // gvtm::DeviceConstants, gvtm::Model5Constants (model 5 plans only)

@@ -130,6 +130,8 @@ struct Extent {
 //   GVTM_TUNE_SKIP    bit mask of stages left out, for counting instructions per stage (tools/collect_skip_counts.sh): a
 //                     skipped stage leaves garbage behind
 //   GVTM_TUNE_TRACE   first of two ticks whose timeline workgroup 0 records (tests/tools/tick_trace.py)
+//   GVTM_TUNE_PLAN_TABLES  which single-voice float shapes read the plan's resampler phase table (bit 0) and its
+//                     static-wavetable flag (bit 1), in place of the selectors' own choice (src_phase_table() below)
 // The design alternatives that were measured and lost (packed resampler rows, coefficient table in device memory, tickets
 // requested ahead / by position, a second pass list for the tube's idle time, role placement by SIMD, ...) are recorded in
 // DESIGN.md's A/B table, not kept here.
@@ -141,6 +143,9 @@ struct Extent {
 #endif
 #ifndef GVTM_TUNE_TRACE
 #define GVTM_TUNE_TRACE 0
+#endif
+#ifndef GVTM_TUNE_PLAN_TABLES
+#define GVTM_TUNE_PLAN_TABLES (-1)
 #endif
 // serial wavefronts that finish their stage early join the helpers for the rest of the tick: bit 1 scan, bit 3 post-tube
 // filters, bit 4 interpolation
@@ -400,6 +405,33 @@ template <int D, int U> constexpr bool fir_literal_taps() { return !((D == 1 && 
 // 73.84 / 83.77 do not gain or lose, and keep the divisions and the parent's instruction stream; so does the 48-lane layout,
 // which was not measured.
 template <typename CT, int D, int U, int LAYOUT> constexpr bool bounds_by_recurrence() { return sizeof(CT) == 4 && U == 4 && LAYOUT == 0 && (D == 2 || D == 3); }
+// which float shapes take what a plan fixes from the plan instead of forming it in every pass: the resampler's 26
+// coefficients of an output phase from the plan's table in device memory (SynthArgs::src_phase; vtm_design.hpp:
+// design_src_phase_table) and "the wavetable is static" from one uniform flag (SynthArgs::static_wavetable).  Adopted shape
+// by shape, by measurement against the parent, and never in the voice variant, whose voices have each their own time
+// increment and pulse shape; every other shape compiles to the code it had.  Parent / table / flag / both, kernel ms, mean
+// of three interleaved runs each (profiles/plan_tables_ab.md; the parent's spread behind it):
+//   four rows, SectionDelay 2 (4096 x 7500)  316.81 / 317.05 / 311.96 / 312.81  (0.46)   the flag alone
+//   four rows, SectionDelay 1 (4096 x 500)   11.890 / 11.720 / 11.803 / 11.561  (0.034)  both
+//   two rows, SectionDelay 2 (512 x 500)      4.800 /  4.729 /  4.765 /  4.728  (0.015)  both
+//   one row, SectionDelay 1 (256 x 500)       2.428 /  2.418 /  2.422 /  2.432  (0.013)  neither: no gain
+//   one row, SectionDelay 2 (256 x 500)       4.504 /  4.569 /  4.532 /  4.503  (0.010)  neither: each alone is slower
+// The other float shapes (SectionDelay 3 and 4, two rows at SectionDelay 1, eight rows, the 48-lane layout) were not measured
+// and take neither.
+// GVTM_TUNE_PLAN_TABLES (a variant library's, for those measurements): bit 0 / bit 1 give every single-voice float shape
+// the table / the flag, and no other shape either.
+template <typename CT, int D, int U, int LAYOUT, bool VOICES> constexpr bool src_phase_table()
+{
+	constexpr bool can = sizeof(CT) == 4 && !VOICES;
+	if (GVTM_TUNE_PLAN_TABLES >= 0) return can && (GVTM_TUNE_PLAN_TABLES & 1) != 0;
+	return can && LAYOUT == 0 && ((U == 4 && D == 1) || (U == 2 && D == 2));
+}
+template <typename CT, int D, int U, int LAYOUT, bool VOICES> constexpr bool static_wavetable_pass()
+{
+	constexpr bool can = sizeof(CT) == 4 && !VOICES;
+	if (GVTM_TUNE_PLAN_TABLES >= 0) return can && (GVTM_TUNE_PLAN_TABLES & 2) != 0;
+	return can && LAYOUT == 0 && ((U == 4 && (D == 1 || D == 2)) || (U == 2 && D == 2));
+}
 template <typename CT, int D, int U, bool VOICES> constexpr bool float_arg_consts() { return sizeof(CT) == 4 && !VOICES && !far_calls_inline<D, U>(); }
 
 template <typename CT, typename ST, int D, int U, int C, int NH, int LAYOUT_FLAGS>
@@ -502,6 +534,8 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	constexpr bool kHelperByRole = sizeof(CT) == 4 || D >= 3 || (sizeof(ST) == 8 && D == 2);
 	constexpr bool kNoiseTable = sizeof(CT) == 4; // one-shot launches of the float model read the noise samples from the plan's table
 	constexpr bool kBoundsRecurrence = bounds_by_recurrence<CT, D, U, LAYOUT>();
+	constexpr bool kSrcPhaseTable = src_phase_table<CT, D, U, LAYOUT, VOICES>();
+	constexpr bool kStaticWavetablePass = static_wavetable_pass<CT, D, U, LAYOUT, VOICES>();
 	constexpr int kKlLen = kl_len(kLaneRec);
 	constexpr int kInjLen = kLaneRec ? kKlLen : kInj; // stride of a step's injection values
 	auto at_kl = [](int slot, int u) { return rec_at<C, U>(kKlLen, slot, u); };
@@ -771,6 +805,35 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	// is three dependent LDS round trips of several hundred cycles each under load, for some 25 instructions.
 	constexpr int kP4aItems = 1; // (two per lane: pass time 170 -> 123 cycles per step but the kernel no faster -- fewer, longer passes at a tick's end)
 	auto stage_p4a = [&](int c, int pass) {
+		if constexpr (kStaticWavetablePass) {
+			// The plan has said that the table never follows the amplitude (a.static_wavetable; every shipped voice): position,
+			// the two entries, interpolate, store -- no amplitude read and nothing from the constants block, which
+			// wavetable_entry below reads (waveform, tn_delta, the two divisions) and waits for before its first table read.
+			if (a.static_wavetable != 0) {
+				static_assert(kP4aItems == 1, "one item per lane and pass");
+				const int item = pass * 64 + hl;
+				const int u = item / (2 * C), h = item - u * 2 * C;
+				if (item >= U * 2 * C || h >= 2 * valid_in(u, c)) return;
+				const CT p = sm.pos[((c & 1) * U + u) * 2 * C + h];
+				// a position in (-1, 0) truncates towards zero, as the reference's cast does
+				const unsigned lower = static_cast<unsigned>(static_cast<int>(p));
+				const unsigned upper = (lower + 1 > 511u) ? lower + 1 - 512u : lower + 1;
+				const CT wl = sm.wavetable[lower];
+				const CT wu = sm.wavetable[upper];
+				const CT v = wl + rmul(p - static_cast<CT>(lower), wu - wl);
+				CT* slot = sm.w + (static_cast<size_t>(c % 3) * U + u) * (kWPre + 2 * C);
+				slot[kWPre + h] = v;
+				if (GVTM_KERNEL_TAPS && a.debug_taps) {
+					a.debug_taps[(GVTM_ROW_UTT(u, (group * U + u)) * a.max_frames * k.control_steps + static_cast<size_t>(c) * C + (h >> 1)) * 8 + 5 + (h & 1)] = p;
+				}
+				if (h >= 2 * C - kWPre) {
+					// the tail of a chunk doubles as the FIR pre-roll of the next one
+					CT* next = sm.w + (static_cast<size_t>((c + 1) % 3) * U + u) * (kWPre + 2 * C);
+					next[h - (2 * C - kWPre)] = v;
+				}
+				return;
+			}
+		}
 		if constexpr (U == 1) {
 			// one item per lane, reads where they are needed (one utterance per workgroup: measured 1-3 % faster this way)
 			for (int item = pass * 64 + hl; item < U * 2 * C && item < (pass + 1) * 64; item += 64) {
@@ -1161,8 +1224,42 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 #pragma unroll
 				for (int j = 0; j < kZ; ++j) tapv(xv[j], mad(cf[j].dh, ip, cf[j].h));
 			};
+			// The 26 coefficients depend on frac alone, frac on ko mod (a.src_phase_mask + 1): a plan that has tabulated them by
+			// output phase (a.src_phase, device memory) hands a lane its record -- seven 16-byte loads at immediate offsets from
+			// one address, on the vector-memory path, which a tick leaves idle -- and the wings read samples only: no table
+			// entry from LDS, no address arithmetic for 26 of them, no coefficient formed.  The host made each entry with the
+			// operations of mad(cf.dh, ip, cf.h) on the plan's own float tables (design_src_phase_table), so the bits are these.
+			// The wing's rule holds: every read is out before the arithmetic starts, the record's with the first wing's samples.
+			if constexpr (kSrcPhaseTable) {
+				if (a.src_phase != nullptr) {
+					using F4 = float __attribute__((ext_vector_type(4)));
+					constexpr int kZ = kSrcZeroCrossings;
+					static_assert(kSrcPhaseRecord % 4 == 0 && 2 * kZ <= kSrcPhaseRecord, "a record: both wings in whole 16-byte loads");
+					const F4* rec = reinterpret_cast<const F4*>(a.src_phase + static_cast<size_t>(static_cast<unsigned>(ko) & a.src_phase_mask) * kSrcPhaseRecord);
+					F4 cq[kSrcPhaseRecord / 4];
+#pragma unroll
+					for (int q = 0; q < kSrcPhaseRecord / 4; ++q) cq[q] = rec[q];
+					auto wing_samples = [&](int c0, int x0, int xstep) {
+						ST xv[kZ][UG];
+#pragma unroll
+						for (int j = 0; j < kZ; ++j) {
+#pragma unroll
+							for (int u = 0; u < UG; ++u) xv[j][u] = xg[u * XRS + x0 + xstep * j];
+						}
+						asm volatile("" ::: "memory");
+#pragma unroll
+						for (int j = 0; j < kZ; ++j) tapv(xv[j], static_cast<ST>(cq[(c0 + j) >> 2][(c0 + j) & 3]));
+					};
+					wing_samples(0, lo + (kZ - 1), -1);
+					wing_samples(kZ, lo + kZ, 1);
+				} else {
+					wing(l, interp, lo + (kSrcZeroCrossings - 1), -1);
+					wing(l2, interp2, lo + kSrcZeroCrossings, 1);
+				}
+			} else {
 			wing(l, interp, lo + (kSrcZeroCrossings - 1), -1);
 			wing(l2, interp2, lo + kSrcZeroCrossings, 1);
+			}
 			} else if constexpr (U >= 4) {
 				// the double paths: a wing in groups of a few taps, a group's reads before its arithmetic (whole wings
 				// spill there; tap by tap every tap waits for its own LDS round trip)

@@ -116,6 +116,14 @@ struct SynthArgs {
 	// float plans: `fir` is kGlottalFirF32 bit for bit (the plan compared them when it was made), so the decimator's
 	// unrolled tap loop runs, with its coefficients from that table as literals; 0: the generic loop over `fir`
 	int fir_literals = 0;
+	// float plans that up-sample: the converter's coefficients by output phase, [src_phase_mask + 1][kSrcPhaseRecord] floats
+	// in device memory (vtm_design.hpp: design_src_phase_table; the plan uploads it once), read by the shapes
+	// v2::src_phase_table() names; null: every shape forms the coefficients from the LDS table, pass by pass
+	const float* src_phase = nullptr;
+	unsigned src_phase_mask = 0;
+	// the voice's wavetable never follows the amplitude (vtm_design.hpp: static_wavetable): the shapes
+	// v2::static_wavetable_pass() names look the two entries up and read neither amplitude nor constants; 0: wavetable_entry
+	int static_wavetable = 0;
 };
 
 struct GroupVoicesArgs {
