@@ -179,6 +179,11 @@ def _prototypes():
         "gvtm_modification_apply_host": (i, [vp, i, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
         "gvtm_apply_modifications_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]),
         "gvtm_synthesize_modified_device": (i, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]),
+        "gvtm_targets_filter_length": (i64, [vp, i]),
+        "gvtm_targets_output_count": (sz, [vp, sz]),
+        "gvtm_targets_output_capacity": (sz, [vp, sz]),
+        "gvtm_targets_apply_host": (i, [vp, i, vp, vp, vp, i64, vp, vp]),
+        "gvtm_synthesize_targets_device": (i, [vp, vp, sz, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
         "gvtm_stream_push_events": (i, [vp, vp, vp, vp, vp, sz, vp, vp]),
         "gvtm_stream_get_drift": (i, [vp, vp]),
         "gvtm_stream_set_drift": (i, [vp, vp]),
@@ -467,6 +472,34 @@ def modification_apply_host(plan, frames, gestures, voice=0, frames_out=None):
     status = ctypes.c_int32(-1)
     _check(plan._lib, plan._lib.gvtm_modification_apply_host(plan._h, int(voice), _ptr(frames), frames.shape[0], _ptr(table), _ptr(offsets),
                                                              len(gestures), _ptr(steps), _ptr(values), _ptr(out), ctypes.byref(status)))
+    return out, int(status.value)
+
+
+def pack_targets(lists):
+    """lists[l]: one list of points, (steps, values) -> (list_offsets int64 [L + 1], point_steps int32, point_values
+    float32): the tables of the targets entries, the points of all lists back to back.  (An utterance's 16 lists, or a batch's
+    lists with the ids that name them.)"""
+    steps = [np.asarray(l[0], dtype=np.int32).reshape(-1) for l in lists]
+    values = [np.asarray(l[1], dtype=np.float32).reshape(-1) for l in lists]
+    assert all(s.shape == v.shape for s, v in zip(steps, values))
+    offsets = np.zeros(len(lists) + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([len(s) for s in steps])
+    point_steps = np.concatenate(steps) if steps else np.zeros(0, np.int32)
+    point_values = np.concatenate(values) if values else np.zeros(0, np.float32)
+    return offsets, np.ascontiguousarray(point_steps), np.ascontiguousarray(point_values)
+
+
+def targets_apply_host(plan, lists, n_steps, voice=0, frames_out=None):
+    """gvtm_targets_apply_host: the 16 lists of one utterance, each (steps, values), through the 50 ms filter of voice `voice`
+    of `plan` -> (the parameters by step float32 [n_steps][16], status).  A refused utterance leaves frames_out (by default
+    zeros) as it was."""
+    assert len(lists) == N_PARAM
+    offsets, steps, values = pack_targets(lists)
+    out = np.zeros((max(int(n_steps), 0), N_PARAM), dtype=np.float32) if frames_out is None else frames_out
+    assert out.dtype == np.float32 and out.flags.c_contiguous and out.size >= max(int(n_steps), 0) * N_PARAM
+    status = ctypes.c_int32(-1)
+    _check(plan._lib, plan._lib.gvtm_targets_apply_host(plan._h, int(voice), _ptr(offsets), _ptr(steps), _ptr(values), int(n_steps), _ptr(out),
+                                                        ctypes.byref(status)))
     return out, int(status.value)
 
 
@@ -845,6 +878,29 @@ class Plan:
             self._h, _ptr(d_base_params), _ptr(d_base_frame_counts), int(n_bases), _ptr(d_base_ids), _ptr(d_gestures), _ptr(d_gesture_offsets),
             _ptr(d_utt_gestures), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_voice_ids), int(batch), int(max_frames), _ptr(d_audio),
             int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status), _ptr(stream)))
+
+    def targets_filter_length(self, voice=0):
+        """gvtm_targets_filter_length: the samples of the interactive window's 50 ms moving average at the voice's internal rate."""
+        n = int(self._lib.gvtm_targets_filter_length(self._h, int(voice)))
+        if n < 0:
+            raise GvtmError(1, self._lib.gvtm_last_error().decode())
+        return n
+
+    def targets_output_count(self, steps):
+        """gvtm_targets_output_count: the samples of an utterance of `steps` internal steps."""
+        return _count(self._lib, int(self._lib.gvtm_targets_output_count(self._h, int(steps))))
+
+    def targets_output_capacity(self, max_steps):
+        """gvtm_targets_output_capacity: the row length that holds every utterance of up to max_steps steps."""
+        return _count(self._lib, int(self._lib.gvtm_targets_output_capacity(self._h, int(max_steps))))
+
+    def synthesize_targets_device(self, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, batch, max_steps,
+                                  d_audio, audio_stride, d_out_counts=None, d_maxabs=None, d_status=None, stream=None):
+        """Target lists (the tables of pack_targets; d_list_ids None: utterance b's parameter p walks list 16 b + p) in,
+        samples out (gvtm_synthesize_targets_device); all pointers are device memory."""
+        self._check(self._lib.gvtm_synthesize_targets_device(
+            self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
+            int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status), _ptr(stream)))
 
     def synthesize_events_device(self, track_config, d_events, d_offsets, batch, max_frames, d_audio, audio_stride,
                                  d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, stream=None):

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "vtm_host.hpp"
+#include "vtm_targets.hpp"
 
 #ifndef GVTM_NOISE_TABLE
 #define GVTM_NOISE_TABLE 1
@@ -98,9 +99,18 @@ gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 		if (r.voices && !dg.model5) args.stream_chunk = gvtm::synth_chunk_length(dg.k, plan->precision, 1);
 	}
 	// (not for several voices: the hooks' buffers are sized for voice 0's steps and ceil(batch / rows) workgroups)
-	args.debug_taps = r.voices ? nullptr : plan->debug_taps;
+	// (nor the taps from targets: their buffer is laid out by frames)
+	args.debug_taps = r.voices || r.targets ? nullptr : plan->debug_taps;
 	args.phase_cycles = r.voices ? nullptr : plan->phase_cycles;
 	args.k5const = static_cast<const gvtm::Model5Constants*>(plan->d_consts5.ptr);
+	if (r.targets) {
+		args.tg_offsets = r.targets->list_offsets;
+		args.tg_ids = r.targets->list_ids;
+		args.tg_steps = r.targets->point_steps;
+		args.tg_values = r.targets->point_values;
+		args.tg_N = r.targets->N;
+		args.tg_invN = r.targets->invN;
+	}
 	return args;
 }
 
@@ -157,12 +167,16 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (r.batch == 0) return GVTM_OK;
 	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
 	if (r.voices && !r.voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
-	if (r.max_frames > 0 && !r.params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
+	if (r.targets && (r.voices || r.sl || plan->designs[0].model5 || !r.frame_counts)) return fail(GVTM_ERR_UNSUPPORTED, "targets: a one-shot launch of one voice of the models 0 to 4");
+	if (r.max_frames > 0 && !r.params && !r.targets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	// (several voices: the row map's int32 slots also count up to n_voices partly empty workgroups)
 	if (r.batch > (r.voices ? 0x3fffffffu : 0x7fffffffu)) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
-	if (!fits_step_counter(plan, r.max_frames)) return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
+	// (from targets max_frames counts steps, and the entry has held the stride against them)
+	if (r.targets ? !gvtm::targets_fits_step_counter(static_cast<int64_t>(std::min<size_t>(r.max_frames, INT64_MAX))) : !fits_step_counter(plan, r.max_frames)) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_frames * control_steps does not fit the 31-bit step counter");
+	}
 	// (a stream checks its stride against what each call produces: stream_launch)
-	if (const int rc = r.sl ? GVTM_OK : check_audio_stride(plan, r.audio_stride, r.max_frames, r.voices); rc != GVTM_OK) return rc;
+	if (const int rc = r.sl || r.targets ? GVTM_OK : check_audio_stride(plan, r.audio_stride, r.max_frames, r.voices); rc != GVTM_OK) return rc;
 	const bool model5 = plan->designs[0].model5;
 	if (r.voices && model5 && plan->designs[0].f32 && !plan->float5_voices) {
 		return fail(GVTM_ERR_UNSUPPORTED, "a gvtm_plan_create_model5_float plan has no launch of several voices (one voice per plan; "
@@ -194,7 +208,7 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (!model5 && !r.sl && GVTM_NOISE_TABLE && plan->precision == GVTM_PRECISION_F32) {
 		// one-shot launches read the noise samples from the plan's table, one for every voice (every utterance starts from
 		// the same seed), as long as the voice with the most steps needs (streams generate them: their length has no bound)
-		if (const int rc = use_noise_table(plan, r.max_frames * static_cast<size_t>(max_control_steps(plan)), args); rc != GVTM_OK) return rc;
+		if (const int rc = use_noise_table(plan, r.max_frames * static_cast<size_t>(r.targets ? 1u : max_control_steps(plan)), args); rc != GVTM_OK) return rc;
 	}
 	return timed_launch(plan, stream, r.voices ? "vtm_synth_kernel launch (voices)" : "vtm_synth_kernel launch", [&] {
 		return model5 ? gvtm::launch_synth5(args, work, plan->precision, shape.forced - 1, stream) : gvtm::launch_synth(args, work, plan->precision, rows, stream);

@@ -8,12 +8,6 @@ using namespace gvtm::host;
 
 namespace {
 
-// the internal rate as the voice's model holds it (gvtm_info::internal_rate_hz)
-double internal_rate_hz(const gvtm::Design& dg)
-{
-	return dg.model5 ? dg.k5.sample_rate : static_cast<double>(dg.k.sample_rate);
-}
-
 // The batch of a device entry as the caller gives it
 struct ModificationBatch {
 	const float* d_base_params;

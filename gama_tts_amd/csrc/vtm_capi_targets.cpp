@@ -1,0 +1,98 @@
+// C ABI of libgama_vtm.so, synthesis from parameter targets (the editor's interactive window): the filter length, the sample
+// counts by internal steps, the rule on the host, and the device entry, which puts the synthesis launch -- the kernel's
+// targets driver, launch_synthesis with LaunchRequest::targets -- behind the check kernel with the plan's step counts in
+// between.
+#include "vtm_host.hpp"
+#include "vtm_targets.hpp"
+
+using namespace gvtm::host;
+
+extern "C" {
+
+int64_t gvtm_targets_filter_length(const gvtm_plan* plan, int voice)
+{
+	if (!plan || voice < 0 || voice >= plan->n_voices()) { fail(GVTM_ERR_INVALID_ARGUMENT, "null plan or voice index out of range"); return -1; }
+	return gvtm::targets_filter_length(internal_rate_hz(plan->designs[voice]));
+}
+
+size_t gvtm_targets_output_count(const gvtm_plan* plan, size_t n_steps)
+{
+	if (!plan) return static_cast<size_t>(-1);
+	return steps_output_count(plan->designs[0], n_steps);
+}
+
+size_t gvtm_targets_output_capacity(const gvtm_plan* plan, size_t max_steps)
+{
+	if (!plan) return static_cast<size_t>(-1);
+	return steps_output_capacity(plan->designs[0], max_steps);
+}
+
+int gvtm_targets_apply_host(const gvtm_plan* plan, int voice, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
+		int64_t n_steps, float* frames_out, int32_t* status_out)
+{
+	if (!plan || !status_out || !list_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan, status_out or list_offsets");
+	if (!frames_out && n_steps > 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null frames_out with n_steps > 0");
+	if (voice < 0 || voice >= plan->n_voices()) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice index out of range");
+	bool points = false, ordered = true;
+	for (int p = 0; p < GVTM_N_PARAM; ++p) {
+		ordered = ordered && list_offsets[p] >= 0 && list_offsets[p + 1] >= list_offsets[p];
+		points = points || list_offsets[p + 1] > list_offsets[p];
+	}
+	// (offsets out of order are the utterance's status 2, whatever the tables)
+	if (ordered && points && (!point_steps || !point_values)) return fail(GVTM_ERR_INVALID_ARGUMENT, "null point_steps or point_values with points");
+	*status_out = gvtm::targets_apply(gvtm::targets_filter_length(internal_rate_hz(plan->designs[voice])), list_offsets, point_steps, point_values, n_steps,
+			frames_out);
+	return GVTM_OK;
+}
+
+int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
+		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, size_t batch, size_t max_steps, float* d_audio,
+		size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (batch > 0) {
+		if (!d_list_offsets || !d_point_steps || !d_point_values || !d_audio) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "null list offsets, point steps, point values or audio buffer");
+		}
+		if (batch > 0x7fffffffu / GVTM_N_PARAM) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
+		if (!d_list_ids && n_lists != GVTM_N_PARAM * batch) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "without list ids every utterance has 16 lists of its own: n_lists must equal 16 * batch");
+		}
+		if (!gvtm::targets_fits_step_counter(static_cast<int64_t>(std::min<size_t>(max_steps, INT64_MAX)))) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "max_steps does not fit the 31-bit step counter");
+		}
+		if (audio_stride < steps_output_capacity(plan->designs[0], max_steps)) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_targets_output_capacity(plan, max_steps)");
+		}
+	}
+	if (plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_device: a plan of one voice only");
+	if (plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_device: the models 0 to 4 only");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
+	if (batch == 0) return GVTM_OK;
+	// The check kernel and the synthesis launch on the caller's stream, with the plan's step counts in between: the
+	// utterance's own count, or 0 for a refused utterance.
+	DeviceScope scope(plan->device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	hipError_t e;
+	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc step counts");
+	int32_t* const d_steps = plan->async.frames.as<int32_t>();
+	gvtm::TargetsCheckArgs check{};
+	check.list_offsets = d_list_offsets;
+	check.n_lists = static_cast<int64_t>(std::min<size_t>(n_lists, INT64_MAX));
+	check.list_ids = d_list_ids;
+	check.point_steps = d_point_steps;
+	check.point_values = d_point_values;
+	check.step_counts = d_step_counts;
+	check.batch = batch;
+	check.max_steps = max_steps;
+	check.steps_out = d_steps;
+	check.status = d_status;
+	if ((e = gvtm::launch_targets_check(check, static_cast<hipStream_t>(hip_stream))) != hipSuccess) return fail_hip(e, "vtm_targets_check_kernel launch");
+	const int64_t N = gvtm::targets_filter_length(internal_rate_hz(plan->designs[0]));
+	const TargetsLaunch targets{d_list_offsets, d_list_ids, d_point_steps, d_point_values, N, 1.0 / static_cast<double>(N)};
+	LaunchRequest r{nullptr, d_steps, batch, max_steps, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream};
+	r.targets = &targets;
+	return launch_synthesis(plan, r);
+}
+
+} // extern "C"

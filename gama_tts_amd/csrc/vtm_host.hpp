@@ -144,7 +144,7 @@ struct gvtm_plan {
 		void release_sets() { for (DeviceBuffer& s : set) s = DeviceBuffer(); }
 		unsigned char* set_of(size_t i) const { return set[i % 3].as<unsigned char>(); } // slice i's: the sets rotate
 	} host;
-	// ... and the enqueue-only entries' (gvtm_synthesize_events_device's and gvtm_synthesize_modified_device's frames and frame counts, the grouping of
+	// ... and the enqueue-only entries' (gvtm_synthesize_events_device's and gvtm_synthesize_modified_device's frames and frame counts, gvtm_synthesize_targets_device's step counts, the grouping of
 	// gvtm_synthesize_voices_device, the merged event lists and their offsets of gvtm_synthesize_intonation_device): calls to
 	// those on one plan must be ordered on one stream
 	struct {
@@ -278,16 +278,34 @@ inline int events_scratch(gvtm_plan* plan, size_t batch, size_t max_frames, int3
 	return GVTM_OK;
 }
 
-inline size_t design_output_count(const gvtm::Design& dg, size_t n_frames)
+// the internal rate as the voice's model holds it (gvtm_info::internal_rate_hz): what the two moving averages' lengths follow
+inline double internal_rate_hz(const gvtm::Design& dg)
+{
+	return dg.model5 ? dg.k5.sample_rate : static_cast<double>(dg.k.sample_rate);
+}
+
+// the samples finishSynthesis() leaves after n_steps internal steps (flush overrun included), whatever the control rate ...
+inline size_t steps_output_count(const gvtm::Design& dg, size_t n_steps)
 {
 	const gvtm::DeviceConstants& k = dg.k;
-	return static_cast<size_t>(gvtm::src_output_count(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(n_frames) * k.control_steps));
+	return static_cast<size_t>(gvtm::src_output_count(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(n_steps)));
+}
+
+// ... and the row length that holds every utterance of up to max_steps steps
+inline size_t steps_output_capacity(const gvtm::Design& dg, size_t max_steps)
+{
+	const gvtm::DeviceConstants& k = dg.k;
+	return static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(max_steps)));
+}
+
+inline size_t design_output_count(const gvtm::Design& dg, size_t n_frames)
+{
+	return steps_output_count(dg, n_frames * dg.k.control_steps);
 }
 
 inline size_t design_output_capacity(const gvtm::Design& dg, size_t max_frames)
 {
-	const gvtm::DeviceConstants& k = dg.k;
-	return static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(max_frames) * k.control_steps));
+	return steps_output_capacity(dg, max_frames * dg.k.control_steps);
 }
 
 // Host voice ids (the streams of several voices, the packed layouts): all of them in [0, n_voices), or the call is refused
@@ -363,6 +381,17 @@ struct StreamLaunch {
 	int xr;       // the stream's ring length (one for all shapes; several voices: the longest of the plan's voices)
 };
 
+// what a launch from parameter targets (gvtm_synthesize_targets_device) has in the place of frames: the request's
+// frame_counts are then its step counts, as the check kernel left them, and its max_frames the most steps of an utterance
+struct TargetsLaunch {
+	const int64_t* list_offsets;
+	const int32_t* list_ids;   // or null
+	const int32_t* point_steps;
+	const float* point_values;
+	int64_t N;                 // the filter's length and its reciprocal
+	double invN;
+};
+
 // One synthesis launch: the device buffers of a gvtm_synthesize_*_device call, of a slice of the host entries or of a stream
 struct LaunchRequest {
 	const float* params;
@@ -378,6 +407,7 @@ struct LaunchRequest {
 	const int32_t* voice_ids = nullptr;
 	DeviceBuffer* groups = nullptr;     // voices: the caller's scratch for the row map, group voices and sort counts
 	const StreamLaunch* sl = nullptr;   // or null: a one-shot launch
+	const TargetsLaunch* targets = nullptr; // or null: a launch from frames
 };
 
 // Every synthesis launch, enqueue-only (vtm_capi_launch.cpp)

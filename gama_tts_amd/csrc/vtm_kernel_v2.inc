@@ -380,6 +380,13 @@ constexpr int serial_waves()
 // the same code.  (A separate bool parameter would rename every kernel, a wrapper kernel around an inlined body changes
 // what the register allocator spills: float, eight rows 476 -> 620 bytes of scratch.)
 constexpr int kVoicesFlag = 2;
+// Synthesis from parameter targets (gvtm_synthesize_targets_device): a third bit of the same argument, kTargetsFlag (default
+// off, one voice only).  With it the interpolation wavefront has a second driver: lane L of row u walks the points of list
+// a.tg_ids[16 utt + L] through the moving average of vtm_targets.hpp and writes the same float per step into the `prm`
+// record; an utterance is a.frame_counts[utt] STEPS long, and there are no frames.  Nothing else differs between the two
+// drivers, and as with kVoicesFlag every difference is a conditional on the constant TARGETS whose targets arm the
+// compiler never emits for the other kernels.
+constexpr int kTargetsFlag = 4;
 
 __device__ __forceinline__ size_t voice_row(const SynthArgs& a, size_t slot)
 {
@@ -439,6 +446,8 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 {
 	constexpr int LAYOUT = LAYOUT_FLAGS & 1; // gvtm_tube_layout
 	constexpr bool VOICES = (LAYOUT_FLAGS & kVoicesFlag) != 0;
+	constexpr bool TARGETS = (LAYOUT_FLAGS & kTargetsFlag) != 0;
+	static_assert(!(TARGETS && VOICES), "targets: one voice");
 	int voice = 0;
 	if constexpr (VOICES) {
 		voice = a.group_voice[blockIdx.x];
@@ -590,7 +599,8 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			const int f = a.frame_counts ? a.frame_counts[ug] : static_cast<int>(rows_avail);
 			// device-resident counts cannot be validated by the host: clamp to the allocated frames
 			e.frames = f > 0 ? (static_cast<size_t>(f) < rows_avail ? f : static_cast<int>(rows_avail)) : 0;
-			e.steps = static_cast<uint32_t>(e.frames) * sm.kc->control_steps;
+			// (targets: the counts are steps, and `frames` holds them)
+			e.steps = TARGETS ? static_cast<uint32_t>(e.frames) : static_cast<uint32_t>(e.frames) * sm.kc->control_steps;
 			e.nchunks = e.steps == 0 ? 1 : static_cast<int>((e.steps + C - 1) / C);
 			e.last_frame = e.frames - 1 + (kPush ? 1 : 0);
 			if (a.stream) {
@@ -716,7 +726,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	int ip_frame = 0;
 	const int Lp = lane & 15;  // parameter index of an interpolation lane
 	const int rowp = sub * 4 + (lane >> 4); // its utterance
-	if (role == 4 && rowp < U) {
+	if (!TARGETS && role == 4 && rowp < U) {
 		const int frames = sm.ext[rowp].frames;
 		const int last = sm.ext[rowp].last_frame;
 		if (frames > 0) {
@@ -724,6 +734,17 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			ip_this = P[Lp];
 			ip_next = P[static_cast<size_t>(last > 1 ? 1 : last) * 16 + Lp];
 			ip_next2 = P[static_cast<size_t>(last > 2 ? 2 : last) * 16 + Lp];
+		}
+	}
+	// I, from targets: lane L of row u walks the points of utterance u's list for parameter L (vtm_targets.hpp): the filter's
+	// sum, the entering and the leaving value, the two cursors and the steps at which they move next.  (A refused utterance
+	// has 0 steps: its list ids and offsets are never read.)
+	[[maybe_unused]] TargetsWalk tg{};
+	if constexpr (TARGETS) {
+		if (role == 4 && rowp < U && sm.ext[rowp].frames > 0) {
+			const size_t slot = (group * U + rowp) * GVTM_N_PARAM + Lp;
+			const int64_t list = a.tg_ids ? static_cast<int64_t>(a.tg_ids[slot]) : static_cast<int64_t>(slot);
+			targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N);
 		}
 	}
 
@@ -1393,6 +1414,27 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 		const int c = t + (Lp < 3 ? 2 : (Lp < 7 ? -1 : -2));
 		const int valid = valid_in(u, c);
 		if (valid <= 0) return;
+		if constexpr (TARGETS) {
+			// The second driver: the moving average of the lane's target list, step by step.  Blocks of four steps as below:
+			// the cursors' bookkeeping only runs for a block in which some lane's cursor moves (a point enters, or leaves N
+			// steps later); every other block is four times {two double additions, a multiplication, a conversion, a store}.
+			// A partial last block runs on: no cursor passes the end of its list, and the extra rows are never read.
+			float* out = sm.prm + at_prm(c & 1, u) + Lp;
+			const int64_t first = static_cast<int64_t>(c) * C;
+			for (int s0 = 0; s0 < valid; s0 += 4) {
+				if (__builtin_expect(__any(targets_moves(tg, first + s0, 4)), 0)) {
+#pragma unroll
+					for (int q = 0; q < 4; ++q) {
+						targets_move(tg, first + s0 + q, a.tg_steps, a.tg_values, a.tg_N);
+						out[(s0 + q) * kPrm] = targets_step(tg, a.tg_invN);
+					}
+				} else {
+#pragma unroll
+					for (int q = 0; q < 4; ++q) out[(s0 + q) * kPrm] = targets_step(tg, a.tg_invN);
+				}
+			}
+			return;
+		}
 		const int last = sm.ext[u].last_frame;
 		const float* __restrict__ P = a.params + GVTM_ROW_UTT(u, (group * U + u)) * a.max_frames * 16;
 		float* out = sm.prm + at_prm(c & 1, u) + Lp;

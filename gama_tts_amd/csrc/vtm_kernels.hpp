@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "vtm_design.hpp"
+#include "vtm_targets.hpp" // (the walk of the synthesis kernel's targets driver: vtm_kernel_v2.inc is included inside a namespace)
 
 namespace gvtm {
 
@@ -124,6 +125,17 @@ struct SynthArgs {
 	// the voice's wavetable never follows the amplitude (vtm_design.hpp: static_wavetable): the shapes
 	// v2::static_wavetable_pass() names look the two entries up and read neither amplitude nor constants; 0: wavetable_entry
 	int static_wavetable = 0;
+	// launches from parameter targets (tg_offsets set: launch_synth runs the targets variant, vtm_kernels_targets.hip; the
+	// kernel's kTargetsFlag): utterance b's parameter p walks list l = tg_ids ? tg_ids[16 b + p] : 16 b + p, the points
+	// [tg_offsets[l], tg_offsets[l + 1]) of tg_steps / tg_values, through a moving average of tg_N samples (vtm_targets.hpp).
+	// frame_counts then holds the utterances' STEP counts (never null: the check kernel's, 0 for a refused utterance),
+	// max_frames the most steps of an utterance, and params is unused
+	const int64_t* tg_offsets = nullptr;
+	const int32_t* tg_ids = nullptr;
+	const int32_t* tg_steps = nullptr;
+	const float* tg_values = nullptr;
+	int64_t tg_N = 0;
+	double tg_invN = 0.0;
 };
 
 struct GroupVoicesArgs {
@@ -174,6 +186,9 @@ int synth_chunk_length(const DeviceConstants& k, int precision, int rows);
 // batch: utterances, or with args.row_map set (several voices) the workgroups of launch_group_voices' map, of one voice
 // each (args.xr: the longest ring of the voices; a stream's rings follow args.stream_chunk)
 hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream);
+// the targets variant alone (vtm_kernels_targets.hip; launch_synth calls it where args.tg_offsets is set): one voice, one,
+// two or four rows
+hipError_t launch_synth_targets(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream);
 // bytes of one utterance's stream state for a plan (ring length of the one-row shape: streams whose utterances are not in
 // lockstep run one utterance per workgroup, and every shape of a stream uses that ring length)
 size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr);

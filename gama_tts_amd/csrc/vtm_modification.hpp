@@ -21,11 +21,12 @@
 #include "../../include/gama_vtm.h"
 #include "vtm_design.hpp"
 
+// (a name of its own: vtm_math.hpp's GVTM_HD also forces inlining, and the synthesis kernels' units include both headers)
 #if defined(__HIP__)
 #include <hip/hip_runtime.h>
-#define GVTM_HD __host__ __device__
+#define GVTM_HOST_DEVICE __host__ __device__
 #else
-#define GVTM_HD
+#define GVTM_HOST_DEVICE
 #endif
 
 namespace gvtm {
@@ -39,37 +40,56 @@ enum ModificationStatus : int32_t {
 	kModificationBadSteps = 4,    // a negative step, steps not strictly increasing within a gesture
 };
 
-// MovingAverageFilter<float>(static_cast<float>(internalSampleRate()), 20.0e-3): buf_(std::round(sampleRate * period)), a
-// float product rounded half away from zero (at 22 125 Hz the product is 442.5 and N is 443; rounding half to even would say 442)
-GVTM_HD inline int64_t modification_filter_length(double internal_rate_hz)
+// MovingAverageFilter<float>(static_cast<float>(internalSampleRate()), period): buf_(std::round(sampleRate * period)), a
+// float product rounded half away from zero (20 ms at 22 125 Hz: the product is 442.5 and N is 443; rounding half to even
+// would say 442).  The editor has two such filters: the modification window's of 20 ms, the interactive window's of 50 ms
+// (vtm_targets.hpp).
+GVTM_HOST_DEVICE inline int64_t moving_average_length(double internal_rate_hz, float period)
 {
-	const float rate = static_cast<float>(internal_rate_hz), period = static_cast<float>(20.0e-3);
+	const float rate = static_cast<float>(internal_rate_hz);
 	const float product = rate * period;
 	return static_cast<int64_t>(static_cast<size_t>(__builtin_roundf(product)));
 }
 
-GVTM_HD inline unsigned long long modification_bits(double x)
+GVTM_HOST_DEVICE inline int64_t modification_filter_length(double internal_rate_hz)
+{
+	return moving_average_length(internal_rate_hz, static_cast<float>(20.0e-3));
+}
+
+// One call of the filter behind its first (vtm/MovingAverageFilter.h:86-88): sum -= leaving; sum += entering.  Two double
+// additions, each rounded, in this order; THE text of them for both filters, host and device.
+GVTM_HOST_DEVICE inline double moving_average_step(double sum, double leaving, double entering)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+	sum = sum - leaving;
+	sum = sum + entering;
+	return sum;
+}
+
+GVTM_HOST_DEVICE inline unsigned long long modification_bits(double x)
 {
 	unsigned long long u;
 	__builtin_memcpy(&u, &x, sizeof u);
 	return u;
 }
 
-GVTM_HD inline unsigned modification_bits(float x)
+GVTM_HOST_DEVICE inline unsigned modification_bits(float x)
 {
 	unsigned u;
 	__builtin_memcpy(&u, &x, sizeof u);
 	return u;
 }
 
-GVTM_HD inline bool modification_finite(float x)
+GVTM_HOST_DEVICE inline bool modification_finite(float x)
 {
 	return (modification_bits(x) & 0x7f800000u) != 0x7f800000u;
 }
 
 // The first frame a gesture whose first point lies at `step` writes: the frame whose first internal step is the first
 // multiple of cs at or behind it.  (A gesture acts if that frame exists: first < n_frames.)
-GVTM_HD inline int64_t modification_first_frame(int64_t step, int64_t cs)
+GVTM_HOST_DEVICE inline int64_t modification_first_frame(int64_t step, int64_t cs)
 {
 	return (step + cs - 1) / cs + 1;
 }
@@ -83,7 +103,7 @@ GVTM_HD inline int64_t modification_first_frame(int64_t step, int64_t cs)
 // The shortcut: while the entering and the leaving value are the same float v, a step is sum <- RN(RN(sum - v) + v), a
 // function of sum alone; once a step leaves sum as it was, every step up to the next change of either cursor does, and
 // every frame up to there takes the same fm.  The walk jumps there.  A held value so costs the N steps of its entry and one.
-GVTM_HD inline void modification_gesture(const float* orig, float* out, int64_t n_frames, int64_t cs, int64_t N, int p, int op, const int32_t* steps,
+GVTM_HOST_DEVICE inline void modification_gesture(const float* orig, float* out, int64_t n_frames, int64_t cs, int64_t N, int p, int op, const int32_t* steps,
 		const float* values, int64_t n_points, int64_t stop_frame)
 {
 #if defined(__clang__)
@@ -129,15 +149,11 @@ GVTM_HD inline void modification_gesture(const float* orig, float* out, int64_t 
 				// sum <- RN(RN(sum - v) + v): once a step leaves it as it was, every step of the run does
 				for (; count > 0 && !fixed; --count) {
 					const double before = sum;
-					sum = sum - vout;
-					sum = sum + vin;
+					sum = moving_average_step(sum, vout, vin);
 					fixed = modification_bits(sum) == modification_bits(before);
 				}
 			} else {
-				for (; count > 0; --count) {
-					sum = sum - vout;
-					sum = sum + vin;
-				}
+				for (; count > 0; --count) sum = moving_average_step(sum, vout, vin);
 			}
 			if (fixed) {
 				// nothing moves before a cursor does: every frame that begins in the rest of the run takes this sum
@@ -162,7 +178,7 @@ GVTM_HD inline void modification_gesture(const float* orig, float* out, int64_t 
 }
 
 // Per-utterance checks both sides make in the same order; the pieces that look at one gesture or one point
-GVTM_HD inline bool modification_bad_gesture(int32_t parameter, int32_t operation)
+GVTM_HOST_DEVICE inline bool modification_bad_gesture(int32_t parameter, int32_t operation)
 {
 	return parameter < 0 || parameter >= GVTM_N_PARAM || (operation != GVTM_MODIFICATION_ADD && operation != GVTM_MODIFICATION_MULTIPLY);
 }

@@ -50,6 +50,10 @@
  *                               the editor's parameter-modification window: what Processor::process leaves in its modified
  *                               parameter list (gama_tts_editor/src/ParameterModificationSynthesis.cpp:117-194), then
  *                               Controller::synthesizeToFile on it (ParameterModificationWindow.cpp:200-231, 281-322)
+ *   gvtm_synthesize_targets_device / gvtm_targets_apply_host
+ *                               the editor's interactive window: targets for the 16 parameters, each smoothed by a 50 ms
+ *                               MovingAverageFilter<float> on every internal step, then execSynthesisStep()
+ *                               (gama_tts_editor/src/interactive/InteractiveAudio.cpp:164-186)
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
@@ -861,6 +865,97 @@ int gvtm_synthesize_modified_device(gvtm_plan* plan, const float* d_base_params,
 		const int64_t* d_utt_gestures, const int32_t* d_point_steps, const float* d_point_values,
 		const int32_t* d_voice_ids, size_t batch, size_t max_frames, float* d_audio, size_t audio_stride,
 		int32_t* d_frame_counts, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Synthesis from parameter targets.  The editor's interactive window drives the model without control frames: the user sets
+ * targets for the 16 parameters, and on every internal step each parameter passes through its own MovingAverageFilter<float>
+ * of 50 ms into setParameter() before execSynthesisStep() runs (gama_tts_editor/src/interactive/InteractiveAudio.cpp:
+ * 164-186).  There is no linear interpolation: the parameters move on every internal sample.  The entries below do that for a
+ * batch: an utterance is a step count and, per parameter, a handful of (step, value) points, and the filter runs inside the
+ * synthesis kernel, so nothing but the points (8 bytes each) is read per utterance.
+ *
+ * The rule, for a voice with internal rate r: N = (size_t)roundf((float)r * (float)50.0e-3) -- a float product rounded half
+ * away from zero (at 20 050 Hz the product is 1002.5 and N is 1003); gvtm_targets_filter_length gives it -- and invN =
+ * 1.0 / N in double.  An utterance is S internal steps and per parameter p a list of points (step_j, value_j): int32 steps
+ * that strictly increase, float values.
+ *   cur[p] = 0.0f for every p                      (paramValues_ starts at 0, InteractiveAudio.cpp:106-108)
+ *   for s = 0 .. S-1:
+ *     for p = 0 .. 15:
+ *       if list p's next point has step == s: cur[p] = its value
+ *       at s == 0: ring_p[0 .. N) = cur[p]; sum_p = (double)cur[p] * (double)N      (the filter's first call)
+ *       sum_p = sum_p - (double)ring_p[pos]; sum_p = sum_p + (double)cur[p]; ring_p[pos] = cur[p]; pos advances
+ *       v[s][p] = (float)(sum_p * invN);  setParameter(p, v[s][p])
+ *     execSynthesisStep()
+ *   finishSynthesis()
+ * What follows from it:
+ *   - points at or beyond step S never act;
+ *   - a parameter without a point at step 0 is held at 0 until its first point (and a list without points at 0 throughout);
+ *   - the two additions into sum are sequential double operations, each rounded, in this order, without FMA contraction on
+ *     the host and on the device; (double)cur * N is rounded before cur is taken from it.  With values spread over many
+ *     decades the result differs from the exactly rounded window mean, and it is the sequential one that is computed;
+ *   - the window itself reads its parameter ring buffer only between bursts of steps, so its sessions are the lists whose
+ *     steps fall on those boundaries; the rule lets a target act at any step;
+ *   - the window never calls finishSynthesis(); the one-shot entry does, as every gvtm_synthesize_batch_* entry does;
+ *   - the samples are, by definition, what gvtm_synthesize_batch_device returns for the same voice on a plan whose control
+ *     rate is its internal rate (control_steps == 1) fed v[s][0 .. 16) as frame s: that route runs S frames as S steps, and
+ *     frame s is used unchanged at step s (Controller.cpp:294-311).
+ *
+ * An utterance is refused on its own and synthesized as one of 0 steps (exactly as a frame count of 0 is).  Its status says
+ * why; the first that applies, every point being looked at for 3 before any for 4:
+ *   0  ok
+ *   1  a step count that is negative, above max_steps (host: beyond the kernels' 31-bit step counter); a list id outside
+ *      [0, n_lists)
+ *   2  list offsets that are negative or decrease
+ *   3  a value that is not finite
+ *   4  a negative step; steps not strictly increasing within a list
+ */
+
+/* N of the rule for a voice of the plan; -1 on a null plan or a voice outside the plan's.  Host only: works on
+ * GVTM_DEVICE_NONE plans. */
+int64_t gvtm_targets_filter_length(const gvtm_plan* plan, int voice);
+
+/* The samples finishSynthesis() leaves after n_steps internal steps of the plan's (first) voice, flush overrun included, and
+ * the row length that holds every utterance of up to max_steps steps (larger on down-sampling plans, as
+ * gvtm_output_capacity is): gvtm_output_count and gvtm_output_capacity by steps, independent of the plan's control rate.
+ * (size_t)-1 on a null plan. */
+size_t gvtm_targets_output_count(const gvtm_plan* plan, size_t n_steps);
+size_t gvtm_targets_output_capacity(const gvtm_plan* plan, size_t max_steps);
+
+/* The rule's v[s][p] on the host for one utterance under voice `voice` of the plan (its N); needs no device and works on
+ * GVTM_DEVICE_NONE plans.
+ *   list_offsets [17]                            parameter p owns the points [off[p], off[p+1])
+ *   point_steps int32, point_values float        the points of all lists back to back
+ *   frames_out [n_steps][16]                     out: v; a refused utterance leaves it untouched
+ *   status_out                                   out: the status above
+ * GVTM_ERR_INVALID_ARGUMENT for a null plan, status_out or list_offsets, null frames_out with n_steps > 0, null point tables
+ * with points, a voice outside the plan's. */
+int gvtm_targets_apply_host(const gvtm_plan* plan, int voice, const int64_t* list_offsets, const int32_t* point_steps,
+		const float* point_values, int64_t n_steps, float* frames_out, int32_t* status_out);
+
+/* The rule and the synthesis for a batch in one launch, everything resident in device memory.
+ *   d_list_offsets [n_lists + 1]                 list l owns the points [off[l], off[l+1]) of d_point_steps / d_point_values
+ *   d_list_ids [batch][16] int32, or NULL        the list of utterance b's parameter p; NULL: n_lists == 16 * batch and it is
+ *                                                list 16 b + p.  Many utterances may share a list: a study that moves one
+ *                                                articulator shares the other fifteen.
+ *   d_step_counts [batch] int32, or NULL         utterance b's steps S; NULL: all max_steps
+ *   d_audio [batch][audio_stride], d_out_counts [batch] (may be NULL), d_maxabs [batch] (may be NULL)
+ *                                                as gvtm_synthesize_batch_device's; utterance b yields
+ *                                                gvtm_targets_output_count(plan, S_b) samples
+ *   d_status [batch] int32, may be NULL          out: the statuses above
+ * Samples, counts and peaks are those of gvtm_synthesize_batch_device on gvtm_targets_apply_host's frames at one step per
+ * frame (above), in float bit for bit.  One-voice plans of the models 0 to 4, every precision.  Enqueue-only -- a small check
+ * kernel (one wavefront per utterance: statuses and step counts into the plan's scratch) and the synthesis launch on
+ * hip_stream -- with the batch entry's one exception: a float plan's noise table grows to max_steps steps
+ * (gvtm_plan_reserve(plan, frames) reserves frames * control_steps of them).  Calls on one plan must be ordered on one stream,
+ * as the events entries'.  Refused before any device work, in this order: a null plan; with batch > 0 a null offset table,
+ * point table or audio buffer, a NULL d_list_ids with n_lists != 16 * batch, a max_steps beyond the step counter, a stride
+ * below gvtm_targets_output_capacity(plan, max_steps) (GVTM_ERR_INVALID_ARGUMENT); a plan of several voices or a model 5
+ * plan (GVTM_ERR_UNSUPPORTED); a design-only plan (GVTM_ERR_NO_DEVICE), with batch == 0 too; on a plan with a device
+ * batch == 0 returns GVTM_OK. */
+int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
+		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, size_t batch,
+		size_t max_steps, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status,
+		void* hip_stream);
 
 /*
  * Streams fed event lists.  The reference produces an utterance chunk by chunk (one generateOutput() per /c chunk,
