@@ -183,7 +183,11 @@ def _prototypes():
         "gvtm_targets_output_count": (sz, [vp, sz]),
         "gvtm_targets_output_capacity": (sz, [vp, sz]),
         "gvtm_targets_apply_host": (i, [vp, i, vp, vp, vp, i64, vp, vp]),
+        "gvtm_targets_apply_host_from": (i, [vp, i, vp, vp, vp, i64, i64, vp, vp, vp]),
         "gvtm_synthesize_targets_device": (i, [vp, vp, sz, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
+        "gvtm_stream_push_targets": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "gvtm_stream_targets_capacity": (sz, [vp, sz]),
+        "gvtm_stream_targets_points": (i, [vp, vp]),
         "gvtm_stream_push_events": (i, [vp, vp, vp, vp, vp, sz, vp, vp]),
         "gvtm_stream_get_drift": (i, [vp, vp]),
         "gvtm_stream_set_drift": (i, [vp, vp]),
@@ -501,6 +505,21 @@ def targets_apply_host(plan, lists, n_steps, voice=0, frames_out=None):
     _check(plan._lib, plan._lib.gvtm_targets_apply_host(plan._h, int(voice), _ptr(offsets), _ptr(steps), _ptr(values), int(n_steps), _ptr(out),
                                                         ctypes.byref(status)))
     return out, int(status.value)
+
+
+def targets_apply_host_from(plan, lists, first_step, n_steps, sums, voice=0):
+    """gvtm_targets_apply_host_from: the steps [first_step, first_step + n_steps) of the utterance whose 16 lists (absolute
+    steps, possibly trimmed to what the rule still needs) are `lists`, resumed on `sums` (float64 [16], the sums after step
+    first_step - 1; not read at first_step 0) -> (the parameters by step float32 [n_steps][16], the sums after the last step
+    float64 [16], status).  `sums` itself is left alone."""
+    assert len(lists) == N_PARAM
+    offsets, steps, values = pack_targets(lists)
+    out = np.zeros((max(int(n_steps), 0), N_PARAM), dtype=np.float32)
+    sums = np.array(sums, dtype=np.float64).reshape(N_PARAM)
+    status = ctypes.c_int32(-1)
+    _check(plan._lib, plan._lib.gvtm_targets_apply_host_from(plan._h, int(voice), _ptr(offsets), _ptr(steps), _ptr(values), int(first_step), int(n_steps),
+                                                             _ptr(sums), _ptr(out), ctypes.byref(status)))
+    return out, sums, int(status.value)
 
 
 def generate_tracks_host(config, event_lists, max_frames, drift=None, device=0):
@@ -1093,6 +1112,39 @@ class Stream:
         self._plan._check(self._lib.gvtm_stream_push_events(self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks), _ptr(audio),
                                                             int(stride), _ptr(counts), _ptr(frames)))
         return [audio[b, : counts[b]].copy() for b in range(self.batch)], frames
+
+    def targets_capacity(self, max_new_steps):
+        """gvtm_stream_targets_capacity: the row length for a push_targets or finish that adds up to max_new_steps steps."""
+        return _count(self._lib, int(self._lib.gvtm_stream_targets_capacity(self._h, int(max_new_steps))))
+
+    def targets_points(self):
+        """gvtm_stream_targets_points -> int64 [batch]: the points the stream holds for each utterance."""
+        held = np.zeros(self.batch, dtype=np.int64)
+        self._plan._check(self._lib.gvtm_stream_targets_points(self._h, _ptr(held)))
+        return held
+
+    def push_targets(self, utterances, step_counts, max_steps=None):
+        """gvtm_stream_push_targets.  utterances[b]: utterance b's 16 lists of (steps, values), the steps counted from the
+        first step this push adds; step_counts: the steps each utterance advances by (an int: all of them by that many) ->
+        list of float32 arrays, the new samples of each utterance.  A refused push raises GvtmError, whose `statuses` are
+        the utterances' (int32 [batch])."""
+        assert len(utterances) == self.batch and all(len(u) == N_PARAM for u in utterances)
+        counts_in = None if isinstance(step_counts, int) else np.ascontiguousarray(step_counts, dtype=np.int32)
+        assert counts_in is None or counts_in.shape == (self.batch,)
+        if max_steps is None:
+            max_steps = step_counts if counts_in is None else max(int(counts_in.max()), 0)
+        offsets, steps, values = pack_targets([l for u in utterances for l in u])
+        stride = self.targets_capacity(max_steps)
+        audio = np.zeros((self.batch, stride), dtype=np.float32)
+        counts = np.zeros(self.batch, dtype=np.int64)
+        statuses = np.full(self.batch, -1, dtype=np.int32)
+        rc = self._lib.gvtm_stream_push_targets(self._h, _ptr(offsets), _ptr(steps), _ptr(values), _ptr(counts_in), int(max_steps), _ptr(audio), stride,
+                                                _ptr(counts), _ptr(statuses))
+        if rc != 0:
+            error = GvtmError(rc, self._lib.gvtm_last_error().decode() or self._lib.gvtm_status_string(rc).decode())
+            error.statuses = statuses
+            raise error
+        return [audio[b, : counts[b]].copy() for b in range(self.batch)]
 
     def get_drift(self):
         """-> float64 [batch][5]: the drift generators' states (seed, x1, x2, y1, y2), one per utterance."""

@@ -167,7 +167,7 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (r.batch == 0) return GVTM_OK;
 	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
 	if (r.voices && !r.voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
-	if (r.targets && (r.voices || r.sl || plan->designs[0].model5 || !r.frame_counts)) return fail(GVTM_ERR_UNSUPPORTED, "targets: a one-shot launch of one voice of the models 0 to 4");
+	if (r.targets && (r.voices || plan->designs[0].model5 || !r.frame_counts)) return fail(GVTM_ERR_UNSUPPORTED, "targets: a launch of one voice of the models 0 to 4");
 	if (r.max_frames > 0 && !r.params && !r.targets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	// (several voices: the row map's int32 slots also count up to n_voices partly empty workgroups)
 	if (r.batch > (r.voices ? 0x3fffffffu : 0x7fffffffu)) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");

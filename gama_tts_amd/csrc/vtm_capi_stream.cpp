@@ -1,14 +1,21 @@
 // C ABI of libgama_vtm.so, streams: the stateful form of the path (include/gama_vtm.h, "Streams"), fed frames or
-// event lists.
+// event lists or parameter targets.
 #include <cstring>
 #include <memory>
 #include <new>
 
 #include "vtm_host.hpp"
+#include "vtm_targets.hpp"
 
 using namespace gvtm::host;
 
-enum StreamFeed : int { kFeedNone = 0, kFeedFrames = 1, kFeedEvents = 2 };
+enum StreamFeed : int { kFeedNone = 0, kFeedFrames = 1, kFeedEvents = 2, kFeedTargets = 3 };
+
+// the points of one parameter of one utterance of a targets-fed run, in absolute steps
+struct TargetsLog {
+	std::vector<int32_t> steps;
+	std::vector<float> values;
+};
 
 struct gvtm_stream {
 	gvtm_plan* plan = nullptr;
@@ -26,9 +33,17 @@ struct gvtm_stream {
 	std::vector<float> staging;
 	std::vector<int32_t> counts;
 	bool finished = false;
-	// how the stream has been fed since the last reset: frames (gvtm_stream_push) or event lists (gvtm_stream_push_events);
-	// one way per run
+	// how the stream has been fed since the last reset: frames (gvtm_stream_push), event lists (gvtm_stream_push_events) or
+	// parameter targets (gvtm_stream_push_targets); one way per run
 	int feed = kFeedNone;
+	// a targets-fed run: utterance b's parameter p keeps in tg_log[16 b + p] the points the rule still needs in front of the
+	// utterance's next step (vtm_targets.hpp: targets_first_needed) -- every launch uploads them all, and they are few: those
+	// of the filter's window and of the pending steps, and one more -- and tg_pending[b] steps are pushed but not yet
+	// synthesized (fewer than the granule of 12 after a push).  The filters' sums are in the device state.
+	std::vector<TargetsLog> tg_log;
+	std::vector<uint64_t> tg_pending;
+	int64_t tg_N = 0;
+	DeviceBuffer d_tg_offsets, d_tg_steps, d_tg_values;
 	// an events-fed run keeps its unsynthesized frames on the device: utterance b's in the rows [0, held_rows[b]) of its block
 	// of held_cap rows of d_held ([batch][held_cap][16]; at least one row of a block stays spare: a push's launch reads
 	// max_frames - 1 rows at most).  The tracks kernel appends behind them, the synthesis launch reads them in place, the
@@ -93,7 +108,14 @@ uint64_t outputs_before(const gvtm::DeviceConstants& k, uint64_t steps)
 	return ((steps << 16) + k.time_inc - 1) / k.time_inc;
 }
 
-// The samples of one launch on behalf of the stream, known before it: utterance b synthesizes n_frames[b] more frames.
+// the internal steps of n of what the stream is fed: frames, or in a targets-fed run steps
+uint64_t feed_steps(const gvtm_stream* s, size_t b, size_t n)
+{
+	return s->feed == kFeedTargets ? static_cast<uint64_t>(n) : static_cast<uint64_t>(n) * s->plan->designs[voice_of(s, b)].k.control_steps;
+}
+
+// The samples of one launch on behalf of the stream, known before it: utterance b synthesizes n_frames[b] more frames (a
+// targets-fed run: steps).
 // want[b]: its exact sample count; need: the largest of them; too_long: an utterance would pass the 2^31-step limit.
 struct StreamSamples {
 	std::vector<int64_t> want;
@@ -106,7 +128,7 @@ StreamSamples stream_samples(const gvtm_stream* s, const std::vector<size_t>& n_
 	StreamSamples r{std::vector<int64_t>(s->batch, 0)};
 	for (size_t b = 0; b < s->batch; ++b) {
 		const gvtm::DeviceConstants& k = s->plan->designs[voice_of(s, b)].k;
-		const uint64_t after = s->steps_done[b] + static_cast<uint64_t>(n_frames[b]) * k.control_steps;
+		const uint64_t after = s->steps_done[b] + feed_steps(s, b, n_frames[b]);
 		if (after + 4096ull >= (1ull << 31)) r.too_long = true;
 		const uint64_t k1 = final ? gvtm::src_output_count(k.time_inc, k.pad, k.upsampling, after) : outputs_before(k, after);
 		r.want[b] = static_cast<int64_t>(k1 - outputs_before(k, s->steps_done[b]));
@@ -115,20 +137,74 @@ StreamSamples stream_samples(const gvtm_stream* s, const std::vector<size_t>& n_
 	return r;
 }
 
+// a targets-fed run synthesizes in multiples of this many steps (the granule of create_stream, in steps) and keeps the rest
+constexpr uint64_t kTargetsGranule = 12;
+constexpr int32_t kTargetsNullTables = -1;
+
+// One utterance of a gvtm_stream_push_targets call, `count` steps of at most max_steps with the 17 offsets `off`: the status
+// of gvtm_targets_apply_host in its order, where a point at or beyond `count` is a bad step too (4); kTargetsNullTables for
+// points without their tables.
+int32_t targets_push_status(const int64_t* off, const int32_t* point_steps, const float* point_values, int64_t count, int64_t max_steps)
+{
+	if (count < 0 || count > max_steps) return gvtm::kTargetsBadCount;
+	for (int p = 0; p < GVTM_N_PARAM; ++p) {
+		if (off[p] < 0 || off[p + 1] < off[p]) return gvtm::kTargetsBadOffsets;
+	}
+	if (off[GVTM_N_PARAM] > off[0] && (!point_steps || !point_values)) return kTargetsNullTables;
+	for (int64_t j = off[0]; j < off[GVTM_N_PARAM]; ++j) {
+		if (!gvtm::modification_finite(point_values[j])) return gvtm::kTargetsBadValue;
+	}
+	for (int p = 0; p < GVTM_N_PARAM; ++p) {
+		for (int64_t j = off[p]; j < off[p + 1]; ++j) {
+			if (gvtm::targets_bad_step(point_steps, off[p], j) || point_steps[j] >= count) return gvtm::kTargetsBadSteps;
+		}
+	}
+	return gvtm::kTargetsOk;
+}
+
+// forget what the rule no longer needs in front of step s0
+void targets_forget(TargetsLog& log, int64_t s0, int64_t N)
+{
+	const int64_t keep = gvtm::targets_first_needed(log.steps.data(), 0, static_cast<int64_t>(log.steps.size()), N, s0);
+	log.steps.erase(log.steps.begin(), log.steps.begin() + keep);
+	log.values.erase(log.values.begin(), log.values.begin() + keep);
+}
+
+// The log of a targets-fed run as the tables of a targets launch: list 16 b + p holds utterance b's parameter p, the points
+// back to back.  (No table is empty on the device: the launch takes no null pointer.)
+int stream_upload_targets(gvtm_stream* s)
+{
+	std::vector<int64_t> offsets(s->tg_log.size() + 1, 0);
+	for (size_t l = 0; l < s->tg_log.size(); ++l) offsets[l + 1] = offsets[l] + static_cast<int64_t>(s->tg_log[l].steps.size());
+	std::vector<int32_t> steps(static_cast<size_t>(offsets.back()));
+	std::vector<float> values(steps.size());
+	for (size_t l = 0; l < s->tg_log.size(); ++l) {
+		std::copy(s->tg_log[l].steps.begin(), s->tg_log[l].steps.end(), steps.begin() + offsets[l]);
+		std::copy(s->tg_log[l].values.begin(), s->tg_log[l].values.end(), values.begin() + offsets[l]);
+	}
+	int rc = upload(s->d_tg_offsets, offsets, "upload target list offsets");
+	if (rc == GVTM_OK) rc = upload(s->d_tg_steps, steps.data(), steps.size(), "upload target steps", 1);
+	if (rc == GVTM_OK) rc = upload(s->d_tg_values, values.data(), values.size(), "upload target values", 1);
+	return rc;
+}
+
 // One launch on behalf of the stream: utterance b synthesizes n_frames[b] frames from the front of held[b] -- or, in an
 // events-fed run, from the front of its block of d_held, which the launch reads in place (no staging, no copy of frames);
-// behind a push's launch the carry kernel then moves the rows it left to the front of the block.
+// behind a push's launch the carry kernel then moves the rows it left to the front of the block.  In a targets-fed run
+// n_frames counts steps, there are no frames, and the launch walks the stream's log of points (stream_upload_targets).
 int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool final, float* audio, size_t audio_stride, int64_t* out_counts,
 		float* maxabs, bool* launched = nullptr)
 {
 	gvtm_plan* plan = s->plan;
 	const size_t batch = s->batch;
+	const bool targets = s->feed == kFeedTargets;
+	const size_t ahead = final || targets ? 0 : 1; // a push of frames carries the look-ahead frame behind its last one
 	size_t rows_max = 0;
 	bool lockstep = true, any = final;
 	// (lockstep is judged per voice: a workgroup only ever holds one voice; first[v] is voice v's first utterance)
 	std::vector<size_t> first(static_cast<size_t>(plan->n_voices()), batch);
 	for (size_t b = 0; b < batch; ++b) {
-		const size_t rows = n_frames[b] + (final ? 0 : 1); // a push carries the look-ahead frame behind its last one
+		const size_t rows = n_frames[b] + ahead;
 		rows_max = std::max(rows_max, n_frames[b] ? rows : size_t(0));
 		size_t& f = first[static_cast<size_t>(voice_of(s, b))];
 		if (f == batch) f = b;
@@ -150,20 +226,22 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	int rc = scope.entered();
 	if (rc != GVTM_OK) return rc;
 	hipError_t e;
+	const bool staged = !on_device && !targets; // frames from host memory
 	try {
-		s->staging.assign(on_device ? 0 : batch * rows_max * GVTM_N_PARAM, 0.0f);
+		s->staging.assign(staged ? batch * rows_max * GVTM_N_PARAM : 0, 0.0f);
 		s->counts.assign(batch, 0);
 	} catch (const std::bad_alloc&) {
 		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
 	}
 	for (size_t b = 0; b < batch; ++b) {
 		if (!n_frames[b]) continue;
-		const size_t rows = n_frames[b] + (final ? 0 : 1);
-		if (!on_device) std::memcpy(s->staging.data() + b * rows_max * GVTM_N_PARAM, s->held[b].data(), sizeof(float) * rows * GVTM_N_PARAM);
+		const size_t rows = n_frames[b] + ahead;
+		if (staged) std::memcpy(s->staging.data() + b * rows_max * GVTM_N_PARAM, s->held[b].data(), sizeof(float) * rows * GVTM_N_PARAM);
 		s->counts[b] = static_cast<int32_t>(n_frames[b]);
 	}
 	const size_t abytes = sizeof(float) * batch * std::max<size_t>(audio_stride, 1);
-	if (!on_device && (rc = upload(s->d_params, s->staging, "upload params")) != GVTM_OK) return rc;
+	if (staged && (rc = upload(s->d_params, s->staging, "upload params")) != GVTM_OK) return rc;
+	if (targets && (rc = stream_upload_targets(s)) != GVTM_OK) return rc;
 	if ((rc = upload(s->d_frames, s->counts, "upload frame counts")) != GVTM_OK) return rc;
 	if ((e = s->d_audio.ensure(abytes)) != hipSuccess) return fail_hip(e, "hipMalloc audio");
 	if ((e = s->d_counts.ensure(sizeof(int64_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc counts");
@@ -171,9 +249,13 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	if ((e = hipMemsetAsync(s->d_audio.ptr, 0, abytes, nullptr)) != hipSuccess) return fail_hip(e, "hipMemsetAsync");
 	const StreamLaunch sl{static_cast<unsigned char*>(s->d_state.ptr), s->state_stride, final ? gvtm::kStreamFinish : gvtm::kStreamPush, s->xr};
 	// (one utterance per workgroup unless the utterances are in lockstep)
-	float* const d_rows_in = on_device ? s->d_held.as<float>() : s->d_params.as<float>();
-	rc = launch_synthesis(plan, LaunchRequest{d_rows_in, s->d_frames.as<int32_t>(), batch, rows_max, s->d_audio.as<float>(), audio_stride, s->d_counts.as<int64_t>(),
-			s->d_maxabs.as<float>(), nullptr, lockstep ? 0 : 1, s->voices, s->voices ? s->d_voice_ids.as<int32_t>() : nullptr, &s->d_groups, &sl});
+	float* const d_rows_in = targets ? nullptr : on_device ? s->d_held.as<float>() : s->d_params.as<float>();
+	LaunchRequest request{d_rows_in, s->d_frames.as<int32_t>(), batch, rows_max, s->d_audio.as<float>(), audio_stride, s->d_counts.as<int64_t>(),
+			s->d_maxabs.as<float>(), nullptr, lockstep ? 0 : 1, s->voices, s->voices ? s->d_voice_ids.as<int32_t>() : nullptr, &s->d_groups, &sl};
+	const TargetsLaunch tl{s->d_tg_offsets.as<int64_t>(), nullptr, s->d_tg_steps.as<int32_t>(), s->d_tg_values.as<float>(), s->tg_N,
+			1.0 / static_cast<double>(std::max<int64_t>(s->tg_N, 1))};
+	if (targets) request.targets = &tl;
+	rc = launch_synthesis(plan, request);
 	if (rc != GVTM_OK) return rc;
 	if (launched) *launched = true;
 	if (on_device && !final) {
@@ -191,8 +273,9 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	if (out_counts) std::copy(got.begin(), got.end(), out_counts);
 	if (maxabs && (rc = download(maxabs, s->d_maxabs, batch, "D2H maxabs")) != GVTM_OK) return rc;
 	for (size_t b = 0; b < batch; ++b) {
-		s->steps_done[b] += static_cast<uint64_t>(n_frames[b]) * plan->designs[voice_of(s, b)].k.control_steps;
-		if (on_device) s->held_rows[b] -= n_frames[b];
+		s->steps_done[b] += feed_steps(s, b, n_frames[b]);
+		if (targets) s->tg_pending[b] -= n_frames[b];
+		else if (on_device) s->held_rows[b] -= n_frames[b];
 		else s->held[b].erase(s->held[b].begin(), s->held[b].begin() + static_cast<std::ptrdiff_t>(n_frames[b] * GVTM_N_PARAM));
 	}
 	return GVTM_OK;
@@ -229,6 +312,9 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 		s->held.resize(batch);
 		s->held_rows.assign(batch, 0);
 		s->steps_done.assign(batch, 0);
+		s->tg_log.resize(batch * GVTM_N_PARAM);
+		s->tg_pending.assign(batch, 0);
+		s->tg_N = gvtm::targets_filter_length(internal_rate_hz(plan->designs[0]));
 		DeviceScope scope(plan->device);
 		int rc = scope.entered();
 		// (one voice: every utterance's id is 0, which only the tracks kernel of an events-fed run reads)
@@ -350,6 +436,9 @@ int gvtm_stream_reset(gvtm_stream* s)
 	for (auto& h : s->held) h.clear();
 	std::fill(s->held_rows.begin(), s->held_rows.end(), size_t(0));
 	std::fill(s->steps_done.begin(), s->steps_done.end(), uint64_t(0));
+	// (a targets-fed run's sums go with the fresh state: an utterance at step 0 begins its filters anew)
+	for (TargetsLog& l : s->tg_log) l = TargetsLog();
+	std::fill(s->tg_pending.begin(), s->tg_pending.end(), uint64_t(0));
 	s->finished = false;
 	s->feed = kFeedNone; // (the drift generators run on: the reference's Controller never reseeds its own)
 	return stream_upload_fresh_state(s);
@@ -394,6 +483,7 @@ int gvtm_stream_push(gvtm_stream* s, const float* params, const int32_t* frame_c
 	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
 	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
 	if (s->feed == kFeedEvents) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed event lists (gvtm_stream_push_events) until the next gvtm_stream_reset()");
+	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets) until the next gvtm_stream_reset()");
 	if (max_frames > 0 && !params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	if (frame_counts) {
 		for (size_t b = 0; b < s->batch; ++b) {
@@ -437,12 +527,105 @@ int gvtm_stream_finish(gvtm_stream* s, float* audio, size_t audio_stride, int64_
 	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has already been finished");
 	try {
 		std::vector<size_t> n(s->batch, 0);
-		// the last frame stands for its own successor (Controller.cpp:283)
-		for (size_t b = 0; b < s->batch; ++b) n[b] = s->feed == kFeedEvents ? s->held_rows[b] : s->held[b].size() / GVTM_N_PARAM;
+		// the last frame stands for its own successor (Controller.cpp:283); a targets-fed run: the pending steps
+		for (size_t b = 0; b < s->batch; ++b) {
+			n[b] = s->feed == kFeedTargets ? static_cast<size_t>(s->tg_pending[b]) : s->feed == kFeedEvents ? s->held_rows[b] : s->held[b].size() / GVTM_N_PARAM;
+		}
 		const int rc = stream_launch(s, n, true, audio, audio_stride, out_counts, maxabs);
 		if (rc == GVTM_OK) s->finished = true;
 		return rc;
 	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
+}
+
+size_t gvtm_stream_targets_capacity(const gvtm_stream* s, size_t max_new_steps)
+{
+	if (!s) return static_cast<size_t>(-1);
+	// the new steps and what a push can have kept (one short of the granule), flushed, with the overrun's lap
+	const gvtm::DeviceConstants& k = s->plan->designs[0].k;
+	return static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(max_new_steps) + kTargetsGranule - 1) + 1);
+}
+
+int gvtm_stream_targets_points(const gvtm_stream* s, int64_t* held_out)
+{
+	if (!s || !held_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream or held_out");
+	for (size_t b = 0; b < s->batch; ++b) {
+		held_out[b] = 0;
+		for (int p = 0; p < GVTM_N_PARAM; ++p) held_out[b] += static_cast<int64_t>(s->tg_log[b * GVTM_N_PARAM + p].steps.size());
+	}
+	return GVTM_OK;
+}
+
+int gvtm_stream_push_targets(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
+		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
+{
+	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
+	if (s->plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets: a plan of one voice only");
+	if (s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets: the models 0 to 4 only");
+	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
+	if (s->feed == kFeedFrames) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed frames (gvtm_stream_push) until the next gvtm_stream_reset()");
+	if (s->feed == kFeedEvents) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed event lists (gvtm_stream_push_events) until the next gvtm_stream_reset()");
+	if (!list_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null list_offsets");
+	if (!gvtm::targets_fits_step_counter(static_cast<int64_t>(std::min<size_t>(max_steps, INT64_MAX)))) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_steps does not fit the 31-bit step counter");
+	}
+	const size_t batch = s->batch;
+	// every utterance's status first: a refused one refuses the call, and nothing has been touched
+	size_t refused = batch;
+	for (size_t b = 0; b < batch; ++b) {
+		const int64_t count = step_counts ? static_cast<int64_t>(step_counts[b]) : static_cast<int64_t>(max_steps);
+		const int32_t status = targets_push_status(list_offsets + b * GVTM_N_PARAM, point_steps, point_values, count, static_cast<int64_t>(max_steps));
+		if (status == kTargetsNullTables) return fail(GVTM_ERR_INVALID_ARGUMENT, "null point_steps or point_values with points");
+		if (status_out) status_out[b] = status;
+		if (status != gvtm::kTargetsOk && refused == batch) refused = b;
+	}
+	if (refused < batch) return fail(GVTM_ERR_INVALID_ARGUMENT, "utterance " + std::to_string(refused) + " is refused (status_out says why); nothing was pushed");
+	for (size_t b = 0; b < batch; ++b) {
+		const uint64_t count = step_counts ? static_cast<uint64_t>(step_counts[b]) : static_cast<uint64_t>(max_steps);
+		if (s->steps_done[b] + s->tg_pending[b] + count + 4096ull >= (1ull << 31)) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
+	}
+	// a call that fails before its launch leaves the stream as it found it: the points and steps it appended are taken back
+	const int feed_before = s->feed;
+	const std::vector<uint64_t> pending_before = s->tg_pending;
+	std::vector<size_t> held_before(s->tg_log.size(), 0);
+	for (size_t l = 0; l < s->tg_log.size(); ++l) held_before[l] = s->tg_log[l].steps.size();
+	auto roll_back = [&]() {
+		for (size_t l = 0; l < s->tg_log.size(); ++l) {
+			s->tg_log[l].steps.resize(held_before[l]);
+			s->tg_log[l].values.resize(held_before[l]);
+		}
+		s->tg_pending = pending_before;
+		s->feed = feed_before;
+	};
+	try {
+		std::vector<size_t> n(batch, 0);
+		for (size_t b = 0; b < batch; ++b) {
+			// the push's step 0 is the first step the utterance has not been given yet
+			const int64_t base = static_cast<int64_t>(s->steps_done[b] + s->tg_pending[b]);
+			for (int p = 0; p < GVTM_N_PARAM; ++p) {
+				TargetsLog& log = s->tg_log[b * GVTM_N_PARAM + p];
+				for (int64_t j = list_offsets[b * GVTM_N_PARAM + p]; j < list_offsets[b * GVTM_N_PARAM + p + 1]; ++j) {
+					log.steps.push_back(static_cast<int32_t>(base + point_steps[j]));
+					log.values.push_back(point_values[j]);
+				}
+			}
+			s->tg_pending[b] += step_counts ? static_cast<uint64_t>(step_counts[b]) : static_cast<uint64_t>(max_steps);
+			// the serial wavefronts' states are exact at multiples of 12 steps (create_stream); no step waits for a successor
+			n[b] = static_cast<size_t>(s->tg_pending[b] / kTargetsGranule * kTargetsGranule);
+		}
+		s->feed = kFeedTargets;
+		bool launched = false;
+		const int rc = stream_launch(s, n, false, audio, audio_stride, out_counts, nullptr, &launched);
+		if (rc != GVTM_OK && !launched) roll_back(); // (after the launch the device state has moved on: gvtm_stream_reset is the way out)
+		if (rc == GVTM_OK) {
+			for (size_t b = 0; b < batch; ++b) {
+				for (int p = 0; p < GVTM_N_PARAM; ++p) targets_forget(s->tg_log[b * GVTM_N_PARAM + p], static_cast<int64_t>(s->steps_done[b]), s->tg_N);
+			}
+		}
+		return rc;
+	} catch (const std::bad_alloc&) {
+		roll_back();
 		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
 	}
 }
@@ -453,6 +636,7 @@ int gvtm_stream_push_events(gvtm_stream* s, const gvtm_event* events, const int6
 	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
 	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
 	if (s->feed == kFeedFrames) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed frames (gvtm_stream_push) until the next gvtm_stream_reset()");
+	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets) until the next gvtm_stream_reset()");
 	const gvtm_plan* plan = s->plan;
 	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "gvtm_stream_push_events: the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
 	const size_t batch = s->batch;

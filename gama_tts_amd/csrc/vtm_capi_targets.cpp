@@ -7,6 +7,28 @@
 
 using namespace gvtm::host;
 
+namespace {
+
+// the two host entries behind their null checks: the rule from first_step on (0: from the start, sums not read)
+int apply_host(const gvtm_plan* plan, int voice, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values, int64_t first_step,
+		int64_t n_steps, double* sums, float* frames_out, int32_t* status_out)
+{
+	if (!frames_out && n_steps > 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null frames_out with n_steps > 0");
+	if (voice < 0 || voice >= plan->n_voices()) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice index out of range");
+	bool points = false, ordered = true;
+	for (int p = 0; p < GVTM_N_PARAM; ++p) {
+		ordered = ordered && list_offsets[p] >= 0 && list_offsets[p + 1] >= list_offsets[p];
+		points = points || list_offsets[p + 1] > list_offsets[p];
+	}
+	// (offsets out of order are the utterance's status 2, whatever the tables)
+	if (ordered && points && (!point_steps || !point_values)) return fail(GVTM_ERR_INVALID_ARGUMENT, "null point_steps or point_values with points");
+	*status_out = gvtm::targets_apply_from(gvtm::targets_filter_length(internal_rate_hz(plan->designs[voice])), list_offsets, point_steps, point_values,
+			first_step, n_steps, sums, frames_out);
+	return GVTM_OK;
+}
+
+} // namespace
+
 extern "C" {
 
 int64_t gvtm_targets_filter_length(const gvtm_plan* plan, int voice)
@@ -27,22 +49,19 @@ size_t gvtm_targets_output_capacity(const gvtm_plan* plan, size_t max_steps)
 	return steps_output_capacity(plan->designs[0], max_steps);
 }
 
+int gvtm_targets_apply_host_from(const gvtm_plan* plan, int voice, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
+		int64_t first_step, int64_t n_steps, double* sums_inout, float* frames_out, int32_t* status_out)
+{
+	if (!plan || !status_out || !list_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan, status_out or list_offsets");
+	if (!sums_inout) return fail(GVTM_ERR_INVALID_ARGUMENT, "null sums_inout");
+	return apply_host(plan, voice, list_offsets, point_steps, point_values, first_step, n_steps, sums_inout, frames_out, status_out);
+}
+
 int gvtm_targets_apply_host(const gvtm_plan* plan, int voice, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
 		int64_t n_steps, float* frames_out, int32_t* status_out)
 {
 	if (!plan || !status_out || !list_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan, status_out or list_offsets");
-	if (!frames_out && n_steps > 0) return fail(GVTM_ERR_INVALID_ARGUMENT, "null frames_out with n_steps > 0");
-	if (voice < 0 || voice >= plan->n_voices()) return fail(GVTM_ERR_INVALID_ARGUMENT, "voice index out of range");
-	bool points = false, ordered = true;
-	for (int p = 0; p < GVTM_N_PARAM; ++p) {
-		ordered = ordered && list_offsets[p] >= 0 && list_offsets[p + 1] >= list_offsets[p];
-		points = points || list_offsets[p + 1] > list_offsets[p];
-	}
-	// (offsets out of order are the utterance's status 2, whatever the tables)
-	if (ordered && points && (!point_steps || !point_values)) return fail(GVTM_ERR_INVALID_ARGUMENT, "null point_steps or point_values with points");
-	*status_out = gvtm::targets_apply(gvtm::targets_filter_length(internal_rate_hz(plan->designs[voice])), list_offsets, point_steps, point_values, n_steps,
-			frames_out);
-	return GVTM_OK;
+	return apply_host(plan, voice, list_offsets, point_steps, point_values, 0, n_steps, nullptr, frames_out, status_out);
 }
 
 int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,

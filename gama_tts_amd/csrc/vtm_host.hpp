@@ -381,8 +381,9 @@ struct StreamLaunch {
 	int xr;       // the stream's ring length (one for all shapes; several voices: the longest of the plan's voices)
 };
 
-// what a launch from parameter targets (gvtm_synthesize_targets_device) has in the place of frames: the request's
-// frame_counts are then its step counts, as the check kernel left them, and its max_frames the most steps of an utterance
+// what a launch from parameter targets (gvtm_synthesize_targets_device; a targets-fed stream's) has in the place of frames:
+// the request's frame_counts are then its step counts, as the check kernel (the stream: the host) left them, and its
+// max_frames the most steps of an utterance; a stream's points are its log, in absolute steps
 struct TargetsLaunch {
 	const int64_t* list_offsets;
 	const int32_t* list_ids;   // or null

@@ -383,7 +383,8 @@ constexpr int kVoicesFlag = 2;
 // Synthesis from parameter targets (gvtm_synthesize_targets_device): a third bit of the same argument, kTargetsFlag (default
 // off, one voice only).  With it the interpolation wavefront has a second driver: lane L of row u walks the points of list
 // a.tg_ids[16 utt + L] through the moving average of vtm_targets.hpp and writes the same float per step into the `prm`
-// record; an utterance is a.frame_counts[utt] STEPS long, and there are no frames.  Nothing else differs between the two
+// record; an utterance is a.frame_counts[utt] STEPS long, and there are no frames.  On behalf of a stream
+// (gvtm_stream_push_targets) the steps are absolute and the filters' sums travel in the stream state.  Nothing else differs between the two
 // drivers, and as with kVoicesFlag every difference is a conditional on the constant TARGETS whose targets arm the
 // compiler never emits for the other kernels.
 constexpr int kTargetsFlag = 4;
@@ -595,7 +596,8 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 		unsigned peak0 = 0u;
 		if (ug < a.batch) {
 			// a stream's push carries one more row than it synthesizes: the next frame, which the last one interpolates towards
-			const size_t rows_avail = a.max_frames - (kPush ? 1 : 0);
+			// (not from targets: a step does not interpolate towards a successor)
+			const size_t rows_avail = a.max_frames - (kPush && !TARGETS ? 1 : 0);
 			const int f = a.frame_counts ? a.frame_counts[ug] : static_cast<int>(rows_avail);
 			// device-resident counts cannot be validated by the host: clamp to the allocated frames
 			e.frames = f > 0 ? (static_cast<size_t>(f) < rows_avail ? f : static_cast<int>(rows_avail)) : 0;
@@ -739,12 +741,22 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	// I, from targets: lane L of row u walks the points of utterance u's list for parameter L (vtm_targets.hpp): the filter's
 	// sum, the entering and the leaving value, the two cursors and the steps at which they move next.  (A refused utterance
 	// has 0 steps: its list ids and offsets are never read.)
+	// A stream's launch walks absolute steps from the utterance's step_base on: behind step 0 the walk resumes on the sum the
+	// previous launch left in the stream state (targets_resume; the points are the stream's log, in absolute steps), and the
+	// epilogue stores the sum back.  An utterance the launch does not advance keeps its sums.
 	[[maybe_unused]] TargetsWalk tg{};
+	[[maybe_unused]] int64_t tg_base = 0;
 	if constexpr (TARGETS) {
 		if (role == 4 && rowp < U && sm.ext[rowp].frames > 0) {
 			const size_t slot = (group * U + rowp) * GVTM_N_PARAM + Lp;
 			const int64_t list = a.tg_ids ? static_cast<int64_t>(a.tg_ids[slot]) : static_cast<int64_t>(slot);
-			targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N);
+			if (a.stream) tg_base = static_cast<int64_t>(sm.ext[rowp].step_base);
+			if (tg_base > 0) {
+				const double* sums = reinterpret_cast<const double*>(a.stream + (group * U + rowp) * a.stream_stride + SL::sums(kTubeLanes, kTubeWords, XR));
+				targets_resume(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N, tg_base, sums[Lp]);
+			} else {
+				targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N);
+			}
 		}
 	}
 
@@ -1420,7 +1432,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			// steps later); every other block is four times {two double additions, a multiplication, a conversion, a store}.
 			// A partial last block runs on: no cursor passes the end of its list, and the extra rows are never read.
 			float* out = sm.prm + at_prm(c & 1, u) + Lp;
-			const int64_t first = static_cast<int64_t>(c) * C;
+			const int64_t first = tg_base + static_cast<int64_t>(c) * C;
 			for (int s0 = 0; s0 < valid; s0 += 4) {
 				if (__builtin_expect(__any(targets_moves(tg, first + s0, 4)), 0)) {
 #pragma unroll
@@ -2304,6 +2316,13 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 
 	// ---- a stream's states for the next launch
 	if (a.stream) {
+		if constexpr (TARGETS) {
+			// the moving averages' sums, push and finish alike (a push synthesizes whole blocks of four steps: no lane ran on)
+			if (role == 4 && rowp < U && sm.ext[rowp].frames > 0) {
+				double* sums = reinterpret_cast<double*>(a.stream + (group * U + rowp) * a.stream_stride + SL::sums(kTubeLanes, kTubeWords, XR));
+				sums[Lp] = tg.sum;
+			}
+		}
 		if (serial_live && (kTubePerWave && role == 0 ? true : (U >= 4 || row < U))) {
 			unsigned char* sb = a.stream + GVTM_ROW_UTT(serial_utt, (group * U + serial_utt)) * a.stream_stride;
 			CT* sc = reinterpret_cast<CT*>(sb + SL::scalars());

@@ -14,6 +14,7 @@ namespace gvtm {
 // ---- streams (gvtm_stream_*): what an utterance carries from one launch to the next, in device memory ----
 //
 //   StreamHeader | scalars CT[kStreamScalars] | tube CT[lanes][2 * SectionDelay + 1] | decimator pre-roll CT[48] | ring ST[xr]
+//   | targets sums double[16]
 //
 // i.e. exactly the reference model's members that survive a step (vtm/VocalTractModel0.h:221-252): the section delay
 // lines, the filter memories, the oscillator phase, the noise seed, the decimator's and the converter's buffers with
@@ -40,7 +41,10 @@ struct StreamLayout {
 	static constexpr size_t tube() { return scalars() + sizeof(CT) * kStreamScalars; }
 	static constexpr size_t wpre(int lanes, int words) { return tube() + sizeof(CT) * static_cast<size_t>(lanes) * words; }
 	static constexpr size_t ring(int lanes, int words) { return wpre(lanes, words) + sizeof(CT) * kStreamPreRoll; }
-	static constexpr size_t bytes(int lanes, int words, int xr) { return (ring(lanes, words) + sizeof(ST) * static_cast<size_t>(xr) + 15) & ~size_t(15); }
+	// behind the ring (no other offset moves): the 16 sums of a targets-fed run's moving averages (vtm_targets.hpp), doubles
+	// whatever CT is -- the one state of the interpolation wavefront, which a run fed frames does not have
+	static constexpr size_t sums(int lanes, int words, int xr) { return (ring(lanes, words) + sizeof(ST) * static_cast<size_t>(xr) + 7) & ~size_t(7); }
+	static constexpr size_t bytes(int lanes, int words, int xr) { return (sums(lanes, words, xr) + sizeof(double) * GVTM_N_PARAM + 15) & ~size_t(15); }
 };
 
 // Reference model 5 (VocalTractModel5, vtm/VocalTractModel5.h:523-579): what its members keep between steps -- the scans'

@@ -94,7 +94,8 @@ __global__ __launch_bounds__(64) void vtm_targets_check_kernel(const TargetsChec
 
 hipError_t launch_synth_targets(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream)
 {
-	if (!args.tg_offsets || !args.tg_steps || !args.tg_values || !args.frame_counts || args.row_map || args.stream || args.tg_N < 1) return hipErrorInvalidValue;
+	// (a stream's launch, args.stream, takes the shapes launch_v2 gives a stream of frames: the ring is the stream's, args.xr)
+	if (!args.tg_offsets || !args.tg_steps || !args.tg_values || !args.frame_counts || args.row_map || args.tg_N < 1) return hipErrorInvalidValue;
 	return with_shape(precision, rows, args.k.section_delay, args.k.layout, hipErrorInvalidValue,
 			[&](auto s) { return launch_v2_targets<decltype(s)>(args, batch, stream); });
 }

@@ -12,7 +12,8 @@
 // interpolation lanes both run.  No ring: the value that leaves the window at step s is the value fed at step s - N, for
 // s < N the value fed at step 0, so a second cursor through the same points, N steps behind the first, serves (the form
 // vtm_modification.hpp establishes).  Built without FMA contraction (the pragma): (double)cur * N is rounded before cur is
-// taken from it.
+// taken from it.  A walk may also begin in front of any later step (targets_resume: a stream's launches,
+// gvtm_targets_apply_host_from), on the sum carried from the step before.
 #pragma once
 
 #include "vtm_modification.hpp"
@@ -65,6 +66,49 @@ GVTM_HOST_DEVICE inline void targets_begin(TargetsWalk& w, const int32_t* steps,
 	w.next_leave = w.leave < end ? static_cast<int64_t>(steps[w.leave]) + N : kTargetsNever;
 }
 
+// the first point of [first, end) whose step is at or after `step` (end: none is)
+GVTM_HOST_DEVICE inline int64_t targets_first_from(const int32_t* steps, int64_t first, int64_t end, int64_t step)
+{
+	while (first < end) {
+		const int64_t mid = first + (end - first) / 2;
+		if (static_cast<int64_t>(steps[mid]) < step) first = mid + 1;
+		else end = mid;
+	}
+	return first;
+}
+
+// The state in front of step s0 > 0: the one targets_begin and s0 steps of targets_move / targets_step reach, but for the
+// sum, which the caller carried (the double accumulation of floats decades apart is not exact, so it cannot be had again
+// from the points).  The value that enters is the last point's before s0; the one that leaves the last point's at or before
+// the window's far edge s0 - 1 - N, and with no such point the value fed at step 0.  So the list may have forgotten every
+// point whose successor is at or before that edge.
+GVTM_HOST_DEVICE inline void targets_resume(TargetsWalk& w, const int32_t* steps, const float* values, int64_t first, int64_t end, int64_t N, int64_t s0,
+		double sum)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+	w.end = end;
+	w.sum = sum;
+	w.enter = targets_first_from(steps, first, end, s0);
+	w.entering = w.enter > first ? values[w.enter - 1] : 0.0f;
+	w.leave = targets_first_from(steps, first, end, s0 - N);
+	if (w.leave > first) w.leaving = values[w.leave - 1];
+	else w.leaving = first < end && steps[first] == 0 ? values[first] : 0.0f;
+	// (the point at step 0 left with the first call's fill: targets_begin never gives it to the leave cursor)
+	if (w.leave < end && steps[w.leave] == 0) ++w.leave;
+	w.next_enter = w.enter < end ? static_cast<int64_t>(steps[w.enter]) : kTargetsNever;
+	w.next_leave = w.leave < end ? static_cast<int64_t>(steps[w.leave]) + N : kTargetsNever;
+}
+
+// what a list may forget in front of step s0: the first point targets_resume(.., s0, ..) and the steps behind it still
+// need, which is the last one at or before the window's far edge s0 - 1 - N (the list's first where there is none)
+GVTM_HOST_DEVICE inline int64_t targets_first_needed(const int32_t* steps, int64_t first, int64_t end, int64_t N, int64_t s0)
+{
+	const int64_t behind = targets_first_from(steps, first, end, s0 - N);
+	return behind > first ? behind - 1 : first;
+}
+
 // does a cursor move at one of the steps [s, s + n)?  (No cursor is ever behind the step the walk is at.)
 GVTM_HOST_DEVICE inline bool targets_moves(const TargetsWalk& w, int64_t s, int64_t n)
 {
@@ -108,11 +152,12 @@ GVTM_HOST_DEVICE inline bool targets_fits_step_counter(int64_t steps)
 
 // The host's restatement (vtm_capi_targets.cpp): the status of one utterance of n_steps steps whose parameter p owns the
 // points [list_offsets[p], list_offsets[p + 1]), and with status 0 frames_out[s][p] = the parameter at step s.  A refused
-// utterance leaves frames_out alone.
-inline int32_t targets_apply(int64_t N, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values, int64_t n_steps,
-		float* frames_out)
+// utterance leaves frames_out alone.  From first_step > 0 the walk resumes on the 16 sums of `sums`, and frames_out[0] is step
+// first_step's; sums (null: not wanted, first_step 0 only) leaves as the sums after the last step.
+inline int32_t targets_apply_from(int64_t N, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values, int64_t first_step,
+		int64_t n_steps, double* sums, float* frames_out)
 {
-	if (!targets_fits_step_counter(n_steps)) return kTargetsBadCount;
+	if (!targets_fits_step_counter(first_step) || !targets_fits_step_counter(n_steps) || !targets_fits_step_counter(first_step + n_steps)) return kTargetsBadCount;
 	for (int p = 0; p < GVTM_N_PARAM; ++p) {
 		if (list_offsets[p] < 0 || list_offsets[p + 1] < list_offsets[p]) return kTargetsBadOffsets;
 	}
@@ -129,13 +174,21 @@ inline int32_t targets_apply(int64_t N, const int64_t* list_offsets, const int32
 	const double invN = 1.0 / static_cast<double>(N);
 	for (int p = 0; p < GVTM_N_PARAM; ++p) {
 		TargetsWalk w;
-		targets_begin(w, point_steps, point_values, list_offsets[p], list_offsets[p + 1], N);
-		for (int64_t s = 0; s < n_steps; ++s) {
+		if (first_step > 0) targets_resume(w, point_steps, point_values, list_offsets[p], list_offsets[p + 1], N, first_step, sums[p]);
+		else targets_begin(w, point_steps, point_values, list_offsets[p], list_offsets[p + 1], N);
+		for (int64_t s = first_step; s < first_step + n_steps; ++s) {
 			if (targets_moves(w, s, 1)) targets_move(w, s, point_steps, point_values, N);
-			frames_out[s * GVTM_N_PARAM + p] = targets_step(w, invN);
+			frames_out[(s - first_step) * GVTM_N_PARAM + p] = targets_step(w, invN);
 		}
+		if (sums) sums[p] = w.sum;
 	}
 	return kTargetsOk;
+}
+
+inline int32_t targets_apply(int64_t N, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values, int64_t n_steps,
+		float* frames_out)
+{
+	return targets_apply_from(N, list_offsets, point_steps, point_values, 0, n_steps, nullptr, frames_out);
 }
 
 #if defined(__HIP__)

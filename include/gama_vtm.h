@@ -53,7 +53,8 @@
  *   gvtm_synthesize_targets_device / gvtm_targets_apply_host
  *                               the editor's interactive window: targets for the 16 parameters, each smoothed by a 50 ms
  *                               MovingAverageFilter<float> on every internal step, then execSynthesisStep()
- *                               (gama_tts_editor/src/interactive/InteractiveAudio.cpp:164-186)
+ *                               (gama_tts_editor/src/interactive/InteractiveAudio.cpp:164-186);
+ *                               gvtm_stream_push_targets: the same as a session, targets arriving push by push
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
@@ -467,7 +468,8 @@ void gvtm_host_free(void* ptr);
  *
  * A stream also takes its utterances as event lists, chunk by chunk, and generates their frames itself:
  * gvtm_stream_push_events, with gvtm_stream_get_drift / gvtm_stream_set_drift, declared behind the track-generation entries
- * below ("Streams fed event lists").
+ * below ("Streams fed event lists").  And as parameter targets, the interactive window's session: gvtm_stream_push_targets
+ * ("Streams fed parameter targets").
  */
 typedef struct gvtm_stream gvtm_stream;
 
@@ -932,6 +934,26 @@ size_t gvtm_targets_output_capacity(const gvtm_plan* plan, size_t max_steps);
 int gvtm_targets_apply_host(const gvtm_plan* plan, int voice, const int64_t* list_offsets, const int32_t* point_steps,
 		const float* point_values, int64_t n_steps, float* frames_out, int32_t* status_out);
 
+/* The rule from any step: v[first_step .. first_step + n_steps) of the same utterance, given the 16 sums as they stood after
+ * step first_step - 1.  The points keep their absolute steps.  In front of a step s0 > 0 parameter p stands as follows:
+ *   cur[p]       the value of its last point with step <= s0 - 1, or 0.0f without one
+ *   the value that leaves the window at step s (s >= s0): the one fed at step s - N, which is the value of the last point
+ *                with step <= s - N; for s < N, and where no point is that early, the value fed at step 0 (the point at
+ *                step 0, or 0.0f)
+ *   sum_p        carried: the double additions of floats many decades apart are not exact, so the sum cannot be formed
+ *                again from the points
+ * So a list may forget: in front of step s0 a point is no longer needed once its successor has step <= s0 - 1 - N; what is
+ * kept is the last point at or before the window's far edge s0 - 1 - N and every later one.  A list trimmed that way gives
+ * the same bytes.
+ *   first_step == 0          gvtm_targets_apply_host: the sums are not read
+ *   sums_inout [16] double   in (first_step > 0): the sums after step first_step - 1; out: the sums after the last step
+ *   frames_out [n_steps][16] out: frames_out[0] is step first_step's
+ * The same checks, the same statuses; a negative first_step is status 1, and so is a first_step + n_steps beyond the kernels'
+ * step counter.  GVTM_ERR_INVALID_ARGUMENT as gvtm_targets_apply_host, and for a null sums_inout. */
+int gvtm_targets_apply_host_from(const gvtm_plan* plan, int voice, const int64_t* list_offsets, const int32_t* point_steps,
+		const float* point_values, int64_t first_step, int64_t n_steps, double* sums_inout, float* frames_out,
+		int32_t* status_out);
+
 /* The rule and the synthesis for a batch in one launch, everything resident in device memory.
  *   d_list_offsets [n_lists + 1]                 list l owns the points [off[l], off[l+1]) of d_point_steps / d_point_values
  *   d_list_ids [batch][16] int32, or NULL        the list of utterance b's parameter p; NULL: n_lists == 16 * batch and it is
@@ -958,6 +980,50 @@ int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offset
 		void* hip_stream);
 
 /*
+ * Streams fed parameter targets: the interactive window as a session.  Targets arrive while the audio is playing, so a
+ * stream of gvtm_stream_create takes them push by push; the filters run in the synthesis kernel and their 16 sums travel in
+ * the utterance's device state.  All pointers are HOST memory, as gvtm_stream_push's.
+ *   list_offsets [16 * batch + 1]   utterance b's parameter p owns the points [off[16b+p], off[16b+p+1]) of point_steps /
+ *                                   point_values.  Their steps count from the first step THIS push adds for the utterance:
+ *                                   a point at step 0 takes effect on the push's first step
+ *   step_counts [batch] or NULL     the steps utterance b advances by; NULL: all max_steps.  0 is allowed
+ *   audio, audio_stride, out_counts as gvtm_stream_push; audio_stride comes from gvtm_stream_targets_capacity
+ *   status_out [batch] or NULL      out: the statuses of gvtm_targets_apply_host
+ * A push synthesizes the steps that fit the serial wavefronts' granule of 12 steps and keeps the rest (at most 11) pending;
+ * no look-ahead step is kept, since a step does not interpolate towards a successor.  gvtm_stream_finish synthesizes the
+ * pending steps and flushes.  Contract: an utterance's steps pushed in any grouping over any number of calls and then
+ * finished give, in every precision bit for bit, the samples, sample count and maxabs of one gvtm_synthesize_targets_device
+ * call on the whole utterance's lists.
+ *
+ * The stream keeps, per utterance and parameter, the points the rule from any step (gvtm_targets_apply_host_from) still
+ * needs, on the host and in absolute steps: a push appends its points, a launch uploads what is held (8 bytes a point), and
+ * what the rule allows is forgotten.  gvtm_stream_targets_points reports the points held per utterance: never more than the
+ * points of the last N + 12 steps plus 16, however long the session.
+ *
+ * gvtm_stream_targets_capacity is the row length for any push or finish that adds up to max_new_steps steps: the new steps,
+ * 11 pending ones, the flush with its overrun lap, and one more sample.  (size_t)-1 on a null stream.
+ *
+ * Checked on the host before anything is launched; the first that applies: a null stream (GVTM_ERR_INVALID_ARGUMENT); a
+ * stream of a plan of several voices or of a model 5 plan (GVTM_ERR_UNSUPPORTED: the one-shot entry takes neither); then,
+ * all GVTM_ERR_INVALID_ARGUMENT, a finished stream; a stream fed frames or event lists since its last reset; a null
+ * list_offsets; a max_steps beyond the step counter; points without their tables; an utterance that is refused -- status 1
+ * for a count outside [0, max_steps], 2, 3 and 4 as above, and 4 also for a point whose step is at or beyond the
+ * utterance's count in this push -- in which case status_out says which; more than 2^31 internal steps since the reset; an
+ * audio_stride smaller than the call produces or a null audio with samples due.  A refused call leaves the stream exactly
+ * as it found it: no utterance has advanced, and the corrected call synthesizes nothing twice.
+ *
+ * One feed per run, as with frames and event lists: gvtm_stream_push and gvtm_stream_push_events refuse a targets-fed stream
+ * and gvtm_stream_push_targets a frames-fed or events-fed one until the next gvtm_stream_reset, which also clears the held
+ * points, the pending steps and the sums.
+ */
+int gvtm_stream_push_targets(gvtm_stream* stream, const int64_t* list_offsets, const int32_t* point_steps,
+		const float* point_values, const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride,
+		int64_t* out_counts, int32_t* status_out);
+size_t gvtm_stream_targets_capacity(const gvtm_stream* stream, size_t max_new_steps);
+/* held_out [batch] (host): the points the stream holds for each utterance */
+int gvtm_stream_targets_points(const gvtm_stream* stream, int64_t* held_out);
+
+/*
  * Streams fed event lists.  The reference produces an utterance chunk by chunk (one generateOutput() per /c chunk,
  * Controller.cpp:141-154); a stream takes the next chunk or chunks of each of its utterances as they are parsed, generates
  * their frames on the device straight behind the frames it still holds, synthesizes what can be synthesized and returns
@@ -982,8 +1048,9 @@ int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offset
  * precision, the samples, sample count, maxabs, total frame count and final drift state of one
  * gvtm_synthesize_events_chunks_device call on the whole utterance with the same voice and the same initial drift state.
  *
- * One feeding mode per run: between two resets a stream is fed frames (gvtm_stream_push) or event lists, never both; once
- * one entry has been used the other returns GVTM_ERR_INVALID_ARGUMENT until the next reset, and so does
+ * One feeding mode per run: between two resets a stream is fed frames (gvtm_stream_push), event lists or parameter targets
+ * (gvtm_stream_push_targets, above), never two of them; once one entry has been used the others return
+ * GVTM_ERR_INVALID_ARGUMENT until the next reset, and so does
  * gvtm_stream_set_drift between a gvtm_stream_push_events and the next reset.
  *
  * The drift generators: gvtm_stream_create* starts every one fresh ({0.7892347, 0, 0, 0, 0}).  gvtm_stream_reset and
@@ -991,7 +1058,7 @@ int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offset
  * never reseeds its generator); gvtm_stream_set_drift(stream, NULL) is what reseeds them.
  *
  * Refused with GVTM_ERR_INVALID_ARGUMENT, in this order and before any device work: a null stream; a finished stream; a
- * stream fed frames since its last reset; a plan without track configurations; null events or chunk_offsets while chunks
+ * stream fed frames or targets since its last reset; a plan without track configurations; null events or chunk_offsets while chunks
  * are present; offsets that decrease or are negative; more frames than one push can hold; an audio_stride smaller than the
  * call produces, or a null audio with samples due (the host counts every frame and sample in advance); more than 2^31
  * internal steps since the reset.  A call refused here leaves the stream exactly as it found it: held frames, drift states
