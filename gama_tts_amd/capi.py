@@ -202,6 +202,7 @@ def _prototypes():
         "gvtm_debug_launch_shape": (i, [vp, sz, i, vp]),
         "gvtm_debug_stream_launch_shape": (i, [vp, sz, vp]),
         "gvtm_debug_chunk_length": (i, [vp, sz]),
+        "gvtm_debug_plan_filter_split": (i, [vp, i]),
         "gvtm_debug_fir_literals": (i, [vp]),
         "gvtm_debug_plan_fir_literals": (i, [vp]),
         "gvtm_debug_force_generic_fir": (i, [vp]),
@@ -652,6 +653,11 @@ class Plan:
     def force_dynamic_wavetable(self):
         """Diagnostics plans: later launches ask per wavetable entry whether it follows the amplitude."""
         self._check(self._lib.gvtm_debug_force_dynamic_wavetable(self._h))
+
+    def filter_split(self, rows):
+        """Diagnostics plans: which serial filter stages the kernel shape of `rows` utterances per workgroup runs with their
+        feed-forward half 64 steps at a time (bit 0: the post-tube filters); 0: none."""
+        return self._hook_count(self._lib.gvtm_debug_plan_filter_split(self._h, int(rows)))
 
     def output_count(self, frames):
         return int(self._lib.gvtm_output_count(self._h, int(frames)))

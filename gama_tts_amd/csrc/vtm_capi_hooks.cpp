@@ -71,6 +71,16 @@ int gvtm_debug_chunk_length(const gvtm_plan* plan, size_t batch)
 	return gvtm::synth_chunk_length(plan->designs[0].k, plan->precision, shape.rows);
 }
 
+/* Which serial filter stages the single-voice kernel shape of `rows` utterances per workgroup of this plan runs with
+   their feed-forward half 64 steps at a time (v2::filter_split_f2): bit 0 the post-tube filters; 0: none (or model 5, or
+   no such shape); negative: a null plan.  The targets variant of a shape takes what the shape takes.  Needs no device. */
+int gvtm_debug_plan_filter_split(const gvtm_plan* plan, int rows)
+{
+	if (!plan) return -fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (plan->designs[0].model5) return 0;
+	return gvtm::synth_filter_split(plan->designs[0].k, plan->precision, rows);
+}
+
 /* The float decimator's coefficients as the float kernels hold them (gvtm::kGlottalFirF32): out[47].  Needs no device. */
 int gvtm_debug_fir_literals(float* out)
 {

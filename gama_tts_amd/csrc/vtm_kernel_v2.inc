@@ -132,6 +132,8 @@ struct Extent {
 //   GVTM_TUNE_TRACE   first of two ticks whose timeline workgroup 0 records (tests/tools/tick_trace.py)
 //   GVTM_TUNE_PLAN_TABLES  which single-voice float shapes read the plan's resampler phase table (bit 0) and its
 //                     static-wavetable flag (bit 1), in place of the selectors' own choice (src_phase_table() below)
+//   GVTM_TUNE_FILTER_SPLIT  which float shapes run the feed-forward half of the post-tube filters 64 steps at a time
+//                     (bit 0), in place of the selector's own choice (filter_split_f2() below)
 // The design alternatives that were measured and lost (packed resampler rows, coefficient table in device memory, tickets
 // requested ahead / by position, a second pass list for the tube's idle time, role placement by SIMD, ...) are recorded in
 // DESIGN.md's A/B table, not kept here.
@@ -146,6 +148,9 @@ struct Extent {
 #endif
 #ifndef GVTM_TUNE_PLAN_TABLES
 #define GVTM_TUNE_PLAN_TABLES (-1)
+#endif
+#ifndef GVTM_TUNE_FILTER_SPLIT
+#define GVTM_TUNE_FILTER_SPLIT (-1)
 #endif
 // serial wavefronts that finish their stage early join the helpers for the rest of the tick: bit 1 scan, bit 3 post-tube
 // filters, bit 4 interpolation
@@ -440,6 +445,24 @@ template <typename CT, int D, int U, int LAYOUT, bool VOICES> constexpr bool sta
 	if (GVTM_TUNE_PLAN_TABLES >= 0) return can && (GVTM_TUNE_PLAN_TABLES & 2) != 0;
 	return can && LAYOUT == 0 && ((U == 4 && (D == 1 || D == 2)) || (U == 2 && D == 2));
 }
+// which float shapes run the feed-forward half of their post-tube filter stage (stage_f2) 64 steps at a time.  What a step
+// of the radiation filters adds that depends on the inputs of steps n and n - 1 alone -- a x[n] - a x[n-1] -- and the sum of
+// mouth, nose and throat are formed by all 64 lanes of the stage's wavefront, in place in LDS, and the two lanes of a row
+// that own a recurrence keep only the recurrence.  The operations and their order are those of the serial form, so the
+// bits are.  Needs the block record (float, 10 + 6 tube, not SectionDelay 3) and the owning-lanes-only serial stages; never
+// the voice variant (not measured).  Adopted shape by shape, by measurement (profiles/filter_split_ab.md): parent / split,
+// kernel ms, three interleaved runs each: four rows, SectionDelay 2 (4096 x 7500) 312.55 / 308.73 (-1.2 %, 3.2 times the
+// parent's spread of 1.18) with 6.6 % fewer vector instructions issued -- the stage's wavefront is not what a tick waits
+// for, so most of what it sheds was not time.  No other shape was timed with the split: they keep the parent's
+// instruction stream (the forced library of the tests runs them bit for bit).
+// GVTM_TUNE_FILTER_SPLIT (a variant library's, for those measurements): bit 0 gives every shape that can take it the
+// split, and no other shape either.  (Bit 1 is kept for the pre-tube band-pass's feed-forward term, which is not built.)
+template <typename CT, typename ST, int D, int U, int LAYOUT, bool VOICES> constexpr bool filter_split_f2()
+{
+	constexpr bool can = sizeof(CT) == 4 && sizeof(ST) == 4 && LAYOUT == 0 && D != 3 && !VOICES;
+	if (GVTM_TUNE_FILTER_SPLIT >= 0) return can && (GVTM_TUNE_FILTER_SPLIT & 1) != 0;
+	return can && U == 4 && D == 2;
+}
 template <typename CT, int D, int U, bool VOICES> constexpr bool float_arg_consts() { return sizeof(CT) == 4 && !VOICES && !far_calls_inline<D, U>(); }
 
 template <typename CT, typename ST, int D, int U, int C, int NH, int LAYOUT_FLAGS>
@@ -546,6 +569,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	constexpr bool kBoundsRecurrence = bounds_by_recurrence<CT, D, U, LAYOUT>();
 	constexpr bool kSrcPhaseTable = src_phase_table<CT, D, U, LAYOUT, VOICES>();
 	constexpr bool kStaticWavetablePass = static_wavetable_pass<CT, D, U, LAYOUT, VOICES>();
+	constexpr bool kSplitF2 = filter_split_f2<CT, ST, D, U, LAYOUT, VOICES>();
 	constexpr int kKlLen = kl_len(kLaneRec);
 	constexpr int kInjLen = kLaneRec ? kKlLen : kInj; // stride of a step's injection values
 	auto at_kl = [](int slot, int u) { return rec_at<C, U>(kKlLen, slot, u); };
@@ -1663,11 +1687,138 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 		}
 	};
 
+	// F2 where filter_split_f2() says so: the same operations as stage_f2's serial loop below, but only the recurrence runs
+	// on the two lanes of a row.  The radiation filter is oy = (a x - a x1) + a y1 with every product rounded, x being
+	// (1 + k) * top: the difference d = a x[n] - a x[n-1] needs steps n and n - 1 of the tube's output alone, and the
+	// previous step's product has the same operands, hence the same bits, as when that step formed it.  Three passes of
+	// the one wavefront over the chunk, separated by program order alone (a wavefront's LDS operations complete in order):
+	//   1  all 64 lanes, one item per (row, mouth | nose, step): d, IN PLACE over the tube's output in sm.ox (this slot has
+	//      no other reader, and the tube writes the other slot this tick).  An item reads its left neighbour's input, so
+	//      the blocks of 64 items go from the highest down.  Step 0 stores a x[0] alone;
+	//   2  lanes 0 and 1 of a row: y[n] = d[n] + a y[n-1], four steps per 16-byte read and write, in place again.  The lane
+	//      subtracts a * (the x its state carries) from d[0] first, and ends with the state the serial form leaves: the
+	//      last valid step's x (read before pass 1 overwrites it) and y.  A partial last block runs on, as below;
+	//   3  all 64 lanes, one item per (row, step): (mouth + nose) + throat into the ring and its mirror, the steps below the
+	//      row's count only.
+	auto stage_f2_split = [&]([[maybe_unused]] int c, [[maybe_unused]] int valid) {
+		if constexpr (kSplitF2) {
+#pragma clang fp contract(off)
+		using F4 = float __attribute__((ext_vector_type(4)));
+		static_assert(!kSplitF2 || (kBlockRec && kMaskedSerial && kRowView && C % 4 == 0), "split post-tube filters: float, block record, row view");
+		constexpr int kRows = U < 4 ? U : 4;  // utterances of this wavefront
+		const int ub = U >= 4 ? sub * 4 : 0;  // the first of them
+		CT* const oxs = sm.ox + (static_cast<size_t>(c & 1) * U + ub) * C * 2; // [row][mouth | nose][C]
+		const CT* const opks = sm.opk + (static_cast<size_t>(c % 3) * U + ub) * C;
+		const CT* const thys = sm.thy + (static_cast<size_t>(c % 3) * U + ub) * C;
+		// (the lane as an opaque value: the masks and cursors this stage derives from it are formed again every tick.  Left to
+		// the compiler they were kept in scalar registers from tick to tick, across the helper passes' loop, which spills
+		// them: 119 against 108 spilled SGPRs and 35 more v_readlane / v_writelane in that loop's own code, and the flagship
+		// was 0.5 % SLOWER than without the split.  The constants stay kernel arguments: from their LDS copy, which no tick
+		// could keep either, the tube loop ran 141 instead of 136 cycles per step and the flagship +2.9 %;
+		// profiles/filter_split_ab.md)
+		const CT ra_m = GVTM_KF(kKfMouthARad, mouth_a_rad), ra_n = GVTM_KF(kKfNoseARad, nose_a_rad);
+		const CT opk_nose = CT(1.0) + GVTM_KF(kKfNasalK5, nasal_k[5]);
+		int ln = lane;
+		asm volatile("" : "+v"(ln));
+		const int L = ln & 15, row = ln >> 4;
+		const bool owner = (U >= 4 || row < U) && L < 2 && valid > 0; // the lanes of pass 2
+		CT x_last = CT(0.0);
+		if (owner) x_last = rmul(L == 0 ? opks[row * C + valid - 1] : opk_nose, oxs[(row * 2 + L) * C + valid - 1]);
+		// pass 1 (lane = step, row after row: which filter an item belongs to is uniform, and its addresses are the lane's
+		// cursor plus immediates)
+		CT* const lds0 = reinterpret_cast<CT*>(smem_raw);
+		unsigned ix = static_cast<unsigned>(oxs - lds0) + ln, iq = static_cast<unsigned>(opks - lds0) + ln, it = static_cast<unsigned>(thys - lds0) + ln;
+		const int back = ln > 0 ? 1 : 0; // (step 0 of a chunk has no left neighbour: it reads itself, and stores a x[0])
+		unsigned ixb = ix - back, iqb = iq - back;
+		asm volatile("" : "+v"(ix), "+v"(iq), "+v"(it), "+v"(ixb), "+v"(iqb));
+		CT* const px = lds0 + ix;
+		const CT* const pq = lds0 + iq;
+		const CT* const pt = lds0 + it;
+		const CT* const pxb = lds0 + ixb; // the cursors one step back
+		const CT* const pqb = lds0 + iqb;
+#pragma unroll
+		for (int sb = ((C - 1) / 64) * 64; sb >= 0; sb -= 64) { // (from the highest 64 steps down: step sb reads step sb - 1)
+			if (C - sb < 64 && ln >= C - sb) continue;
+			const CT* const pxl = sb > 0 ? px - 1 : pxb;
+			const CT* const pql = sb > 0 ? pq - 1 : pqb;
+			const bool left = sb > 0 || ln > 0;
+#pragma unroll
+			for (int r = 0; r < 2 * kRows; ++r) { // r = 2 * row + (0 mouth | 1 nose)
+				const int o = r * C + sb;
+				const CT x = px[o], xp = pxl[o];
+				CT p, pp;
+				if (r & 1) {
+					p = rmul(ra_n, rmul(opk_nose, x)); pp = rmul(ra_n, rmul(opk_nose, xp));
+				} else {
+					const int oq = (r >> 1) * C + sb;
+					p = rmul(ra_m, rmul(pq[oq], x)); pp = rmul(ra_m, rmul(pql[oq], xp));
+				}
+				px[o] = left ? p - pp : p;
+			}
+		}
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+		// pass 2
+		if (owner) {
+			const CT ra = L == 0 ? ra_m : ra_n;
+			// (the cursor as an opaque element index, see the tube stage: the block offsets become immediates)
+			unsigned id = static_cast<unsigned>(oxs + (row * 2 + L) * C - lds0);
+			asm volatile("" : "+v"(id));
+			F4* pd = reinterpret_cast<F4*>(lds0 + id);
+			CT y1 = rad_y1;
+			auto run = [&](const F4& d) {
+				F4 y;
+				y.x = d.x + rmul(ra, y1);
+				y.y = d.y + rmul(ra, y.x);
+				y.z = d.z + rmul(ra, y.y);
+				y.w = d.w + rmul(ra, y.z);
+				y1 = y.w;
+				return y;
+			};
+			F4 da = pd[0];
+			da.x = da.x - rmul(ra, rad_x1);
+			int s0 = 0;
+			for (; s0 + 4 < valid; s0 += 8) {
+				const F4 db = pd[1];
+				pd[0] = run(da);
+				da = pd[2]; // past the chunk: the next LDS rows, never used
+				pd[1] = run(db);
+				pd += 2;
+			}
+			if (s0 < valid) pd[0] = run(da);
+			rad_x1 = x_last;
+			rad_y1 = y1;
+		}
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+		// pass 3 (lane = step, row after row)
+		const bool dbg = GVTM_KERNEL_TAPS && a.debug_taps != nullptr;
+#pragma unroll
+		for (int sb = 0; sb < C; sb += 64) {
+			if (C - sb < 64 && ln >= C - sb) continue;
+			const int s = sb + ln;
+#pragma unroll
+			for (int r = 0; r < kRows; ++r) {
+				const int uu = ub + r;
+				const CT sample = (px[2 * r * C + sb] + px[(2 * r + 1) * C + sb]) + pt[r * C + sb]; // (mouth + nose) + throat (VocalTractModel0.h:639-441)
+				if (s < valid_in(uu, c)) {
+					const unsigned slot = (static_cast<uint32_t>(sm.ext[uu].step_base) + static_cast<uint32_t>(c) * C + s) & (XR - 1); // ring slots go by the stream's sample number
+					ST* xr = sm.x + uu * XRS;
+					xr[slot] = static_cast<ST>(sample);
+					if (slot < static_cast<unsigned>(kXMirror)) xr[XR + slot] = static_cast<ST>(sample); // the ring's first kXMirror samples a second time behind its end
+					if (dbg) a.debug_taps[(GVTM_ROW_UTT(uu, (group * U + uu)) * a.max_frames * k.control_steps + static_cast<uint32_t>(c) * C + s) * 8 + 7] = sample;
+				}
+			}
+		}
+		}
+	};
+
 	// F2: radiation high-pass at mouth and nose (RadiationFilter.h:68-79), their sum and the throat
 	// contribution (VocalTractModel0.h:639-441) -> internal-rate ring read by the resampler
 	auto stage_f2 = [&](int c) {
 		const int u = urow;
 		const int valid = valid_in(u, c);
+		if constexpr (kSplitF2) {
+			if (c >= 0 && c < max_chunks) stage_f2_split(c, valid); // (all 64 lanes, whatever their own row's chunk count)
+		}
 		if (valid < 0) return;
 		const Extent e = sm.ext[u];
 		const bool active = U >= 4 || row < U;
@@ -1685,8 +1836,9 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 		// the four samples leave in one store.  (One step per iteration made every step wait for an LDS round trip: the
 		// role took as long as the tube.)  A partial last block runs on over stale inputs: only an utterance's last chunk
 		// can be partial, its filter state is not used again and the flush zeros below overwrite the extra ring slots.
-		if (kMaskedSerial && !(active && L < 2)) {
+		if (kSplitF2 || (kMaskedSerial && !(active && L < 2))) {
 			// (only the mouth and nose lanes of a row run the filters; the flush zeros below take the whole row)
+			// (kSplitF2: stage_f2_split has run them)
 		} else {
 		const CT* po = ox + which * C;
 		const CT* pt = thy;

@@ -100,6 +100,14 @@ int synth_chunk_length(const DeviceConstants& k, int precision, int rows)
 	return with_shape(precision, rows, k.section_delay, k.layout, 0, [](auto s) { return decltype(s)::C; });
 }
 
+int synth_filter_split(const DeviceConstants& k, int precision, int rows)
+{
+	return with_shape(precision, rows, k.section_delay, k.layout, 0, [](auto s) {
+		using S = decltype(s);
+		return v2::filter_split_f2<typename S::CT, typename S::ST, S::D, S::U, S::LAYOUT, false>() ? 1 : 0;
+	});
+}
+
 size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr)
 {
 	const int lanes = k.layout == 1 ? 48 : 16, words = 2 * k.section_delay + 1;

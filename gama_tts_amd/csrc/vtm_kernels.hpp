@@ -187,6 +187,9 @@ LaunchShape synth_launch_shape(const Design* voices, int n_voices, int precision
 		int stream_ring = 0, bool fit = true);
 // the chunk length (internal steps per tick) of a shape, which its own ring length follows; 0: no such shape
 int synth_chunk_length(const DeviceConstants& k, int precision, int rows);
+// which of its serial filter stages a single-voice shape runs with the feed-forward half 64 steps at a time
+// (v2::filter_split_f2: bit 0, the post-tube filters); 0: none, or no such shape
+int synth_filter_split(const DeviceConstants& k, int precision, int rows);
 // batch: utterances, or with args.row_map set (several voices) the workgroups of launch_group_voices' map, of one voice
 // each (args.xr: the longest ring of the voices; a stream's rings follow args.stream_chunk)
 hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream);
