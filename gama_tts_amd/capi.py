@@ -185,6 +185,9 @@ def _prototypes():
         "gvtm_targets_apply_host": (i, [vp, i, vp, vp, vp, i64, vp, vp]),
         "gvtm_targets_apply_host_from": (i, [vp, i, vp, vp, vp, i64, i64, vp, vp, vp]),
         "gvtm_synthesize_targets_device": (i, [vp, vp, sz, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
+        "gvtm_targets_voice_output_count": (sz, [vp, i, sz]),
+        "gvtm_targets_voices_output_capacity": (sz, [vp, sz]),
+        "gvtm_synthesize_targets_voices_device": (i, [vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
         "gvtm_stream_push_targets": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
         "gvtm_stream_targets_capacity": (sz, [vp, sz]),
         "gvtm_stream_targets_points": (i, [vp, vp]),
@@ -926,6 +929,24 @@ class Plan:
         self._check(self._lib.gvtm_synthesize_targets_device(
             self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
             int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status), _ptr(stream)))
+
+    def targets_voice_output_count(self, voice, steps):
+        """gvtm_targets_voice_output_count: the samples of an utterance of `steps` internal steps under voice `voice`;
+        (size_t)-1 for a voice outside the plan's, as voice_output_count."""
+        return int(self._lib.gvtm_targets_voice_output_count(self._h, int(voice), int(steps)))
+
+    def targets_voices_output_capacity(self, max_steps):
+        """gvtm_targets_voices_output_capacity: the row length that holds every utterance of up to max_steps steps under any voice."""
+        return int(self._lib.gvtm_targets_voices_output_capacity(self._h, int(max_steps)))
+
+    def synthesize_targets_voices_device(self, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, d_voice_ids,
+                                         batch, max_steps, d_audio, audio_stride, d_out_counts=None, d_maxabs=None, d_status=None, stream=None):
+        """synthesize_targets_device with a voice id per utterance (gvtm_synthesize_targets_voices_device): utterance b walks
+        its lists under voice d_voice_ids[b]; on a plan of one voice the ids are all 0.  All pointers are device memory."""
+        self._check(self._lib.gvtm_synthesize_targets_voices_device(
+            self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
+            _ptr(d_voice_ids), int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status),
+            _ptr(stream)))
 
     def synthesize_events_device(self, track_config, d_events, d_offsets, batch, max_frames, d_audio, audio_stride,
                                  d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, stream=None):

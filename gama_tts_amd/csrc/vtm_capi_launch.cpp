@@ -110,6 +110,8 @@ gvtm::SynthArgs synth_args(const gvtm_plan* plan, const LaunchRequest& r)
 		args.tg_values = r.targets->point_values;
 		args.tg_N = r.targets->N;
 		args.tg_invN = r.targets->invN;
+		args.tg_voice_N = r.targets->voice_N;
+		args.tg_voice_invN = r.targets->voice_invN;
 	}
 	return args;
 }
@@ -167,7 +169,9 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (r.batch == 0) return GVTM_OK;
 	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
 	if (r.voices && !r.voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
-	if (r.targets && (r.voices || plan->designs[0].model5 || !r.frame_counts)) return fail(GVTM_ERR_UNSUPPORTED, "targets: a launch of one voice of the models 0 to 4");
+	if (r.targets && (plan->designs[0].model5 || !r.frame_counts)) return fail(GVTM_ERR_UNSUPPORTED, "targets: a launch of the models 0 to 4 with step counts");
+	// (several voices: a one-shot launch, with the plan's filter lengths by voice)
+	if (r.targets && r.voices && (r.sl || !r.targets->voice_N || !r.targets->voice_invN)) return fail(GVTM_ERR_UNSUPPORTED, "targets of several voices: one-shot launches only");
 	if (r.max_frames > 0 && !r.params && !r.targets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	// (several voices: the row map's int32 slots also count up to n_voices partly empty workgroups)
 	if (r.batch > (r.voices ? 0x3fffffffu : 0x7fffffffu)) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");

@@ -76,6 +76,15 @@ int upload_tables(gvtm_plan* plan)
 	if (!dg.model5) {
 		if ((rc = upload_design(plan->d_wavetable, wavetables, wavetables_f, "upload wavetable")) != GVTM_OK) return rc;
 		if ((rc = upload_design(plan->d_fir, dg.fir, dg.fir_f, "upload fir")) != GVTM_OK) return rc;
+		// the targets' filter by voice, as gvtm_synthesize_targets_device forms the two for its one voice (vtm_capi_targets.cpp)
+		std::vector<int64_t> targets_N;
+		std::vector<double> targets_invN;
+		for (const gvtm::Design& dv : plan->designs) {
+			targets_N.push_back(gvtm::targets_filter_length(internal_rate_hz(dv)));
+			targets_invN.push_back(1.0 / static_cast<double>(targets_N.back()));
+		}
+		if ((rc = upload(plan->d_targets_N, targets_N, "upload targets filter lengths")) != GVTM_OK) return rc;
+		if ((rc = upload(plan->d_targets_invN, targets_invN, "upload targets filter reciprocals")) != GVTM_OK) return rc;
 	}
 	if ((rc = upload_design(plan->d_src_h, dg.src_h, dg.src_h_f, "upload src_h")) != GVTM_OK) return rc;
 	if ((rc = upload_design(plan->d_src_dh, dg.src_dh, dg.src_dh_f, "upload src_dh")) != GVTM_OK) return rc;

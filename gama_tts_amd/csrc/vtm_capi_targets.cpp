@@ -1,7 +1,7 @@
 // C ABI of libgama_vtm.so, synthesis from parameter targets (the editor's interactive window): the filter length, the sample
-// counts by internal steps, the rule on the host, and the device entry, which puts the synthesis launch -- the kernel's
-// targets driver, launch_synthesis with LaunchRequest::targets -- behind the check kernel with the plan's step counts in
-// between.
+// counts by internal steps, the rule on the host, and the two device entries (one voice; a voice id per utterance), which put
+// the synthesis launch -- the kernel's targets driver, launch_synthesis with LaunchRequest::targets -- behind the check kernel
+// with the plan's step counts in between.
 #include "vtm_host.hpp"
 #include "vtm_targets.hpp"
 
@@ -25,6 +25,72 @@ int apply_host(const gvtm_plan* plan, int voice, const int64_t* list_offsets, co
 	*status_out = gvtm::targets_apply_from(gvtm::targets_filter_length(internal_rate_hz(plan->designs[voice])), list_offsets, point_steps, point_values,
 			first_step, n_steps, sums, frames_out);
 	return GVTM_OK;
+}
+
+// the longest row any voice of the plan needs for utterances of up to max_steps steps
+size_t voices_output_capacity(const gvtm_plan* plan, size_t max_steps)
+{
+	size_t capacity = 0;
+	for (const gvtm::Design& dv : plan->designs) capacity = std::max(capacity, steps_output_capacity(dv, max_steps));
+	return capacity;
+}
+
+// what the two device entries ask of a batch's arguments in front of the stride, which each holds against its own capacity
+int check_batch_arguments(const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids, const int32_t* d_point_steps, const float* d_point_values,
+		size_t batch, size_t max_steps, const float* d_audio)
+{
+	if (!d_list_offsets || !d_point_steps || !d_point_values || !d_audio) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "null list offsets, point steps, point values or audio buffer");
+	}
+	if (batch > 0x7fffffffu / GVTM_N_PARAM) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
+	if (!d_list_ids && n_lists != GVTM_N_PARAM * batch) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "without list ids every utterance has 16 lists of its own: n_lists must equal 16 * batch");
+	}
+	if (!gvtm::targets_fits_step_counter(static_cast<int64_t>(std::min<size_t>(max_steps, INT64_MAX)))) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_steps does not fit the 31-bit step counter");
+	}
+	return GVTM_OK;
+}
+
+// The check kernel and the synthesis launch on the caller's stream, with the plan's step counts in between: the utterance's
+// own count, or 0 for a refused utterance.  d_voice_ids null: the one voice of the plan, and the single-voice kernels; set:
+// utterance b under voice d_voice_ids[b], the grouping kernel in front of the voice variant (launch_synthesis), which
+// reads each voice's filter length from the plan's tables.
+int check_and_launch(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids, const int32_t* d_point_steps,
+		const float* d_point_values, const int32_t* d_step_counts, const int32_t* d_voice_ids, size_t batch, size_t max_steps, float* d_audio, size_t audio_stride,
+		int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
+{
+	DeviceScope scope(plan->device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	hipError_t e;
+	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc step counts");
+	int32_t* const d_steps = plan->async.frames.as<int32_t>();
+	gvtm::TargetsCheckArgs check{};
+	check.list_offsets = d_list_offsets;
+	check.n_lists = static_cast<int64_t>(std::min<size_t>(n_lists, INT64_MAX));
+	check.list_ids = d_list_ids;
+	check.point_steps = d_point_steps;
+	check.point_values = d_point_values;
+	check.step_counts = d_step_counts;
+	check.batch = batch;
+	check.max_steps = max_steps;
+	check.steps_out = d_steps;
+	check.status = d_status;
+	check.voice_ids = d_voice_ids;
+	check.n_voices = plan->n_voices();
+	if ((e = gvtm::launch_targets_check(check, static_cast<hipStream_t>(hip_stream))) != hipSuccess) return fail_hip(e, "vtm_targets_check_kernel launch");
+	const int64_t N = gvtm::targets_filter_length(internal_rate_hz(plan->designs[0]));
+	TargetsLaunch targets{d_list_offsets, d_list_ids, d_point_steps, d_point_values, N, 1.0 / static_cast<double>(N)};
+	LaunchRequest r{nullptr, d_steps, batch, max_steps, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream};
+	r.targets = &targets;
+	if (d_voice_ids) {
+		targets.voice_N = plan->d_targets_N.as<int64_t>();
+		targets.voice_invN = plan->d_targets_invN.as<double>();
+		r.voices = true;
+		r.voice_ids = d_voice_ids;
+		r.groups = &plan->async.groups;
+	}
+	return launch_synthesis(plan, r);
 }
 
 } // namespace
@@ -70,48 +136,48 @@ int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offset
 {
 	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
 	if (batch > 0) {
-		if (!d_list_offsets || !d_point_steps || !d_point_values || !d_audio) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "null list offsets, point steps, point values or audio buffer");
-		}
-		if (batch > 0x7fffffffu / GVTM_N_PARAM) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");
-		if (!d_list_ids && n_lists != GVTM_N_PARAM * batch) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "without list ids every utterance has 16 lists of its own: n_lists must equal 16 * batch");
-		}
-		if (!gvtm::targets_fits_step_counter(static_cast<int64_t>(std::min<size_t>(max_steps, INT64_MAX)))) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "max_steps does not fit the 31-bit step counter");
-		}
+		if (const int rc = check_batch_arguments(d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, batch, max_steps, d_audio); rc != GVTM_OK) return rc;
 		if (audio_stride < steps_output_capacity(plan->designs[0], max_steps)) {
 			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_targets_output_capacity(plan, max_steps)");
 		}
 	}
-	if (plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_device: a plan of one voice only");
+	if (plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_device: a plan of one voice only (gvtm_synthesize_targets_voices_device takes several)");
 	if (plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_device: the models 0 to 4 only");
 	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 	if (batch == 0) return GVTM_OK;
-	// The check kernel and the synthesis launch on the caller's stream, with the plan's step counts in between: the
-	// utterance's own count, or 0 for a refused utterance.
-	DeviceScope scope(plan->device);
-	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
-	hipError_t e;
-	if ((e = plan->async.frames.ensure(sizeof(int32_t) * batch)) != hipSuccess) return fail_hip(e, "hipMalloc step counts");
-	int32_t* const d_steps = plan->async.frames.as<int32_t>();
-	gvtm::TargetsCheckArgs check{};
-	check.list_offsets = d_list_offsets;
-	check.n_lists = static_cast<int64_t>(std::min<size_t>(n_lists, INT64_MAX));
-	check.list_ids = d_list_ids;
-	check.point_steps = d_point_steps;
-	check.point_values = d_point_values;
-	check.step_counts = d_step_counts;
-	check.batch = batch;
-	check.max_steps = max_steps;
-	check.steps_out = d_steps;
-	check.status = d_status;
-	if ((e = gvtm::launch_targets_check(check, static_cast<hipStream_t>(hip_stream))) != hipSuccess) return fail_hip(e, "vtm_targets_check_kernel launch");
-	const int64_t N = gvtm::targets_filter_length(internal_rate_hz(plan->designs[0]));
-	const TargetsLaunch targets{d_list_offsets, d_list_ids, d_point_steps, d_point_values, N, 1.0 / static_cast<double>(N)};
-	LaunchRequest r{nullptr, d_steps, batch, max_steps, d_audio, audio_stride, d_out_counts, d_maxabs, hip_stream};
-	r.targets = &targets;
-	return launch_synthesis(plan, r);
+	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, nullptr, batch, max_steps, d_audio, audio_stride,
+			d_out_counts, d_maxabs, d_status, hip_stream);
+}
+
+size_t gvtm_targets_voice_output_count(const gvtm_plan* plan, int voice, size_t n_steps)
+{
+	if (!plan || voice < 0 || voice >= plan->n_voices()) return static_cast<size_t>(-1);
+	return steps_output_count(plan->designs[voice], n_steps);
+}
+
+size_t gvtm_targets_voices_output_capacity(const gvtm_plan* plan, size_t max_steps)
+{
+	if (!plan) return static_cast<size_t>(-1);
+	return voices_output_capacity(plan, max_steps);
+}
+
+int gvtm_synthesize_targets_voices_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
+		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, const int32_t* d_voice_ids, size_t batch, size_t max_steps,
+		float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (batch > 0) {
+		if (const int rc = check_batch_arguments(d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, batch, max_steps, d_audio); rc != GVTM_OK) return rc;
+		if (!d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
+		if (audio_stride < voices_output_capacity(plan, max_steps)) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_targets_voices_output_capacity(plan, max_steps)");
+		}
+	}
+	if (plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_voices_device: the models 0 to 4 only");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
+	if (batch == 0) return GVTM_OK;
+	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, d_voice_ids, batch, max_steps, d_audio,
+			audio_stride, d_out_counts, d_maxabs, d_status, hip_stream);
 }
 
 } // extern "C"

@@ -120,6 +120,9 @@ struct gvtm_plan {
 	// design tables on the device: double, or float (as designed) for GVTM_PRECISION_F32
 	DeviceBuffer d_wavetable, d_fir, d_src_h, d_src_dh;
 	DeviceBuffer d_consts, d_consts5; // gvtm::DeviceConstants, gvtm::Model5Constants (model 5 plans only)
+	// the models 0 to 4: the length of the targets' moving average and its reciprocal by voice (vtm_targets.hpp:
+	// targets_filter_length of the voice's internal rate), what gvtm_synthesize_targets_voices_device's kernel reads
+	DeviceBuffer d_targets_N, d_targets_invN;
 	// the noise source's samples by internal step (the same for every utterance), grown on demand; superseded buffers stay
 	// allocated until the plan goes (a launch in flight on the caller's stream may still read them; the growth is
 	// geometric, so together they are smaller than the live one)
@@ -144,8 +147,8 @@ struct gvtm_plan {
 		void release_sets() { for (DeviceBuffer& s : set) s = DeviceBuffer(); }
 		unsigned char* set_of(size_t i) const { return set[i % 3].as<unsigned char>(); } // slice i's: the sets rotate
 	} host;
-	// ... and the enqueue-only entries' (gvtm_synthesize_events_device's and gvtm_synthesize_modified_device's frames and frame counts, gvtm_synthesize_targets_device's step counts, the grouping of
-	// gvtm_synthesize_voices_device, the merged event lists and their offsets of gvtm_synthesize_intonation_device): calls to
+	// ... and the enqueue-only entries' (gvtm_synthesize_events_device's and gvtm_synthesize_modified_device's frames and frame counts, gvtm_synthesize_targets_device's
+	// and gvtm_synthesize_targets_voices_device's step counts, the grouping of gvtm_synthesize_voices_device and of that entry, the merged event lists and their offsets of gvtm_synthesize_intonation_device): calls to
 	// those on one plan must be ordered on one stream
 	struct {
 		DeviceBuffer params, frames, groups;
@@ -391,6 +394,9 @@ struct TargetsLaunch {
 	const float* point_values;
 	int64_t N;                 // the filter's length and its reciprocal
 	double invN;
+	// a launch of several voices (LaunchRequest::voices): the two by voice, the plan's tables on the device; N and invN unused
+	const int64_t* voice_N = nullptr;
+	const double* voice_invN = nullptr;
 };
 
 // One synthesis launch: the device buffers of a gvtm_synthesize_*_device call, of a slice of the host entries or of a stream

@@ -1,5 +1,6 @@
 // The shapes of vtm_synth_kernel, for the translation units that launch it (vtm_kernels.hip; vtm_kernels_targets.hip, the
-// targets variant's): included inside namespace gvtm, behind vtm_kernel_v2.inc, whose constants a shape is made of.
+// targets variant's; vtm_kernels_targets_voices.hip, that variant's under several voices): included inside namespace gvtm,
+// behind vtm_kernel_v2.inc, whose constants a shape is made of.
 #pragma once
 
 // ---- kernel shapes ----

@@ -386,9 +386,11 @@ constexpr int serial_waves()
 // what the register allocator spills: float, eight rows 476 -> 620 bytes of scratch.)
 constexpr int kVoicesFlag = 2;
 // Synthesis from parameter targets (gvtm_synthesize_targets_device): a third bit of the same argument, kTargetsFlag (default
-// off, one voice only).  With it the interpolation wavefront has a second driver: lane L of row u walks the points of list
+// off).  With it the interpolation wavefront has a second driver: lane L of row u walks the points of list
 // a.tg_ids[16 utt + L] through the moving average of vtm_targets.hpp and writes the same float per step into the `prm`
-// record; an utterance is a.frame_counts[utt] STEPS long, and there are no frames.  On behalf of a stream
+// record; an utterance is a.frame_counts[utt] STEPS long, and there are no frames.  Together with kVoicesFlag
+// (gvtm_synthesize_targets_voices_device; vtm_kernels_targets_voices.hip) utt is the row map's, and the filter's length
+// and reciprocal are the workgroup's voice's, a.tg_voice_N[voice] and a.tg_voice_invN[voice].  On behalf of a stream
 // (gvtm_stream_push_targets) the steps are absolute and the filters' sums travel in the stream state.  Nothing else differs between the two
 // drivers, and as with kVoicesFlag every difference is a conditional on the constant TARGETS whose targets arm the
 // compiler never emits for the other kernels.
@@ -471,7 +473,6 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	constexpr int LAYOUT = LAYOUT_FLAGS & 1; // gvtm_tube_layout
 	constexpr bool VOICES = (LAYOUT_FLAGS & kVoicesFlag) != 0;
 	constexpr bool TARGETS = (LAYOUT_FLAGS & kTargetsFlag) != 0;
-	static_assert(!(TARGETS && VOICES), "targets: one voice");
 	int voice = 0;
 	if constexpr (VOICES) {
 		voice = a.group_voice[blockIdx.x];
@@ -770,16 +771,25 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 	// epilogue stores the sum back.  An utterance the launch does not advance keeps its sums.
 	[[maybe_unused]] TargetsWalk tg{};
 	[[maybe_unused]] int64_t tg_base = 0;
+	// Several voices: the filter's length and its reciprocal are the workgroup's voice's, one uniform read each from the plan's
+	// per-voice tables, here and never per step; with one voice the arguments themselves serve.
+	[[maybe_unused]] int64_t tgv_N = 0;
+	[[maybe_unused]] double tgv_invN = 0.0;
+	if constexpr (TARGETS && VOICES) {
+		tgv_N = a.tg_voice_N[voice];
+		tgv_invN = a.tg_voice_invN[voice];
+	}
 	if constexpr (TARGETS) {
+		// (an empty row of a launch of several voices has 0 frames, as a refused utterance has: it begins no walk)
 		if (role == 4 && rowp < U && sm.ext[rowp].frames > 0) {
-			const size_t slot = (group * U + rowp) * GVTM_N_PARAM + Lp;
+			const size_t slot = GVTM_ROW_UTT(rowp, (group * U + rowp)) * GVTM_N_PARAM + Lp;
 			const int64_t list = a.tg_ids ? static_cast<int64_t>(a.tg_ids[slot]) : static_cast<int64_t>(slot);
 			if (a.stream) tg_base = static_cast<int64_t>(sm.ext[rowp].step_base);
 			if (tg_base > 0) {
-				const double* sums = reinterpret_cast<const double*>(a.stream + (group * U + rowp) * a.stream_stride + SL::sums(kTubeLanes, kTubeWords, XR));
-				targets_resume(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N, tg_base, sums[Lp]);
+				const double* sums = reinterpret_cast<const double*>(a.stream + GVTM_ROW_UTT(rowp, (group * U + rowp)) * a.stream_stride + SL::sums(kTubeLanes, kTubeWords, XR));
+				targets_resume(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], VOICES ? tgv_N : a.tg_N, tg_base, sums[Lp]);
 			} else {
-				targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N);
+				targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], VOICES ? tgv_N : a.tg_N);
 			}
 		}
 	}
@@ -1455,18 +1465,22 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 			// the cursors' bookkeeping only runs for a block in which some lane's cursor moves (a point enters, or leaves N
 			// steps later); every other block is four times {two double additions, a multiplication, a conversion, a store}.
 			// A partial last block runs on: no cursor passes the end of its list, and the extra rows are never read.
+			// (the filter's length and reciprocal through closures whose other arm is never instantiated: this stage's own closure
+			// carries the voice's two in the kernels of several voices only, and is what it was in the others)
+			[[maybe_unused]] const auto tg_length = [&]() -> int64_t { if constexpr (VOICES) return tgv_N; else return a.tg_N; };
+			[[maybe_unused]] const auto tg_inverse = [&]() -> double { if constexpr (VOICES) return tgv_invN; else return a.tg_invN; };
 			float* out = sm.prm + at_prm(c & 1, u) + Lp;
 			const int64_t first = tg_base + static_cast<int64_t>(c) * C;
 			for (int s0 = 0; s0 < valid; s0 += 4) {
 				if (__builtin_expect(__any(targets_moves(tg, first + s0, 4)), 0)) {
 #pragma unroll
 					for (int q = 0; q < 4; ++q) {
-						targets_move(tg, first + s0 + q, a.tg_steps, a.tg_values, a.tg_N);
-						out[(s0 + q) * kPrm] = targets_step(tg, a.tg_invN);
+						targets_move(tg, first + s0 + q, a.tg_steps, a.tg_values, tg_length());
+						out[(s0 + q) * kPrm] = targets_step(tg, tg_inverse());
 					}
 				} else {
 #pragma unroll
-					for (int q = 0; q < 4; ++q) out[(s0 + q) * kPrm] = targets_step(tg, a.tg_invN);
+					for (int q = 0; q < 4; ++q) out[(s0 + q) * kPrm] = targets_step(tg, tg_inverse());
 				}
 			}
 			return;
@@ -2471,7 +2485,7 @@ __global__ __launch_bounds__((serial_waves<U, LAYOUT_FLAGS & 1>() + NH) * 64) vo
 		if constexpr (TARGETS) {
 			// the moving averages' sums, push and finish alike (a push synthesizes whole blocks of four steps: no lane ran on)
 			if (role == 4 && rowp < U && sm.ext[rowp].frames > 0) {
-				double* sums = reinterpret_cast<double*>(a.stream + (group * U + rowp) * a.stream_stride + SL::sums(kTubeLanes, kTubeWords, XR));
+				double* sums = reinterpret_cast<double*>(a.stream + GVTM_ROW_UTT(rowp, (group * U + rowp)) * a.stream_stride + SL::sums(kTubeLanes, kTubeWords, XR));
 				sums[Lp] = tg.sum;
 			}
 		}

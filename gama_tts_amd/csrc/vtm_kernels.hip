@@ -3,7 +3,8 @@
 //   vtm_synth_kernel   (vtm_kernel_v2.inc)  VocalTractModel0 / 2 / 4 semantics: a workgroup owns 1, 2, 4 or 8 utterances and
 //                      5 + NH wavefronts with fixed roles (tube, scans, pre-/post-tube filters, interpolation, helpers),
 //                      software-pipelined over chunks of internal-rate steps with one barrier per tick; see that file's header
-//                      (its targets variant, kTargetsFlag, is compiled in vtm_kernels_targets.hip)
+//                      (its targets variant, kTargetsFlag, is compiled in vtm_kernels_targets.hip, and that variant
+//                      under several voices in vtm_kernels_targets_voices.hip)
 //   vtm5_synth_kernel  (vtm_kernel_m5.inc)  VocalTractModel5 semantics, same organisation (its voice variant is compiled
 //                      in vtm_kernels_m5v.hip, its float class in vtm_kernels_m5f.hip, that class's voice variant in
 //                      vtm_kernels_m5fv.hip)
@@ -87,8 +88,9 @@ hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int 
 		return with_shape(precision, rows, args.k.section_delay, args.k.layout, hipErrorInvalidValue,
 				[&](auto s) { return launch_v2<decltype(s), decltype(voices)::value>(args, batch, stream); });
 	};
-	// (the targets variant lives in vtm_kernels_targets.hip: this file's code object keeps the kernels it had)
-	if (args.tg_offsets) return args.row_map ? hipErrorInvalidValue : launch_synth_targets(args, batch, precision, rows, stream);
+	// (the targets variant lives in vtm_kernels_targets.hip, that of several voices in vtm_kernels_targets_voices.hip: this
+	// file's code object keeps the kernels it had)
+	if (args.tg_offsets) return args.row_map ? launch_synth_targets_voices(args, batch, precision, rows, stream) : launch_synth_targets(args, batch, precision, rows, stream);
 	// (one pass over the shapes per variant, single voice first: the order the code object has its kernels in)
 	if (!args.row_map) return launch(std::false_type{});
 	if (!args.group_voice) return hipErrorInvalidValue;

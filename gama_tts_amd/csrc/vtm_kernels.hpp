@@ -140,6 +140,10 @@ struct SynthArgs {
 	const float* tg_values = nullptr;
 	int64_t tg_N = 0;
 	double tg_invN = 0.0;
+	// targets under several voices (row_map and tg_offsets set: vtm_kernels_targets_voices.hip): the filter's length and its
+	// reciprocal by voice, [n_voices] each in device memory (the plan uploads them once); tg_N and tg_invN are then unused
+	const int64_t* tg_voice_N = nullptr;
+	const double* tg_voice_invN = nullptr;
 };
 
 struct GroupVoicesArgs {
@@ -196,6 +200,9 @@ hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int 
 // the targets variant alone (vtm_kernels_targets.hip; launch_synth calls it where args.tg_offsets is set): one voice, one,
 // two or four rows
 hipError_t launch_synth_targets(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream);
+// the targets variant of several voices alone (vtm_kernels_targets_voices.hip; launch_synth calls it where args.tg_offsets
+// and args.row_map are set): `groups` workgroups of launch_group_voices' map, one, two or four rows
+hipError_t launch_synth_targets_voices(const SynthArgs& args, size_t groups, int precision, int rows, hipStream_t stream);
 // bytes of one utterance's stream state for a plan (ring length of the one-row shape: streams whose utterances are not in
 // lockstep run one utterance per workgroup, and every shape of a stream uses that ring length)
 size_t stream_state_bytes(const DeviceConstants& k, int precision, int xr);

@@ -58,7 +58,9 @@ __global__ __launch_bounds__(64) void vtm_targets_check_kernel(const TargetsChec
 	int32_t status = kTargetsOk;
 	int64_t list = 0, p0 = 0, p1 = 0;
 	if (mine) list = a.list_ids ? static_cast<int64_t>(a.list_ids[utt * GVTM_N_PARAM + lane]) : static_cast<int64_t>(utt * GVTM_N_PARAM + lane);
-	if (steps < 0 || steps > static_cast<int64_t>(a.max_steps) || __ballot(mine && (list < 0 || list >= a.n_lists))) {
+	if (a.voice_ids && (a.voice_ids[utt] < 0 || a.voice_ids[utt] >= a.n_voices)) {
+		status = kTargetsBadVoice;
+	} else if (steps < 0 || steps > static_cast<int64_t>(a.max_steps) || __ballot(mine && (list < 0 || list >= a.n_lists))) {
 		status = kTargetsBadCount;
 	} else {
 		if (mine) {

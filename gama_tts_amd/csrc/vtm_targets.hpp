@@ -27,6 +27,7 @@ enum TargetsStatus : int32_t {
 	kTargetsBadOffsets = 2, // list offsets that are negative or decrease
 	kTargetsBadValue = 3,   // a value that is not finite
 	kTargetsBadSteps = 4,   // a negative step, steps not strictly increasing within a list
+	kTargetsBadVoice = 5,   // device, several voices: a voice id outside [0, n_voices); looked at first
 };
 
 // MovingAverageFilter<float>(sampleRate, PARAMETER_FILTER_PERIOD_SEC = 50.0e-3) (InteractiveAudio.cpp:104): at 20 050 Hz the
@@ -206,6 +207,10 @@ struct TargetsCheckArgs {
 	size_t batch, max_steps;
 	int32_t* steps_out;          // [batch]
 	int32_t* status;             // [batch] or null
+	// several voices (gvtm_synthesize_targets_voices_device), or null: an utterance whose id is outside [0, n_voices) has
+	// status kTargetsBadVoice, looked at before every other, and 0 steps (the grouping kernel leaves it out of the row map)
+	const int32_t* voice_ids;    // [batch] or null
+	int n_voices;
 };
 
 hipError_t launch_targets_check(const TargetsCheckArgs& args, hipStream_t stream);

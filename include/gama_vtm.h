@@ -54,7 +54,8 @@
  *                               the editor's interactive window: targets for the 16 parameters, each smoothed by a 50 ms
  *                               MovingAverageFilter<float> on every internal step, then execSynthesisStep()
  *                               (gama_tts_editor/src/interactive/InteractiveAudio.cpp:164-186);
- *                               gvtm_stream_push_targets: the same as a session, targets arriving push by push
+ *                               gvtm_stream_push_targets: the same as a session, targets arriving push by push;
+ *                               gvtm_synthesize_targets_voices_device: the same for a batch that mixes voices
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
@@ -910,6 +911,9 @@ int gvtm_synthesize_modified_device(gvtm_plan* plan, const float* d_base_params,
  *   2  list offsets that are negative or decrease
  *   3  a value that is not finite
  *   4  a negative step; steps not strictly increasing within a list
+ *   5  gvtm_synthesize_targets_voices_device only: a voice id outside [0, n_voices).  Looked at before every other status;
+ *      such an utterance is not one of 0 steps but left out as gvtm_synthesize_voices_device leaves it out: out_counts -1,
+ *      maxabs 0, its audio row untouched
  */
 
 /* N of the rule for a voice of the plan; -1 on a null plan or a voice outside the plan's.  Host only: works on
@@ -973,11 +977,41 @@ int gvtm_targets_apply_host_from(const gvtm_plan* plan, int voice, const int64_t
  * point table or audio buffer, a NULL d_list_ids with n_lists != 16 * batch, a max_steps beyond the step counter, a stride
  * below gvtm_targets_output_capacity(plan, max_steps) (GVTM_ERR_INVALID_ARGUMENT); a plan of several voices or a model 5
  * plan (GVTM_ERR_UNSUPPORTED); a design-only plan (GVTM_ERR_NO_DEVICE), with batch == 0 too; on a plan with a device
- * batch == 0 returns GVTM_OK. */
+ * batch == 0 returns GVTM_OK.  A plan of several voices has gvtm_synthesize_targets_voices_device (below). */
 int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
 		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, size_t batch,
 		size_t max_steps, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status,
 		void* hip_stream);
+
+/* gvtm_targets_output_count for voice `voice` of a plan of several voices, and the row length that holds every utterance of
+ * up to max_steps steps under any voice of the plan: the largest of the voices' gvtm_targets_output_capacity.  What
+ * gvtm_voice_output_count and gvtm_voices_output_capacity are to the frame entries, by steps.  Host only: they work on
+ * GVTM_DEVICE_NONE plans.  (size_t)-1 on a null plan, the count also for a voice outside the plan's. */
+size_t gvtm_targets_voice_output_count(const gvtm_plan* plan, int voice, size_t n_steps);
+size_t gvtm_targets_voices_output_capacity(const gvtm_plan* plan, size_t max_steps);
+
+/* gvtm_synthesize_targets_device with a voice id per utterance: one articulator trajectory under every speaker in one launch.
+ *   d_voice_ids [batch] int32                    utterance b walks its lists under voice d_voice_ids[b] of the plan: that
+ *                                                voice's own N = gvtm_targets_filter_length(plan, voice) and 1 / N.  Lists
+ *                                                hold no N, so utterances of different voices may share a list
+ *   d_audio [batch][audio_stride]                utterance b yields gvtm_targets_voice_output_count(plan, voice_b, S_b) samples
+ *   every other argument                         as gvtm_synthesize_targets_device's
+ * In every precision voice v's utterances come out bit for bit -- samples, out_counts, maxabs -- as
+ * gvtm_synthesize_targets_device synthesizes them on a one-voice plan made from configs[v].  A voice id outside
+ * [0, n_voices) is status 5 (above); an utterance refused with status 1 to 4 is one of 0 steps of its voice.  Plans of the
+ * models 0 to 4 of any number of voices: on a plan of one voice (gvtm_plan_create, or gvtm_plan_create_voices with one
+ * config) ids that are all 0 give gvtm_synthesize_targets_device's bytes.  Enqueue-only -- the check kernel, the grouping
+ * kernel of gvtm_synthesize_voices_device and the synthesis launch on hip_stream -- with the same exception: a float plan's
+ * noise table grows to max_steps steps.  The call uses the plan's grouping scratch and step-count scratch: calls on one plan
+ * must be ordered on one stream, as gvtm_synthesize_voices_device's.  Refused before any device work, in this order: a null
+ * plan; with batch > 0 what gvtm_synthesize_targets_device refuses, NULL d_voice_ids, a stride below
+ * gvtm_targets_voices_output_capacity(plan, max_steps) (GVTM_ERR_INVALID_ARGUMENT); a model 5 plan of either class
+ * (GVTM_ERR_UNSUPPORTED); a design-only plan (GVTM_ERR_NO_DEVICE), with batch == 0 too; on a plan with a device batch == 0
+ * returns GVTM_OK. */
+int gvtm_synthesize_targets_voices_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists,
+		const int32_t* d_list_ids, const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts,
+		const int32_t* d_voice_ids, size_t batch, size_t max_steps, float* d_audio, size_t audio_stride,
+		int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream);
 
 /*
  * Streams fed parameter targets: the interactive window as a session.  Targets arrive while the audio is playing, so a
