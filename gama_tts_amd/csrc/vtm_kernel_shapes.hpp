@@ -1,6 +1,7 @@
-// The shapes of vtm_synth_kernel, for the translation units that launch it (vtm_kernels.hip; vtm_kernels_targets.hip, the
-// targets variant's; vtm_kernels_targets_voices.hip, that variant's under several voices): included inside namespace gvtm,
-// behind vtm_kernel_v2.inc, whose constants a shape is made of.
+// The shapes of vtm_synth_kernel and the one function that launches them, for the translation units that hold a variant of
+// the kernel (vtm_kernels.hip: frames, one voice and several; vtm_kernels_targets.hip: targets; vtm_kernels_targets_voices.hip:
+// targets under several voices): included inside namespace gvtm, behind vtm_kernel_v2.inc, whose constants a shape is made of.
+// A unit is one launch_v2_variant<FLAGS> call per variant; a new variant is a new unit with one such call.
 #pragma once
 
 // ---- kernel shapes ----
@@ -120,4 +121,50 @@ static R with_shape(int precision, int rows, int delay, int layout, R refused, F
 static int ring_length(const DeviceConstants& k, int chunk)
 {
 	return synth_ring_for(k.upsampling, k.pad, chunk);
+}
+
+// ---- the launch ----
+//
+// The ONE launch of a shape S in a variant of vtm_synth_kernel.  FLAGS: a subset of v2::kVoicesFlag | v2::kTargetsFlag, OR-ed
+// into the kernel's last template argument.  `work`: utterances (one workgroup per S::U of them), or with the voices flag the
+// workgroups of launch_group_voices' map; args.xr is then the longest ring of the launch's voices (what the LDS is sized for;
+// a stream's: of the voices' stream rings, which args.stream_chunk fixes).
+// Eight rows are a diagnostics build's forced shape and the plain frames variant's alone: every other variant refuses them
+// without naming the kernel, so its code object holds the product's shapes only.
+template <typename S, int FLAGS>
+static hipError_t launch_v2(const SynthArgs& args, size_t work, hipStream_t stream)
+{
+	constexpr bool VOICES = (FLAGS & v2::kVoicesFlag) != 0;
+	if constexpr (FLAGS != 0 && S::U == 8) {
+		return hipErrorInvalidValue;
+	} else {
+		auto fn = v2::vtm_synth_kernel<typename S::CT, typename S::ST, S::D, S::U, S::C, S::NH, S::LAYOUT | FLAGS>;
+		if (args.xr < ring_length(args.k, S::C) || (args.xr & (args.xr - 1)) != 0 || 2 * S::C + 4 * args.k.pad + 64 > args.xr) return hipErrorInvalidValue;
+		if (!args.k.upsampling && args.xr != kSrcRing) return hipErrorInvalidValue;
+		// a kernel that takes its plan constants from the float block behind fir_k needs that block filled (synth_args does);
+		// never with several voices: each voice's constants come from its block in LDS
+		if constexpr (v2::float_arg_consts<typename S::CT, S::D, S::U, VOICES>()) {
+			if (args.fir_k.f[kFirKConsts + kKfBasicIncrement] != static_cast<float>(args.k.basic_increment)) return hipErrorInvalidValue;
+		}
+		const size_t lds = S::lds_bytes(args.xr);
+		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+				static_cast<int>(lds));
+		if (e != hipSuccess) return e;
+		const unsigned groups = static_cast<unsigned>(VOICES ? work : (work + S::U - 1) / S::U);
+		hipLaunchKernelGGL(fn, dim3(groups), dim3(S::kWaves * 64), lds, stream, args);
+		return hipGetLastError();
+	}
+}
+
+// What a translation unit calls, once per variant it holds: the variant's preconditions on the arguments, then one pass over
+// the shapes (a stream's launch, args.stream, takes the same shapes: the ring is the stream's, args.xr).
+template <int FLAGS>
+static hipError_t launch_v2_variant(const SynthArgs& args, size_t work, int precision, int rows, hipStream_t stream)
+{
+	constexpr bool VOICES = (FLAGS & v2::kVoicesFlag) != 0, TARGETS = (FLAGS & v2::kTargetsFlag) != 0;
+	if (VOICES ? !args.row_map || !args.group_voice : args.row_map != nullptr) return hipErrorInvalidValue;
+	if (TARGETS && (!args.tg_offsets || !args.tg_steps || !args.tg_values || !args.frame_counts)) return hipErrorInvalidValue;
+	if (TARGETS && (VOICES ? !args.tg_voice_N || !args.tg_voice_invN : args.tg_N < 1)) return hipErrorInvalidValue;
+	return with_shape(precision, rows, args.k.section_delay, args.k.layout, hipErrorInvalidValue,
+			[&](auto s) { return launch_v2<decltype(s), FLAGS>(args, work, stream); });
 }

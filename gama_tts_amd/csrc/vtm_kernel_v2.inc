@@ -124,7 +124,7 @@ struct Extent {
 	unsigned long long k_first;   // first output sample of this launch = ceil(step_base * 2^16 / time_inc)
 };
 
-// Diagnostic instruments (never set in the product build; tools/build_variant.sh makes variant libraries with them):
+// Diagnostic instruments (never set in the product build; tools/build_variant.sh <name> -D... is the Makefile's recipe with them):
 //   GVTM_KERNEL_TAPS  per-step intermediate values to SynthArgs::debug_taps (tests/tools/debug_taps.py); costs the serial
 //                     loops their scheduling
 //   GVTM_TUNE_SKIP    bit mask of stages left out, for counting instructions per stage (tools/collect_skip_counts.sh): a

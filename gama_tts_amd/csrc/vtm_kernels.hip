@@ -10,7 +10,8 @@
 //                      vtm_kernels_m5fv.hip)
 //   vtm_normalize_kernel                    output scaling of Controller::writeOutputToBuffer / writeOutputToFile
 //
-// Which shape a launch has (rows, chunk length, helpers, ring, LDS) is decided in vtm_kernel_shapes.hpp and only there.
+// Which shape a launch has (rows, chunk length, helpers, ring, LDS) is decided in vtm_kernel_shapes.hpp and only there, and
+// there every variant of vtm_synth_kernel is launched (launch_v2): this unit holds the frames variants, one voice and several.
 // Everything between the parameter frames (HBM in) and the audio samples (HBM out) lives in LDS; there is no
 // intermediate global traffic.
 #include <hip/hip_runtime.h>
@@ -52,49 +53,17 @@ __global__ __launch_bounds__(256) void vtm_normalize_kernel(const NormalizeArgs 
 	}
 }
 
-// ---- kernel shapes: vtm_kernel_shapes.hpp, shared with the targets variant's translation unit ----
+// ---- kernel shapes and their launch: vtm_kernel_shapes.hpp, shared with the targets variants' translation units ----
 #include "vtm_kernel_shapes.hpp"
-
-// VOICES: a launch of several voices (the kernel's kVoicesFlag; args.row_map is set); `batch` is then the number of
-// workgroups, and args.xr the longest ring of the launch's voices (what the LDS is sized for; a stream's: of the voices'
-// stream rings, which args.stream_chunk fixes)
-template <typename S, bool VOICES>
-static hipError_t launch_v2(const SynthArgs& args, size_t batch, hipStream_t stream)
-{
-	if constexpr (VOICES && S::U == 8) {
-		// several voices: the product's shapes only (eight rows are a diagnostics build's forced shape)
-		return hipErrorInvalidValue;
-	} else {
-		auto fn = v2::vtm_synth_kernel<typename S::CT, typename S::ST, S::D, S::U, S::C, S::NH, S::LAYOUT | (VOICES ? v2::kVoicesFlag : 0)>;
-		if (args.xr < ring_length(args.k, S::C) || (args.xr & (args.xr - 1)) != 0 || 2 * S::C + 4 * args.k.pad + 64 > args.xr) return hipErrorInvalidValue;
-		if (!args.k.upsampling && args.xr != kSrcRing) return hipErrorInvalidValue;
-		// a kernel that takes its plan constants from the float block behind fir_k needs that block filled (synth_args does)
-		if constexpr (v2::float_arg_consts<typename S::CT, S::D, S::U, VOICES>()) {
-			if (args.fir_k.f[kFirKConsts + kKfBasicIncrement] != static_cast<float>(args.k.basic_increment)) return hipErrorInvalidValue;
-		}
-		const size_t lds = S::lds_bytes(args.xr);
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-				static_cast<int>(lds));
-		if (e != hipSuccess) return e;
-		const unsigned groups = static_cast<unsigned>(VOICES ? batch : (batch + S::U - 1) / S::U);
-		hipLaunchKernelGGL(fn, dim3(groups), dim3(S::kWaves * 64), lds, stream, args);
-		return hipGetLastError();
-	}
-}
 
 hipError_t launch_synth(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream)
 {
-	const auto launch = [&](auto voices) {
-		return with_shape(precision, rows, args.k.section_delay, args.k.layout, hipErrorInvalidValue,
-				[&](auto s) { return launch_v2<decltype(s), decltype(voices)::value>(args, batch, stream); });
-	};
 	// (the targets variant lives in vtm_kernels_targets.hip, that of several voices in vtm_kernels_targets_voices.hip: this
 	// file's code object keeps the kernels it had)
 	if (args.tg_offsets) return args.row_map ? launch_synth_targets_voices(args, batch, precision, rows, stream) : launch_synth_targets(args, batch, precision, rows, stream);
 	// (one pass over the shapes per variant, single voice first: the order the code object has its kernels in)
-	if (!args.row_map) return launch(std::false_type{});
-	if (!args.group_voice) return hipErrorInvalidValue;
-	return launch(std::true_type{});
+	if (!args.row_map) return launch_v2_variant<0>(args, batch, precision, rows, stream);
+	return launch_v2_variant<v2::kVoicesFlag>(args, batch, precision, rows, stream);
 }
 
 int synth_chunk_length(const DeviceConstants& k, int precision, int rows)

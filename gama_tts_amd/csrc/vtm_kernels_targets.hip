@@ -1,7 +1,8 @@
 // The targets variant of the synthesis kernel (vtm_synth_kernel with kTargetsFlag: gvtm_synthesize_targets_device) in every
 // single-voice shape of one, two and four rows, and the check kernel that runs in front of it.  A translation unit, and so a
 // code object, of its own: the code object of vtm_kernels.hip keeps exactly the kernels it had, and the two compile side by
-// side.  The shapes are vtm_kernel_shapes.hpp's, the one table.
+// side.  The shapes and their launch are vtm_kernel_shapes.hpp's, the one table and the one launch_v2: this unit is its
+// check kernel and one launch_v2_variant<kTargetsFlag> call.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -22,29 +23,6 @@ namespace {
 #include "vtm_kernel_shapes.hpp"
 
 namespace {
-
-// launch_v2 of vtm_kernels.hip for the targets variant: the same checks of the ring, the same LDS, one workgroup per S::U utterances
-template <typename S>
-hipError_t launch_v2_targets(const SynthArgs& args, size_t batch, hipStream_t stream)
-{
-	if constexpr (S::U == 8) {
-		// the product's shapes only (eight rows are a diagnostics build's forced shape)
-		return hipErrorInvalidValue;
-	} else {
-		auto fn = v2::vtm_synth_kernel<typename S::CT, typename S::ST, S::D, S::U, S::C, S::NH, S::LAYOUT | v2::kTargetsFlag>;
-		if (args.xr < ring_length(args.k, S::C) || (args.xr & (args.xr - 1)) != 0 || 2 * S::C + 4 * args.k.pad + 64 > args.xr) return hipErrorInvalidValue;
-		if (!args.k.upsampling && args.xr != kSrcRing) return hipErrorInvalidValue;
-		if constexpr (v2::float_arg_consts<typename S::CT, S::D, S::U, false>()) {
-			if (args.fir_k.f[kFirKConsts + kKfBasicIncrement] != static_cast<float>(args.k.basic_increment)) return hipErrorInvalidValue;
-		}
-		const size_t lds = S::lds_bytes(args.xr);
-		hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-		if (e != hipSuccess) return e;
-		const unsigned groups = static_cast<unsigned>((batch + S::U - 1) / S::U);
-		hipLaunchKernelGGL(fn, dim3(groups), dim3(S::kWaves * 64), lds, stream, args);
-		return hipGetLastError();
-	}
-}
 
 // One wavefront per utterance, all 64 lanes active until the store: lanes 0 .. 15 hold the utterance's 16 lists, then all
 // lanes stride over each list's points; every verdict is a ballot, so every lane holds the same status.  The first status
@@ -96,10 +74,7 @@ __global__ __launch_bounds__(64) void vtm_targets_check_kernel(const TargetsChec
 
 hipError_t launch_synth_targets(const SynthArgs& args, size_t batch, int precision, int rows, hipStream_t stream)
 {
-	// (a stream's launch, args.stream, takes the shapes launch_v2 gives a stream of frames: the ring is the stream's, args.xr)
-	if (!args.tg_offsets || !args.tg_steps || !args.tg_values || !args.frame_counts || args.row_map || args.tg_N < 1) return hipErrorInvalidValue;
-	return with_shape(precision, rows, args.k.section_delay, args.k.layout, hipErrorInvalidValue,
-			[&](auto s) { return launch_v2_targets<decltype(s)>(args, batch, stream); });
+	return launch_v2_variant<v2::kTargetsFlag>(args, batch, precision, rows, stream);
 }
 
 hipError_t launch_targets_check(const TargetsCheckArgs& args, hipStream_t stream)

@@ -14,16 +14,16 @@ import json
 import os
 import re
 import shutil
-import subprocess
 import sys
 import tempfile
 
 import pytest
 
+import code_objects
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "gama_tts_amd", "lib", "libgama_vtm.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "codegen_signature.json")
-LLVM = "/opt/rocm/lib/llvm/bin"
 # the shapes the product picks for batch > 512 / <= 256 on the 10 + 6 tube: <CT, ST, SectionDelay, rows, chunk, helpers, layout>
 WATCHED = [
     "float, float, 1, 4, 48, 11, 0", "float, float, 2, 4, 48, 11, 0", "float, float, 1, 1, 144, 3, 0", "float, float, 2, 1, 144, 3, 0",
@@ -34,27 +34,22 @@ WATCHED = [
 
 def signature():
     """{template arguments: {"scratch": bytes per lane, "vgpr_spill": n, "vgprs": n}} of every vtm_synth_kernel in the library."""
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
-    if not os.path.exists(LIB) or not all(os.path.exists(t) for t in tools):
+    if not os.path.exists(LIB) or not code_objects.tools_present():
         return None
     with tempfile.TemporaryDirectory() as wd:
-        fat, co = os.path.join(wd, "fat.bin"), os.path.join(wd, "k.co")
-        subprocess.run([tools[0], "-O", "binary", "--only-section=.hip_fatbin", LIB, fat], check=True)
-        subprocess.run([tools[1], "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co, "--unbundle"], check=True)
-        notes = subprocess.run([tools[2], "--notes", co], check=True, capture_output=True, text=True).stdout
+        kernels = code_objects.kernel_notes(code_objects.unbundle(LIB, wd))
     out = {}
-    for block in notes.split("- .agpr_count:")[1:]:
-        name = re.search(r"\.name:\s+(\S+)", block)
-        if not name or "vtm_synth_kernel" not in name.group(1):
+    for name, block in kernels:
+        if "vtm_synth_kernel" not in name:
             continue
         # _ZN4gvtm2v216vtm_synth_kernelIffLi2ELi4ELi48ELi11ELi0EEEv...: two type letters, five integers
-        m = re.search(r"vtm_synth_kernelI([fd])([fd])Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEE", name.group(1))
+        m = re.search(r"vtm_synth_kernelI([fd])([fd])Li(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)EEE", name)
         if not m:
             continue
         ty = {"f": "float", "d": "double"}
         args = ", ".join([ty[m.group(1)], ty[m.group(2)]] + [m.group(i) for i in range(3, 8)])
-        num = lambda key: int(re.search(r"\.%s:\s+(\d+)" % key, block).group(1))  # noqa: E731
-        out[args] = {"scratch": num("private_segment_fixed_size"), "vgpr_spill": num("vgpr_spill_count"), "vgprs": num("vgpr_count")}
+        d = code_objects.descriptor(block)
+        out[args] = {"scratch": d["private_segment_fixed_size"], "vgpr_spill": d["vgpr_spill_count"], "vgprs": d["vgpr_count"]}
     return out
 
 

@@ -10,6 +10,8 @@ behind a row's count must still be the pattern), and the plans the entry does no
 
 The lists are spoken (targets_cases.spoken_lists): key values of a random utterance at steps that are multiples of nothing in
 the kernel; wide values (six decades apart in one window) go on fricCF and fricBW only, positive."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -253,3 +255,41 @@ def test_unsupported_plans():
         rc = plan._lib.gvtm_synthesize_targets_device(plan._h, capi._ptr(d_offsets), 16, None, capi._ptr(d_steps), capi._ptr(d_values), None, 1, 10,
                                                       capi._ptr(d_audio), stride, None, None, None, None)
         assert rc == UNSUPPORTED
+
+
+# ---- h. eight rows forced ----
+
+def test_forced_eight_rows_on_the_frames_and_the_targets_entry():
+    """Eight utterances per workgroup are the one point where the variants of vtm_synth_kernel differ in their launch
+    (csrc/vtm_kernel_shapes.hpp: launch_v2): the frames variant of one voice has the kernel, every other variant would refuse
+    the shape with hipErrorInvalidValue ahead of any launch.  Through the C ABI that refusal is not reached: the eight-row
+    shape of a float male plan needs 169 072 bytes of LDS, more than a workgroup has (160 KB), so the one row choice
+    (synth_launch_shape) halves the forced rows for every entry alike.  Read on the build before launch_v2 became one
+    function: the targets entry returns status 0 and synthesizes in four rows, as the frames entry does; this pins both,
+    to the bytes of the one-row shape."""
+    eight = male_plan(precision=capi.PRECISION_F32, rows=8)
+    shape = (ctypes.c_size_t * 3)()
+    assert eight._lib.gvtm_debug_launch_shape(eight._h, 2, 0, shape) == 0
+    assert shape[0] == 4 and shape[2] <= 160 * 1024 < eight._lib.gvtm_debug_lds_bytes(eight._h, 8)
+    step_counts = [24, 24]
+    utterances = [host_frames(eight, "male", seed, 24)[0] for seed in (0, 1)]
+    audio, counts, maxabs, statuses = run(eight, utterances, step_counts)  # (raises on a status other than 0)
+    one = run(male_plan(precision=capi.PRECISION_F32), utterances, step_counts)
+    assert not statuses.any() and not one[3].any()
+    assert counts.tolist() == one[1].tolist() == [eight.targets_output_count(24)] * 2 and maxabs.tobytes() == one[2].tobytes()
+    assert audio.tobytes() == one[0].tobytes() and guard_behind_counts(audio, counts)
+    # the frames entry with eight rows forced, one step per frame: the same shape, the same bytes
+    rate = eight.info.internal_rate_hz
+    frames8 = male_plan(precision=capi.PRECISION_F32, crate=rate, rows=8)
+    assert frames8.info.control_steps == 1 and chunk_of(frames8, 2) == chunk_of(eight, 2) == 48
+    stride = frames8.output_capacity(24)
+    assert stride == audio.shape[1]
+    params = np.stack([host_frames(eight, "male", seed, 24)[1] for seed in (0, 1)]).astype(np.float32)
+    d_params, d_frames = to_device(params, np.asarray(step_counts, dtype=np.int32))
+    d_audio, d_counts, d_maxabs = filled((2, stride * 4), GUARD, np.uint8), filled(2, -7, np.int64), filled(2, 5.0, np.float32)
+    frames8.synthesize_device(d_params, 2, 24, d_audio, stride, d_frames, d_counts, d_maxabs, current_stream())
+    f_audio, f_counts, f_maxabs = to_host(d_audio, d_counts, d_maxabs)
+    assert f_counts.tolist() == counts.tolist() and f_maxabs.tobytes() == maxabs.tobytes()
+    f_audio = f_audio.view(np.float32).reshape(2, stride)
+    for b in range(2):
+        assert f_audio[b, : counts[b]].tobytes() == audio[b, : counts[b]].tobytes(), b
