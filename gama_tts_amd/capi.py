@@ -185,6 +185,7 @@ def _prototypes():
         "gvtm_targets_apply_host": (i, [vp, i, vp, vp, vp, i64, vp, vp]),
         "gvtm_targets_apply_host_from": (i, [vp, i, vp, vp, vp, i64, i64, vp, vp, vp]),
         "gvtm_synthesize_targets_device": (i, [vp, vp, sz, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
+        "gvtm_synthesize_targets_model5_device": (i, [vp, vp, sz, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
         "gvtm_targets_voice_output_count": (sz, [vp, i, sz]),
         "gvtm_targets_voices_output_capacity": (sz, [vp, sz]),
         "gvtm_synthesize_targets_voices_device": (i, [vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
@@ -928,6 +929,15 @@ class Plan:
         """Target lists (the tables of pack_targets; d_list_ids None: utterance b's parameter p walks list 16 b + p) in,
         samples out (gvtm_synthesize_targets_device); all pointers are device memory."""
         self._check(self._lib.gvtm_synthesize_targets_device(
+            self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
+            int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status), _ptr(stream)))
+
+    def synthesize_targets_model5_device(self, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, batch, max_steps,
+                                         d_audio, audio_stride, d_out_counts=None, d_maxabs=None, d_status=None, stream=None):
+        """synthesize_targets_device for a one-voice model 5 plan of either class (gvtm_synthesize_targets_model5_device): the
+        samples of the model as the interactive window constructs it, each step's signal divided by its f0.  All pointers are
+        device memory."""
+        self._check(self._lib.gvtm_synthesize_targets_model5_device(
             self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
             int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status), _ptr(stream)))
 

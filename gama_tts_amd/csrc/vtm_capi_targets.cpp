@@ -1,5 +1,6 @@
 // C ABI of libgama_vtm.so, synthesis from parameter targets (the editor's interactive window): the filter length, the sample
-// counts by internal steps, the rule on the host, and the two device entries (one voice; a voice id per utterance), which put
+// counts by internal steps, the rule on the host, and the three device entries (one voice of the models 0 to 4; a voice id per
+// utterance; one voice of model 5, whose kernel also divides each step's signal by its f0 as the interactive model does), which put
 // the synthesis launch -- the kernel's targets driver, launch_synthesis with LaunchRequest::targets -- behind the check kernel
 // with the plan's step counts in between.
 #include "vtm_host.hpp"
@@ -143,6 +144,25 @@ int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offset
 	}
 	if (plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_device: a plan of one voice only (gvtm_synthesize_targets_voices_device takes several)");
 	if (plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_device: the models 0 to 4 only");
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
+	if (batch == 0) return GVTM_OK;
+	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, nullptr, batch, max_steps, d_audio, audio_stride,
+			d_out_counts, d_maxabs, d_status, hip_stream);
+}
+
+int gvtm_synthesize_targets_model5_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
+		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, size_t batch, size_t max_steps, float* d_audio,
+		size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (batch > 0) {
+		if (const int rc = check_batch_arguments(d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, batch, max_steps, d_audio); rc != GVTM_OK) return rc;
+		if (audio_stride < steps_output_capacity(plan->designs[0], max_steps)) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_targets_output_capacity(plan, max_steps)");
+		}
+	}
+	if (plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_model5_device: a plan of one voice only");
+	if (!plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_model5_device: model 5 only (gvtm_synthesize_targets_device takes the models 0 to 4)");
 	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
 	if (batch == 0) return GVTM_OK;
 	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, nullptr, batch, max_steps, d_audio, audio_stride,

@@ -170,9 +170,10 @@ struct gvtm_plan {
 
 	int n_voices() const { return static_cast<int>(designs.size()); }
 	// the shape of a launch of `batch` utterances (vtm_kernels.hpp: synth_launch_shape; forced_rows 0: the plan's own)
-	gvtm::LaunchShape launch_shape(size_t batch, int forced_rows, bool voices, int stream_ring = 0, bool fit = true) const
+	// (targets: a launch from parameter targets, which model 5 has shapes of its own for)
+	gvtm::LaunchShape launch_shape(size_t batch, int forced_rows, bool voices, int stream_ring = 0, bool fit = true, bool targets = false) const
 	{
-		return gvtm::synth_launch_shape(designs.data(), n_voices(), precision, batch, forced_rows ? forced_rows : rows, voices, stream_ring, fit);
+		return gvtm::synth_launch_shape(designs.data(), n_voices(), precision, batch, forced_rows ? forced_rows : rows, voices, stream_ring, fit, targets);
 	}
 	// the ring a stream keeps for voice v (not model 5): the one-row shape's, whatever shape a launch of the stream takes
 	int stream_ring(int v) const { return gvtm::synth_launch_shape(&designs[v], 1, precision, 1, 1, false).ring; }

@@ -1,8 +1,9 @@
 // Reference model 5 (VocalTractModel5<double,1>, vtm/VocalTractModel5.h) on the device.
 // Included inside namespace gvtm, after vtm_kernel_v2.inc (whose wave-wide DPP helpers, Extent and voice_row it shares),
-// by four translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
-// (kVoices5Flag), vtm_kernels_m5f.hip the float class, VocalTractModel5<float,1> (kFloat5Flag), and vtm_kernels_m5fv.hip
-// the voice variant of the float class (both flags), each in a code object of its own.  Besides the kernel, the file
+// by six translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
+// (kVoices5Flag), vtm_kernels_m5f.hip the float class, VocalTractModel5<float,1> (kFloat5Flag), vtm_kernels_m5fv.hip
+// the voice variant of the float class (both flags), vtm_kernels_m5t.hip and vtm_kernels_m5ft.hip the targets variant
+// (kTargets5Flag) of the double and of the float class, each in a code object of its own.  Besides the kernel, the file
 // defines what they launch it with: the description of its shapes (m5_shape,
 // kM5Ring), before the kernel, and the LDS bytes and the launch of a shape (m5_lds_bytes, launch_synth5_shape), at the end.
 //
@@ -55,6 +56,19 @@ constexpr M5Shape m5_shape(bool float_class, int index)
 	if (float_class) return index == 1 ? M5Shape{1, 56, 3, m5_waves(1, 3), 2} : M5Shape{1, 60, 3, m5_waves(1, 3), 1};
 	return index == 1 ? M5Shape{2, 24, 5, m5_waves(2, 5), 1} : M5Shape{1, 60, 3, m5_waves(1, 3), 1};
 }
+// The targets variant (kTargets5Flag below) carries one more LDS record, f0 from pass A1a to pass X: eleven slots of a chunk.
+// Its shapes, by the same (class, index), are the four above wherever the record fits the budget the shape was chosen by:
+// the double class's one-utterance shape (158 928 B) has 4 912 B left of a workgroup's 160 KB where the record takes 5 280 B,
+// so its chunk is the next multiple of four, 56 (156 016 B with the record); the two-utterance shape keeps 24 (152 560 B).
+// The float class's index 0 keeps 60 (one workgroup per compute unit: 87 632 B); index 1, which two workgroups per compute
+// unit define, has 1 120 B left of 80 KB with a chunk of 56 where the record takes 2 464 B, and takes the next multiple of
+// four, 52 (78 896 B).
+constexpr M5Shape m5_targets_shape(bool float_class, int index)
+{
+	if (float_class) return index == 1 ? M5Shape{1, 52, 3, m5_waves(1, 3), 2} : M5Shape{1, 60, 3, m5_waves(1, 3), 1};
+	return index == 1 ? M5Shape{2, 24, 5, m5_waves(2, 5), 1} : M5Shape{1, 56, 3, m5_waves(1, 3), 1};
+}
+constexpr M5Shape m5_shape_of(bool float_class, int index, bool targets) { return targets ? m5_targets_shape(float_class, index) : m5_shape(float_class, index); }
 constexpr int kM5Ring = kSrcRing; // the reference's BUFFER_SIZE: see the flush-overrun epilogue
 
 namespace m5 {
@@ -76,9 +90,11 @@ constexpr int kRkMouth = 0, kRkJ = 5, kRkNk = 12, kRkVl = 13, kRkNVl = 14, kRkNV
 constexpr int kRfr = 4; // A1b record: frication amplitude, left share, right share, first lane
 constexpr int kMouth = 29, kNose = 50, kNasalFirst = 30, kThreeLeft = 11, kThreeRight = 12;
 constexpr int kYr = 512; // ring of converted samples waiting for the difference filter
+constexpr int kF0Slots = 11; // the targets variant's f0 record: written for chunk t - 1 in the tick that reads chunk t - 11
 
-template <int C, int XR, int U = 1, typename R = double>
+template <int C, int XR, int U = 1, typename R = double, bool TARGETS = false>
 struct Offsets {
+	size_t rf0 = 0; // (the targets variant's record alone, behind every other: no other offset moves)
 	size_t kc, k5, ext, kb, src, prm, rd, rm, rst, rn, val, u, pl, rfr, rb0, ra12, inp, fnm, ub, bp, mg, ru, side, ox, rmo, yv, oo, carry, x, y, peak, ticket, diag, dump, total;
 	__host__ __device__ constexpr Offsets()
 		: kc(0), k5(0), ext(0), kb(0), src(0), prm(0), rd(0), rm(0), rst(0), rn(0), val(0), u(0), pl(0), rfr(0), rb0(0), ra12(0), inp(0), fnm(0),
@@ -125,6 +141,7 @@ struct Offsets {
 		ticket = take(sizeof(unsigned) * 4);
 		diag = take(sizeof(unsigned long long) * 10);
 		dump = take(D * 64 * 2);
+		if (TARGETS) rf0 = take(U * (D * kF0Slots * C)); // f0                               A1a -> X      (c % 11)
 		total = off;
 	}
 };
@@ -149,6 +166,14 @@ constexpr int kVoices5Flag = 4;
 // stays double (NoiseSource.h:41-54).  With R = double every R(...) below is the identity, so the double kernels are
 // the code they were.
 constexpr int kFloat5Flag = 8;
+// The model as the editor's interactive window runs it (gvtm_synthesize_targets_model5_device; instantiated by
+// vtm_kernels_m5t.hip and, with kFloat5Flag, vtm_kernels_m5ft.hip alone): VocalTractModel5<T,1>(config, interactive = true)
+// fed parameter targets.  The flag kTargets5Flag in the same argument changes two things.  The interpolation wavefront walks
+// the moving averages of the utterance's sixteen target lists (vtm_targets.hpp) instead of interpolating frames: a.frame_counts
+// holds steps, there are no frames and no control_steps.  And what enters the resampler is divided by the step's
+// fundamental frequency (VocalTractModel5.h:579): pass A1a keeps the f0 it forms for dt in the record rf0, which pass X
+// reads ten ticks later.  One voice, one-shot launches only.  Every difference is a conditional on the constant TARGETS.
+constexpr int kTargets5Flag = 16;
 __device__ __forceinline__ double sin_m5(double t) { return sin(t); }
 __device__ __forceinline__ float sin_m5(float t) { return vmath::sinf_glibc(t); } // std::sin(float), RosenbergBGlottalSource.h:139
 
@@ -158,7 +183,7 @@ __device__ __forceinline__ float sin_m5(float t) { return vmath::sinf_glibc(t); 
 constexpr int m5_waves_per_simd(int chunk, int u_flags)
 {
 	for (int index = 0; index < 2; ++index) {
-		const M5Shape s = m5_shape((u_flags & kFloat5Flag) != 0, index);
+		const M5Shape s = m5_shape_of((u_flags & kFloat5Flag) != 0, index, (u_flags & kTargets5Flag) != 0);
 		if (s.chunk == chunk && s.groups_per_cu > 1) return (s.groups_per_cu * s.waves + 3) / 4;
 	}
 	return 1;
@@ -170,10 +195,12 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 	constexpr int U = U_FLAGS & 3;
 	constexpr bool VOICES = (U_FLAGS & kVoices5Flag) != 0;
 	constexpr bool FLOAT = (U_FLAGS & kFloat5Flag) != 0;
+	constexpr bool TARGETS = (U_FLAGS & kTargets5Flag) != 0;
 	using R = std::conditional_t<FLOAT, float, double>;
 	using R2 = typename Pair<R>::type;
 	static_assert(!FLOAT || U == 1, "the float class has the one-utterance shape only");
 	static_assert(!VOICES || U == 1, "the voice variant has the one-utterance shape only");
+	static_assert(!TARGETS || !VOICES, "the targets variant has one voice");
 	int voice = 0;
 	if constexpr (VOICES) {
 		voice = a.group_voice[blockIdx.x];
@@ -190,7 +217,9 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 	              kN_ox = 2 * C * 2, kN_rmo = 4 * C * 3, kN_yv = 2 * (C + 2) * 4, kN_oo = 2 * C * 2, kN_carry = 4;
 
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-	constexpr Offsets<C, XR, U, R> so;
+	constexpr Offsets<C, XR, U, R, TARGETS> so;
+	[[maybe_unused]] constexpr int kN_rf0 = kF0Slots * C;
+	[[maybe_unused]] R* const s_rf0 = reinterpret_cast<R*>(smem_raw + so.rf0); // (the targets variant's alone)
 	DeviceConstants* const s_kc = reinterpret_cast<DeviceConstants*>(smem_raw + so.kc);
 	Model5Constants* const s_k5 = reinterpret_cast<Model5Constants*>(smem_raw + so.k5);
 	Extent* const s_ext = reinterpret_cast<Extent*>(smem_raw + so.ext);
@@ -283,7 +312,8 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 			const size_t rows_avail = a.max_frames - (kPush ? 1 : 0);
 			const int f = a.frame_counts ? a.frame_counts[ug] : static_cast<int>(rows_avail);
 			e.frames = f > 0 ? (static_cast<size_t>(f) < rows_avail ? f : static_cast<int>(rows_avail)) : 0;
-			e.steps = static_cast<uint32_t>(e.frames) * k.control_steps;
+			if constexpr (TARGETS) e.steps = static_cast<uint32_t>(e.frames); // (a.frame_counts holds steps; a refused utterance's: 0)
+			else e.steps = static_cast<uint32_t>(e.frames) * k.control_steps;
 			e.nchunks = e.steps == 0 ? 1 : static_cast<int>((e.steps + C - 1) / C);
 			e.last_frame = e.frames - 1 + (kPush ? 1 : 0);
 			if (streaming) {
@@ -362,6 +392,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 		const R ga = amplitude_60db_dev(gv);
 		R* rd = s_rd + u * kN_rd + (static_cast<size_t>(c & 1) * (C + 4) + s) * 2;
 		rd[0] = f0 / R(k5.sample_rate);
+		if constexpr (TARGETS) s_rf0[u * kN_rf0 + (c % kF0Slots) * C + s] = f0; // what pass X divides the step's signal by
 		// the amplitude-dependent end of the falling phase: a pure function of the amplitude (setup() skips the
 		// assignment only when it would store the same value)
 		rd[1] = (R(k5.rb_tn_min) == R(k5.rb_tn_max)) ? R(k5.rb_t1) + R(k5.rb_tn_max)
@@ -600,7 +631,10 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 				const uint32_t n0 = static_cast<uint32_t>(s_ext[u].step_base) + static_cast<uint32_t>(c) * C; // ring slots go by the stream's sample number
 				const R* oo = s_oo + u * kN_oo + (static_cast<size_t>(c & 1) * C + s) * 2;
 				const R v = k5.bypass ? s_inp[u * kN_inp + (c % 7) * C + s] : oo[0] + oo[1];
-				s_x[u * XR + ((n0 + s) & (XR - 1))] = v;
+				// (interactive_: signal / f0, one correctly rounded division in R, VocalTractModel5.h:579; the flush's zeros below
+				// are the converter's own and are not divided)
+				if constexpr (TARGETS) s_x[u * XR + ((n0 + s) & (XR - 1))] = v / s_rf0[u * kN_rf0 + (c % kF0Slots) * C + s];
+				else s_x[u * XR + ((n0 + s) & (XR - 1))] = v;
 			}
 		}
 		if (kFinal) {
@@ -779,8 +813,18 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 	const int ip_u = lane >> 4; // lanes 16u .. 16u + 15 interpolate utterance u
 	const int ip_frames = ip_u < U ? s_ext[ip_u].frames : 0;
 	const int ip_last = ip_u < U ? s_ext[ip_u].last_frame : 0; // last readable row: frames - 1, or the look-ahead frame of a push
-	const float* __restrict__ P = a.params + GVTM_M5_UTT(0, (group * U + (ip_u < U ? ip_u : 0))) * a.max_frames * 16;
-	if (role == 3 && ip_u < U && ip_frames > 0) {
+	const float* __restrict__ P = TARGETS ? nullptr : a.params + GVTM_M5_UTT(0, (group * U + (ip_u < U ? ip_u : 0))) * a.max_frames * 16;
+	// I, from targets (kTargets5Flag): lane 16u + p walks the points of utterance u's list for parameter p (vtm_targets.hpp): the
+	// filter's sum, the entering and the leaving value, the two cursors and the steps at which they move next.  (A refused
+	// utterance and a row beyond the batch have 0 steps: their list ids and offsets are never read.)
+	[[maybe_unused]] TargetsWalk tg{};
+	if constexpr (TARGETS) {
+		if (role == 3 && ip_u < U && ip_frames > 0) {
+			const size_t slot = (group * U + ip_u) * GVTM_N_PARAM + Lp;
+			const int64_t list = a.tg_ids ? static_cast<int64_t>(a.tg_ids[slot]) : static_cast<int64_t>(slot);
+			targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N);
+		}
+	} else if (role == 3 && ip_u < U && ip_frames > 0) {
 		ip_this = P[Lp];
 		ip_next = P[static_cast<size_t>(ip_last > 1 ? 1 : ip_last) * 16 + Lp];
 		ip_next2 = P[static_cast<size_t>(ip_last > 2 ? 2 : ip_last) * 16 + Lp];
@@ -793,6 +837,27 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 		const int valid = valid_in(ip_u, c);
 		if (valid <= 0) return;
 		float* out = s_prm + ip_u * kN_prm + static_cast<size_t>(c & 1) * C * 16 + Lp;
+		if constexpr (TARGETS) {
+			// The second driver, as vtm_kernel_v2.inc has it: the moving average of the lane's target list, step by step, in blocks
+			// of four steps.  The cursors' bookkeeping only runs for a block in which some lane's cursor moves (a point enters, or
+			// leaves N steps later); every other block is four times {two double additions, a multiplication, a conversion, a
+			// store}.  A partial last block runs on: no cursor passes the end of its list, and the extra rows are never read
+			// (valid <= C, a multiple of four: they stay inside the chunk's slot).
+			const int64_t first = static_cast<int64_t>(c) * C;
+			for (int s0 = 0; s0 < valid; s0 += 4) {
+				if (__builtin_expect(__any(targets_moves(tg, first + s0, 4)), 0)) {
+#pragma unroll
+					for (int q = 0; q < 4; ++q) {
+						targets_move(tg, first + s0 + q, a.tg_steps, a.tg_values, a.tg_N);
+						out[(s0 + q) * 16] = targets_step(tg, a.tg_invN);
+					}
+				} else {
+#pragma unroll
+					for (int q = 0; q < 4; ++q) out[(s0 + q) * 16] = targets_step(tg, a.tg_invN);
+				}
+			}
+			return;
+		}
 		const uint32_t cs = k.control_steps;
 		const float coef = k.interp_coef;
 		for (int s = 0; s < valid; ++s) {
@@ -1291,23 +1356,26 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 } // namespace m5
 
 // LDS bytes of a workgroup of shape (FLOAT, INDEX)
-template <bool FLOAT, int INDEX>
+template <bool FLOAT, int INDEX, bool TARGETS = false>
 static size_t m5_lds_bytes()
 {
-	constexpr M5Shape s = m5_shape(FLOAT, INDEX);
-	return m5::Offsets<s.chunk, kM5Ring, s.rows, std::conditional_t<FLOAT, float, double>>().total;
+	constexpr M5Shape s = m5_shape_of(FLOAT, INDEX, TARGETS);
+	return m5::Offsets<s.chunk, kM5Ring, s.rows, std::conditional_t<FLOAT, float, double>, TARGETS>().total;
 }
 
 // The launch of shape (FLOAT, INDEX).  VOICES: a launch of several voices (the kernel's kVoices5Flag; args.row_map is
 // set), a one-utterance shape only (the double class's, either of the float class's); `batch` is then the number of
-// workgroups
-template <bool FLOAT, int INDEX, bool VOICES = false>
+// workgroups.  TARGETS: a launch from parameter targets (the kernel's kTargets5Flag; args.tg_offsets is set), in the shape
+// (FLOAT, INDEX) of m5_targets_shape, one voice only
+template <bool FLOAT, int INDEX, bool VOICES = false, bool TARGETS = false>
 static hipError_t launch_synth5_shape(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
-	constexpr M5Shape s = m5_shape(FLOAT, INDEX);
+	constexpr M5Shape s = m5_shape_of(FLOAT, INDEX, TARGETS);
 	static_assert(!VOICES || s.rows == 1, "the voice variant has the one-utterance shapes only");
-	auto fn = m5::vtm5_synth_kernel<s.chunk, s.helpers, kM5Ring, s.rows | (VOICES ? m5::kVoices5Flag : 0) | (FLOAT ? m5::kFloat5Flag : 0)>;
-	const size_t lds = m5_lds_bytes<FLOAT, INDEX>();
+	static_assert(!VOICES || !TARGETS, "the targets variant has one voice");
+	auto fn = m5::vtm5_synth_kernel<s.chunk, s.helpers, kM5Ring,
+			s.rows | (VOICES ? m5::kVoices5Flag : 0) | (FLOAT ? m5::kFloat5Flag : 0) | (TARGETS ? m5::kTargets5Flag : 0)>;
+	const size_t lds = m5_lds_bytes<FLOAT, INDEX, TARGETS>();
 	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(VOICES ? batch : (batch + s.rows - 1) / s.rows)), dim3(s.waves * 64), lds, stream, args);

@@ -187,9 +187,10 @@ constexpr size_t kLdsPerWorkgroup = 160 * 1024;
 // BUFFER_SIZE (1024) when down-sampling, so that the flush overrun aliases as the reference's ring does; otherwise the
 // smallest power of two holding two chunks, the resampler's history and the flush zeros).  With `fit`, rows whose LDS
 // exceeds kLdsPerWorkgroup give way to half as many (not model 5) or to "none fits"; without, they stay whatever their LDS.
+// targets: a launch from parameter targets; it changes the answer for model 5 alone, whose targets variant has shapes of its
+// own by the same index (vtm_kernel_m5.inc: m5_targets_shape; one voice).
 LaunchShape synth_launch_shape(const Design* voices, int n_voices, int precision, size_t batch, int forced_rows, bool several_voices,
-		int stream_ring = 0, bool fit = true);
-// the chunk length (internal steps per tick) of a shape, which its own ring length follows; 0: no such shape
+		int stream_ring = 0, bool fit = true, bool targets = false);// the chunk length (internal steps per tick) of a shape, which its own ring length follows; 0: no such shape
 int synth_chunk_length(const DeviceConstants& k, int precision, int rows);
 // which of its serial filter stages a single-voice shape runs with the feed-forward half 64 steps at a time
 // (v2::filter_split_f2: bit 0, the post-tube filters); 0: none, or no such shape
@@ -220,6 +221,16 @@ size_t synth5_float_lds_bytes(int index);
 hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_t stream);
 // the voice variant of the float class alone (vtm_kernels_m5fv.hip; launch_synth5 calls it), in the float class's shape `index`
 hipError_t launch_synth5_float_voices(const SynthArgs& args, size_t groups, int index, hipStream_t stream);
+// the targets variants alone (vtm_kernels_m5t.hip: the double class; vtm_kernels_m5ft.hip: the float class; launch_synth5
+// calls them where args.tg_offsets is set), in the shape `index` of the class's targets shapes (m5_targets_shape): one voice,
+// one-shot launches
+hipError_t launch_synth5_targets(const SynthArgs& args, size_t batch, int index, hipStream_t stream);
+hipError_t launch_synth5_float_targets(const SynthArgs& args, size_t batch, int index, hipStream_t stream);
+// what both ask of their arguments: the lists, the steps in frame_counts, the filter's length; no row map, no stream
+inline bool synth5_targets_args(const SynthArgs& args)
+{
+	return args.k5const && args.tg_offsets && args.tg_steps && args.tg_values && args.frame_counts && args.tg_N >= 1 && !args.row_map && !args.stream;
+}
 constexpr int kDppSelftestInts = 640;
 hipError_t launch_dpp_selftest(int* d_out /* [kDppSelftestInts] */, hipStream_t stream);
 hipError_t launch_float_math_probe(int kind, const float* d_x, size_t n, float* d_out, hipStream_t stream);

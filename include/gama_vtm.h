@@ -1013,6 +1013,26 @@ int gvtm_synthesize_targets_voices_device(gvtm_plan* plan, const int64_t* d_list
 		const int32_t* d_voice_ids, size_t batch, size_t max_steps, float* d_audio, size_t audio_stride,
 		int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream);
 
+/* gvtm_synthesize_targets_device for reference model 5, as the interactive window runs it: one-voice plans of
+ * gvtm_plan_create_model5 (VocalTractModel5<double,1>) and gvtm_plan_create_model5_float (VocalTractModel5<float,1>).
+ * Every argument, the statuses 0 to 4 and the sample counts (gvtm_targets_output_count / _capacity) are that entry's.
+ * The rule for model 5: utterance b's samples are those of VocalTractModel5<T,1>(config, interactive = true) fed
+ * v[s][0..16) of gvtm_targets_apply_host by setParameter before step s, s = 0 .. S_b - 1, then finishSynthesis(): in the
+ * float class bit for bit, in the double class within the model 5 parity bar.  They are therefore NOT those of
+ * gvtm_synthesize_batch_device on the same frames at one step per frame: a model constructed for the interactive window
+ * divides each step's tube output by that step's fundamental frequency before the sample-rate converter
+ * (vtm/VocalTractModel5.h:579, compensating the difference filter at the output), which the batch protocol's model does not.
+ * Enqueue-only: the check kernel and the synthesis launch on hip_stream, nothing else.  The call uses the plan's step-count
+ * scratch: calls on one plan must be ordered on one stream.  Refused before any device work, in this order: a null plan;
+ * with batch > 0 what gvtm_synthesize_targets_device refuses (GVTM_ERR_INVALID_ARGUMENT); a plan of several voices or a
+ * plan of the models 0 to 4, which have gvtm_synthesize_targets_device (GVTM_ERR_UNSUPPORTED); a design-only plan
+ * (GVTM_ERR_NO_DEVICE), with batch == 0 too; on a plan with a device batch == 0 returns GVTM_OK.  Model 5 targets under
+ * several voices and in streams are not available. */
+int gvtm_synthesize_targets_model5_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
+		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, size_t batch,
+		size_t max_steps, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status,
+		void* hip_stream);
+
 /*
  * Streams fed parameter targets: the interactive window as a session.  Targets arrive while the audio is playing, so a
  * stream of gvtm_stream_create takes them push by push; the filters run in the synthesis kernel and their 16 sums travel in
