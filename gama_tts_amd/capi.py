@@ -190,6 +190,7 @@ def _prototypes():
         "gvtm_targets_voices_output_capacity": (sz, [vp, sz]),
         "gvtm_synthesize_targets_voices_device": (i, [vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
         "gvtm_stream_push_targets": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "gvtm_stream_push_targets_model5": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
         "gvtm_stream_targets_capacity": (sz, [vp, sz]),
         "gvtm_stream_targets_points": (i, [vp, vp]),
         "gvtm_stream_push_events": (i, [vp, vp, vp, vp, vp, sz, vp, vp]),
@@ -1166,6 +1167,14 @@ class Stream:
         first step this push adds; step_counts: the steps each utterance advances by (an int: all of them by that many) ->
         list of float32 arrays, the new samples of each utterance.  A refused push raises GvtmError, whose `statuses` are
         the utterances' (int32 [batch])."""
+        return self._push_targets(self._lib.gvtm_stream_push_targets, utterances, step_counts, max_steps)
+
+    def push_targets_model5(self, utterances, step_counts, max_steps=None):
+        """push_targets for a stream of a one-voice model 5 plan of either class (gvtm_stream_push_targets_model5): the samples
+        are the interactive window's model's, in pieces of gvtm_synthesize_targets_model5_device's."""
+        return self._push_targets(self._lib.gvtm_stream_push_targets_model5, utterances, step_counts, max_steps)
+
+    def _push_targets(self, entry, utterances, step_counts, max_steps):
         assert len(utterances) == self.batch and all(len(u) == N_PARAM for u in utterances)
         counts_in = None if isinstance(step_counts, int) else np.ascontiguousarray(step_counts, dtype=np.int32)
         assert counts_in is None or counts_in.shape == (self.batch,)
@@ -1176,8 +1185,7 @@ class Stream:
         audio = np.zeros((self.batch, stride), dtype=np.float32)
         counts = np.zeros(self.batch, dtype=np.int64)
         statuses = np.full(self.batch, -1, dtype=np.int32)
-        rc = self._lib.gvtm_stream_push_targets(self._h, _ptr(offsets), _ptr(steps), _ptr(values), _ptr(counts_in), int(max_steps), _ptr(audio), stride,
-                                                _ptr(counts), _ptr(statuses))
+        rc = entry(self._h, _ptr(offsets), _ptr(steps), _ptr(values), _ptr(counts_in), int(max_steps), _ptr(audio), stride, _ptr(counts), _ptr(statuses))
         if rc != 0:
             error = GvtmError(rc, self._lib.gvtm_last_error().decode() or self._lib.gvtm_status_string(rc).decode())
             error.statuses = statuses

@@ -170,8 +170,8 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
 	if (r.voices && !r.voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
 	if (r.targets && !r.frame_counts) return fail(GVTM_ERR_UNSUPPORTED, "targets: a launch with step counts");
-	// (model 5 from targets: gvtm_synthesize_targets_model5_device's one-voice, one-shot launch alone)
-	if (r.targets && plan->designs[0].model5 && (r.voices || r.sl)) return fail(GVTM_ERR_UNSUPPORTED, "targets: model 5 in a one-shot launch of one voice only");
+	// (model 5 from targets: one voice, gvtm_synthesize_targets_model5_device's one-shot launch or a stream's)
+	if (r.targets && plan->designs[0].model5 && r.voices) return fail(GVTM_ERR_UNSUPPORTED, "targets: model 5 in a launch of one voice only");
 	// (several voices: a one-shot launch, with the plan's filter lengths by voice)
 	if (r.targets && r.voices && (r.sl || !r.targets->voice_N || !r.targets->voice_invN)) return fail(GVTM_ERR_UNSUPPORTED, "targets of several voices: one-shot launches only");
 	if (r.max_frames > 0 && !r.params && !r.targets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
@@ -189,7 +189,7 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 				"gvtm_plan_create_model5_float_voices makes the float plans that have)");
 	}
 	// (a stream's launches are the voice variant's exactly when its plan has several voices: create_stream)
-	const gvtm::LaunchShape shape = r.sl ? plan->stream_launch_shape(r.batch, r.rows, r.sl->xr) : plan->launch_shape(r.batch, r.rows, r.voices, 0, true, r.targets != nullptr);
+	const gvtm::LaunchShape shape = r.sl ? plan->stream_launch_shape(r.batch, r.rows, r.sl->xr, r.targets != nullptr) : plan->launch_shape(r.batch, r.rows, r.voices, 0, true, r.targets != nullptr);
 	if (!shape.rows) return fail(GVTM_ERR_UNSUPPORTED, "LDS budget exceeded");
 	const int rows = shape.rows;
 

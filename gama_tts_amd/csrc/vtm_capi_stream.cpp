@@ -34,15 +34,18 @@ struct gvtm_stream {
 	std::vector<int32_t> counts;
 	bool finished = false;
 	// how the stream has been fed since the last reset: frames (gvtm_stream_push), event lists (gvtm_stream_push_events) or
-	// parameter targets (gvtm_stream_push_targets); one way per run
+	// parameter targets (gvtm_stream_push_targets, model 5: gvtm_stream_push_targets_model5); one way per run
 	int feed = kFeedNone;
 	// a targets-fed run: utterance b's parameter p keeps in tg_log[16 b + p] the points the rule still needs in front of the
 	// utterance's next step (vtm_targets.hpp: targets_first_needed) -- every launch uploads them all, and they are few: those
 	// of the filter's window and of the pending steps, and one more -- and tg_pending[b] steps are pushed but not yet
-	// synthesized (fewer than the granule of 12 after a push).  The filters' sums are in the device state.
+	// synthesized (fewer than tg_granule after a push).  The filters' sums are in the device state.
 	std::vector<TargetsLog> tg_log;
 	std::vector<uint64_t> tg_pending;
 	int64_t tg_N = 0;
+	// a targets-fed run synthesizes in multiples of this many steps and keeps the rest: the steps at which the serial
+	// wavefronts' states are exact (create_stream: 12; model 5: 4)
+	uint64_t tg_granule = 0;
 	DeviceBuffer d_tg_offsets, d_tg_steps, d_tg_values;
 	// an events-fed run keeps its unsynthesized frames on the device: utterance b's in the rows [0, held_rows[b]) of its block
 	// of held_cap rows of d_held ([batch][held_cap][16]; at least one row of a block stays spare: a push's launch reads
@@ -137,11 +140,12 @@ StreamSamples stream_samples(const gvtm_stream* s, const std::vector<size_t>& n_
 	return r;
 }
 
-// a targets-fed run synthesizes in multiples of this many steps (the granule of create_stream, in steps) and keeps the rest
-constexpr uint64_t kTargetsGranule = 12;
+// the most steps a targets-fed run keeps pending after a push, whatever the plan: one short of the largest granule
+// (gvtm_stream::tg_granule), which gvtm_stream_targets_capacity counts on
+constexpr uint64_t kTargetsMostPending = 11;
 constexpr int32_t kTargetsNullTables = -1;
 
-// One utterance of a gvtm_stream_push_targets call, `count` steps of at most max_steps with the 17 offsets `off`: the status
+// One utterance of a gvtm_stream_push_targets or gvtm_stream_push_targets_model5 call, `count` steps of at most max_steps with the 17 offsets `off`: the status
 // of gvtm_targets_apply_host in its order, where a point at or beyond `count` is a bad step too (4); kTargetsNullTables for
 // points without their tables.
 int32_t targets_push_status(const int64_t* off, const int32_t* point_steps, const float* point_values, int64_t count, int64_t max_steps)
@@ -300,6 +304,7 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 				// of four steps (vtm_kernel_m5.inc)
 				s->state_stride = gvtm::Stream5Layout::bytes();
 				s->granule_frames.push_back(4u / gcd_u(k.control_steps, 4u));
+				s->tg_granule = 4; // (a targets-fed run, gvtm_stream_push_targets_model5: the same blocks of four)
 			} else {
 				// each voice's ring is the one-row shape's, whatever shape a launch takes (the kernel derives it per voice)
 				const int xr = plan->stream_ring(v);
@@ -307,6 +312,7 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 				// the serial wavefronts work in blocks of 2, 4 and 4 or 6 steps (vtm_kernel_v2.inc): their states are exact at
 				// multiples of 12 steps, so a push synthesizes a multiple of 12 / gcd(control_steps, 12) frames and keeps the rest
 				s->granule_frames.push_back(12u / gcd_u(k.control_steps, 12u));
+				s->tg_granule = 12;
 			}
 		}
 		s->held.resize(batch);
@@ -398,6 +404,79 @@ int stream_append_and_launch(gvtm_stream* s, const gvtm_event* events, const int
 	return check_device_frame_counts(s->d_new_counts, batch, [&](size_t b) { return fresh[b]; });
 }
 
+// What gvtm_stream_push_targets and gvtm_stream_push_targets_model5 share, which is everything behind the choice of plans:
+// the refusals in their order, the status pass, the roll-back, the log, targets_forget and the launch.  The granule is the
+// stream's (tg_granule).
+int stream_push_targets(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
+		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
+{
+	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
+	if (s->feed == kFeedFrames) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed frames (gvtm_stream_push) until the next gvtm_stream_reset()");
+	if (s->feed == kFeedEvents) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed event lists (gvtm_stream_push_events) until the next gvtm_stream_reset()");
+	if (!list_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null list_offsets");
+	if (!gvtm::targets_fits_step_counter(static_cast<int64_t>(std::min<size_t>(max_steps, INT64_MAX)))) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_steps does not fit the 31-bit step counter");
+	}
+	const size_t batch = s->batch;
+	// every utterance's status first: a refused one refuses the call, and nothing has been touched
+	size_t refused = batch;
+	for (size_t b = 0; b < batch; ++b) {
+		const int64_t count = step_counts ? static_cast<int64_t>(step_counts[b]) : static_cast<int64_t>(max_steps);
+		const int32_t status = targets_push_status(list_offsets + b * GVTM_N_PARAM, point_steps, point_values, count, static_cast<int64_t>(max_steps));
+		if (status == kTargetsNullTables) return fail(GVTM_ERR_INVALID_ARGUMENT, "null point_steps or point_values with points");
+		if (status_out) status_out[b] = status;
+		if (status != gvtm::kTargetsOk && refused == batch) refused = b;
+	}
+	if (refused < batch) return fail(GVTM_ERR_INVALID_ARGUMENT, "utterance " + std::to_string(refused) + " is refused (status_out says why); nothing was pushed");
+	for (size_t b = 0; b < batch; ++b) {
+		const uint64_t count = step_counts ? static_cast<uint64_t>(step_counts[b]) : static_cast<uint64_t>(max_steps);
+		if (s->steps_done[b] + s->tg_pending[b] + count + 4096ull >= (1ull << 31)) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
+	}
+	// a call that fails before its launch leaves the stream as it found it: the points and steps it appended are taken back
+	const int feed_before = s->feed;
+	const std::vector<uint64_t> pending_before = s->tg_pending;
+	std::vector<size_t> held_before(s->tg_log.size(), 0);
+	for (size_t l = 0; l < s->tg_log.size(); ++l) held_before[l] = s->tg_log[l].steps.size();
+	auto roll_back = [&]() {
+		for (size_t l = 0; l < s->tg_log.size(); ++l) {
+			s->tg_log[l].steps.resize(held_before[l]);
+			s->tg_log[l].values.resize(held_before[l]);
+		}
+		s->tg_pending = pending_before;
+		s->feed = feed_before;
+	};
+	try {
+		std::vector<size_t> n(batch, 0);
+		for (size_t b = 0; b < batch; ++b) {
+			// the push's step 0 is the first step the utterance has not been given yet
+			const int64_t base = static_cast<int64_t>(s->steps_done[b] + s->tg_pending[b]);
+			for (int p = 0; p < GVTM_N_PARAM; ++p) {
+				TargetsLog& log = s->tg_log[b * GVTM_N_PARAM + p];
+				for (int64_t j = list_offsets[b * GVTM_N_PARAM + p]; j < list_offsets[b * GVTM_N_PARAM + p + 1]; ++j) {
+					log.steps.push_back(static_cast<int32_t>(base + point_steps[j]));
+					log.values.push_back(point_values[j]);
+				}
+			}
+			s->tg_pending[b] += step_counts ? static_cast<uint64_t>(step_counts[b]) : static_cast<uint64_t>(max_steps);
+			// the serial wavefronts' states are exact at multiples of the granule (create_stream); no step waits for a successor
+			n[b] = static_cast<size_t>(s->tg_pending[b] / s->tg_granule * s->tg_granule);
+		}
+		s->feed = kFeedTargets;
+		bool launched = false;
+		const int rc = stream_launch(s, n, false, audio, audio_stride, out_counts, nullptr, &launched);
+		if (rc != GVTM_OK && !launched) roll_back(); // (after the launch the device state has moved on: gvtm_stream_reset is the way out)
+		if (rc == GVTM_OK) {
+			for (size_t b = 0; b < batch; ++b) {
+				for (int p = 0; p < GVTM_N_PARAM; ++p) targets_forget(s->tg_log[b * GVTM_N_PARAM + p], static_cast<int64_t>(s->steps_done[b]), s->tg_N);
+			}
+		}
+		return rc;
+	} catch (const std::bad_alloc&) {
+		roll_back();
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
+}
+
 } // namespace
 
 extern "C" {
@@ -483,7 +562,7 @@ int gvtm_stream_push(gvtm_stream* s, const float* params, const int32_t* frame_c
 	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
 	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
 	if (s->feed == kFeedEvents) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed event lists (gvtm_stream_push_events) until the next gvtm_stream_reset()");
-	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets) until the next gvtm_stream_reset()");
+	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets, model 5: gvtm_stream_push_targets_model5) until the next gvtm_stream_reset()");
 	if (max_frames > 0 && !params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	if (frame_counts) {
 		for (size_t b = 0; b < s->batch; ++b) {
@@ -542,9 +621,10 @@ int gvtm_stream_finish(gvtm_stream* s, float* audio, size_t audio_stride, int64_
 size_t gvtm_stream_targets_capacity(const gvtm_stream* s, size_t max_new_steps)
 {
 	if (!s) return static_cast<size_t>(-1);
-	// the new steps and what a push can have kept (one short of the granule), flushed, with the overrun's lap
+	// the new steps and what a push can have kept (one short of the largest granule: model 5 keeps 3 at most), flushed, with
+	// the overrun's lap
 	const gvtm::DeviceConstants& k = s->plan->designs[0].k;
-	return static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(max_new_steps) + kTargetsGranule - 1) + 1);
+	return static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(max_new_steps) + kTargetsMostPending) + 1);
 }
 
 int gvtm_stream_targets_points(const gvtm_stream* s, int64_t* held_out)
@@ -563,71 +643,16 @@ int gvtm_stream_push_targets(gvtm_stream* s, const int64_t* list_offsets, const 
 	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
 	if (s->plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets: a plan of one voice only");
 	if (s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets: the models 0 to 4 only");
-	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
-	if (s->feed == kFeedFrames) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed frames (gvtm_stream_push) until the next gvtm_stream_reset()");
-	if (s->feed == kFeedEvents) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed event lists (gvtm_stream_push_events) until the next gvtm_stream_reset()");
-	if (!list_offsets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null list_offsets");
-	if (!gvtm::targets_fits_step_counter(static_cast<int64_t>(std::min<size_t>(max_steps, INT64_MAX)))) {
-		return fail(GVTM_ERR_INVALID_ARGUMENT, "max_steps does not fit the 31-bit step counter");
-	}
-	const size_t batch = s->batch;
-	// every utterance's status first: a refused one refuses the call, and nothing has been touched
-	size_t refused = batch;
-	for (size_t b = 0; b < batch; ++b) {
-		const int64_t count = step_counts ? static_cast<int64_t>(step_counts[b]) : static_cast<int64_t>(max_steps);
-		const int32_t status = targets_push_status(list_offsets + b * GVTM_N_PARAM, point_steps, point_values, count, static_cast<int64_t>(max_steps));
-		if (status == kTargetsNullTables) return fail(GVTM_ERR_INVALID_ARGUMENT, "null point_steps or point_values with points");
-		if (status_out) status_out[b] = status;
-		if (status != gvtm::kTargetsOk && refused == batch) refused = b;
-	}
-	if (refused < batch) return fail(GVTM_ERR_INVALID_ARGUMENT, "utterance " + std::to_string(refused) + " is refused (status_out says why); nothing was pushed");
-	for (size_t b = 0; b < batch; ++b) {
-		const uint64_t count = step_counts ? static_cast<uint64_t>(step_counts[b]) : static_cast<uint64_t>(max_steps);
-		if (s->steps_done[b] + s->tg_pending[b] + count + 4096ull >= (1ull << 31)) return fail(GVTM_ERR_INVALID_ARGUMENT, "a stream holds at most 2^31 internal steps between resets");
-	}
-	// a call that fails before its launch leaves the stream as it found it: the points and steps it appended are taken back
-	const int feed_before = s->feed;
-	const std::vector<uint64_t> pending_before = s->tg_pending;
-	std::vector<size_t> held_before(s->tg_log.size(), 0);
-	for (size_t l = 0; l < s->tg_log.size(); ++l) held_before[l] = s->tg_log[l].steps.size();
-	auto roll_back = [&]() {
-		for (size_t l = 0; l < s->tg_log.size(); ++l) {
-			s->tg_log[l].steps.resize(held_before[l]);
-			s->tg_log[l].values.resize(held_before[l]);
-		}
-		s->tg_pending = pending_before;
-		s->feed = feed_before;
-	};
-	try {
-		std::vector<size_t> n(batch, 0);
-		for (size_t b = 0; b < batch; ++b) {
-			// the push's step 0 is the first step the utterance has not been given yet
-			const int64_t base = static_cast<int64_t>(s->steps_done[b] + s->tg_pending[b]);
-			for (int p = 0; p < GVTM_N_PARAM; ++p) {
-				TargetsLog& log = s->tg_log[b * GVTM_N_PARAM + p];
-				for (int64_t j = list_offsets[b * GVTM_N_PARAM + p]; j < list_offsets[b * GVTM_N_PARAM + p + 1]; ++j) {
-					log.steps.push_back(static_cast<int32_t>(base + point_steps[j]));
-					log.values.push_back(point_values[j]);
-				}
-			}
-			s->tg_pending[b] += step_counts ? static_cast<uint64_t>(step_counts[b]) : static_cast<uint64_t>(max_steps);
-			// the serial wavefronts' states are exact at multiples of 12 steps (create_stream); no step waits for a successor
-			n[b] = static_cast<size_t>(s->tg_pending[b] / kTargetsGranule * kTargetsGranule);
-		}
-		s->feed = kFeedTargets;
-		bool launched = false;
-		const int rc = stream_launch(s, n, false, audio, audio_stride, out_counts, nullptr, &launched);
-		if (rc != GVTM_OK && !launched) roll_back(); // (after the launch the device state has moved on: gvtm_stream_reset is the way out)
-		if (rc == GVTM_OK) {
-			for (size_t b = 0; b < batch; ++b) {
-				for (int p = 0; p < GVTM_N_PARAM; ++p) targets_forget(s->tg_log[b * GVTM_N_PARAM + p], static_cast<int64_t>(s->steps_done[b]), s->tg_N);
-			}
-		}
-		return rc;
-	} catch (const std::bad_alloc&) {
-		roll_back();
-		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
-	}
+	return stream_push_targets(s, list_offsets, point_steps, point_values, step_counts, max_steps, audio, audio_stride, out_counts, status_out);
+}
+
+int gvtm_stream_push_targets_model5(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
+		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
+{
+	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
+	if (s->plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets_model5: a plan of one voice only (the models 0 to 4: gvtm_stream_push_targets)");
+	if (!s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets_model5: model 5 only; the models 0 to 4 have gvtm_stream_push_targets");
+	return stream_push_targets(s, list_offsets, point_steps, point_values, step_counts, max_steps, audio, audio_stride, out_counts, status_out);
 }
 
 int gvtm_stream_push_events(gvtm_stream* s, const gvtm_event* events, const int64_t* chunk_offsets, const int64_t* utt_chunks, float* audio,
@@ -636,7 +661,7 @@ int gvtm_stream_push_events(gvtm_stream* s, const gvtm_event* events, const int6
 	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
 	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
 	if (s->feed == kFeedFrames) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed frames (gvtm_stream_push) until the next gvtm_stream_reset()");
-	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets) until the next gvtm_stream_reset()");
+	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets, model 5: gvtm_stream_push_targets_model5) until the next gvtm_stream_reset()");
 	const gvtm_plan* plan = s->plan;
 	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "gvtm_stream_push_events: the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
 	const size_t batch = s->batch;

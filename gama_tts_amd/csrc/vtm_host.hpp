@@ -185,8 +185,12 @@ struct gvtm_plan {
 		return xr;
 	}
 	// the shape of a launch on behalf of a stream whose LDS holds rings of xr samples; a stream of a plan of several
-	// voices launches the voice variant (gvtm_stream_create_voices)
-	gvtm::LaunchShape stream_launch_shape(size_t batch, int forced_rows, int xr) const { return launch_shape(batch, forced_rows, n_voices() > 1, xr); }
+	// voices launches the voice variant (gvtm_stream_create_voices); targets: a targets-fed run's launch (model 5: the targets
+	// variant's shapes)
+	gvtm::LaunchShape stream_launch_shape(size_t batch, int forced_rows, int xr, bool targets = false) const
+	{
+		return launch_shape(batch, forced_rows, n_voices() > 1, xr, true, targets);
+	}
 };
 
 namespace gvtm::host {

@@ -172,7 +172,12 @@ constexpr int kFloat5Flag = 8;
 // the moving averages of the utterance's sixteen target lists (vtm_targets.hpp) instead of interpolating frames: a.frame_counts
 // holds steps, there are no frames and no control_steps.  And what enters the resampler is divided by the step's
 // fundamental frequency (VocalTractModel5.h:579): pass A1a keeps the f0 it forms for dt in the record rf0, which pass X
-// reads ten ticks later.  One voice, one-shot launches only.  Every difference is a conditional on the constant TARGETS.
+// reads ten ticks later.  One voice.  A stream's launches (gvtm_stream_push_targets_model5) walk absolute steps from the
+// utterance's step_base on: behind step 0 the walk resumes on the 16 sums the previous launch left in the stream state
+// (targets_resume, Stream5Layout::sums; the points are the stream's log), and the epilogue stores them back.  The record rf0
+// carries nothing from launch to launch: chunk c's slot, c % 11, is written by A1a at tick c + 1 and read by X at tick
+// c + 11 of the same launch -- the tick loop drains every chunk through X (max_chunks + 14 ticks) -- and c restarts at 0 with
+// every launch.  Every difference is a conditional on the constant TARGETS.
 constexpr int kTargets5Flag = 16;
 __device__ __forceinline__ double sin_m5(double t) { return sin(t); }
 __device__ __forceinline__ float sin_m5(float t) { return vmath::sinf_glibc(t); } // std::sin(float), RosenbergBGlottalSource.h:139
@@ -309,7 +314,8 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 		unsigned peak0 = 0u;
 		if (ug < a.batch) {
 			// a stream's push carries one more row than it synthesizes: the next frame, which the last one interpolates towards
-			const size_t rows_avail = a.max_frames - (kPush ? 1 : 0);
+			// (not from targets: no step waits for a successor)
+			const size_t rows_avail = a.max_frames - (kPush && !TARGETS ? 1 : 0);
 			const int f = a.frame_counts ? a.frame_counts[ug] : static_cast<int>(rows_avail);
 			e.frames = f > 0 ? (static_cast<size_t>(f) < rows_avail ? f : static_cast<int>(rows_avail)) : 0;
 			if constexpr (TARGETS) e.steps = static_cast<uint32_t>(e.frames); // (a.frame_counts holds steps; a refused utterance's: 0)
@@ -817,12 +823,22 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 	// I, from targets (kTargets5Flag): lane 16u + p walks the points of utterance u's list for parameter p (vtm_targets.hpp): the
 	// filter's sum, the entering and the leaving value, the two cursors and the steps at which they move next.  (A refused
 	// utterance and a row beyond the batch have 0 steps: their list ids and offsets are never read.)
+	// A stream's launch walks absolute steps from the utterance's step_base on: behind step 0 the walk resumes on the sum the
+	// previous launch left in the stream state (targets_resume; the points are the stream's log, in absolute steps), and the
+	// epilogue stores the sum back.  An utterance the launch does not advance keeps its sums.
 	[[maybe_unused]] TargetsWalk tg{};
+	[[maybe_unused]] int64_t tg_base = 0;
 	if constexpr (TARGETS) {
 		if (role == 3 && ip_u < U && ip_frames > 0) {
 			const size_t slot = (group * U + ip_u) * GVTM_N_PARAM + Lp;
 			const int64_t list = a.tg_ids ? static_cast<int64_t>(a.tg_ids[slot]) : static_cast<int64_t>(slot);
-			targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N);
+			if (streaming) tg_base = static_cast<int64_t>(s_ext[ip_u].step_base);
+			if (tg_base > 0) {
+				const double* sums = reinterpret_cast<const double*>(a.stream + (group * U + ip_u) * a.stream_stride + Stream5Layout::sums());
+				targets_resume(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N, tg_base, sums[Lp]);
+			} else {
+				targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N);
+			}
 		}
 	} else if (role == 3 && ip_u < U && ip_frames > 0) {
 		ip_this = P[Lp];
@@ -842,8 +858,9 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 			// of four steps.  The cursors' bookkeeping only runs for a block in which some lane's cursor moves (a point enters, or
 			// leaves N steps later); every other block is four times {two double additions, a multiplication, a conversion, a
 			// store}.  A partial last block runs on: no cursor passes the end of its list, and the extra rows are never read
-			// (valid <= C, a multiple of four: they stay inside the chunk's slot).
-			const int64_t first = static_cast<int64_t>(c) * C;
+			// (valid <= C, a multiple of four: they stay inside the chunk's slot).  The steps are absolute (tg_base: a stream's
+			// step_base, else 0); the lanes of the wavefront are at different chunks by their lag, which __any covers.
+			const int64_t first = tg_base + static_cast<int64_t>(c) * C;
 			for (int s0 = 0; s0 < valid; s0 += 4) {
 				if (__builtin_expect(__any(targets_moves(tg, first + s0, 4)), 0)) {
 #pragma unroll
@@ -1305,6 +1322,14 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 
 	// ---- a stream's states for the next launch
 	if (streaming) {
+		if constexpr (TARGETS) {
+			// the moving averages' sums of every utterance the launch advanced, push and finish alike (a push synthesizes a
+			// multiple of four steps, so no lane has run on into a partial block when its sum is stored)
+			if (role == 3 && ip_u < U && ip_frames > 0) {
+				double* sums = reinterpret_cast<double*>(a.stream + (group * U + ip_u) * a.stream_stride + Stream5Layout::sums());
+				sums[Lp] = tg.sum;
+			}
+		}
 		if (role == 1 && lane < U && GVTM_M5_UTT(lane, group * U + lane) < a.batch) {
 			double* sc = reinterpret_cast<double*>(a.stream + GVTM_M5_UTT(lane, (group * U + lane)) * a.stream_stride + Stream5Layout::scalars());
 #pragma unroll

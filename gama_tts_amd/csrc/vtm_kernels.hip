@@ -212,7 +212,7 @@ hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream)
 hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int index, hipStream_t stream)
 {
 	if (!args.k5const || (index != 0 && index != 1)) return hipErrorInvalidValue;
-	// (the targets variants live in vtm_kernels_m5t.hip and vtm_kernels_m5ft.hip: one voice, no stream)
+	// (the targets variants live in vtm_kernels_m5t.hip and vtm_kernels_m5ft.hip: one voice, one-shot or a stream's)
 	if (args.tg_offsets) {
 		return precision == GVTM_PRECISION_F32 ? launch_synth5_float_targets(args, batch, index, stream) : launch_synth5_targets(args, batch, index, stream);
 	}

@@ -65,8 +65,13 @@ struct Stream5Layout {
 	static constexpr size_t tube() { return scalars() + sizeof(double) * kStream5Scalars; }
 	static constexpr size_t ring() { return tube() + sizeof(double) * 51 * 4; }
 	static constexpr size_t yring() { return ring() + sizeof(double) * kSrcRing; }
-	static constexpr size_t bytes() { return (yring() + sizeof(float) * 512 + 15) & ~size_t(15); }
+	// behind the ring of converted samples (no other offset moves): the 16 sums of a targets-fed run's moving averages
+	// (vtm_targets.hpp), doubles in both classes -- only 5 of the 24 scalar slots are free.  Every model 5 stream has them; a
+	// run fed frames never touches them
+	static constexpr size_t sums() { return (yring() + sizeof(float) * 512 + 7) & ~size_t(7); }
+	static constexpr size_t bytes() { return (sums() + sizeof(double) * GVTM_N_PARAM + 15) & ~size_t(15); }
 };
+static_assert(Stream5Layout::sums() == 12096 && Stream5Layout::bytes() == 12224, "model 5 stream state layout");
 
 // Plan constants of the all-float kernel as floats, by value behind the 64 coefficient slots of SynthArgs::fir_k: the
 // helper passes and the filter wavefronts then take them from scalar registers instead of reading DeviceConstants' doubles
@@ -223,13 +228,13 @@ hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_
 hipError_t launch_synth5_float_voices(const SynthArgs& args, size_t groups, int index, hipStream_t stream);
 // the targets variants alone (vtm_kernels_m5t.hip: the double class; vtm_kernels_m5ft.hip: the float class; launch_synth5
 // calls them where args.tg_offsets is set), in the shape `index` of the class's targets shapes (m5_targets_shape): one voice,
-// one-shot launches
+// one-shot launches and a stream's (args.stream: the points are the stream's log, in absolute steps)
 hipError_t launch_synth5_targets(const SynthArgs& args, size_t batch, int index, hipStream_t stream);
 hipError_t launch_synth5_float_targets(const SynthArgs& args, size_t batch, int index, hipStream_t stream);
-// what both ask of their arguments: the lists, the steps in frame_counts, the filter's length; no row map, no stream
+// what both ask of their arguments: the lists, the steps in frame_counts, the filter's length; no row map
 inline bool synth5_targets_args(const SynthArgs& args)
 {
-	return args.k5const && args.tg_offsets && args.tg_steps && args.tg_values && args.frame_counts && args.tg_N >= 1 && !args.row_map && !args.stream;
+	return args.k5const && args.tg_offsets && args.tg_steps && args.tg_values && args.frame_counts && args.tg_N >= 1 && !args.row_map;
 }
 constexpr int kDppSelftestInts = 640;
 hipError_t launch_dpp_selftest(int* d_out /* [kDppSelftestInts] */, hipStream_t stream);

@@ -1,6 +1,7 @@
 // The targets variant of the reference model 5 kernel in the float class (vtm5_synth_kernel with kFloat5Flag and
 // kTargets5Flag: VocalTractModel5<float,1>(config, interactive = true) fed parameter targets,
-// gvtm_synthesize_targets_model5_device on a gvtm_plan_create_model5_float plan), in both of its shapes.  A code object of its
+// gvtm_synthesize_targets_model5_device and gvtm_stream_push_targets_model5 on a gvtm_plan_create_model5_float plan), in both
+// of its shapes.  A code object of its
 // own; compiled with -ffp-contract=off as vtm_kernels_m5f.hip is (Makefile): the float class rounds every product before it
 // adds, and the division by f0 is one rounding of its own.
 #include <hip/hip_runtime.h>

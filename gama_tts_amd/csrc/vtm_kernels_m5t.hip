@@ -1,6 +1,6 @@
 // The targets variant of the reference model 5 kernel in the double class (vtm5_synth_kernel with kTargets5Flag:
-// VocalTractModel5<double,1>(config, interactive = true) fed parameter targets, gvtm_synthesize_targets_model5_device on a
-// gvtm_plan_create_model5 plan), in both of its shapes: one utterance per workgroup and two.  A translation unit, and so a
+// VocalTractModel5<double,1>(config, interactive = true) fed parameter targets, gvtm_synthesize_targets_model5_device and
+// gvtm_stream_push_targets_model5 on a gvtm_plan_create_model5 plan), in both of its shapes: one utterance per workgroup and two.  A translation unit, and so a
 // code object, of its own, as the voice variant and the float class have: the code object of vtm_kernels.hip keeps exactly
 // the kernels it had.  Plain flags, as vtm_kernels.hip has them: the same kernel text gives the same samples in each, and the
 // targets filter's additions keep their order by the pragma of vtm_targets.hpp.

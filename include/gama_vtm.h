@@ -54,7 +54,8 @@
  *                               the editor's interactive window: targets for the 16 parameters, each smoothed by a 50 ms
  *                               MovingAverageFilter<float> on every internal step, then execSynthesisStep()
  *                               (gama_tts_editor/src/interactive/InteractiveAudio.cpp:164-186);
- *                               gvtm_stream_push_targets: the same as a session, targets arriving push by push;
+ *                               gvtm_stream_push_targets: the same as a session, targets arriving push by push
+ *                               (reference model 5, which the window constructs: gvtm_stream_push_targets_model5);
  *                               gvtm_synthesize_targets_voices_device: the same for a batch that mixes voices
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
@@ -470,7 +471,7 @@ void gvtm_host_free(void* ptr);
  * A stream also takes its utterances as event lists, chunk by chunk, and generates their frames itself:
  * gvtm_stream_push_events, with gvtm_stream_get_drift / gvtm_stream_set_drift, declared behind the track-generation entries
  * below ("Streams fed event lists").  And as parameter targets, the interactive window's session: gvtm_stream_push_targets
- * ("Streams fed parameter targets").
+ * and, for the one-voice plans of reference model 5, gvtm_stream_push_targets_model5 ("Streams fed parameter targets").
  */
 typedef struct gvtm_stream gvtm_stream;
 
@@ -1026,8 +1027,9 @@ int gvtm_synthesize_targets_voices_device(gvtm_plan* plan, const int64_t* d_list
  * scratch: calls on one plan must be ordered on one stream.  Refused before any device work, in this order: a null plan;
  * with batch > 0 what gvtm_synthesize_targets_device refuses (GVTM_ERR_INVALID_ARGUMENT); a plan of several voices or a
  * plan of the models 0 to 4, which have gvtm_synthesize_targets_device (GVTM_ERR_UNSUPPORTED); a design-only plan
- * (GVTM_ERR_NO_DEVICE), with batch == 0 too; on a plan with a device batch == 0 returns GVTM_OK.  Model 5 targets under
- * several voices and in streams are not available. */
+ * (GVTM_ERR_NO_DEVICE), with batch == 0 too; on a plan with a device batch == 0 returns GVTM_OK.  The same as a session:
+ * gvtm_stream_push_targets_model5 ("Streams fed parameter targets" below).  Model 5 targets under several voices are not
+ * available. */
 int gvtm_synthesize_targets_model5_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
 		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, size_t batch,
 		size_t max_steps, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status,
@@ -1058,7 +1060,8 @@ int gvtm_synthesize_targets_model5_device(gvtm_plan* plan, const int64_t* d_list
  * 11 pending ones, the flush with its overrun lap, and one more sample.  (size_t)-1 on a null stream.
  *
  * Checked on the host before anything is launched; the first that applies: a null stream (GVTM_ERR_INVALID_ARGUMENT); a
- * stream of a plan of several voices or of a model 5 plan (GVTM_ERR_UNSUPPORTED: the one-shot entry takes neither); then,
+ * stream of a plan of several voices or of a model 5 plan (GVTM_ERR_UNSUPPORTED: the one-shot entry takes neither; model 5
+ * has gvtm_stream_push_targets_model5, below); then,
  * all GVTM_ERR_INVALID_ARGUMENT, a finished stream; a stream fed frames or event lists since its last reset; a null
  * list_offsets; a max_steps beyond the step counter; points without their tables; an utterance that is refused -- status 1
  * for a count outside [0, max_steps], 2, 3 and 4 as above, and 4 also for a point whose step is at or beyond the
@@ -1071,6 +1074,27 @@ int gvtm_synthesize_targets_model5_device(gvtm_plan* plan, const int64_t* d_list
  * points, the pending steps and the sums.
  */
 int gvtm_stream_push_targets(gvtm_stream* stream, const int64_t* list_offsets, const int32_t* point_steps,
+		const float* point_values, const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride,
+		int64_t* out_counts, int32_t* status_out);
+/* gvtm_stream_push_targets for reference model 5, the model the interactive window constructs: streams of gvtm_stream_create
+ * on the one-voice plans of gvtm_plan_create_model5 and gvtm_plan_create_model5_float.  Every argument is that entry's.  An
+ * entry of its own for the reason gvtm_synthesize_targets_model5_device is one: the samples are those of the model
+ * constructed with interactive = true, which divides each step's signal by that step's f0 -- not those of a frames-fed
+ * stream of the same plan.
+ * Model 5's serial stages work in blocks of four steps: a push synthesizes the steps that fit a granule of 4 and keeps the
+ * rest (at most 3) pending.  Contract: an utterance's steps pushed in any grouping over any number of calls and then
+ * finished give, in both classes bit for bit, the samples, sample count and maxabs of one
+ * gvtm_synthesize_targets_model5_device call on the whole utterance's lists: in the float class the reference's interactive
+ * model bit for bit, in the double class within the model 5 parity bar.
+ * gvtm_stream_finish, gvtm_stream_reset, gvtm_stream_targets_points and gvtm_stream_targets_capacity serve such a stream as
+ * they are: the capacity's 11 pending steps and the bound on the points held (those of the last N + 12 steps plus 16) hold
+ * with room to spare.
+ * Refused, the first that applies: a null stream (GVTM_ERR_INVALID_ARGUMENT); a stream of a plan of several voices or of a
+ * plan of the models 0 to 4, which have gvtm_stream_push_targets (GVTM_ERR_UNSUPPORTED); then everything
+ * gvtm_stream_push_targets refuses, in its order and with its status codes, and a refused call leaves the stream exactly as
+ * it found it.  One feed per run here too: gvtm_stream_push and gvtm_stream_push_events refuse a model 5 stream fed targets,
+ * this entry one fed frames or event lists, until the next gvtm_stream_reset; after a reset the stream takes either feed. */
+int gvtm_stream_push_targets_model5(gvtm_stream* stream, const int64_t* list_offsets, const int32_t* point_steps,
 		const float* point_values, const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride,
 		int64_t* out_counts, int32_t* status_out);
 size_t gvtm_stream_targets_capacity(const gvtm_stream* stream, size_t max_new_steps);
@@ -1103,7 +1127,7 @@ int gvtm_stream_targets_points(const gvtm_stream* stream, int64_t* held_out);
  * gvtm_synthesize_events_chunks_device call on the whole utterance with the same voice and the same initial drift state.
  *
  * One feeding mode per run: between two resets a stream is fed frames (gvtm_stream_push), event lists or parameter targets
- * (gvtm_stream_push_targets, above), never two of them; once one entry has been used the others return
+ * (gvtm_stream_push_targets or gvtm_stream_push_targets_model5, above), never two of them; once one entry has been used the others return
  * GVTM_ERR_INVALID_ARGUMENT until the next reset, and so does
  * gvtm_stream_set_drift between a gvtm_stream_push_events and the next reset.
  *
