@@ -189,6 +189,7 @@ def _prototypes():
         "gvtm_targets_voice_output_count": (sz, [vp, i, sz]),
         "gvtm_targets_voices_output_capacity": (sz, [vp, sz]),
         "gvtm_synthesize_targets_voices_device": (i, [vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
+        "gvtm_synthesize_targets_model5_voices_device": (i, [vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
         "gvtm_stream_push_targets": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
         "gvtm_stream_push_targets_model5": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
         "gvtm_stream_targets_capacity": (sz, [vp, sz]),
@@ -956,6 +957,16 @@ class Plan:
         """synthesize_targets_device with a voice id per utterance (gvtm_synthesize_targets_voices_device): utterance b walks
         its lists under voice d_voice_ids[b]; on a plan of one voice the ids are all 0.  All pointers are device memory."""
         self._check(self._lib.gvtm_synthesize_targets_voices_device(
+            self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
+            _ptr(d_voice_ids), int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status),
+            _ptr(stream)))
+
+    def synthesize_targets_model5_voices_device(self, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, d_voice_ids,
+                                                batch, max_steps, d_audio, audio_stride, d_out_counts=None, d_maxabs=None, d_status=None, stream=None):
+        """synthesize_targets_model5_device with a voice id per utterance (gvtm_synthesize_targets_model5_voices_device), for
+        model 5 voices plans of either class: utterance b walks its lists under voice d_voice_ids[b], its samples the
+        interactive model's; on a plan of one voice the ids are all 0.  All pointers are device memory."""
+        self._check(self._lib.gvtm_synthesize_targets_model5_voices_device(
             self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
             _ptr(d_voice_ids), int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status),
             _ptr(stream)))

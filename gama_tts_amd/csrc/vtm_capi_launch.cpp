@@ -170,9 +170,8 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
 	if (r.voices && !r.voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
 	if (r.targets && !r.frame_counts) return fail(GVTM_ERR_UNSUPPORTED, "targets: a launch with step counts");
-	// (model 5 from targets: one voice, gvtm_synthesize_targets_model5_device's one-shot launch or a stream's)
-	if (r.targets && plan->designs[0].model5 && r.voices) return fail(GVTM_ERR_UNSUPPORTED, "targets: model 5 in a launch of one voice only");
-	// (several voices: a one-shot launch, with the plan's filter lengths by voice)
+	// (several voices, model 5 as well: a one-shot launch, with the plan's filter lengths by voice; a stream's launches from
+	// targets are of one voice in either model family)
 	if (r.targets && r.voices && (r.sl || !r.targets->voice_N || !r.targets->voice_invN)) return fail(GVTM_ERR_UNSUPPORTED, "targets of several voices: one-shot launches only");
 	if (r.max_frames > 0 && !r.params && !r.targets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	// (several voices: the row map's int32 slots also count up to n_voices partly empty workgroups)

@@ -76,7 +76,10 @@ int upload_tables(gvtm_plan* plan)
 	if (!dg.model5) {
 		if ((rc = upload_design(plan->d_wavetable, wavetables, wavetables_f, "upload wavetable")) != GVTM_OK) return rc;
 		if ((rc = upload_design(plan->d_fir, dg.fir, dg.fir_f, "upload fir")) != GVTM_OK) return rc;
-		// the targets' filter by voice, as gvtm_synthesize_targets_device forms the two for its one voice (vtm_capi_targets.cpp)
+	}
+	{
+		// the targets' filter by voice, as gvtm_synthesize_targets_device forms the two for its one voice (vtm_capi_targets.cpp);
+		// model 5 plans too: gvtm_synthesize_targets_model5_voices_device reads them
 		std::vector<int64_t> targets_N;
 		std::vector<double> targets_invN;
 		for (const gvtm::Design& dv : plan->designs) {

@@ -1,6 +1,7 @@
 // C ABI of libgama_vtm.so, synthesis from parameter targets (the editor's interactive window): the filter length, the sample
-// counts by internal steps, the rule on the host, and the three device entries (one voice of the models 0 to 4; a voice id per
-// utterance; one voice of model 5, whose kernel also divides each step's signal by its f0 as the interactive model does), which put
+// counts by internal steps, the rule on the host, and the four device entries (one voice of the models 0 to 4; a voice id per
+// utterance; one voice of model 5, whose kernel also divides each step's signal by its f0 as the interactive model does; model 5
+// with a voice id per utterance), which put
 // the synthesis launch -- the kernel's targets driver, launch_synthesis with LaunchRequest::targets -- behind the check kernel
 // with the plan's step counts in between.
 #include "vtm_host.hpp"
@@ -167,6 +168,32 @@ int gvtm_synthesize_targets_model5_device(gvtm_plan* plan, const int64_t* d_list
 	if (batch == 0) return GVTM_OK;
 	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, nullptr, batch, max_steps, d_audio, audio_stride,
 			d_out_counts, d_maxabs, d_status, hip_stream);
+}
+
+int gvtm_synthesize_targets_model5_voices_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
+		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, const int32_t* d_voice_ids, size_t batch, size_t max_steps,
+		float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (batch > 0) {
+		if (const int rc = check_batch_arguments(d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, batch, max_steps, d_audio); rc != GVTM_OK) return rc;
+		if (!d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
+		if (audio_stride < voices_output_capacity(plan, max_steps)) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_targets_voices_output_capacity(plan, max_steps)");
+		}
+	}
+	if (!plan->designs[0].model5) {
+		return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_model5_voices_device: model 5 only (gvtm_synthesize_targets_voices_device takes the models 0 to 4)");
+	}
+	// (launch_synthesis' rule, stated here so that a design-only plan shows it)
+	if (plan->designs[0].f32 && !plan->float5_voices) {
+		return fail(GVTM_ERR_UNSUPPORTED, "a gvtm_plan_create_model5_float plan has no launch of several voices (one voice per plan; "
+				"gvtm_plan_create_model5_float_voices makes the float plans that have)");
+	}
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
+	if (batch == 0) return GVTM_OK;
+	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, d_voice_ids, batch, max_steps, d_audio,
+			audio_stride, d_out_counts, d_maxabs, d_status, hip_stream);
 }
 
 size_t gvtm_targets_voice_output_count(const gvtm_plan* plan, int voice, size_t n_steps)

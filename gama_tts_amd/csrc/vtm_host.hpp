@@ -120,8 +120,9 @@ struct gvtm_plan {
 	// design tables on the device: double, or float (as designed) for GVTM_PRECISION_F32
 	DeviceBuffer d_wavetable, d_fir, d_src_h, d_src_dh;
 	DeviceBuffer d_consts, d_consts5; // gvtm::DeviceConstants, gvtm::Model5Constants (model 5 plans only)
-	// the models 0 to 4: the length of the targets' moving average and its reciprocal by voice (vtm_targets.hpp:
-	// targets_filter_length of the voice's internal rate), what gvtm_synthesize_targets_voices_device's kernel reads
+	// the length of the targets' moving average and its reciprocal by voice (vtm_targets.hpp: targets_filter_length of the
+	// voice's internal rate), what the kernels of gvtm_synthesize_targets_voices_device and, on model 5 plans,
+	// gvtm_synthesize_targets_model5_voices_device read
 	DeviceBuffer d_targets_N, d_targets_invN;
 	// the noise source's samples by internal step (the same for every utterance), grown on demand; superseded buffers stay
 	// allocated until the plan goes (a launch in flight on the caller's stream may still read them; the growth is

@@ -1,9 +1,10 @@
 // Reference model 5 (VocalTractModel5<double,1>, vtm/VocalTractModel5.h) on the device.
 // Included inside namespace gvtm, after vtm_kernel_v2.inc (whose wave-wide DPP helpers, Extent and voice_row it shares),
-// by six translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
+// by eight translation units: vtm_kernels.hip instantiates the single-voice kernels, vtm_kernels_m5v.hip the voice variant
 // (kVoices5Flag), vtm_kernels_m5f.hip the float class, VocalTractModel5<float,1> (kFloat5Flag), vtm_kernels_m5fv.hip
 // the voice variant of the float class (both flags), vtm_kernels_m5t.hip and vtm_kernels_m5ft.hip the targets variant
-// (kTargets5Flag) of the double and of the float class, each in a code object of its own.  Besides the kernel, the file
+// (kTargets5Flag) of the double and of the float class, vtm_kernels_m5tv.hip and vtm_kernels_m5ftv.hip that variant under
+// several voices (kTargets5Flag with kVoices5Flag), each in a code object of its own.  Besides the kernel, the file
 // defines what they launch it with: the description of its shapes (m5_shape,
 // kM5Ring), before the kernel, and the LDS bytes and the launch of a shape (m5_lds_bytes, launch_synth5_shape), at the end.
 //
@@ -172,7 +173,8 @@ constexpr int kFloat5Flag = 8;
 // the moving averages of the utterance's sixteen target lists (vtm_targets.hpp) instead of interpolating frames: a.frame_counts
 // holds steps, there are no frames and no control_steps.  And what enters the resampler is divided by the step's
 // fundamental frequency (VocalTractModel5.h:579): pass A1a keeps the f0 it forms for dt in the record rf0, which pass X
-// reads ten ticks later.  One voice.  A stream's launches (gvtm_stream_push_targets_model5) walk absolute steps from the
+// reads ten ticks later.  One voice, or with kVoices5Flag several in a one-shot launch (see the interpolation wavefront's
+// setup).  A stream's launches (gvtm_stream_push_targets_model5; one voice only) walk absolute steps from the
 // utterance's step_base on: behind step 0 the walk resumes on the 16 sums the previous launch left in the stream state
 // (targets_resume, Stream5Layout::sums; the points are the stream's log), and the epilogue stores them back.  The record rf0
 // carries nothing from launch to launch: chunk c's slot, c % 11, is written by A1a at tick c + 1 and read by X at tick
@@ -205,7 +207,6 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 	using R2 = typename Pair<R>::type;
 	static_assert(!FLOAT || U == 1, "the float class has the one-utterance shape only");
 	static_assert(!VOICES || U == 1, "the voice variant has the one-utterance shape only");
-	static_assert(!TARGETS || !VOICES, "the targets variant has one voice");
 	int voice = 0;
 	if constexpr (VOICES) {
 		voice = a.group_voice[blockIdx.x];
@@ -826,18 +827,29 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 	// A stream's launch walks absolute steps from the utterance's step_base on: behind step 0 the walk resumes on the sum the
 	// previous launch left in the stream state (targets_resume; the points are the stream's log, in absolute steps), and the
 	// epilogue stores the sum back.  An utterance the launch does not advance keeps its sums.
+	// Under several voices (kVoices5Flag with kTargets5Flag: gvtm_synthesize_targets_model5_voices_device, one-shot launches
+	// only) the utterance, and with it the slot of its lists, is the row map's, and the filter's length and reciprocal are the
+	// workgroup's voice's, a.tg_voice_N[voice] and a.tg_voice_invN[voice], read once per workgroup as vtm_kernel_v2.inc does.
 	[[maybe_unused]] TargetsWalk tg{};
 	[[maybe_unused]] int64_t tg_base = 0;
+	[[maybe_unused]] int64_t tgv_N = 0;
+	[[maybe_unused]] double tgv_invN = 0.0;
+	if constexpr (TARGETS && VOICES) {
+		tgv_N = a.tg_voice_N[voice];
+		tgv_invN = a.tg_voice_invN[voice];
+	}
+	[[maybe_unused]] const auto tg_length = [&]() -> int64_t { if constexpr (VOICES) return tgv_N; else return a.tg_N; };
+	[[maybe_unused]] const auto tg_inverse = [&]() -> double { if constexpr (VOICES) return tgv_invN; else return a.tg_invN; };
 	if constexpr (TARGETS) {
 		if (role == 3 && ip_u < U && ip_frames > 0) {
-			const size_t slot = (group * U + ip_u) * GVTM_N_PARAM + Lp;
+			const size_t slot = GVTM_M5_UTT(ip_u, (group * U + ip_u)) * GVTM_N_PARAM + Lp;
 			const int64_t list = a.tg_ids ? static_cast<int64_t>(a.tg_ids[slot]) : static_cast<int64_t>(slot);
 			if (streaming) tg_base = static_cast<int64_t>(s_ext[ip_u].step_base);
 			if (tg_base > 0) {
 				const double* sums = reinterpret_cast<const double*>(a.stream + (group * U + ip_u) * a.stream_stride + Stream5Layout::sums());
-				targets_resume(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N, tg_base, sums[Lp]);
+				targets_resume(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], tg_length(), tg_base, sums[Lp]);
 			} else {
-				targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], a.tg_N);
+				targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], tg_length());
 			}
 		}
 	} else if (role == 3 && ip_u < U && ip_frames > 0) {
@@ -865,12 +877,12 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 				if (__builtin_expect(__any(targets_moves(tg, first + s0, 4)), 0)) {
 #pragma unroll
 					for (int q = 0; q < 4; ++q) {
-						targets_move(tg, first + s0 + q, a.tg_steps, a.tg_values, a.tg_N);
-						out[(s0 + q) * 16] = targets_step(tg, a.tg_invN);
+						targets_move(tg, first + s0 + q, a.tg_steps, a.tg_values, tg_length());
+						out[(s0 + q) * 16] = targets_step(tg, tg_inverse());
 					}
 				} else {
 #pragma unroll
-					for (int q = 0; q < 4; ++q) out[(s0 + q) * 16] = targets_step(tg, a.tg_invN);
+					for (int q = 0; q < 4; ++q) out[(s0 + q) * 16] = targets_step(tg, tg_inverse());
 				}
 			}
 			return;
@@ -1391,13 +1403,13 @@ static size_t m5_lds_bytes()
 // The launch of shape (FLOAT, INDEX).  VOICES: a launch of several voices (the kernel's kVoices5Flag; args.row_map is
 // set), a one-utterance shape only (the double class's, either of the float class's); `batch` is then the number of
 // workgroups.  TARGETS: a launch from parameter targets (the kernel's kTargets5Flag; args.tg_offsets is set), in the shape
-// (FLOAT, INDEX) of m5_targets_shape, one voice only
+// (FLOAT, INDEX) of m5_targets_shape; with VOICES (vtm_kernels_m5tv.hip, vtm_kernels_m5ftv.hip) in its one-utterance shapes
 template <bool FLOAT, int INDEX, bool VOICES = false, bool TARGETS = false>
 static hipError_t launch_synth5_shape(const SynthArgs& args, size_t batch, hipStream_t stream)
 {
 	constexpr M5Shape s = m5_shape_of(FLOAT, INDEX, TARGETS);
 	static_assert(!VOICES || s.rows == 1, "the voice variant has the one-utterance shapes only");
-	static_assert(!VOICES || !TARGETS, "the targets variant has one voice");
+	static_assert(!(VOICES && TARGETS) || s.rows == 1, "the targets variant under several voices has the one-utterance shapes only");
 	auto fn = m5::vtm5_synth_kernel<s.chunk, s.helpers, kM5Ring,
 			s.rows | (VOICES ? m5::kVoices5Flag : 0) | (FLOAT ? m5::kFloat5Flag : 0) | (TARGETS ? m5::kTargets5Flag : 0)>;
 	const size_t lds = m5_lds_bytes<FLOAT, INDEX, TARGETS>();

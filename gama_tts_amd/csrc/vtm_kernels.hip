@@ -7,7 +7,8 @@
 //                      under several voices in vtm_kernels_targets_voices.hip)
 //   vtm5_synth_kernel  (vtm_kernel_m5.inc)  VocalTractModel5 semantics, same organisation (its voice variant is compiled
 //                      in vtm_kernels_m5v.hip, its float class in vtm_kernels_m5f.hip, that class's voice variant in
-//                      vtm_kernels_m5fv.hip, its targets variant in vtm_kernels_m5t.hip and vtm_kernels_m5ft.hip)
+//                      vtm_kernels_m5fv.hip, its targets variant in vtm_kernels_m5t.hip and vtm_kernels_m5ft.hip, and
+//                      that variant under several voices in vtm_kernels_m5tv.hip and vtm_kernels_m5ftv.hip)
 //   vtm_normalize_kernel                    output scaling of Controller::writeOutputToBuffer / writeOutputToFile
 //
 // Which shape a launch has (rows, chunk length, helpers, ring, LDS) is decided in vtm_kernel_shapes.hpp and only there, and
@@ -116,10 +117,11 @@ LaunchShape synth_launch_shape(const Design* voices, int n_voices, int precision
 		// share a compute unit (DESIGN.md 4b has the measurement).
 		const bool float_class = precision == GVTM_PRECISION_F32;
 		const int index = float_class ? (forced_rows == 1 ? 0 : (forced_rows == 2 || batch > 256 ? 1 : 0)) : (forced_rows == 2 && !several_voices ? 1 : 0);
-		// The targets variant (one voice) has shapes of its own by the same index and the same rule: each is the shape above
+		// The targets variant has shapes of its own by the same index and the same rule: each is the shape above
 		// with the f0 record, its chunk shortened where the record does not fit the budget the shape stands for
-		// (m5_targets_shape, vtm_kernel_m5.inc).  (Offsets is a constant expression: no kernel is named here.)
-		if (targets && several_voices) return LaunchShape{};
+		// (m5_targets_shape, vtm_kernel_m5.inc).  (Offsets is a constant expression: no kernel is named here.)  Under several
+		// voices the index is the voices launch's above, so the targets shapes are the one-utterance ones: the double class's
+		// chunk of 56 (156 016 B), the float class's of 60 or 52 by the batch (87 632 / 78 896 B).
 		const M5Shape m = m5_shape_of(float_class, index, targets);
 		const size_t lds = targets ? (float_class ? (index == 1 ? m5_lds_bytes<true, 1, true>() : m5_lds_bytes<true, 0, true>())
 		                                          : (index == 1 ? m5_lds_bytes<false, 1, true>() : m5_lds_bytes<false, 0, true>()))
@@ -212,7 +214,12 @@ hipError_t launch_group_voices(const GroupVoicesArgs& args, hipStream_t stream)
 hipError_t launch_synth5(const SynthArgs& args, size_t batch, int precision, int index, hipStream_t stream)
 {
 	if (!args.k5const || (index != 0 && index != 1)) return hipErrorInvalidValue;
-	// (the targets variants live in vtm_kernels_m5t.hip and vtm_kernels_m5ft.hip: one voice, one-shot or a stream's)
+	// (the targets variants live in vtm_kernels_m5t.hip and vtm_kernels_m5ft.hip: one voice, one-shot or a stream's; under
+	// several voices in vtm_kernels_m5tv.hip and vtm_kernels_m5ftv.hip: one-shot, the one-utterance shapes)
+	if (args.tg_offsets && args.row_map) {
+		if (precision == GVTM_PRECISION_F32) return launch_synth5_float_targets_voices(args, batch, index, stream);
+		return index == 0 ? launch_synth5_targets_voices(args, batch, stream) : hipErrorInvalidValue;
+	}
 	if (args.tg_offsets) {
 		return precision == GVTM_PRECISION_F32 ? launch_synth5_float_targets(args, batch, index, stream) : launch_synth5_targets(args, batch, index, stream);
 	}

@@ -193,7 +193,7 @@ constexpr size_t kLdsPerWorkgroup = 160 * 1024;
 // smallest power of two holding two chunks, the resampler's history and the flush zeros).  With `fit`, rows whose LDS
 // exceeds kLdsPerWorkgroup give way to half as many (not model 5) or to "none fits"; without, they stay whatever their LDS.
 // targets: a launch from parameter targets; it changes the answer for model 5 alone, whose targets variant has shapes of its
-// own by the same index (vtm_kernel_m5.inc: m5_targets_shape; one voice).
+// own by the same index (vtm_kernel_m5.inc: m5_targets_shape; with several_voices its one-utterance shapes).
 LaunchShape synth_launch_shape(const Design* voices, int n_voices, int precision, size_t batch, int forced_rows, bool several_voices,
 		int stream_ring = 0, bool fit = true, bool targets = false);// the chunk length (internal steps per tick) of a shape, which its own ring length follows; 0: no such shape
 int synth_chunk_length(const DeviceConstants& k, int precision, int rows);
@@ -227,7 +227,7 @@ hipError_t launch_synth5_voices(const SynthArgs& args, size_t groups, hipStream_
 // the voice variant of the float class alone (vtm_kernels_m5fv.hip; launch_synth5 calls it), in the float class's shape `index`
 hipError_t launch_synth5_float_voices(const SynthArgs& args, size_t groups, int index, hipStream_t stream);
 // the targets variants alone (vtm_kernels_m5t.hip: the double class; vtm_kernels_m5ft.hip: the float class; launch_synth5
-// calls them where args.tg_offsets is set), in the shape `index` of the class's targets shapes (m5_targets_shape): one voice,
+// calls them where args.tg_offsets is set and args.row_map is not), in the shape `index` of the class's targets shapes (m5_targets_shape): one voice,
 // one-shot launches and a stream's (args.stream: the points are the stream's log, in absolute steps)
 hipError_t launch_synth5_targets(const SynthArgs& args, size_t batch, int index, hipStream_t stream);
 hipError_t launch_synth5_float_targets(const SynthArgs& args, size_t batch, int index, hipStream_t stream);
@@ -235,6 +235,18 @@ hipError_t launch_synth5_float_targets(const SynthArgs& args, size_t batch, int 
 inline bool synth5_targets_args(const SynthArgs& args)
 {
 	return args.k5const && args.tg_offsets && args.tg_steps && args.tg_values && args.frame_counts && args.tg_N >= 1 && !args.row_map;
+}
+// the targets variants under several voices alone (vtm_kernels_m5tv.hip: the double class, its one-utterance shape;
+// vtm_kernels_m5ftv.hip: the float class, in its targets shape `index`; launch_synth5 calls them where args.tg_offsets and
+// args.row_map are both set): `groups` workgroups of launch_group_voices' map, one utterance each, one-shot launches only
+hipError_t launch_synth5_targets_voices(const SynthArgs& args, size_t groups, hipStream_t stream);
+hipError_t launch_synth5_float_targets_voices(const SynthArgs& args, size_t groups, int index, hipStream_t stream);
+// what both ask of their arguments: the row map and the groups' voices, the lists, the steps in frame_counts, the filter's
+// length and reciprocal by voice; no stream
+inline bool synth5_targets_voices_args(const SynthArgs& args)
+{
+	return args.k5const && args.row_map && args.group_voice && args.tg_offsets && args.tg_steps && args.tg_values && args.frame_counts && args.tg_voice_N &&
+	       args.tg_voice_invN && !args.stream;
 }
 constexpr int kDppSelftestInts = 640;
 hipError_t launch_dpp_selftest(int* d_out /* [kDppSelftestInts] */, hipStream_t stream);

@@ -57,6 +57,7 @@
  *                               gvtm_stream_push_targets: the same as a session, targets arriving push by push
  *                               (reference model 5, which the window constructs: gvtm_stream_push_targets_model5);
  *                               gvtm_synthesize_targets_voices_device: the same for a batch that mixes voices
+ *                               (reference model 5: gvtm_synthesize_targets_model5_voices_device)
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
@@ -912,7 +913,7 @@ int gvtm_synthesize_modified_device(gvtm_plan* plan, const float* d_base_params,
  *   2  list offsets that are negative or decrease
  *   3  a value that is not finite
  *   4  a negative step; steps not strictly increasing within a list
- *   5  gvtm_synthesize_targets_voices_device only: a voice id outside [0, n_voices).  Looked at before every other status;
+ *   5  gvtm_synthesize_targets_voices_device and gvtm_synthesize_targets_model5_voices_device only: a voice id outside [0, n_voices).  Looked at before every other status;
  *      such an utterance is not one of 0 steps but left out as gvtm_synthesize_voices_device leaves it out: out_counts -1,
  *      maxabs 0, its audio row untouched
  */
@@ -1028,12 +1029,40 @@ int gvtm_synthesize_targets_voices_device(gvtm_plan* plan, const int64_t* d_list
  * with batch > 0 what gvtm_synthesize_targets_device refuses (GVTM_ERR_INVALID_ARGUMENT); a plan of several voices or a
  * plan of the models 0 to 4, which have gvtm_synthesize_targets_device (GVTM_ERR_UNSUPPORTED); a design-only plan
  * (GVTM_ERR_NO_DEVICE), with batch == 0 too; on a plan with a device batch == 0 returns GVTM_OK.  The same as a session:
- * gvtm_stream_push_targets_model5 ("Streams fed parameter targets" below).  Model 5 targets under several voices are not
- * available. */
+ * gvtm_stream_push_targets_model5 ("Streams fed parameter targets" below).  Model 5 targets under several voices:
+ * gvtm_synthesize_targets_model5_voices_device (next). */
 int gvtm_synthesize_targets_model5_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
 		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, size_t batch,
 		size_t max_steps, float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status,
 		void* hip_stream);
+
+/* gvtm_synthesize_targets_model5_device with a voice id per utterance: one articulator trajectory under every model 5 speaker
+ * in one launch, although the five voice variants' tract lengths, and with them their internal rates and their N, differ by
+ * more than a factor of two.  Argument for argument it is gvtm_synthesize_targets_voices_device:
+ *   d_voice_ids [batch] int32                    utterance b walks its lists under voice d_voice_ids[b] of the plan: that
+ *                                                voice's own N = gvtm_targets_filter_length(plan, voice) and 1 / N.  Lists
+ *                                                hold no N, so utterances of different voices may share a list
+ *   d_audio [batch][audio_stride]                utterance b yields gvtm_targets_voice_output_count(plan, voice_b, S_b) samples
+ *   every other argument                         as gvtm_synthesize_targets_device's
+ * Plans of gvtm_plan_create_model5_voices and gvtm_plan_create_model5_float_voices of any number of voices, and a one-voice
+ * gvtm_plan_create_model5 plan, on which ids that are all 0 give gvtm_synthesize_targets_model5_device's bytes.  In both
+ * classes voice v's utterances come out bit for bit -- samples, out_counts, maxabs -- as gvtm_synthesize_targets_model5_device
+ * synthesizes them on a one-voice plan made from configs[v]: the samples are the interactive model's (divided by f0), in the
+ * float class the reference's VocalTractModel5<float,1>(config, interactive = true) bit for bit, in the double class within the
+ * model 5 parity bar.  It is an entry of its own for that reason, as gvtm_synthesize_targets_model5_device is.  A voice id
+ * outside [0, n_voices) is status 5 (above: looked at first, out_counts -1, maxabs 0, the audio row untouched); an utterance
+ * refused with status 1 to 4 is one of 0 steps of its voice.  Enqueue-only: the check kernel, the grouping kernel of
+ * gvtm_synthesize_voices_device and the synthesis launch on hip_stream, nothing else.  The call uses the plan's grouping
+ * scratch and step-count scratch: calls on one plan must be ordered on one stream.  Refused before any device work, in this
+ * order: a null plan; with batch > 0 what gvtm_synthesize_targets_device refuses, NULL d_voice_ids, a stride below
+ * gvtm_targets_voices_output_capacity(plan, max_steps) (GVTM_ERR_INVALID_ARGUMENT); a plan of the models 0 to 4, which have
+ * gvtm_synthesize_targets_voices_device (GVTM_ERR_UNSUPPORTED); a gvtm_plan_create_model5_float plan, which has no launch of
+ * several voices (GVTM_ERR_UNSUPPORTED); a design-only plan (GVTM_ERR_NO_DEVICE), with batch == 0 too; on a plan with a
+ * device batch == 0 returns GVTM_OK.  Not available: streams of targets under several voices, in either model family. */
+int gvtm_synthesize_targets_model5_voices_device(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists,
+		const int32_t* d_list_ids, const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts,
+		const int32_t* d_voice_ids, size_t batch, size_t max_steps, float* d_audio, size_t audio_stride,
+		int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream);
 
 /*
  * Streams fed parameter targets: the interactive window as a session.  Targets arrive while the audio is playing, so a
