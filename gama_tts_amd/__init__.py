@@ -6,6 +6,7 @@ used by the tests, bench.py and __graft_entry__.py; it never computes audio itse
 raises when the native library is missing.
 """
 from .capi import (  # noqa: F401
+    Analysis,
     GvtmError,
     PinnedArray,
     Plan,

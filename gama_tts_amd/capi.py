@@ -201,6 +201,14 @@ def _prototypes():
         "gvtm_synthesize_events_packed_host": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
         "gvtm_synthesize_events_packed_host_pcm16": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]),
         "gvtm_generate_tracks_host": (i, [i, tracks, vp, vp, sz, sz, vp, vp, vp]),
+        "gvtm_analysis_create": (i, [i, vp, vp]),
+        "gvtm_analysis_destroy": (None, [vp]),
+        "gvtm_analysis_bin_count": (sz, [vp]),
+        "gvtm_analysis_window": (i, [vp, vp, sz]),
+        "gvtm_analysis_buffer_count": (sz, [i64, i64, sz]),
+        "gvtm_analysis_reserve": (i, [vp, sz]),
+        "gvtm_analysis_apply_host": (i, [vp, vp, sz, sz, sz, vp, vp, vp]),
+        "gvtm_analyze_spectrum_device": (i, [vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp]),
     }
     hooks = {
         "gvtm_debug_set_rows": (i, [vp, i]),
@@ -565,6 +573,75 @@ def _ptr(x):
     if isinstance(x, np.ndarray):
         return ctypes.c_void_p(x.ctypes.data)
     return ctypes.c_void_p(x.data_ptr())  # torch.Tensor
+
+
+ANALYSIS_FFT_SIZE = 65536  # GVTM_ANALYSIS_FFT_SIZE
+ANALYSIS_MAX_BINS = 32769  # GVTM_ANALYSIS_MAX_BINS
+ANALYSIS_DEFAULT_BUFFERS = 128  # GVTM_ANALYSIS_DEFAULT_BUFFERS
+WINDOW_RECTANGULAR, WINDOW_TRIANGULAR, WINDOW_HANN, WINDOW_HAMMING, WINDOW_BLACKMAN = range(5)  # GVTM_WINDOW_*
+
+
+class AnalysisConfig(ctypes.Structure):
+    """gvtm_analysis_config"""
+    _fields_ = [("window_type", ctypes.c_int32), ("window_size", ctypes.c_int32), ("log_scale", ctypes.c_int32),
+                ("min_db", ctypes.c_double), ("max_freq_hz", ctypes.c_double), ("sample_rate", ctypes.c_uint32)]
+
+
+def analysis_buffer_count(n_samples, first_sample, max_buffers):
+    """gvtm_analysis_buffer_count: the complete buffers of 65 536 samples from first_sample on, max_buffers at the most."""
+    return int(load_library().gvtm_analysis_buffer_count(int(n_samples), int(first_sample), int(max_buffers)))
+
+
+class Analysis:
+    """Owns a gvtm_analysis: the interactive window's spectrum and signal views of synthesized audio (include/gama_vtm.h,
+    "Spectrum analysis").  device=DEVICE_NONE gives a design-only object: window, bin count and the host restatement."""
+
+    def __init__(self, window_type=WINDOW_BLACKMAN, window_size=ANALYSIS_FFT_SIZE, log_scale=True, min_db=-120.0, max_freq_hz=0.0,
+                 sample_rate=44100, device=0):
+        self._lib = load_library()
+        self._h = ctypes.c_void_p()
+        self.config = AnalysisConfig(int(window_type), int(window_size), int(bool(log_scale)), float(min_db), float(max_freq_hz), int(sample_rate))
+        _check(self._lib, self._lib.gvtm_analysis_create(int(device), ctypes.byref(self.config), ctypes.byref(self._h)))
+        self.window_size = int(window_size)
+        self.n_bins = _count(self._lib, self._lib.gvtm_analysis_bin_count(self._h))
+
+    def close(self):
+        if self._h:
+            self._lib.gvtm_analysis_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def window(self):
+        """The window's W doubles, as designed on the host."""
+        out = np.empty(self.window_size, dtype=np.float64)
+        _check(self._lib, self._lib.gvtm_analysis_window(self._h, _ptr(out), out.size))
+        return out
+
+    def reserve(self, n_buffers):
+        """gvtm_analysis_reserve: device scratch for n_buffers buffers in flight (synchronous)."""
+        _check(self._lib, self._lib.gvtm_analysis_reserve(self._h, int(n_buffers)))
+
+    def apply_host(self, samples, first_sample=0, max_buffers=1, spectra=True, signal=True, fill=np.nan):
+        """gvtm_analysis_apply_host on one utterance's samples -> (spectra float32 [max_buffers][n_bins] or None, signal
+        float32 [max_buffers][W] or None, the number of buffers analysed); rows behind it keep `fill`."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        spec = np.full((int(max_buffers), self.n_bins), fill, dtype=np.float32) if spectra else None
+        sig = np.full((int(max_buffers), self.window_size), fill, dtype=np.float32) if signal else None
+        n = ctypes.c_size_t(0)
+        _check(self._lib, self._lib.gvtm_analysis_apply_host(self._h, _ptr(samples), samples.size, int(first_sample), int(max_buffers), _ptr(spec),
+                                                             _ptr(sig), ctypes.byref(n)))
+        return spec, sig, int(n.value)
+
+    def analyze_device(self, d_audio, audio_stride, d_counts, batch, max_buffers, d_first=None, d_spectra=None, d_signal=None,
+                       d_buffers_out=None, stream=None):
+        """gvtm_analyze_spectrum_device, enqueue-only: device tensors (or pointers) in the layouts the header gives."""
+        _check(self._lib, self._lib.gvtm_analyze_spectrum_device(self._h, _ptr(d_audio), int(audio_stride), _ptr(d_counts), _ptr(d_first), int(batch),
+                                                                 int(max_buffers), _ptr(d_spectra), _ptr(d_signal), _ptr(d_buffers_out), _ptr(stream)))
 
 
 class Plan:

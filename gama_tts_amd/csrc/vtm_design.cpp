@@ -4,6 +4,7 @@
 // reproduce; tests/test_capi_cpu.py compares every table with the oracle
 // bit for bit through gvtm_plan_table().
 #include "vtm_design.hpp"
+#include "vtm_analysis.hpp"
 #include "vtm_intonation.hpp"
 
 #include <algorithm>
@@ -719,6 +720,70 @@ int64_t intonation_apply(int cp, bool smooth, const gvtm_event* events, size_t n
 		if (at_point) ++j;
 	}
 	return merged;
+}
+
+// ---- spectrum analysis (vtm_analysis.hpp) ----
+
+// AnalysisWindow::setupWindow (gama_tts_editor/src/interactive/AnalysisWindow.cpp:303-361), expression by expression
+bool design_analysis_window(int type, unsigned size, std::vector<double>& out)
+{
+	const unsigned int windowSize = size;
+	out.assign(windowSize, 0.0);
+	switch (type) {
+	case GVTM_WINDOW_RECTANGULAR:
+		for (unsigned int i = 0; i < windowSize; ++i) out[i] = 1.0;
+		return true;
+	case GVTM_WINDOW_TRIANGULAR: {
+		const double center = (windowSize - 1) / 2.0;
+		for (unsigned int i = 0; i < windowSize; ++i) out[i] = 1.0 - std::abs((i - center) / center);
+		return true;
+	}
+	case GVTM_WINDOW_HANN: {
+		const double coef = 2.0 * M_PI / (windowSize - 1);
+		for (unsigned int i = 0; i < windowSize; ++i) out[i] = 0.5 * (1.0 - std::cos(coef * i));
+		return true;
+	}
+	case GVTM_WINDOW_HAMMING: {
+		const double alpha = 0.53836;
+		const double beta = 0.46164;
+		const double coef = 2.0 * M_PI / (windowSize - 1);
+		for (unsigned int i = 0; i < windowSize; ++i) out[i] = alpha - beta * std::cos(coef * i);
+		return true;
+	}
+	case GVTM_WINDOW_BLACKMAN: {
+		const double alpha = 0.16;
+		const double a0 = (1.0 - alpha) / 2.0;
+		const double a1 = 0.5;
+		const double a2 = alpha / 2.0;
+		const double coef1 = 2.0 * M_PI / (windowSize - 1);
+		const double coef2 = 2.0 * coef1;
+		for (unsigned int i = 0; i < windowSize; ++i) out[i] = a0 - a1 * std::cos(coef1 * i) + a2 * std::cos(coef2 * i);
+		return true;
+	}
+	default:
+		return false;
+	}
+}
+
+// showData's plotX_[i] = i * freqCoef and the loop that cuts the plot at the first plotX_[i] > maxFreq (:257-290)
+size_t design_analysis_bin_count(unsigned sample_rate, double max_freq)
+{
+	if (!(max_freq > 0.0)) return kAnalysisBins;
+	const double freqCoef = static_cast<double>(sample_rate) / kAnalysisSize;
+	for (unsigned int i = 0; i < static_cast<unsigned int>(kAnalysisBins); ++i) {
+		if (i * freqCoef > max_freq) return i;
+	}
+	return kAnalysisBins;
+}
+
+void design_analysis_twiddles(std::vector<float>& out)
+{
+	out.resize(2 * static_cast<size_t>(kAnalysisHalf));
+	for (int k = 0; k < kAnalysisHalf; ++k) {
+		const double angle = 2.0 * M_PI * k / kAnalysisSize;
+		out[2 * k] = static_cast<float>(std::cos(angle));
+		out[2 * k + 1] = static_cast<float>(-std::sin(angle));
+	}
 }
 
 } // namespace gvtm

@@ -58,6 +58,10 @@
  *                               (reference model 5, which the window constructs: gvtm_stream_push_targets_model5);
  *                               gvtm_synthesize_targets_voices_device: the same for a batch that mixes voices
  *                               (reference model 5: gvtm_synthesize_targets_model5_voices_device)
+ *   gvtm_analysis_* / gvtm_analyze_spectrum_device
+ *                               the same window's analysis view: AnalysisWindow::showData and setupWindow
+ *                               (gama_tts_editor/src/interactive/AnalysisWindow.cpp:189-361) on each full ring of 65 536
+ *                               output samples (InteractiveAudio.cpp:146-158, 192-205), for a batch of audio rows
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
@@ -1257,6 +1261,95 @@ int gvtm_synthesize_events_packed_host_pcm16(gvtm_plan* plan, const gvtm_event* 
 int gvtm_generate_tracks_host(int device, const gvtm_track_config* config, const gvtm_event* events,
 		const int64_t* event_offsets, size_t batch, size_t max_frames, float* params, int32_t* frame_counts,
 		gvtm_drift_state* drift);
+
+/*
+ * Spectrum analysis: the listening half of the editor's interactive window.  There every output sample also goes into a
+ * ring of 65 536 samples (InteractiveAudio.cpp:146-158, 192-205), and AnalysisWindow::showData (AnalysisWindow.cpp:189-300)
+ * turns each full ring into the picture the user watches while moving the sliders.  Here: for a whole batch, on the audio
+ * rows and out_counts every synthesis entry leaves on the device, so that a closed loop compares a few thousand bins and
+ * not 256 KB of samples per buffer.
+ *
+ * The rule, for one buffer s[0 .. 65536) of float samples:
+ *   1. peak      maxValue = the largest |s[i]| over all 65 536 samples, not only the window's.  maxValue > 0: normCoef =
+ *                (float)(1.0 / (double)maxValue) and s[i] = s[i] * normCoef (a float product); 0: the samples stay.
+ *   2. signal    the window's "Signal" view: the first W normalised samples, unwindowed.
+ *   3. spectrum  x[i] = (float)((double)s[i] * window[i]) for i < W and 0 behind; X = the 65 536-point real DFT of x in
+ *                float; mag[i] = sqrt(re^2 + im^2) / 256; linear: mag[i]; log: 20 log10(mag[i]), min_db where that is
+ *                below min_db (an empty bin, log10(0) = -inf, is min_db); the bins 0 .. n_bins - 1, n_bins the first i with
+ *                i * ((double)sample_rate / 65536) > max_freq_hz, else 32 769; max_freq_hz <= 0: all 32 769.
+ *   4. buffers   an utterance's buffers are consecutive and complete, as the ring hands them over: buffer k is the samples
+ *                [first + 65536 k, first + 65536 (k + 1)); min(max_buffers, floor((count - first) / 65536)) are analysed,
+ *                none if first > count (or first < 0).
+ * The window scales its output by a running peak before it reaches the ring; step 1 removes any constant scale, so these
+ * entries take the unscaled samples the synthesis entries write.
+ * Steps 1 and 2 are the reference's bit for bit.  The float DFT is not FFTW's bit for bit (float transforms differ by their
+ * factorisation): the yardstick is the double DFT of the same x, which the device's float transform (twiddles from one
+ * table designed in double) and the host's restatement (a double transform rounded to float at the end) both approximate;
+ * tests/analysis_cases.py gives the bars.  Measured: profiles/analysis_ab.md.
+ */
+#define GVTM_ANALYSIS_FFT_SIZE 65536
+#define GVTM_ANALYSIS_MAX_BINS 32769
+#define GVTM_ANALYSIS_DEFAULT_BUFFERS 128 /* what gvtm_analysis_create reserves on a device: 64 MB of scratch, which stays
+                                             in the device's caches; batches of thousands of buffers run some 10 % faster
+                                             with gvtm_analysis_reserve(1024), 512 MB */
+#define GVTM_WINDOW_RECTANGULAR 0 /* AnalysisWindow.cpp's order (WINDOW_RECTANGULAR ...) */
+#define GVTM_WINDOW_TRIANGULAR 1
+#define GVTM_WINDOW_HANN 2
+#define GVTM_WINDOW_HAMMING 3
+#define GVTM_WINDOW_BLACKMAN 4
+
+/* window_size: a power of two in [32, 65536]; log_scale: 0 linear, otherwise log; sample_rate: Hz, not 0.  Anything else
+ * (a NaN min_db or max_freq_hz included) is GVTM_ERR_INVALID_ARGUMENT. */
+struct gvtm_analysis_config {
+	int32_t window_type;
+	int32_t window_size;
+	int32_t log_scale;
+	double min_db;
+	double max_freq_hz;
+	uint32_t sample_rate;
+};
+typedef struct gvtm_analysis_config gvtm_analysis_config;
+typedef struct gvtm_analysis gvtm_analysis;
+
+/* Designs the window (the reference's five formulas in double, on the host) and counts the bins; on a device it also
+ * uploads the window and the twiddle table and reserves scratch for GVTM_ANALYSIS_DEFAULT_BUFFERS buffers in flight.
+ * device GVTM_DEVICE_NONE: a design-only object, whose device entry returns GVTM_ERR_NO_DEVICE, as plans do. */
+int gvtm_analysis_create(int device, const gvtm_analysis_config* config, gvtm_analysis** analysis_out);
+void gvtm_analysis_destroy(gvtm_analysis* analysis);
+/* n_bins; (size_t)-1 for a null object */
+size_t gvtm_analysis_bin_count(const gvtm_analysis* analysis);
+/* the window's W doubles; capacity in doubles */
+int gvtm_analysis_window(const gvtm_analysis* analysis, double* window_out, size_t capacity);
+/* step 4: the buffers analysed of an utterance of n_samples samples */
+size_t gvtm_analysis_buffer_count(int64_t n_samples, int64_t first_sample, size_t max_buffers);
+/* Device scratch for n_buffers (>= 1) buffers in flight: 512 KB each, the two intermediate images of the transform, which
+ * at the default stay in the device's caches.  Synchronous (it waits for the device before it frees the old scratch); the
+ * one place an allocation happens after creation.  A batch with more buffers than reserved runs in slices over the same
+ * scratch, one after the other on the caller's stream, with the same results. */
+int gvtm_analysis_reserve(gvtm_analysis* analysis, size_t n_buffers);
+/* The rule on the host for one utterance, the DFT a plain double transform rounded to float at the end: the restatement
+ * the tests pin, not a fast path.  samples [n_samples]; spectra_out [max_buffers][n_bins] or NULL; signal_out
+ * [max_buffers][W] or NULL (not both); n_buffers_out (may be NULL): the buffers analysed; rows behind them are left
+ * untouched.  Works on a design-only object. */
+int gvtm_analysis_apply_host(const gvtm_analysis* analysis, const float* samples, size_t n_samples, size_t first_sample,
+		size_t max_buffers, float* spectra_out, float* signal_out, size_t* n_buffers_out);
+/* The rule for a batch on the device, enqueue-only on hip_stream: it allocates nothing, copies nothing synchronously and
+ * never waits, so it may follow a synthesis entry on the same stream without synchronisation in between.
+ *   d_audio, audio_stride   float [batch][audio_stride]: the rows a synthesis entry wrote
+ *   d_counts                int64 [batch]: the samples of each row (a synthesis entry's out_counts); a count above
+ *                           audio_stride is taken as audio_stride
+ *   d_first                 int64 [batch], or NULL for 0: each utterance's first analysed sample; any index, odd ones too
+ *   d_spectra               float [batch][max_buffers][n_bins], or NULL
+ *   d_signal                float [batch][max_buffers][W], or NULL
+ *   d_buffers_out           int32 [batch] (may be NULL): gvtm_analysis_buffer_count of each utterance
+ * Rows of d_spectra and d_signal behind an utterance's buffer count are left untouched.  Calls on one object must be
+ * ordered on one stream (they share its scratch).
+ * Refused with GVTM_ERR_INVALID_ARGUMENT: a null object; with batch > 0 and max_buffers > 0, null d_audio or d_counts, both
+ * outputs null, or batch * max_buffers above 2^31.  A design-only object: GVTM_ERR_NO_DEVICE.  batch or max_buffers 0:
+ * GVTM_OK (d_buffers_out is then zeroed for max_buffers 0). */
+int gvtm_analyze_spectrum_device(gvtm_analysis* analysis, const float* d_audio, size_t audio_stride, const int64_t* d_counts,
+		const int64_t* d_first, size_t batch, size_t max_buffers, float* d_spectra, float* d_signal,
+		int32_t* d_buffers_out, void* hip_stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
