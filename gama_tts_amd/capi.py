@@ -209,6 +209,12 @@ def _prototypes():
         "gvtm_analysis_reserve": (i, [vp, sz]),
         "gvtm_analysis_apply_host": (i, [vp, vp, sz, sz, sz, vp, vp, vp]),
         "gvtm_analyze_spectrum_device": (i, [vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp]),
+        "gvtm_listen_buffer_count": (sz, [i64, i64, vp]),
+        "gvtm_stream_listen": (i, [vp, vp, sz, i]),
+        "gvtm_stream_unlisten": (i, [vp]),
+        "gvtm_stream_listen_state": (i, [vp, vp, vp]),
+        "gvtm_stream_take_spectra": (i, [vp, vp, vp, vp]),
+        "gvtm_stream_peek_spectra_device": (i, [vp, vp, vp, vp]),
     }
     hooks = {
         "gvtm_debug_set_rows": (i, [vp, i]),
@@ -585,6 +591,16 @@ class AnalysisConfig(ctypes.Structure):
     """gvtm_analysis_config"""
     _fields_ = [("window_type", ctypes.c_int32), ("window_size", ctypes.c_int32), ("log_scale", ctypes.c_int32),
                 ("min_db", ctypes.c_double), ("max_freq_hz", ctypes.c_double), ("sample_rate", ctypes.c_uint32)]
+
+
+LISTEN_SPECTRA, LISTEN_SIGNAL = 1, 2  # GVTM_LISTEN_*
+
+
+def listen_buffer_count(fill, n_new):
+    """gvtm_listen_buffer_count -> (the buffers n_new more samples complete on a ring holding `fill`, the ring's fill afterwards)."""
+    after = ctypes.c_int64(0)
+    n = load_library().gvtm_listen_buffer_count(int(fill), int(n_new), ctypes.byref(after))
+    return int(n), int(after.value)
 
 
 def analysis_buffer_count(n_samples, first_sample, max_buffers):
@@ -1171,6 +1187,7 @@ class Stream:
         self._lib = plan._lib
         self._h = ctypes.c_void_p()
         self.batch = int(batch)
+        self._listener = None
         if voice_ids is None:
             plan._check(self._lib.gvtm_stream_create(plan._h, self.batch, ctypes.byref(self._h)))
         else:
@@ -1204,25 +1221,26 @@ class Stream:
     def capacity(self, max_new_frames):
         return int(self._lib.gvtm_stream_capacity(self._h, int(max_new_frames)))
 
-    def push(self, params, frame_counts=None):
-        """params float32 [batch][F][16] -> list of float32 arrays, the new samples of each utterance."""
+    def push(self, params, frame_counts=None, audio=True):
+        """params float32 [batch][F][16] -> list of float32 arrays, the new samples of each utterance.  audio=False (a listening
+        stream only): no sample leaves the device -> int64 [batch], the samples synthesized."""
         params = np.ascontiguousarray(params, dtype=np.float32)
         assert params.ndim == 3 and params.shape[0] == self.batch and params.shape[2] == N_PARAM
         frames = params.shape[1]
         stride = self.capacity(frames)
-        audio = np.zeros((self.batch, stride), dtype=np.float32)
+        out = np.zeros((self.batch, stride), dtype=np.float32) if audio else None
         counts = np.zeros(self.batch, dtype=np.int64)
         fc = None
         if frame_counts is not None:
             fc = np.ascontiguousarray(frame_counts, dtype=np.int32)
-        self._plan._check(self._lib.gvtm_stream_push(self._h, _ptr(params), _ptr(fc), frames, _ptr(audio), stride, _ptr(counts)))
-        return [audio[b, : counts[b]].copy() for b in range(self.batch)]
+        self._plan._check(self._lib.gvtm_stream_push(self._h, _ptr(params), _ptr(fc), frames, _ptr(out), stride, _ptr(counts)))
+        return self._samples(out, counts)
 
-    def push_events(self, utterances, stride=None):
+    def push_events(self, utterances, stride=None, audio=True):
         """gvtm_stream_push_events.  utterances[b]: the event tables (float64 [E][38] rows, events_from_table) of the chunks
         utterance b receives in this push, possibly none -> (list of float32 arrays, the new samples of each utterance;
         int32 [batch], the frames generated per utterance).  stride: the audio row length, by default capacity() of the
-        largest frame total of the push."""
+        largest frame total of the push.  audio=False (a listening stream only): int64 [batch] in the samples' place."""
         assert len(utterances) == self.batch
         events, chunk_offsets, utt_chunks = Plan.pack_event_lists(utterances)
         if stride is None:
@@ -1233,12 +1251,12 @@ class Stream:
                                              chunk_offsets[utt_chunks[b]: utt_chunks[b + 1] + 1] - chunk_offsets[utt_chunks[b]])
                    for b in range(self.batch)]
             stride = self.capacity(max(new))
-        audio = np.zeros((self.batch, max(int(stride), 1)), dtype=np.float32)
+        out = np.zeros((self.batch, max(int(stride), 1)), dtype=np.float32) if audio else None
         counts = np.zeros(self.batch, dtype=np.int64)
         frames = np.zeros(self.batch, dtype=np.int32)
-        self._plan._check(self._lib.gvtm_stream_push_events(self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks), _ptr(audio),
+        self._plan._check(self._lib.gvtm_stream_push_events(self._h, _ptr(events), _ptr(chunk_offsets), _ptr(utt_chunks), _ptr(out),
                                                             int(stride), _ptr(counts), _ptr(frames)))
-        return [audio[b, : counts[b]].copy() for b in range(self.batch)], frames
+        return self._samples(out, counts), frames
 
     def targets_capacity(self, max_new_steps):
         """gvtm_stream_targets_capacity: the row length for a push_targets or finish that adds up to max_new_steps steps."""
@@ -1250,19 +1268,20 @@ class Stream:
         self._plan._check(self._lib.gvtm_stream_targets_points(self._h, _ptr(held)))
         return held
 
-    def push_targets(self, utterances, step_counts, max_steps=None):
+    def push_targets(self, utterances, step_counts, max_steps=None, audio=True):
         """gvtm_stream_push_targets.  utterances[b]: utterance b's 16 lists of (steps, values), the steps counted from the
         first step this push adds; step_counts: the steps each utterance advances by (an int: all of them by that many) ->
         list of float32 arrays, the new samples of each utterance.  A refused push raises GvtmError, whose `statuses` are
-        the utterances' (int32 [batch])."""
-        return self._push_targets(self._lib.gvtm_stream_push_targets, utterances, step_counts, max_steps)
+        the utterances' (int32 [batch]).  audio=False (a listening stream only): no sample leaves the device -> int64
+        [batch], the samples synthesized."""
+        return self._push_targets(self._lib.gvtm_stream_push_targets, utterances, step_counts, max_steps, audio)
 
-    def push_targets_model5(self, utterances, step_counts, max_steps=None):
+    def push_targets_model5(self, utterances, step_counts, max_steps=None, audio=True):
         """push_targets for a stream of a one-voice model 5 plan of either class (gvtm_stream_push_targets_model5): the samples
         are the interactive window's model's, in pieces of gvtm_synthesize_targets_model5_device's."""
-        return self._push_targets(self._lib.gvtm_stream_push_targets_model5, utterances, step_counts, max_steps)
+        return self._push_targets(self._lib.gvtm_stream_push_targets_model5, utterances, step_counts, max_steps, audio)
 
-    def _push_targets(self, entry, utterances, step_counts, max_steps):
+    def _push_targets(self, entry, utterances, step_counts, max_steps, audio=True):
         assert len(utterances) == self.batch and all(len(u) == N_PARAM for u in utterances)
         counts_in = None if isinstance(step_counts, int) else np.ascontiguousarray(step_counts, dtype=np.int32)
         assert counts_in is None or counts_in.shape == (self.batch,)
@@ -1270,15 +1289,15 @@ class Stream:
             max_steps = step_counts if counts_in is None else max(int(counts_in.max()), 0)
         offsets, steps, values = pack_targets([l for u in utterances for l in u])
         stride = self.targets_capacity(max_steps)
-        audio = np.zeros((self.batch, stride), dtype=np.float32)
+        out = np.zeros((self.batch, stride), dtype=np.float32) if audio else None
         counts = np.zeros(self.batch, dtype=np.int64)
         statuses = np.full(self.batch, -1, dtype=np.int32)
-        rc = entry(self._h, _ptr(offsets), _ptr(steps), _ptr(values), _ptr(counts_in), int(max_steps), _ptr(audio), stride, _ptr(counts), _ptr(statuses))
+        rc = entry(self._h, _ptr(offsets), _ptr(steps), _ptr(values), _ptr(counts_in), int(max_steps), _ptr(out), stride, _ptr(counts), _ptr(statuses))
         if rc != 0:
             error = GvtmError(rc, self._lib.gvtm_last_error().decode() or self._lib.gvtm_status_string(rc).decode())
             error.statuses = statuses
             raise error
-        return [audio[b, : counts[b]].copy() for b in range(self.batch)]
+        return self._samples(out, counts)
 
     def get_drift(self):
         """-> float64 [batch][5]: the drift generators' states (seed, x1, x2, y1, y2), one per utterance."""
@@ -1293,11 +1312,54 @@ class Stream:
             assert states.shape == (self.batch, 5)
         self._plan._check(self._lib.gvtm_stream_set_drift(self._h, _ptr(states)))
 
-    def finish(self):
-        """-> (list of float32 arrays, maxabs float32 [batch])"""
+    def finish(self, audio=True):
+        """-> (list of float32 arrays, maxabs float32 [batch]); audio=False (a listening stream only): int64 [batch], the
+        samples synthesized, in the arrays' place."""
         stride = self.capacity(0)
-        audio = np.zeros((self.batch, stride), dtype=np.float32)
+        out = np.zeros((self.batch, stride), dtype=np.float32) if audio else None
         counts = np.zeros(self.batch, dtype=np.int64)
         maxabs = np.zeros(self.batch, dtype=np.float32)
-        self._plan._check(self._lib.gvtm_stream_finish(self._h, _ptr(audio), stride, _ptr(counts), _ptr(maxabs)))
-        return [audio[b, : counts[b]].copy() for b in range(self.batch)], maxabs
+        self._plan._check(self._lib.gvtm_stream_finish(self._h, _ptr(out), stride, _ptr(counts), _ptr(maxabs)))
+        return self._samples(out, counts), maxabs
+
+    def _samples(self, out, counts):
+        """What a push or finish returns for its samples: each utterance's new ones, or without audio their counts."""
+        if out is None:
+            return counts
+        return [out[b, : counts[b]].copy() for b in range(self.batch)]
+
+    def listen(self, analysis, max_buffers, spectra=True, signal=False):
+        """gvtm_stream_listen: from here on (a fresh stream) every utterance keeps the interactive window's analysis ring on the
+        device, and each push queues the views of the rings it completes, max_buffers per utterance between two takes."""
+        views = (LISTEN_SPECTRA if spectra else 0) | (LISTEN_SIGNAL if signal else 0)
+        self._plan._check(self._lib.gvtm_stream_listen(self._h, analysis._h, int(max_buffers), views))
+        self._listener = (analysis, int(max_buffers), bool(spectra), bool(signal))  # (keeps the analysis object alive)
+
+    def unlisten(self):
+        self._plan._check(self._lib.gvtm_stream_unlisten(self._h))
+        self._listener = None
+
+    def listen_state(self):
+        """-> (int64 [batch], the samples in each ring; int32 [batch], the buffers queued)"""
+        fill, queued = np.zeros(self.batch, dtype=np.int64), np.zeros(self.batch, dtype=np.int32)
+        self._plan._check(self._lib.gvtm_stream_listen_state(self._h, _ptr(fill), _ptr(queued)))
+        return fill, queued
+
+    def take_spectra(self, fill=np.nan, copy=True):
+        """gvtm_stream_take_spectra -> (spectra float32 [batch][max_buffers][n_bins] or None, signal float32
+        [batch][max_buffers][W] or None, int32 [batch] the buffers taken); rows behind an utterance's count keep `fill`.
+        copy=False: the queues are only emptied -> (None, None, counts)."""
+        analysis, max_buffers, spectra, signal = self._listener
+        spec = np.full((self.batch, max_buffers, analysis.n_bins), fill, dtype=np.float32) if spectra and copy else None
+        sig = np.full((self.batch, max_buffers, analysis.window_size), fill, dtype=np.float32) if signal and copy else None
+        taken = np.zeros(self.batch, dtype=np.int32)
+        self._plan._check(self._lib.gvtm_stream_take_spectra(self._h, _ptr(spec), _ptr(sig), _ptr(taken)))
+        return spec, sig, taken
+
+    def peek_spectra_device(self):
+        """gvtm_stream_peek_spectra_device -> (d_spectra, d_signal, d_queued): device addresses (int; None for a view not
+        kept) of the queues in take_spectra's layout and of the int32 [batch] queued counts, valid until the next call on
+        the stream."""
+        pointers = [ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()]
+        self._plan._check(self._lib.gvtm_stream_peek_spectra_device(self._h, *[ctypes.byref(p) for p in pointers]))
+        return tuple(p.value for p in pointers)

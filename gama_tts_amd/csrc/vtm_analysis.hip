@@ -37,16 +37,17 @@ __device__ __forceinline__ int64_t utterance_buffers(const AnalysisArgs& a, size
 }
 
 // The pair of slot `slot` of this launch: false if it lies behind the batch or behind its utterance's buffers; else its
-// number (the row of the outputs) and its samples.
-__device__ __forceinline__ bool slot_pair(const AnalysisArgs& a, size_t slot, size_t& pair, const float*& samples)
+// row of the outputs (its number, or with a slot table its place in the utterance's block) and its samples.
+__device__ __forceinline__ bool slot_pair(const AnalysisArgs& a, size_t slot, size_t& row, const float*& samples)
 {
-	pair = a.first_pair + slot;
+	const size_t pair = a.first_pair + slot;
 	// (a batch has fewer than 2^31 pairs: 32-bit division)
 	const size_t b = static_cast<unsigned>(pair) / static_cast<unsigned>(a.max_buffers), k = static_cast<unsigned>(pair) % static_cast<unsigned>(a.max_buffers);
 	if (b >= a.batch) return false;
 	int64_t first;
 	if (static_cast<int64_t>(k) >= utterance_buffers(a, b, first)) return false;
 	samples = a.audio + b * a.audio_stride + static_cast<size_t>(first) + k * static_cast<size_t>(kAnalysisSize);
+	row = a.out_slots ? b * a.out_stride + static_cast<size_t>(a.out_slots[b]) + k : pair;
 	return true;
 }
 

@@ -305,6 +305,10 @@ struct AnalysisArgs {
 	float* spectra;                  // [batch][max_buffers][n_bins] or null
 	float* signal;                   // [batch][max_buffers][W] or null
 	int32_t* buffers_out;            // [batch] or null (written by the launch whose first_pair is 0)
+	// null: the outputs' row of pair (b, k) is the pair's number, b * max_buffers + k.  Else utterance b's buffers go to the
+	// rows out_slots[b] + k of its block of out_stride rows (a listening stream's queues: vtm_listen.hpp)
+	const int32_t* out_slots;        // [batch] or null
+	size_t out_stride;
 };
 
 // the kernels of one slice on `stream`: counts (first slice only), peak + signal view, and with spectra the passes A, B, C

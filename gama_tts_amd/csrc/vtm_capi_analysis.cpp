@@ -224,6 +224,22 @@ int gvtm_analyze_spectrum_device(gvtm_analysis* analysis, const float* d_audio, 
 	if (!work && (!d_buffers_out || !d_counts)) return GVTM_OK;
 	DeviceScope scope(analysis->device);
 	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	return analysis_enqueue(analysis, d_audio, audio_stride, d_counts, d_first, batch, max_buffers, d_spectra, d_signal, d_buffers_out, nullptr, 0,
+			static_cast<hipStream_t>(hip_stream));
+}
+
+} // extern "C"
+
+namespace gvtm::host {
+
+AnalysisFacts analysis_facts(const gvtm_analysis* analysis)
+{
+	return {analysis->device, analysis->config.sample_rate, analysis->n_bins, analysis->window.size()};
+}
+
+int analysis_enqueue(gvtm_analysis* analysis, const float* d_audio, size_t audio_stride, const int64_t* d_counts, const int64_t* d_first, size_t batch,
+		size_t max_buffers, float* d_spectra, float* d_signal, int32_t* d_buffers_out, const int32_t* d_out_slots, size_t out_stride, hipStream_t stream)
+{
 	gvtm::AnalysisArgs args{};
 	args.audio = d_audio;
 	args.audio_stride = audio_stride;
@@ -243,6 +259,8 @@ int gvtm_analyze_spectrum_device(gvtm_analysis* analysis, const float* d_audio, 
 	args.spectra = d_spectra;
 	args.signal = d_signal;
 	args.buffers_out = d_buffers_out;
+	args.out_slots = d_out_slots;
+	args.out_stride = out_stride;
 	// slices of the pairs (utterance, buffer) over the reserved scratch, one after the other on the caller's stream
 	if (analysis->reserved == 0) return fail(GVTM_ERR_OUT_OF_MEMORY, "no scratch reserved (the last gvtm_analysis_reserve failed)");
 	const size_t pairs = batch * max_buffers;
@@ -250,10 +268,10 @@ int gvtm_analyze_spectrum_device(gvtm_analysis* analysis, const float* d_audio, 
 	do {
 		args.first_pair = p0;
 		args.n_pairs = std::min(analysis->reserved, pairs - p0);
-		if (const hipError_t e = gvtm::launch_analysis(args, static_cast<hipStream_t>(hip_stream)); e != hipSuccess) return fail_hip(e, "analysis launch");
+		if (const hipError_t e = gvtm::launch_analysis(args, stream); e != hipSuccess) return fail_hip(e, "analysis launch");
 		p0 += args.n_pairs;
 	} while (p0 < pairs);
 	return GVTM_OK;
 }
 
-} // extern "C"
+} // namespace gvtm::host

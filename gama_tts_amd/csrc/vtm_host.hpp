@@ -428,4 +428,16 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r);
 // a one-shot launch's rows hold max_frames frames of every voice
 int check_audio_stride(const gvtm_plan* plan, size_t audio_stride, size_t max_frames, bool voices);
 
+// What a listening stream needs of an analysis object (vtm_capi_analysis.cpp, which alone knows the structure): its facts,
+// and the slices of gvtm_analyze_spectrum_device behind that entry's checks, enqueue-only on `stream` with the object's device
+// current.  d_out_slots (or null) and out_stride: gvtm::AnalysisArgs::out_slots.
+struct AnalysisFacts {
+	int device;
+	uint32_t sample_rate;
+	size_t n_bins, W;
+};
+AnalysisFacts analysis_facts(const gvtm_analysis* analysis);
+int analysis_enqueue(gvtm_analysis* analysis, const float* d_audio, size_t audio_stride, const int64_t* d_counts, const int64_t* d_first, size_t batch,
+		size_t max_buffers, float* d_spectra, float* d_signal, int32_t* d_buffers_out, const int32_t* d_out_slots, size_t out_stride, hipStream_t stream);
+
 } // namespace gvtm::host

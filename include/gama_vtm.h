@@ -62,6 +62,9 @@
  *                               the same window's analysis view: AnalysisWindow::showData and setupWindow
  *                               (gama_tts_editor/src/interactive/AnalysisWindow.cpp:189-361) on each full ring of 65 536
  *                               output samples (InteractiveAudio.cpp:146-158, 192-205), for a batch of audio rows
+ *   gvtm_stream_listen / gvtm_stream_take_spectra
+ *                               that ring itself, kept on the device for every utterance of a stream: each push leaves
+ *                               the views of the rings it completed ("Streams that listen")
  *   gvtm_plan_create_voices / gvtm_plan_create_model5_voices / gvtm_plan_create_model5_float_voices /
  *   gvtm_synthesize_voices_*
  *                               the same for a batch that mixes voices: one VocalTractModel per GamaTTS voice variant
@@ -1350,6 +1353,69 @@ int gvtm_analysis_apply_host(const gvtm_analysis* analysis, const float* samples
 int gvtm_analyze_spectrum_device(gvtm_analysis* analysis, const float* d_audio, size_t audio_stride, const int64_t* d_counts,
 		const int64_t* d_first, size_t batch, size_t max_buffers, float* d_spectra, float* d_signal,
 		int32_t* d_buffers_out, void* hip_stream);
+
+/*
+ * Streams that listen: the two halves of the interactive window in one object.  In the reference
+ * InteractiveAudio::Processor::process writes every output sample into the analysis ring as it is produced
+ * (InteractiveAudio.cpp:146-158, 192-205) and the window reads the ring whenever it is full (AnalysisWindow.cpp:199-225).
+ * gvtm_stream_listen gives a stream that ring, on the device, for every utterance of its batch: each push then leaves the
+ * spectra (and signal views) of the rings it completed in a queue on the device, and need not return audio at all.
+ *
+ * The rule (the ring hands over consecutive, complete buffers: step 4 of the analysis rule above):
+ *   - an utterance's samples since the stream's last reset are numbered from 0, in the order the pushes and the finish
+ *     return them; its buffer k is the samples [65536 k, 65536 (k + 1));
+ *   - a buffer is analysed when the launch that brings its last sample has run;
+ *   - an incomplete ring is never analysed, not at gvtm_stream_finish either: the window shows nothing until the ring is full.
+ * Two things the reference does are deliberately not reproduced:
+ *   - the JACK ring drops samples while the GUI timer has not yet consumed a full ring; here no sample is dropped;
+ *   - the window scales samples by its running peak before they reach the ring.  Step 1 of the analysis rule removes a
+ *     constant scale; the running one depends on JACK's period size, so it is not a property of the model.
+ * Contract: utterance b's queued spectra and signal views, fed in any grouping by any of the stream's feeds, are bit for bit
+ * the rows k of what gvtm_analyze_spectrum_device writes for the same analysis object with first = 0 on the utterance's whole
+ * sample sequence (the pushes' and the finish's samples concatenated) -- where the stream contract makes those samples
+ * bit-identical to the one-shot entry's, on that entry's row.  The arithmetic of the analysis does not depend on where a
+ * buffer lies or how it is aligned; only the width of the loads does.
+ *
+ * A listening stream is taken as it is by every push entry (gvtm_stream_push, _push_events, _push_targets,
+ * _push_targets_model5) and by gvtm_stream_finish, whatever its voices, model and precision.  On it `audio` may be NULL although
+ * samples are due: audio_stride is then ignored, out_counts is still filled, and no sample leaves the device.  One refusal is
+ * added, behind the entry's own and before anything is launched or kept: a call that would complete more buffers than an
+ * utterance's queue has room for is GVTM_ERR_INVALID_ARGUMENT and leaves the stream exactly as found; the same call succeeds
+ * after gvtm_stream_take_spectra.  (Every sample count is known before the launch: gvtm_listen_buffer_count.)
+ * gvtm_stream_reset and _reset_voices empty rings and queues and keep the listener; gvtm_stream_destroy frees them.  A stream
+ * that does not listen is what it has always been: no kernel, allocation or upload is added to its launches, and a NULL
+ * audio with samples due is refused.
+ * The analysis object must outlive the listener.  Calls on streams that share one analysis object must not overlap: they
+ * share its scratch.  A launch analyses the rings it completes in slices of the object's reserved scratch
+ * (gvtm_analysis_reserve), as the one-shot entry does.
+ */
+#define GVTM_LISTEN_SPECTRA 1
+#define GVTM_LISTEN_SIGNAL 2
+
+/* The rule's arithmetic: the buffers completed by n_new more samples on a ring holding `fill` samples, and in *fill_after
+ * (may be NULL) what the ring holds afterwards.  A fill outside [0, 65536) or a negative n_new: 0, the fill unchanged. */
+size_t gvtm_listen_buffer_count(int64_t fill, int64_t n_new, int64_t* fill_after);
+/* Allocates on the stream's device a ring of 65 536 floats per utterance and, for the views asked for (GVTM_LISTEN_*, or'ed),
+ * a queue of max_buffers analysed buffers per utterance.  Called again on a fresh stream it replaces the listener.
+ * GVTM_ERR_INVALID_ARGUMENT: null arguments, max_buffers 0, views 0 or with unknown bits, an analysis object on another
+ * device than the stream's plan, an analysis sample_rate that is not the output_rate of every voice of the plan, a stream
+ * fed since its last reset (the ring starts with the utterance).  GVTM_ERR_NO_DEVICE: a design-only analysis object.
+ * GVTM_ERR_OUT_OF_MEMORY: a failed allocation; the stream is left not listening. */
+int gvtm_stream_listen(gvtm_stream* stream, gvtm_analysis* analysis, size_t max_buffers, int views);
+/* Frees the rings and queues; allowed at any time.  The stream then synthesizes on as one that never listened. */
+int gvtm_stream_unlisten(gvtm_stream* stream);
+/* The samples in each ring and the buffers queued (either may be NULL). */
+int gvtm_stream_listen_state(const gvtm_stream* stream, int64_t* fill_out /* [batch] */, int32_t* queued_out /* [batch] */);
+/* Copies utterance b's queued buffers to the rows 0 .. queued[b] - 1 of its block of the host arrays and leaves the rows behind
+ * them untouched, writes the counts to buffers_out and empties the queues.  With both arrays NULL it only empties.  A
+ * non-null array of a view not asked for at gvtm_stream_listen: GVTM_ERR_INVALID_ARGUMENT. */
+int gvtm_stream_take_spectra(gvtm_stream* stream, float* spectra /* [batch][max_buffers][n_bins] host, or NULL */,
+		float* signal /* [batch][max_buffers][W] host, or NULL */, int32_t* buffers_out /* [batch], or NULL */);
+/* Hands out the queues where they lie on the device, in the layout of take (NULL for a view not kept), and a device table
+ * of the queued counts, for loops whose comparison runs on the device.  Empties nothing.  The pointers stay valid until the
+ * next call on the stream.  Any of the three may be NULL. */
+int gvtm_stream_peek_spectra_device(const gvtm_stream* stream, const float** d_spectra, const float** d_signal,
+		const int32_t** d_queued);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
