@@ -241,6 +241,10 @@ def _prototypes():
         "gvtm_debug_tracks_append": (i, [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]),
         "gvtm_debug_tracks_slice": (i, [vp, vp, i64, vp, vp, vp, vp, sz, sz, vp, vp, vp, vp]),
         "gvtm_debug_carry_rows": (i, [vp, vp, vp, vp, sz, sz]),
+        "gvtm_debug_listen_copy": (i, [i, vp, sz, vp, sz, vp, vp, vp, sz, i64]),
+        "gvtm_debug_listen_move": (i, [i64, i64, vp]),
+        "gvtm_debug_analyze_slots": (i, [vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
+        "gvtm_debug_analysis_float_host": (i, [vp, vp, vp]),
     }
     return product, hooks
 
@@ -610,11 +614,12 @@ def analysis_buffer_count(n_samples, first_sample, max_buffers):
 
 class Analysis:
     """Owns a gvtm_analysis: the interactive window's spectrum and signal views of synthesized audio (include/gama_vtm.h,
-    "Spectrum analysis").  device=DEVICE_NONE gives a design-only object: window, bin count and the host restatement."""
+    "Spectrum analysis").  device=DEVICE_NONE gives a design-only object: window, bin count and the host restatement.
+    diagnostics=True binds the object to libgama_vtm_diag.so, whose gvtm_debug_* hooks the last two methods call."""
 
     def __init__(self, window_type=WINDOW_BLACKMAN, window_size=ANALYSIS_FFT_SIZE, log_scale=True, min_db=-120.0, max_freq_hz=0.0,
-                 sample_rate=44100, device=0):
-        self._lib = load_library()
+                 sample_rate=44100, device=0, diagnostics=False):
+        self._lib = load_library(diagnostics)
         self._h = ctypes.c_void_p()
         self.config = AnalysisConfig(int(window_type), int(window_size), int(bool(log_scale)), float(min_db), float(max_freq_hz), int(sample_rate))
         _check(self._lib, self._lib.gvtm_analysis_create(int(device), ctypes.byref(self.config), ctypes.byref(self._h)))
@@ -658,6 +663,39 @@ class Analysis:
         """gvtm_analyze_spectrum_device, enqueue-only: device tensors (or pointers) in the layouts the header gives."""
         _check(self._lib, self._lib.gvtm_analyze_spectrum_device(self._h, _ptr(d_audio), int(audio_stride), _ptr(d_counts), _ptr(d_first), int(batch),
                                                                  int(max_buffers), _ptr(d_spectra), _ptr(d_signal), _ptr(d_buffers_out), _ptr(stream)))
+
+    def debug_analyze_slots(self, d_audio, audio_stride, d_counts, batch, max_buffers, d_out_slots, out_stride, d_first=None, d_spectra=None,
+                            d_signal=None, d_buffers_out=None, stream=None):
+        """gvtm_debug_analyze_slots (diagnostics): analyze_device with utterance b's buffers at the rows d_out_slots[b] + k of its
+        block of out_stride rows of the outputs."""
+        _check(self._lib, self._lib.gvtm_debug_analyze_slots(self._h, _ptr(d_audio), int(audio_stride), _ptr(d_counts), _ptr(d_first), int(batch),
+                                                             int(max_buffers), _ptr(d_spectra), _ptr(d_signal), _ptr(d_buffers_out), _ptr(d_out_slots),
+                                                             int(out_stride), _ptr(stream)))
+
+    def debug_float_host(self, samples):
+        """gvtm_debug_analysis_float_host (diagnostics): the linear spectrum [n_bins] of one buffer of 65 536 samples by the
+        float transform of csrc/vtm_analysis.hpp run on the host."""
+        samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+        assert samples.size == ANALYSIS_FFT_SIZE, samples.size
+        out = np.full(self.n_bins, np.nan, dtype=np.float32)
+        _check(self._lib, self._lib.gvtm_debug_analysis_float_host(self._h, _ptr(samples), _ptr(out)))
+        return out
+
+
+def debug_listen_move(fill, n):
+    """gvtm_debug_listen_move (diagnostics): listen_move(fill, n) of csrc/vtm_listen.hpp as a dict of its six fields."""
+    out = np.zeros(6, dtype=np.int64)
+    lib = load_library(True)
+    _check(lib, lib.gvtm_debug_listen_move(int(fill), int(n), _ptr(out)))
+    return dict(zip(("buffers", "fill_after", "head_len", "inside_first", "tail_src", "tail_len"), (int(v) for v in out)))
+
+
+def debug_listen_copy(d_src, src_stride, d_dst, dst_stride, d_src_off, d_dst_off, d_len, batch, max_len, device=0):
+    """gvtm_debug_listen_copy (diagnostics): the ragged copy of a listening stream alone on device tensors (or pointers),
+    synchronous."""
+    lib = load_library(True)
+    _check(lib, lib.gvtm_debug_listen_copy(int(device), _ptr(d_src), int(src_stride), _ptr(d_dst), int(dst_stride), _ptr(d_src_off), _ptr(d_dst_off),
+                                           _ptr(d_len), int(batch), int(max_len)))
 
 
 class Plan:

@@ -79,11 +79,15 @@ GVTM_ANALYSIS_HD float analysis_windowed(float normalised, double window)
 }
 
 // what is shown for a bin of magnitude mag (already scaled by 1/256)
+// A bin that is no number (a NaN or an infinity among the window's samples, a peak so small that normCoef is inf) is shown
+// as the one quiet NaN 0x7fc00000, linear or log: IEEE 754 leaves the sign of a NaN result to the lanes, and the host's
+// make ffc00000 of inf - inf where the device's make 7fc00000, so without this the same text gave other bits on either.
 GVTM_ANALYSIS_HD float analysis_level(float mag, bool log_scale, float min_db)
 {
+	if (mag != mag) return __builtin_nanf("");
 	if (!log_scale) return mag;
 	const float db = 20.0f * log10f(mag);
-	return db < min_db ? min_db : db; // (-inf, and the NaN of a NaN bin stays)
+	return db < min_db ? min_db : db; // (-inf: an empty bin is min_db)
 }
 
 // ---- the float transform ----

@@ -1,8 +1,12 @@
 // The gvtm_debug_* hooks of the diagnostics library (libgama_vtm_diag.so; tests and tools only, not in the public header
 // and not in the product library): forced shapes, taps, cycle counters, math probes and single kernels on caller buffers.
+#include <cmath>
 #include <cstring>
+#include <new>
 
 #include "vtm_host.hpp"
+#include "vtm_analysis.hpp"
+#include "vtm_listen.hpp"
 #include "vtm_math.hpp"
 
 using namespace gvtm::host;
@@ -307,6 +311,96 @@ int gvtm_debug_carry_rows(gvtm_plan* plan, float* d_params, const int32_t* d_don
 	DeviceScope scope(plan->device);
 	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
 	return finish_kernel(gvtm::launch_carry_rows(gvtm::CarryArgs{d_params, d_done, d_held, batch, max_frames}, nullptr), "vtm_carry_rows_kernel");
+}
+
+/* Test hook: the ragged copy of a listening stream alone (launch_listen_copy, vtm_listen.hpp), on device buffers of the
+ * caller's on `device`: utterance b's d_len[b] samples from d_src + b * src_stride + d_src_off[b] to d_dst + b * dst_stride +
+ * d_dst_off[b]; the three tables are int64 [batch]; max_len sizes the grid.  Synchronous. */
+int gvtm_debug_listen_copy(int device, const float* d_src, size_t src_stride, float* d_dst, size_t dst_stride, const int64_t* d_src_off,
+		const int64_t* d_dst_off, const int64_t* d_len, size_t batch, int64_t max_len)
+{
+	if (!d_src || !d_dst || !d_src_off || !d_dst_off || !d_len) return fail(GVTM_ERR_INVALID_ARGUMENT, "null buffer");
+	if (const int rc = check_device_index(device, "gvtm_debug_listen_copy"); rc != GVTM_OK) return rc;
+	DeviceScope scope(device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	return finish_kernel(gvtm::launch_listen_copy(gvtm::ListenCopyArgs{d_src, src_stride, d_dst, dst_stride, d_src_off, d_dst_off, d_len, batch}, max_len, nullptr),
+			"listen_copy_kernel");
+}
+
+/* Test hook: listen_move(fill, n) of vtm_listen.hpp: out = {buffers, fill_after, head_len, inside_first, tail_src, tail_len}.
+ * Needs no device. */
+int gvtm_debug_listen_move(int64_t fill, int64_t n, int64_t out[6])
+{
+	if (!out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null buffer");
+	const gvtm::ListenMove m = gvtm::listen_move(fill, n);
+	out[0] = m.buffers, out[1] = m.fill_after, out[2] = m.head_len, out[3] = m.inside_first, out[4] = m.tail_src, out[5] = m.tail_len;
+	return GVTM_OK;
+}
+
+/* Test hook: analysis_enqueue (the body of gvtm_analyze_spectrum_device behind its checks) with a slot table of the
+ * caller's: utterance b's buffers go to the rows d_out_slots[b] + k of its block of out_stride rows of d_spectra and d_signal
+ * (gvtm::AnalysisArgs::out_slots; int32 [batch] on the device).  The other arguments are that entry's; enqueue-only. */
+int gvtm_debug_analyze_slots(gvtm_analysis* analysis, const float* d_audio, size_t audio_stride, const int64_t* d_counts, const int64_t* d_first,
+		size_t batch, size_t max_buffers, float* d_spectra, float* d_signal, int32_t* d_buffers_out, const int32_t* d_out_slots, size_t out_stride,
+		void* hip_stream)
+{
+	if (!analysis || !d_audio || !d_counts || !d_out_slots || (!d_spectra && !d_signal)) return fail(GVTM_ERR_INVALID_ARGUMENT, "null argument");
+	if (batch == 0 || max_buffers == 0 || batch > 0x7fffffffu || max_buffers > 0x7fffffffu || batch * max_buffers > 0x7fffffffu) {
+		return fail(GVTM_ERR_INVALID_ARGUMENT, "batch * max_buffers must lie in [1, 2^31)");
+	}
+	const AnalysisFacts facts = analysis_facts(analysis);
+	if (facts.device == GVTM_DEVICE_NONE) return fail(GVTM_ERR_NO_DEVICE, "design-only analysis");
+	DeviceScope scope(facts.device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	return analysis_enqueue(analysis, d_audio, audio_stride, d_counts, d_first, batch, max_buffers, d_spectra, d_signal, d_buffers_out, d_out_slots,
+			out_stride, static_cast<hipStream_t>(hip_stream));
+}
+
+/* Test hook: steps 1 and 3 of the analysis rule for one buffer samples[65536], with the float transform of vtm_analysis.hpp
+ * run on the host: the very functions the kernels of vtm_analysis.hip call (analysis_pass_a, analysis_pass_b,
+ * analysis_untangle, analysis_magnitude, analysis_level), workgroup by workgroup, phase by phase (the end of a loop over
+ * tid is the kernel's barrier), thread by thread, u, v, T and Z plain arrays.  spectra_out[n_bins] takes the linear
+ * spectrum whatever the object's log_scale.  This file is built without FMA contraction, as vtm_analysis.hip is, so every
+ * operation is the one IEEE float operation the device runs.  Works on a design-only object; needs no device. */
+int gvtm_debug_analysis_float_host(const gvtm_analysis* analysis, const float* samples, float* spectra_out)
+{
+	if (!analysis || !samples || !spectra_out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null argument");
+	try {
+		const AnalysisFacts facts = analysis_facts(analysis);
+		const unsigned W = static_cast<unsigned>(facts.W);
+		std::vector<double> window(W);
+		if (const int rc = gvtm_analysis_window(analysis, window.data(), window.size()); rc != GVTM_OK) return rc;
+		std::vector<float> twiddles;
+		gvtm::design_analysis_twiddles(twiddles);
+		std::vector<gvtm::AnalysisComplex> table(gvtm::kAnalysisHalf);
+		std::memcpy(table.data(), twiddles.data(), sizeof(gvtm::AnalysisComplex) * table.size());
+		// step 1, as analysis_peak_kernel's lanes take it: a NaN never becomes the maximum
+		float max_value = 0.0f;
+		for (int i = 0; i < gvtm::kAnalysisSize; ++i) max_value = fmaxf(max_value, fabsf(samples[i]));
+		const float coef = gvtm::analysis_norm_coef(max_value);
+		const bool aligned8 = (reinterpret_cast<uintptr_t>(samples) & 7) == 0;
+		std::vector<gvtm::AnalysisComplex> u(gvtm::kAnalysisImagePadded), v(gvtm::kAnalysisImagePadded), T(gvtm::kAnalysisHalf), Z(gvtm::kAnalysisHalf);
+		for (unsigned g = 0; g < gvtm::kAnalysisGroupsA; ++g) {
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_a<0>(tid, g, samples, coef, window.data(), W, aligned8, table.data(), u.data(), v.data(), T.data());
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_a<1>(tid, g, samples, coef, window.data(), W, aligned8, table.data(), u.data(), v.data(), T.data());
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_a<2>(tid, g, samples, coef, window.data(), W, aligned8, table.data(), u.data(), v.data(), T.data());
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_a<3>(tid, g, samples, coef, window.data(), W, aligned8, table.data(), u.data(), v.data(), T.data());
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_a<4>(tid, g, samples, coef, window.data(), W, aligned8, table.data(), u.data(), v.data(), T.data());
+		}
+		for (unsigned h = 0; h < gvtm::kAnalysisGroupsB; ++h) {
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_b<0>(tid, h, T.data(), table.data(), u.data(), v.data(), Z.data());
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_b<1>(tid, h, T.data(), table.data(), u.data(), v.data(), Z.data());
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_b<2>(tid, h, T.data(), table.data(), u.data(), v.data(), Z.data());
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_b<3>(tid, h, T.data(), table.data(), u.data(), v.data(), Z.data());
+			for (unsigned tid = 0; tid < gvtm::kAnalysisThreads; ++tid) gvtm::analysis_pass_b<4>(tid, h, T.data(), table.data(), u.data(), v.data(), Z.data());
+		}
+		for (unsigned k = 0; k < facts.n_bins; ++k) {
+			spectra_out[k] = gvtm::analysis_level(gvtm::analysis_magnitude(gvtm::analysis_untangle(Z.data(), table.data(), k)), false, 0.0f);
+		}
+		return GVTM_OK;
+	} catch (const std::bad_alloc&) {
+		return fail(GVTM_ERR_OUT_OF_MEMORY, "host allocation failed");
+	}
 }
 
 #pragma GCC visibility pop

@@ -63,9 +63,12 @@ def normalised(buf):
     """Step 1 on one buffer of 65 536 float32 samples."""
     buf = np.asarray(buf, dtype=np.float32)
     assert buf.shape == (N,)
-    peak = np.abs(buf).max()
+    # the reference's loop is `if (absValue > maxValue) maxValue = absValue` from 0: a NaN is never greater, so it never becomes
+    # the peak (np.abs(buf).max() would make it one); an infinity does, and the coefficient is then 0
+    peak = np.fmax.reduce(np.abs(buf), initial=np.float32(0.0))
     if peak > 0:
-        return buf * np.float32(1.0 / np.float64(peak))
+        with np.errstate(over="ignore", invalid="ignore"):  # (a denormal peak's coefficient is inf; inf * 0 is NaN, as in C)
+            return buf * np.float32(1.0 / np.float64(peak))
     return buf.copy()
 
 
@@ -140,6 +143,85 @@ def empty_input(W):
     if W < N:
         s[W] = 1.0
     return s
+
+
+FIVE_COUNTS = [0, 65535, 65536, 140000, 200000]
+
+
+def five_rows():
+    """The ragged batch of test_gpu_analysis.py (its five_rows fixture, the same samples): five rows of one stride whose counts
+    are FIVE_COUNTS; the samples behind a row's count are there and must not be read as buffers."""
+    rng = np.random.default_rng(55)
+    return [(0.3 * rng.standard_normal(FIVE_COUNTS[-1])).astype(np.float32) for _ in FIVE_COUNTS]
+
+
+# ---- the float transform bit for bit (test_analysis_float_cpu.py, test_gpu_analysis_edges.py) ----
+
+# every W at which the cut 2 n < W of analysis_input meets the column split n = 16 g + f + 128 n2 differently (W <= 256: inside
+# one n2, the first g only up to 32; 512: two n2; above: many), under Blackman; and all five windows at 512
+FLOAT_WINDOWS = [(W, BLACKMAN) for W in (32, 64, 128, 256, 512, 1024, 65536)] + [(512, kind) for kind in (RECTANGULAR, TRIANGULAR, HANN, HAMMING)]
+# the inputs of inputs() the device is held to the host run of the same butterflies on
+BITWISE_INPUTS = ("noise", "golden", "sine-between", "impulse-odd")
+
+
+def ulp_distance(a, b):
+    """The largest distance in float32 steps between two arrays of finite floats (0: the same bits, but for the sign of 0)."""
+    def ordered(x):
+        bits = x.view(np.int32).astype(np.int64)
+        return np.where(bits < 0, -(bits & 0x7fffffff), bits)
+    return int(np.abs(ordered(np.ascontiguousarray(a, dtype=np.float32)) - ordered(np.ascontiguousarray(b, dtype=np.float32))).max())
+
+
+# ---- the value edges of step 1 (test_analysis_cpu.py, test_gpu_analysis_edges.py): one buffer each, W 1024, rectangular ----
+
+EDGE_W = 1024
+# a peak in every lane of a DPP row of analysis_peak_kernel: with 4-byte loads sample p is lane p mod 16 of its row
+# (16 r + l), with 16-byte loads lane (p / 4) mod 16 (64 r + 4 l; 16 * 37 + l lies in the lanes 4 to 7); and the first and
+# last sample of the window, of a thread's loop and of the buffer
+PEAK_POSITIONS = [16 * 37 + l for l in range(16)] + [64 * 5 + 4 * l for l in range(16)] + [0, 63, 64, 1023, 1024, 4095, 4096, 65535]
+
+
+def _quiet(seed=99):
+    return np.random.default_rng(seed).uniform(-0.01, 0.01, N).astype(np.float32)
+
+
+def peak_position_cases():
+    """name -> buffer: noise of amplitude 0.01 with one sample of 0.75 at each of PEAK_POSITIONS; a negative peak; -0.0 only."""
+    cases = {}
+    for at in PEAK_POSITIONS:
+        cases["peak-at-%d" % at] = _quiet()
+        cases["peak-at-%d" % at][at] = 0.75
+    cases["negative-peak"] = _quiet()
+    cases["negative-peak"][16 * 37 + 9] = -0.75
+    cases["minus-zero-only"] = np.full(N, -0.0, dtype=np.float32)
+    return cases
+
+
+def extreme_peak_cases():
+    """name -> buffer whose peak is a float denormal (the coefficient overflows to inf), the smallest normal, FLT_MAX (the
+    coefficient is a denormal), and 3e38 beside 1e38; the other samples are that peak times 0.1 to 0.9, either sign."""
+    rng = np.random.default_rng(98)
+    shape = (rng.uniform(0.1, 0.9, N) * rng.choice([-1.0, 1.0], N))
+    cases = {}
+    for name, peak in [("denormal", np.float32(1e-40)), ("tiny", np.finfo(np.float32).tiny), ("flt-max", np.finfo(np.float32).max), ("3e38", np.float32(3e38))]:
+        buf = (shape * np.float64(peak)).astype(np.float32)
+        buf[123] = peak
+        if name == "3e38":
+            buf[124] = np.float32(1e38)
+        assert np.abs(buf).max() == peak and (buf != 0).all()
+        cases[name] = buf
+    return cases
+
+
+def non_finite_cases():
+    """name -> buffer of noise and a peak of 0.75 with one sample that is no number: behind or inside the window of EDGE_W."""
+    cases = {}
+    for name, at, value in [("nan-behind", 2000, np.nan), ("nan-inside", 100, np.nan), ("inf-behind", 2000, np.inf), ("minus-inf-inside", 100, -np.inf)]:
+        buf = _quiet(97)
+        buf[500] = 0.75
+        buf[at] = value
+        cases[name] = buf
+    return cases
 
 
 def check_log(out, linear, min_db):

@@ -93,13 +93,29 @@ def test_signal_view_is_the_normalised_samples_bit_for_bit(golden_audio):
     negative[40000] = -0.8125 * 3  # the peak is negative
     late = rng.uniform(-0.01, 0.01, ac.N).astype(np.float32)
     late[60000] = 0.3  # the peak lies far behind a window of 32
+    # the value edges of step 1: a sample that is no number (a NaN never becomes the peak, an infinity does), a peak whose
+    # coefficient is inf or a denormal, and -0.0 only
+    edges = {**ac.non_finite_cases(), **ac.extreme_peak_cases(), "minus-zero-only": ac.peak_position_cases()["minus-zero-only"]}
     for name, samples, W in [("negative-peak", negative, 1024), ("late-peak", late, 32), ("silence", np.zeros(ac.N, dtype=np.float32), 1024),
-                             ("golden", golden_audio, 65536), ("golden", golden_audio, 32)]:
+                             ("golden", golden_audio, 65536), ("golden", golden_audio, 32)] + [(name, s, ac.EDGE_W) for name, s in edges.items()]:
         _, signal, n = make(W).apply_host(samples, spectra=False)
         assert n == 1, name
         want = ac.normalised(samples[: ac.N])[:W]
         assert np.array_equal(signal[0].view(np.uint32), want.view(np.uint32)), name
     assert np.abs(ac.normalised(late)[:32]).max() < 0.05 and ac.normalised(negative).min() == -1.0
+    # what the edges are, so that the table cannot lose them: the NaN behind the window changes nothing in front of it, the one
+    # inside stays the only NaN; an infinite peak makes every finite sample a zero and itself a NaN; a denormal peak's
+    # coefficient is inf, FLT_MAX's a denormal
+    nan_behind, nan_inside = (ac.normalised(edges[name])[: ac.EDGE_W] for name in ("nan-behind", "nan-inside"))
+    assert np.isfinite(nan_behind).all() and nan_behind.max() == 1.0
+    assert np.flatnonzero(np.isnan(nan_inside)).tolist() == [100] and np.nanmax(nan_inside) == 1.0
+    assert (ac.normalised(edges["inf-behind"])[: ac.EDGE_W] == 0).all()
+    minus_inf = ac.normalised(edges["minus-inf-inside"])[: ac.EDGE_W]
+    assert np.flatnonzero(np.isnan(minus_inf)).tolist() == [100] and (np.delete(minus_inf, 100) == 0).all()
+    assert np.isinf(ac.normalised(edges["denormal"])).all()
+    flt_max = ac.normalised(edges["flt-max"])
+    assert 0.99 < flt_max.max() <= 1.0 and np.float32(1.0 / np.float64(np.finfo(np.float32).max)) < np.finfo(np.float32).tiny
+    assert np.array_equal(ac.normalised(edges["minus-zero-only"]).view(np.uint32), np.full(ac.N, 0x80000000, dtype=np.uint32))
 
 
 @pytest.mark.parametrize("W,kind", WINDOWS)
