@@ -192,6 +192,8 @@ def _prototypes():
         "gvtm_synthesize_targets_model5_voices_device": (i, [vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
         "gvtm_stream_push_targets": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
         "gvtm_stream_push_targets_model5": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "gvtm_stream_push_targets_voices": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
+        "gvtm_stream_push_targets_model5_voices": (i, [vp, vp, vp, vp, vp, sz, vp, sz, vp, vp]),
         "gvtm_stream_targets_capacity": (sz, [vp, sz]),
         "gvtm_stream_targets_points": (i, [vp, vp]),
         "gvtm_stream_push_events": (i, [vp, vp, vp, vp, vp, sz, vp, vp]),
@@ -243,6 +245,7 @@ def _prototypes():
         "gvtm_debug_carry_rows": (i, [vp, vp, vp, vp, sz, sz]),
         "gvtm_debug_listen_copy": (i, [i, vp, sz, vp, sz, vp, vp, vp, sz, i64]),
         "gvtm_debug_listen_move": (i, [i64, i64, vp]),
+        "gvtm_debug_stream_targets_sums": (i, [vp, vp]),
         "gvtm_debug_analyze_slots": (i, [vp, vp, sz, vp, vp, sz, sz, vp, vp, vp, vp, sz, vp]),
         "gvtm_debug_analysis_float_host": (i, [vp, vp, vp]),
     }
@@ -1306,6 +1309,15 @@ class Stream:
         self._plan._check(self._lib.gvtm_stream_targets_points(self._h, _ptr(held)))
         return held
 
+    def targets_sums(self):
+        """gvtm_debug_stream_targets_sums (a stream of a diagnostics model 5 plan) -> float64 [batch][16]: the targets filters'
+        sums as every utterance's block of the device state holds them."""
+        if not self._plan.diagnostics:
+            raise ValueError("targets_sums reads the state through a hook of the diagnostics library: make the plan with diagnostics=True")
+        sums = np.zeros((self.batch, N_PARAM), dtype=np.float64)
+        self._plan._check(self._lib.gvtm_debug_stream_targets_sums(self._h, _ptr(sums)))
+        return sums
+
     def push_targets(self, utterances, step_counts, max_steps=None, audio=True):
         """gvtm_stream_push_targets.  utterances[b]: utterance b's 16 lists of (steps, values), the steps counted from the
         first step this push adds; step_counts: the steps each utterance advances by (an int: all of them by that many) ->
@@ -1318,6 +1330,17 @@ class Stream:
         """push_targets for a stream of a one-voice model 5 plan of either class (gvtm_stream_push_targets_model5): the samples
         are the interactive window's model's, in pieces of gvtm_synthesize_targets_model5_device's."""
         return self._push_targets(self._lib.gvtm_stream_push_targets_model5, utterances, step_counts, max_steps, audio)
+
+    def push_targets_voices(self, utterances, step_counts, max_steps=None, audio=True):
+        """push_targets under the stream's own voices (gvtm_stream_push_targets_voices; a VoicesPlan of the models 0 to 4, or
+        a one-voice plan): utterance b walks its lists through its voice's filter, in pieces of
+        gvtm_synthesize_targets_voices_device's samples."""
+        return self._push_targets(self._lib.gvtm_stream_push_targets_voices, utterances, step_counts, max_steps, audio)
+
+    def push_targets_model5_voices(self, utterances, step_counts, max_steps=None, audio=True):
+        """push_targets_model5 under the stream's own voices (gvtm_stream_push_targets_model5_voices; a model 5 plan of several
+        voices of either class, or a one-voice one): in pieces of gvtm_synthesize_targets_model5_voices_device's samples."""
+        return self._push_targets(self._lib.gvtm_stream_push_targets_model5_voices, utterances, step_counts, max_steps, audio)
 
     def _push_targets(self, entry, utterances, step_counts, max_steps, audio=True):
         assert len(utterances) == self.batch and all(len(u) == N_PARAM for u in utterances)

@@ -337,6 +337,14 @@ int gvtm_debug_listen_move(int64_t fill, int64_t n, int64_t out[6])
 	return GVTM_OK;
 }
 
+/* Test hook: the 16 sums of the targets filters in every utterance's block of a model 5 stream's device state, out [batch][16]
+ * (host memory; synchronous).  A targets-fed launch leaves utterance b's sums in b's own block whichever workgroup ran it:
+ * under several voices the workgroup's index is not the utterance's. */
+int gvtm_debug_stream_targets_sums(const gvtm_stream* stream, double* out)
+{
+	return stream_download_targets_sums(stream, out);
+}
+
 /* Test hook: analysis_enqueue (the body of gvtm_analyze_spectrum_device behind its checks) with a slot table of the
  * caller's: utterance b's buffers go to the rows d_out_slots[b] + k of its block of out_stride rows of d_spectra and d_signal
  * (gvtm::AnalysisArgs::out_slots; int32 [batch] on the device).  The other arguments are that entry's; enqueue-only. */

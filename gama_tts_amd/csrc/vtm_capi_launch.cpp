@@ -170,9 +170,8 @@ int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r)
 	if (!r.audio) return fail(GVTM_ERR_INVALID_ARGUMENT, "null audio buffer");
 	if (r.voices && !r.voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
 	if (r.targets && !r.frame_counts) return fail(GVTM_ERR_UNSUPPORTED, "targets: a launch with step counts");
-	// (several voices, model 5 as well: a one-shot launch, with the plan's filter lengths by voice; a stream's launches from
-	// targets are of one voice in either model family)
-	if (r.targets && r.voices && (r.sl || !r.targets->voice_N || !r.targets->voice_invN)) return fail(GVTM_ERR_UNSUPPORTED, "targets of several voices: one-shot launches only");
+	// (several voices, model 5 as well, one-shot or a stream's: with the plan's filter lengths by voice)
+	if (r.targets && r.voices && (!r.targets->voice_N || !r.targets->voice_invN)) return fail(GVTM_ERR_UNSUPPORTED, "targets of several voices: a launch with the plan's filter lengths by voice");
 	if (r.max_frames > 0 && !r.params && !r.targets) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	// (several voices: the row map's int32 slots also count up to n_voices partly empty workgroups)
 	if (r.batch > (r.voices ? 0x3fffffffu : 0x7fffffffu)) return fail(GVTM_ERR_INVALID_ARGUMENT, "batch too large for one launch");

@@ -52,15 +52,18 @@ struct gvtm_stream {
 	std::vector<int32_t> counts;
 	bool finished = false;
 	// how the stream has been fed since the last reset: frames (gvtm_stream_push), event lists (gvtm_stream_push_events) or
-	// parameter targets (gvtm_stream_push_targets, model 5: gvtm_stream_push_targets_model5); one way per run
+	// parameter targets (gvtm_stream_push_targets, model 5: gvtm_stream_push_targets_model5; under the stream's several voices
+	// gvtm_stream_push_targets_voices and gvtm_stream_push_targets_model5_voices); one way per run
 	int feed = kFeedNone;
 	// a targets-fed run: utterance b's parameter p keeps in tg_log[16 b + p] the points the rule still needs in front of the
 	// utterance's next step (vtm_targets.hpp: targets_first_needed) -- every launch uploads them all, and they are few: those
 	// of the filter's window and of the pending steps, and one more -- and tg_pending[b] steps are pushed but not yet
-	// synthesized (fewer than tg_granule after a push).  The filters' sums are in the device state.
+	// synthesized (fewer than tg_granule after a push).  The filters' sums are in the device state.  tg_N[v] is the filter
+	// length of the plan's voice v (vtm_targets.hpp: targets_filter_length): utterance b's is its voice's, on the host here
+	// and in the kernel from the plan's table by voice.
 	std::vector<TargetsLog> tg_log;
 	std::vector<uint64_t> tg_pending;
-	int64_t tg_N = 0;
+	std::vector<int64_t> tg_N;
 	// a targets-fed run synthesizes in multiples of this many steps and keeps the rest: the steps at which the serial
 	// wavefronts' states are exact (create_stream: 12; model 5: 4)
 	uint64_t tg_granule = 0;
@@ -165,7 +168,7 @@ StreamSamples stream_samples(const gvtm_stream* s, const std::vector<size_t>& n_
 constexpr uint64_t kTargetsMostPending = 11;
 constexpr int32_t kTargetsNullTables = -1;
 
-// One utterance of a gvtm_stream_push_targets or gvtm_stream_push_targets_model5 call, `count` steps of at most max_steps with the 17 offsets `off`: the status
+// One utterance of a call of gvtm_stream_push_targets or of one of its three siblings, `count` steps of at most max_steps with the 17 offsets `off`: the status
 // of gvtm_targets_apply_host in its order, where a point at or beyond `count` is a bad step too (4); kTargetsNullTables for
 // points without their tables.
 int32_t targets_push_status(const int64_t* off, const int32_t* point_steps, const float* point_values, int64_t count, int64_t max_steps)
@@ -380,8 +383,13 @@ int stream_launch(gvtm_stream* s, const std::vector<size_t>& n_frames, bool fina
 	float* const d_rows_in = targets ? nullptr : on_device ? s->d_held.as<float>() : s->d_params.as<float>();
 	LaunchRequest request{d_rows_in, s->d_frames.as<int32_t>(), batch, rows_max, s->d_audio.as<float>(), audio_stride, s->d_counts.as<int64_t>(),
 			s->d_maxabs.as<float>(), nullptr, lockstep ? 0 : 1, s->voices, s->voices ? s->d_voice_ids.as<int32_t>() : nullptr, &s->d_groups, &sl};
-	const TargetsLaunch tl{s->d_tg_offsets.as<int64_t>(), nullptr, s->d_tg_steps.as<int32_t>(), s->d_tg_values.as<float>(), s->tg_N,
-			1.0 / static_cast<double>(std::max<int64_t>(s->tg_N, 1))};
+	// (several voices: the kernel reads its workgroup's voice's filter length from the plan's tables, as the one-shot entries')
+	TargetsLaunch tl{s->d_tg_offsets.as<int64_t>(), nullptr, s->d_tg_steps.as<int32_t>(), s->d_tg_values.as<float>(), s->tg_N[0],
+			1.0 / static_cast<double>(std::max<int64_t>(s->tg_N[0], 1))};
+	if (s->voices) {
+		tl.voice_N = plan->d_targets_N.as<int64_t>();
+		tl.voice_invN = plan->d_targets_invN.as<double>();
+	}
 	if (targets) request.targets = &tl;
 	rc = launch_synthesis(plan, request);
 	if (rc != GVTM_OK) return rc;
@@ -446,7 +454,7 @@ int create_stream(gvtm_plan* plan, size_t batch, const int32_t* voice_ids, gvtm_
 		s->steps_done.assign(batch, 0);
 		s->tg_log.resize(batch * GVTM_N_PARAM);
 		s->tg_pending.assign(batch, 0);
-		s->tg_N = gvtm::targets_filter_length(internal_rate_hz(plan->designs[0]));
+		for (const gvtm::Design& dv : plan->designs) s->tg_N.push_back(gvtm::targets_filter_length(internal_rate_hz(dv)));
 		DeviceScope scope(plan->device);
 		int rc = scope.entered();
 		// (one voice: every utterance's id is 0, which only the tracks kernel of an events-fed run reads)
@@ -530,9 +538,9 @@ int stream_append_and_launch(gvtm_stream* s, const gvtm_event* events, const int
 	return check_device_frame_counts(s->d_new_counts, batch, [&](size_t b) { return fresh[b]; });
 }
 
-// What gvtm_stream_push_targets and gvtm_stream_push_targets_model5 share, which is everything behind the choice of plans:
-// the refusals in their order, the status pass, the roll-back, the log, targets_forget and the launch.  The granule is the
-// stream's (tg_granule).
+// What gvtm_stream_push_targets, gvtm_stream_push_targets_model5 and their two siblings for the stream's several voices
+// share, which is everything behind the choice of plans: the refusals in their order, the status pass, the roll-back, the
+// log, targets_forget under the utterance's own voice and the launch.  The granule is the stream's (tg_granule).
 int stream_push_targets(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
 		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
 {
@@ -593,7 +601,8 @@ int stream_push_targets(gvtm_stream* s, const int64_t* list_offsets, const int32
 		if (rc != GVTM_OK && !launched) roll_back(); // (after the launch the device state has moved on: gvtm_stream_reset is the way out)
 		if (rc == GVTM_OK) {
 			for (size_t b = 0; b < batch; ++b) {
-				for (int p = 0; p < GVTM_N_PARAM; ++p) targets_forget(s->tg_log[b * GVTM_N_PARAM + p], static_cast<int64_t>(s->steps_done[b]), s->tg_N);
+				const int64_t N = s->tg_N[static_cast<size_t>(voice_of(s, b))];
+				for (int p = 0; p < GVTM_N_PARAM; ++p) targets_forget(s->tg_log[b * GVTM_N_PARAM + p], static_cast<int64_t>(s->steps_done[b]), N);
 			}
 		}
 		return rc;
@@ -604,6 +613,23 @@ int stream_push_targets(gvtm_stream* s, const int64_t* list_offsets, const int32
 }
 
 } // namespace
+
+namespace gvtm::host {
+
+int stream_download_targets_sums(const gvtm_stream* s, double* out)
+{
+	if (!s || !out) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream or buffer");
+	if (!s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "a stream of a model 5 plan");
+	DeviceScope scope(s->plan->device);
+	if (const int rc = scope.entered(); rc != GVTM_OK) return rc;
+	// (utterance b's sums: Stream5Layout::sums() into its own block, whichever workgroup synthesizes it)
+	constexpr size_t bytes = sizeof(double) * GVTM_N_PARAM;
+	const hipError_t e = hipMemcpy2D(out, bytes, static_cast<const unsigned char*>(s->d_state.ptr) + gvtm::Stream5Layout::sums(), s->state_stride, bytes, s->batch,
+			hipMemcpyDeviceToHost);
+	return e == hipSuccess ? GVTM_OK : fail_hip(e, "D2H stream state");
+}
+
+} // namespace gvtm::host
 
 extern "C" {
 
@@ -693,7 +719,7 @@ int gvtm_stream_push(gvtm_stream* s, const float* params, const int32_t* frame_c
 	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
 	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
 	if (s->feed == kFeedEvents) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed event lists (gvtm_stream_push_events) until the next gvtm_stream_reset()");
-	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets, model 5: gvtm_stream_push_targets_model5) until the next gvtm_stream_reset()");
+	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets, model 5: gvtm_stream_push_targets_model5, or their _voices forms) until the next gvtm_stream_reset()");
 	if (max_frames > 0 && !params) return fail(GVTM_ERR_INVALID_ARGUMENT, "null params with max_frames > 0");
 	if (frame_counts) {
 		for (size_t b = 0; b < s->batch; ++b) {
@@ -753,9 +779,14 @@ size_t gvtm_stream_targets_capacity(const gvtm_stream* s, size_t max_new_steps)
 {
 	if (!s) return static_cast<size_t>(-1);
 	// the new steps and what a push can have kept (one short of the largest granule: model 5 keeps 3 at most), flushed, with
-	// the overrun's lap
-	const gvtm::DeviceConstants& k = s->plan->designs[0].k;
-	return static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(max_new_steps) + kTargetsMostPending) + 1);
+	// the overrun's lap; the largest over the plan's voices, whichever the ids name (the rule create_stream sizes the state
+	// by: gvtm_stream_reset_voices never invalidates a stride)
+	size_t m = 0;
+	for (const gvtm::Design& dv : s->plan->designs) {
+		const gvtm::DeviceConstants& k = dv.k;
+		m = std::max(m, static_cast<size_t>(gvtm::src_output_capacity(k.time_inc, k.pad, k.upsampling, static_cast<uint64_t>(max_new_steps) + kTargetsMostPending) + 1));
+	}
+	return m;
 }
 
 int gvtm_stream_targets_points(const gvtm_stream* s, int64_t* held_out)
@@ -786,13 +817,31 @@ int gvtm_stream_push_targets_model5(gvtm_stream* s, const int64_t* list_offsets,
 	return stream_push_targets(s, list_offsets, point_steps, point_values, step_counts, max_steps, audio, audio_stride, out_counts, status_out);
 }
 
+// The two entries under the stream's own voices (gvtm_stream_create_voices, gvtm_stream_reset_voices): utterance b walks its
+// lists through its voice's filter.  On a one-voice plan each is the entry above it.
+int gvtm_stream_push_targets_voices(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
+		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
+{
+	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
+	if (s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets_voices: the models 0 to 4 only; model 5 has gvtm_stream_push_targets_model5_voices");
+	return stream_push_targets(s, list_offsets, point_steps, point_values, step_counts, max_steps, audio, audio_stride, out_counts, status_out);
+}
+
+int gvtm_stream_push_targets_model5_voices(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
+		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
+{
+	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
+	if (!s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets_model5_voices: model 5 only; the models 0 to 4 have gvtm_stream_push_targets_voices");
+	return stream_push_targets(s, list_offsets, point_steps, point_values, step_counts, max_steps, audio, audio_stride, out_counts, status_out);
+}
+
 int gvtm_stream_push_events(gvtm_stream* s, const gvtm_event* events, const int64_t* chunk_offsets, const int64_t* utt_chunks, float* audio,
 		size_t audio_stride, int64_t* out_counts, int32_t* frame_counts_out)
 {
 	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
 	if (s->finished) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream has been finished: gvtm_stream_reset() starts the next utterances");
 	if (s->feed == kFeedFrames) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed frames (gvtm_stream_push) until the next gvtm_stream_reset()");
-	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets, model 5: gvtm_stream_push_targets_model5) until the next gvtm_stream_reset()");
+	if (s->feed == kFeedTargets) return fail(GVTM_ERR_INVALID_ARGUMENT, "the stream is fed targets (gvtm_stream_push_targets, model 5: gvtm_stream_push_targets_model5, or their _voices forms) until the next gvtm_stream_reset()");
 	const gvtm_plan* plan = s->plan;
 	if (plan->voice_tracks.empty()) return fail(GVTM_ERR_INVALID_ARGUMENT, "gvtm_stream_push_events: the plan has no track configurations yet (gvtm_plan_set_voice_tracks)");
 	const size_t batch = s->batch;

@@ -427,6 +427,9 @@ struct LaunchRequest {
 int launch_synthesis(gvtm_plan* plan, const LaunchRequest& r);
 // a one-shot launch's rows hold max_frames frames of every voice
 int check_audio_stride(const gvtm_plan* plan, size_t audio_stride, size_t max_frames, bool voices);
+// The 16 sums of the targets filters as every utterance's block of a model 5 stream's device state holds them, out [batch][16]
+// (vtm_capi_stream.cpp, which alone knows the structure; the diagnostics library's gvtm_debug_stream_targets_sums)
+int stream_download_targets_sums(const gvtm_stream* stream, double* out);
 
 // What a listening stream needs of an analysis object (vtm_capi_analysis.cpp, which alone knows the structure): its facts,
 // and the slices of gvtm_analyze_spectrum_device behind that entry's checks, enqueue-only on `stream` with the object's device

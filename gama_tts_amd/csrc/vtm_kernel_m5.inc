@@ -173,8 +173,8 @@ constexpr int kFloat5Flag = 8;
 // the moving averages of the utterance's sixteen target lists (vtm_targets.hpp) instead of interpolating frames: a.frame_counts
 // holds steps, there are no frames and no control_steps.  And what enters the resampler is divided by the step's
 // fundamental frequency (VocalTractModel5.h:579): pass A1a keeps the f0 it forms for dt in the record rf0, which pass X
-// reads ten ticks later.  One voice, or with kVoices5Flag several in a one-shot launch (see the interpolation wavefront's
-// setup).  A stream's launches (gvtm_stream_push_targets_model5; one voice only) walk absolute steps from the
+// reads ten ticks later.  One voice, or with kVoices5Flag several (see the interpolation wavefront's
+// setup).  A stream's launches (gvtm_stream_push_targets_model5, several voices: _model5_voices) walk absolute steps from the
 // utterance's step_base on: behind step 0 the walk resumes on the 16 sums the previous launch left in the stream state
 // (targets_resume, Stream5Layout::sums; the points are the stream's log), and the epilogue stores them back.  The record rf0
 // carries nothing from launch to launch: chunk c's slot, c % 11, is written by A1a at tick c + 1 and read by X at tick
@@ -827,8 +827,9 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 	// A stream's launch walks absolute steps from the utterance's step_base on: behind step 0 the walk resumes on the sum the
 	// previous launch left in the stream state (targets_resume; the points are the stream's log, in absolute steps), and the
 	// epilogue stores the sum back.  An utterance the launch does not advance keeps its sums.
-	// Under several voices (kVoices5Flag with kTargets5Flag: gvtm_synthesize_targets_model5_voices_device, one-shot launches
-	// only) the utterance, and with it the slot of its lists, is the row map's, and the filter's length and reciprocal are the
+	// Under several voices (kVoices5Flag with kTargets5Flag: gvtm_synthesize_targets_model5_voices_device, and a stream's
+	// gvtm_stream_push_targets_model5_voices) the utterance, and with it the slot of its lists and of its sums in the stream
+	// state, is the row map's, and the filter's length and reciprocal are the
 	// workgroup's voice's, a.tg_voice_N[voice] and a.tg_voice_invN[voice], read once per workgroup as vtm_kernel_v2.inc does.
 	[[maybe_unused]] TargetsWalk tg{};
 	[[maybe_unused]] int64_t tg_base = 0;
@@ -846,7 +847,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 			const int64_t list = a.tg_ids ? static_cast<int64_t>(a.tg_ids[slot]) : static_cast<int64_t>(slot);
 			if (streaming) tg_base = static_cast<int64_t>(s_ext[ip_u].step_base);
 			if (tg_base > 0) {
-				const double* sums = reinterpret_cast<const double*>(a.stream + (group * U + ip_u) * a.stream_stride + Stream5Layout::sums());
+				const double* sums = reinterpret_cast<const double*>(a.stream + GVTM_M5_UTT(ip_u, (group * U + ip_u)) * a.stream_stride + Stream5Layout::sums());
 				targets_resume(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], tg_length(), tg_base, sums[Lp]);
 			} else {
 				targets_begin(tg, a.tg_steps, a.tg_values, a.tg_offsets[list], a.tg_offsets[list + 1], tg_length());
@@ -1338,7 +1339,7 @@ __global__ __launch_bounds__(m5_waves(U_FLAGS & 3, NH) * 64, m5_waves_per_simd(C
 			// the moving averages' sums of every utterance the launch advanced, push and finish alike (a push synthesizes a
 			// multiple of four steps, so no lane has run on into a partial block when its sum is stored)
 			if (role == 3 && ip_u < U && ip_frames > 0) {
-				double* sums = reinterpret_cast<double*>(a.stream + (group * U + ip_u) * a.stream_stride + Stream5Layout::sums());
+				double* sums = reinterpret_cast<double*>(a.stream + GVTM_M5_UTT(ip_u, (group * U + ip_u)) * a.stream_stride + Stream5Layout::sums());
 				sums[Lp] = tg.sum;
 			}
 		}

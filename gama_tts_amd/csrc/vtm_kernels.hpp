@@ -238,15 +238,16 @@ inline bool synth5_targets_args(const SynthArgs& args)
 }
 // the targets variants under several voices alone (vtm_kernels_m5tv.hip: the double class, its one-utterance shape;
 // vtm_kernels_m5ftv.hip: the float class, in its targets shape `index`; launch_synth5 calls them where args.tg_offsets and
-// args.row_map are both set): `groups` workgroups of launch_group_voices' map, one utterance each, one-shot launches only
+// args.row_map are both set): `groups` workgroups of launch_group_voices' map, one utterance each, one-shot launches and a
+// stream's (args.stream: the points are the stream's log, in absolute steps, and every state address follows the row map)
 hipError_t launch_synth5_targets_voices(const SynthArgs& args, size_t groups, hipStream_t stream);
 hipError_t launch_synth5_float_targets_voices(const SynthArgs& args, size_t groups, int index, hipStream_t stream);
 // what both ask of their arguments: the row map and the groups' voices, the lists, the steps in frame_counts, the filter's
-// length and reciprocal by voice; no stream
+// length and reciprocal by voice
 inline bool synth5_targets_voices_args(const SynthArgs& args)
 {
 	return args.k5const && args.row_map && args.group_voice && args.tg_offsets && args.tg_steps && args.tg_values && args.frame_counts && args.tg_voice_N &&
-	       args.tg_voice_invN && !args.stream;
+	       args.tg_voice_invN;
 }
 constexpr int kDppSelftestInts = 640;
 hipError_t launch_dpp_selftest(int* d_out /* [kDppSelftestInts] */, hipStream_t stream);

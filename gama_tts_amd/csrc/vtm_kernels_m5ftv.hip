@@ -1,6 +1,6 @@
 // The targets variant of the reference model 5 kernel under several voices, in the float class (vtm5_synth_kernel with
-// kFloat5Flag, kTargets5Flag and kVoices5Flag: gvtm_synthesize_targets_model5_voices_device on a
-// gvtm_plan_create_model5_float_voices plan), in both targets shapes of the float class.  A code object of its own: those of
+// kFloat5Flag, kTargets5Flag and kVoices5Flag: gvtm_synthesize_targets_model5_voices_device and a stream's
+// gvtm_stream_push_targets_model5_voices on a gvtm_plan_create_model5_float_voices plan), in both targets shapes of the float class.  A code object of its own: those of
 // vtm_kernels_m5fv.hip and vtm_kernels_m5ft.hip keep exactly the kernels they had.  Compiled with -ffp-contract=off as they
 // are (Makefile): the float class rounds every product before it adds, and the division by f0 is one rounding of its own.
 #include <hip/hip_runtime.h>

@@ -57,7 +57,8 @@
  *                               gvtm_stream_push_targets: the same as a session, targets arriving push by push
  *                               (reference model 5, which the window constructs: gvtm_stream_push_targets_model5);
  *                               gvtm_synthesize_targets_voices_device: the same for a batch that mixes voices
- *                               (reference model 5: gvtm_synthesize_targets_model5_voices_device)
+ *                               (reference model 5: gvtm_synthesize_targets_model5_voices_device), and as a session
+ *                               gvtm_stream_push_targets_voices (gvtm_stream_push_targets_model5_voices)
  *   gvtm_analysis_* / gvtm_analyze_spectrum_device
  *                               the same window's analysis view: AnalysisWindow::showData and setupWindow
  *                               (gama_tts_editor/src/interactive/AnalysisWindow.cpp:189-361) on each full ring of 65 536
@@ -479,7 +480,8 @@ void gvtm_host_free(void* ptr);
  * A stream also takes its utterances as event lists, chunk by chunk, and generates their frames itself:
  * gvtm_stream_push_events, with gvtm_stream_get_drift / gvtm_stream_set_drift, declared behind the track-generation entries
  * below ("Streams fed event lists").  And as parameter targets, the interactive window's session: gvtm_stream_push_targets
- * and, for the one-voice plans of reference model 5, gvtm_stream_push_targets_model5 ("Streams fed parameter targets").
+ * and, for the one-voice plans of reference model 5, gvtm_stream_push_targets_model5; under the stream's several voices
+ * gvtm_stream_push_targets_voices and gvtm_stream_push_targets_model5_voices ("Streams fed parameter targets").
  */
 typedef struct gvtm_stream gvtm_stream;
 
@@ -1097,7 +1099,7 @@ int gvtm_synthesize_targets_model5_voices_device(gvtm_plan* plan, const int64_t*
  *
  * Checked on the host before anything is launched; the first that applies: a null stream (GVTM_ERR_INVALID_ARGUMENT); a
  * stream of a plan of several voices or of a model 5 plan (GVTM_ERR_UNSUPPORTED: the one-shot entry takes neither; model 5
- * has gvtm_stream_push_targets_model5, below); then,
+ * has gvtm_stream_push_targets_model5, several voices gvtm_stream_push_targets_voices, both below); then,
  * all GVTM_ERR_INVALID_ARGUMENT, a finished stream; a stream fed frames or event lists since its last reset; a null
  * list_offsets; a max_steps beyond the step counter; points without their tables; an utterance that is refused -- status 1
  * for a count outside [0, max_steps], 2, 3 and 4 as above, and 4 also for a point whose step is at or beyond the
@@ -1133,6 +1135,33 @@ int gvtm_stream_push_targets(gvtm_stream* stream, const int64_t* list_offsets, c
 int gvtm_stream_push_targets_model5(gvtm_stream* stream, const int64_t* list_offsets, const int32_t* point_steps,
 		const float* point_values, const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride,
 		int64_t* out_counts, int32_t* status_out);
+/* The two entries above under a mix of voices: streams of gvtm_stream_create_voices on a plan of several voices, utterance b
+ * spoken by the stream's own voice of it (the ids of gvtm_stream_create_voices or of the last gvtm_stream_reset_voices; no
+ * id travels with a push).  gvtm_stream_push_targets_voices takes plans of the models 0 to 4 in every precision,
+ * gvtm_stream_push_targets_model5_voices the plans of gvtm_plan_create_model5_voices and
+ * gvtm_plan_create_model5_float_voices; each takes the arguments of gvtm_stream_push_targets, argument for argument, and also
+ * a stream of a one-voice plan of its family, on which it is bit for bit the one-voice entry above (the two may alternate
+ * within a run).  Every utterance walks its lists through the filter of its own voice (gvtm_targets_filter_length(plan, v):
+ * the voices' internal rates differ, and so do their lengths); the granules stay the stream's, 12 steps resp. 4.
+ * Contract: for every voice v, the steps of an utterance of voice v pushed in any grouping over any number of calls and
+ * then finished give, bit for bit in every precision resp. both classes, the samples, sample count and maxabs of one
+ * gvtm_synthesize_targets_voices_device resp. gvtm_synthesize_targets_model5_voices_device call on the whole lists under
+ * voice v -- so the float class of model 5 stays the reference's interactive model bit for bit under every voice.
+ * gvtm_stream_finish, gvtm_stream_reset, gvtm_stream_reset_voices (the next run walks the new voices' filters),
+ * gvtm_stream_listen with its take and peek entries and gvtm_stream_targets_points serve such a stream; the points held for
+ * utterance b never exceed those of its last N_v + 12 steps plus 16, N_v its own voice's length.
+ * gvtm_stream_targets_capacity answers the largest count over ALL the plan's voices, whichever the ids name, so that
+ * gvtm_stream_reset_voices never invalidates a stride (on a one-voice plan: the value it always had).
+ * Refused, the first that applies: a null stream (GVTM_ERR_INVALID_ARGUMENT); a stream of the other model family
+ * (GVTM_ERR_UNSUPPORTED); then everything gvtm_stream_push_targets refuses, in its order and with its status codes, and a
+ * refused call leaves the stream exactly as it found it.  The two one-voice entries above keep refusing a plan of several
+ * voices. */
+int gvtm_stream_push_targets_voices(gvtm_stream* stream, const int64_t* list_offsets, const int32_t* point_steps,
+		const float* point_values, const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride,
+		int64_t* out_counts, int32_t* status_out);
+int gvtm_stream_push_targets_model5_voices(gvtm_stream* stream, const int64_t* list_offsets, const int32_t* point_steps,
+		const float* point_values, const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride,
+		int64_t* out_counts, int32_t* status_out);
 size_t gvtm_stream_targets_capacity(const gvtm_stream* stream, size_t max_new_steps);
 /* held_out [batch] (host): the points the stream holds for each utterance */
 int gvtm_stream_targets_points(const gvtm_stream* stream, int64_t* held_out);
@@ -1163,7 +1192,7 @@ int gvtm_stream_targets_points(const gvtm_stream* stream, int64_t* held_out);
  * gvtm_synthesize_events_chunks_device call on the whole utterance with the same voice and the same initial drift state.
  *
  * One feeding mode per run: between two resets a stream is fed frames (gvtm_stream_push), event lists or parameter targets
- * (gvtm_stream_push_targets or gvtm_stream_push_targets_model5, above), never two of them; once one entry has been used the others return
+ * (gvtm_stream_push_targets, gvtm_stream_push_targets_model5 or their _voices forms, above), never two of them; once one entry has been used the others return
  * GVTM_ERR_INVALID_ARGUMENT until the next reset, and so does
  * gvtm_stream_set_drift between a gvtm_stream_push_events and the next reset.
  *
@@ -1377,7 +1406,7 @@ int gvtm_analyze_spectrum_device(gvtm_analysis* analysis, const float* d_audio, 
  * buffer lies or how it is aligned; only the width of the loads does.
  *
  * A listening stream is taken as it is by every push entry (gvtm_stream_push, _push_events, _push_targets,
- * _push_targets_model5) and by gvtm_stream_finish, whatever its voices, model and precision.  On it `audio` may be NULL although
+ * _push_targets_model5, _push_targets_voices, _push_targets_model5_voices) and by gvtm_stream_finish, whatever its voices, model and precision.  On it `audio` may be NULL although
  * samples are due: audio_stride is then ignored, out_counts is still filled, and no sample leaves the device.  One refusal is
  * added, behind the entry's own and before anything is launched or kept: a call that would complete more buffers than an
  * utterance's queue has room for is GVTM_ERR_INVALID_ARGUMENT and leaves the stream exactly as found; the same call succeeds
