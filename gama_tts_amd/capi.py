@@ -217,6 +217,12 @@ def _prototypes():
         "gvtm_stream_listen_state": (i, [vp, vp, vp]),
         "gvtm_stream_take_spectra": (i, [vp, vp, vp, vp]),
         "gvtm_stream_peek_spectra_device": (i, [vp, vp, vp, vp]),
+        "gvtm_rules_create": (i, [i, vp, vp]),
+        "gvtm_rules_destroy": (None, [vp]),
+        "gvtm_rules_apply_host": (i, [vp, i, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp]),
+        "gvtm_rules_event_count": (i64, [vp, i, vp, sz, vp]),
+        "gvtm_generate_events_device": (i, [vp, i, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
+        "gvtm_synthesize_postures_device": (i, [vp, vp, tracks, vp, vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]),
     }
     hooks = {
         "gvtm_debug_set_rows": (i, [vp, i]),
@@ -470,6 +476,95 @@ def intonation_apply_host(config, events, points, count_only=False, capacity=Non
     if n < 0:
         raise GvtmError(1, lib.gvtm_last_error().decode())
     return (int(n) if count_only else out[:n].copy()), int(status.value)
+
+
+# gvtm_posture and gvtm_rule_data as numpy record layouts (24 and 48 bytes)
+POSTURE_DTYPE = np.dtype([("posture", "<i4"), ("marked", "<i4"), ("tempo", "<f8"), ("rule_tempo", "<f8")])
+RULE_DATA_DTYPE = np.dtype([("number", "<i4"), ("first_posture", "<i4"), ("last_posture", "<i4"), ("start", "<i4"), ("mark1", "<f8"),
+                            ("mark2", "<f8"), ("duration", "<f8"), ("beat", "<f8")])
+RULES_OK, RULES_NO_RULE, RULES_TOO_SMALL, RULES_BAD_VALUE, RULES_BAD_POSTURE, RULES_NO_ROOM = range(6)  # the statuses of the rule
+
+
+class RulesModel(ctypes.Structure):
+    """gvtm_rules_model: eight counts, then the arrays (control_model.ARRAYS names them as the header does)."""
+    _COUNTS = ("n_postures", "n_rules", "n_equations", "n_program_ops", "n_transitions", "n_items", "n_points", "n_slopes")
+    _ARRAYS = (("param_target", np.float32), ("symbol_target", np.float32), ("param_min", np.float32), ("param_max", np.float32),
+               ("rule_n_expr", np.int32), ("rule_equations", np.int32), ("rule_param_transition", np.int32),
+               ("rule_special_transition", np.int32), ("match", np.uint8), ("equation_offsets", np.int32), ("program_op", np.int32),
+               ("program_const", np.float32), ("transition_offsets", np.int32), ("items", np.int32), ("point_type", np.int32),
+               ("point_value", np.float32), ("point_free_time", np.float32), ("point_time_eq", np.int32), ("slopes", np.float32))
+    _fields_ = [(n, ctypes.c_int32) for n in _COUNTS] + [(n, ctypes.c_void_p) for n, _ in _ARRAYS]
+
+
+def postures_from_table(table):
+    """rows (posture id, marked, tempo, rule_tempo) -> gvtm_posture records."""
+    table = np.asarray(table, dtype=np.float64).reshape(-1, 4)
+    out = np.zeros(table.shape[0], dtype=POSTURE_DTYPE)
+    out["posture"], out["marked"], out["tempo"], out["rule_tempo"] = table[:, 0].astype(np.int32), table[:, 1].astype(np.int32), table[:, 2], table[:, 3]
+    return out
+
+
+class Rules:
+    """Owns a gvtm_rules: a compiled articulatory model (the arrays of control_model.compile_model, or of an .npz written from
+    them), checked and, unless device is DEVICE_NONE, uploaded."""
+
+    def __init__(self, model, device=DEVICE_NONE):
+        self._lib = load_library()
+        self._h = ctypes.c_void_p()
+        arrays = {name: np.ascontiguousarray(model[name], dtype=dtype) for name, dtype in RulesModel._ARRAYS}
+        m = RulesModel()
+        m.n_postures, m.n_rules = arrays["param_target"].shape[0], arrays["rule_n_expr"].shape[0]
+        m.n_equations, m.n_program_ops = arrays["equation_offsets"].shape[0] - 1, arrays["program_op"].shape[0]
+        m.n_transitions, m.n_items = arrays["transition_offsets"].shape[0] - 1, arrays["items"].size // 5
+        m.n_points, m.n_slopes = arrays["point_type"].shape[0], arrays["slopes"].shape[0]
+        for name, _ in RulesModel._ARRAYS:
+            setattr(m, name, arrays[name].ctypes.data)
+        self.n_postures, self.device = int(m.n_postures), int(device)
+        _check(self._lib, self._lib.gvtm_rules_create(int(device), ctypes.byref(m), ctypes.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._lib.gvtm_rules_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def event_count(self, control_period, postures):
+        """gvtm_rules_event_count -> (events, status)."""
+        postures = np.ascontiguousarray(postures, dtype=POSTURE_DTYPE)
+        status = ctypes.c_int32(-1)
+        n = self._lib.gvtm_rules_event_count(self._h, int(control_period), _ptr(postures), postures.shape[0], ctypes.byref(status))
+        if n < 0:
+            raise GvtmError(1, self._lib.gvtm_last_error().decode())
+        return int(n), int(status.value)
+
+    def apply_host(self, control_period, postures, capacity=None, rule_capacity=None):
+        """gvtm_rules_apply_host: gvtm_posture records -> (gvtm_event records, gvtm_rule_data records, onsets float64 [n],
+        status).  A refused utterance has no events and no rule data.  capacity: events the output is sized for (default:
+        what gvtm_rules_event_count says); rule_capacity: rows of rule data (default: one per posture)."""
+        postures = np.ascontiguousarray(postures, dtype=POSTURE_DTYPE)
+        n = postures.shape[0]
+        capacity = self.event_count(control_period, postures)[0] if capacity is None else int(capacity)
+        rule_capacity = n if rule_capacity is None else int(rule_capacity)
+        events = np.zeros(max(capacity, 1), dtype=EVENT_DTYPE)
+        rule_data = np.zeros(max(rule_capacity, 1), dtype=RULE_DATA_DTYPE)
+        onsets = np.zeros(max(n, 1), dtype=np.float64)
+        n_events, n_rules, status = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_int32(-1)
+        _check(self._lib, self._lib.gvtm_rules_apply_host(self._h, int(control_period), _ptr(postures), n, _ptr(events), capacity, ctypes.byref(n_events),
+                                                         _ptr(rule_data), rule_capacity, ctypes.byref(n_rules), _ptr(onsets), ctypes.byref(status)))
+        return events[: n_events.value].copy(), rule_data[: min(n_rules.value, rule_capacity)].copy(), onsets[:n], int(status.value)
+
+    def generate_events_device(self, control_period, d_postures, d_posture_offsets, batch, d_events_out, out_capacity, d_event_offsets_out,
+                               d_rule_data=None, max_rules=0, d_rule_counts=None, d_onsets=None, d_status=None, stream=None):
+        """gvtm_generate_events_device: posture sequences -> event lists, their offsets, rule data, onsets and statuses; all
+        pointers are device memory."""
+        _check(self._lib, self._lib.gvtm_generate_events_device(
+            self._h, int(control_period), _ptr(d_postures), _ptr(d_posture_offsets), int(batch), _ptr(d_events_out), int(out_capacity),
+            _ptr(d_event_offsets_out), _ptr(d_rule_data), int(max_rules), _ptr(d_rule_counts), _ptr(d_onsets), _ptr(d_status), _ptr(stream)))
 
 
 MODIFICATION_ADD, MODIFICATION_MULTIPLY = 0, 1  # GVTM_MODIFICATION_*
@@ -1111,6 +1206,15 @@ class Plan:
         self._check(self._lib.gvtm_synthesize_events_device(
             self._h, ctypes.byref(track_config), _ptr(d_events), _ptr(d_offsets), int(batch), int(max_frames), _ptr(d_audio),
             int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift), _ptr(stream)))
+
+    def synthesize_postures_device(self, rules, track_config, d_postures, d_posture_offsets, events_capacity, batch, max_frames, d_audio,
+                                   audio_stride, d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, d_status=None, stream=None):
+        """Posture sequences in, samples out (gvtm_synthesize_postures_device; rules: a Rules on the plan's device); all
+        pointers are device memory."""
+        self._check(self._lib.gvtm_synthesize_postures_device(
+            self._h, rules._h, ctypes.byref(track_config), _ptr(d_postures), _ptr(d_posture_offsets), int(events_capacity), int(batch),
+            int(max_frames), _ptr(d_audio), int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift),
+            _ptr(d_status), _ptr(stream)))
 
     def normalize_device(self, d_audio, batch, audio_stride, d_maxabs, d_counts=None, d_out_f32=None, d_out_i16=None,
                          d_scales=None, stream=None):

@@ -17,6 +17,7 @@
 // Bit parity with the reference: the same double operations in the same order, no FMA contraction (the pragma below and
 // the Makefile's flag), IEEE division.
 #include "vtm_intonation.hpp"
+#include "vtm_offsets_scan.hpp"
 
 namespace gvtm {
 
@@ -116,62 +117,11 @@ __global__ __launch_bounds__(64) void vtm_intonation_count_kernel(const Intonati
 	}
 }
 
-constexpr int kScanThreads = 1024;
-
 // event_offsets_out[1 ..= batch] hold the lengths; they leave as the ends of the lists laid back to back, a list that
-// would end beyond out_capacity counted as empty
+// would end beyond out_capacity counted as empty (vtm_offsets_scan.hpp)
 __global__ __launch_bounds__(kScanThreads) void vtm_intonation_scan_kernel(const IntonationArgs a)
 {
-	__shared__ int64_t sums[2][kScanThreads];
-	__shared__ int64_t running; // the end of the lists in front of this block of lengths
-	const int t = threadIdx.x;
-	if (t == 0) {
-		running = 0;
-		a.event_offsets_out[0] = 0;
-	}
-	for (size_t block = 0; block < a.batch; block += kScanThreads) {
-		const size_t utt = block + t;
-		const bool mine = utt < a.batch;
-		int64_t length = mine ? a.event_offsets_out[utt + 1] : 0;
-		if (length < 0) length = 0;
-		sums[0][t] = length;
-		__syncthreads(); // (also: `running` of the block before is written)
-		const int64_t start = running;
-		int from = 0;
-		for (int step = 1; step < kScanThreads; step <<= 1) { // inclusive sums, doubling
-			sums[from ^ 1][t] = sums[from][t] + (t >= step ? sums[from][t - step] : 0);
-			from ^= 1;
-			__syncthreads();
-		}
-		int64_t end = start + sums[from][t];
-		const bool all_fit = start + sums[from][kScanThreads - 1] <= a.out_capacity; // the same for every thread
-		__syncthreads(); // every thread has read `running` and the block's total
-		if (all_fit) {
-			if (t == kScanThreads - 1) running = end;
-		} else {
-			// a list of this block does not fit: one thread lays the block out, list by list
-			sums[0][t] = length;
-			__syncthreads();
-			if (t == 0) {
-				int64_t at = start;
-				for (int i = 0; i < kScanThreads; ++i) {
-					const int64_t len = sums[0][i];
-					const bool fits = at + len <= a.out_capacity;
-					if (fits) at += len;
-					sums[0][i] = fits ? at : -at - 1; // the list's end, or (dropped) the end before it, marked
-				}
-				running = at;
-			}
-			__syncthreads();
-			end = sums[0][t];
-			if (end < 0) {
-				end = -end - 1;
-				if (mine && a.status) a.status[utt] = kIntonationNoRoom;
-			}
-		}
-		if (mine) a.event_offsets_out[utt + 1] = end;
-		__syncthreads(); // `running` is written, sums may be overwritten
-	}
+	lengths_to_offsets(a.event_offsets_out, a.batch, a.out_capacity, a.status, kIntonationNoRoom);
 }
 
 __global__ __launch_bounds__(64) void vtm_intonation_write_kernel(const IntonationArgs a)

@@ -46,6 +46,9 @@
  *   gvtm_synthesize_events_packed_host*
  *                               Controller::synthesizePhoneticStringToFile (vtm_control_model/Controller.cpp:194-200 with
  *                               :141-154) for a ragged batch: event lists in from host memory, int16 samples out
+ *   gvtm_rules_create / gvtm_generate_events_device / gvtm_synthesize_postures_device / gvtm_rules_apply_host
+ *                               EventList::generateEventList and applyRule (vtm_control_model/EventList.cpp:435-676) for a
+ *                               batch: posture sequences in, event lists (resp. samples) out
  *   gvtm_apply_modifications_device / gvtm_synthesize_modified_device / gvtm_modification_apply_host
  *                               the editor's parameter-modification window: what Processor::process leaves in its modified
  *                               parameter list (gama_tts_editor/src/ParameterModificationSynthesis.cpp:117-194), then
@@ -1445,6 +1448,155 @@ int gvtm_stream_take_spectra(gvtm_stream* stream, float* spectra /* [batch][max_
  * next call on the stream.  Any of the three may be NULL. */
 int gvtm_stream_peek_spectra_device(const gvtm_stream* stream, const float** d_spectra, const float** d_signal,
 		const int32_t** d_queued);
+
+/* ---------------------------------------------------------------------------------------------
+ * Event lists from posture sequences: the step in front of everything above.  Replaces
+ * EventList::generateEventList() / applyRule() / createSlopeRatioEvents() / insertEvent() / setZeroRef()
+ * (vtm_control_model/EventList.cpp:302-371, 373-432, 435-676) for a batch: per phone a posture id, a marked bit and two
+ * tempos in, gvtm_event lists out, in the layout every events entry above reads, never leaving the device.  The rule
+ * data and the posture onsets that EventList::applyIntonation() places its points by come out beside them.
+ * Bit-identical to the reference's list (the debug `flag` of an event is not kept).
+ *
+ * The articulatory database arrives compiled to flat arrays (gama_tts_amd/control_model.py compiles an artic.xml;
+ * INTEGRATION.md tells how a GamaTTS build fills them from its Model).  Every number is held in the type the reference
+ * holds it in.  (The three structures of this section are declared in two steps, `struct X {...}; typedef struct X X;`.)
+ */
+
+/* The compiled model: host arrays, read during gvtm_rules_create only. */
+struct gvtm_rules_model {
+	int32_t n_postures, n_rules, n_equations, n_program_ops, n_transitions, n_items, n_points, n_slopes;
+	/* postures */
+	const float* param_target;    /* [n_postures][16] Posture::getParameterTarget */
+	const float* symbol_target;   /* [n_postures][6] transition, qssa, qssb, marked transition, marked qssa, marked qssb
+	                                 (Rule::evaluateExpressionSymbols, Rule.cpp:468-548) */
+	const float* param_min;       /* [16] Parameter::minimum() */
+	const float* param_max;       /* [16] */
+	/* rules, in database order */
+	const int32_t* rule_n_expr;   /* [n_rules] boolean expressions: 2, 3 or 4, which is also the rule's type */
+	const int32_t* rule_equations;          /* [n_rules][5] equations of rd, beat, mark1, mark2, mark3; -1: none */
+	const int32_t* rule_param_transition;   /* [n_rules][16] */
+	const int32_t* rule_special_transition; /* [n_rules][16], -1: none; points only */
+	const uint8_t* match;         /* [n_rules][4][n_postures] bit 0: the position's expression holds for the posture
+	                                 unmarked, bit 1: marked */
+	/* equations: postfix programs.  program_op: the operation in the low byte -- 0 push program_const[i], 1 push the
+	 * FormulaSymbol (op >> 8) (FormulaSymbol.h:36-60), 2 negate, 3 add, 4 subtract, 5 multiply, 6 divide (the operand
+	 * pushed first is the left one) -- all in float, one rounding per operation.  At most 8 operands at once. */
+	const int32_t* equation_offsets; /* [n_equations + 1] into the programs */
+	const int32_t* program_op;       /* [n_program_ops] */
+	const float* program_const;      /* [n_program_ops] */
+	/* transitions: items in pointOrSlopeList() order.  items[i] = {kind, first_point, n_points, first_slope, n_slopes}:
+	 * kind 0 a point (n_points 1, n_slopes 0), kind 1 a slope ratio, a run of points and the slopes between them. */
+	const int32_t* transition_offsets; /* [n_transitions + 1] into the items */
+	const int32_t* items;              /* [n_items][5] */
+	const int32_t* point_type;         /* [n_points] 2 diphone, 3 triphone, 4 tetraphone */
+	const float* point_value;          /* [n_points] */
+	const float* point_free_time;      /* [n_points] milliseconds; read when point_time_eq is -1 */
+	const int32_t* point_time_eq;      /* [n_points] the time equation, or -1 */
+	const float* slopes;               /* [n_slopes] */
+};
+typedef struct gvtm_rules_model gvtm_rules_model;
+
+/* One phone of an utterance.  tempo is postureData_.tempo AFTER applyRhythm(): feet and tone groups are the caller's. */
+struct gvtm_posture {
+	int32_t posture;    /* index into the model's postures */
+	int32_t marked;     /* 0 or not */
+	double tempo;
+	double rule_tempo;  /* postureData_.ruleTempo: the rule that starts at this posture runs 1 / rule_tempo as long */
+};
+typedef struct gvtm_posture gvtm_posture;
+
+/* EventList.h:85-103, one per rule application */
+struct gvtm_rule_data {
+	int32_t number;         /* the rule's index + 1 */
+	int32_t first_posture, last_posture;
+	int32_t start;          /* zeroRef_ at the rule's start, ms */
+	double mark1, mark2, duration;
+	double beat;            /* the rule's beat + start */
+};
+typedef struct gvtm_rule_data gvtm_rule_data;
+
+typedef struct gvtm_rules gvtm_rules;
+
+/* Checks the model, keeps a copy and, unless device is GVTM_DEVICE_NONE (host use only), uploads it; synchronous.
+ * GVTM_ERR_INVALID_ARGUMENT, with the reason in gvtm_last_error(): a null argument or array, an index outside its table, a
+ * rule without a parameter-profile transition, a special-profile transition that holds a slope ratio, a program that is
+ * not a well-formed postfix expression or holds more than 8 operands at once, and -- where the reference throws when it
+ * walks the transition -- a slope ratio that is empty or whose points are not its slopes plus one. */
+int gvtm_rules_create(int device, const gvtm_rules_model* model, gvtm_rules** rules_out);
+void gvtm_rules_destroy(gvtm_rules* rules);
+
+/*
+ * The rule for one utterance of n postures, on the host; needs no device.  Reproduced, not tidied: an event's time is
+ * zeroRef + (int)time less its remainder by control_period, taken of the ABSOLUTE time, so with a rule start that is no
+ * multiple of the period an event can fall before the start; insertEvent refuses a time below 0 or above the CURRENT
+ * rule's (int)duration + control_period; a later value at the same (time, parameter) wins -- the parameter loop runs
+ * before the special loop, rule k + 1's targets land on rule k's closing event, the last item of a transition (a slope
+ * ratio's last point only if the ratio is the last item) is a phantom that inserts nothing; the equal-targets shortcut
+ * compares the float targets widened to double; the marker events carry no value and still make an event of 32 empty
+ * (+infinity) values; the intervals are checked against control_period + 1.  Every event has has_interp = 0, interp = 0.
+ *
+ * An utterance is refused with a status, its list empty and its rule count 0 (onsets are then not defined):
+ *   0  ok
+ *   1  no rule matches at some posture (the reference throws)
+ *   2  "the time interval between two postures is too small" (the reference throws)
+ *   3  where the reference is undefined: a rule symbol that is not finite (a rule_tempo of 0), an (int) of a value no int
+ *      holds, a point time that is a NaN, a list that runs beyond INT_MAX ms
+ *   4  a posture id outside the model, or fewer than two postures
+ *   5  device only: the list does not fit behind the lists before it in out_capacity events, or one rule spans more
+ *      than 4094 control periods (the kernels' window; the host has no such limit)
+ * The first refusal in the reference's order of work decides.  (A list dropped for want of room in out_capacity had been
+ * accepted by the rule: its rule data, rule count and onsets stand.)
+ *
+ *   events_out [capacity]          may be NULL (count only).  More events than capacity: GVTM_ERR_INVALID_ARGUMENT, with
+ *                                  *n_events_out the count needed.
+ *   rule_data_out [rule_capacity]  may be NULL; rows beyond rule_capacity are dropped, *n_rules_out counts them all
+ *   onsets_out [n]                 may be NULL; postureData_[i].onset: 0 for the first posture, start + beat of its rule
+ * Returns GVTM_OK also for a refused utterance; GVTM_ERR_INVALID_ARGUMENT for null rules, postures with n > 0, n_events_out
+ * or status_out, or a control_period outside 1..4.
+ */
+int gvtm_rules_apply_host(const gvtm_rules* rules, int32_t control_period, const gvtm_posture* postures, size_t n,
+		gvtm_event* events_out, size_t capacity, size_t* n_events_out, gvtm_rule_data* rule_data_out, size_t rule_capacity,
+		size_t* n_rules_out, double* onsets_out, int32_t* status_out);
+/* The count alone: events of the utterance (0 when refused; status_out may be NULL), or -1 on a bad call. */
+int64_t gvtm_rules_event_count(const gvtm_rules* rules, int32_t control_period, const gvtm_posture* postures, size_t n,
+		int32_t* status_out);
+
+/*
+ * The rule for a batch, everything resident in device memory.
+ *   d_postures, d_posture_offsets [batch + 1] int64   utterance b owns the postures [off[b], off[b+1])
+ *   d_events_out                  out, out_capacity events: the lists back to back in utterance order
+ *   d_event_offsets_out [batch + 1] int64   out: exactly the d_event_offsets that gvtm_generate_tracks_device,
+ *                                 gvtm_apply_intonation_device (as d_list_offsets) and the *_events_* entries take
+ *   d_rule_data [batch][max_rules], d_rule_counts [batch] int32   out, either may be NULL: the rule data; rows beyond
+ *                                 max_rules are dropped, the count covers them
+ *   d_onsets                      out, may be NULL: one double per posture, laid out as d_postures
+ *   d_status [batch] int32        out, may be NULL
+ * Lists, offsets, rule data, onsets and statuses are bit for bit gvtm_rules_apply_host's, utterance by utterance.  Nothing
+ * is written at or beyond out_capacity events and nothing for a refused utterance; a list that would end beyond
+ * out_capacity is refused (5) and takes no room, so a shorter one behind it may still fit.  Enqueue-only: three kernels
+ * on hip_stream (count, scan, write), no scratch.  GVTM_ERR_INVALID_ARGUMENT: null rules, with batch > 0 a null d_postures,
+ * d_posture_offsets, d_events_out or d_event_offsets_out, a control_period outside 1..4; GVTM_ERR_NO_DEVICE: rules created
+ * with GVTM_DEVICE_NONE; batch == 0 returns GVTM_OK.
+ */
+int gvtm_generate_events_device(const gvtm_rules* rules, int32_t control_period, const gvtm_posture* d_postures,
+		const int64_t* d_posture_offsets, size_t batch, gvtm_event* d_events_out, size_t out_capacity,
+		int64_t* d_event_offsets_out, gvtm_rule_data* d_rule_data, size_t max_rules, int32_t* d_rule_counts,
+		double* d_onsets, int32_t* d_status, void* hip_stream);
+
+/*
+ * Postures in, audio out: gvtm_generate_events_device into an event buffer the plan owns (grown to events_capacity events:
+ * the out_capacity above; gvtm_rules_event_count sizes it on the host), then gvtm_synthesize_events_device on those lists,
+ * all enqueued on hip_stream.  Samples, counts, peaks, frame counts and drift states are bit for bit those of the two calls
+ * made separately; a refused utterance has 0 frames.  config, max_frames and the audio arguments are
+ * gvtm_synthesize_events_device's, for every plan that entry takes; the control period is config's.  The rules must live on
+ * the plan's device.  The event buffer is one more buffer of the plan's that the one-stream ordering rule of that entry
+ * covers.  Refused before any device work: what gvtm_synthesize_events_device and gvtm_generate_events_device refuse, and
+ * rules on another device than the plan's (GVTM_ERR_INVALID_ARGUMENT).
+ */
+int gvtm_synthesize_postures_device(gvtm_plan* plan, const gvtm_rules* rules, const gvtm_track_config* config,
+		const gvtm_posture* d_postures, const int64_t* d_posture_offsets, size_t events_capacity, size_t batch,
+		size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts,
+		float* d_maxabs, gvtm_drift_state* d_drift, int32_t* d_status, void* hip_stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
