@@ -796,6 +796,9 @@ def debug_listen_copy(d_src, src_stride, d_dst, dst_stride, d_src_off, d_dst_off
                                            _ptr(d_len), int(batch), int(max_len)))
 
 
+_NO_VOICE_IDS = object()  # (Plan._synthesize_targets: the entry has no d_voice_ids argument)
+
+
 class Plan:
     """Owns a gvtm_plan.  device=DEVICE_NONE gives a design-only plan (no GPU needed)."""
 
@@ -1159,18 +1162,24 @@ class Plan:
                                   d_audio, audio_stride, d_out_counts=None, d_maxabs=None, d_status=None, stream=None):
         """Target lists (the tables of pack_targets; d_list_ids None: utterance b's parameter p walks list 16 b + p) in,
         samples out (gvtm_synthesize_targets_device); all pointers are device memory."""
-        self._check(self._lib.gvtm_synthesize_targets_device(
-            self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
-            int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status), _ptr(stream)))
+        self._synthesize_targets(self._lib.gvtm_synthesize_targets_device, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values,
+                                 d_step_counts, batch, max_steps, d_audio, audio_stride, d_out_counts, d_maxabs, d_status, stream)
+
+    def _synthesize_targets(self, entry, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, batch, max_steps, d_audio,
+                            audio_stride, d_out_counts, d_maxabs, d_status, stream, d_voice_ids=_NO_VOICE_IDS):
+        """What the four synthesize_targets*_device methods do: `entry`, with d_voice_ids where the entry takes them (None is NULL there)."""
+        voices = () if d_voice_ids is _NO_VOICE_IDS else (_ptr(d_voice_ids),)
+        self._check(entry(self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
+                          *voices, int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status),
+                          _ptr(stream)))
 
     def synthesize_targets_model5_device(self, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, batch, max_steps,
                                          d_audio, audio_stride, d_out_counts=None, d_maxabs=None, d_status=None, stream=None):
         """synthesize_targets_device for a one-voice model 5 plan of either class (gvtm_synthesize_targets_model5_device): the
         samples of the model as the interactive window constructs it, each step's signal divided by its f0.  All pointers are
         device memory."""
-        self._check(self._lib.gvtm_synthesize_targets_model5_device(
-            self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
-            int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status), _ptr(stream)))
+        self._synthesize_targets(self._lib.gvtm_synthesize_targets_model5_device, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values,
+                                 d_step_counts, batch, max_steps, d_audio, audio_stride, d_out_counts, d_maxabs, d_status, stream)
 
     def targets_voice_output_count(self, voice, steps):
         """gvtm_targets_voice_output_count: the samples of an utterance of `steps` internal steps under voice `voice`;
@@ -1185,20 +1194,16 @@ class Plan:
                                          batch, max_steps, d_audio, audio_stride, d_out_counts=None, d_maxabs=None, d_status=None, stream=None):
         """synthesize_targets_device with a voice id per utterance (gvtm_synthesize_targets_voices_device): utterance b walks
         its lists under voice d_voice_ids[b]; on a plan of one voice the ids are all 0.  All pointers are device memory."""
-        self._check(self._lib.gvtm_synthesize_targets_voices_device(
-            self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
-            _ptr(d_voice_ids), int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status),
-            _ptr(stream)))
+        self._synthesize_targets(self._lib.gvtm_synthesize_targets_voices_device, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values,
+                                 d_step_counts, batch, max_steps, d_audio, audio_stride, d_out_counts, d_maxabs, d_status, stream, d_voice_ids)
 
     def synthesize_targets_model5_voices_device(self, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, d_voice_ids,
                                                 batch, max_steps, d_audio, audio_stride, d_out_counts=None, d_maxabs=None, d_status=None, stream=None):
         """synthesize_targets_model5_device with a voice id per utterance (gvtm_synthesize_targets_model5_voices_device), for
         model 5 voices plans of either class: utterance b walks its lists under voice d_voice_ids[b], its samples the
         interactive model's; on a plan of one voice the ids are all 0.  All pointers are device memory."""
-        self._check(self._lib.gvtm_synthesize_targets_model5_voices_device(
-            self._h, _ptr(d_list_offsets), int(n_lists), _ptr(d_list_ids), _ptr(d_point_steps), _ptr(d_point_values), _ptr(d_step_counts),
-            _ptr(d_voice_ids), int(batch), int(max_steps), _ptr(d_audio), int(audio_stride), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_status),
-            _ptr(stream)))
+        self._synthesize_targets(self._lib.gvtm_synthesize_targets_model5_voices_device, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values,
+                                 d_step_counts, batch, max_steps, d_audio, audio_stride, d_out_counts, d_maxabs, d_status, stream, d_voice_ids)
 
     def synthesize_events_device(self, track_config, d_events, d_offsets, batch, max_frames, d_audio, audio_stride,
                                  d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, stream=None):

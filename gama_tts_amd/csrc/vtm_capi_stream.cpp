@@ -612,6 +612,16 @@ int stream_push_targets(gvtm_stream* s, const int64_t* list_offsets, const int32
 	}
 }
 
+// What the four gvtm_stream_push_targets* entries ask in front of stream_push_targets, in this order: a stream, (voices
+// false: the one-voice entries) a plan of one voice, and the entry's family of models.  The two texts name the entry.
+int check_push_targets_entry(const gvtm_stream* s, bool voices, bool model5, const char* several_voices, const char* other_family)
+{
+	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
+	if (!voices && s->plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, several_voices);
+	if (s->plan->designs[0].model5 != model5) return fail(GVTM_ERR_UNSUPPORTED, other_family);
+	return GVTM_OK;
+}
+
 } // namespace
 
 namespace gvtm::host {
@@ -802,18 +812,16 @@ int gvtm_stream_targets_points(const gvtm_stream* s, int64_t* held_out)
 int gvtm_stream_push_targets(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
 		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
 {
-	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
-	if (s->plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets: a plan of one voice only");
-	if (s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets: the models 0 to 4 only");
+	if (const int rc = check_push_targets_entry(s, false, false, "gvtm_stream_push_targets: a plan of one voice only",
+			"gvtm_stream_push_targets: the models 0 to 4 only"); rc != GVTM_OK) return rc;
 	return stream_push_targets(s, list_offsets, point_steps, point_values, step_counts, max_steps, audio, audio_stride, out_counts, status_out);
 }
 
 int gvtm_stream_push_targets_model5(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
 		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
 {
-	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
-	if (s->plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets_model5: a plan of one voice only (the models 0 to 4: gvtm_stream_push_targets)");
-	if (!s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets_model5: model 5 only; the models 0 to 4 have gvtm_stream_push_targets");
+	if (const int rc = check_push_targets_entry(s, false, true, "gvtm_stream_push_targets_model5: a plan of one voice only (the models 0 to 4: gvtm_stream_push_targets)",
+			"gvtm_stream_push_targets_model5: model 5 only; the models 0 to 4 have gvtm_stream_push_targets"); rc != GVTM_OK) return rc;
 	return stream_push_targets(s, list_offsets, point_steps, point_values, step_counts, max_steps, audio, audio_stride, out_counts, status_out);
 }
 
@@ -822,16 +830,16 @@ int gvtm_stream_push_targets_model5(gvtm_stream* s, const int64_t* list_offsets,
 int gvtm_stream_push_targets_voices(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
 		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
 {
-	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
-	if (s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets_voices: the models 0 to 4 only; model 5 has gvtm_stream_push_targets_model5_voices");
+	if (const int rc = check_push_targets_entry(s, true, false, nullptr,
+			"gvtm_stream_push_targets_voices: the models 0 to 4 only; model 5 has gvtm_stream_push_targets_model5_voices"); rc != GVTM_OK) return rc;
 	return stream_push_targets(s, list_offsets, point_steps, point_values, step_counts, max_steps, audio, audio_stride, out_counts, status_out);
 }
 
 int gvtm_stream_push_targets_model5_voices(gvtm_stream* s, const int64_t* list_offsets, const int32_t* point_steps, const float* point_values,
 		const int32_t* step_counts, size_t max_steps, float* audio, size_t audio_stride, int64_t* out_counts, int32_t* status_out)
 {
-	if (!s) return fail(GVTM_ERR_INVALID_ARGUMENT, "null stream");
-	if (!s->plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_stream_push_targets_model5_voices: model 5 only; the models 0 to 4 have gvtm_stream_push_targets_voices");
+	if (const int rc = check_push_targets_entry(s, true, true, nullptr,
+			"gvtm_stream_push_targets_model5_voices: model 5 only; the models 0 to 4 have gvtm_stream_push_targets_voices"); rc != GVTM_OK) return rc;
 	return stream_push_targets(s, list_offsets, point_steps, point_values, step_counts, max_steps, audio, audio_stride, out_counts, status_out);
 }
 

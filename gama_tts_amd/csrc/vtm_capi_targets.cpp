@@ -95,6 +95,54 @@ int check_and_launch(gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_li
 	return launch_synthesis(plan, r);
 }
 
+// What tells the four device entries apart: whether there is a voice id per utterance, which family the plan must be, and
+// the texts of the two refusals that name the entry and its neighbour.
+struct TargetsEntry {
+	bool voices;
+	bool model5;
+	const char* several_voices; // (the one-voice entries) what a plan of several voices is told
+	const char* other_family;
+};
+
+// The four device entries.  The refusals in their order: the plan, the batch's arguments, (voices) the voice ids, the stride
+// against the entry's own capacity, (one voice) a plan of several, the family, (voices of model 5) launch_synthesis' rule for
+// one-voice float plans, stated here so that a design-only plan shows it, a design-only plan; then nothing to do, or the launch.
+int synthesize_targets(const TargetsEntry& entry, gvtm_plan* plan, const int64_t* d_list_offsets, size_t n_lists, const int32_t* d_list_ids,
+		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, const int32_t* d_voice_ids, size_t batch, size_t max_steps,
+		float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
+{
+	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
+	if (batch > 0) {
+		if (const int rc = check_batch_arguments(d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, batch, max_steps, d_audio); rc != GVTM_OK) return rc;
+		if (entry.voices && !d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
+		if (audio_stride < (entry.voices ? voices_output_capacity(plan, max_steps) : steps_output_capacity(plan->designs[0], max_steps))) {
+			return fail(GVTM_ERR_INVALID_ARGUMENT, entry.voices ? "audio_stride smaller than gvtm_targets_voices_output_capacity(plan, max_steps)"
+					: "audio_stride smaller than gvtm_targets_output_capacity(plan, max_steps)");
+		}
+	}
+	if (!entry.voices && plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, entry.several_voices);
+	if (plan->designs[0].model5 != entry.model5) return fail(GVTM_ERR_UNSUPPORTED, entry.other_family);
+	if (entry.voices && entry.model5 && plan->designs[0].f32 && !plan->float5_voices) {
+		return fail(GVTM_ERR_UNSUPPORTED, "a gvtm_plan_create_model5_float plan has no launch of several voices (one voice per plan; "
+				"gvtm_plan_create_model5_float_voices makes the float plans that have)");
+	}
+	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
+	if (batch == 0) return GVTM_OK;
+	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, entry.voices ? d_voice_ids : nullptr, batch,
+			max_steps, d_audio, audio_stride, d_out_counts, d_maxabs, d_status, hip_stream);
+}
+
+constexpr TargetsEntry kTargets{false, false,
+		"gvtm_synthesize_targets_device: a plan of one voice only (gvtm_synthesize_targets_voices_device takes several)",
+		"gvtm_synthesize_targets_device: the models 0 to 4 only"};
+constexpr TargetsEntry kTargetsModel5{false, true,
+		"gvtm_synthesize_targets_model5_device: a plan of one voice only",
+		"gvtm_synthesize_targets_model5_device: model 5 only (gvtm_synthesize_targets_device takes the models 0 to 4)"};
+constexpr TargetsEntry kTargetsVoices{true, false, nullptr,
+		"gvtm_synthesize_targets_voices_device: the models 0 to 4 only"};
+constexpr TargetsEntry kTargetsModel5Voices{true, true, nullptr,
+		"gvtm_synthesize_targets_model5_voices_device: model 5 only (gvtm_synthesize_targets_voices_device takes the models 0 to 4)"};
+
 } // namespace
 
 extern "C" {
@@ -136,18 +184,7 @@ int gvtm_synthesize_targets_device(gvtm_plan* plan, const int64_t* d_list_offset
 		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, size_t batch, size_t max_steps, float* d_audio,
 		size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
 {
-	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
-	if (batch > 0) {
-		if (const int rc = check_batch_arguments(d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, batch, max_steps, d_audio); rc != GVTM_OK) return rc;
-		if (audio_stride < steps_output_capacity(plan->designs[0], max_steps)) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_targets_output_capacity(plan, max_steps)");
-		}
-	}
-	if (plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_device: a plan of one voice only (gvtm_synthesize_targets_voices_device takes several)");
-	if (plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_device: the models 0 to 4 only");
-	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
-	if (batch == 0) return GVTM_OK;
-	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, nullptr, batch, max_steps, d_audio, audio_stride,
+	return synthesize_targets(kTargets, plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, nullptr, batch, max_steps, d_audio, audio_stride,
 			d_out_counts, d_maxabs, d_status, hip_stream);
 }
 
@@ -155,18 +192,7 @@ int gvtm_synthesize_targets_model5_device(gvtm_plan* plan, const int64_t* d_list
 		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, size_t batch, size_t max_steps, float* d_audio,
 		size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
 {
-	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
-	if (batch > 0) {
-		if (const int rc = check_batch_arguments(d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, batch, max_steps, d_audio); rc != GVTM_OK) return rc;
-		if (audio_stride < steps_output_capacity(plan->designs[0], max_steps)) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_targets_output_capacity(plan, max_steps)");
-		}
-	}
-	if (plan->n_voices() > 1) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_model5_device: a plan of one voice only");
-	if (!plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_model5_device: model 5 only (gvtm_synthesize_targets_device takes the models 0 to 4)");
-	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
-	if (batch == 0) return GVTM_OK;
-	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, nullptr, batch, max_steps, d_audio, audio_stride,
+	return synthesize_targets(kTargetsModel5, plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, nullptr, batch, max_steps, d_audio, audio_stride,
 			d_out_counts, d_maxabs, d_status, hip_stream);
 }
 
@@ -174,26 +200,8 @@ int gvtm_synthesize_targets_model5_voices_device(gvtm_plan* plan, const int64_t*
 		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, const int32_t* d_voice_ids, size_t batch, size_t max_steps,
 		float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
 {
-	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
-	if (batch > 0) {
-		if (const int rc = check_batch_arguments(d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, batch, max_steps, d_audio); rc != GVTM_OK) return rc;
-		if (!d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
-		if (audio_stride < voices_output_capacity(plan, max_steps)) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_targets_voices_output_capacity(plan, max_steps)");
-		}
-	}
-	if (!plan->designs[0].model5) {
-		return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_model5_voices_device: model 5 only (gvtm_synthesize_targets_voices_device takes the models 0 to 4)");
-	}
-	// (launch_synthesis' rule, stated here so that a design-only plan shows it)
-	if (plan->designs[0].f32 && !plan->float5_voices) {
-		return fail(GVTM_ERR_UNSUPPORTED, "a gvtm_plan_create_model5_float plan has no launch of several voices (one voice per plan; "
-				"gvtm_plan_create_model5_float_voices makes the float plans that have)");
-	}
-	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
-	if (batch == 0) return GVTM_OK;
-	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, d_voice_ids, batch, max_steps, d_audio,
-			audio_stride, d_out_counts, d_maxabs, d_status, hip_stream);
+	return synthesize_targets(kTargetsModel5Voices, plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, d_voice_ids, batch, max_steps, d_audio, audio_stride,
+			d_out_counts, d_maxabs, d_status, hip_stream);
 }
 
 size_t gvtm_targets_voice_output_count(const gvtm_plan* plan, int voice, size_t n_steps)
@@ -212,19 +220,8 @@ int gvtm_synthesize_targets_voices_device(gvtm_plan* plan, const int64_t* d_list
 		const int32_t* d_point_steps, const float* d_point_values, const int32_t* d_step_counts, const int32_t* d_voice_ids, size_t batch, size_t max_steps,
 		float* d_audio, size_t audio_stride, int64_t* d_out_counts, float* d_maxabs, int32_t* d_status, void* hip_stream)
 {
-	if (!plan) return fail(GVTM_ERR_INVALID_ARGUMENT, "null plan");
-	if (batch > 0) {
-		if (const int rc = check_batch_arguments(d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, batch, max_steps, d_audio); rc != GVTM_OK) return rc;
-		if (!d_voice_ids) return fail(GVTM_ERR_INVALID_ARGUMENT, "null voice ids");
-		if (audio_stride < voices_output_capacity(plan, max_steps)) {
-			return fail(GVTM_ERR_INVALID_ARGUMENT, "audio_stride smaller than gvtm_targets_voices_output_capacity(plan, max_steps)");
-		}
-	}
-	if (plan->designs[0].model5) return fail(GVTM_ERR_UNSUPPORTED, "gvtm_synthesize_targets_voices_device: the models 0 to 4 only");
-	if (plan->device == GVTM_DEVICE_NONE) return refuse_design_only();
-	if (batch == 0) return GVTM_OK;
-	return check_and_launch(plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, d_voice_ids, batch, max_steps, d_audio,
-			audio_stride, d_out_counts, d_maxabs, d_status, hip_stream);
+	return synthesize_targets(kTargetsVoices, plan, d_list_offsets, n_lists, d_list_ids, d_point_steps, d_point_values, d_step_counts, d_voice_ids, batch, max_steps, d_audio, audio_stride,
+			d_out_counts, d_maxabs, d_status, hip_stream);
 }
 
 } // extern "C"

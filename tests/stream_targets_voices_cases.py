@@ -1,6 +1,7 @@
 """What the tests of the targets-fed streams of several voices share (gvtm_stream_push_targets_voices,
 gvtm_stream_push_targets_model5_voices): the sessions an utterance of voice v is cut into, with v's OWN filter length N_v,
-and the session driver.  An utterance is 16 lists of (steps, values), as in targets_cases.py.
+and the rules their schedules are held to (targets_io.session drives them).  An utterance is 16 lists of (steps, values), as in
+targets_cases.py.
 
 A voice's sessions, between them, must have
   * pieces of 1, granule - 1, granule and granule + 1 steps (the granule: 12 steps, model 5: 4) -- what a push keeps pending;
@@ -14,7 +15,6 @@ A voice's sessions, between them, must have
 `covers` states this rule, and the CPU test holds every session of the GPU tests to it."""
 import numpy as np
 
-import stream_targets_cases as sessions
 from stream_targets5_cases import pieces5
 
 GRANULE, GRANULE5 = 12, 4
@@ -81,32 +81,6 @@ def schedule_of(pieces_by_utterance):
     return [[int(p[i]) if i < len(p) else 0 for p in pieces_by_utterance] for i in range(pushes)]
 
 
-def session(stream, push, utterances, schedule, after_push=None):
-    """Pushes schedule[i][b] steps of utterance b in push i through `push` (a bound Stream.push_targets* method; the points of
-    those steps, counted from the push's first), then finishes -> (samples per utterance, maxabs)."""
-    batch = len(utterances)
-    done, outs = [0] * batch, [[] for _ in range(batch)]
-    for counts in schedule:
-        given = [sessions.slice_lists(utterances[b], done[b], int(counts[b])) for b in range(batch)]
-        got = push(given, np.asarray(counts, dtype=np.int32))
-        for b in range(batch):
-            outs[b].append(got[b])
-            done[b] += int(counts[b])
-        if after_push:
-            after_push(done)
-    tail, maxabs = stream.finish()
-    return [np.concatenate(outs[b] + [tail[b]]) for b in range(batch)], maxabs
-
-
-def same_as_one_shot(got, got_maxabs, one_shot, what=None):
-    """A session's samples, counts and peaks against a one-shot voices call's (audio [B][stride], counts, maxabs, ...), as bytes."""
-    audio, counts, maxabs = one_shot[:3]
-    for b in range(len(got)):
-        assert got[b].size == counts[b], (what, b, got[b].size, int(counts[b]))
-        assert got[b].tobytes() == audio[b, : counts[b]].tobytes(), (what, b)
-    assert np.asarray(got_maxabs).tobytes() == np.asarray(maxabs).tobytes(), what
-
-
 def log_bound(lists, done, n):
     """The most points a stream may hold for an utterance with `done` steps given: those of its last n + 12 steps, and one
     more per list."""
@@ -114,7 +88,7 @@ def log_bound(lists, done, n):
 
 
 def no_own_index(voice_ids):
-    """The rule of test_gpu_targets5_voices.at_own_index, restated: the grouping is a stable sort by voice, one workgroup per
+    """The rule of targets_io.at_own_index, restated: the grouping is a stable sort by voice, one workgroup per
     utterance; is NO utterance left at the workgroup of its own index?"""
     return not [b for g, b in enumerate(sorted(range(len(voice_ids)), key=lambda b: voice_ids[b])) if g == b]
 

@@ -48,8 +48,10 @@ import voices_matrix_cases as vm
 from device_io import current_stream, filled, to_device, to_host
 from modification_cases import wide_values
 from shape_matrix_cases import BATCH, POOL
+from stream_targets_cases import slice_lists  # noqa: F401 (the matrix tests cut their sessions with it)
 from stream_targets_voices_cases import GRANULE
 from targets_cases import FRIC_BW, FRIC_CF
+from targets_io import GUARD
 from voice_cases import oracle_config
 
 GROUPS = ((0, 1, 2), (3, 4, 5, 6), tuple(range(7, 16)))  # stage_interp's tick offsets: Lp < 3, Lp < 7, the rest
@@ -59,7 +61,6 @@ ROLE_A, ROLE_B, ROLE_C = (0, 3, 7), (1, 4, 8), (2, 5, 9)
 WHOLE, ONLY_STEP_0, EMPTY = 13, 14, 15
 NO_STEP_0 = (0, 3, EMPTY)  # pitch and fricVol may start at 0
 KEYS = 24  # key values per parameter, cycled
-GUARD = 0xA5  # every byte of the audio buffer before the call
 BAD_VOICE = 5
 STREAM_BATCH = 5
 
@@ -209,16 +210,6 @@ def coincidences(lists, C, N, S):
     return out
 
 
-def slice_lists(lists, first, count):
-    """The points of the steps [first, first + count), their steps counted from `first`: what a push of those steps is given."""
-    out = []
-    for steps, values in lists:
-        steps = np.asarray(steps, dtype=np.int64)
-        keep = (steps >= first) & (steps < first + count)
-        out.append(((steps[keep] - first).tolist(), np.asarray(values, dtype=np.float32)[keep]))
-    return out
-
-
 def pool_lists(C, N, pool, seed):
     """Every pool member's own lists."""
     return [edge_lists(C, N, int(s), seed + t) for t, s in enumerate(pool)]
@@ -268,29 +259,6 @@ def oracle_voices(cell, plan, case, workers=8):
 
 # ---- the device ----
 
-def run_targets(plan, utterances, step_counts, voice_ids=None):
-    """gvtm_synthesize_targets_voices_device (voice_ids given) or gvtm_synthesize_targets_device on `utterances` (16 lists
-    each) -> (audio float32 [B][stride] that started out as GUARD bytes, counts that started out -7, maxabs that started out
-    5.0, statuses that started out -9)."""
-    batch = len(step_counts)
-    offsets, steps, values = capi.pack_targets([l for u in utterances for l in u])
-    max_steps = max([int(s) for s in step_counts] + [0])
-    stride = plan.targets_output_capacity(max_steps) if voice_ids is None else plan.targets_voices_output_capacity(max_steps)
-    # (no table is empty on the device: one spare entry each)
-    d_offsets, d_steps, d_values, d_counts_in = to_device(offsets, np.concatenate([steps, np.zeros(1, np.int32)]),
-                                                           np.concatenate([values, np.zeros(1, np.float32)]), np.asarray(step_counts, dtype=np.int32))
-    d_audio = filled((batch, stride * 4), GUARD, np.uint8)
-    d_counts, d_maxabs, d_status = filled(batch, -7, np.int64), filled(batch, 5.0, np.float32), filled(batch, -9, np.int32)
-    tail = (batch, max_steps, d_audio, stride, d_counts, d_maxabs, d_status, current_stream())
-    if voice_ids is None:
-        plan.synthesize_targets_device(d_offsets, 16 * batch, None, d_steps, d_values, d_counts_in, *tail)
-    else:
-        d_voices, = to_device(np.asarray(voice_ids, dtype=np.int32))
-        plan.synthesize_targets_voices_device(d_offsets, 16 * batch, None, d_steps, d_values, d_counts_in, d_voices, *tail)
-    audio, counts, maxabs, statuses = to_host(d_audio, d_counts, d_maxabs, d_status)
-    return audio.view(np.float32).reshape(batch, stride), counts, maxabs, statuses
-
-
 def run_frames(plan, frames, step_counts):
     """gvtm_synthesize_batch_device on a plan of one step per frame, frames[b] float32 [S_b][16] -> (audio that started out as
     GUARD bytes, counts, maxabs)."""
@@ -305,8 +273,3 @@ def run_frames(plan, frames, step_counts):
     audio, counts, maxabs = to_host(d_audio, d_counts, d_maxabs)
     return audio.view(np.float32).reshape(batch, stride), counts, maxabs
 
-
-def guard_behind_counts(audio, counts):
-    """Is every sample behind a row's count (a row left out, count -1: the whole row) still the pattern?"""
-    pattern = np.frombuffer(bytes([GUARD] * 4), dtype=np.uint32)[0]
-    return all((audio[b, max(int(counts[b]), 0):].view(np.uint32) == pattern).all() for b in range(audio.shape[0]))

@@ -34,8 +34,9 @@ import gama_tts_amd as g
 import oracle
 import targets_cases
 import tracks
-from device_io import current_stream, filled, run_batch_device, to_device, to_host
+from device_io import run_batch_device
 from gama_tts_amd import capi
+from targets_io import run_targets
 from voice_cases import male_plan, padded
 
 pytestmark = pytest.mark.gpu
@@ -226,24 +227,11 @@ def odd_reference(seed, steps):
     return ref
 
 
-def run_targets(plan, step_counts):
-    """The entry on utterances 0 .. B - 1 of spoken() -> (audio float32 [B][stride] that started out zero, counts)."""
-    batch = len(step_counts)
-    offsets, steps, values = capi.pack_targets([l for b in range(batch) for l in spoken(b)[0]])
-    stride = plan.targets_output_capacity(max(step_counts))
-    d_offsets, d_steps, d_values, d_counts_in = to_device(offsets, np.concatenate([steps, np.zeros(1, np.int32)]),
-                                                           np.concatenate([values, np.zeros(1, np.float32)]), np.asarray(step_counts, dtype=np.int32))
-    d_audio, d_counts, d_status = filled((batch, stride), 0.0, np.float32), filled(batch, -7, np.int64), filled(batch, -9, np.int32)
-    plan.synthesize_targets_device(d_offsets, 16 * batch, None, d_steps, d_values, d_counts_in, batch, max(step_counts), d_audio, stride, d_counts,
-                                   None, d_status, current_stream())
-    audio, counts, statuses = to_host(d_audio, d_counts, d_status)
-    assert not statuses.any()
-    return audio, counts
-
-
 def check_odd_steps(plan, rows):
     assert int(plan._lib.gvtm_debug_chunk_length(plan._h, len(ODD_STEPS))) == CHUNK[rows]
-    audio, counts = run_targets(plan, ODD_STEPS)
+    # (zeros, not the guard pattern, behind the counts: check_against wants them)
+    audio, counts, _, statuses = run_targets(plan, [spoken(b)[0] for b in range(len(ODD_STEPS))], ODD_STEPS, peaks=False, fill=0)
+    assert not statuses.any()
     refs = [odd_reference(b, s) for b, s in enumerate(ODD_STEPS)]
     for b, s in enumerate(ODD_STEPS):
         assert refs[b].size == plan.targets_output_count(s)

@@ -18,11 +18,11 @@ import gama_tts_amd as g
 from gama_tts_amd import capi
 import stream_targets_cases as sessions
 import targets_cases
+from targets_io import one_shot
 import tracks
 from test_gpu_analysis import check_against_host, run_device
 from test_gpu_events_chunks import audio_plan
 from test_gpu_stream_events import stream_utterances
-from test_gpu_stream_targets import one_shot
 from voice_cases import configs, male_plan, model5_plan
 
 pytestmark = pytest.mark.gpu

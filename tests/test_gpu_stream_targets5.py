@@ -26,8 +26,8 @@ import stream_targets5_cases as sessions5
 import stream_targets_cases as sessions
 import targets5_cases as cases
 import tracks
-from device_io import current_stream, filled, to_device, to_host
 from parity_rules import check_batch
+from targets_io import one_shot, refused_push_changes_nothing, same, session
 from voice_cases import configs5, male_plan, model5_plan
 
 pytestmark = pytest.mark.gpu
@@ -40,48 +40,6 @@ spoken_lists = cases.targets_cases.spoken_lists
 @pytest.fixture(scope="module")
 def fixture():
     return np.load(os.path.join(oracle.GOLDEN_DIR, "targets5_golden.npz"))
-
-
-def one_shot(plan, utterances, step_counts):
-    """gvtm_synthesize_targets_model5_device on whole utterances -> (samples per utterance, maxabs)."""
-    batch = len(step_counts)
-    offsets, steps, values = capi.pack_targets([l for u in utterances for l in u])
-    max_steps = max([int(s) for s in step_counts] + [0])
-    stride = plan.targets_output_capacity(max_steps)
-    # (no table is empty on the device: one spare entry each)
-    d_offsets, d_steps, d_values, d_counts_in = to_device(offsets, np.concatenate([steps, np.zeros(1, np.int32)]),
-                                                           np.concatenate([values, np.zeros(1, np.float32)]), np.asarray(step_counts, dtype=np.int32))
-    d_audio, d_counts, d_maxabs, d_status = filled((batch, stride), 0.0, np.float32), filled(batch, -7, np.int64), filled(batch, 5.0, np.float32), filled(batch, -9, np.int32)
-    plan.synthesize_targets_model5_device(d_offsets, 16 * batch, None, d_steps, d_values, d_counts_in, batch, max_steps, d_audio, stride, d_counts,
-                                          d_maxabs, d_status, current_stream())
-    audio, counts, maxabs, statuses = to_host(d_audio, d_counts, d_maxabs, d_status)
-    assert not statuses.any()
-    assert [int(c) for c in counts] == [plan.targets_output_count(int(s)) for s in step_counts]
-    return [audio[b, : counts[b]].copy() for b in range(batch)], maxabs
-
-
-def session(stream, utterances, schedule, after_push=None):
-    """Pushes schedule[i][b] steps of utterance b in push i (the points of those steps, counted from the push's first), then
-    finishes -> (samples per utterance, maxabs, the samples each push returned for utterance 0)."""
-    batch = len(utterances)
-    done, outs, first = [0] * batch, [[] for _ in range(batch)], []
-    for counts in schedule:
-        given = [sessions.slice_lists(utterances[b], done[b], int(counts[b])) for b in range(batch)]
-        got = stream.push_targets_model5(given, np.asarray(counts, dtype=np.int32))
-        for b in range(batch):
-            outs[b].append(got[b])
-            done[b] += int(counts[b])
-        first.append(got[0].size)
-        if after_push:
-            after_push(done)
-    tail, maxabs = stream.finish()
-    return [np.concatenate(outs[b] + [tail[b]]) for b in range(batch)], maxabs, first
-
-
-def same(got, got_maxabs, want, want_maxabs):
-    for b in range(len(want)):
-        assert got[b].size == want[b].size and got[b].tobytes() == want[b].tobytes(), b
-    assert np.asarray(got_maxabs).tobytes() == np.asarray(want_maxabs).tobytes()
 
 
 def lockstep(pieces, batch):
@@ -177,50 +135,8 @@ def test_edges_of_resuming_and_the_bounded_log(float_class):
 # ---- e. a refused push leaves the stream as it was ----
 
 def test_a_refused_push_changes_nothing():
-    plan = model5_plan(float_class=True)
-    lib = plan._lib
-    totals = [250, 200, 200, 200, 220]
-    utterances = [spoken_lists(t, 50 + b) for b, t in enumerate(totals)]
-    want, want_maxabs = one_shot(plan, utterances, totals)
-    stream = g.Stream(plan, 5)
-    outs = [[] for _ in range(5)]
-
-    def push(counts):
-        given = [sessions.slice_lists(utterances[b], done[b], counts[b]) for b in range(5)]
-        for b, samples in enumerate(stream.push_targets_model5(given, np.asarray(counts, dtype=np.int32))):
-            outs[b].append(samples)
-            done[b] += counts[b]
-
-    done = [0] * 5
-    push([13, 13, 7, 25, 0])  # (steps pending in every utterance but the last)
-    held = stream.targets_points().copy()
-    # utterance 1: a value that is not finite; 2: a point at step == its count; 3: a count above max_steps
-    counts = [100, 100, 100, 100, 100]
-    given = [sessions.slice_lists(utterances[b], done[b], counts[b]) for b in range(5)]
-    bad = [list(u) for u in given]
-    bad[1][3] = ([5], np.float32([np.nan]))
-    bad[2][5] = ([0, 100], np.float32([1.0, 2.0]))
-    with pytest.raises(g.GvtmError) as refused:
-        stream.push_targets_model5(bad, np.asarray([100, 100, 100, 101, 100], dtype=np.int32), max_steps=100)
-    assert refused.value.status == INVALID_ARGUMENT and refused.value.statuses.tolist() == [0, 3, 4, 1, 0]
-    assert stream.targets_points().tolist() == held.tolist()
-    # a stride one sample short and a null audio buffer with samples due are refused the same way
-    offsets, steps, values = capi.pack_targets([l for u in given for l in u])
-    stride = stream.targets_capacity(100)
-    audio, out_counts, statuses = np.zeros((5, stride), np.float32), np.zeros(5, np.int64), np.full(5, -1, np.int32)
-    p = capi._ptr
-    # (utterance 3 holds 125 steps then and synthesizes 124 of them: more than 8 samples)
-    assert lib.gvtm_stream_push_targets_model5(stream._h, p(offsets), p(steps), p(values), None, 100, p(audio), 8, p(out_counts), p(statuses)) == INVALID_ARGUMENT
-    assert b"audio_stride" in lib.gvtm_last_error() and not statuses.any()
-    assert lib.gvtm_stream_push_targets_model5(stream._h, p(offsets), p(steps), p(values), None, 100, None, stride, p(out_counts), p(statuses)) == INVALID_ARGUMENT
-    assert stream.targets_points().tolist() == held.tolist() and not audio.any()
-    # the corrected push and the rest of the session: nothing was synthesized twice
-    push(counts)
-    push([t - d for t, d in zip(totals, done)])
-    tail, maxabs = stream.finish()
-    same([np.concatenate(outs[b] + [tail[b]]) for b in range(5)], maxabs, want, want_maxabs)
-    with pytest.raises(g.GvtmError):
-        stream.push_targets_model5(given, 100)  # finished
+    # (the stride of 8 samples is short: utterance 3 holds 125 steps then and synthesizes 124 of them)
+    refused_push_changes_nothing(model5_plan(float_class=True), "push_targets_model5", [250, 200, 200, 200, 220])
 
 
 # ---- f. feeds and plans ----

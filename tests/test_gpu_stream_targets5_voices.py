@@ -28,8 +28,7 @@ import targets5_cases as cases5
 import targets5_voices_cases as cases
 from parity_rules import check_batch
 from targets_cases import spoken_lists
-from test_gpu_stream_targets5 import one_shot as one_voice_one_shot
-from test_gpu_targets5_voices import at_own_index, run as one_shot_voices
+from targets_io import at_own_index, one_shot as one_voice_one_shot, run_targets as one_shot_voices, same_as_one_shot, session
 from voice_cases import male_plan
 from voice_files import VOICES
 
@@ -75,10 +74,10 @@ def fixture_sessions(fixtures, float_class, rows, chunk):
             utterances.append(lists)
         if held:
             stream.reset()
-        got, maxabs = sv.session(stream, stream.push_targets_model5_voices, utterances, schedule)
+        got, maxabs, _ = session(stream, utterances, schedule, push=stream.push_targets_model5_voices)
         want = one_shot_voices(plan, utterances, totals, ids)
         assert not want[3].any()
-        sv.same_as_one_shot(got, maxabs, want, (name, chunk))
+        same_as_one_shot(got, maxabs, want, (name, chunk))
         for b, (v, t) in enumerate(zip(ids, totals)):
             assert got[b].size == plan.targets_voice_output_count(v, t), (name, b)
         held += [(got[b], maxabs[b], refs[b]) for b in fixture_at]
@@ -145,8 +144,8 @@ def test_ragged_sessions_a_refused_push_and_reset_voices(float_class):
             assert refused.value.status == INVALID_ARGUMENT and refused.value.statuses.tolist() == [0, 3, 0, 0, 0, 0, 0]
             assert stream.targets_points().tolist() == held[-1]
 
-    got, maxabs = sv.session(stream, stream.push_targets_model5_voices, utterances, schedule, after_push)
-    sv.same_as_one_shot(got, maxabs, want, "ragged")
+    got, maxabs, _ = session(stream, utterances, schedule, after_push, push=stream.push_targets_model5_voices)
+    same_as_one_shot(got, maxabs, want, "ragged")
     assert held[-1][5] == 0
     # reset_voices with the ids permuted: the next session runs under the new voices' filters; once more after a session
     # that was not finished
@@ -155,8 +154,8 @@ def test_ragged_sessions_a_refused_push_and_reset_voices(float_class):
         stream.reset(voice_ids=permuted)
         schedule, totals = ragged_schedule(n, permuted)
         utterances = [spoken_lists(max(t, 1), 30 + b) for b, t in enumerate(totals)]
-        got, maxabs = sv.session(stream, stream.push_targets_model5_voices, utterances, schedule)
-        sv.same_as_one_shot(got, maxabs, one_shot_voices(plan, utterances, totals, permuted), tuple(permuted))
+        got, maxabs, _ = session(stream, utterances, schedule, push=stream.push_targets_model5_voices)
+        same_as_one_shot(got, maxabs, one_shot_voices(plan, utterances, totals, permuted), tuple(permuted))
         if permuted[0] == 2:
             stream.reset(voice_ids=ids)
             stream.push_targets_model5_voices([sessions.slice_lists(u, 0, min(t, 77)) for u, t in zip(utterances, totals)], np.minimum(totals, 77).astype(np.int32))

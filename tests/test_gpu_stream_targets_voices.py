@@ -21,8 +21,7 @@ import stream_targets_voices_cases as sv
 import tracks
 import voices_matrix_cases
 from targets_cases import spoken_lists
-from test_gpu_stream_targets import one_shot as one_voice_one_shot
-from test_gpu_targets_voices import run as one_shot_voices
+from targets_io import one_shot as one_voice_one_shot, run_targets as one_shot_voices, same_as_one_shot, session
 from voice_cases import configs, male_plan, model5_plan
 
 pytestmark = pytest.mark.gpu
@@ -52,8 +51,8 @@ def whole_session(plan, ids, utterances, pieces, stream=None):
     want = one_shot_voices(plan, utterances, totals, list(ids))
     assert not want[3].any()
     stream = stream or g.Stream(plan, len(ids), voice_ids=list(ids))
-    got, maxabs = sv.session(stream, stream.push_targets_voices, utterances, sv.schedule_of(pieces))
-    sv.same_as_one_shot(got, maxabs, want, tuple(ids))
+    got, maxabs, _ = session(stream, utterances, sv.schedule_of(pieces), push=stream.push_targets_voices)
+    same_as_one_shot(got, maxabs, want, tuple(ids))
     for b, v in enumerate(ids):
         assert got[b].size == plan.targets_voice_output_count(v, totals[b]), b
     return got
@@ -136,8 +135,8 @@ def test_the_log_is_bounded_by_each_utterances_own_window(names):
 
     pieces = [[120] * (total // 120)] * 2
     want = one_shot_voices(plan, utterances, [total] * 2, [0, 1])
-    got, maxabs = sv.session(stream, stream.push_targets_voices, utterances, sv.schedule_of(pieces), after_push)
-    sv.same_as_one_shot(got, maxabs, want, names)
+    got, maxabs, _ = session(stream, utterances, sv.schedule_of(pieces), after_push, push=stream.push_targets_voices)
+    same_as_one_shot(got, maxabs, want, names)
     # (the shorter window holds fewer points: a log kept by the longer one would show here)
     short = n.index(min(n))
     assert held[-1][short] < held[-1][1 - short]
@@ -204,7 +203,7 @@ def test_statuses_and_refusals():
     first = stream.push_targets_voices([sessions.slice_lists(u, 13, 100) for u in utterances], 100)
     rest = stream.push_targets_voices([sessions.slice_lists(u, 113, 187) for u in utterances], 187)
     tail, maxabs = stream.finish()
-    sv.same_as_one_shot([np.concatenate([start[b], first[b], rest[b], tail[b]]) for b in range(3)], maxabs, want)
+    same_as_one_shot([np.concatenate([start[b], first[b], rest[b], tail[b]]) for b in range(3)], maxabs, want)
     with pytest.raises(g.GvtmError):
         stream.push_targets_voices(bad, 100)  # finished
     # a frames-fed stream is refused until a reset
@@ -214,8 +213,8 @@ def test_statuses_and_refusals():
         stream.push_targets_voices([sessions.slice_lists(u, 0, 30) for u in utterances], 30)
     assert e.value.status == INVALID_ARGUMENT and "frames" in str(e.value)
     stream.reset()
-    got, maxabs = sv.session(stream, stream.push_targets_voices, utterances, [[150] * 3, [150] * 3])
-    sv.same_as_one_shot(got, maxabs, want)
+    got, maxabs, _ = session(stream, utterances, [[150] * 3, [150] * 3], push=stream.push_targets_voices)
+    same_as_one_shot(got, maxabs, want)
     # a model 5 stream has the other entry
     five = g.Stream(model5_plan("male"), 1)
     with pytest.raises(g.GvtmError) as e:

@@ -13,9 +13,9 @@ import analysis_cases as ac
 import gama_tts_amd as g
 from gama_tts_amd import capi
 from targets_cases import spoken_lists
+from targets_io import run_targets as one_shot_voices
 from test_gpu_analysis import run_device
 from test_gpu_stream_listen import Heard, analysis, same_views, targets_session
-from test_gpu_targets_voices import run as one_shot_voices
 from voice_cases import configs
 
 pytestmark = pytest.mark.gpu

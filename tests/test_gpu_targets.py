@@ -21,11 +21,11 @@ import oracle
 import targets_cases as cases
 from device_io import current_stream, filled, to_device, to_host
 from parity_rules import TOL, check_batch, within
+from targets_io import GUARD, guard_behind_counts, run_targets
 from voice_cases import configs, male_plan, model5_plan
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0xA5  # every byte of the audio buffer before the call
 UNSUPPORTED = 4
 LONGEST = 6200  # steps the host rule's frames are made for, once per utterance: a shorter utterance's are their first rows
 
@@ -53,33 +53,6 @@ def host_frames(plan, key, seed, n_steps, wide=False):
     return lists, frames[:n_steps]
 
 
-def run(plan, utterances, step_counts, ids=None, max_steps=None, status=True, doctor=None, peaks=True):
-    """The entry on `utterances` (16 lists each; with ids: the lists, and ids [B][16] into them) -> (audio float32
-    [B][stride] that started out as GUARD bytes, counts, maxabs, statuses)."""
-    lists = utterances if ids is not None else [l for u in utterances for l in u]
-    batch = len(step_counts)
-    offsets, steps, values = capi.pack_targets(lists)
-    if doctor:
-        doctor(offsets, steps, values)
-    max_steps = max([int(s) for s in step_counts] + [0]) if max_steps is None else max_steps
-    stride = plan.targets_output_capacity(max_steps)
-    # (no table is empty on the device: one spare entry each)
-    d_offsets, d_steps, d_values, d_counts_in = to_device(offsets, np.concatenate([steps, np.zeros(1, np.int32)]),
-                                                           np.concatenate([values, np.zeros(1, np.float32)]), np.asarray(step_counts, dtype=np.int32))
-    d_ids = None if ids is None else to_device(np.asarray(ids, dtype=np.int32).reshape(batch, 16))[0]
-    d_audio = filled((batch, stride * 4), GUARD, np.uint8)
-    d_counts, d_maxabs, d_status = filled(batch, -7, np.int64), filled(batch, 5.0, np.float32), filled(batch, -9, np.int32)
-    plan.synthesize_targets_device(d_offsets, len(lists), d_ids, d_steps, d_values, d_counts_in, batch, max_steps, d_audio, stride, d_counts,
-                                   d_maxabs if peaks else None, d_status if status else None, current_stream())
-    audio, counts, maxabs, statuses = to_host(d_audio, d_counts, d_maxabs, d_status)
-    return audio.view(np.float32).reshape(batch, stride), counts, maxabs, statuses
-
-
-def guard_behind_counts(audio, counts):
-    pattern = np.frombuffer(bytes([GUARD] * 4), dtype=np.uint32)[0]
-    return all((audio[b, int(counts[b]):].view(np.uint32) == pattern).all() for b in range(audio.shape[0]))
-
-
 def oracle_refs(plan, cfg, key, seeds, step_counts, wide=False):
     rate = plan.info.internal_rate_hz
     assert oracle.derive(cfg, rate).control_steps == 1
@@ -89,7 +62,7 @@ def oracle_refs(plan, cfg, key, seeds, step_counts, wide=False):
 def check_float(plan, cfg, key, step_counts, wide=False):
     seeds = list(range(len(step_counts)))
     utterances = [host_frames(plan, key, seed, s, wide)[0] for seed, s in zip(seeds, step_counts)]
-    audio, counts, maxabs, statuses = run(plan, utterances, step_counts)
+    audio, counts, maxabs, statuses = run_targets(plan, utterances, step_counts)
     assert not statuses.any()
     refs = oracle_refs(plan, cfg, key, seeds, step_counts, wide)
     for b, s in enumerate(step_counts):
@@ -121,7 +94,7 @@ def test_float_equals_the_batch_entry_at_one_step_per_frame():
     step_counts = [ragged(chunk, n)[i] for i in (1, 3, 5, 6, 7, 8, 10, 12, 13)]
     seeds = list(range(9))
     utterances = [host_frames(plan, "male", seed, s)[0] for seed, s in zip(seeds, step_counts)]
-    audio, counts, maxabs, _ = run(plan, utterances, step_counts)
+    audio, counts, maxabs, _ = run_targets(plan, utterances, step_counts)
     rate = plan.info.internal_rate_hz
     today = male_plan(precision=capi.PRECISION_F32, crate=rate)
     assert today.info.control_steps == 1 and today.info.internal_rate_hz == rate
@@ -171,7 +144,7 @@ def test_double_classes_against_the_oracle(precision, rows):
     seeds = list(range(5))
     # (the double classes' frames: the same float rule, under this plan's rate)
     utterances = [host_frames(plan, "male", seed, s)[0] for seed, s in zip(seeds, step_counts)]
-    audio, counts, maxabs, statuses = run(plan, utterances, step_counts)
+    audio, counts, maxabs, statuses = run_targets(plan, utterances, step_counts)
     assert not statuses.any()
     refs = oracle_refs(plan, oracle.male_config(44100.0, 1), "male", seeds, step_counts)
     for b, ref in enumerate(refs):
@@ -189,9 +162,9 @@ def test_shared_lists_give_the_bytes_of_lists_of_their_own():
     moved = [cases.spoken_lists(700, 10 + b)[9] for b in range(8)]  # r3, one list per utterance
     step_counts = [700, 650, 700, 1, 333, 700, 0, 512]
     ids = [[16 + b if p == 9 else p for p in range(16)] for b in range(8)]
-    a = run(plan, shared + moved, step_counts, ids=ids, max_steps=700)
+    a = run_targets(plan, shared + moved, step_counts, ids=ids, max_steps=700)
     own = [[moved[b] if p == 9 else shared[p] for p in range(16)] for b in range(8)]
-    b = run(plan, own, step_counts, max_steps=700)
+    b = run_targets(plan, own, step_counts, max_steps=700)
     assert not a[3].any() and not b[3].any()
     assert a[0].tobytes() == b[0].tobytes() and a[1].tolist() == b[1].tolist() and a[2].tobytes() == b[2].tobytes()
     assert len({a[0][i, : a[1][i]].tobytes() for i in (0, 2, 5)}) == 3  # (the one parameter that differs is heard)
@@ -220,25 +193,25 @@ def test_a_refused_utterance_of_every_status_between_good_ones():
         offsets[10 * 16 + 3] = offsets[10 * 16 + 4] + 1  # utterance 10's list 3 ends before it begins
 
     lists = [l for u in utterances for l in u]
-    audio, counts, maxabs, statuses = run(plan, lists, step_counts, ids=ids, max_steps=400, doctor=doctor)
+    audio, counts, maxabs, statuses = run_targets(plan, lists, step_counts, ids=ids, max_steps=400, doctor=doctor)
     assert statuses.tolist() == want
     zero = plan.targets_output_count(0)
     assert all(counts[b] == (plan.targets_output_count(step_counts[b]) if want[b] == 0 else zero) for b in range(13))
     assert guard_behind_counts(audio, counts)
     # the good utterances' bytes are those of the same batch without the refused ones
     keep = [b for b in range(13) if want[b] == 0]
-    alone = run(plan, [utterances[b] for b in keep], [step_counts[b] for b in keep], max_steps=400)
+    alone = run_targets(plan, [utterances[b] for b in keep], [step_counts[b] for b in keep], max_steps=400)
     assert not alone[3].any()
     for i, b in enumerate(keep):
         assert alone[1][i] == counts[b] and alone[2][i].tobytes() == maxabs[b].tobytes()
         assert alone[0][i, : counts[b]].tobytes() == audio[b, : counts[b]].tobytes(), b
     # a refused utterance is one of 0 steps
-    empty = run(plan, [good(0)], [0], max_steps=400)
+    empty = run_targets(plan, [good(0)], [0], max_steps=400)
     for b in range(13):
         if want[b]:
             assert audio[b, :zero].tobytes() == empty[0][0, :zero].tobytes() and maxabs[b] == empty[2][0]
     # no status asked for: the same audio
-    silent = run(plan, lists, step_counts, ids=ids, max_steps=400, doctor=doctor, status=False)
+    silent = run_targets(plan, lists, step_counts, ids=ids, max_steps=400, doctor=doctor, status=False)
     assert silent[0].tobytes() == audio.tobytes() and (silent[3] == -9).all()
     # nothing to do
     assert plan._lib.gvtm_synthesize_targets_device(plan._h, None, 0, None, None, None, None, 0, 0, None, 0, None, None, None, None) == 0
@@ -273,8 +246,8 @@ def test_forced_eight_rows_on_the_frames_and_the_targets_entry():
     assert shape[0] == 4 and shape[2] <= 160 * 1024 < eight._lib.gvtm_debug_lds_bytes(eight._h, 8)
     step_counts = [24, 24]
     utterances = [host_frames(eight, "male", seed, 24)[0] for seed in (0, 1)]
-    audio, counts, maxabs, statuses = run(eight, utterances, step_counts)  # (raises on a status other than 0)
-    one = run(male_plan(precision=capi.PRECISION_F32), utterances, step_counts)
+    audio, counts, maxabs, statuses = run_targets(eight, utterances, step_counts)  # (raises on a status other than 0)
+    one = run_targets(male_plan(precision=capi.PRECISION_F32), utterances, step_counts)
     assert not statuses.any() and not one[3].any()
     assert counts.tolist() == one[1].tolist() == [eight.targets_output_count(24)] * 2 and maxabs.tobytes() == one[2].tobytes()
     assert audio.tobytes() == one[0].tobytes() and guard_behind_counts(audio, counts)

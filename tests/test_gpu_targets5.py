@@ -13,53 +13,21 @@ import os
 import numpy as np
 import pytest
 
-from gama_tts_amd import capi
 import oracle
 import targets5_cases as cases
-from device_io import current_stream, filled, to_device, to_host
 from parity_rules import check_batch
+from targets_io import guard_behind_counts, run_targets
 from voice_cases import model5_plan
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 0xA5  # every byte of the audio buffer before the call
-
 
 @pytest.fixture(scope="module")
 def fixture():
     return np.load(os.path.join(oracle.GOLDEN_DIR, "targets5_golden.npz"))
 
 
-def run(plan, utterances, step_counts, ids=None, max_steps=None, status=True, doctor=None, peaks=True, counts=True, steps_in=True):
-    """The entry on `utterances` (16 lists each; with ids: the lists, and ids [B][16] into them) -> (audio float32
-    [B][stride] that started out as GUARD bytes, counts, maxabs, statuses); an output not asked for keeps its fill."""
-    lists = utterances if ids is not None else [l for u in utterances for l in u]
-    batch = len(step_counts)
-    offsets, steps, values = capi.pack_targets(lists)
-    if doctor:
-        doctor(offsets, steps, values)
-    max_steps = max([int(s) for s in step_counts] + [0]) if max_steps is None else max_steps
-    stride = plan.targets_output_capacity(max_steps)
-    # (no table is empty on the device: one spare entry each)
-    d_offsets, d_steps, d_values, d_counts_in = to_device(offsets, np.concatenate([steps, np.zeros(1, np.int32)]),
-                                                           np.concatenate([values, np.zeros(1, np.float32)]), np.asarray(step_counts, dtype=np.int32))
-    d_ids = None if ids is None else to_device(np.asarray(ids, dtype=np.int32).reshape(batch, 16))[0]
-    d_audio = filled((batch, stride * 4), GUARD, np.uint8)
-    d_counts, d_maxabs, d_status = filled(batch, -7, np.int64), filled(batch, 5.0, np.float32), filled(batch, -9, np.int32)
-    plan.synthesize_targets_model5_device(d_offsets, len(lists), d_ids, d_steps, d_values, d_counts_in if steps_in else None, batch, max_steps, d_audio,
-                                          stride, d_counts if counts else None, d_maxabs if peaks else None, d_status if status else None,
-                                          current_stream())
-    audio, out_counts, maxabs, statuses = to_host(d_audio, d_counts, d_maxabs, d_status)
-    return audio.view(np.float32).reshape(batch, stride), out_counts, maxabs, statuses
-
-
-def guard_behind_counts(audio, counts):
-    pattern = np.frombuffer(bytes([GUARD] * 4), dtype=np.uint32)[0]
-    return all((audio[b, int(counts[b]):].view(np.uint32) == pattern).all() for b in range(audio.shape[0]))
-
-
 def check_against_fixture(fixture, plan, float_class, step_counts):
-    audio, counts, maxabs, statuses = run(plan, [cases.lists_of(s) for s in step_counts], step_counts)
+    audio, counts, maxabs, statuses = run_targets(plan, [cases.lists_of(s) for s in step_counts], step_counts)
     assert not statuses.any()
     refs = [fixture[cases.name(float_class, s)] for s in step_counts]
     for s, ref in zip(step_counts, refs):
@@ -105,8 +73,8 @@ def test_double_class_against_the_reference(fixture, rows, chunk):
 def test_double_class_two_rows_equal_one_row(fixture):
     step_counts = [cases.N + 24, 51, 0, 25, 2 * cases.N + 24 + 5]
     utterances = [cases.lists_of(s) for s in step_counts]
-    one = run(model5_plan(rows=1), utterances, step_counts)
-    two = run(model5_plan(rows=2), utterances, step_counts)
+    one = run_targets(model5_plan(rows=1), utterances, step_counts)
+    two = run_targets(model5_plan(rows=2), utterances, step_counts)
     assert one[1].tolist() == two[1].tolist() and one[0].tobytes() == two[0].tobytes() and one[2].tobytes() == two[2].tobytes()
 
 
@@ -115,7 +83,7 @@ def test_double_class_two_rows_equal_one_row(fixture):
 def test_samples_are_the_interactive_models_not_the_batch_protocols(fixture):
     plan = model5_plan(float_class=True)
     for s in cases.PLAIN:
-        audio, counts, _, _ = run(plan, [cases.lists_of(s)], [s])
+        audio, counts, _, _ = run_targets(plan, [cases.lists_of(s)], [s])
         got = audio[0, : counts[0]]
         assert got.tobytes() == fixture[cases.name(True, s)].tobytes()
         assert got.tobytes() != fixture[cases.name(True, s, plain=True)].tobytes()
@@ -130,9 +98,9 @@ def test_shared_lists_give_the_bytes_of_lists_of_their_own(float_class):
     moved = [cases.targets_cases.spoken_lists(700, 10 + b)[9] for b in range(8)]  # r3, one list per utterance: fifteen are shared
     step_counts = [700, 650, 700, 1, 333, 700, 0, 512]
     ids = [[16 + b if p == 9 else p for p in range(16)] for b in range(8)]
-    a = run(plan, shared + moved, step_counts, ids=ids, max_steps=700)
+    a = run_targets(plan, shared + moved, step_counts, ids=ids, max_steps=700)
     own = [[moved[b] if p == 9 else shared[p] for p in range(16)] for b in range(8)]
-    b = run(plan, own, step_counts, max_steps=700)
+    b = run_targets(plan, own, step_counts, max_steps=700)
     assert not a[3].any() and not b[3].any()
     assert a[0].tobytes() == b[0].tobytes() and a[1].tolist() == b[1].tolist() and a[2].tobytes() == b[2].tobytes()
     assert guard_behind_counts(a[0], a[1])
@@ -163,25 +131,25 @@ def test_a_refused_utterance_of_every_status_between_good_ones(float_class, rows
         offsets[10 * 16 + 3] = offsets[10 * 16 + 4] + 1  # utterance 10's list 3 ends before it begins
 
     lists = [l for u in utterances for l in u]
-    audio, counts, maxabs, statuses = run(plan, lists, step_counts, ids=ids, max_steps=400, doctor=doctor)
+    audio, counts, maxabs, statuses = run_targets(plan, lists, step_counts, ids=ids, max_steps=400, doctor=doctor)
     assert statuses.tolist() == want
     zero = plan.targets_output_count(0)
     assert all(counts[b] == (plan.targets_output_count(step_counts[b]) if want[b] == 0 else zero) for b in range(13))
     assert guard_behind_counts(audio, counts)
     # the good utterances' bytes are those of the same batch without the refused ones
     keep = [b for b in range(13) if want[b] == 0]
-    alone = run(plan, [utterances[b] for b in keep], [step_counts[b] for b in keep], max_steps=400)
+    alone = run_targets(plan, [utterances[b] for b in keep], [step_counts[b] for b in keep], max_steps=400)
     assert not alone[3].any()
     for i, b in enumerate(keep):
         assert alone[1][i] == counts[b] and alone[2][i].tobytes() == maxabs[b].tobytes()
         assert alone[0][i, : counts[b]].tobytes() == audio[b, : counts[b]].tobytes(), b
     # a refused utterance is one of 0 steps
-    empty = run(plan, [good(0)], [0], max_steps=400)
+    empty = run_targets(plan, [good(0)], [0], max_steps=400)
     for b in range(13):
         if want[b]:
             assert audio[b, :zero].tobytes() == empty[0][0, :zero].tobytes() and maxabs[b] == empty[2][0]
     # no status asked for: the same audio
-    silent = run(plan, lists, step_counts, ids=ids, max_steps=400, doctor=doctor, status=False)
+    silent = run_targets(plan, lists, step_counts, ids=ids, max_steps=400, doctor=doctor, status=False)
     assert silent[0].tobytes() == audio.tobytes() and (silent[3] == -9).all()
     # nothing to do
     assert plan._lib.gvtm_synthesize_targets_model5_device(plan._h, None, 0, None, None, None, None, 0, 0, None, 0, None, None, None, None) == 0
@@ -193,12 +161,12 @@ def test_null_step_counts_and_null_outputs(fixture):
     plan = model5_plan(float_class=True)
     s = 2 * 52 + 3
     utterances = [cases.lists_of(s)] * 3
-    full = run(plan, utterances, [s] * 3)
+    full = run_targets(plan, utterances, [s] * 3)
     assert full[0][0, : full[1][0]].tobytes() == fixture[cases.name(True, s)].tobytes()
     # d_step_counts == NULL: every utterance has max_steps steps
-    every = run(plan, utterances, [s] * 3, steps_in=False)
+    every = run_targets(plan, utterances, [s] * 3, steps_in=False)
     assert every[0].tobytes() == full[0].tobytes() and every[1].tolist() == full[1].tolist() and every[2].tobytes() == full[2].tobytes()
     # no status, no peaks, no counts: the same samples, the fills untouched
-    bare = run(plan, utterances, [s] * 3, status=False, peaks=False, counts=False)
+    bare = run_targets(plan, utterances, [s] * 3, status=False, peaks=False, counts=False)
     assert bare[0].tobytes() == full[0].tobytes()
     assert (bare[1] == -7).all() and (bare[2] == 5.0).all() and (bare[3] == -9).all()

@@ -23,15 +23,15 @@ from gama_tts_amd import capi
 import oracle
 import targets5_cases as cases5
 import targets5_voices_cases as cases
-from device_io import current_stream, filled, to_device, to_host
+from device_io import filled, to_device, to_host
 from parity_rules import check_batch
 from targets_cases import spoken_lists
+from targets_io import GUARD, at_own_index, guard_behind_counts, run_targets
 from voice_cases import configs
 from voice_files import VOICES
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0xA5  # every byte of the audio buffer before the call
 OK, INVALID_ARGUMENT, UNSUPPORTED = 0, 1, 4
 BAD_VOICE = 5
 ENTRY = "gvtm_synthesize_targets_model5_voices_device"
@@ -43,39 +43,6 @@ SHAPE_IDS = ["float-chunk60", "float-chunk52", "double-chunk56"]
 @pytest.fixture(scope="module")
 def fixtures():
     return (np.load(os.path.join(oracle.GOLDEN_DIR, "targets5_voices_golden.npz")), np.load(os.path.join(oracle.GOLDEN_DIR, "targets5_golden.npz")))
-
-
-def run(plan, utterances, step_counts, voice_ids=None, ids=None, max_steps=None, status=True, peaks=True, counts=True, doctor=None):
-    """gvtm_synthesize_targets_model5_voices_device (voice_ids given) or gvtm_synthesize_targets_model5_device on `utterances`
-    (16 lists each; with ids: the lists, and ids [B][16] into them) -> (audio float32 [B][stride] that started out as GUARD
-    bytes, counts that started out -7, maxabs that started out 5.0, statuses that started out -9)."""
-    lists = utterances if ids is not None else [l for u in utterances for l in u]
-    batch = len(step_counts)
-    offsets, steps, values = capi.pack_targets(lists)
-    if doctor:
-        doctor(offsets, steps, values)
-    max_steps = max([int(s) for s in step_counts] + [0]) if max_steps is None else max_steps
-    stride = plan.targets_output_capacity(max_steps) if voice_ids is None else plan.targets_voices_output_capacity(max_steps)
-    # (no table is empty on the device: one spare entry each)
-    d_offsets, d_steps, d_values, d_counts_in = to_device(offsets, np.concatenate([steps, np.zeros(1, np.int32)]),
-                                                           np.concatenate([values, np.zeros(1, np.float32)]), np.asarray(step_counts, dtype=np.int32))
-    d_ids = None if ids is None else to_device(np.asarray(ids, dtype=np.int32).reshape(batch, 16))[0]
-    d_audio = filled((batch, stride * 4), GUARD, np.uint8)
-    d_counts, d_maxabs, d_status = filled(batch, -7, np.int64), filled(batch, 5.0, np.float32), filled(batch, -9, np.int32)
-    tail = (batch, max_steps, d_audio, stride, d_counts if counts else None, d_maxabs if peaks else None, d_status if status else None, current_stream())
-    if voice_ids is None:
-        plan.synthesize_targets_model5_device(d_offsets, len(lists), d_ids, d_steps, d_values, d_counts_in, *tail)
-    else:
-        d_voices, = to_device(np.asarray(voice_ids, dtype=np.int32))
-        plan.synthesize_targets_model5_voices_device(d_offsets, len(lists), d_ids, d_steps, d_values, d_counts_in, d_voices, *tail)
-    audio, out_counts, maxabs, statuses = to_host(d_audio, d_counts, d_maxabs, d_status)
-    return audio.view(np.float32).reshape(batch, stride), out_counts, maxabs, statuses
-
-
-def guard_behind_counts(audio, counts):
-    """Is every sample behind a row's count (a row left out, count -1: the whole row) still the pattern?"""
-    pattern = np.frombuffer(bytes([GUARD] * 4), dtype=np.uint32)[0]
-    return all((audio[b, max(int(counts[b]), 0):].view(np.uint32) == pattern).all() for b in range(audio.shape[0]))
 
 
 class Singles:
@@ -96,7 +63,7 @@ class Singles:
         for v in sorted(set(w for w in voice_ids if 0 <= w < len(self.names))):
             mine = [b for b, w in enumerate(voice_ids) if w == v]
             plan = self.plan(v)
-            audio, counts, maxabs, statuses = run(plan, [utterances[b] for b in mine], [step_counts[b] for b in mine], max_steps=max_steps)
+            audio, counts, maxabs, statuses = run_targets(plan, [utterances[b] for b in mine], [step_counts[b] for b in mine], max_steps=max_steps)
             assert not statuses.any() and guard_behind_counts(audio, counts)
             for i, b in enumerate(mine):
                 assert counts[i] == plan.targets_output_count(step_counts[b])
@@ -124,11 +91,6 @@ def shuffled_ids(batch, seed):
     return order, ids.reshape(batch, 16)
 
 
-def at_own_index(voice_ids):
-    """The utterances that the grouping (a stable sort by voice, one workgroup each) leaves at the workgroup of their own index."""
-    return [b for g, b in enumerate(sorted(range(len(voice_ids)), key=lambda b: voice_ids[b])) if g == b]
-
-
 # ---- a. as the one-voice plans, in every shape; implicit lists and list ids ----
 
 # (the two voices that take every edge, the voice with a single utterance; a fourth voice of the five has none)
@@ -154,7 +116,7 @@ def test_as_the_one_voice_plans(shape, full, one):
         utterances = [spoken_lists(s, 40 * half + b) for b, s in enumerate(step_counts)]
         refs = singles.of(utterances, step_counts, voice_ids, max(step_counts))
         # d_list_ids == NULL: utterance b walks the lists 16 b + p, whichever workgroup it runs in
-        got = run(plan, utterances, step_counts, voice_ids)
+        got = run_targets(plan, utterances, step_counts, voice_ids)
         assert not got[3].any() and guard_behind_counts(got[0], got[1])
         for b, s in enumerate(step_counts):
             assert got[1][b] == plan.targets_voice_output_count(voice_ids[b], s), b
@@ -162,7 +124,7 @@ def test_as_the_one_voice_plans(shape, full, one):
         # list ids: the same lists stored in another order
         order, ids = shuffled_ids(len(step_counts), half)
         flat = [l for u in utterances for l in u]
-        with_ids = run(plan, [flat[i] for i in order], step_counts, voice_ids, ids=ids)
+        with_ids = run_targets(plan, [flat[i] for i in order], step_counts, voice_ids, ids=ids)
         assert not with_ids[3].any() and guard_behind_counts(with_ids[0], with_ids[1])
         assert_as_singles(with_ids, refs, (chunk, half, "ids"))
     singles.close()
@@ -184,7 +146,7 @@ def test_against_the_reference(fixtures, float_class, rows, chunk):
         batch.append((0, s, cases5.lists_of(s), male[cases5.name(float_class, s)]))
     batch = [batch[i] for i in np.random.default_rng(5).permutation(len(batch))]
     voice_ids, step_counts = [c[0] for c in batch], [c[1] for c in batch]
-    audio, counts, maxabs, statuses = run(plan, [c[2] for c in batch], step_counts, voice_ids)
+    audio, counts, maxabs, statuses = run_targets(plan, [c[2] for c in batch], step_counts, voice_ids)
     assert not statuses.any()
     check_batch(audio, counts, maxabs, [c[3] for c in batch], float_class)
     assert guard_behind_counts(audio, counts)
@@ -199,11 +161,11 @@ def test_shared_lists_across_five_voices(float_class):
     lists = spoken_lists(700, 3)
     voice_ids = [2, 0, 4, 1, 3]
     ids = [list(range(16))] * 5
-    got = run(plan, lists, [700] * 5, voice_ids, ids=ids)
+    got = run_targets(plan, lists, [700] * 5, voice_ids, ids=ids)
     assert not got[3].any() and guard_behind_counts(got[0], got[1])
     assert len({got[0][b, : got[1][b]].tobytes() for b in range(5)}) == 5  # five speakers
     for b, v in enumerate(voice_ids):
-        ref = run(singles.plan(v), lists, [700], ids=ids[:1])
+        ref = run_targets(singles.plan(v), lists, [700], ids=ids[:1])
         assert got[1][b] == ref[1][0] == plan.targets_voice_output_count(v, 700) and got[2][b].tobytes() == ref[2][0].tobytes()
         assert got[0][b, : got[1][b]].tobytes() == ref[0][0, : ref[1][0]].tobytes(), v
     singles.close()
@@ -231,7 +193,7 @@ def test_refused_utterances_between_good_ones(float_class):
     def doctor(offsets, steps, values):
         offsets[5 * 16 + 3] = offsets[5 * 16 + 4] + 1  # utterance 5's list 3 ends before it begins
 
-    audio, counts, maxabs, statuses = run(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor)
+    audio, counts, maxabs, statuses = run_targets(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor)
     assert statuses.tolist() == want
     assert guard_behind_counts(audio, counts)
     # a voice outside the plan: left out, the whole row still the pattern (guard_behind_counts above)
@@ -240,26 +202,26 @@ def test_refused_utterances_between_good_ones(float_class):
     # statuses 1 to 4: an utterance of 0 steps of its voice, the one-voice plan's
     for b in (4, 5, 6, 7):
         v = voice_ids[b]
-        empty = run(singles.plan(v), [good(0)], [0], max_steps=400)
+        empty = run_targets(singles.plan(v), [good(0)], [0], max_steps=400)
         zero = plan.targets_voice_output_count(v, 0)
         assert counts[b] == zero == empty[1][0] and maxabs[b].tobytes() == empty[2][0].tobytes()
         assert audio[b, :zero].tobytes() == empty[0][0, :zero].tobytes(), b
     # the good utterances' bytes, counts and peaks are those of the same batch without the refused ones
     keep = [b for b in range(len(want)) if want[b] == 0]
-    alone = run(plan, [utterances[b] for b in keep], [step_counts[b] for b in keep], [voice_ids[b] for b in keep], max_steps=400)
+    alone = run_targets(plan, [utterances[b] for b in keep], [step_counts[b] for b in keep], [voice_ids[b] for b in keep], max_steps=400)
     assert not alone[3].any()
     for i, b in enumerate(keep):
         assert counts[b] == alone[1][i] == plan.targets_voice_output_count(voice_ids[b], step_counts[b])
         assert maxabs[b].tobytes() == alone[2][i].tobytes()
         assert audio[b, : counts[b]].tobytes() == alone[0][i, : counts[b]].tobytes(), b
     # d_status, d_out_counts and d_maxabs left out in turn: the same audio, the others' values, the fill untouched
-    silent = run(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, status=False)
+    silent = run_targets(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, status=False)
     assert silent[0].tobytes() == audio.tobytes() and (silent[3] == -9).all() and silent[1].tolist() == counts.tolist()
     assert silent[2].tobytes() == maxabs.tobytes()
-    uncounted = run(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, counts=False)
+    uncounted = run_targets(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, counts=False)
     assert uncounted[0].tobytes() == audio.tobytes() and uncounted[3].tolist() == want and (uncounted[1] == -7).all()
     assert uncounted[2].tobytes() == maxabs.tobytes()
-    peakless = run(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, peaks=False)
+    peakless = run_targets(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, peaks=False)
     assert peakless[0].tobytes() == audio.tobytes() and peakless[3].tolist() == want and (peakless[2] == 5.0).all()
     assert peakless[1].tolist() == counts.tolist()
     singles.close()
@@ -277,8 +239,8 @@ def test_one_voice(kind):
     step_counts = [n + 1, 0, chunk + 1, 2 * n + chunk + 5, 5]
     assert plan.targets_voices_output_capacity(max(step_counts)) == single.targets_output_capacity(max(step_counts))
     utterances = [spoken_lists(s, b) for b, s in enumerate(step_counts)]
-    a = run(plan, utterances, step_counts, [0] * 5)
-    b = run(single, utterances, step_counts)
+    a = run_targets(plan, utterances, step_counts, [0] * 5)
+    b = run_targets(single, utterances, step_counts)
     assert not a[3].any() and not b[3].any() and guard_behind_counts(a[0], a[1])
     assert a[0].tobytes() == b[0].tobytes() and a[1].tolist() == b[1].tolist() and a[2].tobytes() == b[2].tobytes()
     assert a[1].tolist() == [single.targets_output_count(s) for s in step_counts]

@@ -40,9 +40,10 @@ from gama_tts_amd import capi
 from parity_rules import TOL, check_batch, peak_err, within
 from shape_matrix_cases import (BATCH, CELLS, FALL_BACK, LAUNCHABLE, POOL, STREAM_FALL_BACK, cell_id, chunk_length, float_model, launch_shape,
                                 plan_of, seed_of, stream_launch_shape, stream_rows)
-from targets_matrix_cases import (BAD_VOICE, GROUPS, LETTERS, STREAM_BATCH, VOICE_CELLS, coincidences, edge_lists, guard_behind_counts,
-                                  host_frames, oracle_voices, pool_lists, resume_edges, run_frames, run_targets, slice_lists, step_pool,
-                                  stream_bases, stream_pieces, stream_total, tiled_steps, voices_case)
+from targets_io import guard_behind_counts, run_targets
+from targets_matrix_cases import (BAD_VOICE, GROUPS, LETTERS, STREAM_BATCH, VOICE_CELLS, coincidences, edge_lists, host_frames, oracle_voices,
+                                  pool_lists, resume_edges, run_frames, slice_lists, step_pool, stream_bases, stream_pieces, stream_total,
+                                  tiled_steps, voices_case)
 
 pytestmark = pytest.mark.gpu
 

@@ -21,49 +21,16 @@ from gama_tts_amd import capi
 import oracle
 import targets_cases as cases
 import voices_matrix_cases
-from device_io import current_stream, filled, to_device, to_host
+from device_io import filled, to_device, to_host
 from parity_rules import check_batch
+from targets_io import GUARD, guard_behind_counts, run_targets
 from voice_cases import configs, configs5, oracle_config
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0xA5  # every byte of the audio buffer before the call
 INVALID_ARGUMENT, UNSUPPORTED = 1, 4
 BAD_VOICE = 5
 CRATE = 250.0
-
-
-def run(plan, utterances, step_counts, voice_ids=None, ids=None, max_steps=None, status=True, peaks=True, counts=True, doctor=None):
-    """gvtm_synthesize_targets_voices_device (voice_ids given) or gvtm_synthesize_targets_device on `utterances` (16 lists
-    each; with ids: the lists, and ids [B][16] into them) -> (audio float32 [B][stride] that started out as GUARD bytes,
-    counts that started out -7, maxabs that started out 5.0, statuses that started out -9)."""
-    lists = utterances if ids is not None else [l for u in utterances for l in u]
-    batch = len(step_counts)
-    offsets, steps, values = capi.pack_targets(lists)
-    if doctor:
-        doctor(offsets, steps, values)
-    max_steps = max([int(s) for s in step_counts] + [0]) if max_steps is None else max_steps
-    stride = plan.targets_output_capacity(max_steps) if voice_ids is None else plan.targets_voices_output_capacity(max_steps)
-    # (no table is empty on the device: one spare entry each)
-    d_offsets, d_steps, d_values, d_counts_in = to_device(offsets, np.concatenate([steps, np.zeros(1, np.int32)]),
-                                                           np.concatenate([values, np.zeros(1, np.float32)]), np.asarray(step_counts, dtype=np.int32))
-    d_ids = None if ids is None else to_device(np.asarray(ids, dtype=np.int32).reshape(batch, 16))[0]
-    d_audio = filled((batch, stride * 4), GUARD, np.uint8)
-    d_counts, d_maxabs, d_status = filled(batch, -7, np.int64), filled(batch, 5.0, np.float32), filled(batch, -9, np.int32)
-    tail = (batch, max_steps, d_audio, stride, d_counts if counts else None, d_maxabs if peaks else None, d_status if status else None, current_stream())
-    if voice_ids is None:
-        plan.synthesize_targets_device(d_offsets, len(lists), d_ids, d_steps, d_values, d_counts_in, *tail)
-    else:
-        d_voices, = to_device(np.asarray(voice_ids, dtype=np.int32))
-        plan.synthesize_targets_voices_device(d_offsets, len(lists), d_ids, d_steps, d_values, d_counts_in, d_voices, *tail)
-    audio, out_counts, maxabs, statuses = to_host(d_audio, d_counts, d_maxabs, d_status)
-    return audio.view(np.float32).reshape(batch, stride), out_counts, maxabs, statuses
-
-
-def guard_behind_counts(audio, counts):
-    """Is every sample behind a row's count (a row left out, count -1: the whole row) still the pattern?"""
-    pattern = np.frombuffer(bytes([GUARD] * 4), dtype=np.uint32)[0]
-    return all((audio[b, max(int(counts[b]), 0):].view(np.uint32) == pattern).all() for b in range(audio.shape[0]))
 
 
 def singles(cfgs, utterances, step_counts, voice_ids, rows, max_steps):
@@ -75,7 +42,7 @@ def singles(cfgs, utterances, step_counts, voice_ids, rows, max_steps):
         if not mine:
             continue
         plan = g.Plan(cfg, CRATE, 0, diagnostics=bool(rows), rows=rows)
-        audio, counts, maxabs, statuses = run(plan, [utterances[b] for b in mine], [step_counts[b] for b in mine], max_steps=max_steps)
+        audio, counts, maxabs, statuses = run_targets(plan, [utterances[b] for b in mine], [step_counts[b] for b in mine], max_steps=max_steps)
         assert not statuses.any() and guard_behind_counts(audio, counts)
         for i, b in enumerate(mine):
             assert counts[i] == plan.targets_output_count(step_counts[b])
@@ -116,7 +83,7 @@ def mixed_plan(names, precision, delay, rows):
 def check_mix(cfgs, plan, rows, voice_ids, step_counts, wide=()):
     """The batch on the plan of several voices against the one-voice plans at `rows`; utterance b speaks the lists of seed b."""
     utterances = [cases.spoken_lists(s, b, wide=b in wide) for b, s in enumerate(step_counts)]
-    got = run(plan, utterances, step_counts, voice_ids)
+    got = run_targets(plan, utterances, step_counts, voice_ids)
     assert not got[3].any()
     for b, s in enumerate(step_counts):
         assert got[1][b] == plan.targets_voice_output_count(voice_ids[b], s), b
@@ -189,7 +156,7 @@ def test_float_against_the_oracle():
     step_counts = [n + 145, 0, 5, n - 1]
     voice_ids = [1, 0, 2, 1]
     utterances = [cases.spoken_lists(s, b) for b, s in enumerate(step_counts)]
-    audio, counts, maxabs, statuses = run(plan, utterances, step_counts, voice_ids)
+    audio, counts, maxabs, statuses = run_targets(plan, utterances, step_counts, voice_ids)
     assert not statuses.any()
     cfg = oracle_config("female", 44100.0, 1, 0, capi.PRECISION_F32)
     rate = plan.voice_info(1).internal_rate_hz
@@ -210,12 +177,12 @@ def test_shared_lists_across_voices():
     cfgs, plan, _ = mixed_plan(["male", "female", "baby"], capi.PRECISION_F32, 1, 0)
     lists = cases.spoken_lists(700, 3)
     ids = [list(range(16))] * 3
-    got = run(plan, lists, [700, 700, 700], [2, 0, 1], ids=ids)
+    got = run_targets(plan, lists, [700, 700, 700], [2, 0, 1], ids=ids)
     assert not got[3].any() and guard_behind_counts(got[0], got[1])
     assert len({got[0][b, : got[1][b]].tobytes() for b in range(3)}) == 3  # three speakers
     for b, v in enumerate([2, 0, 1]):
         single = g.Plan(cfgs[v], CRATE, 0)
-        ref = run(single, lists, [700], ids=ids[:1])
+        ref = run_targets(single, lists, [700], ids=ids[:1])
         assert got[1][b] == ref[1][0] and got[2][b].tobytes() == ref[2][0].tobytes()
         assert got[0][b, : got[1][b]].tobytes() == ref[0][0, : ref[1][0]].tobytes(), v
         single.close()
@@ -241,7 +208,7 @@ def test_refused_utterances_between_good_ones():
     def doctor(offsets, steps, values):
         offsets[5 * 16 + 3] = offsets[5 * 16 + 4] + 1  # utterance 5's list 3 ends before it begins
 
-    audio, counts, maxabs, statuses = run(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor)
+    audio, counts, maxabs, statuses = run_targets(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor)
     assert statuses.tolist() == want
     assert guard_behind_counts(audio, counts)
     # a voice outside the plan: left out
@@ -251,23 +218,23 @@ def test_refused_utterances_between_good_ones():
     for b in (4, 5, 6, 7):
         v = voice_ids[b]
         single = g.Plan(cfgs[v], CRATE, 0)
-        empty = run(single, [good(0)], [0], max_steps=400)
+        empty = run_targets(single, [good(0)], [0], max_steps=400)
         zero = plan.targets_voice_output_count(v, 0)
         assert counts[b] == zero == empty[1][0] and maxabs[b].tobytes() == empty[2][0].tobytes()
         assert audio[b, :zero].tobytes() == empty[0][0, :zero].tobytes(), b
         single.close()
     # the good utterances' bytes, counts and peaks are those of the same batch without the refused ones
     keep = [b for b in range(len(want)) if want[b] == 0]
-    alone = run(plan, [utterances[b] for b in keep], [step_counts[b] for b in keep], [voice_ids[b] for b in keep], max_steps=400)
+    alone = run_targets(plan, [utterances[b] for b in keep], [step_counts[b] for b in keep], [voice_ids[b] for b in keep], max_steps=400)
     assert not alone[3].any()
     for i, b in enumerate(keep):
         assert counts[b] == alone[1][i] == plan.targets_voice_output_count(voice_ids[b], step_counts[b])
         assert maxabs[b].tobytes() == alone[2][i].tobytes()
         assert audio[b, : counts[b]].tobytes() == alone[0][i, : counts[b]].tobytes(), b
     # no status asked for: the same audio; neither counts nor peaks asked for: the same audio
-    silent = run(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, status=False)
+    silent = run_targets(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, status=False)
     assert silent[0].tobytes() == audio.tobytes() and (silent[3] == -9).all() and silent[1].tolist() == counts.tolist()
-    bare = run(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, counts=False, peaks=False)
+    bare = run_targets(plan, utterances, step_counts, voice_ids, max_steps=400, doctor=doctor, counts=False, peaks=False)
     assert bare[0].tobytes() == audio.tobytes() and bare[3].tolist() == want and (bare[1] == -7).all() and (bare[2] == 5.0).all()
 
 
@@ -281,8 +248,8 @@ def test_one_voice(kind):
     step_counts = [n + 1, 0, 145, 2 * n + 147, 5]
     assert plan.targets_voices_output_capacity(max(step_counts)) == plan.targets_output_capacity(max(step_counts))
     utterances = [cases.spoken_lists(s, b) for b, s in enumerate(step_counts)]
-    a = run(plan, utterances, step_counts, [0] * 5)
-    b = run(plan, utterances, step_counts)
+    a = run_targets(plan, utterances, step_counts, [0] * 5)
+    b = run_targets(plan, utterances, step_counts)
     assert not a[3].any() and not b[3].any() and guard_behind_counts(a[0], a[1])
     assert a[0].tobytes() == b[0].tobytes() and a[1].tolist() == b[1].tolist() and a[2].tobytes() == b[2].tobytes()
     assert a[1].tolist() == [plan.targets_output_count(s) for s in step_counts]

@@ -9,6 +9,7 @@ the fixture stores; the fixture's own sanity -- its frames are the host rule's o
 the batch protocol's model on the same frames and are as many -- and, where oracle/_ref is built, that ref_vtm gives the
 fixture's bytes again."""
 import ctypes
+import functools
 import os
 import subprocess
 
@@ -19,6 +20,7 @@ import gama_tts_amd as g
 from gama_tts_amd import capi
 import oracle
 import targets5_cases as cases
+import targets_io
 from test_capi_prototypes_cpu import HEADER, c_prototypes, problems, read
 from voice_cases import configs, configs5, male_plan, model5_plan
 
@@ -46,13 +48,7 @@ def test_the_symbol_is_exported_and_its_prototype_is_the_headers():
 
 # ---- 2. the refusals ----
 
-def device_entry(plan, batch=2, null=None, n_lists=32, ids=False, stride=None, max_steps=8):
-    """Status of the entry on a small (host-memory, never dereferenced) batch; null: an argument to leave out."""
-    a = dict(offsets=np.zeros(33, np.int64), steps=np.zeros(2, np.int32), values=np.zeros(2, np.float32), audio=np.zeros((2, 65536), np.float32))
-    ptr = {k: (None if k == null else v.ctypes.data) for k, v in a.items()}
-    list_ids = np.zeros((2, 16), np.int32).ctypes.data if ids else None
-    return getattr(plan._lib, ENTRY)(plan._h, ptr["offsets"], n_lists, list_ids, ptr["steps"], ptr["values"], None, batch, max_steps, ptr["audio"],
-                                     65536 if stride is None else stride, None, None, None, None)
+device_entry = functools.partial(targets_io.device_entry, entry_name=ENTRY, voices=False)
 
 
 def plan_of(kind):

@@ -6,6 +6,7 @@ order of the entry's refusals -- arguments, then the plan's model family, then t
 design-only plans of every kind; the filter lengths of a five-voice model 5 plan; per fixture case the sample count by steps
 of its voice and the SHA-256 of the frames the reference was fed, so that the fixture's inputs cannot drift from the rule."""
 import ctypes
+import functools
 import os
 import subprocess
 
@@ -16,6 +17,7 @@ import gama_tts_amd as g
 from gama_tts_amd import capi
 import oracle
 import targets5_voices_cases as cases
+import targets_io
 from voice_cases import configs, male_plan
 from voice_files import VOICES
 
@@ -41,14 +43,7 @@ def test_name_in_the_header_the_library_and_the_binding():
 
 # ---- the refusals ----
 
-def device_entry(plan, batch=2, null=None, n_lists=32, ids=False, stride=None, max_steps=8):
-    """Status of the entry on a small (host-memory, never dereferenced) batch; null: an argument to leave out."""
-    a = dict(offsets=np.zeros(33, np.int64), steps=np.zeros(2, np.int32), values=np.zeros(2, np.float32), audio=np.zeros((2, 65536), np.float32),
-             voices=np.zeros(2, np.int32))
-    ptr = {k: (None if k == null else v.ctypes.data) for k, v in a.items()}
-    list_ids = np.zeros((2, 16), np.int32).ctypes.data if ids else None
-    return getattr(plan._lib, ENTRY)(plan._h, ptr["offsets"], n_lists, list_ids, ptr["steps"], ptr["values"], None, ptr["voices"],
-                                     batch, max_steps, ptr["audio"], 65536 if stride is None else stride, None, None, None, None)
+device_entry = functools.partial(targets_io.device_entry, entry_name=ENTRY, voices=True)
 
 
 # kind -> (the plan, what the entry answers once its arguments are in order, a word of that refusal's message)

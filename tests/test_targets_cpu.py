@@ -9,6 +9,7 @@ MovingAverageFilter<float> under the loop of the rule as the header states it); 
 oracle's at one step per frame; where oracle/_ref is built, the oracle at one step per frame against the compiled reference
 on the host rule's frames; every refusal of the device entry as far as a design-only plan lets it go."""
 import ctypes
+import functools
 import os
 import subprocess
 
@@ -20,6 +21,7 @@ from gama_tts_amd import capi
 import modification_cases
 import oracle
 import targets_cases as cases
+import targets_io
 from voice_cases import configs, male_plan, model5_plan
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -247,13 +249,7 @@ def test_oracle_at_one_step_per_frame_equals_the_reference(plans, name, tmp_path
 
 # ---- 6. the device entry's refusals ----
 
-def device_entry(plan, batch=2, null=None, n_lists=32, ids=False, stride=None, max_steps=8):
-    """Status of the device entry on a small (host-memory, never dereferenced) batch; null: an argument to leave out."""
-    a = dict(offsets=np.zeros(33, np.int64), steps=np.zeros(2, np.int32), values=np.zeros(2, np.float32), audio=np.zeros((2, 65536), np.float32))
-    ptr = {k: (None if k == null else v.ctypes.data) for k, v in a.items()}
-    list_ids = np.zeros((2, 16), np.int32).ctypes.data if ids else None
-    return plan._lib.gvtm_synthesize_targets_device(plan._h, ptr["offsets"], n_lists, list_ids, ptr["steps"], ptr["values"], None, batch, max_steps,
-                                                    ptr["audio"], 65536 if stride is None else stride, None, None, None, None)
+device_entry = functools.partial(targets_io.device_entry, entry_name="gvtm_synthesize_targets_device", voices=False)
 
 
 @pytest.mark.parametrize("kind", ["one-voice", "two-voices", "model5", "model5-float"])

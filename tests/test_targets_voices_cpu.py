@@ -8,14 +8,15 @@ of the voices'; (size_t)-1 for a null plan and a voice outside the plan; the ord
 the plan's model, then the device -- on plans of one voice, of several, and of model 5 in both classes; the three names in
 the header, the library and the binding."""
 import ctypes
+import functools
 import os
 import subprocess
 
-import numpy as np
 import pytest
 
 import gama_tts_amd as g
 from gama_tts_amd import capi
+import targets_io
 from voice_cases import configs, configs5, male_plan, model5_plan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -76,14 +77,7 @@ def test_error_returns():
 
 # ---- 2. the device entry's refusals ----
 
-def device_entry(plan, batch=2, null=None, n_lists=32, ids=False, stride=None, max_steps=8):
-    """Status of the entry on a small (host-memory, never dereferenced) batch; null: an argument to leave out."""
-    a = dict(offsets=np.zeros(33, np.int64), steps=np.zeros(2, np.int32), values=np.zeros(2, np.float32), audio=np.zeros((2, 65536), np.float32),
-             voices=np.zeros(2, np.int32))
-    ptr = {k: (None if k == null else v.ctypes.data) for k, v in a.items()}
-    list_ids = np.zeros((2, 16), np.int32).ctypes.data if ids else None
-    return plan._lib.gvtm_synthesize_targets_voices_device(plan._h, ptr["offsets"], n_lists, list_ids, ptr["steps"], ptr["values"], None, ptr["voices"],
-                                                           batch, max_steps, ptr["audio"], 65536 if stride is None else stride, None, None, None, None)
+device_entry = functools.partial(targets_io.device_entry, entry_name="gvtm_synthesize_targets_voices_device", voices=True)
 
 
 def plan_of(kind):
