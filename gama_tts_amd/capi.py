@@ -223,6 +223,14 @@ def _prototypes():
         "gvtm_rules_event_count": (i64, [vp, i, vp, sz, vp]),
         "gvtm_generate_events_device": (i, [vp, i, vp, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp]),
         "gvtm_synthesize_postures_device": (i, [vp, vp, tracks, vp, vp, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp]),
+        "gvtm_prosody_create": (i, [i, vp, vp, sz, vp]),
+        "gvtm_prosody_destroy": (None, [vp]),
+        "gvtm_prosody_rhythm_host": (i, [vp, vp, sz, vp, sz, vp, vp]),
+        "gvtm_prosody_point_count": (i64, [sz, vp, sz, vp, sz]),
+        "gvtm_prosody_points_host": (i, [vp, i, vp, sz, vp, sz, vp, sz, vp, vp, sz, vp, i, vp, sz, vp, vp]),
+        "gvtm_apply_rhythm_device": (i, [vp, vp, vp, sz, vp, vp, sz, sz, vp, vp, vp]),
+        "gvtm_place_intonation_device": (i, [vp, i, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp]),
+        "gvtm_synthesize_prosody_device": (i, [vp, vp, vp, vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, sz, sz, sz, sz, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp]),
     }
     hooks = {
         "gvtm_debug_set_rows": (i, [vp, i]),
@@ -565,6 +573,113 @@ class Rules:
         _check(self._lib, self._lib.gvtm_generate_events_device(
             self._h, int(control_period), _ptr(d_postures), _ptr(d_posture_offsets), int(batch), _ptr(d_events_out), int(out_capacity),
             _ptr(d_event_offsets_out), _ptr(d_rule_data), int(max_rules), _ptr(d_rule_counts), _ptr(d_onsets), _ptr(d_status), _ptr(stream)))
+
+
+# gvtm_foot, gvtm_tone_group and gvtm_prosody_config as numpy record layouts (24, 32 and 112 bytes)
+FOOT_DTYPE = np.dtype([("start", "<i4"), ("end", "<i4"), ("marked", "<i4"), ("reserved_", "<i4"), ("tempo", "<f8")])
+TONE_GROUP_DTYPE = np.dtype([("start_foot", "<i4"), ("end_foot", "<i4"), ("type", "<i4"), ("param", "<f4", 5)])
+PROSODY_INTONATION_KEYS = ("time_offset", "pretonic_base_slope", "pretonic_base_slope_random", "pretonic_slope_random_factor", "tonic_base_slope",
+                           "tonic_continuation_base_slope", "tonic_slope_random_factor", "tonic_slope_offset")  # intonation.txt
+PROSODY_RHYTHM_KEYS = ("marked_a", "marked_b", "marked_div", "unmarked_a", "unmarked_b", "unmarked_div", "min_tempo", "max_tempo")  # rhythm.txt
+PROSODY_CONFIG_DTYPE = np.dtype([(k, "<f4") for k in PROSODY_INTONATION_KEYS] + [("intonation_factor", "<f4"), ("reserved_", "<f4")] +
+                                [(k, "<f8") for k in PROSODY_RHYTHM_KEYS] + [("global_tempo", "<f8")])
+PROSODY_OK, PROSODY_BAD_STRUCTURE, PROSODY_NO_RULES, PROSODY_TOO_MANY, PROSODY_BAD_VALUE, PROSODY_NO_ROOM = range(6)  # the statuses of the two rules
+TONE_GROUP_CONTINUATION, TONE_GROUP_NONE = 3, 5
+
+
+def feet_from_table(table):
+    """rows (start, end, marked, tempo) -> gvtm_foot records."""
+    table = np.asarray(table, dtype=np.float64).reshape(-1, 4)
+    out = np.zeros(table.shape[0], dtype=FOOT_DTYPE)
+    out["start"], out["end"], out["marked"], out["tempo"] = table[:, 0].astype(np.int32), table[:, 1].astype(np.int32), table[:, 2].astype(np.int32), table[:, 3]
+    return out
+
+
+def tone_groups_from_table(table):
+    """rows (start_foot, end_foot, type, param[5]) -> gvtm_tone_group records (the parameters rounded to float once)."""
+    table = np.asarray(table, dtype=np.float64).reshape(-1, 8)
+    out = np.zeros(table.shape[0], dtype=TONE_GROUP_DTYPE)
+    out["start_foot"], out["end_foot"], out["type"] = table[:, 0].astype(np.int32), table[:, 1].astype(np.int32), table[:, 2].astype(np.int32)
+    out["param"] = table[:, 3:8].astype(np.float32)
+    return out
+
+
+def prosody_config(intonation, rhythm, intonation_factor=1.0, global_tempo=1.0):
+    """The eight floats of intonation.txt and the eight doubles of rhythm.txt (dicts by the files' keys, or sequences in
+    PROSODY_INTONATION_KEYS / PROSODY_RHYTHM_KEYS order) with the two factors -> one gvtm_prosody_config record."""
+    out = np.zeros((), dtype=PROSODY_CONFIG_DTYPE)
+    for keys, values in ((PROSODY_INTONATION_KEYS, intonation), (PROSODY_RHYTHM_KEYS, rhythm)):
+        for k, key in enumerate(keys):
+            out[key] = values[key] if isinstance(values, dict) else values[k]
+    out["intonation_factor"], out["global_tempo"] = intonation_factor, global_tempo
+    return out
+
+
+def prosody_point_count(n_postures, feet, groups):
+    """gvtm_prosody_point_count: the points the tables alone promise, or -1 for a structure the rule refuses."""
+    lib = load_library()
+    feet, groups = np.ascontiguousarray(feet, dtype=FOOT_DTYPE), np.ascontiguousarray(groups, dtype=TONE_GROUP_DTYPE)
+    return int(lib.gvtm_prosody_point_count(int(n_postures), _ptr(feet), feet.shape[0], _ptr(groups), groups.shape[0]))
+
+
+class Prosody:
+    """Owns a gvtm_prosody: a gvtm_prosody_config record (prosody_config) and the model's vocoid table
+    (control_model.compile_model(...)["vocoid"]; None, a model without the category, is refused), checked and, unless device
+    is DEVICE_NONE, uploaded."""
+
+    def __init__(self, config, vocoid, device=DEVICE_NONE):
+        self._lib = load_library()
+        self._h = ctypes.c_void_p()
+        config = np.ascontiguousarray(config, dtype=PROSODY_CONFIG_DTYPE).reshape(1)
+        table = None if vocoid is None else np.ascontiguousarray(vocoid, dtype=np.uint8)
+        self.device = int(device)
+        _check(self._lib, self._lib.gvtm_prosody_create(int(device), _ptr(config), _ptr(table), 0 if table is None else table.shape[0], ctypes.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._lib.gvtm_prosody_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def rhythm_host(self, postures, feet, in_place=False):
+        """gvtm_prosody_rhythm_host: gvtm_posture and gvtm_foot records -> (the postures after rhythm, status)."""
+        postures, feet = np.array(postures, dtype=POSTURE_DTYPE), np.ascontiguousarray(feet, dtype=FOOT_DTYPE)
+        out = postures if in_place else np.zeros(max(postures.shape[0], 1), dtype=POSTURE_DTYPE)
+        status = ctypes.c_int32(-1)
+        _check(self._lib, self._lib.gvtm_prosody_rhythm_host(self._h, _ptr(postures), postures.shape[0], _ptr(feet), feet.shape[0], _ptr(out), ctypes.byref(status)))
+        return out[: postures.shape[0]], int(status.value)
+
+    def points_host(self, control_period, postures, feet, groups, draws, rule_data, onsets, rule_status=0, capacity=MAX_INTONATION_POINTS):
+        """gvtm_prosody_points_host: the postures after rhythm, the tables, the draws (float64 [feet][2] or None) and what
+        the rules entry left -> (gvtm_intonation_point records, status)."""
+        postures, feet = np.ascontiguousarray(postures, dtype=POSTURE_DTYPE), np.ascontiguousarray(feet, dtype=FOOT_DTYPE)
+        groups, rule_data = np.ascontiguousarray(groups, dtype=TONE_GROUP_DTYPE), np.ascontiguousarray(rule_data, dtype=RULE_DATA_DTYPE)
+        onsets = np.ascontiguousarray(onsets, dtype=np.float64)
+        draws = None if draws is None else np.ascontiguousarray(draws, dtype=np.float64).reshape(feet.shape[0], 2)
+        points = np.zeros(max(int(capacity), 1), dtype=POINT_DTYPE)
+        n_points, status = ctypes.c_size_t(0), ctypes.c_int32(-1)
+        _check(self._lib, self._lib.gvtm_prosody_points_host(
+            self._h, int(control_period), _ptr(postures), postures.shape[0], _ptr(feet), feet.shape[0], _ptr(groups), groups.shape[0], _ptr(draws),
+            _ptr(rule_data), rule_data.shape[0], _ptr(onsets), int(rule_status), _ptr(points), int(capacity), ctypes.byref(n_points), ctypes.byref(status)))
+        return points[: n_points.value].copy(), int(status.value)
+
+    def apply_rhythm_device(self, d_postures, d_posture_offsets, n_postures, d_feet, d_foot_offsets, n_feet, batch, d_postures_out, d_status=None, stream=None):
+        """gvtm_apply_rhythm_device; all pointers are device memory (d_postures_out may be d_postures)."""
+        _check(self._lib, self._lib.gvtm_apply_rhythm_device(self._h, _ptr(d_postures), _ptr(d_posture_offsets), int(n_postures), _ptr(d_feet), _ptr(d_foot_offsets),
+                                                             int(n_feet), int(batch), _ptr(d_postures_out), _ptr(d_status), _ptr(stream)))
+
+    def place_intonation_device(self, control_period, d_postures, d_posture_offsets, d_feet, d_foot_offsets, d_groups, d_group_offsets, d_draws, batch,
+                                d_rule_data, max_rules, d_rule_counts, d_onsets, d_points_out, points_capacity, d_point_offsets_out, d_status=None, stream=None):
+        """gvtm_place_intonation_device: what gvtm_generate_events_device left -> points, their offsets and statuses."""
+        _check(self._lib, self._lib.gvtm_place_intonation_device(
+            self._h, int(control_period), _ptr(d_postures), _ptr(d_posture_offsets), _ptr(d_feet), _ptr(d_foot_offsets), _ptr(d_groups), _ptr(d_group_offsets),
+            _ptr(d_draws), int(batch), _ptr(d_rule_data), int(max_rules), _ptr(d_rule_counts), _ptr(d_onsets), _ptr(d_points_out), int(points_capacity),
+            _ptr(d_point_offsets_out), _ptr(d_status), _ptr(stream)))
 
 
 MODIFICATION_ADD, MODIFICATION_MULTIPLY = 0, 1  # GVTM_MODIFICATION_*
@@ -1219,6 +1334,17 @@ class Plan:
         self._check(self._lib.gvtm_synthesize_postures_device(
             self._h, rules._h, ctypes.byref(track_config), _ptr(d_postures), _ptr(d_posture_offsets), int(events_capacity), int(batch),
             int(max_frames), _ptr(d_audio), int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift),
+            _ptr(d_status), _ptr(stream)))
+
+    def synthesize_prosody_device(self, rules, prosody, d_postures, d_posture_offsets, n_postures, d_feet, d_foot_offsets, n_feet, d_groups, d_group_offsets,
+                                  d_draws, d_voice_ids, max_rules, points_capacity, events_capacity, batch, max_frames, d_audio, audio_stride,
+                                  d_frame_counts=None, d_out_counts=None, d_maxabs=None, d_drift=None, d_prosody_status=None, d_status=None, stream=None):
+        """Postures, feet and tone groups in, samples out (gvtm_synthesize_prosody_device; a plan with track configurations,
+        rules and prosody on its device); all pointers are device memory, everything is enqueued on `stream`."""
+        self._check(self._lib.gvtm_synthesize_prosody_device(
+            self._h, rules._h, prosody._h, _ptr(d_postures), _ptr(d_posture_offsets), int(n_postures), _ptr(d_feet), _ptr(d_foot_offsets), int(n_feet),
+            _ptr(d_groups), _ptr(d_group_offsets), _ptr(d_draws), _ptr(d_voice_ids), int(max_rules), int(points_capacity), int(events_capacity), int(batch),
+            int(max_frames), _ptr(d_audio), int(audio_stride), _ptr(d_frame_counts), _ptr(d_out_counts), _ptr(d_maxabs), _ptr(d_drift), _ptr(d_prosody_status),
             _ptr(d_status), _ptr(stream)))
 
     def normalize_device(self, d_audio, batch, audio_stride, d_maxabs, d_counts=None, d_out_f32=None, d_out_i16=None,

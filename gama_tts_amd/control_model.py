@@ -253,7 +253,7 @@ def _attr(elem, name, optional=False):
 
 def compile_model(source):
     """`source`: the path of an artic.xml, or its text.  Returns a dict: the arrays named in ARRAYS (what gvtm_rules_model
-    points at) and the name lists posture_names, equation_names, transition_names (numpy string arrays; ids are positions; the postures are in
+    points at), vocoid (uint8 [postures], or None) and the name lists posture_names, equation_names, transition_names (numpy string arrays; ids are positions; the postures are in
     the reference's order, sorted by name)."""
     root = ET.fromstring(source) if source.lstrip().startswith("<") else ET.parse(source).getroot()
     categories = [_attr(c, "name") for c in _children(root.find("categories"), "category")]
@@ -426,6 +426,10 @@ def compile_model(source):
         "point_free_time": np.asarray(point_free_time, dtype=np.float32),
         "point_time_eq": np.asarray(point_time_eq, dtype=np.int32),
         "slopes": np.asarray(slopes, dtype=np.float32),
+        # is the posture a member of the category "vocoid" (EventList::applyIntonation's search); None: the database has no
+        # such category.  Not one of ARRAYS: it goes to gvtm_prosody_create, not into gvtm_rules_model
+        "vocoid": (np.asarray([p in category_members["vocoid"] for p in range(n_postures)], dtype=np.uint8)
+                   if "vocoid" in category_members else None),
         "posture_names": np.asarray(posture_names),
         "equation_names": np.asarray(equation_names),
         "transition_names": np.asarray(transition_names),

@@ -65,6 +65,8 @@ bool bad_control_period(int32_t cp) { return cp < 1 || cp > 4; }
 
 } // namespace
 
+int gvtm::host::rules_device(const gvtm_rules* rules) { return rules->device; }
+
 extern "C" {
 
 int gvtm_rules_create(int device, const gvtm_rules_model* model, gvtm_rules** rules_out)

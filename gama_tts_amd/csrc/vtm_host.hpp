@@ -154,6 +154,10 @@ struct gvtm_plan {
 	struct {
 		DeviceBuffer params, frames, groups;
 		DeviceBuffer events, event_offsets;
+		// gvtm_synthesize_prosody_device's: what lies between its kernels (the merged lists go into the two above)
+		struct {
+			DeviceBuffer postures, rhythm_status, events, event_offsets, rule_data, rule_counts, onsets, points, point_offsets, status, list_ids;
+		} prosody;
 	} async;
 	// gvtm_plan_set_voice_tracks: one designed track configuration per voice, and (device plans) the table the voice
 	// variant of the tracks kernel reads; empty until the first call that succeeds
@@ -430,6 +434,9 @@ int check_audio_stride(const gvtm_plan* plan, size_t audio_stride, size_t max_fr
 // The 16 sums of the targets filters as every utterance's block of a model 5 stream's device state holds them, out [batch][16]
 // (vtm_capi_stream.cpp, which alone knows the structure; the diagnostics library's gvtm_debug_stream_targets_sums)
 int stream_download_targets_sums(const gvtm_stream* stream, double* out);
+
+// The device a rules object lives on, GVTM_DEVICE_NONE for a host-only one (vtm_capi_rules.cpp, which alone knows the structure)
+int rules_device(const gvtm_rules* rules);
 
 // What a listening stream needs of an analysis object (vtm_capi_analysis.cpp, which alone knows the structure): its facts,
 // and the slices of gvtm_analyze_spectrum_device behind that entry's checks, enqueue-only on `stream` with the object's device

@@ -1598,6 +1598,148 @@ int gvtm_synthesize_postures_device(gvtm_plan* plan, const gvtm_rules* rules, co
 		size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts,
 		float* d_maxabs, gvtm_drift_state* d_drift, int32_t* d_status, void* hip_stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Rhythm and intonation points: the two steps of EventList that stand on either side of the rule above.
+ * EventList::applyRhythm() (EventList.cpp:796-819) runs at the head of generateEventList() and turns feet into posture
+ * tempi; EventList::applyIntonation() / addIntonationPoint() (:687-793, :903-927) runs behind it and places the
+ * IntonationPoints by the rule data and the posture onsets.  With the entries below a batch goes from postures, feet and
+ * tone groups to samples without leaving the device: bit for bit the reference's generateEventList(); applyIntonation();
+ * generateOutput().  (The four structures of this section are declared in two steps, as those of the section above.)
+ *
+ * Rhythm, per foot in order: n = end - start + 1; tempo += (a * n + b) / div with the marked or the unmarked constants;
+ * clamped to [min_tempo, max_tempo]; multiplied by global_tempo; then postures[j].tempo *= tempo for every posture of the
+ * foot.  Postures in no foot keep their tempo.
+ *
+ * Points, per tone group and per foot of it in order: startTime and endTime are the onsets of feet[start_foot].start and
+ * feet[end_foot].end; pretonicDelta = deltaTime < 1.0e-6 ? 0.0 : param[0] / deltaTime.  The posture of a foot is its first
+ * vocoid, or `start` if it has none; its rule is the first row with first_posture <= p <= last_posture.  An unmarked
+ * (pretonic) foot gets one point, semitone (onset[p] - startTime) * pretonicDelta + param[0] + r, slope
+ * pretonic_base_slope, or with draws r = (draw[0] - 0.5) * param[2] and slope draw[1] * pretonic_slope_random_factor +
+ * pretonic_base_slope_random.  A marked (tonic) foot gets two: semitone (param[1] + param[0], a float sum) + r, slope
+ * tonic_base_slope (type 3: tonic_continuation_base_slope) + tonic_slope_offset, or with draws r = (draw[0] - 0.5) *
+ * param[4] and + draw[1] * tonic_slope_random_factor; then, at the rule of feet[j].end searched from the rule of the first,
+ * semitone param[1] + param[0] + param[3] (a float sum) with offset 0 and slope 0.  The offset is 0 for the first foot of
+ * the utterance and time_offset for every foot behind it; it is not reset per group.  One closing point stands at the last
+ * rule with the last group's param[1] + param[0] + param[3], offset 0, slope 0.  Every point goes through
+ * addIntonationPoint: semitone and slope are multiplied by the float intonation_factor; time = max(beat + offset, 0);
+ * minTime = (the time stored for the point before, or 0 for the first) + 2.0 * control_period; if time < minTime, offset +=
+ * minTime - time; the time_ms stored is max(beat + offset, 0) once more, not minTime.  Floats widen to double where the C++
+ * expression widens them; no FMA contraction; IEEE division.  An utterance without a tone group gets no points.
+ *
+ * An utterance is refused on its own, with 0 points, and by the prosody entry with 0 frames.  Its status, the first that
+ * applies:
+ *   0  ok
+ *   1  a structure the reference could not have built: a foot outside the postures or with start > end, feet that are not
+ *      strictly increasing and disjoint, a group outside the feet or with start_foot > end_foot, groups that are not
+ *      increasing and disjoint, a type outside 0..5, a posture id outside the vocoid table
+ *   2  an utterance the rules entry refused (any status but 0), no rule rows or more than max_rules, a posture in no row
+ *   3  more than GVTM_MAX_INTONATION_POINTS points: feet in groups + marked feet in groups + 1
+ *   4  a foot tempo (rhythm), a draw, a parameter or a resulting time, semitone or slope that is not finite
+ *   5  device only: the points do not fit behind those before them in points_capacity
+ * Rhythm knows 0, 1 and 4 only; a foot it refuses multiplies nothing, the largest status of an utterance's feet is the
+ * utterance's, and the tempi of a refused utterance are not defined.
+ */
+struct gvtm_foot {
+	int32_t start, end;   /* posture indices within the utterance, inclusive (feet_[i].start, .end) */
+	int32_t marked;       /* 0 or not: a tonic foot */
+	int32_t reserved_;
+	double tempo;         /* Foot::tempo before rhythm: the parser's /f value, otherwise 1.0 */
+};
+typedef struct gvtm_foot gvtm_foot;
+
+/* Only closed feet and closed groups are listed: the reference's loops stop at currentFoot_ and currentToneGroup_. */
+struct gvtm_tone_group {
+	int32_t start_foot, end_foot;  /* inclusive, into the utterance's feet */
+	int32_t type;                  /* IntonationRhythm::ToneGroup 0..4 (3: continuation), 5: none */
+	float param[5];                /* what intonationParameters(type) returned: notional pitch, pretonic pitch range, pretonic
+	                                  perturbation range, tonic pitch range, tonic perturbation range.  Choosing the set
+	                                  (fixed, first of the file, a random index) is the caller's. */
+};
+typedef struct gvtm_tone_group gvtm_tone_group;
+
+/* Every number in the type the reference holds it in: intonation.txt, EventList::intonationFactor_, rhythm.txt,
+ * EventList::globalTempo_. */
+struct gvtm_prosody_config {
+	float time_offset, pretonic_base_slope, pretonic_base_slope_random, pretonic_slope_random_factor;
+	float tonic_base_slope, tonic_continuation_base_slope, tonic_slope_random_factor, tonic_slope_offset;
+	float intonation_factor;
+	float reserved_;
+	double marked_a, marked_b, marked_div, unmarked_a, unmarked_b, unmarked_div, min_tempo, max_tempo;
+	double global_tempo;
+};
+typedef struct gvtm_prosody_config gvtm_prosody_config;
+
+typedef struct gvtm_prosody gvtm_prosody;
+
+/* Checks and keeps the configuration and the table and, unless device is GVTM_DEVICE_NONE (host use only), uploads the
+ * table; synchronous.  vocoid [n_postures]: is the posture a member of the category "vocoid" (control_model.compile_model
+ * gives it beside the rules model).  GVTM_ERR_INVALID_ARGUMENT: a null argument -- a model without the category has no
+ * table, which is the reference's UnavailableResourceException --, n_postures 0, a number that is not finite. */
+int gvtm_prosody_create(int device, const gvtm_prosody_config* config, const uint8_t* vocoid, size_t n_postures,
+		gvtm_prosody** prosody_out);
+void gvtm_prosody_destroy(gvtm_prosody* prosody);
+
+/* Rhythm for one utterance, on the host; needs no device.  postures_out [n] may be postures (in place).  Returns GVTM_OK
+ * also for a refused utterance (*status_out 1 or 4). */
+int gvtm_prosody_rhythm_host(const gvtm_prosody* prosody, const gvtm_posture* postures, size_t n, const gvtm_foot* feet,
+		size_t n_feet, gvtm_posture* postures_out, int32_t* status_out);
+/* The points the tables alone promise (0 without a group), or -1: a bad call, or a structure of status 1. */
+int64_t gvtm_prosody_point_count(size_t n_postures, const gvtm_foot* feet, size_t n_feet, const gvtm_tone_group* groups,
+		size_t n_groups);
+/* The points of one utterance, on the host; needs no device.  postures: after rhythm, as the rules entry took them;
+ * draws: two doubles in [0, 1) per foot, laid out as the feet -- [0] the semitone draw, [1] the slope draw, of a pretonic
+ * and of a tonic foot alike -- or NULL: randomIntonation() is false; rule_data [n_rules], onsets [n] and rule_status: what
+ * gvtm_rules_apply_host left.  points_out [capacity] may be NULL (count and status only).  Returns GVTM_OK also for a
+ * refused utterance; GVTM_ERR_INVALID_ARGUMENT for a null argument, a control_period outside 1..4, more points than
+ * capacity. */
+int gvtm_prosody_points_host(const gvtm_prosody* prosody, int32_t control_period, const gvtm_posture* postures, size_t n,
+		const gvtm_foot* feet, size_t n_feet, const gvtm_tone_group* groups, size_t n_groups, const double* draws,
+		const gvtm_rule_data* rule_data, size_t n_rules, const double* onsets, int32_t rule_status,
+		gvtm_intonation_point* points_out, size_t capacity, size_t* n_points_out, int32_t* status_out);
+
+/* Rhythm for a batch, everything resident in device memory: postures and feet back to back, utterance b owning the
+ * records between d_posture_offsets[b] and [b + 1] resp. d_foot_offsets[b] and [b + 1] (int64, [batch + 1]); n_postures
+ * and n_feet are the records behind the two arrays (the tables' last entries, which the caller knows).  d_postures_out
+ * [n_postures] may be d_postures (in place); otherwise the postures are copied first.  d_status [batch] may be NULL.
+ * Bit for bit gvtm_prosody_rhythm_host's, utterance by utterance.  Enqueue-only: a copy, a clearing of the statuses and
+ * one kernel, a lane per foot, on hip_stream.  GVTM_ERR_NO_DEVICE: an object created with GVTM_DEVICE_NONE. */
+int gvtm_apply_rhythm_device(const gvtm_prosody* prosody, const gvtm_posture* d_postures, const int64_t* d_posture_offsets,
+		size_t n_postures, const gvtm_foot* d_feet, const int64_t* d_foot_offsets, size_t n_feet, size_t batch,
+		gvtm_posture* d_postures_out, int32_t* d_status, void* hip_stream);
+
+/* The points for a batch.  d_postures (after rhythm), d_rule_data [batch][max_rules], d_rule_counts, d_onsets and d_status
+ * are exactly what gvtm_generate_events_device took and left; d_status [batch] (may be NULL: every utterance counts as
+ * accepted by the rule) is read and then overwritten with the statuses above.  d_groups, d_group_offsets as the feet;
+ * d_draws two doubles per foot laid out as the feet, or NULL.  d_points_out [points_capacity] and d_point_offsets_out
+ * [batch + 1] are exactly what gvtm_apply_intonation_device takes.  Points, offsets and statuses are bit for bit
+ * gvtm_prosody_points_host's.  Nothing is written at or beyond points_capacity and nothing for a refused utterance; points
+ * that would end beyond points_capacity are refused (5) and take no room.  Enqueue-only: three kernels on hip_stream. */
+int gvtm_place_intonation_device(const gvtm_prosody* prosody, int32_t control_period, const gvtm_posture* d_postures,
+		const int64_t* d_posture_offsets, const gvtm_foot* d_feet, const int64_t* d_foot_offsets,
+		const gvtm_tone_group* d_groups, const int64_t* d_group_offsets, const double* d_draws, size_t batch,
+		const gvtm_rule_data* d_rule_data, size_t max_rules, const int32_t* d_rule_counts, const double* d_onsets,
+		gvtm_intonation_point* d_points_out, size_t points_capacity, int64_t* d_point_offsets_out, int32_t* d_status,
+		void* hip_stream);
+
+/* Postures, feet and tone groups in, audio out, on a plan with track configurations (gvtm_plan_set_voice_tracks):
+ * gvtm_apply_rhythm_device, gvtm_generate_events_device, gvtm_place_intonation_device, gvtm_apply_intonation_device and
+ * gvtm_synthesize_events_voices_device, all enqueued on hip_stream with buffers the plan owns in between: postures,
+ * max_rules rule rows per utterance, onsets, events_capacity generated events, points_capacity points and events_capacity +
+ * points_capacity merged events.  They are more buffers of the plan's that the one-stream ordering rule covers.  The
+ * control period is the plan's.  The reference merges points only if macroIntonation_: an utterance whose voice has
+ * macro_intonation 0 gets no points, its list is the generated one.  A refused utterance reaches the apply step with list
+ * id -1 and so has 0 frames.  d_prosody_status [batch] (may be NULL) gets the statuses above, d_status [batch] (may be NULL)
+ * gvtm_apply_intonation_device's.  Samples, counts, peaks, frame counts, drift states and statuses are bit for bit those
+ * of the five calls made one by one.  Refused before any device work: a null plan, rules or prosody, a plan without track
+ * configurations, a design-only plan, rules or a prosody object on another device than the plan's, and with batch > 0 a
+ * null table, voice ids or audio buffer, a stride too short, max_rules 0. */
+int gvtm_synthesize_prosody_device(gvtm_plan* plan, const gvtm_rules* rules, const gvtm_prosody* prosody,
+		const gvtm_posture* d_postures, const int64_t* d_posture_offsets, size_t n_postures, const gvtm_foot* d_feet,
+		const int64_t* d_foot_offsets, size_t n_feet, const gvtm_tone_group* d_groups, const int64_t* d_group_offsets,
+		const double* d_draws, const int32_t* d_voice_ids, size_t max_rules, size_t points_capacity, size_t events_capacity,
+		size_t batch, size_t max_frames, float* d_audio, size_t audio_stride, int32_t* d_frame_counts, int64_t* d_out_counts,
+		float* d_maxabs, gvtm_drift_state* d_drift, int32_t* d_prosody_status, int32_t* d_status, void* hip_stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
